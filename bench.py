@@ -58,6 +58,11 @@ COLOUR_STEP_VALU_INSTRUCTIONS = 105          # round 5: a class step of the impu
 ISSUE_CYCLES_PER_INSTRUCTION = 4.5
 SIMDS = 1024
 COLOUR_STEP_FLOOR_CYCLES = 64 + COLOUR_STEP_VALU_INSTRUCTIONS * 4 + 13 + 128
+# phx_solver_bench / phx_solver_bench_stage take at most this many steps per call (csrc/solver.hip): longer blocks are queued as
+# several calls, unstaged (every step restores its input from the resident arrays, as any block too big to stage does)
+MAX_STEPS_PER_CALL = 4096
+STAGE_BYTES_MAX = 8 << 30        # ... and phx_solver_bench_stage stages no block whose copies would take more than this (csrc/solver.hip)
+DUMP_BYTES_MAX = 64 << 20        # --dump-outputs: at most this much in all; larger outputs are a fixed, seeded sample of rows
 
 
 def pmc_file(name):
@@ -142,7 +147,11 @@ def main():
                          "islands and all-gathers everybody's results every step")
     ap.add_argument("--backend", default="rccl", help="rccl: the library's own RCCL transport (csrc/comm.hip), torch only for the rendezvous; "
                     "nccl: torch.distributed's ProcessGroupNCCL from a step hook; gloo: host-staged (ranks sharing one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed (body velocities, "
+                    "displacing velocities, accumulated impulses) as DIR/<name>.npy; one rank only")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs needs --gpus 1")
 
     from phyx_amd import dist as pdist
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -229,20 +238,23 @@ def run_bench(args, pdist):
         want_sum = slv.bench_checksum()
         sums = []
         blocks = []
+        chunks = [min(MAX_STEPS_PER_CALL, steps - k) for k in range(0, steps, MAX_STEPS_PER_CALL)] or [steps]
         for _ in range(max(repeats, 1)):
-            slv.bench_stage(d_bodies, d_joints, steps)                    # K copies of the input, resident in HBM before the clock starts
+            slv.bench_stage(d_bodies, d_joints, steps if len(chunks) == 1 else 0)     # K copies of the input, resident in HBM before the clock starts
             group.barrier()
             slv.synchronize()
             t0 = time.perf_counter()
             # each step: one full SolveJoints of this rank's groups on that step's copy of the input, then (N > 1) pack ->
             # all-gather -> unpack, all queued on the solver's stream; the host queues the K steps back to back inside one library call
-            r = slv.bench(d_bodies, d_cps, d_joints, config, 0, steps, hook=hk)
+            # (or MAX_STEPS_PER_CALL at a time)
+            rs = [slv.bench(d_bodies, d_cps, d_joints, config, 0, n, hook=hk) for n in chunks]
             slv.synchronize()
             group.barrier()
             el = time.perf_counter() - t0
             sums.append(slv.bench_checksum())                             # (outside the clock: the last timed step's results)
-            blocks.append(dict(elapsed=el, total_ms=r.total_ms, sweep_ms=r.impulse_kernel_ms, launches=r.impulse_launches, bracketed=r.bracketed_launches,
-                               visits=r.joint_visits, iterations=r.impulse_iterations))
+            blocks.append(dict(elapsed=el, total_ms=sum(r.total_ms for r in rs), sweep_ms=sum(r.impulse_kernel_ms for r in rs),
+                               launches=sum(r.impulse_launches for r in rs), bracketed=sum(r.bracketed_launches for r in rs),
+                               visits=sum(r.joint_visits for r in rs), iterations=sum(r.impulse_iterations for r in rs)))
         # the block every rank reports must be the same one: rank by the max-over-ranks time
         times = [group.reduce_max(b["elapsed"]) for b in blocks]
         mid = int(np.argsort(times)[len(times) // 2])
@@ -250,6 +262,8 @@ def run_bench(args, pdist):
         tot["elapsed_max"] = times[mid]
         tot["all_blocks_ms_per_step"] = [1e3 * t / max(steps, 1) for t in times]
         tot["stats"] = slv.stats()
+        # staged: every timed step solved a copy of the input made before the clock started; else each step restored its input inside it
+        tot["staged"] = len(chunks) == 1 and steps > 0 and steps * (nb * 32 + nj * joints.dtype.itemsize) <= STAGE_BYTES_MAX
         tot["result_check"] = {"what": "64-bit checksum of the last timed step's velocities, displacing velocities and accumulated impulses against the "
                                        "warm-up solve's, every timed block, outside the clock (same input, same schedule: bit-equal)",
                                "checksum": "%016x" % want_sum, "blocks_checked": len(sums), "equal": all(x == want_sum for x in sums)}
@@ -264,6 +278,8 @@ def run_bench(args, pdist):
 
     # ---- timed region: K steps, barrier + device sync on both sides (inside run()), median of `repeats` blocks
     main_tot = run(cfg, args.warmup, args.steps, args.repeats)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, bodies, d_cps, joints, cfg, device, int(main_tot["result_check"]["checksum"], 16))
     st = main_tot["stats"]
     elapsed_max = main_tot["elapsed_max"]
     visits_all = group.reduce_sum(main_tot["visits"])
@@ -445,6 +461,7 @@ def run_bench(args, pdist):
             "unit": "joint-visits/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step,
+            "staged": main_tot["staged"],
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("cfg2: stack(%d,%d) = %d bodies / %d joints, Single Sloppy island mode, %d+%d iterations, one SolveJoints "
@@ -541,6 +558,66 @@ def run_bench(args, pdist):
             out["cpu_baseline"] = cpu_baseline(bodies, cps, joints, args.iters, args.cpu_seconds)
         print(json.dumps(out))
     group.shutdown()
+
+
+def _mix64(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def result_checksum(bodies, joints):
+    """phx_solver_bench_checksum (csrc/solver.hip k_result_checksum) of host records: the sum, modulo 2^64, of one mixed
+    (position, bits) term per velocity word of every body and per accumulated impulse of every joint."""
+    with np.errstate(over="ignore"):
+        words = np.stack([bodies["velocity"]["x"], bodies["velocity"]["y"], bodies["angular_velocity"], bodies["displacing_velocity"]["x"],
+                          bodies["displacing_velocity"]["y"], bodies["displacing_angular_velocity"]], axis=1).astype(np.float32).view(np.uint32)
+        pos = (np.arange(words.size, dtype=np.uint64) + np.uint64(1)) & np.uint64(0xFFFFFFFF)         # 6 i + k + 1, 32-bit as on the device
+        h = _mix64((pos << np.uint64(32)) | words.reshape(-1).astype(np.uint64)).sum(dtype=np.uint64)
+        i1 = np.arange(1, len(joints) + 1, dtype=np.uint64)
+        for mul, field in ((0x9E3779B97F4A7C15, "normal_acc"), (0xC2B2AE3D27D4EB4F, "friction_acc")):
+            bits = np.ascontiguousarray(joints[field], dtype=np.float32).view(np.uint32).astype(np.uint64)
+            h += _mix64(np.uint64(mul) * i1 + bits).sum(dtype=np.uint64)
+    return int(h)
+
+
+def dump_outputs(dirname, bodies, d_cps, joints, cfg, device, want_checksum):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of SolveJoints receives it.  The timed steps solve
+    copies of the input the library keeps to itself, so the same input is solved once more — on a handle of its own, which leaves the
+    timed handle's state to the measurements after this — and the result is taken only if its checksum is the last timed step's
+    (phx_solver_bench_checksum)."""
+    import phyx_amd
+    solver = phyx_amd.Solver(device)
+    d_bodies, d_joints = phyx_amd.DeviceArray(bodies, device), phyx_amd.DeviceArray(joints, device)
+    solver.SolveJointsDevice(d_bodies, d_cps, d_joints, cfg)
+    solver.synchronize()
+    b, j = d_bodies.to_host(), d_joints.to_host()
+    del solver, d_bodies, d_joints
+    got = result_checksum(b, j)
+    if got != want_checksum:
+        raise RuntimeError("--dump-outputs: the re-solve's results (checksum %016x) are not the last timed step's (%016x)" % (got, want_checksum))
+    out = {"body_velocity": np.stack([b["velocity"]["x"], b["velocity"]["y"], b["angular_velocity"]], axis=1),
+           "body_displacing_velocity": np.stack([b["displacing_velocity"]["x"], b["displacing_velocity"]["y"], b["displacing_angular_velocity"]], axis=1),
+           "joint_accumulated_impulse": np.stack([j["normal_acc"], j["friction_acc"]], axis=1)}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in sample_rows({k: v.astype(np.float32) for k, v in out.items()}, DUMP_BYTES_MAX).items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def sample_rows(arrays, limit):
+    """`arrays` as they are if they fit in `limit` bytes together; else every array cut to the same share of its rows, drawn with a
+    fixed seed, in row order, with the row numbers beside it as <name>_rows (float64: exact below 2^53)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total <= limit:
+        return arrays
+    share = limit / (total + sum(8 * len(a) for a in arrays.values()))
+    rng = np.random.default_rng(0)
+    out = {}
+    for name, a in arrays.items():
+        rows = np.sort(rng.choice(len(a), int(len(a) * share), replace=False))
+        out[name] = a[rows]
+        out[name + "_rows"] = rows.astype(np.float64)
+    return out
 
 
 def measure_other_mode(phyx_amd, scenes, Configuration, pdist, group, device, args, cfg, mode, full_scene):

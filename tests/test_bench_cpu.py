@@ -94,3 +94,23 @@ def test_self_launch_takes_the_survivors_down(tmp_path):
     script.write_text("import time\ntime.sleep(600)\n")           # nobody fails, nobody finishes: the launcher's own bound
     t0 = time.time()
     assert pdist.self_launch(2, argv=[str(script)], timeout_s=2) == 124 and time.time() - t0 < 30
+
+
+def test_dump_sample_keeps_what_fits_and_samples_the_rest():
+    """--dump-outputs writes at most DUMP_BYTES_MAX: arrays that fit are written whole, larger ones as the same seeded rows every run."""
+    import numpy as np
+    m = _bench_module()
+    small = {"a": np.arange(30, dtype=np.float32).reshape(10, 3)}
+    assert m.sample_rows(small, 1 << 20) is small
+    big = {"a": np.arange(3000, dtype=np.float32).reshape(1000, 3), "b": np.arange(4000, dtype=np.float32).reshape(2000, 2)}
+    s1, s2 = m.sample_rows(big, 8000), m.sample_rows(big, 8000)
+    assert sum(v.nbytes for v in s1.values()) <= 8000 and set(s1) == {"a", "a_rows", "b", "b_rows"}
+    for k in s1:
+        assert s1[k].tobytes() == s2[k].tobytes() and s1[k].dtype in (np.float32, np.float64)
+    rows = s1["a_rows"].astype(np.int64)
+    assert len(rows) > 0 and (np.diff(rows) > 0).all() and s1["a"].tobytes() == big["a"][rows].tobytes()
+
+
+def test_dump_outputs_is_one_rank_only():
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", "out"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 2 and "--dump-outputs needs --gpus 1" in p.stderr

@@ -338,19 +338,56 @@ def test_native_communicator_gives_up_on_a_missing_peer(built_lib):
     assert time.time() - t0 < 120
 
 
-@pytest.mark.parametrize("ranks", [2, 8])
-@pytest.mark.parametrize("mode", ["slab", "replica"])
-def test_bench_launches_its_own_ranks(built_lib, mode, ranks):
-    """`python bench.py --gpus N` without torchrun: bench.py spawns the N ranks itself (here all of them on GPU 0 over gloo) and rank 0
-    prints the one JSON line of the cfg-3 workload — in slab mode (ownership sharding, the default) and in replica mode; N = 8 is
-    the shape of the driver's scaling run (eight processes, eight slabs / eight shares of the groups, the per-step collective)."""
+def test_bench_steps_and_dumped_outputs(built_lib, tmp_path):
+    """`--steps K` times K steps, also past the library's MAX_STEPS_PER_CALL steps per call (every one of them launched), and
+    `--dump-outputs` writes what the last timed step computed (bench.py checks it against that step's checksum): the same input gives
+    the same arrays whatever K is.  The short run keeps the default side measurements, which follow the dump."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs, lines = {}, {}
+    for steps, side in ((3, []), (4100, ["--no-secondary"])):
+        d = str(tmp_path / ("k%d" % steps))
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--columns", "48", "--rows", "30", "--steps", str(steps), "--warmup", "1",
+                            "--repeats", "1", "--no-cpu-baseline", "--dump-outputs", d] + side, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                           text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
+        out = lines[steps] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert out["steps"] == steps and out["ms_per_step"] > 0 and out["result_check"]["equal"] and "error" not in out
+        outs[steps] = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert lines[3]["staged"] is True and lines[4100]["staged"] is False
+    assert lines[3]["live_topology"]["ms_per_step"] > 0 and lines[3]["cfg2_world_step"]["ms_per_step"] > 0
+    # identical input => identical launches per step: 4100 timed steps were launched, not just the last call's
+    per_step = lines[3]["roofline"]["launches"] / 3
+    assert per_step >= 1 and lines[4100]["roofline"]["launches"] == per_step * 4100
+    assert sorted(outs[3]) == ["body_displacing_velocity.npy", "body_velocity.npy", "joint_accumulated_impulse.npy"]
+    assert len(outs[3]["body_velocity.npy"]) == 48 * 30 + 1
+    for f, a in outs[3].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.tobytes() == outs[4100][f].tobytes(), f
+    assert np.abs(outs[3]["joint_accumulated_impulse.npy"]).max() > 0
+
+
+@pytest.mark.parametrize("ranks", [2, 8])
+@pytest.mark.parametrize("mode", ["slab", "replica"])
+def test_bench_launches_its_own_ranks(built_lib, mode, ranks):
+    """`python bench.py --gpus N` without torchrun: bench.py spawns the N ranks itself and rank 0 prints the one JSON line of the cfg-3
+    workload — in slab mode (ownership sharding, the default) and in replica mode.  N = 2: both ranks on GPU 0 over gloo.  N = 8 is
+    the shape of the driver's scaling run (eight processes, eight slabs / eight shares of the groups, the per-step collective) and is
+    run as that run is: bench.py's default transport (RCCL), one rank per GPU (device = local rank)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    # two ranks share GPU 0 over gloo; eight ranks get a GPU each (the rccl transport places rank r on device r)
+    backend = "gloo" if ranks == 2 else "rccl"
+    n_dev = built_lib.phx_device_count()
+    if backend == "rccl" and n_dev < ranks:
+        pytest.skip("needs %d GPUs (one per rank), found %d" % (ranks, n_dev))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--backend", "gloo", "--mode", mode, "--columns", "48", "--rows", "30", "--steps", "3",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--backend", backend, "--mode", mode, "--columns", "48", "--rows", "30", "--steps", "3",
                         "--warmup", "1", "--repeats", "1", "--no-secondary", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
