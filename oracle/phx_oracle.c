@@ -346,12 +346,14 @@ typedef struct {
      * sw_iter[p][b] = the iteration (parity p) in which a joint on b was last productive,
      * sw_col[p][b]  = the smallest colour index that was productive in that iteration. */
     int32_t *sw_iter[2], *sw_col[2];
+    int32_t* statics; int nstatic;   /* the static bodies (prepare_bodies): the only ones whose words above are ever read */
     phxo_solve_stats* st;
 } sctx;
 
 /* ref: Solver.cpp:456-480 */
 static void prepare_bodies(sctx* c, const phxo_body* bodies)
 {
+    c->nstatic = 0;
     for (int i = 0; i < c->nb; ++i) {
         const phxo_body* b = &bodies[i];
         c->par[i].im = b->inv_mass; c->par[i].ii = b->inv_inertia;
@@ -360,6 +362,7 @@ static void prepare_bodies(sctx* c, const phxo_body* bodies)
         c->disp[i].vx = b->displacing_velocity.x; c->disp[i].vy = b->displacing_velocity.y;
         c->disp[i].w = b->displacing_angular_velocity; c->disp[i].tag = -1;
         c->is_static[i] = (b->inv_mass == 0.f && b->inv_inertia == 0.f); /* ref: Solver.cpp:304 */
+        if (c->is_static[i]) c->statics[c->nstatic++] = i;
     }
 }
 
@@ -499,8 +502,14 @@ static inline void mark_productive(sctx* c, sbody* arr, int body, int slot, int 
 
 static void reset_static_words(sctx* c)
 {
-    for (int p = 0; p < 2; ++p)
-        for (int i = 0; i < c->nb; ++i) { c->sw_iter[p][i] = -100; c->sw_col[p][i] = 0; }
+    /* (every body's words at first; once the static bodies are listed, theirs only — per island, a world of thousands of islands
+     *  would otherwise pay islands x bodies) */
+    for (int p = 0; p < 2; ++p) {
+        if (c->statics)
+            for (int k = 0; k < c->nstatic; ++k) { c->sw_iter[p][c->statics[k]] = -100; c->sw_col[p][c->statics[k]] = 0; }
+        else
+            for (int i = 0; i < c->nb; ++i) { c->sw_iter[p][i] = -100; c->sw_col[p][i] = 0; }
+    }
 }
 
 /* one joint of ref: Solver.cpp:800-911; returns productive */
@@ -716,6 +725,7 @@ static void ctx_alloc(sctx* c, int nb, int slots)
         c->sw_col[p] = (int32_t*)malloc((nb + 1) * sizeof(int32_t));
     }
     reset_static_words(c);
+    c->statics = (int32_t*)malloc((nb + 1) * sizeof(int32_t));
     c->pj = (pjoint*)calloc(slots + 8, sizeof(pjoint));
     c->joint_index = (int32_t*)malloc((slots + 8) * sizeof(int32_t));
 }
@@ -723,7 +733,7 @@ static void ctx_alloc(sctx* c, int nb, int slots)
 static void ctx_free(sctx* c)
 {
     free(c->imp); free(c->disp); free(c->par); free(c->is_static); for (int p = 0; p < 2; ++p) { free(c->sw_iter[p]); free(c->sw_col[p]); }
-    free(c->pj); free(c->joint_index);
+    free(c->pj); free(c->joint_index); free(c->statics);
 }
 
 /* ref: Solver.cpp:509-521 CopyJoints into packed slots */
@@ -909,7 +919,7 @@ void phxo_solver_solve_grouped_fp16(phxo_body* bodies, int nb, const phxo_contac
     for (int g = 0; g < ngroups; ++g) {
         int b = group_offsets[g], e = group_offsets[g + 1];
         if (e - b > stats->island_max_size) stats->island_max_size = e - b;
-        for (int i = 0; i < nb; ++i) if (c.is_static[i]) { c.imp[i].tag = -1; c.disp[i].tag = -1; }
+        for (int k = 0; k < c.nstatic; ++k) { c.imp[c.statics[k]].tag = -1; c.disp[c.statics[k]].tag = -1; }
         c.fp16 = g < fp16_groups;
         if (c.fp16) {       /* the group's working copy of its bodies is binary16 from the start (the statics' copy is private) */
             for (int s = b; s < e; ++s)

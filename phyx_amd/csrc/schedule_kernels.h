@@ -683,7 +683,8 @@ struct BinBuildView {
     // the bin's units, in any order: records (k_joint_scatter) ...
     const int4* rec_a; const int2* rec_b;
     // ... or manifolds (k_manifold_slots; rec_a null): the unit's joints are its contact points' solver_index
-    const int2* unit_m; const phx_manifold* manifolds; const phx_contact_point* cps; const phx_contact_joint* joints; int nj;
+    const int2* unit_m; const phx_manifold* manifolds; const phx_contact_point* cps; const phx_contact_joint* joints;
+    int nj;                           // the solve's joints — on EVERY path: it picks the sort below (packed key only if every joint index fits it)
     const int* group_offsets;         // slots of bin g = [group_offsets[g], group_offsets[g+1]) — its units' records / manifolds from the first slot on
     const unsigned* cursor;           // units dealt to each bin
     const int* spoil;                 // (may be null) the dealers' fail bits: nobody builds on a spoiled deal
@@ -793,7 +794,8 @@ static __global__ void __launch_bounds__(T) k_build_bin(BinBuildView v)
         constexpr int LANE_BITS = LANES > 256 ? 9 : 8;
         static_assert(LANES <= (1 << LANE_BITS), "lane index must fit the packed sort key");
         if (v.nj < (1 << (31 - LANE_BITS))) {
-            // joint indices below 2^(31 - LANE_BITS): (joint, lane) is ONE 32-bit key — a shuffle, a min and a max per step of the network
+            // every joint index below 2^(31 - LANE_BITS) (v.nj is set by all three builds): (joint, lane) is ONE 32-bit key whose bit 31
+            // stays clear for the idle lanes — a shuffle, a min and a max per step of the network
             unsigned kv = tid < nu ? ((unsigned)ra.x << LANE_BITS) | (unsigned)tid : 0x80000000u | (unsigned)tid;      // (the lanes beyond the bin's units sort behind them)
 #pragma unroll
             for (int k = 2; k <= LANES; k <<= 1) {
@@ -813,6 +815,7 @@ static __global__ void __launch_bounds__(T) k_build_bin(BinBuildView v)
             }
             src = (int)(kv & (unsigned)((1 << LANE_BITS) - 1));
         } else {
+            // larger solves (2^23 joints and more, 2^22 with 512 lanes): (joint, lane) as two words
             unsigned key = tid < nu ? (unsigned)ra.x : 0x80000000u + (unsigned)tid;
 #pragma unroll
             for (int k = 2; k <= LANES; k <<= 1) {

@@ -476,7 +476,7 @@ int DeviceSolver::build_schedule_device(const float4* d_bodies, int nb, const ph
         BinBuildView bv{};
         PHX_TRY(isl_.units.reserve(nbins)); PHX_TRY(isl_.unit_recs.reserve(2 * (size_t)nbins * cap_units));
         bv.rec_a = bld_.rec_a.p; bv.rec_b = bld_.rec_b.p; bv.group_offsets = grp_goff; bv.cursor = bld_.bin_cursor.p; bv.spoil = bld_.sb_small.p + 3;
-        bv.nb = nb; bv.max_static = 1 << 30;
+        bv.nb = nb; bv.nj = nj; bv.max_static = 1 << 30;      // (nj: k_build_bin's sort key width)
         bv.order = hbm_.order.p; bv.slot_local = isl_.slot_local.p; bv.slot_colour = isl_.slot_colour.p; bv.desc = isl_.desc.p; bv.ncol = isl_.ncol.p;
         bv.units = isl_.units.p; bv.unit_recs = isl_.unit_recs.p;
         bv.bodies = isl_.bodies.p; bv.rejected = bld_.sb_small.p + 2; bv.poison = hash_.p + hash_slot_;
@@ -739,7 +739,7 @@ int DeviceSolver::build_bins_speculative(const float4* d_bodies, int nb, const p
     PHX_TRY(isl_.slot_local.reserve(nj)); PHX_TRY(isl_.slot_colour.reserve(nj));
     PHX_TRY(isl_.units.reserve(grid)); PHX_TRY(isl_.unit_recs.reserve(2 * (size_t)grid * cap_units));
     bv.group_offsets = goff; bv.cursor = bld_.bin_cursor.p;
-    bv.nb = nb; bv.max_static = 1 << 30;
+    bv.nb = nb; bv.nj = nj; bv.max_static = 1 << 30;      // (nj: k_build_bin's sort key width, on either path)
     bv.order = hbm_.order.p; bv.slot_local = isl_.slot_local.p; bv.slot_colour = isl_.slot_colour.p; bv.desc = isl_.desc.p; bv.ncol = isl_.ncol.p;
     bv.units = isl_.units.p; bv.unit_recs = isl_.unit_recs.p;
     bv.bodies = isl_.bodies.p; bv.rejected = bld_.sb_small.p + 2; bv.poison = hash_.p + hash_slot_;

@@ -12,28 +12,36 @@ from helpers import oracle_world
 pytestmark = pytest.mark.gpu
 
 
-def _lockstep(oracle, scene, steps, cfg, check_every=1):
+def _lockstep(oracle, scene, steps, cfg, check_every=1, check_at=(), on_step=None):
+    """Steps the device World and the oracle World side by side, the oracle's solver replaying the device's schedule; every byte is
+    compared at every `check_every`-th step, at the steps in `check_at` and at the last one.  `on_step(pw, step)`, if given, is called
+    once the step's schedule has been fetched (the solver's statistics are settled then)."""
     pw = phyx_amd.World(0, gravity=-200.0)
     pw.add_scene(scene)
     ow = oracle_world(scene)
     assert pw.bodies.tobytes() == ow.bodies().tobytes()                    # AddBody / RigidBody ctor
+    check_at = set(check_at)
     for step in range(steps):
         pw.Update(1.0 / 60.0, cfg)
         ow.pre_solve(1.0 / 60.0)
         order, offs = pw.solver.schedule()
         groups, _ = pw.solver.groups()
+        if on_step is not None:
+            on_step(pw, step)
         b, cp, j = ow.bodies(), ow.contact_points(), ow.joints()           # live views into the oracle world
         assert len(order) == len(j)
         oracle.solver_solve_grouped(b, cp, j, order, offs, groups, cfg.contactIterationsCount, cfg.penetrationIterationsCount,
                                     oracle.STAG_COLOUR_SYNC)
         ow.integrate_position(1.0 / 60.0)
-        if step % check_every == 0 or step == steps - 1:
+        if step % check_every == 0 or step in check_at or step == steps - 1:
             assert pw.counts() == (len(ow.bodies()), len(ow.manifolds()), len(ow.contact_points()), len(ow.joints())), "step %d" % step
             assert pw.manifolds.tobytes() == ow.manifolds().tobytes(), "manifolds differ at step %d" % step
             assert pw.contactJoints.tobytes() == ow.joints().tobytes(), "joints differ at step %d" % step
             assert pw.bodies.tobytes() == ow.bodies().tobytes(), "bodies differ at step %d" % step
+            # the manifolds' contact points, manifold by manifold (the slots past a manifold's point_count are not live)
             m = ow.manifolds()
-            live = np.concatenate([np.arange(int(x["point_index"]), int(x["point_index"]) + int(x["point_count"])) for x in m] + [np.zeros(0, dtype=np.int64)]).astype(np.int64)
+            first, count = m["point_index"].astype(np.int64), m["point_count"].astype(np.int64)
+            live = np.repeat(first - (np.cumsum(count) - count), count) + np.arange(int(count.sum()), dtype=np.int64)
             assert pw.contactPoints[live].tobytes() == ow.contact_points()[live].tobytes(), "contact points differ at step %d" % step
     return pw, ow
 
