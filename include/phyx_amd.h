@@ -394,6 +394,36 @@ int  phx_world_get_bodies(phx_world* w, phx_rigid_body* out, int32_t cap);
 int  phx_world_get_manifolds(phx_world* w, phx_manifold* out, int32_t cap);
 int  phx_world_get_contact_points(phx_world* w, phx_contact_point* out, int32_t cap);
 int  phx_world_get_joints(phx_world* w, phx_contact_joint* out, int32_t cap);
+/* EDITS BETWEEN STEPS — what the reference's application does to its public RigidBody array before every Update (ref: main.cpp:337-349,
+ * the mouse drag; RigidBody.h:38-42).  Every edit is a batch: `count` body indices with their values, read from host memory.
+ *   - Queued on phx_world_stream(w) behind whatever is queued there; the call returns as soon as the caller's arrays may be reused
+ *     (they are staged through pinned memory the world owns) and does not wait for a step still in flight.
+ *   - Between steps only: an edit made between phx_world_pre_solve and phx_world_finish_step, or between phx_world_step_begin and
+ *     phx_world_step_end, returns PHX_ERR_STATE.
+ *   - Checked completely before anything is queued: count >= 0, every index in [0, body count), no index twice in one call;
+ *     PHX_ERR_INVALID otherwise, and the world is unchanged.  Edits of separate calls apply in call order.
+ *   - An edit of host-staged bodies (before the first step, or after add_body / set_body_static / set_body_inverse_mass) acts as if
+ *     written into their records; edits queued on the device survive a later host-staging call.
+ *   - They change no joint topology: the cached solver schedule stays valid.
+ *   - Sharded worlds: in replica mode (phx_world_set_shard / set_comm) every rank must apply the same batches, as with every other
+ *     input.  The indices are the world's own; an ownership-sharded (slab) world's indices are local to its rank.
+ * acceleration += {ax, ay}, angularAcceleration += angular (ref: main.cpp:343-346), accel = 3 floats per body.  They add to whatever is
+ * pending (accelerations restored by phx_world_set_state included), show in the records until the next step's IntegrateVelocity
+ * consumes them (ref: World.cpp:44-53), and read as zero after it. */
+int  phx_world_add_accelerations(phx_world* w, const int32_t* bodies, const float* accel, int32_t count);
+/* velocity = {vx, vy}, angularVelocity = angular; vel = 3 floats per body */
+int  phx_world_set_velocities(phx_world* w, const int32_t* bodies, const float* vel, int32_t count);
+/* coords = {pos, xVector, yVector}, then UpdateGeom (ref: RigidBody.h:38-42, Geom.h:79-85): the AABB is recomputed, and the next step's
+ * broadphase and UpdateManifolds see the new geometry.  pose = 6 floats per body {pos.x, pos.y, xv.x, xv.y, yv.x, yv.y}: a frame,
+ * not an angle, so that nothing is rounded on the way (phyx_amd.World.set_poses builds frames from angles as add_body does). */
+int  phx_world_set_poses(phx_world* w, const int32_t* bodies, const float* pose, int32_t count);
+/* GATHERS (any time, like phx_world_get_bodies; they wait for the queued work).  The 128-byte records of the listed bodies,
+ * byte-equal to phx_world_get_bodies()[bodies[k]]; O(count) work and transfer.  Indices as above, repeats allowed. */
+int  phx_world_get_body_states(phx_world* w, const int32_t* bodies, int32_t count, phx_rigid_body* out);
+/* {pos.x, pos.y, xVector.x, xVector.y} of every body, 16 B per body (cap: room for that many bodies, PHX_ERR_CAPACITY otherwise) */
+int  phx_world_get_poses(phx_world* w, float* out, int32_t cap);
+/* the same into caller-owned device memory (16-byte aligned), queued on phx_world_stream(w): no host wait, nothing over PCIe */
+int  phx_world_get_poses_device(phx_world* w, void* d_out, int32_t cap);
 /* Restore a world from what the four getters above returned (checkpoint / resume; the hand-over of bodies between the ranks of an
  * ownership-sharded world): bodies, the contact cache — manifolds with their two contact-point slots each, ref: Collider.h:57-58 —
  * and the joints with their warm-start impulses (ref: World.h:33).  The broadphase's pair set is rebuilt from the manifolds'

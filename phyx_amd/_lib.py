@@ -152,6 +152,12 @@ _SIGNATURES = {
     "phx_world_get_contact_points": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_get_joints": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_set_state": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32]),
+    "phx_world_add_accelerations": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_set_velocities": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_set_poses": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_get_body_states": (C.c_int, [_vp, _vp, _i32, _vp]),
+    "phx_world_get_poses": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_get_poses_device": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_get_solve_stats": (C.c_int, [_vp, C.POINTER(SolveStats)]),
     "phx_world_get_broadphase_stats": (C.c_int, [_vp, C.POINTER(BroadphaseStats)]),
     "phx_world_solver": (_vp, [_vp]),

@@ -10,6 +10,7 @@ handed to the oracle in tests/.  All compute happens inside libphyx_amd.so (HIP)
 falls back to numpy or the CPU.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -42,6 +43,14 @@ assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def frame_from_angle(px, py, angle):
+    """{pos.x, pos.y, xv.x, xv.y, yv.x, yv.y} of a body at `angle`, rounded as AddBody rounds it (ref: RigidBody.h:15-36, Coords2.h:10-17:
+    the float angle and angle + pi / 2 go through the double cos / sin, then narrow to float)."""
+    a = np.float32(angle)
+    quarter = np.float32(a + np.float32(np.float32(3.141592) / np.float32(2.0)))
+    return np.array([px, py, math.cos(float(a)), math.sin(float(a)), math.cos(float(quarter)), math.sin(float(quarter))], dtype=np.float32)
 
 
 def _contig(a, dtype):
@@ -638,6 +647,69 @@ class World:
         b = np.ascontiguousarray(bodies, dtype=rigid_body_dtype); m = np.ascontiguousarray(manifolds, dtype=manifold_dtype)
         c = np.ascontiguousarray(contact_points, dtype=contact_point_dtype); j = np.ascontiguousarray(joints, dtype=contact_joint_dtype)
         check(self.L.phx_world_set_state(self.h, _ptr(b), len(b), _ptr(m), len(m), _ptr(c), len(c), _ptr(j), len(j)))
+
+    # ---- edits and gathers between steps (include/phyx_amd.h: phx_world_add_accelerations ...) ----
+    def _indices(self, bodies, what):
+        idx = np.asarray(bodies)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu":
+            raise TypeError("%s: body indices must be a 1-D integer array, got %s of shape %s" % (what, idx.dtype, idx.shape))
+        if idx.size and (idx.min() < np.iinfo(np.int32).min or idx.max() > np.iinfo(np.int32).max):
+            raise ValueError("%s: body index out of the int32 range" % what)
+        return np.ascontiguousarray(idx, dtype=np.int32)
+
+    def _values(self, values, count, width, what):
+        v = np.asarray(values)
+        if v.dtype.kind != "f":
+            raise TypeError("%s: values must be a float array, got %s" % (what, v.dtype))
+        if v.shape != (count, width):
+            raise ValueError("%s: values must have shape (%d, %d), got %s" % (what, count, width, v.shape))
+        return np.ascontiguousarray(v, dtype=np.float32)
+
+    def _edit(self, fn, bodies, values, width, what):
+        idx = self._indices(bodies, what)
+        v = self._values(values, len(idx), width, what)
+        check(getattr(self.L, fn)(self.h, _ptr(idx), _ptr(v), len(idx)))
+
+    def add_accelerations(self, bodies, accel):
+        """acceleration += accel[k] on body bodies[k]: accel is (K, 3) {ax, ay, angular} (ref: main.cpp:343-346).  The next Update's
+        IntegrateVelocity consumes them; until then they show in the records."""
+        self._edit("phx_world_add_accelerations", bodies, accel, 3, "add_accelerations")
+
+    def set_velocities(self, bodies, vel):
+        """velocity, angularVelocity = vel[k] {vx, vy, angular} on body bodies[k]."""
+        self._edit("phx_world_set_velocities", bodies, vel, 3, "set_velocities")
+
+    def set_poses(self, bodies, poses):
+        """Move bodies (ref: RigidBody.h:38-42: coords, then UpdateGeom).  poses: (K, 6) frames {pos.x, pos.y, xv.x, xv.y, yv.x, yv.y},
+        or (K, 3) {pos.x, pos.y, angle}, turned into a frame by the float formula of AddBody (ref: RigidBody.h:15-36, Coords2.h:10-17)."""
+        p = np.asarray(poses)
+        if p.ndim == 2 and p.shape[1] == 3:
+            p = self._values(p, p.shape[0], 3, "set_poses")
+            p = np.stack([frame_from_angle(x, y, a) for x, y, a in p]) if len(p) else np.zeros((0, 6), dtype=np.float32)
+        self._edit("phx_world_set_poses", bodies, p, 6, "set_poses")
+
+    def body_states(self, bodies):
+        """The 128-byte records of the listed bodies, equal to bodies[bodies] byte for byte, at O(len(bodies)) cost."""
+        idx = self._indices(bodies, "body_states")
+        out = np.zeros(len(idx), dtype=rigid_body_dtype)
+        check(self.L.phx_world_get_body_states(self.h, _ptr(idx), len(idx), _ptr(out)))
+        return out
+
+    def poses(self, out=None):
+        """(N, 4) float32 {pos.x, pos.y, xv.x, xv.y} of every body (16 B per body instead of the 128-byte record)."""
+        n = self.counts()[0]
+        if out is None:
+            out = np.zeros((n, 4), dtype=np.float32)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float32 or out.shape != (n, 4) or not out.flags.c_contiguous:
+            raise ValueError("poses: out must be a C-contiguous float32 array of shape (%d, 4)" % n)
+        check(self.L.phx_world_get_poses(self.h, _ptr(out), n))
+        return out
+
+    def poses_device(self, ptr, cap=None):
+        """The same into device memory at `ptr` (16-byte aligned, room for `cap` bodies, default all of them), queued on the world's
+        stream (stream_ptr()); e.g. a torch tensor's data_ptr()."""
+        n = self.counts()[0]
+        check(self.L.phx_world_get_poses_device(self.h, C.c_void_p(int(ptr)), n if cap is None else int(cap)))
 
     def sync(self):
         """Wait for the queued step (Update returns once the step is queued; getters synchronise on their own)."""

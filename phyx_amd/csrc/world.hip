@@ -50,6 +50,12 @@ public:
     int set_state(const phx_rigid_body* bodies, int body_count, const phx_manifold* manifolds, int manifold_count,
                   const phx_contact_point* cps, int cp_count, const phx_contact_joint* joints, int joint_count);
     int get_slab_state(const long long* global_index, int count, SlabState* out);      // this world as a re-slab hands it over (reslab.h)
+    // edits and gathers between steps (phx_world_add_accelerations ... phx_world_get_poses_device)
+    enum Edit { EDIT_ACCELERATIONS, EDIT_VELOCITIES, EDIT_POSES };
+    int edit(Edit kind, const int* bodies, const float* values, int count);
+    int get_body_states(const int* bodies, int count, phx_rigid_body* out);
+    int get_poses(float* out, int cap);
+    int get_poses_device(void* d_out, int cap);
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -115,12 +121,27 @@ private:
     unsigned sharded_steps_ = 0;
     size_t agreed_seg_ = 0;                  // segment bytes of the last host-read agreement (0: none): step_sharded
     int ensure_exchange_capacity(size_t bytes);
+    // edits between steps: the bracket they are refused in, and their staging
+    bool mid_step_ = false;                  // set by pre_solve, cleared by finish_step / step_end (and by the calls that wrap them)
+    int check_batch(const char* what, const int* bodies, const void* values, int count, bool edit);
+    int stage_batch(const int* bodies, const float* values, int count, int width, const int** d_bodies, const float** d_values);
+    std::vector<unsigned> edit_seen_; unsigned edit_epoch_ = 0;      // duplicate check: edit_seen_[i] == edit_epoch_ <=> body i is in this batch
+    char* stage_pin_ = nullptr; size_t stage_cap_ = 0, stage_used_ = 0;      // pinned staging of the batches: bump-allocated while copies are pending
+    hipEvent_t stage_done_ = nullptr;        // recorded behind the last batch's copy: once it has passed, the staging buffer is free again
+    std::vector<char*> stage_retired_;       // outgrown staging buffers a pending copy may still read: freed with the world
+    DevBuf<char> edit_dev_;                  // the batch on the device (stream order protects it from the next batch's copy)
+    std::vector<DevBuf<char>> edit_dev_retired_;      // outgrown device batches a pending scatter may still read: freed with the world
+    DevBuf<phx_rigid_body> gathered_;
+    DevBuf<float4> poses_;
 };
 
 World::~World()
 {
     if (hipSetDevice(device_) != hipSuccess) return;
     if (stream_) (void)hipStreamSynchronize(stream_);
+    for (char* p : stage_retired_) (void)hipHostFree(p);
+    if (stage_pin_) (void)hipHostFree(stage_pin_);
+    if (stage_done_) (void)hipEventDestroy(stage_done_);
     // (device buffers are DevBuf members: freed with the object)
     // (stream_ belongs to the broadphase handle, which is destroyed after this body and after the solver handle)
 }
@@ -431,6 +452,7 @@ int World::pre_solve(float dt)
 {
     using clk = std::chrono::steady_clock;
     PHX_TRY(use_device(device_));
+    mid_step_ = true;
     PHX_TRY(sync_bodies_to_device());
     auto t = clk::now();
     auto lap = [&](int phase) { if (!phase_timing) return; (void)hipStreamSynchronize(stream_); auto n = clk::now(); phase_ms[phase] = std::chrono::duration<double, std::milli>(n - t).count(); t = n; };
@@ -476,6 +498,7 @@ int World::step_begin(float dt, const phx_config& cfg, size_t* segment_bytes)
 
 int World::step_end(float dt)
 {
+    mid_step_ = false;
     PHX_TRY(use_device(device_));
     { RoctxRange r("Exchange: unpack"); PHX_TRY(solver_.exchange_unpack_resident(resident().s, d_joints_.p)); }
     RoctxRange r("IntegratePosition");
@@ -519,6 +542,7 @@ int World::set_comm(Comm* c)
 int World::step_sharded(float dt, const phx_config& cfg)
 {
     const int st = step_sharded_inner(dt, cfg);
+    mid_step_ = false;
     if (st != PHX_OK) agreed_seg_ = 0;
     return st;
 }
@@ -614,6 +638,7 @@ int World::finish_step(float dt, const phx_config& cfg)
 {
     using clk = std::chrono::steady_clock;
     if (shard_count > 1) { set_error("a sharded world steps through phx_world_step_begin / all-gather / phx_world_step_end"); return PHX_ERR_STATE; }
+    mid_step_ = false;
     PHX_TRY(use_device(device_));
     PHX_TRY(sync_bodies_to_device());
     auto t = clk::now();
@@ -641,7 +666,8 @@ int World::synchronize()
 int World::update(float dt, const phx_config& cfg)
 {
     if (shard_count > 1) { set_error("a sharded world steps through phx_world_step_begin / all-gather / phx_world_step_end"); return PHX_ERR_STATE; }
-    PHX_TRY(pre_solve(dt));
+    const int st = pre_solve(dt);
+    if (st != PHX_OK) { mid_step_ = false; return st; }
     return finish_step(dt, cfg);
 }
 
@@ -699,7 +725,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     for (int i = 0; i < nm; ++i) pairs[i] = make_uint2((unsigned)manifolds[i].body1, (unsigned)manifolds[i].body2);
     PHX_TRY(broadphase_.reset_pairs(pairs.data(), nm));
     // nothing of the old world's bookkeeping survives
-    joints_changed_ = true; pack_pending_ = false; expect_no_dead_manifolds_ = false; fresh_manifolds_ = 0; manifolds_updated_ = 0; fuse_velocity_ = false;
+    joints_changed_ = true; pack_pending_ = false; expect_no_dead_manifolds_ = false; fresh_manifolds_ = 0; manifolds_updated_ = 0; fuse_velocity_ = false; mid_step_ = false;
     if (joint_seen_.p) { PHX_HIP(hipMemsetAsync(joint_seen_.p, 0, joint_seen_.cap * sizeof(unsigned), stream_)); }
     joint_epoch_ = 0;
     PHX_HIP(hipStreamSynchronize(stream_));
@@ -728,6 +754,156 @@ int World::download_bodies(phx_rigid_body* out, int cap)
     PHX_TRY(refresh_records());
     PHX_HIP(hipStreamSynchronize(stream_));
     if (n) PHX_HIP(hipMemcpy(out, d_bodies_.p, (size_t)n * sizeof(phx_rigid_body), hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+// ---- edits and gathers between steps ------------------------------------------------------------------------------------------
+// The reference's application writes into its public RigidBody array before every Update (ref: main.cpp:337-346: the mouse drag).
+// Here an edit is a batch of body indices with values from host memory: checked completely first (all of it or none of it), then
+// either written into the host-staged records (bodies_dirty_: before the first step, after add_body / set_inverse_mass / set_static),
+// or staged through pinned memory and scattered by one kernel queued on the stream — no host wait for a step still in flight.
+// (`edit`: an edit — refused inside a step, every index at most once — rather than a gather)
+int World::check_batch(const char* what, const int* bodies, const void* values, int count, bool edit)
+{
+    if (edit && mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && (!bodies || !values)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    const int n = nb();
+    for (int k = 0; k < count; ++k)
+        if (bodies[k] < 0 || bodies[k] >= n) { set_error("%s: body index %d out of range [0, %d)", what, bodies[k], n); return PHX_ERR_INVALID; }
+    if (!edit || count < 2) return PHX_OK;
+    if (edit_seen_.size() < (size_t)n) { edit_seen_.assign((size_t)n, 0u); edit_epoch_ = 0; }
+    if (++edit_epoch_ == 0) { std::fill(edit_seen_.begin(), edit_seen_.end(), 0u); edit_epoch_ = 1; }
+    for (int k = 0; k < count; ++k) {
+        unsigned& seen = edit_seen_[(size_t)bodies[k]];
+        if (seen == edit_epoch_) { set_error("%s: body %d appears twice in one call", what, bodies[k]); return PHX_ERR_INVALID; }
+        seen = edit_epoch_;
+    }
+    return PHX_OK;
+}
+
+// {indices | values} in one H2D copy.  The pinned buffer is bump-allocated while earlier batches' copies are still queued (they may sit
+// behind a step in flight) and reused from the start once stage_done_ has passed; an outgrown buffer is kept until the world goes.
+int World::stage_batch(const int* bodies, const float* values, int count, int width, const int** d_bodies, const float** d_values)
+{
+    const size_t ib = ((size_t)count * sizeof(int) + 15) & ~size_t(15), bytes = ib + (size_t)count * (size_t)width * sizeof(float);
+    if (!stage_done_) PHX_HIP(hipEventCreateWithFlags(&stage_done_, hipEventDisableTiming));
+    else if (stage_used_) {
+        const hipError_t q = hipEventQuery(stage_done_);
+        if (q == hipSuccess) stage_used_ = 0;
+        else if (q != hipErrorNotReady) { set_error("staging: %s", hipGetErrorString(q)); return PHX_ERR_HIP; }
+    }
+    size_t off = (stage_used_ + 15) & ~size_t(15);
+    if (off + bytes > stage_cap_) {
+        const size_t cap = std::max<size_t>(std::max<size_t>(2 * bytes, 2 * stage_cap_), 64u << 10);
+        if (stage_pin_) stage_retired_.push_back(stage_pin_);
+        stage_pin_ = nullptr; stage_cap_ = 0;
+        PHX_HIP(hipHostMalloc(reinterpret_cast<void**>(&stage_pin_), cap, hipHostMallocDefault));
+        stage_cap_ = cap;
+        off = 0;
+    }
+    if (bytes > edit_dev_.cap && edit_dev_.p) edit_dev_retired_.push_back(std::move(edit_dev_));
+    PHX_TRY(edit_dev_.reserve(bytes));
+    std::memcpy(stage_pin_ + off, bodies, (size_t)count * sizeof(int));
+    if (width) std::memcpy(stage_pin_ + off + ib, values, bytes - ib);
+    PHX_HIP(hipMemcpyAsync(edit_dev_.p, stage_pin_ + off, bytes, hipMemcpyHostToDevice, stream_));
+    PHX_HIP(hipEventRecord(stage_done_, stream_));
+    stage_used_ = off + bytes;
+    *d_bodies = reinterpret_cast<const int*>(edit_dev_.p);
+    *d_values = reinterpret_cast<const float*>(edit_dev_.p + ib);
+    return PHX_OK;
+}
+
+int World::edit(Edit kind, const int* bodies, const float* values, int count)
+{
+    static const char* const what[] = {"phx_world_add_accelerations", "phx_world_set_velocities", "phx_world_set_poses"};
+    PHX_TRY(check_batch(what[kind], bodies, values, count, true));
+    if (!count) return PHX_OK;
+    const int width = kind == EDIT_POSES ? 6 : 3;
+    if (bodies_dirty_ || !d_bodies_.p) {                                    // the host-staged records are the world: write into them
+        for (int k = 0; k < count; ++k) {
+            phx_rigid_body& b = host_bodies_[(size_t)bodies[k]];
+            const float* v = values + (size_t)width * k;
+            if (kind == EDIT_ACCELERATIONS) { b.acceleration.x += v[0]; b.acceleration.y += v[1]; b.angular_acceleration += v[2]; }
+            else if (kind == EDIT_VELOCITIES) { b.velocity.x = v[0]; b.velocity.y = v[1]; b.angular_velocity = v[2]; }
+            else { b.pos.x = v[0]; b.pos.y = v[1]; b.xvector.x = v[2]; b.xvector.y = v[3]; b.yvector.x = v[4]; b.yvector.y = v[5]; update_geom(b); }
+        }
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());             // (the edit goes behind a settled solve, never under a replay)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, values, count, width, &d_bodies, &d_values));
+    if (kind == EDIT_ACCELERATIONS) {
+        // the next IntegrateVelocity consumes accel_ (ref: World.cpp:44-53); the first edit after a step starts it from zero on the device
+        if (!accel_pending_) {
+            PHX_TRY(accel_.reserve((size_t)nb()));
+            PHX_HIP(hipMemsetAsync(accel_.p, 0, (size_t)nb() * sizeof(float4), stream_));
+            accel_pending_ = true;
+        }
+        hipLaunchKernelGGL(k_add_accelerations, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, accel_.p, d_bodies_.p);
+    } else if (kind == EDIT_VELOCITIES) {
+        hipLaunchKernelGGL(k_set_velocities, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, vel_.p);
+        records_stale_ = true;
+    } else {
+        hipLaunchKernelGGL(k_set_poses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, resident());
+        records_stale_ = true;
+    }
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+int World::get_body_states(const int* bodies, int count, phx_rigid_body* out)
+{
+    PHX_TRY(check_batch("phx_world_get_body_states", bodies, out, count, false));
+    if (!count) return PHX_OK;
+    if (bodies_dirty_ || !d_bodies_.p) {
+        for (int k = 0; k < count; ++k) out[k] = host_bodies_[(size_t)bodies[k]];
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before its results are read)
+    const int* d_bodies = nullptr; const float* unused = nullptr;
+    PHX_TRY(stage_batch(bodies, nullptr, count, 0, &d_bodies, &unused));
+    PHX_TRY(gathered_.reserve((size_t)count));
+    hipLaunchKernelGGL(k_gather_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, resident(), (const phx_rigid_body*)d_bodies_.p, d_bodies, count, gathered_.p);
+    PHX_HIP(hipGetLastError());
+    PHX_TRY(rb_.add(out, gathered_.p, (size_t)count * sizeof(phx_rigid_body), stream_));
+    return rb_.wait(stream_);
+}
+
+int World::get_poses(float* out, int cap)
+{
+    const int n = nb();
+    if (cap < n) { set_error("phx_world_get_poses: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    if (bodies_dirty_ || !d_bodies_.p) {
+        for (int i = 0; i < n; ++i) {
+            const phx_rigid_body& b = host_bodies_[(size_t)i];
+            out[4 * i] = b.pos.x; out[4 * i + 1] = b.pos.y; out[4 * i + 2] = b.xvector.x; out[4 * i + 3] = b.xvector.y;
+        }
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());
+    PHX_TRY(poses_.reserve((size_t)n));
+    hipLaunchKernelGGL(k_world_poses, dim3(wgrid(n)), dim3(256), 0, stream_, resident(), n, poses_.p);
+    PHX_HIP(hipGetLastError());
+    PHX_TRY(rb_.add(out, poses_.p, (size_t)n * sizeof(float4), stream_));
+    return rb_.wait(stream_);
+}
+
+int World::get_poses_device(void* d_out, int cap)
+{
+    const int n = nb();
+    if (cap < n) { set_error("phx_world_get_poses_device: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) { set_error("phx_world_get_poses_device: the output must be a 16-byte aligned device pointer"); return PHX_ERR_INVALID; }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    hipLaunchKernelGGL(k_world_poses, dim3(wgrid(n)), dim3(256), 0, stream_, resident(), n, static_cast<float4*>(d_out));
+    PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
 
@@ -853,6 +1029,33 @@ int phx_world_get_bodies(phx_world* w, phx_rigid_body* out, int32_t cap) { PHX_R
 int phx_world_get_manifolds(phx_world* w, phx_manifold* out, int32_t cap) { PHX_REQUIRE(w && out, "null handle / buffer"); return w->impl.download_manifolds(out, cap); }
 int phx_world_get_contact_points(phx_world* w, phx_contact_point* out, int32_t cap) { PHX_REQUIRE(w && out, "null handle / buffer"); return w->impl.download_contact_points(out, cap); }
 int phx_world_get_joints(phx_world* w, phx_contact_joint* out, int32_t cap) { PHX_REQUIRE(w && out, "null handle / buffer"); return w->impl.download_joints(out, cap); }
+
+int phx_world_add_accelerations(phx_world* w, const int32_t* bodies, const float* accel, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.edit(phx::World::EDIT_ACCELERATIONS, bodies, accel, count);
+}
+
+int phx_world_set_velocities(phx_world* w, const int32_t* bodies, const float* vel, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.edit(phx::World::EDIT_VELOCITIES, bodies, vel, count);
+}
+
+int phx_world_set_poses(phx_world* w, const int32_t* bodies, const float* pose, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.edit(phx::World::EDIT_POSES, bodies, pose, count);
+}
+
+int phx_world_get_body_states(phx_world* w, const int32_t* bodies, int32_t count, phx_rigid_body* out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.get_body_states(bodies, count, out);
+}
+
+int phx_world_get_poses(phx_world* w, float* out, int32_t cap) { PHX_REQUIRE(w && out, "null handle / buffer"); return w->impl.get_poses(out, cap); }
+int phx_world_get_poses_device(phx_world* w, void* d_out, int32_t cap) { PHX_REQUIRE(w, "null handle"); return w->impl.get_poses_device(d_out, cap); }
 
 int phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,
                         const phx_contact_point* contact_points, int32_t contact_point_count, const phx_contact_joint* joints, int32_t joint_count)

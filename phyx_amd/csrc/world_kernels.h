@@ -34,18 +34,86 @@ static __global__ void __launch_bounds__(256) k_bodies_to_world(const phx_rigid_
 }
 
 // everything a step changes goes back into the records (inverse masses, size, index, the vestigial fields and the accelerations —
-// zero after every IntegrateVelocity, ref: World.cpp:49-52 — are what the upload left there)
+// zero after every IntegrateVelocity, ref: World.cpp:49-52, or what phx_world_add_accelerations left pending — are what the upload
+// left there): body i's record `b` from the resident arrays
+__device__ __forceinline__ void world_record(const WorldBodies& w, int i, phx_rigid_body& b)
+{
+    const float4 v = w.s.vel[i], d = w.s.dvel[i], m = w.s.mpos[i], f = w.frame[i], a = w.aabb[i];
+    b.velocity.x = v.x; b.velocity.y = v.y; b.angular_velocity = v.z;
+    b.displacing_velocity.x = d.x; b.displacing_velocity.y = d.y; b.displacing_angular_velocity = d.z;
+    b.pos.x = m.z; b.pos.y = m.w;
+    b.xvector.x = f.x; b.xvector.y = f.y; b.yvector.x = f.z; b.yvector.y = f.w;
+    b.geom_xvector = b.xvector; b.geom_yvector = b.yvector; b.geom_pos = b.pos;      // UpdateGeom (ref: RigidBody.h:38-42)
+    b.aabb_min.x = a.x; b.aabb_min.y = a.y; b.aabb_max.x = a.z; b.aabb_max.y = a.w;
+}
+
 static __global__ void __launch_bounds__(256) k_world_to_bodies(WorldBodies w, int n, phx_rigid_body* __restrict__ bodies)
 {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) world_record(w, i, bodies[i]);
+}
+
+// the records of the listed bodies only (phx_world_get_body_states): what k_world_to_bodies would leave in records[idx[k]]
+static __global__ void __launch_bounds__(256) k_gather_bodies(WorldBodies w, const phx_rigid_body* __restrict__ records, const int* __restrict__ idx, int count,
+                                                              phx_rigid_body* __restrict__ out)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const int i = idx[k];
+        phx_rigid_body b = records[i];
+        world_record(w, i, b);
+        out[k] = b;
+    }
+}
+
+// {pos.x, pos.y, xVector.x, xVector.y} of every body (phx_world_get_poses / _device)
+static __global__ void __launch_bounds__(256) k_world_poses(WorldBodies w, int n, float4* __restrict__ out)
+{
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float4 v = w.s.vel[i], d = w.s.dvel[i], m = w.s.mpos[i], f = w.frame[i], a = w.aabb[i];
-        phx_rigid_body& b = bodies[i];
-        b.velocity.x = v.x; b.velocity.y = v.y; b.angular_velocity = v.z;
-        b.displacing_velocity.x = d.x; b.displacing_velocity.y = d.y; b.displacing_angular_velocity = d.z;
-        b.pos.x = m.z; b.pos.y = m.w;
-        b.xvector.x = f.x; b.xvector.y = f.y; b.yvector.x = f.z; b.yvector.y = f.w;
-        b.geom_xvector = b.xvector; b.geom_yvector = b.yvector; b.geom_pos = b.pos;      // UpdateGeom (ref: RigidBody.h:38-42)
-        b.aabb_min.x = a.x; b.aabb_min.y = a.y; b.aabb_max.x = a.z; b.aabb_max.y = a.w;
+        const float4 m = w.s.mpos[i], f = w.frame[i];
+        out[i] = make_float4(m.z, m.w, f.x, f.y);
+    }
+}
+
+// ---- edits between steps (phx_world_add_accelerations / set_velocities / set_poses): one lane per listed body.  The host has
+// checked that the indices are in range and distinct, so no two lanes touch the same body.
+// `acceleration += a` (ref: main.cpp:343-346) on the pending accelerations the next IntegrateVelocity consumes (`accel`, zeroed by
+// the first edit after a step), mirrored into the records so that the getters show it until that step (ref: World.cpp:50, 53)
+static __global__ void __launch_bounds__(256) k_add_accelerations(const int* __restrict__ idx, const float* __restrict__ a, int count, float4* __restrict__ accel,
+                                                                  phx_rigid_body* __restrict__ records)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const int i = idx[k];
+        float4 s = accel[i];
+        s.x += a[3 * k]; s.y += a[3 * k + 1]; s.z += a[3 * k + 2];
+        accel[i] = s;
+        records[i].acceleration.x = s.x; records[i].acceleration.y = s.y; records[i].angular_acceleration = s.z;
+    }
+}
+
+// velocity = {v.x, v.y}, angularVelocity = v.z
+static __global__ void __launch_bounds__(256) k_set_velocities(const int* __restrict__ idx, const float* __restrict__ v, int count, float4* __restrict__ vel)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const int i = idx[k];
+        float4 o = vel[i];
+        o.x = v[3 * k]; o.y = v[3 * k + 1]; o.z = v[3 * k + 2];
+        vel[i] = o;
+    }
+}
+
+// coords = {pos, xVector, yVector}, then UpdateGeom (ref: RigidBody.h:38-42, Geom.h:79-85): the frame is given, not an angle
+static __global__ void __launch_bounds__(256) k_set_poses(const int* __restrict__ idx, const float* __restrict__ p, int count, WorldBodies w)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const int i = idx[k];
+        const float* q = p + 6 * k;
+        float4 m = w.s.mpos[i];
+        m.z = q[0]; m.w = q[1];
+        const float2 sz = w.size[i];
+        float4 box;
+        geom_aabb(v2(q[0], q[1]), v2(q[2], q[3]), v2(q[4], q[5]), v2(sz.x, sz.y), box.x, box.y, box.z, box.w);
+        w.s.mpos[i] = m;
+        w.frame[i] = make_float4(q[2], q[3], q[4], q[5]);
+        w.aabb[i] = box;
     }
 }
 
