@@ -1,5 +1,6 @@
-"""ctypes binding of the CPU oracle (oracle/liboracle.so) and of the reference leaf shims
-(oracle/_ref/libphyx_ref_leaf.so).
+"""ctypes binding of the CPU oracle (oracle/liboracle.so), of the reference leaf shims
+(oracle/_ref/libphyx_ref_leaf.so) and of the reference's own World / Collider / Solver
+(oracle/_ref/libphyx_ref_full_{strict,fast}.so, ref_harness/full_harness.cpp).
 
 TEST INFRASTRUCTURE.  May be imported only from tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py.  Nothing under phyx_amd/ imports this module.
@@ -45,7 +46,7 @@ class SolveStats(C.Structure):
 
 
 def build(force=False):
-    """Compile liboracle.so (always possible) and, when /root/reference exists, the leaf shims."""
+    """Compile liboracle.so (always possible) and, when /root/reference exists, the leaf shims and the full reference libraries."""
     so = os.path.join(_HERE, "liboracle.so")
     src_newer = (not os.path.exists(so)) or any(
         os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(so) for f in ("phx_oracle.c", "phx_oracle.h"))
@@ -56,10 +57,17 @@ def build(force=False):
     ref_so = os.path.join(_HERE, "_ref", "libphyx_ref_leaf.so")
     if os.path.isdir("/root/reference/src") and (force or not os.path.exists(ref_so)):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
+    full = [os.path.join(_HERE, "_ref", "libphyx_ref_full_%s.so" % k) for k in REF_KINDS]
+    if os.path.isdir("/root/reference/src") and (force or not all(os.path.exists(f) for f in full)):
+        subprocess.check_call(["make", "-C", _HERE, "ref_full"], stdout=subprocess.DEVNULL)
 
+
+REF_KINDS = ("strict", "fast")
+PAIRS_SERIAL, PAIRS_PARALLEL = 0, 1
 
 _lib = None
 _ref = None
+_ref_full = {}
 
 
 def _p(arr):
@@ -178,6 +186,143 @@ def ref_lib():
                 getattr(R, name).argtypes = [C.c_int, C.c_float, C.c_float]
         _ref = R
     return _ref
+
+
+def ref_full_path(kind):
+    return os.path.join(_HERE, "_ref", "libphyx_ref_full_%s.so" % kind)
+
+
+def ref_full_lib(kind="strict"):
+    """The reference's own World / Collider / Solver linked with ref_harness/full_harness.cpp (None when the prebuilt library is
+    absent).  kind: 'strict' (the oracle's IEEE flags) or 'fast' (the reference's own flags).  Loading either leaves the process's
+    floating-point environment as it was (oracle/Makefile links them without crtfastmath.o)."""
+    if kind not in _ref_full:
+        path = ref_full_path(kind)
+        if not os.path.exists(path):
+            return None
+        R = C.CDLL(path)
+        R.reff_world_create.restype = C.c_void_p
+        R.reff_world_create.argtypes = [C.c_float]
+        R.reff_world_destroy.restype = None
+        R.reff_world_destroy.argtypes = [C.c_void_p]
+        R.reff_world_add_body.restype = C.c_int
+        R.reff_world_add_body.argtypes = [C.c_void_p] + [C.c_float] * 5 + [C.c_int]
+        R.reff_world_pin_body.restype = None
+        R.reff_world_pin_body.argtypes = [C.c_void_p, C.c_int]
+        R.reff_world_update.restype = None
+        R.reff_world_update.argtypes = [C.c_void_p, C.c_float] + [C.c_int] * 4
+        R.reff_world_update_pairs.restype = None
+        R.reff_world_update_pairs.argtypes = [C.c_void_p, C.c_float] + [C.c_int] * 5
+        R.reff_world_pre_solve.restype = None
+        R.reff_world_pre_solve.argtypes = [C.c_void_p, C.c_float]
+        R.reff_world_pre_solve_pairs.restype = None
+        R.reff_world_pre_solve_pairs.argtypes = [C.c_void_p, C.c_float, C.c_int]
+        R.reff_world_solve.restype = None
+        R.reff_world_solve.argtypes = [C.c_void_p] + [C.c_int] * 4
+        R.reff_world_integrate_position.restype = None
+        R.reff_world_integrate_position.argtypes = [C.c_void_p, C.c_float]
+        R.reff_collider_update.restype = C.c_int
+        R.reff_collider_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        for name in ("bodies", "manifolds", "contact_points", "joints", "joint_index", "island_offset", "island_size",
+                     "broadphase_entries", "broadphase_sorted", "solve_bodies_impulse"):
+            f = getattr(R, "reff_" + name)
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        R.reff_joint_packed.restype = C.c_int
+        R.reff_joint_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        R.reff_island_stats.restype = None
+        R.reff_island_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _ref_full[kind] = R
+    return _ref_full[kind]
+
+
+class RefWorld:
+    """The reference's World (ref: World.h) behind full_harness.cpp, 0 workers.  `pairs` picks the pair path of every step:
+    PAIRS_PARALLEL (UpdatePairsParallel, the path of the reference's threaded configuration) or PAIRS_SERIAL (UpdatePairsSerial,
+    the path World::Update takes with 0 workers; DESIGN.md §9 item 2)."""
+
+    def __init__(self, kind="strict", gravity=-200.0, pairs=PAIRS_PARALLEL):
+        self.L = ref_full_lib(kind)
+        if self.L is None:
+            raise FileNotFoundError(ref_full_path(kind))
+        self.h = C.c_void_p(self.L.reff_world_create(gravity))
+        self.pairs = pairs
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.reff_world_destroy(self.h)
+            self.h = None
+
+    def add_scene(self, scene):
+        pinned = scene.get("pinned")
+        for k in range(len(scene["px"])):
+            self.L.reff_world_add_body(self.h, float(scene["px"][k]), float(scene["py"][k]), float(scene["angle"][k]),
+                                       float(scene["sx"][k]), float(scene["sy"][k]), int(bool(scene["static"][k])))
+        if pinned is not None and np.any(pinned):
+            for i in np.flatnonzero(np.asarray(pinned, dtype=bool)):
+                self.L.reff_world_pin_body(self.h, int(i))
+
+    def _get(self, name, dtype, *args):
+        fn = getattr(self.L, "reff_" + name)
+        n = fn(self.h, *args, None, 0)
+        out = np.zeros(max(n, 1), dtype=dtype)
+        fn(self.h, *args, _p(out), n)
+        return out[:n]
+
+    def bodies(self):
+        return self._get("bodies", body_dtype)
+
+    def manifolds(self):
+        return self._get("manifolds", manifold_dtype)
+
+    def contact_points(self):
+        return self._get("contact_points", contact_point_dtype)
+
+    def joints(self):
+        return self._get("joints", joint_dtype)
+
+    def joint_index(self):
+        return self._get("joint_index", np.int32)
+
+    def island_offset(self):
+        return self._get("island_offset", np.int32)
+
+    def island_size(self):
+        return self._get("island_size", np.int32)
+
+    def broadphase_entries(self):
+        return self._get("broadphase_entries", bp_entry_dtype)
+
+    def broadphase_sorted(self):
+        return self._get("broadphase_sorted", sort_entry_dtype)
+
+    def joint_packed(self, n, words=35):
+        return np.frombuffer(self._get("joint_packed", np.dtype(("u1", words * 4 * n)), C.c_int(n)).tobytes(), dtype=np.float32)
+
+    def island_stats(self):
+        cnt, mx = C.c_int(0), C.c_int(0)
+        self.L.reff_island_stats(self.h, C.byref(cnt), C.byref(mx))
+        return cnt.value, mx.value
+
+    def update(self, dt=1.0 / 60.0, solve_mode=SOLVE_SCALAR, island_mode=ISLAND_SINGLE, contact_iters=15, penetration_iters=15):
+        self.L.reff_world_update_pairs(self.h, dt, solve_mode, island_mode, contact_iters, penetration_iters, self.pairs)
+
+    def pre_solve(self, dt=1.0 / 60.0):
+        self.L.reff_world_pre_solve_pairs(self.h, dt, self.pairs)
+
+    def solve(self, solve_mode=SOLVE_SCALAR, island_mode=ISLAND_SINGLE, contact_iters=15, penetration_iters=15):
+        self.L.reff_world_solve(self.h, solve_mode, island_mode, contact_iters, penetration_iters)
+
+    def integrate_position(self, dt=1.0 / 60.0):
+        self.L.reff_world_integrate_position(self.h, dt)
+
+    def collider_update(self, bodies):
+        """UpdateBroadphase + this world's pair path over `bodies` (a body_dtype array) in the harness's own Collider, whose pair
+        set persists.  Returns the new pairs in emission order, (n, 2) uint32."""
+        b = np.ascontiguousarray(bodies, dtype=body_dtype)
+        n = self.L.reff_collider_update(self.h, _p(b), len(b), self.pairs)
+        m = self.manifolds()[-n:] if n else np.zeros(0, manifold_dtype)
+        return np.stack([m["body1"], m["body2"]], axis=1).astype(np.uint32)
 
 
 ARITH_SOURCE, ARITH_FUSED = 0, 1

@@ -14,13 +14,12 @@
  *             of ProjectPointToLine, AABB2::Intersects, the scalar / SSE2 / AVX2 flipsign, max and abs wrappers the
  *             solve loops use, DenseHashSet insert/contains (set
  *             semantics on tombstone-free sequences).
- *   UNPINNED ("parity unpinned"): everything that lives in the reference's .cpp files —
- *             Solver.cpp, Collider.cpp, World.cpp.  Those translation units include
- *             "microprofile.h", an un-vendored submodule (/root/reference/.gitmodules:1-3,
- *             src/microprofile/ is empty), so they cannot be built here without writing a
- *             stand-in header, which the build rules forbid.  The reference ships no tests,
- *             fixtures or golden vectors either.  For those functions this
- *             file is a line-cited restatement only.
+ *   PINNED   (whole step, against the reference's own Solver.cpp, Collider.cpp, World.cpp built as
+ *             they lie by oracle/Makefile `ref_full`, with our no-op header for the profiler
+ *             submodule the reference does not ship): bit for bit against the strict build, stage by
+ *             stage and step by step in every solve / island mode (tests/test_reference_goldens.py,
+ *             tests/test_reference_lockstep.py).  The reference runs its parallel pair
+ *             path; its serial path's duplicate pairs are a stated deviation.
  *
  * Arithmetic: strict IEEE-754 binary32, one rounding per operation, evaluated in the order the
  * reference source writes it (built with -ffp-contract=off, no fast-math).  The reference's own

@@ -1,6 +1,6 @@
 """Soft pins: what BASELINE.md §2 records of the COMPILED reference (the survey's probe runs, made when the reference could be
-built with a stub profiler header) and the oracle reproduces today.  The reference's Solver.cpp / Collider.cpp / World.cpp cannot
-be compiled in this image (un-vendored microprofile.h), so these are not golden vectors and pin nothing formally:
+built with a stub profiler header) and the oracle reproduces today.  They were written before the reference's Solver.cpp / Collider.cpp /
+World.cpp could be built here (tests/test_reference_*.py pin those now); they are not golden vectors and pin nothing formally:
 they are bands around recorded behaviour of the real thing, and they fail if the restatement drifts away from it.
 
   * scalar vs AVX2 grouping on the 1k-box stack (cfg 1 scene): max |delta pos| after step 1 / 10 / 60 = 2.7e-2 / 0.50 / 81
