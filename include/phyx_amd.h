@@ -424,6 +424,33 @@ int  phx_world_get_body_states(phx_world* w, const int32_t* bodies, int32_t coun
 int  phx_world_get_poses(phx_world* w, float* out, int32_t cap);
 /* the same into caller-owned device memory (16-byte aligned), queued on phx_world_stream(w): no host wait, nothing over PCIe */
 int  phx_world_get_poses_device(phx_world* w, void* d_out, int32_t cap);
+/* REMOVAL BETWEEN STEPS.  Removing the set R of bodies leaves exactly the world phx_world_set_state would make of the filtered state
+ * filter(bodies, manifolds, contact points, joints, R), where
+ *   - bodies: the bodies not in R, in their old order; new[i] = the new index of old body i, or -1 if it was removed.  Each kept record
+ *     is copied unchanged except `index`, which becomes its new position (ref: World.cpp:14); pending accelerations move with it;
+ *   - manifolds: kept iff both bodies are kept, in their old order, body1 / body2 remapped through new[] (new[] is monotonic, so
+ *     body1 < body2 still holds wherever it held), point_index = 2 * the manifold's new index;
+ *   - contact points: the two slots of each kept manifold move with it; a live slot's (k < point_count) solver_index becomes its
+ *     joint's new index (-1 if that joint goes; an index outside [0, joint count) stays as it is); dead slots are copied byte for byte;
+ *   - joints: kept iff their manifold is kept (equivalently: both of their bodies are), in their old order, body1 / body2 remapped,
+ *     contact_point_index = 2 * (the manifold's new index) + old % 2, warm-start impulses unchanged;
+ *   - the broadphase's pair set becomes the kept manifolds' remapped pairs, and everything set_state resets is reset: the cached
+ *     solver schedule is rebuilt at the next step.
+ * Rules as for the edits above: between steps only (PHX_ERR_STATE inside pre_solve .. finish_step or step_begin .. step_end); a sharded
+ * or communicator-attached world gets PHX_ERR_STATE, as set_state does; the arguments are checked completely before anything is
+ * queued (every index in [0, body count), none twice; PHX_ERR_INVALID otherwise, the world unchanged).  Removing no body is a true
+ * no-op (the cached schedule stays valid), removing every body is allowed.  Host-staged bodies (before the first step, after add_body /
+ * set_body_static / set_body_inverse_mass) are uploaded first, as the next step would upload them.  The work runs on the world's
+ * stream with one host round trip for the new counts; nothing of the state crosses PCIe but the remap, when asked for.
+ * Every index the caller holds shifts: body i is now remap[i].  An ownership-sharded (slab) world's indices are local to its rank;
+ * phyx_amd/dist.py SlabWorld's scene indices are not kept in step with a removal.
+ * remap (may be NULL): room for the old body count; receives new[] (new index or -1). */
+int  phx_world_remove_bodies(phx_world* w, const int32_t* bodies, int32_t count, int32_t* remap);
+/* Remove every body whose AABB does not overlap the closed box {min.x, min.y, max.x, max.y} (the despawn rule: a kill plane, a play
+ * area).  The test runs on the device over the resident AABBs: no positions cross PCIe.  Static bodies are not exempt.  The box must be
+ * finite with min <= max (PHX_ERR_INVALID otherwise).  *removed (may be NULL) = how many went; remap as above.  When every body is
+ * inside, nothing changes. */
+int  phx_world_remove_outside(phx_world* w, const float box[4], int32_t* removed, int32_t* remap);
 /* Restore a world from what the four getters above returned (checkpoint / resume; the hand-over of bodies between the ranks of an
  * ownership-sharded world): bodies, the contact cache — manifolds with their two contact-point slots each, ref: Collider.h:57-58 —
  * and the joints with their warm-start impulses (ref: World.h:33).  The broadphase's pair set is rebuilt from the manifolds'

@@ -711,6 +711,33 @@ class World:
         n = self.counts()[0]
         check(self.L.phx_world_get_poses_device(self.h, C.c_void_p(int(ptr)), n if cap is None else int(cap)))
 
+    # ---- removal between steps (include/phyx_amd.h: phx_world_remove_bodies / phx_world_remove_outside) ----
+    def remove_bodies(self, bodies):
+        """Remove the listed bodies (each at most once) and compact the world on the device; exactly what set_state of the filtered
+        state() would make (tests/removal_spec.py).  Returns remap: int32 of the old body count, remap[i] = body i's new index or -1.
+        Indices held elsewhere shift (the drag's body 1 becomes remap[1])."""
+        if isinstance(bodies, (list, tuple)) and not len(bodies):
+            bodies = np.zeros(0, dtype=np.int32)                    # ([] reads as float64)
+        idx = self._indices(bodies, "remove_bodies")
+        remap = np.zeros(self.counts()[0], dtype=np.int32)
+        check(self.L.phx_world_remove_bodies(self.h, _ptr(idx), len(idx), _ptr(remap)))
+        return remap
+
+    def remove_outside(self, box):
+        """Remove every body whose AABB does not overlap the closed box (min.x, min.y, max.x, max.y), tested on the device.
+        Returns (removed, remap) as remove_bodies."""
+        b = np.asarray(box)
+        if b.shape != (4,) or b.dtype.kind not in "iuf":
+            raise TypeError("remove_outside: box must be 4 numbers (min.x, min.y, max.x, max.y), got %s of shape %s" % (b.dtype, b.shape))
+        with np.errstate(over="ignore"):
+            b = np.ascontiguousarray(b, dtype=np.float32)      # (a box beyond the float range becomes infinite: refused below)
+        if not np.isfinite(b).all() or b[0] > b[2] or b[1] > b[3]:
+            raise ValueError("remove_outside: the box must be finite with min <= max, got %s" % (b.tolist(),))
+        remap = np.zeros(self.counts()[0], dtype=np.int32)
+        removed = C.c_int32(0)
+        check(self.L.phx_world_remove_outside(self.h, _ptr(b), C.byref(removed), _ptr(remap)))
+        return removed.value, remap
+
     def sync(self):
         """Wait for the queued step (Update returns once the step is queued; getters synchronise on their own)."""
         check(self.L.phx_world_synchronize(self.h))

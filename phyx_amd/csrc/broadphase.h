@@ -28,6 +28,7 @@ public:
     int erase_pairs(const uint32_t* pairs, int count);
     int erase_pairs_device(const uint2* d_pairs, int count);      // pairs already in HBM
     int reset_pairs(const uint2* pairs, int count);               // the pair set becomes exactly these (host) pairs: a world restored from a saved state
+    int reset_pairs_device(const uint2* d_pairs, int count);      // ... these pairs in HBM (queued: no host wait)
     const uint2* new_pairs_device() const { return new_pairs_.p; }   // pairs emitted by the last update, in HBM
     int get_stats(phx_broadphase_stats* out);
     int new_pair_count() const { return last_new_; }

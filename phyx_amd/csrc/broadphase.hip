@@ -751,15 +751,26 @@ int DeviceBroadphase::reset_pairs(const uint2* pairs, int count)
 {
     PHX_TRY(use_device(device_));
     PHX_REQUIRE(count >= 0 && (count == 0 || pairs), "bad pair list");
+    if (count) {
+        PHX_TRY(scratch_pairs_.reserve((size_t)count));
+        PHX_HIP(hipMemcpyAsync(scratch_pairs_.p, pairs, (size_t)count * sizeof(uint2), hipMemcpyHostToDevice, stream_));
+    }
+    PHX_TRY(reset_pairs_device(scratch_pairs_.p, count));
+    PHX_HIP(hipStreamSynchronize(stream_));          // (`pairs` is the caller's)
+    return PHX_OK;
+}
+
+// the same from pairs already in HBM (a World's removal of bodies: the kept manifolds' pairs), queued on the stream
+int DeviceBroadphase::reset_pairs_device(const uint2* d_pairs, int count)
+{
+    PHX_TRY(use_device(device_));
+    PHX_REQUIRE(count >= 0 && (count == 0 || d_pairs), "bad pair list");
     PHX_TRY(clear());
     have_update_ = false;
     if (!count) return PHX_OK;
     PHX_TRY(resize_table(4u * (unsigned)count + 1024u));
-    PHX_TRY(scratch_pairs_.reserve((size_t)count));
-    PHX_HIP(hipMemcpyAsync(scratch_pairs_.p, pairs, (size_t)count * sizeof(uint2), hipMemcpyHostToDevice, stream_));
-    hipLaunchKernelGGL(k_ps_insert, dim3(grid_for(count)), dim3(256), 0, stream_, table_.p, table_cap_ - 1, (const uint2*)scratch_pairs_.p, count, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(k_ps_insert, dim3(grid_for(count)), dim3(256), 0, stream_, table_.p, table_cap_ - 1, d_pairs, count, (unsigned long long*)nullptr);
     PHX_HIP(hipGetLastError());
-    PHX_HIP(hipStreamSynchronize(stream_));          // (`pairs` is the caller's)
     set_size_ = count;
     stats_.set_size = count;
     return PHX_OK;

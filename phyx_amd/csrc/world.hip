@@ -20,6 +20,7 @@
 namespace phx {
 
 static inline int wgrid(int n) { return std::max(1, std::min(div_up(n, 256), 4096)); }
+static inline int rgrid(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }      // the removal's streaming passes (grid-stride beyond 2048 workgroups)
 constexpr int PRELABEL_EARLY_MANIFOLDS = 400000;      // worlds from this size on queue the side stream's share of the schedule rebuild before the joint match (refresh_contact_joints)
 
 class World {
@@ -56,6 +57,9 @@ public:
     int get_body_states(const int* bodies, int count, phx_rigid_body* out);
     int get_poses(float* out, int cap);
     int get_poses_device(void* d_out, int cap);
+    // removal between steps (phx_world_remove_bodies / phx_world_remove_outside): the listed bodies, or (`box` non-null) every body
+    // whose AABB does not overlap the box
+    int remove(const char* what, const int* bodies, int count, const float* box, int* removed, int* remap);
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -85,6 +89,7 @@ private:
     int solve(const phx_config& cfg, bool settle);
     int solve_and_integrate(float dt, const phx_config& cfg);
     int scratch_for(int n);
+    int forget_step_history();           // the bookkeeping a restored or compacted contact cache starts without
 
     int device_;
     DeviceBroadphase& broadphase_;
@@ -133,6 +138,20 @@ private:
     std::vector<DevBuf<char>> edit_dev_retired_;      // outgrown device batches a pending scatter may still read: freed with the world
     DevBuf<phx_rigid_body> gathered_;
     DevBuf<float4> poses_;
+    // removal: keep flags and the exclusive scans that place the kept bodies / manifolds / joints, the counts ([0] bodies, [1] manifolds,
+    // [2] joints kept, [3] kept records with an acceleration), the remap, the kept pairs; the compaction writes into the spare buffers,
+    // which then change places with the world's own (the old ones are the spares of the next removal)
+    DevBuf<unsigned> rm_keep_, rm_bnew_, rm_mnew_, rm_jnew_, rm_counts_;
+    DevBuf<int> rm_remap_;
+    DevBuf<uint2> rm_pairs_;
+    struct Spare {
+        DevBuf<phx_rigid_body> bodies;
+        DevBuf<float4> vel, dvel, mpos, frame, aabb, accel;
+        DevBuf<float2> size;
+        DevBuf<phx_manifold> manifolds;
+        DevBuf<phx_contact_point> cps;
+        DevBuf<phx_contact_joint> joints;
+    } spare_;
 };
 
 World::~World()
@@ -724,11 +743,18 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     std::vector<uint2> pairs((size_t)nm);
     for (int i = 0; i < nm; ++i) pairs[i] = make_uint2((unsigned)manifolds[i].body1, (unsigned)manifolds[i].body2);
     PHX_TRY(broadphase_.reset_pairs(pairs.data(), nm));
-    // nothing of the old world's bookkeeping survives
+    PHX_TRY(forget_step_history());
+    PHX_HIP(hipStreamSynchronize(stream_));
+    return PHX_OK;
+}
+
+// nothing of the old world's bookkeeping survives: the schedule is rebuilt, no pack or joint match is pending, the velocity step is
+// not fused yet, and the joints' match stamps start again from zero
+int World::forget_step_history()
+{
     joints_changed_ = true; pack_pending_ = false; expect_no_dead_manifolds_ = false; fresh_manifolds_ = 0; manifolds_updated_ = 0; fuse_velocity_ = false; mid_step_ = false;
     if (joint_seen_.p) { PHX_HIP(hipMemsetAsync(joint_seen_.p, 0, joint_seen_.cap * sizeof(unsigned), stream_)); }
     joint_epoch_ = 0;
-    PHX_HIP(hipStreamSynchronize(stream_));
     return PHX_OK;
 }
 
@@ -907,6 +933,85 @@ int World::get_poses_device(void* d_out, int cap)
     return PHX_OK;
 }
 
+// ---- removal between steps ------------------------------------------------------------------------------------------------------
+// Defined as phx_world_set_state of the filtered state (include/phyx_amd.h); computed on the world's stream without the state
+// crossing PCIe: keep flags per body (scattered from the staged list, or the box test on the resident AABBs), three exclusive scans
+// (bodies; manifolds: both bodies kept; joints: their manifold kept), then the compaction kernels, out of place into the spare
+// buffers, grid-strided over the OLD counts — all queued before the one host round trip that brings back the three new counts (and
+// the remap if asked for).  The records are compacted as the truth and the resident arrays made from them by the upload's own
+// conversion, so the result is set_state's by construction.
+int World::remove(const char* what, const int* bodies, int count, const float* box, int* removed, int* remap)
+{
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world cannot remove bodies", what); return PHX_ERR_STATE; }
+    if (box) {
+        if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+        for (int k = 0; k < 4; ++k)
+            if (!std::isfinite(box[k])) { set_error("%s: the box is not finite", what); return PHX_ERR_INVALID; }
+        if (!(box[0] <= box[2] && box[1] <= box[3])) { set_error("%s: the box's min exceeds its max", what); return PHX_ERR_INVALID; }
+    } else PHX_TRY(check_batch(what, bodies, bodies, count, true));        // (no values: the indices stand in for them)
+    const int n = nb();
+    if (removed) *removed = 0;
+    if ((!box && !count) || !n) {                                           // a true no-op: the cached schedule stays valid
+        if (remap) for (int i = 0; i < n; ++i) remap[i] = i;
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    const bool pending_accel = accel_pending_;
+    PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n)); PHX_TRY(rm_counts_.reserve(4));
+    PHX_TRY(rm_mnew_.reserve((size_t)nm + 2)); PHX_TRY(rm_jnew_.reserve((size_t)nj + 2)); PHX_TRY(rm_pairs_.reserve(std::max<size_t>(nm, 1)));
+    PHX_TRY(spare_.bodies.reserve((size_t)n)); PHX_TRY(spare_.vel.reserve((size_t)n)); PHX_TRY(spare_.dvel.reserve((size_t)n)); PHX_TRY(spare_.mpos.reserve((size_t)n));
+    PHX_TRY(spare_.frame.reserve((size_t)n)); PHX_TRY(spare_.aabb.reserve((size_t)n)); PHX_TRY(spare_.size.reserve((size_t)n));
+    if (pending_accel) PHX_TRY(spare_.accel.reserve((size_t)n));
+    PHX_TRY(spare_.manifolds.reserve(std::max<size_t>(nm, 1))); PHX_TRY(spare_.cps.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(spare_.joints.reserve(std::max<size_t>(nj, 1)));
+    // 1. keep flags per body
+    if (box) {
+        hipLaunchKernelGGL(k_keep_inside, dim3(rgrid(n)), dim3(256), 0, stream_, (const float4*)aabb_.p, n, make_float4(box[0], box[1], box[2], box[3]), rm_keep_.p);
+    } else {
+        const int* d_bodies = nullptr; const float* unused = nullptr;
+        PHX_TRY(stage_batch(bodies, nullptr, count, 0, &d_bodies, &unused));
+        PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rm_keep_.p), 1, (size_t)n, stream_));
+        hipLaunchKernelGGL(k_remove_listed, dim3(rgrid(count)), dim3(256), 0, stream_, d_bodies, count, rm_keep_.p);
+    }
+    PHX_HIP(hipGetLastError());
+    // 2. where the kept bodies, manifolds and joints go (a zero count writes a zero total)
+    PHX_TRY(device_exclusive_scan_of(BodyKeepLoad{rm_keep_.p}, rm_bnew_.p, n, rm_counts_.p, scan_tiles_, stream_));
+    PHX_TRY(device_exclusive_scan_of(ManifoldKeepLoad{d_manifolds_.p, rm_keep_.p}, rm_mnew_.p, nm, rm_counts_.p + 1, scan_tiles_, stream_));
+    PHX_TRY(device_exclusive_scan_of(JointKeepLoad{d_joints_.p, d_manifolds_.p, rm_keep_.p}, rm_jnew_.p, nj, rm_counts_.p + 2, scan_tiles_, stream_));
+    PHX_HIP(hipMemsetAsync(rm_counts_.p + 3, 0, sizeof(unsigned), stream_));
+    // 3. compaction into the spares
+    const WorldBodies out{BodyView{spare_.vel.p, spare_.dvel.p, spare_.mpos.p}, spare_.frame.p, spare_.aabb.p, spare_.size.p};
+    hipLaunchKernelGGL(k_remove_bodies, dim3(rgrid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)d_bodies_.p, resident(), n, records_stale_ ? 1 : 0,
+                       (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, spare_.bodies.p, out, pending_accel ? spare_.accel.p : (float4*)nullptr,
+                       rm_remap_.p, rm_counts_.p + 3);
+    if (nm) hipLaunchKernelGGL(k_remove_manifolds, dim3(rgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, (const phx_contact_point*)d_cps_.p, nm,
+                               (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p,
+                               (const unsigned*)(rm_counts_.p + 2), nj, spare_.manifolds.p, spare_.cps.p, rm_pairs_.p);
+    if (nj) hipLaunchKernelGGL(k_remove_joints, dim3(rgrid(nj)), dim3(256), 0, stream_, (const phx_contact_joint*)d_joints_.p, nj, (const phx_manifold*)d_manifolds_.p,
+                               (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, spare_.joints.p);
+    PHX_HIP(hipGetLastError());
+    // 4. the one round trip
+    unsigned got[4] = {0, 0, 0, 0};
+    PHX_TRY(rb_.add(got, rm_counts_.p, sizeof got, stream_));
+    if (remap) PHX_TRY(rb_.add(remap, rm_remap_.p, (size_t)n * sizeof(int), stream_));
+    PHX_TRY(rb_.wait(stream_));
+    const int kept = (int)got[0];
+    if (removed) *removed = n - kept;
+    if (kept == n) return PHX_OK;                                           // every body is inside the box: nothing changes (the spares are dropped)
+    // 5. the compacted arrays become the world's
+    std::swap(d_bodies_, spare_.bodies);
+    std::swap(vel_, spare_.vel); std::swap(dvel_, spare_.dvel); std::swap(mpos_, spare_.mpos); std::swap(frame_, spare_.frame); std::swap(aabb_, spare_.aabb); std::swap(size_, spare_.size);
+    if (pending_accel) std::swap(accel_, spare_.accel);
+    std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
+    host_bodies_.resize((size_t)kept);                                      // (only its size counts while the device copy is the world)
+    records_stale_ = false;
+    accel_pending_ = pending_accel && got[3] != 0;                          // (what the upload of the kept records would find)
+    nm = (int)got[1]; nj = (int)got[2];
+    PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
+    return forget_step_history();
+}
+
 } // namespace phx
 
 // ---- C ABI ------------------------------------------------------------------------------------------------
@@ -1056,6 +1161,19 @@ int phx_world_get_body_states(phx_world* w, const int32_t* bodies, int32_t count
 
 int phx_world_get_poses(phx_world* w, float* out, int32_t cap) { PHX_REQUIRE(w && out, "null handle / buffer"); return w->impl.get_poses(out, cap); }
 int phx_world_get_poses_device(phx_world* w, void* d_out, int32_t cap) { PHX_REQUIRE(w, "null handle"); return w->impl.get_poses_device(d_out, cap); }
+
+int phx_world_remove_bodies(phx_world* w, const int32_t* bodies, int32_t count, int32_t* remap)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.remove("phx_world_remove_bodies", bodies, count, nullptr, nullptr, remap);
+}
+
+int phx_world_remove_outside(phx_world* w, const float box[4], int32_t* removed, int32_t* remap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(box, "phx_world_remove_outside: null box");
+    return w->impl.remove("phx_world_remove_outside", nullptr, 0, box, removed, remap);
+}
 
 int phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,
                         const phx_contact_point* contact_points, int32_t contact_point_count, const phx_contact_joint* joints, int32_t joint_count)

@@ -20,17 +20,19 @@
 namespace phx {
 
 // ---- 128-byte records <-> the World's resident arrays (body_view.h): upload after construction, download for the getters -------
+__device__ __forceinline__ void record_to_world(const phx_rigid_body& b, const WorldBodies& w, int i)
+{
+    w.s.vel[i] = make_float4(b.velocity.x, b.velocity.y, b.angular_velocity, 0.f);
+    w.s.dvel[i] = make_float4(b.displacing_velocity.x, b.displacing_velocity.y, b.displacing_angular_velocity, 0.f);
+    w.s.mpos[i] = make_float4(b.inv_mass, b.inv_inertia, b.pos.x, b.pos.y);
+    w.frame[i] = make_float4(b.xvector.x, b.xvector.y, b.yvector.x, b.yvector.y);
+    w.aabb[i] = make_float4(b.aabb_min.x, b.aabb_min.y, b.aabb_max.x, b.aabb_max.y);
+    w.size[i] = make_float2(b.geom_size.x, b.geom_size.y);
+}
+
 static __global__ void __launch_bounds__(256) k_bodies_to_world(const phx_rigid_body* __restrict__ bodies, int n, WorldBodies w)
 {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const phx_rigid_body& b = bodies[i];
-        w.s.vel[i] = make_float4(b.velocity.x, b.velocity.y, b.angular_velocity, 0.f);
-        w.s.dvel[i] = make_float4(b.displacing_velocity.x, b.displacing_velocity.y, b.displacing_angular_velocity, 0.f);
-        w.s.mpos[i] = make_float4(b.inv_mass, b.inv_inertia, b.pos.x, b.pos.y);
-        w.frame[i] = make_float4(b.xvector.x, b.xvector.y, b.yvector.x, b.yvector.y);
-        w.aabb[i] = make_float4(b.aabb_min.x, b.aabb_min.y, b.aabb_max.x, b.aabb_max.y);
-        w.size[i] = make_float2(b.geom_size.x, b.geom_size.y);
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) record_to_world(bodies[i], w, i);
 }
 
 // everything a step changes goes back into the records (inverse masses, size, index, the vestigial fields and the accelerations —
@@ -370,6 +372,148 @@ static __global__ void __launch_bounds__(256) k_joints_fill(phx_contact_joint* _
         const phx_contact_joint moved = joints[mover_pos[h]];
         joints[i] = moved;
         cps[moved.contact_point_index].solver_index = i;
+    }
+}
+
+// ---- removal of bodies between steps (phx_world_remove_bodies / remove_outside) -----------------------------------------------
+// The result is defined as what phx_world_set_state would make of the filtered state (include/phyx_amd.h): kept bodies, manifolds
+// and joints stay in their old order, so every new position is an exclusive scan of keep flags.  keep[] holds one word per body;
+// the manifold and joint flags are the LOADERS of their scans (device_scan.h), and the compaction kernels recompute them.  Every
+// kernel is a grid-stride pass over the OLD counts, writing out of place into the world's spare buffers: nothing here needs a
+// count from the host.
+
+// keep[i] = 0 for the listed bodies (keep[] was filled with 1; the host has checked the indices: in range, each at most once)
+static __global__ void __launch_bounds__(256) k_remove_listed(const int* __restrict__ idx, int count, unsigned* __restrict__ keep)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) keep[idx[k]] = 0u;
+}
+
+// keep[i] = body i's AABB overlaps the closed box {min.x, min.y, max.x, max.y} (a NaN AABB overlaps nothing)
+static __global__ void __launch_bounds__(256) k_keep_inside(const float4* __restrict__ aabb, int n, float4 box, unsigned* __restrict__ keep)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 a = aabb[i];
+        keep[i] = (a.x <= box.z && a.z >= box.x && a.y <= box.w && a.w >= box.y) ? 1u : 0u;
+    }
+}
+
+__device__ __forceinline__ bool manifold_kept(const phx_manifold& m, const unsigned* __restrict__ keep) { return (keep[m.body1] & keep[m.body2]) != 0u; }
+
+// loaders of the three scans: a body is kept by its flag, a manifold iff both of its bodies are, a joint iff its manifold is
+struct BodyKeepLoad {
+    static constexpr bool in_place = false;
+    const unsigned* keep;
+    __device__ unsigned operator()(int i) const { return keep[i]; }
+    __device__ bool load4(int base, uint4& out) const
+    {
+        if (reinterpret_cast<uintptr_t>(keep) & 15u) return false;
+        out = *reinterpret_cast<const uint4*>(keep + base);
+        return true;
+    }
+};
+struct ManifoldKeepLoad {
+    static constexpr bool in_place = false;
+    const phx_manifold* manifolds; const unsigned* keep;
+    __device__ unsigned operator()(int i) const { return manifold_kept(manifolds[i], keep) ? 1u : 0u; }
+};
+struct JointKeepLoad {
+    static constexpr bool in_place = false;
+    const phx_contact_joint* joints; const phx_manifold* manifolds; const unsigned* keep;
+    __device__ unsigned operator()(int j) const { return manifold_kept(manifolds[joints[j].contact_point_index >> 1], keep) ? 1u : 0u; }
+};
+
+// element i's flag from the exclusive scan of the flags (`total`: their sum)
+__device__ __forceinline__ bool scanned_flag(const unsigned* __restrict__ before, const unsigned* __restrict__ total, int i, int n)
+{
+    return ((i + 1 < n) ? before[i + 1] : *total) != before[i];
+}
+
+// Bodies: kept record i goes to out[to], to = bnew[i], as one 128-byte line, with `index` = to; the resident arrays (and the pending
+// accelerations) at `to` are made from it by the upload's own conversion (record_to_world), as phx_world_set_state would make them.
+// `refresh` (the records are stale): the record is first brought up to date from the resident arrays (world_record), as the getter
+// would.  remap[i] = to, or -1.  accel_nonzero counts the kept records with an acceleration (the upload's test, world.hip).
+static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_body* __restrict__ records, WorldBodies w, int n, int refresh,
+                                                              const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
+                                                              phx_rigid_body* __restrict__ out_records, WorldBodies out, float4* __restrict__ out_accel,
+                                                              int* __restrict__ remap, unsigned* __restrict__ accel_nonzero)
+{
+    static_assert(sizeof(phx_rigid_body) == 8 * sizeof(float4), "a record is one 128-byte line");
+    unsigned nonzero = 0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int to = keep[i] ? (int)bnew[i] : -1;
+        remap[i] = to;
+        if (to < 0) continue;
+        const float4* src = reinterpret_cast<const float4*>(records) + 8 * (size_t)i;
+        float4 line[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) line[k] = src[k];
+        phx_rigid_body b;
+        __builtin_memcpy(&b, line, sizeof b);
+        if (refresh) world_record(w, i, b);
+        b.index = (uint32_t)to;
+        __builtin_memcpy(line, &b, sizeof b);
+        float4* dst = reinterpret_cast<float4*>(out_records) + 8 * (size_t)to;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) dst[k] = line[k];
+        record_to_world(b, out, to);
+        if (out_accel) {
+            out_accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
+            if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) nonzero += __shfl_down(nonzero, off);
+    if ((threadIdx.x & 63) == 0 && nonzero) atomicAdd(accel_nonzero, nonzero);
+}
+
+// Manifolds with their two contact-point slots (32 bytes each, moved as two 16-byte halves): kept manifold i goes to to = mnew[i]
+// with its bodies remapped and point_index = 2 * to; a live slot's solver_index follows its joint (-1 if the joint goes), a dead
+// slot is copied as it is.  pairs[to] = the remapped body pair (the new broadphase pair set).
+static __global__ void __launch_bounds__(256) k_remove_manifolds(const phx_manifold* __restrict__ manifolds, const phx_contact_point* __restrict__ cps, int nm,
+                                                                 const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
+                                                                 const unsigned* __restrict__ mnew, const unsigned* __restrict__ jnew,
+                                                                 const unsigned* __restrict__ jtotal, int nj, phx_manifold* __restrict__ out_manifolds,
+                                                                 phx_contact_point* __restrict__ out_cps, uint2* __restrict__ pairs)
+{
+    static_assert(sizeof(phx_contact_point) == 2 * sizeof(float4), "a contact point is two 16-byte halves");
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nm; i += gridDim.x * blockDim.x) {
+        const phx_manifold m = manifolds[i];
+        if (!manifold_kept(m, keep)) continue;
+        const int to = (int)mnew[i];
+        phx_manifold o;
+        o.body1 = (int)bnew[m.body1]; o.body2 = (int)bnew[m.body2]; o.point_count = m.point_count; o.point_index = 2 * to;
+        out_manifolds[to] = o;
+        pairs[to] = make_uint2((unsigned)o.body1, (unsigned)o.body2);
+        const float4* src = reinterpret_cast<const float4*>(cps) + 4 * (size_t)i;
+        float4* dst = reinterpret_cast<float4*>(out_cps) + 4 * (size_t)to;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            float4 half[2] = {src[2 * k], src[2 * k + 1]};
+            if (k < m.point_count) {
+                phx_contact_point cp;
+                __builtin_memcpy(&cp, half, sizeof cp);
+                const int si = cp.solver_index;
+                if (si >= 0 && si < nj) cp.solver_index = scanned_flag(jnew, jtotal, si, nj) ? (int)jnew[si] : -1;
+                __builtin_memcpy(half, &cp, sizeof cp);
+            }
+            dst[2 * k] = half[0]; dst[2 * k + 1] = half[1];
+        }
+    }
+}
+
+// Joints: kept joint j goes to jnew[j] with its bodies remapped and contact_point_index = 2 * (its manifold's new index) + old % 2;
+// the warm-start impulses are unchanged
+static __global__ void __launch_bounds__(256) k_remove_joints(const phx_contact_joint* __restrict__ joints, int nj, const phx_manifold* __restrict__ manifolds,
+                                                              const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
+                                                              const unsigned* __restrict__ mnew, const unsigned* __restrict__ jnew,
+                                                              phx_contact_joint* __restrict__ out)
+{
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nj; j += gridDim.x * blockDim.x) {
+        phx_contact_joint q = joints[j];
+        const int mi = q.contact_point_index >> 1;
+        if (!manifold_kept(manifolds[mi], keep)) continue;
+        q.contact_point_index = 2 * (int)mnew[mi] + (q.contact_point_index & 1);
+        q.body1 = (int)bnew[q.body1]; q.body2 = (int)bnew[q.body2];
+        out[jnew[j]] = q;
     }
 }
 
