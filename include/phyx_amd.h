@@ -238,7 +238,7 @@ typedef struct {
     int32_t lds_islands;               /* islands solved by the one-workgroup-per-island kernel */
     int32_t recoloured;                /* 1 if the joint topology changed and the schedule was rebuilt; 2 if that rebuild ran without a host
                                           round trip (bins made on the device with last build's bin count as the launch grid) */
-    int32_t graph_replay;              /* 1 if the launch sequence was replayed from cached hipGraphs */
+    int32_t graph_replay;              /* always 0: the launch sequence is never replayed from captured graphs (kept for the layout) */
     double  device_ms;                 /* HIP-event time of the device work of the last solve */
     int64_t joint_visits;              /* joints swept by the impulse loop, skipped ones included; per-island early exits honoured */
 } phx_solve_stats;

@@ -48,81 +48,8 @@ template <bool HALF> __device__ __forceinline__ float4 body_round(float4 v)
     return make_float4(h2f_bits(f2h_bits(v.x)), h2f_bits(f2h_bits(v.y)), h2f_bits(f2h_bits(v.z)), __int_as_float((int)(short)__float_as_int(v.w)));
 }
 
-// the refreshed constants and accumulators of one joint, in registers for the whole solve
-struct IslJoint { float nx, ny, aN1, aN2, aF1, aF2, cimN, cimF, dstV, dstD, accN, accF, accD; };
-
-// RefreshJoints (ref: Solver.cpp:642-693) — same expressions as k_pack_refresh
-__device__ __forceinline__ void isl_refresh(IslJoint& q, float d1x, float d1y, float d2x, float d2y, const float4& p1, const float4& p2)
-{
-    const float pt1x = d1x + p1.z, pt1y = d1y + p1.w;
-    const float pt2x = d2x + p2.z, pt2y = d2y + p2.w;
-    const float w2x = pt1x - p2.z, w2y = pt1y - p2.w;
-    const Limiter N = refresh_limiter(q.nx, q.ny, d1x, d1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
-    const Limiter F = refresh_limiter(-q.ny, q.nx, d1x, d1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
-    const float depth = (pt2x - pt1x) * q.nx + (pt2y - pt1y) * q.ny;
-    const float dst = 0.f;
-    q.dstV = depth < 1.f ? dst - 0.1f : dst;
-    q.dstD = 0.1f * max_ref(0.f, depth - 2.0f * 1.f);
-    q.aN1 = N.a1; q.aN2 = N.a2; q.cimN = N.cim; q.aF1 = F.a1; q.aF2 = F.a2; q.cimF = F.cim;
-}
-
-// PreStepJoints (ref: Solver.cpp:736-750) of one joint on the bodies held in registers
-__device__ __forceinline__ void isl_prestep(const IslJoint& q, float4& B1, float4& B2, float im1, float ii1, float im2, float ii2)
-{
-    const float tx = -q.ny, ty = q.nx;
-    B1.x = mul_add(q.nx * im1, q.accN, B1.x); B1.y = mul_add(q.ny * im1, q.accN, B1.y); B1.z = mul_add(q.aN1 * ii1, q.accN, B1.z);
-    B1.x = mul_add(tx * im1, q.accF, B1.x); B1.y = mul_add(ty * im1, q.accF, B1.y); B1.z = mul_add(q.aF1 * ii1, q.accF, B1.z);
-    B2.x = mul_add((-q.nx) * im2, q.accN, B2.x); B2.y = mul_add((-q.ny) * im2, q.accN, B2.y); B2.z = mul_add(q.aN2 * ii2, q.accN, B2.z);
-    B2.x = mul_add((-tx) * im2, q.accF, B2.x); B2.y = mul_add((-ty) * im2, q.accF, B2.y); B2.z = mul_add(q.aF2 * ii2, q.accF, B2.z);
-}
-
-// the arithmetic of one impulse visit (ref: Solver.cpp:800-896) on the two bodies held in registers; returns whether the joint moved
-// (kProductiveImpulse, ref: Solver.cpp:8, 894-896).  The skip test and the tags are the caller's.
-__device__ __forceinline__ bool isl_impulse_eval(IslJoint& q, float4& B1, float4& B2, float im1, float ii1, float im2, float ii2)
-{
-    // (Measured and removed: the x / y halves of every body-wide step as v_pk_mul_f32 / v_pk_add_f32 on the register pairs a
-    //  ds_read_b128 leaves — 24 VALU instructions fewer per unit of ~145, no extra moves, bit-exact — is 3 % SLOWER: the step is a
-    //  dependent chain, a packed fp32 operation occupies the pipe twice as long as a plain one, and nothing waits to fill the slots
-    //  it frees.  DESIGN.md §4.2.)
-    const float nx = q.nx, ny = q.ny, tx = -ny, ty = nx;
-    float dv = q.dstV;
-    dv = mul_sub(nx, B1.x, dv); dv = mul_sub(ny, B1.y, dv); dv = mul_sub(q.aN1, B1.z, dv);
-    dv = mul_sub(-nx, B2.x, dv); dv = mul_sub(-ny, B2.y, dv); dv = mul_sub(q.aN2, B2.z, dv);
-    float dn = dv * q.cimN;
-    dn = max_ref(dn, -q.accN);
-    B1.x = mul_add(nx * im1, dn, B1.x); B1.y = mul_add(ny * im1, dn, B1.y); B1.z = mul_add(q.aN1 * ii1, dn, B1.z);
-    B2.x = mul_add((-nx) * im2, dn, B2.x); B2.y = mul_add((-ny) * im2, dn, B2.y); B2.z = mul_add(q.aN2 * ii2, dn, B2.z);
-    q.accN += dn;
-    float fv = 0.f;
-    fv = mul_sub(tx, B1.x, fv); fv = mul_sub(ty, B1.y, fv); fv = mul_sub(q.aF1, B1.z, fv);
-    fv = mul_sub(-tx, B2.x, fv); fv = mul_sub(-ty, B2.y, fv); fv = mul_sub(q.aF2, B2.z, fv);
-    float df = fv * q.cimF;
-    const float force = q.accF + df;
-    const float limit = q.accN * 0.3f;
-    const float signed_limit = force < 0.f ? -limit : limit;
-    const float adjusted = signed_limit - q.accF;
-    if (fabsf(force) > limit) df = adjusted;
-    q.accF += df;
-    B1.x = mul_add(tx * im1, df, B1.x); B1.y = mul_add(ty * im1, df, B1.y); B1.z = mul_add(q.aF1 * ii1, df, B1.z);
-    B2.x = mul_add((-tx) * im2, df, B2.x); B2.y = mul_add((-ty) * im2, df, B2.y); B2.z = mul_add(q.aF2 * ii2, df, B2.z);
-    return max_ref(fabsf(dn), fabsf(df)) > 1e-4f;
-}
-
-// the arithmetic of one displacement visit (ref: Solver.cpp:960-1005) on the two bodies' displacing velocities held in registers;
-// returns whether the joint moved.  The skip test and the tags are the caller's.
-__device__ __forceinline__ bool isl_displace_eval(IslJoint& q, float4& D1, float4& D2, float im1, float ii1, float im2, float ii2)
-{
-    const float nx = q.nx, ny = q.ny;
-    float dv = q.dstD;
-    dv = mul_sub(nx, D1.x, dv); dv = mul_sub(ny, D1.y, dv); dv = mul_sub(q.aN1, D1.z, dv);
-    dv = mul_sub(-nx, D2.x, dv); dv = mul_sub(-ny, D2.y, dv); dv = mul_sub(q.aN2, D2.z, dv);
-    float di = dv * q.cimN;
-    di = max_ref(di, -q.accD);
-    D1.x = mul_add(nx * im1, di, D1.x); D1.y = mul_add(ny * im1, di, D1.y); D1.z = mul_add(q.aN1 * ii1, di, D1.z);
-    D2.x = mul_add((-nx) * im2, di, D2.x); D2.y = mul_add((-ny) * im2, di, D2.y); D2.z = mul_add(q.aN2 * ii2, di, D2.z);
-    q.accD += di;
-    return fabsf(di) > 1e-4f;
-}
+// the refreshed constants and accumulators of one joint, in registers for the whole solve; the arithmetic is solver_kernels.h's
+struct IslJoint : JointConsts { float accN, accF, accD; };
 
 template <int T, int NB, bool HALF, bool TRACE = false>
 __global__ void __launch_bounds__(T, 4) k_solve_islands(SolverView v, IslandView iv, BodyView bv,
@@ -240,8 +167,8 @@ __global__ void __launch_bounds__(T, 4) k_solve_islands(SolverView v, IslandView
     float im1 = 0.f, ii1 = 0.f, im2 = 0.f, ii2 = 0.f;
     if (live) {
         const float4 p1 = par[l1], p2 = par[l2];           // {im, ii, pos.x, pos.y} of the two bodies
-        isl_refresh(q0, da0.x, da0.y, da0.z, da0.w, p1, p2);
-        if (has2) isl_refresh(q1, da1.x, da1.y, da1.z, da1.w, p1, p2);
+        refresh_joint(q0, da0.x, da0.y, da0.z, da0.w, p1, p2);
+        if (has2) refresh_joint(q1, da1.x, da1.y, da1.z, da1.w, p1, p2);
         im1 = p1.x; ii1 = p1.y; im2 = p2.x; ii2 = p2.y;
     }
     // THE DISPLACEMENT HALF OF A GROUP THAT HAS NOTHING TO PUSH APART IS A NO-OP, bit for bit: if every displacing velocity of the group
@@ -272,10 +199,10 @@ __global__ void __launch_bounds__(T, 4) k_solve_islands(SolverView v, IslandView
     for (int c = 0; c < ncol; ++c) {
         if (col == c) {
             float4 B1 = body_load(imp, l1), B2 = body_load(imp, l2);
-            isl_prestep(q0, B1, B2, im1, ii1, im2, ii2);
+            prestep_joint(q0, q0.accN, q0.accF, B1, B2, im1, ii1, im2, ii2, false, false);
             if (has2) {
                 if (HALF) { B1 = body_round<HALF>(B1); B2 = body_round<HALF>(B2); }      // (the ablation rounds on every joint's store)
-                isl_prestep(q1, B1, B2, im1, ii1, im2, ii2);
+                prestep_joint(q1, q1.accN, q1.accF, B1, B2, im1, ii1, im2, ii2, false, false);
             }
             if (!st1) body_store(imp, l1, B1);
             if (!st2) body_store(imp, l2, B2);
@@ -350,14 +277,16 @@ __global__ void __launch_bounds__(T, 4) k_solve_islands(SolverView v, IslandView
         }
         if (active) {
             const float4 S1 = B1, S2 = B2;
-            bool prod = IMP ? isl_impulse_eval(q0, B1, B2, im1, ii1, im2, ii2) : isl_displace_eval(q0, B1, B2, im1, ii1, im2, ii2);
+            bool prod = IMP ? impulse_productive(impulse_visit(q0, q0.accN, q0.accF, B1, B2, im1, ii1, im2, ii2))
+                             : displacement_productive(displacement_visit(q0, q0.accD, B1, B2, im1, ii1, im2, ii2));
             if (has2) {
                 if (HALF) { B1 = body_round<HALF>(B1); B2 = body_round<HALF>(B2); }      // (the ablation rounds on every joint's store)
                 if (ws) {
                     B1.x = sm1 ? S1.x : B1.x; B1.y = sm1 ? S1.y : B1.y; B1.z = sm1 ? S1.z : B1.z; B1.w = sm1 ? S1.w : B1.w;
                     B2.x = sm2 ? S2.x : B2.x; B2.y = sm2 ? S2.y : B2.y; B2.z = sm2 ? S2.z : B2.z; B2.w = sm2 ? S2.w : B2.w;
                 }
-                prod |= IMP ? isl_impulse_eval(q1, B1, B2, im1, ii1, im2, ii2) : isl_displace_eval(q1, B1, B2, im1, ii1, im2, ii2);
+                prod |= IMP ? impulse_productive(impulse_visit(q1, q1.accN, q1.accF, B1, B2, im1, ii1, im2, ii2))
+                             : displacement_productive(displacement_visit(q1, q1.accD, B1, B2, im1, ii1, im2, ii2));
             }
             B1.w = prod ? __int_as_float(it) : B1.w; B2.w = prod ? __int_as_float(it) : B2.w;
             if (prod) {

@@ -73,7 +73,7 @@ public:
     int set_body_state_bits(int bits);
     int set_shard(int shard, int count);
     void set_schedule_reuse(bool on) { reuse_schedule_ = on; }
-    void set_trace(int level) { trace_islands_ = level != 0; trace_waves_ = level != 1; drop_graphs(); }      // 1: phase stamps only; else also per-wave step cycles
+    void set_trace(int level) { trace_islands_ = level != 0; trace_waves_ = level != 1; }      // 1: phase stamps only; else also per-wave step cycles
     int get_island_trace(unsigned long long* out, int cap_groups, int* groups);
     int get_wave_trace(unsigned long long* out, int cap_words, int* waves_per_group);
     int get_groups(int* offsets, int cap, int* count, int* lds_count);
@@ -141,23 +141,10 @@ private:
     bool spec_build_applies(bool want_islands, int nj) const;
     void begin_set(bool hash_runs);                   // the solve being queued takes the other control set
     int complete_partial();                           // ISL_COMPLETE for the groups a verified launch left uncommitted
-    struct GraphKey {
-        const void *bodies = nullptr, *cps = nullptr, *joints = nullptr;
-        int nb = 0, nj = 0, ncp = 0, ci = 0, pi = 0;
-        long long schedule_version = -1;
-        bool valid = false;
-        bool operator==(const GraphKey& o) const
-        {
-            return bodies == o.bodies && cps == o.cps && joints == o.joints && nb == o.nb && nj == o.nj && ncp == o.ncp && ci == o.ci && pi == o.pi &&
-                   schedule_version == o.schedule_version;
-        }
-    };
     int enqueue(const Arrays& a, int nb, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, const phx_config& cfg);
     int enqueue_pre(const BodyView& bodies, int nb, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj);
     int enqueue_sweeps(const BodyView& bodies, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, int ci, int pi, int mode_override = -1);
     int enqueue_post(const BodyView& bodies, int nb, phx_contact_joint* d_joints, int nj);
-    int capture_graphs(const GraphKey& key, const BodyView& bodies, const phx_contact_point* d_cps, phx_contact_joint* d_joints);
-    void drop_graphs();
     int collect_stats(unsigned long long* extra = nullptr, const unsigned long long* extra_src = nullptr, const std::function<int()>* while_waiting = nullptr,
                       const MailCarrier* carrier = nullptr);
     SolverView view() const;
@@ -181,7 +168,6 @@ private:
         bool no_tail = false;             // PHX_NO_TAIL=1: the HBM group's trailing tiny classes one launch each (k_solve_colour) instead of one workgroup's launch (k_solve_tail)
         bool no_parts = false;            // PHX_NO_PARTS=1: sweep the interior classes one launch each
         bool no_fused_verify = false;     // PHX_NO_FUSED_VERIFY=1: always the hash pass (also set for good once a verified launch timed out)
-        bool use_graphs = false;          // PHX_GRAPHS=1
         bool gpu_builder = true;          // PHX_SCHEDULE_BUILDER=host clears it
         bool speculate = true;            // PHX_NO_SPECULATION=1 clears it
         bool no_islands = false;          // PHX_NO_ISLANDS=1
@@ -329,9 +315,7 @@ private:
     phx_solve_stats stats_{};
     bool stats_pending_ = false, have_solve_ = false;
     int last_ci_ = 0, last_pi_ = 0, last_island_mode_ = 0;
-    long long sweep_launches_ = 0, graph_sweep_launches_ = 0, schedule_version_ = 0;
-    hipGraphExec_t graph_[3] = {nullptr, nullptr, nullptr};
-    GraphKey graph_key_, last_key_;
+    long long sweep_launches_ = 0, schedule_version_ = 0;
     bool half_state_ = false, reuse_schedule_ = true;
     bool owns_stream_ = true;
     int shard_ = 0, shard_count_ = 1;    // this handle sweeps groups g with g % shard_count_ == shard_ (the HBM group counts as group lds_groups)

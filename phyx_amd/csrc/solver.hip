@@ -6,6 +6,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <numeric>
+#include <type_traits>
 
 namespace phx {
 
@@ -19,7 +20,6 @@ DeviceSolver::~DeviceSolver()
 {
     if (hipSetDevice(device_) != hipSuccess) return;
     if (stream_) (void)hipStreamSynchronize(stream_);
-    drop_graphs();
     for (hipEvent_t e : bench_events_) (void)hipEventDestroy(e);
     // (every device buffer is a DevBuf member: freed with the object, after this body — the device is selected above)
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
@@ -38,7 +38,6 @@ int DeviceSolver::adopt_stream(hipStream_t s)
 {
     PHX_TRY(use_device(device_));
     PHX_TRY(synchronize());
-    drop_graphs();
     if (stream_ && owns_stream_) PHX_HIP(hipStreamDestroy(stream_));
     stream_ = s;
     owns_stream_ = false;
@@ -57,13 +56,12 @@ DeviceSolver::Options DeviceSolver::Options::from_env()
     o.no_fused_verify = on("PHX_NO_FUSED_VERIFY");        // the topology hash pass in front of every solve on a cached schedule
     const char* wp = getenv("PHX_ISL_WAIT_POLLS");        // tests: 0 makes every workgroup of a verified launch give up, so that ISL_COMPLETE runs
     o.isl_wait_polls = wp ? std::max(0, atoi(wp)) : ISL_WAIT_POLLS;
-    o.use_graphs = on("PHX_GRAPHS");                      // replay the launch sequence from hipGraphs (measured slower: off by default)
     const char* sb = getenv("PHX_SCHEDULE_BUILDER");      // "host" forces the host builder
     o.gpu_builder = !(sb && sb[0] == 'h');
     o.speculate = !on("PHX_NO_SPECULATION");
     o.no_islands = on("PHX_NO_ISLANDS");                  // ignore island modes, always the HBM colour path
     o.no_prelabel = on("PHX_NO_PRELABEL");
-    o.no_spec_bins = on("PHX_NO_SPEC_BINS") || o.use_graphs;      // every rebuild reads the component sizes back and bins them on the host
+    o.no_spec_bins = on("PHX_NO_SPEC_BINS");      // every rebuild reads the component sizes back and bins them on the host
     o.trace_schedule = getenv("PHX_TRACE_SCHEDULE") != nullptr;  // print the schedule builders' laps to stderr
     return o;
 }
@@ -133,13 +131,8 @@ int DeviceSolver::launch_fingerprint(const float4* d_mpos, int nb, const phx_con
     cw.flags = hbm_.flags.p; cw.nflags = hbm_.flags.p ? 2 * max_iters_ : 0;
     cw.sw = hbm_.sw.p; cw.nsw = hbm_.sw.p ? (int)std::min<size_t>(hbm_.sw.cap, 1u << 30) : 0;      // (the whole table: a rebuilt schedule may use more of it)
     sw_cleared_ = hbm_.sw.p; sw_cleared_words_ = (size_t)cw.nsw;
-    int next = hash_slot_ ^ 1;
+    const int next = hash_slot_ ^ 1;
     cw.next_ctl = hash_.p + next;
-    if (opt_.use_graphs) {        // captured graphs have the control set's addresses baked in: always set 0 — its word cleared by a memset, its
-        hash_slot_ = 0;       // counters by this kernel (nothing else touches them while it runs)
-        PHX_HIP(hipMemsetAsync(hash_.p, 0, sizeof(unsigned long long), stream_));
-        next = 0; cw.next_ctl = hash_.p + 1;
-    }
     cw.next_executed = isl_.stats.p + (size_t)next * STATS_SET; cw.next_visits = isl_.visits.p + (size_t)next * VISITS_SET;
     cw.next_shards = isl_.shards.p + (size_t)next * SHARDS_SET;
     hipLaunchKernelGGL(k_topology_hash, dim3(std::max(1, std::min(div_up(std::max(nj, nb), HASH_T), HASH_BLOCKS))), dim3(HASH_T), 0, stream_, d_joints, nj, d_mpos, nb, ncp,
@@ -151,10 +144,10 @@ int DeviceSolver::launch_fingerprint(const float4* d_mpos, int nb, const phx_con
 
 // May a launch of `groups` island workgroups check the cached schedule itself (ISL_VERIFY, island_view.h)?  Only if all of them
 // are resident at once — they wait for each other before they commit — and nobody else needs the topology hash (a sharded solve
-// puts it into its exchange header; graphs bake the launch arguments in).
+// puts it into its exchange header).
 bool DeviceSolver::verify_eligible(int groups, bool big_shape) const
 {
-    if (opt_.no_fused_verify || !opt_.speculate || opt_.use_graphs || shard_count_ != 1 || xch_send_ || groups <= 0) return false;
+    if (opt_.no_fused_verify || !opt_.speculate || shard_count_ != 1 || xch_send_ || groups <= 0) return false;
     // (LDS — 37 / 50 KB — and the 128-register budget admit 4 / 2 workgroups per CU; asked of the runtime for the instantiation
     //  at hand rather than assumed, and never more than that: the occupancy query has been seen one block high)
     const int per_cu = std::min(island_blocks_per_cu(big_shape, half_state_), big_shape ? 2 : 4);
@@ -234,6 +227,15 @@ int DeviceSolver::tail_first_class(int from) const
     return ncol - t >= 2 ? t : ncol;
 }
 
+// The sweep kernels' <impulses, displacement> instantiation for a sweep with the halves imp / disp (at least one): launch(I, D), I and D
+// std::true_type / std::false_type
+template <class Launch> static void with_halves(bool imp, bool disp, Launch launch)
+{
+    if (imp && disp) launch(std::true_type{}, std::true_type{});
+    else if (imp)    launch(std::true_type{}, std::false_type{});
+    else             launch(std::false_type{}, std::true_type{});
+}
+
 int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, int ci, int pi, int mode_override)
 {
     const SolverView v = view();
@@ -282,7 +284,7 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
         // A schedule with LDS islands AND an HBM group (a world that is merging, or settled around a few loose stacks): the island
         // launch is one group's chain of class steps — ~90 us whatever the group count — and touches nothing the HBM group's
         // classes x sweeps launches touch, so it runs beside them on a second stream: fork here, join behind the sweeps.
-        forked = owns_hbm_group() && !opt_.use_graphs && !opt_.no_side_stream && !trace_islands_ && side_stream_;
+        forked = owns_hbm_group() && !opt_.no_side_stream && !trace_islands_ && side_stream_;
         if (forked) {
             PHX_HIP(hipEventRecord(ev_fork_, stream_));
             PHX_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
@@ -300,15 +302,12 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
                 for (int level = 0; level < part_levels(); ++level) {
                     const PartsView pv = parts_view(level, v.nb);
                     const dim3 g(pv.parts), b(PARTS_T);
-                    if (level == 0) {      // a part's ~1000 units, class by class, the next class's constants requested a class ahead (solver_kernels.h)
-                        if (imp && disp) hipLaunchKernelGGL((k_solve_parts_ahead<true, true>), g, b, 0, stream_, v, pv, it);
-                        else if (imp)    hipLaunchKernelGGL((k_solve_parts_ahead<true, false>), g, b, 0, stream_, v, pv, it);
-                        else             hipLaunchKernelGGL((k_solve_parts_ahead<false, true>), g, b, 0, stream_, v, pv, it);
-                    } else {           // a level-1 part has a few dozen units: a lane owns one, everything requested up front
-                        if (imp && disp) hipLaunchKernelGGL((k_solve_parts<true, true, true>), g, b, 0, stream_, v, pv, it);
-                        else if (imp)    hipLaunchKernelGGL((k_solve_parts<true, false, true>), g, b, 0, stream_, v, pv, it);
-                        else             hipLaunchKernelGGL((k_solve_parts<false, true, true>), g, b, 0, stream_, v, pv, it);
-                    }
+                    with_halves(imp, disp, [&](auto I, auto D) {
+                        if (level == 0)    // a part's ~1000 units, class by class, the next class's constants requested a class ahead (solver_kernels.h)
+                            hipLaunchKernelGGL((k_solve_parts_ahead<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, pv, it);
+                        else               // a level-1 part has a few dozen units: a lane owns one, everything requested up front
+                            hipLaunchKernelGGL((k_solve_parts<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, pv, it);
+                    });
                     ++sweep_launches_;
                 }
                 c0 = sched_.hbm_interior_classes;
@@ -317,16 +316,16 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
             for (int c = c0; c < tail; ++c) {
                 const int cb = sched_.hbm_colour_offsets[c], ce = sched_.hbm_colour_offsets[c + 1], lead = sched_.hbm_class_leaders[c], foll = ce - cb - lead;
                 const dim3 g(std::max(1, std::min(div_up(lead, SOLVE_BLOCK), 8192))), b(SOLVE_BLOCK);
-                if (imp && disp) hipLaunchKernelGGL((k_solve_colour<true, true>), g, b, 0, stream_, v, cb, lead, foll, c, it);
-                else if (imp)    hipLaunchKernelGGL((k_solve_colour<true, false>), g, b, 0, stream_, v, cb, lead, foll, c, it);
-                else             hipLaunchKernelGGL((k_solve_colour<false, true>), g, b, 0, stream_, v, cb, lead, foll, c, it);
+                with_halves(imp, disp, [&](auto I, auto D) {
+                    hipLaunchKernelGGL((k_solve_colour<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, cb, lead, foll, c, it);
+                });
                 ++sweep_launches_;
             }
             if (tail < ncol) {
                 const int4* tab = parts_.class_tab.p;
-                if (imp && disp) hipLaunchKernelGGL((k_solve_tail<true, true>), dim3(1), dim3(TAIL_T), 0, stream_, v, tab, tail, ncol - tail, it);
-                else if (imp)    hipLaunchKernelGGL((k_solve_tail<true, false>), dim3(1), dim3(TAIL_T), 0, stream_, v, tab, tail, ncol - tail, it);
-                else             hipLaunchKernelGGL((k_solve_tail<false, true>), dim3(1), dim3(TAIL_T), 0, stream_, v, tab, tail, ncol - tail, it);
+                with_halves(imp, disp, [&](auto I, auto D) {
+                    hipLaunchKernelGGL((k_solve_tail<decltype(I)::value, decltype(D)::value>), dim3(1), dim3(TAIL_T), 0, stream_, v, tab, tail, ncol - tail, it);
+                });
                 ++sweep_launches_;
             }
         }
@@ -350,37 +349,6 @@ int DeviceSolver::enqueue_post(const BodyView& d_bodies, int nb, phx_contact_joi
     return PHX_OK;
 }
 
-void DeviceSolver::drop_graphs()
-{
-    for (hipGraphExec_t& g : graph_) { if (g) (void)hipGraphExecDestroy(g); g = nullptr; }
-    graph_key_ = GraphKey{};
-}
-
-// Capture the three segments into hipGraphs.  A solve of the 200k-box scene is ~230 launches of 1-4 us
-// kernels; launched eagerly the host (~4 us per launch) is the bottleneck, replayed from a graph it is not.
-int DeviceSolver::capture_graphs(const GraphKey& key, const BodyView& d_bodies, const phx_contact_point* d_cps, phx_contact_joint* d_joints)
-{
-    drop_graphs();
-    for (int seg = 0; seg < 3; ++seg) {
-        hipGraph_t graph = nullptr;
-        PHX_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-        int st = seg == 0 ? enqueue_pre(d_bodies, key.nb, d_cps, d_joints, key.nj)
-               : seg == 1 ? enqueue_sweeps(d_bodies, d_cps, d_joints, key.nj, key.ci, key.pi)
-                          : enqueue_post(d_bodies, key.nb, d_joints, key.nj);
-        hipError_t e = hipStreamEndCapture(stream_, &graph);
-        if (st != PHX_OK) { if (graph) (void)hipGraphDestroy(graph); drop_graphs(); return st; }
-        if (e != hipSuccess) { set_error("hipStreamEndCapture: %s", hipGetErrorString(e)); drop_graphs(); return PHX_ERR_HIP; }
-        if (graph) {
-            e = hipGraphInstantiate(&graph_[seg], graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) { set_error("hipGraphInstantiate: %s", hipGetErrorString(e)); drop_graphs(); return PHX_ERR_HIP; }
-        }
-    }
-    graph_key_ = key;
-    graph_sweep_launches_ = sweep_launches_;
-    return PHX_OK;
-}
-
 int DeviceSolver::enqueue(const Arrays& arrays, int nb, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, const phx_config& cfg)
 {
     cur_ = arrays;
@@ -392,36 +360,24 @@ int DeviceSolver::enqueue(const Arrays& arrays, int nb, const phx_contact_point*
         max_iters_ = std::max(iters + 1, 64);
         PHX_TRY(hbm_.flags.reserve(2 * (size_t)max_iters_));
         PHX_HIP(hipMemsetAsync(hbm_.flags.p, 0, 2 * (size_t)max_iters_ * sizeof(int), stream_));
-        drop_graphs();
     }
-    GraphKey key;
-    key.bodies = d_bodies.vel; key.cps = d_cps; key.joints = d_joints; key.nb = nb; key.nj = nj; key.ncp = ncp_; key.ci = ci; key.pi = pi;
-    key.schedule_version = schedule_version_; key.valid = true;
-    // graphs pay off from the second solve of an unchanged (schedule, buffers, iteration counts) tuple on
-    const bool have = graph_key_.valid && graph_key_ == key;
-    if (!have && opt_.use_graphs && last_key_.valid && last_key_ == key) PHX_TRY(capture_graphs(key, d_bodies, d_cps, d_joints));
-    last_key_ = key;
-    const bool replay = graph_key_.valid && graph_key_ == key;
 
     // No HIP events around a solve: an event record is a barrier packet of its own and idles the queue for ~5 us.  The device time
     // (phx_solve_stats.device_ms) comes from clock stamps the solve's first and last kernels leave (solve_stamp_begin / _end); only
     // bench() brackets the sweeps with events — the live launch time its roofline is computed from — and device_ms reports those.
     {
         RoctxRange r("PrepareBodies + PrepareJoints + RefreshJoints + PreStepJoints (HBM group)");      // ref: Solver.cpp:70, 135, 146, 157
-        if (replay) { if (graph_[0]) PHX_HIP(hipGraphLaunch(graph_[0], stream_)); }
-        else PHX_TRY(enqueue_pre(d_bodies, nb, d_cps, d_joints, nj));
+        PHX_TRY(enqueue_pre(d_bodies, nb, d_cps, d_joints, nj));
     }
     if (time_sweeps_) PHX_HIP(hipEventRecord(ev_sweep_begin_, stream_));
     {
         RoctxRange r("SolveJointIsland: Impulse + Displacement");                                        // ref: Solver.cpp:133, 171, 193
-        if (replay) { if (graph_[1]) PHX_HIP(hipGraphLaunch(graph_[1], stream_)); sweep_launches_ = graph_sweep_launches_; }
-        else PHX_TRY(enqueue_sweeps(d_bodies, d_cps, d_joints, nj, ci, pi));
+        PHX_TRY(enqueue_sweeps(d_bodies, d_cps, d_joints, nj, ci, pi));
     }
     if (time_sweeps_) PHX_HIP(hipEventRecord(ev_sweep_end_, stream_));
     {
         RoctxRange r("FinishJoints + FinishBodies (HBM group)");                                         // ref: Solver.cpp:213, 114
-        if (replay) { if (graph_[2]) PHX_HIP(hipGraphLaunch(graph_[2], stream_)); }
-        else PHX_TRY(enqueue_post(d_bodies, nb, d_joints, nj));
+        PHX_TRY(enqueue_post(d_bodies, nb, d_joints, nj));
         // a solve that came through the C-ABI edge: FinishBodies into the caller's records, behind the same gate
         if (arrays.aos && nb) {
             hipLaunchKernelGGL(k_view_to_bodies, dim3(grid_for(nb)), dim3(256), 0, stream_, d_bodies, nb, arrays.aos, (const unsigned long long*)(hash_.p + hash_slot_), gate_expected_);
@@ -432,7 +388,6 @@ int DeviceSolver::enqueue(const Arrays& arrays, int nb, const phx_contact_point*
     last_ci_ = ci; last_pi_ = pi; last_island_mode_ = cfg.island_mode;
     stats_pending_ = true;
     have_solve_ = true;
-    stats_.graph_replay = replay ? 1 : 0;
     return PHX_OK;
 }
 
@@ -810,7 +765,7 @@ int DeviceSolver::get_wave_trace(unsigned long long* out, int cap_words, int* wa
 int DeviceSolver::set_body_state_bits(int bits)
 {
     PHX_REQUIRE(bits == 16 || bits == 32, "body state precision must be 16 or 32 bits");
-    if ((bits == 16) != half_state_) { half_state_ = bits == 16; drop_graphs(); }
+    if ((bits == 16) != half_state_) { half_state_ = bits == 16; }
     return PHX_OK;
 }
 
@@ -824,7 +779,7 @@ int DeviceSolver::set_shard(int shard, int count)
         PHX_TRY(synchronize());
         // a sharded solve's schedule also carries the groups' body counts for the exchange layout: rebuild on a new count
         if (count != shard_count_) sched_.valid = false;
-        shard_ = shard; shard_count_ = count; drop_graphs();
+        shard_ = shard; shard_count_ = count;
     }
     return PHX_OK;
 }

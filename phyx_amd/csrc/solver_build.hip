@@ -91,7 +91,6 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
             if (!spec_bins_pending_) gate_expected_ = fp;
             sched_.valid = true;
             ++schedule_version_;
-            drop_graphs();
             stats_.recoloured = spec_bins_pending_ ? 2 : 1;
             return PHX_OK;
         }
@@ -217,7 +216,6 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
     raw_fingerprint_ = raw; gate_expected_ = raw; have_hash_ = true;
     sched_.valid = true;
     ++schedule_version_;
-    drop_graphs();
     stats_.recoloured = 1;
     return PHX_OK;
 }

@@ -190,6 +190,94 @@ __device__ __forceinline__ Limiter refresh_limiter(float n1x, float n1y, float w
     return L;
 }
 
+// ---- the constraint arithmetic, stated once: the LDS island kernel (island_kernel.h) and the HBM path below both call these -------------
+// The refreshed constants of one contact joint.  Of the reference's packed limiter (ref: Solver.h:7-45) the rest is recomputed: the
+// friction projector is the rotated normal, projector2 = -projector1 and compMass* = projector * invMass are single rounded multiplies.
+struct JointConsts { float nx, ny, aN1, aN2, aF1, aF2, cimN, cimF, dstV, dstD; };
+
+// RefreshJoints (ref: Solver.cpp:642-693) of one joint with normal (k.nx, k.ny): fills the rest of k.  p1, p2 = {im, ii, pos.x, pos.y}.
+// bounce == 0 makes dv = -0 * (relV . n); max(dv - 1, 0) is then +0 for every finite or non-finite relV, so the velocity gathers of
+// :619-625 are dead and dropped.
+__device__ __forceinline__ void refresh_joint(JointConsts& k, float d1x, float d1y, float d2x, float d2y, const float4& p1, const float4& p2)
+{
+    const float pt1x = d1x + p1.z, pt1y = d1y + p1.w;
+    const float pt2x = d2x + p2.z, pt2y = d2y + p2.w;
+    const float w2x = pt1x - p2.z, w2y = pt1y - p2.w;                  // (body 1's point, sic)
+    const Limiter N = refresh_limiter(k.nx, k.ny, d1x, d1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
+    const Limiter F = refresh_limiter(-k.ny, k.nx, d1x, d1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
+    const float depth = (pt2x - pt1x) * k.nx + (pt2y - pt1y) * k.ny;
+    const float dst = 0.f;
+    k.dstV = depth < 1.f ? dst - 0.1f : dst;
+    k.dstD = 0.1f * max_ref(0.f, depth - 2.0f * 1.f);
+    k.aN1 = N.a1; k.aN2 = N.a2; k.cimN = N.cim; k.aF1 = F.a1; k.aF2 = F.a2; k.cimF = F.cim;
+}
+
+// PreStepJoints (ref: Solver.cpp:736-750) of one joint on the two bodies held in registers; a static body (st1 / st2) is left as it is
+__device__ __forceinline__ void prestep_joint(const JointConsts& k, float accN, float accF, float4& B1, float4& B2, float im1, float ii1, float im2, float ii2,
+                                              bool st1, bool st2)
+{
+    const float nx = k.nx, ny = k.ny, tx = -ny, ty = nx;
+    if (!st1) {
+        B1.x = mul_add(nx * im1, accN, B1.x); B1.y = mul_add(ny * im1, accN, B1.y); B1.z = mul_add(k.aN1 * ii1, accN, B1.z);
+        B1.x = mul_add(tx * im1, accF, B1.x); B1.y = mul_add(ty * im1, accF, B1.y); B1.z = mul_add(k.aF1 * ii1, accF, B1.z);
+    }
+    if (!st2) {
+        B2.x = mul_add((-nx) * im2, accN, B2.x); B2.y = mul_add((-ny) * im2, accN, B2.y); B2.z = mul_add(k.aN2 * ii2, accN, B2.z);
+        B2.x = mul_add((-tx) * im2, accF, B2.x); B2.y = mul_add((-ty) * im2, accF, B2.y); B2.z = mul_add(k.aF2 * ii2, accF, B2.z);
+    }
+}
+
+// The arithmetic of one impulse visit (ref: Solver.cpp:800-889) on the two bodies held in registers: the normal, then the friction
+// limiter.  Returns the two impulses applied; impulse_productive says whether the joint moved.  The skip test and the tags are the caller's.
+__device__ __forceinline__ float2 impulse_visit(const JointConsts& k, float& accN, float& accF, float4& B1, float4& B2, float im1, float ii1, float im2, float ii2)
+{
+    // (Measured and removed in the island kernel: the x / y halves of every body-wide step as v_pk_mul_f32 / v_pk_add_f32 on the register
+    //  pairs a ds_read_b128 leaves — 24 VALU instructions fewer per unit of ~145, no extra moves, bit-exact — is 3 % SLOWER: the step is a
+    //  dependent chain, a packed fp32 operation occupies the pipe twice as long as a plain one, and nothing waits to fill the slots it
+    //  frees.  DESIGN.md §4.2.)
+    const float nx = k.nx, ny = k.ny, tx = -ny, ty = nx;
+    float dv = k.dstV;
+    dv = mul_sub(nx, B1.x, dv); dv = mul_sub(ny, B1.y, dv); dv = mul_sub(k.aN1, B1.z, dv);
+    dv = mul_sub(-nx, B2.x, dv); dv = mul_sub(-ny, B2.y, dv); dv = mul_sub(k.aN2, B2.z, dv);
+    float dn = dv * k.cimN;
+    dn = max_ref(dn, -accN);
+    B1.x = mul_add(nx * im1, dn, B1.x); B1.y = mul_add(ny * im1, dn, B1.y); B1.z = mul_add(k.aN1 * ii1, dn, B1.z);
+    B2.x = mul_add((-nx) * im2, dn, B2.x); B2.y = mul_add((-ny) * im2, dn, B2.y); B2.z = mul_add(k.aN2 * ii2, dn, B2.z);
+    accN += dn;
+    float fv = 0.f;
+    fv = mul_sub(tx, B1.x, fv); fv = mul_sub(ty, B1.y, fv); fv = mul_sub(k.aF1, B1.z, fv);
+    fv = mul_sub(-tx, B2.x, fv); fv = mul_sub(-ty, B2.y, fv); fv = mul_sub(k.aF2, B2.z, fv);
+    float df = fv * k.cimF;
+    const float force = accF + df;
+    const float limit = accN * 0.3f;
+    const float signed_limit = force < 0.f ? -limit : limit;          // scalar flipsign, ref: SIMD_Scalar.h:265-268
+    const float adjusted = signed_limit - accF;
+    if (fabsf(force) > limit) df = adjusted;
+    accF += df;
+    B1.x = mul_add(tx * im1, df, B1.x); B1.y = mul_add(ty * im1, df, B1.y); B1.z = mul_add(k.aF1 * ii1, df, B1.z);
+    B2.x = mul_add((-tx) * im2, df, B2.x); B2.y = mul_add((-ty) * im2, df, B2.y); B2.z = mul_add(k.aF2 * ii2, df, B2.z);
+    return make_float2(dn, df);
+}
+// kProductiveImpulse (ref: Solver.cpp:8, 894-896) of the impulses impulse_visit applied
+__device__ __forceinline__ bool impulse_productive(float2 d) { return max_ref(fabsf(d.x), fabsf(d.y)) > 1e-4f; }
+
+// The arithmetic of one displacement visit (ref: Solver.cpp:960-1005) on the two bodies' displacing velocities held in registers.  Returns
+// the impulse applied; displacement_productive says whether the joint moved.  The skip test and the tags are the caller's.
+__device__ __forceinline__ float displacement_visit(const JointConsts& k, float& accD, float4& D1, float4& D2, float im1, float ii1, float im2, float ii2)
+{
+    const float nx = k.nx, ny = k.ny;
+    float dv = k.dstD;
+    dv = mul_sub(nx, D1.x, dv); dv = mul_sub(ny, D1.y, dv); dv = mul_sub(k.aN1, D1.z, dv);
+    dv = mul_sub(-nx, D2.x, dv); dv = mul_sub(-ny, D2.y, dv); dv = mul_sub(k.aN2, D2.z, dv);
+    float di = dv * k.cimN;
+    di = max_ref(di, -accD);
+    D1.x = mul_add(nx * im1, di, D1.x); D1.y = mul_add(ny * im1, di, D1.y); D1.z = mul_add(k.aN1 * ii1, di, D1.z);
+    D2.x = mul_add((-nx) * im2, di, D2.x); D2.y = mul_add((-ny) * im2, di, D2.y); D2.z = mul_add(k.aN2 * ii2, di, D2.z);
+    accD += di;
+    return di;
+}
+__device__ __forceinline__ bool displacement_productive(float di) { return fabsf(di) > 1e-4f; }      // ref: Solver.cpp:999
+
 static __global__ void __launch_bounds__(256) k_pack_refresh(SolverView v, int begin, int end, const phx_contact_joint* __restrict__ joints,
                                                       const phx_contact_point* __restrict__ cps, const int* __restrict__ static_slot)
 {
@@ -200,32 +288,19 @@ static __global__ void __launch_bounds__(256) k_pack_refresh(SolverView v, int b
         j.body1 = clamp_index(j.body1, v.nb); j.body2 = clamp_index(j.body2, v.nb);
         const phx_contact_point& cp = cps[clamp_index(j.contact_point_index, v.ncp)];
         const float d1x = cp.delta1.x, d1y = cp.delta1.y, d2x = cp.delta2.x, d2y = cp.delta2.y;
-        const float nx = cp.normal.x, ny = cp.normal.y;
+        JointConsts k;
+        k.nx = cp.normal.x; k.ny = cp.normal.y;
         const float4 p1 = v.sb_par[j.body1], p2 = v.sb_par[j.body2];       // {im, ii, pos.x, pos.y}
-
-        const float pt1x = d1x + p1.z, pt1y = d1y + p1.w;
-        const float pt2x = d2x + p2.z, pt2y = d2y + p2.w;
-        const float w1x = d1x, w1y = d1y;
-        const float w2x = pt1x - p2.z, w2y = pt1y - p2.w;                  // ref: Solver.cpp:649-650 (body-1's point, sic)
-
-        const Limiter N = refresh_limiter(nx, ny, w1x, w1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
-        const Limiter F = refresh_limiter(-ny, nx, w1x, w1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
-
-        // ref: Solver.cpp:658-680.  bounce == 0 makes dv = -0 * (relV . n); max(dv - 1, 0) is then +0 for
-        // every finite or non-finite relV, so the velocity gathers of :619-625 are dead and dropped.
-        const float depth = (pt2x - pt1x) * nx + (pt2y - pt1y) * ny;
-        const float dst = 0.f;
-        const float n_dst = depth < 1.f ? dst - 0.1f : dst;
-        const float n_dst_disp = 0.1f * max_ref(0.f, depth - 2.0f * 1.f);
+        refresh_joint(k, d1x, d1y, d2x, d2y, p1, p2);
 
         const int s1 = static_slot[j.body1], s2 = static_slot[j.body2];
-        v.q0[s] = make_float4(nx, ny, N.a1, N.a2);
-        v.q1[s] = make_float4(F.a1, F.a2, F.cim, n_dst);
-        v.q2[s] = make_float4(N.cim, p1.x, p1.y, p2.x);
-        v.qn[s] = N.cim;                        // (again, 4 bytes apart: all a unit's FOLLOWER needs of q2 / q3 — the rest is its leader's)
+        v.q0[s] = make_float4(k.nx, k.ny, k.aN1, k.aN2);
+        v.q1[s] = make_float4(k.aF1, k.aF2, k.cimF, k.dstV);
+        v.q2[s] = make_float4(k.cimN, p1.x, p1.y, p2.x);
+        v.qn[s] = k.cimN;                       // (again, 4 bytes apart: all a unit's FOLLOWER needs of q2 / q3 — the rest is its leader's)
         v.q3[s] = make_int4(__float_as_int(p2.y), j.body1, j.body2, s1 >= 0 ? s1 : s2);
         v.acc[s] = make_float2(j.normal_accumulated_impulse, j.friction_accumulated_impulse);
-        v.dd[s] = make_float2(n_dst_disp, 0.f);
+        v.dd[s] = make_float2(k.dstD, 0.f);
     }
 }
 
@@ -235,15 +310,8 @@ __device__ __forceinline__ void prestep_one(const SolverView& v, int s, float4& 
 {
     const float4 a = v.q0[s], b = v.q1[s];
     const float2 acc = v.acc[s];
-    const float nx = a.x, ny = a.y, tx = -ny, ty = nx;
-    if (!st1) {
-        B1.x = mul_add(nx * im1, acc.x, B1.x); B1.y = mul_add(ny * im1, acc.x, B1.y); B1.z = mul_add(a.z * ii1, acc.x, B1.z);
-        B1.x = mul_add(tx * im1, acc.y, B1.x); B1.y = mul_add(ty * im1, acc.y, B1.y); B1.z = mul_add(b.x * ii1, acc.y, B1.z);
-    }
-    if (!st2) {
-        B2.x = mul_add((-nx) * im2, acc.x, B2.x); B2.y = mul_add((-ny) * im2, acc.x, B2.y); B2.z = mul_add(a.w * ii2, acc.x, B2.z);
-        B2.x = mul_add((-tx) * im2, acc.y, B2.x); B2.y = mul_add((-ty) * im2, acc.y, B2.y); B2.z = mul_add(b.y * ii2, acc.y, B2.z);
-    }
+    const JointConsts k{a.x, a.y, a.z, a.w, b.x, b.y, 0.f, b.z, b.w, 0.f};
+    prestep_joint(k, acc.x, acc.y, B1, B2, im1, ii1, im2, ii2, st1, st2);
 }
 
 static __global__ void __launch_bounds__(256) k_prestep(SolverView v, int begin, int leaders, int followers)
@@ -311,39 +379,16 @@ __device__ __forceinline__ void solve_one(const SolverView& v, int s, HbmJoint& 
 {
     // sp_imp / sp_disp: 'the unit's static body was productive' (static_productive) — read once per unit: a class cannot
     // change what the test returns for that class (tags raised in it carry the class itself, which is not 'earlier')
-    const float4 a = q.a, f = q.f, c = q.c;
-    const float nx = a.x, ny = a.y, tx = -ny, ty = nx;
+    JointConsts k{q.a.x, q.a.y, q.a.z, q.a.w, q.f.x, q.f.y, q.c.x, q.f.z, q.f.w, 0.f};
     if (imp_on) {
         // ref: Solver.cpp:790-798
         const bool p1 = st1 ? sp_imp : (__float_as_int(B1.w) > iter - 2);
         const bool p2 = st2 ? sp_imp : (__float_as_int(B2.w) > iter - 2);
         if (p1 || p2) {
             float2 acc = q.acc;
-            // normal limiter (ref: :833-858)
-            float dv = f.w;
-            dv = mul_sub(nx, B1.x, dv); dv = mul_sub(ny, B1.y, dv); dv = mul_sub(a.z, B1.z, dv);
-            dv = mul_sub(-nx, B2.x, dv); dv = mul_sub(-ny, B2.y, dv); dv = mul_sub(a.w, B2.z, dv);
-            float dn = dv * c.x;
-            dn = max_ref(dn, -acc.x);
-            B1.x = mul_add(nx * im1, dn, B1.x); B1.y = mul_add(ny * im1, dn, B1.y); B1.z = mul_add(a.z * ii1, dn, B1.z);
-            B2.x = mul_add((-nx) * im2, dn, B2.x); B2.y = mul_add((-ny) * im2, dn, B2.y); B2.z = mul_add(a.w * ii2, dn, B2.z);
-            acc.x += dn;
-            // friction limiter (ref: :860-889)
-            float fv = 0.f;
-            fv = mul_sub(tx, B1.x, fv); fv = mul_sub(ty, B1.y, fv); fv = mul_sub(f.x, B1.z, fv);
-            fv = mul_sub(-tx, B2.x, fv); fv = mul_sub(-ty, B2.y, fv); fv = mul_sub(f.y, B2.z, fv);
-            float df = fv * f.z;
-            const float force = acc.y + df;
-            const float limit = acc.x * 0.3f;
-            const float signed_limit = force < 0.f ? -limit : limit;          // scalar flipsign, ref: SIMD_Scalar.h:265-268
-            const float adjusted = signed_limit - acc.y;
-            if (fabsf(force) > limit) df = adjusted;
-            acc.y += df;
-            B1.x = mul_add(tx * im1, df, B1.x); B1.y = mul_add(ty * im1, df, B1.y); B1.z = mul_add(f.x * ii1, df, B1.z);
-            B2.x = mul_add((-tx) * im2, df, B2.x); B2.y = mul_add((-ty) * im2, df, B2.y); B2.z = mul_add(f.y * ii2, df, B2.z);
+            const float2 d = impulse_visit(k, acc.x, acc.y, B1, B2, im1, ii1, im2, ii2);
             v.acc[s] = acc;
-            const bool productive = max_ref(fabsf(dn), fabsf(df)) > 1e-4f;      // ref: :894-896
-            if (productive) {
+            if (impulse_productive(d)) {
                 B1.w = __int_as_float(iter); B2.w = __int_as_float(iter);
                 any_imp = true;
                 if ((st1 || st2) && ss >= 0) tag_imp = true;
@@ -356,17 +401,10 @@ __device__ __forceinline__ void solve_one(const SolverView& v, int s, HbmJoint& 
         const bool p2 = st2 ? sp_disp : (__float_as_int(D2.w) > iter - 2);
         if (p1 || p2) {
             float2 d = q.d;
-            float dv = d.x;                                                      // ref: :973-981
-            dv = mul_sub(nx, D1.x, dv); dv = mul_sub(ny, D1.y, dv); dv = mul_sub(a.z, D1.z, dv);
-            dv = mul_sub(-nx, D2.x, dv); dv = mul_sub(-ny, D2.y, dv); dv = mul_sub(a.w, D2.z, dv);
-            float di = dv * c.x;
-            di = max_ref(di, -d.y);
-            D1.x = mul_add(nx * im1, di, D1.x); D1.y = mul_add(ny * im1, di, D1.y); D1.z = mul_add(a.z * ii1, di, D1.z);
-            D2.x = mul_add((-nx) * im2, di, D2.x); D2.y = mul_add((-ny) * im2, di, D2.y); D2.z = mul_add(a.w * ii2, di, D2.z);
-            d.y += di;
+            k.dstD = d.x;
+            const float di = displacement_visit(k, d.y, D1, D2, im1, ii1, im2, ii2);
             v.dd[s] = d;
-            const bool productive = fabsf(di) > 1e-4f;                           // ref: :999
-            if (productive) {
+            if (displacement_productive(di)) {
                 D1.w = __int_as_float(iter); D2.w = __int_as_float(iter);
                 any_disp = true;
                 if ((st1 || st2) && ss >= 0) tag_disp = true;
@@ -374,6 +412,34 @@ __device__ __forceinline__ void solve_one(const SolverView& v, int s, HbmJoint& 
             dirty_disp = true;
         }
     }
+}
+
+// The global-memory unit step (k_solve_colour, k_solve_tail): the unit's leader, then its follower (has2), on the body state gathered for it;
+// then the dynamic bodies' state scattered back and the wave's static tags raised.  sp(imp): static_productive of the unit's static body
+// for the impulse (true) or the displacement half — asked only of a unit that has one.
+template <bool DO_IMP, bool DO_DISP, class StaticProductive>
+__device__ __forceinline__ void hbm_unit_step(const SolverView& v, int s0, HbmJoint& q0, int s1, HbmJoint& q1, bool has2, int colour, int iter, bool disp_on,
+                                              float4& B1, float4& B2, float4& D1, float4& D2, StaticProductive sp, bool& any_imp, bool& any_disp)
+{
+    const int b1 = q0.k.y, b2 = q0.k.z, ss = q0.k.w;
+    const float im1 = q0.c.y, ii1 = q0.c.z, im2 = q0.c.w, ii2 = __int_as_float(q0.k.x);
+    const bool st1 = (im1 == 0.f && ii1 == 0.f), st2 = (im2 == 0.f && ii2 == 0.f);
+    const float4 S1 = B1, S2 = B2, T1 = D1, T2 = D2;
+    bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
+    const bool sp_imp = DO_IMP && (st1 || st2) && sp(true);
+    const bool sp_disp = disp_on && (st1 || st2) && sp(false);
+    solve_one(v, s0, q0, colour, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+    if (has2) {                                        // a static body's record is never stored: the follower must see it untouched
+        if (st1) { B1 = S1; D1 = T1; }
+        if (st2) { B2 = S2; D2 = T2; }
+        solve_one(v, s1, q1, colour, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+    }
+    if (dirty_imp) { if (!st1) v.sb_imp[b1] = B1; if (!st2) v.sb_imp[b2] = B2; }
+    if (dirty_disp) { if (!st1) v.sb_disp[b1] = D1; if (!st2) v.sb_disp[b2] = D2; }
+    // static-tag updates of this wave, one atomic per distinct static body: every joint on the ground raises the
+    // same word to the same value, and same-address atomics serialise at the L2 (thousands per colour otherwise)
+    if (DO_IMP) wave_tag_update(v.sw_imp + (iter & 1) * v.nstatic, tag_imp, ss, static_word(iter, colour));
+    if (DO_DISP) wave_tag_update(v.sw_disp + (iter & 1) * v.nstatic, tag_disp, ss, static_word(iter, colour));
 }
 
 // one class: `leaders` leader slots from `begin`, then `followers` follower slots; lane i sweeps leader i, then follower i
@@ -398,24 +464,8 @@ static __global__ void __launch_bounds__(SOLVE_BLOCK) k_solve_colour(SolverView 
         float4 B1 = make_float4(0.f, 0.f, 0.f, 0.f), B2 = B1, D1 = B1, D2 = B1;
         if (imp_on) { B1 = v.sb_imp[b1]; B2 = v.sb_imp[b2]; }
         if (disp_on) { D1 = v.sb_disp[b1]; D2 = v.sb_disp[b2]; }
-        const float im1 = q0.c.y, ii1 = q0.c.z, im2 = q0.c.w, ii2 = __int_as_float(q0.k.x);
-        const bool st1 = (im1 == 0.f && ii1 == 0.f), st2 = (im2 == 0.f && ii2 == 0.f);
-        const float4 S1 = B1, S2 = B2, T1 = D1, T2 = D2;
-        bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
-        const bool sp_imp = imp_on && (st1 || st2) && static_productive(v.sw_imp, v.nstatic, ss, iter, colour);
-        const bool sp_disp = disp_on && (st1 || st2) && static_productive(v.sw_disp, v.nstatic, ss, iter, colour);
-        solve_one(v, s0, q0, colour, iter, imp_on, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        if (has2) {                                    // a static body's record is never stored: the follower must see it untouched
-            if (st1) { B1 = S1; D1 = T1; }
-            if (st2) { B2 = S2; D2 = T2; }
-            solve_one(v, s1, q1, colour, iter, imp_on, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        }
-        if (dirty_imp) { if (!st1) v.sb_imp[b1] = B1; if (!st2) v.sb_imp[b2] = B2; }
-        if (dirty_disp) { if (!st1) v.sb_disp[b1] = D1; if (!st2) v.sb_disp[b2] = D2; }
-        // static-tag updates of this wave, one atomic per distinct static body: every joint on the ground raises the
-        // same word to the same value, and same-address atomics serialise at the L2 (thousands per colour otherwise)
-        if (DO_IMP) wave_tag_update(v.sw_imp + (iter & 1) * v.nstatic, tag_imp, ss, static_word(iter, colour));
-        if (DO_DISP) wave_tag_update(v.sw_disp + (iter & 1) * v.nstatic, tag_disp, ss, static_word(iter, colour));
+        auto sp = [&](bool imp) { return static_productive(imp ? v.sw_imp : v.sw_disp, v.nstatic, ss, iter, colour); };
+        hbm_unit_step<DO_IMP, DO_DISP>(v, s0, q0, s1, q1, has2, colour, iter, disp_on, B1, B2, D1, D2, sp, any_imp, any_disp);
     }
     // any(productive) of the sweep (ref: Solver.cpp:913, 1017): one store per wave that saw one
     if (DO_IMP && __any(any_imp) && (threadIdx.x & 63) == 0) v.imp_active[iter] = 1;
@@ -480,24 +530,8 @@ __device__ __forceinline__ void tail_body(const SolverView& v, const int4* s_tab
     };
     auto sweep = [&](TailUnit& r, int colour) {                // (k_solve_colour's loop body on requested constants and gathered bodies)
         if (!r.have) return;
-        const int b1 = r.q0.k.y, b2 = r.q0.k.z, ss = r.q0.k.w;
-        float4 B1 = r.B1, B2 = r.B2, D1 = r.D1, D2 = r.D2;
-        const float im1 = r.q0.c.y, ii1 = r.q0.c.z, im2 = r.q0.c.w, ii2 = __int_as_float(r.q0.k.x);
-        const bool st1 = (im1 == 0.f && ii1 == 0.f), st2 = (im2 == 0.f && ii2 == 0.f);
-        const float4 S1 = B1, S2 = B2, T1 = D1, T2 = D2;
-        bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
-        const bool sp_imp = DO_IMP && (st1 || st2) && static_productive_words(r.tag[0], r.tag[1], iter, colour);
-        const bool sp_disp = DO_DISP && (st1 || st2) && static_productive_words(r.tag[2], r.tag[3], iter, colour);
-        solve_one(v, r.s0, r.q0, colour, iter, DO_IMP, DO_DISP, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        if (r.s1 >= 0) {                               // a static body's record is never stored: the follower must see it untouched
-            if (st1) { B1 = S1; D1 = T1; }
-            if (st2) { B2 = S2; D2 = T2; }
-            solve_one(v, r.s1, r.q1, colour, iter, DO_IMP, DO_DISP, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        }
-        if (dirty_imp) { if (!st1) v.sb_imp[b1] = B1; if (!st2) v.sb_imp[b2] = B2; }
-        if (dirty_disp) { if (!st1) v.sb_disp[b1] = D1; if (!st2) v.sb_disp[b2] = D2; }
-        if (DO_IMP) wave_tag_update(v.sw_imp + (iter & 1) * v.nstatic, tag_imp, ss, static_word(iter, colour));
-        if (DO_DISP) wave_tag_update(v.sw_disp + (iter & 1) * v.nstatic, tag_disp, ss, static_word(iter, colour));
+        auto sp = [&](bool imp) { return imp ? static_productive_words(r.tag[0], r.tag[1], iter, colour) : static_productive_words(r.tag[2], r.tag[3], iter, colour); };
+        hbm_unit_step<DO_IMP, DO_DISP>(v, r.s0, r.q0, r.s1, r.q1, r.s1 >= 0, colour, iter, DO_DISP, r.B1, r.B2, r.D1, r.D2, sp, any_imp, any_disp);
     };
     TailUnit a{}, b{};
     request(0, a);
@@ -548,24 +582,14 @@ constexpr int PARTS_T = 256;
 //  bare `s_waitcnt lgkmcnt(0); s_barrier` between classes so that those loads stay in flight — bit-exact, and 23 us per launch
 //  against 15.)
 
-// OWN_ONE (the level-1 launch: a part there has a few dozen units): lane t owns the part's t-th unit and requests its constants
-// together with the part's bodies — one memory round trip for the whole launch instead of one per class; units beyond the lanes
-// (a part with more than PARTS_T of them) are requested in their class step as in the plain form.
-template <bool DO_IMP, bool DO_DISP, bool OWN_ONE>
-static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, PartsView pv, int iter)
+// A part's rows of the level's class tables and its bodies' state, staged in LDS (round 6: the tables read from memory in the class loop were a
+// round trip per class, and twice that in the level-1 launch, whose lanes first walk the classes to find their unit: 8.4 us for a few dozen
+// units per part); part_store writes the bodies back.  (Bodies outside [0, nb): part_first_body's level 1 starts below body 0.)
+template <bool DO_IMP, bool DO_DISP>
+__device__ __forceinline__ void part_stage(const SolverView& v, const PartsView& pv, int part, int base, int nclass, bool disp_on,
+                                           int4* s_tab, int4* s_rg, float4* s_imp, float4* s_disp)
 {
-    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
-    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
-    // (round 6: the level's rows of the class tables staged in LDS with the part's bodies — read from memory in the class loop they were a
-    //  round trip per class, and twice that in the level-1 launch, whose lanes first walk the classes to find their unit: 8.4 us for a few
-    //  dozen units per part)
-    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
-    const int part = pv.first_part + (int)blockIdx.x, tid = threadIdx.x;
-    const bool imp_on = DO_IMP;
-    const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
-    const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
-    const int base = part_first_body(part, v.nb);           // (level 1: shifted by half a part; its first part starts below body 0)
-    const int units_before = pv.part_begin[part], units_after = pv.part_begin[part + 1];
+    const int tid = threadIdx.x;
     if (tid < nclass) { s_tab[tid] = pv.class_tab[pv.c0 + tid]; s_rg[tid] = pv.ranges[(size_t)part * PARTS_CLASS_STRIDE + pv.c0 + tid]; }
     for (int i = tid; i < PART_BODIES; i += PARTS_T) {
         const int g = base + i;
@@ -573,12 +597,59 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, Pa
         if (DO_IMP) s_imp[i] = v.sb_imp[g];
         if (DO_DISP) { if (disp_on) s_disp[i] = v.sb_disp[g]; }
     }
+}
+
+template <bool DO_IMP, bool DO_DISP>
+__device__ __forceinline__ void part_store(const SolverView& v, int base, bool disp_on, const float4* s_imp, const float4* s_disp)
+{
+    for (int i = threadIdx.x; i < PART_BODIES; i += PARTS_T) {
+        const int g = base + i;
+        if (g < 0 || g >= v.nb) continue;
+        if (DO_IMP) v.sb_imp[g] = s_imp[i];
+        if (DO_DISP) { if (disp_on) v.sb_disp[g] = s_disp[i]; }
+    }
+}
+
+// The LDS unit step (k_solve_parts, parts_ahead_body): the unit's leader, then its follower (s1 >= 0), on its two bodies' state in LDS.
+// Interior units touch no static body.
+template <bool DO_IMP, bool DO_DISP>
+__device__ __forceinline__ void part_unit_step(const SolverView& v, float4* s_imp, float4* s_disp, int base, int s0, int s1, HbmJoint& q0, HbmJoint& q1,
+                                               int c, int iter, bool disp_on, bool& any_imp, bool& any_disp)
+{
+    const int b1 = (q0.k.y - base) & (PART_BODIES - 1), b2 = (q0.k.z - base) & (PART_BODIES - 1);      // (masked: a stale schedule may meet other joints, solver.h)
+    float4 B1 = make_float4(0.f, 0.f, 0.f, 0.f), B2 = B1, D1 = B1, D2 = B1;
+    if (DO_IMP) { B1 = s_imp[b1]; B2 = s_imp[b2]; }
+    if (DO_DISP) { if (disp_on) { D1 = s_disp[b1]; D2 = s_disp[b2]; } }
+    const float im1 = q0.c.y, ii1 = q0.c.z, im2 = q0.c.w, ii2 = __int_as_float(q0.k.x);
+    bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
+    solve_one(v, s0, q0, c, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+    if (s1 >= 0)
+        solve_one(v, s1, q1, c, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+    if (DO_IMP) { if (dirty_imp) { s_imp[b1] = B1; s_imp[b2] = B2; } }
+    if (DO_DISP) { if (dirty_disp) { s_disp[b1] = D1; s_disp[b2] = D2; } }
+}
+
+// The level-1 launch (a part there has a few dozen units): lane t owns the part's t-th unit and requests its constants together with the
+// part's bodies — one memory round trip for the whole launch instead of one per class; units beyond the lanes (a part with more than
+// PARTS_T of them) are requested in their class step.
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, PartsView pv, int iter)
+{
+    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
+    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
+    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
+    const int part = pv.first_part + (int)blockIdx.x, tid = threadIdx.x;
+    const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
+    const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
+    const int base = part_first_body(part, v.nb);
+    const int units_before = pv.part_begin[part], units_after = pv.part_begin[part + 1];
+    part_stage<DO_IMP, DO_DISP>(v, pv, part, base, nclass, disp_on, s_tab, s_rg, s_imp, s_disp);
     if (units_before == units_after) return;                // nothing of a partitioned component in this part
-    if (!imp_on && !disp_on) return;
+    if (!DO_IMP && !disp_on) return;
     __syncthreads();
     int own_c = -1, own_s0 = 0, own_s1 = -1;
     HbmJoint own_q0{}, own_q1{};
-    if (OWN_ONE) {
+    {
         int before = 0;
         for (int k = 0; k < nclass && own_c < 0; ++k) {
             const int4 tab = s_tab[k], rg = s_rg[k];
@@ -586,53 +657,34 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, Pa
             if (u < n) {
                 own_c = pv.c0 + k;
                 own_s0 = u < n2 ? rg.x + u : rg.z + (u - n2);
-                own_q0 = hbm_load(v, own_s0, imp_on, disp_on, false);
-                if (u < n2) { own_s1 = tab.x + tab.y + (own_s0 - tab.x); own_q1 = hbm_load(v, own_s1, imp_on, disp_on, true); }
+                own_q0 = hbm_load(v, own_s0, DO_IMP, disp_on, false);
+                if (u < n2) { own_s1 = tab.x + tab.y + (own_s0 - tab.x); own_q1 = hbm_load(v, own_s1, DO_IMP, disp_on, true); }
             }
             before += n;
         }
     }
     bool any_imp = false, any_disp = false;
-    auto sweep = [&](int s0, int s1, HbmJoint& q0, HbmJoint& q1, int c) {
-        const int b1 = (q0.k.y - base) & (PART_BODIES - 1), b2 = (q0.k.z - base) & (PART_BODIES - 1);      // (masked: a stale schedule may meet other joints, solver.h)
-        float4 B1 = make_float4(0.f, 0.f, 0.f, 0.f), B2 = B1, D1 = B1, D2 = B1;
-        if (DO_IMP) { B1 = s_imp[b1]; B2 = s_imp[b2]; }
-        if (DO_DISP) { if (disp_on) { D1 = s_disp[b1]; D2 = s_disp[b2]; } }
-        const float im1 = q0.c.y, ii1 = q0.c.z, im2 = q0.c.w, ii2 = __int_as_float(q0.k.x);
-        bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
-        solve_one(v, s0, q0, c, iter, imp_on, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        if (s1 >= 0)
-            solve_one(v, s1, q1, c, iter, imp_on, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        if (DO_IMP) { if (dirty_imp) { s_imp[b1] = B1; s_imp[b2] = B2; } }
-        if (DO_DISP) { if (dirty_disp) { s_disp[b1] = D1; s_disp[b2] = D2; } }
-    };
     int before = 0;                                         // units of the level's earlier classes in this part
     for (int k = 0; k < nclass; ++k) {
         const int c = pv.c0 + k;
         const int4 tab = s_tab[k], rg = s_rg[k];
         const int n2 = rg.y - rg.x, n = n2 + rg.w - rg.z;      // the part's units of this class: n2 with a follower, then the single ones
-        if (OWN_ONE) { if (own_c == c) sweep(own_s0, own_s1, own_q0, own_q1, c); }
-        for (int u = OWN_ONE ? max(PARTS_T - before, 0) + tid : tid; u < n; u += PARTS_T) {      // (OWN_ONE: the units no lane owns)
+        if (own_c == c) part_unit_step<DO_IMP, DO_DISP>(v, s_imp, s_disp, base, own_s0, own_s1, own_q0, own_q1, c, iter, disp_on, any_imp, any_disp);
+        for (int u = max(PARTS_T - before, 0) + tid; u < n; u += PARTS_T) {      // the units no lane owns
             const bool has2 = u < n2;
             const int s0 = has2 ? rg.x + u : rg.z + (u - n2), i = s0 - tab.x;
             const int s1 = has2 ? tab.x + tab.y + i : -1;
-            HbmJoint q0 = hbm_load(v, s0, imp_on, disp_on, false), q1{};
-            if (has2) q1 = hbm_load(v, s1, imp_on, disp_on, true);
-            sweep(s0, s1, q0, q1, c);
+            HbmJoint q0 = hbm_load(v, s0, DO_IMP, disp_on, false), q1{};
+            if (has2) q1 = hbm_load(v, s1, DO_IMP, disp_on, true);
+            part_unit_step<DO_IMP, DO_DISP>(v, s_imp, s_disp, base, s0, s1, q0, q1, c, iter, disp_on, any_imp, any_disp);
         }
         before += n;
         __syncthreads();
     }
-    for (int i = tid; i < PART_BODIES; i += PARTS_T) {
-        const int g = base + i;
-        if (g < 0 || g >= v.nb) continue;
-        if (DO_IMP) v.sb_imp[g] = s_imp[i];
-        if (DO_DISP) { if (disp_on) v.sb_disp[g] = s_disp[i]; }
-    }
+    part_store<DO_IMP, DO_DISP>(v, base, disp_on, s_imp, s_disp);
     if (DO_IMP && __any(any_imp) && (threadIdx.x & 63) == 0) v.imp_active[iter] = 1;
     if (DO_DISP && __any(any_disp) && (threadIdx.x & 63) == 0) v.disp_active[iter] = 1;
 }
-
 
 // ---- the same sweep of a level's parts with the NEXT class's constants requested a class ahead (round 6, level 0) ------------------------
 // k_solve_parts' class step was an HBM round trip: the step's loads are requested when the step begins (12 classes x ~1.6 us were the
@@ -655,13 +707,7 @@ __device__ __forceinline__ void parts_ahead_body(const SolverView& v, const Part
                                                  int base, int nclass)
 {
     const int tid = threadIdx.x;
-    for (int i = tid; i < PART_BODIES; i += PARTS_T) {
-        const int g = base + i;
-        if (g < 0 || g >= v.nb) continue;
-        if (DO_IMP) s_imp[i] = v.sb_imp[g];
-        if (DO_DISP) s_disp[i] = v.sb_disp[g];
-    }
-    __syncthreads();
+    __syncthreads();                                       // (the part's tables and bodies: staged by the kernel below)
     bool any_imp = false, any_disp = false;
     // lane t's unit of the level's k-th class: located (n2 units with a follower, then the single ones) and requested.  EVERY lane requests
     // something in every step, under no branch — a lane without a unit the class's first, a unit without a follower its leader's row, a
@@ -681,18 +727,7 @@ __device__ __forceinline__ void parts_ahead_body(const SolverView& v, const Part
         r.s0 = s0; r.s1 = has2 ? s1 : -1;
     };
     auto sweep = [&](PartUnit& r, int c) {
-        if (!r.have) return;
-        const int b1 = (r.q0.k.y - base) & (PART_BODIES - 1), b2 = (r.q0.k.z - base) & (PART_BODIES - 1);      // (masked: a stale schedule may meet other joints, solver.h)
-        float4 B1 = make_float4(0.f, 0.f, 0.f, 0.f), B2 = B1, D1 = B1, D2 = B1;
-        if (DO_IMP) { B1 = s_imp[b1]; B2 = s_imp[b2]; }
-        if (DO_DISP) { D1 = s_disp[b1]; D2 = s_disp[b2]; }
-        const float im1 = r.q0.c.y, ii1 = r.q0.c.z, im2 = r.q0.c.w, ii2 = __int_as_float(r.q0.k.x);
-        bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
-        solve_one(v, r.s0, r.q0, c, iter, DO_IMP, DO_DISP, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        if (r.s1 >= 0)
-            solve_one(v, r.s1, r.q1, c, iter, DO_IMP, DO_DISP, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
-        if (DO_IMP) { if (dirty_imp) { s_imp[b1] = B1; s_imp[b2] = B2; } }
-        if (DO_DISP) { if (dirty_disp) { s_disp[b1] = D1; s_disp[b2] = D2; } }
+        if (r.have) part_unit_step<DO_IMP, DO_DISP>(v, s_imp, s_disp, base, r.s0, r.s1, r.q0, r.q1, c, iter, DO_DISP, any_imp, any_disp);
     };
     // (ONE class ahead, two register sets taking turns.  Two ahead — three sets, 112 registers — measured slower: 17.2 against 16.3 us per
     //  launch in the settled 200k world, the plain form 19.8.)
@@ -707,12 +742,7 @@ __device__ __forceinline__ void parts_ahead_body(const SolverView& v, const Part
         sweep(b, pv.c0 + k + 1);
         parts_lds_barrier();
     }
-    for (int i = tid; i < PART_BODIES; i += PARTS_T) {
-        const int g = base + i;
-        if (g < 0 || g >= v.nb) continue;
-        if (DO_IMP) v.sb_imp[g] = s_imp[i];
-        if (DO_DISP) v.sb_disp[g] = s_disp[i];
-    }
+    part_store<DO_IMP, DO_DISP>(v, base, DO_DISP, s_imp, s_disp);
     if (DO_IMP && __any(any_imp) && (threadIdx.x & 63) == 0) v.imp_active[iter] = 1;
     if (DO_DISP && __any(any_disp) && (threadIdx.x & 63) == 0) v.disp_active[iter] = 1;
 }
@@ -723,15 +753,14 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_ahead(SolverView
     __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
     __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
     __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
-    const int part = pv.first_part + (int)blockIdx.x, tid = threadIdx.x;
+    const int part = pv.first_part + (int)blockIdx.x;
     if (pv.part_begin[part] == pv.part_begin[part + 1]) return;      // nothing of a partitioned component in this part
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
     if (!DO_IMP && !disp_on) return;
     const int base = part_first_body(part, v.nb);
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
     if (nclass <= 0) return;
-    if (tid < nclass) { s_tab[tid] = pv.class_tab[pv.c0 + tid]; s_rg[tid] = pv.ranges[(size_t)part * PARTS_CLASS_STRIDE + pv.c0 + tid]; }
-    // (the tables are published by the body's first barrier, behind its load of the part's bodies)
+    part_stage<DO_IMP, DO_DISP>(v, pv, part, base, nclass, disp_on, s_tab, s_rg, s_imp, s_disp);
     if (DO_DISP && disp_on) parts_ahead_body<DO_IMP, true>(v, pv, iter, s_imp, s_disp, s_tab, s_rg, base, nclass);
     else if (DO_IMP)        parts_ahead_body<true, false>(v, pv, iter, s_imp, s_disp, s_tab, s_rg, base, nclass);
 }
@@ -745,8 +774,7 @@ static __global__ void __launch_bounds__(PARTS_T) k_prestep_parts(SolverView v, 
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
     const int base = part_first_body(part, v.nb);
     const int units_before = pv.part_begin[part], units_after = pv.part_begin[part + 1];
-    if ((int)threadIdx.x < nclass) { s_tab[threadIdx.x] = pv.class_tab[pv.c0 + threadIdx.x]; s_rg[threadIdx.x] = pv.ranges[(size_t)part * PARTS_CLASS_STRIDE + pv.c0 + threadIdx.x]; }
-    for (int i = threadIdx.x; i < PART_BODIES; i += PARTS_T) { const int g = base + i; if (g >= 0 && g < v.nb) s_imp[i] = v.sb_imp[g]; }
+    part_stage<true, false>(v, pv, part, base, nclass, false, s_tab, s_rg, s_imp, nullptr);
     if (units_before == units_after) return;
     __syncthreads();
     for (int k = 0; k < nclass; ++k) {
@@ -765,7 +793,7 @@ static __global__ void __launch_bounds__(PARTS_T) k_prestep_parts(SolverView v, 
         }
         __syncthreads();
     }
-    for (int i = threadIdx.x; i < PART_BODIES; i += PARTS_T) { const int g = base + i; if (g >= 0 && g < v.nb) v.sb_imp[g] = s_imp[i]; }
+    part_store<true, false>(v, base, false, s_imp, nullptr);
 }
 
 // ---- FinishJoints + FinishBodies (ref: Solver.cpp:482-494, 527-547) --------------------------------

@@ -144,7 +144,7 @@ def grid_state(seed=3):
     return units_state(seed, nb, r, static=[0])
 
 
-# ---- partitioned components (k_solve_parts_ahead at level 0, k_solve_parts<OWN_ONE> at level 1) ----------------------------------------
+# ---- partitioned components (k_solve_parts_ahead at level 0, k_solve_parts at level 1) ----------------------------------------
 def unit_part(a, b, nb):
     """csrc/schedule.h unit_part restated for two dynamic bodies: the part a unit is interior to, or -1."""
     P = (nb + PART_BODIES - 1) // PART_BODIES
@@ -197,7 +197,7 @@ def level1_degrees(sizes):
 NB_PARTS = 3 * PART_BODIES + 300
 PARTS_CASES = {
     # level 0: full parts' class 0 = 256 units (every lane of k_solve_parts_ahead); level 1: a part of 256 units in all (200 + 56: every
-    # unit owned by a lane), one of 267 (200 + 57 + 10: the 257th unit in the middle of class 1, swept by OWN_ONE's loop past the owned
+    # unit owned by a lane), one of 267 (200 + 57 + 10: the 257th unit in the middle of class 1, swept by k_solve_parts' loop past the owned
     # units, and a class behind it whose `before` passes PARTS_T: the clamp max(PARTS_T - before, 0)), one of 3; the last level-0 part
     # holds 300 bodies
     "lanes_256_257": (NB_PARTS, [[200, 56], [200, 57, 10], [2, 1]], 0, 0),

@@ -126,7 +126,7 @@ def test_colour_grid_past_one_pass(oracle, built_lib):
 @pytest.mark.parametrize("iters", ITERS)
 @pytest.mark.parametrize("name", list(pe.PARTS_CASES))
 def test_parts_at_their_edges(oracle, built_lib, monkeypatch, capfd, name, iters):
-    """The partitioned-component path (csrc/solver_kernels.h k_solve_parts_ahead at level 0, k_solve_parts<OWN_ONE> at level 1, one
+    """The partitioned-component path (csrc/solver_kernels.h k_solve_parts_ahead at level 0, k_solve_parts at level 1, one
     launch per level and sweep; PARTS_CLASS_STRIDE = 64; csrc/schedule_kernels.h k_colour_parts, CP_MAXU = 3072).  Cases:
     lanes_256_257 — a body count that is not a multiple of 512 (the last level-0 part partial), level-0 classes of exactly 256 units (a
     perfect matching of a part's 512 bodies: every lane of PARTS_T = 256), level-1 parts of 256 units in all (200 + 56: every unit owned

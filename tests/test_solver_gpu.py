@@ -168,13 +168,10 @@ def test_edge_inputs(solver, oracle):
     assert st.colour_count >= 10                                          # the hub serialises its contacts
 
 
-def test_schedule_reuse_and_device_resident_path(oracle, built_lib):
-    import os
-    os.environ["PHX_GRAPHS"] = "1"                     # also exercise the optional hipGraph replay of the launch sequence
-    try:
-        solver = phyx_amd.Solver(0)
-    finally:
-        del os.environ["PHX_GRAPHS"]
+def test_schedule_reuse_and_repeated_device_resident_solves(oracle, built_lib):
+    """A cached schedule is reused on an unchanged topology, repeated solves on device-resident arrays are byte-equal to the
+    first, no launch sequence is replayed from captured graphs (graph_replay stays 0), and a changed joint list rebuilds."""
+    solver = phyx_amd.Solver(0)
     state = presolve_state(scenes.stack(10, 100), 3)
     cfg = Configuration(0, 0, 20, 20)
     gb, gj, order, offs, st1 = _device_solve(solver, state, cfg)
@@ -184,7 +181,7 @@ def test_schedule_reuse_and_device_resident_path(oracle, built_lib):
     st2 = solver.stats()
     assert st2.recoloured == 0                                            # same topology: schedule reused
     assert d_b.to_host().tobytes() == gb.tobytes() and d_j.to_host().tobytes() == gj.tobytes()
-    # third identical solve replays the captured hipGraphs and still matches
+    # repeated identical solves on the device-resident arrays still match
     import ctypes as C
     d_b2, d_j2 = phyx_amd.DeviceArray(state[0]), phyx_amd.DeviceArray(state[2])
     for rep in range(3):
@@ -193,7 +190,7 @@ def test_schedule_reuse_and_device_resident_path(oracle, built_lib):
         solver.SolveJointsDevice(d_b2, d_cp, d_j2, cfg)
         solver.synchronize()
         assert d_b2.to_host().tobytes() == gb.tobytes() and d_j2.to_host().tobytes() == gj.tobytes()
-    assert solver.stats().graph_replay == 1
+    assert solver.stats().graph_replay == 0
     # a different joint list invalidates the schedule
     state2 = (state[0], state[1], state[2][::-1].copy())
     _, _, order2, _, st3 = _device_solve(solver, state2, cfg)
