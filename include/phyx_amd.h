@@ -451,6 +451,22 @@ int  phx_world_remove_bodies(phx_world* w, const int32_t* bodies, int32_t count,
  * finite with min <= max (PHX_ERR_INVALID otherwise).  *removed (may be NULL) = how many went; remap as above.  When every body is
  * inside, nothing changes. */
 int  phx_world_remove_outside(phx_world* w, const float box[4], int32_t* removed, int32_t* remap);
+/* SPAWN BETWEEN STEPS.  Appends `count` bodies; body first + k is byte for byte the record the k-th of `count` calls of
+ * phx_world_add_body(px, py, angle, half_x, half_y) would have made (index = its position).  spawn = 5 floats per body
+ * {px, py, angle, half_x, half_y}; *first (may be NULL) receives the index of the first new body.
+ * Rules as for the edits and the removal above: between steps only (PHX_ERR_STATE); a sharded or communicator-attached world gets
+ * PHX_ERR_STATE; checked completely before anything is queued (count >= 0, no NULL array when count > 0, every value finite, both half
+ * extents > 0, the new body count within int32; PHX_ERR_INVALID otherwise, the world unchanged); an empty call is a true no-op.
+ * Before the first step (host-staged bodies) it is exactly `count` phx_world_add_body calls.  After a step it is queued on
+ * phx_world_stream(w) and returns once `spawn` may be reused: the frame is built on the host as add_body builds it, 40 bytes per body
+ * cross PCIe, and one kernel writes the records and the resident state.  Nothing of the existing world crosses PCIe, and it waits for a
+ * step in flight only where a body buffer has to grow (geometrically, keeping its contents).  The spawned bodies belong to no joint:
+ * the cached solver schedule and the broadphase's splitters stay in use. */
+int  phx_world_add_bodies(phx_world* w, const float* spawn, int32_t count, int32_t* first);
+/* the batch form of phx_world_set_body_inverse_mass: values = {inv_mass, inv_inertia} per body (0, 0 = static).  Rules as for the
+ * edits above (indices in range and distinct; values finite and >= 0), except that it changes the joint topology as the single form
+ * does: the static set is part of the solver's schedule, which is rebuilt at the next step. */
+int  phx_world_set_inverse_masses(phx_world* w, const int32_t* bodies, const float* values, int32_t count);
 /* Restore a world from what the four getters above returned (checkpoint / resume; the hand-over of bodies between the ranks of an
  * ownership-sharded world): bodies, the contact cache — manifolds with their two contact-point slots each, ref: Collider.h:57-58 —
  * and the joints with their warm-start impulses (ref: World.h:33).  The broadphase's pair set is rebuilt from the manifolds'

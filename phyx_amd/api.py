@@ -53,6 +53,14 @@ def frame_from_angle(px, py, angle):
     return np.array([px, py, math.cos(float(a)), math.sin(float(a)), math.cos(float(quarter)), math.sin(float(quarter))], dtype=np.float32)
 
 
+def pinned_inv_inertia(sx, sy):
+    """invInertia of a box pinned by invMass = 0 only (ref: main.cpp:176-177): AddBody's float formula (RigidBody.h:15-36)."""
+    sx, sy = float(sx), float(sy)
+    mass = np.float32(1e-5) * (np.float32(sx) * np.float32(sy))
+    inertia = mass * (np.float32(sx) * np.float32(sx) + np.float32(sy) * np.float32(sy))
+    return float(np.float32(1.0) / inertia)
+
+
 def _contig(a, dtype):
     a = np.asarray(a)
     if a.dtype != dtype or not a.flags["C_CONTIGUOUS"]:
@@ -563,10 +571,7 @@ class World:
             i = self.AddBody((float(scene["px"][k]), float(scene["py"][k])), float(scene["angle"][k]),
                              (float(scene["sx"][k]), float(scene["sy"][k])), bool(scene["static"][k]))
             if pinned is not None and pinned[k]:
-                sx, sy = float(scene["sx"][k]), float(scene["sy"][k])
-                mass = np.float32(1e-5) * (np.float32(sx) * np.float32(sy))
-                inertia = mass * (np.float32(sx) * np.float32(sx) + np.float32(sy) * np.float32(sy))
-                self.set_inverse_mass(i, 0.0, float(np.float32(1.0) / inertia))
+                self.set_inverse_mass(i, 0.0, pinned_inv_inertia(scene["sx"][k], scene["sy"][k]))
 
     def set_shard(self, shard, shard_count):
         check(self.L.phx_world_set_shard(self.h, shard, shard_count))
@@ -737,6 +742,55 @@ class World:
         removed = C.c_int32(0)
         check(self.L.phx_world_remove_outside(self.h, _ptr(b), C.byref(removed), _ptr(remap)))
         return removed.value, remap
+
+    # ---- spawn between steps (include/phyx_amd.h: phx_world_add_bodies / phx_world_set_inverse_masses) ----
+    def add_bodies(self, spawn):
+        """Append bodies, each exactly the record AddBody would make, on the device without a state round trip.  spawn: a (K, 5) float
+        array {px, py, angle, half_x, half_y}, or a scenes.py dict (px, py, angle, sx, sy; optional static, pinned — applied through
+        set_inverse_masses as add_scene applies them).  Returns the new bodies' indices, np.arange(first, first + K)."""
+        flags = None
+        if isinstance(spawn, dict):
+            try:
+                cols = [np.asarray(spawn[k]) for k in ("px", "py", "angle", "sx", "sy")]
+            except KeyError as e:
+                raise ValueError("add_bodies: the scene dict has no %s" % (e,))
+            if any(c.ndim != 1 or c.dtype.kind not in "iuf" for c in cols):
+                raise TypeError("add_bodies: the scene's px, py, angle, sx, sy must be 1-D numeric arrays")
+            if len({len(c) for c in cols}) != 1:
+                raise ValueError("add_bodies: the scene's px, py, angle, sx, sy differ in length")
+            k = len(cols[0])
+            static = np.asarray(spawn.get("static", np.zeros(k, dtype=bool)), dtype=bool)
+            pinned = np.asarray(spawn.get("pinned", np.zeros(k, dtype=bool)), dtype=bool)
+            if static.shape != (k,) or pinned.shape != (k,):
+                raise ValueError("add_bodies: static / pinned must have one entry per body")
+            s = np.ascontiguousarray(np.stack(cols, axis=1), dtype=np.float32) if k else np.zeros((0, 5), dtype=np.float32)
+            flags = (static, pinned)
+        else:
+            a = np.asarray(spawn)
+            if a.dtype.kind != "f":
+                raise TypeError("add_bodies: spawn must be a float array, got %s" % (a.dtype,))
+            if a.ndim != 2 or a.shape[1] != 5:
+                raise ValueError("add_bodies: spawn must have shape (K, 5) {px, py, angle, half_x, half_y}, got %s" % (a.shape,))
+            s = np.ascontiguousarray(a, dtype=np.float32)
+        first = C.c_int32(0)
+        check(self.L.phx_world_add_bodies(self.h, _ptr(s), len(s), C.byref(first)))
+        idx = np.arange(first.value, first.value + len(s), dtype=np.int64)
+        if flags is not None and (flags[0].any() or flags[1].any()):
+            static, pinned = flags
+            sel = np.flatnonzero(static | pinned)
+            vals = np.zeros((len(sel), 2), dtype=np.float32)
+            for r, k in enumerate(sel):              # (pinned after static, as add_scene applies them)
+                if pinned[k]:
+                    vals[r, 1] = pinned_inv_inertia(s[k, 3], s[k, 4])
+            self.set_inverse_masses(idx[sel], vals)
+        return idx
+
+    def set_inverse_masses(self, bodies, values):
+        """invMass, invInertia = values[k] on body bodies[k], values (K, 2) ((0, 0): static).  Like set_inverse_mass, a topology change:
+        the next step rebuilds the solver's schedule."""
+        if isinstance(bodies, (list, tuple)) and not len(bodies):
+            bodies = np.zeros(0, dtype=np.int32)
+        self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
 
     def sync(self):
         """Wait for the queued step (Update returns once the step is queued; getters synchronise on their own)."""

@@ -29,6 +29,9 @@ public:
     int erase_pairs_device(const uint2* d_pairs, int count);      // pairs already in HBM
     int reset_pairs(const uint2* pairs, int count);               // the pair set becomes exactly these (host) pairs: a world restored from a saved state
     int reset_pairs_device(const uint2* d_pairs, int count);      // ... these pairs in HBM (queued: no host wait)
+    // World only: bodies [old_n, new_n) were appended.  Their composites are new, unique values, and any splitters give the exact sort
+    // (splitter_sort.h): the next update deals the grown set into the buckets of the splitters on record, then takes new ones
+    void bodies_appended(int old_n, int new_n) { if (splitters_n_ == old_n && old_n > 0) splitters_n_ = new_n; }
     const uint2* new_pairs_device() const { return new_pairs_.p; }   // pairs emitted by the last update, in HBM
     int get_stats(phx_broadphase_stats* out);
     int new_pair_count() const { return last_new_; }
@@ -56,7 +59,8 @@ private:
     DevBuf<unsigned long long> splitters_, bucketed_;
     DevBuf<unsigned> ss_count_, ss_base_, ss_stats_;
     DevBuf<unsigned short> bucket_of_;
-    int splitters_n_ = -1;                    // body count the splitters on record were taken for
+    int splitters_n_ = -1;                    // body count the splitters on record serve: the count they were taken for, or that plus appended bodies
+    int splitters_from_ = -1;                 // the body count they were taken for (its ss_buckets are the buckets they deal into)
     bool split_unbalanced_ = false, split_sorted_ = false;
     unsigned ss_last_max_ = 0u;          // the largest bucket of the last split-sorted update (0: none above twice the stride): picks k_bucket_sort's LDS shape
     DevBuf<int> erase_count_;                 // pairs really tombstoned since the last settle_erase_check()

@@ -575,19 +575,23 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
     // The sort.  With last update's splitters on record (same body count): the two-level sort of splitter_sort.h — three launches;
     // otherwise (first update, another body count, buckets that got out of balance) the stable LSD radix sort — eleven — whose
     // gather leaves the splitters for the next update.  Both produce the reference's sorted sequence (ref: base/RadixSort.h:28-95).
+    // Bodies appended since the splitters were taken (bodies_appended; at most as many again) are dealt into the buckets of the splitters
+    // on record (`deal`); the next splitters are taken at the new count's stride all the same.
     const int buckets = ss_buckets(n);
+    const bool appended = splitters_n_ == n && splitters_from_ > 0 && splitters_from_ < n;
+    const int deal = appended ? ss_buckets(splitters_from_) : buckets;
     PHX_TRY(splitters_.reserve(SS_MAX_BUCKETS)); PHX_TRY(ss_stats_.reserve(2));
     static const bool no_split = getenv("PHX_NO_SPLIT_SORT") != nullptr;      // A/B measurements, tests
-    const bool split = !no_split && buckets <= SS_MAX_BUCKETS && (buckets == 1 || (splitters_n_ == n && !split_unbalanced_));
+    const bool split = !no_split && buckets <= SS_MAX_BUCKETS && (buckets == 1 || (splitters_n_ == n && !split_unbalanced_ && (!appended || n <= 2 * splitters_from_)));
     int src = 0;
     if (split) {
         if (!ss_count_.p) { PHX_TRY(ss_count_.reserve(2 * SS_MAX_BUCKETS)); PHX_HIP(hipMemsetAsync(ss_count_.p, 0, ss_count_.cap * sizeof(unsigned), stream_)); }
         PHX_TRY(ss_base_.reserve(SS_MAX_BUCKETS + 1)); PHX_TRY(bucket_of_.reserve(n)); PHX_TRY(bucketed_.reserve(n));
         SplitSortView sv{};
-        sv.aabb = d_bodies; sv.n = n; sv.buckets = buckets; sv.stride = ss_stride(n); sv.splitters = splitters_.p; sv.keys = keys_[0].p; sv.bucket_of = bucket_of_.p;
+        sv.aabb = d_bodies; sv.n = n; sv.buckets = deal; sv.stride = ss_stride(n); sv.splitters = splitters_.p; sv.keys = keys_[0].p; sv.bucket_of = bucket_of_.p;
         sv.count = ss_count_.p; sv.cursor = ss_count_.p + SS_MAX_BUCKETS; sv.base = ss_base_.p; sv.bucketed = bucketed_.p;
         sv.keys_out = keys_[1].p; sv.idx_out = idx_[1].p; sv.entries = entries_.p; sv.next_splitters = splitters_.p; sv.max_bucket = ss_stats_.p;
-        const int items = ss_tile_items(buckets);
+        const int items = ss_tile_items(deal);
         const dim3 tiles(div_up(n, SS_TILE_T * items));
 #define PHX_KEYS_BUCKETS(INTEGRATE, ITEMS, ...) hipLaunchKernelGGL((k_keys_buckets<INTEGRATE, ITEMS>), tiles, dim3(SS_TILE_T), 0, stream_, sv, __VA_ARGS__)
         if (prologue) {
@@ -601,8 +605,8 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
         if (items == SS_ITEMS_LARGE) hipLaunchKernelGGL((k_bucket_scatter<SS_ITEMS_LARGE>), tiles, dim3(SS_TILE_T), 0, stream_, sv);
         else hipLaunchKernelGGL((k_bucket_scatter<SS_ITEMS_SMALL>), tiles, dim3(SS_TILE_T), 0, stream_, sv);
         // (the small LDS shape while the last update's largest bucket left room: all buckets resident at once)
-        if (ss_last_max_ <= (unsigned)SS_LDS_SMALL_LIMIT) hipLaunchKernelGGL((k_bucket_sort<SS_LDS_SMALL>), dim3(buckets), dim3(SS_SORT_T), 0, stream_, sv);
-        else hipLaunchKernelGGL((k_bucket_sort<SS_LDS_RECORDS>), dim3(buckets), dim3(SS_SORT_T), 0, stream_, sv);
+        if (ss_last_max_ <= (unsigned)SS_LDS_SMALL_LIMIT) hipLaunchKernelGGL((k_bucket_sort<SS_LDS_SMALL>), dim3(deal), dim3(SS_SORT_T), 0, stream_, sv);
+        else hipLaunchKernelGGL((k_bucket_sort<SS_LDS_RECORDS>), dim3(deal), dim3(SS_SORT_T), 0, stream_, sv);
         src = 1;
     } else {
         if (prologue) hipLaunchKernelGGL((k_build_keys<true>), dim3(grid_for(n)), dim3(256), 0, stream_, d_bodies, prologue->vel, prologue->mpos, n, keys_[0].p, idx_[0].p, small_.p, 16 + 2 * STAT_SLOTS,
@@ -615,7 +619,7 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
         split_unbalanced_ = false;
     }
     sorted_ = src;
-    splitters_n_ = n;
+    splitters_n_ = n; splitters_from_ = n;
     split_sorted_ = split;
 
     // sweep: count -> scan -> emit

@@ -39,6 +39,7 @@ struct PartsView {
     const int4* class_tab;      // per class of the HBM group: {first slot, leaders, followers, leaders of the classes before}
     int first_part, parts;      // the parts of ONE level (schedule.h): a launch sweeps them, workgroup w = part first_part + w
     int c0, c1;                 // ... and that level's classes [c0, c1)
+    int nb;                     // the body count the parts were laid out for (part_first_body): the schedule's, which appended bodies do not move
 };
 constexpr int PARTS_CLASS_STRIDE = 64;      // = JP_MAX_COLOURS, the device schedule builder's class limit
 
@@ -68,6 +69,10 @@ public:
     bool prelabel_pending() const { return prelabel_pending_; }
     void build_counts(int64_t out2[2]) const { out2[0] = lite_builds_; out2[1] = full_builds_; }      // device rebuilds whose components and bins came from the manifolds (side stream) / from the joints
     int synchronize(const std::function<int()>* while_waiting = nullptr, const MailCarrier* carrier = nullptr);      // (`carrier`: Readback::wait)
+    // World only: bodies [old_nb, new_nb) were appended to the resident arrays.  They belong to no joint, so a cached schedule for old_nb
+    // bodies is the schedule of the grown world too: the per-body tables grow, nb_ and the fingerprint move to new_nb, nothing is rebuilt.
+    // (Nothing may be pending: the caller settles first.  The standalone solver keeps its nb == nb_ rule.)
+    int bodies_appended(int old_nb, int new_nb);
     int get_stats(phx_solve_stats* out);
     int get_schedule(int* order, int order_cap, int* offsets, int offsets_cap, int* ncolours);
     int set_body_state_bits(int bits);
@@ -253,11 +258,11 @@ private:
     int upload_part_tables();            // host-built schedules: part_units_ / part_class_begin_ from sched_
     bool parts_in_use() const { return !opt_.no_parts && parts_.count > 0 && sched_.hbm_interior_classes > 0; }
     int part_levels() const { return sched_.hbm_interior_classes > sched_.hbm_interior_classes0 ? 2 : 1; }
-    PartsView parts_view(int level, int nb) const
+    PartsView parts_view(int level) const
     {
-        const int P = parts_per_level(nb), ki0 = sched_.hbm_interior_classes0, ki = sched_.hbm_interior_classes;
-        return level == 0 ? PartsView{parts_.ranges.p, parts_.begin.p, parts_.class_tab.p, 0, P, 0, ki0}
-                          : PartsView{parts_.ranges.p, parts_.begin.p, parts_.class_tab.p, P, P + 1, ki0, ki};
+        const int P = parts_per_level(parts_nb_), ki0 = sched_.hbm_interior_classes0, ki = sched_.hbm_interior_classes;
+        return level == 0 ? PartsView{parts_.ranges.p, parts_.begin.p, parts_.class_tab.p, 0, P, 0, ki0, parts_nb_}
+                          : PartsView{parts_.ranges.p, parts_.begin.p, parts_.class_tab.p, P, P + 1, ki0, ki, parts_nb_};
     }
     int jp_rounds_guess_ = 0;
     long long jp_walk_entries_ = -1;      // entries the last build's colouring walk visited (-1: no build yet): few -> k_jp_walk_one
@@ -311,6 +316,7 @@ private:
     Schedule sched_;
     std::vector<int> h_static_slot_;
     int nstatic_ = 0, nb_ = 0, nj_ = 0;
+    int parts_nb_ = 0;                   // the body count the schedule was built for (nb_ moves on when bodies are appended: bodies_appended)
     int max_iters_ = 0;
     phx_solve_stats stats_{};
     bool stats_pending_ = false, have_solve_ = false;

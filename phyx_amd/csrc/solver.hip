@@ -201,7 +201,7 @@ int DeviceSolver::enqueue_pre(const BodyView& d_bodies, int nb, const phx_contac
         size_t c0 = 0;
         if (parts_in_use()) {          // the interior classes of partitioned components: one launch per level, a workgroup per part
             for (int level = 0; level < part_levels(); ++level) {
-                const PartsView pv = parts_view(level, nb);
+                const PartsView pv = parts_view(level);
                 hipLaunchKernelGGL(k_prestep_parts, dim3(pv.parts), dim3(PARTS_T), 0, stream_, v, pv);
             }
             c0 = (size_t)sched_.hbm_interior_classes;
@@ -300,7 +300,7 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
             int c0 = 0;
             if (parts_in_use()) {      // classes [0, KI) of this sweep: one launch per level (solver_kernels.h k_solve_parts)
                 for (int level = 0; level < part_levels(); ++level) {
-                    const PartsView pv = parts_view(level, v.nb);
+                    const PartsView pv = parts_view(level);
                     const dim3 g(pv.parts), b(PARTS_T);
                     with_halves(imp, disp, [&](auto I, auto D) {
                         if (level == 0)    // a part's ~1000 units, class by class, the next class's constants requested a class ahead (solver_kernels.h)
@@ -427,6 +427,22 @@ int DeviceSolver::solve_resident(const BodyView& bodies, int nb, const void* d_c
     Arrays a;
     a.view = bodies;
     return solve_common(a, nb, d_cps, ncp, d_joints, nj, cfg, topology_changed);
+}
+
+int DeviceSolver::bodies_appended(int old_nb, int new_nb)
+{
+    PHX_REQUIRE(new_nb >= old_nb && !pending_.active, "bodies_appended: bad counts, or a solve is still pending");
+    if (!sched_.valid || nb_ != old_nb || new_nb == old_nb) return PHX_OK;      // (no schedule for these bodies: the next solve builds one)
+    PHX_TRY(use_device(device_));
+    // the tables indexed by body: the HBM path's working copies (k_solve_parts stages every body of a part) and the static slots
+    PHX_TRY(hbm_.sb_imp.reserve_keep((size_t)new_nb, hbm_.sb_imp.cap, stream_)); PHX_TRY(hbm_.sb_disp.reserve_keep((size_t)new_nb, hbm_.sb_disp.cap, stream_));
+    const size_t slots = std::min<size_t>(hbm_.static_slot.cap, (size_t)old_nb);
+    PHX_TRY(hbm_.static_slot.reserve_keep((size_t)new_nb, slots, stream_));
+    PHX_HIP(hipMemsetAsync(hbm_.static_slot.p + slots, 0xFF, ((size_t)new_nb - slots) * sizeof(int), stream_));      // (-1: not static)
+    if (!h_static_slot_.empty()) h_static_slot_.resize((size_t)new_nb, -1);
+    sched_.fingerprint ^= (unsigned long long)(unsigned)nb_ ^ (unsigned)new_nb;      // (the fingerprint mixes in the body count: ensure_schedule)
+    nb_ = new_nb;
+    return PHX_OK;
 }
 
 bool DeviceSolver::same_as_pending(const Arrays& a, int nb, const void* cps, int ncp, const void* joints, int nj, const phx_config& cfg) const

@@ -72,7 +72,7 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
     //    the specification and the fallback (bins that exceed the caps, more than 64 colours, ...).
     if (device_builder) {
         bool fallback = false;
-        nb_ = nb; nj_ = nj;
+        nb_ = nb; nj_ = nj; parts_nb_ = nb;
         fp_wanted_ = have_fp ? nullptr : &fp;
         const int st = build_schedule_device(d_bodies, nb, d_joints, nj, want_islands, &fallback);
         if (st != PHX_OK) { fp_wanted_ = nullptr; return st; }
@@ -150,7 +150,7 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
     nstatic_ = 0;
     for (int i = 0; i < nb; ++i) if (is_static[i]) h_static_slot_[i] = nstatic_++;
 
-    nb_ = nb; nj_ = nj;
+    nb_ = nb; nj_ = nj; parts_nb_ = nb;
     PHX_TRY(hbm_.order.reserve(std::max(nj, 1)));
     PHX_TRY(hbm_.static_slot.reserve(std::max(nb, 1)));
     PHX_TRY(hbm_.sw.reserve(4 * (size_t)std::max(nstatic_, 1)));

@@ -641,7 +641,7 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, Pa
     const int part = pv.first_part + (int)blockIdx.x, tid = threadIdx.x;
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
-    const int base = part_first_body(part, v.nb);
+    const int base = part_first_body(part, pv.nb);
     const int units_before = pv.part_begin[part], units_after = pv.part_begin[part + 1];
     part_stage<DO_IMP, DO_DISP>(v, pv, part, base, nclass, disp_on, s_tab, s_rg, s_imp, s_disp);
     if (units_before == units_after) return;                // nothing of a partitioned component in this part
@@ -757,7 +757,7 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_ahead(SolverView
     if (pv.part_begin[part] == pv.part_begin[part + 1]) return;      // nothing of a partitioned component in this part
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
     if (!DO_IMP && !disp_on) return;
-    const int base = part_first_body(part, v.nb);
+    const int base = part_first_body(part, pv.nb);
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
     if (nclass <= 0) return;
     part_stage<DO_IMP, DO_DISP>(v, pv, part, base, nclass, disp_on, s_tab, s_rg, s_imp, s_disp);
@@ -772,7 +772,7 @@ static __global__ void __launch_bounds__(PARTS_T) k_prestep_parts(SolverView v, 
     __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];      // (the level's rows of the class tables: k_solve_parts)
     const int part = pv.first_part + (int)blockIdx.x;
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
-    const int base = part_first_body(part, v.nb);
+    const int base = part_first_body(part, pv.nb);
     const int units_before = pv.part_begin[part], units_after = pv.part_begin[part + 1];
     part_stage<true, false>(v, pv, part, base, nclass, false, s_tab, s_rg, s_imp, nullptr);
     if (units_before == units_after) return;

@@ -39,7 +39,8 @@ static inline int ss_stride(int n) { return std::max(SS_STRIDE, div_up(div_up(st
 static inline int ss_buckets(int n) { return std::max(1, div_up(n, ss_stride(n))); }
 
 struct SplitSortView {
-    const float4* aabb; int n, buckets, stride;      // stride = ss_stride(n)
+    const float4* aabb; int n, buckets, stride;      // stride = ss_stride(n), the next splitters'; buckets = what the splitters on record deal
+                                                     // into: ss_buckets(n), or fewer when bodies were appended since they were taken
     const unsigned long long* splitters;       // buckets - 1 composites, ascending (last update's records at positions SS_STRIDE, 2 SS_STRIDE, ...)
     unsigned* keys;                            // scratch: key per body
     unsigned short* bucket_of;                 // scratch: bucket per body

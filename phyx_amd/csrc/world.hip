@@ -30,6 +30,7 @@ public:
     int init();
 
     int add_body(float px, float py, float angle, float sx, float sy);
+    int add_bodies(const float* spawn, int count, int* first);      // phx_world_add_bodies
     int set_static(int body);
     int set_inverse_mass(int body, float inv_mass, float inv_inertia);
     int synchronize();
@@ -54,6 +55,7 @@ public:
     // edits and gathers between steps (phx_world_add_accelerations ... phx_world_get_poses_device)
     enum Edit { EDIT_ACCELERATIONS, EDIT_VELOCITIES, EDIT_POSES };
     int edit(Edit kind, const int* bodies, const float* values, int count);
+    int set_inverse_masses(const int* bodies, const float* values, int count);      // phx_world_set_inverse_masses
     int get_body_states(const int* bodies, int count, phx_rigid_body* out);
     int get_poses(float* out, int cap);
     int get_poses_device(void* d_out, int cap);
@@ -95,7 +97,7 @@ private:
     DeviceBroadphase& broadphase_;
     DeviceSolver& solver_;
     hipStream_t stream_ = nullptr;
-    std::vector<phx_rigid_body> host_bodies_;     // construction-time staging; the device copy is authoritative after upload
+    std::vector<phx_rigid_body> host_bodies_;     // construction-time staging; the device copy is authoritative after upload (then only its size counts)
     bool bodies_dirty_ = false;
     DevBuf<phx_rigid_body> d_bodies_;             // the records: uploaded once, refreshed from the resident arrays only when a getter asks
     DevBuf<float4> vel_, dvel_, mpos_, frame_, aabb_;      // the resident body state (body_view.h)
@@ -138,6 +140,7 @@ private:
     std::vector<DevBuf<char>> edit_dev_retired_;      // outgrown device batches a pending scatter may still read: freed with the world
     DevBuf<phx_rigid_body> gathered_;
     DevBuf<float4> poses_;
+    std::vector<float> spawn_rows_;          // add_bodies: the 10-float rows of a batch (spawn_row), staged from here
     // removal: keep flags and the exclusive scans that place the kept bodies / manifolds / joints, the counts ([0] bodies, [1] manifolds,
     // [2] joints kept, [3] kept records with an acceleration), the remap, the kept pairs; the compaction writes into the spare buffers,
     // which then change places with the world's own (the old ones are the spares of the next removal)
@@ -177,10 +180,11 @@ int World::init()
     return PHX_OK;
 }
 
-// ref: World.cpp:11-17, RigidBody.h:15-36, Coords2.h:10-17 (cos/sin resolve to the double overloads)
-int World::add_body(float px, float py, float angle, float sx, float sy)
+// ref: World.cpp:11-17, RigidBody.h:15-36, Coords2.h:10-17 (cos/sin resolve to the double overloads): the record AddBody makes (index
+// aside).  add_body and add_bodies both build from it; the frame stays on the host because the device's cos / sin are not promised to
+// round as the host's do.
+static phx_rigid_body body_record(float px, float py, float angle, float sx, float sy)
 {
-    if (!bodies_dirty_ && !host_bodies_.empty() && d_bodies_.p) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
     phx_rigid_body b;
     std::memset(&b, 0, sizeof b);
     const float pi = 3.141592f;
@@ -195,6 +199,13 @@ int World::add_body(float px, float py, float angle, float sx, float sy)
     b.inv_mass = 1.0f / mass;
     b.inv_inertia = 1.0f / inertia;
     update_geom(b);
+    return b;
+}
+
+int World::add_body(float px, float py, float angle, float sx, float sy)
+{
+    if (!bodies_dirty_ && !host_bodies_.empty() && d_bodies_.p) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
+    phx_rigid_body b = body_record(px, py, angle, sx, sy);
     b.index = (uint32_t)host_bodies_.size();
     host_bodies_.push_back(b);
     bodies_dirty_ = true;
@@ -808,11 +819,11 @@ int World::check_batch(const char* what, const int* bodies, const void* values, 
     return PHX_OK;
 }
 
-// {indices | values} in one H2D copy.  The pinned buffer is bump-allocated while earlier batches' copies are still queued (they may sit
+// {indices | values} in one H2D copy (values only when `bodies` is null).  The pinned buffer is bump-allocated while earlier batches' copies are still queued (they may sit
 // behind a step in flight) and reused from the start once stage_done_ has passed; an outgrown buffer is kept until the world goes.
 int World::stage_batch(const int* bodies, const float* values, int count, int width, const int** d_bodies, const float** d_values)
 {
-    const size_t ib = ((size_t)count * sizeof(int) + 15) & ~size_t(15), bytes = ib + (size_t)count * (size_t)width * sizeof(float);
+    const size_t ib = bodies ? ((size_t)count * sizeof(int) + 15) & ~size_t(15) : 0, bytes = ib + (size_t)count * (size_t)width * sizeof(float);
     if (!stage_done_) PHX_HIP(hipEventCreateWithFlags(&stage_done_, hipEventDisableTiming));
     else if (stage_used_) {
         const hipError_t q = hipEventQuery(stage_done_);
@@ -830,12 +841,12 @@ int World::stage_batch(const int* bodies, const float* values, int count, int wi
     }
     if (bytes > edit_dev_.cap && edit_dev_.p) edit_dev_retired_.push_back(std::move(edit_dev_));
     PHX_TRY(edit_dev_.reserve(bytes));
-    std::memcpy(stage_pin_ + off, bodies, (size_t)count * sizeof(int));
+    if (bodies) std::memcpy(stage_pin_ + off, bodies, (size_t)count * sizeof(int));
     if (width) std::memcpy(stage_pin_ + off + ib, values, bytes - ib);
     PHX_HIP(hipMemcpyAsync(edit_dev_.p, stage_pin_ + off, bytes, hipMemcpyHostToDevice, stream_));
     PHX_HIP(hipEventRecord(stage_done_, stream_));
     stage_used_ = off + bytes;
-    *d_bodies = reinterpret_cast<const int*>(edit_dev_.p);
+    *d_bodies = bodies ? reinterpret_cast<const int*>(edit_dev_.p) : nullptr;
     *d_values = reinterpret_cast<const float*>(edit_dev_.p + ib);
     return PHX_OK;
 }
@@ -1012,6 +1023,86 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     return forget_step_history();
 }
 
+// ---- spawn between steps ---------------------------------------------------------------------------------------------------------
+// Appending bodies is add_body's record, `count` times over.  Before the first step (host-staged bodies) that is literally what runs.
+// After it, the host builds each body's row from body_record — the frame and the two inverse masses, 40 bytes — and one kernel writes
+// the records and the resident state behind whatever the stream holds.  The body buffers grow geometrically, keeping their contents
+// (a buffer that grows waits for the stream once).  The new bodies are in no joint and no pair: the solver keeps its cached schedule
+// and the broadphase its splitters (DeviceSolver::bodies_appended, DeviceBroadphase::bodies_appended).
+constexpr int SPAWN_ROW = 10;      // {pos.x, pos.y, half x, half y, inv_mass, inv_inertia, xv.x, xv.y, yv.x, yv.y}
+
+int World::add_bodies(const float* spawn, int count, int* first)
+{
+    static const char* const what = "phx_world_add_bodies";
+    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world cannot spawn bodies", what); return PHX_ERR_STATE; }
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && !spawn) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    const int n = nb();
+    if ((long long)n + count > (long long)INT32_MAX) { set_error("%s: %d + %d bodies exceed the int32 range", what, n, count); return PHX_ERR_INVALID; }
+    for (int k = 0; k < count; ++k) {
+        const float* q = spawn + 5 * (size_t)k;
+        for (int c = 0; c < 5; ++c)
+            if (!std::isfinite(q[c])) { set_error("%s: body %d: value %d is not finite", what, k, c); return PHX_ERR_INVALID; }
+        if (!(q[3] > 0.f && q[4] > 0.f)) { set_error("%s: body %d: half sizes must be positive", what, k); return PHX_ERR_INVALID; }
+    }
+    if (first) *first = n;
+    if (!count) return PHX_OK;
+    if (bodies_dirty_ || !d_bodies_.p) {                                    // host-staged: exactly `count` add_body calls
+        host_bodies_.reserve((size_t)n + count);
+        for (int k = 0; k < count; ++k) { const float* q = spawn + 5 * (size_t)k; add_body(q[0], q[1], q[2], q[3], q[4]); }
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());             // (the spawn goes behind a settled solve, never under a replay)
+    spawn_rows_.resize((size_t)count * SPAWN_ROW);
+    bool any_static = false;
+    for (int k = 0; k < count; ++k) {
+        const float* q = spawn + 5 * (size_t)k;
+        const phx_rigid_body b = body_record(q[0], q[1], q[2], q[3], q[4]);
+        float* r = spawn_rows_.data() + (size_t)SPAWN_ROW * k;
+        r[0] = b.pos.x; r[1] = b.pos.y; r[2] = b.geom_size.x; r[3] = b.geom_size.y; r[4] = b.inv_mass; r[5] = b.inv_inertia;
+        r[6] = b.xvector.x; r[7] = b.xvector.y; r[8] = b.yvector.x; r[9] = b.yvector.y;
+        any_static |= b.inv_mass == 0.f && b.inv_inertia == 0.f;           // (sizes so large that the mass overflows: a static body)
+    }
+    const size_t total = (size_t)n + count;
+    PHX_TRY(d_bodies_.reserve_keep(total, n, stream_));
+    PHX_TRY(vel_.reserve_keep(total, n, stream_)); PHX_TRY(dvel_.reserve_keep(total, n, stream_)); PHX_TRY(mpos_.reserve_keep(total, n, stream_));
+    PHX_TRY(frame_.reserve_keep(total, n, stream_)); PHX_TRY(aabb_.reserve_keep(total, n, stream_)); PHX_TRY(size_.reserve_keep(total, n, stream_));
+    if (accel_pending_) PHX_TRY(accel_.reserve_keep(total, n, stream_));
+    const int* unused = nullptr; const float* d_rows = nullptr;
+    PHX_TRY(stage_batch(nullptr, spawn_rows_.data(), count, SPAWN_ROW, &unused, &d_rows));
+    hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), d_bodies_.p, accel_pending_ ? accel_.p : (float4*)nullptr);
+    PHX_HIP(hipGetLastError());
+    host_bodies_.resize(total);                                             // (only its size counts while the device copy is the world)
+    if (any_static) joints_changed_ = true;                                 // (the static set is part of the schedule)
+    PHX_TRY(solver_.bodies_appended(n, (int)total));
+    broadphase_.bodies_appended(n, (int)total);
+    return PHX_OK;
+}
+
+// body->invMass, body->invInertia of a batch (phx_world_set_inverse_masses): an edit that changes the schedule's static set
+int World::set_inverse_masses(const int* bodies, const float* values, int count)
+{
+    static const char* const what = "phx_world_set_inverse_masses";
+    PHX_TRY(check_batch(what, bodies, values, count, true));
+    for (int k = 0; k < 2 * count; ++k)
+        if (!std::isfinite(values[k]) || !(values[k] >= 0.f)) { set_error("%s: entry %d: inverse masses must be finite and >= 0", what, k / 2); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    joints_changed_ = true;                                                 // which bodies are static is part of the schedule's topology
+    if (bodies_dirty_ || !d_bodies_.p) {
+        for (int k = 0; k < count; ++k) { phx_rigid_body& b = host_bodies_[(size_t)bodies[k]]; b.inv_mass = values[2 * k]; b.inv_inertia = values[2 * k + 1]; }
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, values, count, 2, &d_bodies, &d_values));
+    hipLaunchKernelGGL(k_set_inverse_masses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, mpos_.p, d_bodies_.p);
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
 } // namespace phx
 
 // ---- C ABI ------------------------------------------------------------------------------------------------
@@ -1173,6 +1264,18 @@ int phx_world_remove_outside(phx_world* w, const float box[4], int32_t* removed,
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(box, "phx_world_remove_outside: null box");
     return w->impl.remove("phx_world_remove_outside", nullptr, 0, box, removed, remap);
+}
+
+int phx_world_add_bodies(phx_world* w, const float* spawn, int32_t count, int32_t* first)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.add_bodies(spawn, count, first);
+}
+
+int phx_world_set_inverse_masses(phx_world* w, const int32_t* bodies, const float* values, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_inverse_masses(bodies, values, count);
 }
 
 int phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,

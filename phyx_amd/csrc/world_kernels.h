@@ -119,6 +119,49 @@ static __global__ void __launch_bounds__(256) k_set_poses(const int* __restrict_
     }
 }
 
+// body->invMass = v[0], body->invInertia = v[1] (phx_world_set_inverse_masses): the resident {invMass, invInertia} and the records,
+// whose inverse masses are what the upload left there (world_record does not refresh them)
+static __global__ void __launch_bounds__(256) k_set_inverse_masses(const int* __restrict__ idx, const float* __restrict__ v, int count, float4* __restrict__ mpos,
+                                                                   phx_rigid_body* __restrict__ records)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const int i = idx[k];
+        float4 m = mpos[i];
+        m.x = v[2 * k]; m.y = v[2 * k + 1];
+        mpos[i] = m;
+        records[i].inv_mass = m.x; records[i].inv_inertia = m.y;
+    }
+}
+
+// spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
+// as AddBody does (world.hip body_record); only the AABB is computed here, by the UpdateGeom of set_poses (ref: Geom.h:79-85).  The
+// record is AddBody's byte for byte, the resident state has zero velocities, and a pending acceleration slot starts at zero.
+static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __restrict__ rows, int count, int first, WorldBodies w,
+                                                             phx_rigid_body* __restrict__ records, float4* __restrict__ accel)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const float* q = rows + 10 * (size_t)k;
+        const int i = first + k;
+        const V2 pos = v2(q[0], q[1]), size = v2(q[2], q[3]), xv = v2(q[6], q[7]), yv = v2(q[8], q[9]);
+        float4 box;
+        geom_aabb(pos, xv, yv, size, box.x, box.y, box.z, box.w);
+        phx_rigid_body b = {};
+        b.index = (uint32_t)i;
+        b.geom_size = pv(size); b.geom_xvector = pv(xv); b.geom_yvector = pv(yv); b.geom_pos = pv(pos);
+        b.aabb_min.x = box.x; b.aabb_min.y = box.y; b.aabb_max.x = box.z; b.aabb_max.y = box.w;
+        b.inv_mass = q[4]; b.inv_inertia = q[5];
+        b.xvector = pv(xv); b.yvector = pv(yv); b.pos = pv(pos);
+        records[i] = b;
+        w.s.vel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        w.s.dvel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        w.s.mpos[i] = make_float4(q[4], q[5], pos.x, pos.y);
+        w.frame[i] = make_float4(xv.x, xv.y, yv.x, yv.y);
+        w.aabb[i] = box;
+        w.size[i] = make_float2(size.x, size.y);
+        if (accel) accel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
 // IntegrateVelocity (ref: World.cpp:39-55).  The reference zeroes both accelerations at the end of every IntegrateVelocity
 // (World.cpp:49-52) and nothing on the path sets them, so the resident world carries no acceleration arrays: they are zero
 // whenever this runs — except in the FIRST step after an upload of records that came with accelerations (phx_world_set_state /
