@@ -467,6 +467,59 @@ int  phx_world_add_bodies(phx_world* w, const float* spawn, int32_t count, int32
  * edits above (indices in range and distinct; values finite and >= 0), except that it changes the joint topology as the single form
  * does: the static set is part of the solver's schedule, which is rebuilt at the next step. */
 int  phx_world_set_inverse_masses(phx_world* w, const int32_t* bodies, const float* values, int32_t count);
+/* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first.  Batched, answered on the device
+ * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
+ * its AABB {aabb_min, aabb_max} and its box {pos, xvector = xv, yvector = yv, geom_size = h (half extents)} (UpdateGeom copies the
+ * first three into geom_pos / geom_xvector / geom_yvector, ref: RigidBody.h:38-42).  Every
+ * operation below is rounded on its own (the library is built without contraction or fast math): results are exact functions of the
+ * records, pinned bit for bit by tests/query_spec.py, which states each formula as the same expression.
+ *   - AABB overlap with box q (closed): a.min.x <= q.max.x && a.max.x >= q.min.x && a.min.y <= q.max.y && a.max.y >= q.min.y (as
+ *     phx_world_remove_outside tests).  A NaN AABB overlaps nothing.
+ *   - Point p in body b iff p is inside b's AABB (closed: a.min.x <= p.x && a.max.x >= p.x && a.min.y <= p.y && a.max.y >= p.y) AND, with
+ *     dx = p.x - pos.x, dy = p.y - pos.y:  |dx*xv.x + dy*xv.y| <= h.x  &&  |dx*yv.x + dy*yv.y| <= h.y.  (The fp32 AABB does not exactly
+ *     enclose the rounded box test; with the AABB conjunct, pruning by AABBs or tree bounds can never change a result.)
+ *   - Ray {ox, oy, dx, dy, max_t}: o + t*d for t in [0, max_t], t in units of d (d need not be unit length).  The slab of one axis with
+ *     origin o, direction d and bounds [lo, hi]: if d == 0, all t when lo <= o && o <= hi, else empty (no division by zero); otherwise
+ *     a = (lo - o)/d, b = (hi - o)/d, t0 = (a <= b ? a : b), t1 = (a <= b ? b : a).  Over both axes tin = (t0x >= t0y ? t0x : t0y),
+ *     tout = (t1x <= t1y ? t1x : t1y), and the test passes iff tin <= tout && tout >= 0 && tin <= max_t.
+ *     Body b is a candidate iff its AABB has min <= max on both axes (false for a NaN AABB) and the test passes on the AABB (world
+ *     o, d, lo = aabb_min, hi = aabb_max).  The ray hits b iff the test then passes in b's frame: r = o - pos (per component),
+ *     o' = (r.x*xv.x + r.y*xv.y, r.x*yv.x + r.y*yv.y), d' = (d.x*xv.x + d.y*xv.y, d.x*yv.x + d.y*yv.y), lo = -h, hi = h.  Then
+ *       t      = (tin > 0 ? tin : 0)   (never -0);
+ *       normal = (0, 0) if tin < 0 (the origin is inside the box); otherwise the entering axis's stored vector (xv if t0x >= t0y, else
+ *                yv), negated when d' on that axis is > 0: always an exact copy or negation of stored floats;
+ *       point  = (ox + t*dx, oy + t*dy).
+ *     The closest hit is the smallest t, ties to the lowest body index.
+ * flags: PHX_QUERY_SKIP_STATIC leaves static bodies (inv_mass == 0 && inv_inertia == 0) out of every result (picking without the ground).
+ * Rules:
+ *   - Any time, like the gathers: a query sees the geometry at its point of phx_world_stream(w) (between phx_world_pre_solve and
+ *     phx_world_finish_step: the geometry before IntegratePosition); the host forms wait for it.
+ *   - Host-staged bodies (before the first step, after add_body / set_body_static / set_body_inverse_mass) are uploaded first, as the
+ *     removal uploads them.
+ *   - The host forms check all their input before anything is queued: count >= 0, no NULL array when count > 0, every value finite,
+ *     min <= max for boxes, max_t >= 0 and d != (0, 0) for rays, flags in {0, PHX_QUERY_SKIP_STATIC}; PHX_ERR_INVALID otherwise.
+ *   - The device forms cannot check values: a query with a non-finite component, a ray with max_t < 0 or d == (0, 0) matches nothing.
+ *   - An empty world and count == 0 are valid.
+ *   - Sharded worlds (replica or slab) answer from their own world, in its local indices; there is no query across ranks.
+ *   - A query changes nothing: not the records, the cached solver schedule, the broadphase's state or the next step's result.
+ * Two paths give byte-identical results: a scan of the resident arrays (few queries) and a 64-wide tree over the bodies in Morton
+ * order (batches), built by the first query after the geometry changed and kept until it changes again.  The library picks one from
+ * the kind and number of queries; PHX_QUERY_PATH=scan|index (read when the world is created; any other value makes phx_world_create
+ * return PHX_ERR_INVALID) forces one. */
+#define PHX_QUERY_SKIP_STATIC 1
+typedef struct { int32_t body; float t; phx_vec2 normal, point; } phx_ray_hit;      /* 24 B; no hit: body -1, every other field 0 */
+/* boxes: 4 floats per query {min.x, min.y, max.x, max.y}.  offsets: count + 1 entries; the hits of query q are hits[offsets[q] ..
+ * offsets[q + 1]), ascending body index; *total = offsets[count].  offsets and *total are filled even when the total exceeds hit_cap:
+ * then PHX_ERR_CAPACITY is returned and the contents of hits are unspecified.  A total beyond the int32 range also gives
+ * PHX_ERR_CAPACITY (*total is exact; offsets past the int32 range are not). */
+int  phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total);
+/* points: 2 floats per query; body[q] = the LOWEST index of a body whose box contains the point, -1 if none */
+int  phx_world_query_points(phx_world* w, const float* points, int32_t count, int32_t flags, int32_t* body);
+/* rays: 5 floats per query {ox, oy, dx, dy, max_t}; out[q] = the closest hit of ray q */
+int  phx_world_raycast(phx_world* w, const float* rays, int32_t count, int32_t flags, phx_ray_hit* out);
+/* the same two on caller-owned device memory (4-byte aligned), queued on phx_world_stream(w): no host wait, nothing over PCIe */
+int  phx_world_query_points_device(phx_world* w, const void* d_points, int32_t count, int32_t flags, void* d_body);
+int  phx_world_raycast_device(phx_world* w, const void* d_rays, int32_t count, int32_t flags, void* d_out);
 /* Restore a world from what the four getters above returned (checkpoint / resume; the hand-over of bodies between the ranks of an
  * ownership-sharded world): bodies, the contact cache — manifolds with their two contact-point slots each, ref: Collider.h:57-58 —
  * and the joints with their warm-start impulses (ref: World.h:33).  The broadphase's pair set is rebuilt from the manifolds'
@@ -521,6 +574,9 @@ int  phx_world_debug_counters(phx_world* w, int64_t out4[4]);
  * side stream while the joint list was refreshed), [1] rebuilds that took them from the joints.  The schedule is the same pure function of
  * the joints either way; PHX_NO_PRELABEL=1 forces [0] to stay 0. */
 int  phx_world_build_counts(phx_world* w, int64_t out2[2]);
+/* diagnostics of the queries: queue the build of the query index unless it is current for the world's geometry (the queries build it
+ * themselves when they take the index path); *builds (may be NULL) = how many times this world has built it */
+int  phx_world_query_index(phx_world* w, int64_t* builds);
 /* per-phase host timers cost one stream synchronisation per phase; off by default (get_phase_ms then returns the last
  * values measured while it was on) */
 int  phx_world_set_phase_timing(phx_world* w, int32_t on);

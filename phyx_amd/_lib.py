@@ -162,6 +162,12 @@ _SIGNATURES = {
     "phx_world_remove_outside": (C.c_int, [_vp, _vp, _vp, _vp]),
     "phx_world_add_bodies": (C.c_int, [_vp, _vp, _i32, _vp]),
     "phx_world_set_inverse_masses": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_query_aabb": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
+    "phx_world_query_points": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "phx_world_raycast": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "phx_world_query_points_device": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "phx_world_raycast_device": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "phx_world_query_index": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "phx_world_get_solve_stats": (C.c_int, [_vp, C.POINTER(SolveStats)]),
     "phx_world_get_broadphase_stats": (C.c_int, [_vp, C.POINTER(BroadphaseStats)]),
     "phx_world_solver": (_vp, [_vp]),

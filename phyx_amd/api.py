@@ -38,11 +38,18 @@ contact_joint_dtype = np.dtype([("contact_point_index", "<i4"), ("body1", "<i4")
 broadphase_entry_dtype = np.dtype([("minx", "<f4"), ("maxx", "<f4"), ("centery", "<f4"), ("extenty", "<f4"), ("index", "<u4")])
 sort_entry_dtype = np.dtype([("value", "<u4"), ("index", "<u4")])
 assert rigid_body_dtype.itemsize == 128 and contact_point_dtype.itemsize == 32
+ray_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,)), ("point", "<f4", (2,))])      # phx_ray_hit
+assert ray_hit_dtype.itemsize == 24
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
 
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _dev_ptr(p):
+    """A device address given as an int (a torch tensor's data_ptr()) or a ctypes pointer (DeviceBuffer.address())."""
+    return p if isinstance(p, C.c_void_p) else C.c_void_p(int(p))
 
 
 def frame_from_angle(px, py, angle):
@@ -791,6 +798,75 @@ class World:
         if isinstance(bodies, (list, tuple)) and not len(bodies):
             bodies = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
+
+    # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----
+    @staticmethod
+    def _queries(q, width, what, names):
+        if isinstance(q, (list, tuple)) and not len(q):
+            q = np.zeros((0, width), dtype=np.float32)
+        a = np.asarray(q)
+        if a.dtype.kind not in "iuf":
+            raise TypeError("%s: queries must be a numeric array, got %s" % (what, a.dtype))
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError("%s: queries must have shape (K, %d) %s, got %s" % (what, width, names, a.shape))
+        if len(a) > np.iinfo(np.int32).max:
+            raise ValueError("%s: more than 2^31 - 1 queries" % what)
+        with np.errstate(over="ignore"):
+            a = np.ascontiguousarray(a, dtype=np.float32)          # (a value beyond the float range becomes infinite: refused below)
+        if not np.isfinite(a).all():
+            raise ValueError("%s: every value must be finite" % what)
+        return a
+
+    def query_aabb(self, boxes, skip_static=False):
+        """Bodies whose AABB overlaps each closed box; boxes (K, 4) {min.x, min.y, max.x, max.y}.  Returns (offsets, hits): int32 arrays,
+        the hits of box q are hits[offsets[q]:offsets[q + 1]], ascending."""
+        b = self._queries(boxes, 4, "query_aabb", "{min.x, min.y, max.x, max.y}")
+        if ((b[:, 0] > b[:, 2]) | (b[:, 1] > b[:, 3])).any():
+            raise ValueError("query_aabb: every box must have min <= max")
+        flags = 1 if skip_static else 0
+        offsets = np.zeros(len(b) + 1, dtype=np.int32)
+        total = C.c_int64(0)
+        cap = max(1024, 4 * len(b))
+        for _ in range(2):                                         # (the second call with the size the first one reported)
+            hits = np.zeros(cap, dtype=np.int32)
+            st = self.L.phx_world_query_aabb(self.h, _ptr(b), len(b), flags, _ptr(offsets), _ptr(hits), cap, C.byref(total))
+            if st != -4 or total.value > np.iinfo(np.int32).max:
+                break
+            cap = int(total.value)
+        check(st)
+        return offsets, hits[:total.value].copy() if total.value < cap else hits
+
+    def query_points(self, points, skip_static=False):
+        """For each point (K, 2), the lowest index of a body whose box contains it, -1 if none (int32)."""
+        p = self._queries(points, 2, "query_points", "{x, y}")
+        out = np.zeros(len(p), dtype=np.int32)
+        check(self.L.phx_world_query_points(self.h, _ptr(p), len(p), 1 if skip_static else 0, _ptr(out)))
+        return out
+
+    def raycast(self, rays, skip_static=False):
+        """The closest hit of each ray (K, 5) {ox, oy, dx, dy, max_t}: a ray_hit_dtype array (body -1 and zeros: no hit)."""
+        r = self._queries(rays, 5, "raycast", "{ox, oy, dx, dy, max_t}")
+        if (r[:, 4] < 0).any():
+            raise ValueError("raycast: max_t must be >= 0")
+        if ((r[:, 2] == 0) & (r[:, 3] == 0)).any():
+            raise ValueError("raycast: a ray's direction must not be zero")
+        out = np.zeros(len(r), dtype=ray_hit_dtype)
+        check(self.L.phx_world_raycast(self.h, _ptr(r), len(r), 1 if skip_static else 0, _ptr(out)))
+        return out
+
+    def query_points_device(self, points_ptr, count, body_ptr, skip_static=False):
+        """query_points on device memory (2 floats per point in, int32 per point out), queued on the world's stream (stream_ptr())."""
+        check(self.L.phx_world_query_points_device(self.h, _dev_ptr(points_ptr), int(count), 1 if skip_static else 0, _dev_ptr(body_ptr)))
+
+    def raycast_device(self, rays_ptr, count, out_ptr, skip_static=False):
+        """raycast on device memory (5 floats per ray in, a 24-byte ray_hit_dtype record per ray out), queued on the world's stream."""
+        check(self.L.phx_world_raycast_device(self.h, _dev_ptr(rays_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
+
+    def query_index(self):
+        """Queue the build of the query index unless it is current; returns how many times this world has built it."""
+        n = C.c_int64(0)
+        check(self.L.phx_world_query_index(self.h, C.byref(n)))
+        return n.value
 
     def sync(self):
         """Wait for the queued step (Update returns once the step is queued; getters synchronise on their own)."""

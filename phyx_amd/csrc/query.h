@@ -1,0 +1,64 @@
+// query.h — the World's queries (include/phyx_amd.h, QUERIES): the host side of query_kernels.h.  The World hands over its resident
+// arrays, its body count, its geometry epoch and its stream; everything is queued on that stream.  The query index (a 64-wide tree over
+// the bodies in Morton order) is built by the first index-path query after the geometry changed and kept while the epoch stays.
+#pragma once
+
+#include "body_view.h"
+#include "device_scan.h"
+
+#include <cstdint>
+#include <vector>
+
+namespace phx {
+
+class DeviceQuery {
+public:
+    enum Path { AUTO = 0, SCAN = 1, INDEX = 2 };
+    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2 };
+    // the scan path answers batches up to this many queries of each kind, the index larger ones: the largest batch size at which
+    // tools/query_cost.py measured the scan faster at cfg 2, each call after a step so that the index pays its build (INTEGRATION.md
+    // §4b: points 2048 scan / 4096 index, rays 512 / 1024, boxes 1024 / 2048; sizes between two measured ones are not measured)
+    static constexpr int SCAN_MAX[3] = {2048, 512, 1024};
+
+    // PHX_QUERY_PATH=scan|index forces a path; PHX_QUERY_SCAN_CHUNK=q (a multiple of 64) lowers the queries per chunk of the scan path's
+    // AABB table.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
+    int configure_from_env();
+    Path choose(Kind kind, int count) const { return forced_ != AUTO ? forced_ : (count <= SCAN_MAX[kind] ? SCAN : INDEX); }
+
+    // device inputs and outputs; d_body gets -1 where no body contains the point
+    int points(const WorldBodies& w, int n, unsigned long long epoch, const float* d_pts, int count, int flags, int* d_body, hipStream_t s);
+    int rays(const WorldBodies& w, int n, unsigned long long epoch, const float* d_rays, int count, int flags, phx_ray_hit* d_out, hipStream_t s);
+    // host outputs (offsets: count + 1); waits through `rb`.  PHX_ERR_CAPACITY as phx_world_query_aabb.
+    int aabb(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
+             int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
+    // the index alone (tools/query_cost.py times it): built unless it is current
+    int ensure_index(const WorldBodies& w, int n, unsigned long long epoch, hipStream_t s);
+    int index_builds() const { return builds_; }
+
+private:
+    int scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
+                  int64_t* total, Readback& rb, hipStream_t s);
+    int index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
+                   int64_t* total, Readback& rb, hipStream_t s);
+    int offsets_from_counts(int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits);
+
+    Path forced_ = AUTO;
+    int scan_chunk_ = INT32_MAX;
+    // the index
+    bool built_ = false;
+    unsigned long long built_epoch_ = 0;
+    int built_n_ = -1, builds_ = 0;
+    int levels_ = 0, level_off_[8] = {0}, level_cnt_[8] = {0};
+    const unsigned* perm_ = nullptr;
+    DevBuf<unsigned> keys0_, vals0_, keys1_, vals1_, hist_, bounds_;
+    DevBuf<float4> nodes_;
+    ScanScratch scan_;
+    // per-call scratch
+    DevBuf<unsigned long long> ray_keys_;
+    DevBuf<unsigned> qcount_, qseg_, table_;
+    DevBuf<int> hits_;
+    DevBuf<unsigned> sort_k1_, sort_v0_, sort_v1_;
+    std::vector<unsigned> counts_;
+};
+
+} // namespace phx

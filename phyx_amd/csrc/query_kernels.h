@@ -1,0 +1,465 @@
+// query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box and the
+// closest ray hit over the resident arrays (body_view.h).  The predicates below are the header's formulas one for one, each operation
+// rounded on its own (the library is compiled with -ffp-contract=off); tests/query_spec.py states them again in numpy.
+//
+// Two paths give byte-identical results:
+//   scan   bodies in lanes, a tile of Q_TILE queries in LDS, one coalesced pass over the resident arrays per tile; points and rays
+//          reduce with atomicMin (the body index; (bits(t) << 32) | body), AABB queries count per (query, workgroup), scan, fill;
+//   index  a tree of 64-wide nodes over the bodies in Morton order (leaves: 64 consecutive sorted bodies), one wave per query: the
+//          64 lanes test one node's 64 children and __ballot picks the ones to descend into; the stack lives in LDS.
+// Pruning is exact: a node's bounds are the exact min / max of what it holds, and every test is monotonic in the box it is made
+// against (Queries), so a body that passes its own test passes every ancestor's.
+#pragma once
+
+#include "body_view.h"
+
+#include <climits>
+
+namespace phx {
+
+constexpr int Q_TILE = 64;              // queries per scan-path tile (LDS)
+constexpr int Q_FANOUT = 64;            // children per tree node: one wave's lanes
+constexpr int Q_MAX_LEVELS = 6;         // 64^6 > 2^31 bodies
+constexpr int Q_SORT_MAX = 4096;        // AABB segments up to this long are sorted in LDS by one workgroup (16 KiB)
+constexpr int Q_SKIP_STATIC = 1;        // PHX_QUERY_SKIP_STATIC
+
+struct QRay { float ox, oy, dx, dy, max_t; };
+
+// the tree: level 0 is the sorted bodies (perm), level L >= 1 holds cnt[L] nodes at nodes[off[L] ..]; node i of level L bounds
+// children 64i .. 64i + 63 of level L - 1; the root is the one node of level `levels`
+struct QTree {
+    const float4* nodes;
+    const unsigned* perm;
+    int n, levels;
+    int off[Q_MAX_LEVELS + 1], cnt[Q_MAX_LEVELS + 1];
+};
+
+// ---- the predicates (include/phyx_amd.h) ----------------------------------------------------------------------------------------
+__device__ __forceinline__ bool q_static(float4 m) { return m.x == 0.f && m.y == 0.f; }
+
+__device__ __forceinline__ bool q_overlap(float4 a, float4 q) { return a.x <= q.z && a.z >= q.x && a.y <= q.w && a.w >= q.y; }
+
+__device__ __forceinline__ bool q_point_in_box(float4 a, float4 m, float4 f, float2 h, float px, float py)
+{
+    if (!(a.x <= px && a.z >= px && a.y <= py && a.w >= py)) return false;
+    const float dx = px - m.z, dy = py - m.w;
+    const float u = dx * f.x + dy * f.y, v = dx * f.z + dy * f.w;
+    return fabsf(u) <= h.x && fabsf(v) <= h.y;
+}
+
+// one axis's slab: false when it is empty
+__device__ __forceinline__ bool q_slab(float o, float d, float lo, float hi, float& t0, float& t1)
+{
+    if (d == 0.f) { t0 = -INFINITY; t1 = INFINITY; return lo <= o && o <= hi; }
+    const float a = (lo - o) / d, b = (hi - o) / d;
+    t0 = a <= b ? a : b; t1 = a <= b ? b : a;
+    return true;
+}
+
+// the two-axis test over [0, max_t]; tin and which axis entered (x on a tie)
+__device__ __forceinline__ bool q_ray_test(float ox, float oy, float dx, float dy, float lox, float loy, float hix, float hiy, float max_t,
+                                           float& tin, bool& xenter)
+{
+    float t0x, t1x, t0y, t1y;
+    const bool sx = q_slab(ox, dx, lox, hix, t0x, t1x), sy = q_slab(oy, dy, loy, hiy, t0y, t1y);
+    if (!sx || !sy) return false;
+    xenter = t0x >= t0y;
+    tin = xenter ? t0x : t0y;
+    const float tout = t1x <= t1y ? t1x : t1y;
+    return tin <= tout && tout >= 0.f && tin <= max_t;
+}
+
+// candidate test against an AABB (a body's or a node's bounds)
+__device__ __forceinline__ bool q_ray_aabb(const QRay& r, float4 a)
+{
+    if (!(a.x <= a.z && a.y <= a.w)) return false;
+    float tin; bool xe;
+    return q_ray_test(r.ox, r.oy, r.dx, r.dy, a.x, a.y, a.z, a.w, r.max_t, tin, xe);
+}
+
+struct QRayBox { float tin, dxp, dyp; bool xenter; };
+
+// the test in the body's frame (after the candidate test)
+__device__ __forceinline__ bool q_ray_box(const QRay& r, float4 m, float4 f, float2 h, QRayBox& out)
+{
+    const float rx = r.ox - m.z, ry = r.oy - m.w;
+    const float oxp = rx * f.x + ry * f.y, oyp = rx * f.z + ry * f.w;
+    out.dxp = r.dx * f.x + r.dy * f.y;
+    out.dyp = r.dx * f.z + r.dy * f.w;
+    return q_ray_test(oxp, oyp, out.dxp, out.dyp, -h.x, -h.y, h.x, h.y, r.max_t, out.tin, out.xenter);
+}
+
+__device__ __forceinline__ unsigned long long q_ray_key(float tin, int body)
+{
+    const float t = tin > 0.f ? tin : 0.f;                       // t >= 0: its bits order like its value
+    return ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)body;
+}
+
+__device__ __forceinline__ bool q_point_ok(float px, float py) { return isfinite(px) && isfinite(py); }
+__device__ __forceinline__ bool q_ray_ok(const QRay& r)
+{
+    return isfinite(r.ox) && isfinite(r.oy) && isfinite(r.dx) && isfinite(r.dy) && isfinite(r.max_t) && r.max_t >= 0.f && (r.dx != 0.f || r.dy != 0.f);
+}
+__device__ __forceinline__ bool q_box_ok(float4 q) { return isfinite(q.x) && isfinite(q.y) && isfinite(q.z) && isfinite(q.w); }
+
+__device__ __forceinline__ QRay q_load_ray(const float* __restrict__ rays, int q)
+{
+    const float* p = rays + 5 * (size_t)q;
+    return QRay{p[0], p[1], p[2], p[3], p[4]};
+}
+
+__device__ __forceinline__ unsigned long long q_lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+
+__device__ __forceinline__ unsigned long long q_wave_min64(unsigned long long v)
+{
+    for (int s = 32; s > 0; s >>= 1) { const unsigned long long o = __shfl_xor(v, s); v = o < v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ unsigned q_wave_min(unsigned v)
+{
+    for (int s = 32; s > 0; s >>= 1) v = min(v, (unsigned)__shfl_xor(v, s));
+    return v;
+}
+__device__ __forceinline__ unsigned q_wave_sum(unsigned v)
+{
+    for (int s = 32; s > 0; s >>= 1) v += (unsigned)__shfl_xor(v, s);
+    return v;
+}
+
+// ---- small fills ------------------------------------------------------------------------------------------------------------------
+static __global__ void __launch_bounds__(256) k_qfill_u64(unsigned long long* __restrict__ p, int n, unsigned long long v)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v;
+}
+
+// the ray results from the winners' keys: the winner's test is made again, by the same code, for its normal
+static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const float* __restrict__ rays, int count,
+                                                            const unsigned long long* __restrict__ keys, phx_ray_hit* __restrict__ out)
+{
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < count; q += gridDim.x * blockDim.x) {
+        const unsigned long long k = keys[q];
+        phx_ray_hit h;
+        h.body = -1; h.t = 0.f; h.normal.x = h.normal.y = 0.f; h.point.x = h.point.y = 0.f;
+        if (k != ~0ull) {
+            const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
+            const QRay r = q_load_ray(rays, q);
+            const float4 m = w.s.mpos[b], f = w.frame[b];
+            QRayBox rb;
+            (void)q_ray_box(r, m, f, w.size[b], rb);
+            const float t = rb.tin > 0.f ? rb.tin : 0.f;
+            h.body = b; h.t = t;
+            if (!(rb.tin < 0.f)) {
+                const float nx = rb.xenter ? f.x : f.z, ny = rb.xenter ? f.y : f.w;
+                const bool flip = (rb.xenter ? rb.dxp : rb.dyp) > 0.f;
+                h.normal.x = flip ? -nx : nx; h.normal.y = flip ? -ny : ny;
+            }
+            h.point.x = r.ox + t * r.dx;
+            h.point.y = r.oy + t * r.dy;
+        }
+        out[q] = h;
+    }
+}
+
+// ---- scan path --------------------------------------------------------------------------------------------------------------------
+// blockIdx.y = the tile of queries [q0, q0 + Q_TILE); bodies grid-strided in lanes.  out: 0xFFFFFFFF (= -1) where nothing was found.
+static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int n, const float* __restrict__ pts, int count, int q0, int flags,
+                                                             unsigned* __restrict__ out)
+{
+    __shared__ float2 qp[Q_TILE];
+    __shared__ int qok[Q_TILE];
+    const int base_q = q0 + blockIdx.y * Q_TILE, nq = min(Q_TILE, count - base_q);
+    if ((int)threadIdx.x < nq) {
+        const float px = pts[2 * (size_t)(base_q + threadIdx.x)], py = pts[2 * (size_t)(base_q + threadIdx.x) + 1];
+        qp[threadIdx.x] = make_float2(px, py);
+        qok[threadIdx.x] = q_point_ok(px, py);
+    }
+    __syncthreads();
+    const bool skip = (flags & Q_SKIP_STATIC) != 0;
+    for (int base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {      // (uniform trip count: the ballots below)
+        const int i = base + threadIdx.x;
+        const bool live = i < n;
+        float4 a = make_float4(NAN, NAN, NAN, NAN), m = make_float4(0.f, 0.f, 0.f, 0.f), f = m;
+        float2 h = make_float2(0.f, 0.f);
+        if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
+        const bool any = live && !(skip && q_static(m));
+        for (int q = 0; q < nq; ++q) {
+            const float2 p = qp[q];
+            const bool hit = any && qok[q] && q_point_in_box(a, m, f, h, p.x, p.y);
+            const unsigned long long mask = __ballot(hit);
+            if (mask && (int)(threadIdx.x & 63) == __builtin_ctzll(mask)) atomicMin(&out[base_q + q], (unsigned)i);      // (the lowest lane holds the lowest body)
+        }
+    }
+}
+
+static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n, const float* __restrict__ rays, int count, int q0, int flags,
+                                                           unsigned long long* __restrict__ keys)
+{
+    __shared__ QRay qr[Q_TILE];
+    __shared__ int qok[Q_TILE];
+    const int base_q = q0 + blockIdx.y * Q_TILE, nq = min(Q_TILE, count - base_q);
+    if ((int)threadIdx.x < nq) {
+        const QRay r = q_load_ray(rays, base_q + threadIdx.x);
+        qr[threadIdx.x] = r;
+        qok[threadIdx.x] = q_ray_ok(r);
+    }
+    __syncthreads();
+    const bool skip = (flags & Q_SKIP_STATIC) != 0;
+    for (int base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {
+        const int i = base + threadIdx.x;
+        const bool live = i < n;
+        float4 a = make_float4(NAN, NAN, NAN, NAN), m = make_float4(0.f, 0.f, 0.f, 0.f), f = m;
+        float2 h = make_float2(0.f, 0.f);
+        if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
+        const bool any = live && !(skip && q_static(m));
+        for (int q = 0; q < nq; ++q) {
+            const QRay r = qr[q];
+            QRayBox rb;
+            const bool hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_box(r, m, f, h, rb);
+            if (!__ballot(hit)) continue;
+            const unsigned long long k = q_wave_min64(hit ? q_ray_key(rb.tin, i) : ~0ull);
+            if ((threadIdx.x & 63) == 0) atomicMin(&keys[base_q + q], k);
+        }
+    }
+}
+
+// AABB queries, one workgroup per 256 consecutive bodies (blockIdx.x = body block of `bblocks`), blockIdx.y = tile.
+//   QS_COUNT    writes the hit count of every (query, body block) to table[(q - q0) * bblocks + block] (query-major: its exclusive scan
+//               places the blocks' hits of a query one after the other, in body order) and adds it to qcount[q];
+//   QS_RECOUNT  the table alone (a later chunk of queries counted again: the table holds one chunk);
+//   QS_FILL     writes the hits at base + table[...] + rank.
+enum { QS_COUNT = 0, QS_RECOUNT = 1, QS_FILL = 2 };
+template <int MODE>
+static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n, const float* __restrict__ boxes, int count, int q0, int flags, int bblocks,
+                                                           unsigned* __restrict__ table, unsigned* __restrict__ qcount, unsigned base, int* __restrict__ hits)
+{
+    __shared__ float4 qb[Q_TILE];
+    __shared__ int qok[Q_TILE];
+    __shared__ unsigned long long masks[Q_TILE][4];
+    const int tile_q = blockIdx.y * Q_TILE, base_q = q0 + tile_q, nq = min(Q_TILE, count - base_q);
+    if ((int)threadIdx.x < nq) {
+        const float* p = boxes + 4 * (size_t)(base_q + threadIdx.x);
+        const float4 q = make_float4(p[0], p[1], p[2], p[3]);
+        qb[threadIdx.x] = q;
+        qok[threadIdx.x] = q_box_ok(q);
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool live = i < n;
+    const float4 a = live ? w.aabb[i] : make_float4(NAN, NAN, NAN, NAN);
+    const bool any = live && !((flags & Q_SKIP_STATIC) && q_static(w.s.mpos[live ? i : 0]));
+    unsigned long long mine = 0;
+    for (int q = 0; q < nq; ++q) {
+        const bool hit = any && qok[q] && q_overlap(a, qb[q]);
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0) masks[q][wave] = mask;
+        mine |= (unsigned long long)hit << q;
+    }
+    __syncthreads();
+    if (MODE != QS_FILL) {
+        if ((int)threadIdx.x < nq) {
+            const unsigned c = (unsigned)(__popcll(masks[threadIdx.x][0]) + __popcll(masks[threadIdx.x][1]) + __popcll(masks[threadIdx.x][2]) + __popcll(masks[threadIdx.x][3]));
+            table[(size_t)(tile_q + threadIdx.x) * bblocks + blockIdx.x] = c;
+            if (MODE == QS_COUNT && c) atomicAdd(&qcount[base_q + threadIdx.x], c);
+        }
+        return;
+    }
+    while (mine) {
+        const int q = __builtin_ctzll(mine);
+        mine &= mine - 1;
+        unsigned pos = base + table[(size_t)(tile_q + q) * bblocks + blockIdx.x] + (unsigned)__popcll(masks[q][wave] & q_lanes_below());
+        for (int v = 0; v < wave; ++v) pos += (unsigned)__popcll(masks[q][v]);
+        hits[pos] = i;
+    }
+}
+
+// ---- index path: build ------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned q_fkey(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float q_funkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+// bounds of the AABB centres (bounds = {min x, min y, max x, max y} as order keys; NaN centres left out)
+static __global__ void __launch_bounds__(256) k_qcentre_bounds(const float4* __restrict__ aabb, int n, unsigned* __restrict__ bounds)
+{
+    unsigned lx = 0xFFFFFFFFu, ly = 0xFFFFFFFFu, hx = 0u, hy = 0u;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 a = aabb[i];
+        const float cx = (a.x + a.z) * 0.5f, cy = (a.y + a.w) * 0.5f;
+        if (!(cx == cx) || !(cy == cy)) continue;
+        const unsigned kx = q_fkey(cx), ky = q_fkey(cy);
+        lx = min(lx, kx); ly = min(ly, ky); hx = max(hx, kx); hy = max(hy, ky);
+    }
+    lx = q_wave_min(lx); ly = q_wave_min(ly);
+    for (int s = 32; s > 0; s >>= 1) { hx = max(hx, (unsigned)__shfl_xor(hx, s)); hy = max(hy, (unsigned)__shfl_xor(hy, s)); }
+    if ((threadIdx.x & 63) == 0 && lx != 0xFFFFFFFFu) { atomicMin(&bounds[0], lx); atomicMin(&bounds[1], ly); atomicMax(&bounds[2], hx); atomicMax(&bounds[3], hy); }
+}
+
+__device__ __forceinline__ unsigned q_spread16(unsigned v)
+{
+    v &= 0xFFFFu;
+    v = (v | (v << 8)) & 0x00FF00FFu;
+    v = (v | (v << 4)) & 0x0F0F0F0Fu;
+    v = (v | (v << 2)) & 0x33333333u;
+    v = (v | (v << 1)) & 0x55555555u;
+    return v;
+}
+
+__device__ __forceinline__ unsigned q_quantise(float c, float lo, float hi)
+{
+    const float span = hi - lo;
+    if (!(span > 0.f)) return 0u;
+    const float s = (c - lo) / span * 65535.f;
+    return s <= 0.f ? 0u : s >= 65535.f ? 65535u : (unsigned)s;
+}
+
+// 32-bit Morton keys of the quantised centres (NaN centres: 0xFFFFFFFF, at the end); vals = the body index
+static __global__ void __launch_bounds__(256) k_qmorton(const float4* __restrict__ aabb, int n, const unsigned* __restrict__ bounds,
+                                                        unsigned* __restrict__ keys, unsigned* __restrict__ vals)
+{
+    const bool none = bounds[0] == 0xFFFFFFFFu;
+    const float lx = none ? 0.f : q_funkey(bounds[0]), ly = none ? 0.f : q_funkey(bounds[1]);
+    const float hx = none ? 0.f : q_funkey(bounds[2]), hy = none ? 0.f : q_funkey(bounds[3]);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 a = aabb[i];
+        const float cx = (a.x + a.z) * 0.5f, cy = (a.y + a.w) * 0.5f;
+        keys[i] = (!(cx == cx) || !(cy == cy)) ? 0xFFFFFFFFu : (q_spread16(q_quantise(cx, lx, hx)) | (q_spread16(q_quantise(cy, ly, hy)) << 1));
+        vals[i] = (unsigned)i;
+    }
+}
+
+// one wave per node: the exact union of its (up to) 64 children — bodies through perm (level 1) or the nodes of the level below.
+// fminf / fmaxf drop a NaN operand, so a NaN AABB widens nothing; a node of nothing but NaN AABBs stays {+inf, -inf}: it passes no test.
+static __global__ void __launch_bounds__(256) k_qnodes(const float4* __restrict__ src, const unsigned* __restrict__ perm, int src_cnt,
+                                                       float4* __restrict__ dst, int dst_cnt)
+{
+    const int node = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (node >= dst_cnt) return;
+    const int c = node * Q_FANOUT + lane;
+    float lx = INFINITY, ly = INFINITY, hx = -INFINITY, hy = -INFINITY;
+    if (c < src_cnt) {
+        const float4 a = src[perm ? perm[c] : (unsigned)c];
+        lx = a.x; ly = a.y; hx = a.z; hy = a.w;
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+        lx = fminf(lx, __shfl_xor(lx, s)); ly = fminf(ly, __shfl_xor(ly, s));
+        hx = fmaxf(hx, __shfl_xor(hx, s)); hy = fmaxf(hy, __shfl_xor(hy, s));
+    }
+    if (lane == 0) dst[node] = make_float4(lx, ly, hx, hy);
+}
+
+// ---- index path: traversal ----------------------------------------------------------------------------------------------------------
+enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3 };
+
+// one wave per query, 4 per workgroup.  A stack entry is (level << 26) | node; a popped node's 64 children are tested by the 64 lanes,
+// the passing inner nodes pushed in lane order.  Depth bound: a pop pushes at most 64 entries of the level below, so the stack never
+// holds more than (levels - 1) * 63 + 64 <= Q_MAX_LEVELS * 64 entries.
+//   QK_POINT       out_u32[q] = the lowest body index containing the point (0xFFFFFFFF: none)
+//   QK_RAY         out_key[q] = min over hits of q_ray_key (~0: none)
+//   QK_AABB_COUNT  out_u32[q] = the number of hits
+//   QK_AABB_FILL   the hits at hits[seg[q] ..], in traversal order (sorted afterwards)
+template <int KIND>
+static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, const float* __restrict__ queries, int count, int flags,
+                                                      unsigned* __restrict__ out_u32, unsigned long long* __restrict__ out_key,
+                                                      const unsigned* __restrict__ seg, int* __restrict__ hits)
+{
+    __shared__ unsigned stack_mem[4][Q_MAX_LEVELS * Q_FANOUT];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const bool skip = (flags & Q_SKIP_STATIC) != 0;
+    for (int q = blockIdx.x * 4 + wave; q < count; q += gridDim.x * 4) {      // (the whole wave: grid-strided over the queries)
+        float4 qbox = make_float4(0.f, 0.f, 0.f, 0.f);
+        QRay r{0.f, 0.f, 0.f, 0.f, 0.f};
+        bool ok;
+        if (KIND == QK_POINT) {
+            const float px = queries[2 * (size_t)q], py = queries[2 * (size_t)q + 1];
+            ok = q_point_ok(px, py);
+            qbox = make_float4(px, py, px, py);                            // (the point's closed AABB test is the overlap test with this box)
+        } else if (KIND == QK_RAY) {
+            r = q_load_ray(queries, q);
+            ok = q_ray_ok(r);
+        } else {
+            const float* p = queries + 4 * (size_t)q;
+            qbox = make_float4(p[0], p[1], p[2], p[3]);
+            ok = q_box_ok(qbox);
+        }
+        unsigned best = 0xFFFFFFFFu, n_hits = 0u, cursor = 0u;
+        unsigned long long best_key = ~0ull;
+        if (ok && t.levels > 0) {
+            volatile unsigned* st = stack_mem[wave];
+            if (lane == 0) st[0] = (unsigned)t.levels << 26;
+            __builtin_amdgcn_wave_barrier();
+            int sp = 1;
+            while (sp > 0) {
+                const unsigned e = st[--sp];
+                __builtin_amdgcn_wave_barrier();
+                const int level = (int)(e >> 26), node = (int)(e & ((1u << 26) - 1u));
+                const int c = node * Q_FANOUT + lane;
+                if (level == 1) {
+                    bool hit = false;
+                    int b = 0;
+                    if (c < t.n) {
+                        b = (int)t.perm[c];
+                        const float4 a = w.aabb[b], m = w.s.mpos[b];
+                        if (!(skip && q_static(m))) {
+                            if (KIND == QK_POINT) hit = q_point_in_box(a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
+                            else if (KIND == QK_RAY) {
+                                QRayBox rb;
+                                hit = q_ray_aabb(r, a) && q_ray_box(r, m, w.frame[b], w.size[b], rb);
+                                if (hit) { const unsigned long long k = q_ray_key(rb.tin, b); best_key = k < best_key ? k : best_key; }
+                            } else hit = q_overlap(a, qbox);
+                        }
+                    }
+                    if (KIND == QK_POINT && hit) best = min(best, (unsigned)b);
+                    if (KIND == QK_AABB_COUNT) n_hits += hit ? 1u : 0u;
+                    if (KIND == QK_AABB_FILL) {
+                        const unsigned long long mask = __ballot(hit);
+                        if (hit) hits[seg[q] + cursor + (unsigned)__popcll(mask & q_lanes_below())] = b;
+                        cursor += (unsigned)__popcll(mask);
+                    }
+                } else {
+                    bool pass = false;
+                    if (c < t.cnt[level - 1]) {
+                        const float4 nb = t.nodes[t.off[level - 1] + c];
+                        pass = KIND == QK_RAY ? q_ray_aabb(r, nb) : q_overlap(nb, qbox);
+                    }
+                    const unsigned long long mask = __ballot(pass);
+                    if (pass) st[sp + __popcll(mask & q_lanes_below())] = ((unsigned)(level - 1) << 26) | (unsigned)c;
+                    sp += __popcll(mask);
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+        if (KIND == QK_POINT) { best = q_wave_min(best); if (lane == 0) out_u32[q] = best; }
+        if (KIND == QK_RAY) { best_key = q_wave_min64(best_key); if (lane == 0) out_key[q] = best_key; }
+        if (KIND == QK_AABB_COUNT) { n_hits = q_wave_sum(n_hits); if (lane == 0) out_u32[q] = n_hits; }
+        __builtin_amdgcn_wave_barrier();                                    // (the stack is reused by the wave's next query)
+    }
+}
+
+// ascending order of each AABB segment of 2 .. Q_SORT_MAX hits: a workgroup per query (grid-strided), a bitonic sort in LDS
+static __global__ void __launch_bounds__(256) k_qsort_segments(const unsigned* __restrict__ seg, const unsigned* __restrict__ len_of, int count, int* __restrict__ hits)
+{
+    __shared__ int s[Q_SORT_MAX];
+    for (int q = blockIdx.x; q < count; q += gridDim.x) {             // (q and len are uniform over the workgroup: the barriers below)
+        const unsigned len = len_of[q];
+        if (len <= 1u || len > (unsigned)Q_SORT_MAX) continue;
+        int p = 1;
+        while (p < (int)len) p <<= 1;
+        int* h = hits + seg[q];
+        for (int i = threadIdx.x; i < p; i += blockDim.x) s[i] = i < (int)len ? h[i] : INT_MAX;
+        __syncthreads();
+        for (int k = 2; k <= p; k <<= 1)
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                for (int i = threadIdx.x; i < p; i += blockDim.x) {
+                    const int l = i ^ j;
+                    if (l > i) {
+                        const int x = s[i], y = s[l];
+                        if (((i & k) == 0) ? x > y : x < y) { s[i] = y; s[l] = x; }
+                    }
+                }
+                __syncthreads();
+            }
+        for (int i = threadIdx.x; i < (int)len; i += blockDim.x) h[i] = s[i];
+        __syncthreads();                                                    // (s is refilled for the next segment)
+    }
+}
+
+} // namespace phx

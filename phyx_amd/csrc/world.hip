@@ -12,6 +12,7 @@
 #include "handles.h"
 #include "device_scan.h"
 #include "world_kernels.h"
+#include "query.h"
 
 #include <algorithm>
 #include <chrono>
@@ -62,6 +63,14 @@ public:
     // removal between steps (phx_world_remove_bodies / phx_world_remove_outside): the listed bodies, or (`box` non-null) every body
     // whose AABB does not overlap the box
     int remove(const char* what, const int* bodies, int count, const float* box, int* removed, int* remap);
+    // queries (phx_world_query_aabb ... phx_world_raycast_device): any time, nothing changes
+    int query_aabb(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total);
+    int query_points(const float* points, int count, int flags, int32_t* body);
+    int raycast(const float* rays, int count, int flags, phx_ray_hit* out);
+    int query_points_device(const void* d_points, int count, int flags, void* d_body);
+    int raycast_device(const void* d_rays, int count, int flags, void* d_out);
+    int query_index_build();             // the query index alone, built unless current (tools/query_cost.py)
+    int query_index_builds() const { return query_.index_builds(); }
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -155,6 +164,13 @@ private:
         DevBuf<phx_contact_point> cps;
         DevBuf<phx_contact_joint> joints;
     } spare_;
+    // queries: the geometry epoch is bumped by every path that writes aabb_ (or the frames behind it) or changes the body count; the
+    // query index is current while it was built for this epoch
+    unsigned long long geom_epoch_ = 0;
+    DeviceQuery query_;
+    DevBuf<int> q_body_;
+    DevBuf<phx_ray_hit> q_hits_;
+    int query_prepare(bool host_wait);
 };
 
 World::~World()
@@ -177,7 +193,7 @@ int World::init()
     stream_ = broadphase_.stream();
     PHX_TRY(solver_.adopt_stream(stream_));
     PHX_TRY(counters_.reserve(8));
-    return PHX_OK;
+    return query_.configure_from_env();
 }
 
 // ref: World.cpp:11-17, RigidBody.h:15-36, Coords2.h:10-17 (cos/sin resolve to the double overloads): the record AddBody makes (index
@@ -257,6 +273,7 @@ int World::sync_bodies_to_device()
     PHX_HIP(hipStreamSynchronize(stream_));
     bodies_dirty_ = false;
     records_stale_ = false;
+    ++geom_epoch_;
     return PHX_OK;
 }
 
@@ -453,6 +470,7 @@ int World::solve_and_integrate(float dt, const phx_config& cfg)
 {
     { RoctxRange r("SolveJoints"); PHX_TRY(solve(cfg, false)); }
     RoctxRange r("IntegratePosition");                                      // ref: World.cpp:57-70
+    ++geom_epoch_;
     const bool pending = solver_.has_pending();
     const unsigned replays = solver_.replays();
     // (what the settle reads is final when the solve's last kernel ends, so its mailbox post goes in FRONT of the integrator and the
@@ -533,6 +551,7 @@ int World::step_end(float dt)
     { RoctxRange r("Exchange: unpack"); PHX_TRY(solver_.exchange_unpack_resident(resident().s, d_joints_.p)); }
     RoctxRange r("IntegratePosition");
     records_stale_ = true;
+    ++geom_epoch_;
     if (nb()) hipLaunchKernelGGL(k_integrate_position, dim3(wgrid(nb())), dim3(256), 0, stream_, resident(), nb(), dt, (const unsigned long long*)nullptr, 0ull, MailRide{});            // ref: World.cpp:57-70
     PHX_HIP(hipGetLastError());
     return PHX_OK;
@@ -676,6 +695,7 @@ int World::finish_step(float dt, const phx_config& cfg)
     if (phase_timing) {                                                     // (per-phase host timing: settle the solve before the integrator)
         { RoctxRange r("SolveJoints"); PHX_TRY(solve(cfg, true)); lap(6); }
         RoctxRange r("IntegratePosition");
+        ++geom_epoch_;
         if (nb()) hipLaunchKernelGGL(k_integrate_position, dim3(wgrid(nb())), dim3(256), 0, stream_, resident(), nb(), dt, (const unsigned long long*)nullptr, 0ull, MailRide{});
         PHX_HIP(hipGetLastError());
     } else PHX_TRY(solve_and_integrate(dt, cfg));
@@ -884,6 +904,7 @@ int World::edit(Edit kind, const int* bodies, const float* values, int count)
         records_stale_ = true;
     } else {
         hipLaunchKernelGGL(k_set_poses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, resident());
+        ++geom_epoch_;
         records_stale_ = true;
     }
     PHX_HIP(hipGetLastError());
@@ -1016,6 +1037,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     if (pending_accel) std::swap(accel_, spare_.accel);
     std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
     host_bodies_.resize((size_t)kept);                                      // (only its size counts while the device copy is the world)
+    ++geom_epoch_;
     records_stale_ = false;
     accel_pending_ = pending_accel && got[3] != 0;                          // (what the upload of the kept records would find)
     nm = (int)got[1]; nj = (int)got[2];
@@ -1075,6 +1097,7 @@ int World::add_bodies(const float* spawn, int count, int* first)
     hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), d_bodies_.p, accel_pending_ ? accel_.p : (float4*)nullptr);
     PHX_HIP(hipGetLastError());
     host_bodies_.resize(total);                                             // (only its size counts while the device copy is the world)
+    ++geom_epoch_;
     if (any_static) joints_changed_ = true;                                 // (the static set is part of the schedule)
     PHX_TRY(solver_.bodies_appended(n, (int)total));
     broadphase_.bodies_appended(n, (int)total);
@@ -1101,6 +1124,102 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
     hipLaunchKernelGGL(k_set_inverse_masses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, mpos_.p, d_bodies_.p);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
+}
+
+// ---- queries ------------------------------------------------------------------------------------------------------------------------
+// Answered on the world's stream from the resident arrays (query.h / query_kernels.h).  The host forms check everything first, stage the
+// queries through the world's pinned staging and wait for their results; the device forms only queue.  Nothing of the world changes:
+// the upload of host-staged bodies is the one the next step would make.
+static int query_check(const char* what, const float* v, int count, int width, int flags, bool device, const void* out)
+{
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (flags != 0 && flags != PHX_QUERY_SKIP_STATIC) { set_error("%s: flags %d (0 or PHX_QUERY_SKIP_STATIC)", what, flags); return PHX_ERR_INVALID; }
+    if (count && (!v || !out)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    if (device) return PHX_OK;
+    for (int k = 0; k < count; ++k) {
+        const float* q = v + (size_t)width * k;
+        for (int c = 0; c < width; ++c)
+            if (!std::isfinite(q[c])) { set_error("%s: query %d: value %d is not finite", what, k, c); return PHX_ERR_INVALID; }
+        if (width == 4 && !(q[0] <= q[2] && q[1] <= q[3])) { set_error("%s: box %d: min exceeds max", what, k); return PHX_ERR_INVALID; }
+        if (width == 5 && !(q[4] >= 0.f)) { set_error("%s: ray %d: max_t < 0", what, k); return PHX_ERR_INVALID; }
+        if (width == 5 && q[2] == 0.f && q[3] == 0.f) { set_error("%s: ray %d: zero direction", what, k); return PHX_ERR_INVALID; }
+    }
+    return PHX_OK;
+}
+
+int World::query_prepare(bool host_wait)
+{
+    PHX_TRY(use_device(device_));
+    if (host_wait || solver_.has_pending()) PHX_TRY(solver_.synchronize());      // (an unverified solve is settled before its results are read)
+    return sync_bodies_to_device();                                         // (host-staged bodies go up as the next step would take them)
+}
+
+int World::query_aabb(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
+{
+    static const char* const what = "phx_world_query_aabb";
+    PHX_TRY(query_check(what, boxes, count, 4, flags, false, boxes));
+    if (!offsets || !total) { set_error("%s: null offsets / total", what); return PHX_ERR_INVALID; }
+    if (hit_cap < 0 || (hit_cap > 0 && !hits)) { set_error("%s: bad hits buffer (cap %d)", what, hit_cap); return PHX_ERR_INVALID; }
+    PHX_TRY(query_prepare(true));
+    const float* d_boxes = nullptr;
+    if (count && nb()) { const int* unused = nullptr; PHX_TRY(stage_batch(nullptr, boxes, count, 4, &unused, &d_boxes)); }
+    return query_.aabb(resident(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
+}
+
+int World::query_points(const float* points, int count, int flags, int32_t* body)
+{
+    static const char* const what = "phx_world_query_points";
+    PHX_TRY(query_check(what, points, count, 2, flags, false, body));
+    if (!count) return PHX_OK;
+    PHX_TRY(query_prepare(true));
+    if (!nb()) { for (int k = 0; k < count; ++k) body[k] = -1; return PHX_OK; }
+    const int* unused = nullptr; const float* d_points = nullptr;
+    PHX_TRY(stage_batch(nullptr, points, count, 2, &unused, &d_points));
+    PHX_TRY(q_body_.reserve((size_t)count));
+    PHX_TRY(query_.points(resident(), nb(), geom_epoch_, d_points, count, flags, q_body_.p, stream_));
+    PHX_TRY(rb_.add(body, q_body_.p, (size_t)count * sizeof(int), stream_));
+    return rb_.wait(stream_);
+}
+
+int World::raycast(const float* rays, int count, int flags, phx_ray_hit* out)
+{
+    static const char* const what = "phx_world_raycast";
+    PHX_TRY(query_check(what, rays, count, 5, flags, false, out));
+    if (!count) return PHX_OK;
+    PHX_TRY(query_prepare(true));
+    if (!nb()) { std::memset(out, 0, (size_t)count * sizeof(phx_ray_hit)); for (int k = 0; k < count; ++k) out[k].body = -1; return PHX_OK; }
+    const int* unused = nullptr; const float* d_rays = nullptr;
+    PHX_TRY(stage_batch(nullptr, rays, count, 5, &unused, &d_rays));
+    PHX_TRY(q_hits_.reserve((size_t)count));
+    PHX_TRY(query_.rays(resident(), nb(), geom_epoch_, d_rays, count, flags, q_hits_.p, stream_));
+    PHX_TRY(rb_.add(out, q_hits_.p, (size_t)count * sizeof(phx_ray_hit), stream_));
+    return rb_.wait(stream_);
+}
+
+int World::query_points_device(const void* d_points, int count, int flags, void* d_body)
+{
+    static const char* const what = "phx_world_query_points_device";
+    PHX_TRY(query_check(what, static_cast<const float*>(d_points), count, 2, flags, true, d_body));
+    if (count && ((reinterpret_cast<uintptr_t>(d_points) | reinterpret_cast<uintptr_t>(d_body)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    PHX_TRY(query_prepare(false));
+    return query_.points(resident(), nb(), geom_epoch_, static_cast<const float*>(d_points), count, flags, static_cast<int*>(d_body), stream_);
+}
+
+int World::raycast_device(const void* d_rays, int count, int flags, void* d_out)
+{
+    static const char* const what = "phx_world_raycast_device";
+    PHX_TRY(query_check(what, static_cast<const float*>(d_rays), count, 5, flags, true, d_out));
+    if (count && ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    PHX_TRY(query_prepare(false));
+    return query_.rays(resident(), nb(), geom_epoch_, static_cast<const float*>(d_rays), count, flags, static_cast<phx_ray_hit*>(d_out), stream_);
+}
+
+int World::query_index_build()
+{
+    PHX_TRY(query_prepare(false));
+    return query_.ensure_index(resident(), nb(), geom_epoch_, stream_);
 }
 
 } // namespace phx
@@ -1278,6 +1397,36 @@ int phx_world_set_inverse_masses(phx_world* w, const int32_t* bodies, const floa
     return w->impl.set_inverse_masses(bodies, values, count);
 }
 
+int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_aabb(boxes, count, flags, offsets, hits, hit_cap, total);
+}
+
+int phx_world_query_points(phx_world* w, const float* points, int32_t count, int32_t flags, int32_t* body)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_points(points, count, flags, body);
+}
+
+int phx_world_raycast(phx_world* w, const float* rays, int32_t count, int32_t flags, phx_ray_hit* out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.raycast(rays, count, flags, out);
+}
+
+int phx_world_query_points_device(phx_world* w, const void* d_points, int32_t count, int32_t flags, void* d_body)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_points_device(d_points, count, flags, d_body);
+}
+
+int phx_world_raycast_device(phx_world* w, const void* d_rays, int32_t count, int32_t flags, void* d_out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.raycast_device(d_rays, count, flags, d_out);
+}
+
 int phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,
                         const phx_contact_point* contact_points, int32_t contact_point_count, const phx_contact_joint* joints, int32_t joint_count)
 {
@@ -1370,6 +1519,14 @@ int phx_world_build_counts(phx_world* w, int64_t out2[2])
 {
     PHX_REQUIRE(w && out2, "null handle / buffer");
     w->impl.solver().build_counts(out2);
+    return PHX_OK;
+}
+
+int phx_world_query_index(phx_world* w, int64_t* builds)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_TRY(w->impl.query_index_build());
+    if (builds) *builds = w->impl.query_index_builds();
     return PHX_OK;
 }
 

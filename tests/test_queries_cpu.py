@@ -1,0 +1,196 @@
+"""Queries (include/phyx_amd.h, QUERIES) without a GPU: the entry points refuse a null handle, the Python wrappers refuse bad input before
+any C call and retry a too-small AABB buffer once, the specification (tests/query_spec.py) gives the stated answers on hand-built
+boundary cases, and examples/pick.c builds and fails loudly without a device."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import query_spec as spec
+from phyx_amd.api import rigid_body_dtype
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+
+
+def test_null_handle_is_an_error(built_lib):
+    L = built_lib
+    q = np.zeros(8, dtype=np.float32)
+    out = np.zeros(8, dtype=np.int32)
+    total = C.c_int64(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    assert L.phx_world_query_aabb(None, vp(q), 1, 0, vp(out), vp(out), 4, C.byref(total)) == -1
+    assert L.phx_world_query_points(None, vp(q), 1, 0, vp(out)) == -1
+    assert L.phx_world_raycast(None, vp(q), 1, 0, vp(out)) == -1
+    assert L.phx_world_query_points_device(None, vp(q), 1, 0, vp(out)) == -1
+    assert L.phx_world_raycast_device(None, vp(q), 1, 0, vp(out)) == -1
+    assert L.phx_world_query_index(None, None) == -1
+    assert b"null handle" in L.phx_last_error()
+
+
+class _NoC:
+    """Stands in for the library: any call into C fails the test."""
+
+    def __getattr__(self, name):
+        raise AssertionError("%s was called with input the wrapper should have refused" % name)
+
+
+def _world(lib=None):
+    from phyx_amd import World
+    w = World.__new__(World)
+    w.L, w.h = lib if lib is not None else _NoC(), None
+    return w
+
+
+@pytest.mark.parametrize("boxes", [np.zeros((3, 3), dtype=np.float32), np.zeros(4, dtype=np.float32), np.zeros((2, 4, 1)),
+                                   np.array([[0, 0, np.nan, 1]]), np.array([[0, 0, np.inf, 1]]), np.array([[0, 0, 1e39, 1]]),
+                                   np.array([[1, 0, 0, 1]], dtype=np.float32), np.array([[0, 1, 1, 0]], dtype=np.float32),
+                                   np.zeros((1, 4), dtype=bool), [["a"] * 4]])
+def test_query_aabb_refuses_bad_input(boxes):
+    with pytest.raises((TypeError, ValueError)):
+        _world().query_aabb(boxes)
+
+
+@pytest.mark.parametrize("points", [np.zeros((3, 3), dtype=np.float32), np.zeros(2, dtype=np.float32), np.array([[0.0, np.nan]]),
+                                    np.array([[np.inf, 0.0]]), np.zeros((1, 2), dtype=bool), [["a", "b"]]])
+def test_query_points_refuses_bad_input(points):
+    with pytest.raises((TypeError, ValueError)):
+        _world().query_points(points)
+
+
+@pytest.mark.parametrize("rays", [np.zeros((3, 4), dtype=np.float32), np.zeros(5, dtype=np.float32), np.array([[0, 0, 1, 0, np.nan]]),
+                                  np.array([[0, 0, 1, 0, -1.0]]), np.array([[0, 0, 0, 0, 1.0]]), np.array([[0, 0, -0.0, 0, 1.0]]),
+                                  np.array([[0, np.inf, 1, 0, 1.0]]), np.zeros((1, 5), dtype=bool)])
+def test_raycast_refuses_bad_input(rays):
+    with pytest.raises((TypeError, ValueError)):
+        _world().raycast(rays)
+
+
+class _Recorder:
+    """Answers phx_world_query_aabb: PHX_ERR_CAPACITY with the total while the cap is short, then the hits."""
+
+    def __init__(self, counts):
+        self.counts, self.caps, self.flags = counts, [], []
+
+    def phx_world_query_aabb(self, h, boxes, count, flags, offsets, hits, cap, total):
+        self.caps.append(cap); self.flags.append(flags)
+        off = np.ctypeslib.as_array(C.cast(offsets, C.POINTER(C.c_int32)), shape=(count + 1,))
+        off[:] = np.concatenate([[0], np.cumsum(self.counts)])
+        C.cast(total, C.POINTER(C.c_int64))[0] = int(off[-1])
+        if off[-1] > cap:
+            return -4
+        out = np.ctypeslib.as_array(C.cast(hits, C.POINTER(C.c_int32)), shape=(cap,))
+        out[:off[-1]] = np.arange(off[-1])
+        return 0
+
+
+def test_query_aabb_retries_once_with_the_reported_total():
+    rec = _Recorder([3000, 0, 2])
+    offsets, hits = _world(rec).query_aabb(np.zeros((3, 4), dtype=np.float32), skip_static=True)
+    assert rec.caps == [1024, 3002] and rec.flags == [1, 1]
+    assert offsets.tolist() == [0, 3000, 3000, 3002] and hits.tolist() == list(range(3002))
+    rec = _Recorder([5])
+    offsets, hits = _world(rec).query_aabb([[0, 0, 1, 1]])
+    assert rec.caps == [1024] and rec.flags == [0] and hits.tolist() == list(range(5))
+
+
+# ---- the specification on hand-built cases ------------------------------------------------------------------------------------------
+def _bodies(*boxes, static=()):
+    """Axis-aligned boxes (px, py, hx, hy): frame (1, 0), (0, 1); the AABB is pos -/+ h, exact."""
+    b = np.zeros(len(boxes), dtype=rigid_body_dtype)
+    for i, (px, py, hx, hy) in enumerate(boxes):
+        b[i]["index"] = i
+        b[i]["pos"] = b[i]["geom_pos"] = (px, py)
+        b[i]["xv"] = b[i]["geom_xv"] = (1, 0)
+        b[i]["yv"] = b[i]["geom_yv"] = (0, 1)
+        b[i]["geom_size"] = (hx, hy)
+        b[i]["aabb_min"] = (F(px) - F(hx), F(py) - F(hy))
+        b[i]["aabb_max"] = (F(px) + F(hx), F(py) + F(hy))
+        b[i]["inv_mass"], b[i]["inv_inertia"] = (0, 0) if i in static else (1, 1)
+    return b
+
+
+def _bits(x):
+    return np.asarray(x, dtype=np.float32).view(np.uint32).tolist()
+
+
+def test_spec_axis_parallel_ray_with_a_zero_local_component():
+    b = _bodies((0, 0, 1, 1))
+    h = spec.raycast(b, [[-10, 0.5, 1, 0, 100]])[0]      # d' = (1, 0): the y slab is all of t (|o'.y| = 0.5 <= 1)
+    assert h["body"] == 0 and h["t"] == 9
+    assert _bits(h["normal"]) == _bits([-1.0, -0.0])    # -xv, an exact negation (of +0 too)
+    assert h["point"].tolist() == [-1.0, 0.5]
+    assert spec.raycast(b, [[-10, 1.5, 1, 0, 100]])[0]["body"] == -1      # outside the y slab: empty
+    assert spec.raycast(b, [[-10, 0.5, 1, 0, 8.5]])[0]["body"] == -1      # max_t short of the box
+
+
+def test_spec_ray_starting_inside():
+    h = spec.raycast(_bodies((0, 0, 1, 1)), [[0.25, -0.5, 0, 3, 10]])[0]
+    assert h["body"] == 0 and _bits(h["t"]) == _bits(0.0)
+    assert _bits(h["normal"]) == _bits([0.0, 0.0]) and h["point"].tolist() == [0.25, -0.5]
+
+
+def test_spec_grazing_ray_and_corner_hit():
+    b = _bodies((0, 0, 1, 1))
+    h = spec.raycast(b, [[-10, 1, 1, 0, 100]])[0]         # along the top edge: the closed slab keeps it
+    assert h["body"] == 0 and h["t"] == 9 and h["point"].tolist() == [-1.0, 1.0]
+    assert spec.raycast(b, [[-10, np.nextafter(F(1), F(2)), 1, 0, 100]])[0]["body"] == -1
+    h = spec.raycast(b, [[-3, -3, 1, 1, 100]])[0]         # aimed at the corner: both axes enter at t = 2, the tie goes to x
+    assert h["body"] == 0 and h["t"] == 2
+    assert _bits(h["normal"]) == _bits([-1.0, -0.0]) and h["point"].tolist() == [-1.0, -1.0]
+    h = spec.raycast(b, [[3, 3, -2, -1, 100]])[0]         # y enters later: the normal is +yv (d'.y < 0)
+    assert h["body"] == 0 and h["t"] == 2 and _bits(h["normal"]) == _bits([0.0, 1.0])
+
+
+def test_spec_points_on_boundaries():
+    b = _bodies((0, 0, 1, 1))
+    assert spec.query_points(b, [[1, 0.3], [1, 1], [-1, -1], [0, 0]]).tolist() == [0, 0, 0, 0]
+    assert spec.query_points(b, [[np.nextafter(F(1), F(2)), 0], [0, -1.0000001]]).tolist() == [-1, -1]
+
+
+def test_spec_identical_bodies_lowest_index_wins():
+    b = _bodies((5, 5, 2, 1), (0, 0, 1, 1), (0, 0, 1, 1))
+    assert spec.query_points(b, [[0.5, 0.5]]).tolist() == [1]
+    assert spec.raycast(b, [[-5, 0, 1, 0, 10]])["body"].tolist() == [1]
+    off, hits = spec.query_aabb(b, [[-0.5, -0.5, 0.5, 0.5], [-10, -10, 10, 10], [1, 1, 3, 4]])
+    assert off.tolist() == [0, 2, 5, 8] and hits.tolist() == [1, 2, 0, 1, 2, 0, 1, 2]     # closed: touching at (1, 1) / (3, 4) counts
+
+
+def test_spec_skip_static():
+    b = _bodies((0, 0, 10, 10), (0, 0, 1, 1), static=(0,))
+    assert spec.query_points(b, [[0, 0], [5, 5]]).tolist() == [0, 0]
+    assert spec.query_points(b, [[0, 0], [5, 5]], skip_static=True).tolist() == [1, -1]
+    assert spec.raycast(b, [[-20, 0, 1, 0, 100]], skip_static=True)["body"].tolist() == [1]
+    assert spec.query_aabb(b, [[-2, -2, 2, 2]], skip_static=True)[1].tolist() == [1]
+
+
+def test_spec_nan_aabb_matches_nothing():
+    b = _bodies((0, 0, 1, 1), (0, 0, 1, 1))
+    b[0]["aabb_min"] = (np.nan, 0)
+    assert spec.query_points(b, [[0, 0]]).tolist() == [1]
+    assert spec.raycast(b, [[-5, 0, 1, 0, 10]])["body"].tolist() == [1]
+    assert spec.query_aabb(b, [[-5, -5, 5, 5]])[1].tolist() == [1]
+
+
+def test_spec_device_form_rules():
+    b = _bodies((0, 0, 1, 1))
+    assert spec.query_points(b, [[np.nan, 0], [0, np.inf]]).tolist() == [-1, -1]
+    assert spec.raycast(b, [[-5, 0, 0, 0, 10], [-5, 0, 1, 0, -1], [-5, 0, np.nan, 0, 10]])["body"].tolist() == [-1, -1, -1]
+
+
+def test_pick_example_compiles_and_fails_loudly_without_a_gpu(tmp_path, built_lib):
+    import phyx_amd
+    exe = str(tmp_path / "pick")
+    lib_dir = os.path.join(ROOT, "phyx_amd")
+    subprocess.check_call(["gcc", "-std=gnu11", "-O2", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "examples", "pick.c"), "-L" + lib_dir, "-lphyx_amd", "-Wl,-rpath," + lib_dir, "-lm", "-o", exe])
+    try:
+        have_gpu = phyx_amd.device_count() > 0
+    except phyx_amd.PhxError:
+        have_gpu = False
+    if have_gpu:
+        pytest.skip("a GPU is present: covered by the gpu test")
+    r = subprocess.run([exe, "10"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 3 and "no CPU fallback" in r.stderr
