@@ -520,6 +520,62 @@ int  phx_world_raycast(phx_world* w, const float* rays, int32_t count, int32_t f
 /* the same two on caller-owned device memory (4-byte aligned), queued on phx_world_stream(w): no host wait, nothing over PCIe */
 int  phx_world_query_points_device(phx_world* w, const void* d_points, int32_t count, int32_t flags, void* d_body);
 int  phx_world_raycast_device(phx_world* w, const void* d_rays, int32_t count, int32_t flags, void* d_out);
+/* CONTACTS — what touches what, and how hard.  Answered on the device from the resident contact cache; nothing of the world crosses
+ * PCIe but the answers.  Write s for the state the four getters would return at the call: bodies, manifolds, contact points (cps) and
+ * joints.  A manifold m's live slots are k in [0, m.point_count); slot k is contact point cps[m.point_index + k].
+ *   - Contacts of body b: one record per live slot k of every manifold m with m.body1 == b or m.body2 == b, cp = cps[m.point_index + k]:
+ *       other    = the manifold's other body;   manifold = m's index in phx_world_get_manifolds();   slot = k;
+ *       point    = pos_b + delta_b, per component in fp32 (bodies[b].pos plus cp.delta1 if b is body1, cp.delta2 if b is body2; the
+ *                  reference's demo draws contact points so, ref: main.cpp:405/411);
+ *       normal   = cp.normal if b is body1, its exact negation if b is body2.  The stored normal is the contact axis turned so that
+ *                  dot(normal, pos1 - pos2) >= 0 when the point was generated (ref: Collider.cpp GenerateContacts): it points from body2
+ *                  towards body1.  So the record's normal points from `other` towards b: the direction the contact pushes b;
+ *       normal_impulse, friction_impulse = joints[cp.solver_index]'s accumulated impulses as stored; if solver_index is outside
+ *                  [0, joint count) both are 0 and PHX_CONTACT_NO_JOINT is set (set_state does not rule that out);
+ *       flags    = PHX_CONTACT_NEW if cp.is_newly_created != 0, | PHX_CONTACT_NO_JOINT as above.
+ *     Records are ordered by (other, manifold, slot) ascending; the order does not depend on where PackManifolds moved a manifold.
+ *     flags PHX_QUERY_SKIP_STATIC leaves out records whose `other` is static (inv_mass == 0 && inv_inertia == 0, as for the queries).
+ *     Output as phx_world_query_aabb: offsets has count + 1 entries, body q's records are out[offsets[q] .. offsets[q + 1]), *total =
+ *     offsets[count]; offsets and *total are filled even when the total exceeds cap, which returns PHX_ERR_CAPACITY with the contents of
+ *     out unspecified.  A body may be listed more than once: each listing has its own segment.
+ *   - Touch events: the touching set T(s) = {(m.body1, m.body2) : m.point_count > 0}, a set of pairs.  The world keeps a baseline B,
+ *     empty when the world is created.  phx_world_contact_events returns begin = T(s) \ B and end = B \ T(s), each as {body1, body2}
+ *     int32 pairs sorted ascending by (body1, body2), then sets B := T(s).  The semantics are "since the last call": call it once per
+ *     step for per-step events; a pair that began and ended between two calls reports nothing.  If either list exceeds its cap, both
+ *     totals are still filled, PHX_ERR_CAPACITY is returned and B is NOT advanced (a retry with bigger buffers returns the same events).
+ *     What the other calls do to B: a removal remaps it through new[] and drops the pairs with a removed body (new[] is monotonic: B
+ *     stays sorted); spawns, edits and set_inverse_masses leave it alone; phx_world_set_state sets B := T(restored state) (a world saved
+ *     right after its events call and restored elsewhere reports the same later events); a sharded or communicator-attached world
+ *     refuses the events call with PHX_ERR_STATE (a re-slab renumbers bodies).
+ *   - Markers (the demo's contact view, ref: main.cpp:393-413): 2 * manifold count records into caller device memory, record i for
+ *     contact point i (the slots of manifold i / 2): a live slot has point1 = pos1 + delta1, point2 = pos2 + delta2 (fp32, per
+ *     component), live = 1, newly_created = cp.is_newly_created; a dead slot is all zero bytes.  Queued on phx_world_stream(w) with no
+ *     host wait; the buffer must be 8-byte aligned; cap (records) < 2 * manifold count gives PHX_ERR_CAPACITY.
+ * Rules, the same for all three:
+ *   - Between steps only: inside phx_world_pre_solve .. phx_world_finish_step or phx_world_step_begin .. phx_world_step_end they return
+ *     PHX_ERR_STATE (the manifolds are mid-update there).
+ *   - A pending speculative solve is settled before the joints are read, and host-staged bodies are uploaded first, as for the queries.
+ *   - All host input is checked before anything is queued: every body index in [0, body count), count >= 0, no NULL array where one is
+ *     needed, caps >= 0, flags in {0, PHX_QUERY_SKIP_STATIC}; PHX_ERR_INVALID otherwise, and nothing changes.
+ *   - Contacts and markers of a sharded world answer from the rank's own world, exactly what its getters would return.
+ *   - None of them changes the records, the cached schedule, the broadphase or the next step's result; the events call changes B only.
+ * Contacts have two paths with byte-identical results: a scan of the manifolds per chunk of listed bodies (few bodies) and a body ->
+ * (other, manifold) incidence in CSR form (batches), built by the first call after the contact cache changed and kept until it changes
+ * again (a step, a removal, set_state, a change of the body count).  point, normal and the impulses are read at the call.  The library
+ * picks a path from the number of listed bodies; PHX_CONTACT_PATH=scan|index (read when the world is created; any other value makes
+ * phx_world_create return PHX_ERR_INVALID) forces one. */
+#define PHX_CONTACT_NEW 1
+#define PHX_CONTACT_NO_JOINT 2
+typedef struct {
+    int32_t  other, manifold, slot, flags;
+    phx_vec2 point, normal;
+    float    normal_impulse, friction_impulse;
+} phx_contact;                                                                  /* 40 B */
+typedef struct { phx_vec2 point1, point2; int32_t live, newly_created; } phx_contact_marker;   /* 24 B */
+int  phx_world_query_contacts(phx_world* w, const int32_t* bodies, int32_t count, int32_t flags, int32_t* offsets, phx_contact* out, int32_t cap, int64_t* total);
+/* begin / end: 2 int32 per pair; caps in pairs; *begin_total / *end_total: the numbers of pairs */
+int  phx_world_contact_events(phx_world* w, int32_t* begin, int32_t begin_cap, int64_t* begin_total, int32_t* end, int32_t end_cap, int64_t* end_total);
+int  phx_world_get_contact_markers_device(phx_world* w, void* d_out, int32_t cap);
 /* Restore a world from what the four getters above returned (checkpoint / resume; the hand-over of bodies between the ranks of an
  * ownership-sharded world): bodies, the contact cache — manifolds with their two contact-point slots each, ref: Collider.h:57-58 —
  * and the joints with their warm-start impulses (ref: World.h:33).  The broadphase's pair set is rebuilt from the manifolds'
@@ -577,6 +633,10 @@ int  phx_world_build_counts(phx_world* w, int64_t out2[2]);
 /* diagnostics of the queries: queue the build of the query index unless it is current for the world's geometry (the queries build it
  * themselves when they take the index path); *builds (may be NULL) = how many times this world has built it */
 int  phx_world_query_index(phx_world* w, int64_t* builds);
+/* diagnostics of the contacts: queue the build of the contact incidence unless it is current for the world's contact cache (the
+ * contacts build it themselves when they take the index path); *builds (may be NULL) = how many times this world has built it.
+ * Between steps only, as the contacts. */
+int  phx_world_contact_index(phx_world* w, int64_t* builds);
 /* per-phase host timers cost one stream synchronisation per phase; off by default (get_phase_ms then returns the last
  * values measured while it was on) */
 int  phx_world_set_phase_timing(phx_world* w, int32_t on);

@@ -168,6 +168,10 @@ _SIGNATURES = {
     "phx_world_query_points_device": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_raycast_device": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_query_index": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "phx_world_query_contacts": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
+    "phx_world_contact_events": (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int64), _vp, _i32, C.POINTER(C.c_int64)]),
+    "phx_world_get_contact_markers_device": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_contact_index": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "phx_world_get_solve_stats": (C.c_int, [_vp, C.POINTER(SolveStats)]),
     "phx_world_get_broadphase_stats": (C.c_int, [_vp, C.POINTER(BroadphaseStats)]),
     "phx_world_solver": (_vp, [_vp]),

@@ -40,6 +40,11 @@ sort_entry_dtype = np.dtype([("value", "<u4"), ("index", "<u4")])
 assert rigid_body_dtype.itemsize == 128 and contact_point_dtype.itemsize == 32
 ray_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,)), ("point", "<f4", (2,))])      # phx_ray_hit
 assert ray_hit_dtype.itemsize == 24
+contact_dtype = np.dtype([("other", "<i4"), ("manifold", "<i4"), ("slot", "<i4"), ("flags", "<i4"), ("point", "<f4", (2,)), ("normal", "<f4", (2,)),
+                          ("normal_impulse", "<f4"), ("friction_impulse", "<f4")])                                     # phx_contact
+contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
+assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
+CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
 
 
@@ -866,6 +871,65 @@ class World:
         """Queue the build of the query index unless it is current; returns how many times this world has built it."""
         n = C.c_int64(0)
         check(self.L.phx_world_query_index(self.h, C.byref(n)))
+        return n.value
+
+    # ---- contact reports (include/phyx_amd.h: CONTACTS; the specification: tests/contact_spec.py) ----
+    def contacts(self, bodies, skip_static=False):
+        """The contacts of each listed body (repeats allowed): one contact_dtype record per live contact-point slot of every manifold the
+        body is in, ordered by (other, manifold, slot).  Returns (offsets, records): body q's records are records[offsets[q]:offsets[q + 1]]."""
+        if isinstance(bodies, (list, tuple)) and not len(bodies):
+            bodies = np.zeros(0, dtype=np.int32)
+        idx = self._indices(bodies, "contacts")
+        if idx.size and idx.min() < 0:
+            raise ValueError("contacts: negative body index")
+        flags = 1 if skip_static else 0
+        offsets = np.zeros(len(idx) + 1, dtype=np.int32)
+        total = C.c_int64(0)
+        cap = max(256, 8 * len(idx))
+        for _ in range(2):                                         # (the second call with the size the first one reported)
+            out = np.zeros(cap, dtype=contact_dtype)
+            st = self.L.phx_world_query_contacts(self.h, _ptr(idx), len(idx), flags, _ptr(offsets), _ptr(out), cap, C.byref(total))
+            if st != -4 or total.value > np.iinfo(np.int32).max:
+                break
+            cap = int(total.value)
+        check(st)
+        return offsets, out[:total.value].copy() if total.value < cap else out
+
+    def contact_events(self):
+        """Touch events since the last call: (begin, end), (K, 2) int32 arrays of {body1, body2} pairs sorted ascending; the pairs that
+        started / stopped touching (a manifold with point_count > 0).  The baseline advances only when the call succeeds."""
+        caps = [max(64, self.counts()[1]), 64]
+        bt, et = C.c_int64(0), C.c_int64(0)
+        for _ in range(2):
+            begin = np.zeros((caps[0], 2), dtype=np.int32)
+            end = np.zeros((caps[1], 2), dtype=np.int32)
+            st = self.L.phx_world_contact_events(self.h, _ptr(begin), caps[0], C.byref(bt), _ptr(end), caps[1], C.byref(et))
+            if st != -4:
+                break
+            caps = [max(caps[0], int(bt.value)), max(caps[1], int(et.value))]
+        check(st)
+        return begin[:bt.value].copy(), end[:et.value].copy()
+
+    def contact_markers_device(self, out, cap=None):
+        """The demo's contact markers (contact_marker_dtype, 24 B each, 2 per manifold) into device memory, queued on the world's stream:
+        `out` is a torch tensor (its data_ptr()) or a device address (int or ctypes pointer, 8-byte aligned); cap in markers (default:
+        2 * the manifold count)."""
+        if hasattr(out, "data_ptr"):
+            if cap is None:
+                cap = out.numel() * out.element_size() // contact_marker_dtype.itemsize
+            out = out.data_ptr()
+        if isinstance(out, bool) or not isinstance(out, (int, np.integer, C.c_void_p)):
+            raise TypeError("contact_markers_device: expected a tensor or a device address, got %s" % type(out).__name__)
+        if cap is None:
+            cap = 2 * self.counts()[1]
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0 or cap > np.iinfo(np.int32).max:
+            raise ValueError("contact_markers_device: cap must be an int32 >= 0")
+        check(self.L.phx_world_get_contact_markers_device(self.h, _dev_ptr(out), int(cap)))
+
+    def contact_index(self):
+        """Queue the build of the contact index unless it is current; returns how many times this world has built it."""
+        n = C.c_int64(0)
+        check(self.L.phx_world_contact_index(self.h, C.byref(n)))
         return n.value
 
     def sync(self):

@@ -13,6 +13,7 @@
 #include "device_scan.h"
 #include "world_kernels.h"
 #include "query.h"
+#include "contact.h"
 
 #include <algorithm>
 #include <chrono>
@@ -71,6 +72,12 @@ public:
     int raycast_device(const void* d_rays, int count, int flags, void* d_out);
     int query_index_build();             // the query index alone, built unless current (tools/query_cost.py)
     int query_index_builds() const { return query_.index_builds(); }
+    // contact reports (phx_world_query_contacts ... phx_world_contact_index): between steps; only the events' baseline changes
+    int query_contacts(const int32_t* bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total);
+    int contact_events(int32_t* begin, int begin_cap, int64_t* begin_total, int32_t* end, int end_cap, int64_t* end_total);
+    int contact_markers_device(void* d_out, int cap);
+    int contact_index_build();           // the contact index alone, built unless current (tools/contact_cost.py)
+    int contact_index_builds() const { return contacts_.index_builds(); }
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -171,6 +178,12 @@ private:
     DevBuf<int> q_body_;
     DevBuf<phx_ray_hit> q_hits_;
     int query_prepare(bool host_wait);
+    // contact reports: the contact epoch is bumped by every path that can change the manifolds (every step, a removal, set_state and so
+    // a re-slab) or the body count; the contact index is current while it was built for this epoch
+    unsigned long long contact_epoch_ = 0;
+    DeviceContacts contacts_;
+    ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, mpos_.p, nb()}; }
+    int contact_prepare(const char* what, bool host_wait);
 };
 
 World::~World()
@@ -193,7 +206,8 @@ int World::init()
     stream_ = broadphase_.stream();
     PHX_TRY(solver_.adopt_stream(stream_));
     PHX_TRY(counters_.reserve(8));
-    return query_.configure_from_env();
+    PHX_TRY(query_.configure_from_env());
+    return contacts_.configure_from_env();
 }
 
 // ref: World.cpp:11-17, RigidBody.h:15-36, Coords2.h:10-17 (cos/sin resolve to the double overloads): the record AddBody makes (index
@@ -274,6 +288,7 @@ int World::sync_bodies_to_device()
     bodies_dirty_ = false;
     records_stale_ = false;
     ++geom_epoch_;
+    ++contact_epoch_;
     return PHX_OK;
 }
 
@@ -501,6 +516,7 @@ int World::pre_solve(float dt)
     using clk = std::chrono::steady_clock;
     PHX_TRY(use_device(device_));
     mid_step_ = true;
+    ++contact_epoch_;
     PHX_TRY(sync_bodies_to_device());
     auto t = clk::now();
     auto lap = [&](int phase) { if (!phase_timing) return; (void)hipStreamSynchronize(stream_); auto n = clk::now(); phase_ms[phase] = std::chrono::duration<double, std::milli>(n - t).count(); t = n; };
@@ -775,6 +791,13 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     for (int i = 0; i < nm; ++i) pairs[i] = make_uint2((unsigned)manifolds[i].body1, (unsigned)manifolds[i].body2);
     PHX_TRY(broadphase_.reset_pairs(pairs.data(), nm));
     PHX_TRY(forget_step_history());
+    ++contact_epoch_;
+    std::vector<unsigned long long> touching;                               // the events' baseline: T(restored state)
+    for (int i = 0; i < nm; ++i)
+        if (manifolds[i].point_count > 0) touching.push_back(((unsigned long long)(unsigned)manifolds[i].body1 << 32) | (unsigned)manifolds[i].body2);
+    std::sort(touching.begin(), touching.end());
+    touching.erase(std::unique(touching.begin(), touching.end()), touching.end());
+    PHX_TRY(contacts_.set_baseline(touching, stream_));
     PHX_HIP(hipStreamSynchronize(stream_));
     return PHX_OK;
 }
@@ -991,7 +1014,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
     const bool pending_accel = accel_pending_;
-    PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n)); PHX_TRY(rm_counts_.reserve(4));
+    PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n)); PHX_TRY(rm_counts_.reserve(5));
     PHX_TRY(rm_mnew_.reserve((size_t)nm + 2)); PHX_TRY(rm_jnew_.reserve((size_t)nj + 2)); PHX_TRY(rm_pairs_.reserve(std::max<size_t>(nm, 1)));
     PHX_TRY(spare_.bodies.reserve((size_t)n)); PHX_TRY(spare_.vel.reserve((size_t)n)); PHX_TRY(spare_.dvel.reserve((size_t)n)); PHX_TRY(spare_.mpos.reserve((size_t)n));
     PHX_TRY(spare_.frame.reserve((size_t)n)); PHX_TRY(spare_.aabb.reserve((size_t)n)); PHX_TRY(spare_.size.reserve((size_t)n));
@@ -1023,8 +1046,9 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     if (nj) hipLaunchKernelGGL(k_remove_joints, dim3(rgrid(nj)), dim3(256), 0, stream_, (const phx_contact_joint*)d_joints_.p, nj, (const phx_manifold*)d_manifolds_.p,
                                (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, spare_.joints.p);
     PHX_HIP(hipGetLastError());
+    PHX_TRY(contacts_.remap_baseline(rm_remap_.p, rm_counts_.p + 4, stream_));      // (the events' baseline through new[]: [4] its new size)
     // 4. the one round trip
-    unsigned got[4] = {0, 0, 0, 0};
+    unsigned got[5] = {0, 0, 0, 0, 0};
     PHX_TRY(rb_.add(got, rm_counts_.p, sizeof got, stream_));
     if (remap) PHX_TRY(rb_.add(remap, rm_remap_.p, (size_t)n * sizeof(int), stream_));
     PHX_TRY(rb_.wait(stream_));
@@ -1038,6 +1062,8 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
     host_bodies_.resize((size_t)kept);                                      // (only its size counts while the device copy is the world)
     ++geom_epoch_;
+    ++contact_epoch_;
+    contacts_.baseline_remapped(got[4]);
     records_stale_ = false;
     accel_pending_ = pending_accel && got[3] != 0;                          // (what the upload of the kept records would find)
     nm = (int)got[1]; nj = (int)got[2];
@@ -1098,6 +1124,7 @@ int World::add_bodies(const float* spawn, int count, int* first)
     PHX_HIP(hipGetLastError());
     host_bodies_.resize(total);                                             // (only its size counts while the device copy is the world)
     ++geom_epoch_;
+    ++contact_epoch_;                                                       // (the index's offsets are sized by the bodies)
     if (any_static) joints_changed_ = true;                                 // (the static set is part of the schedule)
     PHX_TRY(solver_.bodies_appended(n, (int)total));
     broadphase_.bodies_appended(n, (int)total);
@@ -1220,6 +1247,60 @@ int World::query_index_build()
 {
     PHX_TRY(query_prepare(false));
     return query_.ensure_index(resident(), nb(), geom_epoch_, stream_);
+}
+
+// ---- contact reports ----------------------------------------------------------------------------------------------------------------
+// Answered on the world's stream from the resident contact cache (contact.h / contact_kernels.h), between steps only: inside a step the
+// manifolds are mid-update.  The host forms check everything first and wait for their results; the markers only queue.
+int World::contact_prepare(const char* what, bool host_wait)
+{
+    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    return query_prepare(host_wait);
+}
+
+int World::query_contacts(const int32_t* bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total)
+{
+    static const char* const what = "phx_world_query_contacts";
+    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    if (flags != 0 && flags != PHX_QUERY_SKIP_STATIC) { set_error("%s: flags %d (0 or PHX_QUERY_SKIP_STATIC)", what, flags); return PHX_ERR_INVALID; }
+    if (!offsets || !total) { set_error("%s: null offsets / total", what); return PHX_ERR_INVALID; }
+    if (cap < 0 || (cap > 0 && !out)) { set_error("%s: bad output buffer (cap %d)", what, cap); return PHX_ERR_INVALID; }
+    PHX_TRY(check_batch(what, bodies, bodies, count, false));               // (count >= 0, indices in range; repeats allowed)
+    PHX_TRY(contact_prepare(what, true));
+    const int* d_bodies = nullptr;
+    if (count && nm) { const float* unused = nullptr; PHX_TRY(stage_batch(bodies, nullptr, count, 0, &d_bodies, &unused)); }
+    return contacts_.contacts(contact_cache(), contact_epoch_, d_bodies, count, flags, offsets, out, cap, total, rb_, stream_);
+}
+
+int World::contact_events(int32_t* begin, int begin_cap, int64_t* begin_total, int32_t* end, int end_cap, int64_t* end_total)
+{
+    static const char* const what = "phx_world_contact_events";
+    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world has no touch events (a re-slab renumbers bodies)", what); return PHX_ERR_STATE; }
+    if (!begin_total || !end_total) { set_error("%s: null totals", what); return PHX_ERR_INVALID; }
+    if (begin_cap < 0 || end_cap < 0 || (begin_cap > 0 && !begin) || (end_cap > 0 && !end)) {
+        set_error("%s: bad output buffers (caps %d, %d)", what, begin_cap, end_cap);
+        return PHX_ERR_INVALID;
+    }
+    PHX_TRY(contact_prepare(what, true));
+    return contacts_.events(contact_cache(), begin, begin_cap, begin_total, end, end_cap, end_total, rb_, stream_);
+}
+
+int World::contact_markers_device(void* d_out, int cap)
+{
+    static const char* const what = "phx_world_get_contact_markers_device";
+    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    if (cap < 0) { set_error("%s: negative cap %d", what, cap); return PHX_ERR_INVALID; }
+    if (cap > 0 && (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 7u))) { set_error("%s: the output must be an 8-byte aligned device pointer", what); return PHX_ERR_INVALID; }
+    if ((long long)cap < 2ll * nm) { set_error("%s: room for %d markers, the world has %d contact-point slots", what, cap, 2 * nm); return PHX_ERR_CAPACITY; }
+    PHX_TRY(contact_prepare(what, false));
+    return contacts_.markers(contact_cache(), static_cast<phx_contact_marker*>(d_out), stream_);
+}
+
+int World::contact_index_build()
+{
+    PHX_TRY(contact_prepare("phx_world_contact_index", false));
+    return contacts_.ensure_index(contact_cache(), contact_epoch_, stream_);
 }
 
 } // namespace phx
@@ -1427,6 +1508,24 @@ int phx_world_raycast_device(phx_world* w, const void* d_rays, int32_t count, in
     return w->impl.raycast_device(d_rays, count, flags, d_out);
 }
 
+int phx_world_query_contacts(phx_world* w, const int32_t* bodies, int32_t count, int32_t flags, int32_t* offsets, phx_contact* out, int32_t cap, int64_t* total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_contacts(bodies, count, flags, offsets, out, cap, total);
+}
+
+int phx_world_contact_events(phx_world* w, int32_t* begin, int32_t begin_cap, int64_t* begin_total, int32_t* end, int32_t end_cap, int64_t* end_total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.contact_events(begin, begin_cap, begin_total, end, end_cap, end_total);
+}
+
+int phx_world_get_contact_markers_device(phx_world* w, void* d_out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.contact_markers_device(d_out, cap);
+}
+
 int phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,
                         const phx_contact_point* contact_points, int32_t contact_point_count, const phx_contact_joint* joints, int32_t joint_count)
 {
@@ -1527,6 +1626,14 @@ int phx_world_query_index(phx_world* w, int64_t* builds)
     PHX_REQUIRE(w, "null handle");
     PHX_TRY(w->impl.query_index_build());
     if (builds) *builds = w->impl.query_index_builds();
+    return PHX_OK;
+}
+
+int phx_world_contact_index(phx_world* w, int64_t* builds)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_TRY(w->impl.contact_index_build());
+    if (builds) *builds = w->impl.contact_index_builds();
     return PHX_OK;
 }
 
