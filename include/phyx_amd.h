@@ -467,6 +467,39 @@ int  phx_world_add_bodies(phx_world* w, const float* spawn, int32_t count, int32
  * edits above (indices in range and distinct; values finite and >= 0), except that it changes the joint topology as the single form
  * does: the static set is part of the solver's schedule, which is rebuilt at the next step. */
 int  phx_world_set_inverse_masses(phx_world* w, const int32_t* bodies, const float* values, int32_t count);
+/* COLLISION FILTERS — which bodies collide at all.  Every body has a filter {category, mask, group}; the default {1, 0xFFFFFFFF, 0}
+ * lets every pair through, and a world whose filters are all the default steps exactly as one that never heard of filters.
+ *   - Rule: the pair (a, b) may collide iff
+ *       a.group == b.group && a.group != 0:  group > 0 (a shared positive group always collides, a shared negative group never);
+ *       otherwise:                           (a.mask & b.category) != 0 && (b.mask & a.category) != 0.
+ *     Static bodies are filtered like any other body: a body whose mask excludes the ground's category falls through it.
+ *   - Where it acts: UpdatePairs (ref: Collider.cpp:296-366) does not emit a pair that fails it.  The pair never enters the
+ *     broadphase's pair set, never gets a manifold, contact points or joints, and the contact reports never see it.
+ *     phx_broadphase_stats keeps its meaning: candidate_tests and overlapping_pairs count before the filter, new_pairs what was emitted.
+ *   - Setting filters: the rules of the edits above.  Between steps only (PHX_ERR_STATE); checked completely before anything is queued
+ *     (count >= 0, no NULL array when count > 0, every index in [0, body count), none twice; PHX_ERR_INVALID otherwise, the world
+ *     unchanged); staged through pinned memory and queued on phx_world_stream(w); before the first step it writes the host-staged
+ *     bodies' filters.  A sharded or communicator-attached world gets PHX_ERR_STATE.
+ *   - Pairs that exist already: a manifold whose pair fails the new filters is dropped, and the result is exactly what
+ *     phx_world_set_state would make of drop(state): bodies unchanged; the remaining manifolds in their old order with point_index =
+ *     2 * the new index; their contact-point slots move with them, a live slot's solver_index following its joint (-1 if the joint
+ *     goes); the joints of dropped manifolds go, the others keep their order with contact_point_index = 2 * (the manifold's new index)
+ *     + old % 2; the broadphase's pair set becomes the kept manifolds' pairs and the cached solver schedule is rebuilt at the next step.
+ *     (The removal's compaction above, with "the pair passes" as its keep rule.)  *dropped (may be NULL) receives the number of
+ *     manifolds dropped.  When none is, the call changes no topology: the cached schedule stays valid.  Dropped pairs leave the
+ *     touching set, so the next phx_world_contact_events reports them under end; the filters themselves do not touch its baseline.
+ *   - The other calls: add_body / add_bodies give new bodies the default filter; remove_bodies / remove_outside move filters with
+ *     the kept bodies (through new[]); phx_world_set_state resets every filter to the default (a filtered world is checkpointed as
+ *     set_state followed by set_collision_filters); set_inverse_masses, the edits, queries and contact reports leave them alone.
+ *     Queries see every body whatever its filter.
+ *   - Sharded worlds carry no filters: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and
+ *     phx_world_reslab return PHX_ERR_STATE while some body's filter differs from the default.
+ * The test runs on the device inside the broadphase's sweep, before the pair-set lookup: one 16-byte gather per y-overlapping
+ * candidate, and only in a world where some filter was ever set (the sweep of any other world is the unfiltered code). */
+typedef struct { uint32_t category, mask; int32_t group; } phx_collision_filter;     /* 12 B */
+int  phx_world_set_collision_filters(phx_world* w, const int32_t* bodies, const phx_collision_filter* filters, int32_t count, int32_t* dropped);
+/* every body's filter, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
+int  phx_world_get_collision_filters(phx_world* w, phx_collision_filter* out, int32_t cap);
 /* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
  * its AABB {aabb_min, aabb_max} and its box {pos, xvector = xv, yvector = yv, geom_size = h (half extents)} (UpdateGeom copies the

@@ -42,6 +42,7 @@ ray_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,))
 assert ray_hit_dtype.itemsize == 24
 contact_dtype = np.dtype([("other", "<i4"), ("manifold", "<i4"), ("slot", "<i4"), ("flags", "<i4"), ("point", "<f4", (2,)), ("normal", "<f4", (2,)),
                           ("normal_impulse", "<f4"), ("friction_impulse", "<f4")])                                     # phx_contact
+collision_filter_dtype = np.dtype([("category", "<u4"), ("mask", "<u4"), ("group", "<i4")])      # phx_collision_filter
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
@@ -803,6 +804,35 @@ class World:
         if isinstance(bodies, (list, tuple)) and not len(bodies):
             bodies = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
+
+    # ---- collision filters (include/phyx_amd.h COLLISION FILTERS; the specification: tests/filter_spec.py) ----
+    def set_collision_filters(self, bodies, category=1, mask=0xFFFFFFFF, group=0):
+        """Give the listed bodies (each at most once) the filter {category, mask, group}: each a scalar for all of them or one value per
+        body.  A pair (a, b) collides iff a shared non-zero group is positive, or else each mask meets the other's category.  Manifolds
+        whose pair now fails are dropped as set_state of filter_spec.drop(state()) would; returns how many were."""
+        if isinstance(bodies, (list, tuple)) and not len(bodies):
+            bodies = np.zeros(0, dtype=np.int32)
+        idx = self._indices(bodies, "set_collision_filters")
+        f = np.zeros(len(idx), dtype=collision_filter_dtype)
+        for name, v, lo, hi in (("category", category, 0, 2 ** 32 - 1), ("mask", mask, 0, 2 ** 32 - 1),
+                                ("group", group, -2 ** 31, 2 ** 31 - 1)):
+            a = np.asarray(v)
+            if a.dtype.kind not in "iu":
+                raise TypeError("set_collision_filters: %s must be integers, got %s" % (name, a.dtype))
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != (len(idx),)):
+                raise ValueError("set_collision_filters: %s must be a scalar or have shape (%d,), got %s" % (name, len(idx), a.shape))
+            if a.size and (int(a.min()) < lo or int(a.max()) > hi):
+                raise ValueError("set_collision_filters: %s out of the range [%d, %d]" % (name, lo, hi))
+            f[name] = a
+        dropped = C.c_int32(0)
+        check(self.L.phx_world_set_collision_filters(self.h, _ptr(idx), _ptr(f), len(idx), C.byref(dropped)))
+        return dropped.value
+
+    def collision_filters(self):
+        """Every body's filter, in index order: an array of collision_filter_dtype."""
+        out = np.zeros(self.counts()[0], dtype=collision_filter_dtype)
+        check(self.L.phx_world_get_collision_filters(self.h, _ptr(out), len(out)))
+        return out
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----
     @staticmethod

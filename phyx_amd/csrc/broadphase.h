@@ -18,8 +18,10 @@ public:
     // `while_waiting` (may be null): queued-work hook of the update's one host round trip (Readback::wait) — called at most once;
     // the caller checks whether it ran
     // `carrier` (may be null): the kernel `while_waiting` would queue takes the round trip's post along (Readback::wait)
+    // `filters` (may be null; World only): one {category, mask, group, 0} record per body — pairs that fail the collision filter
+    // (common.h collision_filter_pass) are not emitted; null sweeps with the unfiltered kernels
     int update_resident(const float4* d_aabb, int n, const StepPrologue* prologue = nullptr, const std::function<int()>* while_waiting = nullptr,
-                        const MailCarrier* carrier = nullptr);
+                        const MailCarrier* carrier = nullptr, const uint4* filters = nullptr);
     // the C-ABI edge: 128-byte records (their AABBs are extracted into a scratch array first)
     int update_device(const phx_rigid_body* d_bodies, int n);
     int update_host(const phx_rigid_body* bodies, int n, uint32_t* new_pairs, int cap, int* count);

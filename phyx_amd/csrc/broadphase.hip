@@ -179,6 +179,21 @@ struct SweepView {
     unsigned long long* counters;   // statistics, spread over STAT_SLOTS slots to keep the atomics apart: [2 * slot] candidate tests, [2 * slot + 1] overlapping pairs
 };
 
+// A World with collision filters (common.h collision_filter_pass) sweeps with this view: the same kernels instantiated on it test the
+// rule where a y-overlapping candidate's body index is looked up, before the pair-set lookup — a rejected pair costs one 16-byte gather
+// and no hash probe, and is neither counted as new, nor cached, nor emitted (its overlap is still counted: phx_broadphase_stats).
+// Instantiated on the plain SweepView the kernels are the unfiltered code, instruction for instruction.
+struct FilteredSweepView : SweepView {
+    const uint4* filters;      // per body {category, mask, group, 0}
+};
+template <class V> struct SweepFilter { static constexpr bool on = false; };
+template <> struct SweepFilter<FilteredSweepView> { static constexpr bool on = true; };
+template <class V> __device__ __forceinline__ uint4 sweep_filter_of(const V& v, unsigned body)
+{
+    if constexpr (SweepFilter<V>::on) return v.filters[body];
+    else return make_uint4(0u, 0u, 0u, 0u);
+}
+
 constexpr int SWEEP_CAND = 16;       // y-overlapping candidates a row can hold before it must look them up in the pair set
 constexpr int SWEEP_LOOK = 8;        // lookups a row keeps in flight
 constexpr int SWEEP_GROUP = 8;       // candidates the wave reads from its staged block per step of its walk
@@ -207,8 +222,8 @@ __device__ __forceinline__ int scan_end(const float4* __restrict__ entries, int 
 //  transposed step is ~27 mostly scalar instructions, this one ~15 vector ones.  tools/probe/sweep_tiles.hip.txt keeps it.)
 #define PHX_SWEEP_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
-template <bool EMIT>
-__global__ void __launch_bounds__(256) k_sweep_rows(SweepView v, const unsigned* __restrict__ row_offset, uint2* __restrict__ out, unsigned total)
+template <bool EMIT, class V>
+__global__ void __launch_bounds__(256) k_sweep_rows(V v, const unsigned* __restrict__ row_offset, uint2* __restrict__ out, unsigned total)
 {
     // EMIT = false: the count pass (also remembers each row's first ROW_CACHE new partners).
     // EMIT = true : rescans ONLY the rows that found more than ROW_CACHE new pairs; all other rows are emitted from the
@@ -251,6 +266,7 @@ __global__ void __launch_bounds__(256) k_sweep_rows(SweepView v, const unsigned*
             if (next - dst <= (unsigned)ROW_CACHE) scanning = false;      // emitted from the cache
         }
         const unsigned ia = scanning ? v.idx[i] : 0u;
+        const uint4 fa = scanning ? sweep_filter_of(v, ia) : make_uint4(0u, 0u, 0u, 0u);      // (the row's filter: once per row)
         unsigned found = 0;
         // The candidates that overlap in y are only COLLECTED by the scan (their positions, in j order, in LDS); the pair-set
         // lookups — two dependent memory round trips each — are made afterwards, all in flight together.  Done inside the scan
@@ -262,11 +278,19 @@ __global__ void __launch_bounds__(256) k_sweep_rows(SweepView v, const unsigned*
                 unsigned long long first[SWEEP_LOOK];
 #pragma unroll
                 for (int k = 0; k < SWEEP_LOOK; ++k) ib[k] = h + k < ncand ? v.idx[cand[h + k][threadIdx.x]] : 0u;
+                unsigned pass = ~0u;                               // bit k: candidate h + k passes the collision filter (always, unfiltered)
+                if constexpr (SweepFilter<V>::on) {
+                    pass = 0u;
 #pragma unroll
-                for (int k = 0; k < SWEEP_LOOK; ++k) first[k] = h + k < ncand ? v.table[ps_hash(((unsigned long long)ia << 32) | ib[k]) & v.mask] : 0ull;
+                    for (int k = 0; k < SWEEP_LOOK; ++k)
+                        if (h + k < ncand && collision_filter_pass(fa, sweep_filter_of(v, ib[k]))) pass |= 1u << k;
+                }
+#pragma unroll
+                for (int k = 0; k < SWEEP_LOOK; ++k) first[k] = h + k < ncand && ((pass >> k) & 1u) ? v.table[ps_hash(((unsigned long long)ia << 32) | ib[k]) & v.mask] : 0ull;
 #pragma unroll
                 for (int k = 0; k < SWEEP_LOOK; ++k) {
                     if (h + k >= ncand) break;
+                    if (!((pass >> k) & 1u)) continue;             // rejected by the filter: no lookup, not new
                     const unsigned long long key = ((unsigned long long)ia << 32) | ib[k];
                     bool present = first[k] == key;
                     if (!present && first[k] != PS_EMPTY) present = ps_contains(v.table, v.mask, key);       // a collision at the home slot: walk on
@@ -361,8 +385,8 @@ __device__ __forceinline__ void emit_cached_rows(const SweepView& v, const unsig
 }
 
 // one workgroup per hub chunk; tiles of 256 candidates in j order, a running base keeps the emission order
-template <bool EMIT>
-__device__ __forceinline__ void sweep_chunks(const SweepView& v, const unsigned* __restrict__ row_offset, uint2* __restrict__ out, int block, int blocks)
+template <bool EMIT, class V>
+__device__ __forceinline__ void sweep_chunks(const V& v, const unsigned* __restrict__ row_offset, uint2* __restrict__ out, int block, int blocks)
 {
     __shared__ unsigned wave_cnt[4];
     __shared__ unsigned running;
@@ -373,6 +397,7 @@ __device__ __forceinline__ void sweep_chunks(const SweepView& v, const unsigned*
         const int4 ch = v.chunks[c];
         const float4 a = v.entries[ch.x];
         const unsigned ia = v.idx[ch.x];
+        const uint4 fa = sweep_filter_of(v, ia);
         unsigned long long overlaps = 0;
         if constexpr (!EMIT) {
             // the count pass only wants the chunk's number of new pairs: every lane counts its own candidates over all tiles (their
@@ -382,7 +407,9 @@ __device__ __forceinline__ void sweep_chunks(const SweepView& v, const unsigned*
                 const float4 b = v.entries[j];
                 if (fabsf(b.z - a.z) <= a.w + b.w) {
                     ++overlaps;
-                    if (!ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | v.idx[j])) ++mine;
+                    const unsigned ib = v.idx[j];
+                    if (SweepFilter<V>::on && !collision_filter_pass(fa, sweep_filter_of(v, ib))) continue;
+                    if (!ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | ib)) ++mine;
                 }
             }
             for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
@@ -404,7 +431,7 @@ __device__ __forceinline__ void sweep_chunks(const SweepView& v, const unsigned*
                 if (fabsf(b.z - a.z) <= a.w + b.w) {
                     ib = v.idx[j];
                     ++overlaps;
-                    hit = !ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | ib);
+                    hit = (!SweepFilter<V>::on || collision_filter_pass(fa, sweep_filter_of(v, ib))) && !ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | ib);
                 }
             }
             const unsigned long long bal = __ballot(hit);
@@ -427,11 +454,13 @@ __device__ __forceinline__ void sweep_chunks(const SweepView& v, const unsigned*
 }
 
 // the count pass over the hub rows' chunks
-__global__ void __launch_bounds__(256) k_sweep_chunks_count(SweepView v) { sweep_chunks<false>(v, nullptr, nullptr, (int)blockIdx.x, (int)gridDim.x); }
+template <class V>
+__global__ void __launch_bounds__(256) k_sweep_chunks_count(V v) { sweep_chunks<false>(v, nullptr, nullptr, (int)blockIdx.x, (int)gridDim.x); }
 
 // The emit pass, ONE launch: the first `row_blocks` workgroups emit the ordinary rows' new pairs from what the count pass remembered,
 // the others the hub rows' chunks — different rows, different places in the list (two launches of ~5 us each at the dispatch floor).
-__global__ void __launch_bounds__(256) k_emit_pairs(SweepView v, const unsigned* __restrict__ row_offset, uint2* __restrict__ out, unsigned total, int row_blocks)
+template <class V>
+__global__ void __launch_bounds__(256) k_emit_pairs(V v, const unsigned* __restrict__ row_offset, uint2* __restrict__ out, unsigned total, int row_blocks)
 {
     if ((int)blockIdx.x < row_blocks) emit_cached_rows(v, row_offset, out, total, (int)blockIdx.x, row_blocks);
     else sweep_chunks<true>(v, row_offset, out, (int)blockIdx.x - row_blocks, (int)gridDim.x - row_blocks);
@@ -544,7 +573,8 @@ int DeviceBroadphase::update_device(const phx_rigid_body* d_bodies, int n)
     return update_resident(st_aabb_.p, n);
 }
 
-int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepPrologue* prologue, const std::function<int()>* while_waiting, const MailCarrier* carrier)
+int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepPrologue* prologue, const std::function<int()>* while_waiting, const MailCarrier* carrier,
+                                      const uint4* filters)
 {
     PHX_TRY(use_device(device_));
     PHX_REQUIRE(n >= 0 && (n == 0 || d_bodies), "bad body array");
@@ -633,8 +663,14 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
     for (int attempt = 0;; ++attempt) {
         v.chunks = chunks_.p; v.chunk_count = chunk_count_.p; v.chunk_cap = chunk_cap;
         chunk_grid = std::min(chunk_cap, 2048);
-        hipLaunchKernelGGL((k_sweep_rows<false>), dim3(grid_for(n)), dim3(256), 0, stream_, v, (const unsigned*)nullptr, (uint2*)nullptr, 0u);
-        hipLaunchKernelGGL(k_sweep_chunks_count, dim3(chunk_grid), dim3(256), 0, stream_, v);
+        if (filters) {
+            const FilteredSweepView fv{v, filters};
+            hipLaunchKernelGGL((k_sweep_rows<false, FilteredSweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, fv, (const unsigned*)nullptr, (uint2*)nullptr, 0u);
+            hipLaunchKernelGGL((k_sweep_chunks_count<FilteredSweepView>), dim3(chunk_grid), dim3(256), 0, stream_, fv);
+        } else {
+            hipLaunchKernelGGL((k_sweep_rows<false, SweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, v, (const unsigned*)nullptr, (uint2*)nullptr, 0u);
+            hipLaunchKernelGGL((k_sweep_chunks_count<SweepView>), dim3(chunk_grid), dim3(256), 0, stream_, v);
+        }
         // chunk counts -> per-row bases and the hub rows' totals (one small workgroup)
         PHX_TRY(chunk_scan_.reserve(chunk_cap + 1));
         hipLaunchKernelGGL(k_chunk_bases, dim3(1), dim3(1024), 0, stream_, v, chunk_scan_.p);
@@ -672,10 +708,13 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
         v.table = table_.p; v.mask = table_cap_ - 1;
         {
             const int row_blocks = grid_for(n), chunk_blocks = (host_small[2] & 0xFFFFFFFFull) ? std::min((int)(host_small[2] & 0xFFFFFFFFull), chunk_grid) : 0;
-            hipLaunchKernelGGL(k_emit_pairs, dim3(row_blocks + chunk_blocks), dim3(256), 0, stream_, v, (const unsigned*)row_count_.p, new_pairs_.p, total, row_blocks);
+            if (filters) hipLaunchKernelGGL((k_emit_pairs<FilteredSweepView>), dim3(row_blocks + chunk_blocks), dim3(256), 0, stream_, FilteredSweepView{v, filters}, (const unsigned*)row_count_.p, new_pairs_.p, total, row_blocks);
+            else hipLaunchKernelGGL((k_emit_pairs<SweepView>), dim3(row_blocks + chunk_blocks), dim3(256), 0, stream_, v, (const unsigned*)row_count_.p, new_pairs_.p, total, row_blocks);
         }
-        if (host_small[4] & 0xFFFFFFFFull)      // some row found more than ROW_CACHE new pairs: those rows are rescanned
-            hipLaunchKernelGGL((k_sweep_rows<true>), dim3(grid_for(n)), dim3(256), 0, stream_, v, (const unsigned*)row_count_.p, new_pairs_.p, total);
+        if (host_small[4] & 0xFFFFFFFFull) {    // some row found more than ROW_CACHE new pairs: those rows are rescanned (with the count pass's filter)
+            if (filters) hipLaunchKernelGGL((k_sweep_rows<true, FilteredSweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, FilteredSweepView{v, filters}, (const unsigned*)row_count_.p, new_pairs_.p, total);
+            else hipLaunchKernelGGL((k_sweep_rows<true, SweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, v, (const unsigned*)row_count_.p, new_pairs_.p, total);
+        }
         // ref: Collider.cpp:313 / :341 — the emitted pairs join the persistent set
         hipLaunchKernelGGL(k_ps_insert, dim3(grid_for((int)total)), dim3(256), 0, stream_, table_.p, table_cap_ - 1, (const uint2*)new_pairs_.p, (int)total, stamps_.p + 1);
         PHX_HIP(hipGetLastError());

@@ -347,4 +347,16 @@ private:
     Item items_[MAX_ITEMS];
 };
 
+// ---- collision filters (phx_world_set_collision_filters) -------------------------------------------------------------------------
+// The World keeps one 16-byte record per body, {category, mask, (unsigned) group, 0}; the default {1, 0xFFFFFFFF, 0, 0} lets every
+// pair through.  The rule (include/phyx_amd.h): a shared non-zero group decides alone (positive: collide, negative: never), otherwise
+// each body's mask must meet the other's category.  Selects, no branches: it sits inside the predicated sweep (broadphase.hip).
+constexpr unsigned FILTER_DEFAULT_CATEGORY = 1u, FILTER_DEFAULT_MASK = 0xFFFFFFFFu;
+__host__ __device__ __forceinline__ bool collision_filter_pass(uint4 a, uint4 b)
+{
+    const bool shared = a.z == b.z && a.z != 0u;
+    const bool masks = ((a.y & b.x) != 0u) & ((b.y & a.x) != 0u);
+    return shared ? (int)a.z > 0 : masks;
+}
+
 } // namespace phx

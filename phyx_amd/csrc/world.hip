@@ -78,6 +78,11 @@ public:
     int contact_markers_device(void* d_out, int cap);
     int contact_index_build();           // the contact index alone, built unless current (tools/contact_cost.py)
     int contact_index_builds() const { return contacts_.index_builds(); }
+    // collision filters (phx_world_set_collision_filters / get_collision_filters): between steps; a change that makes pairs fail drops
+    // their manifolds as set_state of the dropped state would
+    int set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped);
+    int get_collision_filters(phx_collision_filter* out, int cap);
+    int refuse_filters(const char* what);      // PHX_ERR_STATE if some body's filter is not the default (the sharded modes carry none)
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -163,9 +168,13 @@ private:
     DevBuf<unsigned> rm_keep_, rm_bnew_, rm_mnew_, rm_jnew_, rm_counts_;
     DevBuf<int> rm_remap_;
     DevBuf<uint2> rm_pairs_;
+    int compaction_scratch();
+    template <class Keep> int scan_compaction(const Keep& kept);
+    template <class Keep> int queue_compaction(const Keep& kept);
     struct Spare {
         DevBuf<phx_rigid_body> bodies;
         DevBuf<float4> vel, dvel, mpos, frame, aabb, accel;
+        DevBuf<uint4> filters;
         DevBuf<float2> size;
         DevBuf<phx_manifold> manifolds;
         DevBuf<phx_contact_point> cps;
@@ -184,6 +193,13 @@ private:
     DeviceContacts contacts_;
     ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, mpos_.p, nb()}; }
     int contact_prepare(const char* what, bool host_wait);
+    // collision filters: one {category, mask, group, 0} record per body (common.h collision_filter_pass), kept only once some filter
+    // was set — filters_active_ is conservative (a filter may have been set back to the default) and picks the filtered sweep.  While the
+    // bodies are host-staged host_filters_ is the truth, otherwise filt_ (grown, appended, compacted with the body buffers)
+    bool filters_active_ = false;
+    DevBuf<uint4> filt_;
+    std::vector<uint4> host_filters_;
+    int filters_to_host();               // the bodies become host-staged: so do their filters
 };
 
 World::~World()
@@ -234,17 +250,21 @@ static phx_rigid_body body_record(float px, float py, float angle, float sx, flo
 
 int World::add_body(float px, float py, float angle, float sx, float sy)
 {
-    if (!bodies_dirty_ && !host_bodies_.empty() && d_bodies_.p) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
+    if (!bodies_dirty_ && d_bodies_.p) {
+        if (!host_bodies_.empty()) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
+        PHX_TRY(filters_to_host());
+    }
     phx_rigid_body b = body_record(px, py, angle, sx, sy);
     b.index = (uint32_t)host_bodies_.size();
     host_bodies_.push_back(b);
+    if (filters_active_) host_filters_.push_back(make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u));
     bodies_dirty_ = true;
     return (int)host_bodies_.size() - 1;
 }
 
 int World::set_static(int body)
 {
-    if (!bodies_dirty_ && d_bodies_.p) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
+    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(filters_to_host()); }
     host_bodies_[body].inv_mass = 0.f;
     host_bodies_[body].inv_inertia = 0.f;
     bodies_dirty_ = true;
@@ -253,7 +273,7 @@ int World::set_static(int body)
 
 int World::set_inverse_mass(int body, float inv_mass, float inv_inertia)
 {
-    if (!bodies_dirty_ && d_bodies_.p) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
+    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(filters_to_host()); }
     host_bodies_[body].inv_mass = inv_mass;
     host_bodies_[body].inv_inertia = inv_inertia;
     bodies_dirty_ = true;
@@ -284,7 +304,12 @@ int World::sync_bodies_to_device()
             PHX_HIP(hipStreamSynchronize(stream_));      // (`acc` is a local)
         }
     }
+    if (filters_active_) {
+        PHX_TRY(filt_.reserve(n));
+        if (!host_filters_.empty()) PHX_HIP(hipMemcpyAsync(filt_.p, host_filters_.data(), host_filters_.size() * sizeof(uint4), hipMemcpyHostToDevice, stream_));
+    }
     PHX_HIP(hipStreamSynchronize(stream_));
+    host_filters_.clear();
     bodies_dirty_ = false;
     records_stale_ = false;
     ++geom_epoch_;
@@ -330,7 +355,8 @@ int World::update_pairs()                                                   // r
     // (that launch also CARRIES the post of the new-pair count: its first workgroup posts before it updates — a dispatch fewer per step)
     const MailCarrier old_manifolds_with = [&](const MailRide* ride) -> int { old_ride_ = ride; const int st = old_manifolds(); old_ride_ = nullptr; return st; };
     PHX_TRY(broadphase_.update_resident(aabb_.p, nb(), fuse_velocity_ ? &prologue : nullptr, phase_timing ? nullptr : &old_manifolds,
-                                        phase_timing || !nm ? nullptr : &old_manifolds_with));      // same stream; returns once the new-pair count is known
+                                        phase_timing || !nm ? nullptr : &old_manifolds_with,      // same stream; returns once the new-pair count is known
+                                        filters_active_ ? (const uint4*)filt_.p : nullptr));
     fuse_velocity_ = false;
     if (accel_pending_) {                  // IntegrateVelocity of this step has consumed the uploaded accelerations (ref: World.cpp:50, 53)
         accel_pending_ = false;
@@ -778,6 +804,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     PHX_TRY(synchronize());
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
+    filters_active_ = false; host_filters_.clear();                         // every filter is the default again
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -988,6 +1015,36 @@ int World::get_poses_device(void* d_out, int cap)
     return PHX_OK;
 }
 
+// ---- the compaction of the contact cache (a removal, a change of collision filters) ------------------------------------------------
+// Kept manifolds and joints keep their old order: their new positions are exclusive scans of the keep predicate (world_kernels.h
+// BodiesKept / FilterKept; rm_counts_[1], [2] receive the kept counts), and two kernels write them out of place into the spares, with
+// the kept manifolds' pairs in rm_pairs_ (the new broadphase pair set).  Grid-strided over the OLD counts: no host count needed.
+int World::compaction_scratch()
+{
+    PHX_TRY(rm_counts_.reserve(5));
+    PHX_TRY(rm_mnew_.reserve((size_t)nm + 2)); PHX_TRY(rm_jnew_.reserve((size_t)nj + 2)); PHX_TRY(rm_pairs_.reserve(std::max<size_t>(nm, 1)));
+    PHX_TRY(spare_.manifolds.reserve(std::max<size_t>(nm, 1))); PHX_TRY(spare_.cps.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(spare_.joints.reserve(std::max<size_t>(nj, 1)));
+    return PHX_OK;
+}
+
+template <class Keep>
+int World::scan_compaction(const Keep& kept)
+{
+    PHX_TRY(device_exclusive_scan_of(ManifoldKeepLoad<Keep>{d_manifolds_.p, kept}, rm_mnew_.p, nm, rm_counts_.p + 1, scan_tiles_, stream_));
+    return device_exclusive_scan_of(JointKeepLoad<Keep>{d_joints_.p, d_manifolds_.p, kept}, rm_jnew_.p, nj, rm_counts_.p + 2, scan_tiles_, stream_);
+}
+
+template <class Keep>
+int World::queue_compaction(const Keep& kept)
+{
+    if (nm) hipLaunchKernelGGL((k_remove_manifolds<Keep>), dim3(rgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, (const phx_contact_point*)d_cps_.p, nm,
+                               kept, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, (const unsigned*)(rm_counts_.p + 2), nj, spare_.manifolds.p, spare_.cps.p, rm_pairs_.p);
+    if (nj) hipLaunchKernelGGL((k_remove_joints<Keep>), dim3(rgrid(nj)), dim3(256), 0, stream_, (const phx_contact_joint*)d_joints_.p, nj, (const phx_manifold*)d_manifolds_.p,
+                               kept, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, spare_.joints.p);
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
 // ---- removal between steps ------------------------------------------------------------------------------------------------------
 // Defined as phx_world_set_state of the filtered state (include/phyx_amd.h); computed on the world's stream without the state
 // crossing PCIe: keep flags per body (scattered from the staged list, or the box test on the resident AABBs), three exclusive scans
@@ -1014,12 +1071,12 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
     const bool pending_accel = accel_pending_;
-    PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n)); PHX_TRY(rm_counts_.reserve(5));
-    PHX_TRY(rm_mnew_.reserve((size_t)nm + 2)); PHX_TRY(rm_jnew_.reserve((size_t)nj + 2)); PHX_TRY(rm_pairs_.reserve(std::max<size_t>(nm, 1)));
+    PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n));
     PHX_TRY(spare_.bodies.reserve((size_t)n)); PHX_TRY(spare_.vel.reserve((size_t)n)); PHX_TRY(spare_.dvel.reserve((size_t)n)); PHX_TRY(spare_.mpos.reserve((size_t)n));
     PHX_TRY(spare_.frame.reserve((size_t)n)); PHX_TRY(spare_.aabb.reserve((size_t)n)); PHX_TRY(spare_.size.reserve((size_t)n));
     if (pending_accel) PHX_TRY(spare_.accel.reserve((size_t)n));
-    PHX_TRY(spare_.manifolds.reserve(std::max<size_t>(nm, 1))); PHX_TRY(spare_.cps.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(spare_.joints.reserve(std::max<size_t>(nj, 1)));
+    if (filters_active_) PHX_TRY(spare_.filters.reserve((size_t)n));
+    PHX_TRY(compaction_scratch());
     // 1. keep flags per body
     if (box) {
         hipLaunchKernelGGL(k_keep_inside, dim3(rgrid(n)), dim3(256), 0, stream_, (const float4*)aabb_.p, n, make_float4(box[0], box[1], box[2], box[3]), rm_keep_.p);
@@ -1032,19 +1089,15 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_HIP(hipGetLastError());
     // 2. where the kept bodies, manifolds and joints go (a zero count writes a zero total)
     PHX_TRY(device_exclusive_scan_of(BodyKeepLoad{rm_keep_.p}, rm_bnew_.p, n, rm_counts_.p, scan_tiles_, stream_));
-    PHX_TRY(device_exclusive_scan_of(ManifoldKeepLoad{d_manifolds_.p, rm_keep_.p}, rm_mnew_.p, nm, rm_counts_.p + 1, scan_tiles_, stream_));
-    PHX_TRY(device_exclusive_scan_of(JointKeepLoad{d_joints_.p, d_manifolds_.p, rm_keep_.p}, rm_jnew_.p, nj, rm_counts_.p + 2, scan_tiles_, stream_));
+    const BodiesKept kept{rm_keep_.p, rm_bnew_.p};
+    PHX_TRY(scan_compaction(kept));
     PHX_HIP(hipMemsetAsync(rm_counts_.p + 3, 0, sizeof(unsigned), stream_));
     // 3. compaction into the spares
     const WorldBodies out{BodyView{spare_.vel.p, spare_.dvel.p, spare_.mpos.p}, spare_.frame.p, spare_.aabb.p, spare_.size.p};
     hipLaunchKernelGGL(k_remove_bodies, dim3(rgrid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)d_bodies_.p, resident(), n, records_stale_ ? 1 : 0,
                        (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, spare_.bodies.p, out, pending_accel ? spare_.accel.p : (float4*)nullptr,
-                       rm_remap_.p, rm_counts_.p + 3);
-    if (nm) hipLaunchKernelGGL(k_remove_manifolds, dim3(rgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, (const phx_contact_point*)d_cps_.p, nm,
-                               (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p,
-                               (const unsigned*)(rm_counts_.p + 2), nj, spare_.manifolds.p, spare_.cps.p, rm_pairs_.p);
-    if (nj) hipLaunchKernelGGL(k_remove_joints, dim3(rgrid(nj)), dim3(256), 0, stream_, (const phx_contact_joint*)d_joints_.p, nj, (const phx_manifold*)d_manifolds_.p,
-                               (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, spare_.joints.p);
+                       rm_remap_.p, rm_counts_.p + 3, filters_active_ ? (const uint4*)filt_.p : (const uint4*)nullptr, spare_.filters.p);
+    PHX_TRY(queue_compaction(kept));
     PHX_HIP(hipGetLastError());
     PHX_TRY(contacts_.remap_baseline(rm_remap_.p, rm_counts_.p + 4, stream_));      // (the events' baseline through new[]: [4] its new size)
     // 4. the one round trip
@@ -1052,15 +1105,16 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(rb_.add(got, rm_counts_.p, sizeof got, stream_));
     if (remap) PHX_TRY(rb_.add(remap, rm_remap_.p, (size_t)n * sizeof(int), stream_));
     PHX_TRY(rb_.wait(stream_));
-    const int kept = (int)got[0];
-    if (removed) *removed = n - kept;
-    if (kept == n) return PHX_OK;                                           // every body is inside the box: nothing changes (the spares are dropped)
+    const int kept_bodies = (int)got[0];
+    if (removed) *removed = n - kept_bodies;
+    if (kept_bodies == n) return PHX_OK;                                    // every body is inside the box: nothing changes (the spares are dropped)
     // 5. the compacted arrays become the world's
     std::swap(d_bodies_, spare_.bodies);
     std::swap(vel_, spare_.vel); std::swap(dvel_, spare_.dvel); std::swap(mpos_, spare_.mpos); std::swap(frame_, spare_.frame); std::swap(aabb_, spare_.aabb); std::swap(size_, spare_.size);
     if (pending_accel) std::swap(accel_, spare_.accel);
+    if (filters_active_) std::swap(filt_, spare_.filters);
     std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
-    host_bodies_.resize((size_t)kept);                                      // (only its size counts while the device copy is the world)
+    host_bodies_.resize((size_t)kept_bodies);                               // (only its size counts while the device copy is the world)
     ++geom_epoch_;
     ++contact_epoch_;
     contacts_.baseline_remapped(got[4]);
@@ -1118,9 +1172,11 @@ int World::add_bodies(const float* spawn, int count, int* first)
     PHX_TRY(vel_.reserve_keep(total, n, stream_)); PHX_TRY(dvel_.reserve_keep(total, n, stream_)); PHX_TRY(mpos_.reserve_keep(total, n, stream_));
     PHX_TRY(frame_.reserve_keep(total, n, stream_)); PHX_TRY(aabb_.reserve_keep(total, n, stream_)); PHX_TRY(size_.reserve_keep(total, n, stream_));
     if (accel_pending_) PHX_TRY(accel_.reserve_keep(total, n, stream_));
+    if (filters_active_) PHX_TRY(filt_.reserve_keep(total, n, stream_));
     const int* unused = nullptr; const float* d_rows = nullptr;
     PHX_TRY(stage_batch(nullptr, spawn_rows_.data(), count, SPAWN_ROW, &unused, &d_rows));
-    hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), d_bodies_.p, accel_pending_ ? accel_.p : (float4*)nullptr);
+    hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), d_bodies_.p, accel_pending_ ? accel_.p : (float4*)nullptr,
+                       filters_active_ ? filt_.p : (uint4*)nullptr);
     PHX_HIP(hipGetLastError());
     host_bodies_.resize(total);                                             // (only its size counts while the device copy is the world)
     ++geom_epoch_;
@@ -1150,6 +1206,103 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
     PHX_TRY(stage_batch(bodies, values, count, 2, &d_bodies, &d_values));
     hipLaunchKernelGGL(k_set_inverse_masses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, mpos_.p, d_bodies_.p);
     PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+// ---- collision filters ------------------------------------------------------------------------------------------------------------
+// The rule and the defaults: include/phyx_amd.h COLLISION FILTERS, common.h collision_filter_pass.  The broadphase applies it inside the
+// sweep (broadphase.hip FilteredSweepView), so a failing pair is never emitted; what a change of filters does to pairs that exist already
+// is the removal's compaction of the contact cache with the filter as its keep predicate (FilterKept), bodies untouched.
+int World::filters_to_host()
+{
+    if (!filters_active_) return PHX_OK;
+    host_filters_.resize((size_t)nb());
+    if (!nb()) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_HIP(hipStreamSynchronize(stream_));
+    PHX_HIP(hipMemcpy(host_filters_.data(), filt_.p, (size_t)nb() * sizeof(uint4), hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int World::set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped)
+{
+    static const char* const what = "phx_world_set_collision_filters";
+    static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float), "a filter is staged as three 4-byte words");
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no collision filters", what); return PHX_ERR_STATE; }
+    PHX_TRY(check_batch(what, bodies, filters, count, true));
+    if (dropped) *dropped = 0;
+    if (!count) return PHX_OK;
+    const int n = nb();
+    if ((bodies_dirty_ || !d_bodies_.p) && !nm) {                           // host-staged, and no pair exists to drop
+        if (!filters_active_) host_filters_.assign((size_t)n, make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u));
+        filters_active_ = true;
+        for (int k = 0; k < count; ++k) host_filters_[(size_t)bodies[k]] = make_uint4(filters[k].category, filters[k].mask, (unsigned)filters[k].group, 0u);
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(filters), count, 3, &d_bodies, &d_values));
+    if (!filters_active_) {
+        PHX_TRY(filt_.reserve((size_t)std::max(n, 1)));
+        hipLaunchKernelGGL(k_default_filters, dim3(wgrid(n)), dim3(256), 0, stream_, filt_.p, n);
+        filters_active_ = true;
+    }
+    hipLaunchKernelGGL(k_set_filters, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, reinterpret_cast<const unsigned*>(d_values), count, filt_.p);
+    PHX_HIP(hipGetLastError());
+    if (!nm) return PHX_OK;
+    // the manifolds whose pair now fails go, with their slots and joints; the one round trip brings back the kept counts
+    PHX_TRY(compaction_scratch());
+    const FilterKept kept{filt_.p};
+    PHX_TRY(scan_compaction(kept));
+    PHX_TRY(queue_compaction(kept));
+    unsigned got[5] = {0, 0, 0, 0, 0};
+    PHX_TRY(rb_.add(got, rm_counts_.p, sizeof got, stream_));
+    PHX_TRY(rb_.wait(stream_));
+    if (dropped) *dropped = nm - (int)got[1];
+    if ((int)got[1] == nm) return PHX_OK;                                   // nothing dropped: a true no-op for the topology (the spares are dropped)
+    std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
+    nm = (int)got[1]; nj = (int)got[2];
+    ++contact_epoch_;                                                       // (the touch events' baseline stays: dropped pairs end)
+    PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
+    return forget_step_history();
+}
+
+int World::get_collision_filters(phx_collision_filter* out, int cap)
+{
+    const int n = nb();
+    if (cap < n) { set_error("phx_world_get_collision_filters: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    std::vector<uint4> f;
+    const uint4* src = host_filters_.data();
+    if (!filters_active_) {
+        for (int i = 0; i < n; ++i) out[i] = phx_collision_filter{FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0};
+        return PHX_OK;
+    }
+    if (!(bodies_dirty_ || !d_bodies_.p)) {
+        PHX_TRY(use_device(device_));
+        f.resize((size_t)n);
+        PHX_TRY(rb_.add(f.data(), filt_.p, (size_t)n * sizeof(uint4), stream_));
+        PHX_TRY(rb_.wait(stream_));
+        src = f.data();
+    }
+    for (int i = 0; i < n; ++i) out[i] = phx_collision_filter{src[i].x, src[i].y, (int32_t)src[i].z};
+    return PHX_OK;
+}
+
+// the sharded modes (phx_world_set_shard, set_comm, reslab) carry no filters: refused while some body's filter is not the default
+int World::refuse_filters(const char* what)
+{
+    if (!filters_active_) return PHX_OK;
+    std::vector<phx_collision_filter> f((size_t)nb());
+    PHX_TRY(get_collision_filters(f.data(), nb()));
+    for (const phx_collision_filter& x : f)
+        if (x.category != FILTER_DEFAULT_CATEGORY || x.mask != FILTER_DEFAULT_MASK || x.group != 0) {
+            set_error("%s: the world holds collision filters, which a sharded world does not carry", what);
+            return PHX_ERR_STATE;
+        }
+    filters_active_ = false; host_filters_.clear();                         // (every filter is the default again: the plain sweep)
     return PHX_OK;
 }
 
@@ -1356,6 +1509,7 @@ int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(count >= 1 && shard >= 0 && shard < count, "bad shard");
+    if (count > 1) PHX_TRY(w->impl.refuse_filters("phx_world_set_shard"));
     w->impl.shard = shard; w->impl.shard_count = count;
     PHX_TRY(w->impl.solver().set_shard(shard, count));
     return PHX_OK;
@@ -1396,6 +1550,7 @@ void* phx_world_stream(phx_world* w) { return w ? (void*)w->impl.stream() : null
 int phx_world_set_comm(phx_world* w, phx_comm* c)
 {
     PHX_REQUIRE(w, "null handle");
+    if (c) PHX_TRY(w->impl.refuse_filters("phx_world_set_comm"));
     return w->impl.set_comm(c ? &c->impl : nullptr);
 }
 
@@ -1476,6 +1631,19 @@ int phx_world_set_inverse_masses(phx_world* w, const int32_t* bodies, const floa
 {
     PHX_REQUIRE(w, "null handle");
     return w->impl.set_inverse_masses(bodies, values, count);
+}
+
+int phx_world_set_collision_filters(phx_world* w, const int32_t* bodies, const phx_collision_filter* filters, int32_t count, int32_t* dropped)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_collision_filters(bodies, filters, count, dropped);
+}
+
+int phx_world_get_collision_filters(phx_world* w, phx_collision_filter* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_collision_filters(out, cap);
 }
 
 int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
@@ -1578,6 +1746,7 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
 {
     PHX_REQUIRE(w && global_index && body_count && bounds && moved, "null handle / arguments");
     PHX_REQUIRE(scene_size >= *body_count && capacity >= *body_count, "bad sizes");
+    PHX_TRY(w->impl.refuse_filters("phx_world_reslab"));
     phx::SlabTransport tp;
     PHX_TRY(slab_transport(transport, w->impl, &tp));
     phx::SlabState st;

@@ -135,9 +135,10 @@ static __global__ void __launch_bounds__(256) k_set_inverse_masses(const int* __
 
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
 // as AddBody does (world.hip body_record); only the AABB is computed here, by the UpdateGeom of set_poses (ref: Geom.h:79-85).  The
-// record is AddBody's byte for byte, the resident state has zero velocities, and a pending acceleration slot starts at zero.
+// record is AddBody's byte for byte, the resident state has zero velocities, and a pending acceleration slot starts at zero, a
+// collision filter table (null while every filter is the default) the default filter.
 static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __restrict__ rows, int count, int first, WorldBodies w,
-                                                             phx_rigid_body* __restrict__ records, float4* __restrict__ accel)
+                                                             phx_rigid_body* __restrict__ records, float4* __restrict__ accel, uint4* __restrict__ filters)
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
         const float* q = rows + 10 * (size_t)k;
@@ -159,6 +160,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         w.aabb[i] = box;
         w.size[i] = make_float2(size.x, size.y);
         if (accel) accel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (filters) filters[i] = make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u);
     }
 }
 
@@ -418,6 +420,17 @@ static __global__ void __launch_bounds__(256) k_joints_fill(phx_contact_joint* _
     }
 }
 
+// collision filters (phx_world_set_collision_filters): the table of a world whose filters were all the default is filled first, then
+// the staged batch {indices | {category, mask, group} per body} is scattered into it
+static __global__ void __launch_bounds__(256) k_default_filters(uint4* __restrict__ filters, int n)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) filters[i] = make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u);
+}
+static __global__ void __launch_bounds__(256) k_set_filters(const int* __restrict__ idx, const unsigned* __restrict__ v, int count, uint4* __restrict__ filters)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) filters[idx[k]] = make_uint4(v[3 * k], v[3 * k + 1], v[3 * k + 2], 0u);
+}
+
 // ---- removal of bodies between steps (phx_world_remove_bodies / remove_outside) -----------------------------------------------
 // The result is defined as what phx_world_set_state would make of the filtered state (include/phyx_amd.h): kept bodies, manifolds
 // and joints stay in their old order, so every new position is an exclusive scan of keep flags.  keep[] holds one word per body;
@@ -440,9 +453,21 @@ static __global__ void __launch_bounds__(256) k_keep_inside(const float4* __rest
     }
 }
 
-__device__ __forceinline__ bool manifold_kept(const phx_manifold& m, const unsigned* __restrict__ keep) { return (keep[m.body1] & keep[m.body2]) != 0u; }
+// The compaction of the contact cache is shared by two callers, which differ in the KEEP PREDICATE: which manifolds stay, and where
+// their bodies go.  A removal keeps a manifold iff both of its bodies are kept and renumbers bodies through new[]; a change of collision
+// filters (phx_world_set_collision_filters) keeps it iff its pair passes the filters and leaves the bodies where they are.
+struct BodiesKept {
+    const unsigned* keep; const unsigned* bnew;
+    __device__ bool operator()(const phx_manifold& m) const { return (keep[m.body1] & keep[m.body2]) != 0u; }
+    __device__ int body(int b) const { return (int)bnew[b]; }
+};
+struct FilterKept {
+    const uint4* filters;      // per body {category, mask, group, 0}
+    __device__ bool operator()(const phx_manifold& m) const { return collision_filter_pass(filters[m.body1], filters[m.body2]); }
+    __device__ int body(int b) const { return b; }
+};
 
-// loaders of the three scans: a body is kept by its flag, a manifold iff both of its bodies are, a joint iff its manifold is
+// loaders of the three scans: a body is kept by its flag, a manifold by the predicate, a joint iff its manifold is
 struct BodyKeepLoad {
     static constexpr bool in_place = false;
     const unsigned* keep;
@@ -454,15 +479,15 @@ struct BodyKeepLoad {
         return true;
     }
 };
-struct ManifoldKeepLoad {
+template <class Keep> struct ManifoldKeepLoad {
     static constexpr bool in_place = false;
-    const phx_manifold* manifolds; const unsigned* keep;
-    __device__ unsigned operator()(int i) const { return manifold_kept(manifolds[i], keep) ? 1u : 0u; }
+    const phx_manifold* manifolds; Keep kept;
+    __device__ unsigned operator()(int i) const { return kept(manifolds[i]) ? 1u : 0u; }
 };
-struct JointKeepLoad {
+template <class Keep> struct JointKeepLoad {
     static constexpr bool in_place = false;
-    const phx_contact_joint* joints; const phx_manifold* manifolds; const unsigned* keep;
-    __device__ unsigned operator()(int j) const { return manifold_kept(manifolds[joints[j].contact_point_index >> 1], keep) ? 1u : 0u; }
+    const phx_contact_joint* joints; const phx_manifold* manifolds; Keep kept;
+    __device__ unsigned operator()(int j) const { return kept(manifolds[joints[j].contact_point_index >> 1]) ? 1u : 0u; }
 };
 
 // element i's flag from the exclusive scan of the flags (`total`: their sum)
@@ -474,11 +499,13 @@ __device__ __forceinline__ bool scanned_flag(const unsigned* __restrict__ before
 // Bodies: kept record i goes to out[to], to = bnew[i], as one 128-byte line, with `index` = to; the resident arrays (and the pending
 // accelerations) at `to` are made from it by the upload's own conversion (record_to_world), as phx_world_set_state would make them.
 // `refresh` (the records are stale): the record is first brought up to date from the resident arrays (world_record), as the getter
-// would.  remap[i] = to, or -1.  accel_nonzero counts the kept records with an acceleration (the upload's test, world.hip).
+// would.  remap[i] = to, or -1.  accel_nonzero counts the kept records with an acceleration (the upload's test, world.hip).  A collision
+// filter table (null while every filter is the default) moves with the bodies.
 static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_body* __restrict__ records, WorldBodies w, int n, int refresh,
                                                               const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
                                                               phx_rigid_body* __restrict__ out_records, WorldBodies out, float4* __restrict__ out_accel,
-                                                              int* __restrict__ remap, unsigned* __restrict__ accel_nonzero)
+                                                              int* __restrict__ remap, unsigned* __restrict__ accel_nonzero,
+                                                              const uint4* __restrict__ filters, uint4* __restrict__ out_filters)
 {
     static_assert(sizeof(phx_rigid_body) == 8 * sizeof(float4), "a record is one 128-byte line");
     unsigned nonzero = 0;
@@ -499,6 +526,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
 #pragma unroll
         for (int k = 0; k < 8; ++k) dst[k] = line[k];
         record_to_world(b, out, to);
+        if (filters) out_filters[to] = filters[i];
         if (out_accel) {
             out_accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;
@@ -511,19 +539,19 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
 // Manifolds with their two contact-point slots (32 bytes each, moved as two 16-byte halves): kept manifold i goes to to = mnew[i]
 // with its bodies remapped and point_index = 2 * to; a live slot's solver_index follows its joint (-1 if the joint goes), a dead
 // slot is copied as it is.  pairs[to] = the remapped body pair (the new broadphase pair set).
+template <class Keep>
 static __global__ void __launch_bounds__(256) k_remove_manifolds(const phx_manifold* __restrict__ manifolds, const phx_contact_point* __restrict__ cps, int nm,
-                                                                 const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
-                                                                 const unsigned* __restrict__ mnew, const unsigned* __restrict__ jnew,
+                                                                 Keep kept, const unsigned* __restrict__ mnew, const unsigned* __restrict__ jnew,
                                                                  const unsigned* __restrict__ jtotal, int nj, phx_manifold* __restrict__ out_manifolds,
                                                                  phx_contact_point* __restrict__ out_cps, uint2* __restrict__ pairs)
 {
     static_assert(sizeof(phx_contact_point) == 2 * sizeof(float4), "a contact point is two 16-byte halves");
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nm; i += gridDim.x * blockDim.x) {
         const phx_manifold m = manifolds[i];
-        if (!manifold_kept(m, keep)) continue;
+        if (!kept(m)) continue;
         const int to = (int)mnew[i];
         phx_manifold o;
-        o.body1 = (int)bnew[m.body1]; o.body2 = (int)bnew[m.body2]; o.point_count = m.point_count; o.point_index = 2 * to;
+        o.body1 = kept.body(m.body1); o.body2 = kept.body(m.body2); o.point_count = m.point_count; o.point_index = 2 * to;
         out_manifolds[to] = o;
         pairs[to] = make_uint2((unsigned)o.body1, (unsigned)o.body2);
         const float4* src = reinterpret_cast<const float4*>(cps) + 4 * (size_t)i;
@@ -545,17 +573,17 @@ static __global__ void __launch_bounds__(256) k_remove_manifolds(const phx_manif
 
 // Joints: kept joint j goes to jnew[j] with its bodies remapped and contact_point_index = 2 * (its manifold's new index) + old % 2;
 // the warm-start impulses are unchanged
+template <class Keep>
 static __global__ void __launch_bounds__(256) k_remove_joints(const phx_contact_joint* __restrict__ joints, int nj, const phx_manifold* __restrict__ manifolds,
-                                                              const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
-                                                              const unsigned* __restrict__ mnew, const unsigned* __restrict__ jnew,
+                                                              Keep kept, const unsigned* __restrict__ mnew, const unsigned* __restrict__ jnew,
                                                               phx_contact_joint* __restrict__ out)
 {
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < nj; j += gridDim.x * blockDim.x) {
         phx_contact_joint q = joints[j];
         const int mi = q.contact_point_index >> 1;
-        if (!manifold_kept(manifolds[mi], keep)) continue;
+        if (!kept(manifolds[mi])) continue;
         q.contact_point_index = 2 * (int)mnew[mi] + (q.contact_point_index & 1);
-        q.body1 = (int)bnew[q.body1]; q.body2 = (int)bnew[q.body2];
+        q.body1 = kept.body(q.body1); q.body2 = kept.body(q.body2);
         out[jnew[j]] = q;
     }
 }
