@@ -500,6 +500,39 @@ typedef struct { uint32_t category, mask; int32_t group; } phx_collision_filter;
 int  phx_world_set_collision_filters(phx_world* w, const int32_t* bodies, const phx_collision_filter* filters, int32_t count, int32_t* dropped);
 /* every body's filter, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
 int  phx_world_get_collision_filters(phx_world* w, phx_collision_filter* out, int32_t cap);
+/* MATERIALS — per-body friction and restitution.  Every body has a material {friction, restitution}; the default {0.3f, 0.0f} is the
+ * reference's kFrictionCoefficient (ref: Solver.cpp:9) and bounce (ref: Solver.cpp:658), and a world whose materials are all the default
+ * steps bit for bit as one that never heard of materials.
+ *   - Pair values: a contact between bodies a and b uses mu = (a.friction + b.friction) * 0.5f (one rounded sum, an exact halving) and
+ *     e = a.restitution > b.restitution ? a.restitution : b.restitution.  Both are exact on equal inputs: default bodies give exactly
+ *     0.3f and 0.  The two joints of a body pair share mu and e.
+ *   - RefreshJoints (ref: Solver.cpp:664-678): dv = -e * (relV.x * n.x + relV.y * n.y), relV built as the reference builds it from the
+ *     solve's body velocities (after IntegrateVelocity): pv1 = ((pos1.y - p1.y) * w1 + v1.x, (p1.x - pos1.x) * w1 + v1.y), the same for
+ *     body 2, relV = pv1 - pv2; dst = max(dv - 1, 0); dstVelocity = depth < 1 ? dst - 0.1f : dst.  Source order in both arithmetic forms
+ *     (RefreshJoints is never fused).  With e == 0 the result is +0 for every relV, so a joint whose e is 0 skips the velocity gathers.
+ *   - Impulse sweep (ref: Solver.cpp:873): the friction limit is accN * mu.  Nothing else changes: PreStep, the displacement sweeps,
+ *     the skip tests, the productive thresholds and the static tags stay as they are.
+ *   - Valid values: friction finite in [0, 1e6], restitution finite in [0, 1]; anything else is PHX_ERR_INVALID.
+ *   - Setting materials: the rules of the edits above.  Between steps only (PHX_ERR_STATE); checked completely before anything is queued
+ *     (count >= 0, no NULL array when count > 0, every index in [0, body count), none twice, every value valid; PHX_ERR_INVALID otherwise,
+ *     the world unchanged); staged through pinned memory and queued on phx_world_stream(w); before the first step it writes the
+ *     host-staged bodies' materials.  A new value applies from the next step's refresh.  It changes no topology: the cached schedule
+ *     stays in use (phx_solve_stats.recoloured == 0 on the next step).
+ *   - The other calls: add_body / add_bodies give new bodies the default material; remove_bodies / remove_outside move materials with
+ *     the kept bodies (through new[]); phx_world_set_state resets every material to the default (a world with materials is checkpointed
+ *     as set_state followed by set_materials); the edits, set_inverse_masses, collision filters, queries and contact reports leave them
+ *     alone.  The drop-in solver (phx_solver_solve*) keeps the reference's constants.
+ *   - Sharded worlds carry no materials: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and
+ *     phx_world_reslab return PHX_ERR_STATE while some body's material differs from the default.
+ *   - The fp16 body-state ablation (phx_solver_set_body_state_bits(phx_world_solver(w), 16)) does not support materials: a step of a
+ *     world where some material was ever set (since the last set_state) returns PHX_ERR_STATE.  So does the island trace
+ *     (phx_solver_set_trace): such a world's island kernel records none.
+ * The solver reads the table only in a world where some material was ever set (since the last set_state); every other world launches
+ * the kernels it always did.  Costs and the data path: DESIGN.md. */
+typedef struct { float friction, restitution; } phx_material;      /* 8 B; default {0.3f, 0.0f} */
+int  phx_world_set_materials(phx_world* w, const int32_t* bodies, const phx_material* materials, int32_t count);
+/* every body's material, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
+int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
 /* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
  * its AABB {aabb_min, aabb_max} and its box {pos, xvector = xv, yvector = yv, geom_size = h (half extents)} (UpdateGeom copies the

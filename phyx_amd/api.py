@@ -43,6 +43,8 @@ assert ray_hit_dtype.itemsize == 24
 contact_dtype = np.dtype([("other", "<i4"), ("manifold", "<i4"), ("slot", "<i4"), ("flags", "<i4"), ("point", "<f4", (2,)), ("normal", "<f4", (2,)),
                           ("normal_impulse", "<f4"), ("friction_impulse", "<f4")])                                     # phx_contact
 collision_filter_dtype = np.dtype([("category", "<u4"), ("mask", "<u4"), ("group", "<i4")])      # phx_collision_filter
+material_dtype = np.dtype([("friction", "<f4"), ("restitution", "<f4")])      # phx_material
+assert material_dtype.itemsize == 8
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
@@ -832,6 +834,30 @@ class World:
         """Every body's filter, in index order: an array of collision_filter_dtype."""
         out = np.zeros(self.counts()[0], dtype=collision_filter_dtype)
         check(self.L.phx_world_get_collision_filters(self.h, _ptr(out), len(out)))
+        return out
+
+    # ---- materials (include/phyx_amd.h MATERIALS; the specification: tests/material_spec.py) ----
+    def set_materials(self, bodies, friction=0.3, restitution=0.0):
+        """Give the listed bodies (each at most once) the material {friction, restitution}: each a scalar for all of them or one value per
+        body.  A contact uses mu = (fa + fb) * 0.5 and e = max(ea, eb) from the next step on; the library rejects friction outside
+        [0, 1e6], restitution outside [0, 1] and non-finite values (PhxError), the world unchanged."""
+        if isinstance(bodies, (list, tuple)) and not len(bodies):
+            bodies = np.zeros(0, dtype=np.int32)
+        idx = self._indices(bodies, "set_materials")
+        m = np.zeros(len(idx), dtype=material_dtype)
+        for name, v in (("friction", friction), ("restitution", restitution)):
+            a = np.asarray(v)
+            if a.dtype.kind not in "fiu":
+                raise TypeError("set_materials: %s must be numbers, got %s" % (name, a.dtype))
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != (len(idx),)):
+                raise ValueError("set_materials: %s must be a scalar or have shape (%d,), got %s" % (name, len(idx), a.shape))
+            m[name] = a
+        check(self.L.phx_world_set_materials(self.h, _ptr(idx), _ptr(m), len(idx)))
+
+    def materials(self):
+        """Every body's material, in index order: an array of material_dtype."""
+        out = np.zeros(self.counts()[0], dtype=material_dtype)
+        check(self.L.phx_world_get_materials(self.h, _ptr(out), len(out)))
         return out
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----

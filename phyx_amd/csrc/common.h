@@ -352,6 +352,8 @@ private:
 // pair through.  The rule (include/phyx_amd.h): a shared non-zero group decides alone (positive: collide, negative: never), otherwise
 // each body's mask must meet the other's category.  Selects, no branches: it sits inside the predicated sweep (broadphase.hip).
 constexpr unsigned FILTER_DEFAULT_CATEGORY = 1u, FILTER_DEFAULT_MASK = 0xFFFFFFFFu;
+// ---- materials (phx_world_set_materials): the reference's kFrictionCoefficient (ref: Solver.cpp:9) and bounce (ref: Solver.cpp:658) ----
+constexpr float MATERIAL_DEFAULT_FRICTION = 0.3f, MATERIAL_DEFAULT_RESTITUTION = 0.0f;
 __host__ __device__ __forceinline__ bool collision_filter_pass(uint4 a, uint4 b)
 {
     const bool shared = a.z == b.z && a.z != 0u;

@@ -69,11 +69,12 @@ struct IslandView {
     unsigned long long* next_ctl; int* next_executed; unsigned long long* next_visits; unsigned long long* next_shards;
 };
 
-// launches k_solve_islands<shape, body-state, trace> over `groups` workgroups (islands.hip)
-void launch_solve_islands(hipStream_t stream, int groups, bool big_shape, bool half_state, bool trace, const SolverView& v, const IslandView& iv,
-                          const BodyView& bodies, phx_contact_joint* joints, const phx_contact_point* cps, int ci, int pi);
+// launches k_solve_islands<shape, body-state, trace> over `groups` workgroups (islands.hip); mat: k_solve_islands_mat<shape> (materials,
+// v.mat: fp32 body state and no trace)
+void launch_solve_islands(hipStream_t stream, int groups, bool big_shape, bool half_state, bool trace, const SolverViewMat& v, const IslandView& iv,
+                          const BodyView& bodies, phx_contact_joint* joints, const phx_contact_point* cps, int ci, int pi, bool mat = false);
 
 // resident workgroups per CU of that instantiation (hipOccupancyMaxActiveBlocksPerMultiprocessor, cached; 0 if the query failed)
-int island_blocks_per_cu(bool big_shape, bool half_state);
+int island_blocks_per_cu(bool big_shape, bool half_state, bool mat = false);
 
 } // namespace phx

@@ -6,6 +6,8 @@
 #include "schedule.h"
 #include "comm.h"
 
+#include <type_traits>
+
 namespace phx {
 
 // device-side view of the solver state, passed by value to every kernel (layout: solver_kernels.h)
@@ -30,6 +32,14 @@ struct SolverView {
     int* imp_active;       // [iter] 1 if any joint was productive in sweep `iter`
     int* disp_active;
 };
+// the view of a solve with materials (include/phyx_amd.h MATERIALS), passed to the *_mat kernels only (the plain kernels' arguments stay
+// as they were): per body {friction, restitution}, and per HBM slot the unit's friction coefficient (k_pack_refresh_mat writes it, the
+// sweeps read a leader's)
+struct SolverViewMat : SolverView {
+    const float2* mat;
+    float* mu;
+};
+template <bool MAT> using ViewOf = typename std::conditional<MAT, SolverViewMat, SolverView>::type;
 
 // the interior units of partitioned components by part (schedule.h; solver_kernels.h k_solve_parts)
 struct PartsView {
@@ -78,6 +88,9 @@ public:
     int set_body_state_bits(int bits);
     int set_shard(int shard, int count);
     void set_schedule_reuse(bool on) { reuse_schedule_ = on; }
+    // World only (not part of the C ABI): the device table of per-body materials {friction, restitution} the next solves read, or null
+    // for the reference's constants (the plain kernels).  The table must hold the solve's nb bodies.
+    void set_materials(const float2* d_mat) { mat_ = d_mat; }
     void set_trace(int level) { trace_islands_ = level != 0; trace_waves_ = level != 1; }      // 1: phase stamps only; else also per-wave step cycles
     int get_island_trace(unsigned long long* out, int cap_groups, int* groups);
     int get_wave_trace(unsigned long long* out, int cap_words, int* waves_per_group);
@@ -153,6 +166,7 @@ private:
     int collect_stats(unsigned long long* extra = nullptr, const unsigned long long* extra_src = nullptr, const std::function<int()>* while_waiting = nullptr,
                       const MailCarrier* carrier = nullptr);
     SolverView view() const;
+    SolverViewMat view_mat() const { SolverViewMat m{}; static_cast<SolverView&>(m) = view(); m.mat = mat_; m.mu = hbm_.mu.p; return m; }
 
     int device_;
     hipStream_t stream_ = nullptr;
@@ -186,7 +200,7 @@ private:
     // per-sweep 'productive' flags, static tags, the bodies the HBM group touches
     struct HbmPath {
         DevBuf<float4> sb_imp, sb_disp, q0, q1, q2;
-        DevBuf<float> qn;
+        DevBuf<float> qn, mu;             // (mu: materials only)
         DevBuf<int4> q3;
         DevBuf<float2> acc, dd;
         DevBuf<int> order, static_slot, flags, hbm_body_list;
@@ -323,6 +337,7 @@ private:
     int last_ci_ = 0, last_pi_ = 0, last_island_mode_ = 0;
     long long sweep_launches_ = 0, schedule_version_ = 0;
     bool half_state_ = false, reuse_schedule_ = true;
+    const float2* mat_ = nullptr;        // set_materials
     bool owns_stream_ = true;
     int shard_ = 0, shard_count_ = 1;    // this handle sweeps groups g with g % shard_count_ == shard_ (the HBM group counts as group lds_groups)
     // (the deal of the groups to the ranks: exchange.h exchange_partition; shard_count_ == 1 owns everything)

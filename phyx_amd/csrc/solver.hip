@@ -150,7 +150,7 @@ bool DeviceSolver::verify_eligible(int groups, bool big_shape) const
     if (opt_.no_fused_verify || !opt_.speculate || shard_count_ != 1 || xch_send_ || groups <= 0) return false;
     // (LDS — 37 / 50 KB — and the 128-register budget admit 4 / 2 workgroups per CU; asked of the runtime for the instantiation
     //  at hand rather than assumed, and never more than that: the occupancy query has been seen one block high)
-    const int per_cu = std::min(island_blocks_per_cu(big_shape, half_state_), big_shape ? 2 : 4);
+    const int per_cu = std::min(island_blocks_per_cu(big_shape, half_state_, mat_ != nullptr), big_shape ? 2 : 4);
     return per_cu > 0 && groups <= per_cu * cu_count_ && groups < (int)ISL_BAD / 2;
 }
 
@@ -187,6 +187,7 @@ bool DeviceSolver::arm_cached_solve(const float4* d_mpos, int nb, const phx_cont
 //   post   FinishJoints, FinishBodies
 int DeviceSolver::enqueue_pre(const BodyView& d_bodies, int nb, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj)
 {
+    if (mat_ && nj && owns_hbm_group()) PHX_TRY(hbm_.mu.reserve(std::max<size_t>(hbm_.q0.cap, 1)));      // (the slots' friction coefficients)
     const SolverView v = view();
     // (the control words — productive flags, static tags, island counters — were cleared by launch_fingerprint's
     //  fingerprint kernel, which every solve runs first)
@@ -197,7 +198,8 @@ int DeviceSolver::enqueue_pre(const BodyView& d_bodies, int nb, const phx_contac
         hipLaunchKernelGGL(k_unpack_bodies, dim3(grid_for(hbm_bodies)), dim3(256), 0, stream_, d_bodies, (const int*)hbm_.hbm_body_list.p,
                            hbm_bodies, hbm_.sb_imp.p, hbm_.sb_disp.p, v.stamps);
         const int hb = sched_.hbm_begin(), he = sched_.hbm_end();
-        hipLaunchKernelGGL(k_pack_refresh, dim3(grid_for(he - hb)), dim3(256), 0, stream_, v, hb, he, d_joints, d_cps, hbm_.static_slot.p);
+        if (mat_) hipLaunchKernelGGL(k_pack_refresh_mat, dim3(grid_for(he - hb)), dim3(256), 0, stream_, view_mat(), hb, he, d_joints, d_cps, hbm_.static_slot.p);
+        else      hipLaunchKernelGGL(k_pack_refresh, dim3(grid_for(he - hb)), dim3(256), 0, stream_, v, hb, he, d_joints, d_cps, hbm_.static_slot.p);
         size_t c0 = 0;
         if (parts_in_use()) {          // the interior classes of partitioned components: one launch per level, a workgroup per part
             for (int level = 0; level < part_levels(); ++level) {
@@ -239,6 +241,7 @@ template <class Launch> static void with_halves(bool imp, bool disp, Launch laun
 int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, int ci, int pi, int mode_override)
 {
     const SolverView v = view();
+    const SolverViewMat vm = view_mat();      // (the *_mat kernels: materials set)
     const int iters = std::max(ci, pi);
     sweep_launches_ = 0;
     if (!nj) return PHX_OK;
@@ -273,7 +276,7 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
             iv.next_shards = isl_.shards.p + (size_t)next * SHARDS_SET;
             island_clears_next_ = false;
         }
-        if (trace_islands_) {
+        if (trace_islands_ && !mat_) {                // (the materials' island kernel has no trace form)
             // 8 words per group, then 8 words per wave (16 waves at most) of every group
             if (isl_.trace.reserve((size_t)std::max(lg, 1) * (8 + 128)) != PHX_OK) return PHX_ERR_HIP;
             PHX_HIP(hipMemsetAsync(isl_.trace.p, 0, (size_t)lg * (8 + 128) * sizeof(unsigned long long), stream_));
@@ -289,7 +292,7 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
             PHX_HIP(hipEventRecord(ev_fork_, stream_));
             PHX_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
         }
-        launch_solve_islands(forked ? side_stream_ : stream_, mine, big, half_state_, iv.trace != nullptr, v, iv, d_bodies, d_joints, d_cps, ci, pi);
+        launch_solve_islands(forked ? side_stream_ : stream_, mine, big, half_state_, iv.trace != nullptr, vm, iv, d_bodies, d_joints, d_cps, ci, pi, mat_ != nullptr);
         if (forked) PHX_HIP(hipEventRecord(ev_join_, side_stream_));
         ++sweep_launches_;
     }
@@ -303,10 +306,14 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
                     const PartsView pv = parts_view(level);
                     const dim3 g(pv.parts), b(PARTS_T);
                     with_halves(imp, disp, [&](auto I, auto D) {
-                        if (level == 0)    // a part's ~1000 units, class by class, the next class's constants requested a class ahead (solver_kernels.h)
-                            hipLaunchKernelGGL((k_solve_parts_ahead<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, pv, it);
-                        else               // a level-1 part has a few dozen units: a lane owns one, everything requested up front
-                            hipLaunchKernelGGL((k_solve_parts<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, pv, it);
+                        constexpr bool CI = decltype(I)::value, CD = decltype(D)::value;
+                        if (level == 0) {  // a part's ~1000 units, class by class, the next class's constants requested a class ahead (solver_kernels.h)
+                            if (mat_) hipLaunchKernelGGL((k_solve_parts_ahead_mat<CI, CD>), g, b, 0, stream_, vm, pv, it);
+                            else      hipLaunchKernelGGL((k_solve_parts_ahead<CI, CD>), g, b, 0, stream_, v, pv, it);
+                        } else {           // a level-1 part has a few dozen units: a lane owns one, everything requested up front
+                            if (mat_) hipLaunchKernelGGL((k_solve_parts_mat<CI, CD>), g, b, 0, stream_, vm, pv, it);
+                            else      hipLaunchKernelGGL((k_solve_parts<CI, CD>), g, b, 0, stream_, v, pv, it);
+                        }
                     });
                     ++sweep_launches_;
                 }
@@ -317,14 +324,16 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
                 const int cb = sched_.hbm_colour_offsets[c], ce = sched_.hbm_colour_offsets[c + 1], lead = sched_.hbm_class_leaders[c], foll = ce - cb - lead;
                 const dim3 g(std::max(1, std::min(div_up(lead, SOLVE_BLOCK), 8192))), b(SOLVE_BLOCK);
                 with_halves(imp, disp, [&](auto I, auto D) {
-                    hipLaunchKernelGGL((k_solve_colour<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, cb, lead, foll, c, it);
+                    if (mat_) hipLaunchKernelGGL((k_solve_colour_mat<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, vm, cb, lead, foll, c, it);
+                    else      hipLaunchKernelGGL((k_solve_colour<decltype(I)::value, decltype(D)::value>), g, b, 0, stream_, v, cb, lead, foll, c, it);
                 });
                 ++sweep_launches_;
             }
             if (tail < ncol) {
                 const int4* tab = parts_.class_tab.p;
                 with_halves(imp, disp, [&](auto I, auto D) {
-                    hipLaunchKernelGGL((k_solve_tail<decltype(I)::value, decltype(D)::value>), dim3(1), dim3(TAIL_T), 0, stream_, v, tab, tail, ncol - tail, it);
+                    if (mat_) hipLaunchKernelGGL((k_solve_tail_mat<decltype(I)::value, decltype(D)::value>), dim3(1), dim3(TAIL_T), 0, stream_, vm, tab, tail, ncol - tail, it);
+                    else      hipLaunchKernelGGL((k_solve_tail<decltype(I)::value, decltype(D)::value>), dim3(1), dim3(TAIL_T), 0, stream_, v, tab, tail, ncol - tail, it);
                 });
                 ++sweep_launches_;
             }
@@ -467,6 +476,7 @@ int DeviceSolver::solve_common(const Arrays& a, int nb, const void* d_cps, int n
     PHX_REQUIRE(cfg.solve_mode >= PHX_SOLVE_SCALAR && cfg.solve_mode <= PHX_SOLVE_AVX2, "unknown solve mode");
     PHX_REQUIRE(cfg.island_mode >= PHX_ISLAND_SINGLE && cfg.island_mode <= PHX_ISLAND_MULTIPLE_SLOPPY, "unknown island mode");
     PHX_REQUIRE(nj == 0 || (d_joints && d_cps), "null joints / contact points");
+    if (mat_ && half_state_) { set_error("materials are not supported with the fp16 body-state ablation"); return PHX_ERR_STATE; }
     PHX_REQUIRE((reinterpret_cast<uintptr_t>(a.view.vel) & 15u) == 0 && (reinterpret_cast<uintptr_t>(a.view.dvel) & 15u) == 0 && (reinterpret_cast<uintptr_t>(a.view.mpos) & 15u) == 0 &&
                 (reinterpret_cast<uintptr_t>(d_cps) & 15u) == 0, "device arrays must be 16-byte aligned");
     // an unverified solve on OTHER arrays is still in flight: settle it first (a repeat on the same arrays simply

@@ -197,8 +197,11 @@ struct JointConsts { float nx, ny, aN1, aN2, aF1, aF2, cimN, cimF, dstV, dstD; }
 
 // RefreshJoints (ref: Solver.cpp:642-693) of one joint with normal (k.nx, k.ny): fills the rest of k.  p1, p2 = {im, ii, pos.x, pos.y}.
 // bounce == 0 makes dv = -0 * (relV . n); max(dv - 1, 0) is then +0 for every finite or non-finite relV, so the velocity gathers of
-// :619-625 are dead and dropped.
-__device__ __forceinline__ void refresh_joint(JointConsts& k, float d1x, float d1y, float d2x, float d2y, const float4& p1, const float4& p2)
+// :619-625 are dead and dropped.  MAT (materials, include/phyx_amd.h): bounce is the pair's restitution e, and where e != 0 relV is
+// built from the solve's body velocities v1, v2 = {vx, vy, w, tag} exactly as :664-670 build it (never fused: -ffp-contract=off).
+template <bool MAT = false>
+__device__ __forceinline__ void refresh_joint(JointConsts& k, float d1x, float d1y, float d2x, float d2y, const float4& p1, const float4& p2,
+                                              float e = 0.f, const float4& v1 = float4{}, const float4& v2 = float4{})
 {
     const float pt1x = d1x + p1.z, pt1y = d1y + p1.w;
     const float pt2x = d2x + p2.z, pt2y = d2y + p2.w;
@@ -206,7 +209,14 @@ __device__ __forceinline__ void refresh_joint(JointConsts& k, float d1x, float d
     const Limiter N = refresh_limiter(k.nx, k.ny, d1x, d1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
     const Limiter F = refresh_limiter(-k.ny, k.nx, d1x, d1y, w2x, w2y, p1.x, p1.y, p2.x, p2.y);
     const float depth = (pt2x - pt1x) * k.nx + (pt2y - pt1y) * k.ny;
-    const float dst = 0.f;
+    float dst = 0.f;
+    if (MAT && e != 0.f) {
+        const float pv1x = (p1.w - pt1y) * v1.z + v1.x, pv1y = (pt1x - p1.z) * v1.z + v1.y;
+        const float pv2x = (p2.w - pt2y) * v2.z + v2.x, pv2y = (pt2x - p2.z) * v2.z + v2.y;
+        const float rvx = pv1x - pv2x, rvy = pv1y - pv2y;
+        const float dv = -e * (rvx * k.nx + rvy * k.ny);
+        dst = max_ref(dv - 1.f, 0.f);
+    }
     k.dstV = depth < 1.f ? dst - 0.1f : dst;
     k.dstD = 0.1f * max_ref(0.f, depth - 2.0f * 1.f);
     k.aN1 = N.a1; k.aN2 = N.a2; k.cimN = N.cim; k.aF1 = F.a1; k.aF2 = F.a2; k.cimF = F.cim;
@@ -229,7 +239,9 @@ __device__ __forceinline__ void prestep_joint(const JointConsts& k, float accN, 
 
 // The arithmetic of one impulse visit (ref: Solver.cpp:800-889) on the two bodies held in registers: the normal, then the friction
 // limiter.  Returns the two impulses applied; impulse_productive says whether the joint moved.  The skip test and the tags are the caller's.
-__device__ __forceinline__ float2 impulse_visit(const JointConsts& k, float& accN, float& accF, float4& B1, float4& B2, float im1, float ii1, float im2, float ii2)
+// mu: the pair's friction coefficient (kFrictionCoefficient = 0.3, ref: Solver.cpp:9, unless materials were set: include/phyx_amd.h)
+__device__ __forceinline__ float2 impulse_visit(const JointConsts& k, float& accN, float& accF, float4& B1, float4& B2, float im1, float ii1, float im2, float ii2,
+                                                float mu = 0.3f)
 {
     // (Measured and removed in the island kernel: the x / y halves of every body-wide step as v_pk_mul_f32 / v_pk_add_f32 on the register
     //  pairs a ds_read_b128 leaves — 24 VALU instructions fewer per unit of ~145, no extra moves, bit-exact — is 3 % SLOWER: the step is a
@@ -249,7 +261,7 @@ __device__ __forceinline__ float2 impulse_visit(const JointConsts& k, float& acc
     fv = mul_sub(-tx, B2.x, fv); fv = mul_sub(-ty, B2.y, fv); fv = mul_sub(k.aF2, B2.z, fv);
     float df = fv * k.cimF;
     const float force = accF + df;
-    const float limit = accN * 0.3f;
+    const float limit = accN * mu;
     const float signed_limit = force < 0.f ? -limit : limit;          // scalar flipsign, ref: SIMD_Scalar.h:265-268
     const float adjusted = signed_limit - accF;
     if (fabsf(force) > limit) df = adjusted;
@@ -278,10 +290,19 @@ __device__ __forceinline__ float displacement_visit(const JointConsts& k, float&
 }
 __device__ __forceinline__ bool displacement_productive(float di) { return fabsf(di) > 1e-4f; }      // ref: Solver.cpp:999
 
-static __global__ void __launch_bounds__(256) k_pack_refresh(SolverView v, int begin, int end, const phx_contact_joint* __restrict__ joints,
-                                                      const phx_contact_point* __restrict__ cps, const int* __restrict__ static_slot)
+// ---- materials (include/phyx_amd.h MATERIALS): the pair values of bodies a, b with {friction, restitution} ma, mb -------------------------
+// mu = (fa + fb) * 0.5 (one rounded sum, an exact halving), e = the larger restitution: both exact on equal inputs, so default bodies
+// give exactly kFrictionCoefficient and bounce = 0
+__device__ __forceinline__ float material_mu(float2 ma, float2 mb) { return (ma.x + mb.x) * 0.5f; }
+__device__ __forceinline__ float material_e(float2 ma, float2 mb) { return ma.y > mb.y ? ma.y : mb.y; }
+
+// PrepareJoints + RefreshJoints of the HBM group's slots.  MAT: the pair's e from v.mat, relV from the working copy sb_imp (k_unpack_bodies
+// ran before: it lists every body the group's joints touch, static ones included), and the pair's mu into v.mu for the sweeps.
+template <bool MAT>
+__device__ __forceinline__ void pack_refresh(const ViewOf<MAT>& v, int first, int stride, int end, const phx_contact_joint* __restrict__ joints,
+                                             const phx_contact_point* __restrict__ cps, const int* __restrict__ static_slot)
 {
-    for (int s = begin + blockIdx.x * blockDim.x + threadIdx.x; s < end; s += gridDim.x * blockDim.x) {
+    for (int s = first; s < end; s += stride) {
         phx_contact_joint j = joints[v.order[s]];
         // indices come from the caller's arrays; clamp so that a bad or stale record cannot fault (the host
         // validates them whenever it rebuilds the schedule and the fingerprint kernel poisons itself on a bad one)
@@ -291,7 +312,14 @@ static __global__ void __launch_bounds__(256) k_pack_refresh(SolverView v, int b
         JointConsts k;
         k.nx = cp.normal.x; k.ny = cp.normal.y;
         const float4 p1 = v.sb_par[j.body1], p2 = v.sb_par[j.body2];       // {im, ii, pos.x, pos.y}
-        refresh_joint(k, d1x, d1y, d2x, d2y, p1, p2);
+        if constexpr (MAT) {
+            const float2 m1 = v.mat[j.body1], m2 = v.mat[j.body2];
+            const float e = material_e(m1, m2);
+            float4 V1 = float4{}, V2 = float4{};
+            if (e != 0.f) { V1 = v.sb_imp[j.body1]; V2 = v.sb_imp[j.body2]; }
+            refresh_joint<true>(k, d1x, d1y, d2x, d2y, p1, p2, e, V1, V2);
+            v.mu[s] = material_mu(m1, m2);
+        } else refresh_joint(k, d1x, d1y, d2x, d2y, p1, p2);
 
         const int s1 = static_slot[j.body1], s2 = static_slot[j.body2];
         v.q0[s] = make_float4(k.nx, k.ny, k.aN1, k.aN2);
@@ -302,6 +330,17 @@ static __global__ void __launch_bounds__(256) k_pack_refresh(SolverView v, int b
         v.acc[s] = make_float2(j.normal_accumulated_impulse, j.friction_accumulated_impulse);
         v.dd[s] = make_float2(k.dstD, 0.f);
     }
+}
+
+static __global__ void __launch_bounds__(256) k_pack_refresh(SolverView v, int begin, int end, const phx_contact_joint* __restrict__ joints,
+                                                      const phx_contact_point* __restrict__ cps, const int* __restrict__ static_slot)
+{
+    pack_refresh<false>(v, begin + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, end, joints, cps, static_slot);
+}
+static __global__ void __launch_bounds__(256) k_pack_refresh_mat(SolverViewMat v, int begin, int end, const phx_contact_joint* __restrict__ joints,
+                                                          const phx_contact_point* __restrict__ cps, const int* __restrict__ static_slot)
+{
+    pack_refresh<true>(v, begin + blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, end, joints, cps, static_slot);
 }
 
 // ---- PreStepJoints (ref: Solver.cpp:697-758), one class: a lane applies its unit's leader, then its follower ----------
@@ -355,11 +394,15 @@ __device__ __forceinline__ void wave_tag_update(unsigned* words, bool want, int 
 }
 
 // the constants and accumulators of one slot, loaded up front (nothing here depends on the body gathers)
-struct HbmJoint { float4 a, f, c; int4 k; float2 acc, d; };
+// mu: the unit's friction coefficient (a leader's: the follower shares its body pair), 0.3 unless MAT
+struct HbmJoint { float4 a, f, c; int4 k; float2 acc, d; float mu; };
 
-__device__ __forceinline__ HbmJoint hbm_load(const SolverView& v, int s, bool imp_on, bool disp_on, bool follower)
+template <bool MAT = false>
+__device__ __forceinline__ HbmJoint hbm_load(const ViewOf<MAT>& v, int s, bool imp_on, bool disp_on, bool follower)
 {
     HbmJoint q;
+    if constexpr (MAT) q.mu = (imp_on && !follower) ? v.mu[s] : 0.3f;
+    else q.mu = 0.3f;
     if (follower) {                                        // of q2 / q3 a follower needs its own 1 / (normal mass) only: 4 bytes instead of 32
         q.k = make_int4(0, 0, 0, 0);
         q.c = make_float4(v.qn[s], 0.f, 0.f, 0.f);
@@ -375,7 +418,7 @@ __device__ __forceinline__ HbmJoint hbm_load(const SolverView& v, int s, bool im
 __device__ __forceinline__ void solve_one(const SolverView& v, int s, HbmJoint& q, int colour, int iter, bool imp_on, bool disp_on,
                                           float4& B1, float4& B2, float4& D1, float4& D2, float im1, float ii1, float im2, float ii2, bool st1, bool st2, int ss,
                                           bool sp_imp, bool sp_disp,
-                                          bool& any_imp, bool& any_disp, bool& tag_imp, bool& tag_disp, bool& dirty_imp, bool& dirty_disp)
+                                          bool& any_imp, bool& any_disp, bool& tag_imp, bool& tag_disp, bool& dirty_imp, bool& dirty_disp, float mu)
 {
     // sp_imp / sp_disp: 'the unit's static body was productive' (static_productive) — read once per unit: a class cannot
     // change what the test returns for that class (tags raised in it carry the class itself, which is not 'earlier')
@@ -386,7 +429,7 @@ __device__ __forceinline__ void solve_one(const SolverView& v, int s, HbmJoint& 
         const bool p2 = st2 ? sp_imp : (__float_as_int(B2.w) > iter - 2);
         if (p1 || p2) {
             float2 acc = q.acc;
-            const float2 d = impulse_visit(k, acc.x, acc.y, B1, B2, im1, ii1, im2, ii2);
+            const float2 d = impulse_visit(k, acc.x, acc.y, B1, B2, im1, ii1, im2, ii2, mu);
             v.acc[s] = acc;
             if (impulse_productive(d)) {
                 B1.w = __int_as_float(iter); B2.w = __int_as_float(iter);
@@ -428,11 +471,11 @@ __device__ __forceinline__ void hbm_unit_step(const SolverView& v, int s0, HbmJo
     bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
     const bool sp_imp = DO_IMP && (st1 || st2) && sp(true);
     const bool sp_disp = disp_on && (st1 || st2) && sp(false);
-    solve_one(v, s0, q0, colour, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+    solve_one(v, s0, q0, colour, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp, q0.mu);
     if (has2) {                                        // a static body's record is never stored: the follower must see it untouched
         if (st1) { B1 = S1; D1 = T1; }
         if (st2) { B2 = S2; D2 = T2; }
-        solve_one(v, s1, q1, colour, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+        solve_one(v, s1, q1, colour, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, st1, st2, ss, sp_imp, sp_disp, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp, q0.mu);
     }
     if (dirty_imp) { if (!st1) v.sb_imp[b1] = B1; if (!st2) v.sb_imp[b2] = B2; }
     if (dirty_disp) { if (!st1) v.sb_disp[b1] = D1; if (!st2) v.sb_disp[b2] = D2; }
@@ -444,8 +487,8 @@ __device__ __forceinline__ void hbm_unit_step(const SolverView& v, int s0, HbmJo
 
 // one class: `leaders` leader slots from `begin`, then `followers` follower slots; lane i sweeps leader i, then follower i
 // on the same two bodies (schedule.h) — one gather and one scatter of the body state per unit
-template <bool DO_IMP, bool DO_DISP>
-static __global__ void __launch_bounds__(SOLVE_BLOCK) k_solve_colour(SolverView v, int begin, int leaders, int followers, int colour, int iter)
+template <bool DO_IMP, bool DO_DISP, bool MAT>
+__device__ __forceinline__ void solve_colour_body(const ViewOf<MAT>& v, int first, int stride, int begin, int leaders, int followers, int colour, int iter)
 {
     // A sweep after an unproductive sweep skips every joint (all tags <= iter-2), which is why the reference may
     // stop there (ref: Solver.cpp:189, 210).  The impulse half needs no flag for that — each joint's own skip
@@ -455,11 +498,11 @@ static __global__ void __launch_bounds__(SOLVE_BLOCK) k_solve_colour(SolverView 
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
 
     bool any_imp = false, any_disp = false;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < leaders; i += gridDim.x * blockDim.x) {
+    for (int i = first; i < leaders; i += stride) {      // (first, stride: blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x)
         const bool has2 = i < followers;
         const int s0 = begin + i, s1 = begin + leaders + i;
-        HbmJoint q0 = hbm_load(v, s0, imp_on, disp_on, false), q1{};
-        if (has2) q1 = hbm_load(v, s1, imp_on, disp_on, true);
+        HbmJoint q0 = hbm_load<MAT>(v, s0, imp_on, disp_on, false), q1{};
+        if (has2) q1 = hbm_load<MAT>(v, s1, imp_on, disp_on, true);
         const int b1 = q0.k.y, b2 = q0.k.z, ss = q0.k.w;
         float4 B1 = make_float4(0.f, 0.f, 0.f, 0.f), B2 = B1, D1 = B1, D2 = B1;
         if (imp_on) { B1 = v.sb_imp[b1]; B2 = v.sb_imp[b2]; }
@@ -470,6 +513,18 @@ static __global__ void __launch_bounds__(SOLVE_BLOCK) k_solve_colour(SolverView 
     // any(productive) of the sweep (ref: Solver.cpp:913, 1017): one store per wave that saw one
     if (DO_IMP && __any(any_imp) && (threadIdx.x & 63) == 0) v.imp_active[iter] = 1;
     if (DO_DISP && __any(any_disp) && (threadIdx.x & 63) == 0) v.disp_active[iter] = 1;
+}
+
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(SOLVE_BLOCK) k_solve_colour(SolverView v, int begin, int leaders, int followers, int colour, int iter)
+{
+    solve_colour_body<DO_IMP, DO_DISP, false>(v, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, begin, leaders, followers, colour, iter);
+}
+// the same with materials (v.mu: the units' friction coefficients, k_pack_refresh_mat)
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(SOLVE_BLOCK) k_solve_colour_mat(SolverViewMat v, int begin, int leaders, int followers, int colour, int iter)
+{
+    solve_colour_body<DO_IMP, DO_DISP, true>(v, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, begin, leaders, followers, colour, iter);
 }
 
 // ---- the TAIL of the HBM group's classes in one launch, one workgroup (round 6) ---------------------------------------------------------
@@ -495,8 +550,8 @@ __device__ __forceinline__ bool static_productive_words(unsigned prev, unsigned 
     return (cur >> 16) == (unsigned)(iter + 1) && (0xFFFFu - (cur & 0xFFFFu)) < (unsigned)colour;
 }
 
-template <bool DO_IMP, bool DO_DISP>
-__device__ __forceinline__ void tail_body(const SolverView& v, const int4* s_tab, int c_first, int nclass, int iter)
+template <bool DO_IMP, bool DO_DISP, bool MAT>
+__device__ __forceinline__ void tail_body(const ViewOf<MAT>& v, const int4* s_tab, int c_first, int nclass, int iter)
 {
     const int tid = threadIdx.x;
     bool any_imp = false, any_disp = false;
@@ -509,8 +564,8 @@ __device__ __forceinline__ void tail_body(const SolverView& v, const int4* s_tab
         const int u = r.have ? tid : 0;
         const bool has2 = u < tab.z;
         const int s0 = tab.x + u, s1 = tab.x + tab.y + u;
-        r.q0 = hbm_load(v, s0, DO_IMP, DO_DISP, false);
-        r.q1 = hbm_load(v, has2 ? s1 : s0, DO_IMP, DO_DISP, true);
+        r.q0 = hbm_load<MAT>(v, s0, DO_IMP, DO_DISP, false);
+        r.q1 = hbm_load<MAT>(v, has2 ? s1 : s0, DO_IMP, DO_DISP, true);
         r.s0 = s0; r.s1 = has2 ? s1 : -1;
     };
     auto gather = [&](TailUnit& r) {                            // (r's constants have arrived: requested a class ago, behind a barrier since)
@@ -551,16 +606,28 @@ __device__ __forceinline__ void tail_body(const SolverView& v, const int4* s_tab
 }
 
 // class_tab: the HBM group's class table (solver.h PartsView); classes [c_first, c_first + nclass), each of at most TAIL_T units
-template <bool DO_IMP, bool DO_DISP>
-static __global__ void __launch_bounds__(TAIL_T) k_solve_tail(SolverView v, const int4* __restrict__ class_tab, int c_first, int nclass, int iter)
+template <bool DO_IMP, bool DO_DISP, bool MAT>
+__device__ __forceinline__ void solve_tail_entry(const ViewOf<MAT>& v, const int4* __restrict__ class_tab, int c_first, int nclass, int iter, int4* s_tab)
 {
-    __shared__ int4 s_tab[TAIL_CLASSES_MAX];
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
     if (!DO_IMP && !disp_on) return;
     if ((int)threadIdx.x < nclass) s_tab[threadIdx.x] = class_tab[c_first + threadIdx.x];
     __syncthreads();
-    if (DO_DISP && disp_on) tail_body<DO_IMP, true>(v, s_tab, c_first, nclass, iter);
-    else if (DO_IMP)        tail_body<true, false>(v, s_tab, c_first, nclass, iter);
+    if (DO_DISP && disp_on) tail_body<DO_IMP, true, MAT>(v, s_tab, c_first, nclass, iter);
+    else if (DO_IMP)        tail_body<true, false, MAT>(v, s_tab, c_first, nclass, iter);
+}
+
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(TAIL_T) k_solve_tail(SolverView v, const int4* __restrict__ class_tab, int c_first, int nclass, int iter)
+{
+    __shared__ int4 s_tab[TAIL_CLASSES_MAX];
+    solve_tail_entry<DO_IMP, DO_DISP, false>(v, class_tab, c_first, nclass, iter, s_tab);
+}
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(TAIL_T) k_solve_tail_mat(SolverViewMat v, const int4* __restrict__ class_tab, int c_first, int nclass, int iter)
+{
+    __shared__ int4 s_tab[TAIL_CLASSES_MAX];
+    solve_tail_entry<DO_IMP, DO_DISP, true>(v, class_tab, c_first, nclass, iter, s_tab);
 }
 
 // ---- the interior classes of partitioned components: ONE launch per sweep (schedule.h) ------------------------------------
@@ -622,9 +689,9 @@ __device__ __forceinline__ void part_unit_step(const SolverView& v, float4* s_im
     if (DO_DISP) { if (disp_on) { D1 = s_disp[b1]; D2 = s_disp[b2]; } }
     const float im1 = q0.c.y, ii1 = q0.c.z, im2 = q0.c.w, ii2 = __int_as_float(q0.k.x);
     bool tag_imp = false, tag_disp = false, dirty_imp = false, dirty_disp = false;
-    solve_one(v, s0, q0, c, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+    solve_one(v, s0, q0, c, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp, q0.mu);
     if (s1 >= 0)
-        solve_one(v, s1, q1, c, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp);
+        solve_one(v, s1, q1, c, iter, DO_IMP, disp_on, B1, B2, D1, D2, im1, ii1, im2, ii2, false, false, -1, false, false, any_imp, any_disp, tag_imp, tag_disp, dirty_imp, dirty_disp, q0.mu);
     if (DO_IMP) { if (dirty_imp) { s_imp[b1] = B1; s_imp[b2] = B2; } }
     if (DO_DISP) { if (dirty_disp) { s_disp[b1] = D1; s_disp[b2] = D2; } }
 }
@@ -632,12 +699,9 @@ __device__ __forceinline__ void part_unit_step(const SolverView& v, float4* s_im
 // The level-1 launch (a part there has a few dozen units): lane t owns the part's t-th unit and requests its constants together with the
 // part's bodies — one memory round trip for the whole launch instead of one per class; units beyond the lanes (a part with more than
 // PARTS_T of them) are requested in their class step.
-template <bool DO_IMP, bool DO_DISP>
-static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, PartsView pv, int iter)
+template <bool DO_IMP, bool DO_DISP, bool MAT>
+__device__ __forceinline__ void solve_parts_body(const ViewOf<MAT>& v, const PartsView& pv, int iter, float4* s_imp, float4* s_disp, int4* s_tab, int4* s_rg)
 {
-    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
-    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
-    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
     const int part = pv.first_part + (int)blockIdx.x, tid = threadIdx.x;
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
@@ -657,8 +721,8 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, Pa
             if (u < n) {
                 own_c = pv.c0 + k;
                 own_s0 = u < n2 ? rg.x + u : rg.z + (u - n2);
-                own_q0 = hbm_load(v, own_s0, DO_IMP, disp_on, false);
-                if (u < n2) { own_s1 = tab.x + tab.y + (own_s0 - tab.x); own_q1 = hbm_load(v, own_s1, DO_IMP, disp_on, true); }
+                own_q0 = hbm_load<MAT>(v, own_s0, DO_IMP, disp_on, false);
+                if (u < n2) { own_s1 = tab.x + tab.y + (own_s0 - tab.x); own_q1 = hbm_load<MAT>(v, own_s1, DO_IMP, disp_on, true); }
             }
             before += n;
         }
@@ -674,8 +738,8 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, Pa
             const bool has2 = u < n2;
             const int s0 = has2 ? rg.x + u : rg.z + (u - n2), i = s0 - tab.x;
             const int s1 = has2 ? tab.x + tab.y + i : -1;
-            HbmJoint q0 = hbm_load(v, s0, DO_IMP, disp_on, false), q1{};
-            if (has2) q1 = hbm_load(v, s1, DO_IMP, disp_on, true);
+            HbmJoint q0 = hbm_load<MAT>(v, s0, DO_IMP, disp_on, false), q1{};
+            if (has2) q1 = hbm_load<MAT>(v, s1, DO_IMP, disp_on, true);
             part_unit_step<DO_IMP, DO_DISP>(v, s_imp, s_disp, base, s0, s1, q0, q1, c, iter, disp_on, any_imp, any_disp);
         }
         before += n;
@@ -684,6 +748,23 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, Pa
     part_store<DO_IMP, DO_DISP>(v, base, disp_on, s_imp, s_disp);
     if (DO_IMP && __any(any_imp) && (threadIdx.x & 63) == 0) v.imp_active[iter] = 1;
     if (DO_DISP && __any(any_disp) && (threadIdx.x & 63) == 0) v.disp_active[iter] = 1;
+}
+
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(PARTS_T) k_solve_parts(SolverView v, PartsView pv, int iter)
+{
+    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
+    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
+    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
+    solve_parts_body<DO_IMP, DO_DISP, false>(v, pv, iter, s_imp, s_disp, s_tab, s_rg);
+}
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_mat(SolverViewMat v, PartsView pv, int iter)
+{
+    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
+    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
+    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
+    solve_parts_body<DO_IMP, DO_DISP, true>(v, pv, iter, s_imp, s_disp, s_tab, s_rg);
 }
 
 // ---- the same sweep of a level's parts with the NEXT class's constants requested a class ahead (round 6, level 0) ------------------------
@@ -702,8 +783,8 @@ struct PartUnit { HbmJoint q0, q1; int s0, s1; bool have; };
 
 // the body with BOTH halves decided at compile time: the displacement half's run-time gate (dead after the first sweep of a resting pile)
 // is taken once, by the kernel below — a request under a branch, even a uniform one, would be waited for where the branches join
-template <bool DO_IMP, bool DO_DISP>
-__device__ __forceinline__ void parts_ahead_body(const SolverView& v, const PartsView& pv, int iter, float4* s_imp, float4* s_disp, const int4* s_tab, const int4* s_rg,
+template <bool DO_IMP, bool DO_DISP, bool MAT>
+__device__ __forceinline__ void parts_ahead_body(const ViewOf<MAT>& v, const PartsView& pv, int iter, float4* s_imp, float4* s_disp, const int4* s_tab, const int4* s_rg,
                                                  int base, int nclass)
 {
     const int tid = threadIdx.x;
@@ -722,8 +803,8 @@ __device__ __forceinline__ void parts_ahead_body(const SolverView& v, const Part
         const bool has2 = u < n2;
         const int s0 = has2 ? rg.x + u : rg.z + (u - n2);      // (a class with no unit in this part: slot 0 — some joint's row, read and dropped)
         const int s1 = tab.x + tab.y + (s0 - tab.x);
-        r.q0 = hbm_load(v, s0, DO_IMP, DO_DISP, false);
-        r.q1 = hbm_load(v, has2 ? s1 : s0, DO_IMP, DO_DISP, true);
+        r.q0 = hbm_load<MAT>(v, s0, DO_IMP, DO_DISP, false);
+        r.q1 = hbm_load<MAT>(v, has2 ? s1 : s0, DO_IMP, DO_DISP, true);
         r.s0 = s0; r.s1 = has2 ? s1 : -1;
     };
     auto sweep = [&](PartUnit& r, int c) {
@@ -747,12 +828,9 @@ __device__ __forceinline__ void parts_ahead_body(const SolverView& v, const Part
     if (DO_DISP && __any(any_disp) && (threadIdx.x & 63) == 0) v.disp_active[iter] = 1;
 }
 
-template <bool DO_IMP, bool DO_DISP>
-static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_ahead(SolverView v, PartsView pv, int iter)
+template <bool DO_IMP, bool DO_DISP, bool MAT>
+__device__ __forceinline__ void parts_ahead_entry(const ViewOf<MAT>& v, const PartsView& pv, int iter, float4* s_imp, float4* s_disp, int4* s_tab, int4* s_rg)
 {
-    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
-    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
-    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
     const int part = pv.first_part + (int)blockIdx.x;
     if (pv.part_begin[part] == pv.part_begin[part + 1]) return;      // nothing of a partitioned component in this part
     const bool disp_on = DO_DISP && (iter == 0 || v.disp_active[iter - 1] != 0);
@@ -761,8 +839,25 @@ static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_ahead(SolverView
     const int nclass = min(pv.c1 - pv.c0, PARTS_CLASS_STRIDE);
     if (nclass <= 0) return;
     part_stage<DO_IMP, DO_DISP>(v, pv, part, base, nclass, disp_on, s_tab, s_rg, s_imp, s_disp);
-    if (DO_DISP && disp_on) parts_ahead_body<DO_IMP, true>(v, pv, iter, s_imp, s_disp, s_tab, s_rg, base, nclass);
-    else if (DO_IMP)        parts_ahead_body<true, false>(v, pv, iter, s_imp, s_disp, s_tab, s_rg, base, nclass);
+    if (DO_DISP && disp_on) parts_ahead_body<DO_IMP, true, MAT>(v, pv, iter, s_imp, s_disp, s_tab, s_rg, base, nclass);
+    else if (DO_IMP)        parts_ahead_body<true, false, MAT>(v, pv, iter, s_imp, s_disp, s_tab, s_rg, base, nclass);
+}
+
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_ahead(SolverView v, PartsView pv, int iter)
+{
+    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
+    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
+    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
+    parts_ahead_entry<DO_IMP, DO_DISP, false>(v, pv, iter, s_imp, s_disp, s_tab, s_rg);
+}
+template <bool DO_IMP, bool DO_DISP>
+static __global__ void __launch_bounds__(PARTS_T) k_solve_parts_ahead_mat(SolverViewMat v, PartsView pv, int iter)
+{
+    __shared__ float4 s_imp[DO_IMP ? PART_BODIES : 1];
+    __shared__ float4 s_disp[DO_DISP ? PART_BODIES : 1];
+    __shared__ int4 s_tab[PARTS_CLASS_STRIDE], s_rg[PARTS_CLASS_STRIDE];
+    parts_ahead_entry<DO_IMP, DO_DISP, true>(v, pv, iter, s_imp, s_disp, s_tab, s_rg);
 }
 
 // PreStepJoints of the interior classes, the same way (k_prestep's arithmetic and order)

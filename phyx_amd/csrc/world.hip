@@ -83,6 +83,10 @@ public:
     int set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped);
     int get_collision_filters(phx_collision_filter* out, int cap);
     int refuse_filters(const char* what);      // PHX_ERR_STATE if some body's filter is not the default (the sharded modes carry none)
+    // materials (phx_world_set_materials / get_materials): between steps; they change no topology
+    int set_materials(const int32_t* bodies, const phx_material* materials, int count);
+    int get_materials(phx_material* out, int cap);
+    int refuse_materials(const char* what);    // PHX_ERR_STATE if some body's material is not the default (the sharded modes carry none)
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -175,7 +179,7 @@ private:
         DevBuf<phx_rigid_body> bodies;
         DevBuf<float4> vel, dvel, mpos, frame, aabb, accel;
         DevBuf<uint4> filters;
-        DevBuf<float2> size;
+        DevBuf<float2> size, materials;
         DevBuf<phx_manifold> manifolds;
         DevBuf<phx_contact_point> cps;
         DevBuf<phx_contact_joint> joints;
@@ -200,6 +204,14 @@ private:
     DevBuf<uint4> filt_;
     std::vector<uint4> host_filters_;
     int filters_to_host();               // the bodies become host-staged: so do their filters
+    // materials: one {friction, restitution} per body (include/phyx_amd.h MATERIALS), kept the way the filters are.  materials_active_ is
+    // conservative and picks the solver's material kernels (DeviceSolver::set_materials); while the bodies are host-staged host_mat_ is the
+    // truth, otherwise mat_ (grown, appended, compacted with the body buffers)
+    bool materials_active_ = false;
+    DevBuf<float2> mat_;
+    std::vector<float2> host_mat_;
+    int materials_to_host();             // the bodies become host-staged: so do their materials
+    int staged_to_host() { PHX_TRY(filters_to_host()); return materials_to_host(); }
 };
 
 World::~World()
@@ -252,19 +264,20 @@ int World::add_body(float px, float py, float angle, float sx, float sy)
 {
     if (!bodies_dirty_ && d_bodies_.p) {
         if (!host_bodies_.empty()) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
-        PHX_TRY(filters_to_host());
+        PHX_TRY(staged_to_host());
     }
     phx_rigid_body b = body_record(px, py, angle, sx, sy);
     b.index = (uint32_t)host_bodies_.size();
     host_bodies_.push_back(b);
     if (filters_active_) host_filters_.push_back(make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u));
+    if (materials_active_) host_mat_.push_back(make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION));
     bodies_dirty_ = true;
     return (int)host_bodies_.size() - 1;
 }
 
 int World::set_static(int body)
 {
-    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(filters_to_host()); }
+    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(staged_to_host()); }
     host_bodies_[body].inv_mass = 0.f;
     host_bodies_[body].inv_inertia = 0.f;
     bodies_dirty_ = true;
@@ -273,7 +286,7 @@ int World::set_static(int body)
 
 int World::set_inverse_mass(int body, float inv_mass, float inv_inertia)
 {
-    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(filters_to_host()); }
+    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(staged_to_host()); }
     host_bodies_[body].inv_mass = inv_mass;
     host_bodies_[body].inv_inertia = inv_inertia;
     bodies_dirty_ = true;
@@ -308,8 +321,13 @@ int World::sync_bodies_to_device()
         PHX_TRY(filt_.reserve(n));
         if (!host_filters_.empty()) PHX_HIP(hipMemcpyAsync(filt_.p, host_filters_.data(), host_filters_.size() * sizeof(uint4), hipMemcpyHostToDevice, stream_));
     }
+    if (materials_active_) {
+        PHX_TRY(mat_.reserve(n));
+        if (!host_mat_.empty()) PHX_HIP(hipMemcpyAsync(mat_.p, host_mat_.data(), host_mat_.size() * sizeof(float2), hipMemcpyHostToDevice, stream_));
+    }
     PHX_HIP(hipStreamSynchronize(stream_));
     host_filters_.clear();
+    host_mat_.clear();
     bodies_dirty_ = false;
     records_stale_ = false;
     ++geom_epoch_;
@@ -496,6 +514,7 @@ int World::solve(const phx_config& cfg, bool settle)                        // r
     // island sharding: the solver sweeps only this rank's groups (DeviceSolver::set_shard); the other groups' bodies
     // keep their velocities here
     if (!joints_changed_) PHX_TRY(solver_.cancel_prelabel());              // (no rebuild will pick the side stream's bins up)
+    solver_.set_materials(materials_active_ ? (const float2*)mat_.p : nullptr);      // (the table moves with spawns and removals: handed over every solve)
     PHX_TRY(solver_.solve_resident(resident().s, nb(), d_cps_.p, 2 * nm, d_joints_.p, nj, cfg, joints_changed_));
     joints_changed_ = false;
     // a solve that is still unverified (it ran speculatively on the cached schedule, or on a device-built schedule whose 'every
@@ -805,6 +824,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
     filters_active_ = false; host_filters_.clear();                         // every filter is the default again
+    materials_active_ = false; host_mat_.clear();                           // ... and every material
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -1076,6 +1096,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(spare_.frame.reserve((size_t)n)); PHX_TRY(spare_.aabb.reserve((size_t)n)); PHX_TRY(spare_.size.reserve((size_t)n));
     if (pending_accel) PHX_TRY(spare_.accel.reserve((size_t)n));
     if (filters_active_) PHX_TRY(spare_.filters.reserve((size_t)n));
+    if (materials_active_) PHX_TRY(spare_.materials.reserve((size_t)n));
     PHX_TRY(compaction_scratch());
     // 1. keep flags per body
     if (box) {
@@ -1096,7 +1117,8 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     const WorldBodies out{BodyView{spare_.vel.p, spare_.dvel.p, spare_.mpos.p}, spare_.frame.p, spare_.aabb.p, spare_.size.p};
     hipLaunchKernelGGL(k_remove_bodies, dim3(rgrid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)d_bodies_.p, resident(), n, records_stale_ ? 1 : 0,
                        (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, spare_.bodies.p, out, pending_accel ? spare_.accel.p : (float4*)nullptr,
-                       rm_remap_.p, rm_counts_.p + 3, filters_active_ ? (const uint4*)filt_.p : (const uint4*)nullptr, spare_.filters.p);
+                       rm_remap_.p, rm_counts_.p + 3, filters_active_ ? (const uint4*)filt_.p : (const uint4*)nullptr, spare_.filters.p,
+                       materials_active_ ? (const float2*)mat_.p : (const float2*)nullptr, spare_.materials.p);
     PHX_TRY(queue_compaction(kept));
     PHX_HIP(hipGetLastError());
     PHX_TRY(contacts_.remap_baseline(rm_remap_.p, rm_counts_.p + 4, stream_));      // (the events' baseline through new[]: [4] its new size)
@@ -1113,6 +1135,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     std::swap(vel_, spare_.vel); std::swap(dvel_, spare_.dvel); std::swap(mpos_, spare_.mpos); std::swap(frame_, spare_.frame); std::swap(aabb_, spare_.aabb); std::swap(size_, spare_.size);
     if (pending_accel) std::swap(accel_, spare_.accel);
     if (filters_active_) std::swap(filt_, spare_.filters);
+    if (materials_active_) std::swap(mat_, spare_.materials);
     std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
     host_bodies_.resize((size_t)kept_bodies);                               // (only its size counts while the device copy is the world)
     ++geom_epoch_;
@@ -1173,10 +1196,11 @@ int World::add_bodies(const float* spawn, int count, int* first)
     PHX_TRY(frame_.reserve_keep(total, n, stream_)); PHX_TRY(aabb_.reserve_keep(total, n, stream_)); PHX_TRY(size_.reserve_keep(total, n, stream_));
     if (accel_pending_) PHX_TRY(accel_.reserve_keep(total, n, stream_));
     if (filters_active_) PHX_TRY(filt_.reserve_keep(total, n, stream_));
+    if (materials_active_) PHX_TRY(mat_.reserve_keep(total, n, stream_));
     const int* unused = nullptr; const float* d_rows = nullptr;
     PHX_TRY(stage_batch(nullptr, spawn_rows_.data(), count, SPAWN_ROW, &unused, &d_rows));
     hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), d_bodies_.p, accel_pending_ ? accel_.p : (float4*)nullptr,
-                       filters_active_ ? filt_.p : (uint4*)nullptr);
+                       filters_active_ ? filt_.p : (uint4*)nullptr, materials_active_ ? mat_.p : (float2*)nullptr);
     PHX_HIP(hipGetLastError());
     host_bodies_.resize(total);                                             // (only its size counts while the device copy is the world)
     ++geom_epoch_;
@@ -1303,6 +1327,90 @@ int World::refuse_filters(const char* what)
             return PHX_ERR_STATE;
         }
     filters_active_ = false; host_filters_.clear();                         // (every filter is the default again: the plain sweep)
+    return PHX_OK;
+}
+
+// ---- materials --------------------------------------------------------------------------------------------------------------------
+// The pair rule and the defaults: include/phyx_amd.h MATERIALS.  The table is read by the solver's material kernels only
+// (solver_kernels.h k_pack_refresh_mat and the *_mat sweeps, island_kernel.h k_solve_islands_mat); nothing of the topology depends on it.
+int World::materials_to_host()
+{
+    if (!materials_active_) return PHX_OK;
+    host_mat_.resize((size_t)nb());
+    if (!nb()) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_HIP(hipStreamSynchronize(stream_));
+    PHX_HIP(hipMemcpy(host_mat_.data(), mat_.p, (size_t)nb() * sizeof(float2), hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int World::set_materials(const int32_t* bodies, const phx_material* materials, int count)
+{
+    static const char* const what = "phx_world_set_materials";
+    static_assert(sizeof(phx_material) == sizeof(float2), "a material is staged as two 4-byte words");
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no materials", what); return PHX_ERR_STATE; }
+    PHX_TRY(check_batch(what, bodies, materials, count, true));
+    for (int k = 0; k < count; ++k) {                                       // (NaN fails both comparisons)
+        const float f = materials[k].friction, e = materials[k].restitution;
+        if (!(f >= 0.f && f <= 1e6f)) { set_error("%s: friction %g of body %d is not in [0, 1e6]", what, (double)f, bodies[k]); return PHX_ERR_INVALID; }
+        if (!(e >= 0.f && e <= 1.f)) { set_error("%s: restitution %g of body %d is not in [0, 1]", what, (double)e, bodies[k]); return PHX_ERR_INVALID; }
+    }
+    if (!count) return PHX_OK;
+    const int n = nb();
+    if (bodies_dirty_ || !d_bodies_.p) {                                    // host-staged: the table goes up with the bodies
+        if (!materials_active_) host_mat_.assign((size_t)n, make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION));
+        materials_active_ = true;
+        for (int k = 0; k < count; ++k) host_mat_[(size_t)bodies[k]] = make_float2(materials[k].friction, materials[k].restitution);
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before the table changes)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(materials), count, 2, &d_bodies, &d_values));
+    if (!materials_active_) {
+        PHX_TRY(mat_.reserve((size_t)std::max(n, 1)));
+        hipLaunchKernelGGL(k_default_materials, dim3(wgrid(n)), dim3(256), 0, stream_, mat_.p, n);
+        materials_active_ = true;
+    }
+    hipLaunchKernelGGL(k_set_materials, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, reinterpret_cast<const float2*>(d_values), count, mat_.p);
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+int World::get_materials(phx_material* out, int cap)
+{
+    const int n = nb();
+    if (cap < n) { set_error("phx_world_get_materials: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    if (!materials_active_) {
+        for (int i = 0; i < n; ++i) out[i] = phx_material{MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION};
+        return PHX_OK;
+    }
+    std::vector<float2> m;
+    const float2* src = host_mat_.data();
+    if (!(bodies_dirty_ || !d_bodies_.p)) {
+        PHX_TRY(use_device(device_));
+        m.resize((size_t)n);
+        PHX_TRY(rb_.add(m.data(), mat_.p, (size_t)n * sizeof(float2), stream_));
+        PHX_TRY(rb_.wait(stream_));
+        src = m.data();
+    }
+    for (int i = 0; i < n; ++i) out[i] = phx_material{src[i].x, src[i].y};
+    return PHX_OK;
+}
+
+// the sharded modes (phx_world_set_shard, set_comm, reslab) carry no materials: refused while some body's material is not the default
+int World::refuse_materials(const char* what)
+{
+    if (!materials_active_) return PHX_OK;
+    std::vector<phx_material> m((size_t)nb());
+    PHX_TRY(get_materials(m.data(), nb()));
+    for (const phx_material& x : m)
+        if (x.friction != MATERIAL_DEFAULT_FRICTION || x.restitution != MATERIAL_DEFAULT_RESTITUTION) {
+            set_error("%s: the world holds materials, which a sharded world does not carry", what);
+            return PHX_ERR_STATE;
+        }
+    materials_active_ = false; host_mat_.clear();                           // (every material is the default again: the plain kernels)
     return PHX_OK;
 }
 
@@ -1510,6 +1618,7 @@ int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(count >= 1 && shard >= 0 && shard < count, "bad shard");
     if (count > 1) PHX_TRY(w->impl.refuse_filters("phx_world_set_shard"));
+    if (count > 1) PHX_TRY(w->impl.refuse_materials("phx_world_set_shard"));
     w->impl.shard = shard; w->impl.shard_count = count;
     PHX_TRY(w->impl.solver().set_shard(shard, count));
     return PHX_OK;
@@ -1551,6 +1660,7 @@ int phx_world_set_comm(phx_world* w, phx_comm* c)
 {
     PHX_REQUIRE(w, "null handle");
     if (c) PHX_TRY(w->impl.refuse_filters("phx_world_set_comm"));
+    if (c) PHX_TRY(w->impl.refuse_materials("phx_world_set_comm"));
     return w->impl.set_comm(c ? &c->impl : nullptr);
 }
 
@@ -1644,6 +1754,19 @@ int phx_world_get_collision_filters(phx_world* w, phx_collision_filter* out, int
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
     return w->impl.get_collision_filters(out, cap);
+}
+
+int phx_world_set_materials(phx_world* w, const int32_t* bodies, const phx_material* materials, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_materials(bodies, materials, count);
+}
+
+int phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_materials(out, cap);
 }
 
 int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
@@ -1747,6 +1870,7 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
     PHX_REQUIRE(w && global_index && body_count && bounds && moved, "null handle / arguments");
     PHX_REQUIRE(scene_size >= *body_count && capacity >= *body_count, "bad sizes");
     PHX_TRY(w->impl.refuse_filters("phx_world_reslab"));
+    PHX_TRY(w->impl.refuse_materials("phx_world_reslab"));
     phx::SlabTransport tp;
     PHX_TRY(slab_transport(transport, w->impl, &tp));
     phx::SlabState st;

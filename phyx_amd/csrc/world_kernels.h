@@ -136,9 +136,11 @@ static __global__ void __launch_bounds__(256) k_set_inverse_masses(const int* __
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
 // as AddBody does (world.hip body_record); only the AABB is computed here, by the UpdateGeom of set_poses (ref: Geom.h:79-85).  The
 // record is AddBody's byte for byte, the resident state has zero velocities, and a pending acceleration slot starts at zero, a
-// collision filter table (null while every filter is the default) the default filter.
+// collision filter table (null while every filter is the default) the default filter, a material table (null while no material was
+// set) the default material.
 static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __restrict__ rows, int count, int first, WorldBodies w,
-                                                             phx_rigid_body* __restrict__ records, float4* __restrict__ accel, uint4* __restrict__ filters)
+                                                             phx_rigid_body* __restrict__ records, float4* __restrict__ accel, uint4* __restrict__ filters,
+                                                             float2* __restrict__ materials)
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
         const float* q = rows + 10 * (size_t)k;
@@ -161,6 +163,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         w.size[i] = make_float2(size.x, size.y);
         if (accel) accel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (filters) filters[i] = make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u);
+        if (materials) materials[i] = make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION);
     }
 }
 
@@ -422,6 +425,15 @@ static __global__ void __launch_bounds__(256) k_joints_fill(phx_contact_joint* _
 
 // collision filters (phx_world_set_collision_filters): the table of a world whose filters were all the default is filled first, then
 // the staged batch {indices | {category, mask, group} per body} is scattered into it
+// materials (phx_world_set_materials): the same two steps on the {friction, restitution} table
+static __global__ void __launch_bounds__(256) k_default_materials(float2* __restrict__ materials, int n)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) materials[i] = make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION);
+}
+static __global__ void __launch_bounds__(256) k_set_materials(const int* __restrict__ idx, const float2* __restrict__ v, int count, float2* __restrict__ materials)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) materials[idx[k]] = v[k];
+}
 static __global__ void __launch_bounds__(256) k_default_filters(uint4* __restrict__ filters, int n)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) filters[i] = make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u);
@@ -500,12 +512,13 @@ __device__ __forceinline__ bool scanned_flag(const unsigned* __restrict__ before
 // accelerations) at `to` are made from it by the upload's own conversion (record_to_world), as phx_world_set_state would make them.
 // `refresh` (the records are stale): the record is first brought up to date from the resident arrays (world_record), as the getter
 // would.  remap[i] = to, or -1.  accel_nonzero counts the kept records with an acceleration (the upload's test, world.hip).  A collision
-// filter table (null while every filter is the default) moves with the bodies.
+// filter table (null while every filter is the default) and a material table (null while no material was set) move with the bodies.
 static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_body* __restrict__ records, WorldBodies w, int n, int refresh,
                                                               const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
                                                               phx_rigid_body* __restrict__ out_records, WorldBodies out, float4* __restrict__ out_accel,
                                                               int* __restrict__ remap, unsigned* __restrict__ accel_nonzero,
-                                                              const uint4* __restrict__ filters, uint4* __restrict__ out_filters)
+                                                              const uint4* __restrict__ filters, uint4* __restrict__ out_filters,
+                                                              const float2* __restrict__ materials, float2* __restrict__ out_materials)
 {
     static_assert(sizeof(phx_rigid_body) == 8 * sizeof(float4), "a record is one 128-byte line");
     unsigned nonzero = 0;
@@ -527,6 +540,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
         for (int k = 0; k < 8; ++k) dst[k] = line[k];
         record_to_world(b, out, to);
         if (filters) out_filters[to] = filters[i];
+        if (materials) out_materials[to] = materials[i];
         if (out_accel) {
             out_accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;
