@@ -25,6 +25,102 @@ static inline int wgrid(int n) { return std::max(1, std::min(div_up(n, 256), 409
 static inline int rgrid(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }      // the removal's streaming passes (grid-stride beyond 2048 workgroups)
 constexpr int PRELABEL_EARLY_MANIFOLDS = 400000;      // worlds from this size on queue the side stream's share of the schedule rebuild before the joint match (refresh_contact_joints)
 
+// What every body always has on the device: the 128-byte records (the C-ABI edge: uploaded once, refreshed from the resident arrays only
+// when a getter asks) and the six resident arrays every kernel of the step reads (body_view.h).  The World holds two: the live one and
+// the spare a removal compacts into, which then change places.
+struct BodyStore {
+    DevBuf<phx_rigid_body> records;
+    DevBuf<float4> vel, dvel, mpos, frame, aabb;
+    DevBuf<float2> size;
+    int reserve(size_t n)
+    {
+        PHX_TRY(records.reserve(n));
+        PHX_TRY(vel.reserve(n)); PHX_TRY(dvel.reserve(n)); PHX_TRY(mpos.reserve(n)); PHX_TRY(frame.reserve(n)); PHX_TRY(aabb.reserve(n));
+        return size.reserve(n);
+    }
+    int reserve_keep(size_t total, size_t keep, hipStream_t stream)      // geometric, contents kept; a buffer that grows waits for the stream once
+    {
+        PHX_TRY(records.reserve_keep(total, keep, stream));
+        PHX_TRY(vel.reserve_keep(total, keep, stream)); PHX_TRY(dvel.reserve_keep(total, keep, stream)); PHX_TRY(mpos.reserve_keep(total, keep, stream));
+        PHX_TRY(frame.reserve_keep(total, keep, stream)); PHX_TRY(aabb.reserve_keep(total, keep, stream));
+        return size.reserve_keep(total, keep, stream);
+    }
+    WorldBodies view() const { return WorldBodies{BodyView{vel.p, dvel.p, mpos.p}, frame.p, aabb.p, size.p}; }
+};
+
+// An optional per-body column (world_kernels.h FilterColumn, MaterialColumn) through the bodies' life.  `active` is conservative: it is
+// set by the first value anybody sets and stays set when every value has gone back to the default (that costs time only); while it is
+// clear there is no table and every body has the default.  While the bodies are host-staged `host` is the truth and goes up with them,
+// otherwise `dev`, which grows with a spawn and is compacted into `spare` by a removal, beside the body store.
+template <class Column>
+struct BodyTable {
+    using column = Column;
+    using T = typename Column::value;
+    bool active = false;
+    DevBuf<T> dev, spare;
+    std::vector<T> host;
+
+    T* ptr() const { return active ? dev.p : nullptr; }
+    T* spare_ptr() const { return active ? spare.p : nullptr; }
+    void reset() { active = false; host.clear(); }                          // every body has the default again
+    void push_default() { if (active) host.push_back(Column::initial()); }  // add_body
+    int grow(size_t total, size_t keep, hipStream_t stream) { return active ? dev.reserve_keep(total, keep, stream) : PHX_OK; }
+    int reserve_spare(size_t n) { return active ? spare.reserve(n) : PHX_OK; }
+    void adopt_spare() { if (active) std::swap(dev, spare); }
+    // the bodies become host-staged: so does the table
+    int to_host(int n, int device, hipStream_t stream)
+    {
+        if (!active) return PHX_OK;
+        host.resize((size_t)n);
+        if (!n) return PHX_OK;
+        PHX_TRY(use_device(device));
+        PHX_HIP(hipStreamSynchronize(stream));
+        PHX_HIP(hipMemcpy(host.data(), dev.p, (size_t)n * sizeof(T), hipMemcpyDeviceToHost));
+        return PHX_OK;
+    }
+    // ... and goes up with them again (the caller waits for the stream, then clears `host`)
+    int upload(size_t n, hipStream_t stream)
+    {
+        if (!active) return PHX_OK;
+        PHX_TRY(dev.reserve(n));
+        if (!host.empty()) PHX_HIP(hipMemcpyAsync(dev.p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        return PHX_OK;
+    }
+    // a batch of values for `n` host-staged bodies / a staged batch scattered on the stream; the first one makes the table
+    void set_host(const int32_t* bodies, const typename Column::api* values, int count, int n)
+    {
+        if (!active) host.assign((size_t)n, Column::initial());
+        active = true;
+        for (int k = 0; k < count; ++k) host[(size_t)bodies[k]] = Column::stored(values[k]);
+    }
+    int set_device(const int* d_bodies, const float* d_values, int count, int n, hipStream_t stream)
+    {
+        if (!active) {
+            PHX_TRY(dev.reserve((size_t)std::max(n, 1)));
+            hipLaunchKernelGGL(k_fill_column<Column>, dim3(wgrid(n)), dim3(256), 0, stream, dev.p, n);
+            active = true;
+        }
+        hipLaunchKernelGGL(k_scatter_column<Column>, dim3(wgrid(count)), dim3(256), 0, stream, d_bodies, reinterpret_cast<const typename Column::api*>(d_values), count, dev.p);
+        PHX_HIP(hipGetLastError());
+        return PHX_OK;
+    }
+    // f(i, value) for every body, from wherever the truth is
+    template <class F> int visit(int n, bool host_staged, int device, Readback& rb, hipStream_t stream, F f)
+    {
+        std::vector<T> tmp;
+        const T* src = host.data();
+        if (active && !host_staged && n) {
+            PHX_TRY(use_device(device));
+            tmp.resize((size_t)n);
+            PHX_TRY(rb.add(tmp.data(), dev.p, (size_t)n * sizeof(T), stream));
+            PHX_TRY(rb.wait(stream));
+            src = tmp.data();
+        }
+        for (int i = 0; i < n; ++i) f(i, active ? src[i] : Column::initial());
+        return PHX_OK;
+    }
+};
+
 class World {
 public:
     explicit World(int device) : broadphase_h(device), solver_h(device), device_(device), broadphase_(broadphase_h.impl), solver_(solver_h.impl) {}
@@ -82,11 +178,11 @@ public:
     // their manifolds as set_state of the dropped state would
     int set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped);
     int get_collision_filters(phx_collision_filter* out, int cap);
-    int refuse_filters(const char* what);      // PHX_ERR_STATE if some body's filter is not the default (the sharded modes carry none)
     // materials (phx_world_set_materials / get_materials): between steps; they change no topology
     int set_materials(const int32_t* bodies, const phx_material* materials, int count);
     int get_materials(phx_material* out, int cap);
-    int refuse_materials(const char* what);    // PHX_ERR_STATE if some body's material is not the default (the sharded modes carry none)
+    template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
+    int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
@@ -104,7 +200,10 @@ public:
 private:
     int sync_bodies_to_device();
     int refresh_records();               // resident arrays -> the 128-byte records (getters)
-    WorldBodies resident() const { return WorldBodies{BodyView{vel_.p, dvel_.p, mpos_.p}, frame_.p, aabb_.p, size_.p}; }
+    WorldBodies resident() const { return bodies_.view(); }
+    bool host_staged() const { return bodies_dirty_ || !bodies_.records.p; }      // the host-staged records are the world
+    int restage_on_host();               // ... again, after the device copy was: records and tables come down
+    int refuse_mid_step(const char* what) const;      // PHX_ERR_STATE between pre_solve / step_begin and finish_step / step_end
     int update_pairs();
     bool fuse_velocity_ = false; float step_dt_ = 0.f;      // IntegrateVelocity rides on the broadphase's key build (update_pairs)
     int fresh_manifolds_ = 0;           // pairs UpdatePairs found this step: their manifolds are created by UpdateManifolds' kernel
@@ -124,9 +223,7 @@ private:
     hipStream_t stream_ = nullptr;
     std::vector<phx_rigid_body> host_bodies_;     // construction-time staging; the device copy is authoritative after upload (then only its size counts)
     bool bodies_dirty_ = false;
-    DevBuf<phx_rigid_body> d_bodies_;             // the records: uploaded once, refreshed from the resident arrays only when a getter asks
-    DevBuf<float4> vel_, dvel_, mpos_, frame_, aabb_;      // the resident body state (body_view.h)
-    DevBuf<float2> size_;
+    BodyStore bodies_;
     bool records_stale_ = false;                  // a step has run since the records were last refreshed
     DevBuf<float4> accel_; bool accel_pending_ = false;      // accelerations the uploaded records came with: consumed by the next IntegrateVelocity
     DevBuf<phx_manifold> d_manifolds_;
@@ -175,16 +272,15 @@ private:
     int compaction_scratch();
     template <class Keep> int scan_compaction(const Keep& kept);
     template <class Keep> int queue_compaction(const Keep& kept);
+    int adopt_compaction(const unsigned got[5]);      // the compacted contact cache becomes the world's
     struct Spare {
-        DevBuf<phx_rigid_body> bodies;
-        DevBuf<float4> vel, dvel, mpos, frame, aabb, accel;
-        DevBuf<uint4> filters;
-        DevBuf<float2> size, materials;
+        BodyStore bodies;
+        DevBuf<float4> accel;
         DevBuf<phx_manifold> manifolds;
         DevBuf<phx_contact_point> cps;
         DevBuf<phx_contact_joint> joints;
     } spare_;
-    // queries: the geometry epoch is bumped by every path that writes aabb_ (or the frames behind it) or changes the body count; the
+    // queries: the geometry epoch is bumped by every path that writes the AABBs (or the frames behind it) or changes the body count; the
     // query index is current while it was built for this epoch
     unsigned long long geom_epoch_ = 0;
     DeviceQuery query_;
@@ -195,23 +291,15 @@ private:
     // a re-slab) or the body count; the contact index is current while it was built for this epoch
     unsigned long long contact_epoch_ = 0;
     DeviceContacts contacts_;
-    ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, mpos_.p, nb()}; }
+    ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, bodies_.mpos.p, nb()}; }
     int contact_prepare(const char* what, bool host_wait);
-    // collision filters: one {category, mask, group, 0} record per body (common.h collision_filter_pass), kept only once some filter
-    // was set — filters_active_ is conservative (a filter may have been set back to the default) and picks the filtered sweep.  While the
-    // bodies are host-staged host_filters_ is the truth, otherwise filt_ (grown, appended, compacted with the body buffers)
-    bool filters_active_ = false;
-    DevBuf<uint4> filt_;
-    std::vector<uint4> host_filters_;
-    int filters_to_host();               // the bodies become host-staged: so do their filters
-    // materials: one {friction, restitution} per body (include/phyx_amd.h MATERIALS), kept the way the filters are.  materials_active_ is
-    // conservative and picks the solver's material kernels (DeviceSolver::set_materials); while the bodies are host-staged host_mat_ is the
-    // truth, otherwise mat_ (grown, appended, compacted with the body buffers)
-    bool materials_active_ = false;
-    DevBuf<float2> mat_;
-    std::vector<float2> host_mat_;
-    int materials_to_host();             // the bodies become host-staged: so do their materials
-    int staged_to_host() { PHX_TRY(filters_to_host()); return materials_to_host(); }
+    // the optional columns (BodyTable): collision filters — an active table picks the filtered sweep — and materials — an active table
+    // picks the solver's material kernels (DeviceSolver::set_materials)
+    BodyTable<FilterColumn> filters_;
+    BodyTable<MaterialColumn> materials_;
+    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); return f(materials_); }
+    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr()}; }
+    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr()}; }
 };
 
 World::~World()
@@ -262,22 +350,32 @@ static phx_rigid_body body_record(float px, float py, float angle, float sx, flo
 
 int World::add_body(float px, float py, float angle, float sx, float sy)
 {
-    if (!bodies_dirty_ && d_bodies_.p) {
-        if (!host_bodies_.empty()) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
-        PHX_TRY(staged_to_host());
-    }
+    PHX_TRY(restage_on_host());
     phx_rigid_body b = body_record(px, py, angle, sx, sy);
     b.index = (uint32_t)host_bodies_.size();
     host_bodies_.push_back(b);
-    if (filters_active_) host_filters_.push_back(make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u));
-    if (materials_active_) host_mat_.push_back(make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION));
+    each_table([](auto& t) { t.push_default(); return PHX_OK; });
     bodies_dirty_ = true;
     return (int)host_bodies_.size() - 1;
 }
 
+int World::restage_on_host()
+{
+    if (host_staged()) return PHX_OK;
+    if (!host_bodies_.empty()) PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size()));
+    return each_table([this](auto& t) { return t.to_host(nb(), device_, stream_); });
+}
+
+int World::refuse_mid_step(const char* what) const
+{
+    if (!mid_step_) return PHX_OK;
+    set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what);
+    return PHX_ERR_STATE;
+}
+
 int World::set_static(int body)
 {
-    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(staged_to_host()); }
+    PHX_TRY(restage_on_host());
     host_bodies_[body].inv_mass = 0.f;
     host_bodies_[body].inv_inertia = 0.f;
     bodies_dirty_ = true;
@@ -286,7 +384,7 @@ int World::set_static(int body)
 
 int World::set_inverse_mass(int body, float inv_mass, float inv_inertia)
 {
-    if (!bodies_dirty_ && d_bodies_.p) { PHX_TRY(download_bodies(host_bodies_.data(), (int)host_bodies_.size())); PHX_TRY(staged_to_host()); }
+    PHX_TRY(restage_on_host());
     host_bodies_[body].inv_mass = inv_mass;
     host_bodies_[body].inv_inertia = inv_inertia;
     bodies_dirty_ = true;
@@ -298,12 +396,11 @@ int World::sync_bodies_to_device()
 {
     if (!bodies_dirty_) return PHX_OK;
     PHX_TRY(use_device(device_));
-    PHX_TRY(d_bodies_.reserve(std::max<size_t>(host_bodies_.size(), 1)));
     const size_t n = std::max<size_t>(host_bodies_.size(), 1);
-    PHX_TRY(vel_.reserve(n)); PHX_TRY(dvel_.reserve(n)); PHX_TRY(mpos_.reserve(n)); PHX_TRY(frame_.reserve(n)); PHX_TRY(aabb_.reserve(n)); PHX_TRY(size_.reserve(n));
+    PHX_TRY(bodies_.reserve(n));
     if (!host_bodies_.empty()) {
-        PHX_HIP(hipMemcpyAsync(d_bodies_.p, host_bodies_.data(), host_bodies_.size() * sizeof(phx_rigid_body), hipMemcpyHostToDevice, stream_));
-        hipLaunchKernelGGL(k_bodies_to_world, dim3(wgrid(nb())), dim3(256), 0, stream_, (const phx_rigid_body*)d_bodies_.p, nb(), resident());
+        PHX_HIP(hipMemcpyAsync(bodies_.records.p, host_bodies_.data(), host_bodies_.size() * sizeof(phx_rigid_body), hipMemcpyHostToDevice, stream_));
+        hipLaunchKernelGGL(k_bodies_to_world, dim3(wgrid(nb())), dim3(256), 0, stream_, (const phx_rigid_body*)bodies_.records.p, nb(), resident());
         PHX_HIP(hipGetLastError());
         // records that come with accelerations (a handed-over state; AddBody leaves none): the next IntegrateVelocity applies them,
         // once, like the reference (ref: World.cpp:44-53)
@@ -317,17 +414,9 @@ int World::sync_bodies_to_device()
             PHX_HIP(hipStreamSynchronize(stream_));      // (`acc` is a local)
         }
     }
-    if (filters_active_) {
-        PHX_TRY(filt_.reserve(n));
-        if (!host_filters_.empty()) PHX_HIP(hipMemcpyAsync(filt_.p, host_filters_.data(), host_filters_.size() * sizeof(uint4), hipMemcpyHostToDevice, stream_));
-    }
-    if (materials_active_) {
-        PHX_TRY(mat_.reserve(n));
-        if (!host_mat_.empty()) PHX_HIP(hipMemcpyAsync(mat_.p, host_mat_.data(), host_mat_.size() * sizeof(float2), hipMemcpyHostToDevice, stream_));
-    }
+    PHX_TRY(each_table([&](auto& t) { return t.upload(n, stream_); }));
     PHX_HIP(hipStreamSynchronize(stream_));
-    host_filters_.clear();
-    host_mat_.clear();
+    each_table([](auto& t) { t.host.clear(); return PHX_OK; });
     bodies_dirty_ = false;
     records_stale_ = false;
     ++geom_epoch_;
@@ -338,7 +427,7 @@ int World::sync_bodies_to_device()
 int World::refresh_records()
 {
     if (!records_stale_ || !nb()) return PHX_OK;
-    hipLaunchKernelGGL(k_world_to_bodies, dim3(wgrid(nb())), dim3(256), 0, stream_, resident(), nb(), d_bodies_.p);
+    hipLaunchKernelGGL(k_world_to_bodies, dim3(wgrid(nb())), dim3(256), 0, stream_, resident(), nb(), bodies_.records.p);
     PHX_HIP(hipGetLastError());
     records_stale_ = false;
     return PHX_OK;
@@ -353,7 +442,7 @@ int World::scratch_for(int n)
 
 int World::update_pairs()                                                   // ref: Collider.cpp:251-345
 {
-    const DeviceBroadphase::StepPrologue prologue{gravity, step_dt_, counters_.p, vel_.p, mpos_.p, accel_pending_ ? (const float4*)accel_.p : nullptr};
+    const DeviceBroadphase::StepPrologue prologue{gravity, step_dt_, counters_.p, bodies_.vel.p, bodies_.mpos.p, accel_pending_ ? (const float4*)accel_.p : nullptr};
     // UpdateManifolds of the manifolds that exist already needs nothing from this update (positions, rotations and AABBs do not
     // change in it): it is queued behind the mailbox post of the new-pair count and runs while that round trip is under way — the
     // GPU used to idle through it.  The new pairs' manifolds follow in update_manifolds().  (Not with per-phase timing: the phases
@@ -372,13 +461,13 @@ int World::update_pairs()                                                   // r
     };
     // (that launch also CARRIES the post of the new-pair count: its first workgroup posts before it updates — a dispatch fewer per step)
     const MailCarrier old_manifolds_with = [&](const MailRide* ride) -> int { old_ride_ = ride; const int st = old_manifolds(); old_ride_ = nullptr; return st; };
-    PHX_TRY(broadphase_.update_resident(aabb_.p, nb(), fuse_velocity_ ? &prologue : nullptr, phase_timing ? nullptr : &old_manifolds,
+    PHX_TRY(broadphase_.update_resident(bodies_.aabb.p, nb(), fuse_velocity_ ? &prologue : nullptr, phase_timing ? nullptr : &old_manifolds,
                                         phase_timing || !nm ? nullptr : &old_manifolds_with,      // same stream; returns once the new-pair count is known
-                                        filters_active_ ? (const uint4*)filt_.p : nullptr));
+                                        filters_.ptr()));
     fuse_velocity_ = false;
     if (accel_pending_) {                  // IntegrateVelocity of this step has consumed the uploaded accelerations (ref: World.cpp:50, 53)
         accel_pending_ = false;
-        if (nb()) hipLaunchKernelGGL(k_clear_accelerations, dim3(wgrid(nb())), dim3(256), 0, stream_, d_bodies_.p, nb());
+        if (nb()) hipLaunchKernelGGL(k_clear_accelerations, dim3(wgrid(nb())), dim3(256), 0, stream_, bodies_.records.p, nb());
         PHX_HIP(hipGetLastError());
     }
     const int fresh = broadphase_.new_pair_count();
@@ -455,7 +544,7 @@ int World::refresh_contact_joints()                                         // r
         // (the side stream's share of the rebuild is queued BEHIND the match and its scans in a small world — the host needs ~30 us for its
         //  eight launches, more than those kernels run, and the GPU would idle — but IN FRONT of them in a large one, whose match alone runs
         //  longer than that: at 1M boxes the side stream's 140 us were the critical path of the step, started 100 us after they could have)
-        if (nm >= PRELABEL_EARLY_MANIFOLDS) PHX_TRY(solver_.prelabel_components((const float4*)mpos_.p, nb(), (const phx_manifold*)d_manifolds_.p, nm));
+        if (nm >= PRELABEL_EARLY_MANIFOLDS) PHX_TRY(solver_.prelabel_components((const float4*)bodies_.mpos.p, nb(), (const phx_manifold*)d_manifolds_.p, nm));
         if (nm) {
             hipLaunchKernelGGL(k_joints_match, dim3(wgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, (const phx_contact_point*)d_cps_.p,
                                d_joints_.p, joint_seen_.p, joint_epoch_, flags_.p);
@@ -465,7 +554,7 @@ int World::refresh_contact_joints()                                         // r
         if (nm || nj || pack_pending_) {                                    // counters_[0 .. 3]: adjacent words, one copy
             unsigned got[4] = {0, 0, 0, 0};
             PHX_TRY(rb_.add(got, counters_.p, sizeof got, stream_));
-            PHX_TRY(solver_.prelabel_components((const float4*)mpos_.p, nb(), (const phx_manifold*)d_manifolds_.p, nm));      // (once: the mark is consumed)
+            PHX_TRY(solver_.prelabel_components((const float4*)bodies_.mpos.p, nb(), (const phx_manifold*)d_manifolds_.p, nm));      // (once: the mark is consumed)
             PHX_TRY(rb_.wait(stream_));
             host[0] = got[0]; host[1] = got[1];
             if (pack_pending_) { host[2] = got[2]; host[3] = got[3]; }      // (else PackManifolds has settled them already)
@@ -514,7 +603,7 @@ int World::solve(const phx_config& cfg, bool settle)                        // r
     // island sharding: the solver sweeps only this rank's groups (DeviceSolver::set_shard); the other groups' bodies
     // keep their velocities here
     if (!joints_changed_) PHX_TRY(solver_.cancel_prelabel());              // (no rebuild will pick the side stream's bins up)
-    solver_.set_materials(materials_active_ ? (const float2*)mat_.p : nullptr);      // (the table moves with spawns and removals: handed over every solve)
+    solver_.set_materials(materials_.ptr());      // (the table moves with spawns and removals: handed over every solve)
     PHX_TRY(solver_.solve_resident(resident().s, nb(), d_cps_.p, 2 * nm, d_joints_.p, nj, cfg, joints_changed_));
     joints_changed_ = false;
     // a solve that is still unverified (it ran speculatively on the cached schedule, or on a device-built schedule whose 'every
@@ -572,7 +661,7 @@ int World::pre_solve(float dt)
         fuse_velocity_ = !phase_timing;
         step_dt_ = dt;
         records_stale_ = true;
-        if (nb() && !fuse_velocity_) hipLaunchKernelGGL(k_integrate_velocity, dim3(wgrid(nb())), dim3(256), 0, stream_, vel_.p, (const float4*)mpos_.p, nb(), gravity, dt, counters_.p, accel_pending_ ? (const float4*)accel_.p : nullptr);
+        if (nb() && !fuse_velocity_) hipLaunchKernelGGL(k_integrate_velocity, dim3(wgrid(nb())), dim3(256), 0, stream_, bodies_.vel.p, (const float4*)bodies_.mpos.p, nb(), gravity, dt, counters_.p, accel_pending_ ? (const float4*)accel_.p : nullptr);
         PHX_HIP(hipGetLastError());
         lap(0);
     }
@@ -823,8 +912,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     PHX_TRY(synchronize());
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
-    filters_active_ = false; host_filters_.clear();                         // every filter is the default again
-    materials_active_ = false; host_mat_.clear();                           // ... and every material
+    each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -875,12 +963,12 @@ int World::download_bodies(phx_rigid_body* out, int cap)
 {
     const int n = nb();
     if (cap < n) { set_error("download_bodies: buffer too small"); return PHX_ERR_CAPACITY; }
-    if (bodies_dirty_ || !d_bodies_.p) { if (n && out != host_bodies_.data()) std::memcpy(out, host_bodies_.data(), (size_t)n * sizeof(phx_rigid_body)); return PHX_OK; }
+    if (host_staged()) { if (n && out != host_bodies_.data()) std::memcpy(out, host_bodies_.data(), (size_t)n * sizeof(phx_rigid_body)); return PHX_OK; }
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before its results are read)
     PHX_TRY(refresh_records());
     PHX_HIP(hipStreamSynchronize(stream_));
-    if (n) PHX_HIP(hipMemcpy(out, d_bodies_.p, (size_t)n * sizeof(phx_rigid_body), hipMemcpyDeviceToHost));
+    if (n) PHX_HIP(hipMemcpy(out, bodies_.records.p, (size_t)n * sizeof(phx_rigid_body), hipMemcpyDeviceToHost));
     return PHX_OK;
 }
 
@@ -892,7 +980,7 @@ int World::download_bodies(phx_rigid_body* out, int cap)
 // (`edit`: an edit — refused inside a step, every index at most once — rather than a gather)
 int World::check_batch(const char* what, const int* bodies, const void* values, int count, bool edit)
 {
-    if (edit && mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    if (edit) PHX_TRY(refuse_mid_step(what));
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && (!bodies || !values)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
     const int n = nb();
@@ -947,7 +1035,7 @@ int World::edit(Edit kind, const int* bodies, const float* values, int count)
     PHX_TRY(check_batch(what[kind], bodies, values, count, true));
     if (!count) return PHX_OK;
     const int width = kind == EDIT_POSES ? 6 : 3;
-    if (bodies_dirty_ || !d_bodies_.p) {                                    // the host-staged records are the world: write into them
+    if (host_staged()) {                                    // the host-staged records are the world: write into them
         for (int k = 0; k < count; ++k) {
             phx_rigid_body& b = host_bodies_[(size_t)bodies[k]];
             const float* v = values + (size_t)width * k;
@@ -968,9 +1056,9 @@ int World::edit(Edit kind, const int* bodies, const float* values, int count)
             PHX_HIP(hipMemsetAsync(accel_.p, 0, (size_t)nb() * sizeof(float4), stream_));
             accel_pending_ = true;
         }
-        hipLaunchKernelGGL(k_add_accelerations, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, accel_.p, d_bodies_.p);
+        hipLaunchKernelGGL(k_add_accelerations, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, accel_.p, bodies_.records.p);
     } else if (kind == EDIT_VELOCITIES) {
-        hipLaunchKernelGGL(k_set_velocities, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, vel_.p);
+        hipLaunchKernelGGL(k_set_velocities, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, bodies_.vel.p);
         records_stale_ = true;
     } else {
         hipLaunchKernelGGL(k_set_poses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, resident());
@@ -985,7 +1073,7 @@ int World::get_body_states(const int* bodies, int count, phx_rigid_body* out)
 {
     PHX_TRY(check_batch("phx_world_get_body_states", bodies, out, count, false));
     if (!count) return PHX_OK;
-    if (bodies_dirty_ || !d_bodies_.p) {
+    if (host_staged()) {
         for (int k = 0; k < count; ++k) out[k] = host_bodies_[(size_t)bodies[k]];
         return PHX_OK;
     }
@@ -994,7 +1082,7 @@ int World::get_body_states(const int* bodies, int count, phx_rigid_body* out)
     const int* d_bodies = nullptr; const float* unused = nullptr;
     PHX_TRY(stage_batch(bodies, nullptr, count, 0, &d_bodies, &unused));
     PHX_TRY(gathered_.reserve((size_t)count));
-    hipLaunchKernelGGL(k_gather_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, resident(), (const phx_rigid_body*)d_bodies_.p, d_bodies, count, gathered_.p);
+    hipLaunchKernelGGL(k_gather_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, resident(), (const phx_rigid_body*)bodies_.records.p, d_bodies, count, gathered_.p);
     PHX_HIP(hipGetLastError());
     PHX_TRY(rb_.add(out, gathered_.p, (size_t)count * sizeof(phx_rigid_body), stream_));
     return rb_.wait(stream_);
@@ -1005,7 +1093,7 @@ int World::get_poses(float* out, int cap)
     const int n = nb();
     if (cap < n) { set_error("phx_world_get_poses: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
     if (!n) return PHX_OK;
-    if (bodies_dirty_ || !d_bodies_.p) {
+    if (host_staged()) {
         for (int i = 0; i < n; ++i) {
             const phx_rigid_body& b = host_bodies_[(size_t)i];
             out[4 * i] = b.pos.x; out[4 * i + 1] = b.pos.y; out[4 * i + 2] = b.xvector.x; out[4 * i + 3] = b.xvector.y;
@@ -1065,6 +1153,16 @@ int World::queue_compaction(const Keep& kept)
     return PHX_OK;
 }
 
+// rm_counts_ as the round trip brought them back: [1] manifolds, [2] joints kept.  The compacted cache changes places with the world's,
+// the pair set is reset to its pairs and the step history is forgotten, as set_state would.
+int World::adopt_compaction(const unsigned got[5])
+{
+    std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
+    nm = (int)got[1]; nj = (int)got[2];
+    PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
+    return forget_step_history();
+}
+
 // ---- removal between steps ------------------------------------------------------------------------------------------------------
 // Defined as phx_world_set_state of the filtered state (include/phyx_amd.h); computed on the world's stream without the state
 // crossing PCIe: keep flags per body (scattered from the staged list, or the box test on the resident AABBs), three exclusive scans
@@ -1076,7 +1174,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
 {
     if (shard_count > 1 || comm_) { set_error("%s: a sharded world cannot remove bodies", what); return PHX_ERR_STATE; }
     if (box) {
-        if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+        PHX_TRY(refuse_mid_step(what));
         for (int k = 0; k < 4; ++k)
             if (!std::isfinite(box[k])) { set_error("%s: the box is not finite", what); return PHX_ERR_INVALID; }
         if (!(box[0] <= box[2] && box[1] <= box[3])) { set_error("%s: the box's min exceeds its max", what); return PHX_ERR_INVALID; }
@@ -1090,17 +1188,14 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
-    const bool pending_accel = accel_pending_;
     PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n));
-    PHX_TRY(spare_.bodies.reserve((size_t)n)); PHX_TRY(spare_.vel.reserve((size_t)n)); PHX_TRY(spare_.dvel.reserve((size_t)n)); PHX_TRY(spare_.mpos.reserve((size_t)n));
-    PHX_TRY(spare_.frame.reserve((size_t)n)); PHX_TRY(spare_.aabb.reserve((size_t)n)); PHX_TRY(spare_.size.reserve((size_t)n));
-    if (pending_accel) PHX_TRY(spare_.accel.reserve((size_t)n));
-    if (filters_active_) PHX_TRY(spare_.filters.reserve((size_t)n));
-    if (materials_active_) PHX_TRY(spare_.materials.reserve((size_t)n));
+    PHX_TRY(spare_.bodies.reserve((size_t)n));
+    if (accel_pending_) PHX_TRY(spare_.accel.reserve((size_t)n));
+    PHX_TRY(each_table([n](auto& t) { return t.reserve_spare((size_t)n); }));
     PHX_TRY(compaction_scratch());
     // 1. keep flags per body
     if (box) {
-        hipLaunchKernelGGL(k_keep_inside, dim3(rgrid(n)), dim3(256), 0, stream_, (const float4*)aabb_.p, n, make_float4(box[0], box[1], box[2], box[3]), rm_keep_.p);
+        hipLaunchKernelGGL(k_keep_inside, dim3(rgrid(n)), dim3(256), 0, stream_, (const float4*)bodies_.aabb.p, n, make_float4(box[0], box[1], box[2], box[3]), rm_keep_.p);
     } else {
         const int* d_bodies = nullptr; const float* unused = nullptr;
         PHX_TRY(stage_batch(bodies, nullptr, count, 0, &d_bodies, &unused));
@@ -1114,11 +1209,9 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(scan_compaction(kept));
     PHX_HIP(hipMemsetAsync(rm_counts_.p + 3, 0, sizeof(unsigned), stream_));
     // 3. compaction into the spares
-    const WorldBodies out{BodyView{spare_.vel.p, spare_.dvel.p, spare_.mpos.p}, spare_.frame.p, spare_.aabb.p, spare_.size.p};
-    hipLaunchKernelGGL(k_remove_bodies, dim3(rgrid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)d_bodies_.p, resident(), n, records_stale_ ? 1 : 0,
-                       (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, spare_.bodies.p, out, pending_accel ? spare_.accel.p : (float4*)nullptr,
-                       rm_remap_.p, rm_counts_.p + 3, filters_active_ ? (const uint4*)filt_.p : (const uint4*)nullptr, spare_.filters.p,
-                       materials_active_ ? (const float2*)mat_.p : (const float2*)nullptr, spare_.materials.p);
+    hipLaunchKernelGGL(k_remove_bodies, dim3(rgrid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)bodies_.records.p, resident(), n, records_stale_ ? 1 : 0,
+                       (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, spare_.bodies.records.p, spare_.bodies.view(), rm_remap_.p, rm_counts_.p + 3,
+                       columns(), spare_columns());
     PHX_TRY(queue_compaction(kept));
     PHX_HIP(hipGetLastError());
     PHX_TRY(contacts_.remap_baseline(rm_remap_.p, rm_counts_.p + 4, stream_));      // (the events' baseline through new[]: [4] its new size)
@@ -1131,21 +1224,16 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     if (removed) *removed = n - kept_bodies;
     if (kept_bodies == n) return PHX_OK;                                    // every body is inside the box: nothing changes (the spares are dropped)
     // 5. the compacted arrays become the world's
-    std::swap(d_bodies_, spare_.bodies);
-    std::swap(vel_, spare_.vel); std::swap(dvel_, spare_.dvel); std::swap(mpos_, spare_.mpos); std::swap(frame_, spare_.frame); std::swap(aabb_, spare_.aabb); std::swap(size_, spare_.size);
-    if (pending_accel) std::swap(accel_, spare_.accel);
-    if (filters_active_) std::swap(filt_, spare_.filters);
-    if (materials_active_) std::swap(mat_, spare_.materials);
-    std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
+    std::swap(bodies_, spare_.bodies);
+    if (accel_pending_) std::swap(accel_, spare_.accel);
+    each_table([](auto& t) { t.adopt_spare(); return PHX_OK; });
     host_bodies_.resize((size_t)kept_bodies);                               // (only its size counts while the device copy is the world)
     ++geom_epoch_;
     ++contact_epoch_;
     contacts_.baseline_remapped(got[4]);
     records_stale_ = false;
-    accel_pending_ = pending_accel && got[3] != 0;                          // (what the upload of the kept records would find)
-    nm = (int)got[1]; nj = (int)got[2];
-    PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
-    return forget_step_history();
+    accel_pending_ = accel_pending_ && got[3] != 0;                         // (what the upload of the kept records would find)
+    return adopt_compaction(got);
 }
 
 // ---- spawn between steps ---------------------------------------------------------------------------------------------------------
@@ -1159,7 +1247,7 @@ constexpr int SPAWN_ROW = 10;      // {pos.x, pos.y, half x, half y, inv_mass, i
 int World::add_bodies(const float* spawn, int count, int* first)
 {
     static const char* const what = "phx_world_add_bodies";
-    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    PHX_TRY(refuse_mid_step(what));
     if (shard_count > 1 || comm_) { set_error("%s: a sharded world cannot spawn bodies", what); return PHX_ERR_STATE; }
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && !spawn) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
@@ -1173,7 +1261,7 @@ int World::add_bodies(const float* spawn, int count, int* first)
     }
     if (first) *first = n;
     if (!count) return PHX_OK;
-    if (bodies_dirty_ || !d_bodies_.p) {                                    // host-staged: exactly `count` add_body calls
+    if (host_staged()) {                                    // host-staged: exactly `count` add_body calls
         host_bodies_.reserve((size_t)n + count);
         for (int k = 0; k < count; ++k) { const float* q = spawn + 5 * (size_t)k; add_body(q[0], q[1], q[2], q[3], q[4]); }
         return PHX_OK;
@@ -1191,16 +1279,12 @@ int World::add_bodies(const float* spawn, int count, int* first)
         any_static |= b.inv_mass == 0.f && b.inv_inertia == 0.f;           // (sizes so large that the mass overflows: a static body)
     }
     const size_t total = (size_t)n + count;
-    PHX_TRY(d_bodies_.reserve_keep(total, n, stream_));
-    PHX_TRY(vel_.reserve_keep(total, n, stream_)); PHX_TRY(dvel_.reserve_keep(total, n, stream_)); PHX_TRY(mpos_.reserve_keep(total, n, stream_));
-    PHX_TRY(frame_.reserve_keep(total, n, stream_)); PHX_TRY(aabb_.reserve_keep(total, n, stream_)); PHX_TRY(size_.reserve_keep(total, n, stream_));
+    PHX_TRY(bodies_.reserve_keep(total, n, stream_));
     if (accel_pending_) PHX_TRY(accel_.reserve_keep(total, n, stream_));
-    if (filters_active_) PHX_TRY(filt_.reserve_keep(total, n, stream_));
-    if (materials_active_) PHX_TRY(mat_.reserve_keep(total, n, stream_));
+    PHX_TRY(each_table([&](auto& t) { return t.grow(total, n, stream_); }));
     const int* unused = nullptr; const float* d_rows = nullptr;
     PHX_TRY(stage_batch(nullptr, spawn_rows_.data(), count, SPAWN_ROW, &unused, &d_rows));
-    hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), d_bodies_.p, accel_pending_ ? accel_.p : (float4*)nullptr,
-                       filters_active_ ? filt_.p : (uint4*)nullptr, materials_active_ ? mat_.p : (float2*)nullptr);
+    hipLaunchKernelGGL(k_spawn_bodies, dim3(wgrid(count)), dim3(256), 0, stream_, d_rows, count, n, resident(), bodies_.records.p, columns());
     PHX_HIP(hipGetLastError());
     host_bodies_.resize(total);                                             // (only its size counts while the device copy is the world)
     ++geom_epoch_;
@@ -1220,7 +1304,7 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
         if (!std::isfinite(values[k]) || !(values[k] >= 0.f)) { set_error("%s: entry %d: inverse masses must be finite and >= 0", what, k / 2); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     joints_changed_ = true;                                                 // which bodies are static is part of the schedule's topology
-    if (bodies_dirty_ || !d_bodies_.p) {
+    if (host_staged()) {
         for (int k = 0; k < count; ++k) { phx_rigid_body& b = host_bodies_[(size_t)bodies[k]]; b.inv_mass = values[2 * k]; b.inv_inertia = values[2 * k + 1]; }
         return PHX_OK;
     }
@@ -1228,7 +1312,7 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
     if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
     const int* d_bodies = nullptr; const float* d_values = nullptr;
     PHX_TRY(stage_batch(bodies, values, count, 2, &d_bodies, &d_values));
-    hipLaunchKernelGGL(k_set_inverse_masses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, mpos_.p, d_bodies_.p);
+    hipLaunchKernelGGL(k_set_inverse_masses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, bodies_.mpos.p, bodies_.records.p);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
@@ -1237,48 +1321,25 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
 // The rule and the defaults: include/phyx_amd.h COLLISION FILTERS, common.h collision_filter_pass.  The broadphase applies it inside the
 // sweep (broadphase.hip FilteredSweepView), so a failing pair is never emitted; what a change of filters does to pairs that exist already
 // is the removal's compaction of the contact cache with the filter as its keep predicate (FilterKept), bodies untouched.
-int World::filters_to_host()
-{
-    if (!filters_active_) return PHX_OK;
-    host_filters_.resize((size_t)nb());
-    if (!nb()) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    PHX_HIP(hipStreamSynchronize(stream_));
-    PHX_HIP(hipMemcpy(host_filters_.data(), filt_.p, (size_t)nb() * sizeof(uint4), hipMemcpyDeviceToHost));
-    return PHX_OK;
-}
-
 int World::set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped)
 {
     static const char* const what = "phx_world_set_collision_filters";
-    static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float), "a filter is staged as three 4-byte words");
     if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no collision filters", what); return PHX_ERR_STATE; }
     PHX_TRY(check_batch(what, bodies, filters, count, true));
     if (dropped) *dropped = 0;
     if (!count) return PHX_OK;
     const int n = nb();
-    if ((bodies_dirty_ || !d_bodies_.p) && !nm) {                           // host-staged, and no pair exists to drop
-        if (!filters_active_) host_filters_.assign((size_t)n, make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u));
-        filters_active_ = true;
-        for (int k = 0; k < count; ++k) host_filters_[(size_t)bodies[k]] = make_uint4(filters[k].category, filters[k].mask, (unsigned)filters[k].group, 0u);
-        return PHX_OK;
-    }
+    if (host_staged() && !nm) { filters_.set_host(bodies, filters, count, n); return PHX_OK; }      // (no pair exists to drop)
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
     const int* d_bodies = nullptr; const float* d_values = nullptr;
     PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(filters), count, 3, &d_bodies, &d_values));
-    if (!filters_active_) {
-        PHX_TRY(filt_.reserve((size_t)std::max(n, 1)));
-        hipLaunchKernelGGL(k_default_filters, dim3(wgrid(n)), dim3(256), 0, stream_, filt_.p, n);
-        filters_active_ = true;
-    }
-    hipLaunchKernelGGL(k_set_filters, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, reinterpret_cast<const unsigned*>(d_values), count, filt_.p);
-    PHX_HIP(hipGetLastError());
+    PHX_TRY(filters_.set_device(d_bodies, d_values, count, n, stream_));
     if (!nm) return PHX_OK;
     // the manifolds whose pair now fails go, with their slots and joints; the one round trip brings back the kept counts
     PHX_TRY(compaction_scratch());
-    const FilterKept kept{filt_.p};
+    const FilterKept kept{filters_.dev.p};
     PHX_TRY(scan_compaction(kept));
     PHX_TRY(queue_compaction(kept));
     unsigned got[5] = {0, 0, 0, 0, 0};
@@ -1286,68 +1347,41 @@ int World::set_collision_filters(const int32_t* bodies, const phx_collision_filt
     PHX_TRY(rb_.wait(stream_));
     if (dropped) *dropped = nm - (int)got[1];
     if ((int)got[1] == nm) return PHX_OK;                                   // nothing dropped: a true no-op for the topology (the spares are dropped)
-    std::swap(d_manifolds_, spare_.manifolds); std::swap(d_cps_, spare_.cps); std::swap(d_joints_, spare_.joints);
-    nm = (int)got[1]; nj = (int)got[2];
     ++contact_epoch_;                                                       // (the touch events' baseline stays: dropped pairs end)
-    PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
-    return forget_step_history();
+    return adopt_compaction(got);
 }
 
-int World::get_collision_filters(phx_collision_filter* out, int cap)
+// the two getters: every body's value in the C ABI's form
+template <class Column>
+int World::get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap)
 {
     const int n = nb();
-    if (cap < n) { set_error("phx_world_get_collision_filters: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
-    if (!n) return PHX_OK;
-    std::vector<uint4> f;
-    const uint4* src = host_filters_.data();
-    if (!filters_active_) {
-        for (int i = 0; i < n; ++i) out[i] = phx_collision_filter{FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0};
-        return PHX_OK;
-    }
-    if (!(bodies_dirty_ || !d_bodies_.p)) {
-        PHX_TRY(use_device(device_));
-        f.resize((size_t)n);
-        PHX_TRY(rb_.add(f.data(), filt_.p, (size_t)n * sizeof(uint4), stream_));
-        PHX_TRY(rb_.wait(stream_));
-        src = f.data();
-    }
-    for (int i = 0; i < n; ++i) out[i] = phx_collision_filter{src[i].x, src[i].y, (int32_t)src[i].z};
-    return PHX_OK;
+    if (cap < n) { set_error("%s: room for %d bodies, the world has %d", what, cap, n); return PHX_ERR_CAPACITY; }
+    return table.visit(n, host_staged(), device_, rb_, stream_, [out](int i, const typename Column::value& v) { out[i] = Column::shown(v); });
 }
+int World::get_collision_filters(phx_collision_filter* out, int cap) { return get_table("phx_world_get_collision_filters", filters_, out, cap); }
+int World::get_materials(phx_material* out, int cap) { return get_table("phx_world_get_materials", materials_, out, cap); }
 
-// the sharded modes (phx_world_set_shard, set_comm, reslab) carry no filters: refused while some body's filter is not the default
-int World::refuse_filters(const char* what)
+// the sharded modes (phx_world_set_shard, set_comm, reslab) carry no optional column: refused while some body's value is not the default
+int World::refuse_tables(const char* what)
 {
-    if (!filters_active_) return PHX_OK;
-    std::vector<phx_collision_filter> f((size_t)nb());
-    PHX_TRY(get_collision_filters(f.data(), nb()));
-    for (const phx_collision_filter& x : f)
-        if (x.category != FILTER_DEFAULT_CATEGORY || x.mask != FILTER_DEFAULT_MASK || x.group != 0) {
-            set_error("%s: the world holds collision filters, which a sharded world does not carry", what);
-            return PHX_ERR_STATE;
-        }
-    filters_active_ = false; host_filters_.clear();                         // (every filter is the default again: the plain sweep)
-    return PHX_OK;
+    return each_table([&](auto& t) -> int {
+        using Column = typename std::decay_t<decltype(t)>::column;
+        if (!t.active) return PHX_OK;
+        bool all_default = true;
+        PHX_TRY(t.visit(nb(), host_staged(), device_, rb_, stream_, [&](int, const typename Column::value& v) { all_default &= Column::is_initial(v); }));
+        if (!all_default) { set_error("%s: the world holds %s, which a sharded world does not carry", what, Column::plural); return PHX_ERR_STATE; }
+        t.reset();                                                          // (every value is the default again: the plain kernels)
+        return PHX_OK;
+    });
 }
 
 // ---- materials --------------------------------------------------------------------------------------------------------------------
 // The pair rule and the defaults: include/phyx_amd.h MATERIALS.  The table is read by the solver's material kernels only
 // (solver_kernels.h k_pack_refresh_mat and the *_mat sweeps, island_kernel.h k_solve_islands_mat); nothing of the topology depends on it.
-int World::materials_to_host()
-{
-    if (!materials_active_) return PHX_OK;
-    host_mat_.resize((size_t)nb());
-    if (!nb()) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    PHX_HIP(hipStreamSynchronize(stream_));
-    PHX_HIP(hipMemcpy(host_mat_.data(), mat_.p, (size_t)nb() * sizeof(float2), hipMemcpyDeviceToHost));
-    return PHX_OK;
-}
-
 int World::set_materials(const int32_t* bodies, const phx_material* materials, int count)
 {
     static const char* const what = "phx_world_set_materials";
-    static_assert(sizeof(phx_material) == sizeof(float2), "a material is staged as two 4-byte words");
     if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no materials", what); return PHX_ERR_STATE; }
     PHX_TRY(check_batch(what, bodies, materials, count, true));
     for (int k = 0; k < count; ++k) {                                       // (NaN fails both comparisons)
@@ -1357,61 +1391,12 @@ int World::set_materials(const int32_t* bodies, const phx_material* materials, i
     }
     if (!count) return PHX_OK;
     const int n = nb();
-    if (bodies_dirty_ || !d_bodies_.p) {                                    // host-staged: the table goes up with the bodies
-        if (!materials_active_) host_mat_.assign((size_t)n, make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION));
-        materials_active_ = true;
-        for (int k = 0; k < count; ++k) host_mat_[(size_t)bodies[k]] = make_float2(materials[k].friction, materials[k].restitution);
-        return PHX_OK;
-    }
+    if (host_staged()) { materials_.set_host(bodies, materials, count, n); return PHX_OK; }      // (the table goes up with the bodies)
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before the table changes)
     const int* d_bodies = nullptr; const float* d_values = nullptr;
     PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(materials), count, 2, &d_bodies, &d_values));
-    if (!materials_active_) {
-        PHX_TRY(mat_.reserve((size_t)std::max(n, 1)));
-        hipLaunchKernelGGL(k_default_materials, dim3(wgrid(n)), dim3(256), 0, stream_, mat_.p, n);
-        materials_active_ = true;
-    }
-    hipLaunchKernelGGL(k_set_materials, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, reinterpret_cast<const float2*>(d_values), count, mat_.p);
-    PHX_HIP(hipGetLastError());
-    return PHX_OK;
-}
-
-int World::get_materials(phx_material* out, int cap)
-{
-    const int n = nb();
-    if (cap < n) { set_error("phx_world_get_materials: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
-    if (!n) return PHX_OK;
-    if (!materials_active_) {
-        for (int i = 0; i < n; ++i) out[i] = phx_material{MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION};
-        return PHX_OK;
-    }
-    std::vector<float2> m;
-    const float2* src = host_mat_.data();
-    if (!(bodies_dirty_ || !d_bodies_.p)) {
-        PHX_TRY(use_device(device_));
-        m.resize((size_t)n);
-        PHX_TRY(rb_.add(m.data(), mat_.p, (size_t)n * sizeof(float2), stream_));
-        PHX_TRY(rb_.wait(stream_));
-        src = m.data();
-    }
-    for (int i = 0; i < n; ++i) out[i] = phx_material{src[i].x, src[i].y};
-    return PHX_OK;
-}
-
-// the sharded modes (phx_world_set_shard, set_comm, reslab) carry no materials: refused while some body's material is not the default
-int World::refuse_materials(const char* what)
-{
-    if (!materials_active_) return PHX_OK;
-    std::vector<phx_material> m((size_t)nb());
-    PHX_TRY(get_materials(m.data(), nb()));
-    for (const phx_material& x : m)
-        if (x.friction != MATERIAL_DEFAULT_FRICTION || x.restitution != MATERIAL_DEFAULT_RESTITUTION) {
-            set_error("%s: the world holds materials, which a sharded world does not carry", what);
-            return PHX_ERR_STATE;
-        }
-    materials_active_ = false; host_mat_.clear();                           // (every material is the default again: the plain kernels)
-    return PHX_OK;
+    return materials_.set_device(d_bodies, d_values, count, n, stream_);
 }
 
 // ---- queries ------------------------------------------------------------------------------------------------------------------------
@@ -1515,14 +1500,14 @@ int World::query_index_build()
 // manifolds are mid-update.  The host forms check everything first and wait for their results; the markers only queue.
 int World::contact_prepare(const char* what, bool host_wait)
 {
-    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    PHX_TRY(refuse_mid_step(what));
     return query_prepare(host_wait);
 }
 
 int World::query_contacts(const int32_t* bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total)
 {
     static const char* const what = "phx_world_query_contacts";
-    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    PHX_TRY(refuse_mid_step(what));
     if (flags != 0 && flags != PHX_QUERY_SKIP_STATIC) { set_error("%s: flags %d (0 or PHX_QUERY_SKIP_STATIC)", what, flags); return PHX_ERR_INVALID; }
     if (!offsets || !total) { set_error("%s: null offsets / total", what); return PHX_ERR_INVALID; }
     if (cap < 0 || (cap > 0 && !out)) { set_error("%s: bad output buffer (cap %d)", what, cap); return PHX_ERR_INVALID; }
@@ -1536,7 +1521,7 @@ int World::query_contacts(const int32_t* bodies, int count, int flags, int32_t* 
 int World::contact_events(int32_t* begin, int begin_cap, int64_t* begin_total, int32_t* end, int end_cap, int64_t* end_total)
 {
     static const char* const what = "phx_world_contact_events";
-    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    PHX_TRY(refuse_mid_step(what));
     if (shard_count > 1 || comm_) { set_error("%s: a sharded world has no touch events (a re-slab renumbers bodies)", what); return PHX_ERR_STATE; }
     if (!begin_total || !end_total) { set_error("%s: null totals", what); return PHX_ERR_INVALID; }
     if (begin_cap < 0 || end_cap < 0 || (begin_cap > 0 && !begin) || (end_cap > 0 && !end)) {
@@ -1550,7 +1535,7 @@ int World::contact_events(int32_t* begin, int begin_cap, int64_t* begin_total, i
 int World::contact_markers_device(void* d_out, int cap)
 {
     static const char* const what = "phx_world_get_contact_markers_device";
-    if (mid_step_) { set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what); return PHX_ERR_STATE; }
+    PHX_TRY(refuse_mid_step(what));
     if (cap < 0) { set_error("%s: negative cap %d", what, cap); return PHX_ERR_INVALID; }
     if (cap > 0 && (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 7u))) { set_error("%s: the output must be an 8-byte aligned device pointer", what); return PHX_ERR_INVALID; }
     if ((long long)cap < 2ll * nm) { set_error("%s: room for %d markers, the world has %d contact-point slots", what, cap, 2 * nm); return PHX_ERR_CAPACITY; }
@@ -1617,8 +1602,7 @@ int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(count >= 1 && shard >= 0 && shard < count, "bad shard");
-    if (count > 1) PHX_TRY(w->impl.refuse_filters("phx_world_set_shard"));
-    if (count > 1) PHX_TRY(w->impl.refuse_materials("phx_world_set_shard"));
+    if (count > 1) PHX_TRY(w->impl.refuse_tables("phx_world_set_shard"));
     w->impl.shard = shard; w->impl.shard_count = count;
     PHX_TRY(w->impl.solver().set_shard(shard, count));
     return PHX_OK;
@@ -1659,8 +1643,7 @@ void* phx_world_stream(phx_world* w) { return w ? (void*)w->impl.stream() : null
 int phx_world_set_comm(phx_world* w, phx_comm* c)
 {
     PHX_REQUIRE(w, "null handle");
-    if (c) PHX_TRY(w->impl.refuse_filters("phx_world_set_comm"));
-    if (c) PHX_TRY(w->impl.refuse_materials("phx_world_set_comm"));
+    if (c) PHX_TRY(w->impl.refuse_tables("phx_world_set_comm"));
     return w->impl.set_comm(c ? &c->impl : nullptr);
 }
 
@@ -1869,8 +1852,7 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
 {
     PHX_REQUIRE(w && global_index && body_count && bounds && moved, "null handle / arguments");
     PHX_REQUIRE(scene_size >= *body_count && capacity >= *body_count, "bad sizes");
-    PHX_TRY(w->impl.refuse_filters("phx_world_reslab"));
-    PHX_TRY(w->impl.refuse_materials("phx_world_reslab"));
+    PHX_TRY(w->impl.refuse_tables("phx_world_reslab"));
     phx::SlabTransport tp;
     PHX_TRY(slab_transport(transport, w->impl, &tp));
     phx::SlabState st;

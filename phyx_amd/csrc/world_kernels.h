@@ -133,14 +133,57 @@ static __global__ void __launch_bounds__(256) k_set_inverse_masses(const int* __
     }
 }
 
+// ---- the optional per-body columns ---------------------------------------------------------------------------------------------------
+// A column holds one value per body and exists only once some body's value was set (world.hip BodyTable); until then every body has
+// the column's default and the step runs the kernels it always ran.  A column states its stored type, its default, and the conversions
+// between the stored value and the C ABI's struct, which is also the form a batch is staged in.
+struct FilterColumn {                  // include/phyx_amd.h COLLISION FILTERS; the rule: common.h collision_filter_pass
+    using value = uint4;               // {category, mask, group, 0}
+    using api = phx_collision_filter;
+    static constexpr const char* plural = "collision filters";
+    static __host__ __device__ value initial() { return make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u); }
+    static __host__ __device__ value stored(const api& f) { return make_uint4(f.category, f.mask, (unsigned)f.group, 0u); }
+    static api shown(const value& v) { return api{v.x, v.y, (int32_t)v.z}; }
+    static bool is_initial(const value& v) { return v.x == FILTER_DEFAULT_CATEGORY && v.y == FILTER_DEFAULT_MASK && v.z == 0u; }
+};
+struct MaterialColumn {                // include/phyx_amd.h MATERIALS; the pair rule: solver_kernels.h material_mu / material_e
+    using value = float2;              // {friction, restitution}
+    using api = phx_material;
+    static constexpr const char* plural = "materials";
+    static __host__ __device__ value initial() { return make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION); }
+    static __host__ __device__ value stored(const api& m) { return make_float2(m.friction, m.restitution); }
+    static api shown(const value& v) { return api{v.x, v.y}; }
+    static bool is_initial(const value& v) { return v.x == MATERIAL_DEFAULT_FRICTION && v.y == MATERIAL_DEFAULT_RESTITUTION; }
+};
+static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float), "a batch is staged as 4-byte words");
+
+// a column that becomes active is filled with its default, then the staged batch {indices | values} is scattered into it
+template <class Column>
+static __global__ void __launch_bounds__(256) k_fill_column(typename Column::value* __restrict__ column, int n)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) column[i] = Column::initial();
+}
+template <class Column>
+static __global__ void __launch_bounds__(256) k_scatter_column(const int* __restrict__ idx, const typename Column::api* __restrict__ v, int count,
+                                                               typename Column::value* __restrict__ column)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) column[idx[k]] = Column::stored(v[k]);
+}
+
+// what the spawn and the removal move beside the records and the resident arrays: the pending accelerations (consumed by the next
+// IntegrateVelocity) and the columns above.  Null = absent.  A new column is one member here and one line in each of the two kernels.
+struct BodyColumns {
+    float4* accel;
+    uint4* filters;
+    float2* materials;
+};
+
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
 // as AddBody does (world.hip body_record); only the AABB is computed here, by the UpdateGeom of set_poses (ref: Geom.h:79-85).  The
-// record is AddBody's byte for byte, the resident state has zero velocities, and a pending acceleration slot starts at zero, a
-// collision filter table (null while every filter is the default) the default filter, a material table (null while no material was
-// set) the default material.
+// record is AddBody's byte for byte, the resident state has zero velocities, a pending acceleration slot starts at zero and every
+// column that exists gets its default.
 static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __restrict__ rows, int count, int first, WorldBodies w,
-                                                             phx_rigid_body* __restrict__ records, float4* __restrict__ accel, uint4* __restrict__ filters,
-                                                             float2* __restrict__ materials)
+                                                             phx_rigid_body* __restrict__ records, BodyColumns cols)
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
         const float* q = rows + 10 * (size_t)k;
@@ -161,9 +204,9 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         w.frame[i] = make_float4(xv.x, xv.y, yv.x, yv.y);
         w.aabb[i] = box;
         w.size[i] = make_float2(size.x, size.y);
-        if (accel) accel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (filters) filters[i] = make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u);
-        if (materials) materials[i] = make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION);
+        if (cols.accel) cols.accel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (cols.filters) cols.filters[i] = FilterColumn::initial();
+        if (cols.materials) cols.materials[i] = MaterialColumn::initial();
     }
 }
 
@@ -423,26 +466,6 @@ static __global__ void __launch_bounds__(256) k_joints_fill(phx_contact_joint* _
     }
 }
 
-// collision filters (phx_world_set_collision_filters): the table of a world whose filters were all the default is filled first, then
-// the staged batch {indices | {category, mask, group} per body} is scattered into it
-// materials (phx_world_set_materials): the same two steps on the {friction, restitution} table
-static __global__ void __launch_bounds__(256) k_default_materials(float2* __restrict__ materials, int n)
-{
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) materials[i] = make_float2(MATERIAL_DEFAULT_FRICTION, MATERIAL_DEFAULT_RESTITUTION);
-}
-static __global__ void __launch_bounds__(256) k_set_materials(const int* __restrict__ idx, const float2* __restrict__ v, int count, float2* __restrict__ materials)
-{
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) materials[idx[k]] = v[k];
-}
-static __global__ void __launch_bounds__(256) k_default_filters(uint4* __restrict__ filters, int n)
-{
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) filters[i] = make_uint4(FILTER_DEFAULT_CATEGORY, FILTER_DEFAULT_MASK, 0u, 0u);
-}
-static __global__ void __launch_bounds__(256) k_set_filters(const int* __restrict__ idx, const unsigned* __restrict__ v, int count, uint4* __restrict__ filters)
-{
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) filters[idx[k]] = make_uint4(v[3 * k], v[3 * k + 1], v[3 * k + 2], 0u);
-}
-
 // ---- removal of bodies between steps (phx_world_remove_bodies / remove_outside) -----------------------------------------------
 // The result is defined as what phx_world_set_state would make of the filtered state (include/phyx_amd.h): kept bodies, manifolds
 // and joints stay in their old order, so every new position is an exclusive scan of keep flags.  keep[] holds one word per body;
@@ -511,14 +534,12 @@ __device__ __forceinline__ bool scanned_flag(const unsigned* __restrict__ before
 // Bodies: kept record i goes to out[to], to = bnew[i], as one 128-byte line, with `index` = to; the resident arrays (and the pending
 // accelerations) at `to` are made from it by the upload's own conversion (record_to_world), as phx_world_set_state would make them.
 // `refresh` (the records are stale): the record is first brought up to date from the resident arrays (world_record), as the getter
-// would.  remap[i] = to, or -1.  accel_nonzero counts the kept records with an acceleration (the upload's test, world.hip).  A collision
-// filter table (null while every filter is the default) and a material table (null while no material was set) move with the bodies.
+// would.  remap[i] = to, or -1.  accel_nonzero counts the kept records with an acceleration (the upload's test, world.hip).  The columns
+// that exist in `cols` move with the bodies into `out_cols` (whose accelerations, if pending, are made from the record).
 static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_body* __restrict__ records, WorldBodies w, int n, int refresh,
                                                               const unsigned* __restrict__ keep, const unsigned* __restrict__ bnew,
-                                                              phx_rigid_body* __restrict__ out_records, WorldBodies out, float4* __restrict__ out_accel,
-                                                              int* __restrict__ remap, unsigned* __restrict__ accel_nonzero,
-                                                              const uint4* __restrict__ filters, uint4* __restrict__ out_filters,
-                                                              const float2* __restrict__ materials, float2* __restrict__ out_materials)
+                                                              phx_rigid_body* __restrict__ out_records, WorldBodies out, int* __restrict__ remap,
+                                                              unsigned* __restrict__ accel_nonzero, BodyColumns cols, BodyColumns out_cols)
 {
     static_assert(sizeof(phx_rigid_body) == 8 * sizeof(float4), "a record is one 128-byte line");
     unsigned nonzero = 0;
@@ -539,10 +560,10 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
 #pragma unroll
         for (int k = 0; k < 8; ++k) dst[k] = line[k];
         record_to_world(b, out, to);
-        if (filters) out_filters[to] = filters[i];
-        if (materials) out_materials[to] = materials[i];
-        if (out_accel) {
-            out_accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
+        if (cols.filters) out_cols.filters[to] = cols.filters[i];
+        if (cols.materials) out_cols.materials[to] = cols.materials[i];
+        if (out_cols.accel) {
+            out_cols.accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;
         }
     }
