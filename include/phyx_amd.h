@@ -174,6 +174,12 @@ int phx_solver_get_island_trace(phx_solver* s, uint64_t* out, int32_t cap_groups
  * waited in, [3] working steps with at most 32 lanes << 32 | idle steps, [4] cycles in the joint update with more than 32
  * lanes active, [5] such steps */
 int phx_solver_get_wave_trace(phx_solver* s, uint64_t* out, int32_t cap_words, int32_t* waves_per_group);
+/* per LDS group (groups x *words_per_group words), the 100 MHz clock: [0] the first level of the set-up's loads is back, [1] the second,
+ * [2] records in LDS and compared, [3] refreshed, [4..7] PreStep classes 0..3 done, [8] first sweep done, [9] commit decided,
+ * [10] results issued; [16 + 8 w ...] wave w, summed over its working class steps of the impulse-only sweeps, in shader cycles (filled
+ * with the per-wave counts on only): barrier released -> LDS data back, -> last FMA, -> stores issued, -> LDS acknowledged, -> barrier
+ * released, [5] such steps (only those in which the wave's first lane was evaluated are counted: the intervals are that lane's), [6] 1 if the wave touches a static body */
+int phx_solver_get_phase_trace(phx_solver* s, uint64_t* out, int32_t cap_words, int32_t* words_per_group);
 
 /* Post-solve exchange of an island-sharded solve (BASELINE config 3; counterpart of the reference merging every island's
  * bodies back after its parallel island loop, ref: src/Solver.cpp:86-91, 482-494, 527-547).  Every rank holds a replica

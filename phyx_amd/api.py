@@ -330,6 +330,16 @@ class Solver:
         check(self.L.phx_solver_get_wave_trace(self.h, _ptr(out), out.size, C.byref(w)))
         return out[:n.value]
 
+    def phase_trace(self):
+        """(groups, words) uint64: the island kernel's finer phase stamps and, with waves=True, where a working wave's class step goes
+        (include/phyx_amd.h phx_solver_get_phase_trace)."""
+        n, w = C.c_int32(0), C.c_int32(0)
+        check(self.L.phx_solver_get_island_trace(self.h, None, 0, C.byref(n)))
+        check(self.L.phx_solver_get_phase_trace(self.h, None, 0, C.byref(w)))
+        out = np.zeros((max(n.value, 1), w.value), dtype=np.uint64)
+        check(self.L.phx_solver_get_phase_trace(self.h, _ptr(out), out.size, C.byref(w)))
+        return out[:n.value]
+
     def set_shard(self, shard, shard_count):
         """Sweep only the schedule groups g with g % shard_count == shard (multi-GPU island sharding)."""
         check(self.L.phx_solver_set_shard(self.h, shard, shard_count))

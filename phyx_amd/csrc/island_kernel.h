@@ -22,6 +22,8 @@ namespace phx {
 // phase stamps of the island kernel (tools/island_trace.py; the constant 100 MHz clock all XCDs share): 0 start, 1 records loaded, 2 refreshed, 3 pre-stepped, 4 swept,
 // 5 written back; word 6 = XCC id | s_memtime ticks of the whole workgroup << 4, word 7 = classes << 32 | impulse sweeps executed
 #define PHX_ISL_STAMP(k) do { if (TRACE && threadIdx.x == 0) iv.trace[(size_t)group * 8 + (k)] = wall_clock64(); } while (0)
+// ... and the stamps between them (island_view.h ISL_PHASE_WORDS; tools/island_phase_account.py)
+#define PHX_ISL_PHASE(k) do { if (TRACE && threadIdx.x == 0 && iv.phase_trace) iv.phase_trace[(size_t)group * ISL_PHASE_WORDS + (k)] = wall_clock64(); } while (0)
 
 // ---- body-state storage of the island kernel: fp32 (default) or the fp16 ablation ------------------------------
 template <bool HALF> struct BodyStore { using type = float4; };

@@ -6,8 +6,9 @@
     // body velocities in LDS: float4 {vx, vy, w, tag}, or — fp16 body-state ablation (BASELINE config 5) — four 16-bit
     // words {half vx, half vy, half w, int16 tag}; arithmetic is fp32 either way, HALF rounds on every store
     using BodyT = typename BodyStore<HALF>::type;
-    __shared__ BodyT imp[NB];
-    __shared__ BodyT disp[NB];
+    // (record NB of either table belongs to nobody: what a lane would store for a static body goes there — sl1, sl2 below)
+    __shared__ BodyT imp[NB + 1];
+    __shared__ BodyT disp[NB + 1];
     // static-tag words [imp|disp][parity][body]; during set-up the same 12 KB hold {invMass, invInertia, pos} per body
     __shared__ __attribute__((aligned(16))) unsigned sw_raw[4 * NB];
     __shared__ unsigned char is_st[NB];
@@ -34,63 +35,71 @@
 
     // Set-up is two dependent HBM round trips: level 1 = the group's descriptor, the lane's unit record and its body ids (all at
     // addresses that depend on the group number only), level 2 = the body records, the joints and the contact points.
-    constexpr int BI = (NB + T - 1) / T;                   // body records per lane
+    // EVERY request of both levels is unconditional — a lane without a unit asks for joint 0 and its contact point, a lane without a
+    // body for body 0, and throws the answer away: a request under a branch is waited for at the join with `s_waitcnt vmcnt(0)`
+    // (loads return in order, and the compiler cannot count what a branch may have skipped), which made level 2 THREE round trips:
+    // the joints were asked for only when the body records were back, the follower's contact point only when the leader's was.
+    static_assert(NB % T == 0, "a lane owns NB / T whole body slots");
+    constexpr int BI = NB / T;                             // body records per lane
     int body_id[BI];
 #pragma unroll
-    for (int k = 0; k < BI; ++k) body_id[k] = tid + k * T < NB ? iv.bodies[(size_t)group * NB + tid + k * T] : -1;      // (entries past the group's count: unused words of its table)
+    for (int k = 0; k < BI; ++k) body_id[k] = iv.bodies[(size_t)group * NB + tid + k * T];      // (entries past the group's count: unused words of its table)
     const int4 ua = iv.unit_recs[2 * ((size_t)group * T + tid)], ub = iv.unit_recs[2 * ((size_t)group * T + tid) + 1];
     const int4 d = iv.desc[group];
     const int units_word = iv.units[group];
+    if (TRACE) { __builtin_amdgcn_s_waitcnt(0x0F70); PHX_ISL_PHASE(0); }      // (diagnostic build only: level 1 is back)
     // (schedule.h LANES: the classes' lane ranges sit on wave boundaries where the lanes allow it — a lane has a unit or it has not)
     const int ncol = island_word_classes(units_word), nstatic = island_word_static(units_word);
     const bool live = ua.x >= 0;
-#pragma unroll
-    for (int k = 0; k < BI; ++k) if (tid + k * T >= d.w) body_id[k] = -1;
     const bool has2 = live && ua.y >= 0;
     const int jid0 = live ? ua.x : 0, jid1 = has2 ? ua.y : 0;
     const unsigned loc = live ? (unsigned)ub.x : 0u;
     const int col = live ? ub.y : -1;
-    if (tid < 3) { flag_imp[tid] = 0; flag_disp[tid] = 0; }
-
+    const int l1 = (int)(loc & 0xFFFFu), l2 = (int)(loc >> 16);
+    const bool verify = iv.mode == ISL_VERIFY;             // (launch-uniform)
+    // level 2, in the order its addresses become known: the joints and the contact points hang on `ua` alone ...
+    // (the contact point index is part of the topology the schedule was built — and is gated — for: ua.z == j.contact_point_index)
+    const phx_contact_joint j = joints[jid0], jf = joints[jid1];
+    const float4* const cpa = reinterpret_cast<const float4*>(&cps[clamp_index(live ? ua.z : 0, v.ncp)]);   // 32-byte records
+    const float4* const cpb = reinterpret_cast<const float4*>(&cps[clamp_index(has2 ? ua.w : 0, v.ncp)]);
+    const float4 cpa0 = cpa[0], cpb0 = cpb[0];
+    const float2 nna = *reinterpret_cast<const float2*>(cpa + 1), nnb = *reinterpret_cast<const float2*>(cpb + 1);
+    // ... the body records on the body ids and the group's body count
+#pragma unroll
+    for (int k = 0; k < BI; ++k) if (tid + k * T >= d.w) body_id[k] = -1;
     float4 rec_imp[BI], rec_disp[BI], rec_par[BI];
     float2 rec_mat[BI];
 #pragma unroll
-    for (int k = 0; k < BI; ++k) {                         // level 2: the resident arrays ARE PrepareBodies' staged form
-        if (body_id[k] < 0) continue;                      //          (ref: Solver.cpp:456-480; body_view.h): three coalesced 16-byte loads
-        rec_imp[k] = bv.vel[body_id[k]]; rec_imp[k].w = __int_as_float(-1);
-        rec_disp[k] = bv.dvel[body_id[k]]; rec_disp[k].w = __int_as_float(-1);
-        rec_par[k] = bv.mpos[body_id[k]];
-        if (MAT) rec_mat[k] = view_material<MAT>(v, body_id[k]);      // (and the body's material: one 8-byte load)
+    for (int k = 0; k < BI; ++k) {                         // the resident arrays ARE PrepareBodies' staged form
+        const int b = body_id[k] < 0 ? 0 : body_id[k];     // (ref: Solver.cpp:456-480; body_view.h): three coalesced 16-byte loads
+        rec_imp[k] = bv.vel[b]; rec_imp[k].w = __int_as_float(-1);
+        rec_disp[k] = bv.dvel[b]; rec_disp[k].w = __int_as_float(-1);
+        rec_par[k] = bv.mpos[b];
+        if (MAT) rec_mat[k] = view_material<MAT>(v, b);    // (and the body's material: one 8-byte load)
     }
+    // ISL_VERIFY: the unit record against the joint it points at (the body ids: two more words of the group's table, L2-warm)
+    int g1 = 0, g2 = 0;
+    if (verify) { g1 = iv.bodies[(size_t)group * NB + l1]; g2 = iv.bodies[(size_t)group * NB + l2]; }
+    if (tid < 3) { flag_imp[tid] = 0; flag_disp[tid] = 0; }
+
     IslJoint q0{}, q1{};
     float4 da0 = make_float4(0.f, 0.f, 0.f, 0.f), da1 = da0;     // delta1, delta2 of the two contact points
-    int l1 = 0, l2 = 0;
-    const bool verify = iv.mode == ISL_VERIFY;             // (launch-uniform)
     bool differs = false;                                  // ISL_VERIFY: the schedule was built for other joints / other static bodies
-    phx_contact_joint jf{};
-    if (has2) jf = joints[jid1];
     if (live) {                                            // PrepareJoints (ref: Solver.cpp:509-521)
-        const phx_contact_joint j = joints[jid0];
-        // (the contact point index is part of the topology the schedule was built — and is gated — for: ua.z == j.contact_point_index)
-        const float4* cp4 = reinterpret_cast<const float4*>(&cps[clamp_index(ua.z, v.ncp)]);   // 32-byte records
-        da0 = cp4[0];
-        const float2 nn = *reinterpret_cast<const float2*>(cp4 + 1);
-        q0.nx = nn.x; q0.ny = nn.y;
-        l1 = (int)(loc & 0xFFFFu); l2 = (int)(loc >> 16);
+        da0 = cpa0;
+        q0.nx = nna.x; q0.ny = nna.y;
         q0.accN = j.normal_accumulated_impulse; q0.accF = j.friction_accumulated_impulse;
-        if (verify) {      // the unit record against the joint it points at (the body ids: two more words of the group's table, L2-warm)
-            const int g1 = iv.bodies[(size_t)group * NB + l1], g2 = iv.bodies[(size_t)group * NB + l2];
+        if (verify) {
             differs = j.contact_point_index != ua.z || j.body1 != g1 || j.body2 != g2;
             if (has2) differs |= jf.contact_point_index != ua.w || jf.body1 != g1 || jf.body2 != g2;
         }
     }
     if (has2) {
-        const float4* cp4 = reinterpret_cast<const float4*>(&cps[clamp_index(ua.w, v.ncp)]);
-        da1 = cp4[0];
-        const float2 nn = *reinterpret_cast<const float2*>(cp4 + 1);
-        q1.nx = nn.x; q1.ny = nn.y;
+        da1 = cpb0;
+        q1.nx = nnb.x; q1.ny = nnb.y;
         q1.accN = jf.normal_accumulated_impulse; q1.accF = jf.friction_accumulated_impulse;
     }
+    if (TRACE) { __builtin_amdgcn_s_waitcnt(0x0F70); PHX_ISL_PHASE(1); }      // (diagnostic build only: level 2 is back, nothing of it used yet)
 #pragma unroll
     for (int k = 0; k < BI; ++k) {
         if (body_id[k] < 0) continue;
@@ -103,15 +112,26 @@
         is_st[i] = st ? 1 : 0;
         differs |= st != (i < nstatic);                    // (the builders list a group's static bodies first)
     }
+    // Level 2 is back, whole, in every mode (the refresh behind the barrier needs all of it): said here, in front of the arrival, so
+    // that no later wait for a load — it would be `vmcnt(0)`, the counter is one and in order — also waits for the arrival's answer.
+    __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
     unsigned long long arrived_before = 0ull;              // (lane 0) what the shard counter read when this workgroup arrived
     unsigned my_arrival = 1u;
+    PHX_ISL_PHASE(2);
     if (verify) {
         // ARRIVE: this workgroup has compared everything it owns.  One device-scope atomic carries the arrival and the verdict, so
         // whoever sees all arrivals also sees every verdict (island_view.h).  The returned value is looked at behind PreStep:
         // nothing waits for this round trip.
         const int any = __syncthreads_or(differs ? 1 : 0);
         my_arrival = any ? 1u + ISL_BAD : 1u;
-        if (tid == 0) arrived_before = atomicAdd(&iv.shards[((int)blockIdx.x % ISL_SHARDS) * ISL_SHARD_STRIDE], (unsigned long long)my_arrival);
+        if (tid == 0) {
+            // (the index goes through a vector register on purpose: on a wave-uniform address the compiler's atomic optimiser
+            //  combines the wave's lanes and reads the returned value back with v_readfirstlane at once — `s_waitcnt vmcnt(0)`
+            //  right behind the atomic, a device-scope round trip in front of the barrier every wave of the group waits at)
+            int shard = ((int)blockIdx.x % ISL_SHARDS) * ISL_SHARD_STRIDE;
+            asm volatile("" : "+v"(shard));
+            arrived_before = atomicAdd(&iv.shards[shard], (unsigned long long)my_arrival);
+        }
     } else __syncthreads();
     PHX_ISL_STAMP(1);
     float im1 = 0.f, ii1 = 0.f, im2 = 0.f, ii2 = 0.f;
@@ -148,16 +168,22 @@
 #pragma unroll
     for (int k = 0; k < BI; ++k)
         if (body_id[k] >= 0) stirs |= (__float_as_uint(rec_disp[k].x) | __float_as_uint(rec_disp[k].y) | __float_as_uint(rec_disp[k].z)) != 0u;
+    PHX_ISL_PHASE(3);
     const bool disp_quiet = __syncthreads_or(stirs ? 1 : 0) == 0;      // (the barrier that was here anyway)
     if (MAT) {                                             // the materials are read: the displacing velocities take their place
 #pragma unroll
         for (int k = 0; k < BI; ++k) if (body_id[k] >= 0) body_store(disp, tid + k * T, rec_disp[k]);
     }
-    for (int i = tid; i < 4 * NB; i += T) sw_raw[i] = 0;     // the parameter table is dead: now the tag words
+#pragma unroll
+    for (int k = 0; k < BI; ++k) par[tid + k * T] = make_float4(0.f, 0.f, 0.f, 0.f);      // the parameter table is dead: now the tag words (all zero bits)
     const bool st1 = (im1 == 0.f && ii1 == 0.f), st2 = (im2 == 0.f && ii2 == 0.f);
     const bool wave_static = __any(live && (st1 || st2));      // (wave-uniform, fixed for the solve)
     int sm1 = st1 ? -1 : 0, sm2 = st2 ? -1 : 0;                // (as masks: the hot form selects with them instead of branching)
     asm volatile("" : "+v"(sm1), "+v"(sm2));
+    // A static body's record is never stored.  Said with the ADDRESS, not with a predicate: a lane stores both records of its unit
+    // in every step, a static one into the spare record NB.  (As `if (!st1) store; if (!st2) store` the end of a class step — the
+    // one stretch between a wave's last FMA and the barrier everybody waits at — was two exec regions with two taken branches.)
+    const int sl1 = st1 ? NB : l1, sl2 = st2 ? NB : l2;
     __syncthreads();
     PHX_ISL_STAMP(2);
 
@@ -170,14 +196,18 @@
                 if (HALF) { B1 = body_round<HALF>(B1); B2 = body_round<HALF>(B2); }      // (the ablation rounds on every joint's store)
                 prestep_joint(q1, q1.accN, q1.accF, B1, B2, im1, ii1, im2, ii2, false, false);
             }
-            if (!st1) body_store(imp, l1, B1);
-            if (!st2) body_store(imp, l2, B2);
+            body_store(imp, sl1, B1);
+            body_store(imp, sl2, B2);
         }
         __syncthreads();
+        if (TRACE && c < 4) PHX_ISL_PHASE(4 + c);
     }
 
     if (verify && tid == 0) {
         // the last arriver of a shard forwards the shard's verdict to the solve's control word
+        // (both halves of the answer stay reserved until here: a register of a load in flight that is given to another value is
+        //  waited for where that value is written — the high half is dead, and was, at the head of the refresh)
+        asm volatile("" : "+v"(arrived_before));
         const unsigned now = (unsigned)arrived_before + my_arrival;
         const unsigned shard = blockIdx.x % ISL_SHARDS, want = (iv.nexpect - shard + ISL_SHARDS - 1) / ISL_SHARDS;
         if ((now & ISL_ARRIVE_MASK) == want) atomicAdd(iv.ctl, now >= ISL_BAD ? (unsigned long long)(1u + ISL_BAD) : 1ull);
@@ -197,11 +227,18 @@
     // TRACE level 2 (phx_solver_set_trace: per-wave cycle counts of every class step — ~15 % slower)
     const bool wt = TRACE && iv.wave_trace;
     unsigned long long ts0 = 0ull, ts1 = 0ull; bool working = false;
-    auto step_begin = [&]() { if (wt) { ts0 = __builtin_readcyclecounter(); working = __any(col == c); } };
-    auto step_work_done = [&]() { if (wt) ts1 = __builtin_readcyclecounter(); };
-    auto step_end = [&]() {
+    // ... and, in the impulse-only loop, where a working wave's step goes (island_view.h ISL_PHASE_WORDS; what the wave's FIRST lane saw:
+    // a step in which that lane has no unit of the class, or was left out by the skip test, is not counted): barrier released -> LDS data
+    // back (tp1) -> last FMA (tp2) -> stores issued (tp3) -> lgkmcnt(0) (ts1) -> barrier released; a step the skip test left out counts apart
+    unsigned tp1 = 0u, tp2 = 0u, tp3 = 0u, in_step[5] = {0u, 0u, 0u, 0u, 0u};      // (32-bit: the differences are what counts)
+    unsigned in_n = 0u;
+    auto step_begin = [&]() { if (wt) { ts0 = __builtin_readcyclecounter(); working = __any(col == c); tp3 = 0u; } };
+    auto step_work_done = [&]() { if (wt) { __builtin_amdgcn_s_waitcnt(0xC07F); ts1 = __builtin_readcyclecounter(); } };      // lgkmcnt(0): the barrier's own wait
+    auto step_end = [&](const bool hot) {
         if (!wt) return;
         const unsigned long long ts2 = __builtin_readcyclecounter();
+        if (working && hot && tp3)
+            { in_step[0] += tp1 - (unsigned)ts0; in_step[1] += tp2 - tp1; in_step[2] += tp3 - tp2; in_step[3] += (unsigned)ts1 - tp3; in_step[4] += (unsigned)(ts2 - ts1); ++in_n; }
         if (working) {
             if (__popcll(__ballot(col == c)) > 32) { tw_work_big += ts1 - ts0; ++tw_nbig; } else { tw_work += ts1 - ts0; ++tw_nwork; }
             tw_bar += ts2 - ts1;
@@ -213,7 +250,8 @@
     // raises them to `it` — and one tag update; straight-line but for the follower's mask: a class step is one wave's instruction
     // stream, and every taken branch in it is ~20 cycles.  `ws` = some unit of the wave touches a static body (wave-uniform, fixed for
     // the solve): only then the static tags are looked up and raised (they are class-synchronous: solver_kernels.h), the static records
-    // restored between the joints (a static body's record is never stored: the follower must see it untouched) and left unstored.
+    // restored between the joints (a static body's record is never stored: the follower must see it untouched); what the unit would
+    // store for them goes to the spare record (sl1, sl2).
     // (Rounds 2-4 had a general form beside this one — a skip test and a tag update per joint, two dependent LDS round trips — which
     //  every first sweep still took: same results, ~2.5 x the cycles.)
     auto half_step = [&](auto IMPC, const bool ws) {
@@ -229,6 +267,7 @@
         //  branch — the six velocity words: two dependent round trips on the critical path of every class step)
         if (!HALF) asm volatile("" : "+v"(B1.x), "+v"(B1.y), "+v"(B1.z), "+v"(B1.w), "+v"(B2.x), "+v"(B2.y), "+v"(B2.z), "+v"(B2.w));
         if (ws) asm volatile("" : "+v"(pw1), "+v"(cw1), "+v"(pw2), "+v"(cw2));
+        if (wt) { __builtin_amdgcn_s_waitcnt(0xC07F); tp1 = (unsigned)__builtin_readcyclecounter(); }
         bool active = max(__float_as_int(B1.w), __float_as_int(B2.w)) > it - 2;
         if (ws) {
             // solver_kernels.h static_productive on the words already here — every lane evaluates both bodies' tests and selects (no
@@ -254,6 +293,7 @@
                 prod |= IMP ? impulse_productive(impulse_visit(q1, q1.accN, q1.accF, B1, B2, im1, ii1, im2, ii2, mu))
                              : displacement_productive(displacement_visit(q1, q1.accD, B1, B2, im1, ii1, im2, ii2));
             }
+            if (wt) { asm volatile("" : "+v"(B1.x), "+v"(B1.y), "+v"(B1.z), "+v"(B2.x), "+v"(B2.y), "+v"(B2.z)); tp2 = (unsigned)__builtin_readcyclecounter(); }
             B1.w = prod ? __int_as_float(it) : B1.w; B2.w = prod ? __int_as_float(it) : B2.w;
             if (prod) {
                 if (IMP) flag_imp[slot] = 1; else flag_disp[slot] = 1;
@@ -262,8 +302,9 @@
                     if (st2) atomicMax(&sw[it & 1][l2], static_word(it, c));
                 }
             }
-            if (!ws || !st1) body_store(rec, l1, B1);
-            if (!ws || !st2) body_store(rec, l2, B2);
+            body_store(rec, sl1, B1);
+            body_store(rec, sl2, B2);
+            if (wt) tp3 = (unsigned)__builtin_readcyclecounter() | 1u;
         }
     };
     const std::true_type IMPULSES{}; const std::false_type DISPLACEMENT{};
@@ -291,11 +332,13 @@
             }
             step_work_done();
             __syncthreads();
-            step_end();
+            step_end(false);
         }
         if (imp_on) { done_imp = it + 1; imp_alive = flag_imp[slot] != 0; }        // (behind the last class step's barrier)
         if (disp_on) { done_disp = it + 1; disp_alive = flag_disp[slot] != 0; }
+        if (TRACE && it == 0) PHX_ISL_PHASE(8);
     }
+
     if (hot_from_here)
         for (; it < ci && imp_alive; ++it) {
             peek_ctl();
@@ -305,9 +348,10 @@
                 if (col == c) { if (wave_static) half_step(IMPULSES, true); else half_step(IMPULSES, false); }
                 step_work_done();
                 __syncthreads();
-                step_end();
+                step_end(true);
             }
             done_imp = it + 1; imp_alive = flag_imp[slot] != 0;
+            if (TRACE && it == 0) PHX_ISL_PHASE(8);
         }
 
     PHX_ISL_STAMP(4);
@@ -331,6 +375,7 @@
             if (!settled && polls == iv.wait_polls) atomicOr(iv.ctl, ISL_TIMEOUT);      // (nobody may take this solve for complete)
         }
         __syncthreads();
+        PHX_ISL_PHASE(9);
         if (!s_commit) { if (iv.stamp_end) solve_stamp_end(v.stamps); return; }
     } else if (iv.mode == ISL_GATED && *v.fingerprint != v.expected_fingerprint) { if (iv.stamp_end) solve_stamp_end(v.stamps); return; }
     if (live) {                                            // FinishJoints (ref: Solver.cpp:543-544)
@@ -364,8 +409,15 @@
         w[0] = tw_work; w[1] = tw_bar; w[2] = tw_idle; w[3] = ((unsigned long long)tw_nwork << 32) | tw_nidle; w[4] = tw_work_big; w[5] = tw_nbig;
         w[6] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));        // HW_REG_HW_ID: wave, SIMD, pipe, CU, SH, SE ... (tools/simd_map.py)
         w[7] = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 0xF;  // XCC id
+        if (iv.phase_trace) {
+            unsigned long long* p = iv.phase_trace + (size_t)group * ISL_PHASE_WORDS + 16 + (tid >> 6) * 8;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) p[k] = in_step[k];
+            p[5] = in_n; p[6] = wave_static ? 1ull : 0ull;
+        }
     }
     if (TRACE) {
+        PHX_ISL_PHASE(10);
         __builtin_amdgcn_s_waitcnt(0);         // the stores above have left the wave
         PHX_ISL_STAMP(5);
         if (tid == 0) {

@@ -38,6 +38,13 @@ __host__ __device__ inline int island_word_units(int w) { return w & 0xFFF; }
 __host__ __device__ inline int island_word_classes(int w) { return (w >> 12) & 0xFF; }
 __host__ __device__ inline int island_word_static(int w) { return (int)((unsigned)w >> 20); }
 
+// IslandView::phase_trace, per group (the 100 MHz clock; the TRACE instantiation only, which also WAITS for its loads at [0] and [1]): [0] level 1 of the
+// set-up is back, [1] level 2 is back, [2] records in LDS and compared, [3] refreshed (in front of the barrier), [4 + c] PreStep class
+// c < 4 done, [8] first sweep done, [9] commit decided, [10] results and counters issued (trace word 5: they have left);
+// [16 + 8 w ...] wave w, summed over its working class steps of the impulse-only sweeps, in shader cycles: barrier released -> LDS data
+// back, -> last FMA, -> stores issued, -> lgkmcnt(0), -> barrier released, [5] such steps — those in which the wave's first lane was evaluated: the intervals are that lane's, a step in which it has no unit
+// of the class or was left out by the skip test is not counted —, [6] the wave touches a static body
+constexpr int ISL_PHASE_WORDS = 96;
 constexpr int ISL_T = 256, ISL_B = 768;        // lanes = unit capacity of a group (joints: twice that); body capacity (dynamic + touched static)
 constexpr int ISL_T_BIG = 512, ISL_B_BIG = 1024;
 
@@ -58,6 +65,7 @@ struct IslandView {
     int stamp_begin, stamp_end;       // this launch is the first / last kernel of the solve: it leaves the solve's time stamps (solver_kernels.h)
     unsigned long long* wave_trace;   // null, or 8 words per wave of every group: cycles {working with <= 32 lanes, at the barrier after work, idle steps}, counts, cycles working with > 32 lanes, count
     unsigned long long* trace;        // null, or 8 words per group: shader-clock stamps of the kernel's phases (phx_solver_set_trace)
+    unsigned long long* phase_trace;  // null, or ISL_PHASE_WORDS words per group: the stamps between those, and where a working wave's class step goes
     int mode;                         // ISL_GATED / ISL_VERIFY / ISL_COMPLETE
     unsigned nexpect;                 // ISL_VERIFY: workgroups of this launch (all of them must arrive)
     unsigned long long* ctl;          // the solve's control word (= v.fingerprint): complete shards | ISL_BAD * bad shards | ISL_TIMEOUT

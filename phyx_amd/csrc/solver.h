@@ -94,6 +94,7 @@ public:
     void set_trace(int level) { trace_islands_ = level != 0; trace_waves_ = level != 1; }      // 1: phase stamps only; else also per-wave step cycles
     int get_island_trace(unsigned long long* out, int cap_groups, int* groups);
     int get_wave_trace(unsigned long long* out, int cap_words, int* waves_per_group);
+    int get_phase_trace(unsigned long long* out, int cap_words, int* words_per_group);
     int get_groups(int* offsets, int cap, int* count, int* lds_count);
     int get_lanes(int* leader_slot, int* lane, int cap, int* count);      // the LDS groups' units: leader slot -> lane of the island kernel (schedule.h LANES)
     int get_partition(int* interior_classes, int* parts, int* sweep_launches)

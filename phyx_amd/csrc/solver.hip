@@ -256,7 +256,7 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
         iv.stamp_begin = iv.stamp_end = owns_hbm_group() ? 0 : 1;      // (with an HBM group, its first and last kernels leave the stamps)
         iv.desc = isl_.desc.p; iv.ncol = isl_.ncol.p; iv.units = isl_.units.p; iv.unit_recs = isl_.unit_recs.p; iv.bodies = isl_.bodies.p;
         iv.executed = isl_.stats.p + (size_t)hash_slot_ * STATS_SET; iv.visits = isl_.visits.p + (size_t)hash_slot_ * VISITS_SET;
-        iv.trace = nullptr; iv.wave_trace = nullptr;
+        iv.trace = nullptr; iv.wave_trace = nullptr; iv.phase_trace = nullptr;
         // how the launch is gated (island_view.h).  A launch whose grid is only an upper bound of the group count (speculative
         // binning) is gated by the build it follows.
         iv.mode = mode_override >= 0 ? mode_override : isl_mode_;
@@ -277,11 +277,12 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
             island_clears_next_ = false;
         }
         if (trace_islands_ && !mat_) {                // (the materials' island kernel has no trace form)
-            // 8 words per group, then 8 words per wave (16 waves at most) of every group
-            if (isl_.trace.reserve((size_t)std::max(lg, 1) * (8 + 128)) != PHX_OK) return PHX_ERR_HIP;
-            PHX_HIP(hipMemsetAsync(isl_.trace.p, 0, (size_t)lg * (8 + 128) * sizeof(unsigned long long), stream_));
+            // 8 words per group, then 8 words per wave (16 waves at most) of every group, then ISL_PHASE_WORDS per group
+            if (isl_.trace.reserve((size_t)std::max(lg, 1) * (8 + 128 + ISL_PHASE_WORDS)) != PHX_OK) return PHX_ERR_HIP;
+            PHX_HIP(hipMemsetAsync(isl_.trace.p, 0, (size_t)lg * (8 + 128 + ISL_PHASE_WORDS) * sizeof(unsigned long long), stream_));
             iv.trace = isl_.trace.p;
             iv.wave_trace = trace_waves_ ? isl_.trace.p + (size_t)lg * 8 : nullptr;
+            iv.phase_trace = isl_.trace.p + (size_t)lg * (8 + 128);
         }
         const bool big = sched_.lds_lanes > ISL_T;
         // A schedule with LDS islands AND an HBM group (a world that is merging, or settled around a few loose stacks): the island
@@ -772,6 +773,18 @@ int DeviceSolver::get_island_trace(unsigned long long* out, int cap_groups, int*
     if (!trace_islands_ || !isl_.trace.p) { set_error("island trace is off (phx_solver_set_trace)"); return PHX_ERR_STATE; }
     if (cap_groups < lg) { set_error("island trace buffer too small"); return PHX_ERR_CAPACITY; }
     if (lg) PHX_HIP(hipMemcpy(out, isl_.trace.p, (size_t)lg * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int DeviceSolver::get_phase_trace(unsigned long long* out, int cap_words, int* words_per_group)
+{
+    PHX_TRY(synchronize());
+    const int lg = sched_.valid ? sched_.lds_groups : 0;
+    if (words_per_group) *words_per_group = ISL_PHASE_WORDS;
+    if (!out) return PHX_OK;
+    if (!trace_islands_ || !isl_.trace.p) { set_error("island trace is off (phx_solver_set_trace)"); return PHX_ERR_STATE; }
+    if (cap_words < lg * ISL_PHASE_WORDS) { set_error("phase trace buffer too small"); return PHX_ERR_CAPACITY; }
+    if (lg) PHX_HIP(hipMemcpy(out, isl_.trace.p + (size_t)lg * (8 + 128), (size_t)lg * ISL_PHASE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PHX_OK;
 }
 
