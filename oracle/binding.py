@@ -31,6 +31,7 @@ joint_dtype = np.dtype([("contact_point_index", "<i4"), ("body1", "<i4"), ("body
                         ("normal_acc", "<f4"), ("friction_acc", "<f4")])
 bp_entry_dtype = np.dtype([("minx", "<f4"), ("maxx", "<f4"), ("centery", "<f4"), ("extenty", "<f4"), ("index", "<u4")])
 sort_entry_dtype = np.dtype([("value", "<u4"), ("index", "<u4")])
+trace_record_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("mask", "<u8", (2,))])      # phx_oracle.h phxo_trace_record
 assert body_dtype.itemsize == 128 and contact_point_dtype.itemsize == 32
 assert manifold_dtype.itemsize == 16 and joint_dtype.itemsize == 20 and bp_entry_dtype.itemsize == 20
 
@@ -58,7 +59,8 @@ def build(force=False):
     if os.path.isdir("/root/reference/src") and (force or not os.path.exists(ref_so)):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
     full = [os.path.join(_HERE, "_ref", "libphyx_ref_full_%s.so" % k) for k in REF_KINDS]
-    if os.path.isdir("/root/reference/src") and (force or not all(os.path.exists(f) for f in full)):
+    harness = os.path.getmtime(os.path.join(_HERE, "ref_harness", "full_harness.cpp"))
+    if os.path.isdir("/root/reference/src") and (force or not all(os.path.exists(f) and os.path.getmtime(f) >= harness for f in full)):
         subprocess.check_call(["make", "-C", _HERE, "ref_full"], stdout=subprocess.DEVNULL)
 
 
@@ -138,6 +140,15 @@ def lib():
         L.phxo_world_sweep_tests.argtypes = [C.c_void_p]
         L.phxo_world_point_overflows.restype = C.c_int
         L.phxo_world_point_overflows.argtypes = [C.c_void_p]
+        L.phxo_trace_label_count.restype = C.c_int
+        L.phxo_trace_label.restype = C.c_char_p
+        L.phxo_trace_label.argtypes = [C.c_int]
+        L.phxo_trace_pairs.restype = C.c_int
+        L.phxo_trace_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.phxo_world_set_trace.argtypes = [C.c_void_p, C.c_int]
+        L.phxo_world_trace_records.restype = C.c_void_p
+        L.phxo_world_trace_records.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.phxo_world_trace_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.phxo_time_impulse_loop.restype = C.c_double
         L.phxo_time_impulse_loop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib = L
@@ -230,10 +241,25 @@ def ref_full_lib(kind="strict"):
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         R.reff_joint_packed.restype = C.c_int
         R.reff_joint_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        for name in ("reff_world_set_pose", "reff_world_set_velocity"):      # (a library built from an earlier harness lacks them)
+            if hasattr(R, name):
+                getattr(R, name).restype = None
+                getattr(R, name).argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         R.reff_island_stats.restype = None
         R.reff_island_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _ref_full[kind] = R
     return _ref_full[kind]
+
+
+def ref_full_can_pose(kind="strict"):
+    """Whether the prebuilt library of `kind` exists and has reff_world_set_pose / reff_world_set_velocity: one carried over from
+    an earlier ref_harness/full_harness.cpp does not, and only `make -C oracle ref_full`, where the reference's sources are, renews it."""
+    R = ref_full_lib(kind)
+    return R is not None and hasattr(R, "reff_world_set_pose") and hasattr(R, "reff_world_set_velocity")
+
+
+REF_POSE_SKIP = ("oracle/_ref/libphyx_ref_full_strict.so is absent, or was built before full_harness.cpp had reff_world_set_pose / "
+                 "reff_world_set_velocity: `make -C oracle ref_full` builds it where the reference's sources are")
 
 
 class RefWorld:
@@ -303,6 +329,18 @@ class RefWorld:
         cnt, mx = C.c_int(0), C.c_int(0)
         self.L.reff_island_stats(self.h, C.byref(cnt), C.byref(mx))
         return cnt.value, mx.value
+
+    def set_pose(self, index, frame):
+        """coords = {pos.x, pos.y, xv.x, xv.y, yv.x, yv.y}, then UpdateGeom (ref: RigidBody.h:38-42)."""
+        f = np.ascontiguousarray(frame, dtype=np.float32)
+        assert f.shape == (6,)
+        self.L.reff_world_set_pose(self.h, int(index), _p(f))
+
+    def set_velocity(self, index, v):
+        """velocity, angularVelocity = {vx, vy, angular}."""
+        f = np.ascontiguousarray(v, dtype=np.float32)
+        assert f.shape == (3,)
+        self.L.reff_world_set_velocity(self.h, int(index), _p(f))
 
     def update(self, dt=1.0 / 60.0, solve_mode=SOLVE_SCALAR, island_mode=ISLAND_SINGLE, contact_iters=15, penetration_iters=15):
         self.L.reff_world_update_pairs(self.h, dt, solve_mode, island_mode, contact_iters, penetration_iters, self.pairs)
@@ -410,6 +448,21 @@ class OracleWorld:
     def sweep_tests(self):
         return int(self.L.phxo_world_sweep_tests(self.h))
 
+    # the narrowphase branch trace of the last pre_solve (phx_oracle.h PHXO_T_*)
+    def set_trace(self, on=True):
+        self.L.phxo_world_set_trace(self.h, int(bool(on)))
+
+    def trace_records(self):
+        """One record per manifold the last pre_solve updated, in manifold order: body1, body2, the two mask words."""
+        return self._view(self.L.phxo_world_trace_records, trace_record_dtype).copy()
+
+    def trace_summary(self):
+        """(set of the labels reached in the last pre_solve, {label: number of manifolds that reached it})."""
+        mask = np.zeros(2, dtype=np.uint64)
+        counts = np.zeros(len(trace_labels()), dtype=np.uint32)
+        self.L.phxo_world_trace_summary(self.h, _p(mask), _p(counts))
+        return trace_names(mask), {n: int(c) for n, c in zip(trace_labels(), counts) if c}
+
     def update(self, dt=1.0 / 60.0, solve_mode=SOLVE_SCALAR, island_mode=ISLAND_SINGLE, contact_iters=15, penetration_iters=15):
         self.L.phxo_world_update(self.h, dt, solve_mode, island_mode, contact_iters, penetration_iters)
 
@@ -421,6 +474,36 @@ class OracleWorld:
 
     def integrate_position(self, dt=1.0 / 60.0):
         self.L.phxo_world_integrate_position(self.h, dt)
+
+
+_trace_labels = None
+
+
+def trace_labels():
+    """The trace's label names, index = bit number (phx_oracle.c trace_names)."""
+    global _trace_labels
+    if _trace_labels is None:
+        L = lib()
+        _trace_labels = tuple(L.phxo_trace_label(i).decode() for i in range(L.phxo_trace_label_count()))
+    return _trace_labels
+
+
+def trace_names(mask):
+    """The set of label names in one two-word mask."""
+    bits = (int(mask[1]) << 64) | int(mask[0])
+    return {n for i, n in enumerate(trace_labels()) if bits >> i & 1}
+
+
+def trace_pairs(bodies, points, counts):
+    """UpdateManifold on pairs given by themselves (phxo_trace_pairs): bodies (2n) body_dtype, points (2n) the cached contact points,
+    counts (n).  Returns (points, counts, masks (n, 2) uint64, overflows); the inputs are left as they were."""
+    b = np.ascontiguousarray(bodies, dtype=body_dtype)
+    pts = np.array(points, dtype=contact_point_dtype)
+    cnt = np.array(counts, dtype=np.int32)
+    assert len(b) == 2 * len(cnt) and len(pts) == 2 * len(cnt)
+    masks = np.zeros((len(cnt), 2), dtype=np.uint64)
+    over = lib().phxo_trace_pairs(_p(b), _p(pts), _p(cnt), _p(masks), len(cnt))
+    return pts, cnt, masks, over
 
 
 def solver_solve(bodies, cps, joints, solve_mode, island_mode, contact_iters, penetration_iters):

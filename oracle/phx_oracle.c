@@ -66,6 +66,23 @@ static float f16_to_f32(uint16_t h)
 static inline float qh(int half, float x) { return half ? f16_to_f32(f32_to_f16(x)) : x; }
 float phxo_round_f16(float x) { return f16_to_f32(f32_to_f16(x)); }
 
+/* ---- narrowphase branch trace (phx_oracle.h: PHXO_T_*).  A NULL trace records nothing; no label changes what is computed. ---- */
+static inline void tmark(phxo_trace* t, int label) { if (t) t->w[label >> 6] |= 1ull << (label & 63); }
+
+static const char* const trace_names[PHXO_T_COUNT] = {
+    "sep0", "sep1", "sep2", "sep3", "best0", "best1", "best2", "best3", "flip", "noflip",
+    "sup1_edge_y_pos", "sup1_edge_y_neg", "sup1_edge_x_pos", "sup1_edge_x_neg", "sup1_vertex_pp", "sup1_vertex_pn", "sup1_vertex_np", "sup1_vertex_nn",
+    "sup2_edge_y_pos", "sup2_edge_y_neg", "sup2_edge_x_pos", "sup2_edge_x_neg", "sup2_vertex_pp", "sup2_vertex_pn", "sup2_vertex_np", "sup2_vertex_nn",
+    "collapse1", "collapse2", "vv_hit", "vv_miss", "ve_hit", "ve_miss", "ev_hit", "ev_miss",
+    "ee_tc0", "ee_tc1", "ee_tc2", "ee_tc3", "ee_tc4", "ee_pick01", "ee_pick02", "ee_pick03", "ee_pick12", "ee_pick13", "ee_pick23",
+    "append_slot0", "append_slot1", "append_slot2", "append_slot3", "merge_slot0", "merge_slot1", "merge_slot2", "merge_slot3",
+    "merge_later_candidate", "equals_one_sided",
+    "from0_to0", "from0_to1", "from0_to2", "from1_to0", "from1_to1", "from1_to2", "from2_to0", "from2_to1", "from2_to2",
+    "keep_shift", "overflow", "dead", "empty_alive",
+};
+int phxo_trace_label_count(void) { return PHXO_T_COUNT; }
+const char* phxo_trace_label(int label) { return label >= 0 && label < PHXO_T_COUNT ? trace_names[label] : NULL; }
+
 #define GROW(ptr, cap, need, type)                                           \
     do {                                                                     \
         if ((size_t)(need) > (size_t)(cap)) {                                \
@@ -169,42 +186,45 @@ void phxo_rotate_vec(phxo_vec2* v, float angle)
 }
 
 /* ref: Geom.h:10-20 */
-static phxo_vec2 clipping_vertex(const phxo_body* b, phxo_vec2 axis)
+static phxo_vec2 clipping_vertex(const phxo_body* b, phxo_vec2 axis, phxo_trace* t, int base)
 {
     phxo_vec2 xdim = mul2(b->geom_xv, b->geom_size.x), ydim = mul2(b->geom_yv, b->geom_size.y);
     float xs = dot2(b->geom_xv, axis) < 0.0f ? -1.0f : 1.0f;
     float ys = dot2(b->geom_yv, axis) < 0.0f ? -1.0f : 1.0f;
+    tmark(t, base + PHXO_T_SUP_VERTEX_PP + (xs < 0.0f ? 2 : 0) + (ys < 0.0f ? 1 : 0));
     return add2(add2(b->geom_pos, mul2(xdim, xs)), mul2(ydim, ys));
 }
 
 /* ref: Geom.h:22-64 */
-static void clipping_edge(const phxo_body* b, phxo_vec2 axis, phxo_vec2* e1, phxo_vec2* e2)
+static void clipping_edge(const phxo_body* b, phxo_vec2 axis, phxo_vec2* e1, phxo_vec2* e2, phxo_trace* t, int base)
 {
     phxo_vec2 p1 = b->geom_pos, p2 = b->geom_pos, off = {0.f, 0.f};
     phxo_vec2 xdim = mul2(b->geom_xv, b->geom_size.x), ydim = mul2(b->geom_yv, b->geom_size.y);
     float xdiff = dot2(axis, b->geom_xv), ydiff = dot2(axis, b->geom_yv);
     if (fabsf(xdiff) < fabsf(ydiff)) {
-        if (dot2(axis, ydim) > 0.0f) { off = add2(off, ydim); p1 = add2(p1, xdim); p2 = sub2(p2, xdim); }
-        else                         { off = sub2(off, ydim); p1 = sub2(p1, xdim); p2 = add2(p2, xdim); }
+        if (dot2(axis, ydim) > 0.0f) { off = add2(off, ydim); p1 = add2(p1, xdim); p2 = sub2(p2, xdim); tmark(t, base + PHXO_T_SUP_EDGE_Y_POS); }
+        else                         { off = sub2(off, ydim); p1 = sub2(p1, xdim); p2 = add2(p2, xdim); tmark(t, base + PHXO_T_SUP_EDGE_Y_NEG); }
     } else {
-        if (dot2(axis, xdim) > 0.0f) { off = add2(off, xdim); p1 = sub2(p1, ydim); p2 = add2(p2, ydim); }
-        else                         { off = sub2(off, xdim); p1 = add2(p1, ydim); p2 = sub2(p2, ydim); }
+        if (dot2(axis, xdim) > 0.0f) { off = add2(off, xdim); p1 = sub2(p1, ydim); p2 = add2(p2, ydim); tmark(t, base + PHXO_T_SUP_EDGE_X_POS); }
+        else                         { off = sub2(off, xdim); p1 = add2(p1, ydim); p2 = sub2(p2, ydim); tmark(t, base + PHXO_T_SUP_EDGE_X_NEG); }
     }
     *e1 = add2(p1, off);
     *e2 = add2(p2, off);
 }
 
 /* ref: Geom.h:66-77 */
-int phxo_support_points(const phxo_body* b, float ax, float ay, phxo_vec2 out[2])
+static int support_points(const phxo_body* b, float ax, float ay, phxo_vec2 out[2], phxo_trace* t, int base)
 {
     phxo_vec2 axis = {ax, ay};
     if (fabsf(dot2(axis, b->geom_xv)) < 0.1f || fabsf(dot2(axis, b->geom_yv)) < 0.1f) {
-        clipping_edge(b, axis, &out[0], &out[1]);
+        clipping_edge(b, axis, &out[0], &out[1], t, base);
         return 2;
     }
-    out[0] = clipping_vertex(b, axis);
+    out[0] = clipping_vertex(b, axis, t, base);
     return 1;
 }
+
+int phxo_support_points(const phxo_body* b, float ax, float ay, phxo_vec2 out[2]) { return support_points(b, ax, ay, out, NULL, 0); }
 
 /* ------------------------------------------------------------------------------------------ */
 /* persistent pair set — set semantics of DenseHashSet<pair<u32,u32>> (ref: base/DenseHash.h     */
@@ -955,7 +975,7 @@ void phxo_solver_solve_grouped_fp16(phxo_body* bodies, int nb, const phxo_contac
 /* narrowphase (ref: Collider.cpp:8-245) — the step between the two hot halves                  */
 
 /* ref: Collider.cpp:8-56 — box/box SAT, 4 axes, returns the axis of least penetration */
-static int separating_axis(const phxo_body* b1, const phxo_body* b2, phxo_vec2* axis)
+static int separating_axis(const phxo_body* b1, const phxo_body* b2, phxo_vec2* axis, phxo_trace* t)
 {
     phxo_vec2 a0[2] = {b1->xv, b1->yv}, a1[2] = {b2->xv, b2->yv};
     phxo_vec2 e0 = b1->geom_size, e1 = b2->geom_size;
@@ -964,21 +984,22 @@ static int separating_axis(const phxo_body* b1, const phxo_body* b2, phxo_vec2* 
     ad[0][0] = fabsf(dot2(a0[0], a1[0])); ad[0][1] = fabsf(dot2(a0[0], a1[1]));
     float r0 = e0.x + e1.x * ad[0][0] + e1.y * ad[0][1];
     float d0 = fabsf(dot2(a0[0], d)) - r0;
-    if (d0 > 0) return 0;
-    float best = d0; phxo_vec2 bestaxis = a0[0];
+    if (d0 > 0) { tmark(t, PHXO_T_SEP0); return 0; }
+    float best = d0; phxo_vec2 bestaxis = a0[0]; int kept = 0;
     ad[1][0] = fabsf(dot2(a0[1], a1[0])); ad[1][1] = fabsf(dot2(a0[1], a1[1]));
     float r1 = e0.y + e1.x * ad[1][0] + e1.y * ad[1][1];
     float d1 = fabsf(dot2(a0[1], d)) - r1;
-    if (d1 > 0) return 0;
-    if (d1 > best) { best = d1; bestaxis = a0[1]; }
+    if (d1 > 0) { tmark(t, PHXO_T_SEP0 + 1); return 0; }
+    if (d1 > best) { best = d1; bestaxis = a0[1]; kept = 1; }
     float r2 = e1.x + e0.x * ad[0][0] + e0.y * ad[1][0];
     float d2 = fabsf(dot2(a1[0], d)) - r2;
-    if (d2 > 0) return 0;
-    if (d2 > best) { best = d2; bestaxis = a1[0]; }
+    if (d2 > 0) { tmark(t, PHXO_T_SEP0 + 2); return 0; }
+    if (d2 > best) { best = d2; bestaxis = a1[0]; kept = 2; }
     float r3 = e1.y + e0.x * ad[0][1] + e0.y * ad[1][1];
     float d3 = fabsf(dot2(a1[1], d)) - r3;
-    if (d3 > 0) return 0;
-    if (d3 > best) { best = d3; bestaxis = a1[1]; }
+    if (d3 > 0) { tmark(t, PHXO_T_SEP0 + 3); return 0; }
+    if (d3 > best) { best = d3; bestaxis = a1[1]; kept = 3; }
+    tmark(t, PHXO_T_BEST0 + kept);
     *axis = bestaxis;
     return 1;
 }
@@ -1009,21 +1030,30 @@ void phxo_contact_point_make(phxo_contact_point* out, float p1x, float p1y, floa
 }
 
 /* ref: Collider.cpp:58-92 */
-static void add_point(phxo_contact_point* pts, int* count, phxo_contact_point* nb)
+static void add_point(phxo_contact_point* pts, int* count, phxo_contact_point* nb, phxo_trace* t)
 {
     phxo_contact_point* closest = NULL;
+    phxo_contact_point* first_equal = NULL;                           /* (trace only) */
     float bestdepth = 3.402823466e+38f;
     for (int i = 0; i < *count; ++i) {
         phxo_contact_point* col = &pts[i];
         if (cp_equals(nb, col, 2.0f)) {
             float depth = sqlen2(sub2(nb->delta1, col->delta1)) + sqlen2(sub2(nb->delta2, col->delta2));
             if (depth < bestdepth) { bestdepth = depth; closest = col; }
+            if (t) {
+                if (!first_equal) first_equal = col;
+                int far1 = sqlen2(sub2(col->delta1, nb->delta1)) > 2.0f * 2.0f, far2 = sqlen2(sub2(col->delta2, nb->delta2)) > 2.0f * 2.0f;
+                if (far1 != far2) tmark(t, PHXO_T_EQUALS_ONE_SIDED);
+            }
         }
     }
     if (closest) {
+        tmark(t, PHXO_T_MERGE_SLOT0 + (int)(closest - pts));
+        if (closest != first_equal) tmark(t, PHXO_T_MERGE_LATER_CANDIDATE);
         closest->is_merged = 1; closest->is_newly_created = 0;
         closest->normal = nb->normal; closest->delta1 = nb->delta1; closest->delta2 = nb->delta2;
     } else {
+        tmark(t, PHXO_T_APPEND_SLOT0 + *count);
         nb->is_merged = 1; nb->is_newly_created = 1;
         pts[(*count)++] = *nb;
     }
@@ -1050,75 +1080,84 @@ static int within_segment(phxo_vec2 p, phxo_vec2 a, phxo_vec2 b)
 }
 
 /* ref: Collider.cpp:94-209 */
-static void generate_contacts(const phxo_body* b1, const phxo_body* b2, phxo_contact_point* pts, int* count, phxo_vec2 axis)
+static void generate_contacts(const phxo_body* b1, const phxo_body* b2, phxo_contact_point* pts, int* count, phxo_vec2 axis, phxo_trace* t)
 {
-    if (dot2(axis, sub2(b1->pos, b2->pos)) < 0.0f) axis = neg2(axis);
+    if (dot2(axis, sub2(b1->pos, b2->pos)) < 0.0f) { axis = neg2(axis); tmark(t, PHXO_T_FLIP); }
+    else tmark(t, PHXO_T_NOFLIP);
     phxo_vec2 s1[2], s2[2];
     const float lin_tol = 2.0f;
-    int n1 = phxo_support_points(b1, -axis.x, -axis.y, s1);
-    int n2 = phxo_support_points(b2, axis.x, axis.y, s2);
-    if (n1 == 2 && sqlen2(sub2(s1[0], s1[1])) < lin_tol * lin_tol) { s1[0] = mul2(add2(s1[0], s1[1]), 0.5f); n1 = 1; }
-    if (n2 == 2 && sqlen2(sub2(s2[0], s2[1])) < lin_tol * lin_tol) { s2[0] = mul2(add2(s2[0], s2[1]), 0.5f); n2 = 1; }
+    int n1 = support_points(b1, -axis.x, -axis.y, s1, t, PHXO_T_SUP1);
+    int n2 = support_points(b2, axis.x, axis.y, s2, t, PHXO_T_SUP2);
+    if (n1 == 2 && sqlen2(sub2(s1[0], s1[1])) < lin_tol * lin_tol) { s1[0] = mul2(add2(s1[0], s1[1]), 0.5f); n1 = 1; tmark(t, PHXO_T_COLLAPSE1); }
+    if (n2 == 2 && sqlen2(sub2(s2[0], s2[1])) < lin_tol * lin_tol) { s2[0] = mul2(add2(s2[0], s2[1]), 0.5f); n2 = 1; tmark(t, PHXO_T_COLLAPSE2); }
 
     if (n1 == 1 && n2 == 1) {
         phxo_vec2 delta = sub2(s2[0], s1[0]);
         if (dot2(delta, axis) >= 0.0f) {
+            tmark(t, PHXO_T_VV_HIT);
             phxo_contact_point c = make_point(s1[0], s2[0], axis, b1, b2);
-            add_point(pts, count, &c);
-        }
+            add_point(pts, count, &c, t);
+        } else tmark(t, PHXO_T_VV_MISS);
     } else if (n1 == 1 && n2 == 2) {
         phxo_vec2 n = perp2(sub2(s2[1], s2[0]));
         phxo_vec2 p = project_to_line(s1[0], s2[0], n, axis);
         if (within_segment(p, s2[0], s2[1])) {
+            tmark(t, PHXO_T_VE_HIT);
             phxo_contact_point c = make_point(s1[0], p, axis, b1, b2);
-            add_point(pts, count, &c);
-        }
+            add_point(pts, count, &c, t);
+        } else tmark(t, PHXO_T_VE_MISS);
     } else if (n1 == 2 && n2 == 1) {
         phxo_vec2 n = perp2(sub2(s1[1], s1[0]));
         phxo_vec2 p = project_to_line(s2[0], s1[0], n, axis);
         if (within_segment(p, s1[0], s1[1])) {
+            tmark(t, PHXO_T_EV_HIT);
             phxo_contact_point c = make_point(p, s2[0], axis, b1, b2);
-            add_point(pts, count, &c);
-        }
+            add_point(pts, count, &c, t);
+        } else tmark(t, PHXO_T_EV_MISS);
     } else if (n1 == 2 && n2 == 2) {
         phxo_vec2 t1[4], t2[4]; int tc = 0;
+        int which[4];                                                 /* (trace only) candidate tc is the which[tc]-th of the four tried */
         for (int i = 0; i < 2; ++i) {
             phxo_vec2 n = perp2(sub2(s2[1], s2[0]));
             if (dot2(sub2(s1[i], s2[0]), n) >= 0.0f) {
                 phxo_vec2 p = project_to_line(s1[i], s2[0], n, axis);
-                if (within_segment(p, s2[0], s2[1])) { t1[tc] = s1[i]; t2[tc] = p; tc++; }
+                if (within_segment(p, s2[0], s2[1])) { t1[tc] = s1[i]; t2[tc] = p; which[tc] = i; tc++; }
             }
         }
         for (int i = 0; i < 2; ++i) {
             phxo_vec2 n = perp2(sub2(s1[1], s1[0]));
             if (dot2(sub2(s2[i], s1[0]), n) >= 0.0f) {
                 phxo_vec2 p = project_to_line(s2[i], s1[0], n, axis);
-                if (within_segment(p, s1[0], s1[1])) { t1[tc] = p; t2[tc] = s2[i]; tc++; }
+                if (within_segment(p, s1[0], s1[1])) { t1[tc] = p; t2[tc] = s2[i]; which[tc] = 2 + i; tc++; }
             }
         }
+        tmark(t, PHXO_T_EE_TC0 + tc);
         if (tc == 1) {
             phxo_contact_point c = make_point(t1[0], t2[0], axis, b1, b2);
-            add_point(pts, count, &c);
+            add_point(pts, count, &c, t);
         }
         if (tc >= 2) {
+            static const int pick[4][4] = {{-1, 0, 1, 2}, {-1, -1, 3, 4}, {-1, -1, -1, 5}, {-1, -1, -1, -1}};   /* 01 02 03 12 13 23 */
+            tmark(t, PHXO_T_EE_PICK01 + pick[which[0]][which[1]]);
             phxo_contact_point c1 = make_point(t1[0], t2[0], axis, b1, b2);
-            add_point(pts, count, &c1);
+            add_point(pts, count, &c1, t);
             phxo_contact_point c2 = make_point(t1[1], t2[1], axis, b1, b2);
-            add_point(pts, count, &c2);
+            add_point(pts, count, &c2, t);
         }
     }
 }
 
 /* ref: Collider.cpp:211-245.  Returns 1 if more than kMaxContactPoints merged points had to be
  * clamped (the reference would write past the manifold's slots there). */
-static int update_manifold(phxo_manifold* m, const phxo_body* bodies, phxo_contact_point* pts)
+static int update_manifold(phxo_manifold* m, const phxo_body* bodies, phxo_contact_point* pts, phxo_trace* t)
 {
     phxo_contact_point np[4];
     for (int i = 0; i < m->point_count; ++i) { np[i] = pts[i]; np[i].is_merged = 0; np[i].is_newly_created = 0; }
     int count = m->point_count;
+    const int before = m->point_count;
     const phxo_body *b1 = &bodies[m->body1], *b2 = &bodies[m->body2];
     phxo_vec2 axis;
-    if (separating_axis(b1, b2, &axis)) generate_contacts(b1, b2, np, &count, axis);
+    if (separating_axis(b1, b2, &axis, t)) generate_contacts(b1, b2, np, &count, axis, t);
     m->point_count = 0;
     int overflow = 0;
     for (int i = 0; i < count; ++i)
@@ -1126,6 +1165,11 @@ static int update_manifold(phxo_manifold* m, const phxo_body* bodies, phxo_conta
             if (m->point_count < 2) pts[m->point_count++] = np[i];
             else overflow = 1;
         }
+    if (t) {
+        tmark(t, PHXO_T_FROM0_TO0 + 3 * before + m->point_count);
+        if (before > 0 && !np[0].is_merged && m->point_count > 0) tmark(t, PHXO_T_KEEP_SHIFT);
+        if (overflow) tmark(t, PHXO_T_OVERFLOW);
+    }
     return overflow;
 }
 
@@ -1144,6 +1188,11 @@ struct phxo_world {
     uint64_t sweep_tests;
     int point_overflows;
     phxo_solve_stats stats;
+    /* branch trace of the last pre_solve (off unless phxo_world_set_trace): one record per manifold updated, in manifold order */
+    int trace_on;
+    phxo_trace_record* trace_recs; size_t n_rec, cap_rec;
+    int32_t* trace_slot; size_t cap_slot;                 /* manifold position -> its record, carried through PackManifolds' moves */
+    phxo_trace trace_or; uint32_t trace_counts[PHXO_T_COUNT];
 };
 
 phxo_world* phxo_world_create(void) { return (phxo_world*)calloc(1, sizeof(phxo_world)); }
@@ -1152,7 +1201,7 @@ void phxo_world_destroy(phxo_world* w)
 {
     if (!w) return;
     free(w->bodies); free(w->manifolds); free(w->cps); free(w->joints); free(w->set.slot);
-    free(w->sorted); free(w->entries); free(w->new_pairs); free(w);
+    free(w->sorted); free(w->entries); free(w->new_pairs); free(w->trace_recs); free(w->trace_slot); free(w);
 }
 
 int phxo_world_add_body(phxo_world* w, float px, float py, float angle, float sx, float sy) /* ref: World.cpp:11-17 */
@@ -1225,11 +1274,21 @@ static int aabb_intersects(const phxo_body* a, const phxo_body* b) /* ref: AABB2
 
 int phxo_aabb_intersects(const phxo_body* a, const phxo_body* b) { return aabb_intersects(a, b); }
 
+/* ref: Collider.cpp:387 — the manifold PackManifolds drops */
+static int manifold_dead(const phxo_manifold* m, const phxo_body* bodies, phxo_trace* t)
+{
+    if (m->point_count != 0) return 0;
+    if (!aabb_intersects(&bodies[m->body1], &bodies[m->body2])) { tmark(t, PHXO_T_DEAD); return 1; }
+    tmark(t, PHXO_T_EMPTY_ALIVE);
+    return 0;
+}
+
 static void pack_manifolds(phxo_world* w) /* ref: Collider.cpp:379-416 */
 {
     for (size_t i = 0; i < w->nm;) {
         phxo_manifold* m = &w->manifolds[i];
-        if (m->point_count == 0 && !aabb_intersects(&w->bodies[m->body1], &w->bodies[m->body2])) {
+        if (manifold_dead(m, w->bodies, w->trace_on ? &w->trace_recs[w->trace_slot[i]].trace : NULL)) {
+            if (w->trace_on) w->trace_slot[i] = w->trace_slot[w->nm - 1];
             ps_erase(&w->set, (uint32_t)m->body1, (uint32_t)m->body2);
             phxo_manifold last = w->manifolds[w->nm - 1];
             int32_t slot = m->point_index;
@@ -1280,9 +1339,28 @@ void phxo_world_pre_solve(phxo_world* w, float dt) /* ref: World.cpp:25-32 */
     GROW(w->cps, w->cap_cp, w->nm * 2 + 2, phxo_contact_point);
     for (size_t k = w->ncp; k < w->nm * 2; ++k) { memset(&w->cps[k], 0, sizeof(phxo_contact_point)); w->cps[k].solver_index = -1; }
     w->ncp = w->nm * 2;
-    for (size_t mi = 0; mi < w->nm; ++mi)
-        w->point_overflows += update_manifold(&w->manifolds[mi], w->bodies, w->cps + w->manifolds[mi].point_index);
+    if (w->trace_on) {
+        GROW(w->trace_recs, w->cap_rec, w->nm + 1, phxo_trace_record);
+        GROW(w->trace_slot, w->cap_slot, w->nm + 1, int32_t);
+        w->n_rec = w->nm;
+    }
+    for (size_t mi = 0; mi < w->nm; ++mi) {
+        phxo_trace* t = NULL;
+        if (w->trace_on) {
+            phxo_trace_record* r = &w->trace_recs[mi];
+            r->body1 = w->manifolds[mi].body1; r->body2 = w->manifolds[mi].body2; r->trace.w[0] = r->trace.w[1] = 0;
+            w->trace_slot[mi] = (int32_t)mi;
+            t = &r->trace;
+        }
+        w->point_overflows += update_manifold(&w->manifolds[mi], w->bodies, w->cps + w->manifolds[mi].point_index, t);
+    }
     pack_manifolds(w);
+    if (w->trace_on) {
+        memset(&w->trace_or, 0, sizeof w->trace_or); memset(w->trace_counts, 0, sizeof w->trace_counts);
+        for (size_t k = 0; k < w->n_rec; ++k)
+            for (int l = 0; l < PHXO_T_COUNT; ++l)
+                if (w->trace_recs[k].trace.w[l >> 6] >> (l & 63) & 1u) { w->trace_counts[l]++; w->trace_or.w[l >> 6] |= 1ull << (l & 63); }
+    }
     refresh_contact_joints(w);
 }
 
@@ -1308,6 +1386,33 @@ const uint32_t* phxo_world_new_pairs(phxo_world* w, int* np) { if (np) *np = (in
 const phxo_solve_stats* phxo_world_stats(phxo_world* w) { return &w->stats; }
 uint64_t phxo_world_sweep_tests(phxo_world* w) { return w->sweep_tests; }
 int phxo_world_point_overflows(phxo_world* w) { return w->point_overflows; }
+
+void phxo_world_set_trace(phxo_world* w, int on) { w->trace_on = on ? 1 : 0; if (!on) w->n_rec = 0; }
+const phxo_trace_record* phxo_world_trace_records(phxo_world* w, int* n) { if (n) *n = (int)w->n_rec; return w->trace_recs; }
+void phxo_world_trace_summary(phxo_world* w, uint64_t mask[2], uint32_t counts[PHXO_T_COUNT])
+{
+    if (mask) { mask[0] = w->trace_or.w[0]; mask[1] = w->trace_or.w[1]; }
+    if (counts) memcpy(counts, w->trace_counts, sizeof w->trace_counts);
+}
+
+/* UpdateManifold and PackManifolds' test on pairs given by themselves: pair k is bodies[2k], bodies[2k + 1] (their Geom copy and AABB
+ * are refreshed from the pose first, ref: RigidBody.h:38-42), its cached points pts[2k..] and counts[k]; points and counts come back
+ * updated, masks[2k..] hold the labels reached.  Returns how many pairs overflowed. */
+int phxo_trace_pairs(const phxo_body* bodies, phxo_contact_point* pts, int32_t* counts, uint64_t* masks, int npairs)
+{
+    int overflows = 0;
+    for (int k = 0; k < npairs; ++k) {
+        phxo_body two[2] = {bodies[2 * k], bodies[2 * k + 1]};
+        update_geom(&two[0]); update_geom(&two[1]);
+        phxo_manifold m = {0, 1, counts[k], 0};
+        phxo_trace t = {{0, 0}};
+        overflows += update_manifold(&m, two, pts + 2 * k, &t);
+        manifold_dead(&m, two, &t);
+        counts[k] = m.point_count;
+        masks[2 * k] = t.w[0]; masks[2 * k + 1] = t.w[1];
+    }
+    return overflows;
+}
 
 /* ------------------------------------------------------------------------------------------ */
 /* multi-threaded timing harness (cpu_baseline leg of bench.py only)                           */

@@ -201,6 +201,42 @@ const phxo_solve_stats* phxo_world_stats(phxo_world* w);
 uint64_t               phxo_world_sweep_tests(phxo_world* w);         /* candidate y-tests in the last UpdatePairs */
 int                    phxo_world_point_overflows(phxo_world* w);     /* times quirk C.4 (>2 merged points) was clamped */
 
+/* ---- narrowphase branch trace ----
+ * Which arms of separating_axis / support points / generate_contacts / add_point / update_manifold / PackManifolds' test one
+ * UpdateManifold took, as a bit set of the labels below (68 of them: two 64-bit words).  The traced code is the code the oracle world
+ * runs, with a NULL trace; marking a label changes nothing that is computed.  Labels are in the oracle's terms: body 1 / body 2 of
+ * the manifold, candidates of the edge-edge case numbered in the order they are tried (s1[0], s1[1], s2[0], s2[1]). */
+typedef struct { uint64_t w[2]; } phxo_trace;
+typedef struct { int32_t body1, body2; phxo_trace trace; } phxo_trace_record;          /* 24 bytes */
+enum {
+    PHXO_T_SEP0 = 0,              /* +k: axis k (b1.x, b1.y, b2.x, b2.y) is the first found separating */
+    PHXO_T_BEST0 = 4,             /* +k: axis k is the one kept */
+    PHXO_T_FLIP = 8, PHXO_T_NOFLIP = 9,
+    PHXO_T_SUP1 = 10, PHXO_T_SUP2 = 18,   /* bases of the eight support-point labels of body 1 / body 2, offsets: */
+    PHXO_T_SUP_EDGE_Y_POS = 0, PHXO_T_SUP_EDGE_Y_NEG = 1,    /* |xdiff| < |ydiff|, dot(axis, ydim) > 0 or not */
+    PHXO_T_SUP_EDGE_X_POS = 2, PHXO_T_SUP_EDGE_X_NEG = 3,    /* otherwise,         dot(axis, xdim) > 0 or not */
+    PHXO_T_SUP_VERTEX_PP = 4,     /* +2 if the x sign is -1, +1 if the y sign is -1: pp, pn, np, nn */
+    PHXO_T_COLLAPSE1 = 26, PHXO_T_COLLAPSE2 = 27,
+    PHXO_T_VV_HIT = 28, PHXO_T_VV_MISS = 29, PHXO_T_VE_HIT = 30, PHXO_T_VE_MISS = 31, PHXO_T_EV_HIT = 32, PHXO_T_EV_MISS = 33,
+    PHXO_T_EE_TC0 = 34,           /* +tc, 0..4 */
+    PHXO_T_EE_PICK01 = 39,        /* 01, 02, 03, 12, 13, 23: the two candidates merged when tc >= 2 */
+    PHXO_T_APPEND_SLOT0 = 45, PHXO_T_MERGE_SLOT0 = 49,       /* +slot, 0..3 */
+    PHXO_T_MERGE_LATER_CANDIDATE = 53, PHXO_T_EQUALS_ONE_SIDED = 54,
+    PHXO_T_FROM0_TO0 = 55,        /* + 3 * (count before) + (count after) */
+    PHXO_T_KEEP_SHIFT = 64, PHXO_T_OVERFLOW = 65, PHXO_T_DEAD = 66, PHXO_T_EMPTY_ALIVE = 67,
+    PHXO_T_COUNT = 68
+};
+int         phxo_trace_label_count(void);
+const char* phxo_trace_label(int label);
+/* per pair: see the definition */
+int phxo_trace_pairs(const phxo_body* bodies /*2n*/, phxo_contact_point* pts /*2n, in/out*/, int32_t* counts /*n, in/out*/,
+                     uint64_t* masks /*2n, out*/, int npairs);
+/* per world: off by default; when on, every pre_solve leaves one record per manifold it updated (those PackManifolds then dropped
+ * included), their OR and how many records reached each label */
+void phxo_world_set_trace(phxo_world* w, int on);
+const phxo_trace_record* phxo_world_trace_records(phxo_world* w, int* n);
+void phxo_world_trace_summary(phxo_world* w, uint64_t mask[2], uint32_t counts[PHXO_T_COUNT]);
+
 /* multi-threaded timing harness for bench.py's cpu_baseline leg: Single-Sloppy-style 512-joint
  * batches over `threads` pthreads (races on shared bodies exactly like the reference's sloppy
  * modes; results are NOT used for parity). Returns seconds spent in the impulse loop. */

@@ -100,6 +100,30 @@ void reff_world_pin_body(void* p, int index)
     if (index >= 0 && index < (int)h->world.bodies.size) h->world.bodies[index].invMass = 0.f;
 }
 
+// move a body between steps the way the demo's code would: coords, then UpdateGeom (ref: RigidBody.h:38-42).
+// frame6 = {pos.x, pos.y, xVector.x, xVector.y, yVector.x, yVector.y}
+void reff_world_set_pose(void* p, int index, const float* frame6)
+{
+    FpEnv fp;
+    Harness* h = static_cast<Harness*>(p);
+    if (index < 0 || index >= (int)h->world.bodies.size) return;
+    RigidBody& b = h->world.bodies[index];
+    b.coords.pos = Vector2f(frame6[0], frame6[1]);
+    b.coords.xVector = Vector2f(frame6[2], frame6[3]);
+    b.coords.yVector = Vector2f(frame6[4], frame6[5]);
+    b.UpdateGeom();
+}
+
+// v3 = {velocity.x, velocity.y, angularVelocity}
+void reff_world_set_velocity(void* p, int index, const float* v3)
+{
+    Harness* h = static_cast<Harness*>(p);
+    if (index < 0 || index >= (int)h->world.bodies.size) return;
+    RigidBody& b = h->world.bodies[index];
+    b.velocity = Vector2f(v3[0], v3[1]);
+    b.angularVelocity = v3[2];
+}
+
 // the whole step (ref: World.cpp:19-37), through World::Update itself (0 workers: the serial pair path)
 void reff_world_update(void* p, float dt, int solve_mode, int island_mode, int contact_iters, int penetration_iters)
 {

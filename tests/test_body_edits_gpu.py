@@ -11,7 +11,7 @@ import pytest
 import phyx_amd
 from phyx_amd import Configuration, scenes
 from phyx_amd.api import frame_from_angle
-from helpers import oracle_world
+from helpers import oracle_world, oracle_set_pose as _oracle_set_pose, oracle_set_velocity as _oracle_set_velocity
 
 pytestmark = pytest.mark.gpu
 
@@ -64,19 +64,6 @@ def _oracle_add_accel(ow, i, a):
     b["acceleration"]["x"][i] += a[0]
     b["acceleration"]["y"][i] += a[1]
     b["angular_acceleration"][i] += a[2]
-
-
-def _oracle_set_velocity(ow, i, v):
-    b = ow.bodies()
-    b["velocity"]["x"][i], b["velocity"]["y"][i], b["angular_velocity"][i] = v[0], v[1], v[2]
-
-
-def _oracle_set_pose(oracle, ow, i, p):
-    """coords = ..., then UpdateGeom: the geom copy and the oracle's own RecomputeAABB (ref: RigidBody.h:38-42, Geom.h:79-85)."""
-    b = ow.bodies()
-    b["pos"]["x"][i], b["pos"]["y"][i], b["xv"]["x"][i], b["xv"]["y"][i], b["yv"]["x"][i], b["yv"]["y"][i] = p
-    b["geom_pos"][i], b["geom_xv"][i], b["geom_yv"][i] = b["pos"][i], b["xv"][i], b["yv"][i]
-    oracle.lib().phxo_recompute_aabb(C.c_void_p(b.ctypes.data + i * b.dtype.itemsize))
 
 
 def _oracle_frame(oracle, px, py, angle):

@@ -98,6 +98,17 @@ def test_differential_fuzz_random_worlds(built_lib):
     assert r.returncode == 0 and "0 diverged" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_differential_fuzz_tiny_boxes(built_lib):
+    """tools/fuzz.py --tiny: the same random worlds with half-extents from 0.2 to 3, where edges collapse to points and contact
+    points lie closer than ContactPoint::Equals' 2.0 (DESIGN.md §6).  8 seeds."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "fuzz.py"), "70000", "8", "--tiny"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "0 diverged" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
 class _LocalRanks:
     """k sharded Worlds on ONE GPU: the all-gather of the island-sharded exchange emulated with device-to-device copies
     (every rank's segment into every rank's recv buffer at offset rank * segment_bytes) — what RCCL does on a node."""

@@ -1,5 +1,6 @@
 """Differential fuzz: random worlds (random sizes, angles, overlaps, several static boxes) stepped in lockstep on the device
-and in the oracle; every byte of bodies / manifolds / joints compared after every step.   usage: fuzz.py [first_seed [count]] [--big]"""
+and in the oracle; every byte of bodies / manifolds / joints compared after every step.   usage: fuzz.py [first_seed [count]] [--big] [--tiny]
+--tiny draws half-extents from 0.2 to 3 (edges under ContactPoint::Equals' and the edge collapse's 2.0); the default draw is as it was."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,6 +11,8 @@ from phyx_amd import _lib as _phx_lib
 ob.set_arith(_phx_lib.load().phx_arith_mode())      # the oracle sweeps in the library's arithmetic form
 
 
+TINY = "--tiny" in sys.argv      # half-extents 0.2 .. 3: collapsed edges, vertex-vertex contacts, points closer than 2
+EXTENT = (0.2, 3.0) if TINY else (1.5, 12.0)
 BIG = "--big" in sys.argv        # thousands of bodies: many bins, 1024-lane groups, an HBM group once piles form
 
 
@@ -22,7 +25,7 @@ def scene(rng):
         sx.append(float(rng.uniform(5, 60))); sy.append(float(rng.uniform(2, 10))); st.append(True)
     for _ in range(n):
         px.append(float(rng.uniform(-width, width))); py.append(float(rng.uniform(12, 400))); ang.append(float(rng.uniform(-3.2, 3.2)) if rng.random() < 0.7 else 0.0)
-        sx.append(float(rng.uniform(1.5, 12))); sy.append(float(rng.uniform(1.5, 12))); st.append(False)
+        sx.append(float(rng.uniform(*EXTENT))); sy.append(float(rng.uniform(*EXTENT))); st.append(False)
     f = lambda a: np.asarray(a, dtype=np.float32)
     return {"px": f(px), "py": f(py), "angle": f(ang), "sx": f(sx), "sy": f(sy), "static": np.asarray(st, dtype=bool)}
 
