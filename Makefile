@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example clean
+.PHONY: build test test-gpu bench smoke example place clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -19,6 +19,9 @@ bench: build
 example: build              ## the C ABI from plain C
 	gcc -std=c11 -O2 -Wall -Iinclude examples/drop_in.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -o examples/drop_in
 
+place: build                ## the emitter that looks first (phx_world_query_boxes, phx_world_cast_boxes)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/place.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/place
+
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place
 	rm -rf oracle/_ref

@@ -539,7 +539,8 @@ typedef struct { float friction, restitution; } phx_material;      /* 8 B; defau
 int  phx_world_set_materials(phx_world* w, const int32_t* bodies, const phx_material* materials, int32_t count);
 /* every body's material, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
 int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
-/* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first.  Batched, answered on the device
+/* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first, whether a spot is free for a box
+ * and how far a box can move before it touches something.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
  * its AABB {aabb_min, aabb_max} and its box {pos, xvector = xv, yvector = yv, geom_size = h (half extents)} (UpdateGeom copies the
  * first three into geom_pos / geom_xvector / geom_yvector, ref: RigidBody.h:38-42).  Every
@@ -562,6 +563,28 @@ int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
  *                yv), negated when d' on that axis is > 0: always an exact copy or negation of stored floats;
  *       point  = (ox + t*dx, oy + t*dy).
  *     The closest hit is the smallest t, ties to the lowest body index.
+ *   - Oriented box {P, X, Y, H} (a position, two frame vectors and half extents, spelled out as in phx_world_set_poses so that nothing is
+ *     rounded on the way in; tests/shape_query_spec.py states what follows as the same expressions).  Its extents are
+ *       ex = |X.x|*H.x + |Y.x|*H.y,   ey = |X.y|*H.x + |Y.y|*H.y.
+ *     Against body b there are four axes, in this order: A0 = X, A1 = Y, A2 = xv, A3 = yv.  With c = P - pos (per component), each
+ *     axis A gives, by the same expression for all four (the box's own axes are not special-cased):
+ *       s  = c.x*A.x + c.y*A.y
+ *       rq = |X.x*A.x + X.y*A.y|*H.x + |Y.x*A.x + Y.y*A.y|*H.y
+ *       rb = |xv.x*A.x + xv.y*A.y|*h.x + |yv.x*A.x + yv.y*A.y|*h.y
+ *       R  = rq + rb.
+ *     The box overlaps b (closed) iff  a.min.x - ex <= P.x && a.max.x + ex >= P.x && a.min.y - ey <= P.y && a.max.y + ey >= P.y  AND
+ *     |s| <= R on all four axes.  (Float subtraction and addition are monotone, so a tree node's widened bounds contain its bodies'
+ *     widened AABBs: with the AABB conjunct, pruning can never change a result.)  A NaN AABB overlaps nothing.
+ *   - Box cast {box, d, max_t}: the box moves as P + t*d for t in [0, max_t].  Per axis, v = d.x*A.x + d.y*A.y and the one-axis slab of
+ *     the ray rule is taken with o = s, d = v, lo = -R, hi = R (its d == 0 rule included: no division by zero).  tin is the largest t0
+ *     of the four axes and the entering axis the FIRST in order that attains it; tout is the smallest t1.
+ *     Body b is a candidate iff its AABB has min <= max on both axes and the ray's two-axis test passes with origin P, direction d,
+ *     lo = a.min - (ex, ey), hi = a.max + (ex, ey).  The cast hits b iff b is a candidate, every axis's slab is non-empty and
+ *     tin <= tout && tout >= 0 && tin <= max_t.  Then
+ *       t      = (tin > 0 ? tin : 0)   (never -0);
+ *       normal = (0, 0) if tin < 0 (the boxes overlap at the start); otherwise the entering axis's stored vector (an exact copy of X,
+ *                Y, xv or yv), negated when v on that axis is > 0: it points against the motion.
+ *     The closest hit is the smallest t, ties to the lowest body index.
  * flags: PHX_QUERY_SKIP_STATIC leaves static bodies (inv_mass == 0 && inv_inertia == 0) out of every result (picking without the ground).
  * Rules:
  *   - Any time, like the gathers: a query sees the geometry at its point of phx_world_stream(w) (between phx_world_pre_solve and
@@ -569,8 +592,10 @@ int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
  *   - Host-staged bodies (before the first step, after add_body / set_body_static / set_body_inverse_mass) are uploaded first, as the
  *     removal uploads them.
  *   - The host forms check all their input before anything is queued: count >= 0, no NULL array when count > 0, every value finite,
- *     min <= max for boxes, max_t >= 0 and d != (0, 0) for rays, flags in {0, PHX_QUERY_SKIP_STATIC}; PHX_ERR_INVALID otherwise.
- *   - The device forms cannot check values: a query with a non-finite component, a ray with max_t < 0 or d == (0, 0) matches nothing.
+ *     min <= max for boxes, max_t >= 0 and d != (0, 0) for rays and casts, H > 0 on both axes for oriented boxes, flags in
+ *     {0, PHX_QUERY_SKIP_STATIC}; PHX_ERR_INVALID otherwise.
+ *   - The device forms cannot check values: a query with a non-finite component, a ray or cast with max_t < 0 or d == (0, 0), an oriented
+ *     box with H.x <= 0 or H.y <= 0 matches nothing.
  *   - An empty world and count == 0 are valid.
  *   - Sharded worlds (replica or slab) answer from their own world, in its local indices; there is no query across ranks.
  *   - A query changes nothing: not the records, the cached solver schedule, the broadphase's state or the next step's result.
@@ -592,6 +617,14 @@ int  phx_world_raycast(phx_world* w, const float* rays, int32_t count, int32_t f
 /* the same two on caller-owned device memory (4-byte aligned), queued on phx_world_stream(w): no host wait, nothing over PCIe */
 int  phx_world_query_points_device(phx_world* w, const void* d_points, int32_t count, int32_t flags, void* d_body);
 int  phx_world_raycast_device(phx_world* w, const void* d_rays, int32_t count, int32_t flags, void* d_out);
+/* boxes: 8 floats per query {pos.x, pos.y, xv.x, xv.y, yv.x, yv.y, h.x, h.y}; the bodies whose box overlaps the query box (closed).
+ * Output as phx_world_query_aabb (offsets, ascending hits, *total, PHX_ERR_CAPACITY); no device form: the output size depends on the data. */
+int  phx_world_query_boxes(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total);
+/* casts: 11 floats per query {box[8], dx, dy, max_t}; out[q] = the first body the box touches moving pos + t*d, t in [0, max_t] */
+typedef struct { int32_t body; float t; phx_vec2 normal; } phx_shape_hit;      /* 16 B; no hit: body -1, every other field 0 */
+int  phx_world_cast_boxes(phx_world* w, const float* casts, int32_t count, int32_t flags, phx_shape_hit* out);
+/* the same on caller-owned device memory (4-byte aligned), queued on phx_world_stream(w) */
+int  phx_world_cast_boxes_device(phx_world* w, const void* d_casts, int32_t count, int32_t flags, void* d_out);
 /* CONTACTS — what touches what, and how hard.  Answered on the device from the resident contact cache; nothing of the world crosses
  * PCIe but the answers.  Write s for the state the four getters would return at the call: bodies, manifolds, contact points (cps) and
  * joints.  A manifold m's live slots are k in [0, m.point_count); slot k is contact point cps[m.point_index + k].

@@ -40,6 +40,8 @@ sort_entry_dtype = np.dtype([("value", "<u4"), ("index", "<u4")])
 assert rigid_body_dtype.itemsize == 128 and contact_point_dtype.itemsize == 32
 ray_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,)), ("point", "<f4", (2,))])      # phx_ray_hit
 assert ray_hit_dtype.itemsize == 24
+shape_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,))])      # phx_shape_hit
+assert shape_hit_dtype.itemsize == 16
 contact_dtype = np.dtype([("other", "<i4"), ("manifold", "<i4"), ("slot", "<i4"), ("flags", "<i4"), ("point", "<f4", (2,)), ("normal", "<f4", (2,)),
                           ("normal_impulse", "<f4"), ("friction_impulse", "<f4")])                                     # phx_contact
 collision_filter_dtype = np.dtype([("category", "<u4"), ("mask", "<u4"), ("group", "<i4")])      # phx_collision_filter
@@ -66,6 +68,12 @@ def frame_from_angle(px, py, angle):
     a = np.float32(angle)
     quarter = np.float32(a + np.float32(np.float32(3.141592) / np.float32(2.0)))
     return np.array([px, py, math.cos(float(a)), math.sin(float(a)), math.cos(float(quarter)), math.sin(float(quarter))], dtype=np.float32)
+
+
+def box_from_angle(px, py, angle, hx, hy):
+    """The query box {pos.x, pos.y, xv.x, xv.y, yv.x, yv.y, h.x, h.y} of World.query_boxes / cast_boxes, with the frame add_body builds
+    for `angle` (frame_from_angle)."""
+    return np.concatenate([frame_from_angle(px, py, angle), np.array([hx, hy], dtype=np.float32)])
 
 
 def pinned_inv_inertia(sx, sy):
@@ -894,13 +902,16 @@ class World:
         b = self._queries(boxes, 4, "query_aabb", "{min.x, min.y, max.x, max.y}")
         if ((b[:, 0] > b[:, 2]) | (b[:, 1] > b[:, 3])).any():
             raise ValueError("query_aabb: every box must have min <= max")
+        return self._overlaps(self.L.phx_world_query_aabb, b, skip_static)
+
+    def _overlaps(self, fn, b, skip_static):
         flags = 1 if skip_static else 0
         offsets = np.zeros(len(b) + 1, dtype=np.int32)
         total = C.c_int64(0)
         cap = max(1024, 4 * len(b))
         for _ in range(2):                                         # (the second call with the size the first one reported)
             hits = np.zeros(cap, dtype=np.int32)
-            st = self.L.phx_world_query_aabb(self.h, _ptr(b), len(b), flags, _ptr(offsets), _ptr(hits), cap, C.byref(total))
+            st = fn(self.h, _ptr(b), len(b), flags, _ptr(offsets), _ptr(hits), cap, C.byref(total))
             if st != -4 or total.value > np.iinfo(np.int32).max:
                 break
             cap = int(total.value)
@@ -932,6 +943,37 @@ class World:
     def raycast_device(self, rays_ptr, count, out_ptr, skip_static=False):
         """raycast on device memory (5 floats per ray in, a 24-byte ray_hit_dtype record per ray out), queued on the world's stream."""
         check(self.L.phx_world_raycast_device(self.h, _dev_ptr(rays_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
+
+    def query_boxes(self, boxes, skip_static=False):
+        """Bodies whose box overlaps each oriented query box (closed); boxes (K, 8) {pos.x, pos.y, xv.x, xv.y, yv.x, yv.y, h.x, h.y}
+        (box_from_angle builds one).  Returns (offsets, hits) as query_aabb."""
+        b = self._queries(boxes, 8, "query_boxes", "{pos.x, pos.y, xv.x, xv.y, yv.x, yv.y, h.x, h.y}")
+        if (b[:, 6:8] <= 0).any():
+            raise ValueError("query_boxes: half extents must be positive")
+        return self._overlaps(self.L.phx_world_query_boxes, b, skip_static)
+
+    @staticmethod
+    def _casts(casts, what):
+        c = World._queries(casts, 11, what, "{box[8], dx, dy, max_t}")
+        if (c[:, 6:8] <= 0).any():
+            raise ValueError("%s: half extents must be positive" % what)
+        if (c[:, 10] < 0).any():
+            raise ValueError("%s: max_t must be >= 0" % what)
+        if ((c[:, 8] == 0) & (c[:, 9] == 0)).any():
+            raise ValueError("%s: a cast's direction must not be zero" % what)
+        return c
+
+    def cast_boxes(self, casts, skip_static=False):
+        """The first body each box touches moving pos + t * d, t in [0, max_t]; casts (K, 11) {box[8], dx, dy, max_t}: a shape_hit_dtype
+        array (body -1 and zeros: no hit)."""
+        c = self._casts(casts, "cast_boxes")
+        out = np.zeros(len(c), dtype=shape_hit_dtype)
+        check(self.L.phx_world_cast_boxes(self.h, _ptr(c), len(c), 1 if skip_static else 0, _ptr(out)))
+        return out
+
+    def cast_boxes_device(self, casts_ptr, count, out_ptr, skip_static=False):
+        """cast_boxes on device memory (11 floats per cast in, a 16-byte shape_hit_dtype record per cast out), queued on the world's stream."""
+        check(self.L.phx_world_cast_boxes_device(self.h, _dev_ptr(casts_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
 
     def query_index(self):
         """Queue the build of the query index unless it is current; returns how many times this world has built it."""

@@ -14,11 +14,13 @@ namespace phx {
 class DeviceQuery {
 public:
     enum Path { AUTO = 0, SCAN = 1, INDEX = 2 };
-    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2 };
+    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2, QUERY_SHAPES = 3, QUERY_CASTS = 4 };      // (BOXES: AABBs; SHAPES: oriented boxes)
     // the scan path answers batches up to this many queries of each kind, the index larger ones: the largest batch size at which
     // tools/query_cost.py measured the scan faster at cfg 2, each call after a step so that the index pays its build (INTEGRATION.md
     // §4b: points 2048 scan / 4096 index, rays 512 / 1024, boxes 1024 / 2048; sizes between two measured ones are not measured)
-    static constexpr int SCAN_MAX[3] = {2048, 512, 1024};
+    // Oriented boxes and box casts take the thresholds of the AABB queries and the rays: they share their data path, and their own
+    // crossover was not measured.
+    static constexpr int SCAN_MAX[5] = {2048, 512, 1024, 1024, 512};
 
     // PHX_QUERY_PATH=scan|index forces a path; PHX_QUERY_SCAN_CHUNK=q (a multiple of 64) lowers the queries per chunk of the scan path's
     // AABB table.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
@@ -31,16 +33,28 @@ public:
     // host outputs (offsets: count + 1); waits through `rb`.  PHX_ERR_CAPACITY as phx_world_query_aabb.
     int aabb(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
              int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
+    // oriented boxes (8 floats per query) and box casts (11): as aabb and rays
+    int shapes(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
+               int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
+    int casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s);
     // the index alone (tools/query_cost.py times it): built unless it is current
     int ensure_index(const WorldBodies& w, int n, unsigned long long epoch, hipStream_t s);
     int index_builds() const { return builds_; }
 
 private:
+    // OBB: oriented boxes instead of AABBs
+    template <bool OBB>
+    int overlaps(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
+                 int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
+    template <bool OBB>
     int scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                   int64_t* total, Readback& rb, hipStream_t s);
+    template <bool OBB>
     int index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                    int64_t* total, Readback& rb, hipStream_t s);
-    int offsets_from_counts(int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits);
+    template <bool CAST, class Hit>
+    int closest(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, Hit* d_out, hipStream_t s);
+    int offsets_from_counts(const char* what, int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits);
 
     Path forced_ = AUTO;
     int scan_chunk_ = INT32_MAX;

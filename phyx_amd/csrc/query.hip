@@ -9,6 +9,7 @@
 #include <cstring>
 
 static_assert(sizeof(phx_ray_hit) == 24, "phx_ray_hit is 24 bytes (include/phyx_amd.h)");
+static_assert(sizeof(phx_shape_hit) == 16, "phx_shape_hit is 16 bytes (include/phyx_amd.h)");
 
 namespace phx {
 
@@ -103,29 +104,41 @@ int DeviceQuery::points(const WorldBodies& w, int n, unsigned long long epoch, c
     return PHX_OK;
 }
 
-int DeviceQuery::rays(const WorldBodies& w, int n, unsigned long long epoch, const float* d_rays, int count, int flags, phx_ray_hit* d_out, hipStream_t s)
+template <bool CAST, class Hit>
+int DeviceQuery::closest(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, Hit* d_out, hipStream_t s)
 {
     if (count <= 0) return PHX_OK;
     PHX_TRY(ray_keys_.reserve((size_t)count));
-    if (n == 0 || choose(QUERY_RAYS, count) == SCAN) {
+    if (n == 0 || choose(CAST ? QUERY_CASTS : QUERY_RAYS, count) == SCAN) {
         hipLaunchKernelGGL(k_qfill_u64, dim3(qgrid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
         if (n)
             for (int q0 = 0; q0 < count; q0 += Q_MAX_TILES * Q_TILE)
-                hipLaunchKernelGGL(k_qscan_rays, dim3(qgrid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)), dim3(256), 0, s, w, n, d_rays, count, q0, flags, ray_keys_.p);
+                hipLaunchKernelGGL((k_qscan_rays<CAST>), dim3(qgrid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)), dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p);
     } else {
         PHX_TRY(ensure_index(w, n, epoch, s));
         const QTree t = make_tree(nodes_.p, perm_, n, levels_, level_off_, level_cnt_);
-        hipLaunchKernelGGL((k_qtree<QK_RAY>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_rays, count, flags, (unsigned*)nullptr, ray_keys_.p,
+        hipLaunchKernelGGL((k_qtree<CAST ? QK_CAST : QK_RAY>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
                            (const unsigned*)nullptr, (int*)nullptr);
     }
-    hipLaunchKernelGGL(k_qray_finish, dim3(qgrid(count)), dim3(256), 0, s, w, d_rays, count, (const unsigned long long*)ray_keys_.p, d_out);
+    if constexpr (CAST) hipLaunchKernelGGL(k_qcast_finish, dim3(qgrid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    else hipLaunchKernelGGL(k_qray_finish, dim3(qgrid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
 
-// ---- AABB queries -------------------------------------------------------------------------------------------------------------------
+int DeviceQuery::rays(const WorldBodies& w, int n, unsigned long long epoch, const float* d_rays, int count, int flags, phx_ray_hit* d_out, hipStream_t s)
+{
+    return closest<false>(w, n, epoch, d_rays, count, flags, d_out, s);
+}
+
+int DeviceQuery::casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s)
+{
+    return closest<true>(w, n, epoch, d_casts, count, flags, d_out, s);
+}
+
+// ---- AABB and oriented-box queries ----------------------------------------------------------------------------------------------------
 // offsets[] and *total from the per-query counts read back into counts_; *fits: the total fits hit_cap (and so int32)
-int DeviceQuery::offsets_from_counts(int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits)
+int DeviceQuery::offsets_from_counts(const char* what, int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits)
 {
     long long run = 0;
     offsets[0] = 0;
@@ -135,23 +148,37 @@ int DeviceQuery::offsets_from_counts(int count, int32_t* offsets, int hit_cap, i
     }
     *total = run;
     *fits = run <= (long long)hit_cap;
-    if (!*fits) set_error("phx_world_query_aabb: %lld hits, room for %d", run, hit_cap);
+    if (!*fits) set_error("%s: %lld hits, room for %d", what, run, hit_cap);
     return PHX_OK;
 }
 
-int DeviceQuery::aabb(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
-                      int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
+template <bool OBB>
+int DeviceQuery::overlaps(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
+                          int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
 {
     if (count <= 0 || n == 0) {
         for (int q = 0; q <= std::max(count, 0); ++q) offsets[q] = 0;
         *total = 0;
         return PHX_OK;
     }
-    if (choose(QUERY_BOXES, count) == SCAN) return scan_aabb(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    if (choose(OBB ? QUERY_SHAPES : QUERY_BOXES, count) == SCAN) return scan_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
     PHX_TRY(ensure_index(w, n, epoch, s));
-    return index_aabb(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return index_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
 
+int DeviceQuery::aabb(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
+                      int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
+{
+    return overlaps<false>(w, n, epoch, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+}
+
+int DeviceQuery::shapes(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
+                        int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
+{
+    return overlaps<true>(w, n, epoch, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+}
+
+template <bool OBB>
 int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                            int64_t* total, Readback& rb, hipStream_t s)
 {
@@ -164,23 +191,23 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
     PHX_HIP(hipMemsetAsync(qcount_.p, 0, (size_t)count * sizeof(unsigned), s));
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0);
-        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, qcount_.p, 0u, (int*)nullptr);
+        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, OBB>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, qcount_.p, 0u, (int*)nullptr);
     }
     PHX_HIP(hipGetLastError());
     counts_.resize((size_t)count);
     PHX_TRY(rb.add(counts_.data(), qcount_.p, (size_t)count * sizeof(unsigned), s));
     PHX_TRY(rb.wait(s));
     bool fits = false;
-    PHX_TRY(offsets_from_counts(count, offsets, hit_cap, total, &fits));
+    PHX_TRY(offsets_from_counts(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", count, offsets, hit_cap, total, &fits));
     if (!fits) return PHX_ERR_CAPACITY;
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0), tiles = div_up(nq, Q_TILE);
         if (count > chunk)                                                  // (the table holds the last chunk's counts: count this one again)
-            hipLaunchKernelGGL((k_qscan_aabb<QS_RECOUNT>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr, 0u, (int*)nullptr);
+            hipLaunchKernelGGL((k_qscan_aabb<QS_RECOUNT, OBB>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr, 0u, (int*)nullptr);
         PHX_TRY(device_exclusive_scan(table_.p, nq * bblocks, nullptr, scan_, s));
-        hipLaunchKernelGGL((k_qscan_aabb<QS_FILL>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr,
+        hipLaunchKernelGGL((k_qscan_aabb<QS_FILL, OBB>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr,
                            (unsigned)offsets[q0], hits_.p);
     }
     PHX_HIP(hipGetLastError());
@@ -188,25 +215,26 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
     return rb.wait(s);
 }
 
+template <bool OBB>
 int DeviceQuery::index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                             int64_t* total, Readback& rb, hipStream_t s)
 {
     const QTree t = make_tree(nodes_.p, perm_, n, levels_, level_off_, level_cnt_);
     PHX_TRY(qcount_.reserve((size_t)count)); PHX_TRY(qseg_.reserve((size_t)count));
-    hipLaunchKernelGGL((k_qtree<QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, qcount_.p, (unsigned long long*)nullptr,
+    hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_COUNT : QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, qcount_.p, (unsigned long long*)nullptr,
                        (const unsigned*)nullptr, (int*)nullptr);
     PHX_HIP(hipGetLastError());
     counts_.resize((size_t)count);
     PHX_TRY(rb.add(counts_.data(), qcount_.p, (size_t)count * sizeof(unsigned), s));
     PHX_TRY(rb.wait(s));
     bool fits = false;
-    PHX_TRY(offsets_from_counts(count, offsets, hit_cap, total, &fits));
+    PHX_TRY(offsets_from_counts(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", count, offsets, hit_cap, total, &fits));
     if (!fits) return PHX_ERR_CAPACITY;
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
     PHX_HIP(hipMemcpyAsync(qseg_.p, qcount_.p, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
     PHX_TRY(device_exclusive_scan(qseg_.p, count, nullptr, scan_, s));
-    hipLaunchKernelGGL((k_qtree<QK_AABB_FILL>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
+    hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_FILL : QK_AABB_FILL>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
                        (const unsigned*)qseg_.p, hits_.p);
     // ascending order: short segments in LDS, long ones by the radix sort (31-bit keys: the body indices)
     hipLaunchKernelGGL(k_qsort_segments, dim3(qsort_grid(count)), dim3(256), 0, s, (const unsigned*)qseg_.p, (const unsigned*)qcount_.p, count, hits_.p);

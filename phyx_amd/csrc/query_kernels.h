@@ -1,10 +1,12 @@
-// query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box and the
-// closest ray hit over the resident arrays (body_view.h).  The predicates below are the header's formulas one for one, each operation
-// rounded on its own (the library is compiled with -ffp-contract=off); tests/query_spec.py states them again in numpy.
+// query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box, the closest
+// ray hit, oriented-box overlap and the closest box-cast hit over the resident arrays (body_view.h).  The predicates below are the
+// header's formulas one for one, each operation rounded on its own (the library is compiled with -ffp-contract=off);
+// tests/query_spec.py and tests/shape_query_spec.py state them again in numpy.
 //
 // Two paths give byte-identical results:
 //   scan   bodies in lanes, a tile of Q_TILE queries in LDS, one coalesced pass over the resident arrays per tile; points and rays
-//          reduce with atomicMin (the body index; (bits(t) << 32) | body), AABB queries count per (query, workgroup), scan, fill;
+//          and casts reduce with atomicMin (the body index; (bits(t) << 32) | body), AABB and box queries count per (query,
+//          workgroup), scan, fill;
 //   index  a tree of 64-wide nodes over the bodies in Morton order (leaves: 64 consecutive sorted bodies), one wave per query: the
 //          64 lanes test one node's 64 children and __ballot picks the ones to descend into; the stack lives in LDS.
 // Pruning is exact: a node's bounds are the exact min / max of what it holds, and every test is monotonic in the box it is made
@@ -24,6 +26,8 @@ constexpr int Q_SORT_MAX = 4096;        // AABB segments up to this long are sor
 constexpr int Q_SKIP_STATIC = 1;        // PHX_QUERY_SKIP_STATIC
 
 struct QRay { float ox, oy, dx, dy, max_t; };
+struct QBox { float px, py, xx, xy, yx, yy, hx, hy; };      // a query box {pos, xv, yv, h}
+struct QCast { QBox b; float dx, dy, max_t; };
 
 // the tree: level 0 is the sorted bodies (perm), level L >= 1 holds cnt[L] nodes at nodes[off[L] ..]; node i of level L bounds
 // children 64i .. 64i + 63 of level L - 1; the root is the one node of level `levels`
@@ -89,6 +93,76 @@ __device__ __forceinline__ bool q_ray_box(const QRay& r, float4 m, float4 f, flo
     return q_ray_test(oxp, oyp, out.dxp, out.dyp, -h.x, -h.y, h.x, h.y, r.max_t, out.tin, out.xenter);
 }
 
+// ---- the shape predicates (include/phyx_amd.h: oriented boxes and box casts) -------------------------------------------------------------
+__device__ __forceinline__ float2 q_box_extents(const QBox& q)
+{
+    return make_float2(fabsf(q.xx) * q.hx + fabsf(q.yx) * q.hy, fabsf(q.xy) * q.hx + fabsf(q.yy) * q.hy);
+}
+
+// axis k of the four, in the header's order: X, Y, xv, yv
+__device__ __forceinline__ float2 q_box_axis_of(const QBox& q, float4 f, int k)
+{
+    return k == 0 ? make_float2(q.xx, q.xy) : k == 1 ? make_float2(q.yx, q.yy) : k == 2 ? make_float2(f.x, f.y) : make_float2(f.z, f.w);
+}
+
+// one axis A, the same expression for all four: s = the centres' distance along A, R = the two boxes' radii along A
+__device__ __forceinline__ void q_box_axis(const QBox& q, float cx, float cy, float4 f, float2 h, float2 A, float& s, float& R)
+{
+    s = cx * A.x + cy * A.y;
+    const float rq = fabsf(q.xx * A.x + q.xy * A.y) * q.hx + fabsf(q.yx * A.x + q.yy * A.y) * q.hy;
+    const float rb = fabsf(f.x * A.x + f.y * A.y) * h.x + fabsf(f.z * A.x + f.w * A.y) * h.y;
+    R = rq + rb;
+}
+
+// the AABB conjunct (a body's AABB or a node's bounds, widened by the query's extents e)
+__device__ __forceinline__ bool q_box_near(const QBox& q, float2 e, float4 a)
+{
+    return a.x - e.x <= q.px && a.z + e.x >= q.px && a.y - e.y <= q.py && a.w + e.y >= q.py;
+}
+
+__device__ __forceinline__ bool q_box_overlap(const QBox& q, float2 e, float4 a, float4 m, float4 f, float2 h)
+{
+    if (!q_box_near(q, e, a)) return false;
+    const float cx = q.px - m.z, cy = q.py - m.w;
+    bool in = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float s, R;
+        q_box_axis(q, cx, cy, f, h, q_box_axis_of(q, f, k), s, R);
+        in = in && fabsf(s) <= R;
+    }
+    return in;
+}
+
+// candidate test of a cast against an AABB (a body's or a node's bounds): the ray's test on the bounds widened by e
+__device__ __forceinline__ bool q_cast_aabb(const QCast& c, float2 e, float4 a)
+{
+    if (!(a.x <= a.z && a.y <= a.w)) return false;
+    float tin; bool xe;
+    return q_ray_test(c.b.px, c.b.py, c.dx, c.dy, a.x - e.x, a.y - e.y, a.z + e.x, a.w + e.y, c.max_t, tin, xe);
+}
+
+struct QCastBox { float tin, v; int axis; };      // v: the direction along the entering axis
+
+// the four slabs (after the candidate test); the entering axis is the first that attains tin
+__device__ __forceinline__ bool q_cast_box(const QCast& c, float4 m, float4 f, float2 h, QCastBox& out)
+{
+    const float cx = c.b.px - m.z, cy = c.b.py - m.w;
+    bool ok = true;
+    float tout = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float2 A = q_box_axis_of(c.b, f, k);
+        float s, R, t0, t1;
+        q_box_axis(c.b, cx, cy, f, h, A, s, R);
+        const float v = c.dx * A.x + c.dy * A.y;
+        ok = q_slab(s, v, -R, R, t0, t1) && ok;
+        if (k == 0 || t0 > out.tin) { out.tin = t0; out.v = v; out.axis = k; }
+        if (k == 0 || t1 < tout) tout = t1;
+    }
+    return ok && out.tin <= tout && tout >= 0.f && out.tin <= c.max_t;
+}
+
 __device__ __forceinline__ unsigned long long q_ray_key(float tin, int body)
 {
     const float t = tin > 0.f ? tin : 0.f;                       // t >= 0: its bits order like its value
@@ -102,10 +176,27 @@ __device__ __forceinline__ bool q_ray_ok(const QRay& r)
 }
 __device__ __forceinline__ bool q_box_ok(float4 q) { return isfinite(q.x) && isfinite(q.y) && isfinite(q.z) && isfinite(q.w); }
 
+__device__ __forceinline__ bool q_shape_ok(const QBox& q)
+{
+    return isfinite(q.px) && isfinite(q.py) && isfinite(q.xx) && isfinite(q.xy) && isfinite(q.yx) && isfinite(q.yy) && isfinite(q.hx) && isfinite(q.hy) &&
+           q.hx > 0.f && q.hy > 0.f;
+}
+__device__ __forceinline__ bool q_cast_ok(const QCast& c)
+{
+    return q_shape_ok(c.b) && isfinite(c.dx) && isfinite(c.dy) && isfinite(c.max_t) && c.max_t >= 0.f && (c.dx != 0.f || c.dy != 0.f);
+}
+
 __device__ __forceinline__ QRay q_load_ray(const float* __restrict__ rays, int q)
 {
     const float* p = rays + 5 * (size_t)q;
     return QRay{p[0], p[1], p[2], p[3], p[4]};
+}
+
+__device__ __forceinline__ QBox q_load_box(const float* __restrict__ p) { return QBox{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}; }
+__device__ __forceinline__ QCast q_load_cast(const float* __restrict__ casts, int q)
+{
+    const float* p = casts + 11 * (size_t)q;
+    return QCast{q_load_box(p), p[8], p[9], p[10]};
 }
 
 __device__ __forceinline__ unsigned long long q_lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
@@ -160,6 +251,30 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
     }
 }
 
+// the cast results from the winners' keys, as k_qray_finish
+static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, const float* __restrict__ casts, int count,
+                                                             const unsigned long long* __restrict__ keys, phx_shape_hit* __restrict__ out)
+{
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < count; q += gridDim.x * blockDim.x) {
+        const unsigned long long k = keys[q];
+        phx_shape_hit h;
+        h.body = -1; h.t = 0.f; h.normal.x = h.normal.y = 0.f;
+        if (k != ~0ull) {
+            const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
+            const QCast c = q_load_cast(casts, q);
+            const float4 f = w.frame[b];
+            QCastBox cb;
+            (void)q_cast_box(c, w.s.mpos[b], f, w.size[b], cb);
+            h.body = b; h.t = cb.tin > 0.f ? cb.tin : 0.f;
+            if (!(cb.tin < 0.f)) {
+                const float2 n = q_box_axis_of(c.b, f, cb.axis);
+                h.normal.x = cb.v > 0.f ? -n.x : n.x; h.normal.y = cb.v > 0.f ? -n.y : n.y;
+            }
+        }
+        out[q] = h;
+    }
+}
+
 // ---- scan path --------------------------------------------------------------------------------------------------------------------
 // blockIdx.y = the tile of queries [q0, q0 + Q_TILE); bodies grid-strided in lanes.  out: 0xFFFFFFFF (= -1) where nothing was found.
 static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int n, const float* __restrict__ pts, int count, int q0, int flags,
@@ -191,16 +306,27 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
     }
 }
 
+// CAST: box casts (11 floats per query) instead of rays (5)
+template <bool CAST>
 static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n, const float* __restrict__ rays, int count, int q0, int flags,
                                                            unsigned long long* __restrict__ keys)
 {
     __shared__ QRay qr[Q_TILE];
+    __shared__ QCast qc[Q_TILE];
+    __shared__ float2 qe[Q_TILE];
     __shared__ int qok[Q_TILE];
     const int base_q = q0 + blockIdx.y * Q_TILE, nq = min(Q_TILE, count - base_q);
     if ((int)threadIdx.x < nq) {
-        const QRay r = q_load_ray(rays, base_q + threadIdx.x);
-        qr[threadIdx.x] = r;
-        qok[threadIdx.x] = q_ray_ok(r);
+        if (CAST) {
+            const QCast c = q_load_cast(rays, base_q + threadIdx.x);
+            qc[threadIdx.x] = c;
+            qe[threadIdx.x] = q_box_extents(c.b);
+            qok[threadIdx.x] = q_cast_ok(c);
+        } else {
+            const QRay r = q_load_ray(rays, base_q + threadIdx.x);
+            qr[threadIdx.x] = r;
+            qok[threadIdx.x] = q_ray_ok(r);
+        }
     }
     __syncthreads();
     const bool skip = (flags & Q_SKIP_STATIC) != 0;
@@ -212,45 +338,69 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
         const bool any = live && !(skip && q_static(m));
         for (int q = 0; q < nq; ++q) {
-            const QRay r = qr[q];
-            QRayBox rb;
-            const bool hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_box(r, m, f, h, rb);
+            bool hit;
+            float tin;
+            if (CAST) {
+                const QCast c = qc[q];
+                QCastBox cb;
+                hit = any && qok[q] && q_cast_aabb(c, qe[q], a) && q_cast_box(c, m, f, h, cb);
+                tin = hit ? cb.tin : 0.f;
+            } else {
+                const QRay r = qr[q];
+                QRayBox rb;
+                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_box(r, m, f, h, rb);
+                tin = hit ? rb.tin : 0.f;
+            }
             if (!__ballot(hit)) continue;
-            const unsigned long long k = q_wave_min64(hit ? q_ray_key(rb.tin, i) : ~0ull);
+            const unsigned long long k = q_wave_min64(hit ? q_ray_key(tin, i) : ~0ull);
             if ((threadIdx.x & 63) == 0) atomicMin(&keys[base_q + q], k);
         }
     }
 }
 
-// AABB queries, one workgroup per 256 consecutive bodies (blockIdx.x = body block of `bblocks`), blockIdx.y = tile.
+// AABB queries (OBB: oriented-box queries, 8 floats per query), one workgroup per 256 consecutive bodies (blockIdx.x = body block of
+// `bblocks`), blockIdx.y = tile.
 //   QS_COUNT    writes the hit count of every (query, body block) to table[(q - q0) * bblocks + block] (query-major: its exclusive scan
 //               places the blocks' hits of a query one after the other, in body order) and adds it to qcount[q];
 //   QS_RECOUNT  the table alone (a later chunk of queries counted again: the table holds one chunk);
 //   QS_FILL     writes the hits at base + table[...] + rank.
 enum { QS_COUNT = 0, QS_RECOUNT = 1, QS_FILL = 2 };
-template <int MODE>
+template <int MODE, bool OBB>
 static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n, const float* __restrict__ boxes, int count, int q0, int flags, int bblocks,
                                                            unsigned* __restrict__ table, unsigned* __restrict__ qcount, unsigned base, int* __restrict__ hits)
 {
     __shared__ float4 qb[Q_TILE];
+    __shared__ QBox qo[Q_TILE];
+    __shared__ float2 qe[Q_TILE];
     __shared__ int qok[Q_TILE];
     __shared__ unsigned long long masks[Q_TILE][4];
     const int tile_q = blockIdx.y * Q_TILE, base_q = q0 + tile_q, nq = min(Q_TILE, count - base_q);
     if ((int)threadIdx.x < nq) {
-        const float* p = boxes + 4 * (size_t)(base_q + threadIdx.x);
-        const float4 q = make_float4(p[0], p[1], p[2], p[3]);
-        qb[threadIdx.x] = q;
-        qok[threadIdx.x] = q_box_ok(q);
+        if (OBB) {
+            const QBox q = q_load_box(boxes + 8 * (size_t)(base_q + threadIdx.x));
+            qo[threadIdx.x] = q;
+            qe[threadIdx.x] = q_box_extents(q);
+            qok[threadIdx.x] = q_shape_ok(q);
+        } else {
+            const float* p = boxes + 4 * (size_t)(base_q + threadIdx.x);
+            const float4 q = make_float4(p[0], p[1], p[2], p[3]);
+            qb[threadIdx.x] = q;
+            qok[threadIdx.x] = q_box_ok(q);
+        }
     }
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n;
     const float4 a = live ? w.aabb[i] : make_float4(NAN, NAN, NAN, NAN);
-    const bool any = live && !((flags & Q_SKIP_STATIC) && q_static(w.s.mpos[live ? i : 0]));
+    const float4 m = (OBB || (flags & Q_SKIP_STATIC)) ? w.s.mpos[live ? i : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const bool any = live && !((flags & Q_SKIP_STATIC) && q_static(m));
+    float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
+    float2 h = make_float2(0.f, 0.f);
+    if (OBB && live) { f = w.frame[i]; h = w.size[i]; }
     unsigned long long mine = 0;
     for (int q = 0; q < nq; ++q) {
-        const bool hit = any && qok[q] && q_overlap(a, qb[q]);
+        const bool hit = any && qok[q] && (OBB ? q_box_overlap(qo[q], qe[q], a, m, f, h) : q_overlap(a, qb[q]));
         const unsigned long long mask = __ballot(hit);
         if (lane == 0) masks[q][wave] = mask;
         mine |= (unsigned long long)hit << q;
@@ -347,7 +497,7 @@ static __global__ void __launch_bounds__(256) k_qnodes(const float4* __restrict_
 }
 
 // ---- index path: traversal ----------------------------------------------------------------------------------------------------------
-enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3 };
+enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COUNT = 4, QK_BOX_FILL = 5, QK_CAST = 6 };
 
 // one wave per query, 4 per workgroup.  A stack entry is (level << 26) | node; a popped node's 64 children are tested by the 64 lanes,
 // the passing inner nodes pushed in lane order.  Depth bound: a pop pushes at most 64 entries of the level below, so the stack never
@@ -356,6 +506,8 @@ enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3 };
 //   QK_RAY         out_key[q] = min over hits of q_ray_key (~0: none)
 //   QK_AABB_COUNT  out_u32[q] = the number of hits
 //   QK_AABB_FILL   the hits at hits[seg[q] ..], in traversal order (sorted afterwards)
+//   QK_BOX_COUNT, QK_BOX_FILL   the same two for oriented boxes;   QK_CAST   as QK_RAY for box casts
+// A lane tests a child's bounds with the query's AABB conjunct: the bounds widened by the box's extents for the last three kinds.
 template <int KIND>
 static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, const float* __restrict__ queries, int count, int flags,
                                                       unsigned* __restrict__ out_u32, unsigned long long* __restrict__ out_key,
@@ -364,9 +516,13 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
     __shared__ unsigned stack_mem[4][Q_MAX_LEVELS * Q_FANOUT];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const bool skip = (flags & Q_SKIP_STATIC) != 0;
+    constexpr bool OBB = KIND == QK_BOX_COUNT || KIND == QK_BOX_FILL, COUNT = KIND == QK_AABB_COUNT || KIND == QK_BOX_COUNT;
+    constexpr bool FILL = KIND == QK_AABB_FILL || KIND == QK_BOX_FILL, KEY = KIND == QK_RAY || KIND == QK_CAST;
     for (int q = blockIdx.x * 4 + wave; q < count; q += gridDim.x * 4) {      // (the whole wave: grid-strided over the queries)
         float4 qbox = make_float4(0.f, 0.f, 0.f, 0.f);
         QRay r{0.f, 0.f, 0.f, 0.f, 0.f};
+        QCast cs{{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, 0.f};      // (a box query uses cs.b)
+        float2 ce = make_float2(0.f, 0.f);
         bool ok;
         if (KIND == QK_POINT) {
             const float px = queries[2 * (size_t)q], py = queries[2 * (size_t)q + 1];
@@ -375,6 +531,14 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
         } else if (KIND == QK_RAY) {
             r = q_load_ray(queries, q);
             ok = q_ray_ok(r);
+        } else if (KIND == QK_CAST) {
+            cs = q_load_cast(queries, q);
+            ok = q_cast_ok(cs);
+            ce = q_box_extents(cs.b);
+        } else if (OBB) {
+            cs.b = q_load_box(queries + 8 * (size_t)q);
+            ok = q_shape_ok(cs.b);
+            ce = q_box_extents(cs.b);
         } else {
             const float* p = queries + 4 * (size_t)q;
             qbox = make_float4(p[0], p[1], p[2], p[3]);
@@ -404,12 +568,17 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                                 QRayBox rb;
                                 hit = q_ray_aabb(r, a) && q_ray_box(r, m, w.frame[b], w.size[b], rb);
                                 if (hit) { const unsigned long long k = q_ray_key(rb.tin, b); best_key = k < best_key ? k : best_key; }
-                            } else hit = q_overlap(a, qbox);
+                            } else if (KIND == QK_CAST) {
+                                QCastBox cb;
+                                hit = q_cast_aabb(cs, ce, a) && q_cast_box(cs, m, w.frame[b], w.size[b], cb);
+                                if (hit) { const unsigned long long k = q_ray_key(cb.tin, b); best_key = k < best_key ? k : best_key; }
+                            } else if (OBB) hit = q_box_overlap(cs.b, ce, a, m, w.frame[b], w.size[b]);
+                            else hit = q_overlap(a, qbox);
                         }
                     }
                     if (KIND == QK_POINT && hit) best = min(best, (unsigned)b);
-                    if (KIND == QK_AABB_COUNT) n_hits += hit ? 1u : 0u;
-                    if (KIND == QK_AABB_FILL) {
+                    if (COUNT) n_hits += hit ? 1u : 0u;
+                    if (FILL) {
                         const unsigned long long mask = __ballot(hit);
                         if (hit) hits[seg[q] + cursor + (unsigned)__popcll(mask & q_lanes_below())] = b;
                         cursor += (unsigned)__popcll(mask);
@@ -418,7 +587,7 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                     bool pass = false;
                     if (c < t.cnt[level - 1]) {
                         const float4 nb = t.nodes[t.off[level - 1] + c];
-                        pass = KIND == QK_RAY ? q_ray_aabb(r, nb) : q_overlap(nb, qbox);
+                        pass = KIND == QK_RAY ? q_ray_aabb(r, nb) : KIND == QK_CAST ? q_cast_aabb(cs, ce, nb) : OBB ? q_box_near(cs.b, ce, nb) : q_overlap(nb, qbox);
                     }
                     const unsigned long long mask = __ballot(pass);
                     if (pass) st[sp + __popcll(mask & q_lanes_below())] = ((unsigned)(level - 1) << 26) | (unsigned)c;
@@ -428,8 +597,8 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
             }
         }
         if (KIND == QK_POINT) { best = q_wave_min(best); if (lane == 0) out_u32[q] = best; }
-        if (KIND == QK_RAY) { best_key = q_wave_min64(best_key); if (lane == 0) out_key[q] = best_key; }
-        if (KIND == QK_AABB_COUNT) { n_hits = q_wave_sum(n_hits); if (lane == 0) out_u32[q] = n_hits; }
+        if (KEY) { best_key = q_wave_min64(best_key); if (lane == 0) out_key[q] = best_key; }
+        if (COUNT) { n_hits = q_wave_sum(n_hits); if (lane == 0) out_u32[q] = n_hits; }
         __builtin_amdgcn_wave_barrier();                                    // (the stack is reused by the wave's next query)
     }
 }

@@ -166,6 +166,9 @@ public:
     int raycast(const float* rays, int count, int flags, phx_ray_hit* out);
     int query_points_device(const void* d_points, int count, int flags, void* d_body);
     int raycast_device(const void* d_rays, int count, int flags, void* d_out);
+    int query_boxes(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total);
+    int cast_boxes(const float* casts, int count, int flags, phx_shape_hit* out);
+    int cast_boxes_device(const void* d_casts, int count, int flags, void* d_out);
     int query_index_build();             // the query index alone, built unless current (tools/query_cost.py)
     int query_index_builds() const { return query_.index_builds(); }
     // contact reports (phx_world_query_contacts ... phx_world_contact_index): between steps; only the events' baseline changes
@@ -286,6 +289,7 @@ private:
     DeviceQuery query_;
     DevBuf<int> q_body_;
     DevBuf<phx_ray_hit> q_hits_;
+    DevBuf<phx_shape_hit> q_shape_hits_;
     int query_prepare(bool host_wait);
     // contact reports: the contact epoch is bumped by every path that can change the manifolds (every step, a removal, set_state and so
     // a re-slab) or the body count; the contact index is current while it was built for this epoch
@@ -1416,6 +1420,9 @@ static int query_check(const char* what, const float* v, int count, int width, i
         if (width == 4 && !(q[0] <= q[2] && q[1] <= q[3])) { set_error("%s: box %d: min exceeds max", what, k); return PHX_ERR_INVALID; }
         if (width == 5 && !(q[4] >= 0.f)) { set_error("%s: ray %d: max_t < 0", what, k); return PHX_ERR_INVALID; }
         if (width == 5 && q[2] == 0.f && q[3] == 0.f) { set_error("%s: ray %d: zero direction", what, k); return PHX_ERR_INVALID; }
+        if (width >= 8 && !(q[6] > 0.f && q[7] > 0.f)) { set_error("%s: box %d: half extents must be positive", what, k); return PHX_ERR_INVALID; }
+        if (width == 11 && !(q[10] >= 0.f)) { set_error("%s: cast %d: max_t < 0", what, k); return PHX_ERR_INVALID; }
+        if (width == 11 && q[8] == 0.f && q[9] == 0.f) { set_error("%s: cast %d: zero direction", what, k); return PHX_ERR_INVALID; }
     }
     return PHX_OK;
 }
@@ -1487,6 +1494,43 @@ int World::raycast_device(const void* d_rays, int count, int flags, void* d_out)
     if (!count) return PHX_OK;
     PHX_TRY(query_prepare(false));
     return query_.rays(resident(), nb(), geom_epoch_, static_cast<const float*>(d_rays), count, flags, static_cast<phx_ray_hit*>(d_out), stream_);
+}
+
+int World::query_boxes(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
+{
+    static const char* const what = "phx_world_query_boxes";
+    PHX_TRY(query_check(what, boxes, count, 8, flags, false, boxes));
+    if (!offsets || !total) { set_error("%s: null offsets / total", what); return PHX_ERR_INVALID; }
+    if (hit_cap < 0 || (hit_cap > 0 && !hits)) { set_error("%s: bad hits buffer (cap %d)", what, hit_cap); return PHX_ERR_INVALID; }
+    PHX_TRY(query_prepare(true));
+    const float* d_boxes = nullptr;
+    if (count && nb()) { const int* unused = nullptr; PHX_TRY(stage_batch(nullptr, boxes, count, 8, &unused, &d_boxes)); }
+    return query_.shapes(resident(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
+}
+
+int World::cast_boxes(const float* casts, int count, int flags, phx_shape_hit* out)
+{
+    static const char* const what = "phx_world_cast_boxes";
+    PHX_TRY(query_check(what, casts, count, 11, flags, false, out));
+    if (!count) return PHX_OK;
+    PHX_TRY(query_prepare(true));
+    if (!nb()) { std::memset(out, 0, (size_t)count * sizeof(phx_shape_hit)); for (int k = 0; k < count; ++k) out[k].body = -1; return PHX_OK; }
+    const int* unused = nullptr; const float* d_casts = nullptr;
+    PHX_TRY(stage_batch(nullptr, casts, count, 11, &unused, &d_casts));
+    PHX_TRY(q_shape_hits_.reserve((size_t)count));
+    PHX_TRY(query_.casts(resident(), nb(), geom_epoch_, d_casts, count, flags, q_shape_hits_.p, stream_));
+    PHX_TRY(rb_.add(out, q_shape_hits_.p, (size_t)count * sizeof(phx_shape_hit), stream_));
+    return rb_.wait(stream_);
+}
+
+int World::cast_boxes_device(const void* d_casts, int count, int flags, void* d_out)
+{
+    static const char* const what = "phx_world_cast_boxes_device";
+    PHX_TRY(query_check(what, static_cast<const float*>(d_casts), count, 11, flags, true, d_out));
+    if (count && ((reinterpret_cast<uintptr_t>(d_casts) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    PHX_TRY(query_prepare(false));
+    return query_.casts(resident(), nb(), geom_epoch_, static_cast<const float*>(d_casts), count, flags, static_cast<phx_shape_hit*>(d_out), stream_);
 }
 
 int World::query_index_build()
@@ -1780,6 +1824,24 @@ int phx_world_raycast_device(phx_world* w, const void* d_rays, int32_t count, in
 {
     PHX_REQUIRE(w, "null handle");
     return w->impl.raycast_device(d_rays, count, flags, d_out);
+}
+
+int phx_world_query_boxes(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_boxes(boxes, count, flags, offsets, hits, hit_cap, total);
+}
+
+int phx_world_cast_boxes(phx_world* w, const float* casts, int32_t count, int32_t flags, phx_shape_hit* out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.cast_boxes(casts, count, flags, out);
+}
+
+int phx_world_cast_boxes_device(phx_world* w, const void* d_casts, int32_t count, int32_t flags, void* d_out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.cast_boxes_device(d_casts, count, flags, d_out);
 }
 
 int phx_world_query_contacts(phx_world* w, const int32_t* bodies, int32_t count, int32_t flags, int32_t* offsets, phx_contact* out, int32_t cap, int64_t* total)
