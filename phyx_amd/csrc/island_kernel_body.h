@@ -10,9 +10,11 @@
     __shared__ BodyT imp[NB + 1];
     __shared__ BodyT disp[NB + 1];
     // static-tag words [imp|disp][parity][body]; during set-up the same 12 KB hold {invMass, invInertia, pos} per body
-    __shared__ __attribute__((aligned(16))) unsigned sw_raw[4 * NB];
+    // (... and 64 spare words behind them that nobody reads: where a lane that has no static tag to raise sends its atomicMax)
+    __shared__ __attribute__((aligned(16))) unsigned sw_raw[4 * NB + 64];
     __shared__ unsigned char is_st[NB];
-    __shared__ int flag_imp[3], flag_disp[3];     // 'some joint was productive in sweep it': slot it % 3
+    // 'some joint was productive in sweep it': slot it % 3; word 3 of either table is never read: an unproductive lane's store goes there
+    __shared__ int flag_imp[4], flag_disp[4];
     __shared__ int s_commit;                      // ISL_VERIFY: every workgroup of the launch arrived and none found a difference
     unsigned (*swi)[NB] = reinterpret_cast<unsigned (*)[NB]>(sw_raw);
     unsigned (*swd)[NB] = reinterpret_cast<unsigned (*)[NB]>(sw_raw + 2 * NB);
@@ -260,25 +262,32 @@
         unsigned (*const sw)[NB] = IMP ? swi : swd;
         float4 B1 = body_load(rec, l1), B2 = body_load(rec, l2);
         // (`ws`: the static tags' words travel with the body records — every lane of the wave reads them, a dynamic body's
-        //  are zero — instead of two more dependent LDS round trips for the one lane that needs them)
-        unsigned pw1 = 0u, cw1 = 0u, pw2 = 0u, cw2 = 0u;
-        if (ws) { pw1 = sw[(it - 1) & 1][l1]; cw1 = sw[it & 1][l1]; pw2 = sw[(it - 1) & 1][l2]; cw2 = sw[it & 1][l2]; }
+        //  are zero — instead of two more dependent LDS round trips for the one lane that needs them.  Both parities of both bodies,
+        //  at addresses fixed for the solve: which of the two is sweep it's table is said by the thresholds below, on the scalar unit)
+        unsigned e1 = 0u, o1 = 0u, e2 = 0u, o2 = 0u;
+        if (ws) { e1 = sw[0][l1]; o1 = sw[1][l1]; e2 = sw[0][l2]; o2 = sw[1][l2]; }
         // (everything in ONE LDS round trip: left alone, the compiler reads the two tags, tests, and only then — under the
         //  branch — the six velocity words: two dependent round trips on the critical path of every class step)
-        if (!HALF) asm volatile("" : "+v"(B1.x), "+v"(B1.y), "+v"(B1.z), "+v"(B1.w), "+v"(B2.x), "+v"(B2.y), "+v"(B2.z), "+v"(B2.w));
-        if (ws) asm volatile("" : "+v"(pw1), "+v"(cw1), "+v"(pw2), "+v"(cw2));
+        // (`ws`: the records are inputs of the fence, not tied in-and-out operands: tied, the eight words were copied to other
+        //  registers in front of the leader, which writes its results beside them anyway — the follower's static body wants them back)
+        if (!HALF && !ws) asm volatile("" : "+v"(B1.x), "+v"(B1.y), "+v"(B1.z), "+v"(B1.w), "+v"(B2.x), "+v"(B2.y), "+v"(B2.z), "+v"(B2.w));
+        if (!HALF && ws) asm volatile("" : "+v"(e1), "+v"(o1), "+v"(e2), "+v"(o2) : "v"(B1.x), "v"(B1.y), "v"(B1.z), "v"(B1.w), "v"(B2.x), "v"(B2.y), "v"(B2.z), "v"(B2.w));
+        if (HALF && ws) asm volatile("" : "+v"(e1), "+v"(o1), "+v"(e2), "+v"(o2));
         if (wt) { __builtin_amdgcn_s_waitcnt(0xC07F); tp1 = (unsigned)__builtin_readcyclecounter(); }
         bool active = max(__float_as_int(B1.w), __float_as_int(B2.w)) > it - 2;
         if (ws) {
-            // solver_kernels.h static_productive on the words already here — every lane evaluates both bodies' tests and selects (no
-            // short-circuit: as `st1 && sp(..)` this was four exec-mask regions in the one wave whose step everybody waits for)
-            const unsigned itu = (unsigned)it, clu = (unsigned)c;
-            auto sp = [&](unsigned pw, unsigned cw) {
-                return (int)(it == 0) | (int)((pw >> 16) == itu) | ((int)((cw >> 16) == itu + 1u) & (int)((0xFFFFu - (cw & 0xFFFFu)) < clu));
-            };
-            const int a1 = (sp(pw1, cw1) & sm1) | ((int)(__float_as_int(B1.w) > it - 2) & ~sm1);
-            const int a2 = (sp(pw2, cw2) & sm2) | ((int)(__float_as_int(B2.w) > it - 2) & ~sm2);
-            active = ((a1 | a2) & 1) != 0;
+            // solver_kernels.h static_productive on the words already here, as two unsigned compares per table.  The words only grow
+            // (atomicMax), sweep s raises table s & 1 to static_word(s, class) = (s + 1) << 16 | 0xFFFF - class, so in sweep `it` the
+            // other table holds at most it << 16 | 0xFFFF and this one at most (it + 1) << 16 | 0xFFFF:
+            //   'raised in sweep it - 1' (high half == it; always in sweep 0)             <=>  word >= it << 16
+            //   'raised in this sweep by an earlier class' (high half == it + 1, class < c) <=>  word > static_word(it, c)
+            // And no select between this test and the body's own tag is needed: a static body's record is never stored, its tag
+            // stays -1 and passes `> it - 2` in sweep 0 only, where the static test passes too; a dynamic body's words stay zero
+            // and pass the static test in sweep 0 only, where its tag (-1) passes too.  So the four tests are simply OR-ed.
+            const unsigned prev = (unsigned)it << 16, cur = static_word(it, c) + 1u;
+            const unsigned te = (it & 1) ? prev : cur, to = (it & 1) ? cur : prev;
+            active |= max(e1, e2) >= te;
+            active |= max(o1, o2) >= to;
         }
         if (active) {
             const float4 S1 = B1, S2 = B2;
@@ -286,24 +295,27 @@
                              : displacement_productive(displacement_visit(q0, q0.accD, B1, B2, im1, ii1, im2, ii2));
             if (has2) {
                 if (HALF) { B1 = body_round<HALF>(B1); B2 = body_round<HALF>(B2); }      // (the ablation rounds on every joint's store)
-                if (ws) {
-                    B1.x = sm1 ? S1.x : B1.x; B1.y = sm1 ? S1.y : B1.y; B1.z = sm1 ? S1.z : B1.z; B1.w = sm1 ? S1.w : B1.w;
-                    B2.x = sm2 ? S2.x : B2.x; B2.y = sm2 ? S2.y : B2.y; B2.z = sm2 ? S2.z : B2.z; B2.w = sm2 ? S2.w : B2.w;
+                if (ws) {      // (a visit leaves the tag word alone: three words a body)
+                    B1.x = sm1 ? S1.x : B1.x; B1.y = sm1 ? S1.y : B1.y; B1.z = sm1 ? S1.z : B1.z;
+                    B2.x = sm2 ? S2.x : B2.x; B2.y = sm2 ? S2.y : B2.y; B2.z = sm2 ? S2.z : B2.z;
                 }
                 prod |= IMP ? impulse_productive(impulse_visit(q1, q1.accN, q1.accF, B1, B2, im1, ii1, im2, ii2, mu))
                              : displacement_productive(displacement_visit(q1, q1.accD, B1, B2, im1, ii1, im2, ii2));
             }
             if (wt) { asm volatile("" : "+v"(B1.x), "+v"(B1.y), "+v"(B1.z), "+v"(B2.x), "+v"(B2.y), "+v"(B2.z)); tp2 = (unsigned)__builtin_readcyclecounter(); }
+            // The tail, straight-line and stores first: the velocity words are final at the last FMA, and `prod` hangs on the impulses
+            // alone, so the tag select sits under the last FMAs.  What only a productive lane does is said with the ADDRESS (as sl1,
+            // sl2 are): the sweep's flag goes to the slot or to the table's spare word, a static tag to the body's word or to a
+            // spare word of the lane's own — no exec region and no taken branch between the last FMA and the barrier.
             B1.w = prod ? __int_as_float(it) : B1.w; B2.w = prod ? __int_as_float(it) : B2.w;
-            if (prod) {
-                if (IMP) flag_imp[slot] = 1; else flag_disp[slot] = 1;
-                if (ws) {
-                    if (st1) atomicMax(&sw[it & 1][l1], static_word(it, c));
-                    if (st2) atomicMax(&sw[it & 1][l2], static_word(it, c));
-                }
-            }
             body_store(rec, sl1, B1);
             body_store(rec, sl2, B2);
+            (IMP ? flag_imp : flag_disp)[prod ? slot : 3] = 1;
+            if (ws) {
+                const int tab = (IMP ? 0 : 2 * NB) + (it & 1) * NB, spare = 4 * NB + (tid & 63);
+                atomicMax(&sw_raw[(prod && st1) ? tab + l1 : spare], static_word(it, c));
+                atomicMax(&sw_raw[(prod && st2) ? tab + l2 : spare], static_word(it, c));
+            }
             if (wt) tp3 = (unsigned)__builtin_readcyclecounter() | 1u;
         }
     };
@@ -339,13 +351,16 @@
         if (TRACE && it == 0) PHX_ISL_PHASE(8);
     }
 
-    if (hot_from_here)
+    // (a loop of its own for either kind of wave — wave_static is wave-uniform and fixed, every wave passes the same barriers: with
+    //  both forms of the step in one loop the unit's accumulators were copied between the registers of the two forms, eight moves
+    //  between the stores and the barrier in every step, and every step began with a branch on wave_static)
+    auto hot_sweeps = [&](const bool ws) {
         for (; it < ci && imp_alive; ++it) {
             peek_ctl();
             next_slot();
             for (c = 0; c < ncol; ++c) {
                 step_begin();
-                if (col == c) { if (wave_static) half_step(IMPULSES, true); else half_step(IMPULSES, false); }
+                if (col == c) half_step(IMPULSES, ws);
                 step_work_done();
                 __syncthreads();
                 step_end(true);
@@ -353,6 +368,8 @@
             done_imp = it + 1; imp_alive = flag_imp[slot] != 0;
             if (TRACE && it == 0) PHX_ISL_PHASE(8);
         }
+    };
+    if (hot_from_here) { if (wave_static) hot_sweeps(true); else hot_sweeps(false); }
 
     PHX_ISL_STAMP(4);
     // results go straight back into the caller's records (commit-gated like k_finish_*); the refreshed constants
