@@ -539,6 +539,37 @@ typedef struct { float friction, restitution; } phx_material;      /* 8 B; defau
 int  phx_world_set_materials(phx_world* w, const int32_t* bodies, const phx_material* materials, int32_t count);
 /* every body's material, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
 int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
+/* BODY FLAGS / SENSORS — a body that detects what overlaps it and pushes nothing (a trigger volume).  Every body has a 32-bit flag word,
+ * default 0.  One flag is defined, PHX_BODY_SENSOR; any other bit is PHX_ERR_INVALID.  A world whose flags are all 0 steps bit for bit as
+ * one that never heard of flags.
+ *   - Rule: a manifold is a SENSOR MANIFOLD iff either of its bodies has PHX_BODY_SENSOR.  The change is confined to the Match loop of
+ *     RefreshContactJoints (ref: World.cpp:72-149): for every live slot of a sensor manifold, solver_index = -1, and nothing else happens
+ *     for that slot — no joint is created and none is re-attached.  Reset and Cleanup are the reference's, unchanged.  So a joint whose
+ *     manifold became a sensor manifold is not re-attached and the reference's own swap-remove Cleanup deletes it, in the reference's
+ *     order; and a manifold that stops being a sensor manifold gets fresh joints with zero warm-start impulses at the next step, as any
+ *     point with solver_index < 0 does.
+ *   - Nothing else changes: UpdatePairs, UpdateManifolds, PackManifolds, the narrowphase, the solver and the integrators stay as they
+ *     are.  Sensor pairs have manifolds and contact points, so they are in the touching set T(s) of phx_world_contact_events (begin when
+ *     something enters the sensor, end when it leaves), phx_world_query_contacts returns their records with PHX_CONTACT_NO_JOINT and
+ *     zero impulses, and the markers show them.  A sensor body is otherwise an ordinary body: a dynamic one falls under gravity and is
+ *     integrated (nothing holds it up), a static one is a fixed trigger zone.  Queries see sensor bodies like any other body.
+ *   - Setting flags: the rules of the edits above.  Between steps only (PHX_ERR_STATE); checked completely before anything is queued
+ *     (count >= 0, no NULL array when count > 0, every index in [0, body count), none twice, no unknown bit; PHX_ERR_INVALID otherwise,
+ *     the world unchanged); staged through pinned memory and queued on phx_world_stream(w); before the first step it writes the
+ *     host-staged bodies' flags.  The call changes only the flag words: the joints go or come at the NEXT step's refresh, and until
+ *     that step the getters and the contact reports show the old joints.  The step that deletes or creates joints rebuilds the solver's
+ *     schedule as any step that does (phx_solve_stats.recoloured == 1); a flag change that touches no manifold changes no topology.
+ *   - The other calls: add_body / add_bodies give new bodies 0; remove_bodies / remove_outside move flags with the kept bodies (through
+ *     new[]); phx_world_set_state resets every flag to 0 (a world with sensors is checkpointed as set_state followed by
+ *     set_body_flags); the edits, set_inverse_masses, collision filters, materials, queries and contact reports leave them alone.
+ *   - Sharded worlds carry no flags: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and phx_world_reslab
+ *     return PHX_ERR_STATE while some body's flags are not 0.
+ * The joint match reads the flags (two 4-byte gathers per manifold) only in a world where some flag was ever set (since the last
+ * set_state); every other world launches the kernels it always did.  Costs and the data path: DESIGN.md. */
+#define PHX_BODY_SENSOR 1u
+int  phx_world_set_body_flags(phx_world* w, const int32_t* bodies, const uint32_t* flags, int32_t count);
+/* every body's flags, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
+int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
 /* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first, whether a spot is free for a box
  * and how far a box can move before it touches something.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
@@ -636,7 +667,8 @@ int  phx_world_cast_boxes_device(phx_world* w, const void* d_casts, int32_t coun
  *                  dot(normal, pos1 - pos2) >= 0 when the point was generated (ref: Collider.cpp GenerateContacts): it points from body2
  *                  towards body1.  So the record's normal points from `other` towards b: the direction the contact pushes b;
  *       normal_impulse, friction_impulse = joints[cp.solver_index]'s accumulated impulses as stored; if solver_index is outside
- *                  [0, joint count) both are 0 and PHX_CONTACT_NO_JOINT is set (set_state does not rule that out);
+ *                  [0, joint count) both are 0 and PHX_CONTACT_NO_JOINT is set (set_state does not rule that out, and every
+ *                  contact of a sensor pair carries it from the step after the flag was set: BODY FLAGS / SENSORS);
  *       flags    = PHX_CONTACT_NEW if cp.is_newly_created != 0, | PHX_CONTACT_NO_JOINT as above.
  *     Records are ordered by (other, manifold, slot) ascending; the order does not depend on where PackManifolds moved a manifold.
  *     flags PHX_QUERY_SKIP_STATIC leaves out records whose `other` is static (inv_mass == 0 && inv_inertia == 0, as for the queries).

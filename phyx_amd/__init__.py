@@ -8,7 +8,7 @@ from .api import (Configuration, Solver, Collider, World, Comm, SOLVE_SCALAR, SO
                   ISLAND_SINGLE, ISLAND_MULTIPLE, ISLAND_SINGLE_SLOPPY, ISLAND_MULTIPLE_SLOPPY,
                   rigid_body_dtype, contact_point_dtype, manifold_dtype, contact_joint_dtype, ray_hit_dtype,
                   shape_hit_dtype, box_from_angle,
-                  contact_dtype, contact_marker_dtype, collision_filter_dtype, material_dtype,
+                  contact_dtype, contact_marker_dtype, collision_filter_dtype, material_dtype, BODY_SENSOR,
                   broadphase_entry_dtype, sort_entry_dtype, device_count, device_info, DeviceArray, DeviceBuffer, exchange_layout, schedule_colours, schedule_groups, schedule_islands, schedule_priority)
 from ._lib import PhxError  # noqa: F401
 from . import scenes  # noqa: F401

@@ -167,6 +167,8 @@ _SIGNATURES = {
     "phx_world_get_collision_filters": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_set_materials": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_get_materials": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_set_body_flags": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_get_body_flags": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_query_aabb": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "phx_world_query_points": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_raycast": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),

@@ -50,6 +50,7 @@ assert material_dtype.itemsize == 8
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
+BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
 
 
@@ -876,6 +877,31 @@ class World:
         """Every body's material, in index order: an array of material_dtype."""
         out = np.zeros(self.counts()[0], dtype=material_dtype)
         check(self.L.phx_world_get_materials(self.h, _ptr(out), len(out)))
+        return out
+
+    # ---- body flags / sensors (include/phyx_amd.h BODY FLAGS / SENSORS; the specification: tests/sensor_spec.py) ----
+    def set_body_flags(self, bodies, flags):
+        """Give the listed bodies (each at most once) the flag word `flags`: a scalar for all of them or one value per body.  BODY_SENSOR
+        makes a body a trigger volume: its pairs keep their manifolds and contact points (touch events, contact reports with
+        CONTACT_NO_JOINT) and get no joints, from the next step on.  The library rejects any other bit (PhxError), the world unchanged."""
+        if isinstance(bodies, (list, tuple)) and not len(bodies):
+            bodies = np.zeros(0, dtype=np.int32)
+        idx = self._indices(bodies, "set_body_flags")
+        a = np.asarray(flags)
+        if a.dtype.kind not in "iu":
+            raise TypeError("set_body_flags: flags must be integers, got %s" % (a.dtype,))
+        if a.ndim > 1 or (a.ndim == 1 and a.shape != (len(idx),)):
+            raise ValueError("set_body_flags: flags must be a scalar or have shape (%d,), got %s" % (len(idx), a.shape))
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 2 ** 32 - 1):
+            raise ValueError("set_body_flags: flags out of the range [0, 2^32)")
+        f = np.zeros(len(idx), dtype=np.uint32)
+        f[:] = a
+        check(self.L.phx_world_set_body_flags(self.h, _ptr(idx), _ptr(f), len(idx)))
+
+    def body_flags(self):
+        """Every body's flag word, in index order: a uint32 array."""
+        out = np.zeros(self.counts()[0], dtype=np.uint32)
+        check(self.L.phx_world_get_body_flags(self.h, _ptr(out), len(out)))
         return out
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----

@@ -184,6 +184,9 @@ public:
     // materials (phx_world_set_materials / get_materials): between steps; they change no topology
     int set_materials(const int32_t* bodies, const phx_material* materials, int count);
     int get_materials(phx_material* out, int cap);
+    // body flags (phx_world_set_body_flags / get_body_flags): between steps; the joints of a sensor go or come at the next step's refresh
+    int set_body_flags(const int32_t* bodies, const uint32_t* flags, int count);
+    int get_body_flags(uint32_t* out, int cap);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
 
@@ -298,12 +301,14 @@ private:
     ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, bodies_.mpos.p, nb()}; }
     int contact_prepare(const char* what, bool host_wait);
     // the optional columns (BodyTable): collision filters — an active table picks the filtered sweep — and materials — an active table
-    // picks the solver's material kernels (DeviceSolver::set_materials)
+    // picks the solver's material kernels (DeviceSolver::set_materials) — and body flags — an active table picks the sensor variants of
+    // the joint match and takes the schedule rebuild's components from the joints (refresh_contact_joints, pre_solve)
     BodyTable<FilterColumn> filters_;
     BodyTable<MaterialColumn> materials_;
-    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); return f(materials_); }
-    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr()}; }
-    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr()}; }
+    BodyTable<FlagsColumn> flags_col_;
+    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); return f(flags_col_); }
+    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr()}; }
+    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr()}; }
 };
 
 World::~World()
@@ -540,6 +545,7 @@ int World::refresh_contact_joints()                                         // r
     // One host round trip for the counts.  A joint is dead iff no contact point re-attached it (the match), which is
     // known before the new joints exist; the new joints are appended behind the old ones and are alive by construction.
     unsigned host[4] = {0, 0, 0, 0};                                        // [0] new joints, [1] dead joints, [2] dead manifolds, [3] dropped points
+    const uint32_t* const sensor_flags = flags_col_.ptr();                  // the sensor rule (world_kernels.h BodySensors); null: no body ever got a flag
     for (;;) {
         if (++joint_epoch_ == 0) {                                          // the epoch wrapped: stale stamps could alias
             PHX_HIP(hipMemsetAsync(joint_seen_.p, 0, joint_seen_.cap * sizeof(unsigned), stream_));
@@ -550,8 +556,11 @@ int World::refresh_contact_joints()                                         // r
         //  longer than that: at 1M boxes the side stream's 140 us were the critical path of the step, started 100 us after they could have)
         if (nm >= PRELABEL_EARLY_MANIFOLDS) PHX_TRY(solver_.prelabel_components((const float4*)bodies_.mpos.p, nb(), (const phx_manifold*)d_manifolds_.p, nm));
         if (nm) {
-            hipLaunchKernelGGL(k_joints_match, dim3(wgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, (const phx_contact_point*)d_cps_.p,
-                               d_joints_.p, joint_seen_.p, joint_epoch_, flags_.p);
+            // (a null column pointer picks the plain instantiation: the kernels of a world that never set a flag)
+            if (sensor_flags) hipLaunchKernelGGL(k_joints_match<BodySensors>, dim3(wgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, d_cps_.p,
+                                                 d_joints_.p, joint_seen_.p, joint_epoch_, flags_.p, BodySensors{sensor_flags});
+            else hipLaunchKernelGGL(k_joints_match<NoSensors>, dim3(wgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, (const phx_contact_point*)d_cps_.p,
+                                    d_joints_.p, joint_seen_.p, joint_epoch_, flags_.p, NoSensors{});
             PHX_TRY(device_exclusive_scan(flags_.p, nm, counters_.p, scan_tiles_, stream_));
         }
         if (nj) PHX_TRY(device_exclusive_scan_of(JointDeadLoad{(const unsigned*)joint_seen_.p, joint_epoch_}, dead_flags_.p, nj, counters_.p + 1, scan_tiles_, stream_));
@@ -587,8 +596,11 @@ int World::refresh_contact_joints()                                         // r
         joints_changed_ = true;
         PHX_TRY(d_joints_.reserve_keep((size_t)nj + fresh, nj, stream_));
         const int mover_blocks = dead ? wgrid(dead) : 0;                    // the clean-up's movers ride along (independent of the new joints)
-        hipLaunchKernelGGL(k_joints_create, dim3(wgrid(nm) + mover_blocks), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj,
-                           (const unsigned*)flags_.p, mover_blocks, (const unsigned*)dead_flags_.p, (const unsigned*)(counters_.p + 1), total, mover_pos_.p);
+        if (sensor_flags) hipLaunchKernelGGL(k_joints_create<BodySensors>, dim3(wgrid(nm) + mover_blocks), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, d_cps_.p,
+                                             d_joints_.p, nj, (const unsigned*)flags_.p, mover_blocks, (const unsigned*)dead_flags_.p, (const unsigned*)(counters_.p + 1), total,
+                                             mover_pos_.p, BodySensors{sensor_flags});
+        else hipLaunchKernelGGL(k_joints_create<NoSensors>, dim3(wgrid(nm) + mover_blocks), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj,
+                                (const unsigned*)flags_.p, mover_blocks, (const unsigned*)dead_flags_.p, (const unsigned*)(counters_.p + 1), total, mover_pos_.p, NoSensors{});
     }
     if (dead) {                                                             // cleanup (ref: World.cpp:125-143): holes take movers from the tail
         joints_changed_ = true;
@@ -681,7 +693,11 @@ int World::pre_solve(float dt)
     { RoctxRange r("PackManifolds"); PHX_TRY(pack_manifolds()); lap(4); }                            // ref: Collider.cpp:381
     // (marked BEHIND PackManifolds: a pack that runs here moves manifolds, and the side stream must read them where they end up —
     //  ADVICE r5; a pack that is only found necessary later, with the joint counts, voids the side stream's work: refresh_contact_joints)
-    if (!phase_timing) PHX_TRY(solver_.prelabel_mark());
+    // (not in a world with an active flags column either: the side stream takes "a manifold with contact points" for a unit and reads its
+    //  joints through the slots, and a sensor manifold has points and no joints — such a world's rebuild takes its components from the
+    //  joints, the path PHX_NO_PRELABEL=1 takes, which is exact)
+    if (flags_col_.active) PHX_TRY(solver_.cancel_prelabel());
+    else if (!phase_timing) PHX_TRY(solver_.prelabel_mark());
     { RoctxRange r("RefreshContactJoints"); PHX_TRY(refresh_contact_joints()); lap(5); }             // ref: World.cpp:74
     return PHX_OK;
 }
@@ -1403,6 +1419,27 @@ int World::set_materials(const int32_t* bodies, const phx_material* materials, i
     return materials_.set_device(d_bodies, d_values, count, n, stream_);
 }
 
+// ---- body flags / sensors -----------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h BODY FLAGS / SENSORS.  The call writes the column and nothing else; the joint match of the next step
+// (world_kernels.h BodySensors) is what takes a sensor manifold's joints away or lets them come back, and sets joints_changed_ when it does.
+int World::set_body_flags(const int32_t* bodies, const uint32_t* flags, int count)
+{
+    static const char* const what = "phx_world_set_body_flags";
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no body flags", what); return PHX_ERR_STATE; }
+    PHX_TRY(check_batch(what, bodies, flags, count, true));
+    for (int k = 0; k < count; ++k)
+        if (flags[k] & ~(uint32_t)PHX_BODY_SENSOR) { set_error("%s: flags 0x%x of body %d hold an unknown bit", what, flags[k], bodies[k]); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    const int n = nb();
+    if (host_staged()) { flags_col_.set_host(bodies, flags, count, n); return PHX_OK; }      // (the table goes up with the bodies)
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before the table changes)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(flags), count, 1, &d_bodies, &d_values));
+    return flags_col_.set_device(d_bodies, d_values, count, n, stream_);
+}
+int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_get_body_flags", flags_col_, out, cap); }
+
 // ---- queries ------------------------------------------------------------------------------------------------------------------------
 // Answered on the world's stream from the resident arrays (query.h / query_kernels.h).  The host forms check everything first, stage the
 // queries through the world's pinned staging and wait for their results; the device forms only queue.  Nothing of the world changes:
@@ -1794,6 +1831,19 @@ int phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap)
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
     return w->impl.get_materials(out, cap);
+}
+
+int phx_world_set_body_flags(phx_world* w, const int32_t* bodies, const uint32_t* flags, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_body_flags(bodies, flags, count);
+}
+
+int phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_body_flags(out, cap);
 }
 
 int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)

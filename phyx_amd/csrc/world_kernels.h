@@ -155,7 +155,17 @@ struct MaterialColumn {                // include/phyx_amd.h MATERIALS; the pair
     static api shown(const value& v) { return api{v.x, v.y}; }
     static bool is_initial(const value& v) { return v.x == MATERIAL_DEFAULT_FRICTION && v.y == MATERIAL_DEFAULT_RESTITUTION; }
 };
-static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float), "a batch is staged as 4-byte words");
+struct FlagsColumn {                   // include/phyx_amd.h BODY FLAGS / SENSORS; the rule: BodySensors below, in the joint match
+    using value = uint32_t;            // PHX_BODY_* bits
+    using api = uint32_t;
+    static constexpr const char* plural = "body flags";
+    static __host__ __device__ value initial() { return 0u; }
+    static __host__ __device__ value stored(const api& f) { return f; }
+    static api shown(const value& v) { return v; }
+    static bool is_initial(const value& v) { return v == 0u; }
+};
+static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float) && sizeof(uint32_t) == sizeof(float),
+              "a batch is staged as 4-byte words");
 
 // a column that becomes active is filled with its default, then the staged batch {indices | values} is scattered into it
 template <class Column>
@@ -171,11 +181,13 @@ static __global__ void __launch_bounds__(256) k_scatter_column(const int* __rest
 }
 
 // what the spawn and the removal move beside the records and the resident arrays: the pending accelerations (consumed by the next
-// IntegrateVelocity) and the columns above.  Null = absent.  A new column is one member here and one line in each of the two kernels.
+// IntegrateVelocity) and the columns above.  Null = absent.  A new column is one member here, one line in each of the two kernels, and its table in the World's
+// each_table / columns() / spare_columns() (world.hip), which is what fills the member.
 struct BodyColumns {
     float4* accel;
     uint4* filters;
     float2* materials;
+    uint32_t* flags;
 };
 
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
@@ -207,6 +219,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         if (cols.accel) cols.accel[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (cols.filters) cols.filters[i] = FilterColumn::initial();
         if (cols.materials) cols.materials[i] = MaterialColumn::initial();
+        if (cols.flags) cols.flags[i] = FlagsColumn::initial();
     }
 }
 
@@ -387,13 +400,38 @@ static __global__ void __launch_bounds__(256) k_pack_manifolds(phx_manifold* __r
 // Match, pass 1: matched points re-attach their joint and stamp it; count the points that need a new joint.  (A kernel of its
 // own: as the loader of its scan it was slower — 25 us against 9 + 5 at 2e5 manifolds, 112 us at 1e6: a scan workgroup is 1024
 // lanes of four items each, too few lanes in flight for this chain of dependent gathers.)
-static __global__ void __launch_bounds__(256) k_joints_match(const phx_manifold* __restrict__ manifolds, int nm, const phx_contact_point* __restrict__ cps,
+//
+// Sensors (include/phyx_amd.h BODY FLAGS / SENSORS): a manifold one of whose bodies has PHX_BODY_SENSOR keeps its contact points and gets
+// no joints.  The match writes -1 into its live slots and counts no fresh point there, so a joint it had stays unstamped and the clean-up
+// deletes it as it deletes any dead joint; the create pass skips it.  The rule is a parameter of the two kernels: NoSensors (a world
+// without an active flags column) is the code these kernels always were, BodySensors reads two 4-byte flag words per manifold.
+struct NoSensors {
+    static constexpr bool active = false;
+    using cps_pointer = const phx_contact_point*;
+    __device__ bool operator()(const phx_manifold&) const { return false; }
+};
+struct BodySensors {
+    static constexpr bool active = true;
+    using cps_pointer = phx_contact_point*;
+    const uint32_t* flags;             // per body (FlagsColumn)
+    __device__ bool operator()(const phx_manifold& m) const { return ((flags[m.body1] | flags[m.body2]) & PHX_BODY_SENSOR) != 0u; }
+};
+
+template <class Sensors>
+static __global__ void __launch_bounds__(256) k_joints_match(const phx_manifold* __restrict__ manifolds, int nm, typename Sensors::cps_pointer __restrict__ cps,
                                                              phx_contact_joint* __restrict__ joints, unsigned* __restrict__ seen, unsigned epoch,
-                                                             unsigned* __restrict__ new_count)
+                                                             unsigned* __restrict__ new_count, Sensors sensors)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nm; i += gridDim.x * blockDim.x) {
         const phx_manifold m = manifolds[i];
         unsigned fresh = 0;
+        if constexpr (Sensors::active) {
+            if (sensors(m)) {
+                for (int k = 0; k < m.point_count; ++k) cps[m.point_index + k].solver_index = -1;
+                new_count[i] = 0u;
+                continue;
+            }
+        }
         for (int k = 0; k < m.point_count; ++k) {
             const int si = cps[m.point_index + k].solver_index;
             if (si < 0) ++fresh;
@@ -421,10 +459,11 @@ struct JointDeadLoad {
 // Match, pass 2: new joints appended in manifold order, then point order (ref: World.cpp:108-114)
 // (the movers of the clean-up behind it do not depend on the new joints: when there are dead joints too, the last `mover_blocks`
 //  workgroups of the same launch compute them — one dispatch instead of two)
+template <class Sensors>
 static __global__ void __launch_bounds__(256) k_joints_create(const phx_manifold* __restrict__ manifolds, int nm, phx_contact_point* __restrict__ cps,
                                                               phx_contact_joint* __restrict__ joints, int nj_old, const unsigned* __restrict__ new_before,
                                                               int mover_blocks, const unsigned* __restrict__ dead_before, const unsigned* __restrict__ dead_total,
-                                                              int total, int* __restrict__ mover_pos)
+                                                              int total, int* __restrict__ mover_pos, Sensors sensors)
 {
     const int create_blocks = (int)gridDim.x - mover_blocks;
     if ((int)blockIdx.x >= create_blocks) {
@@ -433,6 +472,7 @@ static __global__ void __launch_bounds__(256) k_joints_create(const phx_manifold
     }
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nm; i += create_blocks * blockDim.x) {
         const phx_manifold m = manifolds[i];
+        if (sensors(m)) continue;                                         // (its slots are -1 and stay so)
         int at = nj_old + (int)new_before[i];
         for (int k = 0; k < m.point_count; ++k) {
             phx_contact_point& cp = cps[m.point_index + k];
@@ -562,6 +602,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
         record_to_world(b, out, to);
         if (cols.filters) out_cols.filters[to] = cols.filters[i];
         if (cols.materials) out_cols.materials[to] = cols.materials[i];
+        if (cols.flags) out_cols.flags[to] = cols.flags[i];
         if (out_cols.accel) {
             out_cols.accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;
