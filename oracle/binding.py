@@ -149,6 +149,13 @@ def lib():
         L.phxo_world_trace_records.restype = C.c_void_p
         L.phxo_world_trace_records.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.phxo_world_trace_summary.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.phxo_solver_set_trace.argtypes = [C.c_int]
+        L.phxo_solver_get_trace.restype = C.c_int
+        L.phxo_solver_trace_masks.argtypes = [C.c_void_p, C.c_int]
+        L.phxo_solver_trace_counts.argtypes = [C.c_void_p]
+        L.phxo_solver_trace_label_count.restype = C.c_int
+        L.phxo_solver_trace_label.restype = C.c_char_p
+        L.phxo_solver_trace_label.argtypes = [C.c_int]
         L.phxo_time_impulse_loop.restype = C.c_double
         L.phxo_time_impulse_loop.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _lib = L
@@ -504,6 +511,54 @@ def trace_pairs(bodies, points, counts):
     masks = np.zeros((len(cnt), 2), dtype=np.uint64)
     over = lib().phxo_trace_pairs(_p(b), _p(pts), _p(cnt), _p(masks), len(cnt))
     return pts, cnt, masks, over
+
+
+_solver_trace_labels = None
+
+
+def solver_trace_labels():
+    """The solver trace's label names, index = bit number (phx_oracle.h PHXO_ST_*)."""
+    global _solver_trace_labels
+    if _solver_trace_labels is None:
+        L = lib()
+        _solver_trace_labels = tuple(L.phxo_solver_trace_label(i).decode() for i in range(L.phxo_solver_trace_label_count()))
+    return _solver_trace_labels
+
+
+def solver_trace_names(mask):
+    """The set of label names in one mask word."""
+    return {n for i, n in enumerate(solver_trace_labels()) if int(mask) >> i & 1}
+
+
+class SolverTrace:
+    """The solver branch trace (phx_oracle.h PHXO_ST_*) around the oracle solves made inside the `with` block, over `nj` joints:
+    afterwards .masks (nj uint64: the OR of the labels each joint took), .counts ({label: visits, or groups for the g_ labels}, zeros
+    left out) and .reached (the set of labels with a count).  Process-wide, like set_arith: not nested."""
+
+    def __init__(self, nj):
+        self.masks = np.zeros(max(int(nj), 1), dtype=np.uint64)
+        self.counts, self.reached = {}, set()
+
+    def __enter__(self):
+        L = lib()
+        assert not L.phxo_solver_get_trace(), "the solver trace is process-wide: not nested"
+        L.phxo_solver_trace_masks(_p(self.masks), len(self.masks))
+        L.phxo_solver_set_trace(1)
+        return self
+
+    def __exit__(self, *exc):
+        L = lib()
+        c = np.zeros(len(solver_trace_labels()), dtype=np.uint64)
+        L.phxo_solver_trace_counts(_p(c))
+        L.phxo_solver_set_trace(0)
+        L.phxo_solver_trace_masks(None, 0)
+        self.counts = {n: int(v) for n, v in zip(solver_trace_labels(), c) if v}
+        self.reached = set(self.counts)
+        return False
+
+    def joint_labels(self, joints):
+        """the labels the given joints (indices) took between them"""
+        return solver_trace_names(np.bitwise_or.reduce(self.masks[np.asarray(joints, dtype=np.int64)])) if len(joints) else set()
 
 
 def solver_solve(bodies, cps, joints, solve_mode, island_mode, contact_iters, penetration_iters):

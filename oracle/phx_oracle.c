@@ -32,6 +32,54 @@ static inline phxo_vec2 perp2(phxo_vec2 a) { phxo_vec2 r = {-a.y, a.x}; return r
 static inline float sqlen2(phxo_vec2 a) { return a.x * a.x + a.y * a.y; }
 static inline float maxf_ref(float l, float r) { return l > r ? l : r; }                         /* ref: base/SIMD_Scalar.h:275-278 */
 
+/* ---- solver branch trace (phx_oracle.h: PHXO_ST_*).  Off, nothing below is touched; on, the marks only read what the solve computes.
+ * A visit's labels gather in `visit` and are counted once each when the visit is committed to its joint. ---- */
+static struct { int on; uint64_t visit; uint64_t counts[64]; uint64_t* masks; int nmasks; } g_st;
+static inline void smark(int label) { g_st.visit |= 1ull << label; }
+static void scommit(int joint)
+{
+    uint64_t v = g_st.visit;
+    g_st.visit = 0;
+    if (!g_st.on || !v) return;
+    if (joint >= 0 && g_st.masks && joint < g_st.nmasks) g_st.masks[joint] |= v;
+    for (; v; v &= v - 1) g_st.counts[__builtin_ctzll(v)]++;
+}
+static inline uint32_t fbits(float x) { uint32_t b; memcpy(&b, &x, 4); return b; }
+static inline int is_subnormal(float x) { uint32_t a = fbits(x) & 0x7fffffffu; return a != 0u && a < 0x00800000u; }
+static inline int is_negzero(float x) { return fbits(x) == 0x80000000u; }
+/* one half store: x -> r = the nearest half (f32_to_f16 below: zero up to 2^-25, subnormal below 2^-14, the low 13 bits dropped above) */
+static void smark_half(float x, float r)
+{
+    uint32_t a = fbits(x) & 0x7fffffffu, rb = fbits(r) & 0x7fffffffu;
+    if (a >= 0x477ff000u) return;                              /* infinity as a half, or NaN */
+    if (a != 0u && rb == 0u) smark(PHXO_ST_H_FLUSHED);
+    if (rb != 0u && rb < 0x38800000u) smark(PHXO_ST_H_SUBNORMAL);
+    if (a >= 0x38800000u) { if ((a & 0x1fffu) == 0x1000u) smark(PHXO_ST_H_TIE); }
+    else if (a >= 0x33000000u) {
+        int shift = 126 - (int)(a >> 23);
+        uint32_t m = (a & 0x7fffffu) | 0x800000u;
+        if ((m & ((1u << shift) - 1u)) == 1u << (shift - 1)) smark(PHXO_ST_H_TIE);
+    }
+}
+static const char* const strace_names[PHXO_ST_COUNT] = {
+    "depth_lt1", "depth_1_2", "depth_gt2", "cimN_zero", "cimF_zero",
+    "static_body1", "static_body2", "static_both", "static_moving", "disp_in_nonzero", "disp_in_negzero",
+    "warm_normal", "warm_friction", "cold",
+    "n_free", "n_clamp_strict", "n_clamp_tie",
+    "f_free", "f_clamp_pos", "f_clamp_neg", "f_limit_zero", "f_force_negzero", "f_force_eq_limit",
+    "prod_dn", "prod_df", "prod_both", "prod_none",
+    "i_subnormal", "i_skipped", "i_resumed",
+    "d_free", "d_clamped", "d_productive", "d_unproductive", "d_skipped", "d_subnormal",
+    "h_subnormal", "h_flushed", "h_tie",
+    "g_imp_early", "g_imp_full", "g_disp_first", "g_disp_early", "g_disp_full", "g_imp_outlasts", "g_disp_outlasts",
+};
+void phxo_solver_set_trace(int on) { g_st.on = on ? 1 : 0; g_st.visit = 0; if (on) memset(g_st.counts, 0, sizeof g_st.counts); }
+int phxo_solver_get_trace(void) { return g_st.on; }
+void phxo_solver_trace_masks(uint64_t* masks, int nj) { g_st.masks = masks; g_st.nmasks = masks ? nj : 0; }
+void phxo_solver_trace_counts(uint64_t counts[PHXO_ST_COUNT]) { memcpy(counts, g_st.counts, PHXO_ST_COUNT * sizeof(uint64_t)); }
+int phxo_solver_trace_label_count(void) { return PHXO_ST_COUNT; }
+const char* phxo_solver_trace_label(int label) { return label >= 0 && label < PHXO_ST_COUNT ? strace_names[label] : NULL; }
+
 /* IEEE binary16 round trip (round to nearest even), for the fp16 body-state ablation of BASELINE config 5.
  * Not part of the reference: it models what the HIP island kernel does when asked to keep body velocities in half. */
 static uint16_t f32_to_f16(float f)
@@ -63,7 +111,13 @@ static float f16_to_f32(uint16_t h)
     else x = sign | ((e + 112u) << 23) | (m << 13);
     float f; memcpy(&f, &x, 4); return f;
 }
-static inline float qh(int half, float x) { return half ? f16_to_f32(f32_to_f16(x)) : x; }
+static inline float qh(int half, float x)
+{
+    if (!half) return x;
+    float r = f16_to_f32(f32_to_f16(x));
+    if (g_st.on) smark_half(x, r);
+    return r;
+}
 float phxo_round_f16(float x) { return f16_to_f32(f32_to_f16(x)); }
 
 /* ---- narrowphase branch trace (phx_oracle.h: PHXO_T_*).  A NULL trace records nothing; no label changes what is computed. ---- */
@@ -367,6 +421,7 @@ typedef struct {
      * sw_col[p][b]  = the smallest colour index that was productive in that iteration. */
     int32_t *sw_iter[2], *sw_col[2];
     int32_t* statics; int nstatic;   /* the static bodies (prepare_bodies): the only ones whose words above are ever read */
+    uint8_t* was_skipped;            /* per slot, solver trace only: an impulse sweep of this island's solve has skipped the joint */
     phxo_solve_stats* st;
 } sctx;
 
@@ -439,6 +494,11 @@ static void refresh_one(pjoint* J, const sbody* imp, const sparams* par, const p
 
     float tx = -ny, ty = nx;
     refresh_limiter(&J->f, tx, ty, -tx, -ty, w1x, w1y, w2x, w2y, q1->im, q1->ii, q2->im, q2->ii);
+    if (g_st.on) {
+        smark(depth < delta_depth ? PHXO_ST_DEPTH_LT1 : depth > 2.0f * delta_depth ? PHXO_ST_DEPTH_GT2 : PHXO_ST_DEPTH_1_2);
+        if (J->n.cim == 0.f) smark(PHXO_ST_CIMN_ZERO);
+        if (J->f.cim == 0.f) smark(PHXO_ST_CIMF_ZERO);
+    }
 }
 
 void phxo_refresh_joint(const phxo_body* bodies, const phxo_contact_point* cps, const phxo_contact_joint* j, float out[30])
@@ -543,6 +603,10 @@ static int impulse_one(pjoint* J, sbody* imp, int simd_flipsign, float* out_dn, 
     dv = mul_sub(N->p1x, v1x, dv); dv = mul_sub(N->p1y, v1y, dv); dv = mul_sub(N->a1, w1, dv);
     dv = mul_sub(N->p2x, v2x, dv); dv = mul_sub(N->p2y, v2y, dv); dv = mul_sub(N->a2, w2, dv);
     float dn = dv * N->cim;
+    if (g_st.on) {
+        smark(dn > -J->n_acc ? PHXO_ST_N_FREE : dn < -J->n_acc ? PHXO_ST_N_CLAMP_STRICT : PHXO_ST_N_CLAMP_TIE);
+        if (is_subnormal(v1x) || is_subnormal(v1y) || is_subnormal(w1) || is_subnormal(v2x) || is_subnormal(v2y) || is_subnormal(w2)) smark(PHXO_ST_I_SUBNORMAL);
+    }
     dn = maxf_ref(dn, -J->n_acc);
     v1x = mul_add(N->c1x, dn, v1x); v1y = mul_add(N->c1y, dn, v1y); w1 = mul_add(N->c1a, dn, w1);
     v2x = mul_add(N->c2x, dn, v2x); v2y = mul_add(N->c2y, dn, v2y); w2 = mul_add(N->c2a, dn, w2);
@@ -557,6 +621,12 @@ static int impulse_one(pjoint* J, sbody* imp, int simd_flipsign, float* out_dn, 
     float limit = reaction * 0.3f;                                 /* kFrictionCoefficient, ref: Solver.cpp:9 */
     float signed_limit = simd_flipsign ? flipsign_simd(limit, force) : flipsign_scalar(limit, force);
     float adjusted = signed_limit - acc;
+    if (g_st.on) {
+        smark(!(fabsf(force) > limit) ? PHXO_ST_F_FREE : force < 0.f ? PHXO_ST_F_CLAMP_NEG : PHXO_ST_F_CLAMP_POS);
+        if (limit == 0.f) smark(PHXO_ST_F_LIMIT_ZERO);
+        if (is_negzero(force)) smark(PHXO_ST_F_FORCE_NEGZERO);
+        if (limit > 0.f && fabsf(force) == limit) smark(PHXO_ST_F_FORCE_EQ_LIMIT);
+    }
     if (fabsf(force) > limit) df = adjusted;
     J->f_acc += df;
     v1x = mul_add(F->c1x, df, v1x); v1y = mul_add(F->c1y, df, v1y); w1 = mul_add(F->c1a, df, w1);
@@ -565,6 +635,12 @@ static int impulse_one(pjoint* J, sbody* imp, int simd_flipsign, float* out_dn, 
     if (!(half && is_static[J->b1])) { b1->vx = qh(half, v1x); b1->vy = qh(half, v1y); b1->w = qh(half, w1); }
     if (!(half && is_static[J->b2])) { b2->vx = qh(half, v2x); b2->vy = qh(half, v2y); b2->w = qh(half, w2); }
     *out_dn = dn; *out_df = df;
+    if (g_st.on) {
+        int pn = fabsf(dn) > 1e-4f, pf = fabsf(df) > 1e-4f;
+        smark(pn ? (pf ? PHXO_ST_PROD_BOTH : PHXO_ST_PROD_DN) : (pf ? PHXO_ST_PROD_DF : PHXO_ST_PROD_NONE));
+        if (is_subnormal(dn) || is_subnormal(df) || is_subnormal(v1x) || is_subnormal(v1y) || is_subnormal(w1) || is_subnormal(v2x)
+            || is_subnormal(v2y) || is_subnormal(w2)) smark(PHXO_ST_I_SUBNORMAL);
+    }
     return maxf_ref(fabsf(dn), fabsf(df)) > 1e-4f;                  /* kProductiveImpulse, ref: Solver.cpp:8 */
 }
 
@@ -578,10 +654,19 @@ static int displacement_one(pjoint* J, sbody* disp, int half, const uint8_t* is_
     dv = mul_sub(N->p1x, v1x, dv); dv = mul_sub(N->p1y, v1y, dv); dv = mul_sub(N->a1, w1, dv);
     dv = mul_sub(N->p2x, v2x, dv); dv = mul_sub(N->p2y, v2y, dv); dv = mul_sub(N->a2, w2, dv);
     float di = dv * N->cim;
+    if (g_st.on) {
+        smark(di > -J->n_acc_disp ? PHXO_ST_D_FREE : PHXO_ST_D_CLAMPED);
+        if (is_subnormal(v1x) || is_subnormal(v1y) || is_subnormal(w1) || is_subnormal(v2x) || is_subnormal(v2y) || is_subnormal(w2)) smark(PHXO_ST_D_SUBNORMAL);
+    }
     di = maxf_ref(di, -J->n_acc_disp);
     v1x = mul_add(N->c1x, di, v1x); v1y = mul_add(N->c1y, di, v1y); w1 = mul_add(N->c1a, di, w1);
     v2x = mul_add(N->c2x, di, v2x); v2y = mul_add(N->c2y, di, v2y); w2 = mul_add(N->c2a, di, w2);
     J->n_acc_disp += di;
+    if (g_st.on) {
+        smark(fabsf(di) > 1e-4f ? PHXO_ST_D_PRODUCTIVE : PHXO_ST_D_UNPRODUCTIVE);
+        if (is_subnormal(di) || is_subnormal(v1x) || is_subnormal(v1y) || is_subnormal(w1) || is_subnormal(v2x) || is_subnormal(v2y)
+            || is_subnormal(w2)) smark(PHXO_ST_D_SUBNORMAL);
+    }
     if (!(half && is_static[J->b1])) { b1->vx = qh(half, v1x); b1->vy = qh(half, v1y); b1->w = qh(half, w1); }
     if (!(half && is_static[J->b2])) { b2->vx = qh(half, v2x); b2->vy = qh(half, v2y); b2->w = qh(half, w2); }
     return fabsf(di) > 1e-4f;
@@ -604,6 +689,14 @@ static int sweep(sctx* c, int begin, int end, int iter, int vn, int which)
             if (body_productive(c, arr, J->b1, s, iter) || body_productive(c, arr, J->b2, s, iter)) go = 1;
         }
         if (!which && c->st) c->st->joint_visits += lanes;
+        if (!go && g_st.on)
+            for (int l = 0; l < lanes; ++l) {
+                int s = g + l;
+                if (c->joint_index[s] < 0) continue;
+                if (!which) c->was_skipped[s] = 1;
+                smark(which ? PHXO_ST_D_SKIPPED : PHXO_ST_I_SKIPPED);
+                scommit(c->joint_index[s]);
+            }
         if (!go) continue;
         /* lanes of one group are body-disjoint (PrepareIndices), so lane order is immaterial */
         for (int l = 0; l < lanes; ++l) {
@@ -613,6 +706,10 @@ static int sweep(sctx* c, int begin, int end, int iter, int vn, int which)
             int productive;
             if (which) productive = displacement_one(J, arr, c->fp16, c->is_static);
             else { float dn, df; productive = impulse_one(J, arr, vn > 1, &dn, &df, c->fp16, c->is_static); if (c->st) c->st->joints_computed++; }
+            if (g_st.on) {
+                if (!which && c->was_skipped[s]) smark(PHXO_ST_I_RESUMED);
+                scommit(c->joint_index[s]);
+            }
             if (productive) {
                 mark_productive(c, arr, J->b1, s, iter);
                 mark_productive(c, arr, J->b2, s, iter);
@@ -748,12 +845,13 @@ static void ctx_alloc(sctx* c, int nb, int slots)
     c->statics = (int32_t*)malloc((nb + 1) * sizeof(int32_t));
     c->pj = (pjoint*)calloc(slots + 8, sizeof(pjoint));
     c->joint_index = (int32_t*)malloc((slots + 8) * sizeof(int32_t));
+    c->was_skipped = (uint8_t*)calloc(slots + 8, 1);
 }
 
 static void ctx_free(sctx* c)
 {
     free(c->imp); free(c->disp); free(c->par); free(c->is_static); for (int p = 0; p < 2; ++p) { free(c->sw_iter[p]); free(c->sw_col[p]); }
-    free(c->pj); free(c->joint_index); free(c->statics);
+    free(c->pj); free(c->joint_index); free(c->statics); free(c->was_skipped);
 }
 
 /* ref: Solver.cpp:509-521 CopyJoints into packed slots */
@@ -780,6 +878,21 @@ static void copy_joints_out(sctx* c, int begin, int end)
     }
 }
 
+/* solver trace: what RefreshJoints made of slot s (marked by refresh_one) and what its two bodies are as the island's solve begins */
+static void smark_joint_entry(const sctx* c, int s)
+{
+    const pjoint* J = &c->pj[s];
+    int s1 = c->is_static[J->b1], s2 = c->is_static[J->b2];
+    if (s1 && s2) smark(PHXO_ST_STATIC_BOTH); else if (s1) smark(PHXO_ST_STATIC1); else if (s2) smark(PHXO_ST_STATIC2);
+    for (int side = 0; side < 2; ++side) {
+        int b = side ? J->b2 : J->b1;
+        const sbody *v = &c->imp[b], *d = &c->disp[b];
+        if (c->is_static[b] && (v->vx != 0.f || v->vy != 0.f || v->w != 0.f)) smark(PHXO_ST_STATIC_MOVING);
+        if (d->vx != 0.f || d->vy != 0.f || d->w != 0.f) smark(PHXO_ST_DISP_IN_NONZERO);
+        if (is_negzero(d->vx) || is_negzero(d->vy) || is_negzero(d->w)) smark(PHXO_ST_DISP_IN_NEGZERO);
+    }
+}
+
 /* ref: Solver.cpp:130-215 SolveJointIsland<N>, workers = 0.  With workers = 0 the Sloppy batch
  * split (:138-139) runs the batches back to back in index order, which is the same sequence as
  * the single whole-island batch, so island_mode's sloppy bit does not change the result here. */
@@ -788,16 +901,29 @@ static void solve_island(sctx* c, int begin, int end, int group_offset, int n, i
     int vec_end = group_offset < end ? group_offset : end;
     int tail_begin = group_offset > begin ? group_offset : begin;
 
-    for (int s = begin; s < end; ++s) if (c->joint_index[s] >= 0) refresh_one(&c->pj[s], c->imp, c->par, c->cps);
-    for (int s = begin; s < end; ++s) if (c->joint_index[s] >= 0) prestep_one(&c->pj[s], c->imp, c->fp16, c->is_static);
+    for (int s = begin; s < end; ++s) if (c->joint_index[s] >= 0) {
+        refresh_one(&c->pj[s], c->imp, c->par, c->cps);
+        if (g_st.on) { smark_joint_entry(c, s); c->was_skipped[s] = 0; scommit(c->joint_index[s]); }
+    }
+    for (int s = begin; s < end; ++s) if (c->joint_index[s] >= 0) {
+        if (g_st.on) {
+            const pjoint* J = &c->pj[s];
+            if (J->n_acc != 0.f) smark(PHXO_ST_WARM_NORMAL);
+            if (J->f_acc != 0.f) smark(PHXO_ST_WARM_FRICTION);
+            if (J->n_acc == 0.f && J->f_acc == 0.f) smark(PHXO_ST_COLD);
+        }
+        prestep_one(&c->pj[s], c->imp, c->fp16, c->is_static);
+        if (g_st.on) scommit(c->joint_index[s]);
+    }
 
-    int it;
+    int it, imp_it, disp_it;
     reset_static_words(c);
     for (it = 0; it < contact_iters; ++it) {
         int p = sweep(c, begin, vec_end, it, n, 0);
         p |= sweep(c, tail_begin, end, it, 1, 0);
         if (!p) { ++it; break; }                                      /* ref: Solver.cpp:189 */
     }
+    imp_it = it;
     if (c->st && it > c->st->impulse_iterations) c->st->impulse_iterations = it;
     reset_static_words(c);
     for (it = 0; it < pen_iters; ++it) {
@@ -805,7 +931,15 @@ static void solve_island(sctx* c, int begin, int end, int group_offset, int n, i
         p |= sweep(c, tail_begin, end, it, 1, 1);
         if (!p) { ++it; break; }                                      /* ref: Solver.cpp:210 */
     }
+    disp_it = it;
     if (c->st && it > c->st->displacement_iterations) c->st->displacement_iterations = it;
+    if (g_st.on && end > begin) {
+        if (contact_iters > 0) smark(imp_it < contact_iters ? PHXO_ST_G_IMP_EARLY : PHXO_ST_G_IMP_FULL);
+        if (pen_iters > 0) smark(disp_it == pen_iters ? PHXO_ST_G_DISP_FULL : disp_it == 1 ? PHXO_ST_G_DISP_FIRST : PHXO_ST_G_DISP_EARLY);
+        if (imp_it > disp_it) smark(PHXO_ST_G_IMP_OUTLASTS);
+        if (disp_it > imp_it) smark(PHXO_ST_G_DISP_OUTLASTS);
+        scommit(-1);
+    }
 }
 
 void phxo_solver_solve(phxo_body* bodies, int nb, const phxo_contact_point* cps, phxo_contact_joint* joints, int nj,
@@ -885,7 +1019,9 @@ void phxo_solver_solve_ordered(phxo_body* bodies, int nb, const phxo_contact_poi
         phxo_contact_joint* j2 = (phxo_contact_joint*)malloc((nj + 1) * sizeof(phxo_contact_joint));
         memcpy(b2, bodies, nb * sizeof(phxo_body)); memcpy(j2, joints, nj * sizeof(phxo_contact_joint));
         phxo_solve_stats s2;
+        int traced = g_st.on; g_st.on = 0;                        /* (the scratch run is not traced) */
         phxo_solver_solve_ordered(b2, nb, cps, j2, nj, order, colour_offsets, ncolours, contact_iters, pen_iters, PHXO_STAG_COLOUR_SYNC, &s2);
+        g_st.on = traced;
         solve_island(&c, 0, nj, nj, 1, contact_iters, pen_iters);
         stats->stag_events = stats->joints_computed - s2.joints_computed;
         free(b2); free(j2);
@@ -942,13 +1078,15 @@ void phxo_solver_solve_grouped_fp16(phxo_body* bodies, int nb, const phxo_contac
         for (int k = 0; k < c.nstatic; ++k) { c.imp[c.statics[k]].tag = -1; c.disp[c.statics[k]].tag = -1; }
         c.fp16 = g < fp16_groups;
         if (c.fp16) {       /* the group's working copy of its bodies is binary16 from the start (the statics' copy is private) */
-            for (int s = b; s < e; ++s)
+            for (int s = b; s < e; ++s) {
                 for (int side = 0; side < 2; ++side) {
                     int body = side ? c.pj[s].b2 : c.pj[s].b1;
                     if (c.is_static[body]) continue;
                     c.imp[body].vx = qh(1, c.imp[body].vx); c.imp[body].vy = qh(1, c.imp[body].vy); c.imp[body].w = qh(1, c.imp[body].w);
                     c.disp[body].vx = qh(1, c.disp[body].vx); c.disp[body].vy = qh(1, c.disp[body].vy); c.disp[body].w = qh(1, c.disp[body].w);
                 }
+                if (g_st.on) scommit(c.joint_index[s]);
+            }
             /* static bodies: rounded copies for the duration of the group, originals restored afterwards */
             sbody* keep_i = (sbody*)malloc((nb + 1) * sizeof(sbody));
             sbody* keep_d = (sbody*)malloc((nb + 1) * sizeof(sbody));
@@ -957,6 +1095,7 @@ void phxo_solver_solve_grouped_fp16(phxo_body* bodies, int nb, const phxo_contac
                 c.imp[i].vx = qh(1, c.imp[i].vx); c.imp[i].vy = qh(1, c.imp[i].vy); c.imp[i].w = qh(1, c.imp[i].w);
                 c.disp[i].vx = qh(1, c.disp[i].vx); c.disp[i].vy = qh(1, c.disp[i].vy); c.disp[i].w = qh(1, c.disp[i].w);
             }
+            g_st.visit = 0;                                           /* (the statics' private copies belong to no joint) */
             solve_island(&c, b, e, e, 1, contact_iters, pen_iters);
             for (int i = 0; i < nb; ++i) if (c.is_static[i]) { c.imp[i] = keep_i[i]; c.disp[i] = keep_d[i]; }
             free(keep_i); free(keep_d);

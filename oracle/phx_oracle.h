@@ -237,6 +237,48 @@ void phxo_world_set_trace(phxo_world* w, int on);
 const phxo_trace_record* phxo_world_trace_records(phxo_world* w, int* n);
 void phxo_world_trace_summary(phxo_world* w, uint64_t mask[2], uint32_t counts[PHXO_T_COUNT]);
 
+/* ---- solver branch trace ----
+ * Which arms of RefreshJoints / PreStepJoints / the impulse and displacement visits (ref: Solver.cpp:592-1015) a solve took, and on what
+ * kind of values.  Process-wide like phxo_set_arith, off by default; it works through phxo_solver_solve, _ordered, _grouped and
+ * _grouped_fp16 (and the world's solves).  Marking a label changes nothing that is computed.  Per label the trace counts joint visits
+ * (a joint's refresh, its PreStep and every visit of a sweep are one visit each; the body and refresh labels are therefore counted once
+ * per joint and solve), the per-group labels count groups (islands).  A caller-supplied mask per joint receives the OR of the labels the
+ * joint took (the per-group labels never appear there).
+ *   depth_*            the refresh's depth class: < deltaDepth (dst -= maxPenetrationVelocity), 1..2, > 2 (dstDisplacingVelocity > 0)
+ *   static_moving      a static body of the joint has a nonzero velocity word
+ *   disp_in_*          a displacing-velocity word of one of the joint's bodies is nonzero / is -0.0 when its group's solve begins
+ *   warm_* / cold      the joint's accumulated impulses on entry (-0.0 counts as no impulse)
+ *   n_*                dn against -accN: above (free), below (clamped strictly), equal (clamped on a tie)
+ *   f_*                the friction clamp not taken / taken with force > 0 / with force < 0; limit == 0; force == -0.0; |force| == limit > 0
+ *   prod_*             which of |dn|, |df| passes kProductiveImpulse
+ *   *_subnormal        a subnormal among the visit's impulse(s) or the six velocity words it loads or stores
+ *   i_resumed          evaluated in a sweep after having been skipped in an earlier sweep of the same solve
+ *   h_*                (fp16 groups) a half store whose result is subnormal as a half / whose nonzero value became zero / whose value lay
+ *                      exactly between two halves; the rounding of a group's bodies on entry counts for every joint that holds the body
+ *                      (a body is rounded again for each of its joints: only h_subnormal can repeat, a half rounds to itself) */
+enum {
+    PHXO_ST_DEPTH_LT1 = 0, PHXO_ST_DEPTH_1_2, PHXO_ST_DEPTH_GT2, PHXO_ST_CIMN_ZERO, PHXO_ST_CIMF_ZERO,
+    PHXO_ST_STATIC1, PHXO_ST_STATIC2, PHXO_ST_STATIC_BOTH, PHXO_ST_STATIC_MOVING, PHXO_ST_DISP_IN_NONZERO, PHXO_ST_DISP_IN_NEGZERO,
+    PHXO_ST_WARM_NORMAL, PHXO_ST_WARM_FRICTION, PHXO_ST_COLD,
+    PHXO_ST_N_FREE, PHXO_ST_N_CLAMP_STRICT, PHXO_ST_N_CLAMP_TIE,
+    PHXO_ST_F_FREE, PHXO_ST_F_CLAMP_POS, PHXO_ST_F_CLAMP_NEG, PHXO_ST_F_LIMIT_ZERO, PHXO_ST_F_FORCE_NEGZERO, PHXO_ST_F_FORCE_EQ_LIMIT,
+    PHXO_ST_PROD_DN, PHXO_ST_PROD_DF, PHXO_ST_PROD_BOTH, PHXO_ST_PROD_NONE,
+    PHXO_ST_I_SUBNORMAL, PHXO_ST_I_SKIPPED, PHXO_ST_I_RESUMED,
+    PHXO_ST_D_FREE, PHXO_ST_D_CLAMPED, PHXO_ST_D_PRODUCTIVE, PHXO_ST_D_UNPRODUCTIVE, PHXO_ST_D_SKIPPED, PHXO_ST_D_SUBNORMAL,
+    PHXO_ST_H_SUBNORMAL, PHXO_ST_H_FLUSHED, PHXO_ST_H_TIE,
+    PHXO_ST_JOINT_LABELS,                                  /* the labels above are per joint, the ones below per group */
+    PHXO_ST_G_IMP_EARLY = PHXO_ST_JOINT_LABELS, PHXO_ST_G_IMP_FULL,            /* impulse sweeps: fewer than ci / ci of them */
+    PHXO_ST_G_DISP_FIRST, PHXO_ST_G_DISP_EARLY, PHXO_ST_G_DISP_FULL,           /* displacement sweeps: 1 < pi / 2 .. pi - 1 / pi */
+    PHXO_ST_G_IMP_OUTLASTS, PHXO_ST_G_DISP_OUTLASTS,                           /* more impulse sweeps than displacement sweeps / fewer */
+    PHXO_ST_COUNT
+};
+void        phxo_solver_set_trace(int on);                 /* turning it on clears the counts */
+int         phxo_solver_get_trace(void);
+void        phxo_solver_trace_masks(uint64_t* masks, int nj);      /* nj words that later solves OR into, by joint index; NULL detaches */
+void        phxo_solver_trace_counts(uint64_t counts[PHXO_ST_COUNT]);
+int         phxo_solver_trace_label_count(void);
+const char* phxo_solver_trace_label(int label);
+
 /* multi-threaded timing harness for bench.py's cpu_baseline leg: Single-Sloppy-style 512-joint
  * batches over `threads` pthreads (races on shared bodies exactly like the reference's sloppy
  * modes; results are NOT used for parity). Returns seconds spent in the impulse loop. */

@@ -616,7 +616,7 @@ def _random_state(rng, nb, nj, static_frac, dup_ids=False, hub=0, units=False):
     bodies["inv_inertia"][static] = 0
     bodies["pos"]["x"] = rng.uniform(-100, 100, nb)
     bodies["pos"]["y"] = rng.uniform(-100, 100, nb)
-    bodies["velocity"]["x"] = np.where(static, 0.0, rng.uniform(-1, 1, nb))      # (+0.0 exactly: see DESIGN §4.3 on -0.0 statics)
+    bodies["velocity"]["x"] = np.where(static, 0.0, rng.uniform(-1, 1, nb))      # (+0.0 exactly: see DESIGN §9 item 7 on -0.0 statics)
     bodies["velocity"]["y"] = np.where(static, 0.0, rng.uniform(-1, 1, nb))
     b1 = rng.integers(0, nb, nj)
     b2 = (b1 + rng.integers(1, nb, nj)) % nb                           # never the same body twice
