@@ -721,6 +721,76 @@ int  phx_world_get_contact_markers_device(phx_world* w, void* d_out, int32_t cap
  * solver_index points back at it; PHX_ERR_INVALID otherwise.  Any number of bodies (the world's previous content is dropped). */
 int  phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,
                          const phx_contact_point* contact_points, int32_t contact_point_count, const phx_contact_joint* joints, int32_t joint_count);
+/* SNAPSHOTS — save a whole world, try something, put it back (rollback, "try N actions from the same state", an environment reset, a saved
+ * game), without the state leaving HBM.  A phx_snapshot owns device memory on its device; it grows geometrically and every save reuses it.
+ *   - What a snapshot holds: the complete state World::Update carries from step to step, plus the per-body columns:
+ *       the bodies' 128-byte records as phx_world_get_bodies would return them at the save (a record the steps have left stale is brought up
+ *       to date from the resident arrays on the way; pending accelerations ride in the records, as they do through phx_world_set_state);
+ *       the manifolds, their contact-point slots, the joints with their warm-start impulses;
+ *       the three optional columns (collision filters, materials, body flags), each with its "ever set" bit;
+ *       the touch events' baseline B AS IT IS (not T(state): the next phx_world_contact_events after a load reports what it would have
+ *       reported had the save and the load never happened).
+ *   - What it does NOT hold, and a load leaves alone: gravity, the shard and the communicator, phase timing, the paths chosen from the
+ *     environment (PHX_QUERY_PATH, PHX_CONTACT_PATH, ...), the fp16 body-state ablation and every other setting of the world's solver.
+ *     A snapshot forked into a fresh world needs its gravity set by the caller.
+ *   - Definition of load: after phx_world_load(w, s) the world is exactly what these calls would have made of it, byte for byte in every
+ *     getter and in every later step:
+ *       1. phx_world_set_state of the four saved arrays;
+ *       2. phx_world_set_collision_filters of the saved filters, if that column was active in s;
+ *       3. phx_world_set_materials of the saved materials, if that column was active in s;
+ *       4. phx_world_set_body_flags of the saved flags, if that column was active in s;
+ *       5. B := the saved B.
+ *     A column that was inactive in s is the default for every body afterwards.  Everything set_state resets is reset: the broadphase's
+ *     pair set becomes the saved manifolds' pairs, the query and contact indexes are rebuilt by their next use, and the cached solver
+ *     schedule is rebuilt at the next step (phx_solve_stats.recoloured != 0).  s is unchanged and can be loaded again, into any world on
+ *     its device (a FORK: world A saves, world B loads).
+ *   - Rules, those of the edits, the removal and the spawn: between steps only (PHX_ERR_STATE inside pre_solve .. finish_step or
+ *     step_begin .. step_end); a sharded or communicator-attached world gets PHX_ERR_STATE from both calls; a snapshot that was never
+ *     filled gives PHX_ERR_STATE from load, counts, blob_bytes and export; a snapshot of another device gives PHX_ERR_INVALID; a NULL
+ *     handle gives PHX_ERR_INVALID.  Host-staged bodies (before the first step, after add_body / set_body_static /
+ *     set_body_inverse_mass) are uploaded before a save, as the removal uploads them; a load drops them with the rest of the old world.
+ *     A save into a filled snapshot overwrites it.  A call that fails leaves the world's and the snapshot's contents as they were.
+ *   - Where the host waits: nowhere new.  Both calls are queued on phx_world_stream(w): one kernel each (and, for a load, the reset of
+ *     the pair set).  They wait only to settle an unverified solve, as the removal does, and where a buffer has to grow or the pair
+ *     set's table is replaced.  The counts are on the host between steps, so nothing is read back and nothing of the state crosses PCIe.
+ *     Between worlds: a save records an event that a later load's stream waits for, a load records one that the next save into s, export,
+ *     import and destroy wait for — no host wait, no extra stream.
+ *   - The blob: the one form that leaves the device (disk, another machine, another device).  phx_snapshot_export writes it, phx_snapshot_import
+ *     checks it completely before anything is allocated or copied and fills the snapshot from it.  Little-endian; every section starts at a
+ *     multiple of 16 bytes from the start of the blob and the bytes between sections are zero:
+ *          0  char[8]   "PHXSNAP\0"                  8  uint32  layout version (1)         12  uint32  header bytes (128)
+ *         16  int32     bodies n                     20  int32   manifolds m                24  int32   contact points (2 m)
+ *         28  int32     joints j                     32  uint32  column bits: 1 filters, 2 materials, 4 flags (clear: all default, no section)
+ *         36  int32     baseline pairs t             40  uint64  total bytes                48  uint64[8] section offsets     112  16 zero bytes
+ *       sections, in this order, the first at 128, each next one at the end of the one before rounded up to 16, the total the last end
+ *       rounded up to 16:  bodies n x 128 (phx_rigid_body) | manifolds m x 16 | contact points 2m x 32 | joints j x 20 |
+ *       filters n x 16 ({category, mask, group, 0}: the device's own granule) | materials n x 8 | flags n x 4 |
+ *       baseline t x 8 (uint64 (body1 << 32) | body2, strictly increasing).
+ *     The device side of a snapshot has this layout too: export and import are one copy each.  phx_snapshot_blob_check is the single
+ *     validator (host only): the header, every size and offset against `bytes` in 64-bit arithmetic that cannot overflow, everything
+ *     phx_world_set_state checks, the ranges the setters enforce (friction finite in [0, 1e6], restitution in [0, 1], no unknown flag bit,
+ *     a filter's fourth word zero, zero bytes between the sections) and the baseline strictly increasing with indices in range; PHX_ERR_INVALID with a message
+ *     (phx_last_error) that names the first violated rule.  phx_snapshot_blob_pack makes a blob from host arrays — what the getters
+ *     return — so a state from elsewhere can become a snapshot: a NULL column means every body has the default, a NULL baseline means
+ *     T(state), as phx_world_set_state makes it; baseline_pairs are {body1, body2} int32 pairs.  *bytes always receives the size;
+ *     PHX_ERR_CAPACITY when cap is smaller (blob may then be NULL).
+ * Costs and the data path: DESIGN.md. */
+typedef struct phx_snapshot phx_snapshot;
+int  phx_snapshot_create(phx_snapshot** out, int device);      /* empty; owns device memory, grows geometrically, reused by every save */
+void phx_snapshot_destroy(phx_snapshot* s);
+int  phx_world_save(phx_world* w, phx_snapshot* s);             /* s := the world */
+int  phx_world_load(phx_world* w, phx_snapshot* s);             /* the world := s (s unchanged; any world on s's device) */
+int  phx_snapshot_counts(phx_snapshot* s, int32_t* bodies, int32_t* manifolds, int32_t* contact_points, int32_t* joints);
+int  phx_snapshot_blob_bytes(phx_snapshot* s, size_t* bytes);
+int  phx_snapshot_export(phx_snapshot* s, void* blob, size_t cap);          /* device -> one host blob */
+int  phx_snapshot_import(phx_snapshot* s, const void* blob, size_t bytes);  /* checked completely first */
+/* host only, no device needed */
+int  phx_snapshot_blob_check(const void* blob, size_t bytes);
+int  phx_snapshot_blob_pack(const phx_rigid_body* bodies, int32_t body_count, const phx_manifold* manifolds, int32_t manifold_count,
+                            const phx_contact_point* cps, int32_t cp_count, const phx_contact_joint* joints, int32_t joint_count,
+                            const phx_collision_filter* filters, const phx_material* materials, const uint32_t* flags,
+                            const int32_t* baseline_pairs, int32_t baseline_count,
+                            void* blob, size_t cap, size_t* bytes);
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);
 /* handles owned by the world (for stage-level queries after an update) */

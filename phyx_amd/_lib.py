@@ -196,6 +196,16 @@ _SIGNATURES = {
     "phx_reslab_plan": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp]),
     "phx_reslab_cuts": (C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _vp, _vp]),
     "phx_world_synchronize": (C.c_int, [_vp]),
+    "phx_snapshot_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
+    "phx_snapshot_destroy": (None, [_vp]),
+    "phx_world_save": (C.c_int, [_vp, _vp]),
+    "phx_world_load": (C.c_int, [_vp, _vp]),
+    "phx_snapshot_counts": (C.c_int, [_vp] + [C.POINTER(_i32)] * 4),
+    "phx_snapshot_blob_bytes": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
+    "phx_snapshot_export": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "phx_snapshot_import": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "phx_snapshot_blob_check": (C.c_int, [_vp, C.c_size_t]),
+    "phx_snapshot_blob_pack": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
 

@@ -558,6 +558,76 @@ class Collider:
         return st
 
 
+class Snapshot:
+    """A saved world in device memory (phx_snapshot): filled by World.save or from_bytes, emptied into any world of its device by
+    World.load, as often as wanted.  Its memory grows geometrically and is reused by every save."""
+
+    def __init__(self, device=0):
+        self.L = _lib.load()
+        h = C.c_void_p()
+        check(self.L.phx_snapshot_create(C.byref(h), device))
+        self.h = h
+        self.device = device
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.phx_snapshot_destroy(self.h)
+            self.h = None
+
+    @property
+    def counts(self):
+        """(bodies, manifolds, contact points, joints) of the saved world."""
+        v = [C.c_int32() for _ in range(4)]
+        check(self.L.phx_snapshot_counts(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def to_bytes(self):
+        """The snapshot as one versioned blob (phx_snapshot_export): the form for disk or another machine."""
+        n = C.c_size_t(0)
+        check(self.L.phx_snapshot_blob_bytes(self.h, C.byref(n)))
+        buf = C.create_string_buffer(n.value)
+        check(self.L.phx_snapshot_export(self.h, buf, n.value))
+        return buf.raw
+
+    @classmethod
+    def from_bytes(cls, blob, device=0):
+        """A snapshot filled from a blob (phx_snapshot_import); the blob is checked completely first (PhxError if it is not valid)."""
+        snap = cls(device)
+        blob = bytes(blob)
+        check(snap.L.phx_snapshot_import(snap.h, blob, len(blob)))
+        return snap
+
+    @staticmethod
+    def check_bytes(blob):
+        """phx_snapshot_blob_check on the host: raises PhxError naming the first violated rule."""
+        blob = bytes(blob)
+        check(_lib.load().phx_snapshot_blob_check(blob, len(blob)))
+
+    @staticmethod
+    def pack(bodies, manifolds, contact_points, joints, filters=None, materials=None, flags=None, baseline=None):
+        """phx_snapshot_blob_pack on the host: a blob from what the getters return.  A column left None is the default for every body;
+        baseline: (T, 2) int32 pairs sorted by (body1, body2), or None for the touching pairs of the manifolds."""
+        L = _lib.load()
+        b = np.ascontiguousarray(bodies, dtype=rigid_body_dtype); m = np.ascontiguousarray(manifolds, dtype=manifold_dtype)
+        c = np.ascontiguousarray(contact_points, dtype=contact_point_dtype); j = np.ascontiguousarray(joints, dtype=contact_joint_dtype)
+        f = None if filters is None else np.ascontiguousarray(filters, dtype=collision_filter_dtype)
+        mt = None if materials is None else np.ascontiguousarray(materials, dtype=material_dtype)
+        fl = None if flags is None else np.ascontiguousarray(flags, dtype=np.uint32)
+        for name, col in (("filters", f), ("materials", mt), ("flags", fl)):
+            if col is not None and col.shape != (len(b),):
+                raise ValueError("Snapshot.pack: %s must have one entry per body" % name)
+        base = None if baseline is None else np.ascontiguousarray(baseline, dtype=np.int32).reshape(-1, 2)
+        args = (_ptr(b), len(b), _ptr(m), len(m), _ptr(c), len(c), _ptr(j), len(j), _ptr(f), _ptr(mt), _ptr(fl),
+                _ptr(base), 0 if base is None else len(base))
+        n = C.c_size_t(0)
+        st = L.phx_snapshot_blob_pack(*args, None, 0, C.byref(n))
+        if st != _lib.PHX_ERR_CAPACITY:
+            check(st)
+        buf = C.create_string_buffer(max(n.value, 1))
+        check(L.phx_snapshot_blob_pack(*args, buf, n.value, C.byref(n)))
+        return buf.raw[:n.value]
+
+
 class World:
     """Device-backed World (ref: World.h:9-36)."""
 
@@ -686,6 +756,26 @@ class World:
         b = np.ascontiguousarray(bodies, dtype=rigid_body_dtype); m = np.ascontiguousarray(manifolds, dtype=manifold_dtype)
         c = np.ascontiguousarray(contact_points, dtype=contact_point_dtype); j = np.ascontiguousarray(joints, dtype=contact_joint_dtype)
         check(self.L.phx_world_set_state(self.h, _ptr(b), len(b), _ptr(m), len(m), _ptr(c), len(c), _ptr(j), len(j)))
+
+    # ---- snapshots (include/phyx_amd.h SNAPSHOTS; the blob's specification: tests/snapshot_spec.py) ----
+    def save(self, snap=None):
+        """snap := this world (phx_world_save), queued on the world's stream; a new Snapshot on the world's device when none is given.
+        Returns the snapshot.  It holds the state and the per-body columns, not settings such as gravity."""
+        if snap is None:
+            snap = Snapshot(self.device)
+        check(self.L.phx_world_save(self.h, snap.h))
+        return snap
+
+    def load(self, snap):
+        """This world := snap (phx_world_load): exactly what set_state of the saved arrays, the three column setters and the saved
+        touch-event baseline would have made of it.  snap is unchanged; gravity and every other setting of this world stay."""
+        check(self.L.phx_world_load(self.h, snap.h))
+
+    def fork(self):
+        """A new world on the same device with the same gravity, loaded from a fresh save of this one: both step identically from here."""
+        other = World(self.device, self.gravity)
+        other.load(self.save())
+        return other
 
     # ---- edits and gathers between steps (include/phyx_amd.h: phx_world_add_accelerations ...) ----
     def _indices(self, bodies, what):

@@ -51,6 +51,12 @@ public:
     // caller has read that count back, baseline_remapped(count) makes it B (a removal that changes nothing does not call it)
     int remap_baseline(const int* d_remap, unsigned* d_count, hipStream_t s);
     void baseline_remapped(unsigned count) { std::swap(base_, base_spare_); base_n_ = (int)count; }
+    // snapshots (world.hip save / load): B as it is — its keys in HBM and their number; a load makes room (the old B goes), queues the
+    // copy itself and then says how many keys B has
+    unsigned long long* baseline() const { return base_.p; }
+    int baseline_count() const { return base_n_; }
+    int reserve_baseline(size_t count) { return base_.reserve(std::max<size_t>(count, 1)); }
+    void baseline_replaced(int count) { base_n_ = count; }
 
 private:
     int scan_contacts(const ContactCache& c, const int* d_bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total,

@@ -1,0 +1,64 @@
+// snapshot.h — a saved world in HBM (include/phyx_amd.h SNAPSHOTS): one device allocation in the blob's own layout
+// (snapshot_blob.h, bytes [128, total)), filled and emptied by the two kernels of snapshot_kernels.h on the stream of the world
+// that saves or loads.  The World (world.hip) hands out its arrays as a SnapshotWorld; everything else lives here: the layout, the
+// growth of the allocation, and the two events that order a save by one world against a load by another without a host wait.
+#pragma once
+
+#include "body_view.h"
+#include "snapshot_blob.h"
+
+namespace phx {
+
+// a world's arrays as a save reads them / a load writes them (the load's buffers hold at least `counts` elements each)
+struct SnapshotWorld {
+    phx_rigid_body* records;
+    WorldBodies resident;
+    bool records_stale;                  // save: the records must be refreshed from the resident arrays on the way
+    float4* accel;                       // the pending accelerations' own array (load: null unless the snapshot carries some)
+    phx_manifold* manifolds;
+    phx_contact_point* cps;
+    phx_contact_joint* joints;
+    uint4* filters; float2* materials; uint32_t* flags;      // a column the counts' bits do not name is not looked at
+    unsigned long long* baseline;
+    uint2* pairs;                        // load: receives the manifolds' body pairs
+    SnapCounts counts;                   // save: the world's
+    bool accel_pending;                  // save: some record may carry an acceleration
+};
+
+class Snapshot {
+public:
+    explicit Snapshot(int device) : device_(device) {}
+    ~Snapshot();
+    Snapshot(const Snapshot&) = delete;
+    Snapshot& operator=(const Snapshot&) = delete;
+    int init();
+    int device() const { return device_; }
+    bool filled() const { return filled_; }
+    const SnapCounts& counts() const { return counts_; }
+    bool accel_pending() const { return accel_pending_; }
+
+    int save(const SnapshotWorld& w, hipStream_t stream);      // queued on `stream` behind the loads that still read the old contents
+    int load(const SnapshotWorld& w, hipStream_t stream);      // queued on `stream` behind the save that wrote the contents
+    int blob_bytes(size_t* bytes) const;
+    int export_blob(void* blob, size_t cap);
+    int import_blob(const void* blob, size_t bytes);
+
+private:
+    int settle();                        // the host waits for the queued save and loads (export, import, destroy)
+    int refuse_empty(const char* what) const;
+
+    int device_;
+    DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save
+    bool filled_ = false, accel_pending_ = false;
+    SnapCounts counts_;
+    SnapLayout layout_ = {};
+    hipEvent_t saved_ = nullptr, loaded_ = nullptr;      // recorded behind the last save / the last load
+    bool saved_pending_ = false, loaded_pending_ = false;
+};
+
+} // namespace phx
+
+struct phx_snapshot {
+    phx::Snapshot impl;
+    explicit phx_snapshot(int device) : impl(device) {}
+};

@@ -14,6 +14,7 @@
 #include "world_kernels.h"
 #include "query.h"
 #include "contact.h"
+#include "snapshot.h"
 
 #include <algorithm>
 #include <chrono>
@@ -150,6 +151,9 @@ public:
     int set_state(const phx_rigid_body* bodies, int body_count, const phx_manifold* manifolds, int manifold_count,
                   const phx_contact_point* cps, int cp_count, const phx_contact_joint* joints, int joint_count);
     int get_slab_state(const long long* global_index, int count, SlabState* out);      // this world as a re-slab hands it over (reslab.h)
+    // snapshots (phx_world_save / phx_world_load): between steps; the whole state stays in HBM
+    int save(Snapshot& s);
+    int load(Snapshot& s);
     // edits and gathers between steps (phx_world_add_accelerations ... phx_world_get_poses_device)
     enum Edit { EDIT_ACCELERATIONS, EDIT_VELOCITIES, EDIT_POSES };
     int edit(Edit kind, const int* bodies, const float* values, int count);
@@ -222,6 +226,8 @@ private:
     int solve_and_integrate(float dt, const phx_config& cfg);
     int scratch_for(int n);
     int forget_step_history();           // the bookkeeping a restored or compacted contact cache starts without
+    int snapshot_guard(const char* what, const Snapshot& s) const;      // the refusals save and load share
+    SnapshotWorld snapshot_view();       // the world's arrays as a save reads them / a load writes them
 
     int device_;
     DeviceBroadphase& broadphase_;
@@ -916,19 +922,8 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     PHX_REQUIRE(body_count >= 0 && manifold_count >= 0 && joint_count >= 0 && cp_count == 2 * manifold_count, "bad counts (two contact-point slots per manifold)");
     PHX_REQUIRE((body_count == 0 || bodies) && (manifold_count == 0 || (manifolds && cps)) && (joint_count == 0 || joints), "null array");
     PHX_REQUIRE(shard_count == 1 && !comm_, "a sharded world cannot be restored");
-    // the invariants the step's kernels rely on
-    for (int i = 0; i < manifold_count; ++i) {
-        const phx_manifold& m = manifolds[i];
-        PHX_REQUIRE((unsigned)m.body1 < (unsigned)body_count && (unsigned)m.body2 < (unsigned)body_count, "manifold: body index out of range");
-        PHX_REQUIRE(m.point_index == 2 * i && m.point_count >= 0 && m.point_count <= 2, "manifold: its contact points are slots 2i, 2i + 1");
-    }
-    for (int j = 0; j < joint_count; ++j) {
-        const phx_contact_joint& q = joints[j];
-        PHX_REQUIRE((unsigned)q.contact_point_index < (unsigned)cp_count, "joint: contact point out of range");
-        const phx_manifold& m = manifolds[q.contact_point_index / 2];
-        PHX_REQUIRE(q.body1 == m.body1 && q.body2 == m.body2, "joint: bodies differ from its manifold's");
-        PHX_REQUIRE(cps[q.contact_point_index].solver_index == j, "joint: its contact point does not point back at it");
-    }
+    // the invariants the step's kernels rely on (shared with the snapshot blob's validator: snapshot_blob.h)
+    if (const char* bad = snap_check_state(body_count, manifolds, manifold_count, cps, cp_count, joints, joint_count)) { set_error("%s", bad); return PHX_ERR_INVALID; }
     PHX_TRY(synchronize());
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
@@ -965,6 +960,80 @@ int World::forget_step_history()
     if (joint_seen_.p) { PHX_HIP(hipMemsetAsync(joint_seen_.p, 0, joint_seen_.cap * sizeof(unsigned), stream_)); }
     joint_epoch_ = 0;
     return PHX_OK;
+}
+
+// ---- snapshots ---------------------------------------------------------------------------------------------------------------------
+// Defined in include/phyx_amd.h SNAPSHOTS: a load leaves exactly the world that phx_world_set_state of the saved arrays, the three
+// column setters and B := saved B would have made.  Here the state never leaves HBM: one kernel each way on the world's stream
+// (snapshot.hip), and the host does what set_state's tail and the removal's do — the counts are on the host between steps.
+int World::snapshot_guard(const char* what, const Snapshot& s) const
+{
+    PHX_TRY(refuse_mid_step(what));
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world has no snapshots", what); return PHX_ERR_STATE; }
+    if (s.device() != device_) { set_error("%s: the snapshot lives on device %d, the world on device %d (move it as a blob)", what, s.device(), device_); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+SnapshotWorld World::snapshot_view()
+{
+    SnapshotWorld v = {};
+    v.records = bodies_.records.p; v.resident = resident(); v.records_stale = records_stale_;
+    v.accel = accel_.p;
+    v.manifolds = d_manifolds_.p; v.cps = d_cps_.p; v.joints = d_joints_.p;
+    v.filters = filters_.dev.p; v.materials = materials_.dev.p; v.flags = flags_col_.dev.p;
+    v.baseline = contacts_.baseline();
+    v.pairs = rm_pairs_.p;
+    return v;
+}
+
+int World::save(Snapshot& s)
+{
+    static const char* const what = "phx_world_save";
+    PHX_TRY(snapshot_guard(what, s));
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before its results are read)
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    SnapshotWorld v = snapshot_view();
+    v.counts.bodies = nb(); v.counts.manifolds = nm; v.counts.joints = nj; v.counts.baseline = contacts_.baseline_count();
+    v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
+    v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
+    return s.save(v, stream_);
+}
+
+int World::load(Snapshot& s)
+{
+    static const char* const what = "phx_world_load";
+    PHX_TRY(snapshot_guard(what, s));
+    if (!s.filled()) { set_error("%s: the snapshot was never filled (phx_world_save, phx_snapshot_import)", what); return PHX_ERR_STATE; }
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything is replaced)
+    const SnapCounts& c = s.counts();
+    const size_t n = (size_t)c.bodies;
+    // room first (a buffer that has to grow is replaced: its contents go anyway); nothing of the world changes before the kernel is queued
+    PHX_TRY(bodies_.reserve(std::max<size_t>(n, 1)));
+    if (s.accel_pending()) PHX_TRY(accel_.reserve(std::max<size_t>(n, 1)));
+    PHX_TRY(d_manifolds_.reserve(std::max<size_t>((size_t)c.manifolds, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)c.manifolds, 1)));
+    PHX_TRY(d_joints_.reserve(std::max<size_t>((size_t)c.joints, 1)));
+    PHX_TRY(rm_pairs_.reserve(std::max<size_t>((size_t)c.manifolds, 1)));
+    if (c.columns & SNAP_HAS_FILTERS) PHX_TRY(filters_.dev.reserve(std::max<size_t>(n, 1)));
+    if (c.columns & SNAP_HAS_MATERIALS) PHX_TRY(materials_.dev.reserve(std::max<size_t>(n, 1)));
+    if (c.columns & SNAP_HAS_FLAGS) PHX_TRY(flags_col_.dev.reserve(std::max<size_t>(n, 1)));
+    PHX_TRY(contacts_.reserve_baseline((size_t)c.baseline));
+    PHX_TRY(s.load(snapshot_view(), stream_));
+    // the device copy is the world (host-staged bodies and tables are dropped with the rest of the old world)
+    host_bodies_.resize(n);                                                 // (only its size counts while the device copy is the world)
+    bodies_dirty_ = false;
+    records_stale_ = false;
+    accel_pending_ = s.accel_pending();
+    filters_.active = (c.columns & SNAP_HAS_FILTERS) != 0; materials_.active = (c.columns & SNAP_HAS_MATERIALS) != 0; flags_col_.active = (c.columns & SNAP_HAS_FLAGS) != 0;
+    each_table([](auto& t) { t.host.clear(); return PHX_OK; });
+    nm = c.manifolds; nj = c.joints;
+    contacts_.baseline_replaced(c.baseline);
+    ++geom_epoch_;
+    ++contact_epoch_;
+    // what set_state resets: the pair set becomes the saved manifolds' pairs, the schedule is rebuilt at the next step
+    PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
+    return forget_step_history();
 }
 
 int World::get_slab_state(const long long* global_index, int count, SlabState* out)
@@ -1979,6 +2048,18 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
     for (size_t k = 0; k < st.global_index.size(); ++k) global_index[k] = st.global_index[k];
     *body_count = (int32_t)st.bodies.size();
     return PHX_OK;
+}
+
+int phx_world_save(phx_world* w, phx_snapshot* s)
+{
+    PHX_REQUIRE(w && s, "phx_world_save: null handle");
+    return w->impl.save(s->impl);
+}
+
+int phx_world_load(phx_world* w, phx_snapshot* s)
+{
+    PHX_REQUIRE(w && s, "phx_world_load: null handle");
+    return w->impl.load(s->impl);
 }
 
 int phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out) { PHX_REQUIRE(w, "null handle"); return w->impl.solver().get_stats(out); }

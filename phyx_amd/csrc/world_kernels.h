@@ -19,34 +19,11 @@
 
 namespace phx {
 
-// ---- 128-byte records <-> the World's resident arrays (body_view.h): upload after construction, download for the getters -------
-__device__ __forceinline__ void record_to_world(const phx_rigid_body& b, const WorldBodies& w, int i)
-{
-    w.s.vel[i] = make_float4(b.velocity.x, b.velocity.y, b.angular_velocity, 0.f);
-    w.s.dvel[i] = make_float4(b.displacing_velocity.x, b.displacing_velocity.y, b.displacing_angular_velocity, 0.f);
-    w.s.mpos[i] = make_float4(b.inv_mass, b.inv_inertia, b.pos.x, b.pos.y);
-    w.frame[i] = make_float4(b.xvector.x, b.xvector.y, b.yvector.x, b.yvector.y);
-    w.aabb[i] = make_float4(b.aabb_min.x, b.aabb_min.y, b.aabb_max.x, b.aabb_max.y);
-    w.size[i] = make_float2(b.geom_size.x, b.geom_size.y);
-}
-
+// ---- 128-byte records <-> the World's resident arrays (body_view.h record_to_world / world_record): upload after construction, download
+// for the getters -------
 static __global__ void __launch_bounds__(256) k_bodies_to_world(const phx_rigid_body* __restrict__ bodies, int n, WorldBodies w)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) record_to_world(bodies[i], w, i);
-}
-
-// everything a step changes goes back into the records (inverse masses, size, index, the vestigial fields and the accelerations —
-// zero after every IntegrateVelocity, ref: World.cpp:49-52, or what phx_world_add_accelerations left pending — are what the upload
-// left there): body i's record `b` from the resident arrays
-__device__ __forceinline__ void world_record(const WorldBodies& w, int i, phx_rigid_body& b)
-{
-    const float4 v = w.s.vel[i], d = w.s.dvel[i], m = w.s.mpos[i], f = w.frame[i], a = w.aabb[i];
-    b.velocity.x = v.x; b.velocity.y = v.y; b.angular_velocity = v.z;
-    b.displacing_velocity.x = d.x; b.displacing_velocity.y = d.y; b.displacing_angular_velocity = d.z;
-    b.pos.x = m.z; b.pos.y = m.w;
-    b.xvector.x = f.x; b.xvector.y = f.y; b.yvector.x = f.z; b.yvector.y = f.w;
-    b.geom_xvector = b.xvector; b.geom_yvector = b.yvector; b.geom_pos = b.pos;      // UpdateGeom (ref: RigidBody.h:38-42)
-    b.aabb_min.x = a.x; b.aabb_min.y = a.y; b.aabb_max.x = a.z; b.aabb_max.y = a.w;
 }
 
 static __global__ void __launch_bounds__(256) k_world_to_bodies(WorldBodies w, int n, phx_rigid_body* __restrict__ bodies)
