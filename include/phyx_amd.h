@@ -732,7 +732,8 @@ int  phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t bod
  *       reported had the save and the load never happened).
  *   - What it does NOT hold, and a load leaves alone: gravity, the shard and the communicator, phase timing, the paths chosen from the
  *     environment (PHX_QUERY_PATH, PHX_CONTACT_PATH, ...), the fp16 body-state ablation and every other setting of the world's solver.
- *     A snapshot forked into a fresh world needs its gravity set by the caller.
+ *     A snapshot forked into a fresh world needs its gravity set by the caller, and its pin iteration count (phx_world_set_pin_iterations)
+ *     if it is not the default: the pins and their impulses are saved, the number of sweeps is a setting of the world and is not.
  *   - Definition of load: after phx_world_load(w, s) the world is exactly what these calls would have made of it, byte for byte in every
  *     getter and in every later step:
  *       1. phx_world_set_state of the four saved arrays;
@@ -791,6 +792,68 @@ int  phx_snapshot_blob_pack(const phx_rigid_body* bodies, int32_t body_count, co
                             const phx_collision_filter* filters, const phx_material* materials, const uint32_t* flags,
                             const int32_t* baseline_pairs, int32_t baseline_count,
                             void* blob, size_t cap, size_t* bytes);
+
+/* PINS — hold a point of one body on a point of another (a revolute joint), or on a fixed point of the world (body2 = -1): chains,
+ * pendulums, hinges, a dragged body that follows the cursor rigidly.  The reference has no such constraint; tests/pin_spec.py is the
+ * definition (scalar float32, every operation rounded on its own, no fused multiply-add in either phx_arith_mode, IEEE division) and
+ * the device matches it byte for byte.
+ *   - anchor1 / anchor2 are in the bodies' own frames: the world point of an anchor is pos + xVector * a.x + yVector * a.y.  With
+ *     body2 == -1, anchor2 is a world point.  impulse is the accumulated impulse: the warm start, carried from step to step, 0 for a new
+ *     pin unless the caller restores one.
+ *   - The pass runs once per step at the end of phx_world_pre_solve: IntegrateVelocity and RefreshContactJoints are done, SolveJoints
+ *     has not started.  It reads positions and frames as the last IntegratePosition left them and reads and writes velocity and
+ *     angularVelocity only; contacts are solved afterwards on the velocities the pins left, so a contact has the last word.  Per pin,
+ *     with m, i the inverse mass and inertia (0 for the world), ra, rb the rotated anchors (rb = 0 for the world), and w x r = (w r.y, -w r.x):
+ *     the reference's angularVelocity is clockwise-positive (IntegratePosition rotates by -w dt, ref: World.cpp:63; the contact limiters
+ *     project it with n x r, ref: Solver.cpp:559), so that is the velocity its w gives the point r, and P at r changes w by -i (r x P):
+ *         C    = (posB + rb) - (posA + ra)                      (world pin: anchor2 - (posA + ra))
+ *         k11  = mA + mB + iA ra.y^2 + iB rb.y^2,  k12 = -iA ra.x ra.y - iB rb.x rb.y,  k22 = mA + mB + iA ra.x^2 + iB rb.x^2
+ *         det  = k11 k22 - k12^2;  a pin with !(det > 0) is INACTIVE this step: impulse := 0, nothing else
+ *         bias = C * (0.2f / dt);  warm start: apply impulse;  n sweeps: cdot = (vB + wB x rb) - (vA + wA x ra), rhs = -(cdot + bias),
+ *         d = (1/det) * (k22 rhs.x - k12 rhs.y, k11 rhs.y - k12 rhs.x), impulse += d, apply d
+ *         apply P: vA -= mA P, wA += iA (ra.x P.y - ra.y P.x), vB += mB P, wB -= iB (rb.x P.y - rb.y P.x)   (a static body is not written)
+ *     n = phx_world_set_pin_iterations (1 .. 64, default 8), a setting of the world like gravity.  There is no cap on the bias: a pin
+ *     whose anchor is moved far in one step pulls hard.  The bias is part of the accumulated impulse, hence of the next step's warm start:
+ *     a chain whose tension the n sweeps do not carry from end to end within a step oscillates, and the oscillation grows (the spec's
+ *     hanging chain of 16 links diverges at n = 8 and rests at n = 32: tests/pin_spec.py) - give long chains more sweeps.  Pins do not stop their two bodies from colliding: collision filters do that.
+ *   - Order is semantics: prestep and warm start in the slot order of the pin schedule, then n sweeps in slot order.  The schedule
+ *     (phx_world_get_pin_schedule, host-only twin phx_pin_schedule) is phx_schedule_groups' with one pin per unit, the world anchor as one
+ *     virtual static body (index body_count) and at most `group_pins` pins per group (256; PHX_PIN_GROUP_PINS=n, 1 .. 256, read when a
+ *     world is created, lowers it for tests): connected components binned into groups that one workgroup solves out of LDS in ONE launch,
+ *     whatever does not fit in one trailing group swept class by class out of HBM.  It is rebuilt on the host, lazily at the next step,
+ *     when the pin set or the static set changed (add_pins, remove_pins, a removal of bodies that took pins with it, set_inverse_masses,
+ *     set_body_static, set_body_inverse_mass, set_state, load); anchor edits, spawns and every other call keep it.  O(pins) bytes cross PCIe at such
+ *     a change, nothing per step.  phx_world_pin_schedule_builds counts the builds.
+ *   - Rules, those of the edits: between steps only (PHX_ERR_STATE otherwise); arguments are checked completely before anything is queued
+ *     and a failed check (PHX_ERR_INVALID) leaves the world unchanged: count >= 0, no NULL array when count > 0, body1 in range, body2 in
+ *     range or -1, body1 != body2, anchors and impulse finite, pin indices in range and distinct.  An empty call is a true no-op.  A pin
+ *     between two static bodies is accepted and merely inactive.  remove_pins keeps the others' order (indices shift).  Before the first
+ *     step the pins wait on the host with the host-staged bodies.
+ *   - The other calls: phx_world_remove_bodies / remove_outside drop every pin that has a removed body, remap the rest through new[] and
+ *     keep their order; phx_world_set_state drops every pin; phx_world_save / load carry the pins with their impulses in HBM (the
+ *     definition of load gains: 6. phx_world_add_pins of the saved pins), but the blob stays layout version 1 and holds none, so
+ *     phx_snapshot_export and phx_snapshot_blob_bytes of a snapshot that holds pins return PHX_ERR_STATE; sharded worlds carry none:
+ *     phx_world_set_shard (count > 1), set_comm and reslab return PHX_ERR_STATE while a pin exists, and so does add_pins on a sharded world.
+ *     A world without pins launches nothing new and allocates nothing new. */
+typedef struct { int32_t body1, body2; phx_vec2 anchor1, anchor2; phx_vec2 impulse; } phx_pin;   /* 32 B */
+int  phx_world_add_pins(phx_world* w, const phx_pin* pins, int32_t count, int32_t* first);      /* *first (may be NULL) = index of the first new pin */
+int  phx_world_remove_pins(phx_world* w, const int32_t* pins, int32_t count);
+int  phx_world_set_pin_anchors(phx_world* w, const int32_t* pins, const float* anchors /* 4 per pin: anchor1, anchor2 */, int32_t count);
+int  phx_world_get_pins(phx_world* w, phx_pin* out, int32_t cap);
+int  phx_world_pin_count(phx_world* w, int32_t* count);
+int  phx_world_set_pin_iterations(phx_world* w, int32_t n);
+int  phx_world_get_pin_iterations(phx_world* w, int32_t* n);
+int  phx_world_pin_schedule_builds(phx_world* w, int64_t* builds);
+/* The schedule the next step's pin pass uses (built now unless current; between steps only): order[k] = the pin in slot k, class c owns
+ * slots [class_offsets[c], class_offsets[c + 1]), group g owns slots [group_offsets[g], group_offsets[g + 1]); the first *lds_group_count
+ * groups run one workgroup each out of LDS, the rest (at most one) out of HBM.  Pass NULL arrays (cap 0) to ask for the counts. */
+int  phx_world_get_pin_schedule(phx_world* w, int32_t* order, int32_t order_cap, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
+                                int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count);
+/* host only, no device needed: the same schedule from the pins' bodies (body2 = -1: the world) and the bodies' static flags */
+int  phx_pin_schedule(const int32_t* body1, const int32_t* body2, int32_t pin_count, const uint8_t* is_static, int32_t body_count, int32_t group_pins,
+                      int32_t* order, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
+                      int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count);
+
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);
 /* handles owned by the world (for stage-level queries after an update) */

@@ -196,6 +196,16 @@ _SIGNATURES = {
     "phx_reslab_plan": (C.c_int, [_vp, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp]),
     "phx_reslab_cuts": (C.c_int, [_vp, _vp, _i32, _i32, C.c_double, _vp, _vp]),
     "phx_world_synchronize": (C.c_int, [_vp]),
+    "phx_world_add_pins": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
+    "phx_world_remove_pins": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_set_pin_anchors": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_get_pins": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_pin_count": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "phx_world_set_pin_iterations": (C.c_int, [_vp, _i32]),
+    "phx_world_get_pin_iterations": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "phx_world_pin_schedule_builds": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "phx_world_get_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "phx_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "phx_snapshot_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "phx_snapshot_destroy": (None, [_vp]),
     "phx_world_save": (C.c_int, [_vp, _vp]),

@@ -49,6 +49,8 @@ material_dtype = np.dtype([("friction", "<f4"), ("restitution", "<f4")])      # 
 assert material_dtype.itemsize == 8
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
+pin_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("impulse", "<f4", (2,))])      # phx_pin
+assert pin_dtype.itemsize == 32
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
@@ -162,6 +164,22 @@ def schedule_groups(body1, body2, is_static, priority_ids=None, lanes=256, body_
     ng = lg.value + (1 if lg.value == 0 or goff[lg.value] < n else 0)
     return dict(order=order[:n], colour_offsets=offs[:nc.value + 1], lds_groups=lg.value, group_offsets=goff[:ng + 1], group_first_colour=gfc[:ng + 1],
                 unit_lane=ulane[:nu], unit_leader_slot=uslot[:nu])
+
+
+def pin_schedule(body1, body2, is_static, group_pins=256):
+    """Host-only: the schedule of the pin pass (include/phyx_amd.h phx_pin_schedule; body2 = -1: the world) -> dict with order,
+    class_offsets, group_offsets, lds_groups."""
+    L = _lib.load()
+    b1 = np.ascontiguousarray(body1, dtype=np.int32)
+    b2 = np.ascontiguousarray(body2, dtype=np.int32)
+    st = np.ascontiguousarray(is_static, dtype=np.uint8)
+    n = len(b1)
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    coff = np.zeros(n + 2, dtype=np.int32); goff = np.zeros(n + 2, dtype=np.int32)
+    nc = C.c_int32(0); ng = C.c_int32(0); lg = C.c_int32(0)
+    check(L.phx_pin_schedule(_ptr(b1), _ptr(b2), n, _ptr(st), len(st), int(group_pins), _ptr(order), _ptr(coff), len(coff), C.byref(nc),
+                             _ptr(goff), len(goff), C.byref(ng), C.byref(lg)))
+    return dict(order=order[:n], class_offsets=coff[:nc.value + 1], group_offsets=goff[:ng.value + 1], lds_groups=lg.value)
 
 
 def schedule_islands(body1, body2, is_static):
@@ -915,6 +933,72 @@ class World:
         if isinstance(bodies, (list, tuple)) and not len(bodies):
             bodies = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
+
+    # ---- pins (include/phyx_amd.h PINS; the specification: tests/pin_spec.py) ----
+    def add_pins(self, pins):
+        """Append pins: a pin_dtype array, or rows (body1, body2, (a1x, a1y), (a2x, a2y)) with impulse 0.  body2 = -1 pins body1 to the
+        world point anchor2.  Returns the new pins' indices."""
+        if isinstance(pins, np.ndarray) and pins.dtype == pin_dtype:
+            p = np.ascontiguousarray(pins)
+        else:
+            rows = list(pins)
+            p = np.zeros(len(rows), dtype=pin_dtype)
+            for k, r in enumerate(rows):
+                p["body1"][k], p["body2"][k], p["anchor1"][k], p["anchor2"][k] = int(r[0]), int(r[1]), r[2], r[3]
+        first = C.c_int32(0)
+        check(self.L.phx_world_add_pins(self.h, _ptr(p), len(p), C.byref(first)))
+        return np.arange(first.value, first.value + len(p), dtype=np.int64)
+
+    def remove_pins(self, pins):
+        """Remove the listed pins (each at most once); the others keep their order, so their indices shift."""
+        if isinstance(pins, (list, tuple)) and not len(pins):
+            pins = np.zeros(0, dtype=np.int32)
+        idx = self._indices(pins, "remove_pins")
+        check(self.L.phx_world_remove_pins(self.h, _ptr(idx), len(idx)))
+
+    def set_pin_anchors(self, pins, anchors):
+        """anchor1, anchor2 = anchors[k] {a1.x, a1.y, a2.x, a2.y} of pin pins[k]; the schedule stays (a dragged body's world pin
+        follows the cursor this way)."""
+        if isinstance(pins, (list, tuple)) and not len(pins):
+            pins = np.zeros(0, dtype=np.int32)
+        self._edit("phx_world_set_pin_anchors", pins, anchors, 4, "set_pin_anchors")
+
+    def pin_count(self):
+        n = C.c_int32(0)
+        check(self.L.phx_world_pin_count(self.h, C.byref(n)))
+        return n.value
+
+    def pins(self):
+        """Every pin as a pin_dtype array, with the impulses the last step accumulated."""
+        out = np.zeros(self.pin_count(), dtype=pin_dtype)
+        check(self.L.phx_world_get_pins(self.h, _ptr(out), len(out)))
+        return out
+
+    @property
+    def pin_iterations(self):
+        n = C.c_int32(0)
+        check(self.L.phx_world_get_pin_iterations(self.h, C.byref(n)))
+        return n.value
+
+    @pin_iterations.setter
+    def pin_iterations(self, n):
+        check(self.L.phx_world_set_pin_iterations(self.h, int(n)))
+
+    def pin_schedule(self):
+        """The schedule the next step's pin pass uses (built now unless current) -> dict with order, class_offsets, group_offsets,
+        lds_groups, as api.pin_schedule."""
+        nc = C.c_int32(0); ng = C.c_int32(0); lg = C.c_int32(0)
+        check(self.L.phx_world_get_pin_schedule(self.h, None, 0, None, 0, C.byref(nc), None, 0, C.byref(ng), C.byref(lg)))
+        n = self.pin_count()
+        order = np.zeros(max(n, 1), dtype=np.int32)
+        coff = np.zeros(nc.value + 1, dtype=np.int32); goff = np.zeros(ng.value + 1, dtype=np.int32)
+        check(self.L.phx_world_get_pin_schedule(self.h, _ptr(order), n, _ptr(coff), len(coff), C.byref(nc), _ptr(goff), len(goff), C.byref(ng), C.byref(lg)))
+        return dict(order=order[:n], class_offsets=coff, group_offsets=goff, lds_groups=lg.value)
+
+    def pin_schedule_builds(self):
+        n = C.c_int64(0)
+        check(self.L.phx_world_pin_schedule_builds(self.h, C.byref(n)))
+        return n.value
 
     # ---- collision filters (include/phyx_amd.h COLLISION FILTERS; the specification: tests/filter_spec.py) ----
     def set_collision_filters(self, bodies, category=1, mask=0xFFFFFFFF, group=0):

@@ -1,0 +1,227 @@
+// pin_kernels.h — the pin pass (include/phyx_amd.h PINS; the definition: tests/pin_spec.py).
+//
+// One copy of the arithmetic (pin_prestep, pin_delta, pin_apply_*), written operation for operation as the spec writes it; the library
+// is built with -ffp-contract=off -fno-fast-math, so every product and sum below is rounded on its own in either PHX_ARITH mode.
+//   k_solve_pins     one workgroup per LDS group, the whole pass in ONE launch: the group's body velocities are staged in LDS (16 bytes
+//                    per body, the only thing staged), one lane owns one pin and keeps ra, rb, k11, k12, k22, 1/det, bias and the
+//                    impulse in registers from the prestep to the write-back; classes are body-disjoint, so a class is one parallel
+//                    step and a barrier separates it from the next.
+//   k_pin_prestep /  the trailing group, out of HBM: the prestep leaves the lanes' registers in a work array, then one launch per
+//   k_pin_class      class for the warm start and per class and sweep (the fallback, not the fast path).
+// Static bodies (both inverses 0) and the world are read, never written: a class may share them among its lanes.
+#pragma once
+
+#include "pins.h"
+
+namespace phx {
+
+
+// a slot of the schedule as the kernels read it
+struct PinSlot { int pin; int a, b; int colour; };      // LDS groups: a, b local body indices (b = -1: the world); HBM group: global ones
+// an LDS group: its slots, its bodies in `group_bodies` (the static ones first), its classes
+struct PinGroup { int slot_begin, slot_end, body_begin, body_count; int first_dynamic, classes, pad0, pad1; };
+
+// what a lane keeps of its pin from the prestep on
+struct PinRegs {
+    float rax, ray, rbx, rby;
+    float k11, k12, k22, inv_det;
+    float biasx, biasy;
+    float ma, ia, mb, ib;
+    float px, py;                       // the accumulated impulse
+    bool active, write_a, write_b;
+};
+
+__device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta)
+{
+    PinRegs r;
+    const float4 qa = mpos[p.body1], fa = frame[p.body1];
+    r.ma = qa.x; r.ia = qa.y;
+    r.rax = fa.x * p.anchor1.x + fa.z * p.anchor1.y;
+    r.ray = fa.y * p.anchor1.x + fa.w * p.anchor1.y;
+    const float pax = qa.z + r.rax, pay = qa.w + r.ray;
+    float pbx, pby;
+    if (p.body2 >= 0) {
+        const float4 qb = mpos[p.body2], fb = frame[p.body2];
+        r.mb = qb.x; r.ib = qb.y;
+        r.rbx = fb.x * p.anchor2.x + fb.z * p.anchor2.y;
+        r.rby = fb.y * p.anchor2.x + fb.w * p.anchor2.y;
+        pbx = qb.z + r.rbx; pby = qb.w + r.rby;
+    } else {
+        r.mb = 0.f; r.ib = 0.f; r.rbx = 0.f; r.rby = 0.f;
+        pbx = p.anchor2.x; pby = p.anchor2.y;
+    }
+    const float cx = pbx - pax, cy = pby - pay;
+    const float ms = r.ma + r.mb;
+    r.k11 = (ms + (r.ia * r.ray) * r.ray) + (r.ib * r.rby) * r.rby;
+    r.k12 = -((r.ia * r.rax) * r.ray) - (r.ib * r.rbx) * r.rby;
+    r.k22 = (ms + (r.ia * r.rax) * r.rax) + (r.ib * r.rbx) * r.rbx;
+    const float det = r.k11 * r.k22 - r.k12 * r.k12;
+    r.active = det > 0.f;
+    r.inv_det = 1.0f / det;
+    r.biasx = cx * beta; r.biasy = cy * beta;
+    r.px = r.active ? p.impulse.x : 0.f;
+    r.py = r.active ? p.impulse.y : 0.f;
+    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
+    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+    return r;
+}
+
+// The engine's angularVelocity is CLOCKWISE-positive: IntegratePosition rotates the frame by -w dt (ref: World.cpp:63) and the contact
+// limiters project it with n x r (ref: Solver.cpp:559-560), so the velocity of a body's point at r is v - w x r = (v.x + w r.y, v.y - w r.x)
+// and an impulse P at r changes w by -i (r x P).
+// apply P to the two velocities {v.x, v.y, w, .}
+__device__ __forceinline__ void pin_apply(const PinRegs& r, float px, float py, float4& va, float4& vb)
+{
+    va.x = va.x - r.ma * px;
+    va.y = va.y - r.ma * py;
+    va.z = va.z + r.ia * (r.rax * py - r.ray * px);
+    vb.x = vb.x + r.mb * px;
+    vb.y = vb.y + r.mb * py;
+    vb.z = vb.z - r.ib * (r.rbx * py - r.rby * px);
+}
+
+// one sweep's impulse of the pin on velocities va, vb; accumulates it
+__device__ __forceinline__ void pin_delta(PinRegs& r, const float4& va, const float4& vb, float& dx, float& dy)
+{
+    const float vbx = vb.x + vb.z * r.rby, vby = vb.y - vb.z * r.rbx;
+    const float vax = va.x + va.z * r.ray, vay = va.y - va.z * r.rax;
+    const float rx = -((vbx - vax) + r.biasx), ry = -((vby - vay) + r.biasy);
+    dx = r.inv_det * (r.k22 * rx - r.k12 * ry);
+    dy = r.inv_det * (r.k11 * ry - r.k12 * rx);
+    r.px = r.px + dx;
+    r.py = r.py + dy;
+}
+
+// The LDS layout: one float4 per local body.  A lane's two bodies are anywhere in the table, so a class step is a gather / scatter of
+// 16-byte granules (ds_read_b128 / ds_write_b128).  A 16-byte read is served in four groups of 16 lanes over the 64 banks: a group
+// is conflict-free when its granules differ mod 16.  The two classes of a chain take every other pin, so a class's lanes sit two
+// granules apart and read two-way conflicted (8 LDS cycles instead of 4 per wave); the 16-byte store's cost is its register transfer
+// either way.  Both are small beside the dependent chain of a class step (read, ~20 dependent flops, write, barrier), which is what
+// the pass waits for.
+static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __restrict__ pins, const PinSlot* __restrict__ slots, const PinGroup* __restrict__ groups,
+                                                                 const int* __restrict__ group_bodies, float4* __restrict__ vel, const float4* __restrict__ mpos,
+                                                                 const float4* __restrict__ frame, float beta, int iterations)
+{
+    __shared__ float4 sv[PIN_BODIES];
+    const PinGroup g = groups[blockIdx.x];
+    const int* const bodies = group_bodies + g.body_begin;
+    for (int i = threadIdx.x; i < g.body_count; i += PIN_LANES) {
+        const int b = bodies[i];
+        sv[i] = b >= 0 ? vel[b] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int slot = g.slot_begin + (int)threadIdx.x;
+    const bool mine = slot < g.slot_end;
+    PinSlot s = {0, 0, -1, -1};
+    PinRegs r = {};
+    if (mine) {
+        s = slots[slot];
+        r = pin_prestep(pins[s.pin], mpos, frame, beta);
+    }
+    const bool work = mine && r.active;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    __syncthreads();
+    for (int c = 0; c < g.classes; ++c) {                                   // warm start, class by class
+        if (work && s.colour == c) {
+            float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
+            pin_apply(r, r.px, r.py, va, vb);
+            if (r.write_a) sv[s.a] = va;
+            if (r.write_b) sv[s.b] = vb;
+        }
+        __syncthreads();
+    }
+    for (int it = 0; it < iterations; ++it)
+        for (int c = 0; c < g.classes; ++c) {
+            if (work && s.colour == c) {
+                float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
+                float dx, dy;
+                pin_delta(r, va, vb, dx, dy);
+                pin_apply(r, dx, dy, va, vb);
+                if (r.write_a) sv[s.a] = va;
+                if (r.write_b) sv[s.b] = vb;
+            }
+            __syncthreads();
+        }
+    for (int i = g.first_dynamic + (int)threadIdx.x; i < g.body_count; i += PIN_LANES) vel[bodies[i]] = sv[i];
+    if (mine) pins[s.pin].impulse = phx_vec2{r.px, r.py};
+}
+
+// ---- the trailing group, out of HBM ----
+struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags, pad; };      // flags: 1 active, 2 write a, 4 write b
+
+__device__ __forceinline__ PinRegs pin_regs(const PinWork& w, const phx_pin& p)
+{
+    PinRegs r;
+    r.rax = w.rax; r.ray = w.ray; r.rbx = w.rbx; r.rby = w.rby; r.k11 = w.k11; r.k12 = w.k12; r.k22 = w.k22; r.inv_det = w.inv_det;
+    r.biasx = w.biasx; r.biasy = w.biasy; r.ma = w.ma; r.ia = w.ia; r.mb = w.mb; r.ib = w.ib;
+    r.px = p.impulse.x; r.py = p.impulse.y;
+    r.active = (w.flags & 1) != 0; r.write_a = (w.flags & 2) != 0; r.write_b = (w.flags & 4) != 0;
+    return r;
+}
+
+// slots [begin, end): the prestep; an inactive pin's impulse becomes 0 here
+static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, const PinSlot* __restrict__ slots, int begin, int end, const float4* __restrict__ mpos,
+                                                            const float4* __restrict__ frame, float beta, PinWork* __restrict__ work)
+{
+    for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
+        const int pin = slots[k].pin;
+        const PinRegs r = pin_prestep(pins[pin], mpos, frame, beta);
+        PinWork w;
+        w.rax = r.rax; w.ray = r.ray; w.rbx = r.rbx; w.rby = r.rby; w.k11 = r.k11; w.k12 = r.k12; w.k22 = r.k22; w.inv_det = r.inv_det;
+        w.biasx = r.biasx; w.biasy = r.biasy; w.ma = r.ma; w.ia = r.ia; w.mb = r.mb; w.ib = r.ib;
+        w.flags = (r.active ? 1 : 0) | (r.write_a ? 2 : 0) | (r.write_b ? 4 : 0); w.pad = 0;
+        work[k - begin] = w;
+        if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
+    }
+}
+
+// one class, slots [begin, end) of a group whose work array starts at slot `base`: the warm start (sweep == 0) or one sweep
+static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ pins, const PinSlot* __restrict__ slots, int begin, int end, int base,
+                                                          const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep)
+{
+    for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
+        const PinSlot s = slots[k];
+        PinRegs r = pin_regs(work[k - base], pins[s.pin]);
+        if (!r.active) continue;
+        float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
+        float dx = r.px, dy = r.py;
+        if (sweep) pin_delta(r, va, vb, dx, dy);
+        pin_apply(r, dx, dy, va, vb);
+        if (r.write_a) vel[s.a] = va;
+        if (r.write_b) vel[s.b] = vb;
+        if (sweep) pins[s.pin].impulse = phx_vec2{r.px, r.py};
+    }
+}
+
+// ---- what the host asks between steps ----
+// per pin: are its bodies static (bit 0: body1, bit 1: body2)?  O(pins) bytes for the schedule build
+static __global__ void __launch_bounds__(256) k_pin_statics(const phx_pin* __restrict__ pins, int n, const float4* __restrict__ mpos, unsigned* __restrict__ out)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const phx_pin p = pins[i];
+        const float4 a = mpos[p.body1];
+        unsigned bits = (a.x == 0.f && a.y == 0.f) ? 1u : 0u;
+        if (p.body2 >= 0) { const float4 b = mpos[p.body2]; if (b.x == 0.f && b.y == 0.f) bits |= 2u; }
+        out[i] = bits;
+    }
+}
+
+// a removal of bodies: every pin's bodies through new[] (-1: removed; the world stays -1 and is told apart by the old index)
+static __global__ void __launch_bounds__(256) k_pin_remap(const phx_pin* __restrict__ pins, int n, const int* __restrict__ remap, int2* __restrict__ out)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const phx_pin p = pins[i];
+        out[i] = make_int2(remap[p.body1], p.body2 >= 0 ? remap[p.body2] : -2);
+    }
+}
+
+// phx_world_set_pin_anchors on the device copy
+static __global__ void __launch_bounds__(256) k_pin_anchors(const int* __restrict__ which, const float* __restrict__ anchors, int count, phx_pin* __restrict__ pins)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        phx_pin& p = pins[which[k]];
+        p.anchor1 = phx_vec2{anchors[4 * k], anchors[4 * k + 1]};
+        p.anchor2 = phx_vec2{anchors[4 * k + 2], anchors[4 * k + 3]};
+    }
+}
+
+} // namespace phx

@@ -1,0 +1,257 @@
+// pins.hip — PinSet: the World's pins, their schedule and the pass that solves them (include/phyx_amd.h PINS; kernels: pin_kernels.h).
+//
+// The data path.  At a change of the pin set or the static set: the pins' static bits come down (4 bytes per pin), the host builds the
+// schedule with the contact schedule's own builder (one pin per unit, the world as one virtual static body) and one upload carries the
+// slot, group and group-body tables.  Per step nothing crosses PCIe: k_solve_pins, one workgroup per LDS group, does the whole pass of
+// those groups in one launch; the trailing group — components that do not fit a workgroup — takes a prestep launch and one launch per
+// class for the warm start and per class and sweep.
+#include "pins.h"
+#include "pin_kernels.h"
+
+namespace phx {
+
+static inline int pgrid(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }
+
+void build_pin_schedule(const int32_t* body1, const int32_t* body2, int count, const unsigned char* is_static, int nb, int group_pins, Schedule& out)
+{
+    // the builder numbers a component per dynamic body and bins consecutive components (schedule.h BINNING): it is given the pins' own
+    // bodies only, renumbered in body order, so that bodies no pin touches do not thin the groups out.  The world is the body behind
+    // them, static; priority ids 2 k never differ in the lowest bit only, so no two pins are paired into a unit.
+    std::vector<int> ids;
+    ids.reserve(2 * (size_t)count);
+    for (int k = 0; k < count; ++k) { ids.push_back(body1[k]); if (body2[k] >= 0) ids.push_back(body2[k]); }
+    std::sort(ids.begin(), ids.end());
+    ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+    const int dense = (int)ids.size();
+    auto local = [&](int b) { return (int)(std::lower_bound(ids.begin(), ids.end(), b) - ids.begin()); };
+    std::vector<int> b1((size_t)count), b2((size_t)count), prio((size_t)count);
+    std::vector<unsigned char> st((size_t)dense + 1, 1);
+    for (int i = 0; i < dense; ++i) st[(size_t)i] = is_static[ids[(size_t)i]];
+    for (int k = 0; k < count; ++k) { b1[(size_t)k] = local(body1[k]); b2[(size_t)k] = body2[k] < 0 ? dense : local(body2[k]); prio[(size_t)k] = 2 * k; }
+    LdsCaps caps;
+    caps.max_units = group_pins; caps.max_joints = group_pins; caps.max_bodies = PIN_BODIES; caps.max_colours = 64;
+    build_island_schedule(b1.data(), b2.data(), count, st.data(), dense + 1, caps, out, nullptr, prio.data());
+    for (int& b : out.group_bodies) b = b == dense ? nb : ids[(size_t)b];  // (the LDS groups' bodies under their own numbers again; the world: nb)
+}
+
+int PinSet::configure_from_env()
+{
+    group_pins_ = PIN_LANES;
+    const char* c = getenv("PHX_PIN_GROUP_PINS");
+    if (!c) return PHX_OK;
+    char* end = nullptr;
+    const long v = strtol(c, &end, 10);
+    if (!*c || *end || v < 1 || v > PIN_LANES) { set_error("PHX_PIN_GROUP_PINS=%s: expected an integer in [1, %d]", c, PIN_LANES); return PHX_ERR_INVALID; }
+    group_pins_ = (int)v;
+    return PHX_OK;
+}
+
+int PinSet::fetch(hipStream_t stream)
+{
+    if (dirty_ || host_.empty()) return PHX_OK;
+    PHX_HIP(hipStreamSynchronize(stream));
+    PHX_HIP(hipMemcpy(host_.data(), d_pins_.p, host_.size() * sizeof(phx_pin), hipMemcpyDeviceToHost));
+    return PHX_OK;
+}
+
+int PinSet::upload(hipStream_t stream)
+{
+    if (!dirty_ || host_.empty()) return PHX_OK;
+    PHX_TRY(d_pins_.reserve(host_.size()));
+    PHX_HIP(hipMemcpyAsync(d_pins_.p, host_.data(), host_.size() * sizeof(phx_pin), hipMemcpyHostToDevice, stream));
+    PHX_HIP(hipStreamSynchronize(stream));
+    dirty_ = false;
+    return PHX_OK;
+}
+
+int PinSet::add(const phx_pin* pins, int count, hipStream_t stream)
+{
+    PHX_TRY(fetch(stream));
+    host_.insert(host_.end(), pins, pins + count);
+    dirty_ = true; sched_dirty_ = true;
+    return PHX_OK;
+}
+
+int PinSet::remove(const int32_t* which, int count, hipStream_t stream)
+{
+    PHX_TRY(fetch(stream));
+    std::vector<unsigned char> gone(host_.size(), 0);
+    for (int k = 0; k < count; ++k) gone[(size_t)which[k]] = 1;
+    size_t at = 0;
+    for (size_t i = 0; i < host_.size(); ++i) if (!gone[i]) host_[at++] = host_[i];
+    host_.resize(at);
+    dirty_ = true; sched_dirty_ = true;
+    return PHX_OK;
+}
+
+int PinSet::set_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream)
+{
+    for (int k = 0; k < count; ++k) {
+        phx_pin& p = host_[(size_t)which[k]];
+        p.anchor1 = phx_vec2{anchors[4 * k], anchors[4 * k + 1]};
+        p.anchor2 = phx_vec2{anchors[4 * k + 2], anchors[4 * k + 3]};
+    }
+    if (!on_device()) return PHX_OK;
+    hipLaunchKernelGGL(k_pin_anchors, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_anchors, count, d_pins_.p);
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+int PinSet::get(phx_pin* out, hipStream_t stream)
+{
+    PHX_TRY(fetch(stream));
+    if (!host_.empty()) std::memcpy(out, host_.data(), host_.size() * sizeof(phx_pin));
+    return PHX_OK;
+}
+
+int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
+{
+    const int n = count();
+    if (!n) return PHX_OK;
+    PHX_TRY(upload(stream));
+    PHX_TRY(d_moved_.reserve((size_t)n));
+    hipLaunchKernelGGL(k_pin_remap, dim3(pgrid(n)), dim3(256), 0, stream, (const phx_pin*)d_pins_.p, n, d_remap, d_moved_.p);
+    PHX_HIP(hipGetLastError());
+    // one round trip: the remapped bodies and the pins themselves (their impulses are the device's)
+    std::vector<int2> moved((size_t)n);
+    PHX_TRY(rb.add(moved.data(), d_moved_.p, (size_t)n * sizeof(int2), stream));
+    PHX_TRY(rb.add(host_.data(), d_pins_.p, (size_t)n * sizeof(phx_pin), stream));
+    PHX_TRY(rb.wait(stream));
+    size_t at = 0;
+    for (size_t i = 0; i < host_.size(); ++i) {
+        if (moved[i].x == -1 || moved[i].y == -1) continue;
+        phx_pin p = host_[i];
+        p.body1 = moved[i].x; p.body2 = moved[i].y == -2 ? -1 : moved[i].y;
+        host_[at++] = p;
+    }
+    host_.resize(at);
+    dirty_ = true; sched_dirty_ = true;
+    return PHX_OK;
+}
+
+int PinSet::adopt_device(const phx_pin* d_src, int count, hipStream_t stream)
+{
+    host_.resize((size_t)count);
+    dirty_ = true; sched_dirty_ = true;
+    if (!count) return PHX_OK;
+    // (the bodies and anchors are needed on the host for the schedule and the later edits: the list comes down once, O(pins))
+    PHX_HIP(hipMemcpyAsync(host_.data(), d_src, (size_t)count * sizeof(phx_pin), hipMemcpyDeviceToHost, stream));
+    PHX_HIP(hipStreamSynchronize(stream));
+    return PHX_OK;
+}
+
+int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
+{
+    const int n = count();
+    if (!n) return PHX_OK;
+    PHX_TRY(upload(stream));
+    if (!sched_dirty_) return PHX_OK;
+    PHX_TRY(d_bits_.reserve((size_t)n));
+    hipLaunchKernelGGL(k_pin_statics, dim3(pgrid(n)), dim3(256), 0, stream, (const phx_pin*)d_pins_.p, n, mpos, d_bits_.p);
+    PHX_HIP(hipGetLastError());
+    std::vector<unsigned> bits((size_t)n);
+    PHX_TRY(rb.add(bits.data(), d_bits_.p, (size_t)n * sizeof(unsigned), stream));
+    PHX_TRY(rb.wait(stream));
+    std::vector<unsigned char> is_static((size_t)nb, 0);
+    std::vector<int32_t> b1((size_t)n), b2((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const phx_pin& p = host_[(size_t)k];
+        b1[(size_t)k] = p.body1; b2[(size_t)k] = p.body2;
+        if (bits[(size_t)k] & 1u) is_static[(size_t)p.body1] = 1;
+        if (p.body2 >= 0 && (bits[(size_t)k] & 2u)) is_static[(size_t)p.body2] = 1;
+    }
+    build_pin_schedule(b1.data(), b2.data(), n, is_static.data(), nb, group_pins_, sched_);
+    ++builds_;
+    const Schedule& s = sched_;
+    // the kernels' tables: a slot per pin, a record per LDS group, the LDS groups' bodies (the world: -1)
+    const int lds_slots = s.lds_groups ? s.group_offsets[(size_t)s.lds_groups] : 0;
+    std::vector<PinSlot> slots((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const phx_pin& p = host_[(size_t)s.order[(size_t)k]];
+        if (k < lds_slots) {
+            const uint32_t local = s.slot_local[(size_t)k];
+            slots[(size_t)k] = PinSlot{s.order[(size_t)k], (int)(local & 0xFFFFu), p.body2 >= 0 ? (int)(local >> 16) : -1, (int)s.slot_colour[(size_t)k]};
+        } else slots[(size_t)k] = PinSlot{s.order[(size_t)k], p.body1, p.body2, 0};
+    }
+    std::vector<PinGroup> groups((size_t)s.lds_groups);
+    std::vector<int> gbodies(s.group_bodies);
+    for (int g = 0; g < s.lds_groups; ++g) {
+        PinGroup& G = groups[(size_t)g];
+        G.slot_begin = s.group_offsets[(size_t)g]; G.slot_end = s.group_offsets[(size_t)g + 1];
+        G.body_begin = s.group_body_offsets[(size_t)g]; G.body_count = s.group_body_offsets[(size_t)g + 1] - G.body_begin;
+        G.classes = s.group_first_colour[(size_t)g + 1] - s.group_first_colour[(size_t)g];
+        G.first_dynamic = 0; G.pad0 = G.pad1 = 0;
+        for (int i = 0; i < G.body_count; ++i) {
+            int& b = gbodies[(size_t)(G.body_begin + i)];
+            const bool fixed = b == nb || is_static[(size_t)b];
+            if (fixed) {
+                if (G.first_dynamic != i) { set_error("pin schedule: a static body behind a dynamic one in a group's body table"); return PHX_ERR_STATE; }
+                G.first_dynamic = i + 1;
+            }
+            if (b == nb) b = -1;
+        }
+        if (G.slot_end - G.slot_begin > PIN_LANES || G.body_count > PIN_BODIES) { set_error("pin schedule: a group exceeds the workgroup"); return PHX_ERR_STATE; }
+    }
+    hbm_classes_ = s.hbm_colour_offsets;
+    auto pad16 = [](size_t v) { return (v + 15) & ~size_t(15); };
+    off_groups_ = pad16(slots.size() * sizeof(PinSlot));
+    off_bodies_ = off_groups_ + pad16(groups.size() * sizeof(PinGroup));
+    std::vector<char> blob(off_bodies_ + pad16(gbodies.size() * sizeof(int)) + 16, 0);
+    std::memcpy(blob.data(), slots.data(), slots.size() * sizeof(PinSlot));
+    if (!groups.empty()) std::memcpy(blob.data() + off_groups_, groups.data(), groups.size() * sizeof(PinGroup));
+    if (!gbodies.empty()) std::memcpy(blob.data() + off_bodies_, gbodies.data(), gbodies.size() * sizeof(int));
+    PHX_HIP(hipStreamSynchronize(stream));                                  // (a pass still queued may read the old tables)
+    PHX_TRY(d_tables_.reserve(blob.size()));
+    PHX_HIP(hipMemcpyAsync(d_tables_.p, blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
+    PHX_HIP(hipStreamSynchronize(stream));                                  // (`blob` is a local)
+    if (s.has_hbm_group()) PHX_TRY(d_work_.reserve((size_t)(s.hbm_end() - s.hbm_begin()) * sizeof(PinWork)));
+    sched_dirty_ = false;
+    return PHX_OK;
+}
+
+int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hipStream_t stream)
+{
+    if (!count()) return PHX_OK;
+    PHX_TRY(prepare(bodies.s.mpos, nb, rb, stream));
+    const float beta = 0.2f / dt;
+    const PinSlot* slots = reinterpret_cast<const PinSlot*>(d_tables_.p);
+    if (sched_.lds_groups)
+        hipLaunchKernelGGL(k_solve_pins, dim3(sched_.lds_groups), dim3(PIN_LANES), 0, stream, d_pins_.p, slots, reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_),
+                           reinterpret_cast<const int*>(d_tables_.p + off_bodies_), bodies.s.vel, (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, iterations);
+    if (hbm_classes_.size() > 1) {
+        const int begin = hbm_classes_.front(), end = hbm_classes_.back();
+        PinWork* work = reinterpret_cast<PinWork*>(d_work_.p);
+        hipLaunchKernelGGL(k_pin_prestep, dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins_.p, slots, begin, end, (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, work);
+        for (int sweep = 0; sweep <= iterations; ++sweep)
+            for (size_t c = 0; c + 1 < hbm_classes_.size(); ++c) {
+                const int b = hbm_classes_[c], e = hbm_classes_[c + 1];
+                if (e > b) hipLaunchKernelGGL(k_pin_class, dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins_.p, slots, b, e, begin, (const PinWork*)work, bodies.s.vel, sweep);
+            }
+    }
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+} // namespace phx
+
+// ---- C ABI: the host-only builder (the world's calls: world.hip) ----
+extern "C" int phx_pin_schedule(const int32_t* body1, const int32_t* body2, int32_t pin_count, const uint8_t* is_static, int32_t body_count, int32_t group_pins,
+                                int32_t* order, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
+                                int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count)
+{
+    PHX_REQUIRE(pin_count >= 0 && body_count >= 0 && (pin_count == 0 || (body1 && body2)) && (body_count == 0 || is_static) && class_count && group_count && lds_group_count,
+                "phx_pin_schedule: bad arguments");
+    PHX_REQUIRE(group_pins >= 1 && group_pins <= phx::PIN_LANES, "phx_pin_schedule: group_pins out of [1, 256]");
+    for (int k = 0; k < pin_count; ++k)
+        PHX_REQUIRE((unsigned)body1[k] < (unsigned)body_count && (body2[k] == -1 || (unsigned)body2[k] < (unsigned)body_count) && body1[k] != body2[k], "phx_pin_schedule: bad body index");
+    phx::Schedule s;
+    phx::build_pin_schedule(body1, body2, pin_count, is_static, body_count, group_pins, s);
+    *class_count = (int)s.colour_offsets.size() - 1; *group_count = s.ngroups(); *lds_group_count = s.lds_groups;
+    if (!order && !class_offsets && !group_offsets) return PHX_OK;
+    if ((pin_count && !order) || !class_offsets || !group_offsets) { phx::set_error("phx_pin_schedule: null output"); return PHX_ERR_INVALID; }
+    if ((int)s.colour_offsets.size() > class_cap || s.ngroups() + 1 > group_cap) { phx::set_error("phx_pin_schedule: offsets arrays too small"); return PHX_ERR_CAPACITY; }
+    std::copy(s.order.begin(), s.order.end(), order);
+    std::copy(s.colour_offsets.begin(), s.colour_offsets.end(), class_offsets);
+    std::copy(s.group_offsets.begin(), s.group_offsets.end(), group_offsets);
+    return PHX_OK;
+}

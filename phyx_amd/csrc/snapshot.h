@@ -39,6 +39,12 @@ public:
 
     int save(const SnapshotWorld& w, hipStream_t stream);      // queued on `stream` behind the loads that still read the old contents
     int load(const SnapshotWorld& w, hipStream_t stream);      // queued on `stream` behind the save that wrote the contents
+    // the world's pins (include/phyx_amd.h PINS) ride beside the blob's layout, which holds none: room first (nothing changes if that
+    // fails), then a device copy queued behind the save, in front of the event the loads wait for
+    int reserve_pins(int count, hipStream_t stream) { return pins_.reserve_keep((size_t)std::max(count, 1), (size_t)pin_count_, stream); }      // (a save that fails afterwards leaves the old pins whole)
+    int save_pins(const phx_pin* d_pins, int count, hipStream_t stream);
+    const phx_pin* pins() const { return pins_.p; }
+    int pin_count() const { return pin_count_; }
     int blob_bytes(size_t* bytes) const;
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
@@ -46,6 +52,9 @@ public:
 private:
     int settle();                        // the host waits for the queued save and loads (export, import, destroy)
     int refuse_empty(const char* what) const;
+    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins
+    DevBuf<phx_pin> pins_;
+    int pin_count_ = 0;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

@@ -43,6 +43,22 @@ int Snapshot::refuse_empty(const char* what) const
     return PHX_ERR_STATE;
 }
 
+int Snapshot::refuse_pins(const char* what) const
+{
+    if (!pin_count_) return PHX_OK;
+    set_error("%s: the snapshot holds %d pins, which the blob (layout version 1) does not carry", what, pin_count_);
+    return PHX_ERR_STATE;
+}
+
+int Snapshot::save_pins(const phx_pin* d_pins, int count, hipStream_t stream)
+{
+    pin_count_ = count;
+    if (!count) return PHX_OK;
+    PHX_HIP(hipMemcpyAsync(pins_.p, d_pins, (size_t)count * sizeof(phx_pin), hipMemcpyDeviceToDevice, stream));
+    PHX_HIP(hipEventRecord(saved_, stream));                                // (the event moves behind the copy)
+    return PHX_OK;
+}
+
 // the largest walk of a launch: the bodies, or the granules of the largest array
 static unsigned long long snap_items(const SnapTable& t)
 {
@@ -109,6 +125,7 @@ int Snapshot::load(const SnapshotWorld& w, hipStream_t stream)
 int Snapshot::blob_bytes(size_t* bytes) const
 {
     PHX_TRY(refuse_empty("phx_snapshot_blob_bytes"));
+    PHX_TRY(refuse_pins("phx_snapshot_blob_bytes"));
     *bytes = (size_t)layout_.total;
     return PHX_OK;
 }
@@ -116,6 +133,7 @@ int Snapshot::blob_bytes(size_t* bytes) const
 int Snapshot::export_blob(void* blob, size_t cap)
 {
     PHX_TRY(refuse_empty("phx_snapshot_export"));
+    PHX_TRY(refuse_pins("phx_snapshot_export"));
     if (!blob) { set_error("phx_snapshot_export: null buffer"); return PHX_ERR_INVALID; }
     if ((uint64_t)cap < layout_.total) { set_error("phx_snapshot_export: the blob needs %llu bytes, room for %zu", (unsigned long long)layout_.total, cap); return PHX_ERR_CAPACITY; }
     PHX_TRY(use_device(device_));
@@ -137,7 +155,7 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     const size_t rest = (size_t)(l.total - SNAP_HEADER_BYTES);
     PHX_TRY(buf_.reserve(rest / 16));
     if (rest) PHX_HIP(hipMemcpy(buf_.p, static_cast<const unsigned char*>(blob) + SNAP_HEADER_BYTES, rest, hipMemcpyHostToDevice));
-    counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true;
+    counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true; pin_count_ = 0;
     return PHX_OK;
 }
 

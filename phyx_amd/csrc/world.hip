@@ -15,6 +15,7 @@
 #include "query.h"
 #include "contact.h"
 #include "snapshot.h"
+#include "pins.h"
 
 #include <algorithm>
 #include <chrono>
@@ -192,6 +193,15 @@ public:
     int set_body_flags(const int32_t* bodies, const uint32_t* flags, int count);
     int get_body_flags(uint32_t* out, int cap);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
+    // pins (phx_world_add_pins ... phx_world_get_pin_schedule): between steps; solved at the end of pre_solve (pins.h)
+    int add_pins(const phx_pin* pins, int count, int* first);
+    int remove_pins(const int32_t* which, int count);
+    int set_pin_anchors(const int32_t* which, const float* anchors, int count);
+    int get_pins(phx_pin* out, int cap);
+    int set_pin_iterations(int n);
+    int pin_schedule(const Schedule** out);
+    int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin exists (the sharded modes carry none)
+    PinSet& pins() { return pins_; }
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
 
     int nb() const { return (int)host_bodies_.size(); }
@@ -313,6 +323,8 @@ private:
     BodyTable<MaterialColumn> materials_;
     BodyTable<FlagsColumn> flags_col_;
     template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); return f(flags_col_); }
+    PinSet pins_;
+    int check_pin_indices(const char* what, const int32_t* which, const void* values, int count);
     BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr()}; }
     BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr()}; }
 };
@@ -338,6 +350,7 @@ int World::init()
     PHX_TRY(solver_.adopt_stream(stream_));
     PHX_TRY(counters_.reserve(8));
     PHX_TRY(query_.configure_from_env());
+    PHX_TRY(pins_.configure_from_env());
     return contacts_.configure_from_env();
 }
 
@@ -394,6 +407,7 @@ int World::set_static(int body)
     host_bodies_[body].inv_mass = 0.f;
     host_bodies_[body].inv_inertia = 0.f;
     bodies_dirty_ = true;
+    pins_.statics_changed();
     return PHX_OK;
 }
 
@@ -404,6 +418,7 @@ int World::set_inverse_mass(int body, float inv_mass, float inv_inertia)
     host_bodies_[body].inv_inertia = inv_inertia;
     bodies_dirty_ = true;
     joints_changed_ = true;              // which bodies are static is part of the schedule's topology
+    pins_.statics_changed();
     return PHX_OK;
 }
 
@@ -705,6 +720,8 @@ int World::pre_solve(float dt)
     if (flags_col_.active) PHX_TRY(solver_.cancel_prelabel());
     else if (!phase_timing) PHX_TRY(solver_.prelabel_mark());
     { RoctxRange r("RefreshContactJoints"); PHX_TRY(refresh_contact_joints()); lap(5); }             // ref: World.cpp:74
+    // the pins edit the velocities the contacts are then solved on (include/phyx_amd.h PINS); a world without pins queues nothing
+    if (pins_.count()) { RoctxRange r("SolvePins"); PHX_TRY(pins_.solve(resident(), nb(), dt, rb_, stream_)); }
     return PHX_OK;
 }
 
@@ -928,6 +945,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
+    pins_.clear();                                                          // ... and no pin is left
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -997,7 +1015,10 @@ int World::save(Snapshot& s)
     v.counts.bodies = nb(); v.counts.manifolds = nm; v.counts.joints = nj; v.counts.baseline = contacts_.baseline_count();
     v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
-    return s.save(v, stream_);
+    PHX_TRY(pins_.upload(stream_));
+    PHX_TRY(s.reserve_pins(pins_.count(), stream_));
+    PHX_TRY(s.save(v, stream_));
+    return s.save_pins(pins_.device_pins(), pins_.count(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -1033,7 +1054,8 @@ int World::load(Snapshot& s)
     ++contact_epoch_;
     // what set_state resets: the pair set becomes the saved manifolds' pairs, the schedule is rebuilt at the next step
     PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
-    return forget_step_history();
+    PHX_TRY(forget_step_history());
+    return pins_.adopt_device(s.pins(), s.pin_count(), stream_);            // 6. add_pins of the saved pins
 }
 
 int World::get_slab_state(const long long* global_index, int count, SlabState* out)
@@ -1322,7 +1344,8 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     contacts_.baseline_remapped(got[4]);
     records_stale_ = false;
     accel_pending_ = accel_pending_ && got[3] != 0;                         // (what the upload of the kept records would find)
-    return adopt_compaction(got);
+    PHX_TRY(adopt_compaction(got));
+    return pins_.bodies_removed(rm_remap_.p, rb_, stream_);                 // (the pins of the removed bodies go, the rest through new[])
 }
 
 // ---- spawn between steps ---------------------------------------------------------------------------------------------------------
@@ -1393,6 +1416,7 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
         if (!std::isfinite(values[k]) || !(values[k] >= 0.f)) { set_error("%s: entry %d: inverse masses must be finite and >= 0", what, k / 2); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     joints_changed_ = true;                                                 // which bodies are static is part of the schedule's topology
+    pins_.statics_changed();
     if (host_staged()) {
         for (int k = 0; k < count; ++k) { phx_rigid_body& b = host_bodies_[(size_t)bodies[k]]; b.inv_mass = values[2 * k]; b.inv_inertia = values[2 * k + 1]; }
         return PHX_OK;
@@ -1508,6 +1532,112 @@ int World::set_body_flags(const int32_t* bodies, const uint32_t* flags, int coun
     return flags_col_.set_device(d_bodies, d_values, count, n, stream_);
 }
 int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_get_body_flags", flags_col_, out, cap); }
+
+// ---- pins -------------------------------------------------------------------------------------------------------------------------
+// The rules and the arithmetic: include/phyx_amd.h PINS; the list, the schedule and the pass: pins.h.  The calls check everything first,
+// then change the list; the schedule follows lazily at the next step.
+int World::refuse_pins(const char* what)
+{
+    if (!pins_.count()) return PHX_OK;
+    set_error("%s: the world holds pins, which a sharded world does not carry", what);
+    return PHX_ERR_STATE;
+}
+
+int World::check_pin_indices(const char* what, const int32_t* which, const void* values, int count)
+{
+    PHX_TRY(refuse_mid_step(what));
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && (!which || !values)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    const int n = pins_.count();
+    std::vector<unsigned char> seen((size_t)n, 0);
+    for (int k = 0; k < count; ++k) {
+        if (which[k] < 0 || which[k] >= n) { set_error("%s: pin index %d out of range [0, %d)", what, which[k], n); return PHX_ERR_INVALID; }
+        if (seen[(size_t)which[k]]) { set_error("%s: pin %d appears twice in one call", what, which[k]); return PHX_ERR_INVALID; }
+        seen[(size_t)which[k]] = 1;
+    }
+    return PHX_OK;
+}
+
+int World::add_pins(const phx_pin* pins, int count, int* first)
+{
+    static const char* const what = "phx_world_add_pins";
+    PHX_TRY(refuse_mid_step(what));
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no pins", what); return PHX_ERR_STATE; }
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && !pins) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    if ((long long)pins_.count() + count > (long long)INT32_MAX) { set_error("%s: %d + %d pins exceed the int32 range", what, pins_.count(), count); return PHX_ERR_INVALID; }
+    const int n = nb();
+    for (int k = 0; k < count; ++k) {
+        const phx_pin& p = pins[k];
+        if (p.body1 < 0 || p.body1 >= n) { set_error("%s: pin %d: body1 %d out of range [0, %d)", what, k, p.body1, n); return PHX_ERR_INVALID; }
+        if (p.body2 < -1 || p.body2 >= n) { set_error("%s: pin %d: body2 %d is neither -1 nor in [0, %d)", what, k, p.body2, n); return PHX_ERR_INVALID; }
+        if (p.body1 == p.body2) { set_error("%s: pin %d: both ends on body %d", what, k, p.body1); return PHX_ERR_INVALID; }
+        const float v[6] = {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.impulse.x, p.impulse.y};
+        for (int c = 0; c < 6; ++c)
+            if (!std::isfinite(v[c])) { set_error("%s: pin %d: value %d is not finite", what, k, c); return PHX_ERR_INVALID; }
+    }
+    if (first) *first = pins_.count();
+    if (!count) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    return pins_.add(pins, count, stream_);
+}
+
+int World::remove_pins(const int32_t* which, int count)
+{
+    PHX_TRY(check_pin_indices("phx_world_remove_pins", which, which, count));
+    if (!count) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    return pins_.remove(which, count, stream_);
+}
+
+int World::set_pin_anchors(const int32_t* which, const float* anchors, int count)
+{
+    static const char* const what = "phx_world_set_pin_anchors";
+    PHX_TRY(check_pin_indices(what, which, anchors, count));
+    for (int k = 0; k < 4 * count; ++k)
+        if (!std::isfinite(anchors[k])) { set_error("%s: entry %d: value %d is not finite", what, k / 4, k % 4); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    const int* d_which = nullptr; const float* d_anchors = nullptr;
+    if (pins_.on_device()) {
+        PHX_TRY(use_device(device_));
+        if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+        PHX_TRY(stage_batch(which, anchors, count, 4, &d_which, &d_anchors));
+    }
+    return pins_.set_anchors(which, anchors, count, d_which, d_anchors, stream_);
+}
+
+int World::get_pins(phx_pin* out, int cap)
+{
+    const int n = pins_.count();
+    if (cap < n) { set_error("phx_world_get_pins: room for %d pins, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());
+    return pins_.get(out, stream_);
+}
+
+int World::set_pin_iterations(int n)
+{
+    PHX_TRY(refuse_mid_step("phx_world_set_pin_iterations"));
+    if (n < 1 || n > PIN_MAX_ITERATIONS) { set_error("phx_world_set_pin_iterations: %d is not in [1, %d]", n, PIN_MAX_ITERATIONS); return PHX_ERR_INVALID; }
+    pins_.iterations = n;
+    return PHX_OK;
+}
+
+int World::pin_schedule(const Schedule** out)
+{
+    PHX_TRY(refuse_mid_step("phx_world_get_pin_schedule"));
+    *out = nullptr;
+    if (!pins_.count()) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    PHX_TRY(pins_.prepare(bodies_.mpos.p, nb(), rb_, stream_));
+    *out = &pins_.schedule();
+    return PHX_OK;
+}
 
 // ---- queries ------------------------------------------------------------------------------------------------------------------------
 // Answered on the world's stream from the resident arrays (query.h / query_kernels.h).  The host forms check everything first, stage the
@@ -1752,6 +1882,7 @@ int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(count >= 1 && shard >= 0 && shard < count, "bad shard");
+    if (count > 1) PHX_TRY(w->impl.refuse_pins("phx_world_set_shard"));
     if (count > 1) PHX_TRY(w->impl.refuse_tables("phx_world_set_shard"));
     w->impl.shard = shard; w->impl.shard_count = count;
     PHX_TRY(w->impl.solver().set_shard(shard, count));
@@ -1793,6 +1924,7 @@ void* phx_world_stream(phx_world* w) { return w ? (void*)w->impl.stream() : null
 int phx_world_set_comm(phx_world* w, phx_comm* c)
 {
     PHX_REQUIRE(w, "null handle");
+    if (c) PHX_TRY(w->impl.refuse_pins("phx_world_set_comm"));
     if (c) PHX_TRY(w->impl.refuse_tables("phx_world_set_comm"));
     return w->impl.set_comm(c ? &c->impl : nullptr);
 }
@@ -2033,6 +2165,7 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
 {
     PHX_REQUIRE(w && global_index && body_count && bounds && moved, "null handle / arguments");
     PHX_REQUIRE(scene_size >= *body_count && capacity >= *body_count, "bad sizes");
+    PHX_TRY(w->impl.refuse_pins("phx_world_reslab"));
     PHX_TRY(w->impl.refuse_tables("phx_world_reslab"));
     phx::SlabTransport tp;
     PHX_TRY(slab_transport(transport, w->impl, &tp));
@@ -2047,6 +2180,79 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
                               st.joints.data(), (int)st.joints.size()));
     for (size_t k = 0; k < st.global_index.size(); ++k) global_index[k] = st.global_index[k];
     *body_count = (int32_t)st.bodies.size();
+    return PHX_OK;
+}
+
+int phx_world_add_pins(phx_world* w, const phx_pin* pins, int32_t count, int32_t* first)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.add_pins(pins, count, first);
+}
+
+int phx_world_remove_pins(phx_world* w, const int32_t* pins, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.remove_pins(pins, count);
+}
+
+int phx_world_set_pin_anchors(phx_world* w, const int32_t* pins, const float* anchors, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_pin_anchors(pins, anchors, count);
+}
+
+int phx_world_get_pins(phx_world* w, phx_pin* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_pins(out, cap);
+}
+
+int phx_world_pin_count(phx_world* w, int32_t* count)
+{
+    PHX_REQUIRE(w && count, "null handle / output");
+    *count = w->impl.pins().count();
+    return PHX_OK;
+}
+
+int phx_world_set_pin_iterations(phx_world* w, int32_t n)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_pin_iterations(n);
+}
+
+int phx_world_get_pin_iterations(phx_world* w, int32_t* n)
+{
+    PHX_REQUIRE(w && n, "null handle / output");
+    *n = w->impl.pins().iterations;
+    return PHX_OK;
+}
+
+int phx_world_pin_schedule_builds(phx_world* w, int64_t* builds)
+{
+    PHX_REQUIRE(w && builds, "null handle / output");
+    *builds = w->impl.pins().builds();
+    return PHX_OK;
+}
+
+int phx_world_get_pin_schedule(phx_world* w, int32_t* order, int32_t order_cap, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
+                               int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count)
+{
+    PHX_REQUIRE(w && class_count && group_count && lds_group_count, "null handle / output");
+    const phx::Schedule* s = nullptr;
+    PHX_TRY(w->impl.pin_schedule(&s));
+    *class_count = s ? (int)s->colour_offsets.size() - 1 : 0;
+    *group_count = s ? s->ngroups() : 0;
+    *lds_group_count = s ? s->lds_groups : 0;
+    if (!order && !class_offsets && !group_offsets) return PHX_OK;
+    PHX_REQUIRE(class_offsets && group_offsets && (order || !s), "phx_world_get_pin_schedule: null output");
+    const int n = s ? (int)s->order.size() : 0;
+    if (order_cap < n || class_cap < *class_count + 1 || group_cap < *group_count + 1) { phx::set_error("phx_world_get_pin_schedule: arrays too small"); return PHX_ERR_CAPACITY; }
+    class_offsets[0] = 0; group_offsets[0] = 0;
+    if (!s) return PHX_OK;
+    std::copy(s->order.begin(), s->order.end(), order);
+    std::copy(s->colour_offsets.begin(), s->colour_offsets.end(), class_offsets);
+    std::copy(s->group_offsets.begin(), s->group_offsets.end(), group_offsets);
     return PHX_OK;
 }
 

@@ -1,0 +1,95 @@
+"""The cost of the pin pass (include/phyx_amd.h PINS): a synchronised World::Update of one world of hanging chains, with and without
+its pins, on the same build.
+
+    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--import-from DIR]
+
+The world: a ground and `chains` chains of `links` links (boxes of 2 x 8, 10 apart), each hung from a world pin, side by side.  The
+pinned world runs under gravity (the pins carry the chains); the pinless twin has the same bodies and gravity 0, so that they stay
+where they are and the rest of the step — broadphase, narrowphase, the empty contact solve — sees the same load.  Each repeat times
+`steps` updates between two synchronisations with the host clock, the two worlds alternating; the result is one JSON line per world
+with the median and every repeat.  --no-pins times the pinless world alone, and --import-from takes phyx_amd from another tree (a
+build of the parent commit), which together give the parent's time for the same world.  The pass's own kernel time comes from a
+kernel trace of `--steps N --repeats 1` (k_solve_pins in the statistics), in a run of its own.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+
+def build(phyx_amd, chains, links, pinned, spacing=10.0):
+    pw = phyx_amd.World(0, gravity=-200.0 if pinned else 0.0)
+    pw.AddBody((0.0, 0.0), 0.0, (8.0 * chains + 100.0, 10.0), static=True)
+    rows = np.zeros((chains * links, 5), dtype=np.float32)
+    c, k = np.divmod(np.arange(chains * links), links)
+    top = 40.0 + spacing * links
+    rows[:, 0] = 8.0 * (c - chains / 2.0)
+    rows[:, 1] = top - spacing * (k + 0.5)
+    rows[:, 3], rows[:, 4] = 1.0, 4.0
+    for r in rows:
+        pw.AddBody((float(r[0]), float(r[1])), 0.0, (float(r[3]), float(r[4])))
+    if pinned:
+        from phyx_amd.api import pin_dtype
+        pins = np.zeros(chains * links, dtype=pin_dtype)
+        body = 1 + np.arange(chains * links)
+        pins["body1"] = body
+        pins["body2"] = np.where(k == 0, -1, body - 1)
+        pins["anchor1"] = (0.0, spacing / 2.0)
+        pins["anchor2"] = (0.0, -spacing / 2.0)
+        heads = k == 0
+        pins["anchor2"][heads, 0] = rows[heads, 0]
+        pins["anchor2"][heads, 1] = top
+        pw.add_pins(pins)
+    return pw
+
+
+def timed(pw, cfg, steps, dt=1.0 / 60.0):
+    pw.sync()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        pw.Update(dt, cfg)
+    pw.sync()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--chains", type=int, default=4096)
+    ap.add_argument("--links", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=60)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--iterations", type=int, default=32, help="pin sweeps per step (a hanging chain of 16 links is not stable at the default 8)")
+    ap.add_argument("--no-pins", action="store_true")
+    ap.add_argument("--import-from", default=None)
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.import_from) if a.import_from else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import phyx_amd
+    cfg = phyx_amd.Configuration(phyx_amd.SOLVE_AVX2, phyx_amd.ISLAND_MULTIPLE_SLOPPY, 15, 15)
+    worlds = {} if a.no_pins else {"pins": build(phyx_amd, a.chains, a.links, True)}
+    worlds["pinless"] = build(phyx_amd, a.chains, a.links, False)
+    if not a.no_pins:
+        worlds["pins"].pin_iterations = a.iterations
+    for pw in worlds.values():
+        timed(pw, cfg, a.warmup)
+    times = {name: [] for name in worlds}
+    for _ in range(a.repeats):
+        for name, pw in worlds.items():
+            times[name].append(timed(pw, cfg, a.steps))
+    for name, pw in worlds.items():
+        out = {"world": name, "tree": os.path.dirname(os.path.abspath(phyx_amd.__file__)), "chains": a.chains, "links": a.links, "bodies": pw.counts()[0],
+               "manifolds": pw.counts()[1], "steps": a.steps, "ms_per_step_median": round(statistics.median(times[name]), 4),
+               "ms_per_step": [round(t, 4) for t in times[name]]}
+        if name == "pins":
+            s = pw.pin_schedule()
+            out.update(pins=pw.pin_count(), lds_groups=s["lds_groups"], groups=len(s["group_offsets"]) - 1, classes=len(s["class_offsets"]) - 1,
+                       iterations=pw.pin_iterations, schedule_builds=pw.pin_schedule_builds(), impulse_max=float(np.abs(pw.pins()["impulse"]).max()))
+        print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
