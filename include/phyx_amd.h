@@ -808,7 +808,8 @@ int  phx_snapshot_blob_pack(const phx_rigid_body* bodies, int32_t body_count, co
  *     project it with n x r, ref: Solver.cpp:559), so that is the velocity its w gives the point r, and P at r changes w by -i (r x P):
  *         C    = (posB + rb) - (posA + ra)                      (world pin: anchor2 - (posA + ra))
  *         k11  = mA + mB + iA ra.y^2 + iB rb.y^2,  k12 = -iA ra.x ra.y - iB rb.x rb.y,  k22 = mA + mB + iA ra.x^2 + iB rb.x^2
- *         det  = k11 k22 - k12^2;  a pin with !(det > 0) is INACTIVE this step: impulse := 0, nothing else
+ *         det  = k11 k22 - k12^2;  a pin with !(det > 2^-20 (k11 k22)) is INACTIVE this step: impulse := 0, nothing else (the floor is
+ *                the float32 det expression's rounding noise, at most 14 x 2^-24 k11 k22: a singular K - invMass 0, invInertia > 0, pinned off-centre - is not solved with 1/noise)
  *         bias = C * (0.2f / dt);  warm start: apply impulse;  n sweeps: cdot = (vB + wB x rb) - (vA + wA x ra), rhs = -(cdot + bias),
  *         d = (1/det) * (k22 rhs.x - k12 rhs.y, k11 rhs.y - k12 rhs.x), impulse += d, apply d
  *         apply P: vA -= mA P, wA += iA (ra.x P.y - ra.y P.x), vB += mB P, wB -= iB (rb.x P.y - rb.y P.x)   (a static body is not written)

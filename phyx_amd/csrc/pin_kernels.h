@@ -56,7 +56,7 @@ __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* _
     r.k12 = -((r.ia * r.rax) * r.ray) - (r.ib * r.rbx) * r.rby;
     r.k22 = (ms + (r.ia * r.rax) * r.rax) + (r.ib * r.rbx) * r.rbx;
     const float det = r.k11 * r.k22 - r.k12 * r.k12;
-    r.active = det > 0.f;
+    r.active = det > 0x1p-20f * (r.k11 * r.k22);              // above the rounding noise of the det expression (pin_spec.py DET_FLOOR)
     r.inv_det = 1.0f / det;
     r.biasx = cx * beta; r.biasy = cy * beta;
     r.px = r.active ? p.impulse.x : 0.f;

@@ -19,6 +19,20 @@ import numpy as np
 F = np.float32
 BETA = F(0.2)
 
+# The activity rule: a pin is active where det > DET_FLOOR * (k11 * k22), both sides in float32 as written in prestep.
+# K is singular in real arithmetic where nothing resists the impulse along some direction: no inverse mass on either side and
+# lever arms that are parallel (or one body that cannot turn, or an anchor at a centre) — a wheel on a fixed axle pinned off-centre
+# to the world, two such wheels pinned on the line through their axles.  There det = k11 k22 - k12^2 is exactly 0 and the float32
+# expression returns its own rounding error, which `det > 0` took for a determinant (1/det of noise; the body left spinning).
+# How large that error is, in units of u = 2^-24 (one rounding) times k11 k22, to first order: with ms = 0 each of k11, k22 is per
+# body a term of two rounded products, and one rounded sum of two non-negative terms (which adds 1 u to the larger of their errors):
+# 3 u each, their rounded product 7 u.  k12's two terms have the same sign where the arms are parallel, so likewise 3 u, squared 6 u,
+# the rounded square 7 u, and k12^2 = k11 k22 there.  The difference rounds relative to its result and cannot change its sign.  So
+# the noise is at most 14 u k11 k22 (10 u for the single wheel, whose second body contributes nothing), and 16 u = 2^-20 clears it.
+# A well-posed pin is nowhere near: det / (k11 k22) >= 1 / cond(K), and a pin of condition 1e6 has lost every digit float32
+# could give its impulse anyway.
+DET_FLOOR = F(2.0 ** -20)
+
 
 class _Pin:
     __slots__ = ("a", "b", "rax", "ray", "rbx", "rby", "k11", "k12", "k22", "inv_det", "biasx", "biasy", "ma", "ia", "mb", "ib",
@@ -56,7 +70,7 @@ def prestep(bodies, pin, beta):
     p.k12 = -((p.ia * p.rax) * p.ray) - (p.ib * p.rbx) * p.rby
     p.k22 = (ms + (p.ia * p.rax) * p.rax) + (p.ib * p.rbx) * p.rbx
     det = p.k11 * p.k22 - p.k12 * p.k12
-    p.active = bool(det > 0)
+    p.active = bool(det > DET_FLOOR * (p.k11 * p.k22))
     with np.errstate(divide="ignore", invalid="ignore"):
         p.inv_det = F(1) / det
     p.biasx, p.biasy = cx * beta, cy * beta

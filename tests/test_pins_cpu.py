@@ -1,10 +1,12 @@
 """Pins without a GPU (include/phyx_amd.h PINS): the new symbols, the host-only schedule builder on small graphs, and the specification
-(tests/pin_spec.py) on its own — it is the only reference the feature has, so it must hold a pendulum and a chain together."""
+(tests/pin_spec.py) on its own: it must hold a pendulum and a chain together (tests/test_pin_corpus_cpu.py holds it to an independent
+float64 reference)."""
 import numpy as np
 import pytest
 
 import phyx_amd
 from phyx_amd import _lib, api
+import pin_corpus
 import pin_spec
 
 SYMBOLS = ("phx_world_add_pins", "phx_world_remove_pins", "phx_world_set_pin_anchors", "phx_world_get_pins", "phx_world_pin_count",
@@ -52,29 +54,8 @@ GRAPHS = ("world_pin", "pair", "chain3", "chain40_cap16", "pairs300", "pendulums
 def test_pin_schedule_on_small_graphs(built_lib, name):
     b1, b2, st, cap = _graph(name)
     s = api.pin_schedule(b1, b2, st, group_pins=cap)
-    n = len(b1)
-    order, coff, goff = s["order"], s["class_offsets"], s["group_offsets"]
-    assert sorted(order.tolist()) == list(range(n)), "every pin appears once"
-    assert coff[0] == 0 and coff[-1] == n and goff[0] == 0 and goff[-1] == n
-    assert (np.diff(coff) > 0).all() and (np.diff(goff) > 0).all()
-    assert set(goff.tolist()) <= set(coff.tolist()), "a class never spans two groups"
-    assert 0 <= s["lds_groups"] <= len(goff) - 1 and len(goff) - 1 - s["lds_groups"] <= 1, "at most one trailing group"
-
-    def dynamic(k):
-        return {b for b in (b1[k], b2[k]) if b >= 0 and not st[b]}
-
-    for c in range(len(coff) - 1):                      # the classes share no dynamic body
-        seen = set()
-        for k in order[coff[c]:coff[c + 1]]:
-            d = dynamic(int(k))
-            assert not (seen & d), "class %d of %s shares a dynamic body" % (c, name)
-            seen |= d
-    owner = {}
-    for g in range(len(goff) - 1):                      # the groups are body-disjoint, statics and the world aside
-        assert goff[g + 1] - goff[g] <= cap or g >= s["lds_groups"], "an LDS group exceeds the cap"
-        for k in order[goff[g]:goff[g + 1]]:
-            for b in dynamic(int(k)):
-                assert owner.setdefault(b, g) == g, "body %d is in two groups" % b
+    pin_corpus.check_schedule(b1, b2, st, s, cap, name)          # every pin once, classes and groups body-disjoint, the cap kept
+    coff, goff = s["class_offsets"], s["group_offsets"]
     if name == "pendulums50":
         assert len(coff) - 1 == 1, "50 pendulums on one static body need one class"
     if name == "chain40_cap16":
