@@ -847,13 +847,56 @@ int  phx_world_get_pin_iterations(phx_world* w, int32_t* n);
 int  phx_world_pin_schedule_builds(phx_world* w, int64_t* builds);
 /* The schedule the next step's pin pass uses (built now unless current; between steps only): order[k] = the pin in slot k, class c owns
  * slots [class_offsets[c], class_offsets[c + 1]), group g owns slots [group_offsets[g], group_offsets[g + 1]); the first *lds_group_count
- * groups run one workgroup each out of LDS, the rest (at most one) out of HBM.  Pass NULL arrays (cap 0) to ask for the counts. */
+ * groups run one workgroup each out of LDS, the rest (at most one) out of HBM.  Pass NULL arrays (cap 0) to ask for the counts.
+ * With links (LINKS) the slots hold units - pins, then links - and order needs room for pin_count + link_count of them. */
 int  phx_world_get_pin_schedule(phx_world* w, int32_t* order, int32_t order_cap, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
                                 int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count);
 /* host only, no device needed: the same schedule from the pins' bodies (body2 = -1: the world) and the bodies' static flags */
 int  phx_pin_schedule(const int32_t* body1, const int32_t* body2, int32_t pin_count, const uint8_t* is_static, int32_t body_count, int32_t group_pins,
                       int32_t* order, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
                       int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count);
+
+/* LINKS — constrain the DISTANCE between a point of one body and a point of another, or of the world (body2 = -1): a rigid rod, a rope
+ * that is slack until it is taut, a spring (a soft drag where a pin pulls hard).  tests/link_spec.py is the definition (scalar float32,
+ * every operation rounded on its own, no fused multiply-add, IEEE division, correctly rounded square root) and the device matches it byte
+ * for byte.  Links are solved IN the pin pass: its units are the pins followed by the links (unit u < pin_count is pin u, otherwise link
+ * u - pin_count), one schedule, one launch, one Gauss-Seidel sweep in which a rope tied to a chain link interleaves with the chain's pins.
+ * Wherever PINS says "pin" of the schedule it means a unit: PHX_PIN_GROUP_PINS caps units per group, phx_world_set_pin_iterations is the
+ * pass's sweep count, phx_world_get_pin_schedule returns units (order_cap >= pin_count + link_count), phx_world_pin_schedule_builds
+ * counts the builds of the one schedule, which add_links / remove_links rebuild in addition to PINS' causes.
+ *   - Anchors and bodies as for a pin.  impulse is the accumulated scalar impulse along the axis: the warm start, 0 for a new link.
+ *     With ra, rb the rotated anchors exactly as the pin's:
+ *         d = (posB + rb) - (posA + ra),  len = sqrt(d.x d.x + d.y d.y),  n = d / len,  kinv = mA + mB + iA (ra x n)^2 + iB (rb x n)^2
+ *     A link with !(len > 2^-10) or !(kinv > 0) is INACTIVE this step: impulse := 0, nothing else (below 2^-10 the axis is the rounding
+ *     noise of the position subtraction; kinv <= 0: both ends static or the world).
+ *   - The kind follows from the data:
+ *         rod     min_length == max_length == L, hertz == 0: C = len - L, impulse unbounded, bias = C (0.2f / dt), gamma = 0
+ *         spring  min_length == max_length == L, hertz > 0 (the Box2D soft constraint): mass = 1 / kinv, w = 6.2831855f hertz,
+ *                 dmp = 2 mass damping_ratio w, k = mass w^2, gamma = 1 / (dt (dmp + dt k)), bias = C dt k gamma, kinv += gamma
+ *         rope / limits  min_length < max_length, hertz == 0: the engaged limit is decided at the prestep - len >= max: C = len - max,
+ *                 impulse <= 0; len <= min: C = len - min, impulse >= 0; otherwise the link is IDLE this step: impulse := 0, nothing
+ *                 else.  A rope is min_length = 0.  This is deliberately NOT speculative: a limit engages the step after the length
+ *                 overshoots it, and the bias (that of the rod) pulls it back; until then the bodies move exactly as without the link.
+ *     warm start: impulse clamped to the engaged limit's range, P = impulse n applied with the pin's apply;  n sweeps:
+ *         cdot = n . ((vB + wB x rb) - (vA + wA x ra)),  d = -(1 / kinv) ((cdot + bias) + gamma impulse)
+ *         rod, spring: impulse += d, apply d n;  limits: new = clamp(impulse + d) (x < lo ? lo : x > hi ? hi : x, so a NaN passes),
+ *         apply (new - impulse) n, impulse = new
+ *   - The calls follow the pins' rules word for word (between steps, checked completely first, PHX_ERR_INVALID leaves the world
+ *     unchanged, an empty call is a no-op, before the first step the links wait on the host).  Checked: the pins' body rules, every float
+ *     finite, 0 <= min_length <= max_length, hertz >= 0, damping_ratio >= 0, hertz > 0 only with min_length == max_length, reserved == 0;
+ *     set_link_lengths is checked against the link's stored hertz.  set_link_anchors and set_link_lengths keep the schedule.
+ *   - The other calls, as for pins: remove_bodies / remove_outside drop the links of removed bodies and remap the rest; set_state drops
+ *     every link; save / load carry the links with their impulses in HBM; phx_snapshot_export and phx_snapshot_blob_bytes of a snapshot
+ *     that holds links return PHX_ERR_STATE (the blob stays layout version 1); set_shard (count > 1), set_comm, reslab and add_links on a
+ *     sharded world return PHX_ERR_STATE.  A world without links allocates and launches exactly what it did without them. */
+typedef struct { int32_t body1, body2; phx_vec2 anchor1, anchor2; float min_length, max_length; float hertz, damping_ratio;
+                 float impulse; uint32_t reserved; } phx_link;   /* 48 B */
+int  phx_world_add_links(phx_world* w, const phx_link* links, int32_t count, int32_t* first);   /* *first (may be NULL) = index of the first new link */
+int  phx_world_remove_links(phx_world* w, const int32_t* links, int32_t count);
+int  phx_world_set_link_anchors(phx_world* w, const int32_t* links, const float* anchors /* 4 per link: anchor1, anchor2 */, int32_t count);
+int  phx_world_set_link_lengths(phx_world* w, const int32_t* links, const float* lengths /* 2 per link: min, max */, int32_t count);
+int  phx_world_get_links(phx_world* w, phx_link* out, int32_t cap);
+int  phx_world_link_count(phx_world* w, int32_t* count);
 
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);

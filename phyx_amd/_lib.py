@@ -205,6 +205,12 @@ _SIGNATURES = {
     "phx_world_get_pin_iterations": (C.c_int, [_vp, C.POINTER(_i32)]),
     "phx_world_pin_schedule_builds": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "phx_world_get_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "phx_world_add_links": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
+    "phx_world_remove_links": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_set_link_anchors": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_set_link_lengths": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_get_links": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_link_count": (C.c_int, [_vp, C.POINTER(_i32)]),
     "phx_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "phx_snapshot_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "phx_snapshot_destroy": (None, [_vp]),

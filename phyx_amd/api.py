@@ -51,6 +51,9 @@ contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 pin_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("impulse", "<f4", (2,))])      # phx_pin
 assert pin_dtype.itemsize == 32
+link_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("min_length", "<f4"), ("max_length", "<f4"),
+                       ("hertz", "<f4"), ("damping_ratio", "<f4"), ("impulse", "<f4"), ("reserved", "<u4")])      # phx_link
+assert link_dtype.itemsize == 48
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
@@ -986,10 +989,10 @@ class World:
 
     def pin_schedule(self):
         """The schedule the next step's pin pass uses (built now unless current) -> dict with order, class_offsets, group_offsets,
-        lds_groups, as api.pin_schedule."""
+        lds_groups, as api.pin_schedule.  The slots hold units: unit u < pin_count() is pin u, otherwise link u - pin_count()."""
         nc = C.c_int32(0); ng = C.c_int32(0); lg = C.c_int32(0)
         check(self.L.phx_world_get_pin_schedule(self.h, None, 0, None, 0, C.byref(nc), None, 0, C.byref(ng), C.byref(lg)))
-        n = self.pin_count()
+        n = self.pin_count() + self.link_count()
         order = np.zeros(max(n, 1), dtype=np.int32)
         coff = np.zeros(nc.value + 1, dtype=np.int32); goff = np.zeros(ng.value + 1, dtype=np.int32)
         check(self.L.phx_world_get_pin_schedule(self.h, _ptr(order), n, _ptr(coff), len(coff), C.byref(nc), _ptr(goff), len(goff), C.byref(ng), C.byref(lg)))
@@ -999,6 +1002,55 @@ class World:
         n = C.c_int64(0)
         check(self.L.phx_world_pin_schedule_builds(self.h, C.byref(n)))
         return n.value
+
+    # ---- links (include/phyx_amd.h LINKS; the specification: tests/link_spec.py) ----
+    def add_links(self, links):
+        """Append links: a link_dtype array, or rows (body1, body2, (a1x, a1y), (a2x, a2y), min_length, max_length[, hertz[, damping_ratio]])
+        with impulse 0.  min == max: a rod, with hertz > 0 a spring; min < max: limits (a rope: min = 0).  Returns the new links' indices."""
+        if isinstance(links, np.ndarray) and links.dtype == link_dtype:
+            p = np.ascontiguousarray(links)
+        else:
+            rows = list(links)
+            p = np.zeros(len(rows), dtype=link_dtype)
+            for k, r in enumerate(rows):
+                p["body1"][k], p["body2"][k], p["anchor1"][k], p["anchor2"][k], p["min_length"][k], p["max_length"][k] = int(r[0]), int(r[1]), r[2], r[3], r[4], r[5]
+                if len(r) > 6:
+                    p["hertz"][k] = r[6]
+                if len(r) > 7:
+                    p["damping_ratio"][k] = r[7]
+        first = C.c_int32(0)
+        check(self.L.phx_world_add_links(self.h, _ptr(p), len(p), C.byref(first)))
+        return np.arange(first.value, first.value + len(p), dtype=np.int64)
+
+    def remove_links(self, links):
+        """Remove the listed links (each at most once); the others keep their order, so their indices shift."""
+        if isinstance(links, (list, tuple)) and not len(links):
+            links = np.zeros(0, dtype=np.int32)
+        idx = self._indices(links, "remove_links")
+        check(self.L.phx_world_remove_links(self.h, _ptr(idx), len(idx)))
+
+    def set_link_anchors(self, links, anchors):
+        """anchor1, anchor2 = anchors[k] {a1.x, a1.y, a2.x, a2.y} of link links[k]; the schedule stays (a spring to the cursor)."""
+        if isinstance(links, (list, tuple)) and not len(links):
+            links = np.zeros(0, dtype=np.int32)
+        self._edit("phx_world_set_link_anchors", links, anchors, 4, "set_link_anchors")
+
+    def set_link_lengths(self, links, lengths):
+        """min_length, max_length = lengths[k] of link links[k]; the schedule stays (a rope reeled in)."""
+        if isinstance(links, (list, tuple)) and not len(links):
+            links = np.zeros(0, dtype=np.int32)
+        self._edit("phx_world_set_link_lengths", links, lengths, 2, "set_link_lengths")
+
+    def link_count(self):
+        n = C.c_int32(0)
+        check(self.L.phx_world_link_count(self.h, C.byref(n)))
+        return n.value
+
+    def links(self):
+        """Every link as a link_dtype array, with the impulses the last step accumulated."""
+        out = np.zeros(self.link_count(), dtype=link_dtype)
+        check(self.L.phx_world_get_links(self.h, _ptr(out), len(out)))
+        return out
 
     # ---- collision filters (include/phyx_amd.h COLLISION FILTERS; the specification: tests/filter_spec.py) ----
     def set_collision_filters(self, bodies, category=1, mask=0xFFFFFFFF, group=0):

@@ -9,6 +9,10 @@
 //   k_pin_prestep /  the trailing group, out of HBM: the prestep leaves the lanes' registers in a work array, then one launch per
 //   k_pin_class      class for the warm start and per class and sweep (the fallback, not the fast path).
 // Static bodies (both inverses 0) and the world are read, never written: a class may share them among its lanes.
+//
+// Links (include/phyx_amd.h LINKS; the definition: tests/link_spec.py) are the pass's other kind of unit: unit u < npins is pin u, otherwise
+// link u - npins.  A link's prestep (link_prestep) fills the same registers under other names (PinRegs' unions), its sweep differs in the
+// delta only (link_delta) and ends in the same pin_apply.
 #pragma once
 
 #include "pins.h"
@@ -22,18 +26,26 @@ struct PinSlot { int pin; int a, b; int colour; };      // LDS groups: a, b loca
 struct PinGroup { int slot_begin, slot_end, body_begin, body_count; int first_dynamic, classes, pad0, pad1; };
 
 // what a lane keeps of its pin from the prestep on
+// (a link's names for the registers a pin calls otherwise: the axis n, gamma, 1/kinv, the scalar bias, the clamp's bounds, lambda)
 struct PinRegs {
     float rax, ray, rbx, rby;
-    float k11, k12, k22, inv_det;
-    float biasx, biasy;
+    union { float k11; float nx; };
+    union { float k12; float ny; };
+    union { float k22; float gamma; };
+    union { float inv_det; float inv_k; };
+    union { float biasx; float bias; };
+    union { float biasy; float lo; };
     float ma, ia, mb, ib;
-    float px, py;                       // the accumulated impulse
+    union { float px; float lambda; };  // the accumulated impulse
+    union { float py; float hi; };
     bool active, write_a, write_b;
+    bool link, clamps;                  // a link; one whose impulse is clamped to [lo, hi] (a rope or a limit)
 };
 
-__device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta)
+// the rotated anchors, the inverse masses and who is written; -> C = (posB + rb) - (posA + ra).  `P` is a phx_pin or a phx_link.
+template <class P>
+__device__ __forceinline__ void pin_anchors(const P& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, PinRegs& r, float& cx, float& cy)
 {
-    PinRegs r;
     const float4 qa = mpos[p.body1], fa = frame[p.body1];
     r.ma = qa.x; r.ia = qa.y;
     r.rax = fa.x * p.anchor1.x + fa.z * p.anchor1.y;
@@ -50,7 +62,17 @@ __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* _
         r.mb = 0.f; r.ib = 0.f; r.rbx = 0.f; r.rby = 0.f;
         pbx = p.anchor2.x; pby = p.anchor2.y;
     }
-    const float cx = pbx - pax, cy = pby - pay;
+    cx = pbx - pax; cy = pby - pay;
+    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
+    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+}
+
+__device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta)
+{
+    PinRegs r;
+    float cx, cy;
+    pin_anchors(p, mpos, frame, r, cx, cy);
+    r.link = false; r.clamps = false;
     const float ms = r.ma + r.mb;
     r.k11 = (ms + (r.ia * r.ray) * r.ray) + (r.ib * r.rby) * r.rby;
     r.k12 = -((r.ia * r.rax) * r.ray) - (r.ib * r.rbx) * r.rby;
@@ -61,8 +83,46 @@ __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* _
     r.biasx = cx * beta; r.biasy = cy * beta;
     r.px = r.active ? p.impulse.x : 0.f;
     r.py = r.active ? p.impulse.y : 0.f;
-    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
-    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+    return r;
+}
+
+// the clamp, written as comparisons so that a NaN passes through
+__device__ __forceinline__ float link_clamp(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// tests/link_spec.py prestep, operation for operation
+__device__ __forceinline__ PinRegs link_prestep(const phx_link& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt)
+{
+    PinRegs r;
+    float dx, dy;
+    pin_anchors(p, mpos, frame, r, dx, dy);
+    r.link = true;
+    const float len = sqrtf(dx * dx + dy * dy);                 // (sqrtf: correctly rounded under the library's flags)
+    r.nx = dx / len; r.ny = dy / len;
+    const float cra = r.rax * r.ny - r.ray * r.nx, crb = r.rbx * r.ny - r.rby * r.nx;
+    float kinv = ((r.ma + r.mb) + (r.ia * cra) * cra) + (r.ib * crb) * crb;
+    r.active = len > 0x1p-10f && kinv > 0.f;
+    const float inf = __builtin_inff();
+    float c;
+    r.clamps = p.min_length < p.max_length;
+    r.lo = -inf; r.hi = inf;
+    if (!r.clamps) c = len - p.min_length;
+    else if (len >= p.max_length) { c = len - p.max_length; r.hi = 0.f; }
+    else if (len <= p.min_length) { c = len - p.min_length; r.lo = 0.f; }
+    else { c = 0.f; r.active = false; }                        // idle this step
+    if (p.hertz > 0.f) {
+        const float mass = 1.0f / kinv;
+        const float omega = 6.2831855f * p.hertz;
+        const float dmp = ((2.0f * mass) * p.damping_ratio) * omega;
+        const float k = (mass * omega) * omega;
+        r.gamma = 1.0f / (dt * (dmp + dt * k));
+        r.bias = ((c * dt) * k) * r.gamma;
+        kinv = kinv + r.gamma;
+    } else {
+        r.gamma = 0.f;
+        r.bias = c * beta;
+    }
+    r.inv_k = 1.0f / kinv;
+    r.lambda = r.active ? link_clamp(p.impulse, r.lo, r.hi) : 0.f;
     return r;
 }
 
@@ -92,15 +152,43 @@ __device__ __forceinline__ void pin_delta(PinRegs& r, const float4& va, const fl
     r.py = r.py + dy;
 }
 
+// one sweep's impulse of the link, as a vector along its axis; accumulates lambda
+__device__ __forceinline__ void link_delta(PinRegs& r, const float4& va, const float4& vb, float& dx, float& dy)
+{
+    const float vbx = vb.x + vb.z * r.rby, vby = vb.y - vb.z * r.rbx;
+    const float vax = va.x + va.z * r.ray, vay = va.y - va.z * r.rax;
+    const float cdot = r.nx * (vbx - vax) + r.ny * (vby - vay);
+    float d = -(r.inv_k * ((cdot + r.bias) + r.gamma * r.lambda));
+    if (r.clamps) {
+        const float next = link_clamp(r.lambda + d, r.lo, r.hi);
+        d = next - r.lambda;
+        r.lambda = next;
+    } else r.lambda = r.lambda + d;
+    dx = d * r.nx; dy = d * r.ny;
+}
+
+// a unit's first impulse (the warm start) and its impulse of one sweep.  LINKS: the world has links; without them every kernel below
+// is the pins' alone, instruction for instruction what it was before there were links (a lane's branch on the kind costs the pass
+// 4 us of 30 on the world of DESIGN.md 5b, all pins: the launch is a chain of class steps, and each one pays for it).
+template <bool LINKS> __device__ __forceinline__ void unit_warm(const PinRegs& r, float& dx, float& dy)
+{
+    if (LINKS && r.link) { dx = r.lambda * r.nx; dy = r.lambda * r.ny; } else { dx = r.px; dy = r.py; }
+}
+template <bool LINKS> __device__ __forceinline__ void unit_delta(PinRegs& r, const float4& va, const float4& vb, float& dx, float& dy)
+{
+    if (LINKS && r.link) link_delta(r, va, vb, dx, dy); else pin_delta(r, va, vb, dx, dy);
+}
+
 // The LDS layout: one float4 per local body.  A lane's two bodies are anywhere in the table, so a class step is a gather / scatter of
 // 16-byte granules (ds_read_b128 / ds_write_b128).  A 16-byte read is served in four groups of 16 lanes over the 64 banks: a group
 // is conflict-free when its granules differ mod 16.  The two classes of a chain take every other pin, so a class's lanes sit two
 // granules apart and read two-way conflicted (8 LDS cycles instead of 4 per wave); the 16-byte store's cost is its register transfer
 // either way.  Both are small beside the dependent chain of a class step (read, ~20 dependent flops, write, barrier), which is what
 // the pass waits for.
-static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __restrict__ pins, const PinSlot* __restrict__ slots, const PinGroup* __restrict__ groups,
-                                                                 const int* __restrict__ group_bodies, float4* __restrict__ vel, const float4* __restrict__ mpos,
-                                                                 const float4* __restrict__ frame, float beta, int iterations)
+template <bool LINKS>
+static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots,
+                                                                 const PinGroup* __restrict__ groups, const int* __restrict__ group_bodies, float4* __restrict__ vel,
+                                                                 const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, int iterations)
 {
     __shared__ float4 sv[PIN_BODIES];
     const PinGroup g = groups[blockIdx.x];
@@ -115,7 +203,7 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     PinRegs r = {};
     if (mine) {
         s = slots[slot];
-        r = pin_prestep(pins[s.pin], mpos, frame, beta);
+        r = (!LINKS || s.pin < npins) ? pin_prestep(pins[s.pin], mpos, frame, beta) : link_prestep(links[s.pin - npins], mpos, frame, beta, dt);
     }
     const bool work = mine && r.active;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -123,7 +211,9 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     for (int c = 0; c < g.classes; ++c) {                                   // warm start, class by class
         if (work && s.colour == c) {
             float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-            pin_apply(r, r.px, r.py, va, vb);
+            float dx, dy;
+            unit_warm<LINKS>(r, dx, dy);
+            pin_apply(r, dx, dy, va, vb);
             if (r.write_a) sv[s.a] = va;
             if (r.write_b) sv[s.b] = vb;
         }
@@ -134,7 +224,7 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
             if (work && s.colour == c) {
                 float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
                 float dx, dy;
-                pin_delta(r, va, vb, dx, dy);
+                unit_delta<LINKS>(r, va, vb, dx, dy);
                 pin_apply(r, dx, dy, va, vb);
                 if (r.write_a) sv[s.a] = va;
                 if (r.write_b) sv[s.b] = vb;
@@ -142,62 +232,76 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
             __syncthreads();
         }
     for (int i = g.first_dynamic + (int)threadIdx.x; i < g.body_count; i += PIN_LANES) vel[bodies[i]] = sv[i];
-    if (mine) pins[s.pin].impulse = phx_vec2{r.px, r.py};
+    if (mine) {
+        if (LINKS && r.link) links[s.pin - npins].impulse = r.lambda; else pins[s.pin].impulse = phx_vec2{r.px, r.py};
+    }
 }
 
 // ---- the trailing group, out of HBM ----
-struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags, pad; };      // flags: 1 active, 2 write a, 4 write b
+struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };      // flags: 1 active, 2 write a, 4 write b, 8 link, 16 clamps
 
-__device__ __forceinline__ PinRegs pin_regs(const PinWork& w, const phx_pin& p)
+// (k11 .. biasy hold a link's nx, ny, gamma, inv_k, bias, lo: PinRegs' unions; px, py = the unit's accumulated impulse, a link's in px)
+__device__ __forceinline__ PinRegs pin_regs(const PinWork& w, float px, float py)
 {
     PinRegs r;
     r.rax = w.rax; r.ray = w.ray; r.rbx = w.rbx; r.rby = w.rby; r.k11 = w.k11; r.k12 = w.k12; r.k22 = w.k22; r.inv_det = w.inv_det;
     r.biasx = w.biasx; r.biasy = w.biasy; r.ma = w.ma; r.ia = w.ia; r.mb = w.mb; r.ib = w.ib;
-    r.px = p.impulse.x; r.py = p.impulse.y;
+    r.link = (w.flags & 8) != 0; r.clamps = (w.flags & 16) != 0;
+    r.px = px; r.py = r.link ? w.hi : py;
     r.active = (w.flags & 1) != 0; r.write_a = (w.flags & 2) != 0; r.write_b = (w.flags & 4) != 0;
     return r;
 }
 
-// slots [begin, end): the prestep; an inactive pin's impulse becomes 0 here
-static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, const PinSlot* __restrict__ slots, int begin, int end, const float4* __restrict__ mpos,
-                                                            const float4* __restrict__ frame, float beta, PinWork* __restrict__ work)
+// slots [begin, end): the prestep; an inactive pin's impulse becomes 0 here, a link's its warm start (clamped; 0 when inactive or idle)
+template <bool LINKS>
+static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
+                                                            const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, PinWork* __restrict__ work)
 {
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const int pin = slots[k].pin;
-        const PinRegs r = pin_prestep(pins[pin], mpos, frame, beta);
+        const PinRegs r = (!LINKS || pin < npins) ? pin_prestep(pins[pin], mpos, frame, beta) : link_prestep(links[pin - npins], mpos, frame, beta, dt);
         PinWork w;
         w.rax = r.rax; w.ray = r.ray; w.rbx = r.rbx; w.rby = r.rby; w.k11 = r.k11; w.k12 = r.k12; w.k22 = r.k22; w.inv_det = r.inv_det;
         w.biasx = r.biasx; w.biasy = r.biasy; w.ma = r.ma; w.ia = r.ia; w.mb = r.mb; w.ib = r.ib;
-        w.flags = (r.active ? 1 : 0) | (r.write_a ? 2 : 0) | (r.write_b ? 4 : 0); w.pad = 0;
+        w.flags = (r.active ? 1 : 0) | (r.write_a ? 2 : 0) | (r.write_b ? 4 : 0) | (r.link ? 8 : 0) | (r.clamps ? 16 : 0);
+        w.hi = (LINKS && r.link) ? r.hi : 0.f;
         work[k - begin] = w;
-        if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
+        if (LINKS && r.link) links[pin - npins].impulse = r.lambda;
+        else if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
     }
 }
 
 // one class, slots [begin, end) of a group whose work array starts at slot `base`: the warm start (sweep == 0) or one sweep
-static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ pins, const PinSlot* __restrict__ slots, int begin, int end, int base,
-                                                          const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep)
+template <bool LINKS>
+static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
+                                                          int base, const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep)
 {
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const PinSlot s = slots[k];
-        PinRegs r = pin_regs(work[k - base], pins[s.pin]);
-        if (!r.active) continue;
+        const PinWork w = work[k - base];
+        if (!(w.flags & 1)) continue;
+        const bool link = LINKS && (w.flags & 8) != 0;
+        float px, py = 0.f;
+        if (link) px = links[s.pin - npins].impulse; else { const phx_vec2 p = pins[s.pin].impulse; px = p.x; py = p.y; }
+        PinRegs r = pin_regs(w, px, py);
         float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
-        float dx = r.px, dy = r.py;
-        if (sweep) pin_delta(r, va, vb, dx, dy);
+        float dx, dy;
+        if (sweep) unit_delta<LINKS>(r, va, vb, dx, dy); else unit_warm<LINKS>(r, dx, dy);
         pin_apply(r, dx, dy, va, vb);
         if (r.write_a) vel[s.a] = va;
         if (r.write_b) vel[s.b] = vb;
-        if (sweep) pins[s.pin].impulse = phx_vec2{r.px, r.py};
+        if (sweep) { if (link) links[s.pin - npins].impulse = r.lambda; else pins[s.pin].impulse = phx_vec2{r.px, r.py}; }
     }
 }
 
 // ---- what the host asks between steps ----
+// (`P`: phx_pin or phx_link, which begin alike: body1, body2, anchor1, anchor2)
 // per pin: are its bodies static (bit 0: body1, bit 1: body2)?  O(pins) bytes for the schedule build
-static __global__ void __launch_bounds__(256) k_pin_statics(const phx_pin* __restrict__ pins, int n, const float4* __restrict__ mpos, unsigned* __restrict__ out)
+template <class P>
+static __global__ void __launch_bounds__(256) k_pin_statics(const P* __restrict__ pins, int n, const float4* __restrict__ mpos, unsigned* __restrict__ out)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const phx_pin p = pins[i];
+        const P& p = pins[i];
         const float4 a = mpos[p.body1];
         unsigned bits = (a.x == 0.f && a.y == 0.f) ? 1u : 0u;
         if (p.body2 >= 0) { const float4 b = mpos[p.body2]; if (b.x == 0.f && b.y == 0.f) bits |= 2u; }
@@ -206,21 +310,33 @@ static __global__ void __launch_bounds__(256) k_pin_statics(const phx_pin* __res
 }
 
 // a removal of bodies: every pin's bodies through new[] (-1: removed; the world stays -1 and is told apart by the old index)
-static __global__ void __launch_bounds__(256) k_pin_remap(const phx_pin* __restrict__ pins, int n, const int* __restrict__ remap, int2* __restrict__ out)
+template <class P>
+static __global__ void __launch_bounds__(256) k_pin_remap(const P* __restrict__ pins, int n, const int* __restrict__ remap, int2* __restrict__ out)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const phx_pin p = pins[i];
+        const P& p = pins[i];
         out[i] = make_int2(remap[p.body1], p.body2 >= 0 ? remap[p.body2] : -2);
     }
 }
 
-// phx_world_set_pin_anchors on the device copy
-static __global__ void __launch_bounds__(256) k_pin_anchors(const int* __restrict__ which, const float* __restrict__ anchors, int count, phx_pin* __restrict__ pins)
+// phx_world_set_pin_anchors / set_link_anchors on the device copy
+template <class P>
+static __global__ void __launch_bounds__(256) k_pin_anchors(const int* __restrict__ which, const float* __restrict__ anchors, int count, P* __restrict__ pins)
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        phx_pin& p = pins[which[k]];
+        P& p = pins[which[k]];
         p.anchor1 = phx_vec2{anchors[4 * k], anchors[4 * k + 1]};
         p.anchor2 = phx_vec2{anchors[4 * k + 2], anchors[4 * k + 3]};
+    }
+}
+
+// phx_world_set_link_lengths on the device copy
+static __global__ void __launch_bounds__(256) k_link_lengths(const int* __restrict__ which, const float* __restrict__ lengths, int count, phx_link* __restrict__ links)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        phx_link& p = links[which[k]];
+        p.min_length = lengths[2 * k];
+        p.max_length = lengths[2 * k + 1];
     }
 }
 

@@ -5,6 +5,8 @@
 // slot, group and group-body tables.  Per step nothing crosses PCIe: k_solve_pins, one workgroup per LDS group, does the whole pass of
 // those groups in one launch; the trailing group — components that do not fit a workgroup — takes a prestep launch and one launch per
 // class for the warm start and per class and sweep.
+// Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: UnitList<P> is the list machinery for either record, the
+// schedule is built over the pins followed by the links, and a world that has links launches the kernels' LINKS instantiations.
 #include "pins.h"
 #include "pin_kernels.h"
 
@@ -46,33 +48,33 @@ int PinSet::configure_from_env()
     return PHX_OK;
 }
 
-int PinSet::fetch(hipStream_t stream)
+template <class P> int UnitList<P>::fetch(hipStream_t stream)
 {
     if (dirty_ || host_.empty()) return PHX_OK;
     PHX_HIP(hipStreamSynchronize(stream));
-    PHX_HIP(hipMemcpy(host_.data(), d_pins_.p, host_.size() * sizeof(phx_pin), hipMemcpyDeviceToHost));
+    PHX_HIP(hipMemcpy(host_.data(), d_.p, host_.size() * sizeof(P), hipMemcpyDeviceToHost));
     return PHX_OK;
 }
 
-int PinSet::upload(hipStream_t stream)
+template <class P> int UnitList<P>::upload(hipStream_t stream)
 {
     if (!dirty_ || host_.empty()) return PHX_OK;
-    PHX_TRY(d_pins_.reserve(host_.size()));
-    PHX_HIP(hipMemcpyAsync(d_pins_.p, host_.data(), host_.size() * sizeof(phx_pin), hipMemcpyHostToDevice, stream));
+    PHX_TRY(d_.reserve(host_.size()));
+    PHX_HIP(hipMemcpyAsync(d_.p, host_.data(), host_.size() * sizeof(P), hipMemcpyHostToDevice, stream));
     PHX_HIP(hipStreamSynchronize(stream));
     dirty_ = false;
     return PHX_OK;
 }
 
-int PinSet::add(const phx_pin* pins, int count, hipStream_t stream)
+template <class P> int UnitList<P>::add(const P* recs, int count, hipStream_t stream)
 {
     PHX_TRY(fetch(stream));
-    host_.insert(host_.end(), pins, pins + count);
-    dirty_ = true; sched_dirty_ = true;
+    host_.insert(host_.end(), recs, recs + count);
+    dirty_ = true;
     return PHX_OK;
 }
 
-int PinSet::remove(const int32_t* which, int count, hipStream_t stream)
+template <class P> int UnitList<P>::remove(const int32_t* which, int count, hipStream_t stream)
 {
     PHX_TRY(fetch(stream));
     std::vector<unsigned char> gone(host_.size(), 0);
@@ -80,85 +82,120 @@ int PinSet::remove(const int32_t* which, int count, hipStream_t stream)
     size_t at = 0;
     for (size_t i = 0; i < host_.size(); ++i) if (!gone[i]) host_[at++] = host_[i];
     host_.resize(at);
-    dirty_ = true; sched_dirty_ = true;
+    dirty_ = true;
     return PHX_OK;
 }
 
-int PinSet::set_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream)
+template <class P> int UnitList<P>::set_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream)
 {
-    for (int k = 0; k < count; ++k) {
-        phx_pin& p = host_[(size_t)which[k]];
+    edit(which, count, [&](P& p, int k) {
         p.anchor1 = phx_vec2{anchors[4 * k], anchors[4 * k + 1]};
         p.anchor2 = phx_vec2{anchors[4 * k + 2], anchors[4 * k + 3]};
-    }
+    });
     if (!on_device()) return PHX_OK;
-    hipLaunchKernelGGL(k_pin_anchors, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_anchors, count, d_pins_.p);
+    hipLaunchKernelGGL(k_pin_anchors<P>, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_anchors, count, d_.p);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
 
-int PinSet::get(phx_pin* out, hipStream_t stream)
+template <class P> int UnitList<P>::get(P* out, hipStream_t stream)
 {
     PHX_TRY(fetch(stream));
-    if (!host_.empty()) std::memcpy(out, host_.data(), host_.size() * sizeof(phx_pin));
+    if (!host_.empty()) std::memcpy(out, host_.data(), host_.size() * sizeof(P));
     return PHX_OK;
 }
 
-int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
+template <class P> int UnitList<P>::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream, bool* changed)
 {
     const int n = count();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
     PHX_TRY(d_moved_.reserve((size_t)n));
-    hipLaunchKernelGGL(k_pin_remap, dim3(pgrid(n)), dim3(256), 0, stream, (const phx_pin*)d_pins_.p, n, d_remap, d_moved_.p);
+    hipLaunchKernelGGL(k_pin_remap<P>, dim3(pgrid(n)), dim3(256), 0, stream, (const P*)d_.p, n, d_remap, d_moved_.p);
     PHX_HIP(hipGetLastError());
-    // one round trip: the remapped bodies and the pins themselves (their impulses are the device's)
+    // one round trip: the remapped bodies and the records themselves (their impulses are the device's)
     std::vector<int2> moved((size_t)n);
     PHX_TRY(rb.add(moved.data(), d_moved_.p, (size_t)n * sizeof(int2), stream));
-    PHX_TRY(rb.add(host_.data(), d_pins_.p, (size_t)n * sizeof(phx_pin), stream));
+    PHX_TRY(rb.add(host_.data(), d_.p, (size_t)n * sizeof(P), stream));
     PHX_TRY(rb.wait(stream));
     size_t at = 0;
     for (size_t i = 0; i < host_.size(); ++i) {
         if (moved[i].x == -1 || moved[i].y == -1) continue;
-        phx_pin p = host_[i];
+        P p = host_[i];
         p.body1 = moved[i].x; p.body2 = moved[i].y == -2 ? -1 : moved[i].y;
         host_[at++] = p;
     }
     host_.resize(at);
-    dirty_ = true; sched_dirty_ = true;
+    dirty_ = true; *changed = true;
     return PHX_OK;
 }
 
-int PinSet::adopt_device(const phx_pin* d_src, int count, hipStream_t stream)
+template <class P> int UnitList<P>::adopt_device(const P* d_src, int count, hipStream_t stream)
 {
     host_.resize((size_t)count);
-    dirty_ = true; sched_dirty_ = true;
+    dirty_ = true;
     if (!count) return PHX_OK;
-    // (the bodies and anchors are needed on the host for the schedule and the later edits: the list comes down once, O(pins))
-    PHX_HIP(hipMemcpyAsync(host_.data(), d_src, (size_t)count * sizeof(phx_pin), hipMemcpyDeviceToHost, stream));
+    // (the bodies and anchors are needed on the host for the schedule and the later edits: the list comes down once, O(records))
+    PHX_HIP(hipMemcpyAsync(host_.data(), d_src, (size_t)count * sizeof(P), hipMemcpyDeviceToHost, stream));
     PHX_HIP(hipStreamSynchronize(stream));
     return PHX_OK;
 }
 
-int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
+template <class P> int UnitList<P>::statics(const float4* mpos, unsigned* d_bits, hipStream_t stream) const
 {
     const int n = count();
+    if (!n) return PHX_OK;
+    hipLaunchKernelGGL(k_pin_statics<P>, dim3(pgrid(n)), dim3(256), 0, stream, (const P*)d_.p, n, mpos, d_bits);
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+template class UnitList<phx_pin>;
+template class UnitList<phx_link>;
+
+int PinSet::set_link_lengths(const int32_t* which, const float* lengths, int count, const int* d_which, const float* d_lengths, hipStream_t stream)
+{
+    links_.edit(which, count, [&](phx_link& p, int k) { p.min_length = lengths[2 * k]; p.max_length = lengths[2 * k + 1]; });
+    if (!links_.on_device()) return PHX_OK;
+    hipLaunchKernelGGL(k_link_lengths, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_lengths, count, links_.device());
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
+}
+
+int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
+{
+    PHX_TRY(pins_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
+    return links_.bodies_removed(d_remap, rb, stream, &sched_dirty_);
+}
+
+int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, hipStream_t stream)
+{
+    sched_dirty_ = true;
+    PHX_TRY(pins_.adopt_device(d_pins, pin_count, stream));
+    return links_.adopt_device(d_links, link_count, stream);
+}
+
+int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
+{
+    const int n = units(), np = count();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
     if (!sched_dirty_) return PHX_OK;
     PHX_TRY(d_bits_.reserve((size_t)n));
-    hipLaunchKernelGGL(k_pin_statics, dim3(pgrid(n)), dim3(256), 0, stream, (const phx_pin*)d_pins_.p, n, mpos, d_bits_.p);
-    PHX_HIP(hipGetLastError());
+    PHX_TRY(pins_.statics(mpos, d_bits_.p, stream));
+    PHX_TRY(links_.statics(mpos, d_bits_.p + np, stream));
+    // a unit's bodies: pin u, or link u - np
+    auto body1 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body1 : links_.host()[(size_t)(u - np)].body1; };
+    auto body2 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body2 : links_.host()[(size_t)(u - np)].body2; };
     std::vector<unsigned> bits((size_t)n);
     PHX_TRY(rb.add(bits.data(), d_bits_.p, (size_t)n * sizeof(unsigned), stream));
     PHX_TRY(rb.wait(stream));
     std::vector<unsigned char> is_static((size_t)nb, 0);
     std::vector<int32_t> b1((size_t)n), b2((size_t)n);
     for (int k = 0; k < n; ++k) {
-        const phx_pin& p = host_[(size_t)k];
-        b1[(size_t)k] = p.body1; b2[(size_t)k] = p.body2;
-        if (bits[(size_t)k] & 1u) is_static[(size_t)p.body1] = 1;
-        if (p.body2 >= 0 && (bits[(size_t)k] & 2u)) is_static[(size_t)p.body2] = 1;
+        b1[(size_t)k] = body1(k); b2[(size_t)k] = body2(k);
+        if (bits[(size_t)k] & 1u) is_static[(size_t)b1[(size_t)k]] = 1;
+        if (b2[(size_t)k] >= 0 && (bits[(size_t)k] & 2u)) is_static[(size_t)b2[(size_t)k]] = 1;
     }
     build_pin_schedule(b1.data(), b2.data(), n, is_static.data(), nb, group_pins_, sched_);
     ++builds_;
@@ -167,11 +204,11 @@ int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream
     const int lds_slots = s.lds_groups ? s.group_offsets[(size_t)s.lds_groups] : 0;
     std::vector<PinSlot> slots((size_t)n);
     for (int k = 0; k < n; ++k) {
-        const phx_pin& p = host_[(size_t)s.order[(size_t)k]];
+        const int u = s.order[(size_t)k], ub1 = b1[(size_t)u], ub2 = b2[(size_t)u];
         if (k < lds_slots) {
             const uint32_t local = s.slot_local[(size_t)k];
-            slots[(size_t)k] = PinSlot{s.order[(size_t)k], (int)(local & 0xFFFFu), p.body2 >= 0 ? (int)(local >> 16) : -1, (int)s.slot_colour[(size_t)k]};
-        } else slots[(size_t)k] = PinSlot{s.order[(size_t)k], p.body1, p.body2, 0};
+            slots[(size_t)k] = PinSlot{u, (int)(local & 0xFFFFu), ub2 >= 0 ? (int)(local >> 16) : -1, (int)s.slot_colour[(size_t)k]};
+        } else slots[(size_t)k] = PinSlot{u, ub1, ub2, 0};
     }
     std::vector<PinGroup> groups((size_t)s.lds_groups);
     std::vector<int> gbodies(s.group_bodies);
@@ -211,21 +248,30 @@ int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream
 
 int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hipStream_t stream)
 {
-    if (!count()) return PHX_OK;
+    if (!units()) return PHX_OK;
     PHX_TRY(prepare(bodies.s.mpos, nb, rb, stream));
+    phx_pin* const d_pins = pins_.device();
+    phx_link* const d_links = links_.device();
+    const int np = count();
     const float beta = 0.2f / dt;
     const PinSlot* slots = reinterpret_cast<const PinSlot*>(d_tables_.p);
+    // a world without links runs the pins' own instantiation of each kernel: what it ran before there were links
+    const bool with_links = link_count() > 0;
+    auto pick = [with_links](auto with, auto without) { return with_links ? with : without; };
     if (sched_.lds_groups)
-        hipLaunchKernelGGL(k_solve_pins, dim3(sched_.lds_groups), dim3(PIN_LANES), 0, stream, d_pins_.p, slots, reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_),
-                           reinterpret_cast<const int*>(d_tables_.p + off_bodies_), bodies.s.vel, (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, iterations);
+        hipLaunchKernelGGL(pick(k_solve_pins<true>, k_solve_pins<false>), dim3(sched_.lds_groups), dim3(PIN_LANES), 0, stream, d_pins, d_links, np, slots,
+                           reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_), reinterpret_cast<const int*>(d_tables_.p + off_bodies_), bodies.s.vel,
+                           (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, dt, iterations);
     if (hbm_classes_.size() > 1) {
         const int begin = hbm_classes_.front(), end = hbm_classes_.back();
         PinWork* work = reinterpret_cast<PinWork*>(d_work_.p);
-        hipLaunchKernelGGL(k_pin_prestep, dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins_.p, slots, begin, end, (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, work);
+        hipLaunchKernelGGL(pick(k_pin_prestep<true>, k_pin_prestep<false>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end,
+                           (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, dt, work);
         for (int sweep = 0; sweep <= iterations; ++sweep)
             for (size_t c = 0; c + 1 < hbm_classes_.size(); ++c) {
                 const int b = hbm_classes_[c], e = hbm_classes_[c + 1];
-                if (e > b) hipLaunchKernelGGL(k_pin_class, dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins_.p, slots, b, e, begin, (const PinWork*)work, bodies.s.vel, sweep);
+                if (e > b) hipLaunchKernelGGL(pick(k_pin_class<true>, k_pin_class<false>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
+                                              (const PinWork*)work, bodies.s.vel, sweep);
             }
     }
     PHX_HIP(hipGetLastError());

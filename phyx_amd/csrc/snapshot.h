@@ -41,10 +41,13 @@ public:
     int load(const SnapshotWorld& w, hipStream_t stream);      // queued on `stream` behind the save that wrote the contents
     // the world's pins (include/phyx_amd.h PINS) ride beside the blob's layout, which holds none: room first (nothing changes if that
     // fails), then a device copy queued behind the save, in front of the event the loads wait for
-    int reserve_pins(int count, hipStream_t stream) { return pins_.reserve_keep((size_t)std::max(count, 1), (size_t)pin_count_, stream); }      // (a save that fails afterwards leaves the old pins whole)
-    int save_pins(const phx_pin* d_pins, int count, hipStream_t stream);
-    const phx_pin* pins() const { return pins_.p; }
-    int pin_count() const { return pin_count_; }
+    // (a save that fails afterwards leaves the old ones whole).  The links (LINKS) ride the same way.
+    int reserve_units(int pins, int links, hipStream_t stream) { PHX_TRY(pins_.reserve(pins, stream)); return links_.reserve(links, stream); }
+    int save_units(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, hipStream_t stream);
+    const phx_pin* pins() const { return pins_.buf.p; }
+    int pin_count() const { return pins_.count; }
+    const phx_link* links() const { return links_.buf.p; }
+    int link_count() const { return links_.count; }
     int blob_bytes(size_t* bytes) const;
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
@@ -52,9 +55,14 @@ public:
 private:
     int settle();                        // the host waits for the queued save and loads (export, import, destroy)
     int refuse_empty(const char* what) const;
-    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins
-    DevBuf<phx_pin> pins_;
-    int pin_count_ = 0;
+    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins and no links
+    template <class P> struct Riders {            // a list of records beside the blob
+        DevBuf<P> buf; int count = 0;
+        int reserve(int n, hipStream_t stream) { return n ? buf.reserve_keep((size_t)n, (size_t)count, stream) : PHX_OK; }      // (none: nothing is allocated)
+    };
+    template <class P> int save_riders(Riders<P>& r, const P* d_src, int count, hipStream_t stream);
+    Riders<phx_pin> pins_;
+    Riders<phx_link> links_;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

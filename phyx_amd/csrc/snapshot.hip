@@ -45,18 +45,25 @@ int Snapshot::refuse_empty(const char* what) const
 
 int Snapshot::refuse_pins(const char* what) const
 {
-    if (!pin_count_) return PHX_OK;
-    set_error("%s: the snapshot holds %d pins, which the blob (layout version 1) does not carry", what, pin_count_);
+    if (!pins_.count && !links_.count) return PHX_OK;
+    if (pins_.count) set_error("%s: the snapshot holds %d pins, which the blob (layout version 1) does not carry", what, pins_.count);
+    else set_error("%s: the snapshot holds %d links, which the blob (layout version 1) does not carry", what, links_.count);
     return PHX_ERR_STATE;
 }
 
-int Snapshot::save_pins(const phx_pin* d_pins, int count, hipStream_t stream)
+template <class P> int Snapshot::save_riders(Riders<P>& r, const P* d_src, int count, hipStream_t stream)
 {
-    pin_count_ = count;
+    r.count = count;
     if (!count) return PHX_OK;
-    PHX_HIP(hipMemcpyAsync(pins_.p, d_pins, (size_t)count * sizeof(phx_pin), hipMemcpyDeviceToDevice, stream));
+    PHX_HIP(hipMemcpyAsync(r.buf.p, d_src, (size_t)count * sizeof(P), hipMemcpyDeviceToDevice, stream));
     PHX_HIP(hipEventRecord(saved_, stream));                                // (the event moves behind the copy)
     return PHX_OK;
+}
+
+int Snapshot::save_units(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, hipStream_t stream)
+{
+    PHX_TRY(save_riders(pins_, d_pins, pin_count, stream));
+    return save_riders(links_, d_links, link_count, stream);
 }
 
 // the largest walk of a launch: the bodies, or the granules of the largest array
@@ -155,7 +162,7 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     const size_t rest = (size_t)(l.total - SNAP_HEADER_BYTES);
     PHX_TRY(buf_.reserve(rest / 16));
     if (rest) PHX_HIP(hipMemcpy(buf_.p, static_cast<const unsigned char*>(blob) + SNAP_HEADER_BYTES, rest, hipMemcpyHostToDevice));
-    counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true; pin_count_ = 0;
+    counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true; pins_.count = 0; links_.count = 0;
     return PHX_OK;
 }
 

@@ -200,7 +200,13 @@ public:
     int get_pins(phx_pin* out, int cap);
     int set_pin_iterations(int n);
     int pin_schedule(const Schedule** out);
-    int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin exists (the sharded modes carry none)
+    int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
+    // links (phx_world_add_links ...): the pin pass's second kind of unit (include/phyx_amd.h LINKS)
+    int add_links(const phx_link* links, int count, int* first);
+    int remove_links(const int32_t* which, int count);
+    int set_link_anchors(const int32_t* which, const float* anchors, int count);
+    int set_link_lengths(const int32_t* which, const float* lengths, int count);
+    int get_links(phx_link* out, int cap);
     PinSet& pins() { return pins_; }
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
 
@@ -324,7 +330,10 @@ private:
     BodyTable<FlagsColumn> flags_col_;
     template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); return f(flags_col_); }
     PinSet pins_;
-    int check_pin_indices(const char* what, const int32_t* which, const void* values, int count);
+    int check_pin_indices(const char* what, const int32_t* which, const void* values, int count, bool links = false);
+    int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2, const float* v, int nv);
+    // an edit of `width` floats per listed unit: staged for the scatter kernel when the list is on the device
+    int stage_unit_edit(bool on_device, const int32_t* which, const float* values, int count, int width, const int** d_which, const float** d_values);
     BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr()}; }
     BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr()}; }
 };
@@ -720,8 +729,8 @@ int World::pre_solve(float dt)
     if (flags_col_.active) PHX_TRY(solver_.cancel_prelabel());
     else if (!phase_timing) PHX_TRY(solver_.prelabel_mark());
     { RoctxRange r("RefreshContactJoints"); PHX_TRY(refresh_contact_joints()); lap(5); }             // ref: World.cpp:74
-    // the pins edit the velocities the contacts are then solved on (include/phyx_amd.h PINS); a world without pins queues nothing
-    if (pins_.count()) { RoctxRange r("SolvePins"); PHX_TRY(pins_.solve(resident(), nb(), dt, rb_, stream_)); }
+    // the pins and links edit the velocities the contacts are then solved on (include/phyx_amd.h PINS, LINKS); a world without queues nothing
+    if (pins_.units()) { RoctxRange r("SolvePins"); PHX_TRY(pins_.solve(resident(), nb(), dt, rb_, stream_)); }
     return PHX_OK;
 }
 
@@ -945,7 +954,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
-    pins_.clear();                                                          // ... and no pin is left
+    pins_.clear();                                                          // ... and no pin or link is left
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -1016,9 +1025,9 @@ int World::save(Snapshot& s)
     v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
     PHX_TRY(pins_.upload(stream_));
-    PHX_TRY(s.reserve_pins(pins_.count(), stream_));
+    PHX_TRY(s.reserve_units(pins_.count(), pins_.link_count(), stream_));
     PHX_TRY(s.save(v, stream_));
-    return s.save_pins(pins_.device_pins(), pins_.count(), stream_);
+    return s.save_units(pins_.device_pins(), pins_.count(), pins_.device_links(), pins_.link_count(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -1055,7 +1064,7 @@ int World::load(Snapshot& s)
     // what set_state resets: the pair set becomes the saved manifolds' pairs, the schedule is rebuilt at the next step
     PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
     PHX_TRY(forget_step_history());
-    return pins_.adopt_device(s.pins(), s.pin_count(), stream_);            // 6. add_pins of the saved pins
+    return pins_.adopt_device(s.pins(), s.pin_count(), s.links(), s.link_count(), stream_);      // 6. add_pins, add_links of the saved ones
 }
 
 int World::get_slab_state(const long long* global_index, int count, SlabState* out)
@@ -1538,24 +1547,46 @@ int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_
 // then change the list; the schedule follows lazily at the next step.
 int World::refuse_pins(const char* what)
 {
-    if (!pins_.count()) return PHX_OK;
-    set_error("%s: the world holds pins, which a sharded world does not carry", what);
+    if (!pins_.units()) return PHX_OK;
+    set_error("%s: the world holds %s, which a sharded world does not carry", what, pins_.count() ? "pins" : "links");
     return PHX_ERR_STATE;
 }
 
-int World::check_pin_indices(const char* what, const int32_t* which, const void* values, int count)
+int World::check_pin_indices(const char* what, const int32_t* which, const void* values, int count, bool links)
 {
     PHX_TRY(refuse_mid_step(what));
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && (!which || !values)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
-    const int n = pins_.count();
+    const int n = links ? pins_.link_count() : pins_.count();
+    const char* const noun = links ? "link" : "pin";
     std::vector<unsigned char> seen((size_t)n, 0);
     for (int k = 0; k < count; ++k) {
-        if (which[k] < 0 || which[k] >= n) { set_error("%s: pin index %d out of range [0, %d)", what, which[k], n); return PHX_ERR_INVALID; }
-        if (seen[(size_t)which[k]]) { set_error("%s: pin %d appears twice in one call", what, which[k]); return PHX_ERR_INVALID; }
+        if (which[k] < 0 || which[k] >= n) { set_error("%s: %s index %d out of range [0, %d)", what, noun, which[k], n); return PHX_ERR_INVALID; }
+        if (seen[(size_t)which[k]]) { set_error("%s: %s %d appears twice in one call", what, noun, which[k]); return PHX_ERR_INVALID; }
         seen[(size_t)which[k]] = 1;
     }
     return PHX_OK;
+}
+
+// the body rules and the finite floats of entry k of an add_pins / add_links call
+int World::check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2, const float* v, int nv)
+{
+    const int n = nb();
+    if (body1 < 0 || body1 >= n) { set_error("%s: %s %d: body1 %d out of range [0, %d)", what, noun, k, body1, n); return PHX_ERR_INVALID; }
+    if (body2 < -1 || body2 >= n) { set_error("%s: %s %d: body2 %d is neither -1 nor in [0, %d)", what, noun, k, body2, n); return PHX_ERR_INVALID; }
+    if (body1 == body2) { set_error("%s: %s %d: both ends on body %d", what, noun, k, body1); return PHX_ERR_INVALID; }
+    for (int c = 0; c < nv; ++c)
+        if (!std::isfinite(v[c])) { set_error("%s: %s %d: value %d is not finite", what, noun, k, c); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int World::stage_unit_edit(bool on_device, const int32_t* which, const float* values, int count, int width, const int** d_which, const float** d_values)
+{
+    *d_which = nullptr; *d_values = nullptr;
+    if (!on_device) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    return stage_batch(which, values, count, width, d_which, d_values);
 }
 
 int World::add_pins(const phx_pin* pins, int count, int* first)
@@ -1566,15 +1597,10 @@ int World::add_pins(const phx_pin* pins, int count, int* first)
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && !pins) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
     if ((long long)pins_.count() + count > (long long)INT32_MAX) { set_error("%s: %d + %d pins exceed the int32 range", what, pins_.count(), count); return PHX_ERR_INVALID; }
-    const int n = nb();
     for (int k = 0; k < count; ++k) {
         const phx_pin& p = pins[k];
-        if (p.body1 < 0 || p.body1 >= n) { set_error("%s: pin %d: body1 %d out of range [0, %d)", what, k, p.body1, n); return PHX_ERR_INVALID; }
-        if (p.body2 < -1 || p.body2 >= n) { set_error("%s: pin %d: body2 %d is neither -1 nor in [0, %d)", what, k, p.body2, n); return PHX_ERR_INVALID; }
-        if (p.body1 == p.body2) { set_error("%s: pin %d: both ends on body %d", what, k, p.body1); return PHX_ERR_INVALID; }
         const float v[6] = {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.impulse.x, p.impulse.y};
-        for (int c = 0; c < 6; ++c)
-            if (!std::isfinite(v[c])) { set_error("%s: pin %d: value %d is not finite", what, k, c); return PHX_ERR_INVALID; }
+        PHX_TRY(check_unit_bodies(what, "pin", k, p.body1, p.body2, v, 6));
     }
     if (first) *first = pins_.count();
     if (!count) return PHX_OK;
@@ -1600,11 +1626,7 @@ int World::set_pin_anchors(const int32_t* which, const float* anchors, int count
         if (!std::isfinite(anchors[k])) { set_error("%s: entry %d: value %d is not finite", what, k / 4, k % 4); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     const int* d_which = nullptr; const float* d_anchors = nullptr;
-    if (pins_.on_device()) {
-        PHX_TRY(use_device(device_));
-        if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
-        PHX_TRY(stage_batch(which, anchors, count, 4, &d_which, &d_anchors));
-    }
+    PHX_TRY(stage_unit_edit(pins_.on_device(), which, anchors, count, 4, &d_which, &d_anchors));
     return pins_.set_anchors(which, anchors, count, d_which, d_anchors, stream_);
 }
 
@@ -1630,13 +1652,88 @@ int World::pin_schedule(const Schedule** out)
 {
     PHX_TRY(refuse_mid_step("phx_world_get_pin_schedule"));
     *out = nullptr;
-    if (!pins_.count()) return PHX_OK;
+    if (!pins_.units()) return PHX_OK;
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
     PHX_TRY(pins_.prepare(bodies_.mpos.p, nb(), rb_, stream_));
     *out = &pins_.schedule();
     return PHX_OK;
+}
+
+// ---- links: the pins' calls for the pass's other kind of unit (include/phyx_amd.h LINKS) ----
+static int check_link_lengths(const char* what, int k, float lo, float hi, float hertz)
+{
+    if (!std::isfinite(lo) || !std::isfinite(hi)) { set_error("%s: link %d: a length is not finite", what, k); return PHX_ERR_INVALID; }
+    if (!(0.f <= lo && lo <= hi)) { set_error("%s: link %d: lengths [%g, %g] are not 0 <= min <= max", what, k, (double)lo, (double)hi); return PHX_ERR_INVALID; }
+    if (hertz > 0.f && lo != hi) { set_error("%s: link %d: a spring (hertz %g) needs min_length == max_length", what, k, (double)hertz); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int World::add_links(const phx_link* links, int count, int* first)
+{
+    static const char* const what = "phx_world_add_links";
+    PHX_TRY(refuse_mid_step(what));
+    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no links", what); return PHX_ERR_STATE; }
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && !links) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    if ((long long)pins_.units() + count > (long long)INT32_MAX) { set_error("%s: %d + %d units exceed the int32 range", what, pins_.units(), count); return PHX_ERR_INVALID; }
+    for (int k = 0; k < count; ++k) {
+        const phx_link& p = links[k];
+        const float v[9] = {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.min_length, p.max_length, p.hertz, p.damping_ratio, p.impulse};
+        PHX_TRY(check_unit_bodies(what, "link", k, p.body1, p.body2, v, 9));
+        if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: link %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
+        PHX_TRY(check_link_lengths(what, k, p.min_length, p.max_length, p.hertz));
+        if (p.reserved != 0) { set_error("%s: link %d: reserved must be 0", what, k); return PHX_ERR_INVALID; }
+    }
+    if (first) *first = pins_.link_count();
+    if (!count) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    return pins_.add_links(links, count, stream_);
+}
+
+int World::remove_links(const int32_t* which, int count)
+{
+    PHX_TRY(check_pin_indices("phx_world_remove_links", which, which, count, true));
+    if (!count) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    return pins_.remove_links(which, count, stream_);
+}
+
+int World::set_link_anchors(const int32_t* which, const float* anchors, int count)
+{
+    static const char* const what = "phx_world_set_link_anchors";
+    PHX_TRY(check_pin_indices(what, which, anchors, count, true));
+    for (int k = 0; k < 4 * count; ++k)
+        if (!std::isfinite(anchors[k])) { set_error("%s: entry %d: value %d is not finite", what, k / 4, k % 4); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    const int* d_which = nullptr; const float* d_anchors = nullptr;
+    PHX_TRY(stage_unit_edit(pins_.links_on_device(), which, anchors, count, 4, &d_which, &d_anchors));
+    return pins_.set_link_anchors(which, anchors, count, d_which, d_anchors, stream_);
+}
+
+int World::set_link_lengths(const int32_t* which, const float* lengths, int count)
+{
+    static const char* const what = "phx_world_set_link_lengths";
+    PHX_TRY(check_pin_indices(what, which, lengths, count, true));
+    for (int k = 0; k < count; ++k)
+        PHX_TRY(check_link_lengths(what, k, lengths[2 * k], lengths[2 * k + 1], pins_.host_links()[(size_t)which[k]].hertz));
+    if (!count) return PHX_OK;
+    const int* d_which = nullptr; const float* d_lengths = nullptr;
+    PHX_TRY(stage_unit_edit(pins_.links_on_device(), which, lengths, count, 2, &d_which, &d_lengths));
+    return pins_.set_link_lengths(which, lengths, count, d_which, d_lengths, stream_);
+}
+
+int World::get_links(phx_link* out, int cap)
+{
+    const int n = pins_.link_count();
+    if (cap < n) { set_error("phx_world_get_links: room for %d links, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());
+    return pins_.get_links(out, stream_);
 }
 
 // ---- queries ------------------------------------------------------------------------------------------------------------------------
@@ -2206,6 +2303,44 @@ int phx_world_get_pins(phx_world* w, phx_pin* out, int32_t cap)
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
     return w->impl.get_pins(out, cap);
+}
+
+int phx_world_add_links(phx_world* w, const phx_link* links, int32_t count, int32_t* first)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.add_links(links, count, first);
+}
+
+int phx_world_remove_links(phx_world* w, const int32_t* links, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.remove_links(links, count);
+}
+
+int phx_world_set_link_anchors(phx_world* w, const int32_t* links, const float* anchors, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_link_anchors(links, anchors, count);
+}
+
+int phx_world_set_link_lengths(phx_world* w, const int32_t* links, const float* lengths, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_link_lengths(links, lengths, count);
+}
+
+int phx_world_get_links(phx_world* w, phx_link* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_links(out, cap);
+}
+
+int phx_world_link_count(phx_world* w, int32_t* count)
+{
+    PHX_REQUIRE(w && count, "null handle / output");
+    *count = w->impl.pins().link_count();
+    return PHX_OK;
 }
 
 int phx_world_pin_count(phx_world* w, int32_t* count)

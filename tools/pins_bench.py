@@ -1,7 +1,7 @@
 """The cost of the pin pass (include/phyx_amd.h PINS): a synchronised World::Update of one world of hanging chains, with and without
 its pins, on the same build.
 
-    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--import-from DIR]
+    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--ropes] [--only WORLD] [--import-from DIR]
 
 The world: a ground and `chains` chains of `links` links (boxes of 2 x 8, 10 apart), each hung from a world pin, side by side.  The
 pinned world runs under gravity (the pins carry the chains); the pinless twin has the same bodies and gravity 0, so that they stay
@@ -10,6 +10,10 @@ where they are and the rest of the step — broadphase, narrowphase, the empty c
 with the median and every repeat.  --no-pins times the pinless world alone, and --import-from takes phyx_amd from another tree (a
 build of the parent commit), which together give the parent's time for the same world.  The pass's own kernel time comes from a
 kernel trace of `--steps N --repeats 1` (k_solve_pins in the statistics), in a run of its own.
+
+--ropes adds a third world, "links" (include/phyx_amd.h LINKS): the pinned world plus one rope per chain from its last link to a world
+point beside and below it, half a unit short, so that every rope is taut: 4096 more units in the same pass.  (`--links` was taken: it
+is the chains' length.)  --only pins|pinless|links runs that world alone, for a kernel trace in which k_solve_pins is one world's.
 """
 import argparse
 import json
@@ -21,7 +25,7 @@ import time
 import numpy as np
 
 
-def build(phyx_amd, chains, links, pinned, spacing=10.0):
+def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False):
     pw = phyx_amd.World(0, gravity=-200.0 if pinned else 0.0)
     pw.AddBody((0.0, 0.0), 0.0, (8.0 * chains + 100.0, 10.0), static=True)
     rows = np.zeros((chains * links, 5), dtype=np.float32)
@@ -44,6 +48,16 @@ def build(phyx_amd, chains, links, pinned, spacing=10.0):
         pins["anchor2"][heads, 0] = rows[heads, 0]
         pins["anchor2"][heads, 1] = top
         pw.add_pins(pins)
+    if ropes:
+        from phyx_amd.api import link_dtype
+        last = np.flatnonzero(k == links - 1)
+        r = np.zeros(chains, dtype=link_dtype)
+        r["body1"], r["body2"] = 1 + last, -1
+        r["anchor1"] = (0.0, -spacing / 2.0)                     # the chain's free end, at (x, top - spacing * links) ...
+        r["anchor2"][:, 0] = rows[last, 0] + 3.0
+        r["anchor2"][:, 1] = top - spacing * links - 4.0         # ... 5 from this point, on a rope of 4.5
+        r["max_length"] = 4.5
+        pw.add_links(r)
     return pw
 
 
@@ -65,15 +79,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--iterations", type=int, default=32, help="pin sweeps per step (a hanging chain of 16 links is not stable at the default 8)")
     ap.add_argument("--no-pins", action="store_true")
+    ap.add_argument("--ropes", action="store_true", help="also time the pinned world with one taut rope per chain (the 'links' world)")
+    ap.add_argument("--only", choices=("pins", "pinless", "links"), default=None, help="run this world alone")
     ap.add_argument("--import-from", default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.import_from) if a.import_from else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import phyx_amd
     cfg = phyx_amd.Configuration(phyx_amd.SOLVE_AVX2, phyx_amd.ISLAND_MULTIPLE_SLOPPY, 15, 15)
-    worlds = {} if a.no_pins else {"pins": build(phyx_amd, a.chains, a.links, True)}
-    worlds["pinless"] = build(phyx_amd, a.chains, a.links, False)
-    if not a.no_pins:
-        worlds["pins"].pin_iterations = a.iterations
+    want = [a.only] if a.only else ([] if a.no_pins else ["pins"]) + ["pinless"] + (["links"] if a.ropes else [])
+    worlds = {name: build(phyx_amd, a.chains, a.links, name != "pinless", ropes=(name == "links")) for name in want}
+    for name, pw in worlds.items():
+        if name != "pinless":
+            pw.pin_iterations = a.iterations
     for pw in worlds.values():
         timed(pw, cfg, a.warmup)
     times = {name: [] for name in worlds}
@@ -84,7 +101,9 @@ def main():
         out = {"world": name, "tree": os.path.dirname(os.path.abspath(phyx_amd.__file__)), "chains": a.chains, "links": a.links, "bodies": pw.counts()[0],
                "manifolds": pw.counts()[1], "steps": a.steps, "ms_per_step_median": round(statistics.median(times[name]), 4),
                "ms_per_step": [round(t, 4) for t in times[name]]}
-        if name == "pins":
+        if name == "links":
+            out.update(links=pw.link_count(), link_impulse_min=float(pw.links()["impulse"].min()), link_impulse_max=float(pw.links()["impulse"].max()))
+        if name != "pinless":
             s = pw.pin_schedule()
             out.update(pins=pw.pin_count(), lds_groups=s["lds_groups"], groups=len(s["group_offsets"]) - 1, classes=len(s["class_offsets"]) - 1,
                        iterations=pw.pin_iterations, schedule_builds=pw.pin_schedule_builds(), impulse_max=float(np.abs(pw.pins()["impulse"]).max()))
