@@ -90,6 +90,11 @@ def pinned_inv_inertia(sx, sy):
     return float(np.float32(1.0) / inertia)
 
 
+def _or_empty(a, shape, dtype):
+    """An empty list or tuple as the empty array it stands for ([] alone reads as float64)."""
+    return np.zeros(shape, dtype=dtype) if isinstance(a, (list, tuple)) and not len(a) else a
+
+
 def _contig(a, dtype):
     a = np.asarray(a)
     if a.dtype != dtype or not a.flags["C_CONTIGUOUS"]:
@@ -800,7 +805,7 @@ class World:
 
     # ---- edits and gathers between steps (include/phyx_amd.h: phx_world_add_accelerations ...) ----
     def _indices(self, bodies, what):
-        idx = np.asarray(bodies)
+        idx = np.asarray(_or_empty(bodies, 0, np.int32))
         if idx.ndim != 1 or idx.dtype.kind not in "iu":
             raise TypeError("%s: body indices must be a 1-D integer array, got %s of shape %s" % (what, idx.dtype, idx.shape))
         if idx.size and (idx.min() < np.iinfo(np.int32).min or idx.max() > np.iinfo(np.int32).max):
@@ -866,8 +871,6 @@ class World:
         """Remove the listed bodies (each at most once) and compact the world on the device; exactly what set_state of the filtered
         state() would make (tests/removal_spec.py).  Returns remap: int32 of the old body count, remap[i] = body i's new index or -1.
         Indices held elsewhere shift (the drag's body 1 becomes remap[1])."""
-        if isinstance(bodies, (list, tuple)) and not len(bodies):
-            bodies = np.zeros(0, dtype=np.int32)                    # ([] reads as float64)
         idx = self._indices(bodies, "remove_bodies")
         remap = np.zeros(self.counts()[0], dtype=np.int32)
         check(self.L.phx_world_remove_bodies(self.h, _ptr(idx), len(idx), _ptr(remap)))
@@ -933,55 +936,59 @@ class World:
     def set_inverse_masses(self, bodies, values):
         """invMass, invInertia = values[k] on body bodies[k], values (K, 2) ((0, 0): static).  Like set_inverse_mass, a topology change:
         the next step rebuilds the solver's schedule."""
-        if isinstance(bodies, (list, tuple)) and not len(bodies):
-            bodies = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
 
-    # ---- pins (include/phyx_amd.h PINS; the specification: tests/pin_spec.py) ----
+    # ---- units: pins and links (include/phyx_amd.h PINS, LINKS; the specifications: tests/pin_spec.py, tests/link_spec.py) ----
+    def _add_units(self, fn, recs, dtype, extra=(), required=0):
+        """recs: an array of `dtype`, or rows (body1, body2, anchor1, anchor2, then the fields `extra`, the first `required` of them
+        always); the rest of a record is zero."""
+        if isinstance(recs, np.ndarray) and recs.dtype == dtype:
+            p = np.ascontiguousarray(recs)
+        else:
+            rows = list(recs)
+            p = np.zeros(len(rows), dtype=dtype)
+            for k, r in enumerate(rows):
+                p["body1"][k], p["body2"][k], p["anchor1"][k], p["anchor2"][k] = int(r[0]), int(r[1]), r[2], r[3]
+                for i, name in enumerate(extra):
+                    if i < required or len(r) > 4 + i:
+                        p[name][k] = r[4 + i]
+        first = C.c_int32(0)
+        check(getattr(self.L, fn)(self.h, _ptr(p), len(p), C.byref(first)))
+        return np.arange(first.value, first.value + len(p), dtype=np.int64)
+
+    def _remove_units(self, fn, which, what):
+        idx = self._indices(which, what)
+        check(getattr(self.L, fn)(self.h, _ptr(idx), len(idx)))
+
+    def _int32(self, fn):
+        n = C.c_int32(0)
+        check(getattr(self.L, fn)(self.h, C.byref(n)))
+        return n.value
+
     def add_pins(self, pins):
         """Append pins: a pin_dtype array, or rows (body1, body2, (a1x, a1y), (a2x, a2y)) with impulse 0.  body2 = -1 pins body1 to the
         world point anchor2.  Returns the new pins' indices."""
-        if isinstance(pins, np.ndarray) and pins.dtype == pin_dtype:
-            p = np.ascontiguousarray(pins)
-        else:
-            rows = list(pins)
-            p = np.zeros(len(rows), dtype=pin_dtype)
-            for k, r in enumerate(rows):
-                p["body1"][k], p["body2"][k], p["anchor1"][k], p["anchor2"][k] = int(r[0]), int(r[1]), r[2], r[3]
-        first = C.c_int32(0)
-        check(self.L.phx_world_add_pins(self.h, _ptr(p), len(p), C.byref(first)))
-        return np.arange(first.value, first.value + len(p), dtype=np.int64)
+        return self._add_units("phx_world_add_pins", pins, pin_dtype)
 
     def remove_pins(self, pins):
         """Remove the listed pins (each at most once); the others keep their order, so their indices shift."""
-        if isinstance(pins, (list, tuple)) and not len(pins):
-            pins = np.zeros(0, dtype=np.int32)
-        idx = self._indices(pins, "remove_pins")
-        check(self.L.phx_world_remove_pins(self.h, _ptr(idx), len(idx)))
+        self._remove_units("phx_world_remove_pins", pins, "remove_pins")
 
     def set_pin_anchors(self, pins, anchors):
         """anchor1, anchor2 = anchors[k] {a1.x, a1.y, a2.x, a2.y} of pin pins[k]; the schedule stays (a dragged body's world pin
         follows the cursor this way)."""
-        if isinstance(pins, (list, tuple)) and not len(pins):
-            pins = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_pin_anchors", pins, anchors, 4, "set_pin_anchors")
 
     def pin_count(self):
-        n = C.c_int32(0)
-        check(self.L.phx_world_pin_count(self.h, C.byref(n)))
-        return n.value
+        return self._int32("phx_world_pin_count")
 
     def pins(self):
         """Every pin as a pin_dtype array, with the impulses the last step accumulated."""
-        out = np.zeros(self.pin_count(), dtype=pin_dtype)
-        check(self.L.phx_world_get_pins(self.h, _ptr(out), len(out)))
-        return out
+        return self._get(self.L.phx_world_get_pins, pin_dtype, self.pin_count())
 
     @property
     def pin_iterations(self):
-        n = C.c_int32(0)
-        check(self.L.phx_world_get_pin_iterations(self.h, C.byref(n)))
-        return n.value
+        return self._int32("phx_world_get_pin_iterations")
 
     @pin_iterations.setter
     def pin_iterations(self, n):
@@ -1003,139 +1010,95 @@ class World:
         check(self.L.phx_world_pin_schedule_builds(self.h, C.byref(n)))
         return n.value
 
-    # ---- links (include/phyx_amd.h LINKS; the specification: tests/link_spec.py) ----
     def add_links(self, links):
         """Append links: a link_dtype array, or rows (body1, body2, (a1x, a1y), (a2x, a2y), min_length, max_length[, hertz[, damping_ratio]])
         with impulse 0.  min == max: a rod, with hertz > 0 a spring; min < max: limits (a rope: min = 0).  Returns the new links' indices."""
-        if isinstance(links, np.ndarray) and links.dtype == link_dtype:
-            p = np.ascontiguousarray(links)
-        else:
-            rows = list(links)
-            p = np.zeros(len(rows), dtype=link_dtype)
-            for k, r in enumerate(rows):
-                p["body1"][k], p["body2"][k], p["anchor1"][k], p["anchor2"][k], p["min_length"][k], p["max_length"][k] = int(r[0]), int(r[1]), r[2], r[3], r[4], r[5]
-                if len(r) > 6:
-                    p["hertz"][k] = r[6]
-                if len(r) > 7:
-                    p["damping_ratio"][k] = r[7]
-        first = C.c_int32(0)
-        check(self.L.phx_world_add_links(self.h, _ptr(p), len(p), C.byref(first)))
-        return np.arange(first.value, first.value + len(p), dtype=np.int64)
+        return self._add_units("phx_world_add_links", links, link_dtype, ("min_length", "max_length", "hertz", "damping_ratio"), required=2)
 
     def remove_links(self, links):
         """Remove the listed links (each at most once); the others keep their order, so their indices shift."""
-        if isinstance(links, (list, tuple)) and not len(links):
-            links = np.zeros(0, dtype=np.int32)
-        idx = self._indices(links, "remove_links")
-        check(self.L.phx_world_remove_links(self.h, _ptr(idx), len(idx)))
+        self._remove_units("phx_world_remove_links", links, "remove_links")
 
     def set_link_anchors(self, links, anchors):
         """anchor1, anchor2 = anchors[k] {a1.x, a1.y, a2.x, a2.y} of link links[k]; the schedule stays (a spring to the cursor)."""
-        if isinstance(links, (list, tuple)) and not len(links):
-            links = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_link_anchors", links, anchors, 4, "set_link_anchors")
 
     def set_link_lengths(self, links, lengths):
         """min_length, max_length = lengths[k] of link links[k]; the schedule stays (a rope reeled in)."""
-        if isinstance(links, (list, tuple)) and not len(links):
-            links = np.zeros(0, dtype=np.int32)
         self._edit("phx_world_set_link_lengths", links, lengths, 2, "set_link_lengths")
 
     def link_count(self):
-        n = C.c_int32(0)
-        check(self.L.phx_world_link_count(self.h, C.byref(n)))
-        return n.value
+        return self._int32("phx_world_link_count")
 
     def links(self):
         """Every link as a link_dtype array, with the impulses the last step accumulated."""
-        out = np.zeros(self.link_count(), dtype=link_dtype)
-        check(self.L.phx_world_get_links(self.h, _ptr(out), len(out)))
-        return out
+        return self._get(self.L.phx_world_get_links, link_dtype, self.link_count())
+
+    # ---- the per-body columns: collision filters, materials, body flags ----
+    @staticmethod
+    def _per_body(what, name, v, count, kinds, lo=None, hi=None, range_text=None):
+        """A setter's value `name`: a scalar for all `count` bodies or one value per body, of the dtype kinds `kinds` ("iu": integers,
+        "fiu": numbers) and within [lo, hi] where given."""
+        a = np.asarray(v)
+        if a.dtype.kind not in kinds:
+            raise TypeError("%s: %s must be %s, got %s" % (what, name, "integers" if kinds == "iu" else "numbers", a.dtype))
+        if a.ndim > 1 or (a.ndim == 1 and a.shape != (count,)):
+            raise ValueError("%s: %s must be a scalar or have shape (%d,), got %s" % (what, name, count, a.shape))
+        if lo is not None and a.size and (int(a.min()) < lo or int(a.max()) > hi):
+            raise ValueError("%s: %s out of the range %s" % (what, name, range_text or "[%d, %d]" % (lo, hi)))
+        return a
 
     # ---- collision filters (include/phyx_amd.h COLLISION FILTERS; the specification: tests/filter_spec.py) ----
     def set_collision_filters(self, bodies, category=1, mask=0xFFFFFFFF, group=0):
         """Give the listed bodies (each at most once) the filter {category, mask, group}: each a scalar for all of them or one value per
         body.  A pair (a, b) collides iff a shared non-zero group is positive, or else each mask meets the other's category.  Manifolds
         whose pair now fails are dropped as set_state of filter_spec.drop(state()) would; returns how many were."""
-        if isinstance(bodies, (list, tuple)) and not len(bodies):
-            bodies = np.zeros(0, dtype=np.int32)
         idx = self._indices(bodies, "set_collision_filters")
         f = np.zeros(len(idx), dtype=collision_filter_dtype)
         for name, v, lo, hi in (("category", category, 0, 2 ** 32 - 1), ("mask", mask, 0, 2 ** 32 - 1),
                                 ("group", group, -2 ** 31, 2 ** 31 - 1)):
-            a = np.asarray(v)
-            if a.dtype.kind not in "iu":
-                raise TypeError("set_collision_filters: %s must be integers, got %s" % (name, a.dtype))
-            if a.ndim > 1 or (a.ndim == 1 and a.shape != (len(idx),)):
-                raise ValueError("set_collision_filters: %s must be a scalar or have shape (%d,), got %s" % (name, len(idx), a.shape))
-            if a.size and (int(a.min()) < lo or int(a.max()) > hi):
-                raise ValueError("set_collision_filters: %s out of the range [%d, %d]" % (name, lo, hi))
-            f[name] = a
+            f[name] = self._per_body("set_collision_filters", name, v, len(idx), "iu", lo, hi)
         dropped = C.c_int32(0)
         check(self.L.phx_world_set_collision_filters(self.h, _ptr(idx), _ptr(f), len(idx), C.byref(dropped)))
         return dropped.value
 
     def collision_filters(self):
         """Every body's filter, in index order: an array of collision_filter_dtype."""
-        out = np.zeros(self.counts()[0], dtype=collision_filter_dtype)
-        check(self.L.phx_world_get_collision_filters(self.h, _ptr(out), len(out)))
-        return out
+        return self._get(self.L.phx_world_get_collision_filters, collision_filter_dtype, self.counts()[0])
 
     # ---- materials (include/phyx_amd.h MATERIALS; the specification: tests/material_spec.py) ----
     def set_materials(self, bodies, friction=0.3, restitution=0.0):
         """Give the listed bodies (each at most once) the material {friction, restitution}: each a scalar for all of them or one value per
         body.  A contact uses mu = (fa + fb) * 0.5 and e = max(ea, eb) from the next step on; the library rejects friction outside
         [0, 1e6], restitution outside [0, 1] and non-finite values (PhxError), the world unchanged."""
-        if isinstance(bodies, (list, tuple)) and not len(bodies):
-            bodies = np.zeros(0, dtype=np.int32)
         idx = self._indices(bodies, "set_materials")
         m = np.zeros(len(idx), dtype=material_dtype)
         for name, v in (("friction", friction), ("restitution", restitution)):
-            a = np.asarray(v)
-            if a.dtype.kind not in "fiu":
-                raise TypeError("set_materials: %s must be numbers, got %s" % (name, a.dtype))
-            if a.ndim > 1 or (a.ndim == 1 and a.shape != (len(idx),)):
-                raise ValueError("set_materials: %s must be a scalar or have shape (%d,), got %s" % (name, len(idx), a.shape))
-            m[name] = a
+            m[name] = self._per_body("set_materials", name, v, len(idx), "fiu")
         check(self.L.phx_world_set_materials(self.h, _ptr(idx), _ptr(m), len(idx)))
 
     def materials(self):
         """Every body's material, in index order: an array of material_dtype."""
-        out = np.zeros(self.counts()[0], dtype=material_dtype)
-        check(self.L.phx_world_get_materials(self.h, _ptr(out), len(out)))
-        return out
+        return self._get(self.L.phx_world_get_materials, material_dtype, self.counts()[0])
 
     # ---- body flags / sensors (include/phyx_amd.h BODY FLAGS / SENSORS; the specification: tests/sensor_spec.py) ----
     def set_body_flags(self, bodies, flags):
         """Give the listed bodies (each at most once) the flag word `flags`: a scalar for all of them or one value per body.  BODY_SENSOR
         makes a body a trigger volume: its pairs keep their manifolds and contact points (touch events, contact reports with
         CONTACT_NO_JOINT) and get no joints, from the next step on.  The library rejects any other bit (PhxError), the world unchanged."""
-        if isinstance(bodies, (list, tuple)) and not len(bodies):
-            bodies = np.zeros(0, dtype=np.int32)
         idx = self._indices(bodies, "set_body_flags")
-        a = np.asarray(flags)
-        if a.dtype.kind not in "iu":
-            raise TypeError("set_body_flags: flags must be integers, got %s" % (a.dtype,))
-        if a.ndim > 1 or (a.ndim == 1 and a.shape != (len(idx),)):
-            raise ValueError("set_body_flags: flags must be a scalar or have shape (%d,), got %s" % (len(idx), a.shape))
-        if a.size and (int(a.min()) < 0 or int(a.max()) > 2 ** 32 - 1):
-            raise ValueError("set_body_flags: flags out of the range [0, 2^32)")
         f = np.zeros(len(idx), dtype=np.uint32)
-        f[:] = a
+        f[:] = self._per_body("set_body_flags", "flags", flags, len(idx), "iu", 0, 2 ** 32 - 1, "[0, 2^32)")
         check(self.L.phx_world_set_body_flags(self.h, _ptr(idx), _ptr(f), len(idx)))
 
     def body_flags(self):
         """Every body's flag word, in index order: a uint32 array."""
-        out = np.zeros(self.counts()[0], dtype=np.uint32)
-        check(self.L.phx_world_get_body_flags(self.h, _ptr(out), len(out)))
-        return out
+        return self._get(self.L.phx_world_get_body_flags, np.uint32, self.counts()[0])
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----
     @staticmethod
     def _queries(q, width, what, names):
-        if isinstance(q, (list, tuple)) and not len(q):
-            q = np.zeros((0, width), dtype=np.float32)
-        a = np.asarray(q)
+        a = np.asarray(_or_empty(q, (0, width), np.float32))
         if a.dtype.kind not in "iuf":
             raise TypeError("%s: queries must be a numeric array, got %s" % (what, a.dtype))
         if a.ndim != 2 or a.shape[1] != width:
@@ -1237,8 +1200,6 @@ class World:
     def contacts(self, bodies, skip_static=False):
         """The contacts of each listed body (repeats allowed): one contact_dtype record per live contact-point slot of every manifold the
         body is in, ordered by (other, manifold, slot).  Returns (offsets, records): body q's records are records[offsets[q]:offsets[q + 1]]."""
-        if isinstance(bodies, (list, tuple)) and not len(bodies):
-            bodies = np.zeros(0, dtype=np.int32)
         idx = self._indices(bodies, "contacts")
         if idx.size and idx.min() < 0:
             raise ValueError("contacts: negative body index")

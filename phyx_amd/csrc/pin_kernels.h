@@ -319,25 +319,11 @@ static __global__ void __launch_bounds__(256) k_pin_remap(const P* __restrict__ 
     }
 }
 
-// phx_world_set_pin_anchors / set_link_anchors on the device copy
-template <class P>
-static __global__ void __launch_bounds__(256) k_pin_anchors(const int* __restrict__ which, const float* __restrict__ anchors, int count, P* __restrict__ pins)
+// an edit of fields (pins.h AnchorFields, LengthFields: phx_world_set_pin_anchors / set_link_anchors / set_link_lengths) on the device copy
+template <class P, class Fields>
+static __global__ void __launch_bounds__(256) k_unit_fields(const int* __restrict__ which, const float* __restrict__ values, int count, P* __restrict__ units)
 {
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        P& p = pins[which[k]];
-        p.anchor1 = phx_vec2{anchors[4 * k], anchors[4 * k + 1]};
-        p.anchor2 = phx_vec2{anchors[4 * k + 2], anchors[4 * k + 3]};
-    }
-}
-
-// phx_world_set_link_lengths on the device copy
-static __global__ void __launch_bounds__(256) k_link_lengths(const int* __restrict__ which, const float* __restrict__ lengths, int count, phx_link* __restrict__ links)
-{
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
-        phx_link& p = links[which[k]];
-        p.min_length = lengths[2 * k];
-        p.max_length = lengths[2 * k + 1];
-    }
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) Fields::write(units[which[k]], values + Fields::width * k);
 }
 
 } // namespace phx

@@ -6,8 +6,11 @@
 // next step after the pin set or the static set changed.
 //
 // Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: the units are the pins followed by the links, one schedule and
-// one pass for both.  UnitList is the one copy of the list machinery (host and device copy, upload, fetch, remap) for either record.
+// one pass for both.  UnitList is the one copy of the list machinery (host and device copy, upload, fetch, remap, field edits) for either
+// record, and UnitKind states what the World's one copy of the calls (world.hip, "units") needs to know of a record.
 #pragma once
+
+#include <type_traits>
 
 #include "body_view.h"
 #include "schedule.h"
@@ -20,6 +23,33 @@ constexpr int PIN_MAX_ITERATIONS = 64;
 
 // the schedule of `count` pins (body2 = -1: the world, one virtual static body `nb`) as build_island_schedule makes it with one pin per unit
 void build_pin_schedule(const int32_t* body1, const int32_t* body2, int count, const unsigned char* is_static, int nb, int group_pins, Schedule& out);
+
+// what the calls know of a record: its nouns, the C calls' names, and `check`: entry k of an add beyond the body rules (the floats
+// that must be finite, then the record's own rules)
+template <class P> struct UnitKind;
+template <> struct UnitKind<phx_pin> {
+    static constexpr const char* noun = "pin";
+    static constexpr const char* plural = "pins";
+    static constexpr const char* add = "phx_world_add_pins", *remove = "phx_world_remove_pins", *set_anchors = "phx_world_set_pin_anchors", *get = "phx_world_get_pins";
+    static int check(const char* what, int k, const phx_pin& p);
+};
+template <> struct UnitKind<phx_link> {
+    static constexpr const char* noun = "link";
+    static constexpr const char* plural = "links";
+    static constexpr const char* add = "phx_world_add_links", *remove = "phx_world_remove_links", *set_anchors = "phx_world_set_link_anchors", *get = "phx_world_get_links";
+    static int check(const char* what, int k, const phx_link& p);
+    static int check_lengths(const char* what, int k, float lo, float hi, float hertz);      // (also phx_world_set_link_lengths' rule)
+};
+
+// the fields an edit between steps writes, `width` floats per record: on the host list and, by k_unit_fields, on the device copy
+struct AnchorFields {
+    static constexpr int width = 4;
+    template <class P> static __host__ __device__ void write(P& p, const float* v) { p.anchor1 = phx_vec2{v[0], v[1]}; p.anchor2 = phx_vec2{v[2], v[3]}; }
+};
+struct LengthFields {
+    static constexpr int width = 2;
+    static __host__ __device__ void write(phx_link& p, const float* v) { p.min_length = v[0]; p.max_length = v[1]; }
+};
 
 // a list of records `P` (phx_pin, phx_link: body1, body2, anchor1, anchor2 first; `impulse` the device's once uploaded)
 template <class P> class UnitList {
@@ -34,9 +64,8 @@ public:
     int remove(const int32_t* which, int count, hipStream_t stream);
     int get(P* out, hipStream_t stream);
     void clear() { host_.clear(); dirty_ = true; }
-    // an edit of fields that are the host's truth: `edit(record, k)` on the host list; the caller scatters on the device when on_device()
-    template <class F> void edit(const int32_t* which, int count, F f) { for (int k = 0; k < count; ++k) f(host_[(size_t)which[k]], k); }
-    int set_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream);
+    // an edit of fields that are the host's truth: written into the host list and, when on_device(), scattered from the staged batch `d_*`
+    template <class Fields> int set_fields(const int32_t* which, const float* values, int count, const int* d_which, const float* d_values, hipStream_t stream);
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream, bool* changed);
     int adopt_device(const P* d_src, int count, hipStream_t stream);
     int statics(const float4* mpos, unsigned* d_bits, hipStream_t stream) const;      // queues the static bits of every record's bodies
@@ -50,36 +79,21 @@ private:
 class PinSet {
 public:
     int configure_from_env();            // PHX_PIN_GROUP_PINS
-    int count() const { return pins_.count(); }
-    int link_count() const { return links_.count(); }
-    int units() const { return count() + link_count(); }                    // the pass's units: the pins, then the links
+    template <class P> UnitList<P>& list() { if constexpr (std::is_same_v<P, phx_pin>) return pins_; else return links_; }
+    template <class P> const UnitList<P>& list() const { return const_cast<PinSet*>(this)->list<P>(); }
+    int units() const { return pins_.count() + links_.count(); }            // the pass's units: the pins, then the links
     int group_pins() const { return group_pins_; }
     long long builds() const { return builds_; }
     int iterations = 8;
 
-    // the calls (arguments already checked by the World); `stream` is the world's
-    int add(const phx_pin* pins, int count, hipStream_t stream) { sched_dirty_ = true; return pins_.add(pins, count, stream); }
-    int remove(const int32_t* which, int count, hipStream_t stream) { sched_dirty_ = true; return pins_.remove(which, count, stream); }
-    int set_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream)
-    { return pins_.set_anchors(which, anchors, count, d_which, d_anchors, stream); }
-    bool on_device() const { return pins_.on_device(); }              // set_anchors needs its batch staged only then
-    int get(phx_pin* out, hipStream_t stream) { return pins_.get(out, stream); }
-    int add_links(const phx_link* links, int count, hipStream_t stream) { sched_dirty_ = true; return links_.add(links, count, stream); }
-    int remove_links(const int32_t* which, int count, hipStream_t stream) { sched_dirty_ = true; return links_.remove(which, count, stream); }
-    int set_link_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream)
-    { return links_.set_anchors(which, anchors, count, d_which, d_anchors, stream); }
-    int set_link_lengths(const int32_t* which, const float* lengths, int count, const int* d_which, const float* d_lengths, hipStream_t stream);
-    bool links_on_device() const { return links_.on_device(); }
-    int get_links(phx_link* out, hipStream_t stream) { return links_.get(out, stream); }
-    const std::vector<phx_link>& host_links() const { return links_.host(); }      // (bodies, anchors, lengths, hertz: always current)
+    // the calls (world.hip, "units") work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
+    void units_changed() { sched_dirty_ = true; }
     void clear() { pins_.clear(); links_.clear(); sched_dirty_ = true; }
-    void statics_changed() { if (units()) sched_dirty_ = true; }
+    void statics_changed() { if (units()) sched_dirty_ = true; }             // ... and a change of the static set make the schedule stale
     // a removal of bodies compacted them through `d_remap` (old index -> new or -1): the units of removed bodies go, the rest are renumbered
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream);
-    // snapshots: the device copies, current
+    // snapshots: the device copies (list<P>().device()), current
     int upload(hipStream_t stream) { PHX_TRY(pins_.upload(stream)); return links_.upload(stream); }
-    const phx_pin* device_pins() const { return pins_.device(); }
-    const phx_link* device_links() const { return links_.device(); }
     // load: the lists := device arrays (queued; the host lists follow at once)
     int adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, hipStream_t stream);
 

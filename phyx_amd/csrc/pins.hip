@@ -5,8 +5,9 @@
 // slot, group and group-body tables.  Per step nothing crosses PCIe: k_solve_pins, one workgroup per LDS group, does the whole pass of
 // those groups in one launch; the trailing group — components that do not fit a workgroup — takes a prestep launch and one launch per
 // class for the warm start and per class and sweep.
-// Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: UnitList<P> is the list machinery for either record, the
-// schedule is built over the pins followed by the links, and a world that has links launches the kernels' LINKS instantiations.
+// Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: UnitList<P> is the list machinery for either record and
+// UnitKind<P> what the World's calls check of one, the schedule is built over the pins followed by the links, and a world that has
+// links launches the kernels' LINKS instantiations.
 #include "pins.h"
 #include "pin_kernels.h"
 
@@ -86,14 +87,12 @@ template <class P> int UnitList<P>::remove(const int32_t* which, int count, hipS
     return PHX_OK;
 }
 
-template <class P> int UnitList<P>::set_anchors(const int32_t* which, const float* anchors, int count, const int* d_which, const float* d_anchors, hipStream_t stream)
+template <class P> template <class Fields>
+int UnitList<P>::set_fields(const int32_t* which, const float* values, int count, const int* d_which, const float* d_values, hipStream_t stream)
 {
-    edit(which, count, [&](P& p, int k) {
-        p.anchor1 = phx_vec2{anchors[4 * k], anchors[4 * k + 1]};
-        p.anchor2 = phx_vec2{anchors[4 * k + 2], anchors[4 * k + 3]};
-    });
+    for (int k = 0; k < count; ++k) Fields::write(host_[(size_t)which[k]], values + Fields::width * k);
     if (!on_device()) return PHX_OK;
-    hipLaunchKernelGGL(k_pin_anchors<P>, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_anchors, count, d_.p);
+    hipLaunchKernelGGL((k_unit_fields<P, Fields>), dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_values, count, d_.p);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
@@ -153,12 +152,40 @@ template <class P> int UnitList<P>::statics(const float4* mpos, unsigned* d_bits
 template class UnitList<phx_pin>;
 template class UnitList<phx_link>;
 
-int PinSet::set_link_lengths(const int32_t* which, const float* lengths, int count, const int* d_which, const float* d_lengths, hipStream_t stream)
+template int UnitList<phx_pin>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_link>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_link>::set_fields<LengthFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+
+// ---- entry k of an add beyond the body rules (the order of the checks is the calls' contract: the first failure wins) ----
+static int check_finite(const char* what, const char* noun, int k, std::initializer_list<float> values)
 {
-    links_.edit(which, count, [&](phx_link& p, int k) { p.min_length = lengths[2 * k]; p.max_length = lengths[2 * k + 1]; });
-    if (!links_.on_device()) return PHX_OK;
-    hipLaunchKernelGGL(k_link_lengths, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_lengths, count, links_.device());
-    PHX_HIP(hipGetLastError());
+    int c = 0;
+    for (const float v : values) {
+        if (!std::isfinite(v)) { set_error("%s: %s %d: value %d is not finite", what, noun, k, c); return PHX_ERR_INVALID; }
+        ++c;
+    }
+    return PHX_OK;
+}
+
+int UnitKind<phx_pin>::check(const char* what, int k, const phx_pin& p)
+{
+    return check_finite(what, noun, k, {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.impulse.x, p.impulse.y});
+}
+
+int UnitKind<phx_link>::check(const char* what, int k, const phx_link& p)
+{
+    PHX_TRY(check_finite(what, noun, k, {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.min_length, p.max_length, p.hertz, p.damping_ratio, p.impulse}));
+    if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: link %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
+    PHX_TRY(check_lengths(what, k, p.min_length, p.max_length, p.hertz));
+    if (p.reserved != 0) { set_error("%s: link %d: reserved must be 0", what, k); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int UnitKind<phx_link>::check_lengths(const char* what, int k, float lo, float hi, float hertz)
+{
+    if (!std::isfinite(lo) || !std::isfinite(hi)) { set_error("%s: link %d: a length is not finite", what, k); return PHX_ERR_INVALID; }
+    if (!(0.f <= lo && lo <= hi)) { set_error("%s: link %d: lengths [%g, %g] are not 0 <= min <= max", what, k, (double)lo, (double)hi); return PHX_ERR_INVALID; }
+    if (hertz > 0.f && lo != hi) { set_error("%s: link %d: a spring (hertz %g) needs min_length == max_length", what, k, (double)hertz); return PHX_ERR_INVALID; }
     return PHX_OK;
 }
 
@@ -177,7 +204,7 @@ int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d
 
 int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
 {
-    const int n = units(), np = count();
+    const int n = units(), np = pins_.count();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
     if (!sched_dirty_) return PHX_OK;
@@ -252,11 +279,11 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
     PHX_TRY(prepare(bodies.s.mpos, nb, rb, stream));
     phx_pin* const d_pins = pins_.device();
     phx_link* const d_links = links_.device();
-    const int np = count();
+    const int np = pins_.count();
     const float beta = 0.2f / dt;
     const PinSlot* slots = reinterpret_cast<const PinSlot*>(d_tables_.p);
     // a world without links runs the pins' own instantiation of each kernel: what it ran before there were links
-    const bool with_links = link_count() > 0;
+    const bool with_links = links_.count() > 0;
     auto pick = [with_links](auto with, auto without) { return with_links ? with : without; };
     if (sched_.lds_groups)
         hipLaunchKernelGGL(pick(k_solve_pins<true>, k_solve_pins<false>), dim3(sched_.lds_groups), dim3(PIN_LANES), 0, stream, d_pins, d_links, np, slots,

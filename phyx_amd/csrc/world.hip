@@ -193,20 +193,16 @@ public:
     int set_body_flags(const int32_t* bodies, const uint32_t* flags, int count);
     int get_body_flags(uint32_t* out, int cap);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
-    // pins (phx_world_add_pins ... phx_world_get_pin_schedule): between steps; solved at the end of pre_solve (pins.h)
-    int add_pins(const phx_pin* pins, int count, int* first);
-    int remove_pins(const int32_t* which, int count);
-    int set_pin_anchors(const int32_t* which, const float* anchors, int count);
-    int get_pins(phx_pin* out, int cap);
+    // units: pins and links, `P` = phx_pin or phx_link (phx_world_add_pins ... phx_world_get_links, phx_world_get_pin_schedule): between
+    // steps; solved at the end of pre_solve (pins.h)
+    template <class P> int add_units(const P* recs, int count, int* first);
+    template <class P> int remove_units(const int32_t* which, int count);
+    template <class P> int set_unit_anchors(const int32_t* which, const float* anchors, int count);
+    template <class P> int get_units(P* out, int cap);
+    int set_link_lengths(const int32_t* which, const float* lengths, int count);
     int set_pin_iterations(int n);
     int pin_schedule(const Schedule** out);
     int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
-    // links (phx_world_add_links ...): the pin pass's second kind of unit (include/phyx_amd.h LINKS)
-    int add_links(const phx_link* links, int count, int* first);
-    int remove_links(const int32_t* which, int count);
-    int set_link_anchors(const int32_t* which, const float* anchors, int count);
-    int set_link_lengths(const int32_t* which, const float* lengths, int count);
-    int get_links(phx_link* out, int cap);
     PinSet& pins() { return pins_; }
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
 
@@ -230,6 +226,8 @@ private:
     bool host_staged() const { return bodies_dirty_ || !bodies_.records.p; }      // the host-staged records are the world
     int restage_on_host();               // ... again, after the device copy was: records and tables come down
     int refuse_mid_step(const char* what) const;      // PHX_ERR_STATE between pre_solve / step_begin and finish_step / step_end
+    int refuse_sharded(const char* what, const char* plural) const;      // PHX_ERR_STATE: a sharded world carries no columns and no units
+    int settle_on_device();              // this world's device is current and a pending solve settled: what a call queues goes behind it, never under a replay
     int update_pairs();
     bool fuse_velocity_ = false; float step_dt_ = 0.f;      // IntegrateVelocity rides on the broadphase's key build (update_pairs)
     int fresh_manifolds_ = 0;           // pairs UpdatePairs found this step: their manifolds are created by UpdateManifolds' kernel
@@ -329,11 +327,14 @@ private:
     BodyTable<MaterialColumn> materials_;
     BodyTable<FlagsColumn> flags_col_;
     template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); return f(flags_col_); }
+    // the three setters' skeleton: `rule(k)` is the call's own check of entry k
+    template <class Column, class Rule>
+    int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
     PinSet pins_;
-    int check_pin_indices(const char* what, const int32_t* which, const void* values, int count, bool links = false);
-    int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2, const float* v, int nv);
-    // an edit of `width` floats per listed unit: staged for the scatter kernel when the list is on the device
-    int stage_unit_edit(bool on_device, const int32_t* which, const float* values, int count, int width, const int** d_which, const float** d_values);
+    template <class P> int check_unit_indices(const char* what, const int32_t* which, const void* values, int count);
+    int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2);
+    // an edit of Fields::width floats per listed unit (already checked): staged for the scatter kernel when the list is on the device
+    template <class P, class Fields> int set_unit_fields(const int32_t* which, const float* values, int count);
     BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr()}; }
     BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr()}; }
 };
@@ -408,6 +409,19 @@ int World::refuse_mid_step(const char* what) const
     if (!mid_step_) return PHX_OK;
     set_error("%s: the world is between pre_solve / step_begin and finish_step / step_end", what);
     return PHX_ERR_STATE;
+}
+
+int World::refuse_sharded(const char* what, const char* plural) const
+{
+    if (shard_count <= 1 && !comm_) return PHX_OK;
+    set_error("%s: a sharded world carries no %s", what, plural);
+    return PHX_ERR_STATE;
+}
+
+int World::settle_on_device()
+{
+    PHX_TRY(use_device(device_));
+    return solver_.has_pending() ? solver_.synchronize() : PHX_OK;
 }
 
 int World::set_static(int body)
@@ -1025,9 +1039,11 @@ int World::save(Snapshot& s)
     v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
     PHX_TRY(pins_.upload(stream_));
-    PHX_TRY(s.reserve_units(pins_.count(), pins_.link_count(), stream_));
+    const UnitList<phx_pin>& pins = pins_.list<phx_pin>();
+    const UnitList<phx_link>& links = pins_.list<phx_link>();
+    PHX_TRY(s.reserve_units(pins.count(), links.count(), stream_));
     PHX_TRY(s.save(v, stream_));
-    return s.save_units(pins_.device_pins(), pins_.count(), pins_.device_links(), pins_.link_count(), stream_);
+    return s.save_units(pins.device(), pins.count(), links.device(), links.count(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -1165,8 +1181,7 @@ int World::edit(Edit kind, const int* bodies, const float* values, int count)
         }
         return PHX_OK;
     }
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());             // (the edit goes behind a settled solve, never under a replay)
+    PHX_TRY(settle_on_device());
     const int* d_bodies = nullptr; const float* d_values = nullptr;
     PHX_TRY(stage_batch(bodies, values, count, width, &d_bodies, &d_values));
     if (kind == EDIT_ACCELERATIONS) {
@@ -1235,9 +1250,8 @@ int World::get_poses_device(void* d_out, int cap)
     if (cap < n) { set_error("phx_world_get_poses_device: room for %d bodies, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
     if (!n) return PHX_OK;
     if (!d_out || (reinterpret_cast<uintptr_t>(d_out) & 15u)) { set_error("phx_world_get_poses_device: the output must be a 16-byte aligned device pointer"); return PHX_ERR_INVALID; }
-    PHX_TRY(use_device(device_));
+    PHX_TRY(settle_on_device());                                            // (nothing is pending while the bodies are host-staged: every call that stages them settles first)
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
     hipLaunchKernelGGL(k_world_poses, dim3(wgrid(n)), dim3(256), 0, stream_, resident(), n, static_cast<float4*>(d_out));
     PHX_HIP(hipGetLastError());
     return PHX_OK;
@@ -1387,8 +1401,7 @@ int World::add_bodies(const float* spawn, int count, int* first)
         for (int k = 0; k < count; ++k) { const float* q = spawn + 5 * (size_t)k; add_body(q[0], q[1], q[2], q[3], q[4]); }
         return PHX_OK;
     }
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());             // (the spawn goes behind a settled solve, never under a replay)
+    PHX_TRY(settle_on_device());
     spawn_rows_.resize((size_t)count * SPAWN_ROW);
     bool any_static = false;
     for (int k = 0; k < count; ++k) {
@@ -1430,13 +1443,33 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
         for (int k = 0; k < count; ++k) { phx_rigid_body& b = host_bodies_[(size_t)bodies[k]]; b.inv_mass = values[2 * k]; b.inv_inertia = values[2 * k + 1]; }
         return PHX_OK;
     }
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
+    PHX_TRY(settle_on_device());
     const int* d_bodies = nullptr; const float* d_values = nullptr;
     PHX_TRY(stage_batch(bodies, values, count, 2, &d_bodies, &d_values));
     hipLaunchKernelGGL(k_set_inverse_masses, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, d_values, count, bodies_.mpos.p, bodies_.records.p);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
+}
+
+// ---- the optional columns' setters ---------------------------------------------------------------------------------------------
+// One skeleton for the three (phx_world_set_collision_filters / set_materials / set_body_flags).  A sharded world is refused before anything else (also inside a step); then the batch and `rule` for
+// every entry, all of it or none of it; a host-staged world's table is the host's (where `host_path_ok`), otherwise the batch is
+// staged as 4-byte words (world_kernels.h) and scattered behind a settled solve.
+template <class Column, class Rule>
+int World::set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok)
+{
+    PHX_TRY(refuse_sharded(what, Column::plural));
+    PHX_TRY(check_batch(what, bodies, values, count, true));
+    for (int k = 0; k < count; ++k) PHX_TRY(rule(k));
+    if (!count) return PHX_OK;
+    const int n = nb();
+    if (host_staged() && host_path_ok) { table.set_host(bodies, values, count, n); return PHX_OK; }      // (the table goes up with the bodies)
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before the table changes)
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(values), count, (int)(sizeof(typename Column::api) / sizeof(float)), &d_bodies, &d_values));
+    return table.set_device(d_bodies, d_values, count, n, stream_);
 }
 
 // ---- collision filters ------------------------------------------------------------------------------------------------------------
@@ -1445,20 +1478,9 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
 // is the removal's compaction of the contact cache with the filter as its keep predicate (FilterKept), bodies untouched.
 int World::set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped)
 {
-    static const char* const what = "phx_world_set_collision_filters";
-    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no collision filters", what); return PHX_ERR_STATE; }
-    PHX_TRY(check_batch(what, bodies, filters, count, true));
+    PHX_TRY(set_column("phx_world_set_collision_filters", filters_, bodies, filters, count, [](int) { return PHX_OK; }, !nm));      // (on the host while no pair exists to drop)
     if (dropped) *dropped = 0;
-    if (!count) return PHX_OK;
-    const int n = nb();
-    if (host_staged() && !nm) { filters_.set_host(bodies, filters, count, n); return PHX_OK; }      // (no pair exists to drop)
-    PHX_TRY(use_device(device_));
-    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
-    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
-    const int* d_bodies = nullptr; const float* d_values = nullptr;
-    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(filters), count, 3, &d_bodies, &d_values));
-    PHX_TRY(filters_.set_device(d_bodies, d_values, count, n, stream_));
-    if (!nm) return PHX_OK;
+    if (!count || !nm) return PHX_OK;
     // the manifolds whose pair now fails go, with their slots and joints; the one round trip brings back the kept counts
     PHX_TRY(compaction_scratch());
     const FilterKept kept{filters_.dev.p};
@@ -1504,21 +1526,12 @@ int World::refuse_tables(const char* what)
 int World::set_materials(const int32_t* bodies, const phx_material* materials, int count)
 {
     static const char* const what = "phx_world_set_materials";
-    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no materials", what); return PHX_ERR_STATE; }
-    PHX_TRY(check_batch(what, bodies, materials, count, true));
-    for (int k = 0; k < count; ++k) {                                       // (NaN fails both comparisons)
+    return set_column(what, materials_, bodies, materials, count, [=](int k) {      // (NaN fails both comparisons)
         const float f = materials[k].friction, e = materials[k].restitution;
         if (!(f >= 0.f && f <= 1e6f)) { set_error("%s: friction %g of body %d is not in [0, 1e6]", what, (double)f, bodies[k]); return PHX_ERR_INVALID; }
         if (!(e >= 0.f && e <= 1.f)) { set_error("%s: restitution %g of body %d is not in [0, 1]", what, (double)e, bodies[k]); return PHX_ERR_INVALID; }
-    }
-    if (!count) return PHX_OK;
-    const int n = nb();
-    if (host_staged()) { materials_.set_host(bodies, materials, count, n); return PHX_OK; }      // (the table goes up with the bodies)
-    PHX_TRY(use_device(device_));
-    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before the table changes)
-    const int* d_bodies = nullptr; const float* d_values = nullptr;
-    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(materials), count, 2, &d_bodies, &d_values));
-    return materials_.set_device(d_bodies, d_values, count, n, stream_);
+        return PHX_OK;
+    }, true);
 }
 
 // ---- body flags / sensors -----------------------------------------------------------------------------------------------------------
@@ -1527,38 +1540,32 @@ int World::set_materials(const int32_t* bodies, const phx_material* materials, i
 int World::set_body_flags(const int32_t* bodies, const uint32_t* flags, int count)
 {
     static const char* const what = "phx_world_set_body_flags";
-    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no body flags", what); return PHX_ERR_STATE; }
-    PHX_TRY(check_batch(what, bodies, flags, count, true));
-    for (int k = 0; k < count; ++k)
+    return set_column(what, flags_col_, bodies, flags, count, [=](int k) {
         if (flags[k] & ~(uint32_t)PHX_BODY_SENSOR) { set_error("%s: flags 0x%x of body %d hold an unknown bit", what, flags[k], bodies[k]); return PHX_ERR_INVALID; }
-    if (!count) return PHX_OK;
-    const int n = nb();
-    if (host_staged()) { flags_col_.set_host(bodies, flags, count, n); return PHX_OK; }      // (the table goes up with the bodies)
-    PHX_TRY(use_device(device_));
-    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before the table changes)
-    const int* d_bodies = nullptr; const float* d_values = nullptr;
-    PHX_TRY(stage_batch(bodies, reinterpret_cast<const float*>(flags), count, 1, &d_bodies, &d_values));
-    return flags_col_.set_device(d_bodies, d_values, count, n, stream_);
+        return PHX_OK;
+    }, true);
 }
 int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_get_body_flags", flags_col_, out, cap); }
 
-// ---- pins -------------------------------------------------------------------------------------------------------------------------
-// The rules and the arithmetic: include/phyx_amd.h PINS; the list, the schedule and the pass: pins.h.  The calls check everything first,
-// then change the list; the schedule follows lazily at the next step.
+// ---- units: pins and links --------------------------------------------------------------------------------------------------------
+// The rules and the arithmetic: include/phyx_amd.h PINS, LINKS; the lists, the schedule and the pass: pins.h.  One copy of the calls for
+// both records (`P`; what differs is UnitKind<P>): they check everything first — inside a step, sharded, count, null, overflow, the
+// entries in order — then change the list; the schedule follows lazily at the next step.
 int World::refuse_pins(const char* what)
 {
     if (!pins_.units()) return PHX_OK;
-    set_error("%s: the world holds %s, which a sharded world does not carry", what, pins_.count() ? "pins" : "links");
+    set_error("%s: the world holds %s, which a sharded world does not carry", what, pins_.list<phx_pin>().count() ? "pins" : "links");
     return PHX_ERR_STATE;
 }
 
-int World::check_pin_indices(const char* what, const int32_t* which, const void* values, int count, bool links)
+template <class P>
+int World::check_unit_indices(const char* what, const int32_t* which, const void* values, int count)
 {
     PHX_TRY(refuse_mid_step(what));
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && (!which || !values)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
-    const int n = links ? pins_.link_count() : pins_.count();
-    const char* const noun = links ? "link" : "pin";
+    const int n = pins_.list<P>().count();
+    const char* const noun = UnitKind<P>::noun;
     std::vector<unsigned char> seen((size_t)n, 0);
     for (int k = 0; k < count; ++k) {
         if (which[k] < 0 || which[k] >= n) { set_error("%s: %s index %d out of range [0, %d)", what, noun, which[k], n); return PHX_ERR_INVALID; }
@@ -1568,76 +1575,92 @@ int World::check_pin_indices(const char* what, const int32_t* which, const void*
     return PHX_OK;
 }
 
-// the body rules and the finite floats of entry k of an add_pins / add_links call
-int World::check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2, const float* v, int nv)
+// the body rules of entry k of an add (the record's own: UnitKind<P>::check)
+int World::check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2)
 {
     const int n = nb();
     if (body1 < 0 || body1 >= n) { set_error("%s: %s %d: body1 %d out of range [0, %d)", what, noun, k, body1, n); return PHX_ERR_INVALID; }
     if (body2 < -1 || body2 >= n) { set_error("%s: %s %d: body2 %d is neither -1 nor in [0, %d)", what, noun, k, body2, n); return PHX_ERR_INVALID; }
     if (body1 == body2) { set_error("%s: %s %d: both ends on body %d", what, noun, k, body1); return PHX_ERR_INVALID; }
-    for (int c = 0; c < nv; ++c)
-        if (!std::isfinite(v[c])) { set_error("%s: %s %d: value %d is not finite", what, noun, k, c); return PHX_ERR_INVALID; }
     return PHX_OK;
 }
 
-int World::stage_unit_edit(bool on_device, const int32_t* which, const float* values, int count, int width, const int** d_which, const float** d_values)
+template <class P>
+int World::add_units(const P* recs, int count, int* first)
 {
-    *d_which = nullptr; *d_values = nullptr;
-    if (!on_device) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
-    return stage_batch(which, values, count, width, d_which, d_values);
-}
-
-int World::add_pins(const phx_pin* pins, int count, int* first)
-{
-    static const char* const what = "phx_world_add_pins";
+    using Kind = UnitKind<P>;
+    const char* const what = Kind::add;
     PHX_TRY(refuse_mid_step(what));
-    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no pins", what); return PHX_ERR_STATE; }
+    PHX_TRY(refuse_sharded(what, Kind::plural));
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
-    if (count && !pins) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
-    if ((long long)pins_.count() + count > (long long)INT32_MAX) { set_error("%s: %d + %d pins exceed the int32 range", what, pins_.count(), count); return PHX_ERR_INVALID; }
+    if (count && !recs) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    // (the schedule numbers the units, pins and links together, in an int32)
+    if ((long long)pins_.units() + count > (long long)INT32_MAX) { set_error("%s: %d + %d units exceed the int32 range", what, pins_.units(), count); return PHX_ERR_INVALID; }
     for (int k = 0; k < count; ++k) {
-        const phx_pin& p = pins[k];
-        const float v[6] = {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.impulse.x, p.impulse.y};
-        PHX_TRY(check_unit_bodies(what, "pin", k, p.body1, p.body2, v, 6));
+        PHX_TRY(check_unit_bodies(what, Kind::noun, k, recs[k].body1, recs[k].body2));
+        PHX_TRY(Kind::check(what, k, recs[k]));
     }
-    if (first) *first = pins_.count();
+    UnitList<P>& list = pins_.list<P>();
+    if (first) *first = list.count();
     if (!count) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
-    return pins_.add(pins, count, stream_);
+    PHX_TRY(settle_on_device());
+    pins_.units_changed();
+    return list.add(recs, count, stream_);
 }
 
-int World::remove_pins(const int32_t* which, int count)
+template <class P>
+int World::remove_units(const int32_t* which, int count)
 {
-    PHX_TRY(check_pin_indices("phx_world_remove_pins", which, which, count));
+    PHX_TRY(check_unit_indices<P>(UnitKind<P>::remove, which, which, count));
     if (!count) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
-    return pins_.remove(which, count, stream_);
+    PHX_TRY(settle_on_device());
+    pins_.units_changed();
+    return pins_.list<P>().remove(which, count, stream_);
 }
 
-int World::set_pin_anchors(const int32_t* which, const float* anchors, int count)
+template <class P, class Fields>
+int World::set_unit_fields(const int32_t* which, const float* values, int count)
 {
-    static const char* const what = "phx_world_set_pin_anchors";
-    PHX_TRY(check_pin_indices(what, which, anchors, count));
+    if (!count) return PHX_OK;
+    UnitList<P>& list = pins_.list<P>();
+    const int* d_which = nullptr; const float* d_values = nullptr;
+    if (list.on_device()) {
+        PHX_TRY(settle_on_device());
+        PHX_TRY(stage_batch(which, values, count, Fields::width, &d_which, &d_values));
+    }
+    return list.template set_fields<Fields>(which, values, count, d_which, d_values, stream_);
+}
+
+template <class P>
+int World::set_unit_anchors(const int32_t* which, const float* anchors, int count)
+{
+    const char* const what = UnitKind<P>::set_anchors;
+    PHX_TRY(check_unit_indices<P>(what, which, anchors, count));
     for (int k = 0; k < 4 * count; ++k)
         if (!std::isfinite(anchors[k])) { set_error("%s: entry %d: value %d is not finite", what, k / 4, k % 4); return PHX_ERR_INVALID; }
-    if (!count) return PHX_OK;
-    const int* d_which = nullptr; const float* d_anchors = nullptr;
-    PHX_TRY(stage_unit_edit(pins_.on_device(), which, anchors, count, 4, &d_which, &d_anchors));
-    return pins_.set_anchors(which, anchors, count, d_which, d_anchors, stream_);
+    return set_unit_fields<P, AnchorFields>(which, anchors, count);
 }
 
-int World::get_pins(phx_pin* out, int cap)
+int World::set_link_lengths(const int32_t* which, const float* lengths, int count)
 {
-    const int n = pins_.count();
-    if (cap < n) { set_error("phx_world_get_pins: room for %d pins, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
+    static const char* const what = "phx_world_set_link_lengths";
+    PHX_TRY(check_unit_indices<phx_link>(what, which, lengths, count));
+    const std::vector<phx_link>& links = pins_.list<phx_link>().host();     // (bodies, anchors, lengths, hertz: always current)
+    for (int k = 0; k < count; ++k)
+        PHX_TRY(UnitKind<phx_link>::check_lengths(what, k, lengths[2 * k], lengths[2 * k + 1], links[(size_t)which[k]].hertz));
+    return set_unit_fields<phx_link, LengthFields>(which, lengths, count);
+}
+
+template <class P>
+int World::get_units(P* out, int cap)
+{
+    UnitList<P>& list = pins_.list<P>();
+    const int n = list.count();
+    if (cap < n) { set_error("%s: room for %d %s, the world has %d", UnitKind<P>::get, cap, UnitKind<P>::plural, n); return PHX_ERR_CAPACITY; }
     if (!n) return PHX_OK;
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());
-    return pins_.get(out, stream_);
+    return list.get(out, stream_);
 }
 
 int World::set_pin_iterations(int n)
@@ -1659,81 +1682,6 @@ int World::pin_schedule(const Schedule** out)
     PHX_TRY(pins_.prepare(bodies_.mpos.p, nb(), rb_, stream_));
     *out = &pins_.schedule();
     return PHX_OK;
-}
-
-// ---- links: the pins' calls for the pass's other kind of unit (include/phyx_amd.h LINKS) ----
-static int check_link_lengths(const char* what, int k, float lo, float hi, float hertz)
-{
-    if (!std::isfinite(lo) || !std::isfinite(hi)) { set_error("%s: link %d: a length is not finite", what, k); return PHX_ERR_INVALID; }
-    if (!(0.f <= lo && lo <= hi)) { set_error("%s: link %d: lengths [%g, %g] are not 0 <= min <= max", what, k, (double)lo, (double)hi); return PHX_ERR_INVALID; }
-    if (hertz > 0.f && lo != hi) { set_error("%s: link %d: a spring (hertz %g) needs min_length == max_length", what, k, (double)hertz); return PHX_ERR_INVALID; }
-    return PHX_OK;
-}
-
-int World::add_links(const phx_link* links, int count, int* first)
-{
-    static const char* const what = "phx_world_add_links";
-    PHX_TRY(refuse_mid_step(what));
-    if (shard_count > 1 || comm_) { set_error("%s: a sharded world carries no links", what); return PHX_ERR_STATE; }
-    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
-    if (count && !links) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
-    if ((long long)pins_.units() + count > (long long)INT32_MAX) { set_error("%s: %d + %d units exceed the int32 range", what, pins_.units(), count); return PHX_ERR_INVALID; }
-    for (int k = 0; k < count; ++k) {
-        const phx_link& p = links[k];
-        const float v[9] = {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.min_length, p.max_length, p.hertz, p.damping_ratio, p.impulse};
-        PHX_TRY(check_unit_bodies(what, "link", k, p.body1, p.body2, v, 9));
-        if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: link %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
-        PHX_TRY(check_link_lengths(what, k, p.min_length, p.max_length, p.hertz));
-        if (p.reserved != 0) { set_error("%s: link %d: reserved must be 0", what, k); return PHX_ERR_INVALID; }
-    }
-    if (first) *first = pins_.link_count();
-    if (!count) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
-    return pins_.add_links(links, count, stream_);
-}
-
-int World::remove_links(const int32_t* which, int count)
-{
-    PHX_TRY(check_pin_indices("phx_world_remove_links", which, which, count, true));
-    if (!count) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    if (solver_.has_pending()) PHX_TRY(solver_.synchronize());
-    return pins_.remove_links(which, count, stream_);
-}
-
-int World::set_link_anchors(const int32_t* which, const float* anchors, int count)
-{
-    static const char* const what = "phx_world_set_link_anchors";
-    PHX_TRY(check_pin_indices(what, which, anchors, count, true));
-    for (int k = 0; k < 4 * count; ++k)
-        if (!std::isfinite(anchors[k])) { set_error("%s: entry %d: value %d is not finite", what, k / 4, k % 4); return PHX_ERR_INVALID; }
-    if (!count) return PHX_OK;
-    const int* d_which = nullptr; const float* d_anchors = nullptr;
-    PHX_TRY(stage_unit_edit(pins_.links_on_device(), which, anchors, count, 4, &d_which, &d_anchors));
-    return pins_.set_link_anchors(which, anchors, count, d_which, d_anchors, stream_);
-}
-
-int World::set_link_lengths(const int32_t* which, const float* lengths, int count)
-{
-    static const char* const what = "phx_world_set_link_lengths";
-    PHX_TRY(check_pin_indices(what, which, lengths, count, true));
-    for (int k = 0; k < count; ++k)
-        PHX_TRY(check_link_lengths(what, k, lengths[2 * k], lengths[2 * k + 1], pins_.host_links()[(size_t)which[k]].hertz));
-    if (!count) return PHX_OK;
-    const int* d_which = nullptr; const float* d_lengths = nullptr;
-    PHX_TRY(stage_unit_edit(pins_.links_on_device(), which, lengths, count, 2, &d_which, &d_lengths));
-    return pins_.set_link_lengths(which, lengths, count, d_which, d_lengths, stream_);
-}
-
-int World::get_links(phx_link* out, int cap)
-{
-    const int n = pins_.link_count();
-    if (cap < n) { set_error("phx_world_get_links: room for %d links, the world has %d", cap, n); return PHX_ERR_CAPACITY; }
-    if (!n) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    PHX_TRY(solver_.synchronize());
-    return pins_.get_links(out, stream_);
 }
 
 // ---- queries ------------------------------------------------------------------------------------------------------------------------
@@ -2283,44 +2231,44 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
 int phx_world_add_pins(phx_world* w, const phx_pin* pins, int32_t count, int32_t* first)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.add_pins(pins, count, first);
+    return w->impl.add_units(pins, count, first);
 }
 
 int phx_world_remove_pins(phx_world* w, const int32_t* pins, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.remove_pins(pins, count);
+    return w->impl.remove_units<phx_pin>(pins, count);
 }
 
 int phx_world_set_pin_anchors(phx_world* w, const int32_t* pins, const float* anchors, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.set_pin_anchors(pins, anchors, count);
+    return w->impl.set_unit_anchors<phx_pin>(pins, anchors, count);
 }
 
 int phx_world_get_pins(phx_world* w, phx_pin* out, int32_t cap)
 {
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
-    return w->impl.get_pins(out, cap);
+    return w->impl.get_units(out, cap);
 }
 
 int phx_world_add_links(phx_world* w, const phx_link* links, int32_t count, int32_t* first)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.add_links(links, count, first);
+    return w->impl.add_units(links, count, first);
 }
 
 int phx_world_remove_links(phx_world* w, const int32_t* links, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.remove_links(links, count);
+    return w->impl.remove_units<phx_link>(links, count);
 }
 
 int phx_world_set_link_anchors(phx_world* w, const int32_t* links, const float* anchors, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.set_link_anchors(links, anchors, count);
+    return w->impl.set_unit_anchors<phx_link>(links, anchors, count);
 }
 
 int phx_world_set_link_lengths(phx_world* w, const int32_t* links, const float* lengths, int32_t count)
@@ -2333,20 +2281,20 @@ int phx_world_get_links(phx_world* w, phx_link* out, int32_t cap)
 {
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
-    return w->impl.get_links(out, cap);
+    return w->impl.get_units(out, cap);
 }
 
 int phx_world_link_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
-    *count = w->impl.pins().link_count();
+    *count = w->impl.pins().list<phx_link>().count();
     return PHX_OK;
 }
 
 int phx_world_pin_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
-    *count = w->impl.pins().count();
+    *count = w->impl.pins().list<phx_pin>().count();
     return PHX_OK;
 }
 
