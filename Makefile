@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge clean
+.PHONY: build test test-gpu bench smoke example place bridge crank clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -25,6 +25,9 @@ place: build                ## the emitter that looks first (phx_world_query_box
 bridge: build               ## links: a pinned deck on rod hangers, a crate on a rope, a box on a spring (phx_world_add_links)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/bridge.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/bridge
 
+crank: build                ## angles: a door with stops, a wheel on a motor, two boxes welded by a pin plus a lock (phx_world_add_angles)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/crank.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/crank
+
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank
 	rm -rf oracle/_ref

@@ -898,6 +898,58 @@ int  phx_world_set_link_lengths(phx_world* w, const int32_t* links, const float*
 int  phx_world_get_links(phx_world* w, phx_link* out, int32_t cap);
 int  phx_world_link_count(phx_world* w, int32_t* count);
 
+/* ANGLES — constrain the relative ANGLE of two bodies, or of a body against the world (body2 = -1: the identity frame, w = 0): a lock
+ * (with a pin: a weld), limits (a door's stops, an elbow), a torsion spring, a motor (a driven or braked wheel).  tests/angle_spec.py is
+ * the definition (scalar float32, every operation rounded on its own, no fused multiply-add, IEEE division) and the device matches it
+ * byte for byte.  Angles are the pin pass's third kind of unit: the units are the pins, then the links, then the angles (unit
+ * u < pin_count is pin u, u < pin_count + link_count is link u - pin_count, any other is angle u - pin_count - link_count), one
+ * schedule, one launch, one Gauss-Seidel sweep.  Wherever PINS and LINKS say "pin" or "unit" of the schedule the angles count too:
+ * phx_world_get_pin_schedule needs order_cap >= pin_count + link_count + angle_count, add_angles / remove_angles rebuild the schedule.
+ *   - The angle.  With xA, xB the bodies' xVector (the world: (1, 0)):
+ *         c = xA.x xB.x + xA.y xB.y,  s = xA.x xB.y - xA.y xB.x,  theta = (float)atan2((double)(-s), (double)c)
+ *     in the prestep only (the double-precision atan2 rounded to float, as IntegratePosition's cos / sin).  angularVelocity is
+ *     clockwise-positive (PINS), theta is the clockwise angle of B against A and d theta / dt = wB - wA.  Against the world the world is
+ *     B: a body1 that turns with w > 0 LOSES w dt of theta per step (put the reference body first to read it the other way).
+ *         mid = (lower + upper) 0.5f,  half = (upper - lower) 0.5f,  phi = theta - mid, wrapped once: phi > PI: phi - TWO_PI,
+ *         phi < -PI: phi + TWO_PI, with PI = 3.1415927f, TWO_PI = 6.2831855f
+ *     so a lock at 3 rad does not jump where theta crosses pi, and a range wider than 2 PI is never engaged (a pure motor).
+ *   - kinv = iA + iB.  An angle with !(kinv > 0) is INACTIVE this step: impulse := 0, motor_impulse := 0, nothing else.
+ *   - The row L follows from the data (decided at the prestep, not speculative, as a rope's limit):
+ *         lock    lower == upper, hertz == 0: C = phi, impulse unbounded, bias = C (0.2f / dt), gamma = 0
+ *         spring  lower == upper, hertz > 0 (the Box2D soft constraint): C = phi, mass = 1 / kinv, w = 6.2831855f hertz,
+ *                 dmp = 2 mass damping_ratio w, k = mass w^2, gamma = 1 / (dt (dmp + dt k)), bias = C dt k gamma
+ *         limits  lower < upper: phi >= half: C = phi - half, impulse <= 0; phi <= -half: C = phi + half, impulse >= 0 (bias as the
+ *                 lock's); otherwise L is IDLE this step: impulse := 0
+ *     The row M, the motor, is on where max_torque > 0: it drives wB - wA to motor_speed, its accumulated motor_impulse clamped to
+ *     +- max_torque dt.  Off: motor_impulse := 0.  An angle with neither row engaged writes both impulses 0 and nothing else: its bodies
+ *     move bit for bit as without it.
+ *   - warm start: motor_impulse clamped to its range, then impulse clamped to the engaged limit's, each applied where its row is on, M
+ *     first.  n sweeps, M first, then L (Box2D's order), each on the velocities the other left:
+ *         M: cdot = wB - wA, d = -((1 / kinv) (cdot - motor_speed)), new = clamp(motor_impulse + d), apply new - motor_impulse
+ *         L: cdot = wB - wA, d = -((1 / (kinv + gamma)) ((cdot + bias) + gamma impulse)); lock, spring: impulse += d, apply d;
+ *            limits: new = clamp(impulse + d), apply new - impulse          (clamp: x < lo ? lo : x > hi ? hi : x, so a NaN passes)
+ *         apply d: wA -= iA d, wB += iB d.  Linear velocities are not touched; a static body is not written.
+ *   - The calls follow the pins' and links' rules word for word.  Checked at add: the pins' body rules, every float finite,
+ *     lower <= upper, hertz >= 0, damping_ratio >= 0, max_torque >= 0, hertz > 0 only with lower == upper.  set_angle_limits is checked
+ *     against the angle's stored hertz, set_angle_motors wants finite values and max_torque >= 0; both keep the schedule.  There are no
+ *     anchors to set.
+ *   - The other calls, as for links: remove_bodies / remove_outside drop the angles of removed bodies and remap the rest; set_state drops
+ *     every angle; save / load carry the angles with both impulses in HBM; phx_snapshot_export and phx_snapshot_blob_bytes of a snapshot
+ *     that holds angles return PHX_ERR_STATE; set_shard (count > 1), set_comm, reslab and add_angles on a sharded world return
+ *     PHX_ERR_STATE.  A world without angles allocates and launches exactly what it did without them. */
+typedef struct { int32_t body1, body2;            /* body2 = -1: the world (identity frame, w = 0) */
+                 float lower, upper;               /* radians, on the relative angle theta */
+                 float hertz, damping_ratio;       /* > 0 only with lower == upper: a torsion spring */
+                 float motor_speed, max_torque;    /* max_torque > 0: the motor row is on */
+                 float impulse, motor_impulse;     /* accumulated angular impulses: the warm start */
+} phx_angle;                                       /* 40 B */
+int  phx_world_add_angles(phx_world* w, const phx_angle* angles, int32_t count, int32_t* first);   /* *first (may be NULL) = index of the first new angle */
+int  phx_world_remove_angles(phx_world* w, const int32_t* angles, int32_t count);
+int  phx_world_set_angle_limits(phx_world* w, const int32_t* angles, const float* limits /* 2 per angle: lower, upper */, int32_t count);
+int  phx_world_set_angle_motors(phx_world* w, const int32_t* angles, const float* motors /* 2 per angle: motor_speed, max_torque */, int32_t count);
+int  phx_world_get_angles(phx_world* w, phx_angle* out, int32_t cap);
+int  phx_world_angle_count(phx_world* w, int32_t* count);
+
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);
 /* handles owned by the world (for stage-level queries after an update) */

@@ -54,6 +54,9 @@ assert pin_dtype.itemsize == 32
 link_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("min_length", "<f4"), ("max_length", "<f4"),
                        ("hertz", "<f4"), ("damping_ratio", "<f4"), ("impulse", "<f4"), ("reserved", "<u4")])      # phx_link
 assert link_dtype.itemsize == 48
+angle_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("lower", "<f4"), ("upper", "<f4"), ("hertz", "<f4"), ("damping_ratio", "<f4"),
+                        ("motor_speed", "<f4"), ("max_torque", "<f4"), ("impulse", "<f4"), ("motor_impulse", "<f4")])      # phx_angle
+assert angle_dtype.itemsize == 40
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
@@ -938,20 +941,23 @@ class World:
         the next step rebuilds the solver's schedule."""
         self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
 
-    # ---- units: pins and links (include/phyx_amd.h PINS, LINKS; the specifications: tests/pin_spec.py, tests/link_spec.py) ----
-    def _add_units(self, fn, recs, dtype, extra=(), required=0):
-        """recs: an array of `dtype`, or rows (body1, body2, anchor1, anchor2, then the fields `extra`, the first `required` of them
-        always); the rest of a record is zero."""
+    # ---- units: pins, links and angles (include/phyx_amd.h PINS, LINKS, ANGLES; the specifications: tests/pin_spec.py, link_spec.py, angle_spec.py) ----
+    def _add_units(self, fn, recs, dtype, extra=(), required=0, anchors=True):
+        """recs: an array of `dtype`, or rows (body1, body2, anchor1, anchor2 (unless the record has no `anchors`), then the fields
+        `extra`, the first `required` of them always); the rest of a record is zero."""
         if isinstance(recs, np.ndarray) and recs.dtype == dtype:
             p = np.ascontiguousarray(recs)
         else:
             rows = list(recs)
             p = np.zeros(len(rows), dtype=dtype)
             for k, r in enumerate(rows):
-                p["body1"][k], p["body2"][k], p["anchor1"][k], p["anchor2"][k] = int(r[0]), int(r[1]), r[2], r[3]
+                p["body1"][k], p["body2"][k] = int(r[0]), int(r[1])
+                if anchors:
+                    p["anchor1"][k], p["anchor2"][k] = r[2], r[3]
+                at = 4 if anchors else 2
                 for i, name in enumerate(extra):
-                    if i < required or len(r) > 4 + i:
-                        p[name][k] = r[4 + i]
+                    if i < required or len(r) > at + i:
+                        p[name][k] = r[at + i]
         first = C.c_int32(0)
         check(getattr(self.L, fn)(self.h, _ptr(p), len(p), C.byref(first)))
         return np.arange(first.value, first.value + len(p), dtype=np.int64)
@@ -996,10 +1002,10 @@ class World:
 
     def pin_schedule(self):
         """The schedule the next step's pin pass uses (built now unless current) -> dict with order, class_offsets, group_offsets,
-        lds_groups, as api.pin_schedule.  The slots hold units: unit u < pin_count() is pin u, otherwise link u - pin_count()."""
+        lds_groups, as api.pin_schedule.  The slots hold units: the pins, then the links, then the angles."""
         nc = C.c_int32(0); ng = C.c_int32(0); lg = C.c_int32(0)
         check(self.L.phx_world_get_pin_schedule(self.h, None, 0, None, 0, C.byref(nc), None, 0, C.byref(ng), C.byref(lg)))
-        n = self.pin_count() + self.link_count()
+        n = self.pin_count() + self.link_count() + self.angle_count()
         order = np.zeros(max(n, 1), dtype=np.int32)
         coff = np.zeros(nc.value + 1, dtype=np.int32); goff = np.zeros(ng.value + 1, dtype=np.int32)
         check(self.L.phx_world_get_pin_schedule(self.h, _ptr(order), n, _ptr(coff), len(coff), C.byref(nc), _ptr(goff), len(goff), C.byref(ng), C.byref(lg)))
@@ -1033,6 +1039,32 @@ class World:
     def links(self):
         """Every link as a link_dtype array, with the impulses the last step accumulated."""
         return self._get(self.L.phx_world_get_links, link_dtype, self.link_count())
+
+    def add_angles(self, angles):
+        """Append angles: an angle_dtype array, or rows (body1, body2, lower, upper[, hertz[, damping_ratio[, motor_speed[, max_torque]]]])
+        with both impulses 0.  lower == upper: a lock, with hertz > 0 a torsion spring; lower < upper: limits (wider than a full turn:
+        none); max_torque > 0: a motor.  Returns the new angles' indices."""
+        return self._add_units("phx_world_add_angles", angles, angle_dtype, ("lower", "upper", "hertz", "damping_ratio", "motor_speed", "max_torque"),
+                               required=2, anchors=False)
+
+    def remove_angles(self, angles):
+        """Remove the listed angles (each at most once); the others keep their order, so their indices shift."""
+        self._remove_units("phx_world_remove_angles", angles, "remove_angles")
+
+    def set_angle_limits(self, angles, limits):
+        """lower, upper = limits[k] of angle angles[k]; the schedule stays."""
+        self._edit("phx_world_set_angle_limits", angles, limits, 2, "set_angle_limits")
+
+    def set_angle_motors(self, angles, motors):
+        """motor_speed, max_torque = motors[k] of angle angles[k]; the schedule stays (a throttle, a brake)."""
+        self._edit("phx_world_set_angle_motors", angles, motors, 2, "set_angle_motors")
+
+    def angle_count(self):
+        return self._int32("phx_world_angle_count")
+
+    def angles(self):
+        """Every angle as an angle_dtype array, with the impulses the last step accumulated."""
+        return self._get(self.L.phx_world_get_angles, angle_dtype, self.angle_count())
 
     # ---- the per-body columns: collision filters, materials, body flags ----
     @staticmethod

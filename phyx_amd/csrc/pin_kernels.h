@@ -13,6 +13,10 @@
 // Links (include/phyx_amd.h LINKS; the definition: tests/link_spec.py) are the pass's other kind of unit: unit u < npins is pin u, otherwise
 // link u - npins.  A link's prestep (link_prestep) fills the same registers under other names (PinRegs' unions), its sweep differs in the
 // delta only (link_delta) and ends in the same pin_apply.
+//
+// Angles (include/phyx_amd.h ANGLES; the definition: tests/angle_spec.py) are the third kind: unit u >= npins + nlinks is angle
+// u - npins - nlinks.  An angle has no anchors and no axis: its prestep (angle_prestep) keeps its two rows, the motor M and the
+// lock / spring / limit L, in the registers a pin uses for its anchors, and its sweep (angle_sweep) edits the two angular velocities only.
 #pragma once
 
 #include "pins.h"
@@ -26,9 +30,11 @@ struct PinSlot { int pin; int a, b; int colour; };      // LDS groups: a, b loca
 struct PinGroup { int slot_begin, slot_end, body_begin, body_count; int first_dynamic, classes, pad0, pad1; };
 
 // what a lane keeps of its pin from the prestep on
-// (a link's names for the registers a pin calls otherwise: the axis n, gamma, 1/kinv, the scalar bias, the clamp's bounds, lambda)
+// (a link's names for the registers a pin calls otherwise: the axis n, gamma, 1/kinv, the scalar bias, the clamp's bounds, lambda;
+//  an angle's: row L as a link's with 1/(kinv + gamma) beside 1/kinv, row M's speed, its largest impulse and its accumulated impulse)
+enum : unsigned char { UNIT_PIN = 0, UNIT_LINK = 1, UNIT_ANGLE = 2, ANGLE_ROW_L = 4, ANGLE_ROW_M = 8 };      // (an angle: UNIT_ANGLE | its engaged rows)
 struct PinRegs {
-    float rax, ray, rbx, rby;
+    float rax, ray, rbx, rby;           // (an angle's inv_kg, speed, mmax, mlambda: the accessors below)
     union { float k11; float nx; };
     union { float k12; float ny; };
     union { float k22; float gamma; };
@@ -39,7 +45,19 @@ struct PinRegs {
     union { float px; float lambda; };  // the accumulated impulse
     union { float py; float hi; };
     bool active, write_a, write_b;
-    bool link, clamps;                  // a link; one whose impulse is clamped to [lo, hi] (a rope or a limit)
+    unsigned char kind;                 // UNIT_PIN, UNIT_LINK, or UNIT_ANGLE with ANGLE_ROW_L / ANGLE_ROW_M where those rows are engaged
+    bool clamps;                        // a link or an angle whose impulse is clamped to [lo, hi] (a rope or a limit)
+    __device__ float& inv_kg() { return rax; }
+    __device__ float& speed() { return ray; }
+    __device__ float& mmax() { return rbx; }
+    __device__ float& mlambda() { return rby; }
+    __device__ float inv_kg() const { return rax; }
+    __device__ float speed() const { return ray; }
+    __device__ float mmax() const { return rbx; }
+    __device__ float mlambda() const { return rby; }
+    __device__ bool angle() const { return (kind & UNIT_ANGLE) != 0; }
+    __device__ bool lrow() const { return (kind & ANGLE_ROW_L) != 0; }
+    __device__ bool mrow() const { return (kind & ANGLE_ROW_M) != 0; }
 };
 
 // the rotated anchors, the inverse masses and who is written; -> C = (posB + rb) - (posA + ra).  `P` is a phx_pin or a phx_link.
@@ -72,7 +90,7 @@ __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* _
     PinRegs r;
     float cx, cy;
     pin_anchors(p, mpos, frame, r, cx, cy);
-    r.link = false; r.clamps = false;
+    r.kind = UNIT_PIN; r.clamps = false;
     const float ms = r.ma + r.mb;
     r.k11 = (ms + (r.ia * r.ray) * r.ray) + (r.ib * r.rby) * r.rby;
     r.k12 = -((r.ia * r.rax) * r.ray) - (r.ib * r.rbx) * r.rby;
@@ -95,7 +113,7 @@ __device__ __forceinline__ PinRegs link_prestep(const phx_link& p, const float4*
     PinRegs r;
     float dx, dy;
     pin_anchors(p, mpos, frame, r, dx, dy);
-    r.link = true;
+    r.kind = UNIT_LINK;
     const float len = sqrtf(dx * dx + dy * dy);                 // (sqrtf: correctly rounded under the library's flags)
     r.nx = dx / len; r.ny = dy / len;
     const float cra = r.rax * r.ny - r.ray * r.nx, crb = r.rbx * r.ny - r.rby * r.nx;
@@ -124,6 +142,101 @@ __device__ __forceinline__ PinRegs link_prestep(const phx_link& p, const float4*
     r.inv_k = 1.0f / kinv;
     r.lambda = r.active ? link_clamp(p.impulse, r.lo, r.hi) : 0.f;
     return r;
+}
+
+// tests/angle_spec.py prestep, operation for operation.  theta: the double-precision atan2 rounded to float, k_integrate_position's rule
+// for cos / sin; here only, never in a sweep.
+__device__ __forceinline__ PinRegs angle_prestep(const phx_angle& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt)
+{
+    PinRegs r;
+    const float4 qa = mpos[p.body1], fa = frame[p.body1];
+    r.ma = qa.x; r.ia = qa.y;
+    float xbx = 1.f, xby = 0.f;
+    r.mb = 0.f; r.ib = 0.f;
+    if (p.body2 >= 0) {
+        const float4 qb = mpos[p.body2], fb = frame[p.body2];
+        r.mb = qb.x; r.ib = qb.y;
+        xbx = fb.x; xby = fb.y;
+    }
+    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
+    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+    r.nx = 0.f; r.ny = 0.f;                                     // (no axis: the trailing group's work record carries every word)
+    const float c = fa.x * xbx + fa.y * xby, s = fa.x * xby - fa.y * xbx;
+    const float theta = (float)atan2((double)(-s), (double)c);
+    const float mid = (p.lower + p.upper) * 0.5f, half = (p.upper - p.lower) * 0.5f;
+    float phi = theta - mid;
+    if (phi > 3.1415927f) phi = phi - 6.2831855f;
+    else if (phi < -3.1415927f) phi = phi + 6.2831855f;
+    float kinv = r.ia + r.ib;
+    const bool solvable = kinv > 0.f;
+    const float inf = __builtin_inff();
+    float cl;
+    r.clamps = p.lower < p.upper;
+    bool lrow = true;
+    r.lo = -inf; r.hi = inf;
+    if (!r.clamps) cl = phi;
+    else if (phi >= half) { cl = phi - half; r.hi = 0.f; }
+    else if (phi <= -half) { cl = phi + half; r.lo = 0.f; }
+    else { cl = 0.f; lrow = false; }                           // idle this step
+    r.inv_k = 1.0f / kinv;
+    if (p.hertz > 0.f) {
+        const float mass = 1.0f / kinv;
+        const float omega = 6.2831855f * p.hertz;
+        const float dmp = ((2.0f * mass) * p.damping_ratio) * omega;
+        const float k = (mass * omega) * omega;
+        r.gamma = 1.0f / (dt * (dmp + dt * k));
+        r.bias = ((cl * dt) * k) * r.gamma;
+        kinv = kinv + r.gamma;
+    } else {
+        r.gamma = 0.f;
+        r.bias = cl * beta;
+    }
+    r.inv_kg() = 1.0f / kinv;
+    r.speed() = p.motor_speed;
+    r.mmax() = p.max_torque * dt;
+    const bool mrow = solvable && p.max_torque > 0.f;
+    lrow = solvable && lrow;
+    r.kind = UNIT_ANGLE | (lrow ? ANGLE_ROW_L : 0) | (mrow ? ANGLE_ROW_M : 0);
+    r.active = lrow || mrow;
+    r.mlambda() = mrow ? link_clamp(p.motor_impulse, -r.mmax(), r.mmax()) : 0.f;
+    r.lambda = lrow ? link_clamp(p.impulse, r.lo, r.hi) : 0.f;
+    return r;
+}
+
+// an angle's apply: the two angular velocities only
+__device__ __forceinline__ void angle_apply(const PinRegs& r, float d, float4& va, float4& vb)
+{
+    va.z = va.z - r.ia * d;
+    vb.z = vb.z + r.ib * d;
+}
+
+// an angle's warm start: M's accumulated impulse, then L's, each where its row is on
+__device__ __forceinline__ void angle_warm(const PinRegs& r, float4& va, float4& vb)
+{
+    if (r.mrow()) angle_apply(r, r.mlambda(), va, vb);
+    if (r.lrow()) angle_apply(r, r.lambda, va, vb);
+}
+
+// one sweep of an angle: M, then L on the velocities M left; accumulates both
+__device__ __forceinline__ void angle_sweep(PinRegs& r, float4& va, float4& vb)
+{
+    if (r.mrow()) {
+        const float cdot = vb.z - va.z;
+        const float next = link_clamp(r.mlambda() + -(r.inv_k * (cdot - r.speed())), -r.mmax(), r.mmax());
+        const float d = next - r.mlambda();
+        r.mlambda() = next;
+        angle_apply(r, d, va, vb);
+    }
+    if (r.lrow()) {
+        const float cdot = vb.z - va.z;
+        float d = -(r.inv_kg() * ((cdot + r.bias) + r.gamma * r.lambda));
+        if (r.clamps) {
+            const float next = link_clamp(r.lambda + d, r.lo, r.hi);
+            d = next - r.lambda;
+            r.lambda = next;
+        } else r.lambda = r.lambda + d;
+        angle_apply(r, d, va, vb);
+    }
 }
 
 // The engine's angularVelocity is CLOCKWISE-positive: IntegratePosition rotates the frame by -w dt (ref: World.cpp:63) and the contact
@@ -172,12 +285,18 @@ __device__ __forceinline__ void link_delta(PinRegs& r, const float4& va, const f
 // 4 us of 30 on the world of DESIGN.md 5b, all pins: the launch is a chain of class steps, and each one pays for it).
 template <bool LINKS> __device__ __forceinline__ void unit_warm(const PinRegs& r, float& dx, float& dy)
 {
-    if (LINKS && r.link) { dx = r.lambda * r.nx; dy = r.lambda * r.ny; } else { dx = r.px; dy = r.py; }
+    if (LINKS && r.kind == UNIT_LINK) { dx = r.lambda * r.nx; dy = r.lambda * r.ny; } else { dx = r.px; dy = r.py; }
 }
 template <bool LINKS> __device__ __forceinline__ void unit_delta(PinRegs& r, const float4& va, const float4& vb, float& dx, float& dy)
 {
-    if (LINKS && r.link) link_delta(r, va, vb, dx, dy); else pin_delta(r, va, vb, dx, dy);
+    if (LINKS && r.kind == UNIT_LINK) link_delta(r, va, vb, dx, dy); else pin_delta(r, va, vb, dx, dy);
 }
+// The angles' kernel arguments: a pack that is empty in a world without angles, so that the instantiations without them keep the
+// signature, the kernarg layout and the code they had before there were angles; with angles it is (phx_angle* angles, int nlinks).
+struct NoAngles { static constexpr bool present = false; };
+struct AngleArgs { static constexpr bool present = true; phx_angle* angles; int nlinks; };
+__device__ __forceinline__ NoAngles angle_args() { return NoAngles{}; }
+__device__ __forceinline__ AngleArgs angle_args(phx_angle* angles, int nlinks) { return AngleArgs{angles, nlinks}; }
 
 // The LDS layout: one float4 per local body.  A lane's two bodies are anywhere in the table, so a class step is a gather / scatter of
 // 16-byte granules (ds_read_b128 / ds_write_b128).  A 16-byte read is served in four groups of 16 lanes over the 64 banks: a group
@@ -185,11 +304,13 @@ template <bool LINKS> __device__ __forceinline__ void unit_delta(PinRegs& r, con
 // granules apart and read two-way conflicted (8 LDS cycles instead of 4 per wave); the 16-byte store's cost is its register transfer
 // either way.  Both are small beside the dependent chain of a class step (read, ~20 dependent flops, write, barrier), which is what
 // the pass waits for.
-template <bool LINKS>
+template <bool LINKS, class... A>
 static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots,
                                                                  const PinGroup* __restrict__ groups, const int* __restrict__ group_bodies, float4* __restrict__ vel,
-                                                                 const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, int iterations)
+                                                                 const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, int iterations, A... angle_pack)
 {
+    constexpr bool ANGLES = sizeof...(A) > 0;
+    [[maybe_unused]] const auto ang = angle_args(angle_pack...);
     __shared__ float4 sv[PIN_BODIES];
     const PinGroup g = groups[blockIdx.x];
     const int* const bodies = group_bodies + g.body_begin;
@@ -203,7 +324,12 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     PinRegs r = {};
     if (mine) {
         s = slots[slot];
-        r = (!LINKS || s.pin < npins) ? pin_prestep(pins[s.pin], mpos, frame, beta) : link_prestep(links[s.pin - npins], mpos, frame, beta, dt);
+        if constexpr (ANGLES)
+            r = s.pin < npins ? pin_prestep(pins[s.pin], mpos, frame, beta)
+                : s.pin < npins + ang.nlinks ? link_prestep(links[s.pin - npins], mpos, frame, beta, dt)
+                : angle_prestep(ang.angles[s.pin - npins - ang.nlinks], mpos, frame, beta, dt);
+        else
+            r = (!LINKS || s.pin < npins) ? pin_prestep(pins[s.pin], mpos, frame, beta) : link_prestep(links[s.pin - npins], mpos, frame, beta, dt);
     }
     const bool work = mine && r.active;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -211,9 +337,12 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     for (int c = 0; c < g.classes; ++c) {                                   // warm start, class by class
         if (work && s.colour == c) {
             float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-            float dx, dy;
-            unit_warm<LINKS>(r, dx, dy);
-            pin_apply(r, dx, dy, va, vb);
+            if (ANGLES && r.angle()) angle_warm(r, va, vb);
+            else {
+                float dx, dy;
+                unit_warm<LINKS>(r, dx, dy);
+                pin_apply(r, dx, dy, va, vb);
+            }
             if (r.write_a) sv[s.a] = va;
             if (r.write_b) sv[s.b] = vb;
         }
@@ -223,9 +352,12 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
         for (int c = 0; c < g.classes; ++c) {
             if (work && s.colour == c) {
                 float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-                float dx, dy;
-                unit_delta<LINKS>(r, va, vb, dx, dy);
-                pin_apply(r, dx, dy, va, vb);
+                if (ANGLES && r.angle()) angle_sweep(r, va, vb);
+                else {
+                    float dx, dy;
+                    unit_delta<LINKS>(r, va, vb, dx, dy);
+                    pin_apply(r, dx, dy, va, vb);
+                }
                 if (r.write_a) sv[s.a] = va;
                 if (r.write_b) sv[s.b] = vb;
             }
@@ -233,57 +365,106 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
         }
     for (int i = g.first_dynamic + (int)threadIdx.x; i < g.body_count; i += PIN_LANES) vel[bodies[i]] = sv[i];
     if (mine) {
-        if (LINKS && r.link) links[s.pin - npins].impulse = r.lambda; else pins[s.pin].impulse = phx_vec2{r.px, r.py};
+        if constexpr (ANGLES) {
+            if (r.angle()) { phx_angle& a = ang.angles[s.pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
+            else if (r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda;
+            else pins[s.pin].impulse = phx_vec2{r.px, r.py};
+        } else {
+            if (LINKS && r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda; else pins[s.pin].impulse = phx_vec2{r.px, r.py};
+        }
     }
 }
 
 // ---- the trailing group, out of HBM ----
-struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };      // flags: 1 active, 2 write a, 4 write b, 8 link, 16 clamps
+struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };      // flags: 1 active, 2 write a, 4 write b, 8 link, 16 clamps, 32 angle, 64 row L, 128 row M
 
-// (k11 .. biasy hold a link's nx, ny, gamma, inv_k, bias, lo: PinRegs' unions; px, py = the unit's accumulated impulse, a link's in px)
-__device__ __forceinline__ PinRegs pin_regs(const PinWork& w, float px, float py)
+// (k11 .. biasy hold a link's nx, ny, gamma, inv_k, bias, lo: PinRegs' unions; px, py = the unit's accumulated impulse, a link's in px;
+//  an angle's two come from its record: impulse in px, motor_impulse in `rby`)
+template <bool ANGLES>
+__device__ __forceinline__ PinRegs pin_regs(const PinWork& w, float px, float py, float rby)
 {
     PinRegs r;
-    r.rax = w.rax; r.ray = w.ray; r.rbx = w.rbx; r.rby = w.rby; r.k11 = w.k11; r.k12 = w.k12; r.k22 = w.k22; r.inv_det = w.inv_det;
+    r.rax = w.rax; r.ray = w.ray; r.rbx = w.rbx; r.rby = rby; r.k11 = w.k11; r.k12 = w.k12; r.k22 = w.k22; r.inv_det = w.inv_det;
     r.biasx = w.biasx; r.biasy = w.biasy; r.ma = w.ma; r.ia = w.ia; r.mb = w.mb; r.ib = w.ib;
-    r.link = (w.flags & 8) != 0; r.clamps = (w.flags & 16) != 0;
-    r.px = px; r.py = r.link ? w.hi : py;
+    r.kind = (ANGLES && (w.flags & 32) != 0) ? (UNIT_ANGLE | ((w.flags & 64) ? ANGLE_ROW_L : 0) | ((w.flags & 128) ? ANGLE_ROW_M : 0)) : (w.flags & 8) != 0 ? UNIT_LINK : UNIT_PIN;
+    r.clamps = (w.flags & 16) != 0;
+    r.px = px; r.py = r.kind != UNIT_PIN ? w.hi : py;
     r.active = (w.flags & 1) != 0; r.write_a = (w.flags & 2) != 0; r.write_b = (w.flags & 4) != 0;
     return r;
 }
 
-// slots [begin, end): the prestep; an inactive pin's impulse becomes 0 here, a link's its warm start (clamped; 0 when inactive or idle)
-template <bool LINKS>
-static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
-                                                            const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, PinWork* __restrict__ work)
+// what the prestep leaves of a unit (`hi` and an angle's bits: the caller's)
+__device__ __forceinline__ PinWork pin_work(const PinRegs& r)
 {
+    PinWork w;
+    w.rax = r.rax; w.ray = r.ray; w.rbx = r.rbx; w.rby = r.rby; w.k11 = r.k11; w.k12 = r.k12; w.k22 = r.k22; w.inv_det = r.inv_det;
+    w.biasx = r.biasx; w.biasy = r.biasy; w.ma = r.ma; w.ia = r.ia; w.mb = r.mb; w.ib = r.ib;
+    w.flags = (r.active ? 1 : 0) | (r.write_a ? 2 : 0) | (r.write_b ? 4 : 0) | (r.kind == UNIT_LINK ? 8 : 0) | (r.clamps ? 16 : 0);
+    w.hi = 0.f;
+    return w;
+}
+
+// slots [begin, end): the prestep; an inactive pin's impulse becomes 0 here, a link's its warm start (clamped; 0 when inactive or idle),
+// an angle's two likewise
+template <bool LINKS, class... A>
+static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
+                                                            const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, PinWork* __restrict__ work, A... angle_pack)
+{
+    constexpr bool ANGLES = sizeof...(A) > 0;
+    [[maybe_unused]] const auto ang = angle_args(angle_pack...);
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const int pin = slots[k].pin;
-        const PinRegs r = (!LINKS || pin < npins) ? pin_prestep(pins[pin], mpos, frame, beta) : link_prestep(links[pin - npins], mpos, frame, beta, dt);
-        PinWork w;
-        w.rax = r.rax; w.ray = r.ray; w.rbx = r.rbx; w.rby = r.rby; w.k11 = r.k11; w.k12 = r.k12; w.k22 = r.k22; w.inv_det = r.inv_det;
-        w.biasx = r.biasx; w.biasy = r.biasy; w.ma = r.ma; w.ia = r.ia; w.mb = r.mb; w.ib = r.ib;
-        w.flags = (r.active ? 1 : 0) | (r.write_a ? 2 : 0) | (r.write_b ? 4 : 0) | (r.link ? 8 : 0) | (r.clamps ? 16 : 0);
-        w.hi = (LINKS && r.link) ? r.hi : 0.f;
-        work[k - begin] = w;
-        if (LINKS && r.link) links[pin - npins].impulse = r.lambda;
-        else if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
+        if constexpr (ANGLES) {
+            const PinRegs r = pin < npins ? pin_prestep(pins[pin], mpos, frame, beta)
+                              : pin < npins + ang.nlinks ? link_prestep(links[pin - npins], mpos, frame, beta, dt)
+                              : angle_prestep(ang.angles[pin - npins - ang.nlinks], mpos, frame, beta, dt);
+            const bool link = r.kind == UNIT_LINK, angle = r.angle();
+            PinWork w = pin_work(r);
+            if (angle) w.flags |= 32 | (r.lrow() ? 64 : 0) | (r.mrow() ? 128 : 0);
+            w.hi = (link || angle) ? r.hi : 0.f;
+            work[k - begin] = w;
+            if (angle) { phx_angle& a = ang.angles[pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
+            else if (link) links[pin - npins].impulse = r.lambda;
+            else if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
+        } else {
+            const PinRegs r = (!LINKS || pin < npins) ? pin_prestep(pins[pin], mpos, frame, beta) : link_prestep(links[pin - npins], mpos, frame, beta, dt);
+            const bool link = r.kind == UNIT_LINK;
+            PinWork w = pin_work(r);
+            w.hi = (LINKS && link) ? r.hi : 0.f;
+            work[k - begin] = w;
+            if (LINKS && link) links[pin - npins].impulse = r.lambda;
+            else if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
+        }
     }
 }
 
 // one class, slots [begin, end) of a group whose work array starts at slot `base`: the warm start (sweep == 0) or one sweep
-template <bool LINKS>
+template <bool LINKS, class... A>
 static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
-                                                          int base, const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep)
+                                                          int base, const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep, A... angle_pack)
 {
+    constexpr bool ANGLES = sizeof...(A) > 0;
+    [[maybe_unused]] const auto ang = angle_args(angle_pack...);
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const PinSlot s = slots[k];
         const PinWork w = work[k - base];
         if (!(w.flags & 1)) continue;
         const bool link = LINKS && (w.flags & 8) != 0;
+        if constexpr (ANGLES) {
+            if (w.flags & 32) {                                               // an angle: both impulses from its record, w only
+                phx_angle& a = ang.angles[s.pin - npins - ang.nlinks];
+                PinRegs r = pin_regs<true>(w, a.impulse, 0.f, a.motor_impulse);
+                float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (sweep) angle_sweep(r, va, vb); else angle_warm(r, va, vb);
+                if (r.write_a) vel[s.a] = va;
+                if (r.write_b) vel[s.b] = vb;
+                if (sweep) { a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
+                continue;
+            }
+        }
         float px, py = 0.f;
         if (link) px = links[s.pin - npins].impulse; else { const phx_vec2 p = pins[s.pin].impulse; px = p.x; py = p.y; }
-        PinRegs r = pin_regs(w, px, py);
+        PinRegs r = pin_regs<false>(w, px, py, w.rby);
         float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
         float dx, dy;
         if (sweep) unit_delta<LINKS>(r, va, vb, dx, dy); else unit_warm<LINKS>(r, dx, dy);
@@ -295,7 +476,7 @@ static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ 
 }
 
 // ---- what the host asks between steps ----
-// (`P`: phx_pin or phx_link, which begin alike: body1, body2, anchor1, anchor2)
+// (`P`: phx_pin, phx_link or phx_angle, which begin alike: body1, body2; only those are read)
 // per pin: are its bodies static (bit 0: body1, bit 1: body2)?  O(pins) bytes for the schedule build
 template <class P>
 static __global__ void __launch_bounds__(256) k_pin_statics(const P* __restrict__ pins, int n, const float4* __restrict__ mpos, unsigned* __restrict__ out)

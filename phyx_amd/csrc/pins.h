@@ -8,6 +8,9 @@
 // Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: the units are the pins followed by the links, one schedule and
 // one pass for both.  UnitList is the one copy of the list machinery (host and device copy, upload, fetch, remap, field edits) for either
 // record, and UnitKind states what the World's one copy of the calls (world.hip, "units") needs to know of a record.
+//
+// Angles (include/phyx_amd.h ANGLES) are the third kind, behind the links: a record without anchors, so nothing here may ask for any
+// but through AnchorFields, which an angle never instantiates.
 #pragma once
 
 #include <type_traits>
@@ -41,6 +44,15 @@ template <> struct UnitKind<phx_link> {
     static int check_lengths(const char* what, int k, float lo, float hi, float hertz);      // (also phx_world_set_link_lengths' rule)
 };
 
+template <> struct UnitKind<phx_angle> {
+    static constexpr const char* noun = "angle";
+    static constexpr const char* plural = "angles";
+    static constexpr const char* add = "phx_world_add_angles", *remove = "phx_world_remove_angles", *get = "phx_world_get_angles";      // (no anchors to set)
+    static int check(const char* what, int k, const phx_angle& p);
+    static int check_limits(const char* what, int k, float lower, float upper, float hertz);      // (also phx_world_set_angle_limits' rule)
+    static int check_motor(const char* what, int k, float speed, float max_torque);               // (also phx_world_set_angle_motors')
+};
+
 // the fields an edit between steps writes, `width` floats per record: on the host list and, by k_unit_fields, on the device copy
 struct AnchorFields {
     static constexpr int width = 4;
@@ -51,7 +63,16 @@ struct LengthFields {
     static __host__ __device__ void write(phx_link& p, const float* v) { p.min_length = v[0]; p.max_length = v[1]; }
 };
 
-// a list of records `P` (phx_pin, phx_link: body1, body2, anchor1, anchor2 first; `impulse` the device's once uploaded)
+struct LimitFields {
+    static constexpr int width = 2;
+    static __host__ __device__ void write(phx_angle& p, const float* v) { p.lower = v[0]; p.upper = v[1]; }
+};
+struct MotorFields {
+    static constexpr int width = 2;
+    static __host__ __device__ void write(phx_angle& p, const float* v) { p.motor_speed = v[0]; p.max_torque = v[1]; }
+};
+
+// a list of records `P` (phx_pin, phx_link, phx_angle: body1, body2 first; the impulses the device's once uploaded)
 template <class P> class UnitList {
 public:
     int count() const { return (int)host_.size(); }
@@ -79,23 +100,28 @@ private:
 class PinSet {
 public:
     int configure_from_env();            // PHX_PIN_GROUP_PINS
-    template <class P> UnitList<P>& list() { if constexpr (std::is_same_v<P, phx_pin>) return pins_; else return links_; }
+    template <class P> UnitList<P>& list()
+    {
+        if constexpr (std::is_same_v<P, phx_pin>) return pins_;
+        else if constexpr (std::is_same_v<P, phx_link>) return links_;
+        else return angles_;
+    }
     template <class P> const UnitList<P>& list() const { return const_cast<PinSet*>(this)->list<P>(); }
-    int units() const { return pins_.count() + links_.count(); }            // the pass's units: the pins, then the links
+    int units() const { return pins_.count() + links_.count() + angles_.count(); }      // the pass's units: the pins, then the links, then the angles
     int group_pins() const { return group_pins_; }
     long long builds() const { return builds_; }
     int iterations = 8;
 
     // the calls (world.hip, "units") work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
     void units_changed() { sched_dirty_ = true; }
-    void clear() { pins_.clear(); links_.clear(); sched_dirty_ = true; }
+    void clear() { pins_.clear(); links_.clear(); angles_.clear(); sched_dirty_ = true; }
     void statics_changed() { if (units()) sched_dirty_ = true; }             // ... and a change of the static set make the schedule stale
     // a removal of bodies compacted them through `d_remap` (old index -> new or -1): the units of removed bodies go, the rest are renumbered
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream);
     // snapshots: the device copies (list<P>().device()), current
-    int upload(hipStream_t stream) { PHX_TRY(pins_.upload(stream)); return links_.upload(stream); }
+    int upload(hipStream_t stream) { PHX_TRY(pins_.upload(stream)); PHX_TRY(links_.upload(stream)); return angles_.upload(stream); }
     // load: the lists := device arrays (queued; the host lists follow at once)
-    int adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, hipStream_t stream);
+    int adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count, hipStream_t stream);
 
     // the schedule, built unless current
     int prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream);
@@ -106,6 +132,7 @@ public:
 private:
     UnitList<phx_pin> pins_;
     UnitList<phx_link> links_;
+    UnitList<phx_angle> angles_;
     bool sched_dirty_ = true;
     int group_pins_ = 0;
     long long builds_ = 0;

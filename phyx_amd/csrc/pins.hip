@@ -7,7 +7,8 @@
 // class for the warm start and per class and sweep.
 // Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: UnitList<P> is the list machinery for either record and
 // UnitKind<P> what the World's calls check of one, the schedule is built over the pins followed by the links, and a world that has
-// links launches the kernels' LINKS instantiations.
+// links launches the kernels' LINKS instantiations.  Angles (ANGLES) are the third, behind the links; a world that has angles
+// launches the instantiations with both.
 #include "pins.h"
 #include "pin_kernels.h"
 
@@ -151,10 +152,13 @@ template <class P> int UnitList<P>::statics(const float4* mpos, unsigned* d_bits
 
 template class UnitList<phx_pin>;
 template class UnitList<phx_link>;
+template class UnitList<phx_angle>;
 
 template int UnitList<phx_pin>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 template int UnitList<phx_link>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 template int UnitList<phx_link>::set_fields<LengthFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_angle>::set_fields<LimitFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_angle>::set_fields<MotorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 
 // ---- entry k of an add beyond the body rules (the order of the checks is the calls' contract: the first failure wins) ----
 static int check_finite(const char* what, const char* noun, int k, std::initializer_list<float> values)
@@ -189,31 +193,57 @@ int UnitKind<phx_link>::check_lengths(const char* what, int k, float lo, float h
     return PHX_OK;
 }
 
+int UnitKind<phx_angle>::check(const char* what, int k, const phx_angle& p)
+{
+    PHX_TRY(check_finite(what, noun, k, {p.lower, p.upper, p.hertz, p.damping_ratio, p.motor_speed, p.max_torque, p.impulse, p.motor_impulse}));
+    if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: angle %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
+    PHX_TRY(check_limits(what, k, p.lower, p.upper, p.hertz));
+    return check_motor(what, k, p.motor_speed, p.max_torque);
+}
+
+int UnitKind<phx_angle>::check_limits(const char* what, int k, float lower, float upper, float hertz)
+{
+    if (!std::isfinite(lower) || !std::isfinite(upper)) { set_error("%s: angle %d: a limit is not finite", what, k); return PHX_ERR_INVALID; }
+    if (!(lower <= upper)) { set_error("%s: angle %d: limits [%g, %g] are not lower <= upper", what, k, (double)lower, (double)upper); return PHX_ERR_INVALID; }
+    if (hertz > 0.f && lower != upper) { set_error("%s: angle %d: a spring (hertz %g) needs lower == upper", what, k, (double)hertz); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int UnitKind<phx_angle>::check_motor(const char* what, int k, float speed, float max_torque)
+{
+    if (!std::isfinite(speed) || !std::isfinite(max_torque)) { set_error("%s: angle %d: a motor value is not finite", what, k); return PHX_ERR_INVALID; }
+    if (max_torque < 0.f) { set_error("%s: angle %d: negative max_torque %g", what, k, (double)max_torque); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
 int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
 {
     PHX_TRY(pins_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
-    return links_.bodies_removed(d_remap, rb, stream, &sched_dirty_);
+    PHX_TRY(links_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
+    return angles_.bodies_removed(d_remap, rb, stream, &sched_dirty_);
 }
 
-int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, hipStream_t stream)
+int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count, hipStream_t stream)
 {
     sched_dirty_ = true;
     PHX_TRY(pins_.adopt_device(d_pins, pin_count, stream));
-    return links_.adopt_device(d_links, link_count, stream);
+    PHX_TRY(links_.adopt_device(d_links, link_count, stream));
+    return angles_.adopt_device(d_angles, angle_count, stream);
 }
 
 int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
 {
-    const int n = units(), np = pins_.count();
+    const int n = units(), np = pins_.count(), npl = np + links_.count();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
     if (!sched_dirty_) return PHX_OK;
     PHX_TRY(d_bits_.reserve((size_t)n));
     PHX_TRY(pins_.statics(mpos, d_bits_.p, stream));
     PHX_TRY(links_.statics(mpos, d_bits_.p + np, stream));
-    // a unit's bodies: pin u, or link u - np
-    auto body1 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body1 : links_.host()[(size_t)(u - np)].body1; };
-    auto body2 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body2 : links_.host()[(size_t)(u - np)].body2; };
+    PHX_TRY(angles_.statics(mpos, d_bits_.p + npl, stream));
+    // a unit's bodies: pin u, link u - np, or angle u - npl
+    auto body1 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body1 : u < npl ? links_.host()[(size_t)(u - np)].body1 : angles_.host()[(size_t)(u - npl)].body1; };
+    auto body2 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body2 : u < npl ? links_.host()[(size_t)(u - np)].body2 : angles_.host()[(size_t)(u - npl)].body2; };
     std::vector<unsigned> bits((size_t)n);
     PHX_TRY(rb.add(bits.data(), d_bits_.p, (size_t)n * sizeof(unsigned), stream));
     PHX_TRY(rb.wait(stream));
@@ -279,26 +309,44 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
     PHX_TRY(prepare(bodies.s.mpos, nb, rb, stream));
     phx_pin* const d_pins = pins_.device();
     phx_link* const d_links = links_.device();
-    const int np = pins_.count();
+    phx_angle* const d_angles = angles_.device();
+    const int np = pins_.count(), nl = links_.count();
     const float beta = 0.2f / dt;
     const PinSlot* slots = reinterpret_cast<const PinSlot*>(d_tables_.p);
-    // a world without links runs the pins' own instantiation of each kernel: what it ran before there were links
-    const bool with_links = links_.count() > 0;
+    // a world without links runs the pins' own instantiation of each kernel: what it ran before there were links; one without angles
+    // what it ran before there were angles; one with angles the instantiation that knows all three kinds
+    // (whose kernels take the angles' two arguments behind the others': pin_kernels.h AngleArgs)
+    const bool with_angles = angles_.count() > 0, with_links = nl > 0;
     auto pick = [with_links](auto with, auto without) { return with_links ? with : without; };
-    if (sched_.lds_groups)
-        hipLaunchKernelGGL(pick(k_solve_pins<true>, k_solve_pins<false>), dim3(sched_.lds_groups), dim3(PIN_LANES), 0, stream, d_pins, d_links, np, slots,
-                           reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_), reinterpret_cast<const int*>(d_tables_.p + off_bodies_), bodies.s.vel,
-                           (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, dt, iterations);
+    const dim3 lds_grid(sched_.lds_groups), lds_block(PIN_LANES);
+    const PinGroup* const groups = reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_);
+    const int* const group_bodies = reinterpret_cast<const int*>(d_tables_.p + off_bodies_);
+    const float4* const mpos = (const float4*)bodies.s.mpos, *const frame = (const float4*)bodies.frame;
+    if (sched_.lds_groups) {
+        if (with_angles)
+            hipLaunchKernelGGL((k_solve_pins<true, phx_angle*, int>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
+                               mpos, frame, beta, dt, iterations, d_angles, nl);
+        else
+            hipLaunchKernelGGL(pick(k_solve_pins<true>, k_solve_pins<false>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
+                               mpos, frame, beta, dt, iterations);
+    }
     if (hbm_classes_.size() > 1) {
         const int begin = hbm_classes_.front(), end = hbm_classes_.back();
         PinWork* work = reinterpret_cast<PinWork*>(d_work_.p);
-        hipLaunchKernelGGL(pick(k_pin_prestep<true>, k_pin_prestep<false>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end,
-                           (const float4*)bodies.s.mpos, (const float4*)bodies.frame, beta, dt, work);
+        if (with_angles)
+            hipLaunchKernelGGL((k_pin_prestep<true, phx_angle*, int>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame, beta, dt, work, d_angles, nl);
+        else
+            hipLaunchKernelGGL(pick(k_pin_prestep<true>, k_pin_prestep<false>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame, beta, dt, work);
         for (int sweep = 0; sweep <= iterations; ++sweep)
             for (size_t c = 0; c + 1 < hbm_classes_.size(); ++c) {
                 const int b = hbm_classes_[c], e = hbm_classes_[c + 1];
-                if (e > b) hipLaunchKernelGGL(pick(k_pin_class<true>, k_pin_class<false>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
-                                              (const PinWork*)work, bodies.s.vel, sweep);
+                if (e <= b) continue;
+                if (with_angles)
+                    hipLaunchKernelGGL((k_pin_class<true, phx_angle*, int>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
+                                       (const PinWork*)work, bodies.s.vel, sweep, d_angles, nl);
+                else
+                    hipLaunchKernelGGL(pick(k_pin_class<true>, k_pin_class<false>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
+                                       (const PinWork*)work, bodies.s.vel, sweep);
             }
     }
     PHX_HIP(hipGetLastError());
