@@ -1062,6 +1062,27 @@ int phx_memcpy_h2d_on(int device, void* dst, const void* src, size_t bytes, void
 int phx_memcpy_d2d_on(int device, void* dst, const void* src, size_t bytes, void* stream);
 /* diagnostics: with PHX_WAIT_CLOCK=1 in the environment, the time this process has spent waiting for device->host readbacks */
 int phx_debug_wait_clock(long long* ns, long long* calls);
+/* test entry points of the two device primitives everything else stands on (exclusive scan, radix sort of pairs).  Host arrays go in and
+ * come out; each call allocates, copies and synchronises.
+ * phx_debug_scan: `nscans` exclusive prefix sums (modulo 2^32) back to back on one stream and one scan scratch.  Scan k covers the next
+ *   counts[k] words of `words`; its prefix sums land at the same place of `out`, its sum in totals[k].
+ *   loader          0: scanned in place;  1: the words are computed by a loader (read from an array of their own);  2: by a loader that
+ *                   also offers 16-byte loads and declines them on every other 4-word base
+ *   misalign_words  0 .. 3: how far each scan's device range starts behind a 16-byte boundary
+ *   initial_epoch   != 0: the scratch is allocated for the longest scan and its call counter set to this before the first scan
+ *                   (< 2^30; the counter starts over when it nears 2^30)
+ *   PHX_ERR_STATE when a scan wrote a device word outside its range.
+ * phx_debug_radix_sort: one stable sort of n (key, value) pairs; every key must be below 2^bits (bits 0 .. 32).  *which = the buffer
+ *   of the ping-pong pair the result ended in (passes & 1).
+ * phx_debug_primitive_plan (host only, needs no device): what the two dispatchers choose — the sort's digit width and pass count for
+ *   `bits`; for a scan of scan_count words whether it takes the one-workgroup kernel (*scan_single; 0 for an empty scan, which launches
+ *   nothing) and its number of 4096-word tiles. */
+int phx_debug_scan(int device, const uint32_t* words, const int32_t* counts, int32_t nscans, int32_t loader, int32_t misalign_words,
+                   uint32_t initial_epoch, uint32_t* out, uint32_t* totals);
+int phx_debug_radix_sort(int device, const uint32_t* keys, const uint32_t* vals, int32_t n, int32_t bits, uint32_t* keys_out,
+                         uint32_t* vals_out, int32_t* which);
+int phx_debug_primitive_plan(int32_t bits, int32_t scan_count, int32_t* digit_bits, int32_t* passes, int32_t* scan_single,
+                             int32_t* scan_tiles);
 
 #ifdef __cplusplus
 }

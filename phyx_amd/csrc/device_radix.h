@@ -96,9 +96,13 @@ static __global__ void __launch_bounds__(RS_THREADS) k_radix_scatter(const unsig
 }
 
 
-// Sorts n pairs by the low `bits` bits of the key, ping-ponging between (k0,v0) and (k1,v1); *result_buffer = 0 or 1 tells
-// where the sorted sequence ended up.  Digits are 11 bits wide when that needs fewer passes than 8-bit digits (a stable LSD
-// sort's result does not depend on the digit split), 8 bits otherwise.
+// Sorts n pairs by key, stably, ping-ponging between (k0,v0) and (k1,v1); *result_buffer = 0 or 1 tells where the sorted
+// sequence ended up.  PRECONDITION: every key is below 2^bits.  `bits` only chooses the passes, and a pass covers a whole digit:
+// ceil(bits / width) passes sort on passes * width bits (12 bits: two 8-bit passes, so 16 bits), not on the low `bits` bits — a key
+// with bits set at or above `bits` is ordered by them where a pass reaches them and ignored where none does.  Digits are 11 bits
+// wide when that needs fewer passes than 8-bit digits (a stable LSD sort's result does not depend on the digit split), 8 bits
+// otherwise.  *result_buffer = passes & 1 whatever n is (an empty sort launches nothing), so a caller can settle its buffers'
+// roles from `bits` alone.
 // hist scratch: radix_hist_words(n) words; scan scratch: ceil(that / SCAN_TILE) words.
 static inline size_t radix_hist_words(int n) { return (size_t)RS_WIDE_BINS * (size_t)std::max(1, div_up(n, RS_TILE)); }
 
@@ -131,7 +135,7 @@ static inline int device_radix_sort_pairs(unsigned* k0, unsigned* v0, unsigned* 
             src ^= 1;
         }
     PHX_HIP(hipGetLastError());
-    *result_buffer = src;
+    *result_buffer = n > 0 ? src : (passes & 1);      // (an empty sort launched nothing: the roles change all the same)
     return PHX_OK;
 }
 

@@ -1,5 +1,6 @@
 """Contact reports on the device (include/phyx_amd.h, CONTACTS) held byte for byte to tests/contact_spec.py: contacts of all bodies and of
-random listings on four scenes x four island modes x both paths after every step; touch events across steps and across removals, spawns,
+random listings on four scenes x four island modes x both paths after every step, and at the body counts where the index's and the events'
+radix sorts change their digit split; touch events across steps and across removals, spawns,
 set_state and refused calls; markers; no effect on the world; the index's caching; edges; the cfg 2 world; rejections; examples/contacts.c."""
 import ctypes as C
 import os
@@ -82,6 +83,50 @@ def test_exact_on_scenes(built_lib, scene, mode, path):
         assert begin.tobytes() == sb.tobytes() and end.tobytes() == se.tobytes(), "events step %d" % s
         prev = t
     assert len(prev) > 0
+
+
+def _lonely_block_then(scene, n):
+    """`scene` behind a block of isolated bodies that touch nothing, n bodies in all: the bodies that collide carry the highest indices."""
+    lonely = n - len(scene["px"])
+    assert lonely > 0
+    i = np.arange(lonely)
+    block = {"px": 1000.0 + 30.0 * (i % 64), "py": 500.0 + 30.0 * (i // 64), "angle": np.zeros(lonely), "sx": np.full(lonely, 5.0),
+             "sy": np.full(lonely, 5.0), "static": np.zeros(lonely, dtype=bool)}
+    return {k: np.concatenate([block[k], scene[k]]).astype(scene[k].dtype) for k in block}
+
+
+@pytest.mark.parametrize("n", (255, 256, 257, 2047, 2048, 2049))
+def test_body_counts_at_the_sort_key_splits(built_lib, monkeypatch, n):
+    """The index sorts its entries, and the events their pairs, by body index with a radix sort whose digit split follows the key width (device_radix.h):
+    key_bits(n - 1) and key_bits(n).  These body counts straddle 8 | 9 bits (one 8-bit pass | one 11-bit pass) and 11 | 12 bits (one 11-bit pass |
+    two 8-bit passes, after which the result lies in the other buffer and the buffers' roles swap the other way)."""
+    monkeypatch.setenv("PHX_CONTACT_PATH", "index")
+    rng = np.random.default_rng(n)
+    w = _world(_lonely_block_then(scenes.stack(3, 6), n))
+    assert w.counts()[0] == n
+    every = np.arange(n, dtype=np.int32)
+    prev = np.zeros((0, 2), dtype=np.int32)
+    for s in range(10):
+        w.Update(DT, CFG)
+        st = w.state()
+        some = rng.integers(n - 25, n, size=40).astype(np.int32)
+        for skip in (False, True):
+            _check_contacts(w, every, skip, "n = %d step %d all" % (n, s), st)
+            _check_contacts(w, some, skip, "n = %d step %d some" % (n, s), st)
+        t = spec.touching(st[1])
+        begin, end = _events(w)
+        sb, se = spec.diff(t, prev)
+        assert begin.tobytes() == sb.tobytes() and end.tobytes() == se.tobytes(), "events n = %d step %d" % (n, s)
+        prev = t
+    m = w.manifolds
+    assert len(prev) > 0 and len(m) > 0
+    # only the scene at the end collides, and its last bodies do: the keys' upper digit has more than one non-empty bin wherever it can
+    assert min(int(m["body1"].min()), int(m["body2"].min())) >= n - 19
+    top = max(int(m["body1"].max()), int(m["body2"].max()))
+    assert top == n - 1
+    for edge in (256, 2048):
+        if n > edge:
+            assert top >= edge
 
 
 def test_events_every_k_steps_and_the_first_call(built_lib):
