@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge crank clean
+.PHONY: build test test-gpu bench smoke example place bridge crank piston clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -28,6 +28,9 @@ bridge: build               ## links: a pinned deck on rod hangers, a crate on a
 crank: build                ## angles: a door with stops, a wheel on a motor, two boxes welded by a pin plus a lock (phx_world_add_angles)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/crank.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/crank
 
+piston: build               ## sliders: a crank-slider, an elevator between its stops, a box on a spring slider (phx_world_add_sliders)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/piston.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/piston
+
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston
 	rm -rf oracle/_ref

@@ -950,6 +950,64 @@ int  phx_world_set_angle_motors(phx_world* w, const int32_t* angles, const float
 int  phx_world_get_angles(phx_world* w, phx_angle* out, int32_t cap);
 int  phx_world_angle_count(phx_world* w, int32_t* count);
 
+/* SLIDERS — hold a point of body1 (the carriage) ON A LINE of body2 (the rail; body2 = -1: the world): a piston, an elevator, a sliding
+ * door, with an angle lock a prismatic joint, without one a wheel's suspension.  tests/slider_spec.py is the definition (scalar float32,
+ * every operation rounded on its own, no fused multiply-add, IEEE division, correctly rounded sqrt) and the device matches it byte for
+ * byte.  Sliders are the pin pass's fourth kind of unit, behind the angles: unit u >= pin_count + link_count + angle_count is slider
+ * u - pin_count - link_count - angle_count; one schedule, one launch, one Gauss-Seidel sweep.  Wherever PINS, LINKS and ANGLES say "pin"
+ * or "unit" of the schedule the sliders count too: phx_world_get_pin_schedule needs order_cap >= pin_count + link_count + angle_count +
+ * slider_count, add_sliders / remove_sliders rebuild the schedule.
+ *   - The geometry, in the prestep.  ra, rb: the rotated anchors, as a pin's.  e = (posA + ra) - (posB + rb) (the world: - anchor2).
+ *     a = the axis rotated by body2's frame as an anchor is (the world: the axis itself), len = sqrtf(a.x a.x + a.y a.y), n = a / len,
+ *     t = (-n.y, n.x).  s = n . e is the carriage's coordinate along the rail, t . e its distance off it.
+ *   - Both rows act at the carriage's anchor point on both bodies: A's arm is ra, B's is rb' = rb + e (which carries the wB term of an
+ *     axis that turns with the rail).  With w x r = (w r.y, -w r.x) (angularVelocity is clockwise-positive, PINS) and
+ *     r x u = r.x u.y - r.y u.x, for u in {t, n}:
+ *         cdot_u = u . ((vA + wA x ra) - (vB + wB x rb'))
+ *         kinv_u = ((mA + mB) + (iA (ra x u)) (ra x u)) + (iB (rb' x u)) (rb' x u)
+ *         apply P = lambda u:  vA += mA P,  wA -= iA (ra x P),  vB -= mB P,  wB += iB (rb' x P)       (a static body is not written)
+ *     A carriage that moves along +n gains s.
+ *   - !(kinv_t > 0): the slider is INACTIVE this step: its three impulses := 0, nothing else.  !(kinv_n > 0) with kinv_t > 0: rows L and
+ *     M are off, axis_impulse := 0, motor_impulse := 0, and P runs.  Nothing divides by |e|: e = 0 is an ordinary case.
+ *   - The rows:
+ *         P  perpendicular: C = t . e, impulse unbounded, bias = C (0.2f / dt); on whenever the slider is active
+ *         L  along the axis, on s, ANGLES' row L word for word: lower == upper, hertz == 0 a lock (C = s - lower); lower == upper,
+ *            hertz > 0 a spring towards s = lower (the links' soft constraint with mass = 1 / kinv_n); lower < upper limits:
+ *            s >= upper: C = s - upper, impulse <= 0; s <= lower: C = s - lower, impulse >= 0; otherwise IDLE this step:
+ *            axis_impulse := 0.  Decided at the prestep, not speculative, as a rope's limit.
+ *         M  the motor, on where max_force > 0: it drives cdot_n to motor_speed, its accumulated motor_impulse clamped to
+ *            +- max_force dt.  Off: motor_impulse := 0.
+ *   - warm start: motor_impulse and axis_impulse clamped to their ranges, then M, L, P applied, each where its row is on.  n sweeps of
+ *     M, then L, then P, each on the velocities the row before left: the hard row has the last word.
+ *         M: d = -((1 / kinv_n) (cdot_n - motor_speed)), new = clamp(motor_impulse + d), apply new - motor_impulse along n
+ *         L: d = -((1 / (kinv_n + gamma)) ((cdot_n + bias) + gamma axis_impulse)); lock, spring: axis_impulse += d; limits: clamped
+ *         P: d = -((1 / kinv_t) (cdot_t + bias_t)), impulse += d, apply d along t     (clamp: x < lo ? lo : x > hi ? hi : x: a NaN passes)
+ *   - The calls follow the pins', links' and angles' rules word for word.  Checked at add: the pins' body rules, every float finite,
+ *     axis.x^2 + axis.y^2 > 2^-20, lower <= upper, hertz >= 0, damping_ratio >= 0, max_force >= 0, hertz > 0 only with lower == upper,
+ *     reserved == 0.  set_slider_limits is checked against the slider's stored hertz, set_slider_motors wants finite values and
+ *     max_force >= 0; the three setters keep the schedule.
+ *   - The other calls, as for angles: remove_bodies / remove_outside drop the sliders of removed bodies and remap the rest; set_state
+ *     drops every slider; save / load carry the sliders with their three impulses in HBM; phx_snapshot_export and
+ *     phx_snapshot_blob_bytes of a snapshot that holds sliders return PHX_ERR_STATE; set_shard (count > 1), set_comm, reslab and
+ *     add_sliders on a sharded world return PHX_ERR_STATE.  A world without sliders allocates and launches exactly what it did without
+ *     them. */
+typedef struct { int32_t body1, body2;            /* body1: the carriage; body2: the rail, -1 = the world */
+                 phx_vec2 anchor1, anchor2;       /* as a pin's; with body2 = -1 anchor2 is a world point */
+                 phx_vec2 axis;                   /* the rail's direction in body2's frame (the world: world coordinates); need not be unit length */
+                 float lower, upper;              /* on the translation s */
+                 float hertz, damping_ratio;      /* > 0 only with lower == upper: a spring towards s = lower */
+                 float motor_speed, max_force;    /* max_force > 0: the motor row is on */
+                 float impulse, axis_impulse, motor_impulse;   /* accumulated: rows P, L, M; the warm start */
+                 uint32_t reserved;               /* 0 */
+} phx_slider;                                     /* 72 B */
+int  phx_world_add_sliders(phx_world* w, const phx_slider* sliders, int32_t count, int32_t* first);   /* *first (may be NULL) = index of the first new slider */
+int  phx_world_remove_sliders(phx_world* w, const int32_t* sliders, int32_t count);
+int  phx_world_set_slider_anchors(phx_world* w, const int32_t* sliders, const float* anchors /* 4 per slider: anchor1.x, .y, anchor2.x, .y */, int32_t count);
+int  phx_world_set_slider_limits(phx_world* w, const int32_t* sliders, const float* limits /* 2 per slider: lower, upper */, int32_t count);
+int  phx_world_set_slider_motors(phx_world* w, const int32_t* sliders, const float* motors /* 2 per slider: motor_speed, max_force */, int32_t count);
+int  phx_world_get_sliders(phx_world* w, phx_slider* out, int32_t cap);
+int  phx_world_slider_count(phx_world* w, int32_t* count);
+
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);
 /* handles owned by the world (for stage-level queries after an update) */

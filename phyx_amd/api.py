@@ -57,6 +57,10 @@ assert link_dtype.itemsize == 48
 angle_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("lower", "<f4"), ("upper", "<f4"), ("hertz", "<f4"), ("damping_ratio", "<f4"),
                         ("motor_speed", "<f4"), ("max_torque", "<f4"), ("impulse", "<f4"), ("motor_impulse", "<f4")])      # phx_angle
 assert angle_dtype.itemsize == 40
+slider_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("axis", "<f4", (2,)), ("lower", "<f4"), ("upper", "<f4"),
+                         ("hertz", "<f4"), ("damping_ratio", "<f4"), ("motor_speed", "<f4"), ("max_force", "<f4"), ("impulse", "<f4"), ("axis_impulse", "<f4"),
+                         ("motor_impulse", "<f4"), ("reserved", "<u4")])      # phx_slider
+assert slider_dtype.itemsize == 72
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
@@ -941,7 +945,7 @@ class World:
         the next step rebuilds the solver's schedule."""
         self._edit("phx_world_set_inverse_masses", bodies, values, 2, "set_inverse_masses")
 
-    # ---- units: pins, links and angles (include/phyx_amd.h PINS, LINKS, ANGLES; the specifications: tests/pin_spec.py, link_spec.py, angle_spec.py) ----
+    # ---- units: pins, links, angles and sliders (include/phyx_amd.h PINS, LINKS, ANGLES, SLIDERS; the specifications: tests/pin_spec.py, link_spec.py, angle_spec.py, slider_spec.py) ----
     def _add_units(self, fn, recs, dtype, extra=(), required=0, anchors=True):
         """recs: an array of `dtype`, or rows (body1, body2, anchor1, anchor2 (unless the record has no `anchors`), then the fields
         `extra`, the first `required` of them always); the rest of a record is zero."""
@@ -1002,10 +1006,10 @@ class World:
 
     def pin_schedule(self):
         """The schedule the next step's pin pass uses (built now unless current) -> dict with order, class_offsets, group_offsets,
-        lds_groups, as api.pin_schedule.  The slots hold units: the pins, then the links, then the angles."""
+        lds_groups, as api.pin_schedule.  The slots hold units: the pins, then the links, then the angles, then the sliders."""
         nc = C.c_int32(0); ng = C.c_int32(0); lg = C.c_int32(0)
         check(self.L.phx_world_get_pin_schedule(self.h, None, 0, None, 0, C.byref(nc), None, 0, C.byref(ng), C.byref(lg)))
-        n = self.pin_count() + self.link_count() + self.angle_count()
+        n = self.pin_count() + self.link_count() + self.angle_count() + self.slider_count()
         order = np.zeros(max(n, 1), dtype=np.int32)
         coff = np.zeros(nc.value + 1, dtype=np.int32); goff = np.zeros(ng.value + 1, dtype=np.int32)
         check(self.L.phx_world_get_pin_schedule(self.h, _ptr(order), n, _ptr(coff), len(coff), C.byref(nc), _ptr(goff), len(goff), C.byref(ng), C.byref(lg)))
@@ -1065,6 +1069,35 @@ class World:
     def angles(self):
         """Every angle as an angle_dtype array, with the impulses the last step accumulated."""
         return self._get(self.L.phx_world_get_angles, angle_dtype, self.angle_count())
+
+    def add_sliders(self, sliders):
+        """Append sliders: a slider_dtype array, or rows (body1, body2, anchor1, anchor2, axis, lower, upper[, hertz[, damping_ratio[,
+        motor_speed[, max_force]]]]) with the three impulses 0.  body1 is the carriage, body2 the rail (-1: the world); lower == upper: a
+        lock, with hertz > 0 a spring towards s = lower; lower < upper: limits; max_force > 0: a motor.  Returns the new sliders' indices."""
+        return self._add_units("phx_world_add_sliders", sliders, slider_dtype, ("axis", "lower", "upper", "hertz", "damping_ratio", "motor_speed", "max_force"), required=3)
+
+    def remove_sliders(self, sliders):
+        """Remove the listed sliders (each at most once); the others keep their order, so their indices shift."""
+        self._remove_units("phx_world_remove_sliders", sliders, "remove_sliders")
+
+    def set_slider_anchors(self, sliders, anchors):
+        """anchor1, anchor2 = anchors[k] (4 floats) of slider sliders[k]; the schedule stays."""
+        self._edit("phx_world_set_slider_anchors", sliders, anchors, 4, "set_slider_anchors")
+
+    def set_slider_limits(self, sliders, limits):
+        """lower, upper = limits[k] of slider sliders[k]; the schedule stays."""
+        self._edit("phx_world_set_slider_limits", sliders, limits, 2, "set_slider_limits")
+
+    def set_slider_motors(self, sliders, motors):
+        """motor_speed, max_force = motors[k] of slider sliders[k]; the schedule stays (an elevator's reversal)."""
+        self._edit("phx_world_set_slider_motors", sliders, motors, 2, "set_slider_motors")
+
+    def slider_count(self):
+        return self._int32("phx_world_slider_count")
+
+    def sliders(self):
+        """Every slider as a slider_dtype array, with the impulses the last step accumulated."""
+        return self._get(self.L.phx_world_get_sliders, slider_dtype, self.slider_count())
 
     # ---- the per-body columns: collision filters, materials, body flags ----
     @staticmethod

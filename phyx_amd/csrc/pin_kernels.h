@@ -17,6 +17,11 @@
 // Angles (include/phyx_amd.h ANGLES; the definition: tests/angle_spec.py) are the third kind: unit u >= npins + nlinks is angle
 // u - npins - nlinks.  An angle has no anchors and no axis: its prestep (angle_prestep) keeps its two rows, the motor M and the
 // lock / spring / limit L, in the registers a pin uses for its anchors, and its sweep (angle_sweep) edits the two angular velocities only.
+//
+// Sliders (include/phyx_amd.h SLIDERS; the definition: tests/slider_spec.py) are the fourth kind: unit u >= npins + nlinks + nangles is
+// slider u - npins - nlinks - nangles.  A slider has three scalar rows (the motor M and the lock / spring / limit L along the rail, the
+// hard row P across it) at one point with two arms: its lane keeps a link's registers (ra, rb' = rb + e, n, row L) in PinRegs and seven
+// words more (RailRegs), which exist only in the instantiations with sliders.
 #pragma once
 
 #include "pins.h"
@@ -32,7 +37,7 @@ struct PinGroup { int slot_begin, slot_end, body_begin, body_count; int first_dy
 // what a lane keeps of its pin from the prestep on
 // (a link's names for the registers a pin calls otherwise: the axis n, gamma, 1/kinv, the scalar bias, the clamp's bounds, lambda;
 //  an angle's: row L as a link's with 1/(kinv + gamma) beside 1/kinv, row M's speed, its largest impulse and its accumulated impulse)
-enum : unsigned char { UNIT_PIN = 0, UNIT_LINK = 1, UNIT_ANGLE = 2, ANGLE_ROW_L = 4, ANGLE_ROW_M = 8 };      // (an angle: UNIT_ANGLE | its engaged rows)
+enum : unsigned char { UNIT_PIN = 0, UNIT_LINK = 1, UNIT_ANGLE = 2, ANGLE_ROW_L = 4, ANGLE_ROW_M = 8, UNIT_SLIDER = 16 };      // (an angle: UNIT_ANGLE | its engaged rows; a slider: UNIT_SLIDER | its rows L, M)
 struct PinRegs {
     float rax, ray, rbx, rby;           // (an angle's inv_kg, speed, mmax, mlambda: the accessors below)
     union { float k11; float nx; };
@@ -56,6 +61,7 @@ struct PinRegs {
     __device__ float mmax() const { return rbx; }
     __device__ float mlambda() const { return rby; }
     __device__ bool angle() const { return (kind & UNIT_ANGLE) != 0; }
+    __device__ bool slider() const { return (kind & UNIT_SLIDER) != 0; }
     __device__ bool lrow() const { return (kind & ANGLE_ROW_L) != 0; }
     __device__ bool mrow() const { return (kind & ANGLE_ROW_M) != 0; }
 };
@@ -239,6 +245,144 @@ __device__ __forceinline__ void angle_sweep(PinRegs& r, float4& va, float4& vb)
     }
 }
 
+// what a slider's lane keeps beside PinRegs (which holds, under a link's names: ra, rb' in rbx / rby, n, gamma, inv_k = 1 / kinv_n, row L's
+// bias, lo, hi and lambda): row P's 1 / kinv_t, bias and impulse, row L's 1 / (kinv_n + gamma), row M's speed, largest and accumulated impulse
+struct RailRegs { float inv_kt, inv_kng, bias_t, speed, mmax, mlambda, plambda; };
+struct NoRail {};                       // (the instantiations without sliders)
+
+// tests/slider_spec.py prestep, operation for operation
+__device__ __forceinline__ PinRegs slider_prestep(const phx_slider& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, RailRegs& x)
+{
+    PinRegs r;
+    const float4 qa = mpos[p.body1], fa = frame[p.body1];
+    r.ma = qa.x; r.ia = qa.y;
+    r.rax = fa.x * p.anchor1.x + fa.z * p.anchor1.y;
+    r.ray = fa.y * p.anchor1.x + fa.w * p.anchor1.y;
+    const float pax = qa.z + r.rax, pay = qa.w + r.ray;
+    float pbx, pby, wx, wy;
+    if (p.body2 >= 0) {
+        const float4 qb = mpos[p.body2], fb = frame[p.body2];
+        r.mb = qb.x; r.ib = qb.y;
+        r.rbx = fb.x * p.anchor2.x + fb.z * p.anchor2.y;
+        r.rby = fb.y * p.anchor2.x + fb.w * p.anchor2.y;
+        pbx = qb.z + r.rbx; pby = qb.w + r.rby;
+        wx = fb.x * p.axis.x + fb.z * p.axis.y;
+        wy = fb.y * p.axis.x + fb.w * p.axis.y;
+    } else {
+        r.mb = 0.f; r.ib = 0.f; r.rbx = 0.f; r.rby = 0.f;
+        pbx = p.anchor2.x; pby = p.anchor2.y;
+        wx = p.axis.x; wy = p.axis.y;
+    }
+    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
+    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+    const float ex = pax - pbx, ey = pay - pby;                 // (not pin_anchors' separation negated: that differs in the sign of a zero, which C = s - lower keeps)
+    const float len = sqrtf(wx * wx + wy * wy);                 // (sqrtf: correctly rounded under the library's flags)
+    r.nx = wx / len; r.ny = wy / len;
+    r.rbx = r.rbx + ex; r.rby = r.rby + ey;                     // rb' = rb + e: B's arm to the carriage's anchor point
+    const float s = r.nx * ex + r.ny * ey, ct = r.nx * ey - r.ny * ex;
+    const float cat = r.rax * r.nx + r.ray * r.ny, cbt = r.rbx * r.nx + r.rby * r.ny;
+    const float can = r.rax * r.ny - r.ray * r.nx, cbn = r.rbx * r.ny - r.rby * r.nx;
+    const float ms = r.ma + r.mb;
+    const float kinv_t = (ms + (r.ia * cat) * cat) + (r.ib * cbt) * cbt;
+    float kinv = (ms + (r.ia * can) * can) + (r.ib * cbn) * cbn;
+    r.active = kinv_t > 0.f;
+    const bool solvable = r.active && kinv > 0.f;
+    x.inv_kt = 1.0f / kinv_t;
+    x.bias_t = ct * beta;
+    const float inf = __builtin_inff();
+    float c;
+    r.clamps = p.lower < p.upper;
+    bool lrow = true;
+    r.lo = -inf; r.hi = inf;
+    if (!r.clamps) c = s - p.lower;
+    else if (s >= p.upper) { c = s - p.upper; r.hi = 0.f; }
+    else if (s <= p.lower) { c = s - p.lower; r.lo = 0.f; }
+    else { c = 0.f; lrow = false; }                            // idle this step
+    r.inv_k = 1.0f / kinv;
+    if (p.hertz > 0.f) {
+        const float mass = 1.0f / kinv;
+        const float omega = 6.2831855f * p.hertz;
+        const float dmp = ((2.0f * mass) * p.damping_ratio) * omega;
+        const float k = (mass * omega) * omega;
+        r.gamma = 1.0f / (dt * (dmp + dt * k));
+        r.bias = ((c * dt) * k) * r.gamma;
+        kinv = kinv + r.gamma;
+    } else {
+        r.gamma = 0.f;
+        r.bias = c * beta;
+    }
+    x.inv_kng = 1.0f / kinv;
+    x.speed = p.motor_speed;
+    x.mmax = p.max_force * dt;
+    const bool mrow = solvable && p.max_force > 0.f;
+    lrow = solvable && lrow;
+    r.kind = UNIT_SLIDER | (lrow ? ANGLE_ROW_L : 0) | (mrow ? ANGLE_ROW_M : 0);
+    x.mlambda = mrow ? link_clamp(p.motor_impulse, -x.mmax, x.mmax) : 0.f;
+    r.lambda = lrow ? link_clamp(p.axis_impulse, r.lo, r.hi) : 0.f;
+    x.plambda = r.active ? p.impulse : 0.f;
+    return r;
+}
+
+// a slider's apply, P at the carriage's anchor point: vA += mA P, wA -= iA (ra x P), vB -= mB P, wB += iB (rb' x P)
+__device__ __forceinline__ void slider_apply(const PinRegs& r, float px, float py, float4& va, float4& vb)
+{
+    va.x = va.x + r.ma * px;
+    va.y = va.y + r.ma * py;
+    va.z = va.z - r.ia * (r.rax * py - r.ray * px);
+    vb.x = vb.x - r.mb * px;
+    vb.y = vb.y - r.mb * py;
+    vb.z = vb.z + r.ib * (r.rbx * py - r.rby * px);
+}
+
+// (vA + wA x ra) - (vB + wB x rb')
+__device__ __forceinline__ void slider_rel(const PinRegs& r, const float4& va, const float4& vb, float& rx, float& ry)
+{
+    const float uax = va.x + va.z * r.ray, uay = va.y - va.z * r.rax;
+    const float ubx = vb.x + vb.z * r.rby, uby = vb.y - vb.z * r.rbx;
+    rx = uax - ubx; ry = uay - uby;
+}
+
+// a slider's warm start: M's accumulated impulse, then L's, then P's
+__device__ __forceinline__ void slider_warm(const PinRegs& r, const RailRegs& x, float4& va, float4& vb)
+{
+    if (r.mrow()) slider_apply(r, x.mlambda * r.nx, x.mlambda * r.ny, va, vb);
+    if (r.lrow()) slider_apply(r, r.lambda * r.nx, r.lambda * r.ny, va, vb);
+    slider_apply(r, x.plambda * -r.ny, x.plambda * r.nx, va, vb);
+}
+
+// one sweep of a slider: M, then L, then P, each on the velocities the row before left; accumulates the three
+__device__ __forceinline__ void slider_sweep(PinRegs& r, RailRegs& x, float4& va, float4& vb)
+{
+    float rx, ry;
+    if (r.mrow()) {
+        slider_rel(r, va, vb, rx, ry);
+        const float cdot = r.nx * rx + r.ny * ry;
+        const float next = link_clamp(x.mlambda + -(r.inv_k * (cdot - x.speed)), -x.mmax, x.mmax);
+        const float d = next - x.mlambda;
+        x.mlambda = next;
+        slider_apply(r, d * r.nx, d * r.ny, va, vb);
+    }
+    if (r.lrow()) {
+        slider_rel(r, va, vb, rx, ry);
+        const float cdot = r.nx * rx + r.ny * ry;
+        float d = -(x.inv_kng * ((cdot + r.bias) + r.gamma * r.lambda));
+        if (r.clamps) {
+            const float next = link_clamp(r.lambda + d, r.lo, r.hi);
+            d = next - r.lambda;
+            r.lambda = next;
+        } else r.lambda = r.lambda + d;
+        slider_apply(r, d * r.nx, d * r.ny, va, vb);
+    }
+    slider_rel(r, va, vb, rx, ry);
+    const float cdot = r.nx * ry - r.ny * rx;
+    const float d = -(x.inv_kt * (cdot + x.bias_t));
+    x.plambda = x.plambda + d;
+    slider_apply(r, d * -r.ny, d * r.nx, va, vb);
+}
+// (the instantiations without sliders have no RailRegs and never get here)
+__device__ __forceinline__ void slider_warm(const PinRegs&, const NoRail&, float4&, float4&) {}
+__device__ __forceinline__ void slider_sweep(PinRegs&, NoRail&, float4&, float4&) {}
+
 // The engine's angularVelocity is CLOCKWISE-positive: IntegratePosition rotates the frame by -w dt (ref: World.cpp:63) and the contact
 // limiters project it with n x r (ref: Solver.cpp:559-560), so the velocity of a body's point at r is v - w x r = (v.x + w r.y, v.y - w r.x)
 // and an impulse P at r changes w by -i (r x P).
@@ -293,10 +437,15 @@ template <bool LINKS> __device__ __forceinline__ void unit_delta(PinRegs& r, con
 }
 // The angles' kernel arguments: a pack that is empty in a world without angles, so that the instantiations without them keep the
 // signature, the kernarg layout and the code they had before there were angles; with angles it is (phx_angle* angles, int nlinks).
+// The sliders' ride behind them the same way: (phx_slider* sliders, int nangles) and, in the trailing group's kernels, (RailWork* rail).
+struct RailWork;
 struct NoAngles { static constexpr bool present = false; };
 struct AngleArgs { static constexpr bool present = true; phx_angle* angles; int nlinks; };
+struct SliderArgs { static constexpr bool present = true; phx_angle* angles; int nlinks; phx_slider* sliders; int nangles; RailWork* rail; };
 __device__ __forceinline__ NoAngles angle_args() { return NoAngles{}; }
 __device__ __forceinline__ AngleArgs angle_args(phx_angle* angles, int nlinks) { return AngleArgs{angles, nlinks}; }
+__device__ __forceinline__ SliderArgs angle_args(phx_angle* angles, int nlinks, phx_slider* sliders, int nangles) { return SliderArgs{angles, nlinks, sliders, nangles, nullptr}; }
+__device__ __forceinline__ SliderArgs angle_args(phx_angle* angles, int nlinks, phx_slider* sliders, int nangles, RailWork* rail) { return SliderArgs{angles, nlinks, sliders, nangles, rail}; }
 
 // The LDS layout: one float4 per local body.  A lane's two bodies are anywhere in the table, so a class step is a gather / scatter of
 // 16-byte granules (ds_read_b128 / ds_write_b128).  A 16-byte read is served in four groups of 16 lanes over the 64 banks: a group
@@ -309,7 +458,7 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
                                                                  const PinGroup* __restrict__ groups, const int* __restrict__ group_bodies, float4* __restrict__ vel,
                                                                  const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, int iterations, A... angle_pack)
 {
-    constexpr bool ANGLES = sizeof...(A) > 0;
+    constexpr bool ANGLES = sizeof...(A) > 0, SLIDERS = sizeof...(A) > 2;
     [[maybe_unused]] const auto ang = angle_args(angle_pack...);
     __shared__ float4 sv[PIN_BODIES];
     const PinGroup g = groups[blockIdx.x];
@@ -322,9 +471,16 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     const bool mine = slot < g.slot_end;
     PinSlot s = {0, 0, -1, -1};
     PinRegs r = {};
+    [[maybe_unused]] std::conditional_t<SLIDERS, RailRegs, NoRail> x = {};
     if (mine) {
         s = slots[slot];
-        if constexpr (ANGLES)
+        if constexpr (SLIDERS) {
+            const int npl = npins + ang.nlinks, npla = npl + ang.nangles;
+            r = s.pin < npins ? pin_prestep(pins[s.pin], mpos, frame, beta)
+                : s.pin < npl ? link_prestep(links[s.pin - npins], mpos, frame, beta, dt)
+                : s.pin < npla ? angle_prestep(ang.angles[s.pin - npl], mpos, frame, beta, dt)
+                : slider_prestep(ang.sliders[s.pin - npla], mpos, frame, beta, dt, x);
+        } else if constexpr (ANGLES)
             r = s.pin < npins ? pin_prestep(pins[s.pin], mpos, frame, beta)
                 : s.pin < npins + ang.nlinks ? link_prestep(links[s.pin - npins], mpos, frame, beta, dt)
                 : angle_prestep(ang.angles[s.pin - npins - ang.nlinks], mpos, frame, beta, dt);
@@ -337,7 +493,8 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     for (int c = 0; c < g.classes; ++c) {                                   // warm start, class by class
         if (work && s.colour == c) {
             float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-            if (ANGLES && r.angle()) angle_warm(r, va, vb);
+            if (SLIDERS && r.slider()) slider_warm(r, x, va, vb);
+            else if (ANGLES && r.angle()) angle_warm(r, va, vb);
             else {
                 float dx, dy;
                 unit_warm<LINKS>(r, dx, dy);
@@ -352,7 +509,8 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
         for (int c = 0; c < g.classes; ++c) {
             if (work && s.colour == c) {
                 float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-                if (ANGLES && r.angle()) angle_sweep(r, va, vb);
+                if (SLIDERS && r.slider()) slider_sweep(r, x, va, vb);
+                else if (ANGLES && r.angle()) angle_sweep(r, va, vb);
                 else {
                     float dx, dy;
                     unit_delta<LINKS>(r, va, vb, dx, dy);
@@ -365,7 +523,12 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
         }
     for (int i = g.first_dynamic + (int)threadIdx.x; i < g.body_count; i += PIN_LANES) vel[bodies[i]] = sv[i];
     if (mine) {
-        if constexpr (ANGLES) {
+        if constexpr (SLIDERS) {
+            if (r.slider()) { phx_slider& a = ang.sliders[s.pin - npins - ang.nlinks - ang.nangles]; a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda; }
+            else if (r.angle()) { phx_angle& a = ang.angles[s.pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
+            else if (r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda;
+            else pins[s.pin].impulse = phx_vec2{r.px, r.py};
+        } else if constexpr (ANGLES) {
             if (r.angle()) { phx_angle& a = ang.angles[s.pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
             else if (r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda;
             else pins[s.pin].impulse = phx_vec2{r.px, r.py};
@@ -376,7 +539,10 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
 }
 
 // ---- the trailing group, out of HBM ----
-struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };      // flags: 1 active, 2 write a, 4 write b, 8 link, 16 clamps, 32 angle, 64 row L, 128 row M
+struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };      // flags: 1 active, 2 write a, 4 write b, 8 link, 16 clamps, 32 angle, 64 row L, 128 row M, 256 slider
+// a slider's words beyond PinWork (which holds what a link's does, rb' in rbx / rby): a side array beside the work array, slot for slot,
+// which exists only in a world with sliders; its three impulses come from its record
+struct RailWork { float inv_kt, inv_kng, bias_t, speed, mmax, pad0, pad1, pad2; };
 
 // (k11 .. biasy hold a link's nx, ny, gamma, inv_k, bias, lo: PinRegs' unions; px, py = the unit's accumulated impulse, a link's in px;
 //  an angle's two come from its record: impulse in px, motor_impulse in `rby`)
@@ -404,16 +570,42 @@ __device__ __forceinline__ PinWork pin_work(const PinRegs& r)
     return w;
 }
 
+// a slider's lane state out of the trailing group's records
+__device__ __forceinline__ PinRegs slider_regs(const PinWork& w, const RailWork& k, const phx_slider& a, RailRegs& x)
+{
+    PinRegs r = pin_regs<false>(w, a.axis_impulse, 0.f, w.rby);
+    r.kind = UNIT_SLIDER | ((w.flags & 64) ? ANGLE_ROW_L : 0) | ((w.flags & 128) ? ANGLE_ROW_M : 0);
+    r.hi = w.hi;
+    x.inv_kt = k.inv_kt; x.inv_kng = k.inv_kng; x.bias_t = k.bias_t; x.speed = k.speed; x.mmax = k.mmax;
+    x.mlambda = a.motor_impulse; x.plambda = a.impulse;
+    return r;
+}
+
 // slots [begin, end): the prestep; an inactive pin's impulse becomes 0 here, a link's its warm start (clamped; 0 when inactive or idle),
-// an angle's two likewise
+// an angle's two and a slider's three likewise
 template <bool LINKS, class... A>
 static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
                                                             const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, PinWork* __restrict__ work, A... angle_pack)
 {
-    constexpr bool ANGLES = sizeof...(A) > 0;
+    constexpr bool ANGLES = sizeof...(A) > 0, SLIDERS = sizeof...(A) > 2;
     [[maybe_unused]] const auto ang = angle_args(angle_pack...);
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const int pin = slots[k].pin;
+        if constexpr (SLIDERS) {
+            const int npla = npins + ang.nlinks + ang.nangles;
+            if (pin >= npla) {
+                RailRegs x;
+                phx_slider& a = ang.sliders[pin - npla];
+                const PinRegs r = slider_prestep(a, mpos, frame, beta, dt, x);
+                PinWork w = pin_work(r);
+                w.flags |= 256 | (r.lrow() ? 64 : 0) | (r.mrow() ? 128 : 0);
+                w.hi = r.hi;
+                work[k - begin] = w;
+                ang.rail[k - begin] = RailWork{x.inv_kt, x.inv_kng, x.bias_t, x.speed, x.mmax, 0.f, 0.f, 0.f};
+                a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda;
+                continue;
+            }
+        }
         if constexpr (ANGLES) {
             const PinRegs r = pin < npins ? pin_prestep(pins[pin], mpos, frame, beta)
                               : pin < npins + ang.nlinks ? link_prestep(links[pin - npins], mpos, frame, beta, dt)
@@ -443,13 +635,26 @@ template <bool LINKS, class... A>
 static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
                                                           int base, const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep, A... angle_pack)
 {
-    constexpr bool ANGLES = sizeof...(A) > 0;
+    constexpr bool ANGLES = sizeof...(A) > 0, SLIDERS = sizeof...(A) > 2;
     [[maybe_unused]] const auto ang = angle_args(angle_pack...);
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const PinSlot s = slots[k];
         const PinWork w = work[k - base];
         if (!(w.flags & 1)) continue;
         const bool link = LINKS && (w.flags & 8) != 0;
+        if constexpr (SLIDERS) {
+            if (w.flags & 256) {                                              // a slider: its three impulses from its record
+                phx_slider& a = ang.sliders[s.pin - npins - ang.nlinks - ang.nangles];
+                RailRegs x;
+                PinRegs r = slider_regs(w, ang.rail[k - base], a, x);
+                float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
+                if (sweep) slider_sweep(r, x, va, vb); else slider_warm(r, x, va, vb);
+                if (r.write_a) vel[s.a] = va;
+                if (r.write_b) vel[s.b] = vb;
+                if (sweep) { a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda; }
+                continue;
+            }
+        }
         if constexpr (ANGLES) {
             if (w.flags & 32) {                                               // an angle: both impulses from its record, w only
                 phx_angle& a = ang.angles[s.pin - npins - ang.nlinks];
@@ -476,7 +681,7 @@ static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ 
 }
 
 // ---- what the host asks between steps ----
-// (`P`: phx_pin, phx_link or phx_angle, which begin alike: body1, body2; only those are read)
+// (`P`: phx_pin, phx_link, phx_angle or phx_slider, which begin alike: body1, body2; only those are read)
 // per pin: are its bodies static (bit 0: body1, bit 1: body2)?  O(pins) bytes for the schedule build
 template <class P>
 static __global__ void __launch_bounds__(256) k_pin_statics(const P* __restrict__ pins, int n, const float4* __restrict__ mpos, unsigned* __restrict__ out)

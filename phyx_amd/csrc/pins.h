@@ -11,6 +11,8 @@
 //
 // Angles (include/phyx_amd.h ANGLES) are the third kind, behind the links: a record without anchors, so nothing here may ask for any
 // but through AnchorFields, which an angle never instantiates.
+//
+// Sliders (include/phyx_amd.h SLIDERS) are the fourth kind, behind the angles: anchors as a pin's, limits and a motor as an angle's.
 #pragma once
 
 #include <type_traits>
@@ -53,6 +55,15 @@ template <> struct UnitKind<phx_angle> {
     static int check_motor(const char* what, int k, float speed, float max_torque);               // (also phx_world_set_angle_motors')
 };
 
+template <> struct UnitKind<phx_slider> {
+    static constexpr const char* noun = "slider";
+    static constexpr const char* plural = "sliders";
+    static constexpr const char* add = "phx_world_add_sliders", *remove = "phx_world_remove_sliders", *set_anchors = "phx_world_set_slider_anchors", *get = "phx_world_get_sliders";
+    static int check(const char* what, int k, const phx_slider& p);
+    static int check_limits(const char* what, int k, float lower, float upper, float hertz);      // (also phx_world_set_slider_limits' rule)
+    static int check_motor(const char* what, int k, float speed, float max_force);                // (also phx_world_set_slider_motors')
+};
+
 // the fields an edit between steps writes, `width` floats per record: on the host list and, by k_unit_fields, on the device copy
 struct AnchorFields {
     static constexpr int width = 4;
@@ -65,14 +76,15 @@ struct LengthFields {
 
 struct LimitFields {
     static constexpr int width = 2;
-    static __host__ __device__ void write(phx_angle& p, const float* v) { p.lower = v[0]; p.upper = v[1]; }
+    template <class P> static __host__ __device__ void write(P& p, const float* v) { p.lower = v[0]; p.upper = v[1]; }
 };
 struct MotorFields {
     static constexpr int width = 2;
     static __host__ __device__ void write(phx_angle& p, const float* v) { p.motor_speed = v[0]; p.max_torque = v[1]; }
+    static __host__ __device__ void write(phx_slider& p, const float* v) { p.motor_speed = v[0]; p.max_force = v[1]; }
 };
 
-// a list of records `P` (phx_pin, phx_link, phx_angle: body1, body2 first; the impulses the device's once uploaded)
+// a list of records `P` (phx_pin, phx_link, phx_angle, phx_slider: body1, body2 first; the impulses the device's once uploaded)
 template <class P> class UnitList {
 public:
     int count() const { return (int)host_.size(); }
@@ -104,24 +116,26 @@ public:
     {
         if constexpr (std::is_same_v<P, phx_pin>) return pins_;
         else if constexpr (std::is_same_v<P, phx_link>) return links_;
-        else return angles_;
+        else if constexpr (std::is_same_v<P, phx_angle>) return angles_;
+        else return sliders_;
     }
     template <class P> const UnitList<P>& list() const { return const_cast<PinSet*>(this)->list<P>(); }
-    int units() const { return pins_.count() + links_.count() + angles_.count(); }      // the pass's units: the pins, then the links, then the angles
+    int units() const { return pins_.count() + links_.count() + angles_.count() + sliders_.count(); }      // the pass's units: the pins, then the links, then the angles, then the sliders
     int group_pins() const { return group_pins_; }
     long long builds() const { return builds_; }
     int iterations = 8;
 
     // the calls (world.hip, "units") work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
     void units_changed() { sched_dirty_ = true; }
-    void clear() { pins_.clear(); links_.clear(); angles_.clear(); sched_dirty_ = true; }
+    void clear() { pins_.clear(); links_.clear(); angles_.clear(); sliders_.clear(); sched_dirty_ = true; }
     void statics_changed() { if (units()) sched_dirty_ = true; }             // ... and a change of the static set make the schedule stale
     // a removal of bodies compacted them through `d_remap` (old index -> new or -1): the units of removed bodies go, the rest are renumbered
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream);
     // snapshots: the device copies (list<P>().device()), current
-    int upload(hipStream_t stream) { PHX_TRY(pins_.upload(stream)); PHX_TRY(links_.upload(stream)); return angles_.upload(stream); }
+    int upload(hipStream_t stream) { PHX_TRY(pins_.upload(stream)); PHX_TRY(links_.upload(stream)); PHX_TRY(angles_.upload(stream)); return sliders_.upload(stream); }
     // load: the lists := device arrays (queued; the host lists follow at once)
-    int adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count, hipStream_t stream);
+    int adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
+                     const phx_slider* d_sliders, int slider_count, hipStream_t stream);
 
     // the schedule, built unless current
     int prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream);
@@ -133,12 +147,13 @@ private:
     UnitList<phx_pin> pins_;
     UnitList<phx_link> links_;
     UnitList<phx_angle> angles_;
+    UnitList<phx_slider> sliders_;
     bool sched_dirty_ = true;
     int group_pins_ = 0;
     long long builds_ = 0;
     DevBuf<unsigned> d_bits_;
     DevBuf<char> d_tables_;              // slots | groups | group bodies, one upload per build
-    DevBuf<char> d_work_;                // the trailing group's prestep results
+    DevBuf<char> d_work_;                // the trailing group's prestep results (with sliders: the PinWork array, then the RailWork array)
     size_t off_groups_ = 0, off_bodies_ = 0;
     Schedule sched_;
     std::vector<int> hbm_classes_;       // the trailing group's class offsets (absolute slots)

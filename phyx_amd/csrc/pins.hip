@@ -8,7 +8,8 @@
 // Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: UnitList<P> is the list machinery for either record and
 // UnitKind<P> what the World's calls check of one, the schedule is built over the pins followed by the links, and a world that has
 // links launches the kernels' LINKS instantiations.  Angles (ANGLES) are the third, behind the links; a world that has angles
-// launches the instantiations with both.
+// launches the instantiations with both.  Sliders (SLIDERS) are the fourth, behind the angles; a world that has sliders launches the
+// instantiations that know all four kinds.
 #include "pins.h"
 #include "pin_kernels.h"
 
@@ -153,12 +154,16 @@ template <class P> int UnitList<P>::statics(const float4* mpos, unsigned* d_bits
 template class UnitList<phx_pin>;
 template class UnitList<phx_link>;
 template class UnitList<phx_angle>;
+template class UnitList<phx_slider>;
 
 template int UnitList<phx_pin>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 template int UnitList<phx_link>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 template int UnitList<phx_link>::set_fields<LengthFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 template int UnitList<phx_angle>::set_fields<LimitFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 template int UnitList<phx_angle>::set_fields<MotorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_slider>::set_fields<AnchorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_slider>::set_fields<LimitFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
+template int UnitList<phx_slider>::set_fields<MotorFields>(const int32_t*, const float*, int, const int*, const float*, hipStream_t);
 
 // ---- entry k of an add beyond the body rules (the order of the checks is the calls' contract: the first failure wins) ----
 static int check_finite(const char* what, const char* noun, int k, std::initializer_list<float> values)
@@ -216,24 +221,54 @@ int UnitKind<phx_angle>::check_motor(const char* what, int k, float speed, float
     return PHX_OK;
 }
 
+int UnitKind<phx_slider>::check(const char* what, int k, const phx_slider& p)
+{
+    PHX_TRY(check_finite(what, noun, k, {p.anchor1.x, p.anchor1.y, p.anchor2.x, p.anchor2.y, p.axis.x, p.axis.y, p.lower, p.upper, p.hertz, p.damping_ratio,
+                                         p.motor_speed, p.max_force, p.impulse, p.axis_impulse, p.motor_impulse}));
+    if (!(p.axis.x * p.axis.x + p.axis.y * p.axis.y > 0x1p-20f)) { set_error("%s: slider %d: axis (%g, %g) is too short to give a direction", what, k, (double)p.axis.x, (double)p.axis.y); return PHX_ERR_INVALID; }
+    if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: slider %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
+    PHX_TRY(check_limits(what, k, p.lower, p.upper, p.hertz));
+    PHX_TRY(check_motor(what, k, p.motor_speed, p.max_force));
+    if (p.reserved != 0) { set_error("%s: slider %d: reserved must be 0", what, k); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int UnitKind<phx_slider>::check_limits(const char* what, int k, float lower, float upper, float hertz)
+{
+    if (!std::isfinite(lower) || !std::isfinite(upper)) { set_error("%s: slider %d: a limit is not finite", what, k); return PHX_ERR_INVALID; }
+    if (!(lower <= upper)) { set_error("%s: slider %d: limits [%g, %g] are not lower <= upper", what, k, (double)lower, (double)upper); return PHX_ERR_INVALID; }
+    if (hertz > 0.f && lower != upper) { set_error("%s: slider %d: a spring (hertz %g) needs lower == upper", what, k, (double)hertz); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int UnitKind<phx_slider>::check_motor(const char* what, int k, float speed, float max_force)
+{
+    if (!std::isfinite(speed) || !std::isfinite(max_force)) { set_error("%s: slider %d: a motor value is not finite", what, k); return PHX_ERR_INVALID; }
+    if (max_force < 0.f) { set_error("%s: slider %d: negative max_force %g", what, k, (double)max_force); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
 int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
 {
     PHX_TRY(pins_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
     PHX_TRY(links_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
-    return angles_.bodies_removed(d_remap, rb, stream, &sched_dirty_);
+    PHX_TRY(angles_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
+    return sliders_.bodies_removed(d_remap, rb, stream, &sched_dirty_);
 }
 
-int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count, hipStream_t stream)
+int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
+                         const phx_slider* d_sliders, int slider_count, hipStream_t stream)
 {
     sched_dirty_ = true;
     PHX_TRY(pins_.adopt_device(d_pins, pin_count, stream));
     PHX_TRY(links_.adopt_device(d_links, link_count, stream));
-    return angles_.adopt_device(d_angles, angle_count, stream);
+    PHX_TRY(angles_.adopt_device(d_angles, angle_count, stream));
+    return sliders_.adopt_device(d_sliders, slider_count, stream);
 }
 
 int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
 {
-    const int n = units(), np = pins_.count(), npl = np + links_.count();
+    const int n = units(), np = pins_.count(), npl = np + links_.count(), npla = npl + angles_.count();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
     if (!sched_dirty_) return PHX_OK;
@@ -241,9 +276,10 @@ int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream
     PHX_TRY(pins_.statics(mpos, d_bits_.p, stream));
     PHX_TRY(links_.statics(mpos, d_bits_.p + np, stream));
     PHX_TRY(angles_.statics(mpos, d_bits_.p + npl, stream));
-    // a unit's bodies: pin u, link u - np, or angle u - npl
-    auto body1 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body1 : u < npl ? links_.host()[(size_t)(u - np)].body1 : angles_.host()[(size_t)(u - npl)].body1; };
-    auto body2 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body2 : u < npl ? links_.host()[(size_t)(u - np)].body2 : angles_.host()[(size_t)(u - npl)].body2; };
+    PHX_TRY(sliders_.statics(mpos, d_bits_.p + npla, stream));
+    // a unit's bodies: pin u, link u - np, angle u - npl, or slider u - npla
+    auto body1 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body1 : u < npl ? links_.host()[(size_t)(u - np)].body1 : u < npla ? angles_.host()[(size_t)(u - npl)].body1 : sliders_.host()[(size_t)(u - npla)].body1; };
+    auto body2 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body2 : u < npl ? links_.host()[(size_t)(u - np)].body2 : u < npla ? angles_.host()[(size_t)(u - npl)].body2 : sliders_.host()[(size_t)(u - npla)].body2; };
     std::vector<unsigned> bits((size_t)n);
     PHX_TRY(rb.add(bits.data(), d_bits_.p, (size_t)n * sizeof(unsigned), stream));
     PHX_TRY(rb.wait(stream));
@@ -298,7 +334,8 @@ int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream
     PHX_TRY(d_tables_.reserve(blob.size()));
     PHX_HIP(hipMemcpyAsync(d_tables_.p, blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
     PHX_HIP(hipStreamSynchronize(stream));                                  // (`blob` is a local)
-    if (s.has_hbm_group()) PHX_TRY(d_work_.reserve((size_t)(s.hbm_end() - s.hbm_begin()) * sizeof(PinWork)));
+    // (a world with sliders keeps their side records behind the work array: pin_kernels.h RailWork)
+    if (s.has_hbm_group()) PHX_TRY(d_work_.reserve((size_t)(s.hbm_end() - s.hbm_begin()) * (sizeof(PinWork) + (sliders_.count() ? sizeof(RailWork) : 0))));
     sched_dirty_ = false;
     return PHX_OK;
 }
@@ -310,20 +347,25 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
     phx_pin* const d_pins = pins_.device();
     phx_link* const d_links = links_.device();
     phx_angle* const d_angles = angles_.device();
-    const int np = pins_.count(), nl = links_.count();
+    phx_slider* const d_sliders = sliders_.device();
+    const int np = pins_.count(), nl = links_.count(), na = angles_.count();
     const float beta = 0.2f / dt;
     const PinSlot* slots = reinterpret_cast<const PinSlot*>(d_tables_.p);
     // a world without links runs the pins' own instantiation of each kernel: what it ran before there were links; one without angles
     // what it ran before there were angles; one with angles the instantiation that knows all three kinds
-    // (whose kernels take the angles' two arguments behind the others': pin_kernels.h AngleArgs)
-    const bool with_angles = angles_.count() > 0, with_links = nl > 0;
+    // (whose kernels take the angles' two arguments behind the others': pin_kernels.h AngleArgs); one with sliders the instantiation
+    // that knows all four (the sliders' arguments behind the angles': SliderArgs)
+    const bool with_sliders = sliders_.count() > 0, with_angles = na > 0, with_links = nl > 0;
     auto pick = [with_links](auto with, auto without) { return with_links ? with : without; };
     const dim3 lds_grid(sched_.lds_groups), lds_block(PIN_LANES);
     const PinGroup* const groups = reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_);
     const int* const group_bodies = reinterpret_cast<const int*>(d_tables_.p + off_bodies_);
     const float4* const mpos = (const float4*)bodies.s.mpos, *const frame = (const float4*)bodies.frame;
     if (sched_.lds_groups) {
-        if (with_angles)
+        if (with_sliders)
+            hipLaunchKernelGGL((k_solve_pins<true, phx_angle*, int, phx_slider*, int>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
+                               mpos, frame, beta, dt, iterations, d_angles, nl, d_sliders, na);
+        else if (with_angles)
             hipLaunchKernelGGL((k_solve_pins<true, phx_angle*, int>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
                                mpos, frame, beta, dt, iterations, d_angles, nl);
         else
@@ -333,7 +375,11 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
     if (hbm_classes_.size() > 1) {
         const int begin = hbm_classes_.front(), end = hbm_classes_.back();
         PinWork* work = reinterpret_cast<PinWork*>(d_work_.p);
-        if (with_angles)
+        RailWork* const rail = reinterpret_cast<RailWork*>(work + (end - begin));      // (only a world with sliders has it)
+        if (with_sliders)
+            hipLaunchKernelGGL((k_pin_prestep<true, phx_angle*, int, phx_slider*, int, RailWork*>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame,
+                               beta, dt, work, d_angles, nl, d_sliders, na, rail);
+        else if (with_angles)
             hipLaunchKernelGGL((k_pin_prestep<true, phx_angle*, int>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame, beta, dt, work, d_angles, nl);
         else
             hipLaunchKernelGGL(pick(k_pin_prestep<true>, k_pin_prestep<false>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame, beta, dt, work);
@@ -341,7 +387,10 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
             for (size_t c = 0; c + 1 < hbm_classes_.size(); ++c) {
                 const int b = hbm_classes_[c], e = hbm_classes_[c + 1];
                 if (e <= b) continue;
-                if (with_angles)
+                if (with_sliders)
+                    hipLaunchKernelGGL((k_pin_class<true, phx_angle*, int, phx_slider*, int, RailWork*>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
+                                       (const PinWork*)work, bodies.s.vel, sweep, d_angles, nl, d_sliders, na, rail);
+                else if (with_angles)
                     hipLaunchKernelGGL((k_pin_class<true, phx_angle*, int>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
                                        (const PinWork*)work, bodies.s.vel, sweep, d_angles, nl);
                 else

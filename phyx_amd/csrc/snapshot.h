@@ -42,15 +42,21 @@ public:
     // the world's pins (include/phyx_amd.h PINS) ride beside the blob's layout, which holds none: room first (nothing changes if that
     // fails), then a device copy queued behind the save, in front of the event the loads wait for
     // (a save that fails afterwards leaves the old ones whole).  The links (LINKS) ride the same way.
-    // The angles (ANGLES) are the third rider.
-    int reserve_units(int pins, int links, int angles, hipStream_t stream) { PHX_TRY(pins_.reserve(pins, stream)); PHX_TRY(links_.reserve(links, stream)); return angles_.reserve(angles, stream); }
-    int save_units(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count, hipStream_t stream);
+    // The angles (ANGLES) are the third rider, the sliders (SLIDERS) the fourth.
+    int reserve_units(int pins, int links, int angles, int sliders, hipStream_t stream)
+    {
+        PHX_TRY(pins_.reserve(pins, stream)); PHX_TRY(links_.reserve(links, stream)); PHX_TRY(angles_.reserve(angles, stream)); return sliders_.reserve(sliders, stream);
+    }
+    int save_units(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
+                   const phx_slider* d_sliders, int slider_count, hipStream_t stream);
     const phx_pin* pins() const { return pins_.buf.p; }
     int pin_count() const { return pins_.count; }
     const phx_link* links() const { return links_.buf.p; }
     int link_count() const { return links_.count; }
     const phx_angle* angles() const { return angles_.buf.p; }
     int angle_count() const { return angles_.count; }
+    const phx_slider* sliders() const { return sliders_.buf.p; }
+    int slider_count() const { return sliders_.count; }
     int blob_bytes(size_t* bytes) const;
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
@@ -58,7 +64,7 @@ public:
 private:
     int settle();                        // the host waits for the queued save and loads (export, import, destroy)
     int refuse_empty(const char* what) const;
-    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins, no links and no angles
+    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins, no links, no angles and no sliders
     template <class P> struct Riders {            // a list of records beside the blob
         DevBuf<P> buf; int count = 0;
         int reserve(int n, hipStream_t stream) { return n ? buf.reserve_keep((size_t)n, (size_t)count, stream) : PHX_OK; }      // (none: nothing is allocated)
@@ -67,6 +73,7 @@ private:
     Riders<phx_pin> pins_;
     Riders<phx_link> links_;
     Riders<phx_angle> angles_;
+    Riders<phx_slider> sliders_;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

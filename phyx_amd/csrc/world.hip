@@ -193,7 +193,7 @@ public:
     int set_body_flags(const int32_t* bodies, const uint32_t* flags, int count);
     int get_body_flags(uint32_t* out, int cap);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
-    // units: pins, links and angles, `P` = phx_pin, phx_link or phx_angle (phx_world_add_pins ... phx_world_get_angles, phx_world_get_pin_schedule): between
+    // units: pins, links, angles and sliders, `P` = phx_pin, phx_link, phx_angle or phx_slider (phx_world_add_pins ... phx_world_get_sliders, phx_world_get_pin_schedule): between
     // steps; solved at the end of pre_solve (pins.h)
     template <class P> int add_units(const P* recs, int count, int* first);
     template <class P> int remove_units(const int32_t* which, int count);
@@ -202,6 +202,8 @@ public:
     int set_link_lengths(const int32_t* which, const float* lengths, int count);
     int set_angle_limits(const int32_t* which, const float* limits, int count);
     int set_angle_motors(const int32_t* which, const float* motors, int count);
+    int set_slider_limits(const int32_t* which, const float* limits, int count);
+    int set_slider_motors(const int32_t* which, const float* motors, int count);
     int set_pin_iterations(int n);
     int pin_schedule(const Schedule** out);
     int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
@@ -1044,9 +1046,10 @@ int World::save(Snapshot& s)
     const UnitList<phx_pin>& pins = pins_.list<phx_pin>();
     const UnitList<phx_link>& links = pins_.list<phx_link>();
     const UnitList<phx_angle>& angles = pins_.list<phx_angle>();
-    PHX_TRY(s.reserve_units(pins.count(), links.count(), angles.count(), stream_));
+    const UnitList<phx_slider>& sliders = pins_.list<phx_slider>();
+    PHX_TRY(s.reserve_units(pins.count(), links.count(), angles.count(), sliders.count(), stream_));
     PHX_TRY(s.save(v, stream_));
-    return s.save_units(pins.device(), pins.count(), links.device(), links.count(), angles.device(), angles.count(), stream_);
+    return s.save_units(pins.device(), pins.count(), links.device(), links.count(), angles.device(), angles.count(), sliders.device(), sliders.count(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -1083,7 +1086,7 @@ int World::load(Snapshot& s)
     // what set_state resets: the pair set becomes the saved manifolds' pairs, the schedule is rebuilt at the next step
     PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
     PHX_TRY(forget_step_history());
-    return pins_.adopt_device(s.pins(), s.pin_count(), s.links(), s.link_count(), s.angles(), s.angle_count(), stream_);      // 6. add_pins, add_links, add_angles of the saved ones
+    return pins_.adopt_device(s.pins(), s.pin_count(), s.links(), s.link_count(), s.angles(), s.angle_count(), s.sliders(), s.slider_count(), stream_);      // 6. add_pins, add_links, add_angles, add_sliders of the saved ones
 }
 
 int World::get_slab_state(const long long* global_index, int count, SlabState* out)
@@ -1550,14 +1553,14 @@ int World::set_body_flags(const int32_t* bodies, const uint32_t* flags, int coun
 }
 int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_get_body_flags", flags_col_, out, cap); }
 
-// ---- units: pins, links and angles --------------------------------------------------------------------------------------------------------
-// The rules and the arithmetic: include/phyx_amd.h PINS, LINKS, ANGLES; the lists, the schedule and the pass: pins.h.  One copy of the calls for
+// ---- units: pins, links, angles and sliders --------------------------------------------------------------------------------------------------------
+// The rules and the arithmetic: include/phyx_amd.h PINS, LINKS, ANGLES, SLIDERS; the lists, the schedule and the pass: pins.h.  One copy of the calls for
 // both records (`P`; what differs is UnitKind<P>): they check everything first — inside a step, sharded, count, null, overflow, the
 // entries in order — then change the list; the schedule follows lazily at the next step.
 int World::refuse_pins(const char* what)
 {
     if (!pins_.units()) return PHX_OK;
-    set_error("%s: the world holds %s, which a sharded world does not carry", what, pins_.list<phx_pin>().count() ? "pins" : pins_.list<phx_link>().count() ? "links" : "angles");
+    set_error("%s: the world holds %s, which a sharded world does not carry", what, pins_.list<phx_pin>().count() ? "pins" : pins_.list<phx_link>().count() ? "links" : pins_.list<phx_angle>().count() ? "angles" : "sliders");
     return PHX_ERR_STATE;
 }
 
@@ -1597,7 +1600,7 @@ int World::add_units(const P* recs, int count, int* first)
     PHX_TRY(refuse_sharded(what, Kind::plural));
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && !recs) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
-    // (the schedule numbers the units, pins, links and angles together, in an int32)
+    // (the schedule numbers the units, pins, links, angles and sliders together, in an int32)
     if ((long long)pins_.units() + count > (long long)INT32_MAX) { set_error("%s: %d + %d units exceed the int32 range", what, pins_.units(), count); return PHX_ERR_INVALID; }
     for (int k = 0; k < count; ++k) {
         PHX_TRY(check_unit_bodies(what, Kind::noun, k, recs[k].body1, recs[k].body2));
@@ -1670,6 +1673,24 @@ int World::set_angle_motors(const int32_t* which, const float* motors, int count
     PHX_TRY(check_unit_indices<phx_angle>(what, which, motors, count));
     for (int k = 0; k < count; ++k) PHX_TRY(UnitKind<phx_angle>::check_motor(what, k, motors[2 * k], motors[2 * k + 1]));
     return set_unit_fields<phx_angle, MotorFields>(which, motors, count);
+}
+
+int World::set_slider_limits(const int32_t* which, const float* limits, int count)
+{
+    static const char* const what = "phx_world_set_slider_limits";
+    PHX_TRY(check_unit_indices<phx_slider>(what, which, limits, count));
+    const std::vector<phx_slider>& sliders = pins_.list<phx_slider>().host();  // (bodies, anchors, axis, limits, hertz, motor: always current)
+    for (int k = 0; k < count; ++k)
+        PHX_TRY(UnitKind<phx_slider>::check_limits(what, k, limits[2 * k], limits[2 * k + 1], sliders[(size_t)which[k]].hertz));
+    return set_unit_fields<phx_slider, LimitFields>(which, limits, count);
+}
+
+int World::set_slider_motors(const int32_t* which, const float* motors, int count)
+{
+    static const char* const what = "phx_world_set_slider_motors";
+    PHX_TRY(check_unit_indices<phx_slider>(what, which, motors, count));
+    for (int k = 0; k < count; ++k) PHX_TRY(UnitKind<phx_slider>::check_motor(what, k, motors[2 * k], motors[2 * k + 1]));
+    return set_unit_fields<phx_slider, MotorFields>(which, motors, count);
 }
 
 template <class P>
@@ -2347,6 +2368,50 @@ int phx_world_angle_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
     *count = w->impl.pins().list<phx_angle>().count();
+    return PHX_OK;
+}
+
+int phx_world_add_sliders(phx_world* w, const phx_slider* sliders, int32_t count, int32_t* first)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.add_units(sliders, count, first);
+}
+
+int phx_world_remove_sliders(phx_world* w, const int32_t* sliders, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.remove_units<phx_slider>(sliders, count);
+}
+
+int phx_world_set_slider_anchors(phx_world* w, const int32_t* sliders, const float* anchors, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_unit_anchors<phx_slider>(sliders, anchors, count);
+}
+
+int phx_world_set_slider_limits(phx_world* w, const int32_t* sliders, const float* limits, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_slider_limits(sliders, limits, count);
+}
+
+int phx_world_set_slider_motors(phx_world* w, const int32_t* sliders, const float* motors, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_slider_motors(sliders, motors, count);
+}
+
+int phx_world_get_sliders(phx_world* w, phx_slider* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_units(out, cap);
+}
+
+int phx_world_slider_count(phx_world* w, int32_t* count)
+{
+    PHX_REQUIRE(w && count, "null handle / output");
+    *count = w->impl.pins().list<phx_slider>().count();
     return PHX_OK;
 }
 

@@ -1,7 +1,7 @@
 """The cost of the pin pass (include/phyx_amd.h PINS): a synchronised World::Update of one world of hanging chains, with and without
 its pins, on the same build.
 
-    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--ropes] [--hinges] [--only WORLD] [--import-from DIR]
+    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--ropes] [--hinges] [--rails] [--only WORLD] [--import-from DIR]
 
 The world: a ground and `chains` chains of `links` links (boxes of 2 x 8, 10 apart), each hung from a world pin, side by side.  The
 pinned world runs under gravity (the pins carry the chains); the pinless twin has the same bodies and gravity 0, so that they stay
@@ -13,13 +13,18 @@ kernel trace of `--steps N --repeats 1` (k_solve_pins in the statistics), in a r
 
 --ropes adds a third world, "links" (include/phyx_amd.h LINKS): the pinned world plus one rope per chain from its last link to a world
 point beside and below it, half a unit short, so that every rope is taut: 4096 more units in the same pass.  (`--links` was taken: it
-is the chains' length.)  --only pins|pinless|links|angles runs that world alone, for a kernel trace in which k_solve_pins is one world's.
+is the chains' length.)  --only pins|pinless|links|angles|sliders runs that world alone, for a kernel trace in which k_solve_pins is one world's.
 
 --hinges adds the world "angles" (include/phyx_amd.h ANGLES): the pinned world plus one limit per pin, [0, 0.6] rad on the angle of
 each link against the one above it (the first: against the world).  A chain that hangs straight has theta = 0 = lower exactly, so
 every limit is engaged on every step with C = 0 and goes through its whole arithmetic while the chains hang as still as in the
 pinned world - as many angle units again as pins, in the same components.  (A lower limit above 0 bends every joint against
 gravity and the chains writhe: 0.01 rad on the CPU spec at 32 sweeps.)
+
+--rails adds the world "sliders" (include/phyx_amd.h SLIDERS): the pinned world plus one slider per link, its centre on a vertical world
+rail through where it hangs, limited to [0, 5] along it.  A chain that hangs still has s = 0 = lower and t . e = 0 exactly, so on
+every step row P and the lower stop are both engaged with C = 0 and go through their whole arithmetic while the chains hang as still
+as in the pinned world - as many slider units again as pins, in the same components.
 """
 import argparse
 import json
@@ -31,7 +36,7 @@ import time
 import numpy as np
 
 
-def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False, hinges=False):
+def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False, hinges=False, rails=False):
     pw = phyx_amd.World(0, gravity=-200.0 if pinned else 0.0)
     pw.AddBody((0.0, 0.0), 0.0, (8.0 * chains + 100.0, 10.0), static=True)
     rows = np.zeros((chains * links, 5), dtype=np.float32)
@@ -72,6 +77,14 @@ def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False, hinges=Fal
         h["body2"] = np.where(k == 0, -1, body - 1)
         h["lower"], h["upper"] = 0.0, 0.6
         pw.add_angles(h)
+    if rails:
+        from phyx_amd.api import slider_dtype
+        r = np.zeros(chains * links, dtype=slider_dtype)
+        r["body1"], r["body2"] = 1 + np.arange(chains * links), -1
+        r["anchor2"][:, 0], r["anchor2"][:, 1] = rows[:, 0], rows[:, 1]
+        r["axis"] = (0.0, 1.0)
+        r["lower"], r["upper"] = 0.0, 5.0
+        pw.add_sliders(r)
     return pw
 
 
@@ -95,14 +108,15 @@ def main():
     ap.add_argument("--no-pins", action="store_true")
     ap.add_argument("--ropes", action="store_true", help="also time the pinned world with one taut rope per chain (the 'links' world)")
     ap.add_argument("--hinges", action="store_true", help="also time the pinned world with one engaged limit per pin (the 'angles' world)")
-    ap.add_argument("--only", choices=("pins", "pinless", "links", "angles"), default=None, help="run this world alone")
+    ap.add_argument("--rails", action="store_true", help="also time the pinned world with one engaged slider per link (the 'sliders' world)")
+    ap.add_argument("--only", choices=("pins", "pinless", "links", "angles", "sliders"), default=None, help="run this world alone")
     ap.add_argument("--import-from", default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.import_from) if a.import_from else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import phyx_amd
     cfg = phyx_amd.Configuration(phyx_amd.SOLVE_AVX2, phyx_amd.ISLAND_MULTIPLE_SLOPPY, 15, 15)
-    want = [a.only] if a.only else ([] if a.no_pins else ["pins"]) + ["pinless"] + (["links"] if a.ropes else []) + (["angles"] if a.hinges else [])
-    worlds = {name: build(phyx_amd, a.chains, a.links, name != "pinless", ropes=(name == "links"), hinges=(name == "angles")) for name in want}
+    want = [a.only] if a.only else ([] if a.no_pins else ["pins"]) + ["pinless"] + (["links"] if a.ropes else []) + (["angles"] if a.hinges else []) + (["sliders"] if a.rails else [])
+    worlds = {name: build(phyx_amd, a.chains, a.links, name != "pinless", ropes=(name == "links"), hinges=(name == "angles"), rails=(name == "sliders")) for name in want}
     for name, pw in worlds.items():
         if name != "pinless":
             pw.pin_iterations = a.iterations
@@ -121,6 +135,9 @@ def main():
         if name == "angles":
             imp = pw.angles()["impulse"]
             out.update(angles=pw.angle_count(), angle_impulse_max=float(np.abs(imp).max()))
+        if name == "sliders":
+            got = pw.sliders()
+            out.update(sliders=pw.slider_count(), slider_impulse_max=float(np.abs(got["impulse"]).max()), slider_axis_impulse_max=float(np.abs(got["axis_impulse"]).max()))
         if name != "pinless":
             s = pw.pin_schedule()
             out.update(pins=pw.pin_count(), lds_groups=s["lds_groups"], groups=len(s["group_offsets"]) - 1, classes=len(s["class_offsets"]) - 1,
