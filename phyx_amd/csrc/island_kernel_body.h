@@ -24,6 +24,7 @@
     if (iv.next_ctl && blockIdx.x == 0) {                 // first kernel of its solve: the NEXT solve's control set (two sets alternate)
         if (threadIdx.x < ISL_STAT_SLOTS) { iv.next_visits[threadIdx.x] = 0ull; iv.next_executed[2 * threadIdx.x] = 0; iv.next_executed[2 * threadIdx.x + 1] = 0; }
         if (threadIdx.x == 0) { *iv.next_ctl = 0ull; iv.next_visits[ISL_STAT_SLOTS] = ~0ull; iv.next_visits[ISL_STAT_SLOTS + 1] = 0ull; }
+        if (threadIdx.x < STAMP_END_SHARDS) iv.next_visits[ISL_STAT_SLOTS + STAMP_END_BASE + threadIdx.x * STAMP_END_STRIDE] = 0ull;
         if (threadIdx.x < ISL_SHARDS) iv.next_shards[threadIdx.x * ISL_SHARD_STRIDE] = 0ull;
     }
     if (iv.stamp_begin) solve_stamp_begin(v.stamps);      // (no HBM group in front of this launch: it is the solve's first kernel)
@@ -405,13 +406,26 @@
         __builtin_nontemporal_store(q1.accN, &out.normal_accumulated_impulse);
         __builtin_nontemporal_store(q1.accF, &out.friction_accumulated_impulse);
     }
+    // FinishBodies (ref: Solver.cpp:488-492), dynamic bodies only.  A group whose displacement half was skipped (disp_quiet, above)
+    // leaves its displacing velocities alone: by that proof every word of them is the +0 it loaded, and the fourth word is 0 in
+    // every record (body_view.h) — the stores would put back, bit for bit, what is there (cfg 2: every group, 3.1 MB a launch).
+    if (disp_quiet) {                                      // (workgroup-uniform)
 #pragma unroll
-    for (int k = 0; k < BI; ++k) {                         // FinishBodies (ref: Solver.cpp:488-492), dynamic bodies only
-        const int i = tid + k * T;
-        if (body_id[k] < 0 || is_st[i]) continue;
-        const float4 a = body_load(imp, i), e = body_load(disp, i);
-        store_nt(&bv.vel[body_id[k]], a.x, a.y, a.z, 0.f);
-        store_nt(&bv.dvel[body_id[k]], e.x, e.y, e.z, 0.f);
+        for (int k = 0; k < BI; ++k) {
+            const int i = tid + k * T;
+            if (body_id[k] < 0 || is_st[i]) continue;
+            const float4 a = body_load(imp, i);
+            store_nt(&bv.vel[body_id[k]], a.x, a.y, a.z, 0.f);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < BI; ++k) {
+            const int i = tid + k * T;
+            if (body_id[k] < 0 || is_st[i]) continue;
+            const float4 a = body_load(imp, i), e = body_load(disp, i);
+            store_nt(&bv.vel[body_id[k]], a.x, a.y, a.z, 0.f);
+            store_nt(&bv.dvel[body_id[k]], e.x, e.y, e.z, 0.f);
+        }
     }
     if (iv.stamp_end) solve_stamp_end(v.stamps);           // (no HBM group behind this launch: it is the solve's last kernel)
     if (tid == 0) {

@@ -12,7 +12,7 @@ namespace phx {
 
 static inline int grid_for(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }
 
-constexpr int STATS_SET = 2 * ISL_STAT_SLOTS, VISITS_SET = ISL_STAT_SLOTS + 2, SHARDS_SET = ISL_SHARDS * ISL_SHARD_STRIDE;      // words of one control set in isl_.stats / isl_.visits / isl_.shards
+constexpr int STATS_SET = 2 * ISL_STAT_SLOTS, VISITS_SET = ISL_STAT_SLOTS + STAMP_WORDS, SHARDS_SET = ISL_SHARDS * ISL_SHARD_STRIDE;      // words of one control set in isl_.stats / isl_.visits / isl_.shards
 
 // ---------------------------------------------------------------------------------------------------
 
@@ -85,11 +85,12 @@ int DeviceSolver::init()
     PHX_HIP(hipMemsetAsync(hash_.p, 0, 2 * sizeof(unsigned long long), stream_));
     PHX_TRY(isl_.stats.reserve(2 * STATS_SET));
     PHX_HIP(hipMemsetAsync(isl_.stats.p, 0, 2 * STATS_SET * sizeof(int), stream_));
-    PHX_TRY(isl_.visits.reserve(2 * VISITS_SET));               // per set: the slots + the solve's two time stamps
+    PHX_TRY(isl_.visits.reserve(2 * VISITS_SET));               // per set: the slots + the solve's time stamps (begin, end, the island kernel's sharded end)
     {
-        unsigned long long init[2 * VISITS_SET] = {0};
+        static_assert(ISL_STAT_SLOTS % 16 == 0 && VISITS_SET % 16 == 0, "the sharded end stamps of either set sit on 128-byte lines of their own");
+        std::vector<unsigned long long> init(2 * VISITS_SET, 0ull);
         init[ISL_STAT_SLOTS] = ~0ull; init[VISITS_SET + ISL_STAT_SLOTS] = ~0ull;
-        PHX_HIP(hipMemcpyAsync(isl_.visits.p, init, sizeof init, hipMemcpyHostToDevice, stream_));
+        PHX_HIP(hipMemcpyAsync(isl_.visits.p, init.data(), init.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, stream_));
         PHX_HIP(hipStreamSynchronize(stream_));
     }
     PHX_TRY(isl_.shards.reserve(2 * SHARDS_SET));
@@ -606,7 +607,7 @@ int DeviceSolver::collect_stats(unsigned long long* extra, const unsigned long l
     if (extra) PHX_TRY(rb_.add(extra, extra_src, sizeof *extra, stream_));
     PHX_TRY(rb_.add(flags.data(), hbm_.flags.p, flags.size() * sizeof(int), stream_));
     PHX_TRY(rb_.add(isl_slots, isl_.stats.p + (size_t)hash_slot_ * STATS_SET, sizeof isl_slots, stream_));
-    unsigned long long stamps[2] = {0, 0};
+    unsigned long long stamps[STAMP_WORDS] = {0};          // (begin, end, and the island kernel's sharded end words: solver_kernels.h solve_stamp_end)
     PHX_TRY(rb_.add(visit_slots, isl_.visits.p + (size_t)hash_slot_ * VISITS_SET, sizeof visit_slots, stream_));
     PHX_TRY(rb_.add(stamps, isl_.visits.p + (size_t)hash_slot_ * VISITS_SET + ISL_STAT_SLOTS, sizeof stamps, stream_));
     PHX_TRY(with_build());
@@ -632,7 +633,11 @@ int DeviceSolver::collect_stats(unsigned long long* extra, const unsigned long l
     if (timed_sweeps_) {
         PHX_HIP(hipEventSynchronize(ev_sweep_end_));       // (already reached: the mailbox post ran behind it)
         PHX_HIP(hipEventElapsedTime(&ms, ev_sweep_begin_, ev_sweep_end_));
-    } else if (stamps[1] > stamps[0]) ms = (float)((double)(stamps[1] - stamps[0]) * 1e-5);      // 100 MHz ticks -> ms
+    } else {
+        unsigned long long end = stamps[1];                // the last workgroup to finish, whichever word it stamped
+        for (int k = 0; k < STAMP_END_SHARDS; ++k) end = std::max(end, stamps[STAMP_END_BASE + k * STAMP_END_STRIDE]);
+        if (end > stamps[0]) ms = (float)((double)(end - stamps[0]) * 1e-5);      // 100 MHz ticks -> ms
+    }
     stats_.device_ms = ms;
     stats_pending_ = false;
     return PHX_OK;

@@ -74,9 +74,19 @@ __device__ __forceinline__ int clamp_index(int i, int n) { return i < 0 ? 0 : (i
 
 // Device time of a solve (phx_solve_stats.device_ms) without HIP events — an event record is a barrier packet of its own that
 // idles the queue for ~5 us: the first kernel of the solve leaves the constant 100 MHz clock in stamps[0] (min), every workgroup
-// of its last kernel in stamps[1] (max).
+// of its last kernel in stamps[1] (max) — or, the island kernel, in one of STAMP_END_SHARDS words behind them, a 128-byte line each
+// (solve_stamp_end): the host takes the maximum over stamps[1] and those words (solver.hip collect_stats).
+constexpr int STAMP_END_SHARDS = ISL_SHARDS, STAMP_END_STRIDE = ISL_SHARD_STRIDE;      // workgroup b stamps word b % 16, like its arrival (island_view.h)
+constexpr int STAMP_END_BASE = 16;                      // first sharded word, counted from stamps[0]: the next 128-byte line
+constexpr int STAMP_WORDS = STAMP_END_BASE + STAMP_END_SHARDS * STAMP_END_STRIDE;      // stamps[0 .. STAMP_WORDS) belong to the solve's time stamps
 __device__ __forceinline__ void solve_stamp_begin(unsigned long long* stamps) { if (blockIdx.x == 0 && threadIdx.x == 0) atomicMin(&stamps[0], (unsigned long long)wall_clock64()); }
-__device__ __forceinline__ void solve_stamp_end(unsigned long long* stamps) { if (threadIdx.x == 0) atomicMax(&stamps[1], (unsigned long long)wall_clock64()); }
+// the island kernel's workgroups end microseconds apart and the slowest is the one that counts, so EVERY one of them stamps — but a
+// thousand atomics on ONE word take their turns and the launch cannot end before the last of them is served (1.4 - 1.7 us of cfg 2's
+// 54 us launch: profiles/island_phase_account.md)
+__device__ __forceinline__ void solve_stamp_end(unsigned long long* stamps)
+{
+    if (threadIdx.x == 0) atomicMax(&stamps[STAMP_END_BASE + (blockIdx.x % STAMP_END_SHARDS) * STAMP_END_STRIDE], (unsigned long long)wall_clock64());
+}
 // the same from a wide streaming kernel whose workgroups all end at once: every 32nd workgroup and the last one stamp (all of them firing at
 // the one word were ~25 of k_finish_bodies' 30 us in a 200k-body world: same-address atomics take their turns)
 __device__ __forceinline__ void solve_stamp_end_sparse(unsigned long long* stamps)
@@ -141,6 +151,7 @@ static __global__ void __launch_bounds__(HASH_T) k_topology_hash(const phx_conta
         if (i == 0) *cw.next_ctl = 0ull;
         if (i < ISL_STAT_SLOTS) { cw.next_visits[i] = 0ull; cw.next_executed[2 * i] = 0; cw.next_executed[2 * i + 1] = 0; }
         if (i == 0) { cw.next_visits[ISL_STAT_SLOTS] = ~0ull; cw.next_visits[ISL_STAT_SLOTS + 1] = 0ull; }      // the solve's time stamps (solve_stamp)
+        if (i < STAMP_END_SHARDS) cw.next_visits[ISL_STAT_SLOTS + STAMP_END_BASE + i * STAMP_END_STRIDE] = 0ull;
         if (i < ISL_SHARDS) cw.next_shards[i * ISL_SHARD_STRIDE] = 0ull;
         for (int k = i; k < cw.nflags; k += n) cw.flags[k] = 0;
         for (int k = i; k < cw.nsw; k += n) cw.sw[k] = 0u;
