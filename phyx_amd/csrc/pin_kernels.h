@@ -10,18 +10,19 @@
 //   k_pin_class      class for the warm start and per class and sweep (the fallback, not the fast path).
 // Static bodies (both inverses 0) and the world are read, never written: a class may share them among its lanes.
 //
-// Links (include/phyx_amd.h LINKS; the definition: tests/link_spec.py) are the pass's other kind of unit: unit u < npins is pin u, otherwise
-// link u - npins.  A link's prestep (link_prestep) fills the same registers under other names (PinRegs' unions), its sweep differs in the
-// delta only (link_delta) and ends in the same pin_apply.
-//
-// Angles (include/phyx_amd.h ANGLES; the definition: tests/angle_spec.py) are the third kind: unit u >= npins + nlinks is angle
-// u - npins - nlinks.  An angle has no anchors and no axis: its prestep (angle_prestep) keeps its two rows, the motor M and the
-// lock / spring / limit L, in the registers a pin uses for its anchors, and its sweep (angle_sweep) edits the two angular velocities only.
-//
-// Sliders (include/phyx_amd.h SLIDERS; the definition: tests/slider_spec.py) are the fourth kind: unit u >= npins + nlinks + nangles is
-// slider u - npins - nlinks - nangles.  A slider has three scalar rows (the motor M and the lock / spring / limit L along the rail, the
-// hard row P across it) at one point with two arms: its lane keeps a link's registers (ra, rb' = rb + e, n, row L) in PinRegs and seven
-// words more (RailRegs), which exist only in the instantiations with sliders.
+// The pass has four kinds of unit, in this order among the units: pins, links (include/phyx_amd.h LINKS; tests/link_spec.py), angles
+// (ANGLES; tests/angle_spec.py) and sliders (SLIDERS; tests/slider_spec.py).  Unit u is pin u, else link u - npins, else angle
+// u - npins - nlinks, else slider u - npins - nlinks - nangles: that ladder is written where a unit's record is first needed (the
+// prestep in k_solve_pins and in k_pin_prestep, unit_store, work_unpack) and nowhere else.  Every kind keeps its lane state in PinRegs:
+//   a link    fills the same registers under other names (PinRegs' unions); its sweep differs in the delta only (link_delta) and ends
+//             in the same pin_apply;
+//   an angle  has no anchors and no axis: its two rows, the motor M and the lock / spring / limit L, live in the registers a pin uses
+//             for its anchors, and its sweep (angle_sweep) edits the two angular velocities only;
+//   a slider  has three scalar rows (M and L along the rail, the hard row P across it) at one point with two arms: a link's registers
+//             (ra, rb' = rb + e, n, row L) in PinRegs and seven words more (RailRegs), which exist only in the instantiations with sliders.
+// What the kinds share is written once: the anchors (pin_anchors), a limited row's engagement (limit_row), the soft row (soft_row),
+// the two clamped accumulations (row_accumulate, motor_accumulate), a class step (unit_step) and the trailing group's record
+// (work_pack / work_unpack).
 #pragma once
 
 #include "pins.h"
@@ -34,10 +35,14 @@ struct PinSlot { int pin; int a, b; int colour; };      // LDS groups: a, b loca
 // an LDS group: its slots, its bodies in `group_bodies` (the static ones first), its classes
 struct PinGroup { int slot_begin, slot_end, body_begin, body_count; int first_dynamic, classes, pad0, pad1; };
 
+// A unit's kind and bits, the one encoding of both PinRegs::kind (the kind and its engaged rows: the bits of UNIT_KIND) and the
+// trailing group's PinWork::flags (those and the lane's four bools).  An angle is UNIT_ANGLE | its engaged rows, a slider UNIT_SLIDER | its rows L, M.
+enum : int { UNIT_PIN = 0, UNIT_LINK = 1, UNIT_ANGLE = 2, UNIT_ROW_L = 4, UNIT_ROW_M = 8, UNIT_SLIDER = 16, UNIT_KIND = 31,
+             UNIT_ACTIVE = 32, UNIT_WRITE_A = 64, UNIT_WRITE_B = 128, UNIT_CLAMPS = 256 };
+
 // what a lane keeps of its pin from the prestep on
 // (a link's names for the registers a pin calls otherwise: the axis n, gamma, 1/kinv, the scalar bias, the clamp's bounds, lambda;
 //  an angle's: row L as a link's with 1/(kinv + gamma) beside 1/kinv, row M's speed, its largest impulse and its accumulated impulse)
-enum : unsigned char { UNIT_PIN = 0, UNIT_LINK = 1, UNIT_ANGLE = 2, ANGLE_ROW_L = 4, ANGLE_ROW_M = 8, UNIT_SLIDER = 16 };      // (an angle: UNIT_ANGLE | its engaged rows; a slider: UNIT_SLIDER | its rows L, M)
 struct PinRegs {
     float rax, ray, rbx, rby;           // (an angle's inv_kg, speed, mmax, mlambda: the accessors below)
     union { float k11; float nx; };
@@ -50,8 +55,8 @@ struct PinRegs {
     union { float px; float lambda; };  // the accumulated impulse
     union { float py; float hi; };
     bool active, write_a, write_b;
-    unsigned char kind;                 // UNIT_PIN, UNIT_LINK, or UNIT_ANGLE with ANGLE_ROW_L / ANGLE_ROW_M where those rows are engaged
-    bool clamps;                        // a link or an angle whose impulse is clamped to [lo, hi] (a rope or a limit)
+    unsigned char kind;                 // UNIT_PIN, UNIT_LINK, or UNIT_ANGLE / UNIT_SLIDER with UNIT_ROW_L / UNIT_ROW_M where those rows are engaged
+    bool clamps;                        // a link, an angle or a slider whose row L is clamped to [lo, hi] (a rope or a limit)
     __device__ float& inv_kg() { return rax; }
     __device__ float& speed() { return ray; }
     __device__ float& mmax() { return rbx; }
@@ -62,13 +67,25 @@ struct PinRegs {
     __device__ float mlambda() const { return rby; }
     __device__ bool angle() const { return (kind & UNIT_ANGLE) != 0; }
     __device__ bool slider() const { return (kind & UNIT_SLIDER) != 0; }
-    __device__ bool lrow() const { return (kind & ANGLE_ROW_L) != 0; }
-    __device__ bool mrow() const { return (kind & ANGLE_ROW_M) != 0; }
+    __device__ bool lrow() const { return (kind & UNIT_ROW_L) != 0; }
+    __device__ bool mrow() const { return (kind & UNIT_ROW_M) != 0; }
 };
 
-// the rotated anchors, the inverse masses and who is written; -> C = (posB + rb) - (posA + ra).  `P` is a phx_pin or a phx_link.
-template <class P>
-__device__ __forceinline__ void pin_anchors(const P& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, PinRegs& r, float& cx, float& cy)
+// who is written: a body with a mass or an inertia (not the world, not a static body)
+__device__ __forceinline__ void pin_writes(PinRegs& r, int body2)
+{
+    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
+    r.write_b = body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+}
+
+// the rotated anchors and the inverse masses; -> the separation of the two anchor points pa = posA + ra and pb = posB + rb: a pin's or a
+// link's is pb - pa, a slider's (FROM_B) pa - pb, which is not the other negated: the two differ in the sign of a zero.
+// `P` is a phx_pin, a phx_link or a phx_slider.  w: where given, `axis` (a direction fixed in B) rotated with B.
+// (The subtraction and the axis stay in here, beside the loads: handed out as pa and pb and subtracted by the caller, or with B's frame
+// loaded again for the axis, the same arithmetic costs k_solve_pins 4 to 14 instructions more: DESIGN.md, the pin pass's tidy-up.)
+template <bool FROM_B = false, class P>
+__device__ __forceinline__ void pin_anchors(const P& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, PinRegs& r, float& cx, float& cy,
+                                            phx_vec2 axis = phx_vec2{0.f, 0.f}, phx_vec2* w = nullptr)
 {
     const float4 qa = mpos[p.body1], fa = frame[p.body1];
     r.ma = qa.x; r.ia = qa.y;
@@ -82,13 +99,13 @@ __device__ __forceinline__ void pin_anchors(const P& p, const float4* __restrict
         r.rbx = fb.x * p.anchor2.x + fb.z * p.anchor2.y;
         r.rby = fb.y * p.anchor2.x + fb.w * p.anchor2.y;
         pbx = qb.z + r.rbx; pby = qb.w + r.rby;
+        if (w) { w->x = fb.x * axis.x + fb.z * axis.y; w->y = fb.y * axis.x + fb.w * axis.y; }
     } else {
         r.mb = 0.f; r.ib = 0.f; r.rbx = 0.f; r.rby = 0.f;
         pbx = p.anchor2.x; pby = p.anchor2.y;
+        if (w) *w = axis;
     }
-    cx = pbx - pax; cy = pby - pay;
-    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
-    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+    if (FROM_B) { cx = pax - pbx; cy = pay - pby; } else { cx = pbx - pax; cy = pby - pay; }
 }
 
 __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta)
@@ -96,6 +113,7 @@ __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* _
     PinRegs r;
     float cx, cy;
     pin_anchors(p, mpos, frame, r, cx, cy);
+    pin_writes(r, p.body2);
     r.kind = UNIT_PIN; r.clamps = false;
     const float ms = r.ma + r.mb;
     r.k11 = (ms + (r.ia * r.ray) * r.ray) + (r.ib * r.rby) * r.rby;
@@ -113,30 +131,28 @@ __device__ __forceinline__ PinRegs pin_prestep(const phx_pin& p, const float4* _
 // the clamp, written as comparisons so that a NaN passes through
 __device__ __forceinline__ float link_clamp(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
-// tests/link_spec.py prestep, operation for operation
-__device__ __forceinline__ PinRegs link_prestep(const phx_link& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt)
+// Row L's engagement at position x between the bounds lo and hi: a row that does not clamp (`clamps` clear: a rod, a lock, a spring)
+// holds x at `rest`; one that clamps pushes one way only, at the bound x has reached, or is idle this step between the two.
+// Leaves clamps and the impulse's bounds in r and the position error in c, and clears `on` where the row is idle (a flag to clear,
+// not a result: so the idle arm stays a select beside the others, as it was in each of the three copies).
+__device__ __forceinline__ void limit_row(PinRegs& r, bool clamps, float x, float lo, float hi, float rest, float& c, bool& on)
 {
-    PinRegs r;
-    float dx, dy;
-    pin_anchors(p, mpos, frame, r, dx, dy);
-    r.kind = UNIT_LINK;
-    const float len = sqrtf(dx * dx + dy * dy);                 // (sqrtf: correctly rounded under the library's flags)
-    r.nx = dx / len; r.ny = dy / len;
-    const float cra = r.rax * r.ny - r.ray * r.nx, crb = r.rbx * r.ny - r.rby * r.nx;
-    float kinv = ((r.ma + r.mb) + (r.ia * cra) * cra) + (r.ib * crb) * crb;
-    r.active = len > 0x1p-10f && kinv > 0.f;
     const float inf = __builtin_inff();
-    float c;
-    r.clamps = p.min_length < p.max_length;
+    r.clamps = clamps;
     r.lo = -inf; r.hi = inf;
-    if (!r.clamps) c = len - p.min_length;
-    else if (len >= p.max_length) { c = len - p.max_length; r.hi = 0.f; }
-    else if (len <= p.min_length) { c = len - p.min_length; r.lo = 0.f; }
-    else { c = 0.f; r.active = false; }                        // idle this step
-    if (p.hertz > 0.f) {
+    if (!r.clamps) c = x - rest;
+    else if (x >= hi) { c = x - hi; r.hi = 0.f; }
+    else if (x <= lo) { c = x - lo; r.lo = 0.f; }
+    else { c = 0.f; on = false; }
+}
+
+// Row L's softness for the position error c: a spring (hertz > 0) gets gamma and its bias and kinv += gamma, a hard row the bias c beta
+__device__ __forceinline__ void soft_row(PinRegs& r, float& kinv, float c, float hertz, float damping_ratio, float beta, float dt)
+{
+    if (hertz > 0.f) {
         const float mass = 1.0f / kinv;
-        const float omega = 6.2831855f * p.hertz;
-        const float dmp = ((2.0f * mass) * p.damping_ratio) * omega;
+        const float omega = 6.2831855f * hertz;
+        const float dmp = ((2.0f * mass) * damping_ratio) * omega;
         const float k = (mass * omega) * omega;
         r.gamma = 1.0f / (dt * (dmp + dt * k));
         r.bias = ((c * dt) * k) * r.gamma;
@@ -145,6 +161,44 @@ __device__ __forceinline__ PinRegs link_prestep(const phx_link& p, const float4*
         r.gamma = 0.f;
         r.bias = c * beta;
     }
+}
+
+// row L's accumulation: lambda += d, clamped to [lo, hi] where the row clamps; -> the impulse actually applied
+__device__ __forceinline__ float row_accumulate(PinRegs& r, float d)
+{
+    if (r.clamps) {
+        const float next = link_clamp(r.lambda + d, r.lo, r.hi);
+        d = next - r.lambda;
+        r.lambda = next;
+    } else r.lambda = r.lambda + d;
+    return d;
+}
+
+// row M's accumulation at the relative speed cdot: towards `speed`, the accumulated impulse within [-mmax, mmax]; -> the impulse applied
+__device__ __forceinline__ float motor_accumulate(float& mlambda, float inv_k, float cdot, float speed, float mmax)
+{
+    const float next = link_clamp(mlambda + -(inv_k * (cdot - speed)), -mmax, mmax);
+    const float d = next - mlambda;
+    mlambda = next;
+    return d;
+}
+
+// tests/link_spec.py prestep, operation for operation
+__device__ __forceinline__ PinRegs link_prestep(const phx_link& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt)
+{
+    PinRegs r;
+    float dx, dy;
+    pin_anchors(p, mpos, frame, r, dx, dy);
+    pin_writes(r, p.body2);
+    r.kind = UNIT_LINK;
+    const float len = sqrtf(dx * dx + dy * dy);                 // (sqrtf: correctly rounded under the library's flags)
+    r.nx = dx / len; r.ny = dy / len;
+    const float cra = r.rax * r.ny - r.ray * r.nx, crb = r.rbx * r.ny - r.rby * r.nx;
+    float kinv = ((r.ma + r.mb) + (r.ia * cra) * cra) + (r.ib * crb) * crb;
+    r.active = len > 0x1p-10f && kinv > 0.f;
+    float c;
+    limit_row(r, p.min_length < p.max_length, len, p.min_length, p.max_length, p.min_length, c, r.active);
+    soft_row(r, kinv, c, p.hertz, p.damping_ratio, beta, dt);
     r.inv_k = 1.0f / kinv;
     r.lambda = r.active ? link_clamp(p.impulse, r.lo, r.hi) : 0.f;
     return r;
@@ -164,8 +218,7 @@ __device__ __forceinline__ PinRegs angle_prestep(const phx_angle& p, const float
         r.mb = qb.x; r.ib = qb.y;
         xbx = fb.x; xby = fb.y;
     }
-    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
-    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
+    pin_writes(r, p.body2);
     r.nx = 0.f; r.ny = 0.f;                                     // (no axis: the trailing group's work record carries every word)
     const float c = fa.x * xbx + fa.y * xby, s = fa.x * xby - fa.y * xbx;
     const float theta = (float)atan2((double)(-s), (double)c);
@@ -175,34 +228,17 @@ __device__ __forceinline__ PinRegs angle_prestep(const phx_angle& p, const float
     else if (phi < -3.1415927f) phi = phi + 6.2831855f;
     float kinv = r.ia + r.ib;
     const bool solvable = kinv > 0.f;
-    const float inf = __builtin_inff();
     float cl;
-    r.clamps = p.lower < p.upper;
     bool lrow = true;
-    r.lo = -inf; r.hi = inf;
-    if (!r.clamps) cl = phi;
-    else if (phi >= half) { cl = phi - half; r.hi = 0.f; }
-    else if (phi <= -half) { cl = phi + half; r.lo = 0.f; }
-    else { cl = 0.f; lrow = false; }                           // idle this step
+    limit_row(r, p.lower < p.upper, phi, -half, half, 0.f, cl, lrow);      // (phi is measured from the middle of the limits already)
     r.inv_k = 1.0f / kinv;
-    if (p.hertz > 0.f) {
-        const float mass = 1.0f / kinv;
-        const float omega = 6.2831855f * p.hertz;
-        const float dmp = ((2.0f * mass) * p.damping_ratio) * omega;
-        const float k = (mass * omega) * omega;
-        r.gamma = 1.0f / (dt * (dmp + dt * k));
-        r.bias = ((cl * dt) * k) * r.gamma;
-        kinv = kinv + r.gamma;
-    } else {
-        r.gamma = 0.f;
-        r.bias = cl * beta;
-    }
+    soft_row(r, kinv, cl, p.hertz, p.damping_ratio, beta, dt);
     r.inv_kg() = 1.0f / kinv;
     r.speed() = p.motor_speed;
     r.mmax() = p.max_torque * dt;
     const bool mrow = solvable && p.max_torque > 0.f;
     lrow = solvable && lrow;
-    r.kind = UNIT_ANGLE | (lrow ? ANGLE_ROW_L : 0) | (mrow ? ANGLE_ROW_M : 0);
+    r.kind = UNIT_ANGLE | (lrow ? UNIT_ROW_L : 0) | (mrow ? UNIT_ROW_M : 0);
     r.active = lrow || mrow;
     r.mlambda() = mrow ? link_clamp(p.motor_impulse, -r.mmax(), r.mmax()) : 0.f;
     r.lambda = lrow ? link_clamp(p.impulse, r.lo, r.hi) : 0.f;
@@ -226,22 +262,10 @@ __device__ __forceinline__ void angle_warm(const PinRegs& r, float4& va, float4&
 // one sweep of an angle: M, then L on the velocities M left; accumulates both
 __device__ __forceinline__ void angle_sweep(PinRegs& r, float4& va, float4& vb)
 {
-    if (r.mrow()) {
-        const float cdot = vb.z - va.z;
-        const float next = link_clamp(r.mlambda() + -(r.inv_k * (cdot - r.speed())), -r.mmax(), r.mmax());
-        const float d = next - r.mlambda();
-        r.mlambda() = next;
-        angle_apply(r, d, va, vb);
-    }
+    if (r.mrow()) angle_apply(r, motor_accumulate(r.mlambda(), r.inv_k, vb.z - va.z, r.speed(), r.mmax()), va, vb);
     if (r.lrow()) {
         const float cdot = vb.z - va.z;
-        float d = -(r.inv_kg() * ((cdot + r.bias) + r.gamma * r.lambda));
-        if (r.clamps) {
-            const float next = link_clamp(r.lambda + d, r.lo, r.hi);
-            d = next - r.lambda;
-            r.lambda = next;
-        } else r.lambda = r.lambda + d;
-        angle_apply(r, d, va, vb);
+        angle_apply(r, row_accumulate(r, -(r.inv_kg() * ((cdot + r.bias) + r.gamma * r.lambda))), va, vb);
     }
 }
 
@@ -254,28 +278,11 @@ struct NoRail {};                       // (the instantiations without sliders)
 __device__ __forceinline__ PinRegs slider_prestep(const phx_slider& p, const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, RailRegs& x)
 {
     PinRegs r;
-    const float4 qa = mpos[p.body1], fa = frame[p.body1];
-    r.ma = qa.x; r.ia = qa.y;
-    r.rax = fa.x * p.anchor1.x + fa.z * p.anchor1.y;
-    r.ray = fa.y * p.anchor1.x + fa.w * p.anchor1.y;
-    const float pax = qa.z + r.rax, pay = qa.w + r.ray;
-    float pbx, pby, wx, wy;
-    if (p.body2 >= 0) {
-        const float4 qb = mpos[p.body2], fb = frame[p.body2];
-        r.mb = qb.x; r.ib = qb.y;
-        r.rbx = fb.x * p.anchor2.x + fb.z * p.anchor2.y;
-        r.rby = fb.y * p.anchor2.x + fb.w * p.anchor2.y;
-        pbx = qb.z + r.rbx; pby = qb.w + r.rby;
-        wx = fb.x * p.axis.x + fb.z * p.axis.y;
-        wy = fb.y * p.axis.x + fb.w * p.axis.y;
-    } else {
-        r.mb = 0.f; r.ib = 0.f; r.rbx = 0.f; r.rby = 0.f;
-        pbx = p.anchor2.x; pby = p.anchor2.y;
-        wx = p.axis.x; wy = p.axis.y;
-    }
-    r.write_a = !(r.ma == 0.f && r.ia == 0.f);
-    r.write_b = p.body2 >= 0 && !(r.mb == 0.f && r.ib == 0.f);
-    const float ex = pax - pbx, ey = pay - pby;                 // (not pin_anchors' separation negated: that differs in the sign of a zero, which C = s - lower keeps)
+    float ex, ey;                                               // e = pa - pb: from B's anchor point to the carriage's
+    phx_vec2 w;                                                 // the rail: B's axis, rotated with B
+    pin_anchors<true>(p, mpos, frame, r, ex, ey, p.axis, &w);
+    const float wx = w.x, wy = w.y;
+    pin_writes(r, p.body2);
     const float len = sqrtf(wx * wx + wy * wy);                 // (sqrtf: correctly rounded under the library's flags)
     r.nx = wx / len; r.ny = wy / len;
     r.rbx = r.rbx + ex; r.rby = r.rby + ey;                     // rb' = rb + e: B's arm to the carriage's anchor point
@@ -289,34 +296,17 @@ __device__ __forceinline__ PinRegs slider_prestep(const phx_slider& p, const flo
     const bool solvable = r.active && kinv > 0.f;
     x.inv_kt = 1.0f / kinv_t;
     x.bias_t = ct * beta;
-    const float inf = __builtin_inff();
     float c;
-    r.clamps = p.lower < p.upper;
     bool lrow = true;
-    r.lo = -inf; r.hi = inf;
-    if (!r.clamps) c = s - p.lower;
-    else if (s >= p.upper) { c = s - p.upper; r.hi = 0.f; }
-    else if (s <= p.lower) { c = s - p.lower; r.lo = 0.f; }
-    else { c = 0.f; lrow = false; }                            // idle this step
+    limit_row(r, p.lower < p.upper, s, p.lower, p.upper, p.lower, c, lrow);
     r.inv_k = 1.0f / kinv;
-    if (p.hertz > 0.f) {
-        const float mass = 1.0f / kinv;
-        const float omega = 6.2831855f * p.hertz;
-        const float dmp = ((2.0f * mass) * p.damping_ratio) * omega;
-        const float k = (mass * omega) * omega;
-        r.gamma = 1.0f / (dt * (dmp + dt * k));
-        r.bias = ((c * dt) * k) * r.gamma;
-        kinv = kinv + r.gamma;
-    } else {
-        r.gamma = 0.f;
-        r.bias = c * beta;
-    }
+    soft_row(r, kinv, c, p.hertz, p.damping_ratio, beta, dt);
     x.inv_kng = 1.0f / kinv;
     x.speed = p.motor_speed;
     x.mmax = p.max_force * dt;
     const bool mrow = solvable && p.max_force > 0.f;
     lrow = solvable && lrow;
-    r.kind = UNIT_SLIDER | (lrow ? ANGLE_ROW_L : 0) | (mrow ? ANGLE_ROW_M : 0);
+    r.kind = UNIT_SLIDER | (lrow ? UNIT_ROW_L : 0) | (mrow ? UNIT_ROW_M : 0);
     x.mlambda = mrow ? link_clamp(p.motor_impulse, -x.mmax, x.mmax) : 0.f;
     r.lambda = lrow ? link_clamp(p.axis_impulse, r.lo, r.hi) : 0.f;
     x.plambda = r.active ? p.impulse : 0.f;
@@ -356,21 +346,13 @@ __device__ __forceinline__ void slider_sweep(PinRegs& r, RailRegs& x, float4& va
     float rx, ry;
     if (r.mrow()) {
         slider_rel(r, va, vb, rx, ry);
-        const float cdot = r.nx * rx + r.ny * ry;
-        const float next = link_clamp(x.mlambda + -(r.inv_k * (cdot - x.speed)), -x.mmax, x.mmax);
-        const float d = next - x.mlambda;
-        x.mlambda = next;
+        const float d = motor_accumulate(x.mlambda, r.inv_k, r.nx * rx + r.ny * ry, x.speed, x.mmax);
         slider_apply(r, d * r.nx, d * r.ny, va, vb);
     }
     if (r.lrow()) {
         slider_rel(r, va, vb, rx, ry);
         const float cdot = r.nx * rx + r.ny * ry;
-        float d = -(x.inv_kng * ((cdot + r.bias) + r.gamma * r.lambda));
-        if (r.clamps) {
-            const float next = link_clamp(r.lambda + d, r.lo, r.hi);
-            d = next - r.lambda;
-            r.lambda = next;
-        } else r.lambda = r.lambda + d;
+        const float d = row_accumulate(r, -(x.inv_kng * ((cdot + r.bias) + r.gamma * r.lambda)));
         slider_apply(r, d * r.nx, d * r.ny, va, vb);
     }
     slider_rel(r, va, vb, rx, ry);
@@ -380,6 +362,7 @@ __device__ __forceinline__ void slider_sweep(PinRegs& r, RailRegs& x, float4& va
     slider_apply(r, d * -r.ny, d * r.nx, va, vb);
 }
 // (the instantiations without sliders have no RailRegs and never get here)
+__device__ __forceinline__ PinRegs slider_prestep(const phx_slider&, const float4*, const float4*, float, float, NoRail&) { return PinRegs{}; }
 __device__ __forceinline__ void slider_warm(const PinRegs&, const NoRail&, float4&, float4&) {}
 __device__ __forceinline__ void slider_sweep(PinRegs&, NoRail&, float4&, float4&) {}
 
@@ -415,37 +398,69 @@ __device__ __forceinline__ void link_delta(PinRegs& r, const float4& va, const f
     const float vbx = vb.x + vb.z * r.rby, vby = vb.y - vb.z * r.rbx;
     const float vax = va.x + va.z * r.ray, vay = va.y - va.z * r.rax;
     const float cdot = r.nx * (vbx - vax) + r.ny * (vby - vay);
-    float d = -(r.inv_k * ((cdot + r.bias) + r.gamma * r.lambda));
-    if (r.clamps) {
-        const float next = link_clamp(r.lambda + d, r.lo, r.hi);
-        d = next - r.lambda;
-        r.lambda = next;
-    } else r.lambda = r.lambda + d;
+    const float d = row_accumulate(r, -(r.inv_k * ((cdot + r.bias) + r.gamma * r.lambda)));
     dx = d * r.nx; dy = d * r.ny;
 }
 
-// a unit's first impulse (the warm start) and its impulse of one sweep.  LINKS: the world has links; without them every kernel below
-// is the pins' alone, instruction for instruction what it was before there were links (a lane's branch on the kind costs the pass
-// 4 us of 30 on the world of DESIGN.md 5b, all pins: the launch is a chain of class steps, and each one pays for it).
-template <bool LINKS> __device__ __forceinline__ void unit_warm(const PinRegs& r, float& dx, float& dy)
-{
-    if (LINKS && r.kind == UNIT_LINK) { dx = r.lambda * r.nx; dy = r.lambda * r.ny; } else { dx = r.px; dy = r.py; }
-}
-template <bool LINKS> __device__ __forceinline__ void unit_delta(PinRegs& r, const float4& va, const float4& vb, float& dx, float& dy)
-{
-    if (LINKS && r.kind == UNIT_LINK) link_delta(r, va, vb, dx, dy); else pin_delta(r, va, vb, dx, dy);
-}
-// The angles' kernel arguments: a pack that is empty in a world without angles, so that the instantiations without them keep the
+// The later kinds' kernel arguments: a pack that is empty in a world without angles, so that the instantiations without them keep the
 // signature, the kernarg layout and the code they had before there were angles; with angles it is (phx_angle* angles, int nlinks).
 // The sliders' ride behind them the same way: (phx_slider* sliders, int nangles) and, in the trailing group's kernels, (RailWork* rail).
+// What a level lacks is a constant: the ladder's guards (kernels below) drop its arm at compile time.
 struct RailWork;
-struct NoAngles { static constexpr bool present = false; };
-struct AngleArgs { static constexpr bool present = true; phx_angle* angles; int nlinks; };
-struct SliderArgs { static constexpr bool present = true; phx_angle* angles; int nlinks; phx_slider* sliders; int nangles; RailWork* rail; };
+struct NoAngles { static constexpr phx_angle* angles = nullptr; static constexpr int nlinks = 0; static constexpr phx_slider* sliders = nullptr; static constexpr int nangles = 0; static constexpr RailWork* rail = nullptr; };
+struct AngleArgs { phx_angle* angles; int nlinks; static constexpr phx_slider* sliders = nullptr; static constexpr int nangles = 0; static constexpr RailWork* rail = nullptr; };
+struct SliderArgs { phx_angle* angles; int nlinks; phx_slider* sliders; int nangles; RailWork* rail; };
 __device__ __forceinline__ NoAngles angle_args() { return NoAngles{}; }
 __device__ __forceinline__ AngleArgs angle_args(phx_angle* angles, int nlinks) { return AngleArgs{angles, nlinks}; }
-__device__ __forceinline__ SliderArgs angle_args(phx_angle* angles, int nlinks, phx_slider* sliders, int nangles) { return SliderArgs{angles, nlinks, sliders, nangles, nullptr}; }
-__device__ __forceinline__ SliderArgs angle_args(phx_angle* angles, int nlinks, phx_slider* sliders, int nangles, RailWork* rail) { return SliderArgs{angles, nlinks, sliders, nangles, rail}; }
+__device__ __forceinline__ SliderArgs angle_args(phx_angle* angles, int nlinks, phx_slider* sliders, int nangles, RailWork* rail = nullptr) { return SliderArgs{angles, nlinks, sliders, nangles, rail}; }
+
+// The world's level, from the kernels' template arguments <bool LINKS, class... A>: which kinds the units may be.  LINKS: the world has
+// links; without them every kernel below is the pins' alone, instruction for instruction what it was before there were links (a lane's
+// branch on the kind costs the pass 4 us of 30 on the world of DESIGN.md 5b, all pins: the launch is a chain of class steps, and each
+// one pays for it).
+template <bool LINKS, class... A> struct PinLevel {
+    static constexpr bool links = LINKS, angles = sizeof...(A) > 0, sliders = sizeof...(A) > 2;
+    using Rail = std::conditional_t<sliders, RailRegs, NoRail>;
+};
+
+// One class step of a unit on its two velocities: the warm start (sweep clear: the unit's accumulated impulses) or one sweep
+template <class L>
+__device__ __forceinline__ void unit_step(PinRegs& r, typename L::Rail& x, float4& va, float4& vb, bool sweep)
+{
+    if (L::sliders && r.slider()) { if (sweep) slider_sweep(r, x, va, vb); else slider_warm(r, x, va, vb); }
+    else if (L::angles && r.angle()) { if (sweep) angle_sweep(r, va, vb); else angle_warm(r, va, vb); }
+    else {
+        float dx, dy;
+        if (L::links && r.kind == UNIT_LINK) { if (sweep) link_delta(r, va, vb, dx, dy); else { dx = r.lambda * r.nx; dy = r.lambda * r.ny; } }
+        else if (sweep) pin_delta(r, va, vb, dx, dy);
+        else { dx = r.px; dy = r.py; }
+        pin_apply(r, dx, dy, va, vb);
+    }
+}
+
+// ... of the lane's unit on its two bodies in the LDS table (`zero`: the world's velocity)
+template <class L>
+__device__ __forceinline__ void lds_step(PinRegs& r, typename L::Rail& x, const PinSlot& s, float4* sv, const float4& zero, bool sweep)
+{
+    float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
+    unit_step<L>(r, x, va, vb, sweep);
+    if (r.write_a) sv[s.a] = va;
+    if (r.write_b) sv[s.b] = vb;
+}
+
+// Unit u's accumulated impulses to its record (`pin` clear: a pin's stays as it is)
+template <class L, class Args>
+__device__ __forceinline__ void unit_store(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const Args& ang, int u, const PinRegs& r,
+                                           const typename L::Rail& x, bool pin = true)
+{
+    const int npl = npins + ang.nlinks, npla = npl + ang.nangles;
+    if constexpr (L::sliders)
+        if (r.slider()) { phx_slider& a = ang.sliders[u - npla]; a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda; return; }
+    if constexpr (L::angles)
+        if (r.angle()) { phx_angle& a = ang.angles[u - npl]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); return; }
+    if (L::links && r.kind == UNIT_LINK) links[u - npins].impulse = r.lambda;
+    else if (pin) pins[u].impulse = phx_vec2{r.px, r.py};
+}
 
 // The LDS layout: one float4 per local body.  A lane's two bodies are anywhere in the table, so a class step is a gather / scatter of
 // 16-byte granules (ds_read_b128 / ds_write_b128).  A 16-byte read is served in four groups of 16 lanes over the 64 banks: a group
@@ -458,8 +473,8 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
                                                                  const PinGroup* __restrict__ groups, const int* __restrict__ group_bodies, float4* __restrict__ vel,
                                                                  const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, int iterations, A... angle_pack)
 {
-    constexpr bool ANGLES = sizeof...(A) > 0, SLIDERS = sizeof...(A) > 2;
-    [[maybe_unused]] const auto ang = angle_args(angle_pack...);
+    using L = PinLevel<LINKS, A...>;
+    const auto ang = angle_args(angle_pack...);
     __shared__ float4 sv[PIN_BODIES];
     const PinGroup g = groups[blockIdx.x];
     const int* const bodies = group_bodies + g.body_begin;
@@ -471,113 +486,77 @@ static __global__ void __launch_bounds__(PIN_LANES) k_solve_pins(phx_pin* __rest
     const bool mine = slot < g.slot_end;
     PinSlot s = {0, 0, -1, -1};
     PinRegs r = {};
-    [[maybe_unused]] std::conditional_t<SLIDERS, RailRegs, NoRail> x = {};
+    [[maybe_unused]] typename L::Rail x = {};
     if (mine) {
         s = slots[slot];
-        if constexpr (SLIDERS) {
-            const int npl = npins + ang.nlinks, npla = npl + ang.nangles;
-            r = s.pin < npins ? pin_prestep(pins[s.pin], mpos, frame, beta)
-                : s.pin < npl ? link_prestep(links[s.pin - npins], mpos, frame, beta, dt)
-                : s.pin < npla ? angle_prestep(ang.angles[s.pin - npl], mpos, frame, beta, dt)
-                : slider_prestep(ang.sliders[s.pin - npla], mpos, frame, beta, dt, x);
-        } else if constexpr (ANGLES)
-            r = s.pin < npins ? pin_prestep(pins[s.pin], mpos, frame, beta)
-                : s.pin < npins + ang.nlinks ? link_prestep(links[s.pin - npins], mpos, frame, beta, dt)
-                : angle_prestep(ang.angles[s.pin - npins - ang.nlinks], mpos, frame, beta, dt);
-        else
-            r = (!LINKS || s.pin < npins) ? pin_prestep(pins[s.pin], mpos, frame, beta) : link_prestep(links[s.pin - npins], mpos, frame, beta, dt);
+        const int npl = npins + ang.nlinks, npla = npl + ang.nangles;
+        r = (!L::links || s.pin < npins) ? pin_prestep(pins[s.pin], mpos, frame, beta)
+            : (!L::angles || s.pin < npl) ? link_prestep(links[s.pin - npins], mpos, frame, beta, dt)
+            : (!L::sliders || s.pin < npla) ? angle_prestep(ang.angles[s.pin - npl], mpos, frame, beta, dt)
+            : slider_prestep(ang.sliders[s.pin - npla], mpos, frame, beta, dt, x);
     }
     const bool work = mine && r.active;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
     for (int c = 0; c < g.classes; ++c) {                                   // warm start, class by class
-        if (work && s.colour == c) {
-            float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-            if (SLIDERS && r.slider()) slider_warm(r, x, va, vb);
-            else if (ANGLES && r.angle()) angle_warm(r, va, vb);
-            else {
-                float dx, dy;
-                unit_warm<LINKS>(r, dx, dy);
-                pin_apply(r, dx, dy, va, vb);
-            }
-            if (r.write_a) sv[s.a] = va;
-            if (r.write_b) sv[s.b] = vb;
-        }
+        if (work && s.colour == c) lds_step<L>(r, x, s, sv, zero, false);
         __syncthreads();
     }
     for (int it = 0; it < iterations; ++it)
         for (int c = 0; c < g.classes; ++c) {
-            if (work && s.colour == c) {
-                float4 va = sv[s.a], vb = s.b >= 0 ? sv[s.b] : zero;
-                if (SLIDERS && r.slider()) slider_sweep(r, x, va, vb);
-                else if (ANGLES && r.angle()) angle_sweep(r, va, vb);
-                else {
-                    float dx, dy;
-                    unit_delta<LINKS>(r, va, vb, dx, dy);
-                    pin_apply(r, dx, dy, va, vb);
-                }
-                if (r.write_a) sv[s.a] = va;
-                if (r.write_b) sv[s.b] = vb;
-            }
+            if (work && s.colour == c) lds_step<L>(r, x, s, sv, zero, true);
             __syncthreads();
         }
     for (int i = g.first_dynamic + (int)threadIdx.x; i < g.body_count; i += PIN_LANES) vel[bodies[i]] = sv[i];
-    if (mine) {
-        if constexpr (SLIDERS) {
-            if (r.slider()) { phx_slider& a = ang.sliders[s.pin - npins - ang.nlinks - ang.nangles]; a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda; }
-            else if (r.angle()) { phx_angle& a = ang.angles[s.pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
-            else if (r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda;
-            else pins[s.pin].impulse = phx_vec2{r.px, r.py};
-        } else if constexpr (ANGLES) {
-            if (r.angle()) { phx_angle& a = ang.angles[s.pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
-            else if (r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda;
-            else pins[s.pin].impulse = phx_vec2{r.px, r.py};
-        } else {
-            if (LINKS && r.kind == UNIT_LINK) links[s.pin - npins].impulse = r.lambda; else pins[s.pin].impulse = phx_vec2{r.px, r.py};
-        }
-    }
+    if (mine) unit_store<L>(pins, links, npins, ang, s.pin, r, x);
 }
 
 // ---- the trailing group, out of HBM ----
-struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };      // flags: 1 active, 2 write a, 4 write b, 8 link, 16 clamps, 32 angle, 64 row L, 128 row M, 256 slider
+// what the prestep leaves of a unit (k11 .. biasy hold a link's nx, ny, gamma, inv_k, bias, lo: PinRegs' unions; flags: PinRegs' kind and
+// bools, the enum above; the accumulated impulses stay in the unit's record)
+struct PinWork { float rax, ray, rbx, rby, k11, k12, k22, inv_det, biasx, biasy, ma, ia, mb, ib; int flags; float hi; };
 // a slider's words beyond PinWork (which holds what a link's does, rb' in rbx / rby): a side array beside the work array, slot for slot,
-// which exists only in a world with sliders; its three impulses come from its record
+// which exists only in a world with sliders
 struct RailWork { float inv_kt, inv_kng, bias_t, speed, mmax, pad0, pad1, pad2; };
+static_assert(sizeof(PinWork) == 64 && sizeof(RailWork) == 32, "the trailing group's records");
 
-// (k11 .. biasy hold a link's nx, ny, gamma, inv_k, bias, lo: PinRegs' unions; px, py = the unit's accumulated impulse, a link's in px;
-//  an angle's two come from its record: impulse in px, motor_impulse in `rby`)
-template <bool ANGLES>
-__device__ __forceinline__ PinRegs pin_regs(const PinWork& w, float px, float py, float rby)
-{
-    PinRegs r;
-    r.rax = w.rax; r.ray = w.ray; r.rbx = w.rbx; r.rby = rby; r.k11 = w.k11; r.k12 = w.k12; r.k22 = w.k22; r.inv_det = w.inv_det;
-    r.biasx = w.biasx; r.biasy = w.biasy; r.ma = w.ma; r.ia = w.ia; r.mb = w.mb; r.ib = w.ib;
-    r.kind = (ANGLES && (w.flags & 32) != 0) ? (UNIT_ANGLE | ((w.flags & 64) ? ANGLE_ROW_L : 0) | ((w.flags & 128) ? ANGLE_ROW_M : 0)) : (w.flags & 8) != 0 ? UNIT_LINK : UNIT_PIN;
-    r.clamps = (w.flags & 16) != 0;
-    r.px = px; r.py = r.kind != UNIT_PIN ? w.hi : py;
-    r.active = (w.flags & 1) != 0; r.write_a = (w.flags & 2) != 0; r.write_b = (w.flags & 4) != 0;
-    return r;
-}
-
-// what the prestep leaves of a unit (`hi` and an angle's bits: the caller's)
-__device__ __forceinline__ PinWork pin_work(const PinRegs& r)
+// a lane's state into the trailing group's record `slot`
+template <class L>
+__device__ __forceinline__ void work_pack(const PinRegs& r, const typename L::Rail& x, PinWork* __restrict__ work, RailWork* __restrict__ rail, int slot)
 {
     PinWork w;
     w.rax = r.rax; w.ray = r.ray; w.rbx = r.rbx; w.rby = r.rby; w.k11 = r.k11; w.k12 = r.k12; w.k22 = r.k22; w.inv_det = r.inv_det;
     w.biasx = r.biasx; w.biasy = r.biasy; w.ma = r.ma; w.ia = r.ia; w.mb = r.mb; w.ib = r.ib;
-    w.flags = (r.active ? 1 : 0) | (r.write_a ? 2 : 0) | (r.write_b ? 4 : 0) | (r.kind == UNIT_LINK ? 8 : 0) | (r.clamps ? 16 : 0);
-    w.hi = 0.f;
-    return w;
+    w.flags = r.kind | (r.active ? UNIT_ACTIVE : 0) | (r.write_a ? UNIT_WRITE_A : 0) | (r.write_b ? UNIT_WRITE_B : 0) | (r.clamps ? UNIT_CLAMPS : 0);
+    w.hi = r.kind != UNIT_PIN ? r.hi : 0.f;                                // (a pin's second impulse word stays in its record)
+    work[slot] = w;
+    if constexpr (L::sliders)
+        if (r.slider()) rail[slot] = RailWork{x.inv_kt, x.inv_kng, x.bias_t, x.speed, x.mmax, 0.f, 0.f, 0.f};
 }
 
-// a slider's lane state out of the trailing group's records
-__device__ __forceinline__ PinRegs slider_regs(const PinWork& w, const RailWork& k, const phx_slider& a, RailRegs& x)
+// ... and out of it again, with unit u's accumulated impulses from its record
+template <class L, class Args>
+__device__ __forceinline__ PinRegs work_unpack(const PinWork& w, const phx_pin* __restrict__ pins, const phx_link* __restrict__ links, int npins, const Args& ang, int u, int slot,
+                                               typename L::Rail& x)
 {
-    PinRegs r = pin_regs<false>(w, a.axis_impulse, 0.f, w.rby);
-    r.kind = UNIT_SLIDER | ((w.flags & 64) ? ANGLE_ROW_L : 0) | ((w.flags & 128) ? ANGLE_ROW_M : 0);
+    PinRegs r;
+    r.rax = w.rax; r.ray = w.ray; r.rbx = w.rbx; r.rby = w.rby; r.k11 = w.k11; r.k12 = w.k12; r.k22 = w.k22; r.inv_det = w.inv_det;
+    r.biasx = w.biasx; r.biasy = w.biasy; r.ma = w.ma; r.ia = w.ia; r.mb = w.mb; r.ib = w.ib;
+    r.kind = (unsigned char)(w.flags & UNIT_KIND);
+    r.active = (w.flags & UNIT_ACTIVE) != 0; r.write_a = (w.flags & UNIT_WRITE_A) != 0; r.write_b = (w.flags & UNIT_WRITE_B) != 0; r.clamps = (w.flags & UNIT_CLAMPS) != 0;
     r.hi = w.hi;
-    x.inv_kt = k.inv_kt; x.inv_kng = k.inv_kng; x.bias_t = k.bias_t; x.speed = k.speed; x.mmax = k.mmax;
-    x.mlambda = a.motor_impulse; x.plambda = a.impulse;
+    const int npl = npins + ang.nlinks, npla = npl + ang.nangles;
+    if (L::sliders && r.slider()) {
+        if constexpr (L::sliders) {
+            const phx_slider& a = ang.sliders[u - npla];
+            const RailWork k = ang.rail[slot];
+            r.lambda = a.axis_impulse;
+            x.inv_kt = k.inv_kt; x.inv_kng = k.inv_kng; x.bias_t = k.bias_t; x.speed = k.speed; x.mmax = k.mmax;
+            x.mlambda = a.motor_impulse; x.plambda = a.impulse;
+        }
+    } else if (L::angles && r.angle()) { const phx_angle& a = ang.angles[u - npl]; r.lambda = a.impulse; r.mlambda() = a.motor_impulse; }
+    else if (L::links && r.kind == UNIT_LINK) r.lambda = links[u - npins].impulse;
+    else { const phx_vec2 p = pins[u].impulse; r.px = p.x; r.py = p.y; }
     return r;
 }
 
@@ -587,46 +566,18 @@ template <bool LINKS, class... A>
 static __global__ void __launch_bounds__(256) k_pin_prestep(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
                                                             const float4* __restrict__ mpos, const float4* __restrict__ frame, float beta, float dt, PinWork* __restrict__ work, A... angle_pack)
 {
-    constexpr bool ANGLES = sizeof...(A) > 0, SLIDERS = sizeof...(A) > 2;
-    [[maybe_unused]] const auto ang = angle_args(angle_pack...);
+    using L = PinLevel<LINKS, A...>;
+    const auto ang = angle_args(angle_pack...);
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const int pin = slots[k].pin;
-        if constexpr (SLIDERS) {
-            const int npla = npins + ang.nlinks + ang.nangles;
-            if (pin >= npla) {
-                RailRegs x;
-                phx_slider& a = ang.sliders[pin - npla];
-                const PinRegs r = slider_prestep(a, mpos, frame, beta, dt, x);
-                PinWork w = pin_work(r);
-                w.flags |= 256 | (r.lrow() ? 64 : 0) | (r.mrow() ? 128 : 0);
-                w.hi = r.hi;
-                work[k - begin] = w;
-                ang.rail[k - begin] = RailWork{x.inv_kt, x.inv_kng, x.bias_t, x.speed, x.mmax, 0.f, 0.f, 0.f};
-                a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda;
-                continue;
-            }
-        }
-        if constexpr (ANGLES) {
-            const PinRegs r = pin < npins ? pin_prestep(pins[pin], mpos, frame, beta)
-                              : pin < npins + ang.nlinks ? link_prestep(links[pin - npins], mpos, frame, beta, dt)
-                              : angle_prestep(ang.angles[pin - npins - ang.nlinks], mpos, frame, beta, dt);
-            const bool link = r.kind == UNIT_LINK, angle = r.angle();
-            PinWork w = pin_work(r);
-            if (angle) w.flags |= 32 | (r.lrow() ? 64 : 0) | (r.mrow() ? 128 : 0);
-            w.hi = (link || angle) ? r.hi : 0.f;
-            work[k - begin] = w;
-            if (angle) { phx_angle& a = ang.angles[pin - npins - ang.nlinks]; a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
-            else if (link) links[pin - npins].impulse = r.lambda;
-            else if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
-        } else {
-            const PinRegs r = (!LINKS || pin < npins) ? pin_prestep(pins[pin], mpos, frame, beta) : link_prestep(links[pin - npins], mpos, frame, beta, dt);
-            const bool link = r.kind == UNIT_LINK;
-            PinWork w = pin_work(r);
-            w.hi = (LINKS && link) ? r.hi : 0.f;
-            work[k - begin] = w;
-            if (LINKS && link) links[pin - npins].impulse = r.lambda;
-            else if (!r.active) pins[pin].impulse = phx_vec2{0.f, 0.f};
-        }
+        const int npl = npins + ang.nlinks, npla = npl + ang.nangles;
+        [[maybe_unused]] typename L::Rail x;
+        const PinRegs r = (!L::links || pin < npins) ? pin_prestep(pins[pin], mpos, frame, beta)
+                          : (!L::angles || pin < npl) ? link_prestep(links[pin - npins], mpos, frame, beta, dt)
+                          : (!L::sliders || pin < npla) ? angle_prestep(ang.angles[pin - npl], mpos, frame, beta, dt)
+                          : slider_prestep(ang.sliders[pin - npla], mpos, frame, beta, dt, x);
+        work_pack<L>(r, x, work, ang.rail, k - begin);
+        unit_store<L>(pins, links, npins, ang, pin, r, x, !r.active);
     }
 }
 
@@ -635,48 +586,19 @@ template <bool LINKS, class... A>
 static __global__ void __launch_bounds__(256) k_pin_class(phx_pin* __restrict__ pins, phx_link* __restrict__ links, int npins, const PinSlot* __restrict__ slots, int begin, int end,
                                                           int base, const PinWork* __restrict__ work, float4* __restrict__ vel, int sweep, A... angle_pack)
 {
-    constexpr bool ANGLES = sizeof...(A) > 0, SLIDERS = sizeof...(A) > 2;
-    [[maybe_unused]] const auto ang = angle_args(angle_pack...);
+    using L = PinLevel<LINKS, A...>;
+    const auto ang = angle_args(angle_pack...);
     for (int k = begin + blockIdx.x * blockDim.x + threadIdx.x; k < end; k += gridDim.x * blockDim.x) {
         const PinSlot s = slots[k];
         const PinWork w = work[k - base];
-        if (!(w.flags & 1)) continue;
-        const bool link = LINKS && (w.flags & 8) != 0;
-        if constexpr (SLIDERS) {
-            if (w.flags & 256) {                                              // a slider: its three impulses from its record
-                phx_slider& a = ang.sliders[s.pin - npins - ang.nlinks - ang.nangles];
-                RailRegs x;
-                PinRegs r = slider_regs(w, ang.rail[k - base], a, x);
-                float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (sweep) slider_sweep(r, x, va, vb); else slider_warm(r, x, va, vb);
-                if (r.write_a) vel[s.a] = va;
-                if (r.write_b) vel[s.b] = vb;
-                if (sweep) { a.impulse = x.plambda; a.axis_impulse = r.lambda; a.motor_impulse = x.mlambda; }
-                continue;
-            }
-        }
-        if constexpr (ANGLES) {
-            if (w.flags & 32) {                                               // an angle: both impulses from its record, w only
-                phx_angle& a = ang.angles[s.pin - npins - ang.nlinks];
-                PinRegs r = pin_regs<true>(w, a.impulse, 0.f, a.motor_impulse);
-                float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
-                if (sweep) angle_sweep(r, va, vb); else angle_warm(r, va, vb);
-                if (r.write_a) vel[s.a] = va;
-                if (r.write_b) vel[s.b] = vb;
-                if (sweep) { a.impulse = r.lambda; a.motor_impulse = r.mlambda(); }
-                continue;
-            }
-        }
-        float px, py = 0.f;
-        if (link) px = links[s.pin - npins].impulse; else { const phx_vec2 p = pins[s.pin].impulse; px = p.x; py = p.y; }
-        PinRegs r = pin_regs<false>(w, px, py, w.rby);
+        if (!(w.flags & UNIT_ACTIVE)) continue;
+        [[maybe_unused]] typename L::Rail x;
+        PinRegs r = work_unpack<L>(w, pins, links, npins, ang, s.pin, k - base, x);
         float4 va = vel[s.a], vb = s.b >= 0 ? vel[s.b] : make_float4(0.f, 0.f, 0.f, 0.f);
-        float dx, dy;
-        if (sweep) unit_delta<LINKS>(r, va, vb, dx, dy); else unit_warm<LINKS>(r, dx, dy);
-        pin_apply(r, dx, dy, va, vb);
+        unit_step<L>(r, x, va, vb, sweep != 0);
         if (r.write_a) vel[s.a] = va;
         if (r.write_b) vel[s.b] = vb;
-        if (sweep) { if (link) links[s.pin - npins].impulse = r.lambda; else pins[s.pin].impulse = phx_vec2{r.px, r.py}; }
+        if (sweep) unit_store<L>(pins, links, npins, ang, s.pin, r, x);
     }
 }
 

@@ -15,6 +15,7 @@
 // Sliders (include/phyx_amd.h SLIDERS) are the fourth kind, behind the angles: anchors as a pin's, limits and a motor as an angle's.
 #pragma once
 
+#include <tuple>
 #include <type_traits>
 
 #include "body_view.h"
@@ -30,8 +31,11 @@ constexpr int PIN_MAX_ITERATIONS = 64;
 void build_pin_schedule(const int32_t* body1, const int32_t* body2, int count, const unsigned char* is_static, int nb, int group_pins, Schedule& out);
 
 // what the calls know of a record: its nouns, the C calls' names, and `check`: entry k of an add beyond the body rules (the floats
-// that must be finite, then the record's own rules)
+// that must be finite, then the record's own rules); of a kind with limits and a motor also the name of the motor's bound
 template <class P> struct UnitKind;
+// the rules of a limited row's bounds and of a motor's two values (`P`: phx_angle or phx_slider): an add's, and phx_world_set_*_limits' / _motors'
+template <class P> int check_limits(const char* what, int k, float lower, float upper, float hertz);
+template <class P> int check_motor(const char* what, int k, float speed, float bound);
 template <> struct UnitKind<phx_pin> {
     static constexpr const char* noun = "pin";
     static constexpr const char* plural = "pins";
@@ -50,18 +54,16 @@ template <> struct UnitKind<phx_angle> {
     static constexpr const char* noun = "angle";
     static constexpr const char* plural = "angles";
     static constexpr const char* add = "phx_world_add_angles", *remove = "phx_world_remove_angles", *get = "phx_world_get_angles";      // (no anchors to set)
+    static constexpr const char* set_limits = "phx_world_set_angle_limits", *set_motors = "phx_world_set_angle_motors", *motor_bound = "max_torque";
     static int check(const char* what, int k, const phx_angle& p);
-    static int check_limits(const char* what, int k, float lower, float upper, float hertz);      // (also phx_world_set_angle_limits' rule)
-    static int check_motor(const char* what, int k, float speed, float max_torque);               // (also phx_world_set_angle_motors')
 };
 
 template <> struct UnitKind<phx_slider> {
     static constexpr const char* noun = "slider";
     static constexpr const char* plural = "sliders";
     static constexpr const char* add = "phx_world_add_sliders", *remove = "phx_world_remove_sliders", *set_anchors = "phx_world_set_slider_anchors", *get = "phx_world_get_sliders";
+    static constexpr const char* set_limits = "phx_world_set_slider_limits", *set_motors = "phx_world_set_slider_motors", *motor_bound = "max_force";
     static int check(const char* what, int k, const phx_slider& p);
-    static int check_limits(const char* what, int k, float lower, float upper, float hertz);      // (also phx_world_set_slider_limits' rule)
-    static int check_motor(const char* what, int k, float speed, float max_force);                // (also phx_world_set_slider_motors')
 };
 
 // the fields an edit between steps writes, `width` floats per record: on the host list and, by k_unit_fields, on the device copy
@@ -87,6 +89,7 @@ struct MotorFields {
 // a list of records `P` (phx_pin, phx_link, phx_angle, phx_slider: body1, body2 first; the impulses the device's once uploaded)
 template <class P> class UnitList {
 public:
+    using record = P;
     int count() const { return (int)host_.size(); }
     bool on_device() const { return !dirty_ && !host_.empty(); }
     const std::vector<P>& host() const { return host_; }                      // (impulses: only after fetch)
@@ -112,30 +115,30 @@ private:
 class PinSet {
 public:
     int configure_from_env();            // PHX_PIN_GROUP_PINS
-    template <class P> UnitList<P>& list()
+    template <class P> UnitList<P>& list() { return std::get<UnitList<P>>(lists_); }
+    template <class P> const UnitList<P>& list() const { return std::get<UnitList<P>>(lists_); }
+    // f(list) for the four lists in the order of the kinds among the pass's units, up to the first that fails
+    template <class F> int each_list(F f)
     {
-        if constexpr (std::is_same_v<P, phx_pin>) return pins_;
-        else if constexpr (std::is_same_v<P, phx_link>) return links_;
-        else if constexpr (std::is_same_v<P, phx_angle>) return angles_;
-        else return sliders_;
+        int st = PHX_OK;
+        std::apply([&](auto&... l) { ((st = st != PHX_OK ? st : f(l)), ...); }, lists_);
+        return st;
     }
-    template <class P> const UnitList<P>& list() const { return const_cast<PinSet*>(this)->list<P>(); }
-    int units() const { return pins_.count() + links_.count() + angles_.count() + sliders_.count(); }      // the pass's units: the pins, then the links, then the angles, then the sliders
+    int units() const { return std::apply([](const auto&... l) { return (l.count() + ...); }, lists_); }      // the pass's units
     int group_pins() const { return group_pins_; }
     long long builds() const { return builds_; }
     int iterations = 8;
 
     // the calls (world.hip, "units") work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
     void units_changed() { sched_dirty_ = true; }
-    void clear() { pins_.clear(); links_.clear(); angles_.clear(); sliders_.clear(); sched_dirty_ = true; }
+    void clear() { each_list([](auto& l) { l.clear(); return PHX_OK; }); sched_dirty_ = true; }
     void statics_changed() { if (units()) sched_dirty_ = true; }             // ... and a change of the static set make the schedule stale
     // a removal of bodies compacted them through `d_remap` (old index -> new or -1): the units of removed bodies go, the rest are renumbered
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream);
     // snapshots: the device copies (list<P>().device()), current
-    int upload(hipStream_t stream) { PHX_TRY(pins_.upload(stream)); PHX_TRY(links_.upload(stream)); PHX_TRY(angles_.upload(stream)); return sliders_.upload(stream); }
-    // load: the lists := device arrays (queued; the host lists follow at once)
-    int adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
-                     const phx_slider* d_sliders, int slider_count, hipStream_t stream);
+    int upload(hipStream_t stream) { return each_list([&](auto& l) { return l.upload(stream); }); }
+    // load: a list := a device array (queued; the host list follows at once)
+    template <class P> int adopt_device(const P* d_src, int count, hipStream_t stream) { sched_dirty_ = true; return list<P>().adopt_device(d_src, count, stream); }
 
     // the schedule, built unless current
     int prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream);
@@ -144,10 +147,7 @@ public:
     int solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hipStream_t stream);
 
 private:
-    UnitList<phx_pin> pins_;
-    UnitList<phx_link> links_;
-    UnitList<phx_angle> angles_;
-    UnitList<phx_slider> sliders_;
+    std::tuple<UnitList<phx_pin>, UnitList<phx_link>, UnitList<phx_angle>, UnitList<phx_slider>> lists_;      // the kinds, in their order among the pass's units
     bool sched_dirty_ = true;
     int group_pins_ = 0;
     long long builds_ = 0;

@@ -202,24 +202,31 @@ int UnitKind<phx_angle>::check(const char* what, int k, const phx_angle& p)
 {
     PHX_TRY(check_finite(what, noun, k, {p.lower, p.upper, p.hertz, p.damping_ratio, p.motor_speed, p.max_torque, p.impulse, p.motor_impulse}));
     if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: angle %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
-    PHX_TRY(check_limits(what, k, p.lower, p.upper, p.hertz));
-    return check_motor(what, k, p.motor_speed, p.max_torque);
+    PHX_TRY(check_limits<phx_angle>(what, k, p.lower, p.upper, p.hertz));
+    return check_motor<phx_angle>(what, k, p.motor_speed, p.max_torque);
 }
 
-int UnitKind<phx_angle>::check_limits(const char* what, int k, float lower, float upper, float hertz)
+template <class P> int check_limits(const char* what, int k, float lower, float upper, float hertz)
 {
-    if (!std::isfinite(lower) || !std::isfinite(upper)) { set_error("%s: angle %d: a limit is not finite", what, k); return PHX_ERR_INVALID; }
-    if (!(lower <= upper)) { set_error("%s: angle %d: limits [%g, %g] are not lower <= upper", what, k, (double)lower, (double)upper); return PHX_ERR_INVALID; }
-    if (hertz > 0.f && lower != upper) { set_error("%s: angle %d: a spring (hertz %g) needs lower == upper", what, k, (double)hertz); return PHX_ERR_INVALID; }
+    const char* const noun = UnitKind<P>::noun;
+    if (!std::isfinite(lower) || !std::isfinite(upper)) { set_error("%s: %s %d: a limit is not finite", what, noun, k); return PHX_ERR_INVALID; }
+    if (!(lower <= upper)) { set_error("%s: %s %d: limits [%g, %g] are not lower <= upper", what, noun, k, (double)lower, (double)upper); return PHX_ERR_INVALID; }
+    if (hertz > 0.f && lower != upper) { set_error("%s: %s %d: a spring (hertz %g) needs lower == upper", what, noun, k, (double)hertz); return PHX_ERR_INVALID; }
     return PHX_OK;
 }
 
-int UnitKind<phx_angle>::check_motor(const char* what, int k, float speed, float max_torque)
+template <class P> int check_motor(const char* what, int k, float speed, float bound)
 {
-    if (!std::isfinite(speed) || !std::isfinite(max_torque)) { set_error("%s: angle %d: a motor value is not finite", what, k); return PHX_ERR_INVALID; }
-    if (max_torque < 0.f) { set_error("%s: angle %d: negative max_torque %g", what, k, (double)max_torque); return PHX_ERR_INVALID; }
+    const char* const noun = UnitKind<P>::noun;
+    if (!std::isfinite(speed) || !std::isfinite(bound)) { set_error("%s: %s %d: a motor value is not finite", what, noun, k); return PHX_ERR_INVALID; }
+    if (bound < 0.f) { set_error("%s: %s %d: negative %s %g", what, noun, k, UnitKind<P>::motor_bound, (double)bound); return PHX_ERR_INVALID; }
     return PHX_OK;
 }
+
+template int check_limits<phx_angle>(const char*, int, float, float, float);
+template int check_limits<phx_slider>(const char*, int, float, float, float);
+template int check_motor<phx_angle>(const char*, int, float, float);
+template int check_motor<phx_slider>(const char*, int, float, float);
 
 int UnitKind<phx_slider>::check(const char* what, int k, const phx_slider& p)
 {
@@ -227,66 +234,37 @@ int UnitKind<phx_slider>::check(const char* what, int k, const phx_slider& p)
                                          p.motor_speed, p.max_force, p.impulse, p.axis_impulse, p.motor_impulse}));
     if (!(p.axis.x * p.axis.x + p.axis.y * p.axis.y > 0x1p-20f)) { set_error("%s: slider %d: axis (%g, %g) is too short to give a direction", what, k, (double)p.axis.x, (double)p.axis.y); return PHX_ERR_INVALID; }
     if (p.hertz < 0.f || p.damping_ratio < 0.f) { set_error("%s: slider %d: negative hertz or damping_ratio", what, k); return PHX_ERR_INVALID; }
-    PHX_TRY(check_limits(what, k, p.lower, p.upper, p.hertz));
-    PHX_TRY(check_motor(what, k, p.motor_speed, p.max_force));
+    PHX_TRY(check_limits<phx_slider>(what, k, p.lower, p.upper, p.hertz));
+    PHX_TRY(check_motor<phx_slider>(what, k, p.motor_speed, p.max_force));
     if (p.reserved != 0) { set_error("%s: slider %d: reserved must be 0", what, k); return PHX_ERR_INVALID; }
-    return PHX_OK;
-}
-
-int UnitKind<phx_slider>::check_limits(const char* what, int k, float lower, float upper, float hertz)
-{
-    if (!std::isfinite(lower) || !std::isfinite(upper)) { set_error("%s: slider %d: a limit is not finite", what, k); return PHX_ERR_INVALID; }
-    if (!(lower <= upper)) { set_error("%s: slider %d: limits [%g, %g] are not lower <= upper", what, k, (double)lower, (double)upper); return PHX_ERR_INVALID; }
-    if (hertz > 0.f && lower != upper) { set_error("%s: slider %d: a spring (hertz %g) needs lower == upper", what, k, (double)hertz); return PHX_ERR_INVALID; }
-    return PHX_OK;
-}
-
-int UnitKind<phx_slider>::check_motor(const char* what, int k, float speed, float max_force)
-{
-    if (!std::isfinite(speed) || !std::isfinite(max_force)) { set_error("%s: slider %d: a motor value is not finite", what, k); return PHX_ERR_INVALID; }
-    if (max_force < 0.f) { set_error("%s: slider %d: negative max_force %g", what, k, (double)max_force); return PHX_ERR_INVALID; }
     return PHX_OK;
 }
 
 int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
 {
-    PHX_TRY(pins_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
-    PHX_TRY(links_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
-    PHX_TRY(angles_.bodies_removed(d_remap, rb, stream, &sched_dirty_));
-    return sliders_.bodies_removed(d_remap, rb, stream, &sched_dirty_);
-}
-
-int PinSet::adopt_device(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
-                         const phx_slider* d_sliders, int slider_count, hipStream_t stream)
-{
-    sched_dirty_ = true;
-    PHX_TRY(pins_.adopt_device(d_pins, pin_count, stream));
-    PHX_TRY(links_.adopt_device(d_links, link_count, stream));
-    PHX_TRY(angles_.adopt_device(d_angles, angle_count, stream));
-    return sliders_.adopt_device(d_sliders, slider_count, stream);
+    return each_list([&](auto& l) { return l.bodies_removed(d_remap, rb, stream, &sched_dirty_); });
 }
 
 int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
 {
-    const int n = units(), np = pins_.count(), npl = np + links_.count(), npla = npl + angles_.count();
+    const int n = units();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
     if (!sched_dirty_) return PHX_OK;
     PHX_TRY(d_bits_.reserve((size_t)n));
-    PHX_TRY(pins_.statics(mpos, d_bits_.p, stream));
-    PHX_TRY(links_.statics(mpos, d_bits_.p + np, stream));
-    PHX_TRY(angles_.statics(mpos, d_bits_.p + npl, stream));
-    PHX_TRY(sliders_.statics(mpos, d_bits_.p + npla, stream));
-    // a unit's bodies: pin u, link u - np, angle u - npl, or slider u - npla
-    auto body1 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body1 : u < npl ? links_.host()[(size_t)(u - np)].body1 : u < npla ? angles_.host()[(size_t)(u - npl)].body1 : sliders_.host()[(size_t)(u - npla)].body1; };
-    auto body2 = [&](int u) { return u < np ? pins_.host()[(size_t)u].body2 : u < npl ? links_.host()[(size_t)(u - np)].body2 : u < npla ? angles_.host()[(size_t)(u - npl)].body2 : sliders_.host()[(size_t)(u - npla)].body2; };
+    // the units, kind behind kind: each list queues its records' static bits and appends their bodies
+    std::vector<int32_t> b1, b2;
+    b1.reserve((size_t)n); b2.reserve((size_t)n);
+    PHX_TRY(each_list([&](auto& l) -> int {
+        PHX_TRY(l.statics(mpos, d_bits_.p + b1.size(), stream));
+        for (const auto& p : l.host()) { b1.push_back(p.body1); b2.push_back(p.body2); }
+        return PHX_OK;
+    }));
     std::vector<unsigned> bits((size_t)n);
     PHX_TRY(rb.add(bits.data(), d_bits_.p, (size_t)n * sizeof(unsigned), stream));
     PHX_TRY(rb.wait(stream));
     std::vector<unsigned char> is_static((size_t)nb, 0);
-    std::vector<int32_t> b1((size_t)n), b2((size_t)n);
     for (int k = 0; k < n; ++k) {
-        b1[(size_t)k] = body1(k); b2[(size_t)k] = body2(k);
         if (bits[(size_t)k] & 1u) is_static[(size_t)b1[(size_t)k]] = 1;
         if (b2[(size_t)k] >= 0 && (bits[(size_t)k] & 2u)) is_static[(size_t)b2[(size_t)k]] = 1;
     }
@@ -335,7 +313,7 @@ int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream
     PHX_HIP(hipMemcpyAsync(d_tables_.p, blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
     PHX_HIP(hipStreamSynchronize(stream));                                  // (`blob` is a local)
     // (a world with sliders keeps their side records behind the work array: pin_kernels.h RailWork)
-    if (s.has_hbm_group()) PHX_TRY(d_work_.reserve((size_t)(s.hbm_end() - s.hbm_begin()) * (sizeof(PinWork) + (sliders_.count() ? sizeof(RailWork) : 0))));
+    if (s.has_hbm_group()) PHX_TRY(d_work_.reserve((size_t)(s.hbm_end() - s.hbm_begin()) * (sizeof(PinWork) + (list<phx_slider>().count() ? sizeof(RailWork) : 0))));
     sched_dirty_ = false;
     return PHX_OK;
 }
@@ -344,58 +322,49 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
 {
     if (!units()) return PHX_OK;
     PHX_TRY(prepare(bodies.s.mpos, nb, rb, stream));
-    phx_pin* const d_pins = pins_.device();
-    phx_link* const d_links = links_.device();
-    phx_angle* const d_angles = angles_.device();
-    phx_slider* const d_sliders = sliders_.device();
-    const int np = pins_.count(), nl = links_.count(), na = angles_.count();
+    phx_pin* const d_pins = list<phx_pin>().device();
+    phx_link* const d_links = list<phx_link>().device();
+    phx_angle* const d_angles = list<phx_angle>().device();
+    phx_slider* const d_sliders = list<phx_slider>().device();
+    const int np = list<phx_pin>().count(), nl = list<phx_link>().count(), na = list<phx_angle>().count(), ns = list<phx_slider>().count();
     const float beta = 0.2f / dt;
     const PinSlot* slots = reinterpret_cast<const PinSlot*>(d_tables_.p);
-    // a world without links runs the pins' own instantiation of each kernel: what it ran before there were links; one without angles
-    // what it ran before there were angles; one with angles the instantiation that knows all three kinds
-    // (whose kernels take the angles' two arguments behind the others': pin_kernels.h AngleArgs); one with sliders the instantiation
-    // that knows all four (the sliders' arguments behind the angles': SliderArgs)
-    const bool with_sliders = sliders_.count() > 0, with_angles = na > 0, with_links = nl > 0;
-    auto pick = [with_links](auto with, auto without) { return with_links ? with : without; };
-    const dim3 lds_grid(sched_.lds_groups), lds_block(PIN_LANES);
-    const PinGroup* const groups = reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_);
-    const int* const group_bodies = reinterpret_cast<const int*>(d_tables_.p + off_bodies_);
+    // The world's level, picked once: `launch(LINKS, the later kinds' kernel arguments...)` names the instantiation of a kernel that
+    // knows the kinds the world has.  A world without links runs the pins' own instantiation of each kernel: what it ran before there
+    // were links; one without angles what it ran before there were angles; one with angles the instantiation that knows three kinds
+    // (whose kernels take the angles' two arguments behind the others': pin_kernels.h AngleArgs); one with sliders the one that knows
+    // all four (the sliders' arguments behind the angles': SliderArgs, and in the trailing group's kernels the side array `rail...`).
+    auto level = [&](auto launch, auto... rail) {
+        if (ns) launch(std::true_type{}, d_angles, nl, d_sliders, na, rail...);
+        else if (na) launch(std::true_type{}, d_angles, nl);
+        else if (nl) launch(std::true_type{});
+        else launch(std::false_type{});
+    };
     const float4* const mpos = (const float4*)bodies.s.mpos, *const frame = (const float4*)bodies.frame;
     if (sched_.lds_groups) {
-        if (with_sliders)
-            hipLaunchKernelGGL((k_solve_pins<true, phx_angle*, int, phx_slider*, int>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
-                               mpos, frame, beta, dt, iterations, d_angles, nl, d_sliders, na);
-        else if (with_angles)
-            hipLaunchKernelGGL((k_solve_pins<true, phx_angle*, int>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
-                               mpos, frame, beta, dt, iterations, d_angles, nl);
-        else
-            hipLaunchKernelGGL(pick(k_solve_pins<true>, k_solve_pins<false>), lds_grid, lds_block, 0, stream, d_pins, d_links, np, slots, groups, group_bodies, bodies.s.vel,
-                               mpos, frame, beta, dt, iterations);
+        const PinGroup* const groups = reinterpret_cast<const PinGroup*>(d_tables_.p + off_groups_);
+        const int* const group_bodies = reinterpret_cast<const int*>(d_tables_.p + off_bodies_);
+        level([&](auto links, auto... later) {
+            hipLaunchKernelGGL((k_solve_pins<decltype(links)::value, decltype(later)...>), dim3(sched_.lds_groups), dim3(PIN_LANES), 0, stream, d_pins, d_links, np, slots, groups,
+                               group_bodies, bodies.s.vel, mpos, frame, beta, dt, iterations, later...);
+        });
     }
     if (hbm_classes_.size() > 1) {
         const int begin = hbm_classes_.front(), end = hbm_classes_.back();
         PinWork* work = reinterpret_cast<PinWork*>(d_work_.p);
         RailWork* const rail = reinterpret_cast<RailWork*>(work + (end - begin));      // (only a world with sliders has it)
-        if (with_sliders)
-            hipLaunchKernelGGL((k_pin_prestep<true, phx_angle*, int, phx_slider*, int, RailWork*>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame,
-                               beta, dt, work, d_angles, nl, d_sliders, na, rail);
-        else if (with_angles)
-            hipLaunchKernelGGL((k_pin_prestep<true, phx_angle*, int>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame, beta, dt, work, d_angles, nl);
-        else
-            hipLaunchKernelGGL(pick(k_pin_prestep<true>, k_pin_prestep<false>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end, mpos, frame, beta, dt, work);
+        level([&](auto links, auto... later) {
+            hipLaunchKernelGGL((k_pin_prestep<decltype(links)::value, decltype(later)...>), dim3(pgrid(end - begin)), dim3(256), 0, stream, d_pins, d_links, np, slots, begin, end,
+                               mpos, frame, beta, dt, work, later...);
+        }, rail);
         for (int sweep = 0; sweep <= iterations; ++sweep)
             for (size_t c = 0; c + 1 < hbm_classes_.size(); ++c) {
                 const int b = hbm_classes_[c], e = hbm_classes_[c + 1];
                 if (e <= b) continue;
-                if (with_sliders)
-                    hipLaunchKernelGGL((k_pin_class<true, phx_angle*, int, phx_slider*, int, RailWork*>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
-                                       (const PinWork*)work, bodies.s.vel, sweep, d_angles, nl, d_sliders, na, rail);
-                else if (with_angles)
-                    hipLaunchKernelGGL((k_pin_class<true, phx_angle*, int>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
-                                       (const PinWork*)work, bodies.s.vel, sweep, d_angles, nl);
-                else
-                    hipLaunchKernelGGL(pick(k_pin_class<true>, k_pin_class<false>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
-                                       (const PinWork*)work, bodies.s.vel, sweep);
+                level([&](auto links, auto... later) {
+                    hipLaunchKernelGGL((k_pin_class<decltype(links)::value, decltype(later)...>), dim3(pgrid(e - b)), dim3(256), 0, stream, d_pins, d_links, np, slots, b, e, begin,
+                                       (const PinWork*)work, bodies.s.vel, sweep, later...);
+                }, rail);
             }
     }
     PHX_HIP(hipGetLastError());

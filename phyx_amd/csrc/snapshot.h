@@ -4,6 +4,8 @@
 // growth of the allocation, and the two events that order a save by one world against a load by another without a host wait.
 #pragma once
 
+#include <tuple>
+
 #include "body_view.h"
 #include "snapshot_blob.h"
 
@@ -42,21 +44,19 @@ public:
     // the world's pins (include/phyx_amd.h PINS) ride beside the blob's layout, which holds none: room first (nothing changes if that
     // fails), then a device copy queued behind the save, in front of the event the loads wait for
     // (a save that fails afterwards leaves the old ones whole).  The links (LINKS) ride the same way.
-    // The angles (ANGLES) are the third rider, the sliders (SLIDERS) the fourth.
-    int reserve_units(int pins, int links, int angles, int sliders, hipStream_t stream)
+    // The angles (ANGLES) are the third rider, the sliders (SLIDERS) the fourth: `P` is any of the four records, and the caller
+    // goes through the kinds (PinSet::each_list).
+    template <class P> int reserve_units(int n, hipStream_t stream) { return riders<P>().reserve(n, stream); }
+    template <class P> int save_units(const P* d_src, int count, hipStream_t stream)
     {
-        PHX_TRY(pins_.reserve(pins, stream)); PHX_TRY(links_.reserve(links, stream)); PHX_TRY(angles_.reserve(angles, stream)); return sliders_.reserve(sliders, stream);
+        riders<P>().count = count;
+        if (!count) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(riders<P>().buf.p, d_src, (size_t)count * sizeof(P), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
+        return PHX_OK;
     }
-    int save_units(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
-                   const phx_slider* d_sliders, int slider_count, hipStream_t stream);
-    const phx_pin* pins() const { return pins_.buf.p; }
-    int pin_count() const { return pins_.count; }
-    const phx_link* links() const { return links_.buf.p; }
-    int link_count() const { return links_.count; }
-    const phx_angle* angles() const { return angles_.buf.p; }
-    int angle_count() const { return angles_.count; }
-    const phx_slider* sliders() const { return sliders_.buf.p; }
-    int slider_count() const { return sliders_.count; }
+    template <class P> const P* units() const { return std::get<Riders<P>>(riders_).buf.p; }
+    template <class P> int unit_count() const { return std::get<Riders<P>>(riders_).count; }
     int blob_bytes(size_t* bytes) const;
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
@@ -66,14 +66,12 @@ private:
     int refuse_empty(const char* what) const;
     int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins, no links, no angles and no sliders
     template <class P> struct Riders {            // a list of records beside the blob
+        using record = P;
         DevBuf<P> buf; int count = 0;
         int reserve(int n, hipStream_t stream) { return n ? buf.reserve_keep((size_t)n, (size_t)count, stream) : PHX_OK; }      // (none: nothing is allocated)
     };
-    template <class P> int save_riders(Riders<P>& r, const P* d_src, int count, hipStream_t stream);
-    Riders<phx_pin> pins_;
-    Riders<phx_link> links_;
-    Riders<phx_angle> angles_;
-    Riders<phx_slider> sliders_;
+    std::tuple<Riders<phx_pin>, Riders<phx_link>, Riders<phx_angle>, Riders<phx_slider>> riders_;      // (the kinds in the pass's order)
+    template <class P> Riders<P>& riders() { return std::get<Riders<P>>(riders_); }
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

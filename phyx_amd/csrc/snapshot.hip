@@ -7,6 +7,7 @@
 // later load's stream waits for; a load records `loaded_`, which the next save into this snapshot waits for — a fork (world A saves,
 // world B loads) needs no host wait and no extra stream.  The host waits only in export, import and destroy.
 #include "snapshot.h"
+#include "pins.h"
 #include "snapshot_kernels.h"
 
 namespace phx {
@@ -45,30 +46,13 @@ int Snapshot::refuse_empty(const char* what) const
 
 int Snapshot::refuse_pins(const char* what) const
 {
-    if (!pins_.count && !links_.count && !angles_.count && !sliders_.count) return PHX_OK;
-    if (pins_.count) set_error("%s: the snapshot holds %d pins, which the blob (layout version 1) does not carry", what, pins_.count);
-    else if (links_.count) set_error("%s: the snapshot holds %d links, which the blob (layout version 1) does not carry", what, links_.count);
-    else if (angles_.count) set_error("%s: the snapshot holds %d angles, which the blob (layout version 1) does not carry", what, angles_.count);
-    else set_error("%s: the snapshot holds %d sliders, which the blob (layout version 1) does not carry", what, sliders_.count);
-    return PHX_ERR_STATE;
-}
-
-template <class P> int Snapshot::save_riders(Riders<P>& r, const P* d_src, int count, hipStream_t stream)
-{
-    r.count = count;
+    int count = 0;                                                          // the first kind that has riders names the refusal
+    const char* plural = nullptr;
+    auto look = [&](const auto& r) { if (!count && r.count) { count = r.count; plural = UnitKind<typename std::decay_t<decltype(r)>::record>::plural; } };
+    std::apply([&](const auto&... r) { (look(r), ...); }, riders_);
     if (!count) return PHX_OK;
-    PHX_HIP(hipMemcpyAsync(r.buf.p, d_src, (size_t)count * sizeof(P), hipMemcpyDeviceToDevice, stream));
-    PHX_HIP(hipEventRecord(saved_, stream));                                // (the event moves behind the copy)
-    return PHX_OK;
-}
-
-int Snapshot::save_units(const phx_pin* d_pins, int pin_count, const phx_link* d_links, int link_count, const phx_angle* d_angles, int angle_count,
-                         const phx_slider* d_sliders, int slider_count, hipStream_t stream)
-{
-    PHX_TRY(save_riders(pins_, d_pins, pin_count, stream));
-    PHX_TRY(save_riders(links_, d_links, link_count, stream));
-    PHX_TRY(save_riders(angles_, d_angles, angle_count, stream));
-    return save_riders(sliders_, d_sliders, slider_count, stream);
+    set_error("%s: the snapshot holds %d %s, which the blob (layout version 1) does not carry", what, count, plural);
+    return PHX_ERR_STATE;
 }
 
 // the largest walk of a launch: the bodies, or the granules of the largest array
@@ -167,7 +151,8 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     const size_t rest = (size_t)(l.total - SNAP_HEADER_BYTES);
     PHX_TRY(buf_.reserve(rest / 16));
     if (rest) PHX_HIP(hipMemcpy(buf_.p, static_cast<const unsigned char*>(blob) + SNAP_HEADER_BYTES, rest, hipMemcpyHostToDevice));
-    counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true; pins_.count = 0; links_.count = 0; angles_.count = 0; sliders_.count = 0;
+    counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true;
+    std::apply([](auto&... r) { ((r.count = 0), ...); }, riders_);
     return PHX_OK;
 }
 

@@ -200,10 +200,8 @@ public:
     template <class P> int set_unit_anchors(const int32_t* which, const float* anchors, int count);
     template <class P> int get_units(P* out, int cap);
     int set_link_lengths(const int32_t* which, const float* lengths, int count);
-    int set_angle_limits(const int32_t* which, const float* limits, int count);
-    int set_angle_motors(const int32_t* which, const float* motors, int count);
-    int set_slider_limits(const int32_t* which, const float* limits, int count);
-    int set_slider_motors(const int32_t* which, const float* motors, int count);
+    template <class P> int set_unit_limits(const int32_t* which, const float* limits, int count);      // (`P`: phx_angle or phx_slider)
+    template <class P> int set_unit_motors(const int32_t* which, const float* motors, int count);
     int set_pin_iterations(int n);
     int pin_schedule(const Schedule** out);
     int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
@@ -1043,13 +1041,9 @@ int World::save(Snapshot& s)
     v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
     PHX_TRY(pins_.upload(stream_));
-    const UnitList<phx_pin>& pins = pins_.list<phx_pin>();
-    const UnitList<phx_link>& links = pins_.list<phx_link>();
-    const UnitList<phx_angle>& angles = pins_.list<phx_angle>();
-    const UnitList<phx_slider>& sliders = pins_.list<phx_slider>();
-    PHX_TRY(s.reserve_units(pins.count(), links.count(), angles.count(), sliders.count(), stream_));
+    PHX_TRY(pins_.each_list([&](auto& l) { return s.reserve_units<typename std::decay_t<decltype(l)>::record>(l.count(), stream_); }));
     PHX_TRY(s.save(v, stream_));
-    return s.save_units(pins.device(), pins.count(), links.device(), links.count(), angles.device(), angles.count(), sliders.device(), sliders.count(), stream_);
+    return pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.count(), stream_); });
 }
 
 int World::load(Snapshot& s)
@@ -1086,7 +1080,10 @@ int World::load(Snapshot& s)
     // what set_state resets: the pair set becomes the saved manifolds' pairs, the schedule is rebuilt at the next step
     PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
     PHX_TRY(forget_step_history());
-    return pins_.adopt_device(s.pins(), s.pin_count(), s.links(), s.link_count(), s.angles(), s.angle_count(), s.sliders(), s.slider_count(), stream_);      // 6. add_pins, add_links, add_angles, add_sliders of the saved ones
+    return pins_.each_list([&](auto& l) {                                   // 6. add_pins, add_links, add_angles, add_sliders of the saved ones
+        using P = typename std::decay_t<decltype(l)>::record;
+        return pins_.adopt_device(s.units<P>(), s.unit_count<P>(), stream_);
+    });
 }
 
 int World::get_slab_state(const long long* global_index, int count, SlabState* out)
@@ -1560,7 +1557,9 @@ int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_
 int World::refuse_pins(const char* what)
 {
     if (!pins_.units()) return PHX_OK;
-    set_error("%s: the world holds %s, which a sharded world does not carry", what, pins_.list<phx_pin>().count() ? "pins" : pins_.list<phx_link>().count() ? "links" : pins_.list<phx_angle>().count() ? "angles" : "sliders");
+    const char* plural = nullptr;                                           // the first kind the world holds names the refusal
+    pins_.each_list([&](auto& l) { if (!plural && l.count()) plural = UnitKind<typename std::decay_t<decltype(l)>::record>::plural; return PHX_OK; });
+    set_error("%s: the world holds %s, which a sharded world does not carry", what, plural);
     return PHX_ERR_STATE;
 }
 
@@ -1657,40 +1656,24 @@ int World::set_link_lengths(const int32_t* which, const float* lengths, int coun
     return set_unit_fields<phx_link, LengthFields>(which, lengths, count);
 }
 
-int World::set_angle_limits(const int32_t* which, const float* limits, int count)
+template <class P>
+int World::set_unit_limits(const int32_t* which, const float* limits, int count)
 {
-    static const char* const what = "phx_world_set_angle_limits";
-    PHX_TRY(check_unit_indices<phx_angle>(what, which, limits, count));
-    const std::vector<phx_angle>& angles = pins_.list<phx_angle>().host();  // (bodies, limits, hertz, motor: always current)
+    const char* const what = UnitKind<P>::set_limits;
+    PHX_TRY(check_unit_indices<P>(what, which, limits, count));
+    const std::vector<P>& units = pins_.list<P>().host();                   // (bodies, limits, hertz, motor: always current)
     for (int k = 0; k < count; ++k)
-        PHX_TRY(UnitKind<phx_angle>::check_limits(what, k, limits[2 * k], limits[2 * k + 1], angles[(size_t)which[k]].hertz));
-    return set_unit_fields<phx_angle, LimitFields>(which, limits, count);
+        PHX_TRY(check_limits<P>(what, k, limits[2 * k], limits[2 * k + 1], units[(size_t)which[k]].hertz));
+    return set_unit_fields<P, LimitFields>(which, limits, count);
 }
 
-int World::set_angle_motors(const int32_t* which, const float* motors, int count)
+template <class P>
+int World::set_unit_motors(const int32_t* which, const float* motors, int count)
 {
-    static const char* const what = "phx_world_set_angle_motors";
-    PHX_TRY(check_unit_indices<phx_angle>(what, which, motors, count));
-    for (int k = 0; k < count; ++k) PHX_TRY(UnitKind<phx_angle>::check_motor(what, k, motors[2 * k], motors[2 * k + 1]));
-    return set_unit_fields<phx_angle, MotorFields>(which, motors, count);
-}
-
-int World::set_slider_limits(const int32_t* which, const float* limits, int count)
-{
-    static const char* const what = "phx_world_set_slider_limits";
-    PHX_TRY(check_unit_indices<phx_slider>(what, which, limits, count));
-    const std::vector<phx_slider>& sliders = pins_.list<phx_slider>().host();  // (bodies, anchors, axis, limits, hertz, motor: always current)
-    for (int k = 0; k < count; ++k)
-        PHX_TRY(UnitKind<phx_slider>::check_limits(what, k, limits[2 * k], limits[2 * k + 1], sliders[(size_t)which[k]].hertz));
-    return set_unit_fields<phx_slider, LimitFields>(which, limits, count);
-}
-
-int World::set_slider_motors(const int32_t* which, const float* motors, int count)
-{
-    static const char* const what = "phx_world_set_slider_motors";
-    PHX_TRY(check_unit_indices<phx_slider>(what, which, motors, count));
-    for (int k = 0; k < count; ++k) PHX_TRY(UnitKind<phx_slider>::check_motor(what, k, motors[2 * k], motors[2 * k + 1]));
-    return set_unit_fields<phx_slider, MotorFields>(which, motors, count);
+    const char* const what = UnitKind<P>::set_motors;
+    PHX_TRY(check_unit_indices<P>(what, which, motors, count));
+    for (int k = 0; k < count; ++k) PHX_TRY(check_motor<P>(what, k, motors[2 * k], motors[2 * k + 1]));
+    return set_unit_fields<P, MotorFields>(which, motors, count);
 }
 
 template <class P>
@@ -2348,13 +2331,13 @@ int phx_world_remove_angles(phx_world* w, const int32_t* angles, int32_t count)
 int phx_world_set_angle_limits(phx_world* w, const int32_t* angles, const float* limits, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.set_angle_limits(angles, limits, count);
+    return w->impl.set_unit_limits<phx_angle>(angles, limits, count);
 }
 
 int phx_world_set_angle_motors(phx_world* w, const int32_t* angles, const float* motors, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.set_angle_motors(angles, motors, count);
+    return w->impl.set_unit_motors<phx_angle>(angles, motors, count);
 }
 
 int phx_world_get_angles(phx_world* w, phx_angle* out, int32_t cap)
@@ -2392,13 +2375,13 @@ int phx_world_set_slider_anchors(phx_world* w, const int32_t* sliders, const flo
 int phx_world_set_slider_limits(phx_world* w, const int32_t* sliders, const float* limits, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.set_slider_limits(sliders, limits, count);
+    return w->impl.set_unit_limits<phx_slider>(sliders, limits, count);
 }
 
 int phx_world_set_slider_motors(phx_world* w, const int32_t* sliders, const float* motors, int32_t count)
 {
     PHX_REQUIRE(w, "null handle");
-    return w->impl.set_slider_motors(sliders, motors, count);
+    return w->impl.set_unit_motors<phx_slider>(sliders, motors, count);
 }
 
 int phx_world_get_sliders(phx_world* w, phx_slider* out, int32_t cap)

@@ -10,7 +10,7 @@ import pytest
 
 import phyx_amd
 from phyx_amd import Configuration, PhxError, scenes
-from phyx_amd.api import link_dtype, pin_dtype
+from phyx_amd.api import angle_dtype, link_dtype, pin_dtype, slider_dtype
 
 pytestmark = pytest.mark.gpu
 
@@ -238,3 +238,57 @@ def test_sharded_worlds_refuse_columns_in_these_words(built_lib):
     for w in worlds:
         w.StepEnd(DT)
     assert _snapshot(worlds[0]) == _snapshot(worlds[1]), "the refused calls left the rank as its twin"
+
+
+# ---- the limit and motor rules of angles and sliders: one rule for an add and for the set call, one text per kind ----
+LIMITED = {"angle": dict(dtype=angle_dtype, bound="max_torque", first_float=0,      # (`first_float`: value 0 of the add's finite check is `lower` behind this many floats)
+                         good=(0, 1, -0.5, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0), spring=(0, 1, 0.1, 0.1, 2.0, 0.5, 0.0, 0.0, 0.0, 0.0)),
+           "slider": dict(dtype=slider_dtype, bound="max_force", first_float=6,
+                          good=(0, 1, (0.0, 0.0), (0.0, 0.0), (1.0, 0.0), -0.5, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0),
+                          spring=(0, 1, (0.0, 0.0), (0.0, 0.0), (1.0, 0.0), 0.1, 0.1, 2.0, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0))}
+
+
+@pytest.mark.parametrize("kind", ["angle", "slider"])
+def test_limit_and_motor_rules_refuse_in_these_words(built_lib, kind):
+    """Every text of the limits' rule (not finite, not lower <= upper, a spring needs lower == upper) and of the motor's (not finite,
+    a negative bound), whole, through the add and through the set call, on one world of two bodies with one call per case.  An add
+    checks that every float is finite before it looks at a rule, so there the two `not finite` texts are the finite check's own."""
+    K = LIMITED[kind]
+    pw = phyx_amd.World(0, gravity=G)
+    pw.add_scene(scenes.stack(1, 1))
+    assert pw.counts()[0] == 2
+    getattr(pw, "add_%ss" % kind)(np.array([K["good"], K["spring"]], dtype=K["dtype"]))      # unit 0: limits, unit 1: a spring
+    records = lambda: getattr(pw, "%ss" % kind)().tobytes()
+    before = records()
+
+    def add(**fields):
+        p = np.array([K["good"], K["good"]], dtype=K["dtype"])
+        for f, v in fields.items():
+            p[f][1] = v
+        return getattr(pw.L, "phx_world_add_%ss" % kind)(pw.h, vp(p), 2, None)
+
+    def set_(what, which, values):
+        idx, v = np.array([which], dtype=np.int32), np.array([values], dtype=np.float32)
+        return getattr(pw.L, "phx_world_set_%s_%s" % (kind, what))(pw.h, vp(idx), vp(v), 1)
+
+    A = "phx_world_add_%ss: %s 1: " % (kind, kind)
+    L = "phx_world_set_%s_limits: %s 0: " % (kind, kind)
+    M = "phx_world_set_%s_motors: %s 0: " % (kind, kind)
+    bound, f0 = K["bound"], K["first_float"]
+    cases = [(lambda: add(lower=NAN), A + "value %d is not finite" % f0), (lambda: add(upper=np.inf), A + "value %d is not finite" % (f0 + 1)),
+             (lambda: add(lower=1.0), A + "limits [1, 0.5] are not lower <= upper"),
+             (lambda: add(hertz=2.0), A + "a spring (hertz 2) needs lower == upper"),
+             (lambda: add(motor_speed=np.inf), A + "value %d is not finite" % (f0 + 4)), (lambda: add(**{bound: NAN}), A + "value %d is not finite" % (f0 + 5)),
+             (lambda: add(**{bound: -1.0}), A + "negative %s -1" % bound),
+             (lambda: set_("limits", 0, [NAN, 1.0]), L + "a limit is not finite"), (lambda: set_("limits", 0, [1.0, np.inf]), L + "a limit is not finite"),
+             (lambda: set_("limits", 0, [3.0, 2.0]), L + "limits [3, 2] are not lower <= upper"),
+             (lambda: set_("limits", 1, [1.0, 2.0]), L + "a spring (hertz 2) needs lower == upper"),
+             (lambda: set_("motors", 0, [np.inf, 1.0]), M + "a motor value is not finite"), (lambda: set_("motors", 0, [1.0, NAN]), M + "a motor value is not finite"),
+             (lambda: set_("motors", 0, [1.0, -2.0]), M + "negative %s -2" % bound)]
+    for call, message in cases:
+        got = (call(), pw.L.phx_last_error().decode())
+        print(got)
+        assert got == (INVALID, message)
+        assert records() == before, "the world changed: " + message
+    assert set_("limits", 1, [0.25, 0.25]) == 0 and set_("motors", 0, [1.0, 0.0]) == 0, "a spring with lower == upper and a motor bound of 0 are fine"
+
