@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge crank piston clean
+.PHONY: build test test-gpu bench smoke example place bridge crank piston snap clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -31,6 +31,9 @@ crank: build                ## angles: a door with stops, a wheel on a motor, tw
 piston: build               ## sliders: a crank-slider, an elevator between its stops, a box on a spring slider (phx_world_add_sliders)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/piston.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/piston
 
+snap: build                 ## breaks: the bridge's hangers under a limit, crates dropped until they snap (phx_world_set_break_limits, phx_world_break_events)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/snap.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/snap
+
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap
 	rm -rf oracle/_ref

@@ -1008,6 +1008,50 @@ int  phx_world_set_slider_motors(phx_world* w, const int32_t* sliders, const flo
 int  phx_world_get_sliders(phx_world* w, phx_slider* out, int32_t cap);
 int  phx_world_slider_count(phx_world* w, int32_t* count);
 
+/* BREAKS — a joint that gives way: a bridge that collapses, a rope that snaps, a weld that shears.  Every unit of the pin pass (a pin, a
+ * link, an angle, a slider) has a break limit L, a float32 with 0 < L <= +inf; a new unit's is +inf: unbreakable.  The test runs on the
+ * device behind the pass, the broken unit is removed, and a queue of break events is all that comes down: nothing per step crosses PCIe
+ * but a 4-byte count, and the events of a step that has some.  tests/break_spec.py is the definition (scalar float32, every operation
+ * rounded on its own, correctly rounded sqrt) and the device matches it byte for byte.
+ *   - After the pin pass of a step with time step dt, the impulses the pass stored in the unit's record give its reaction impulse R:
+ *         pin     sqrtf(impulse.x impulse.x + impulse.y impulse.y)
+ *         link    fabsf(impulse)
+ *         angle   fabsf(impulse + motor_impulse)
+ *         slider  a = axis_impulse + motor_impulse;  sqrtf(impulse impulse + a a)       (rows P and L, M are orthogonal)
+ *     The unit BREAKS in that step iff R > L dt: one float32 product, a strict comparison, false for a NaN.  L is a force for pins, links
+ *     and sliders and a torque for angles.  An inactive or idle unit has stored 0 and never breaks.
+ *   - A broken unit has acted in the step it broke in: its impulses stay in the velocities and the contacts are solved on them.  Before
+ *     the next step's pass it is gone from its list, exactly as if phx_world_remove_<kind> had been called between the two steps: the
+ *     others keep their order, indices shift, the schedule is rebuilt (phx_world_pin_schedule_builds counts it).  The library applies
+ *     this lazily: at the next step, or at the top of the next call between steps that reads or changes units (the add, remove, set, get
+ *     and count calls of each kind, get_pin_schedule, the three calls below, save, remove_bodies / remove_outside).  A step that breaks
+ *     something costs what any change of the unit set costs, O(units) bytes; one that breaks nothing 4 bytes.
+ *   - Every break is one event; the events of one step are ordered by (kind, index) ascending.  index, body1, body2: the unit's index
+ *     in its list and its bodies, in the numbering that held during the step it broke in, before that step's removals.  reaction: R.
+ *     threshold: L dt.  step: the ordinal of that step among the steps taken since the previous successful phx_world_break_events (or
+ *     since the world was created, restored or loaded), from 0.  Call it once per step: then every event has step 0 and its index is an
+ *     index into the lists as they were before the call's step; a caller that lets several steps pass must apply the index shifts of
+ *     each step's removals, group by group in step order, to read the later groups' indices.
+ *   - phx_world_break_events has phx_world_contact_events' semantics: the events since the last successful call, in step order, then by
+ *     (kind, index); *total is always filled; total > cap returns PHX_ERR_CAPACITY and keeps the queue.
+ *   - The calls follow the unit calls' rules word for word: between steps only (PHX_ERR_STATE otherwise), everything checked before
+ *     anything is queued, PHX_ERR_INVALID leaves the world unchanged, an empty call is a no-op.  Checked: kind in [0, 3], the indices in
+ *     range and distinct, no NULL array with count > 0, every limit > 0 and not NaN (+inf is allowed: unbreakable again).
+ *     set_break_limits keeps the schedule and tests nothing by itself: a limit below the current load breaks at the next step.
+ *   - The other calls: remove_<kind>, remove_bodies and remove_outside carry the limits along with the records they keep; set_state
+ *     drops all limits and clears the event queue; save / load carry the limits (a forked world breaks where the original does), and a
+ *     load discards what the abandoned timeline had not settled yet and clears the event queue.  A world in which no finite limit was
+ *     ever set allocates nothing and launches nothing for this. */
+enum { PHX_UNIT_PIN = 0, PHX_UNIT_LINK = 1, PHX_UNIT_ANGLE = 2, PHX_UNIT_SLIDER = 3 };
+typedef struct { int32_t kind, index, body1, body2;   /* PHX_UNIT_*; the unit's index in its list and its bodies during the step it broke in */
+                 int32_t step;                        /* which step since the previous phx_world_break_events, from 0 */
+                 float reaction, threshold;           /* R > threshold = L dt */
+                 uint32_t reserved;                   /* 0 */
+} phx_break_event;                                    /* 32 B */
+int  phx_world_set_break_limits(phx_world* w, int32_t kind, const int32_t* units, const float* limits, int32_t count);
+int  phx_world_get_break_limits(phx_world* w, int32_t kind, float* out, int32_t cap);   /* cap >= the kind's count; +inf where none was set */
+int  phx_world_break_events(phx_world* w, phx_break_event* out, int32_t cap, int64_t* total);
+
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);
 /* handles owned by the world (for stage-level queries after an update) */

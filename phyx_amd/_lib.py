@@ -227,6 +227,9 @@ _SIGNATURES = {
     "phx_world_set_slider_motors": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_get_sliders": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_slider_count": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "phx_world_set_break_limits": (C.c_int, [_vp, _i32, _vp, _vp, _i32]),
+    "phx_world_get_break_limits": (C.c_int, [_vp, _i32, _vp, _i32]),
+    "phx_world_break_events": (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "phx_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "phx_snapshot_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "phx_snapshot_destroy": (None, [_vp]),

@@ -61,6 +61,10 @@ slider_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", 
                          ("hertz", "<f4"), ("damping_ratio", "<f4"), ("motor_speed", "<f4"), ("max_force", "<f4"), ("impulse", "<f4"), ("axis_impulse", "<f4"),
                          ("motor_impulse", "<f4"), ("reserved", "<u4")])      # phx_slider
 assert slider_dtype.itemsize == 72
+break_event_dtype = np.dtype([("kind", "<i4"), ("index", "<i4"), ("body1", "<i4"), ("body2", "<i4"), ("step", "<i4"), ("reaction", "<f4"), ("threshold", "<f4"),
+                              ("reserved", "<u4")])      # phx_break_event
+assert break_event_dtype.itemsize == 32
+UNIT_KINDS = ("pin", "link", "angle", "slider")      # PHX_UNIT_PIN ... PHX_UNIT_SLIDER
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
@@ -1098,6 +1102,47 @@ class World:
     def sliders(self):
         """Every slider as a slider_dtype array, with the impulses the last step accumulated."""
         return self._get(self.L.phx_world_get_sliders, slider_dtype, self.slider_count())
+
+    # ---- breaks (include/phyx_amd.h BREAKS; the specification: tests/break_spec.py) ----
+    @staticmethod
+    def _unit_kind(kind, what):
+        if isinstance(kind, str):
+            if kind not in UNIT_KINDS:
+                raise ValueError("%s: kind %r is none of %s" % (what, kind, ", ".join(UNIT_KINDS)))
+            return UNIT_KINDS.index(kind)
+        return int(kind)
+
+    def set_break_limits(self, kind, units, limits):
+        """The break limit limits[k] (> 0; inf: unbreakable, a new unit's) of unit units[k] of `kind` (0..3 or "pin", "link", "angle",
+        "slider"): a unit whose reaction impulse exceeds limit * dt after a step's pin pass is removed behind that step and reported by
+        break_events().  The schedule stays."""
+        idx = self._indices(units, "set_break_limits")
+        v = self._values(np.asarray(limits, dtype=np.float32).reshape(-1, 1), len(idx), 1, "set_break_limits")
+        check(self.L.phx_world_set_break_limits(self.h, self._unit_kind(kind, "set_break_limits"), _ptr(idx), _ptr(v), len(idx)))
+
+    def break_limits(self, kind):
+        """Every unit's break limit of `kind`, in index order: a float32 array (inf where none was set)."""
+        k = self._unit_kind(kind, "break_limits")
+        n = C.c_int32(0)
+        if 0 <= k < 4:
+            check(getattr(self.L, "phx_world_%s_count" % UNIT_KINDS[k])(self.h, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.float32)
+        check(self.L.phx_world_get_break_limits(self.h, k, _ptr(out), len(out)))
+        return out
+
+    def break_events(self):
+        """The breaks since the last call: a break_event_dtype array in step order, then by (kind, index); index and the bodies in the
+        numbering of the step the unit broke in.  Call it once per step (then every `step` is 0)."""
+        total = C.c_int64(0)
+        cap = 64
+        while True:
+            out = np.zeros(cap, dtype=break_event_dtype)
+            st = self.L.phx_world_break_events(self.h, _ptr(out), cap, C.byref(total))
+            if st != -4 or total.value <= cap:
+                break
+            cap = int(total.value)                                 # (grown to what the call reported; the queue was kept)
+        check(st)
+        return out[:total.value].copy()
 
     # ---- the per-body columns: collision filters, materials, body flags ----
     @staticmethod

@@ -26,6 +26,7 @@
 #pragma once
 
 #include "pins.h"
+#include "device_scan.h"
 
 namespace phx {
 
@@ -632,6 +633,118 @@ template <class P, class Fields>
 static __global__ void __launch_bounds__(256) k_unit_fields(const int* __restrict__ which, const float* __restrict__ values, int count, P* __restrict__ units)
 {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) Fields::write(units[which[k]], values + Fields::width * k);
+}
+
+// ---- breaks (include/phyx_amd.h BREAKS; the definition: tests/break_spec.py) ----
+// an edit of break limits (phx_world_set_break_limits) on the device copy of a list's limit column
+static __global__ void __launch_bounds__(256) k_unit_limits(const int* __restrict__ which, const float* __restrict__ values, int count, float* __restrict__ limits)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) limits[which[k]] = values[k];
+}
+
+// The lists that have a limit column, kind behind kind: limited unit i is a pin while i < end[0], else a link while i < end[1], and so
+// on (a list without a column counts no unit: its end is the end before it), so i ascending is (kind, index) ascending.
+struct BreakLists {
+    const phx_pin* pins; const phx_link* links; const phx_angle* angles; const phx_slider* sliders;
+    const float* pin_limits, *link_limits, *angle_limits, *slider_limits;
+    int end[4];
+};
+
+constexpr int BREAK_LANES = 1024;       // block_exclusive_scan_1024's workgroup
+constexpr int BREAK_BLOCKS = 1024;      // at most: the last workgroup scans the workgroups' counts in one block scan
+// the words beside the events: a count per workgroup (zero between launches), the ticket the workgroups draw as they finish (64 bits,
+// 8-byte aligned: the tickets drawn so far, and above them the events published so far), the step's event count
+enum : int { BREAK_TICKET = BREAK_BLOCKS, BREAK_COUNT = BREAK_BLOCKS + 2, BREAK_WORDS = BREAK_BLOCKS + 4 };
+
+// limited unit i after the pass: the reaction impulse R of the impulses in its record against L dt, break_spec.py operation for operation
+__device__ __forceinline__ bool unit_breaks(const BreakLists& l, int i, float dt, phx_break_event& e)
+{
+    float r, limit;
+    if (i < l.end[0]) {
+        const phx_pin& p = l.pins[i];
+        e.kind = PHX_UNIT_PIN; e.index = i; e.body1 = p.body1; e.body2 = p.body2;
+        r = sqrtf(p.impulse.x * p.impulse.x + p.impulse.y * p.impulse.y);
+        limit = l.pin_limits[i];
+    } else if (i < l.end[1]) {
+        const int k = i - l.end[0];
+        const phx_link& p = l.links[k];
+        e.kind = PHX_UNIT_LINK; e.index = k; e.body1 = p.body1; e.body2 = p.body2;
+        r = fabsf(p.impulse);
+        limit = l.link_limits[k];
+    } else if (i < l.end[2]) {
+        const int k = i - l.end[1];
+        const phx_angle& p = l.angles[k];
+        e.kind = PHX_UNIT_ANGLE; e.index = k; e.body1 = p.body1; e.body2 = p.body2;
+        r = fabsf(p.impulse + p.motor_impulse);
+        limit = l.angle_limits[k];
+    } else {
+        const int k = i - l.end[2];
+        const phx_slider& p = l.sliders[k];
+        e.kind = PHX_UNIT_SLIDER; e.index = k; e.body1 = p.body1; e.body2 = p.body2;
+        const float a = p.axis_impulse + p.motor_impulse;
+        r = sqrtf(p.impulse * p.impulse + a * a);
+        limit = l.slider_limits[k];
+    }
+    e.step = 0;                                                             // (the host knows the step: PinSet::settle)
+    e.reaction = r;
+    e.threshold = limit * dt;
+    e.reserved = 0;
+    return r > e.threshold;                                                 // (strict, and false for a NaN)
+}
+
+// The break test behind the pass: the step's events, dense and in (kind, index) order, and their count.  An ordered compaction in one
+// launch: workgroup b walks limited units [b chunk, (b + 1) chunk) tile by tile and writes its events, in order (a block scan of the
+// tile's flags), to the front of its own stretch of `staged`; every workgroup then draws a ticket, one 64-bit atomic that also adds
+// its count to the events published so far (the atomic orders nothing in the output), and the workgroup that draws the last one
+// knows the step's total: if there are events it scans the workgroups' counts and moves the stretches together into `events`.
+// A step in which nothing breaks, the common one, takes no fence: a workgroup without events publishes nothing (its count word is
+// zero from the last launch), and the last workgroup reads nothing of the others.  `staged` and `events` hold one record per
+// limited unit, so neither can overflow.  chunk: a multiple of BREAK_LANES; gridDim.x <= BREAK_BLOCKS.
+static __global__ void __launch_bounds__(BREAK_LANES) k_unit_breaks(BreakLists l, float dt, int chunk, phx_break_event* __restrict__ staged, unsigned* __restrict__ words,
+                                                                    phx_break_event* __restrict__ events)
+{
+    __shared__ unsigned lds[16];
+    __shared__ unsigned offsets[BREAK_BLOCKS];
+    __shared__ unsigned long long drawn;
+    unsigned long long* const ticket = reinterpret_cast<unsigned long long*>(words + BREAK_TICKET);
+    const int n = l.end[3];
+    const long long begin = (long long)blockIdx.x * chunk;
+    unsigned mine = 0;
+    for (int t = 0; t < chunk; t += BREAK_LANES) {
+        const long long i = begin + t + threadIdx.x;
+        phx_break_event e;
+        const bool breaks = i < n && unit_breaks(l, (int)i, dt, e);
+        if (!__syncthreads_count(breaks)) continue;                         // (the same for every lane)
+        unsigned total;
+        const unsigned at = block_exclusive_scan_1024(breaks ? 1u : 0u, lds, &total);
+        if (breaks) staged[begin + mine + at] = e;
+        mine += total;
+        __syncthreads();                                                    // (the next tile's scan writes `lds` again)
+    }
+    if (mine) {                                                             // this workgroup's events and count are out before its ticket is drawn
+        if (threadIdx.x == 0) words[blockIdx.x] = mine;
+        __threadfence();
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) drawn = atomicAdd(ticket, ((unsigned long long)mine << 32) | 1ull);
+    __syncthreads();
+    const unsigned long long before = drawn;
+    if ((unsigned)before != gridDim.x - 1) return;
+    const unsigned total = (unsigned)(before >> 32) + mine;
+    if (total) {
+        __threadfence();                                                    // ... and the others' are read behind the last ticket
+        unsigned sum;
+        const unsigned mine_begin = block_exclusive_scan_1024(threadIdx.x < gridDim.x ? words[threadIdx.x] : 0u, lds, &sum);
+        offsets[threadIdx.x] = mine_begin;
+        if (threadIdx.x < gridDim.x) words[threadIdx.x] = 0;                // (the next launch finds the counts zero)
+        __syncthreads();
+        for (unsigned j = threadIdx.x; j < total; j += BREAK_LANES) {
+            unsigned lo = 0, hi = gridDim.x;                                // the last workgroup whose stretch begins at or before event j holds it
+            while (hi - lo > 1) { const unsigned mid = (lo + hi) / 2; if (offsets[mid] <= j) lo = mid; else hi = mid; }
+            events[j] = staged[(long long)lo * chunk + (j - offsets[lo])];
+        }
+    }
+    if (threadIdx.x == 0) { words[BREAK_COUNT] = total; *ticket = 0; }
 }
 
 } // namespace phx

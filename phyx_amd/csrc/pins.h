@@ -13,8 +13,14 @@
 // but through AnchorFields, which an angle never instantiates.
 //
 // Sliders (include/phyx_amd.h SLIDERS) are the fourth kind, behind the angles: anchors as a pin's, limits and a motor as an angle's.
+//
+// Breaks (include/phyx_amd.h BREAKS; tests/break_spec.py): a list may carry a column of break limits beside its records, the host copy
+// the truth as for anchors.  A pass over lists with a column is followed by the break test (pin_kernels.h k_unit_breaks); what it found
+// is settled lazily on the host (PinSet::settle): 4 bytes come down, the events only if there are any, and the broken units leave
+// through UnitList::remove.
 #pragma once
 
+#include <limits>
 #include <tuple>
 #include <type_traits>
 
@@ -99,17 +105,26 @@ public:
     int add(const P* recs, int count, hipStream_t stream);
     int remove(const int32_t* which, int count, hipStream_t stream);
     int get(P* out, hipStream_t stream);
-    void clear() { host_.clear(); dirty_ = true; }
+    void clear() { host_.clear(); limits_.clear(); dirty_ = true; }
+    // the break limits, one per record: a column that exists only once a finite limit was set in this list (without it every limit is +inf)
+    bool limited() const { return !limits_.empty(); }
+    const float* device_limits() const { return limited() ? d_limits_.p : nullptr; }      // (current with the records: upload)
+    void get_limits(float* out) const;
+    // already checked; `d_*`: the staged batch, needed where the list is on the device and has its column already
+    int set_limits(const int32_t* which, const float* values, int count, const int* d_which, const float* d_values, hipStream_t stream);
     // an edit of fields that are the host's truth: written into the host list and, when on_device(), scattered from the staged batch `d_*`
     template <class Fields> int set_fields(const int32_t* which, const float* values, int count, const int* d_which, const float* d_values, hipStream_t stream);
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream, bool* changed);
-    int adopt_device(const P* d_src, int count, hipStream_t stream);
+    int adopt_device(const P* d_src, const float* d_limits, int count, hipStream_t stream);      // (d_limits null: no column)
     int statics(const float4* mpos, unsigned* d_bits, hipStream_t stream) const;      // queues the static bits of every record's bodies
 private:
     std::vector<P> host_;
     bool dirty_ = true;                  // the host list is the truth, impulses included; the device copy is stale
     DevBuf<P> d_;
     DevBuf<int2> d_moved_;
+    std::vector<float> limits_;          // empty, or a limit per record
+    DevBuf<float> d_limits_;
+    template <class Gone> void compact(Gone gone);      // the records (and limits) i with gone(i) leave, the rest keep their order
 };
 
 class PinSet {
@@ -131,20 +146,29 @@ public:
 
     // the calls (world.hip, "units") work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
     void units_changed() { sched_dirty_ = true; }
-    void clear() { each_list([](auto& l) { l.clear(); return PHX_OK; }); sched_dirty_ = true; }
+    void clear() { each_list([](auto& l) { l.clear(); return PHX_OK; }); sched_dirty_ = true; drop_breaks(); }
     void statics_changed() { if (units()) sched_dirty_ = true; }             // ... and a change of the static set make the schedule stale
     // a removal of bodies compacted them through `d_remap` (old index -> new or -1): the units of removed bodies go, the rest are renumbered
     int bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream);
     // snapshots: the device copies (list<P>().device()), current
     int upload(hipStream_t stream) { return each_list([&](auto& l) { return l.upload(stream); }); }
     // load: a list := a device array (queued; the host list follows at once)
-    template <class P> int adopt_device(const P* d_src, int count, hipStream_t stream) { sched_dirty_ = true; return list<P>().adopt_device(d_src, count, stream); }
+    template <class P> int adopt_device(const P* d_src, const float* d_limits, int count, hipStream_t stream) { sched_dirty_ = true; return list<P>().adopt_device(d_src, d_limits, count, stream); }
 
     // the schedule, built unless current
     int prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream);
     const Schedule& schedule() const { return sched_; }
-    // the pass: everything queued on `stream`
-    int solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hipStream_t stream);
+    // the pass: everything queued on `stream`; behind it, where some list has a limit column, the break test of step `step` (its ordinal
+    // among the steps since the events were last taken)
+    int solve(const WorldBodies& bodies, int nb, float dt, int step, Readback& rb, hipStream_t stream);
+    // breaks: does some list have a limit column / has a break test run that settle() has not looked at yet
+    bool limited() const { return std::apply([](const auto&... l) { return (l.limited() || ...); }, lists_); }
+    bool breaks_pending() const { return breaks_pending_; }
+    // the pending test's count comes down (4 bytes) and, only if it is not zero, its events: the broken units leave their lists as a
+    // removal's would and the events join the queue.  Between steps; prepare() begins with it.
+    int settle(Readback& rb, hipStream_t stream);
+    std::vector<phx_break_event>& break_queue() { return queue_; }
+    void drop_breaks() { breaks_pending_ = false; queue_.clear(); }         // an abandoned timeline: nothing pending, no events
 
 private:
     std::tuple<UnitList<phx_pin>, UnitList<phx_link>, UnitList<phx_angle>, UnitList<phx_slider>> lists_;      // the kinds, in their order among the pass's units
@@ -157,6 +181,10 @@ private:
     size_t off_groups_ = 0, off_bodies_ = 0;
     Schedule sched_;
     std::vector<int> hbm_classes_;       // the trailing group's class offsets (absolute slots)
+    bool breaks_pending_ = false; int pending_step_ = 0;
+    DevBuf<phx_break_event> d_staged_, d_events_;      // a record per limited unit each (pin_kernels.h k_unit_breaks)
+    DevBuf<unsigned> d_break_words_;
+    std::vector<phx_break_event> queue_; // the events since phx_world_break_events last took them
 };
 
 } // namespace phx

@@ -64,6 +64,10 @@ template <class P> int UnitList<P>::upload(hipStream_t stream)
     if (!dirty_ || host_.empty()) return PHX_OK;
     PHX_TRY(d_.reserve(host_.size()));
     PHX_HIP(hipMemcpyAsync(d_.p, host_.data(), host_.size() * sizeof(P), hipMemcpyHostToDevice, stream));
+    if (limited()) {
+        PHX_TRY(d_limits_.reserve(limits_.size()));
+        PHX_HIP(hipMemcpyAsync(d_limits_.p, limits_.data(), limits_.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    }
     PHX_HIP(hipStreamSynchronize(stream));
     dirty_ = false;
     return PHX_OK;
@@ -73,6 +77,7 @@ template <class P> int UnitList<P>::add(const P* recs, int count, hipStream_t st
 {
     PHX_TRY(fetch(stream));
     host_.insert(host_.end(), recs, recs + count);
+    if (limited()) limits_.insert(limits_.end(), (size_t)count, std::numeric_limits<float>::infinity());      // (a new unit is unbreakable)
     dirty_ = true;
     return PHX_OK;
 }
@@ -82,10 +87,50 @@ template <class P> int UnitList<P>::remove(const int32_t* which, int count, hipS
     PHX_TRY(fetch(stream));
     std::vector<unsigned char> gone(host_.size(), 0);
     for (int k = 0; k < count; ++k) gone[(size_t)which[k]] = 1;
+    compact([&](size_t i) { return gone[i] != 0; });
+    return PHX_OK;
+}
+
+template <class P> template <class Gone> void UnitList<P>::compact(Gone gone)
+{
     size_t at = 0;
-    for (size_t i = 0; i < host_.size(); ++i) if (!gone[i]) host_[at++] = host_[i];
+    for (size_t i = 0; i < host_.size(); ++i) {
+        if (gone(i)) continue;
+        host_[at] = host_[i];
+        if (limited()) limits_[at] = limits_[i];
+        ++at;
+    }
     host_.resize(at);
+    if (limited()) limits_.resize(at);
     dirty_ = true;
+}
+
+template <class P> void UnitList<P>::get_limits(float* out) const
+{
+    if (limited()) std::copy(limits_.begin(), limits_.end(), out);
+    else std::fill(out, out + host_.size(), std::numeric_limits<float>::infinity());
+}
+
+template <class P> int UnitList<P>::set_limits(const int32_t* which, const float* values, int count, const int* d_which, const float* d_values, hipStream_t stream)
+{
+    const bool had = limited();
+    if (!had) {
+        bool finite = false;
+        for (int k = 0; k < count; ++k) finite = finite || std::isfinite(values[k]);
+        if (!finite) return PHX_OK;                                         // (+inf where every limit is +inf: the list stays without a column)
+        limits_.assign(host_.size(), std::numeric_limits<float>::infinity());
+    }
+    for (int k = 0; k < count; ++k) limits_[(size_t)which[k]] = values[k];
+    if (!on_device()) return PHX_OK;
+    if (had) {
+        hipLaunchKernelGGL(k_unit_limits, dim3(pgrid(count)), dim3(256), 0, stream, d_which, d_values, count, d_limits_.p);
+        PHX_HIP(hipGetLastError());
+        return PHX_OK;
+    }
+    // the column's first appearance beside records that are on the device already: it goes up whole, once
+    PHX_TRY(d_limits_.reserve(limits_.size()));
+    PHX_HIP(hipMemcpyAsync(d_limits_.p, limits_.data(), limits_.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    PHX_HIP(hipStreamSynchronize(stream));
     return PHX_OK;
 }
 
@@ -119,25 +164,21 @@ template <class P> int UnitList<P>::bodies_removed(const int* d_remap, Readback&
     PHX_TRY(rb.add(moved.data(), d_moved_.p, (size_t)n * sizeof(int2), stream));
     PHX_TRY(rb.add(host_.data(), d_.p, (size_t)n * sizeof(P), stream));
     PHX_TRY(rb.wait(stream));
-    size_t at = 0;
-    for (size_t i = 0; i < host_.size(); ++i) {
-        if (moved[i].x == -1 || moved[i].y == -1) continue;
-        P p = host_[i];
-        p.body1 = moved[i].x; p.body2 = moved[i].y == -2 ? -1 : moved[i].y;
-        host_[at++] = p;
-    }
-    host_.resize(at);
-    dirty_ = true; *changed = true;
+    for (size_t i = 0; i < host_.size(); ++i) { host_[i].body1 = moved[i].x; host_[i].body2 = moved[i].y == -2 ? -1 : moved[i].y; }
+    compact([&](size_t i) { return moved[i].x == -1 || moved[i].y == -1; });
+    *changed = true;
     return PHX_OK;
 }
 
-template <class P> int UnitList<P>::adopt_device(const P* d_src, int count, hipStream_t stream)
+template <class P> int UnitList<P>::adopt_device(const P* d_src, const float* d_limits, int count, hipStream_t stream)
 {
     host_.resize((size_t)count);
+    limits_.assign(d_limits ? (size_t)count : 0, 0.f);
     dirty_ = true;
     if (!count) return PHX_OK;
     // (the bodies and anchors are needed on the host for the schedule and the later edits: the list comes down once, O(records))
     PHX_HIP(hipMemcpyAsync(host_.data(), d_src, (size_t)count * sizeof(P), hipMemcpyDeviceToHost, stream));
+    if (d_limits) PHX_HIP(hipMemcpyAsync(limits_.data(), d_limits, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, stream));
     PHX_HIP(hipStreamSynchronize(stream));
     return PHX_OK;
 }
@@ -245,8 +286,36 @@ int PinSet::bodies_removed(const int* d_remap, Readback& rb, hipStream_t stream)
     return each_list([&](auto& l) { return l.bodies_removed(d_remap, rb, stream, &sched_dirty_); });
 }
 
+int PinSet::settle(Readback& rb, hipStream_t stream)
+{
+    if (!breaks_pending_) return PHX_OK;
+    unsigned count = 0;
+    PHX_TRY(rb.add(&count, d_break_words_.p + BREAK_COUNT, sizeof count, stream));
+    PHX_TRY(rb.wait(stream));
+    breaks_pending_ = false;
+    if (!count) return PHX_OK;
+    std::vector<phx_break_event> events((size_t)count);
+    PHX_TRY(rb.add(events.data(), d_events_.p, (size_t)count * sizeof(phx_break_event), stream));
+    PHX_TRY(rb.wait(stream));
+    // the events are in (kind, index) order: each list removes its own stretch, through the one copy of a removal
+    int kind = 0;
+    size_t at = 0;
+    PHX_TRY(each_list([&](auto& l) -> int {
+        std::vector<int32_t> which;
+        for (; at < events.size() && events[at].kind == kind; ++at) which.push_back(events[at].index);
+        ++kind;
+        return which.empty() ? PHX_OK : l.remove(which.data(), (int)which.size(), stream);
+    }));
+    units_changed();
+    // (a world whose last unit broke has no schedule to build at the next step: the rebuild a break stands for is the empty one, counted here)
+    if (!units()) { sched_ = Schedule(); hbm_classes_.clear(); ++builds_; sched_dirty_ = false; }
+    for (phx_break_event& e : events) { e.step = pending_step_; queue_.push_back(e); }
+    return PHX_OK;
+}
+
 int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream)
 {
+    PHX_TRY(settle(rb, stream));                                            // (the last step's breaks leave before the schedule is looked at)
     const int n = units();
     if (!n) return PHX_OK;
     PHX_TRY(upload(stream));
@@ -318,7 +387,7 @@ int PinSet::prepare(const float4* mpos, int nb, Readback& rb, hipStream_t stream
     return PHX_OK;
 }
 
-int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hipStream_t stream)
+int PinSet::solve(const WorldBodies& bodies, int nb, float dt, int step, Readback& rb, hipStream_t stream)
 {
     if (!units()) return PHX_OK;
     PHX_TRY(prepare(bodies.s.mpos, nb, rb, stream));
@@ -368,6 +437,27 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, Readback& rb, hip
             }
     }
     PHX_HIP(hipGetLastError());
+    if (!limited()) return PHX_OK;
+    // the break test, behind the pass's last kernel: over the lists that have a limit column
+    BreakLists l = {};
+    l.pins = d_pins; l.links = d_links; l.angles = d_angles; l.sliders = d_sliders;
+    l.pin_limits = list<phx_pin>().device_limits(); l.link_limits = list<phx_link>().device_limits();
+    l.angle_limits = list<phx_angle>().device_limits(); l.slider_limits = list<phx_slider>().device_limits();
+    l.end[0] = l.pin_limits ? np : 0;
+    l.end[1] = l.end[0] + (l.link_limits ? nl : 0);
+    l.end[2] = l.end[1] + (l.angle_limits ? na : 0);
+    l.end[3] = l.end[2] + (l.slider_limits ? ns : 0);
+    const int n = l.end[3];
+    if (!n) return PHX_OK;
+    if (!d_break_words_.p) {
+        PHX_TRY(d_break_words_.reserve(BREAK_WORDS));
+        PHX_HIP(hipMemsetAsync(d_break_words_.p, 0, BREAK_WORDS * sizeof(unsigned), stream));
+    }
+    PHX_TRY(d_staged_.reserve((size_t)n)); PHX_TRY(d_events_.reserve((size_t)n));
+    const int tiles = div_up(n, BREAK_LANES), chunk = div_up(tiles, BREAK_BLOCKS) * BREAK_LANES;
+    hipLaunchKernelGGL(k_unit_breaks, dim3(div_up(n, chunk)), dim3(BREAK_LANES), 0, stream, l, dt, chunk, d_staged_.p, d_break_words_.p, d_events_.p);
+    PHX_HIP(hipGetLastError());
+    breaks_pending_ = true; pending_step_ = step;
     return PHX_OK;
 }
 

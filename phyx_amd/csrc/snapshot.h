@@ -45,17 +45,21 @@ public:
     // fails), then a device copy queued behind the save, in front of the event the loads wait for
     // (a save that fails afterwards leaves the old ones whole).  The links (LINKS) ride the same way.
     // The angles (ANGLES) are the third rider, the sliders (SLIDERS) the fourth: `P` is any of the four records, and the caller
-    // goes through the kinds (PinSet::each_list).
-    template <class P> int reserve_units(int n, hipStream_t stream) { return riders<P>().reserve(n, stream); }
-    template <class P> int save_units(const P* d_src, int count, hipStream_t stream)
+    // goes through the kinds (PinSet::each_list).  A list's break limits (BREAKS) ride beside its records, where it has a column
+    // (`limited`, d_limits non-null); a list without one allocates and copies what it did before there were limits.
+    template <class P> int reserve_units(int n, bool limited, hipStream_t stream) { return riders<P>().reserve(n, limited, stream); }
+    template <class P> int save_units(const P* d_src, const float* d_limits, int count, hipStream_t stream)
     {
         riders<P>().count = count;
+        riders<P>().limited = count && d_limits;
         if (!count) return PHX_OK;
         PHX_HIP(hipMemcpyAsync(riders<P>().buf.p, d_src, (size_t)count * sizeof(P), hipMemcpyDeviceToDevice, stream));
+        if (d_limits) PHX_HIP(hipMemcpyAsync(riders<P>().limits.p, d_limits, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, stream));
         PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
         return PHX_OK;
     }
     template <class P> const P* units() const { return std::get<Riders<P>>(riders_).buf.p; }
+    template <class P> const float* unit_limits() const { const Riders<P>& r = std::get<Riders<P>>(riders_); return r.limited ? r.limits.p : nullptr; }
     template <class P> int unit_count() const { return std::get<Riders<P>>(riders_).count; }
     int blob_bytes(size_t* bytes) const;
     int export_blob(void* blob, size_t cap);
@@ -68,7 +72,12 @@ private:
     template <class P> struct Riders {            // a list of records beside the blob
         using record = P;
         DevBuf<P> buf; int count = 0;
-        int reserve(int n, hipStream_t stream) { return n ? buf.reserve_keep((size_t)n, (size_t)count, stream) : PHX_OK; }      // (none: nothing is allocated)
+        DevBuf<float> limits; bool limited = false;      // the records' break limits, where the saved list had a column
+        int reserve(int n, bool with_limits, hipStream_t stream)                // (none: nothing is allocated)
+        {
+            if (n && with_limits) PHX_TRY(limits.reserve_keep((size_t)n, limited ? (size_t)count : 0, stream));
+            return n ? buf.reserve_keep((size_t)n, (size_t)count, stream) : PHX_OK;
+        }
     };
     std::tuple<Riders<phx_pin>, Riders<phx_link>, Riders<phx_angle>, Riders<phx_slider>> riders_;      // (the kinds in the pass's order)
     template <class P> Riders<P>& riders() { return std::get<Riders<P>>(riders_); }

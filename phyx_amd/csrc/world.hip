@@ -202,8 +202,13 @@ public:
     int set_link_lengths(const int32_t* which, const float* lengths, int count);
     template <class P> int set_unit_limits(const int32_t* which, const float* limits, int count);      // (`P`: phx_angle or phx_slider)
     template <class P> int set_unit_motors(const int32_t* which, const float* motors, int count);
+    template <class P> int unit_count(int* out);
     int set_pin_iterations(int n);
     int pin_schedule(const Schedule** out);
+    // breaks (phx_world_set_break_limits, get_break_limits, break_events): between steps
+    int set_break_limits(int kind, const int32_t* which, const float* limits, int count);
+    int get_break_limits(int kind, float* out, int cap);
+    int break_events(phx_break_event* out, int cap, int64_t* total);
     int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
     PinSet& pins() { return pins_; }
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
@@ -333,6 +338,8 @@ private:
     template <class Column, class Rule>
     int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
     PinSet pins_;
+    int break_step_ = 0;                 // the steps taken since the break events were last taken: the next step's ordinal in them
+    int settle_breaks();                 // between steps: what the last step's break test found is applied (PinSet::settle); at the top of every call that reads or changes units
     template <class P> int check_unit_indices(const char* what, const int32_t* which, const void* values, int count);
     int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2);
     // an edit of Fields::width floats per listed unit (already checked): staged for the scatter kernel when the list is on the device
@@ -746,7 +753,8 @@ int World::pre_solve(float dt)
     else if (!phase_timing) PHX_TRY(solver_.prelabel_mark());
     { RoctxRange r("RefreshContactJoints"); PHX_TRY(refresh_contact_joints()); lap(5); }             // ref: World.cpp:74
     // the pins and links edit the velocities the contacts are then solved on (include/phyx_amd.h PINS, LINKS); a world without queues nothing
-    if (pins_.units()) { RoctxRange r("SolvePins"); PHX_TRY(pins_.solve(resident(), nb(), dt, rb_, stream_)); }
+    const int ordinal = break_step_++;
+    if (pins_.units()) { RoctxRange r("SolvePins"); PHX_TRY(pins_.solve(resident(), nb(), dt, ordinal, rb_, stream_)); }
     return PHX_OK;
 }
 
@@ -970,7 +978,8 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
-    pins_.clear();                                                          // ... and no pin or link is left
+    pins_.clear();                                                          // ... and no pin or link is left, no break limit and no break event
+    break_step_ = 0;
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -1036,14 +1045,15 @@ int World::save(Snapshot& s)
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before its results are read)
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    PHX_TRY(settle_breaks());
     SnapshotWorld v = snapshot_view();
     v.counts.bodies = nb(); v.counts.manifolds = nm; v.counts.joints = nj; v.counts.baseline = contacts_.baseline_count();
     v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
     PHX_TRY(pins_.upload(stream_));
-    PHX_TRY(pins_.each_list([&](auto& l) { return s.reserve_units<typename std::decay_t<decltype(l)>::record>(l.count(), stream_); }));
+    PHX_TRY(pins_.each_list([&](auto& l) { return s.reserve_units<typename std::decay_t<decltype(l)>::record>(l.count(), l.limited(), stream_); }));
     PHX_TRY(s.save(v, stream_));
-    return pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.count(), stream_); });
+    return pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); });
 }
 
 int World::load(Snapshot& s)
@@ -1080,9 +1090,11 @@ int World::load(Snapshot& s)
     // what set_state resets: the pair set becomes the saved manifolds' pairs, the schedule is rebuilt at the next step
     PHX_TRY(broadphase_.reset_pairs_device(rm_pairs_.p, nm));
     PHX_TRY(forget_step_history());
-    return pins_.each_list([&](auto& l) {                                   // 6. add_pins, add_links, add_angles, add_sliders of the saved ones
+    pins_.drop_breaks();                                                    // (the abandoned timeline's unsettled breaks and its events go with it)
+    break_step_ = 0;
+    return pins_.each_list([&](auto& l) {                                   // 6. add_pins, add_links, add_angles, add_sliders of the saved ones, with their break limits
         using P = typename std::decay_t<decltype(l)>::record;
-        return pins_.adopt_device(s.units<P>(), s.unit_count<P>(), stream_);
+        return pins_.adopt_device(s.units<P>(), s.unit_limits<P>(), s.unit_count<P>(), stream_);
     });
 }
 
@@ -1324,6 +1336,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     }
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
+    PHX_TRY(settle_breaks());
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
     PHX_TRY(rm_keep_.reserve((size_t)n + 2)); PHX_TRY(rm_bnew_.reserve((size_t)n + 2)); PHX_TRY(rm_remap_.reserve((size_t)n));
     PHX_TRY(spare_.bodies.reserve((size_t)n));
@@ -1567,6 +1580,7 @@ template <class P>
 int World::check_unit_indices(const char* what, const int32_t* which, const void* values, int count)
 {
     PHX_TRY(refuse_mid_step(what));
+    PHX_TRY(settle_breaks());
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && (!which || !values)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
     const int n = pins_.list<P>().count();
@@ -1597,6 +1611,7 @@ int World::add_units(const P* recs, int count, int* first)
     const char* const what = Kind::add;
     PHX_TRY(refuse_mid_step(what));
     PHX_TRY(refuse_sharded(what, Kind::plural));
+    PHX_TRY(settle_breaks());
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     if (count && !recs) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
     // (the schedule numbers the units, pins, links, angles and sliders together, in an int32)
@@ -1679,6 +1694,7 @@ int World::set_unit_motors(const int32_t* which, const float* motors, int count)
 template <class P>
 int World::get_units(P* out, int cap)
 {
+    PHX_TRY(settle_breaks());
     UnitList<P>& list = pins_.list<P>();
     const int n = list.count();
     if (cap < n) { set_error("%s: room for %d %s, the world has %d", UnitKind<P>::get, cap, UnitKind<P>::plural, n); return PHX_ERR_CAPACITY; }
@@ -1686,6 +1702,86 @@ int World::get_units(P* out, int cap)
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());
     return list.get(out, stream_);
+}
+
+template <class P>
+int World::unit_count(int* out)
+{
+    PHX_TRY(settle_breaks());
+    *out = pins_.list<P>().count();
+    return PHX_OK;
+}
+
+// ---- breaks ---------------------------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h BREAKS; the test runs behind the pass (PinSet::solve) and is settled here, lazily.
+int World::settle_breaks()
+{
+    if (mid_step_ || !pins_.breaks_pending()) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());
+    return pins_.settle(rb_, stream_);
+}
+
+// f(a P*) for the record of `kind`
+template <class F> static int with_kind(const char* what, int kind, F f)
+{
+    switch (kind) {
+    case PHX_UNIT_PIN: return f((phx_pin*)nullptr);
+    case PHX_UNIT_LINK: return f((phx_link*)nullptr);
+    case PHX_UNIT_ANGLE: return f((phx_angle*)nullptr);
+    case PHX_UNIT_SLIDER: return f((phx_slider*)nullptr);
+    }
+    set_error("%s: kind %d is none of PHX_UNIT_PIN ... PHX_UNIT_SLIDER [0, 3]", what, kind);
+    return PHX_ERR_INVALID;
+}
+
+int World::set_break_limits(int kind, const int32_t* which, const float* limits, int count)
+{
+    static const char* const what = "phx_world_set_break_limits";
+    PHX_TRY(refuse_mid_step(what));
+    return with_kind(what, kind, [&](auto* tag) -> int {
+        using P = std::remove_pointer_t<decltype(tag)>;
+        PHX_TRY(check_unit_indices<P>(what, which, limits, count));
+        for (int k = 0; k < count; ++k)
+            if (!(limits[k] > 0.f)) { set_error("%s: %s %d: break limit %g is not > 0", what, UnitKind<P>::noun, k, (double)limits[k]); return PHX_ERR_INVALID; }
+        if (!count) return PHX_OK;
+        UnitList<P>& list = pins_.list<P>();
+        const int* d_which = nullptr; const float* d_values = nullptr;
+        if (list.on_device()) {
+            PHX_TRY(settle_on_device());
+            if (list.limited()) PHX_TRY(stage_batch(which, limits, count, 1, &d_which, &d_values));
+        }
+        return list.set_limits(which, limits, count, d_which, d_values, stream_);
+    });
+}
+
+int World::get_break_limits(int kind, float* out, int cap)
+{
+    static const char* const what = "phx_world_get_break_limits";
+    PHX_TRY(refuse_mid_step(what));
+    return with_kind(what, kind, [&](auto* tag) -> int {
+        using P = std::remove_pointer_t<decltype(tag)>;
+        PHX_TRY(settle_breaks());
+        const UnitList<P>& list = pins_.list<P>();
+        if (cap < list.count()) { set_error("%s: room for %d %s, the world has %d", what, cap, UnitKind<P>::plural, list.count()); return PHX_ERR_CAPACITY; }
+        list.get_limits(out);
+        return PHX_OK;
+    });
+}
+
+int World::break_events(phx_break_event* out, int cap, int64_t* total)
+{
+    static const char* const what = "phx_world_break_events";
+    PHX_TRY(refuse_mid_step(what));
+    if (cap < 0) { set_error("%s: negative cap %d", what, cap); return PHX_ERR_INVALID; }
+    PHX_TRY(settle_breaks());
+    std::vector<phx_break_event>& queue = pins_.break_queue();
+    *total = (int64_t)queue.size();
+    if ((int64_t)cap < *total) { set_error("%s: room for %d events, the queue holds %lld", what, cap, (long long)*total); return PHX_ERR_CAPACITY; }
+    std::copy(queue.begin(), queue.end(), out);
+    queue.clear();
+    break_step_ = 0;
+    return PHX_OK;
 }
 
 int World::set_pin_iterations(int n)
@@ -1700,6 +1796,7 @@ int World::pin_schedule(const Schedule** out)
 {
     PHX_TRY(refuse_mid_step("phx_world_get_pin_schedule"));
     *out = nullptr;
+    PHX_TRY(settle_breaks());
     if (!pins_.units()) return PHX_OK;
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());
@@ -2312,8 +2409,7 @@ int phx_world_get_links(phx_world* w, phx_link* out, int32_t cap)
 int phx_world_link_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
-    *count = w->impl.pins().list<phx_link>().count();
-    return PHX_OK;
+    return w->impl.unit_count<phx_link>(count);
 }
 
 int phx_world_add_angles(phx_world* w, const phx_angle* angles, int32_t count, int32_t* first)
@@ -2350,8 +2446,7 @@ int phx_world_get_angles(phx_world* w, phx_angle* out, int32_t cap)
 int phx_world_angle_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
-    *count = w->impl.pins().list<phx_angle>().count();
-    return PHX_OK;
+    return w->impl.unit_count<phx_angle>(count);
 }
 
 int phx_world_add_sliders(phx_world* w, const phx_slider* sliders, int32_t count, int32_t* first)
@@ -2394,15 +2489,33 @@ int phx_world_get_sliders(phx_world* w, phx_slider* out, int32_t cap)
 int phx_world_slider_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
-    *count = w->impl.pins().list<phx_slider>().count();
-    return PHX_OK;
+    return w->impl.unit_count<phx_slider>(count);
+}
+
+int phx_world_set_break_limits(phx_world* w, int32_t kind, const int32_t* units, const float* limits, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_break_limits(kind, units, limits, count);
+}
+
+int phx_world_get_break_limits(phx_world* w, int32_t kind, float* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_break_limits(kind, out, cap);
+}
+
+int phx_world_break_events(phx_world* w, phx_break_event* out, int32_t cap, int64_t* total)
+{
+    PHX_REQUIRE(w && total, "null handle / output");
+    PHX_REQUIRE(out || cap <= 0, "null buffer");
+    return w->impl.break_events(out, cap, total);
 }
 
 int phx_world_pin_count(phx_world* w, int32_t* count)
 {
     PHX_REQUIRE(w && count, "null handle / output");
-    *count = w->impl.pins().list<phx_pin>().count();
-    return PHX_OK;
+    return w->impl.unit_count<phx_pin>(count);
 }
 
 int phx_world_set_pin_iterations(phx_world* w, int32_t n)

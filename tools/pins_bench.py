@@ -1,7 +1,7 @@
 """The cost of the pin pass (include/phyx_amd.h PINS): a synchronised World::Update of one world of hanging chains, with and without
 its pins, on the same build.
 
-    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--ropes] [--hinges] [--rails] [--only WORLD] [--import-from DIR]
+    python tools/pins_bench.py [--chains 4096] [--links 16] [--iterations 32] [--steps 200] [--warmup 60] [--repeats 5] [--no-pins] [--ropes] [--hinges] [--rails] [--breakable] [--only WORLD] [--import-from DIR]
 
 The world: a ground and `chains` chains of `links` links (boxes of 2 x 8, 10 apart), each hung from a world pin, side by side.  The
 pinned world runs under gravity (the pins carry the chains); the pinless twin has the same bodies and gravity 0, so that they stay
@@ -25,6 +25,10 @@ gravity and the chains writhe: 0.01 rad on the CPU spec at 32 sweeps.)
 rail through where it hangs, limited to [0, 5] along it.  A chain that hangs still has s = 0 = lower and t . e = 0 exactly, so on
 every step row P and the lower stop are both engaged with C = 0 and go through their whole arithmetic while the chains hang as still
 as in the pinned world - as many slider units again as pins, in the same components.
+
+--breakable adds the world "breakable" (include/phyx_amd.h BREAKS): the pinned world with a finite break limit on every pin, 1000, far
+above a chain's weight (the top pin of 16 links carries about 0.5), so that the break test runs behind every pass, its 4-byte count
+comes down at every step and nothing ever breaks: the same pass on the same units, plus what a world with limits pays per step.
 """
 import argparse
 import json
@@ -36,7 +40,7 @@ import time
 import numpy as np
 
 
-def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False, hinges=False, rails=False):
+def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False, hinges=False, rails=False, breakable=False):
     pw = phyx_amd.World(0, gravity=-200.0 if pinned else 0.0)
     pw.AddBody((0.0, 0.0), 0.0, (8.0 * chains + 100.0, 10.0), static=True)
     rows = np.zeros((chains * links, 5), dtype=np.float32)
@@ -59,6 +63,8 @@ def build(phyx_amd, chains, links, pinned, spacing=10.0, ropes=False, hinges=Fal
         pins["anchor2"][heads, 0] = rows[heads, 0]
         pins["anchor2"][heads, 1] = top
         pw.add_pins(pins)
+        if breakable:
+            pw.set_break_limits("pin", np.arange(len(pins)), np.full(len(pins), 1000.0, dtype=np.float32))
     if ropes:
         from phyx_amd.api import link_dtype
         last = np.flatnonzero(k == links - 1)
@@ -109,14 +115,15 @@ def main():
     ap.add_argument("--ropes", action="store_true", help="also time the pinned world with one taut rope per chain (the 'links' world)")
     ap.add_argument("--hinges", action="store_true", help="also time the pinned world with one engaged limit per pin (the 'angles' world)")
     ap.add_argument("--rails", action="store_true", help="also time the pinned world with one engaged slider per link (the 'sliders' world)")
-    ap.add_argument("--only", choices=("pins", "pinless", "links", "angles", "sliders"), default=None, help="run this world alone")
+    ap.add_argument("--breakable", action="store_true", help="also time the pinned world with a break limit on every pin that none reaches (the 'breakable' world)")
+    ap.add_argument("--only", choices=("pins", "pinless", "links", "angles", "sliders", "breakable"), default=None, help="run this world alone")
     ap.add_argument("--import-from", default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.import_from) if a.import_from else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import phyx_amd
     cfg = phyx_amd.Configuration(phyx_amd.SOLVE_AVX2, phyx_amd.ISLAND_MULTIPLE_SLOPPY, 15, 15)
-    want = [a.only] if a.only else ([] if a.no_pins else ["pins"]) + ["pinless"] + (["links"] if a.ropes else []) + (["angles"] if a.hinges else []) + (["sliders"] if a.rails else [])
-    worlds = {name: build(phyx_amd, a.chains, a.links, name != "pinless", ropes=(name == "links"), hinges=(name == "angles"), rails=(name == "sliders")) for name in want}
+    want = [a.only] if a.only else ([] if a.no_pins else ["pins"]) + ["pinless"] + (["links"] if a.ropes else []) + (["angles"] if a.hinges else []) + (["sliders"] if a.rails else []) + (["breakable"] if a.breakable else [])
+    worlds = {name: build(phyx_amd, a.chains, a.links, name != "pinless", ropes=(name == "links"), hinges=(name == "angles"), rails=(name == "sliders"), breakable=(name == "breakable")) for name in want}
     for name, pw in worlds.items():
         if name != "pinless":
             pw.pin_iterations = a.iterations
@@ -138,6 +145,8 @@ def main():
         if name == "sliders":
             got = pw.sliders()
             out.update(sliders=pw.slider_count(), slider_impulse_max=float(np.abs(got["impulse"]).max()), slider_axis_impulse_max=float(np.abs(got["axis_impulse"]).max()))
+        if name == "breakable":
+            out.update(break_events=len(pw.break_events()), break_limit_max=float(pw.break_limits("pin").max()))
         if name != "pinless":
             s = pw.pin_schedule()
             out.update(pins=pw.pin_count(), lds_groups=s["lds_groups"], groups=len(s["group_offsets"]) - 1, classes=len(s["class_offsets"]) - 1,
