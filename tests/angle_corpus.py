@@ -216,3 +216,8 @@ def spring_with_motor(m):
 
 NAMES = tuple(CASES)
 assert len(ON_A_COMPARISON) * 6 <= len(NAMES)
+
+
+def rows_of(w):
+    """an angle's prestep record as the cases' `expect_angles` names it: its engaged rows, or idle / inactive"""
+    return ("L" if w.lrow else "") + ("M" if w.mrow else "") or ("idle" if w.idle else "inactive")

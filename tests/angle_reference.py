@@ -1,6 +1,5 @@
-"""The pass over pins, links and angles (include/phyx_amd.h ANGLES) in float64, written from the mechanics with the means of
+"""The angles (include/phyx_amd.h ANGLES) for the pass in float64 (tests/unit_reference.py), written from the mechanics with the means of
 tests/pin_reference.py - generalised velocities q = (vx, vy, w), Jacobians, rotation matrices - and not from tests/angle_spec.py.
-It extends link_reference.solve to the three kinds.
 
 An angle's constraint is scalar and touches w only: J_a = J_b = (0, 0, 1), so
 
@@ -23,10 +22,6 @@ import pin_reference as ref
 PI = float(np.float32(3.1415927))
 TWO_PI = float(np.float32(6.2831855))
 J_W = np.array([[0.0, 0.0, 1.0]])
-
-
-class Result:
-    __slots__ = ("q", "pin_impulse", "link_impulse", "link_active", "impulse", "motor_impulse", "lrow", "mrow", "theta")
 
 
 def orientation(st, i):
@@ -74,92 +69,6 @@ def _angle(st, angle, dt):
         bias = c * t(dt) * stiff * gamma
     mrow = solvable and bool(torque > 0)
     return a, b, j, kinv, theta, (lrow, gamma, bias, lo, hi), (mrow, speed, torque * t(dt))
-
-
-def solve(bodies, pins, links, angles, order, dt, iterations=8, dtype=np.float64):
-    """The pass on copies, in slot order over the units (pins, links, angles) -> Result: q (n, 3), pin_impulse (pins, 2),
-    link_impulse, link_active (links,), impulse, motor_impulse, lrow, mrow, theta (angles,)."""
-    st = ref.State(bodies, dtype)
-    npins, npl = len(pins), len(pins) + len(links)
-    out = Result()
-    out.pin_impulse = np.zeros((npins, 2), dtype=dtype)
-    out.link_impulse = np.zeros(len(links), dtype=dtype)
-    out.link_active = np.zeros(len(links), dtype=bool)
-    out.impulse, out.motor_impulse, out.theta = (np.zeros(len(angles), dtype=dtype) for _ in range(3))
-    out.lrow, out.mrow = np.zeros(len(angles), dtype=bool), np.zeros(len(angles), dtype=bool)
-    beta = dtype(ref.BETA) / dtype(dt)
-    work = []
-    for u in order:
-        u = int(u)
-        if u < npins:
-            a, b, ja, jb, kk, c = ref._constraint(st, pins[u])
-            if ref.well_posed(kk):
-                out.pin_impulse[u] = np.asarray(pins["impulse"][u], dtype=dtype)
-                work.append(("pin", u, a, b, ja, jb, kk, beta * c))
-        elif u < npl:
-            k = u - npins
-            a, b, ja, jb, keff, gamma, bias, lo, hi, active = lref._link(st, links[k], dt)
-            out.link_active[k] = active
-            if active:
-                out.link_impulse[k] = min(max(dtype(links["impulse"][k]), lo), hi)
-                work.append(("link", k, a, b, ja, jb, keff, (gamma, bias, lo, hi)))
-        else:
-            k = u - npl
-            a, b, j, kinv, theta, (lrow, gamma, bias, lo, hi), (mrow, speed, mmax) = _angle(st, angles[k], dt)
-            out.theta[k], out.lrow[k], out.mrow[k] = theta, lrow, mrow
-            if mrow:
-                out.motor_impulse[k] = min(max(dtype(angles["motor_impulse"][k]), -mmax), mmax)
-            if lrow:
-                out.impulse[k] = min(max(dtype(angles["impulse"][k]), lo), hi)
-            if lrow or mrow:
-                work.append(("angle", k, a, b, j, j, kinv, (lrow, gamma, bias, lo, hi, mrow, speed, mmax)))
-
-    def push(a, b, ja, jb, p):
-        st.q[a] -= st.w[a] * (ja.T @ p)
-        if b >= 0:
-            st.q[b] += st.w[b] * (jb.T @ p)
-
-    def rel(a, b, ja, jb):
-        v = -(ja @ st.q[a])
-        return v + jb @ st.q[b] if b >= 0 else v
-
-    for kind, k, a, b, ja, jb, kk, rest in work:
-        if kind == "pin":
-            push(a, b, ja, jb, out.pin_impulse[k])
-        elif kind == "link":
-            push(a, b, ja, jb, out.link_impulse[k:k + 1])
-        else:
-            if rest[5]:
-                push(a, b, ja, jb, out.motor_impulse[k:k + 1])
-            if rest[0]:
-                push(a, b, ja, jb, out.impulse[k:k + 1])
-    with np.errstate(all="ignore"):
-        for _ in range(int(iterations)):
-            for kind, k, a, b, ja, jb, kk, rest in work:
-                if kind == "pin":
-                    dp = np.linalg.solve(kk, -(rel(a, b, ja, jb) + rest)).astype(dtype)
-                    out.pin_impulse[k] += dp
-                    push(a, b, ja, jb, dp)
-                elif kind == "link":
-                    gamma, bias, lo, hi = rest
-                    new = out.link_impulse[k] - (rel(a, b, ja, jb)[0] + bias + gamma * out.link_impulse[k]) / kk
-                    new = min(max(new, lo), hi)
-                    push(a, b, ja, jb, np.array([new - out.link_impulse[k]], dtype=dtype))
-                    out.link_impulse[k] = new
-                else:
-                    lrow, gamma, bias, lo, hi, mrow, speed, mmax = rest
-                    if mrow:
-                        new = out.motor_impulse[k] - (rel(a, b, ja, jb)[0] - speed) / kk
-                        new = min(max(new, -mmax), mmax)
-                        push(a, b, ja, jb, np.array([new - out.motor_impulse[k]], dtype=dtype))
-                        out.motor_impulse[k] = new
-                    if lrow:
-                        new = out.impulse[k] - (rel(a, b, ja, jb)[0] + bias + gamma * out.impulse[k]) / (kk + gamma)
-                        new = min(max(new, lo), hi)
-                        push(a, b, ja, jb, np.array([new - out.impulse[k]], dtype=dtype))
-                        out.impulse[k] = new
-    out.q = st.q
-    return out
 
 
 deviation = lref.deviation

@@ -10,7 +10,7 @@ xA, xB the bodies' xVector:
 the double-precision arctan2 rounded to float32 (the rule of the integrators' cos / sin), in the prestep only.  The engine's
 angularVelocity is clockwise-positive (pin_spec.py), theta is the clockwise angle of B against A, and d theta / dt = wB - wA: the sign
 every row below is written in.  Against the world the world is B, so a body1 turning with w > 0 LOSES w dt of theta per step, and a
-free body2 against a resting body1 gains it (tests/test_angles_cpu.py pins both to link_spec.step_free).
+free body2 against a resting body1 gains it (tests/test_angles_cpu.py pins both to unit_spec.step_free).
 
     mid = (lower + upper) * 0.5,  half = (upper - lower) * 0.5,  phi = theta - mid, wrapped once with the float32 constants PI, TWO_PI:
     phi > PI: phi - TWO_PI;  phi < -PI: phi + TWO_PI
@@ -31,15 +31,14 @@ The row M, the motor, is on where max_torque > 0: it drives wB - wA to motor_spe
 The warm start applies M's clamped impulse, then L's, each where its row is on.  A sweep is M, then L on the velocities M left
 (Box2D's order).  Applying d: wA -= iA d, wB += iB d; linear velocities are not touched; a static body is not written.
 
-solve_units(bodies, pins, links, angles, order, dt, iterations) is the whole pass over the units: the pins, then the links, then the
+unit_spec.solve_units(bodies, lists, order, dt, iterations) is the whole pass over the units: the pins, then the links, then the
 angles.  Pin and link units go through pin_spec / link_spec unchanged.
 """
 import numpy as np
 
-import link_spec
 import pin_spec
 from link_spec import clamp
-from pin_spec import F, BETA
+from pin_spec import F
 
 PI = F(3.1415927)
 TWO_PI = F(6.2831855)
@@ -164,80 +163,8 @@ def sweep(bodies, p):
         apply(bodies, p, d)
 
 
-def solve_units(bodies, pins, links, angles, order, dt, iterations=8):
-    """The whole pass, in place: bodies' velocities, pins["impulse"], links["impulse"], angles["impulse"], angles["motor_impulse"].
-    Returns (the links' work records in link order, the angles' in angle order)."""
-    npins, npl = len(pins), len(pins) + len(links)
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        beta = BETA / F(dt)
-        work = []
-        for u in order:
-            u = int(u)
-            if u < npins:
-                work.append((u, pin_spec.prestep(bodies, pins[u], beta)))
-            elif u < npl:
-                work.append((u, link_spec.prestep(bodies, links[u - npins], beta, dt)))
-            else:
-                work.append((u, prestep(bodies, angles[u - npl], beta, dt)))
-        for u, p in work:
-            if p.active:
-                if u < npins:
-                    pin_spec.apply(bodies, p, p.px, p.py)
-                elif u < npl:
-                    link_spec.apply(bodies, p, p.lam)
-                else:
-                    warm(bodies, p)
-        for _ in range(int(iterations)):
-            for u, p in work:
-                if p.active:
-                    if u < npins:
-                        pin_spec.sweep(bodies, p)
-                    elif u < npl:
-                        link_spec.sweep(bodies, p)
-                    else:
-                        sweep(bodies, p)
-        by_link, by_angle = [None] * len(links), [None] * len(angles)
-        for u, p in work:
-            if u < npins:
-                pins["impulse"][u] = (p.px, p.py)
-            elif u < npl:
-                links["impulse"][u - npins] = p.lam
-                by_link[u - npins] = p
-            else:
-                angles["impulse"][u - npl], angles["motor_impulse"][u - npl] = p.lam, p.mlam
-                by_angle[u - npl] = p
-    return by_link, by_angle
-
-
-def step_free(bodies, pins, links, angles, order, dt, gravity, iterations=8, torque=None):
-    """link_spec.step_free with the three kinds in the pass: IntegrateVelocity (with `torque`: per body, w += inv_inertia torque dt,
-    the test's own constant torque), the units, IntegratePosition; no contacts."""
-    dt = F(dt)
-    for i in range(len(bodies)):
-        if bodies["inv_mass"][i] != 0:
-            bodies["velocity"]["y"][i] = F(bodies["velocity"]["y"][i]) + F(gravity) * dt
-        if torque is not None and torque[i] != 0:
-            bodies["angular_velocity"][i] = F(bodies["angular_velocity"][i]) + F(F(bodies["inv_inertia"][i]) * F(torque[i])) * dt
-    work = solve_units(bodies, pins, links, angles, order, dt, iterations)
-    _integrate_position(bodies, dt)
-    return work
-
-
-def _integrate_position(bodies, dt):
-    """link_spec.step_free's position step"""
-    for i in range(len(bodies)):
-        b = bodies[i]
-        px = F(b["pos"]["x"]) + F(b["velocity"]["x"]) * dt
-        py = F(b["pos"]["y"]) + F(b["velocity"]["y"]) * dt
-        bodies["pos"]["x"][i], bodies["pos"]["y"][i] = px, py
-        ang = -(F(b["angular_velocity"]) * dt)            # ref: World.cpp:63 Rotate(-(... + angularVelocity * dt))
-        c, s = F(np.cos(np.float64(ang))), F(np.sin(np.float64(ang)))
-        xx, xy = F(b["xv"]["x"]), F(b["xv"]["y"])
-        nx, ny = xx * c - xy * s, xx * s + xy * c
-        n = F(np.sqrt(np.float64(nx * nx + ny * ny)))
-        nx, ny = nx / n, ny / n
-        bodies["xv"]["x"][i], bodies["xv"]["y"][i] = nx, ny
-        bodies["yv"]["x"][i], bodies["yv"]["y"][i] = -ny, nx
+def store(angles, k, p):
+    angles["impulse"][k], angles["motor_impulse"][k] = p.lam, p.mlam
 
 
 def make_angles(rows):

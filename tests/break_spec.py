@@ -20,12 +20,12 @@ add to a joint's load shows in the next step's pass, when the joint resists it.
 """
 import numpy as np
 
-import slider_spec
+import unit_spec
 from pin_spec import F
 
 INF = F(np.inf)
-PIN, LINK, ANGLE, SLIDER = 0, 1, 2, 3
-KINDS = ("pin", "link", "angle", "slider")
+PIN, LINK, ANGLE, SLIDER = unit_spec.PIN, unit_spec.LINK, unit_spec.ANGLE, unit_spec.SLIDER
+KINDS = tuple(kind.name for kind in unit_spec.KINDS)
 
 
 def event_dtype():
@@ -33,37 +33,32 @@ def event_dtype():
     return break_event_dtype
 
 
-def no_limits(pins, links, angles, sliders):
+def no_limits(lists):
     """the limits of new units: +inf each, one float32 array per kind"""
-    return [np.full(len(l), INF, dtype=np.float32) for l in (pins, links, angles, sliders)]
+    return [np.full(len(l), INF, dtype=np.float32) for l in unit_spec.full(lists)]
 
 
-def reactions(pins, links, angles, sliders):
+def _norm(x, y):
+    return np.sqrt(F(F(x * x) + F(y * y)))
+
+
+REACTION = (lambda p: _norm(F(p["impulse"][0]), F(p["impulse"][1])),
+            lambda p: np.abs(F(p["impulse"])),
+            lambda p: np.abs(F(F(p["impulse"]) + F(p["motor_impulse"]))),
+            lambda p: _norm(F(p["impulse"]), F(F(p["axis_impulse"]) + F(p["motor_impulse"]))))       # in the order of unit_spec.KINDS
+
+
+def reactions(lists):
     """R of every unit from the impulses in its record: one float32 array per kind"""
     with np.errstate(over="ignore", invalid="ignore"):
-        rp = np.zeros(len(pins), dtype=np.float32)
-        for k in range(len(pins)):
-            x, y = F(pins["impulse"][k][0]), F(pins["impulse"][k][1])
-            rp[k] = np.sqrt(F(F(x * x) + F(y * y)))
-        rl = np.zeros(len(links), dtype=np.float32)
-        for k in range(len(links)):
-            rl[k] = np.abs(F(links["impulse"][k]))
-        ra = np.zeros(len(angles), dtype=np.float32)
-        for k in range(len(angles)):
-            ra[k] = np.abs(F(F(angles["impulse"][k]) + F(angles["motor_impulse"][k])))
-        rs = np.zeros(len(sliders), dtype=np.float32)
-        for k in range(len(sliders)):
-            p = F(sliders["impulse"][k])
-            a = F(F(sliders["axis_impulse"][k]) + F(sliders["motor_impulse"][k]))
-            rs[k] = np.sqrt(F(F(p * p) + F(a * a)))
-    return [rp, rl, ra, rs]
+        return [np.array([r(p) for p in units], dtype=np.float32) for r, units in zip(REACTION, unit_spec.full(lists))]
 
 
-def breaks(pins, links, angles, sliders, limits, dt, step=0):
+def breaks(lists, limits, dt, step=0):
     """The events of the step whose pass left the lists as they are, in (kind, index) order: a break_event_dtype array."""
     events = []
     with np.errstate(over="ignore", invalid="ignore"):
-        for kind, (units, r, lim) in enumerate(zip((pins, links, angles, sliders), reactions(pins, links, angles, sliders), limits)):
+        for kind, (units, r, lim) in enumerate(zip(unit_spec.full(lists), reactions(lists), limits)):
             assert len(lim) == len(units)
             for k in range(len(units)):
                 threshold = F(F(lim[k]) * F(dt))
@@ -72,22 +67,22 @@ def breaks(pins, links, angles, sliders, limits, dt, step=0):
     return np.array(events, dtype=event_dtype()) if events else np.zeros(0, dtype=event_dtype())
 
 
-def settle(pins, links, angles, sliders, limits, events):
-    """The lists and the limits without the units the events name: ([pins, links, angles, sliders], limits)."""
-    lists, kept = [], []
-    for kind, (units, lim) in enumerate(zip((pins, links, angles, sliders), limits)):
+def settle(lists, limits, events):
+    """The lists and the limits without the units the events name: (lists, limits)."""
+    left, kept = [], []
+    for kind, (units, lim) in enumerate(zip(unit_spec.full(lists), limits)):
         gone = [int(e["index"]) for e in events if int(e["kind"]) == kind]
-        lists.append(np.delete(units, gone))
+        left.append(np.delete(units, gone))
         kept.append(np.delete(np.asarray(lim, dtype=np.float32), gone))
-    return lists, kept
+    return left, kept
 
 
-def step_free(bodies, pins, links, angles, sliders, limits, order, dt, gravity, iterations=8, force=None, step=0):
-    """slider_spec.step_free, then the break test of that pass: -> (events, [the lists as the next step finds them], their limits).
-    `order`: the pass's order of units (None: pins, links, angles, sliders, each in index order)."""
+def step_free(bodies, lists, limits, order, dt, gravity, iterations=8, force=None, step=0):
+    """unit_spec.step_free, then the break test of that pass: -> (events, [the lists as the next step finds them], their limits).
+    `order`: the pass's order of units (None: the kinds in unit_spec.KINDS' order, each in index order)."""
     if order is None:
-        order = range(len(pins) + len(links) + len(angles) + len(sliders))
-    slider_spec.step_free(bodies, pins, links, angles, sliders, order, dt, gravity, iterations, force)
-    events = breaks(pins, links, angles, sliders, limits, dt, step)
-    lists, kept = settle(pins, links, angles, sliders, limits, events)
-    return events, lists, kept
+        order = range(sum(len(units) for units in lists))
+    unit_spec.step_free(bodies, lists, order, dt, gravity, iterations, force)
+    events = breaks(lists, limits, dt, step)
+    left, kept = settle(lists, limits, events)
+    return events, left, kept

@@ -372,3 +372,8 @@ def _sqrt_case(m, d):
 NAMES = tuple(CASES) + tuple("sqrt_%d" % k for k in range(len(SQRT_D)))
 ON_A_COMPARISON = ("at_max", "at_min", "at_len_floor")
 NON_FINITE = ("overflow_after_an_anchor_edit", "overflow_on_a_rope")
+
+
+def state_of(w):
+    """a link's prestep record as the cases' `expect` names it"""
+    return "active" if w.active else ("idle" if w.idle else "inactive")

@@ -8,7 +8,7 @@ at most one is engaged, decided at the prestep (a rope is min_length = 0).  A li
 else.  That is deliberately not speculative: a limit engages the step after the length overshoots it and the bias pulls it back, and
 until then the bodies move bit for bit as they would without the link.
 
-solve_units(bodies, pins, links, order, dt, iterations) is the whole pass: the units are the pins followed by the links (unit
+unit_spec.solve_units(bodies, lists, order, dt, iterations) is the whole pass: the units are the pins followed by the links (unit
 u < len(pins) is pin u, otherwise link u - len(pins)); prestep and warm start of every unit in the slot order `order`, then
 `iterations` sweeps in slot order.  Pin units go through pin_spec.prestep / apply / sweep unchanged.
 
@@ -27,7 +27,7 @@ The activity rule: a link is active where len > LEN_FLOOR and kinv > 0, both in 
 import numpy as np
 
 import pin_spec
-from pin_spec import F, BETA
+from pin_spec import F
 
 LEN_FLOOR = F(2.0 ** -10)
 TWO_PI = F(6.2831855)
@@ -116,6 +116,10 @@ def apply(bodies, p, lam):
     pin_spec.apply(bodies, p, lam * p.nx, lam * p.ny)
 
 
+def warm(bodies, p):
+    apply(bodies, p, p.lam)
+
+
 def sweep(bodies, p):
     vax, vay, wa = pin_spec._vel(bodies, p.a)
     vbx, vby, wb = pin_spec._vel(bodies, p.b)
@@ -132,60 +136,8 @@ def sweep(bodies, p):
     apply(bodies, p, d)
 
 
-def solve_units(bodies, pins, links, order, dt, iterations=8):
-    """The whole pass, in place: bodies' velocities, pins["impulse"], links["impulse"].  Returns the links' work records in link order
-    (len, c, active, idle of the prestep) for the tests' own assertions."""
-    npins = len(pins)
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        beta = BETA / F(dt)
-        work = []
-        for u in order:
-            u = int(u)
-            work.append((u, pin_spec.prestep(bodies, pins[u], beta)) if u < npins else (u, prestep(bodies, links[u - npins], beta, dt)))
-        for u, p in work:
-            if p.active:
-                if u < npins:
-                    pin_spec.apply(bodies, p, p.px, p.py)
-                else:
-                    apply(bodies, p, p.lam)
-        for _ in range(int(iterations)):
-            for u, p in work:
-                if p.active:
-                    if u < npins:
-                        pin_spec.sweep(bodies, p)
-                    else:
-                        sweep(bodies, p)
-        by_link = [None] * len(links)
-        for u, p in work:
-            if u < npins:
-                pins["impulse"][u] = (p.px, p.py)
-            else:
-                links["impulse"][u - npins] = p.lam
-                by_link[u - npins] = p
-    return by_link
-
-
-def step_free(bodies, pins, links, order, dt, gravity, iterations=8):
-    """pin_spec.step_free with the whole pass in the pins' place: IntegrateVelocity, the units, IntegratePosition; no contacts."""
-    dt = F(dt)
-    for i in range(len(bodies)):
-        if bodies["inv_mass"][i] != 0:
-            bodies["velocity"]["y"][i] = F(bodies["velocity"]["y"][i]) + F(gravity) * dt
-    work = solve_units(bodies, pins, links, order, dt, iterations)
-    for i in range(len(bodies)):                          # pin_spec.step_free's position step
-        b = bodies[i]
-        px = F(b["pos"]["x"]) + F(b["velocity"]["x"]) * dt
-        py = F(b["pos"]["y"]) + F(b["velocity"]["y"]) * dt
-        bodies["pos"]["x"][i], bodies["pos"]["y"][i] = px, py
-        ang = -(F(b["angular_velocity"]) * dt)            # ref: World.cpp:63 Rotate(-(... + angularVelocity * dt))
-        c, s = F(np.cos(np.float64(ang))), F(np.sin(np.float64(ang)))
-        xx, xy = F(b["xv"]["x"]), F(b["xv"]["y"])
-        nx, ny = xx * c - xy * s, xx * s + xy * c
-        n = F(np.sqrt(np.float64(nx * nx + ny * ny)))
-        nx, ny = nx / n, ny / n
-        bodies["xv"]["x"][i], bodies["xv"]["y"][i] = nx, ny
-        bodies["yv"]["x"][i], bodies["yv"]["y"][i] = -ny, nx
-    return work
+def store(links, k, p):
+    links["impulse"][k] = p.lam
 
 
 def make_links(rows):

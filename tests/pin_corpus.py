@@ -57,6 +57,7 @@ import zlib
 import numpy as np
 
 from phyx_amd.api import pin_dtype
+import pin_reference as ref
 
 DT = 1.0 / 60.0
 G = -200.0
@@ -598,3 +599,72 @@ def random_axle_pair(seed):
     m.pin_at(0, 1, tuple(pa + t * (pb - pa)), flags=(False, True, True), impulse=tuple(r.uniform(-1, 1, 2)))
     m.shape = (1, [1], 1)
     return m
+
+
+# ---- the checks that tests/test_pin_corpus_cpu.py makes on the spec's output and tests/test_pin_corpus_gpu.py on the device's ----
+ULP = 2.0 ** -23
+U = 2.0 ** -24                  # one float32 rounding
+MARGIN = 8.0                    # x the reference's own float32-vs-float64 deviation: the bound of a comparison with the reference
+
+
+def check_the_anchor_is_followed(m, start, bodies, steps):
+    """kinematic_anchor: IntegratePosition moved the static body by its velocities, and the bodies pinned to it went along: their
+    pins' separations stay a tenth of the way the pins' points on the anchor travelled (a pin that ignored the anchor's velocity
+    would fall behind by all of it)."""
+    vx, vy, w = m.vel[0]
+    assert abs(float(bodies["pos"]["x"][0]) - float(start["pos"]["x"][0]) - vx * DT * steps) < 1e-4
+    assert abs(float(bodies["pos"]["y"][0]) - float(start["pos"]["y"][0]) - vy * DT * steps) < 1e-4
+    assert bodies["xv"]["x"][0] != start["xv"]["x"][0], "the anchor never turned"
+    st0, st1 = ref.State(start), ref.State(bodies)
+    pins = m.pins
+    for k in range(len(pins)):
+        end = 1 if pins["body1"][k] == 0 else 2
+        a = np.asarray(pins["anchor%d" % end][k], dtype=np.float64)
+        travelled = np.hypot(*((st1.pos[0] + st1.rot[0] @ a) - (st0.pos[0] + st0.rot[0] @ a)))
+        apart = np.hypot(*ref._constraint(st1, pins[k])[5])
+        print("pin %d: its point on the anchor travelled %.4g, the pin is %.4g apart" % (k, travelled, apart))
+        assert travelled > 0.3 and apart < 0.1 * travelled
+
+
+ONE_PIN = ("pair", "b1_static", "lever100")
+
+
+def check_residual(before, after, pin):
+    """A block solve is exact up to the rounding of its own arithmetic: cond(K) times a few roundings (16: the spec's sweep is
+    about that many operations deep) of the terms the residual is made of, before and after."""
+    start, k, terms0 = ref.residual(before, before, pin, DT)
+    res, _, terms1 = ref.residual(before, after, pin, DT)
+    tol = 16 * U * np.linalg.cond(k) * (terms0 + terms1)
+    print("residual %s (before the sweep %s), tolerance %.3g" % (res, start, tol))
+    assert np.abs(start).max() > 100 * tol, "the pin had nothing to solve"
+    assert np.abs(res).max() <= tol
+
+
+def conserves_momentum(m):
+    b1, b2, st = m.graph()
+    return not any(st) and min(b2) >= 0 and not m.masses
+
+
+CONSERVING = tuple(n for n in NAMES if conserves_momentum(build(n)))
+
+
+def check_momentum(m, before, after, impulse, iterations):
+    """sum m v and sum (m x cross v - I w) before and after the pass, in float64.  The two ends of a pin are C apart, so its impulse
+    pair carries the angular momentum C x P: that is taken off.  Every write of a velocity rounds it (two roundings per component),
+    a body is written (iterations + 1) x its pins times: the bound is that many roundings of sum m |v| (sum m |x| |v| + I |w|)."""
+    lin0, ang0 = ref.momenta(before)
+    lin1, ang1 = ref.momenta(after)
+    st = ref.State(before)
+    pins = m.pins
+    for k in range(len(pins)):
+        c = ref._constraint(st, pins[k])[5]
+        ang1 -= c[0] * float(impulse[k][1]) - c[1] * float(impulse[k][0])
+    degree = np.bincount(np.concatenate([pins["body1"], pins["body2"]])).max()
+    s_lin, s_ang = np.maximum(ref.momentum_scale(before), ref.momentum_scale(after))
+    bound = 4 * U * (iterations + 1) * degree
+    print("%s: linear %.3g of %.3g, angular %.3g of %.3g, bound %.3g" % (m.name, np.abs(lin1 - lin0).max(), s_lin, abs(ang1 - ang0), s_ang, bound))
+    assert np.abs(lin1 - lin0).max() <= bound * s_lin
+    assert abs(ang1 - ang0) <= bound * s_ang
+
+
+INACTIVE = ("static_static", "static_world", "axle_world", "axle_centre", "axles_in_line")

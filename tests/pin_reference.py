@@ -11,8 +11,8 @@ moves by J q dt).  Everything else follows from J:
     dP = solve(K, -(J_b q_b - J_a q_a + beta C)),  beta = 0.2 / dt,  C = (pos_b + rb) - (pos_a + ra)
     q_a -= W_a J_a^T P,   q_b += W_b J_b^T P
 
-solve() runs the pass as the header defines it: every pin's K and C from the poses, the warm start P = the stored impulse in slot
-order, then `iterations` sweeps in slot order.  A static body has W = 0 and is left alone by the algebra itself; a pin is inactive
+unit_reference.solve runs the pass as the header defines it: every pin's K and C from the poses, the warm start P = the stored impulse
+in slot order, then `iterations` sweeps in slot order.  A static body has W = 0 and is left alone by the algebra itself; a pin is inactive
 where K is singular (its smallest eigenvalue is not above SINGULAR x the largest, decided in float64 whatever `dtype` is: whether a
 pin is well posed is a property of the problem, not of the precision it is solved in).
 
@@ -45,10 +45,6 @@ class State:
         self.w = np.stack([bodies["inv_mass"], bodies["inv_mass"], bodies["inv_inertia"]], axis=1).astype(dtype)
 
 
-class Result:
-    __slots__ = ("q", "impulse", "active", "c")
-
-
 def _constraint(st, pin):
     """-> (a, b, J_a, J_b, K, C) of one pin in st.dtype; b = -1 and J_b = 0 for the world"""
     dt_ = st.dtype
@@ -71,45 +67,6 @@ def _constraint(st, pin):
 def well_posed(k):
     lam = np.linalg.eigvalsh(np.asarray(k, dtype=np.float64))
     return bool(lam[0] > SINGULAR * lam[1])
-
-
-def solve(bodies, pins, order, dt, iterations=8, dtype=np.float64):
-    """The pin pass on copies: -> Result with q (n, 3) the velocities after it, impulse (pins, 2) in pin order, active (pins,),
-    c (pins, 2) the separations the prestep saw.  Nothing is edited in place."""
-    st = State(bodies, dtype)
-    exact = st if dtype == np.float64 else State(bodies, np.float64)
-    beta = dtype(BETA) / dtype(dt)
-    out = Result()
-    out.impulse = np.zeros((len(pins), 2), dtype=dtype)
-    out.active = np.zeros(len(pins), dtype=bool)
-    out.c = np.zeros((len(pins), 2), dtype=dtype)
-    work = []
-    for k in order:
-        k = int(k)
-        a, b, ja, jb, kk, c = _constraint(st, pins[k])
-        out.c[k] = c
-        out.active[k] = well_posed(_constraint(exact, pins[k])[4])
-        if out.active[k]:
-            out.impulse[k] = np.asarray(pins["impulse"][k], dtype=dtype)
-            work.append((k, a, b, ja, jb, kk, beta * c))
-
-    def push(a, b, ja, jb, p):
-        st.q[a] -= st.w[a] * (ja.T @ p)
-        if b >= 0:
-            st.q[b] += st.w[b] * (jb.T @ p)
-
-    for k, a, b, ja, jb, kk, bias in work:
-        push(a, b, ja, jb, out.impulse[k])
-    for _ in range(int(iterations)):
-        for k, a, b, ja, jb, kk, bias in work:
-            cdot = -(ja @ st.q[a])
-            if b >= 0:
-                cdot = cdot + jb @ st.q[b]
-            dp = np.linalg.solve(kk, -(cdot + bias)).astype(dtype)
-            out.impulse[k] += dp
-            push(a, b, ja, jb, dp)
-    out.q = st.q
-    return out
 
 
 def velocities(bodies):
@@ -180,12 +137,13 @@ def step_free(bodies, pins, order, dt, gravity, iterations=8):
     rec["xv"]["x"], rec["xv"]["y"], rec["yv"]["x"], rec["yv"]["y"] = c, s, -s, c
     rec["velocity"]["x"], rec["velocity"]["y"], rec["angular_velocity"] = q[:, 0], q[:, 1], q[:, 2]
     rec["inv_mass"], rec["inv_inertia"] = bodies["w"][:, 0], bodies["w"][:, 2]
-    r = solve(rec, pins, order, dt, iterations, np.float64)
-    pins["impulse"][:] = r.impulse
+    import unit_reference
+    r = unit_reference.solve(rec, [pins], order, dt, iterations, np.float64)
+    pins["impulse"][:] = r.pin_impulse
     bodies["q"] = r.q
     bodies["pos"] = bodies["pos"] + r.q[:, :2] * dt
     bodies["angle"] = bodies["angle"] - r.q[:, 2] * dt          # clockwise-positive w turns the frame by -w dt
-    return float(np.hypot(r.c[:, 0], r.c[:, 1])[r.active].max(initial=0.0))
+    return float(np.hypot(r.pin_c[:, 0], r.pin_c[:, 1])[r.pin_active].max(initial=0.0))
 
 
 def _record_dtype():

@@ -1,18 +1,16 @@
 """The definition of the pin pass (include/phyx_amd.h PINS): scalar float32, every operation rounded on its own, no fused
 multiply-add, IEEE division.  The device kernels (phyx_amd/csrc/pin_kernels.h) follow this file operation for operation.
 
-solve(bodies, pins, order, dt, iterations) edits bodies["velocity"], bodies["angular_velocity"] and pins["impulse"] in place: the
-prestep and the warm start of every pin in the slot order `order`, then `iterations` sweeps in slot order.  `bodies` is a
-rigid_body_dtype array (the oracle World's own, or a copy), `pins` a pin_dtype array.
+The pass itself is unit_spec.solve_units, which walks prestep, warm, sweep and store below (and the other kinds') and edits
+bodies["velocity"], bodies["angular_velocity"] and pins["impulse"] in place: the prestep and the warm start of every pin in the slot
+order `order`, then `iterations` sweeps in slot order.  `bodies` is a rigid_body_dtype array (the oracle World's own, or a copy), `pins`
+a pin_dtype array.
 
 The engine's angularVelocity is CLOCKWISE-positive: IntegratePosition rotates the frame by -(angularVelocity * dt) (ref: World.cpp:63)
 and the contact limiters project it with n x r, not r x n (ref: Solver.cpp:559-560).  So the velocity of the point r of a body is
 v - w x r = (v.x + w r.y, v.y - w r.x), and an impulse P at r changes w by -i (r x P).  Written with the counter-clockwise cross
 product (-w r.y, w r.x) the pass pumps energy into everything that turns: a pendulum climbs above its release height and a chain
-comes apart within a second.  step_free below rotates as the reference does, so the CPU suite sees that.
-
-Also here: a minimal free-body stepper (step_free) — IntegrateVelocity, the pins, IntegratePosition as the reference's World does
-them, without contacts — with which the CPU suite checks that the spec holds chains together.
+comes apart within a second.  unit_spec.step_free rotates as the reference does, so the CPU suite sees that.
 """
 import numpy as np
 
@@ -43,7 +41,7 @@ def _static(m, i):
     return m == 0 and i == 0
 
 
-def prestep(bodies, pin, beta):
+def prestep(bodies, pin, beta, dt=None):
     p = _Pin()
     a, b = int(pin["body1"]), int(pin["body2"])
     p.a, p.b = a, b
@@ -115,46 +113,12 @@ def sweep(bodies, p):
     apply(bodies, p, dx, dy)
 
 
-def solve(bodies, pins, order, dt, iterations=8):
-    """The whole pass, in place.  Returns the largest |C| of the active pins at the prestep (0.0 without any)."""
-    with np.errstate(over="ignore", invalid="ignore"):
-        beta = BETA / F(dt)
-        work = [prestep(bodies, pins[int(k)], beta) for k in order]
-        for p in work:
-            if p.active:
-                apply(bodies, p, p.px, p.py)
-        for _ in range(int(iterations)):
-            for p in work:
-                if p.active:
-                    sweep(bodies, p)
-        for k, p in zip(order, work):
-            pins["impulse"][int(k)] = (p.px, p.py)
-    return max([float(np.hypot(float(p.c[0]), float(p.c[1]))) for p in work if p.active], default=0.0)
+def warm(bodies, p):
+    apply(bodies, p, p.px, p.py)
 
 
-# ---- a free-body stepper for the spec's own sanity test (no contacts) ----
-def step_free(bodies, pins, order, dt, gravity, iterations=8):
-    """IntegrateVelocity (ref: World.cpp:39-55), the pins, IntegratePosition (ref: World.cpp:57-70) on dynamic bodies; float32.
-    Returns the largest |C| the prestep saw."""
-    dt = F(dt)
-    for i in range(len(bodies)):
-        if bodies["inv_mass"][i] != 0:
-            bodies["velocity"]["y"][i] = F(bodies["velocity"]["y"][i]) + F(gravity) * dt
-    worst = solve(bodies, pins, order, dt, iterations)
-    for i in range(len(bodies)):
-        b = bodies[i]
-        px = F(b["pos"]["x"]) + F(b["velocity"]["x"]) * dt
-        py = F(b["pos"]["y"]) + F(b["velocity"]["y"]) * dt
-        bodies["pos"]["x"][i], bodies["pos"]["y"][i] = px, py
-        ang = -(F(b["angular_velocity"]) * dt)            # ref: World.cpp:63 Rotate(-(... + angularVelocity * dt))
-        c, s = F(np.cos(np.float64(ang))), F(np.sin(np.float64(ang)))
-        xx, xy = F(b["xv"]["x"]), F(b["xv"]["y"])
-        nx, ny = xx * c - xy * s, xx * s + xy * c
-        n = F(np.sqrt(np.float64(nx * nx + ny * ny)))
-        nx, ny = nx / n, ny / n
-        bodies["xv"]["x"][i], bodies["xv"]["y"][i] = nx, ny
-        bodies["yv"]["x"][i], bodies["yv"]["y"][i] = -ny, nx
-    return worst
+def store(pins, k, p):
+    pins["impulse"][k] = (p.px, p.py)
 
 
 def make_bodies(rows):

@@ -233,3 +233,10 @@ def motor_with_idle_limit(m):
 
 NAMES = tuple(CASES)
 assert len(ON_A_COMPARISON) * 6 <= len(NAMES)
+
+
+def state_of(w):
+    """a slider's prestep record as the cases' `expect_sliders` names it"""
+    if not w.active:
+        return "inactive"
+    return "P" + ("L" if w.lrow else "") + ("M" if w.mrow else "") + ("-idle" if w.idle else "")

@@ -1,6 +1,6 @@
-"""The pass over pins, links, angles and sliders (include/phyx_amd.h SLIDERS) in float64, written from the mechanics with the means
+"""The sliders (include/phyx_amd.h SLIDERS) for the pass in float64 (tests/unit_reference.py), written from the mechanics with the means
 of tests/pin_reference.py - generalised velocities q = (vx, vy, w), point Jacobians, rotation matrices - and not from
-tests/slider_spec.py.  It extends angle_reference.solve to the four kinds.
+tests/slider_spec.py.
 
 A slider holds the carriage's anchor point pa = pos_a + R_a anchor1 on the line through pb = pos_b + R_b anchor2 along n = R_b axis /
 |axis| (the world: R_b = 1).  With e = pa - pb the coordinate along the rail is s = n . e and the distance off it t . e, t = n turned
@@ -20,16 +20,10 @@ Every decision is taken in float64 on float64 positions: a case that sits exactl
 here (tests/slider_corpus.py ON_A_COMPARISON)."""
 import numpy as np
 
-import angle_reference as aref
 import link_reference as lref
 import pin_reference as ref
 
 TWO_PI = lref.TWO_PI
-
-
-class Result:
-    __slots__ = ("q", "pin_impulse", "link_impulse", "link_active", "angle_impulse", "angle_motor_impulse", "angle_lrow", "angle_mrow",
-                 "impulse", "axis_impulse", "motor_impulse", "active", "lrow", "mrow", "s")
 
 
 def rail(st, slider):
@@ -92,119 +86,6 @@ def _slider(st, slider, dt):
         bias = c * t_(dt) * stiff * gamma
     mrow = solvable and bool(force > 0)
     return a, b, s, active, (jta, jtb, kinv_t, (t @ e) * beta), (lrow, jna, jnb, kinv_n, gamma, bias, lo, hi), (mrow, speed, force * t_(dt))
-
-
-def solve(bodies, pins, links, angles, sliders, order, dt, iterations=8, dtype=np.float64):
-    """The pass on copies, in slot order over the units (pins, links, angles, sliders) -> Result: q (n, 3), pin_impulse (pins, 2),
-    link_impulse, link_active (links,), angle_impulse, angle_motor_impulse, angle_lrow, angle_mrow (angles,), impulse, axis_impulse,
-    motor_impulse, active, lrow, mrow, s (sliders,)."""
-    st = ref.State(bodies, dtype)
-    npins, npl = len(pins), len(pins) + len(links)
-    npla = npl + len(angles)
-    out = Result()
-    out.pin_impulse = np.zeros((npins, 2), dtype=dtype)
-    out.link_impulse = np.zeros(len(links), dtype=dtype)
-    out.link_active = np.zeros(len(links), dtype=bool)
-    out.angle_impulse, out.angle_motor_impulse = np.zeros(len(angles), dtype=dtype), np.zeros(len(angles), dtype=dtype)
-    out.angle_lrow, out.angle_mrow = np.zeros(len(angles), dtype=bool), np.zeros(len(angles), dtype=bool)
-    out.impulse, out.axis_impulse, out.motor_impulse, out.s = (np.zeros(len(sliders), dtype=dtype) for _ in range(4))
-    out.active, out.lrow, out.mrow = (np.zeros(len(sliders), dtype=bool) for _ in range(3))
-    beta = dtype(ref.BETA) / dtype(dt)
-    work = []
-    for u in order:
-        u = int(u)
-        if u < npins:
-            a, b, ja, jb, kk, c = ref._constraint(st, pins[u])
-            if ref.well_posed(kk):
-                out.pin_impulse[u] = np.asarray(pins["impulse"][u], dtype=dtype)
-                work.append(("pin", u, a, b, ja, jb, kk, beta * c))
-        elif u < npl:
-            k = u - npins
-            a, b, ja, jb, keff, gamma, bias, lo, hi, active = lref._link(st, links[k], dt)
-            out.link_active[k] = active
-            if active:
-                out.link_impulse[k] = min(max(dtype(links["impulse"][k]), lo), hi)
-                work.append(("link", k, a, b, ja, jb, keff, (gamma, bias, lo, hi)))
-        elif u < npla:
-            k = u - npl
-            a, b, j, kinv, theta, (lrow, gamma, bias, lo, hi), (mrow, speed, mmax) = aref._angle(st, angles[k], dt)
-            out.angle_lrow[k], out.angle_mrow[k] = lrow, mrow
-            if mrow:
-                out.angle_motor_impulse[k] = min(max(dtype(angles["motor_impulse"][k]), -mmax), mmax)
-            if lrow:
-                out.angle_impulse[k] = min(max(dtype(angles["impulse"][k]), lo), hi)
-            if lrow or mrow:
-                work.append(("angle", k, a, b, j, j, kinv, (lrow, gamma, bias, lo, hi, mrow, speed, mmax)))
-        else:
-            k = u - npla
-            a, b, s, active, prow, lrow, mrow = _slider(st, sliders[k], dt)
-            out.s[k], out.active[k], out.lrow[k], out.mrow[k] = s, active, lrow[0], mrow[0]
-            if not active:
-                continue
-            if mrow[0]:
-                out.motor_impulse[k] = min(max(dtype(sliders["motor_impulse"][k]), -mrow[2]), mrow[2])
-            if lrow[0]:
-                out.axis_impulse[k] = min(max(dtype(sliders["axis_impulse"][k]), lrow[6]), lrow[7])
-            out.impulse[k] = dtype(sliders["impulse"][k])
-            work.append(("slider", k, a, b, None, None, None, (prow, lrow, mrow)))
-
-    def push(a, b, ja, jb, p):
-        st.q[a] -= st.w[a] * (ja.T @ p)
-        if b >= 0:
-            st.q[b] += st.w[b] * (jb.T @ p)
-
-    def rel(a, b, ja, jb):
-        v = -(ja @ st.q[a])
-        return v + jb @ st.q[b] if b >= 0 else v
-
-    def scalar_row(acc, k, a, b, ja, jb, keff, gamma, bias, lo, hi):
-        new = acc[k] - (rel(a, b, ja, jb)[0] + bias + gamma * acc[k]) / keff
-        new = min(max(new, lo), hi)
-        push(a, b, ja, jb, np.array([new - acc[k]], dtype=dtype))
-        acc[k] = new
-
-    for kind, k, a, b, ja, jb, kk, rest in work:
-        if kind == "pin":
-            push(a, b, ja, jb, out.pin_impulse[k])
-        elif kind == "link":
-            push(a, b, ja, jb, out.link_impulse[k:k + 1])
-        elif kind == "angle":
-            if rest[5]:
-                push(a, b, ja, jb, out.angle_motor_impulse[k:k + 1])
-            if rest[0]:
-                push(a, b, ja, jb, out.angle_impulse[k:k + 1])
-        else:
-            prow, lrow, mrow = rest
-            if mrow[0]:
-                push(a, b, lrow[1], lrow[2], out.motor_impulse[k:k + 1])
-            if lrow[0]:
-                push(a, b, lrow[1], lrow[2], out.axis_impulse[k:k + 1])
-            push(a, b, prow[0], prow[1], out.impulse[k:k + 1])
-    with np.errstate(all="ignore"):
-        for _ in range(int(iterations)):
-            for kind, k, a, b, ja, jb, kk, rest in work:
-                if kind == "pin":
-                    dp = np.linalg.solve(kk, -(rel(a, b, ja, jb) + rest)).astype(dtype)
-                    out.pin_impulse[k] += dp
-                    push(a, b, ja, jb, dp)
-                elif kind == "link":
-                    gamma, bias, lo, hi = rest
-                    scalar_row(out.link_impulse, k, a, b, ja, jb, kk, gamma, bias, lo, hi)
-                elif kind == "angle":
-                    lrow, gamma, bias, lo, hi, mrow, speed, mmax = rest
-                    if mrow:
-                        scalar_row(out.angle_motor_impulse, k, a, b, ja, jb, kk, 0, -speed, -mmax, mmax)
-                    if lrow:
-                        scalar_row(out.angle_impulse, k, a, b, ja, jb, kk + gamma, gamma, bias, lo, hi)
-                else:
-                    (jta, jtb, kinv_t, bias_t), (lrow, jna, jnb, kinv_n, gamma, bias, lo, hi), (mrow, speed, mmax) = rest
-                    if mrow:
-                        scalar_row(out.motor_impulse, k, a, b, jna, jnb, kinv_n, 0, -speed, -mmax, mmax)
-                    if lrow:
-                        scalar_row(out.axis_impulse, k, a, b, jna, jnb, kinv_n + gamma, gamma, bias, lo, hi)
-                    scalar_row(out.impulse, k, a, b, jta, jtb, kinv_t, 0, bias_t, -np.inf, np.inf)
-    out.q = st.q
-    return out
 
 
 deviation = lref.deviation

@@ -37,16 +37,14 @@ The rows:
 The warm start applies M's clamped impulse, then L's, then P's, each where its row is on.  A sweep is M, then L, then P, each on the
 velocities the row before left: the hard row has the last word.
 
-solve_units(bodies, pins, links, angles, sliders, order, dt, iterations) is the whole pass over the units: the pins, then the links,
+unit_spec.solve_units(bodies, lists, order, dt, iterations) is the whole pass over the units: the pins, then the links,
 then the angles, then the sliders.  The first three go through pin_spec / link_spec / angle_spec unchanged.
 """
 import numpy as np
 
-import angle_spec
-import link_spec
 import pin_spec
 from link_spec import clamp, TWO_PI
-from pin_spec import F, BETA
+from pin_spec import F
 
 INF = F(np.inf)
 AXIS_FLOOR = F(2.0 ** -20)      # add's rule: axis.x^2 + axis.y^2 > 2^-20
@@ -216,75 +214,8 @@ def sweep(bodies, p):
     apply(bodies, p, d * -p.ny, d * p.nx)
 
 
-def solve_units(bodies, pins, links, angles, sliders, order, dt, iterations=8):
-    """The whole pass, in place: bodies' velocities and every list's impulses.  Returns (the links' work records in link order, the
-    angles' in angle order, the sliders' in slider order)."""
-    npins, npl = len(pins), len(pins) + len(links)
-    npla = npl + len(angles)
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        beta = BETA / F(dt)
-        work = []
-        for u in order:
-            u = int(u)
-            if u < npins:
-                work.append((u, pin_spec.prestep(bodies, pins[u], beta)))
-            elif u < npl:
-                work.append((u, link_spec.prestep(bodies, links[u - npins], beta, dt)))
-            elif u < npla:
-                work.append((u, angle_spec.prestep(bodies, angles[u - npl], beta, dt)))
-            else:
-                work.append((u, prestep(bodies, sliders[u - npla], beta, dt)))
-        for u, p in work:
-            if p.active:
-                if u < npins:
-                    pin_spec.apply(bodies, p, p.px, p.py)
-                elif u < npl:
-                    link_spec.apply(bodies, p, p.lam)
-                elif u < npla:
-                    angle_spec.warm(bodies, p)
-                else:
-                    warm(bodies, p)
-        for _ in range(int(iterations)):
-            for u, p in work:
-                if p.active:
-                    if u < npins:
-                        pin_spec.sweep(bodies, p)
-                    elif u < npl:
-                        link_spec.sweep(bodies, p)
-                    elif u < npla:
-                        angle_spec.sweep(bodies, p)
-                    else:
-                        sweep(bodies, p)
-        by_link, by_angle, by_slider = [None] * len(links), [None] * len(angles), [None] * len(sliders)
-        for u, p in work:
-            if u < npins:
-                pins["impulse"][u] = (p.px, p.py)
-            elif u < npl:
-                links["impulse"][u - npins] = p.lam
-                by_link[u - npins] = p
-            elif u < npla:
-                angles["impulse"][u - npl], angles["motor_impulse"][u - npl] = p.lam, p.mlam
-                by_angle[u - npl] = p
-            else:
-                k = u - npla
-                sliders["impulse"][k], sliders["axis_impulse"][k], sliders["motor_impulse"][k] = p.plam, p.lam, p.mlam
-                by_slider[k] = p
-    return by_link, by_angle, by_slider
-
-
-def step_free(bodies, pins, links, angles, sliders, order, dt, gravity, iterations=8, force=None):
-    """angle_spec.step_free with the four kinds in the pass: IntegrateVelocity (with `force`: per body (fx, fy), v += inv_mass force dt,
-    the test's own constant force), the units, IntegratePosition; no contacts."""
-    dt = F(dt)
-    for i in range(len(bodies)):
-        if bodies["inv_mass"][i] != 0:
-            bodies["velocity"]["y"][i] = F(bodies["velocity"]["y"][i]) + F(gravity) * dt
-            if force is not None:
-                bodies["velocity"]["x"][i] = F(bodies["velocity"]["x"][i]) + F(F(bodies["inv_mass"][i]) * F(force[i][0])) * dt
-                bodies["velocity"]["y"][i] = F(bodies["velocity"]["y"][i]) + F(F(bodies["inv_mass"][i]) * F(force[i][1])) * dt
-    work = solve_units(bodies, pins, links, angles, sliders, order, dt, iterations)
-    angle_spec._integrate_position(bodies, dt)
-    return work
+def store(sliders, k, p):
+    sliders["impulse"][k], sliders["axis_impulse"][k], sliders["motor_impulse"][k] = p.plam, p.lam, p.mlam
 
 
 def make_sliders(rows):

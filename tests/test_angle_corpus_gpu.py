@@ -1,13 +1,13 @@
 """The angle corpus on the device (tests/angle_corpus.py): every case, none left out, through k_solve_pins plain and tethered to a pin
 and a link (the three kinds in one class sequence), and tethered a second time under PHX_PIN_GROUP_PINS=1 through the trailing
-group's kernels (k_pin_prestep / k_pin_class); the lockstep of tests/test_angles_gpu.py, byte for byte against the spec
+group's kernels (k_pin_prestep / k_pin_class); the lockstep of tests/unit_lockstep.py, byte for byte against the spec
 (tests/angle_spec.py).  The two cases whose bodies are all static have no component to exceed the cap and run on the LDS path only."""
 import pytest
 
 import phyx_amd
 import angle_corpus
-from test_angles_gpu import _cfg, _check, _step
-from test_angles_cpu import _state
+import unit_lockstep as ul
+from unit_spec import ANGLE
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +23,15 @@ def test_case_on_the_device(oracle, built_lib, monkeypatch, name, path):
         monkeypatch.setenv("PHX_PIN_GROUP_PINS", "1")
     pw, ow = m.device_world(phyx_amd), m.oracle_world(oracle)
     assert pw.bodies.tobytes() == ow.bodies().tobytes()
-    pins, links, angles, cfg = m.pins, m.links, m.angles, _cfg()
+    units, cfg = ul.lists(pins=m.pins, links=m.links, angles=m.angles), ul.cfg()
     sched = pw.pin_schedule()
     if path == "cap1":
         assert sched["lds_groups"] == 0 and len(sched["group_offsets"]) == 2, "the whole case in the trailing group"
     elif name not in NO_COMPONENT:
         assert sched["lds_groups"] >= 1
     for s in range(m.steps):
-        _, work = _step(oracle, pw, ow, cfg, pins, links, angles)
+        _, work = ul.step(oracle, pw, ow, cfg, units)
         assert pw.counts()[1] == 0, "bodies touch at step %d" % s
         if s == 0:
-            assert [_state(w) for w in work] == m.expect_angles
-        _check(pw, ow, pins, links, angles, s)
+            assert [angle_corpus.rows_of(w) for w in work[ANGLE]] == m.expect_angles
+        ul.check(pw, ow, units, s)

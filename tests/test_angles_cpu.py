@@ -10,9 +10,10 @@ from phyx_amd import api
 import angle_corpus
 import angle_reference as aref
 import angle_spec
-import link_spec
 import pin_reference as ref
 import pin_spec
+import unit_reference
+import unit_spec
 
 F = np.float32
 DT = 1.0 / 60.0
@@ -46,7 +47,7 @@ def _box(angle=0.0, w=0.0, count=1):
 
 
 def test_the_sign_of_theta_against_the_integrator():
-    """d theta / dt = wB - wA, through link_spec.step_free's IntegratePosition: a free body2 with w > 0 gains w dt of theta per step
+    """d theta / dt = wB - wA, through unit_spec.step_free's IntegratePosition: a free body2 with w > 0 gains w dt of theta per step
     against a resting body1; against the world the body is body1 and the world is B, so there it loses w dt.  The reference's
     relative_angle must move the same way."""
     w, steps = 0.9, 20
@@ -58,7 +59,7 @@ def test_the_sign_of_theta_against_the_integrator():
         got_world.append(float(angle_spec.theta(b, 1, -1)))
         st = ref.State(b, np.float64)
         got_ref.append((float(aref.relative_angle(st, 0, 1)), float(aref.relative_angle(st, 1, -1))))
-        link_spec.step_free(b, NO_PINS, NO_LINKS, [], DT, 0.0)
+        unit_spec.step_free(b, [], [], DT, 0.0)
     want = w * DT * np.arange(steps + 1)
     assert np.abs(np.array(got) - want).max() < 1e-5, "theta of a free body2 gains w dt per step"
     assert np.abs(np.array(got_world) + want).max() < 1e-5, "against the world (the body is body1) theta loses w dt per step"
@@ -72,7 +73,7 @@ def _run(angle_row, steps, angle=0.0, w=0.0, torque=0.0):
     angles = angle_spec.make_angles([angle_row])
     works, states = [], []
     for _ in range(steps):
-        _, by_angle = angle_spec.step_free(b, NO_PINS, NO_LINKS, angles, [0], DT, 0.0, torque=[torque])
+        by_angle = unit_spec.step_free(b, [NO_PINS, NO_LINKS, angles], [0], DT, 0.0, torque=[torque])[unit_spec.ANGLE]
         works.append(by_angle[0])
         states.append(b.tobytes())
     return works, states, angles, b
@@ -170,12 +171,6 @@ def _order(m):
     return api.pin_schedule(b1, b2, st)["order"]
 
 
-def _state(w):
-    if w.lrow or w.mrow:
-        return ("L" if w.lrow else "") + ("M" if w.mrow else "")
-    return "idle" if w.idle else "inactive"
-
-
 @pytest.mark.parametrize("tether", [False, True], ids=["plain", "tethered"])
 @pytest.mark.parametrize("name", angle_corpus.NAMES)
 def test_case_reaches_what_it_claims(built_lib, oracle, name, tether):
@@ -183,8 +178,8 @@ def test_case_reaches_what_it_claims(built_lib, oracle, name, tether):
     bodies = _pre_solve_bodies(oracle, m)
     before = bodies.copy()
     pins, links, angles = m.pins, m.links, m.angles
-    _, work = angle_spec.solve_units(bodies, pins, links, angles, _order(m), DT, 8)
-    assert [_state(w) for w in work] == m.expect_angles
+    work = unit_spec.solve_units(bodies, [pins, links, angles], _order(m), DT, 8)[unit_spec.ANGLE]
+    assert [angle_corpus.rows_of(w) for w in work] == m.expect_angles
     for k, w in enumerate(work):
         if not w.lrow:
             assert angles["impulse"][k] == 0, "a row that is off reads impulse 0"
@@ -247,17 +242,17 @@ def _impulses(angles):
     return np.stack([angles["impulse"], angles["motor_impulse"]], axis=1).astype(np.float64)
 
 
-def _compare(bodies, pins, links, angles, order, what, impulses=True):
-    exact = aref.solve(bodies, pins, links, angles, order, DT, 8, np.float64)
-    single = aref.solve(bodies, pins, links, angles, order, DT, 8, np.float32)
-    b, p, l, a = bodies.copy(), pins.copy(), links.copy(), angles.copy()
-    _, work = angle_spec.solve_units(b, p, l, a, order, DT, 8)
-    assert [w.lrow for w in work] == exact.lrow.tolist() and [w.mrow for w in work] == exact.mrow.tolist(), "%s: the reference decides a kind otherwise" % what
+def _compare(bodies, lists, order, what, impulses=True):
+    exact = unit_reference.solve(bodies, lists, order, DT, 8, np.float64)
+    single = unit_reference.solve(bodies, lists, order, DT, 8, np.float32)
+    b, own = bodies.copy(), [units.copy() for units in lists]
+    work = unit_spec.solve_units(b, own, order, DT, 8)[unit_spec.ANGLE]
+    assert [w.lrow for w in work] == exact.angle_lrow.tolist() and [w.mrow for w in work] == exact.angle_mrow.tolist(), "%s: the reference decides a kind otherwise" % what
     if not impulses:
         return 0.0
-    want = np.stack([exact.impulse, exact.motor_impulse], axis=1)
-    noise = max(ref.deviation(np.stack([single.impulse, single.motor_impulse], axis=1), want), ULP)
-    dev = ref.deviation(_impulses(a), want)
+    want = np.stack([exact.angle_impulse, exact.angle_motor_impulse], axis=1)
+    noise = max(ref.deviation(np.stack([single.angle_impulse, single.angle_motor_impulse], axis=1), want), ULP)
+    dev = ref.deviation(_impulses(own[unit_spec.ANGLE]), want)
     qnoise = max(ref.deviation(single.q, exact.q), ULP)
     qdev = ref.deviation(ref.velocities(b), exact.q)
     print("%-44s impulses: noise %.3g spec %.3g ratio %.2f   velocities: ratio %.2f" % (what, noise, dev, dev / noise, qdev / qnoise))
@@ -283,11 +278,11 @@ def _scenes():
 def test_spec_against_the_float64_reference(built_lib, oracle):
     worst = 0.0
     for name, b, angles in _scenes():
-        worst = max(worst, _compare(b, NO_PINS, NO_LINKS, angles, [0], "scene " + name))
+        worst = max(worst, _compare(b, [NO_PINS, NO_LINKS, angles], [0], "scene " + name))
     for name in angle_corpus.NAMES:
         for tether in (False, True):
             m = angle_corpus.build(name, tether)
-            worst = max(worst, _compare(_pre_solve_bodies(oracle, m), m.pins, m.links, m.angles, _order(m), name + (" tethered" if tether else ""),
+            worst = max(worst, _compare(_pre_solve_bodies(oracle, m), [m.pins, m.links, m.angles], _order(m), name + (" tethered" if tether else ""),
                                         impulses=name not in angle_corpus.ON_A_COMPARISON))
     print("worst ratio %.2f" % worst)
     assert worst <= MARGIN

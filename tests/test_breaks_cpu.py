@@ -62,14 +62,14 @@ def _one_body(kind):
 def _run(kind, limit, steps, dt=DT):
     """-> (per step the events, per step R of the loaded unit before the step's removals, the lists at the end)"""
     bodies, lists, k = _one_body(kind)
-    limits = break_spec.no_limits(*lists)
+    limits = break_spec.no_limits(lists)
     if limit is not None:
         limits[k][0] = limit
     events, loads = [], []
     for s in range(steps):
         before = [l.copy() for l in lists]
-        ev, after, kept = break_spec.step_free(bodies, *before, limits, None, dt, G, step=s)
-        loads.append(break_spec.reactions(*before)[k][0] if len(before[k]) else None)
+        ev, after, kept = break_spec.step_free(bodies, before, limits, None, dt, G, step=s)
+        loads.append(break_spec.reactions(before)[k][0] if len(before[k]) else None)
         events.append(ev)
         lists, limits = after, kept
     return events, loads, lists
@@ -115,10 +115,10 @@ def test_a_nan_never_breaks_and_an_idle_unit_has_no_reaction():
     pins = _pins([(0, -1, O, O), (1, -1, O, O)])
     pins["impulse"][0] = (np.nan, 1.0)
     lists = [pins, link_spec.make_links([]), angle_spec.make_angles([]), slider_spec.make_sliders([])]
-    limits = break_spec.no_limits(*lists)
+    limits = break_spec.no_limits(lists)
     limits[0][:] = 1.0
-    assert len(break_spec.breaks(*lists, limits, DT)) == 0
-    assert break_spec.reactions(*lists)[0][1] == 0
+    assert len(break_spec.breaks(lists, limits, DT)) == 0
+    assert break_spec.reactions(lists)[0][1] == 0
 
 
 # ---- settle ----
@@ -128,14 +128,14 @@ def test_settle_is_remove():
     links = link_spec.make_links([(i, i + 1, O, O, 10.0, 10.0) for i in range(5)])
     links["impulse"] = -(np.arange(5) + 1.0)
     lists = [pins, links, angle_spec.make_angles([]), slider_spec.make_sliders([])]
-    limits = break_spec.no_limits(*lists)
+    limits = break_spec.no_limits(lists)
     limits[0][:] = [0.5, 100.0, 0.5, 200.0, 0.5]                 # the first, the middle and the last pin break at dt = 1
     limits[1][:] = [10.0, 20.0, 2.5, 40.0, 50.0]                 # and link 2
-    events = break_spec.breaks(*lists, limits, 1.0, step=7)
+    events = break_spec.breaks(lists, limits, 1.0, step=7)
     assert [(e["kind"], e["index"]) for e in events] == [(0, 0), (0, 2), (0, 4), (1, 2)], "(kind, index) ascending"
     assert set(events["step"]) == {7} and list(events["body1"]) == [0, 2, 4, 2] and list(events["body2"]) == [-1, -1, -1, 3]
     assert list(events["reaction"]) == [1.0, 3.0, 5.0, 3.0]
-    after, kept = break_spec.settle(*lists, limits, events)
+    after, kept = break_spec.settle(lists, limits, events)
     assert after[0].tobytes() == np.delete(pins, [0, 2, 4]).tobytes() and after[1].tobytes() == np.delete(links, [2]).tobytes()
     assert list(kept[0]) == [100.0, 200.0] and list(kept[1]) == [10.0, 20.0, 40.0, 50.0], "the limits follow their units"
     assert len(after[2]) == len(after[3]) == len(kept[2]) == len(kept[3]) == 0

@@ -7,7 +7,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# The same scene, the same cursor and 16 sweeps through tests/pin_spec.py and tests/link_spec.py (link_spec.step_free: no contacts, and
+# The same scene, the same cursor and 16 sweeps through tests/pin_spec.py and tests/link_spec.py (unit_spec.step_free: no contacts, and
 # none forms in the example either), 600 steps on the CPU: the largest pin separation was 0.1704, the largest rod length error 0.0556.
 # The bounds are twice those.
 PIN_SEPARATION = 2.0 * 0.1704

@@ -1,5 +1,5 @@
 """The link corpus on the device (tests/link_corpus.py): every case through k_solve_pins and, tethered, a second time under
-PHX_PIN_GROUP_PINS=1 through the trailing group's kernels (k_pin_prestep / k_pin_class); the lockstep of tests/test_links_gpu.py, byte
+PHX_PIN_GROUP_PINS=1 through the trailing group's kernels (k_pin_prestep / k_pin_class); the lockstep of tests/unit_lockstep.py, byte
 for byte against the spec (tests/link_spec.py) on velocities and impulses.  The two cases that overflow compare NaN as NaN: which NaN a
 processor makes of inf - inf is its own affair, that it makes one is the spec's."""
 import numpy as np
@@ -7,7 +7,8 @@ import pytest
 
 import phyx_amd
 import link_corpus
-from test_links_gpu import _cfg, _check, _step
+import unit_lockstep as ul
+from unit_spec import LINK
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,8 @@ def test_case_on_the_device(oracle, built_lib, monkeypatch, name, path):
     if path == "cap1":
         monkeypatch.setenv("PHX_PIN_GROUP_PINS", "1")
     pw, ow = m.device_world(phyx_amd), m.oracle_world(oracle)
-    pins, links, cfg = m.pins, m.links, _cfg()
+    links, cfg = m.links, ul.cfg()
+    units = ul.lists(pins=m.pins, links=links)
     sched = pw.pin_schedule()
     if path == "cap1":
         assert sched["lds_groups"] == 0 and len(sched["group_offsets"]) == 2, "the whole case in the trailing group"
@@ -42,10 +44,10 @@ def test_case_on_the_device(oracle, built_lib, monkeypatch, name, path):
             k, anchors = m.edit
             pw.set_link_anchors([k], np.array([anchors], dtype=np.float32))
             links["anchor1"][k], links["anchor2"][k] = anchors[:2], anchors[2:]
-        _, work = _step(oracle, pw, ow, cfg, pins, links)
+        _, work = ul.step(oracle, pw, ow, cfg, units)
         assert pw.counts()[1] == 0, "bodies touch at step %d" % s
         if s == 0:
-            assert ["active" if w.active else ("idle" if w.idle else "inactive") for w in work] == m.expect
+            assert [link_corpus.state_of(w) for w in work[LINK]] == m.expect
         if s == 1 and m.edit:
             assert not np.isfinite(links["impulse"][m.edit[0]]), "the edit did not overflow the impulse"
             got, want = pw.bodies, ow.bodies()
@@ -54,4 +56,4 @@ def test_case_on_the_device(oracle, built_lib, monkeypatch, name, path):
             assert _same_numbers(pw.links()["impulse"], links["impulse"]), "impulses differ at step %d" % s
             assert np.isinf(_floats(got["velocity"])).any() or np.isnan(_floats(got["velocity"])).any()
         else:
-            _check(pw, ow, pins, links, s)
+            ul.check(pw, ow, units, s)

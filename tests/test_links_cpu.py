@@ -12,6 +12,8 @@ import link_reference as lref
 import link_spec
 import pin_corpus
 import pin_spec
+import unit_reference
+import unit_spec
 
 F = np.float32
 DT = 1.0 / 60.0
@@ -42,8 +44,8 @@ def _one_body(link, steps, pos, gravity=G):
     none = link_spec.make_links([])
     out, fall = [], []
     for _ in range(steps):
-        w = link_spec.step_free(b, NO_PINS, links, [0], DT, gravity)[0]
-        link_spec.step_free(free, NO_PINS, none, [], DT, gravity)
+        w = unit_spec.step_free(b, [NO_PINS, links], [0], DT, gravity)[unit_spec.LINK][0]
+        unit_spec.step_free(free, [NO_PINS, none], [], DT, gravity)
         out.append((w, b["pos"].copy().tobytes()))
         fall.append(free["pos"].copy().tobytes())
     return out, fall, b
@@ -118,10 +120,6 @@ def _order(m):
     return api.pin_schedule(b1, b2, st)["order"]
 
 
-def _state(w):
-    return "active" if w.active else ("idle" if w.idle else "inactive")
-
-
 @pytest.mark.parametrize("tether", [False, True], ids=["plain", "tethered"])
 @pytest.mark.parametrize("name", link_corpus.NAMES)
 def test_case_reaches_what_it_claims(built_lib, oracle, name, tether):
@@ -129,8 +127,8 @@ def test_case_reaches_what_it_claims(built_lib, oracle, name, tether):
     bodies = _pre_solve_bodies(oracle, m)
     before = bodies.copy()
     pins, links = m.pins, m.links
-    work = link_spec.solve_units(bodies, pins, links, _order(m), DT, 8)
-    assert [_state(w) for w in work] == m.expect
+    work = unit_spec.solve_units(bodies, [pins, links], _order(m), DT, 8)[unit_spec.LINK]
+    assert [link_corpus.state_of(w) for w in work] == m.expect
     for k, w in enumerate(work):
         if not w.active:
             assert links["impulse"][k] == 0, "an inactive or idle link reads impulse 0"
@@ -173,17 +171,17 @@ def _scenes():
         b = pin_spec.make_bodies([(pos[0], pos[1], 2.0, 2.0, False)])
         links = link_spec.make_links([link])
         for _ in range(steps):
-            link_spec.step_free(b, NO_PINS, links, [0], DT, gravity)
+            unit_spec.step_free(b, [NO_PINS, links], [0], DT, gravity)
         b["velocity"]["y"][0] = F(b["velocity"]["y"][0]) + F(gravity) * F(DT)
         yield b, links
 
 
-def _compare(bodies, pins, links, order, what):
-    exact = lref.solve(bodies, pins, links, order, DT, 8)
-    b, p, l = bodies.copy(), pins.copy(), links.copy()
-    work = link_spec.solve_units(b, p, l, order, DT, 8)
-    assert [w.active for w in work] == exact.active.tolist(), "%s: the reference decides a kind otherwise" % what
-    dev = lref.deviation(l["impulse"], exact.impulse)
+def _compare(bodies, lists, order, what):
+    exact = unit_reference.solve(bodies, lists, order, DT, 8)
+    own = [units.copy() for units in lists]
+    work = unit_spec.solve_units(bodies.copy(), own, order, DT, 8)[unit_spec.LINK]
+    assert [w.active for w in work] == exact.link_active.tolist(), "%s: the reference decides a kind otherwise" % what
+    dev = lref.deviation(own[unit_spec.LINK]["impulse"], exact.link_impulse)
     print("%-40s %.3g" % (what, dev))
     assert dev <= BOUND, what
     return dev
@@ -192,9 +190,9 @@ def _compare(bodies, pins, links, order, what):
 def test_spec_against_the_float64_reference(built_lib, oracle):
     worst = 0.0
     for k, (b, links) in enumerate(_scenes()):
-        worst = max(worst, _compare(b, NO_PINS, links, [0], "scene %d" % k))
+        worst = max(worst, _compare(b, [NO_PINS, links], [0], "scene %d" % k))
     for name in link_corpus.NAMES:                         # (none left out: link_corpus.ON_A_COMPARISON)
         for tether in (False, True):
             m = link_corpus.build(name, tether)
-            worst = max(worst, _compare(_pre_solve_bodies(oracle, m), m.pins, m.links, _order(m), name + (" tethered" if tether else "")))
+            worst = max(worst, _compare(_pre_solve_bodies(oracle, m), [m.pins, m.links], _order(m), name + (" tethered" if tether else "")))
     print("worst %.3g" % worst)

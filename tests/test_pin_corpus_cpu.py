@@ -11,13 +11,13 @@ import pytest
 
 from phyx_amd import api
 import pin_corpus
+from pin_corpus import CONSERVING, INACTIVE, MARGIN, ONE_PIN, U, ULP, check_momentum, check_residual, check_the_anchor_is_followed
 import pin_reference as ref
 import pin_spec
+import unit_reference
+import unit_spec
 
 DT = pin_corpus.DT
-ULP = 2.0 ** -23
-U = 2.0 ** -24                  # one float32 rounding
-MARGIN = 8.0
 
 
 def _pre_solve_bodies(oracle, m, gravity=None):
@@ -41,8 +41,8 @@ def _order(m, cap=None):
 def noise_and_deviation(bodies, pins, order, iterations, q):
     """-> (the float64 result, the float32 result, the reference's own float32-vs-float64 deviation floored at an ulp, the deviation
     of q from float64)"""
-    exact = ref.solve(bodies, pins, order, DT, iterations, np.float64)
-    single = ref.solve(bodies, pins, order, DT, iterations, np.float32)
+    exact = unit_reference.solve(bodies, [pins], order, DT, iterations, np.float64)
+    single = unit_reference.solve(bodies, [pins], order, DT, iterations, np.float32)
     return exact, single, max(ref.deviation(single.q, exact.q), ULP), ref.deviation(q, exact.q)
 
 
@@ -87,7 +87,7 @@ def free_steps(oracle, m, steps):
     for s in range(steps):
         ow.pre_solve(DT)
         assert len(ow.manifolds()) == 0, "%s: bodies touch at step %d" % (m.name, s)
-        pin_spec.solve(ow.bodies(), pins, order, DT, 8)
+        unit_spec.solve_units(ow.bodies(), [pins], order, DT, 8)
         ow.integrate_position(DT)
     return ow, pins
 
@@ -98,25 +98,6 @@ def test_no_contact_forms_in_the_steps_a_motif_runs(built_lib, oracle, name):
     ow, pins = free_steps(oracle, m, m.steps + 1)
     b = ow.bodies()
     assert np.isfinite(b["pos"]["x"]).all() and np.isfinite(b["velocity"]["x"]).all() and np.isfinite(pins["impulse"]).all()
-
-
-def check_the_anchor_is_followed(m, start, bodies, steps):
-    """kinematic_anchor: IntegratePosition moved the static body by its velocities, and the bodies pinned to it went along: their
-    pins' separations stay a tenth of the way the pins' points on the anchor travelled (a pin that ignored the anchor's velocity
-    would fall behind by all of it)."""
-    vx, vy, w = m.vel[0]
-    assert abs(float(bodies["pos"]["x"][0]) - float(start["pos"]["x"][0]) - vx * DT * steps) < 1e-4
-    assert abs(float(bodies["pos"]["y"][0]) - float(start["pos"]["y"][0]) - vy * DT * steps) < 1e-4
-    assert bodies["xv"]["x"][0] != start["xv"]["x"][0], "the anchor never turned"
-    st0, st1 = ref.State(start), ref.State(bodies)
-    pins = m.pins
-    for k in range(len(pins)):
-        end = 1 if pins["body1"][k] == 0 else 2
-        a = np.asarray(pins["anchor%d" % end][k], dtype=np.float64)
-        travelled = np.hypot(*((st1.pos[0] + st1.rot[0] @ a) - (st0.pos[0] + st0.rot[0] @ a)))
-        apart = np.hypot(*ref._constraint(st1, pins[k])[5])
-        print("pin %d: its point on the anchor travelled %.4g, the pin is %.4g apart" % (k, travelled, apart))
-        assert travelled > 0.3 and apart < 0.1 * travelled
 
 
 def test_the_pinned_bodies_follow_a_kinematic_anchor(built_lib, oracle):
@@ -134,16 +115,16 @@ def test_spec_against_the_float64_reference(built_lib, oracle, name, iterations)
     before = _pre_solve_bodies(oracle, m)
     order = _order(m)["order"]
     bodies, pins = before.copy(), m.pins
-    pin_spec.solve(bodies, pins, order, DT, iterations)
+    unit_spec.solve_units(bodies, [pins], order, DT, iterations)
     exact, single, noise, dev = noise_and_deviation(before, m.pins, order, iterations, ref.velocities(bodies))
-    impulse_noise = max(ref.deviation(single.impulse, exact.impulse), ULP)
+    impulse_noise = max(ref.deviation(single.pin_impulse, exact.pin_impulse), ULP)
     print("%-24s n=%d noise %.3g spec %.3g ratio %.2f%s" % (name, iterations, noise, dev, dev / noise, " x" if noise > pin_corpus.EXCLUDE_ABOVE else ""))
-    assert exact.active.tolist() == [f[0] for f in m.flags], "the reference finds the same pins well posed"
+    assert exact.pin_active.tolist() == [f[0] for f in m.flags], "the reference finds the same pins well posed"
     if noise > pin_corpus.EXCLUDE_ABOVE:
         assert name in pin_corpus.MAY_BE_EXCLUDED, "%s is too ill-conditioned for the comparison (%.3g): only %s may be" % (name, noise, pin_corpus.MAY_BE_EXCLUDED)
         return
     assert dev <= MARGIN * noise
-    assert ref.deviation(pins["impulse"], exact.impulse) <= MARGIN * impulse_noise, "the accumulated impulses"
+    assert ref.deviation(pins["impulse"], exact.pin_impulse) <= MARGIN * impulse_noise, "the accumulated impulses"
 
 
 def test_spec_against_the_float64_reference_on_random_chains(built_lib, oracle):
@@ -154,7 +135,7 @@ def test_spec_against_the_float64_reference_on_random_chains(built_lib, oracle):
             before = _initial_bodies(oracle, m, 0.0)
             order = _order(m)["order"]
             bodies, pins = before.copy(), m.pins
-            pin_spec.solve(bodies, pins, order, DT, iterations)
+            unit_spec.solve_units(bodies, [pins], order, DT, iterations)
             _, _, noise, dev = noise_and_deviation(before, m.pins, order, iterations, ref.velocities(bodies))
             assert noise <= pin_corpus.EXCLUDE_ABOVE, "chain %d is ill-conditioned" % seed
             assert dev <= MARGIN * noise, "chain %d" % seed
@@ -191,7 +172,7 @@ def test_point_jacobian_is_what_the_integrators_do(oracle, integrator, v, w):
         end = _frame(ow.bodies())
     else:
         copy = b.copy()
-        pin_spec.step_free(copy, np.zeros(0, dtype=api.pin_dtype), [], dt, 0.0)
+        unit_spec.step_free(copy, [], [], dt, 0.0)
         end = _frame(copy)
     got = (_carried_point(*end, a) - p0) / dt
     r = p0 - np.array(start[0])
@@ -216,7 +197,7 @@ def test_the_spec_pendulum_never_rises_above_its_release():
     rise = rise64 = -np.inf
     lowest = np.inf
     for _ in range(steps):
-        pin_spec.step_free(bodies, pins, [0], DT, -200.0, iterations=8)
+        unit_spec.step_free(bodies, [pins], [0], DT, -200.0, iterations=8)
         ref.step_free(state, pins64, [0], DT, -200.0, iterations=8)
         rise, rise64 = max(rise, float(bodies["pos"]["y"][0]) - release), max(rise64, float(state["pos"][0, 1]) - release)
         lowest = min(lowest, float(bodies["pos"]["y"][0]))
@@ -227,55 +208,14 @@ def test_the_spec_pendulum_never_rises_above_its_release():
 
 
 # ---- checks without a reference ----
-ONE_PIN = ("pair", "b1_static", "lever100")
-
-
-def check_residual(before, after, pin):
-    """A block solve is exact up to the rounding of its own arithmetic: cond(K) times a few roundings (16: the spec's sweep is
-    about that many operations deep) of the terms the residual is made of, before and after."""
-    start, k, terms0 = ref.residual(before, before, pin, DT)
-    res, _, terms1 = ref.residual(before, after, pin, DT)
-    tol = 16 * U * np.linalg.cond(k) * (terms0 + terms1)
-    print("residual %s (before the sweep %s), tolerance %.3g" % (res, start, tol))
-    assert np.abs(start).max() > 100 * tol, "the pin had nothing to solve"
-    assert np.abs(res).max() <= tol
-
-
 @pytest.mark.parametrize("name", ONE_PIN + tuple("random%d" % s for s in range(20)))
 def test_one_sweep_of_one_pin_leaves_no_residual(built_lib, oracle, name):
     m = pin_corpus.random_chain(int(name[6:]), links=1) if name.startswith("random") else pin_corpus.build(name)
     before = _pre_solve_bodies(oracle, m)
     after, pins = before.copy(), m.pins
     assert len(pins) == 1 and not pins["impulse"].any()
-    pin_spec.solve(after, pins, [0], DT, 1)
+    unit_spec.solve_units(after, [pins], [0], DT, 1)
     check_residual(before, after, m.pins[0])
-
-
-def conserves_momentum(m):
-    b1, b2, st = m.graph()
-    return not any(st) and min(b2) >= 0 and not m.masses
-
-
-CONSERVING = tuple(n for n in pin_corpus.NAMES if conserves_momentum(pin_corpus.build(n)))
-
-
-def check_momentum(m, before, after, impulse, iterations):
-    """sum m v and sum (m x cross v - I w) before and after the pass, in float64.  The two ends of a pin are C apart, so its impulse
-    pair carries the angular momentum C x P: that is taken off.  Every write of a velocity rounds it (two roundings per component),
-    a body is written (iterations + 1) x its pins times: the bound is that many roundings of sum m |v| (sum m |x| |v| + I |w|)."""
-    lin0, ang0 = ref.momenta(before)
-    lin1, ang1 = ref.momenta(after)
-    st = ref.State(before)
-    pins = m.pins
-    for k in range(len(pins)):
-        c = ref._constraint(st, pins[k])[5]
-        ang1 -= c[0] * float(impulse[k][1]) - c[1] * float(impulse[k][0])
-    degree = np.bincount(np.concatenate([pins["body1"], pins["body2"]])).max()
-    s_lin, s_ang = np.maximum(ref.momentum_scale(before), ref.momentum_scale(after))
-    bound = 4 * U * (iterations + 1) * degree
-    print("%s: linear %.3g of %.3g, angular %.3g of %.3g, bound %.3g" % (m.name, np.abs(lin1 - lin0).max(), s_lin, abs(ang1 - ang0), s_ang, bound))
-    assert np.abs(lin1 - lin0).max() <= bound * s_lin
-    assert abs(ang1 - ang0) <= bound * s_ang
 
 
 def test_the_conserving_motifs():
@@ -287,12 +227,9 @@ def test_the_pass_conserves_momentum(built_lib, oracle, name):
     m = pin_corpus.build(name)
     before = _pre_solve_bodies(oracle, m, gravity=0.0)
     after, pins = before.copy(), m.pins
-    pin_spec.solve(after, pins, _order(m)["order"], DT, 8)
+    unit_spec.solve_units(after, [pins], _order(m)["order"], DT, 8)
     assert after["velocity"].tobytes() != before["velocity"].tobytes()
     check_momentum(m, before, after, pins["impulse"], 8)
-
-
-INACTIVE = ("static_static", "static_world", "axle_world", "axle_centre", "axles_in_line")
 
 
 @pytest.mark.parametrize("name", INACTIVE)
@@ -301,7 +238,7 @@ def test_an_inactive_pin_changes_nothing(built_lib, oracle, name):
     before = _pre_solve_bodies(oracle, m)
     after, pins = before.copy(), m.pins
     assert pins["impulse"].any()
-    pin_spec.solve(after, pins, [0], DT, 8)
+    unit_spec.solve_units(after, [pins], [0], DT, 8)
     assert after.tobytes() == before.tobytes()
     assert not pins["impulse"].any(), "an inactive pin reads impulse 0"
 
@@ -319,11 +256,11 @@ def test_a_singular_pin_is_inactive(built_lib, oracle, make):
         p = pin_spec.prestep(before, m.pins[0], beta)
         noisy += bool(np.float32(p.k11) * np.float32(p.k22) - np.float32(p.k12) * np.float32(p.k12) > 0)
         after, pins = before.copy(), m.pins
-        pin_spec.solve(after, pins, [0], DT, 8)
+        unit_spec.solve_units(after, [pins], [0], DT, 8)
         assert not p.active, "case %d is active" % seed
         assert after.tobytes() == before.tobytes(), "case %d: the bodies changed" % seed
         assert not pins["impulse"].any(), "case %d: the impulse reads %s" % (seed, pins["impulse"])
-        assert not ref.solve(before, m.pins, [0], DT, 8).active[0], "the reference finds case %d well posed" % seed
+        assert not unit_reference.solve(before, [m.pins], [0], DT, 8).pin_active[0], "the reference finds case %d well posed" % seed
     print("%s: det > 0 in %d of 200" % (make.__name__, noisy))
     assert noisy > 0, "the cases never produce a positive det: they do not test the floor"
 
@@ -332,6 +269,6 @@ def test_a_wheel_pinned_to_a_dynamic_body_is_active(built_lib, oracle):
     m = pin_corpus.build("axle_dynamic")
     before = _pre_solve_bodies(oracle, m)
     after, pins = before.copy(), m.pins
-    pin_spec.solve(after, pins, _order(m)["order"], DT, 8)
+    unit_spec.solve_units(after, [pins], _order(m)["order"], DT, 8)
     assert pins["impulse"].all() and after["angular_velocity"][0] != before["angular_velocity"][0]
     assert (after["velocity"][0], after["pos"][0]) == (before["velocity"][0], before["pos"][0]), "the axle itself does not move"

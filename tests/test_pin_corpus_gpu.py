@@ -1,6 +1,6 @@
 """The pin corpus on the device (tests/pin_corpus.py): every motif through k_solve_pins on its own schedule and, where it has more than
 one pin, a second time under PHX_PIN_GROUP_PINS=1 through the trailing group's kernels.  Each run is judged twice:
-  - the lockstep of tests/test_pins_gpu.py, byte for byte against the spec (tests/pin_spec.py), for a few steps;
+  - the lockstep of tests/unit_lockstep.py, byte for byte against the spec (tests/pin_spec.py), for a few steps;
   - the first step's velocities against the float64 reference (tests/pin_reference.py) run on the oracle's pre_solve output, within
     8 x the reference's own float32-vs-float64 deviation on that motif (no contact forms, so the velocities after Update are the
     pass's output),
@@ -13,9 +13,9 @@ import phyx_amd
 from phyx_amd import api
 import pin_corpus
 import pin_reference as ref
-from test_pins_gpu import _cfg, _step
-from spawn_lockstep import compare
-from test_pin_corpus_cpu import CONSERVING, INACTIVE, MARGIN, ONE_PIN, ULP, check_momentum, check_residual, check_the_anchor_is_followed
+import unit_reference
+import unit_lockstep as ul
+from pin_corpus import CONSERVING, INACTIVE, MARGIN, ONE_PIN, ULP, check_momentum, check_residual, check_the_anchor_is_followed
 
 pytestmark = pytest.mark.gpu
 
@@ -61,18 +61,17 @@ def test_motif_on_the_device(oracle, built_lib, monkeypatch, name, path, iterati
     probe = m.oracle_world(oracle)
     probe.pre_solve(DT)
     before = probe.bodies().copy()
-    exact = ref.solve(before, m.pins, sched["order"], DT, iterations, np.float64)
-    single = ref.solve(before, m.pins, sched["order"], DT, iterations, np.float32)
+    exact = unit_reference.solve(before, [m.pins], sched["order"], DT, iterations, np.float64)
+    single = unit_reference.solve(before, [m.pins], sched["order"], DT, iterations, np.float32)
     noise = max(ref.deviation(single.q, exact.q), ULP)
-    impulse_noise = max(ref.deviation(single.impulse, exact.impulse), ULP)
+    impulse_noise = max(ref.deviation(single.pin_impulse, exact.pin_impulse), ULP)
 
-    pins, cfg = m.pins, _cfg()
+    pins, cfg = m.pins, ul.cfg()
     steps = min(m.steps, 3) if (name == "hub130" and path == "cap1") else m.steps
     for s in range(steps):
-        _step(oracle, pw, ow, cfg, pins)
+        ul.step(oracle, pw, ow, cfg, [pins])
         assert pw.counts()[1] == 0, "bodies touch at step %d" % s
-        compare(pw, ow, s)
-        assert pw.pins().tobytes() == pins.tobytes(), "pins differ at step %d" % s
+        ul.check(pw, ow, ul.lists(pins=pins), s)
         if s:
             continue
         after = _after_first_step(m, before, pw)
@@ -82,7 +81,7 @@ def test_motif_on_the_device(oracle, built_lib, monkeypatch, name, path, iterati
             assert name in pin_corpus.MAY_BE_EXCLUDED, "%s is too ill-conditioned for the comparison (%.3g)" % (name, noise)
         else:
             assert dev <= MARGIN * noise
-            assert ref.deviation(pw.pins()["impulse"], exact.impulse) <= MARGIN * impulse_noise, "the accumulated impulses"
+            assert ref.deviation(pw.pins()["impulse"], exact.pin_impulse) <= MARGIN * impulse_noise, "the accumulated impulses"
         if name in ONE_PIN and iterations == 1:
             check_residual(before, after, m.pins[0])
         if name in INACTIVE:
@@ -102,7 +101,7 @@ def test_the_pass_conserves_momentum_on_the_device(oracle, built_lib, monkeypatc
     m = pin_corpus.build(name)
     pw, ow, _ = _worlds(oracle, monkeypatch, m, path, 8, gravity=0.0)
     before = ow.bodies().copy()
-    pw.Update(DT, _cfg())
+    pw.Update(DT, ul.cfg())
     assert pw.counts()[1] == 0
     after = _after_first_step(m, before, pw)
     assert after["velocity"].tobytes() != before["velocity"].tobytes()

@@ -8,6 +8,7 @@ import phyx_amd
 from phyx_amd import _lib, api
 import pin_corpus
 import pin_spec
+import unit_spec
 
 SYMBOLS = ("phx_world_add_pins", "phx_world_remove_pins", "phx_world_set_pin_anchors", "phx_world_get_pins", "phx_world_pin_count",
            "phx_world_set_pin_iterations", "phx_world_get_pin_iterations", "phx_world_pin_schedule_builds", "phx_world_get_pin_schedule",
@@ -92,7 +93,7 @@ def test_spec_holds_a_chain_together(name, links):
     order = np.arange(links)
     worst, lowest = 0.0, 300.0
     for _ in range(300):
-        worst = max(worst, pin_spec.step_free(bodies, pins, order, DT, G, iterations=8))
+        worst = max(worst, unit_spec.worst_c(unit_spec.step_free(bodies, [pins], order, DT, G, iterations=8)[unit_spec.PIN]))
         lowest = min(lowest, float(bodies["pos"]["y"].min()))
     print("largest |C| of %s: %.6g" % (name, worst))
     assert np.isfinite(bodies["pos"]["x"]).all() and np.isfinite(bodies["pos"]["y"]).all()
@@ -107,6 +108,6 @@ def test_an_inactive_pin_changes_nothing():
     pins = np.zeros(1, dtype=api.pin_dtype)
     pins[0] = (0, 1, (5.0, 0.0), (-5.0, 0.0), (7.0, -7.0))
     before = bodies.copy()
-    pin_spec.solve(bodies, pins, [0], DT, 8)
+    unit_spec.solve_units(bodies, [pins], [0], DT, 8)
     assert bodies.tobytes() == before.tobytes()
     assert pins["impulse"].tolist() == [[0.0, 0.0]], "an inactive pin reads impulse 0"

@@ -1,104 +1,49 @@
-"""Pins on the device (include/phyx_amd.h PINS) held to their specification, tests/pin_spec.py: the device World and the oracle World in
-lockstep, the spec applied to the oracle's bodies between its pre_solve and its solve on the device's own pin schedule, every byte of
-the state and of the pins' impulses compared after every step; then the schedule's paths, the life cycle by twins, and the refusals."""
+"""Pins on the device (include/phyx_amd.h PINS) held to their specification, tests/pin_spec.py, in the lockstep of
+tests/unit_lockstep.py; then the schedule's paths, the life cycle by twins, and the refusals.  (What every kind of unit has alike is in
+tests/test_units_gpu.py.)"""
 import numpy as np
 import pytest
 
 import phyx_amd
-from phyx_amd import Configuration, PhxError, scenes
+from phyx_amd import PhxError, scenes
 from phyx_amd.api import pin_dtype
-from helpers import oracle_world
-from spawn_lockstep import compare
-import pin_spec
 import removal_spec
+import unit_lockstep as ul
+from unit_lockstep import DT, G, MODES, ERR_INVALID, ERR_STATE, lists
+from unit_scenes import chain as _chain, mixed_world
+from unit_spec import KINDS, PIN
 
 pytestmark = pytest.mark.gpu
 
-DT = 1.0 / 60.0
-G = -200.0
 ITERS = 8
-NAMES = ("bodies", "manifolds", "contact points", "joints")
-MODES = {"single": phyx_amd.ISLAND_SINGLE, "multiple_sloppy": phyx_amd.ISLAND_MULTIPLE_SLOPPY}
-ERR_INVALID, ERR_STATE = -1, -5
-
-
-def _cfg(mode=phyx_amd.ISLAND_MULTIPLE_SLOPPY, iters=15):
-    return Configuration(phyx_amd.SOLVE_AVX2, mode, iters, iters)
-
-
-def _scene(rows):
-    """rows (px, py, half_x, half_y, static) -> a scenes.py dict"""
-    r = np.asarray([(a, b, c, d) for a, b, c, d, _ in rows], dtype=np.float32).reshape(-1, 4)
-    return {"px": r[:, 0].copy(), "py": r[:, 1].copy(), "angle": np.zeros(len(rows), dtype=np.float32), "sx": r[:, 2].copy(), "sy": r[:, 3].copy(),
-            "static": np.asarray([bool(s) for *_, s in rows], dtype=bool)}
 
 
 def _join(base, rows):
-    extra = _scene(rows)
+    extra = ul.scene(rows)
     return {k: np.concatenate([base[k], extra[k]]) for k in ("px", "py", "angle", "sx", "sy", "static")}
 
 
-def _pins(rows):
-    p = np.zeros(len(rows), dtype=pin_dtype)
-    for k, (a, b, a1, a2) in enumerate(rows):
-        p[k] = (a, b, a1, a2, (0.0, 0.0))
-    return p
-
-
-def _chain(first_body, links, top, hang_from=-1, hang_anchor=None, spacing=10.0):
-    """`links` boxes of 6 x 2 laid level with `top`, to its right, body numbers from first_body on; the first hangs from the world point
-    `top` or from the point `hang_anchor` (its own frame) of body `hang_from`.  -> (body rows, pin rows).  The links are short of their
-    joints (pins do not keep neighbours from colliding: only a sharp fold makes them touch)."""
-    h = spacing / 2.0
-    bodies = [(top[0] + spacing * (k + 0.5), top[1], 3.0, 1.0, False) for k in range(links)]
-    pins = [(first_body, hang_from, (-h, 0.0), top if hang_from < 0 else hang_anchor)]
-    pins += [(first_body + k, first_body + k - 1, (-h, 0.0), (h, 0.0)) for k in range(1, links)]
-    return bodies, pins
-
-
-def _worlds(scene, pins, gravity=G, with_oracle=True):
-    pw = phyx_amd.World(0, gravity=gravity)
-    pw.add_scene(scene)
-    got = pw.add_pins(pins)
-    assert got.tolist() == list(range(len(pins)))
-    return pw, (oracle_world(scene, gravity) if with_oracle else None)
-
-
-def _step(oracle, pw, ow, cfg, pins, dt=DT):
-    """spawn_lockstep.step with the pins: 1. pw.Update  2. ow.pre_solve  3. pin_spec on ow.bodies() on the device's own pin schedule
-    4. the oracle's solver on the device's contact schedule  5. ow.integrate_position.  `pins` is the spec's own list."""
-    sched = pw.pin_schedule()
-    assert sorted(sched["order"].tolist()) == list(range(len(pins)))
-    pw.Update(dt, cfg)
-    ow.pre_solve(dt)
-    pin_spec.solve(ow.bodies(), pins, sched["order"], dt, pw.pin_iterations)
-    order, offs = pw.solver.schedule()
-    groups, _ = pw.solver.groups()
-    b, cp, j = ow.bodies(), ow.contact_points(), ow.joints()
-    assert len(order) == len(j)
-    oracle.solver_solve_grouped(b, cp, j, order, offs, groups, cfg.contactIterationsCount, cfg.penetrationIterationsCount, oracle.STAG_COLOUR_SYNC)
-    ow.integrate_position(dt)
-    return sched
+def _worlds(scene, pins):
+    return ul.worlds(scene, lists(pins=pins))
 
 
 def _lockstep(oracle, pw, ow, cfg, pins, steps, watch=slice(None)):
     """-> (the last schedule, the lowest pos.y the bodies `watch` reached)"""
     lowest = np.inf
     for s in range(steps):
-        sched = _step(oracle, pw, ow, cfg, pins)
-        compare(pw, ow, s)
-        assert pw.pins().tobytes() == pins.tobytes(), "pins differ at step %d" % s
+        sched, _ = ul.step(oracle, pw, ow, cfg, lists(pins=pins))
+        ul.check(pw, ow, lists(pins=pins), s)
         lowest = min(lowest, float(ow.bodies()["pos"]["y"][watch].min()))
     return sched, lowest
 
 
 def test_one_body_on_a_world_pin(oracle, built_lib):
     bodies, rows = _chain(0, 1, (0.0, 100.0))
-    pins = _pins(rows)
-    pw, ow = _worlds(_scene(bodies), pins)
+    pins = ul.pins(rows)
+    pw, ow = _worlds(ul.scene(bodies), pins)
     assert pw.pin_iterations == ITERS and pw.pin_count() == 1
     assert pw.pins().tobytes() == pins.tobytes(), "before the first step the pins wait on the host"
-    sched, lowest = _lockstep(oracle, pw, ow, _cfg(), pins, 60)
+    sched, lowest = _lockstep(oracle, pw, ow, ul.cfg(), pins, 60)
     assert sched["lds_groups"] == 1 and len(sched["class_offsets"]) == 2
     assert np.abs(pins["impulse"]).max() > 0 and lowest < 96.0, "the pendulum never swung"
 
@@ -112,9 +57,9 @@ def test_chains_and_pairs(oracle, built_lib):
     bodies += [(200.0, 200.0, 5.0, 5.0, True)]
     b12, p12 = _chain(6, 12, (205.0, 200.0), hang_from=5, hang_anchor=(5.0, 0.0))
     bodies += b12; rows += p12
-    pins = _pins(rows)
-    pw, ow = _worlds(_scene(bodies), pins)
-    sched, lowest = _lockstep(oracle, pw, ow, _cfg(), pins, 40, watch=slice(6, None))
+    pins = ul.pins(rows)
+    pw, ow = _worlds(ul.scene(bodies), pins)
+    sched, lowest = _lockstep(oracle, pw, ow, ul.cfg(), pins, 40, watch=slice(6, None))
     assert sched["lds_groups"] == 1 and len(sched["group_offsets"]) == 2
     assert len(sched["class_offsets"]) - 1 == 2, "chains need two classes"
     b = pw.bodies
@@ -130,7 +75,7 @@ def test_pins_among_contacts(oracle, built_lib, mode):
     n = len(base["px"])
     chain_bodies, rows = _chain(n, 8, (-45.0, 135.0))
     rows += [(4, 5, (0.0, 5.0), (0.0, -5.0))]
-    pins = _pins(rows)
+    pins = ul.pins(rows)
     pw, ow = _worlds(_join(base, chain_bodies), pins)
 
     def at(s):
@@ -142,9 +87,8 @@ def test_pins_among_contacts(oracle, built_lib, mode):
     builds = None
     for s in range(40):
         at(s)
-        _step(oracle, pw, ow, _cfg(MODES[mode]), pins)
-        compare(pw, ow, s)
-        assert pw.pins().tobytes() == pins.tobytes(), "pins differ at step %d" % s
+        ul.step(oracle, pw, ow, ul.cfg(MODES[mode]), lists(pins=pins))
+        ul.check(pw, ow, lists(pins=pins), s)
         builds = builds or pw.pin_schedule_builds()
     assert pw.pin_schedule_builds() == builds == 1, "an anchor edit keeps the schedule"
     m = pw.manifolds
@@ -180,9 +124,9 @@ def test_the_paths(oracle, built_lib, monkeypatch, case):
         bodies, rows = _chain(0, 40, (0.0, 500.0))
         steps = 12
         lds, groups = (0, 1) if case == "chain40_cap16" else (1, 1)
-    pins = _pins(rows)
-    pw, ow = _worlds(_scene(bodies), pins)
-    sched, _ = _lockstep(oracle, pw, ow, _cfg(), pins, steps)
+    pins = ul.pins(rows)
+    pw, ow = _worlds(ul.scene(bodies), pins)
+    sched, _ = _lockstep(oracle, pw, ow, ul.cfg(), pins, steps)
     assert sched["lds_groups"] == lds and len(sched["group_offsets"]) - 1 == groups
     assert np.abs(pins["impulse"]).max() > 0
     if case == "pairs5_chain40_cap16":
@@ -199,24 +143,12 @@ def test_group_pins_knob_refuses_other_values(built_lib, monkeypatch, value):
 
 
 # ---- the life cycle, by twins ----
-def _same(a, b, what):
-    assert a.counts() == b.counts(), "counts differ %s" % what
-    for name, x, y in zip(NAMES, a.state(), b.state()):
-        assert x.tobytes() == y.tobytes(), "%s differ %s" % (name, what)
-    assert a.pins().tobytes() == b.pins().tobytes(), "pins differ %s" % what
-
-
 def _chain_world(links=12, extra_pair=True):
-    bodies, rows = _chain(0, links, (0.0, 300.0))
-    if extra_pair:
-        bodies += [(-100.0, 300.0, 4.0, 1.5, False), (-90.0, 300.0, 4.0, 1.5, False)]
-        rows += [(links, links + 1, (5.0, 1.0), (-5.0, 0.0))]
-    pw, _ = _worlds(_scene(bodies), _pins(rows), with_oracle=False)
-    return pw
+    return mixed_world("pin", links=links, extra_pair=extra_pair)
 
 
 def test_remove_bodies_through_a_chain(built_lib):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pa = _chain_world()
     for _ in range(10):
         pa.Update(DT, cfg)
@@ -224,26 +156,18 @@ def test_remove_bodies_through_a_chain(built_lib):
     removed = [5]
     filtered = removal_spec.filter(state, removed)
     new = removal_spec.new_index(len(state[0]), removed)
-    keep = np.array([new[p["body1"]] >= 0 and (p["body2"] < 0 or new[p["body2"]] >= 0) for p in pins])
-    kept = pins[keep].copy()
-    kept["body1"] = new[kept["body1"]]
-    kept["body2"] = np.where(kept["body2"] < 0, -1, new[np.maximum(kept["body2"], 0)])
+    kept = ul.remapped(pins, new)
     assert len(kept) == len(pins) - 2
     remap = pa.remove_bodies(removed)
     assert remap.tolist() == new.tolist()
     assert pa.pins().tobytes() == kept.tobytes()
-    pb = phyx_amd.World(0, gravity=G)
-    pb.set_state(*filtered[0])
-    pb.add_pins(kept)
-    _same(pa, pb, "right after the removal")
-    for s in range(10):
-        pa.Update(DT, cfg)
-        pb.Update(DT, cfg)
-        _same(pa, pb, "at step %d after the removal" % s)
+    pb = ul.twin(filtered[0], lists(pins=kept))
+    ul.same(pa, pb, "right after the removal")
+    ul.run_twins(pa, pb, 10, "the removal")
 
 
 def test_remove_pins(built_lib):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pa = _chain_world()
     for _ in range(5):
         pa.Update(DT, cfg)
@@ -252,18 +176,12 @@ def test_remove_pins(built_lib):
     pa.remove_pins([12, 3])
     kept = np.delete(pins, [3, 12])
     assert pa.pins().tobytes() == kept.tobytes(), "the others keep their order"
-    pb = phyx_amd.World(0, gravity=G)
-    pb.set_state(*state)
-    pb.add_pins(kept)
-    for s in range(5):
-        pa.Update(DT, cfg)
-        pb.Update(DT, cfg)
-        _same(pa, pb, "at step %d after remove_pins" % s)
+    ul.run_twins(pa, ul.twin(state, lists(pins=kept)), 5, "remove_pins")
     assert pa.pin_schedule_builds() == builds + 1
 
 
 def test_what_rebuilds_the_schedule(built_lib):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pw = _chain_world()
     pw.Update(DT, cfg)
     builds = pw.pin_schedule_builds()
@@ -281,7 +199,7 @@ def test_what_rebuilds_the_schedule(built_lib):
 
 
 def test_a_pin_whose_bodies_became_static(built_lib):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pw = _chain_world(links=3)
     for _ in range(5):
         pw.Update(DT, cfg)
@@ -298,16 +216,8 @@ def test_a_pin_whose_bodies_became_static(built_lib):
     assert np.abs(pins["impulse"][:3]).max() > 0
 
 
-def test_set_state_leaves_no_pin(built_lib):
-    pw = _chain_world()
-    pw.Update(DT, _cfg())
-    pw.set_state(*pw.state())
-    assert pw.pin_count() == 0 and len(pw.pins()) == 0
-    pw.Update(DT, _cfg())
-
-
 def test_save_load_and_fork(built_lib):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pw = _chain_world()
     pw.pin_iterations = 6
     for _ in range(5):
@@ -333,59 +243,31 @@ def test_save_load_and_fork(built_lib):
     assert e.value.status == ERR_STATE and "pins" in str(e.value)
 
 
-def test_a_world_that_lost_its_pins_is_a_world_without(built_lib):
-    cfg = _cfg()
-    sc = scenes.stack(3, 6)
-    pa, pb = phyx_amd.World(0, gravity=G), phyx_amd.World(0, gravity=G)
-    pa.add_scene(sc); pb.add_scene(sc)
-    pa.add_pins(_pins([(1, 2, (0.0, 5.0), (0.0, -5.0)), (3, -1, (0.0, 0.0), (0.0, 50.0))]))
-    pa.remove_pins([0, 1])
-    assert pa.pin_count() == 0
-    for s in range(10):
-        pa.Update(DT, cfg)
-        pb.Update(DT, cfg)
-        for name, x, y in zip(NAMES, pa.state(), pb.state()):
-            assert x.tobytes() == y.tobytes(), "%s differ at step %d" % (name, s)
-    assert pa.pin_schedule_builds() == 0
-    assert pa.save().to_bytes() == pb.save().to_bytes(), "a snapshot without pins is what it was"
-
-
 # ---- the refusals ----
-def _unchanged(pw, before):
-    bodies, pins, builds = before
-    assert pw.bodies.tobytes() == bodies and pw.pins().tobytes() == pins and pw.pin_schedule_builds() == builds
-
-
-def _raw_add(pw, pins, count=None, null=False):
-    import ctypes as C
-    p = np.ascontiguousarray(pins, dtype=pin_dtype)
-    return pw.L.phx_world_add_pins(pw.h, None if null else p.ctypes.data_as(C.c_void_p), len(p) if count is None else count, None)
-
-
 @pytest.mark.parametrize("staged", ["host", "device"])
 def test_rejections_leave_the_world_unchanged(built_lib, staged):
     import ctypes as C
-    cfg = _cfg()
+    cfg = ul.cfg()
     pw = _chain_world(links=4)
     if staged == "device":
         pw.Update(DT, cfg)
     n = pw.counts()[0]
-    before = (pw.bodies.tobytes(), pw.pins().tobytes(), pw.pin_schedule_builds())
+    before = ul.snapshot_of(pw)
     good = (0, 1, (1.0, 0.0), (0.0, 1.0), (0.0, 0.0))
     bad = [(-1, 1), (n, 1), (0, n), (0, -2), (2, 2)]
     for b1, b2 in bad:
         p = np.array([good, (b1, b2, (0.0, 0.0), (0.0, 0.0), (0.0, 0.0))], dtype=pin_dtype)
-        assert _raw_add(pw, p) == ERR_INVALID, (b1, b2)
-        _unchanged(pw, before)
+        assert ul.raw_add(pw, KINDS[PIN], p) == ERR_INVALID, (b1, b2)
+        ul.unchanged(pw, before)
     for field, value in (("anchor1", np.nan), ("anchor2", np.inf), ("impulse", -np.inf)):
         p = np.array([good, good], dtype=pin_dtype)
         p[field][1][1] = value
-        assert _raw_add(pw, p) == ERR_INVALID, field
-        _unchanged(pw, before)
-    assert _raw_add(pw, np.array([good], dtype=pin_dtype), count=-1) == ERR_INVALID
-    assert _raw_add(pw, np.array([good], dtype=pin_dtype), null=True) == ERR_INVALID
-    assert _raw_add(pw, np.zeros(0, dtype=pin_dtype), count=0, null=True) == 0, "an empty call is a true no-op"
-    _unchanged(pw, before)
+        assert ul.raw_add(pw, KINDS[PIN], p) == ERR_INVALID, field
+        ul.unchanged(pw, before)
+    assert ul.raw_add(pw, KINDS[PIN], np.array([good], dtype=pin_dtype), count=-1) == ERR_INVALID
+    assert ul.raw_add(pw, KINDS[PIN], np.array([good], dtype=pin_dtype), null=True) == ERR_INVALID
+    assert ul.raw_add(pw, KINDS[PIN], np.zeros(0, dtype=pin_dtype), count=0, null=True) == 0, "an empty call is a true no-op"
+    ul.unchanged(pw, before)
     np_ = pw.pin_count()
     for which in ([np_], [-1], [1, 1]):
         with pytest.raises(PhxError) as e:
@@ -394,7 +276,7 @@ def test_rejections_leave_the_world_unchanged(built_lib, staged):
         with pytest.raises(PhxError) as e:
             pw.set_pin_anchors(which, np.zeros((len(which), 4), dtype=np.float32))
         assert e.value.status == ERR_INVALID
-        _unchanged(pw, before)
+        ul.unchanged(pw, before)
     with pytest.raises(PhxError) as e:
         pw.set_pin_anchors([0], np.array([[0.0, np.nan, 0.0, 0.0]], dtype=np.float32))
     assert e.value.status == ERR_INVALID
@@ -403,7 +285,7 @@ def test_rejections_leave_the_world_unchanged(built_lib, staged):
     assert pw.L.phx_world_remove_pins(pw.h, idx.ctypes.data_as(C.c_void_p), -1) == ERR_INVALID
     assert pw.L.phx_world_set_pin_anchors(pw.h, idx.ctypes.data_as(C.c_void_p), None, 1) == ERR_INVALID
     pw.remove_pins([]); pw.set_pin_anchors([], np.zeros((0, 4), dtype=np.float32))
-    _unchanged(pw, before)
+    ul.unchanged(pw, before)
     for bad_n in (0, 65, -3):
         with pytest.raises(PhxError) as e:
             pw.pin_iterations = bad_n
@@ -417,39 +299,3 @@ def test_rejections_leave_the_world_unchanged(built_lib, staged):
         assert e.value.status == ERR_STATE
     pw.FinishStep(DT, cfg)
     assert pw.pin_count() == np_ and pw.pin_iterations == ITERS
-
-
-def test_sharded_worlds_carry_no_pins(built_lib):
-    pw = _chain_world(links=3)
-    with pytest.raises(PhxError) as e:
-        pw.set_shard(0, 2)
-    assert e.value.status == ERR_STATE and "pins" in str(e.value)
-    n = pw.counts()[0]
-    with pytest.raises(PhxError) as e:
-        pw.reslab(np.arange(n, dtype=np.int64), n, (-1e9, 1e9))
-    assert e.value.status == ERR_STATE and "pins" in str(e.value)
-    pw.set_shard(0, 1)
-    sharded = phyx_amd.World(0, gravity=G)
-    sharded.add_scene(scenes.stack(2, 3))
-    sharded.set_shard(0, 2)
-    with pytest.raises(PhxError) as e:
-        sharded.add_pins(_pins([(1, 2, (0.0, 5.0), (0.0, -5.0))]))
-    assert e.value.status == ERR_STATE and sharded.pin_count() == 0
-
-
-def test_set_comm_refuses_a_world_with_pins(built_lib):
-    """phx_world_set_comm with a one-rank communicator on a world that holds pins: PHX_ERR_STATE, nothing changed; without pins it attaches,
-    and add_pins is then refused.  In a child process, as the other tests that create a communicator: RCCL's bootstrap must not be able
-    to hang the suite's process (the library gives up after PHX_COMM_TIMEOUT_S)."""
-    import os
-    import subprocess
-    import sys
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "pins_comm_worker.py")
-    env = dict(os.environ, PHX_COMM_TIMEOUT_S="60")
-    for attempt in range(2):
-        p = subprocess.run([sys.executable, worker], env=env, capture_output=True, text=True, timeout=300)
-        if "NO COMMUNICATOR" not in p.stdout:
-            break
-    if "NO COMMUNICATOR" in p.stdout:
-        pytest.skip("no RCCL communicator on this box: " + p.stdout[-300:])
-    assert p.returncode == 0 and "pins comm worker ok" in p.stdout, p.stdout[-1500:] + p.stderr[-3000:]

@@ -1,13 +1,13 @@
 """The slider corpus on the device (tests/slider_corpus.py): every case, none left out, through k_solve_pins plain and tethered to a pin,
 a link and an angle (the four kinds in one class sequence), and tethered a second time under PHX_PIN_GROUP_PINS=1 through the trailing
-group's kernels (k_pin_prestep / k_pin_class); the lockstep of tests/test_sliders_gpu.py, byte for byte against the spec
+group's kernels (k_pin_prestep / k_pin_class); the lockstep of tests/unit_lockstep.py, byte for byte against the spec
 (tests/slider_spec.py).  The two cases whose bodies are all static have no component to exceed the cap and run on the LDS path only."""
 import pytest
 
 import phyx_amd
 import slider_corpus
-from test_sliders_gpu import _cfg, _check, _step
-from test_sliders_cpu import _state
+import unit_lockstep as ul
+from unit_spec import SLIDER
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +23,15 @@ def test_case_on_the_device(oracle, built_lib, monkeypatch, name, path):
         monkeypatch.setenv("PHX_PIN_GROUP_PINS", "1")
     pw, ow = m.device_world(phyx_amd), m.oracle_world(oracle)
     assert pw.bodies.tobytes() == ow.bodies().tobytes()
-    pins, links, angles, sliders, cfg = m.pins, m.links, m.angles, m.sliders, _cfg()
+    units, cfg = ul.lists(pins=m.pins, links=m.links, angles=m.angles, sliders=m.sliders), ul.cfg()
     sched = pw.pin_schedule()
     if path == "cap1":
         assert sched["lds_groups"] == 0 and len(sched["group_offsets"]) == 2, "the whole case in the trailing group"
     elif name not in NO_COMPONENT:
         assert sched["lds_groups"] >= 1
     for s in range(m.steps):
-        _, work = _step(oracle, pw, ow, cfg, pins, links, angles, sliders)
+        _, work = ul.step(oracle, pw, ow, cfg, units)
         assert pw.counts()[1] == 0, "bodies touch at step %d" % s
         if s == 0:
-            assert [_state(w) for w in work] == m.expect_sliders
-        _check(pw, ow, pins, links, angles, sliders, s)
+            assert [slider_corpus.state_of(w) for w in work[SLIDER]] == m.expect_sliders
+        ul.check(pw, ow, units, s)

@@ -7,11 +7,15 @@ import numpy as np
 import pytest
 
 from phyx_amd import api
+import angle_corpus
+import link_corpus
 import pin_reference as ref
 import pin_spec
 import slider_corpus
 import slider_reference as sref
 import slider_spec
+import unit_reference
+import unit_spec
 
 F = np.float32
 DT = 1.0 / 60.0
@@ -46,7 +50,7 @@ def _boxes(count=1, x=0.0, y=0.0, v=(0.0, 0.0), w=0.0):
 
 
 def _free(b):
-    slider_spec.step_free(b, NO_PINS, NO_LINKS, NO_ANGLES, np.zeros(0, dtype=api.slider_dtype), [], DT, 0.0)
+    unit_spec.step_free(b, [], [], DT, 0.0)
 
 
 def test_the_sign_of_s_against_the_integrator():
@@ -104,7 +108,7 @@ def _run(row, steps, x=0.0, y=0.0, v=(0.0, 0.0), w=0.0, gravity=0.0, force=None)
     sliders = slider_spec.make_sliders([row])
     works, states = [], []
     for _ in range(steps):
-        _, _, by_slider = slider_spec.step_free(b, NO_PINS, NO_LINKS, NO_ANGLES, sliders, [0], DT, gravity, force=None if force is None else [force])
+        by_slider = unit_spec.step_free(b, [NO_PINS, NO_LINKS, NO_ANGLES, sliders], [0], DT, gravity, force=None if force is None else [force])[unit_spec.SLIDER]
         works.append(by_slider[0])
         states.append(b.tobytes())
     return works, states, sliders, b
@@ -194,12 +198,6 @@ def _order(m):
     return api.pin_schedule(b1, b2, st)["order"]
 
 
-def _state(w):
-    if not w.active:
-        return "inactive"
-    return "P" + ("L" if w.lrow else "") + ("M" if w.mrow else "") + ("-idle" if w.idle else "")
-
-
 @pytest.mark.parametrize("tether", [False, True], ids=["plain", "tethered"])
 @pytest.mark.parametrize("name", slider_corpus.NAMES)
 def test_case_reaches_what_it_claims(built_lib, oracle, name, tether):
@@ -207,12 +205,11 @@ def test_case_reaches_what_it_claims(built_lib, oracle, name, tether):
     bodies = _pre_solve_bodies(oracle, m)
     before = bodies.copy()
     pins, links, angles, sliders = m.pins, m.links, m.angles, m.sliders
-    by_link, by_angle, work = slider_spec.solve_units(bodies, pins, links, angles, sliders, _order(m), DT, 8)
-    assert [_state(w) for w in work] == m.expect_sliders
+    _, by_link, by_angle, work = unit_spec.solve_units(bodies, [pins, links, angles, sliders], _order(m), DT, 8)
+    assert [slider_corpus.state_of(w) for w in work] == m.expect_sliders
     if tether:
-        import test_angles_cpu
-        assert [test_angles_cpu._state(w) for w in by_angle] == m.expect_angles
-        assert [("active" if w.active else "idle" if w.idle else "inactive") for w in by_link] == m.expect
+        assert [angle_corpus.rows_of(w) for w in by_angle] == m.expect_angles
+        assert [link_corpus.state_of(w) for w in by_link] == m.expect
     for k, w in enumerate(work):
         if not w.active:
             assert sliders["impulse"][k] == 0, "an inactive slider reads impulse 0"
@@ -280,18 +277,18 @@ def _impulses(s):
     return np.stack([s["impulse"], s["axis_impulse"], s["motor_impulse"]], axis=1).astype(np.float64)
 
 
-def _compare(bodies, pins, links, angles, sliders, order, what, impulses=True):
-    exact = sref.solve(bodies, pins, links, angles, sliders, order, DT, 8, np.float64)
-    single = sref.solve(bodies, pins, links, angles, sliders, order, DT, 8, np.float32)
-    b, p, l, a, s = bodies.copy(), pins.copy(), links.copy(), angles.copy(), sliders.copy()
-    _, _, work = slider_spec.solve_units(b, p, l, a, s, order, DT, 8)
-    assert [w.active for w in work] == exact.active.tolist() and [w.lrow for w in work] == exact.lrow.tolist() \
-        and [w.mrow for w in work] == exact.mrow.tolist(), "%s: the reference decides a row otherwise" % what
+def _compare(bodies, lists, order, what, impulses=True):
+    exact = unit_reference.solve(bodies, lists, order, DT, 8, np.float64)
+    single = unit_reference.solve(bodies, lists, order, DT, 8, np.float32)
+    b, own = bodies.copy(), [units.copy() for units in lists]
+    work = unit_spec.solve_units(b, own, order, DT, 8)[unit_spec.SLIDER]
+    assert [w.active for w in work] == exact.slider_active.tolist() and [w.lrow for w in work] == exact.slider_lrow.tolist() \
+        and [w.mrow for w in work] == exact.slider_mrow.tolist(), "%s: the reference decides a row otherwise" % what
     if not impulses:
         return 0.0
-    want = np.stack([exact.impulse, exact.axis_impulse, exact.motor_impulse], axis=1)
-    noise = max(ref.deviation(np.stack([single.impulse, single.axis_impulse, single.motor_impulse], axis=1), want), ULP)
-    dev = ref.deviation(_impulses(s), want)
+    want = np.stack([exact.slider_impulse, exact.slider_axis_impulse, exact.slider_motor_impulse], axis=1)
+    noise = max(ref.deviation(np.stack([single.slider_impulse, single.slider_axis_impulse, single.slider_motor_impulse], axis=1), want), ULP)
+    dev = ref.deviation(_impulses(own[unit_spec.SLIDER]), want)
     qnoise = max(ref.deviation(single.q, exact.q), ULP)
     qdev = ref.deviation(ref.velocities(b), exact.q)
     print("%-44s impulses: noise %.3g spec %.3g ratio %.2f   velocities: ratio %.2f" % (what, noise, dev, dev / noise, qdev / qnoise))
@@ -316,12 +313,12 @@ def _scenes():
 def test_spec_against_the_float64_reference(built_lib, oracle):
     worst = (0.0, "")
     for name, b, sliders in _scenes():
-        worst = max(worst, (_compare(b, NO_PINS, NO_LINKS, NO_ANGLES, sliders, [0], "scene " + name), name))
+        worst = max(worst, (_compare(b, [NO_PINS, NO_LINKS, NO_ANGLES, sliders], [0], "scene " + name), name))
     for name in slider_corpus.NAMES:
         for tether in (False, True):
             m = slider_corpus.build(name, tether)
             what = name + (" tethered" if tether else "")
-            worst = max(worst, (_compare(_pre_solve_bodies(oracle, m), m.pins, m.links, m.angles, m.sliders, _order(m), what,
+            worst = max(worst, (_compare(_pre_solve_bodies(oracle, m), [m.pins, m.links, m.angles, m.sliders], _order(m), what,
                                          impulses=name not in slider_corpus.ON_A_COMPARISON), what))
     print("worst ratio %.2f (%s)" % worst)
     assert worst[0] <= MARGIN

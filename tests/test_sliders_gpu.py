@@ -1,75 +1,38 @@
-"""Sliders on the device (include/phyx_amd.h SLIDERS) held to their specification, tests/slider_spec.py: the device World and the oracle
-World in lockstep, the spec's pass over pins, links, angles and sliders applied to the oracle's bodies between its pre_solve and its
-solve on the device's own schedule of units, every byte of the state and of the four lists compared after every step; then the
-schedule's paths, the life cycle by twins, and the refusals.  (The lockstep is that of tests/test_angles_gpu.py with the fourth list.)"""
+"""Sliders on the device (include/phyx_amd.h SLIDERS) held to their specification, tests/slider_spec.py, in the lockstep of
+tests/unit_lockstep.py; then the schedule's paths, the life cycle by twins, and the refusals.  (What every kind of unit has alike is in
+tests/test_units_gpu.py.)"""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import phyx_amd
-from phyx_amd import PhxError, scenes
-from phyx_amd.api import angle_dtype, link_dtype, pin_dtype, slider_dtype
-from helpers import oracle_world
-from spawn_lockstep import compare
+from phyx_amd import PhxError
+from phyx_amd.api import slider_dtype
 import angle_spec
-import link_spec
 import removal_spec
+from slider_corpus import state_of as _state
 import slider_spec
-from test_angles_gpu import DT, G, MODES, NAMES, _cfg, _pins, _scene
-from test_sliders_cpu import _state
+import unit_lockstep as ul
+from unit_lockstep import DT, G, MODES, ERR_INVALID, ERR_CAPACITY, ERR_STATE, O, X, Y, lists
+from unit_scenes import MIXED, mixed_chain as _mixed_chain, mixed_world
+from unit_spec import KINDS, SLIDER
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID, ERR_CAPACITY, ERR_STATE = -1, -4, -5
-NO_PINS = np.zeros(0, dtype=pin_dtype)
-NO_LINKS = np.zeros(0, dtype=link_dtype)
-NO_ANGLES = np.zeros(0, dtype=angle_dtype)
-O, X, Y = (0.0, 0.0), (1.0, 0.0), (0.0, 1.0)
+
+def _step(oracle, pw, ow, cfg, units):
+    """-> (the schedule, the sliders' prestep records)"""
+    sched, work = ul.step(oracle, pw, ow, cfg, units)
+    return sched, work[SLIDER]
 
 
-def _worlds(scene, pins, links, angles, sliders, gravity=G, with_oracle=True):
-    pw = phyx_amd.World(0, gravity=gravity)
-    pw.add_scene(scene)
-    assert pw.add_pins(pins).tolist() == list(range(len(pins)))
-    assert pw.add_links(links).tolist() == list(range(len(links)))
-    assert pw.add_angles(angles).tolist() == list(range(len(angles)))
-    assert pw.add_sliders(sliders).tolist() == list(range(len(sliders)))
-    return pw, (oracle_world(scene, gravity) if with_oracle else None)
-
-
-def _step(oracle, pw, ow, cfg, pins, links, angles, sliders, dt=DT):
-    """1. pw.Update  2. ow.pre_solve  3. slider_spec.solve_units on ow.bodies() on the device's own schedule of units  4. the oracle's
-    solver on the device's contact schedule  5. ow.integrate_position.  The four lists are the spec's own.
-    -> (the schedule, the sliders' prestep records)"""
-    sched = pw.pin_schedule()
-    assert sorted(sched["order"].tolist()) == list(range(len(pins) + len(links) + len(angles) + len(sliders)))
-    pw.Update(dt, cfg)
-    ow.pre_solve(dt)
-    _, _, work = slider_spec.solve_units(ow.bodies(), pins, links, angles, sliders, sched["order"], dt, pw.pin_iterations)
-    order, offs = pw.solver.schedule()
-    groups, _ = pw.solver.groups()
-    b, cp, j = ow.bodies(), ow.contact_points(), ow.joints()
-    assert len(order) == len(j)
-    oracle.solver_solve_grouped(b, cp, j, order, offs, groups, cfg.contactIterationsCount, cfg.penetrationIterationsCount, oracle.STAG_COLOUR_SYNC)
-    ow.integrate_position(dt)
-    return sched, work
-
-
-def _check(pw, ow, pins, links, angles, sliders, s):
-    compare(pw, ow, s)
-    assert pw.pins().tobytes() == pins.tobytes(), "pins differ at step %d" % s
-    assert pw.links().tobytes() == links.tobytes(), "links differ at step %d" % s
-    assert pw.angles().tobytes() == angles.tobytes(), "angles differ at step %d" % s
-    assert pw.sliders().tobytes() == sliders.tobytes(), "sliders differ at step %d" % s
-
-
-def _lockstep(oracle, pw, ow, cfg, pins, links, angles, sliders, steps, first=0):
+def _lockstep(oracle, pw, ow, cfg, units, steps, first=0):
     """-> (the last schedule, per step the sliders' states as tests/slider_corpus.py names them)"""
     states = []
     for s in range(first, first + steps):
-        sched, work = _step(oracle, pw, ow, cfg, pins, links, angles, sliders)
-        _check(pw, ow, pins, links, angles, sliders, s)
+        sched, work = _step(oracle, pw, ow, cfg, units)
+        ul.check(pw, ow, units, s)
         states.append([_state(w) for w in work])
     return sched, states
 
@@ -83,10 +46,10 @@ def test_one_body_on_a_world_slider(oracle, built_lib, kind):
               "spring": (0, -1, O, (0.0, 100.0), Y, 0.0, 0.0, 2.0, 0.3),
               "motor": (0, -1, O, (0.0, 100.0), X, -1.0e5, 1.0e5, 0.0, 0.0, 1000.0, 1.0e-3)}[kind]      # (weak: still accelerating, its impulse at the clamp, after 60 steps)
     sliders = slider_spec.make_sliders([slider])
-    pw, ow = _worlds(_scene(body), NO_PINS, NO_LINKS, NO_ANGLES, sliders)
+    pw, ow = ul.worlds(ul.scene(body), lists(sliders=sliders))
     assert pw.slider_count() == 1 and pw.pin_count() == 0 and pw.link_count() == 0 and pw.angle_count() == 0
     assert pw.sliders().tobytes() == sliders.tobytes(), "before the first step the sliders wait on the host"
-    sched, states = _lockstep(oracle, pw, ow, _cfg(), NO_PINS, NO_LINKS, NO_ANGLES, sliders, 60)
+    sched, states = _lockstep(oracle, pw, ow, ul.cfg(), lists(sliders=sliders), 60)
     assert sched["lds_groups"] == 1 and len(sched["class_offsets"]) == 2
     flat = [s[0] for s in states]
     if kind in ("lock", "motor"):
@@ -108,11 +71,11 @@ def test_a_limited_slider_among_contacts(oracle, built_lib, mode):
     """a platform on a vertical world rail falls to its lower stop and a box lands on it there"""
     rows = [(0.0, 20.0, 4.0, 1.0, False), (0.5, 26.0, 2.0, 2.0, False)]
     sliders = slider_spec.make_sliders([(0, -1, O, (0.0, 20.0), Y, -5.0, 5.0)])
-    pw, ow = _worlds(_scene(rows), NO_PINS, NO_LINKS, NO_ANGLES, sliders)
+    pw, ow = ul.worlds(ul.scene(rows), lists(sliders=sliders))
     touched, seen = False, set()
     for s in range(60):
-        _, work = _step(oracle, pw, ow, _cfg(MODES[mode]), NO_PINS, NO_LINKS, NO_ANGLES, sliders)
-        _check(pw, ow, NO_PINS, NO_LINKS, NO_ANGLES, sliders, s)
+        _, work = _step(oracle, pw, ow, ul.cfg(MODES[mode]), lists(sliders=sliders))
+        ul.check(pw, ow, lists(sliders=sliders), s)
         seen.add(_state(work[0]))
         touched = touched or len(pw.manifolds) > 0
     assert pw.pin_schedule_builds() == 1
@@ -122,27 +85,6 @@ def test_a_limited_slider_among_contacts(oracle, built_lib, mode):
 
 
 # ---- the paths ----
-def _mixed_chain(count, top=(0.0, 500.0), spacing=10.0):
-    """`count` boxes level with `top`, joined end to end from the world point `top`, two units a joint, the four kinds in one component:
-    joint k % 3 == 0 a pin and an angle limited to +-0.3, 1 a slider along the body before (limits +-1) and an angle lock (a telescope),
-    2 a pin and a spring link between the centres -> (body rows, pins, links, angles, sliders)"""
-    h = spacing / 2.0
-    bodies = [(top[0] + spacing * (k + 0.5), top[1], 3.0, 1.0, False) for k in range(count)]
-    pins, links, angles, sliders = [], [], [], []
-    for k in range(count):
-        b, a2 = (k - 1, (h, 0.0)) if k else (-1, top)
-        if k % 3 == 1:
-            sliders.append((k, b, (-h, 0.0), a2, X, -1.0, 1.0))
-            angles.append((k, b, 0.0, 0.0))
-        else:
-            pins.append((k, b, (-h, 0.0), a2))
-            if k % 3 == 0:
-                angles.append((k, b, -0.3, 0.3))
-            else:
-                links.append((k, b, O, O, spacing, spacing, 3.0, 0.5))
-    return bodies, _pins(pins), link_spec.make_links(links), angle_spec.make_angles(angles), slider_spec.make_sliders(sliders)
-
-
 @pytest.mark.parametrize("case", ["chain20_cap16", "chain20_pairs_cap16", "chain20", "chain65", "chain130"])
 def test_the_paths(oracle, built_lib, monkeypatch, case):
     """40 units in one component above a cap of 16: the trailing group alone; the same chain beside 20 pairs of a slider and a lock at
@@ -150,7 +92,7 @@ def test_the_paths(oracle, built_lib, monkeypatch, case):
     LDS group of three waves; 260 units in one component, more than a workgroup: the HBM path at the default"""
     if case in ("chain20_cap16", "chain20_pairs_cap16"):
         monkeypatch.setenv("PHX_PIN_GROUP_PINS", "16")
-    bodies, pins, links, angles, sliders = _mixed_chain({"chain65": 65, "chain130": 130}.get(case, 20))
+    bodies, (pins, links, angles, sliders) = _mixed_chain({"chain65": 65, "chain130": 130}.get(case, 20))
     if case == "chain20_pairs_cap16":
         first, slider_rows, angle_rows = len(bodies), [], []
         for k in range(20):
@@ -159,9 +101,9 @@ def test_the_paths(oracle, built_lib, monkeypatch, case):
             slider_rows += [(a + 1, a, (-5.0, 0.0), (5.0, 0.0), (1.0, 0.1 * (k % 3)), -0.5, 0.5, 0.0, 0.0, 1.0, 1.0e-4 * (k % 2))]
             angle_rows += [(a + 1, a, 0.0, 0.0)]
         sliders, angles = np.concatenate([sliders, slider_spec.make_sliders(slider_rows)]), np.concatenate([angles, angle_spec.make_angles(angle_rows)])
-    pw, ow = _worlds(_scene(bodies), pins, links, angles, sliders)
+    pw, ow = ul.worlds(ul.scene(bodies), [pins, links, angles, sliders])
     steps = 4 if case in ("chain65", "chain130") else 14
-    sched, states = _lockstep(oracle, pw, ow, _cfg(), pins, links, angles, sliders, steps)
+    sched, states = _lockstep(oracle, pw, ow, ul.cfg(), [pins, links, angles, sliders], steps)
     lds, groups = sched["lds_groups"], len(sched["group_offsets"]) - 1
     if case in ("chain20", "chain65"):
         assert (lds, groups) == (1, 1)
@@ -180,116 +122,62 @@ def test_a_world_with_sliders_only(oracle, built_lib):
     bodies = [(30.0 * k, 100.0, 3.0, 1.0, False, 0.2 * k) for k in range(6)]
     sliders = slider_spec.make_sliders([(1, 0, O, O, X, 30.0, 30.0), (2, 1, (1.0, 0.0), (0.0, 1.0), (1.0, 1.0), 10.0, 30.0), (3, 2, O, O, X, 30.0, 30.0, 1.5, 0.2),
                                         (4, 3, O, O, X, -900.0, 900.0, 0.0, 0.0, 2.0, 1.0e-4), (5, -1, O, (150.0, 100.0), Y, 0.0, 0.0)])
-    pw, ow = _worlds(_scene(bodies), NO_PINS, NO_LINKS, NO_ANGLES, sliders)
+    pw, ow = ul.worlds(ul.scene(bodies), lists(sliders=sliders))
     pw.set_velocities([0], np.array([[5.0, 0.0, 1.5]], dtype=np.float32))
     b = ow.bodies()
     b["velocity"]["x"][0], b["angular_velocity"][0] = 5.0, 1.5
-    sched, states = _lockstep(oracle, pw, ow, _cfg(), NO_PINS, NO_LINKS, NO_ANGLES, sliders, 12)
+    sched, states = _lockstep(oracle, pw, ow, ul.cfg(), lists(sliders=sliders), 12)
     assert pw.pin_count() == 0 and pw.link_count() == 0 and pw.angle_count() == 0 and len(sched["order"]) == 5
     assert states[0] == ["PL", "P-idle", "PL", "PM-idle", "PL"]
 
 
 # ---- the life cycle, by twins ----
-def _same(a, b, what):
-    assert a.counts() == b.counts(), "counts differ %s" % what
-    for name, x, y in zip(NAMES, a.state(), b.state()):
-        assert x.tobytes() == y.tobytes(), "%s differ %s" % (name, what)
-    assert a.pins().tobytes() == b.pins().tobytes(), "pins differ %s" % what
-    assert a.links().tobytes() == b.links().tobytes(), "links differ %s" % what
-    assert a.angles().tobytes() == b.angles().tobytes(), "angles differ %s" % what
-    assert a.sliders().tobytes() == b.sliders().tobytes(), "sliders differ %s" % what
-
-
-def _mixed():
-    """a mixed chain of 12 and, beside it, a carriage on a world rail with a motor and a second carriage on the first, sprung
-    -> (body rows, pins, links, angles, sliders)"""
-    bodies, pins, links, angles, sliders = _mixed_chain(12, top=(0.0, 300.0))
-    n = len(bodies)
-    bodies += [(-100.0, 300.0, 4.0, 1.5, False), (-100.0, 310.0, 2.0, 2.0, False)]
-    sliders = np.concatenate([sliders, slider_spec.make_sliders([(n, -1, O, (-100.0, 300.0), X, -20.0, 20.0, 0.0, 0.0, 4.0, 5.0e-4),
-                                                                 (n + 1, n, O, (0.0, 10.0), Y, 0.0, 0.0, 2.0, 0.4)])])
-    angles = np.concatenate([angles, angle_spec.make_angles([(n, -1, 0.0, 0.0)])])
-    return bodies, pins, links, angles, sliders
-
-
 def _mixed_world():
-    bodies, pins, links, angles, sliders = _mixed()
-    pw, _ = _worlds(_scene(bodies), pins, links, angles, sliders, with_oracle=False)
-    return pw
-
-
-def _lists(pw):
-    return pw.pins(), pw.links(), pw.angles(), pw.sliders()
-
-
-def _twin(state, pins, links, angles, sliders):
-    pb = phyx_amd.World(0, gravity=G)
-    pb.set_state(*state)
-    pb.add_pins(pins)
-    pb.add_links(links)
-    pb.add_angles(angles)
-    pb.add_sliders(sliders)
-    return pb
-
-
-def _run_twins(pa, pb, steps, what):
-    cfg = _cfg()
-    for s in range(steps):
-        pa.Update(DT, cfg)
-        pb.Update(DT, cfg)
-        _same(pa, pb, "at step %d after %s" % (s, what))
+    return mixed_world("slider")
 
 
 def test_remove_sliders(built_lib):
     pa = _mixed_world()
     for _ in range(8):
-        pa.Update(DT, _cfg())
-    state, (pins, links, angles, sliders) = pa.state(), _lists(pa)
+        pa.Update(DT, ul.cfg())
+    state, (pins, links, angles, sliders) = pa.state(), ul.lists_of(pa)
     builds = pa.pin_schedule_builds()
     assert all(np.abs(sliders[f]).max() > 0 for f in ("impulse", "axis_impulse", "motor_impulse"))
     pa.remove_sliders([4, 1])
     kept = np.delete(sliders, [1, 4])
     assert pa.sliders().tobytes() == kept.tobytes(), "the others keep their order"
-    _run_twins(pa, _twin(state, pins, links, angles, kept), 5, "remove_sliders")
+    ul.run_twins(pa, ul.twin(state, [pins, links, angles, kept]), 5, "remove_sliders")
     assert pa.pin_schedule_builds() == builds + 1
 
 
 def test_removing_pins_links_and_angles_shifts_the_slider_units(oracle, built_lib):
-    bodies, pins, links, angles, sliders = _mixed()
-    pw, ow = _worlds(_scene(bodies), pins, links, angles, sliders)
-    cfg = _cfg()
-    _lockstep(oracle, pw, ow, cfg, pins, links, angles, sliders, 4)
+    bodies, (pins, links, angles, sliders) = MIXED["slider"]()
+    pw, ow = ul.worlds(ul.scene(bodies), [pins, links, angles, sliders])
+    cfg = ul.cfg()
+    _lockstep(oracle, pw, ow, cfg, [pins, links, angles, sliders], 4)
     pw.remove_pins([3, 5])
     pw.remove_links([0])
     pw.remove_angles([2])
     pins, links, angles = np.delete(pins, [3, 5]), np.delete(links, [0]), np.delete(angles, [2])
-    sched, _ = _lockstep(oracle, pw, ow, cfg, pins, links, angles, sliders, 4, first=4)
+    sched, _ = _lockstep(oracle, pw, ow, cfg, [pins, links, angles, sliders], 4, first=4)
     assert len(sched["order"]) == len(pins) + len(links) + len(angles) + len(sliders) and pw.pin_schedule_builds() == 2
 
 
 def test_remove_bodies_through_a_slider_chain(built_lib):
     pa = _mixed_world()
     for _ in range(8):
-        pa.Update(DT, _cfg())
-    state, lists = pa.state(), _lists(pa)
+        pa.Update(DT, ul.cfg())
+    state, units = pa.state(), ul.lists_of(pa)
     removed = [12, 4]                                       # the carriage on the world rail (the rail of the second), and a telescope's carriage
     filtered = removal_spec.filter(state, removed)
     new = removal_spec.new_index(len(state[0]), removed)
-
-    def remapped(units):
-        keep = np.array([new[p["body1"]] >= 0 and (p["body2"] < 0 or new[p["body2"]] >= 0) for p in units], dtype=bool)
-        kept = units[keep].copy()
-        kept["body1"] = new[kept["body1"]]
-        kept["body2"] = np.where(kept["body2"] < 0, -1, new[np.maximum(kept["body2"], 0)])
-        return kept
-
-    kept = [remapped(u) for u in lists]
-    assert len(kept[3]) == len(lists[3]) - 3, "the telescope of body 4 and both sliders of body 12 went"
+    kept = [ul.remapped(u, new) for u in units]
+    assert len(kept[SLIDER]) == len(units[SLIDER]) - 3, "the telescope of body 4 and both sliders of body 12 went"
     assert pa.remove_bodies(removed).tolist() == new.tolist()
-    assert [u.tobytes() for u in _lists(pa)] == [u.tobytes() for u in kept]
-    pb = _twin(filtered[0], *kept)
-    _same(pa, pb, "right after the removal")
-    _run_twins(pa, pb, 8, "the removal")
+    assert [u.tobytes() for u in ul.lists_of(pa)] == [u.tobytes() for u in kept]
+    pb = ul.twin(filtered[0], kept)
+    ul.same(pa, pb, "right after the removal")
+    ul.run_twins(pa, pb, 8, "the removal")
 
 
 def test_limit_motor_and_anchor_edits_keep_the_schedule(oracle, built_lib):
@@ -297,9 +185,9 @@ def test_limit_motor_and_anchor_edits_keep_the_schedule(oracle, built_lib):
     reversed; an anchor is moved across the rail and row P pulls the carriage over"""
     bodies = [(0.0, 100.0, 3.0, 1.0, False, 0.3), (50.0, 100.0, 3.0, 1.0, False)]
     sliders = slider_spec.make_sliders([(0, -1, O, (-2.0, 100.0), X, -10.0, 10.0), (1, -1, O, (50.0, 100.0), X, -500.0, 500.0)])
-    pw, ow = _worlds(_scene(bodies), NO_PINS, NO_LINKS, NO_ANGLES, sliders, gravity=0.0)
-    cfg = _cfg()
-    _, states = _lockstep(oracle, pw, ow, cfg, NO_PINS, NO_LINKS, NO_ANGLES, sliders, 3)
+    pw, ow = ul.worlds(ul.scene(bodies), lists(sliders=sliders), gravity=0.0)
+    cfg = ul.cfg()
+    _, states = _lockstep(oracle, pw, ow, cfg, lists(sliders=sliders), 3)
     assert states == [["P-idle", "P-idle"]] * 3
     builds = pw.pin_schedule_builds()
     pw.set_slider_limits([0], np.array([[-1.0, 1.0]], dtype=np.float32))                  # s = 2: past the new upper stop
@@ -307,9 +195,9 @@ def test_limit_motor_and_anchor_edits_keep_the_schedule(oracle, built_lib):
     pw.set_slider_motors([1], np.array([[2.0, 1.0e-4]], dtype=np.float32))
     sliders["motor_speed"][1], sliders["max_force"][1] = 2.0, 1.0e-4
     assert pw.sliders().tobytes() == sliders.tobytes()
-    _, states = _lockstep(oracle, pw, ow, cfg, NO_PINS, NO_LINKS, NO_ANGLES, sliders, 1, first=3)
+    _, states = _lockstep(oracle, pw, ow, cfg, lists(sliders=sliders), 1, first=3)
     assert states == [["PL", "PM-idle"]] and sliders["axis_impulse"][0] < 0, "the narrowed limit pushed back at the step after the edit"
-    _lockstep(oracle, pw, ow, cfg, NO_PINS, NO_LINKS, NO_ANGLES, sliders, 2, first=4)
+    _lockstep(oracle, pw, ow, cfg, lists(sliders=sliders), 2, first=4)
     assert sliders["motor_impulse"][1] > 0
     pw.set_slider_motors([1, 0], np.array([[-2.0, 1.0e-4], [0.5, 2.0e-5]], dtype=np.float32))
     sliders["motor_speed"][1] = -2.0
@@ -317,7 +205,7 @@ def test_limit_motor_and_anchor_edits_keep_the_schedule(oracle, built_lib):
     pw.set_slider_anchors([1], np.array([[0.0, 0.0, 50.0, 101.0]], dtype=np.float32))
     sliders["anchor2"][1] = (50.0, 101.0)
     assert pw.sliders().tobytes() == sliders.tobytes()
-    _, states = _lockstep(oracle, pw, ow, cfg, NO_PINS, NO_LINKS, NO_ANGLES, sliders, 3, first=6)
+    _, states = _lockstep(oracle, pw, ow, cfg, lists(sliders=sliders), 3, first=6)
     assert all(s[0] in ("PLM", "PM-idle") and s[1] == "PM-idle" for s in states)
     assert sliders["motor_impulse"][1] < 0 and sliders["impulse"][1] != 0
     assert pw.bodies["velocity"]["y"][1] > 0, "the rail moved up by 1 and row P pulls the carriage after it"
@@ -338,85 +226,45 @@ def test_edits_before_the_first_step_are_host_staged(built_lib):
     assert pa.sliders().tobytes() == sliders.tobytes() and pa.pin_schedule_builds() == 0
     pb.remove_sliders(list(range(len(sliders))))
     pb.add_sliders(sliders)
-    _run_twins(pa, pb, 4, "host-staged edits")
+    ul.run_twins(pa, pb, 4, "host-staged edits")
     assert pa.pin_schedule_builds() == 1
 
 
 def test_save_load_and_fork(built_lib):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pw = _mixed_world()
     for _ in range(6):
         pw.Update(DT, cfg)
     snap = pw.save()
 
-    def lists(w):
-        return tuple(u.tobytes() for u in _lists(w))
+    def bytes_of(w):
+        return tuple(u.tobytes() for u in ul.lists_of(w))
 
-    saved = lists(pw)
+    saved = bytes_of(pw)
     assert all(np.abs(pw.sliders()[f]).max() > 0 for f in ("impulse", "axis_impulse", "motor_impulse"))
     first = []
     for _ in range(8):
         pw.Update(DT, cfg)
-        first.append((pw.bodies.tobytes(),) + lists(pw))
+        first.append((pw.bodies.tobytes(),) + bytes_of(pw))
     other = phyx_amd.World(0, gravity=G)
     other.load(snap)
     pw.load(snap)
-    assert lists(pw) == saved == lists(other)
+    assert bytes_of(pw) == saved == bytes_of(other)
     for s in range(8):
         pw.Update(DT, cfg)
         other.Update(DT, cfg)
-        assert (pw.bodies.tobytes(),) + lists(pw) == first[s], "the loaded world differs at step %d" % s
-        assert (other.bodies.tobytes(),) + lists(other) == first[s], "the fork differs at step %d" % s
-
-
-def test_a_snapshot_with_sliders_has_no_blob(built_lib):
-    pw = phyx_amd.World(0, gravity=G)
-    pw.add_scene(scenes.stack(2, 3))
-    pw.add_sliders([(1, -1, O, O, X, -0.5, 0.5)])
-    snap = pw.save()
-    with pytest.raises(PhxError) as e:
-        snap.to_bytes()
-    assert e.value.status == ERR_STATE and "the snapshot holds 1 sliders, which the blob (layout version 1) does not carry" in str(e.value)
-    n = C.c_size_t(0)
-    assert pw.L.phx_snapshot_blob_bytes(snap.h, C.byref(n)) == ERR_STATE
-    assert pw.L.phx_last_error().decode() == "phx_snapshot_blob_bytes: the snapshot holds 1 sliders, which the blob (layout version 1) does not carry"
-    pw.remove_sliders([0])
-    assert len(pw.save().to_bytes()) > 0
-
-
-def test_set_state_leaves_no_slider(built_lib):
-    pw = _mixed_world()
-    pw.Update(DT, _cfg())
-    pw.set_state(*pw.state())
-    assert pw.slider_count() == 0 and len(pw.sliders()) == 0 and pw.pin_count() == 0 and pw.link_count() == 0 and pw.angle_count() == 0
-    pw.Update(DT, _cfg())
-
-
-def test_a_world_that_lost_its_sliders_is_a_world_without(built_lib):
-    cfg = _cfg()
-    sc = scenes.stack(3, 6)
-    pa, pb = phyx_amd.World(0, gravity=G), phyx_amd.World(0, gravity=G)
-    pa.add_scene(sc); pb.add_scene(sc)
-    pa.add_sliders([(1, 2, O, O, X, 0.0, 0.0), (3, -1, O, O, Y, -0.2, 0.2, 0.0, 0.0, 1.0, 5.0)])
-    pa.remove_sliders([0, 1])
-    assert pa.slider_count() == 0
-    for s in range(10):
-        pa.Update(DT, cfg)
-        pb.Update(DT, cfg)
-        for name, x, y in zip(NAMES, pa.state(), pb.state()):
-            assert x.tobytes() == y.tobytes(), "%s differ at step %d" % (name, s)
-    assert pa.pin_schedule_builds() == 0, "no units: no schedule, no pass"
-    assert pa.save().to_bytes() == pb.save().to_bytes(), "a snapshot without sliders is what it was"
+        assert (pw.bodies.tobytes(),) + bytes_of(pw) == first[s], "the loaded world differs at step %d" % s
+        assert (other.bodies.tobytes(),) + bytes_of(other) == first[s], "the fork differs at step %d" % s
 
 
 def test_an_all_idle_slider_leaves_its_bodies_as_without_it(built_lib):
     """limits not reached, no motor, and a body that moves along its rail only: a box at rest, frame the identity, falls along a
     vertical world rail through its centre.  Row P is on, its C and its cdot are exactly 0, so its impulse is, and L and M are off: the
     body's bytes are those of the twin world that has no slider, on every step."""
-    cfg = _cfg()
+    cfg = ul.cfg()
     rows = [(0.0, 500.0, 3.0, 1.0, False)]
     pa, pb = phyx_amd.World(0, gravity=G), phyx_amd.World(0, gravity=G)
-    pa.add_scene(_scene(rows)); pb.add_scene(_scene(rows))
+    pa.add_scene(ul.scene(rows)); pb.add_scene(ul.scene(rows))
     pa.add_sliders([(0, -1, O, (0.0, 500.0), Y, -1.0e5, 1.0e5)])
     for s in range(20):
         pa.Update(DT, cfg)
@@ -428,23 +276,6 @@ def test_an_all_idle_slider_leaves_its_bodies_as_without_it(built_lib):
 
 
 # ---- the refusals ----
-def _unchanged(pw, before):
-    assert _snapshot_of(pw) == before
-
-
-def _snapshot_of(pw):
-    return (pw.bodies.tobytes(),) + tuple(u.tobytes() for u in _lists(pw)) + (pw.pin_schedule_builds(),)
-
-
-def _raw_add(pw, sliders, count=None, null=False):
-    p = np.ascontiguousarray(sliders, dtype=slider_dtype)
-    return pw.L.phx_world_add_sliders(pw.h, None if null else p.ctypes.data_as(C.c_void_p), len(p) if count is None else count, None)
-
-
-def _message(pw):
-    return pw.L.phx_last_error().decode()
-
-
 GOOD = (0, 1, (0.0, 0.0), (0.0, 0.0), (1.0, 0.0), -0.5, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0)
 
 
@@ -457,12 +288,12 @@ def _bad(**fields):
 
 @pytest.mark.parametrize("staged", ["host", "device"])
 def test_rejections_leave_the_world_unchanged(built_lib, staged):
-    cfg = _cfg()
+    cfg = ul.cfg()
     pw = _mixed_world()
     if staged == "device":
         pw.Update(DT, cfg)
     n = pw.counts()[0]
-    before = _snapshot_of(pw)
+    before = ul.snapshot_of(pw)
     A = "phx_world_add_sliders: slider 1: "
     nan, inf = np.nan, np.inf
     bad = [(dict(body1=-1), A + "body1 -1 out of range [0, %d)" % n), (dict(body1=n), A + "body1 %d out of range [0, %d)" % (n, n)),
@@ -483,17 +314,17 @@ def test_rejections_leave_the_world_unchanged(built_lib, staged):
            (dict(max_force=-1.0), A + "negative max_force -1"),
            (dict(reserved=7), A + "reserved must be 0")]
     for fields, message in bad:
-        assert _raw_add(pw, _bad(**fields)) == ERR_INVALID, fields
-        assert _message(pw) == message
-        _unchanged(pw, before)
-    assert _raw_add(pw, _bad(hertz=2.0, lower=0.5, axis=(0.0, 2.0 ** -9))) == 0, "a spring with lower == upper is fine, and so is an axis of 2^-9"
+        assert ul.raw_add(pw, KINDS[SLIDER], _bad(**fields)) == ERR_INVALID, fields
+        assert ul.message(pw) == message
+        ul.unchanged(pw, before)
+    assert ul.raw_add(pw, KINDS[SLIDER], _bad(hertz=2.0, lower=0.5, axis=(0.0, 2.0 ** -9))) == 0, "a spring with lower == upper is fine, and so is an axis of 2^-9"
     pw.remove_sliders([pw.slider_count() - 1, pw.slider_count() - 2])
-    before = _snapshot_of(pw)
+    before = ul.snapshot_of(pw)
     one = np.array([GOOD], dtype=slider_dtype)
-    assert _raw_add(pw, one, count=-1) == ERR_INVALID and _message(pw) == "phx_world_add_sliders: negative count -1"
-    assert _raw_add(pw, one, null=True) == ERR_INVALID and _message(pw) == "phx_world_add_sliders: null array"
-    assert _raw_add(pw, np.zeros(0, dtype=slider_dtype), count=0, null=True) == 0, "an empty call is a true no-op"
-    _unchanged(pw, before)
+    assert ul.raw_add(pw, KINDS[SLIDER], one, count=-1) == ERR_INVALID and ul.message(pw) == "phx_world_add_sliders: negative count -1"
+    assert ul.raw_add(pw, KINDS[SLIDER], one, null=True) == ERR_INVALID and ul.message(pw) == "phx_world_add_sliders: null array"
+    assert ul.raw_add(pw, KINDS[SLIDER], np.zeros(0, dtype=slider_dtype), count=0, null=True) == 0, "an empty call is a true no-op"
+    ul.unchanged(pw, before)
     ns = pw.slider_count()
     calls = {"phx_world_remove_sliders": lambda which: pw.remove_sliders(which),
              "phx_world_set_slider_anchors": lambda which: pw.set_slider_anchors(which, np.zeros((len(which), 4), dtype=np.float32)),
@@ -505,40 +336,40 @@ def test_rejections_leave_the_world_unchanged(built_lib, staged):
             with pytest.raises(PhxError) as e:
                 call(which)
             assert e.value.status == ERR_INVALID and str(e.value).endswith(name + ": " + tail), str(e.value)
-            _unchanged(pw, before)
+            ul.unchanged(pw, before)
     spring = pw.add_sliders([(0, 1, O, O, X, 0.1, 0.1, 2.0, 0.5)])[0]
-    before = _snapshot_of(pw)
+    before = ul.snapshot_of(pw)
     L = "phx_world_set_slider_limits: slider 0: "
     for which, limits, message in (([0], [1.0, np.nan], L + "a limit is not finite"), ([0], [3.0, 2.0], L + "limits [3, 2] are not lower <= upper"),
                                    ([int(spring)], [1.0, 2.0], L + "a spring (hertz 2) needs lower == upper")):
         with pytest.raises(PhxError) as e:
             pw.set_slider_limits(which, np.array([limits], dtype=np.float32))
         assert e.value.status == ERR_INVALID and str(e.value).endswith(message), str(e.value)
-        _unchanged(pw, before)
+        ul.unchanged(pw, before)
     M = "phx_world_set_slider_motors: slider 0: "
     for motors, message in (([np.inf, 1.0], M + "a motor value is not finite"), ([1.0, np.nan], M + "a motor value is not finite"),
                             ([1.0, -2.0], M + "negative max_force -2")):
         with pytest.raises(PhxError) as e:
             pw.set_slider_motors([0], np.array([motors], dtype=np.float32))
         assert e.value.status == ERR_INVALID and str(e.value).endswith(message), str(e.value)
-        _unchanged(pw, before)
+        ul.unchanged(pw, before)
     with pytest.raises(PhxError) as e:
         pw.set_slider_anchors([0], np.array([[0.0, 0.0, np.nan, 0.0]], dtype=np.float32))
     assert e.value.status == ERR_INVALID and str(e.value).endswith("phx_world_set_slider_anchors: entry 0: value 2 is not finite"), str(e.value)
-    _unchanged(pw, before)
+    ul.unchanged(pw, before)
     idx = np.zeros(1, dtype=np.int32)
     ip = idx.ctypes.data_as(C.c_void_p)
-    assert pw.L.phx_world_remove_sliders(pw.h, None, 1) == ERR_INVALID and _message(pw) == "phx_world_remove_sliders: null array"
-    assert pw.L.phx_world_remove_sliders(pw.h, ip, -1) == ERR_INVALID and _message(pw) == "phx_world_remove_sliders: negative count -1"
-    assert pw.L.phx_world_set_slider_anchors(pw.h, ip, None, 1) == ERR_INVALID and _message(pw) == "phx_world_set_slider_anchors: null array"
-    assert pw.L.phx_world_set_slider_limits(pw.h, ip, None, 1) == ERR_INVALID and _message(pw) == "phx_world_set_slider_limits: null array"
-    assert pw.L.phx_world_set_slider_motors(pw.h, ip, None, 1) == ERR_INVALID and _message(pw) == "phx_world_set_slider_motors: null array"
+    assert pw.L.phx_world_remove_sliders(pw.h, None, 1) == ERR_INVALID and ul.message(pw) == "phx_world_remove_sliders: null array"
+    assert pw.L.phx_world_remove_sliders(pw.h, ip, -1) == ERR_INVALID and ul.message(pw) == "phx_world_remove_sliders: negative count -1"
+    assert pw.L.phx_world_set_slider_anchors(pw.h, ip, None, 1) == ERR_INVALID and ul.message(pw) == "phx_world_set_slider_anchors: null array"
+    assert pw.L.phx_world_set_slider_limits(pw.h, ip, None, 1) == ERR_INVALID and ul.message(pw) == "phx_world_set_slider_limits: null array"
+    assert pw.L.phx_world_set_slider_motors(pw.h, ip, None, 1) == ERR_INVALID and ul.message(pw) == "phx_world_set_slider_motors: null array"
     out = np.zeros(1, dtype=slider_dtype)
     assert pw.L.phx_world_get_sliders(pw.h, out.ctypes.data_as(C.c_void_p), 1) == ERR_CAPACITY
-    assert _message(pw) == "phx_world_get_sliders: room for 1 sliders, the world has %d" % pw.slider_count()
+    assert ul.message(pw) == "phx_world_get_sliders: room for 1 sliders, the world has %d" % pw.slider_count()
     pw.remove_sliders([]); pw.set_slider_limits([], np.zeros((0, 2), dtype=np.float32)); pw.set_slider_motors([], np.zeros((0, 2), dtype=np.float32))
     pw.set_slider_anchors([], np.zeros((0, 4), dtype=np.float32))
-    _unchanged(pw, before)
+    ul.unchanged(pw, before)
     # inside a step every call is refused
     pw.PreSolve(DT)
     for call in (lambda: pw.add_sliders(one), lambda: pw.remove_sliders([0]), lambda: pw.set_slider_limits([0], np.zeros((1, 2), dtype=np.float32)),
@@ -548,54 +379,3 @@ def test_rejections_leave_the_world_unchanged(built_lib, staged):
         assert e.value.status == ERR_STATE
     pw.FinishStep(DT, cfg)
     assert pw.slider_count() == ns + 1
-
-
-def test_the_schedule_call_needs_room_for_all_four_kinds(built_lib):
-    pw = _mixed_world()
-    n = pw.pin_count() + pw.link_count() + pw.angle_count() + pw.slider_count()
-    nc, ng, lg = C.c_int32(0), C.c_int32(0), C.c_int32(0)
-    assert pw.L.phx_world_get_pin_schedule(pw.h, None, 0, None, 0, C.byref(nc), None, 0, C.byref(ng), C.byref(lg)) == 0
-    order = np.zeros(n, dtype=np.int32)
-    coff, goff = np.zeros(nc.value + 1, dtype=np.int32), np.zeros(ng.value + 1, dtype=np.int32)
-    args = (coff.ctypes.data_as(C.c_void_p), len(coff), C.byref(nc), goff.ctypes.data_as(C.c_void_p), len(goff), C.byref(ng), C.byref(lg))
-    assert pw.L.phx_world_get_pin_schedule(pw.h, order.ctypes.data_as(C.c_void_p), n - 1, *args) == ERR_CAPACITY
-    assert _message(pw) == "phx_world_get_pin_schedule: arrays too small"
-    assert pw.L.phx_world_get_pin_schedule(pw.h, order.ctypes.data_as(C.c_void_p), n, *args) == 0
-    assert sorted(order.tolist()) == list(range(n))
-
-
-def test_sharded_worlds_carry_no_sliders(built_lib):
-    pw = phyx_amd.World(0, gravity=G)
-    pw.add_scene(scenes.stack(2, 3))
-    rail = slider_spec.make_sliders([(1, -1, O, O, Y, -0.5, 0.5)])
-    pw.add_sliders(rail)
-    with pytest.raises(PhxError) as e:
-        pw.set_shard(0, 2)
-    assert e.value.status == ERR_STATE and str(e.value).endswith("phx_world_set_shard: the world holds sliders, which a sharded world does not carry")
-    n = pw.counts()[0]
-    with pytest.raises(PhxError) as e:
-        pw.reslab(np.arange(n, dtype=np.int64), n, (-1e9, 1e9))
-    assert e.value.status == ERR_STATE and str(e.value).endswith("phx_world_reslab: the world holds sliders, which a sharded world does not carry")
-    pw.set_shard(0, 1)
-    sharded = phyx_amd.World(0, gravity=G)
-    sharded.add_scene(scenes.stack(2, 3))
-    sharded.set_shard(0, 2)
-    with pytest.raises(PhxError) as e:
-        sharded.add_sliders(rail)
-    assert e.value.status == ERR_STATE and str(e.value).endswith("phx_world_add_sliders: a sharded world carries no sliders") and sharded.slider_count() == 0
-
-
-def test_set_comm_refuses_a_world_with_sliders(built_lib):
-    """as tests/test_angles_gpu.py: in a child process, so that RCCL's bootstrap cannot hang the suite's"""
-    import os
-    import subprocess
-    import sys
-    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "sliders_comm_worker.py")
-    env = dict(os.environ, PHX_COMM_TIMEOUT_S="60")
-    for attempt in range(2):
-        p = subprocess.run([sys.executable, worker], env=env, capture_output=True, text=True, timeout=300)
-        if "NO COMMUNICATOR" not in p.stdout:
-            break
-    if "NO COMMUNICATOR" in p.stdout:
-        pytest.skip("no RCCL communicator on this box: " + p.stdout[-300:])
-    assert p.returncode == 0 and "sliders comm worker ok" in p.stdout, p.stdout[-1500:] + p.stderr[-3000:]
