@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge crank piston snap clean
+.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -34,6 +34,9 @@ piston: build               ## sliders: a crank-slider, an elevator between its 
 snap: build                 ## breaks: the bridge's hangers under a limit, crates dropped until they snap (phx_world_set_break_limits, phx_world_break_events)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/snap.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/snap
 
+rest: build                 ## sleeping: boxes drop onto a shelf until the pile rests, a crate wakes the column it hits (phx_world_set_sleeping)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/rest.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/rest
+
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest
 	rm -rf oracle/_ref

@@ -617,6 +617,8 @@ int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
  *                Y, xv or yv), negated when v on that axis is > 0: it points against the motion.
  *     The closest hit is the smallest t, ties to the lowest body index.
  * flags: PHX_QUERY_SKIP_STATIC leaves static bodies (inv_mass == 0 && inv_inertia == 0) out of every result (picking without the ground).
+ *   A body that sleeps (SLEEPING below) is not static to a query although its inverse masses read 0 while it does: picking a box out of a
+ *   resting pile finds it.  A world with sleeping off answers as it always did.
  * Rules:
  *   - Any time, like the gathers: a query sees the geometry at its point of phx_world_stream(w) (between phx_world_pre_solve and
  *     phx_world_finish_step: the geometry before IntegratePosition); the host forms wait for it.
@@ -672,6 +674,7 @@ int  phx_world_cast_boxes_device(phx_world* w, const void* d_casts, int32_t coun
  *       flags    = PHX_CONTACT_NEW if cp.is_newly_created != 0, | PHX_CONTACT_NO_JOINT as above.
  *     Records are ordered by (other, manifold, slot) ascending; the order does not depend on where PackManifolds moved a manifold.
  *     flags PHX_QUERY_SKIP_STATIC leaves out records whose `other` is static (inv_mass == 0 && inv_inertia == 0, as for the queries).
+ *     A sleeping `other` is kept, as for the queries.
  *     Output as phx_world_query_aabb: offsets has count + 1 entries, body q's records are out[offsets[q] .. offsets[q + 1]), *total =
  *     offsets[count]; offsets and *total are filled even when the total exceeds cap, which returns PHX_ERR_CAPACITY with the contents of
  *     out unspecified.  A body may be listed more than once: each listing has its own segment.
@@ -1051,6 +1054,49 @@ typedef struct { int32_t kind, index, body1, body2;   /* PHX_UNIT_*; the unit's 
 int  phx_world_set_break_limits(phx_world* w, int32_t kind, const int32_t* units, const float* limits, int32_t count);
 int  phx_world_get_break_limits(phx_world* w, int32_t kind, float* out, int32_t cap);   /* cap >= the kind's count; +inf where none was set */
 int  phx_world_break_events(phx_world* w, phx_break_event* out, int32_t cap, int64_t* total);
+
+/* SLEEPING — settled islands rest on the device and wake on touch.  tests/sleep_spec.py is the definition and the device matches it byte
+ * for byte.  The contract: a world that sleeps is a world that does not sleep on which somebody applies edits between every two steps:
+ * for every body the rule puts to sleep phx_world_set_inverse_masses(body, 0, 0) and phx_world_set_velocities(body, 0, 0, 0), for every
+ * body it wakes phx_world_set_inverse_masses(body, its saved values).  A sleeper is a static body to every kernel of the step.
+ *   - State per body: asleep, timer (float32), its saved {inv_mass, inv_inertia}.  A body is DYNAMIC iff inv_mass != 0 || inv_inertia != 0,
+ *     MOBILE iff dynamic or asleep, AWAKE iff dynamic and not asleep.
+ *   - The pass runs once per step on the state the step leaves behind, after IntegratePosition: (1) an awake body with
+ *     vx vx + vy vy <= lin lin && w w <= ang ang has timer += dt, every other awake body timer = 0; (2) the edges are the manifolds with
+ *     point_count > 0 whose bodies are both mobile and neither a PHX_BODY_SENSOR, and the units of every kind whose bodies are both
+ *     mobile (a unit to the world is no edge; a unit that broke in this step still counts in it); (3) components, labelled by their
+ *     smallest body; (4) a sleeper is STRUCK if it shares a point_count > 0 manifold with a body that is not mobile and has a nonzero
+ *     velocity or angular-velocity word (a conveyor, a kinematic platform); (5) a component with a sleeper and an awake body or a struck
+ *     sleeper wakes: masses restored, timer = 0 for all of it; a component without a sleeper whose smallest timer is >= time_to_sleep
+ *     sleeps: masses saved and zeroed, velocities +0; anything else stays.  In the step in which something lands on a sleeper the sleeper
+ *     still acts as a static; it wakes at that step's end.
+ *   - No defaults: the scenes' units are the caller's, so sleeping is off until parameters are set; all three finite and >= 0, else
+ *     PHX_ERR_INVALID.  phx_world_set_sleeping(w, NULL) wakes everything, drops the column and turns sleeping off; every mass is then what
+ *     it was, byte for byte.  A world that never enabled it launches exactly what it launched before this existed.
+ *   - Between steps only (PHX_ERR_STATE otherwise), checked whole before anything is queued; a sharded or communicator-attached world
+ *     refuses it, and a world with sleeping enabled refuses to become one.
+ *   - phx_world_get_bodies and the other records show a sleeper as the step sees it: inverse masses 0, velocities 0.
+ *     phx_world_get_sleep_states shows the body's own masses whether it sleeps or not.
+ *   - Every call between steps that names a body or a unit first wakes the sleeping components of the bodies named (a unit names both
+ *     of its bodies): add_accelerations, set_velocities, set_poses, set_inverse_masses (the new values then apply), set_body_inverse_mass,
+ *     set_body_static, set_collision_filters, set_materials, set_body_flags, remove_bodies / remove_outside (the components that lose a
+ *     member, before the compaction), every add_ / remove_ / set_ of pins, links, angles and sliders, and set_break_limits.
+ *     phx_world_set_gravity wakes everything.  phx_world_wake_bodies does only that.  New bodies are awake with timer 0; a removal
+ *     carries the column along; phx_world_set_state resets it (nobody asleep, the totals 0) and keeps the parameters.
+ *   - phx_world_save / phx_world_load with sleeping enabled return PHX_ERR_STATE and change nothing: the snapshot's layout does not carry
+ *     the column.  Turn sleeping off first (which wakes everything).
+ *   - Queries and contact reports: a sleeper is not static under PHX_QUERY_SKIP_STATIC; a query names no body and wakes nobody.
+ *   - phx_world_sleep_counts: the bodies asleep now, and the totals of bodies put to sleep and woken since sleeping was first enabled or
+ *     the last phx_world_set_state.
+ *   - Cost: one 16-byte column, a handful of launches per step behind IntegratePosition and no host wait of its own: the number of
+ *     bodies whose static-ness changed comes down with the next step's joint counts, which is when the schedule needs it. */
+typedef struct { float linear_tolerance, angular_tolerance, time_to_sleep; } phx_sleep_params;
+int  phx_world_set_sleeping(phx_world* w, const phx_sleep_params* p);   /* NULL: wake everything, drop the column, sleeping off */
+int  phx_world_get_sleeping(phx_world* w, phx_sleep_params* out, int32_t* enabled);
+typedef struct { int32_t asleep; float timer, inv_mass, inv_inertia; } phx_sleep_state;   /* 16 B; the body's own masses whether asleep or not */
+int  phx_world_get_sleep_states(phx_world* w, phx_sleep_state* out, int32_t cap);
+int  phx_world_wake_bodies(phx_world* w, const int32_t* bodies, int32_t count);   /* wakes the sleeping component of each listed body */
+int  phx_world_sleep_counts(phx_world* w, int32_t* asleep, int64_t* slept_total, int64_t* woken_total);
 
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);

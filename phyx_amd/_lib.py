@@ -230,6 +230,11 @@ _SIGNATURES = {
     "phx_world_set_break_limits": (C.c_int, [_vp, _i32, _vp, _vp, _i32]),
     "phx_world_get_break_limits": (C.c_int, [_vp, _i32, _vp, _i32]),
     "phx_world_break_events": (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int64)]),
+    "phx_world_set_sleeping": (C.c_int, [_vp, _vp]),
+    "phx_world_get_sleeping": (C.c_int, [_vp, _vp, C.POINTER(_i32)]),
+    "phx_world_get_sleep_states": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_wake_bodies": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_sleep_counts": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "phx_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "phx_snapshot_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "phx_snapshot_destroy": (None, [_vp]),

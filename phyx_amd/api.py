@@ -64,6 +64,8 @@ assert slider_dtype.itemsize == 72
 break_event_dtype = np.dtype([("kind", "<i4"), ("index", "<i4"), ("body1", "<i4"), ("body2", "<i4"), ("step", "<i4"), ("reaction", "<f4"), ("threshold", "<f4"),
                               ("reserved", "<u4")])      # phx_break_event
 assert break_event_dtype.itemsize == 32
+sleep_state_dtype = np.dtype([("asleep", "<i4"), ("timer", "<f4"), ("inv_mass", "<f4"), ("inv_inertia", "<f4")])      # phx_sleep_state
+assert sleep_state_dtype.itemsize == 16
 UNIT_KINDS = ("pin", "link", "angle", "slider")      # PHX_UNIT_PIN ... PHX_UNIT_SLIDER
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
@@ -1143,6 +1145,43 @@ class World:
             cap = int(total.value)                                 # (grown to what the call reported; the queue was kept)
         check(st)
         return out[:total.value].copy()
+
+    # ---- sleeping (include/phyx_amd.h SLEEPING; the specification: tests/sleep_spec.py) ----
+    def set_sleeping(self, linear_tolerance=None, angular_tolerance=None, time_to_sleep=None):
+        """Enable sleeping with the three parameters (all finite and >= 0; no defaults: the scene's units are the caller's), or, with
+        no argument, wake everything and turn it off.  A component whose bodies all stayed below both tolerances for time_to_sleep
+        rests as static bodies until something awake touches it or a call names one of its bodies."""
+        given = [v is not None for v in (linear_tolerance, angular_tolerance, time_to_sleep)]
+        if not any(given):
+            check(self.L.phx_world_set_sleeping(self.h, None))
+            return
+        if not all(given):
+            raise ValueError("set_sleeping: linear_tolerance, angular_tolerance and time_to_sleep go together (none of them: sleeping off)")
+        p = np.array([linear_tolerance, angular_tolerance, time_to_sleep], dtype=np.float32)
+        check(self.L.phx_world_set_sleeping(self.h, _ptr(p)))
+
+    def sleeping(self):
+        """(linear_tolerance, angular_tolerance, time_to_sleep) while sleeping is enabled, else None."""
+        p = np.zeros(3, dtype=np.float32)
+        on = C.c_int32(0)
+        check(self.L.phx_world_get_sleeping(self.h, _ptr(p), C.byref(on)))
+        return tuple(float(x) for x in p) if on.value else None
+
+    def sleep_states(self):
+        """Every body's sleep_state_dtype record: asleep, timer, and its own inverse masses whether it sleeps or not (bodies shows a
+        sleeper as the step sees it: inverse masses and velocities 0)."""
+        return self._get(self.L.phx_world_get_sleep_states, sleep_state_dtype, self.counts()[0])
+
+    def wake_bodies(self, bodies):
+        """Wake the sleeping component of each listed body (a body that is awake is left alone)."""
+        idx = self._indices(bodies, "wake_bodies")
+        check(self.L.phx_world_wake_bodies(self.h, _ptr(idx), len(idx)))
+
+    def sleep_counts(self):
+        """(asleep now, bodies put to sleep in total, bodies woken in total)."""
+        asleep, slept, woken = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        check(self.L.phx_world_sleep_counts(self.h, C.byref(asleep), C.byref(slept), C.byref(woken)))
+        return asleep.value, slept.value, woken.value
 
     # ---- the per-body columns: collision filters, materials, body flags ----
     @staticmethod

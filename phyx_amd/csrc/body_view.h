@@ -30,6 +30,7 @@ struct WorldBodies {
     float4* frame;      // {xVector.x, xVector.y, yVector.x, yVector.y}
     float4* aabb;       // {min.x, min.y, max.x, max.y}
     float2* size;       // geom.size
+    const struct SleepCell* sleep;      // the queries only (query_kernels.h q_static): the sleep column (sleep.h), null while sleeping is off and in every other view
 };
 
 // 16-byte non-temporal store (results that nobody re-reads before the kernel ends: they should not wait in L2 for the

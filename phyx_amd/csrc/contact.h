@@ -5,6 +5,7 @@
 #pragma once
 
 #include "body_view.h"
+#include "sleep.h"
 #include "device_scan.h"
 
 #include <cstdint>
@@ -19,6 +20,7 @@ struct ContactCache {
     const phx_contact_point* cps;
     const phx_contact_joint* joints; int nj;
     const float4* mpos; int n;
+    const SleepCell* sleep;      // the sleep column (sleep.h), null while sleeping is off: PHX_QUERY_SKIP_STATIC keeps a sleeper
 };
 
 class DeviceContacts {

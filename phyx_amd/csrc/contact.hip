@@ -103,7 +103,7 @@ int DeviceContacts::scan_contacts(const ContactCache& c, const int* d_bodies, in
     PHX_TRY(qcount_.reserve((size_t)count)); PHX_TRY(qseg_.reserve((size_t)count));
     PHX_HIP(hipMemsetAsync(qcount_.p, 0, (size_t)count * sizeof(unsigned), s));
     for (int q0 = 0; q0 < count; q0 += scan_chunk_)
-        hipLaunchKernelGGL((k_cscan<false>), dim3(cgrid(c.nm)), dim3(256), 0, s, c.manifolds, c.nm, c.mpos, c.cps, c.joints, c.nj, d_bodies, q0,
+        hipLaunchKernelGGL((k_cscan<false>), dim3(cgrid(c.nm)), dim3(256), 0, s, c.manifolds, c.nm, c.mpos, c.sleep, c.cps, c.joints, c.nj, d_bodies, q0,
                            std::min(scan_chunk_, count - q0), flags, qcount_.p, (unsigned*)nullptr, (phx_contact*)nullptr);
     PHX_HIP(hipGetLastError());
     counts_.resize((size_t)count);
@@ -119,7 +119,7 @@ int DeviceContacts::scan_contacts(const ContactCache& c, const int* d_bodies, in
     // (the cursors start at the segments' offsets: qcount_ becomes them, the counts are on the host)
     PHX_HIP(hipMemcpyAsync(qcount_.p, qseg_.p, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
     for (int q0 = 0; q0 < count; q0 += scan_chunk_)
-        hipLaunchKernelGGL((k_cscan<true>), dim3(cgrid(c.nm)), dim3(256), 0, s, c.manifolds, c.nm, c.mpos, c.cps, c.joints, c.nj, d_bodies, q0,
+        hipLaunchKernelGGL((k_cscan<true>), dim3(cgrid(c.nm)), dim3(256), 0, s, c.manifolds, c.nm, c.mpos, c.sleep, c.cps, c.joints, c.nj, d_bodies, q0,
                            std::min(scan_chunk_, count - q0), flags, (unsigned*)nullptr, qcount_.p, recs_.p);
     // (the cursors have moved to the segments' ends)
     hipLaunchKernelGGL(k_csort_segments, dim3(csort_grid(count)), dim3(256), 0, s, (const phx_contact*)recs_.p, (const unsigned*)qseg_.p,
@@ -133,7 +133,7 @@ int DeviceContacts::index_contacts(const ContactCache& c, const int* d_bodies, i
                                    int64_t* total, Readback& rb, hipStream_t s)
 {
     PHX_TRY(qcount_.reserve((size_t)count)); PHX_TRY(qseg_.reserve((size_t)count));
-    hipLaunchKernelGGL((k_cidx_query<false>), dim3(cgrid(count)), dim3(256), 0, s, c.manifolds, c.mpos, c.cps, c.joints, c.nj, (const unsigned*)offsets_.p,
+    hipLaunchKernelGGL((k_cidx_query<false>), dim3(cgrid(count)), dim3(256), 0, s, c.manifolds, c.mpos, c.sleep, c.cps, c.joints, c.nj, (const unsigned*)offsets_.p,
                        entries_, d_bodies, count, flags, qcount_.p, (const unsigned*)nullptr, (phx_contact*)nullptr);
     PHX_HIP(hipGetLastError());
     counts_.resize((size_t)count);
@@ -146,7 +146,7 @@ int DeviceContacts::index_contacts(const ContactCache& c, const int* d_bodies, i
     PHX_TRY(recs_.reserve((size_t)*total));
     PHX_HIP(hipMemcpyAsync(qseg_.p, qcount_.p, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
     PHX_TRY(device_exclusive_scan(qseg_.p, count, nullptr, scan_, s));
-    hipLaunchKernelGGL((k_cidx_query<true>), dim3(cgrid(count)), dim3(256), 0, s, c.manifolds, c.mpos, c.cps, c.joints, c.nj, (const unsigned*)offsets_.p,
+    hipLaunchKernelGGL((k_cidx_query<true>), dim3(cgrid(count)), dim3(256), 0, s, c.manifolds, c.mpos, c.sleep, c.cps, c.joints, c.nj, (const unsigned*)offsets_.p,
                        entries_, d_bodies, count, flags, (unsigned*)nullptr, (const unsigned*)qseg_.p, recs_.p);
     PHX_HIP(hipGetLastError());
     PHX_TRY(rb.add(out, recs_.p, (size_t)*total * sizeof(phx_contact), s));

@@ -15,6 +15,7 @@
 #pragma once
 
 #include "body_view.h"
+#include "sleep.h"
 
 namespace phx {
 
@@ -22,7 +23,12 @@ constexpr int C_SKIP_STATIC = 1;                // PHX_QUERY_SKIP_STATIC
 constexpr int C_CHUNK_MAX = 1024;               // listed bodies per scan-path chunk (LDS: 4 KiB of bodies, 4 KiB of counters)
 constexpr int C_SORT_TILE = 1024;               // keys per LDS tile of the segment ranking
 
-__device__ __forceinline__ bool c_static(float4 m) { return m.x == 0.f && m.y == 0.f; }
+// (`sleep`: the sleep column, null while sleeping is off: a sleeper is not static to a report, as to a query)
+__device__ __forceinline__ bool c_static(const float4* __restrict__ mpos, const SleepCell* __restrict__ sleep, int b)
+{
+    const float4 m = mpos[b];
+    return m.x == 0.f && m.y == 0.f && !(sleep && sleep[b].asleep);
+}
 
 // live slots of a manifold: point_count clamped to the two slots it owns (set_state and the step keep it in [0, 2])
 __device__ __forceinline__ int c_live(const phx_manifold& m) { return m.point_count < 0 ? 0 : (m.point_count > 2 ? 2 : m.point_count); }
@@ -65,7 +71,7 @@ __device__ __forceinline__ unsigned long long c_key(const phx_contact& r)
 // ---- scan path ------------------------------------------------------------------------------------------------------------------
 // FILL = false: counts[q0 + q] += the records of listing q0 + q;  FILL = true: each record goes to out[cursor[q0 + q]++] (unordered)
 template <bool FILL>
-static __global__ void __launch_bounds__(256) k_cscan(const phx_manifold* __restrict__ manifolds, int nm, const float4* __restrict__ mpos,
+static __global__ void __launch_bounds__(256) k_cscan(const phx_manifold* __restrict__ manifolds, int nm, const float4* __restrict__ mpos, const SleepCell* __restrict__ sleep,
                                                       const phx_contact_point* __restrict__ cps, const phx_contact_joint* __restrict__ joints, int nj,
                                                       const int* __restrict__ bodies, int q0, int nq, int flags, unsigned* __restrict__ counts,
                                                       unsigned* __restrict__ cursor, phx_contact* __restrict__ out)
@@ -79,8 +85,8 @@ static __global__ void __launch_bounds__(256) k_cscan(const phx_manifold* __rest
         const phx_manifold m = manifolds[i];
         const int live = c_live(m);
         if (!live) continue;
-        const bool keep1 = !skip || !c_static(mpos[m.body2]);      // records of body1 (other = body2)
-        const bool keep2 = !skip || !c_static(mpos[m.body1]);
+        const bool keep1 = !skip || !c_static(mpos, sleep, m.body2);      // records of body1 (other = body2)
+        const bool keep2 = !skip || !c_static(mpos, sleep, m.body1);
         for (int q = 0; q < nq; ++q) {
             const int b = s_body[q];
             for (int side = 0; side < 2; ++side) {
@@ -156,7 +162,7 @@ static __global__ void __launch_bounds__(256) k_cidx_body_keys(const phx_manifol
 
 // COUNT: counts[q] = the records of listing q;  FILL: its records at out[seg[q] ..], in segment order
 template <bool FILL>
-static __global__ void __launch_bounds__(256) k_cidx_query(const phx_manifold* __restrict__ manifolds, const float4* __restrict__ mpos,
+static __global__ void __launch_bounds__(256) k_cidx_query(const phx_manifold* __restrict__ manifolds, const float4* __restrict__ mpos, const SleepCell* __restrict__ sleep,
                                                            const phx_contact_point* __restrict__ cps, const phx_contact_joint* __restrict__ joints, int nj,
                                                            const unsigned* __restrict__ offsets, const unsigned* __restrict__ entries,
                                                            const int* __restrict__ bodies, int count, int flags, unsigned* __restrict__ counts,
@@ -172,7 +178,7 @@ static __global__ void __launch_bounds__(256) k_cidx_query(const phx_manifold* _
             const int mi = (int)(e >> 1), side = (int)(e & 1u);
             const phx_manifold m = manifolds[mi];
             const int live = c_live(m);
-            if (!live || (skip && c_static(mpos[side ? m.body1 : m.body2]))) continue;
+            if (!live || (skip && c_static(mpos, sleep, side ? m.body1 : m.body2))) continue;
             if constexpr (FILL) { for (int k = 0; k < live; ++k) out[at + k] = c_record(m, mi, k, side, mpos, cps, joints, nj); }
             at += (unsigned)live;
         }

@@ -14,6 +14,7 @@
 #pragma once
 
 #include "body_view.h"
+#include "sleep.h"
 
 #include <climits>
 
@@ -39,7 +40,9 @@ struct QTree {
 };
 
 // ---- the predicates (include/phyx_amd.h) ----------------------------------------------------------------------------------------
-__device__ __forceinline__ bool q_static(float4 m) { return m.x == 0.f && m.y == 0.f; }
+// (`sleep`: the sleep column, null while sleeping is off — a sleeper's inverse masses are zeroed, but it is a body at rest, not ground:
+//  picking a box out of a resting pile is the first thing a user does)
+__device__ __forceinline__ bool q_static(float4 m, const SleepCell* __restrict__ sleep, int i) { return m.x == 0.f && m.y == 0.f && !(sleep && sleep[i].asleep); }
 
 __device__ __forceinline__ bool q_overlap(float4 a, float4 q) { return a.x <= q.z && a.z >= q.x && a.y <= q.w && a.w >= q.y; }
 
@@ -296,7 +299,7 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
         float4 a = make_float4(NAN, NAN, NAN, NAN), m = make_float4(0.f, 0.f, 0.f, 0.f), f = m;
         float2 h = make_float2(0.f, 0.f);
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
-        const bool any = live && !(skip && q_static(m));
+        const bool any = live && !(skip && q_static(m, w.sleep, i));
         for (int q = 0; q < nq; ++q) {
             const float2 p = qp[q];
             const bool hit = any && qok[q] && q_point_in_box(a, m, f, h, p.x, p.y);
@@ -336,7 +339,7 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
         float4 a = make_float4(NAN, NAN, NAN, NAN), m = make_float4(0.f, 0.f, 0.f, 0.f), f = m;
         float2 h = make_float2(0.f, 0.f);
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
-        const bool any = live && !(skip && q_static(m));
+        const bool any = live && !(skip && q_static(m, w.sleep, i));
         for (int q = 0; q < nq; ++q) {
             bool hit;
             float tin;
@@ -394,7 +397,7 @@ static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n,
     const bool live = i < n;
     const float4 a = live ? w.aabb[i] : make_float4(NAN, NAN, NAN, NAN);
     const float4 m = (OBB || (flags & Q_SKIP_STATIC)) ? w.s.mpos[live ? i : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
-    const bool any = live && !((flags & Q_SKIP_STATIC) && q_static(m));
+    const bool any = live && !((flags & Q_SKIP_STATIC) && q_static(m, w.sleep, i));
     float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
     float2 h = make_float2(0.f, 0.f);
     if (OBB && live) { f = w.frame[i]; h = w.size[i]; }
@@ -562,7 +565,7 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                     if (c < t.n) {
                         b = (int)t.perm[c];
                         const float4 a = w.aabb[b], m = w.s.mpos[b];
-                        if (!(skip && q_static(m))) {
+                        if (!(skip && q_static(m, w.sleep, b))) {
                             if (KIND == QK_POINT) hit = q_point_in_box(a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
                             else if (KIND == QK_RAY) {
                                 QRayBox rb;

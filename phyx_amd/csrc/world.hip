@@ -209,13 +209,20 @@ public:
     int set_break_limits(int kind, const int32_t* which, const float* limits, int count);
     int get_break_limits(int kind, float* out, int cap);
     int break_events(phx_break_event* out, int cap, int64_t* total);
+    // sleeping (phx_world_set_sleeping ... phx_world_sleep_counts): between steps; the pass runs at the end of finish_step (sleep.h)
+    int set_sleeping(const phx_sleep_params* p);
+    int get_sleeping(phx_sleep_params* out, int32_t* enabled) const;
+    int get_sleep_states(phx_sleep_state* out, int cap);
+    int wake_bodies(const int32_t* bodies, int count);
+    int sleep_counts(int32_t* asleep, int64_t* slept_total, int64_t* woken_total);
+    int set_gravity(float g);
     int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
     PinSet& pins() { return pins_; }
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
 
     int nb() const { return (int)host_bodies_.size(); }
     int nm = 0, nj = 0;
-    float gravity = 0.f;
+    float gravity = 0.f;      // (written through set_gravity)
     int shard = 0, shard_count = 1;
     double phase_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool phase_timing = false;          // per-phase host timers: one stream synchronisation per phase, off by default
@@ -230,6 +237,7 @@ private:
     int sync_bodies_to_device();
     int refresh_records();               // resident arrays -> the 128-byte records (getters)
     WorldBodies resident() const { return bodies_.view(); }
+    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); return w; }      // (to a query a sleeper is not static)
     bool host_staged() const { return bodies_dirty_ || !bodies_.records.p; }      // the host-staged records are the world
     int restage_on_host();               // ... again, after the device copy was: records and tables come down
     int refuse_mid_step(const char* what) const;      // PHX_ERR_STATE between pre_solve / step_begin and finish_step / step_end
@@ -325,7 +333,7 @@ private:
     // a re-slab) or the body count; the contact index is current while it was built for this epoch
     unsigned long long contact_epoch_ = 0;
     DeviceContacts contacts_;
-    ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, bodies_.mpos.p, nb()}; }
+    ContactCache contact_cache() const { return ContactCache{d_manifolds_.p, nm, d_cps_.p, d_joints_.p, nj, bodies_.mpos.p, nb(), sleep_col_.ptr()}; }
     int contact_prepare(const char* what, bool host_wait);
     // the optional columns (BodyTable): collision filters — an active table picks the filtered sweep — and materials — an active table
     // picks the solver's material kernels (DeviceSolver::set_materials) — and body flags — an active table picks the sensor variants of
@@ -333,7 +341,20 @@ private:
     BodyTable<FilterColumn> filters_;
     BodyTable<MaterialColumn> materials_;
     BodyTable<FlagsColumn> flags_col_;
-    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); return f(flags_col_); }
+    // ... and the sleep states (sleep.h): active exactly while sleeping is enabled
+    BodyTable<SleepColumn> sleep_col_;
+    DeviceSleep sleep_;
+    bool sleep_count_pending_ = false;   // the pass or a wake may have changed the static set: the device's count has not been looked at yet
+    DevBuf<phx_sleep_state> sleep_out_;
+    SleepGraph sleep_graph();            // the edges as the device holds them now (the unit lists uploaded)
+    int sleep_pass(float dt);            // queued behind IntegratePosition
+    // the sleeping components of the named bodies wake (queued; nothing happens in a world without the column): `bodies`, or the bodies
+    // whose `d_keep` word is 0, or (`all`) every sleeper.  At the top of every call between steps that names a body or a unit.
+    int wake_named(const int* bodies, int count, const unsigned* d_keep = nullptr, bool all = false);
+    template <class P> int wake_units(const int32_t* which, int count);      // both bodies of the listed units
+    void take_sleep_count(unsigned changed);      // what set_inverse_masses does when the static set changed
+    int settle_sleep_count();            // ... by a readback of its own, where no step's count readback has brought it yet
+    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); return f(sleep_col_); }
     // the three setters' skeleton: `rule(k)` is the call's own check of entry k
     template <class Column, class Rule>
     int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
@@ -344,8 +365,8 @@ private:
     int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2);
     // an edit of Fields::width floats per listed unit (already checked): staged for the scatter kernel when the list is on the device
     template <class P, class Fields> int set_unit_fields(const int32_t* which, const float* values, int count);
-    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr()}; }
-    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr()}; }
+    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr()}; }
+    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr()}; }
 };
 
 World::~World()
@@ -435,6 +456,7 @@ int World::settle_on_device()
 
 int World::set_static(int body)
 {
+    PHX_TRY(wake_named(&body, 1));
     PHX_TRY(restage_on_host());
     host_bodies_[body].inv_mass = 0.f;
     host_bodies_[body].inv_inertia = 0.f;
@@ -445,6 +467,7 @@ int World::set_static(int body)
 
 int World::set_inverse_mass(int body, float inv_mass, float inv_inertia)
 {
+    PHX_TRY(wake_named(&body, 1));
     PHX_TRY(restage_on_host());
     host_bodies_[body].inv_mass = inv_mass;
     host_bodies_[body].inv_inertia = inv_inertia;
@@ -618,10 +641,13 @@ int World::refresh_contact_joints()                                         // r
         }
         if (nj) PHX_TRY(device_exclusive_scan_of(JointDeadLoad{(const unsigned*)joint_seen_.p, joint_epoch_}, dead_flags_.p, nj, counters_.p + 1, scan_tiles_, stream_));
         if (nm || nj || pack_pending_) {                                    // counters_[0 .. 3]: adjacent words, one copy
-            unsigned got[4] = {0, 0, 0, 0};
+            unsigned got[4] = {0, 0, 0, 0}, sleep_changed = 0;
             PHX_TRY(rb_.add(got, counters_.p, sizeof got, stream_));
+            const bool with_sleep = sleep_count_pending_;                  // (the last pass's count rides along: no wait of its own)
+            if (with_sleep) PHX_TRY(rb_.add(&sleep_changed, sleep_.words() + SLEEP_CHANGED, sizeof sleep_changed, stream_));
             PHX_TRY(solver_.prelabel_components((const float4*)bodies_.mpos.p, nb(), (const phx_manifold*)d_manifolds_.p, nm));      // (once: the mark is consumed)
             PHX_TRY(rb_.wait(stream_));
+            if (with_sleep) take_sleep_count(sleep_changed);
             host[0] = got[0]; host[1] = got[1];
             if (pack_pending_) { host[2] = got[2]; host[3] = got[3]; }      // (else PackManifolds has settled them already)
             if (!nm) host[0] = 0;                                           // (not written this step)
@@ -642,6 +668,7 @@ int World::refresh_contact_joints()                                         // r
         if (nm == nm_before) break;
         ++deferred_pack_retries;                                            // the bet was lost: match again under a new epoch (one more pass: nothing is pending now)
     }
+    PHX_TRY(settle_sleep_count());                                          // (a world without manifolds and joints: nothing brought it)
     const int fresh = (int)host[0], dead = (int)host[1], old = nj;
     const int total = nj + fresh;
     if (dead) PHX_TRY(mover_pos_.reserve((size_t)total + 2));
@@ -926,6 +953,7 @@ int World::finish_step(float dt, const phx_config& cfg)
         PHX_HIP(hipGetLastError());
     } else PHX_TRY(solve_and_integrate(dt, cfg));
     records_stale_ = true;
+    if (sleep_.on()) PHX_TRY(sleep_pass(dt));                               // (a world that never enabled sleeping queues nothing here)
     lap(7);
     return PHX_OK;
 }
@@ -980,6 +1008,11 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
     pins_.clear();                                                          // ... and no pin or link is left, no break limit and no break event
     break_step_ = 0;
+    if (sleep_.on()) {                                                      // sleeping stays enabled: nobody asleep, the totals 0
+        sleep_col_.host.assign((size_t)body_count, SleepColumn::initial());
+        sleep_col_.active = true;
+        PHX_TRY(sleep_.clear_totals(stream_));
+    }
     PHX_TRY(sync_bodies_to_device());
     nm = manifold_count; nj = joint_count;
     PHX_TRY(d_manifolds_.reserve(std::max<size_t>(nm, 1))); PHX_TRY(d_cps_.reserve(std::max<size_t>(2 * (size_t)nm, 1))); PHX_TRY(d_joints_.reserve(std::max<size_t>(nj, 1)));
@@ -1022,6 +1055,7 @@ int World::snapshot_guard(const char* what, const Snapshot& s) const
 {
     PHX_TRY(refuse_mid_step(what));
     if (shard_count > 1 || comm_) { set_error("%s: a sharded world has no snapshots", what); return PHX_ERR_STATE; }
+    if (sleep_.on()) { set_error("%s: sleeping is enabled and a snapshot does not carry the sleep states (phx_world_set_sleeping(w, NULL) first)", what); return PHX_ERR_STATE; }
     if (s.device() != device_) { set_error("%s: the snapshot lives on device %d, the world on device %d (move it as a blob)", what, s.device(), device_); return PHX_ERR_INVALID; }
     return PHX_OK;
 }
@@ -1185,6 +1219,7 @@ int World::edit(Edit kind, const int* bodies, const float* values, int count)
     static const char* const what[] = {"phx_world_add_accelerations", "phx_world_set_velocities", "phx_world_set_poses"};
     PHX_TRY(check_batch(what[kind], bodies, values, count, true));
     if (!count) return PHX_OK;
+    PHX_TRY(wake_named(bodies, count));
     const int width = kind == EDIT_POSES ? 6 : 3;
     if (host_staged()) {                                    // the host-staged records are the world: write into them
         for (int k = 0; k < count; ++k) {
@@ -1353,6 +1388,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
         hipLaunchKernelGGL(k_remove_listed, dim3(rgrid(count)), dim3(256), 0, stream_, d_bodies, count, rm_keep_.p);
     }
     PHX_HIP(hipGetLastError());
+    PHX_TRY(wake_named(nullptr, 0, rm_keep_.p));                            // (the sleeping components that lose a member wake before anything moves)
     // 2. where the kept bodies, manifolds and joints go (a zero count writes a zero total)
     PHX_TRY(device_exclusive_scan_of(BodyKeepLoad{rm_keep_.p}, rm_bnew_.p, n, rm_counts_.p, scan_tiles_, stream_));
     const BodiesKept kept{rm_keep_.p, rm_bnew_.p};
@@ -1453,6 +1489,7 @@ int World::set_inverse_masses(const int* bodies, const float* values, int count)
     for (int k = 0; k < 2 * count; ++k)
         if (!std::isfinite(values[k]) || !(values[k] >= 0.f)) { set_error("%s: entry %d: inverse masses must be finite and >= 0", what, k / 2); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
+    PHX_TRY(wake_named(bodies, count));                                     // (a sleeper's own masses come back first; the new values then apply)
     joints_changed_ = true;                                                 // which bodies are static is part of the schedule's topology
     pins_.statics_changed();
     if (host_staged()) {
@@ -1478,6 +1515,7 @@ int World::set_column(const char* what, BodyTable<Column>& table, const int32_t*
     PHX_TRY(check_batch(what, bodies, values, count, true));
     for (int k = 0; k < count; ++k) PHX_TRY(rule(k));
     if (!count) return PHX_OK;
+    PHX_TRY(wake_named(bodies, count));
     const int n = nb();
     if (host_staged() && host_path_ok) { table.set_host(bodies, values, count, n); return PHX_OK; }      // (the table goes up with the bodies)
     PHX_TRY(use_device(device_));
@@ -1525,6 +1563,7 @@ int World::get_materials(phx_material* out, int cap) { return get_table("phx_wor
 // the sharded modes (phx_world_set_shard, set_comm, reslab) carry no optional column: refused while some body's value is not the default
 int World::refuse_tables(const char* what)
 {
+    if (sleep_.on()) { set_error("%s: sleeping is enabled, which a sharded world does not carry (phx_world_set_sleeping(w, NULL) first)", what); return PHX_ERR_STATE; }
     return each_table([&](auto& t) -> int {
         using Column = typename std::decay_t<decltype(t)>::column;
         if (!t.active) return PHX_OK;
@@ -1623,6 +1662,11 @@ int World::add_units(const P* recs, int count, int* first)
     UnitList<P>& list = pins_.list<P>();
     if (first) *first = list.count();
     if (!count) return PHX_OK;
+    if (sleep_col_.active) {                                                // (the new units' bodies)
+        std::vector<int> named;
+        for (int k = 0; k < count; ++k) { named.push_back(recs[k].body1); if (recs[k].body2 >= 0) named.push_back(recs[k].body2); }
+        PHX_TRY(wake_named(named.data(), (int)named.size()));
+    }
     PHX_TRY(settle_on_device());
     pins_.units_changed();
     return list.add(recs, count, stream_);
@@ -1633,6 +1677,7 @@ int World::remove_units(const int32_t* which, int count)
 {
     PHX_TRY(check_unit_indices<P>(UnitKind<P>::remove, which, which, count));
     if (!count) return PHX_OK;
+    PHX_TRY(wake_units<P>(which, count));
     PHX_TRY(settle_on_device());
     pins_.units_changed();
     return pins_.list<P>().remove(which, count, stream_);
@@ -1642,6 +1687,7 @@ template <class P, class Fields>
 int World::set_unit_fields(const int32_t* which, const float* values, int count)
 {
     if (!count) return PHX_OK;
+    PHX_TRY(wake_units<P>(which, count));
     UnitList<P>& list = pins_.list<P>();
     const int* d_which = nullptr; const float* d_values = nullptr;
     if (list.on_device()) {
@@ -1745,6 +1791,7 @@ int World::set_break_limits(int kind, const int32_t* which, const float* limits,
         for (int k = 0; k < count; ++k)
             if (!(limits[k] > 0.f)) { set_error("%s: %s %d: break limit %g is not > 0", what, UnitKind<P>::noun, k, (double)limits[k]); return PHX_ERR_INVALID; }
         if (!count) return PHX_OK;
+        PHX_TRY(wake_units<P>(which, count));
         UnitList<P>& list = pins_.list<P>();
         const int* d_which = nullptr; const float* d_values = nullptr;
         if (list.on_device()) {
@@ -1801,8 +1848,171 @@ int World::pin_schedule(const Schedule** out)
     PHX_TRY(use_device(device_));
     PHX_TRY(solver_.synchronize());
     PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    PHX_TRY(settle_sleep_count());                                          // (bodies the last pass put to sleep or woke are part of the static set)
     PHX_TRY(pins_.prepare(bodies_.mpos.p, nb(), rb_, stream_));
     *out = &pins_.schedule();
+    return PHX_OK;
+}
+
+// ---- sleeping ---------------------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h SLEEPING, tests/sleep_spec.py; the column, the pass and the wake by list: sleep.h.  Here: the calls, the
+// place of the pass in the step, and how the host learns that the static set changed — the device counts the bodies the pass (or a wake)
+// put to sleep or woke, and the next step's joint-count readback brings the count along (refresh_contact_joints), in front of the
+// solve and of the pin pass, which are what consult the static set.
+SleepGraph World::sleep_graph()
+{
+    SleepGraph g = {};
+    g.manifolds = d_manifolds_.p; g.nm = nm; g.flags = flags_col_.ptr();
+    int kind = 0;
+    pins_.each_list([&](auto& l) {
+        using P = typename std::decay_t<decltype(l)>::record;
+        static_assert(offsetof(P, body1) == 0 && offsetof(P, body2) == 4, "a unit's record begins with its bodies");
+        g.units[kind++] = SleepGraph::List{reinterpret_cast<const char*>(l.device()), (int)sizeof(P), l.count()};
+        return PHX_OK;
+    });
+    return g;
+}
+
+int World::sleep_pass(float dt)
+{
+    if (!nb()) return PHX_OK;
+    if (pins_.units()) PHX_TRY(pins_.upload(stream_));                      // (current already behind a pin pass: nothing is copied)
+    PHX_TRY(sleep_.pass(resident(), bodies_.records.p, sleep_col_.dev.p, nb(), sleep_graph(), dt, stream_));
+    sleep_count_pending_ = true;
+    return PHX_OK;
+}
+
+void World::take_sleep_count(unsigned changed)
+{
+    sleep_count_pending_ = false;
+    if (!changed) return;
+    joints_changed_ = true;                                                 // which bodies are static is part of the schedule's topology
+    pins_.statics_changed();
+}
+
+int World::settle_sleep_count()
+{
+    if (!sleep_count_pending_) return PHX_OK;
+    unsigned changed = 0;
+    PHX_TRY(rb_.add(&changed, sleep_.words() + SLEEP_CHANGED, sizeof changed, stream_));
+    PHX_TRY(rb_.wait(stream_));
+    take_sleep_count(changed);
+    return PHX_OK;
+}
+
+int World::wake_named(const int* bodies, int count, const unsigned* d_keep, bool all)
+{
+    if (!sleep_col_.active || !nb() || (!all && !d_keep && !count)) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before masses change)
+    PHX_TRY(settle_breaks());                                               // (a unit that broke in the last step is no edge any more)
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies and the column go up as the next step would take them)
+    if (pins_.units()) PHX_TRY(pins_.upload(stream_));
+    const int* d_list = nullptr; const float* unused = nullptr;
+    if (!all && !d_keep) PHX_TRY(stage_batch(bodies, nullptr, count, 0, &d_list, &unused));
+    PHX_TRY(sleep_.wake(resident(), bodies_.records.p, sleep_col_.dev.p, nb(), sleep_graph(), d_list, count, d_keep, all, stream_));
+    sleep_count_pending_ = true;
+    return PHX_OK;
+}
+
+template <class P>
+int World::wake_units(const int32_t* which, int count)
+{
+    if (!sleep_col_.active || !count) return PHX_OK;
+    const std::vector<P>& units = pins_.list<P>().host();                   // (the bodies: always current)
+    std::vector<int> named;
+    for (int k = 0; k < count; ++k) {
+        const P& u = units[(size_t)which[k]];
+        named.push_back(u.body1);
+        if (u.body2 >= 0) named.push_back(u.body2);
+    }
+    return wake_named(named.data(), (int)named.size());
+}
+
+int World::set_sleeping(const phx_sleep_params* p)
+{
+    static const char* const what = "phx_world_set_sleeping";
+    PHX_TRY(refuse_mid_step(what));
+    PHX_TRY(refuse_sharded(what, SleepColumn::plural));
+    if (!p) {
+        if (!sleep_.on()) return PHX_OK;
+        PHX_TRY(wake_named(nullptr, 0, nullptr, true));                     // every mass is its own again, byte for byte
+        sleep_.disable();
+        sleep_col_.reset();
+        return PHX_OK;
+    }
+    const float v[3] = {p->linear_tolerance, p->angular_tolerance, p->time_to_sleep};
+    static const char* const names[3] = {"linear_tolerance", "angular_tolerance", "time_to_sleep"};
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(v[k]) || !(v[k] >= 0.f)) { set_error("%s: %s %g must be finite and >= 0", what, names[k], (double)v[k]); return PHX_ERR_INVALID; }
+    PHX_TRY(use_device(device_));
+    if (!sleep_col_.active) {                                               // the column: every body awake, timer 0
+        if (host_staged()) sleep_col_.host.assign((size_t)nb(), SleepColumn::initial());
+        else {
+            PHX_TRY(settle_on_device());
+            PHX_TRY(sleep_col_.dev.reserve((size_t)std::max(nb(), 1)));
+            PHX_TRY(sleep_.fill(sleep_col_.dev.p, nb(), stream_));
+        }
+        sleep_col_.active = true;
+    }
+    return sleep_.enable(*p, stream_);
+}
+
+int World::get_sleeping(phx_sleep_params* out, int32_t* enabled) const
+{
+    if (out) *out = sleep_.params();
+    if (enabled) *enabled = sleep_.on() ? 1 : 0;
+    return PHX_OK;
+}
+
+int World::get_sleep_states(phx_sleep_state* out, int cap)
+{
+    static const char* const what = "phx_world_get_sleep_states";
+    PHX_TRY(refuse_mid_step(what));
+    const int n = nb();
+    if (cap < n) { set_error("%s: room for %d bodies, the world has %d", what, cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    PHX_TRY(sleep_out_.reserve((size_t)n));
+    PHX_TRY(sleep_.states(bodies_.mpos.p, sleep_col_.ptr(), n, sleep_out_.p, stream_));
+    PHX_TRY(rb_.add(out, sleep_out_.p, (size_t)n * sizeof(phx_sleep_state), stream_));
+    return rb_.wait(stream_);
+}
+
+int World::wake_bodies(const int32_t* bodies, int count)
+{
+    static const char* const what = "phx_world_wake_bodies";
+    PHX_TRY(refuse_mid_step(what));
+    PHX_TRY(refuse_sharded(what, SleepColumn::plural));
+    PHX_TRY(check_batch(what, bodies, bodies, count, false));              // (no values: the indices stand in for them; a body may be named twice)
+    return wake_named(bodies, count);
+}
+
+int World::sleep_counts(int32_t* asleep, int64_t* slept_total, int64_t* woken_total)
+{
+    PHX_TRY(refuse_mid_step("phx_world_sleep_counts"));
+    unsigned long long totals[2] = {0, 0};
+    if (sleep_.words()) {
+        PHX_TRY(use_device(device_));
+        PHX_TRY(solver_.synchronize());
+        PHX_TRY(rb_.add(totals, sleep_.words() + SLEEP_SLEPT, sizeof totals, stream_));
+        PHX_TRY(rb_.wait(stream_));
+    }
+    if (asleep) *asleep = (int32_t)(totals[0] - totals[1]);
+    if (slept_total) *slept_total = (int64_t)totals[0];
+    if (woken_total) *woken_total = (int64_t)totals[1];
+    return PHX_OK;
+}
+
+int World::set_gravity(float g)
+{
+    if (sleep_.on()) {                                                      // a change of gravity disturbs every pile
+        PHX_TRY(refuse_mid_step("phx_world_set_gravity"));
+        PHX_TRY(wake_named(nullptr, 0, nullptr, true));
+    }
+    gravity = g;
     return PHX_OK;
 }
 
@@ -1846,7 +2056,7 @@ int World::query_aabb(const float* boxes, int count, int flags, int32_t* offsets
     PHX_TRY(query_prepare(true));
     const float* d_boxes = nullptr;
     if (count && nb()) { const int* unused = nullptr; PHX_TRY(stage_batch(nullptr, boxes, count, 4, &unused, &d_boxes)); }
-    return query_.aabb(resident(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
+    return query_.aabb(query_view(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
 }
 
 int World::query_points(const float* points, int count, int flags, int32_t* body)
@@ -1859,7 +2069,7 @@ int World::query_points(const float* points, int count, int flags, int32_t* body
     const int* unused = nullptr; const float* d_points = nullptr;
     PHX_TRY(stage_batch(nullptr, points, count, 2, &unused, &d_points));
     PHX_TRY(q_body_.reserve((size_t)count));
-    PHX_TRY(query_.points(resident(), nb(), geom_epoch_, d_points, count, flags, q_body_.p, stream_));
+    PHX_TRY(query_.points(query_view(), nb(), geom_epoch_, d_points, count, flags, q_body_.p, stream_));
     PHX_TRY(rb_.add(body, q_body_.p, (size_t)count * sizeof(int), stream_));
     return rb_.wait(stream_);
 }
@@ -1874,7 +2084,7 @@ int World::raycast(const float* rays, int count, int flags, phx_ray_hit* out)
     const int* unused = nullptr; const float* d_rays = nullptr;
     PHX_TRY(stage_batch(nullptr, rays, count, 5, &unused, &d_rays));
     PHX_TRY(q_hits_.reserve((size_t)count));
-    PHX_TRY(query_.rays(resident(), nb(), geom_epoch_, d_rays, count, flags, q_hits_.p, stream_));
+    PHX_TRY(query_.rays(query_view(), nb(), geom_epoch_, d_rays, count, flags, q_hits_.p, stream_));
     PHX_TRY(rb_.add(out, q_hits_.p, (size_t)count * sizeof(phx_ray_hit), stream_));
     return rb_.wait(stream_);
 }
@@ -1886,7 +2096,7 @@ int World::query_points_device(const void* d_points, int count, int flags, void*
     if (count && ((reinterpret_cast<uintptr_t>(d_points) | reinterpret_cast<uintptr_t>(d_body)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     PHX_TRY(query_prepare(false));
-    return query_.points(resident(), nb(), geom_epoch_, static_cast<const float*>(d_points), count, flags, static_cast<int*>(d_body), stream_);
+    return query_.points(query_view(), nb(), geom_epoch_, static_cast<const float*>(d_points), count, flags, static_cast<int*>(d_body), stream_);
 }
 
 int World::raycast_device(const void* d_rays, int count, int flags, void* d_out)
@@ -1896,7 +2106,7 @@ int World::raycast_device(const void* d_rays, int count, int flags, void* d_out)
     if (count && ((reinterpret_cast<uintptr_t>(d_rays) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     PHX_TRY(query_prepare(false));
-    return query_.rays(resident(), nb(), geom_epoch_, static_cast<const float*>(d_rays), count, flags, static_cast<phx_ray_hit*>(d_out), stream_);
+    return query_.rays(query_view(), nb(), geom_epoch_, static_cast<const float*>(d_rays), count, flags, static_cast<phx_ray_hit*>(d_out), stream_);
 }
 
 int World::query_boxes(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
@@ -1908,7 +2118,7 @@ int World::query_boxes(const float* boxes, int count, int flags, int32_t* offset
     PHX_TRY(query_prepare(true));
     const float* d_boxes = nullptr;
     if (count && nb()) { const int* unused = nullptr; PHX_TRY(stage_batch(nullptr, boxes, count, 8, &unused, &d_boxes)); }
-    return query_.shapes(resident(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
+    return query_.shapes(query_view(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
 }
 
 int World::cast_boxes(const float* casts, int count, int flags, phx_shape_hit* out)
@@ -1921,7 +2131,7 @@ int World::cast_boxes(const float* casts, int count, int flags, phx_shape_hit* o
     const int* unused = nullptr; const float* d_casts = nullptr;
     PHX_TRY(stage_batch(nullptr, casts, count, 11, &unused, &d_casts));
     PHX_TRY(q_shape_hits_.reserve((size_t)count));
-    PHX_TRY(query_.casts(resident(), nb(), geom_epoch_, d_casts, count, flags, q_shape_hits_.p, stream_));
+    PHX_TRY(query_.casts(query_view(), nb(), geom_epoch_, d_casts, count, flags, q_shape_hits_.p, stream_));
     PHX_TRY(rb_.add(out, q_shape_hits_.p, (size_t)count * sizeof(phx_shape_hit), stream_));
     return rb_.wait(stream_);
 }
@@ -1933,13 +2143,13 @@ int World::cast_boxes_device(const void* d_casts, int count, int flags, void* d_
     if (count && ((reinterpret_cast<uintptr_t>(d_casts) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     PHX_TRY(query_prepare(false));
-    return query_.casts(resident(), nb(), geom_epoch_, static_cast<const float*>(d_casts), count, flags, static_cast<phx_shape_hit*>(d_out), stream_);
+    return query_.casts(query_view(), nb(), geom_epoch_, static_cast<const float*>(d_casts), count, flags, static_cast<phx_shape_hit*>(d_out), stream_);
 }
 
 int World::query_index_build()
 {
     PHX_TRY(query_prepare(false));
-    return query_.ensure_index(resident(), nb(), geom_epoch_, stream_);
+    return query_.ensure_index(query_view(), nb(), geom_epoch_, stream_);
 }
 
 // ---- contact reports ----------------------------------------------------------------------------------------------------------------
@@ -2043,7 +2253,7 @@ int phx_world_set_body_inverse_mass(phx_world* w, int32_t body, float inv_mass, 
     return w->impl.set_inverse_mass(body, inv_mass, inv_inertia);
 }
 
-int phx_world_set_gravity(phx_world* w, float g) { PHX_REQUIRE(w, "null handle"); w->impl.gravity = g; return PHX_OK; }
+int phx_world_set_gravity(phx_world* w, float g) { PHX_REQUIRE(w, "null handle"); return w->impl.set_gravity(g); }
 
 int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
 {
@@ -2503,6 +2713,16 @@ int phx_world_get_break_limits(phx_world* w, int32_t kind, float* out, int32_t c
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
     return w->impl.get_break_limits(kind, out, cap);
+}
+
+int phx_world_set_sleeping(phx_world* w, const phx_sleep_params* p) { PHX_REQUIRE(w, "null handle"); return w->impl.set_sleeping(p); }
+int phx_world_get_sleeping(phx_world* w, phx_sleep_params* out, int32_t* enabled) { PHX_REQUIRE(w, "null handle"); return w->impl.get_sleeping(out, enabled); }
+int phx_world_get_sleep_states(phx_world* w, phx_sleep_state* out, int32_t cap) { PHX_REQUIRE(w && (out || cap == 0), "null handle / buffer"); return w->impl.get_sleep_states(out, cap); }
+int phx_world_wake_bodies(phx_world* w, const int32_t* bodies, int32_t count) { PHX_REQUIRE(w, "null handle"); return w->impl.wake_bodies(bodies, count); }
+int phx_world_sleep_counts(phx_world* w, int32_t* asleep, int64_t* slept_total, int64_t* woken_total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.sleep_counts(asleep, slept_total, woken_total);
 }
 
 int phx_world_break_events(phx_world* w, phx_break_event* out, int32_t cap, int64_t* total)

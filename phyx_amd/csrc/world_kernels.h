@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "narrowphase.h"
+#include "sleep.h"
 
 namespace phx {
 
@@ -165,6 +166,7 @@ struct BodyColumns {
     uint4* filters;
     float2* materials;
     uint32_t* flags;
+    SleepCell* sleep;
 };
 
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
@@ -197,6 +199,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         if (cols.filters) cols.filters[i] = FilterColumn::initial();
         if (cols.materials) cols.materials[i] = MaterialColumn::initial();
         if (cols.flags) cols.flags[i] = FlagsColumn::initial();
+        if (cols.sleep) cols.sleep[i] = SleepColumn::initial();      // (awake, timer 0)
     }
 }
 
@@ -580,6 +583,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
         if (cols.filters) out_cols.filters[to] = cols.filters[i];
         if (cols.materials) out_cols.materials[to] = cols.materials[i];
         if (cols.flags) out_cols.flags[to] = cols.flags[i];
+        if (cols.sleep) out_cols.sleep[to] = cols.sleep[i];
         if (out_cols.accel) {
             out_cols.accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;
