@@ -1098,6 +1098,60 @@ int  phx_world_get_sleep_states(phx_world* w, phx_sleep_state* out, int32_t cap)
 int  phx_world_wake_bodies(phx_world* w, const int32_t* bodies, int32_t count);   /* wakes the sleeping component of each listed body */
 int  phx_world_sleep_counts(phx_world* w, int32_t* asleep, int64_t* slept_total, int64_t* woken_total);
 
+/* FORCE FIELDS — wind, attractors, drag zones and blasts, computed on the device from the bodies' own state.  tests/field_spec.py is the
+ * definition (float32, every operation rounded on its own, IEEE division and square root) and the device matches it byte for byte.  The
+ * list is a setting of the world, like gravity: at most PHX_MAX_FIELDS records, applied in list order at the head of every step.
+ *   - Who: body i is affected iff inv_mass > 0 (the rule gravity uses, ref: World.cpp:44: static bodies and sleepers are never written)
+ *     and category_i & mask != 0, category_i the body's collision-filter category (1 for every body while no filter was ever set).
+ *   - Region, tested on the body's centre {x, y}; a NaN centre is outside every shape but ALL.  PHX_REGION_ALL: every body, region = 0.
+ *     PHX_REGION_BOX: region = {min.x, min.y, max.x, max.y}, closed: x >= min.x && x <= max.x && y >= min.y && y <= max.y.
+ *     PHX_REGION_DISC: region = {c.x, c.y, r, 0}, closed: dx = x - c.x, dy = y - c.y, dx dx + dy dy <= r r.
+ *   - PHX_FIELD_UNIFORM: value = {ax, ay, angular, 0}; a = {ax, ay, angular}.
+ *     PHX_FIELD_RADIAL: value = {c.x, c.y, strength, falloff_radius}; dx = x - c.x, dy = y - c.y, d = sqrt(dx dx + dy dy); nothing if
+ *     !(d > 2^-10); mag = strength, or with falloff_radius > 0: t = 1 - d / falloff_radius, nothing if !(t > 0), mag = strength t;
+ *     a = {(dx / d) mag, (dy / d) mag, 0}.  Positive strength pushes away from the centre, negative attracts.
+ *     PHX_FIELD_DRAG: value = {flow.x, flow.y, k_lin, k_ang}; c = min(k_lin dt, 1) / dt, ca = min(k_ang dt, 1) / dt;
+ *     a = {(flow.x - v.x) c, (flow.y - v.y) c, (0 - w) ca}: the clamp keeps any stiffness from overshooting the flow in one explicit step.
+ *     PHX_FIELD_FORCE in flags: the value is a force / torque: a.xy *= inv_mass, a.z *= inv_inertia.
+ *   - Sum: accel_i = pending_i + a(field 0) + a(field 1) + ... in list order, every + rounded; pending_i is what
+ *     phx_world_add_accelerations or phx_world_set_state left pending, 0 where nothing is.  A field that does not contribute adds
+ *     nothing (not + 0).
+ *   - When: the pass runs at the head of every step (phx_world_update, phx_world_pre_solve, phx_world_step_begin) with that step's dt, on
+ *     the positions and velocities the step starts from, in front of IntegrateVelocity, which consumes the sums as it consumes pending
+ *     accelerations; the records' accelerations read zero after the step, as always.  One launch per step whatever the list's length;
+ *     a world with an empty list launches nothing and allocates nothing.
+ *   - phx_field_check is the single validator (host only, no device): 0 <= count <= PHX_MAX_FIELDS, no NULL array with count > 0; per
+ *     field, in this order: a known kind, a known shape, no unknown flag bit, mask != 0, every float finite, box min <= max, disc r >= 0,
+ *     the words its shape and kind do not use exactly 0, falloff_radius >= 0, both k >= 0.  The first failure wins: PHX_ERR_INVALID,
+ *     named in phx_last_error.
+ *   - phx_world_set_fields replaces the whole list (count 0: none) and phx_world_pulse_fields applies one: both call the validator and
+ *     leave the world unchanged on failure; between steps only (PHX_ERR_STATE inside pre_solve .. finish_step and step_begin .. step_end);
+ *     a sharded or communicator-attached world refuses them (PHX_ERR_STATE), and phx_world_set_shard / set_comm refuse a world whose
+ *     list is not empty.  phx_world_get_fields: *count = the list's length, the records into out (PHX_ERR_CAPACITY if cap is smaller).
+ *   - The list names no body: phx_world_set_state, phx_world_load, removals and spawns leave it alone, and snapshots do not hold it.
+ *     Setting or clearing it changes no joint topology: the cached schedule, the broadphase's splitters and the query / contact indexes stay.
+ *   - phx_world_pulse_fields — a blast is a RADIAL pulse with a falloff radius: the velocity change the listed fields would cause in one
+ *     step of dt = 1, applied now by the same arithmetic with the velocity as the sum's start: vel_i = vel_i + a(field 0) + a(field 1) + ...
+ *     (a DRAG reads the velocity the call found).  Pending accelerations are not touched.  Host-staged bodies are uploaded first, as a removal
+ *     uploads them.  Sleepers rest as static bodies and are not affected: a caller that wants a blast to wake a pile calls
+ *     phx_world_query_aabb over the blast's extent and phx_world_wake_bodies on the hits first.
+ *   - phx_world_apply_impulses is an edit with the edits' rules (EDITS BETWEEN STEPS: indices in range and distinct, checked whole, staged
+ *     and queued; every value finite): on a body with inv_mass > 0, r = point - pos, v += inv_mass J, w -= inv_inertia (r.x J.y - r.y J.x) —
+ *     the engine's angular velocity is clockwise-positive (tests/pin_spec.py); a static body is skipped.  Like the other edits it wakes
+ *     the sleeping components of the bodies it names.
+ *   - phx_world_field_passes: the step passes launched so far (pulses do not count). */
+#define PHX_MAX_FIELDS 256
+enum { PHX_FIELD_UNIFORM = 0, PHX_FIELD_RADIAL = 1, PHX_FIELD_DRAG = 2 };      /* kind  */
+enum { PHX_REGION_ALL = 0, PHX_REGION_BOX = 1, PHX_REGION_DISC = 2 };          /* shape */
+#define PHX_FIELD_FORCE 1u   /* value is a force / torque: scaled by the body's inverse mass / inverse inertia */
+typedef struct { int32_t kind, shape; uint32_t mask, flags; float region[4]; float value[4]; } phx_field;   /* 48 B */
+int  phx_field_check(const phx_field* fields, int32_t count);
+int  phx_world_set_fields(phx_world* w, const phx_field* fields, int32_t count);
+int  phx_world_get_fields(phx_world* w, phx_field* out, int32_t cap, int32_t* count);
+int  phx_world_pulse_fields(phx_world* w, const phx_field* fields, int32_t count);
+int  phx_world_apply_impulses(phx_world* w, const int32_t* bodies, const float* impulses /* 4 per body: J.x, J.y, point.x, point.y */, int32_t count);
+int  phx_world_field_passes(phx_world* w, int64_t* passes);
+
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);
 /* handles owned by the world (for stage-level queries after an update) */

@@ -8,6 +8,8 @@ from .api import (Configuration, Solver, Collider, World, Snapshot, Comm, SOLVE_
                   ISLAND_SINGLE, ISLAND_MULTIPLE, ISLAND_SINGLE_SLOPPY, ISLAND_MULTIPLE_SLOPPY,
                   rigid_body_dtype, contact_point_dtype, manifold_dtype, contact_joint_dtype, ray_hit_dtype,
                   shape_hit_dtype, box_from_angle,
+                  field_dtype, uniform_field, radial_field, drag_field, field_check, MAX_FIELDS, FIELD_UNIFORM, FIELD_RADIAL, FIELD_DRAG,
+                  REGION_ALL, REGION_BOX, REGION_DISC, FIELD_FORCE,
                   contact_dtype, contact_marker_dtype, collision_filter_dtype, material_dtype, BODY_SENSOR,
                   broadphase_entry_dtype, sort_entry_dtype, device_count, device_info, DeviceArray, DeviceBuffer, exchange_layout, schedule_colours, schedule_groups, schedule_islands, schedule_priority)
 from ._lib import PhxError  # noqa: F401

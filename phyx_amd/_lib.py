@@ -56,6 +56,11 @@ class SlabTransport(C.Structure):
                 ("user", C.c_void_p)]
 
 
+class Field(C.Structure):
+    """phx_field: one force field (include/phyx_amd.h FORCE FIELDS), 48 bytes; api.field_dtype is its numpy mirror."""
+    _fields_ = [("kind", C.c_int32), ("shape", C.c_int32), ("mask", C.c_uint32), ("flags", C.c_uint32), ("region", C.c_float * 4), ("value", C.c_float * 4)]
+
+
 _lib = None
 
 _vp, _i32, _f32 = C.c_void_p, C.c_int32, C.c_float
@@ -235,6 +240,12 @@ _SIGNATURES = {
     "phx_world_get_sleep_states": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_wake_bodies": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_sleep_counts": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "phx_field_check": (C.c_int, [_vp, _i32]),
+    "phx_world_set_fields": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_get_fields": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
+    "phx_world_pulse_fields": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_apply_impulses": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_field_passes": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "phx_pin_schedule": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "phx_snapshot_create": (C.c_int, [C.POINTER(_vp), C.c_int]),
     "phx_snapshot_destroy": (None, [_vp]),

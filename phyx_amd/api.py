@@ -66,6 +66,12 @@ break_event_dtype = np.dtype([("kind", "<i4"), ("index", "<i4"), ("body1", "<i4"
 assert break_event_dtype.itemsize == 32
 sleep_state_dtype = np.dtype([("asleep", "<i4"), ("timer", "<f4"), ("inv_mass", "<f4"), ("inv_inertia", "<f4")])      # phx_sleep_state
 assert sleep_state_dtype.itemsize == 16
+field_dtype = np.dtype([("kind", "<i4"), ("shape", "<i4"), ("mask", "<u4"), ("flags", "<u4"), ("region", "<f4", (4,)), ("value", "<f4", (4,))])      # phx_field
+assert field_dtype.itemsize == 48 == C.sizeof(_lib.Field)
+MAX_FIELDS = 256                                               # PHX_MAX_FIELDS
+FIELD_UNIFORM, FIELD_RADIAL, FIELD_DRAG = 0, 1, 2              # phx_field.kind
+REGION_ALL, REGION_BOX, REGION_DISC = 0, 1, 2                  # phx_field.shape
+FIELD_FORCE = 1                                                # PHX_FIELD_FORCE (phx_field.flags)
 UNIT_KINDS = ("pin", "link", "angle", "slider")      # PHX_UNIT_PIN ... PHX_UNIT_SLIDER
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
@@ -113,6 +119,63 @@ def _contig(a, dtype):
     if a.dtype != dtype or not a.flags["C_CONTIGUOUS"]:
         raise TypeError("expected a C-contiguous array of dtype %s" % (dtype,))
     return a
+
+
+def _field(kind, value, box, disc, mask, force):
+    """One field_dtype row; the region is ALL unless `box` = (min.x, min.y, max.x, max.y) or `disc` = (c.x, c.y, r) is given."""
+    if box is not None and disc is not None:
+        raise ValueError("a field's region is a box or a disc, not both")
+    f = np.zeros((), dtype=field_dtype)
+    f["kind"], f["mask"], f["flags"] = kind, mask, FIELD_FORCE if force else 0
+    f["value"][:len(value)] = value
+    if box is not None:
+        f["shape"], f["region"] = REGION_BOX, box
+    elif disc is not None:
+        f["shape"] = REGION_DISC
+        f["region"][:3] = disc
+    return f
+
+
+def uniform_field(ax, ay, angular=0.0, box=None, disc=None, mask=0xFFFFFFFF, force=False):
+    """A wind, a current, a zero-gravity room (ay = -gravity): the same acceleration {ax, ay, angular} for every body in the region
+    (a force / torque with force=True: scaled by the body's inverse mass / inverse inertia)."""
+    return _field(FIELD_UNIFORM, (ax, ay, angular), box, disc, mask, force)
+
+
+def radial_field(cx, cy, strength, falloff_radius=0.0, box=None, disc=None, mask=0xFFFFFFFF, force=False):
+    """A magnet, a planet, a blast: `strength` along the direction from (cx, cy) to the body (negative: toward the centre), fading
+    linearly to nothing at falloff_radius where that is > 0."""
+    return _field(FIELD_RADIAL, (cx, cy, strength, falloff_radius), box, disc, mask, force)
+
+
+def drag_field(k_lin, k_ang=0.0, flow=(0.0, 0.0), box=None, disc=None, mask=0xFFFFFFFF, force=False):
+    """A water volume, a conveyor current: the velocity is drawn toward `flow` at rate k_lin per second and the angular velocity
+    toward 0 at k_ang, never past them in one step."""
+    return _field(FIELD_DRAG, (flow[0], flow[1], k_lin, k_ang), box, disc, mask, force)
+
+
+def _fields(fields, what):
+    """A list of field_dtype rows (or one array of them) as one contiguous field_dtype array."""
+    if isinstance(fields, np.ndarray):
+        a = fields.reshape(-1) if fields.dtype == field_dtype else None
+    else:
+        rows = list(fields)
+        a = np.zeros(len(rows), dtype=field_dtype)
+        for k, r in enumerate(rows):
+            r = np.asarray(r)
+            if r.dtype != field_dtype or r.size != 1:
+                a = None
+                break
+            a[k] = r.reshape(())
+    if a is None:
+        raise TypeError("%s: fields must be field_dtype rows (uniform_field, radial_field, drag_field)" % what)
+    return np.ascontiguousarray(a)
+
+
+def field_check(fields):
+    """phx_field_check: raises PhxError naming the first rule a field of the list breaks (no device needed)."""
+    f = _fields(fields, "field_check")
+    check(_lib.load().phx_field_check(_ptr(f), len(f)))
 
 
 def device_count():
@@ -1182,6 +1245,37 @@ class World:
         asleep, slept, woken = C.c_int32(0), C.c_int64(0), C.c_int64(0)
         check(self.L.phx_world_sleep_counts(self.h, C.byref(asleep), C.byref(slept), C.byref(woken)))
         return asleep.value, slept.value, woken.value
+
+    # ---- force fields (include/phyx_amd.h FORCE FIELDS; the specification: tests/field_spec.py) ----
+    def set_fields(self, fields):
+        """Replace the world's field list (rows of uniform_field / radial_field / drag_field, at most MAX_FIELDS; []: none).  From the
+        next Update on, every step first adds the fields' accelerations, in list order, to what IntegrateVelocity consumes."""
+        f = _fields(fields, "set_fields")
+        check(self.L.phx_world_set_fields(self.h, _ptr(f), len(f)))
+
+    def fields(self):
+        """The field list as a field_dtype array."""
+        n = C.c_int32(0)
+        out = np.zeros(MAX_FIELDS, dtype=field_dtype)
+        check(self.L.phx_world_get_fields(self.h, _ptr(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def pulse_fields(self, fields):
+        """One shot, between steps: velocity += what the listed fields would add in a step of dt = 1 (a blast: a radial_field with a
+        falloff radius).  Sleepers are not affected; wake_bodies(query_aabb(...)) first for a blast that wakes a pile."""
+        f = _fields(fields, "pulse_fields")
+        check(self.L.phx_world_pulse_fields(self.h, _ptr(f), len(f)))
+
+    def apply_impulses(self, bodies, impulses):
+        """The impulse (J.x, J.y) at the world point (point.x, point.y) on body bodies[k]: impulses is (K, 4) {J.x, J.y, point.x, point.y};
+        v += inv_mass J, w -= inv_inertia (r x J) with r = point - pos (the engine's angular velocity is clockwise-positive)."""
+        self._edit("phx_world_apply_impulses", bodies, impulses, 4, "apply_impulses")
+
+    def field_passes(self):
+        """How many field passes the steps have launched so far: one per step while the list is not empty, none otherwise."""
+        n = C.c_int64(0)
+        check(self.L.phx_world_field_passes(self.h, C.byref(n)))
+        return n.value
 
     # ---- the per-body columns: collision filters, materials, body flags ----
     @staticmethod

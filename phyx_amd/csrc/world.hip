@@ -16,6 +16,7 @@
 #include "contact.h"
 #include "snapshot.h"
 #include "pins.h"
+#include "fields.h"
 
 #include <algorithm>
 #include <chrono>
@@ -216,6 +217,13 @@ public:
     int wake_bodies(const int32_t* bodies, int count);
     int sleep_counts(int32_t* asleep, int64_t* slept_total, int64_t* woken_total);
     int set_gravity(float g);
+    // force fields (phx_world_set_fields ... phx_world_field_passes): between steps; the pass runs at the head of pre_solve (fields.h)
+    int set_fields(const phx_field* fields, int count);
+    int get_fields(phx_field* out, int cap, int32_t* count) const;
+    int pulse_fields(const phx_field* fields, int count);
+    int apply_impulses(const int* bodies, const float* impulses, int count);
+    long long field_passes() const { return fields_.passes(); }
+    int refuse_fields(const char* what) const;      // PHX_ERR_STATE while the field list is not empty (the sharded modes carry none)
     int refuse_pins(const char* what);         // PHX_ERR_STATE while a pin or a link exists (the sharded modes carry none)
     PinSet& pins() { return pins_; }
     int refuse_tables(const char* what);       // PHX_ERR_STATE if some body's value in an optional column is not the default (the sharded modes carry none)
@@ -359,6 +367,10 @@ private:
     template <class Column, class Rule>
     int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
     PinSet pins_;
+    DeviceFields fields_;
+    FieldBodies field_bodies() const { return FieldBodies{bodies_.mpos.p, bodies_.vel.p, filters_.ptr(), nb()}; }
+    int field_pass(float dt);            // queued in front of IntegrateVelocity; a world without fields queues nothing
+    bool accel_from_fields_ = false;     // accel_ holds this step's field sums alone: the records' accelerations are zero already
     int break_step_ = 0;                 // the steps taken since the break events were last taken: the next step's ordinal in them
     int settle_breaks();                 // between steps: what the last step's break test found is applied (PinSet::settle); at the top of every call that reads or changes units
     template <class P> int check_unit_indices(const char* what, const int32_t* which, const void* values, int count);
@@ -552,7 +564,7 @@ int World::update_pairs()                                                   // r
     fuse_velocity_ = false;
     if (accel_pending_) {                  // IntegrateVelocity of this step has consumed the uploaded accelerations (ref: World.cpp:50, 53)
         accel_pending_ = false;
-        if (nb()) hipLaunchKernelGGL(k_clear_accelerations, dim3(wgrid(nb())), dim3(256), 0, stream_, bodies_.records.p, nb());
+        if (nb() && !accel_from_fields_) hipLaunchKernelGGL(k_clear_accelerations, dim3(wgrid(nb())), dim3(256), 0, stream_, bodies_.records.p, nb());
         PHX_HIP(hipGetLastError());
     }
     const int fresh = broadphase_.new_pair_count();
@@ -757,6 +769,7 @@ int World::pre_solve(float dt)
         fuse_velocity_ = !phase_timing;
         step_dt_ = dt;
         records_stale_ = true;
+        PHX_TRY(field_pass(dt));
         if (nb() && !fuse_velocity_) hipLaunchKernelGGL(k_integrate_velocity, dim3(wgrid(nb())), dim3(256), 0, stream_, bodies_.vel.p, (const float4*)bodies_.mpos.p, nb(), gravity, dt, counters_.p, accel_pending_ ? (const float4*)accel_.p : nullptr);
         PHX_HIP(hipGetLastError());
         lap(0);
@@ -2016,6 +2029,93 @@ int World::set_gravity(float g)
     return PHX_OK;
 }
 
+// ---- force fields ---------------------------------------------------------------------------------------------------------------------
+// The rules and the arithmetic: include/phyx_amd.h FORCE FIELDS; the list, its device copy and the launches: fields.h.  The world's part
+// is the seam: the pass fills accel_, the dense pending accelerations the unchanged IntegrateVelocity consumes (fused into the
+// broadphase's first kernel or on its own under phase timing), so no kernel of the step knows about fields.
+int World::refuse_fields(const char* what) const
+{
+    if (!fields_.count()) return PHX_OK;
+    set_error("%s: the world holds force fields, which a sharded world does not carry (phx_world_set_fields(w, NULL, 0) first)", what);
+    return PHX_ERR_STATE;
+}
+
+int World::set_fields(const phx_field* fields, int count)
+{
+    static const char* const what = "phx_world_set_fields";
+    PHX_TRY(refuse_mid_step(what));
+    PHX_TRY(refuse_sharded(what, "force fields"));
+    PHX_TRY(phx_field_check(fields, count));
+    const int* unused = nullptr; const float* d_fields = nullptr;
+    if (count) {
+        PHX_TRY(use_device(device_));
+        PHX_TRY(stage_batch(nullptr, reinterpret_cast<const float*>(fields), count, (int)(sizeof(phx_field) / sizeof(float)), &unused, &d_fields));
+    }
+    return fields_.set(fields, count, reinterpret_cast<const phx_field*>(d_fields), stream_);
+}
+
+int World::get_fields(phx_field* out, int cap, int32_t* count) const
+{
+    const int n = fields_.count();
+    if (count) *count = n;
+    if (cap < n || (n && !out)) { set_error("phx_world_get_fields: room for %d fields, the world has %d", out ? cap : 0, n); return PHX_ERR_CAPACITY; }
+    if (n) std::memcpy(out, fields_.list().data(), (size_t)n * sizeof(phx_field));
+    return PHX_OK;
+}
+
+int World::field_pass(float dt)
+{
+    accel_from_fields_ = false;
+    if (!fields_.count() || !nb()) return PHX_OK;
+    // (pending accelerations fill accel_ for every body already; otherwise the kernel starts every slot from zero itself)
+    if (!accel_pending_) PHX_TRY(accel_.reserve((size_t)nb()));
+    PHX_TRY(fields_.apply(field_bodies(), accel_.p, accel_pending_, dt, stream_));
+    accel_from_fields_ = !accel_pending_;
+    accel_pending_ = true;
+    return PHX_OK;
+}
+
+int World::pulse_fields(const phx_field* fields, int count)
+{
+    static const char* const what = "phx_world_pulse_fields";
+    PHX_TRY(refuse_mid_step(what));
+    PHX_TRY(refuse_sharded(what, "force fields"));
+    PHX_TRY(phx_field_check(fields, count));
+    if (!count || !nb()) return PHX_OK;
+    PHX_TRY(settle_on_device());
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    const int* unused = nullptr; const float* d_fields = nullptr;
+    PHX_TRY(stage_batch(nullptr, reinterpret_cast<const float*>(fields), count, (int)(sizeof(phx_field) / sizeof(float)), &unused, &d_fields));
+    records_stale_ = true;
+    return DeviceFields::pulse(field_bodies(), reinterpret_cast<const phx_field*>(d_fields), count, field_traits(fields, count), stream_);
+}
+
+int World::apply_impulses(const int* bodies, const float* impulses, int count)
+{
+    static const char* const what = "phx_world_apply_impulses";
+    PHX_TRY(check_batch(what, bodies, impulses, count, true));
+    for (int k = 0; k < 4 * count; ++k)
+        if (!std::isfinite(impulses[k])) { set_error("%s: entry %d: value %d is not finite", what, k / 4, k % 4); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    PHX_TRY(wake_named(bodies, count));
+    if (host_staged()) {                                    // the host-staged records are the world: the kernel's statements on them
+        for (int k = 0; k < count; ++k) {
+            phx_rigid_body& b = host_bodies_[(size_t)bodies[k]];
+            if (!(b.inv_mass > 0.0f)) continue;
+            const float* q = impulses + 4 * (size_t)k;
+            const float rx = q[2] - b.pos.x, ry = q[3] - b.pos.y;
+            b.velocity.x = b.velocity.x + b.inv_mass * q[0]; b.velocity.y = b.velocity.y + b.inv_mass * q[1];
+            b.angular_velocity = b.angular_velocity - b.inv_inertia * (rx * q[1] - ry * q[0]);
+        }
+        return PHX_OK;
+    }
+    PHX_TRY(settle_on_device());
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_batch(bodies, impulses, count, 4, &d_bodies, &d_values));
+    records_stale_ = true;
+    return DeviceFields::impulses(field_bodies(), d_bodies, d_values, count, stream_);
+}
+
 // ---- queries ------------------------------------------------------------------------------------------------------------------------
 // Answered on the world's stream from the resident arrays (query.h / query_kernels.h).  The host forms check everything first, stage the
 // queries through the world's pinned staging and wait for their results; the device forms only queue.  Nothing of the world changes:
@@ -2261,6 +2361,7 @@ int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
     PHX_REQUIRE(count >= 1 && shard >= 0 && shard < count, "bad shard");
     if (count > 1) PHX_TRY(w->impl.refuse_pins("phx_world_set_shard"));
     if (count > 1) PHX_TRY(w->impl.refuse_tables("phx_world_set_shard"));
+    if (count > 1) PHX_TRY(w->impl.refuse_fields("phx_world_set_shard"));
     w->impl.shard = shard; w->impl.shard_count = count;
     PHX_TRY(w->impl.solver().set_shard(shard, count));
     return PHX_OK;
@@ -2303,6 +2404,7 @@ int phx_world_set_comm(phx_world* w, phx_comm* c)
     PHX_REQUIRE(w, "null handle");
     if (c) PHX_TRY(w->impl.refuse_pins("phx_world_set_comm"));
     if (c) PHX_TRY(w->impl.refuse_tables("phx_world_set_comm"));
+    if (c) PHX_TRY(w->impl.refuse_fields("phx_world_set_comm"));
     return w->impl.set_comm(c ? &c->impl : nullptr);
 }
 
@@ -2350,6 +2452,12 @@ int phx_world_set_poses(phx_world* w, const int32_t* bodies, const float* pose, 
     PHX_REQUIRE(w, "null handle");
     return w->impl.edit(phx::World::EDIT_POSES, bodies, pose, count);
 }
+
+int phx_world_set_fields(phx_world* w, const phx_field* fields, int32_t count) { PHX_REQUIRE(w, "null handle"); return w->impl.set_fields(fields, count); }
+int phx_world_get_fields(phx_world* w, phx_field* out, int32_t cap, int32_t* count) { PHX_REQUIRE(w, "null handle"); return w->impl.get_fields(out, cap, count); }
+int phx_world_pulse_fields(phx_world* w, const phx_field* fields, int32_t count) { PHX_REQUIRE(w, "null handle"); return w->impl.pulse_fields(fields, count); }
+int phx_world_apply_impulses(phx_world* w, const int32_t* bodies, const float* impulses, int32_t count) { PHX_REQUIRE(w, "null handle"); return w->impl.apply_impulses(bodies, impulses, count); }
+int phx_world_field_passes(phx_world* w, int64_t* passes) { PHX_REQUIRE(w && passes, "null handle / output"); *passes = w->impl.field_passes(); return PHX_OK; }
 
 int phx_world_get_body_states(phx_world* w, const int32_t* bodies, int32_t count, phx_rigid_body* out)
 {
