@@ -506,6 +506,50 @@ typedef struct { uint32_t category, mask; int32_t group; } phx_collision_filter;
 int  phx_world_set_collision_filters(phx_world* w, const int32_t* bodies, const phx_collision_filter* filters, int32_t count, int32_t* dropped);
 /* every body's filter, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
 int  phx_world_get_collision_filters(phx_world* w, phx_collision_filter* out, int32_t cap);
+/* COLLISION EXCLUSIONS — body pairs that never collide.  The world owns a set of unordered body pairs {a, b}, a != b: a setting, like
+ * the filter column.  It says what the filters cannot: a chain's link i passes through links i - 1 and i + 1, which it overlaps at
+ * the hinge, and still collides with every other link (a shared negative group is transitive, a chain's neighbour relation is not).
+ * A world whose set is empty allocates and launches exactly what it did before there were exclusions.
+ *   - Rule: a pair in the set is not emitted by UpdatePairs (ref: Collider.cpp:296-366).  It never enters the broadphase's pair set,
+ *     never gets a manifold, contact points or joints, and the contact reports never see it.
+ *   - Where it acts: inside the sweep, behind the collision filter and in front of the pair-set lookup.  phx_broadphase_stats keeps
+ *     its meaning: candidate_tests and overlapping_pairs count before both tests, new_pairs what was emitted.  The drop-in
+ *     phx_broadphase_* handles know no exclusions.
+ *   - The set: a pair is stored as {lo, hi} = {min(a, b), max(a, b)}.  add is set union (a pair already present changes nothing),
+ *     remove set difference (an absent pair is ignored), clear empties the set.  get writes the pairs ascending by (lo, hi), two
+ *     int32 per pair; it always fills *count (may be NULL) and returns PHX_ERR_CAPACITY if cap (in pairs) is smaller.
+ *   - Checks: the rules of the edits above.  Between steps only (PHX_ERR_STATE); checked completely before anything is queued
+ *     (count >= 0, no NULL array when count > 0, both indices of every pair in [0, body count), a != b, no pair twice in one call —
+ *     (a, b) and (b, a) are the same pair; PHX_ERR_INVALID otherwise, phx_last_error names the first failure, the world unchanged).
+ *     An empty call is a true no-op.  A sharded or communicator-attached world gets PHX_ERR_STATE.  Before the first step the set
+ *     waits on the host with the host-staged bodies, as pins do.
+ *   - Pairs that exist already: add drops the manifolds whose pair is now excluded, and the result is exactly what
+ *     phx_world_set_state would make of drop(state): bodies unchanged; the remaining manifolds in their old order with point_index =
+ *     2 * the new index; their contact-point slots move with them, a live slot's solver_index following its joint (-1 if the joint
+ *     goes); the joints of dropped manifolds go, the others keep their order with contact_point_index = 2 * (the manifold's new index)
+ *     + old % 2; the broadphase's pair set becomes the kept manifolds' pairs and the cached solver schedule is rebuilt at the next step.
+ *     (The compaction COLLISION FILTERS describes, with "the pair is not in the set" as its keep rule.)  *dropped (may be NULL) receives
+ *     the number of manifolds dropped.  When none is, the call changes no topology: the cached schedule stays valid
+ *     (phx_solve_stats.recoloured == 0 on the next step).  Dropped pairs leave the touching set, so the next phx_world_contact_events
+ *     reports them under end.
+ *   - remove and clear touch no manifold: a pair that overlaps is simply new to the next step's UpdatePairs, which gives it a fresh
+ *     manifold (the last ones of that step) and joints with zero warm start.
+ *   - The other calls: add_body / add_bodies leave the set alone (new bodies are in no pair); remove_bodies / remove_outside drop
+ *     every pair that has a removed body and renumber the rest through new[] (increasing on kept bodies: lo < hi and the order both
+ *     survive); phx_world_set_state empties the set, as it resets the filters; phx_world_save / load and so a fork carry the set in
+ *     HBM beside the blob's layout, as they carry pins; phx_snapshot_export and phx_snapshot_blob_bytes of a snapshot that holds
+ *     exclusions return PHX_ERR_STATE (the blob stays layout version 1).  With sleeping enabled add and remove first wake the sleeping
+ *     components of the bodies they name, clear those of every pair it removes.  Queries see every body.  Sleeping's edges are manifolds
+ *     and units: an excluded pair joined by a pin is still an edge through the pin.
+ *   - Sharded worlds carry no exclusions: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and
+ *     phx_world_reslab return PHX_ERR_STATE while the set is not empty.
+ * The host keeps the sorted list; the device a hash table of the keys (lo << 32 | hi, at most half full) and one word per body that
+ * says whether the body is in any pair: the sweep row of any other body makes no probe.  O(pairs) bytes cross PCIe when the set or
+ * the body numbering changes, nothing per step.  Costs and the data path: DESIGN.md. */
+int  phx_world_add_collision_exclusions(phx_world* w, const int32_t* pairs /* 2 per pair */, int32_t count, int32_t* dropped);
+int  phx_world_remove_collision_exclusions(phx_world* w, const int32_t* pairs, int32_t count);
+int  phx_world_clear_collision_exclusions(phx_world* w);
+int  phx_world_get_collision_exclusions(phx_world* w, int32_t* out /* 2 per pair */, int32_t cap /* pairs */, int32_t* count);
 /* MATERIALS — per-body friction and restitution.  Every body has a material {friction, restitution}; the default {0.3f, 0.0f} is the
  * reference's kFrictionCoefficient (ref: Solver.cpp:9) and bounce (ref: Solver.cpp:658), and a world whose materials are all the default
  * steps bit for bit as one that never heard of materials.
@@ -819,7 +863,7 @@ int  phx_snapshot_blob_pack(const phx_rigid_body* bodies, int32_t body_count, co
  *     n = phx_world_set_pin_iterations (1 .. 64, default 8), a setting of the world like gravity.  There is no cap on the bias: a pin
  *     whose anchor is moved far in one step pulls hard.  The bias is part of the accumulated impulse, hence of the next step's warm start:
  *     a chain whose tension the n sweeps do not carry from end to end within a step oscillates, and the oscillation grows (the spec's
- *     hanging chain of 16 links diverges at n = 8 and rests at n = 32: tests/pin_spec.py) - give long chains more sweeps.  Pins do not stop their two bodies from colliding: collision filters do that.
+ *     hanging chain of 16 links diverges at n = 8 and rests at n = 32: tests/pin_spec.py) - give long chains more sweeps.  Pins do not stop their two bodies from colliding: collision exclusions (COLLISION EXCLUSIONS) or filters do that.
  *   - Order is semantics: prestep and warm start in the slot order of the pin schedule, then n sweeps in slot order.  The schedule
  *     (phx_world_get_pin_schedule, host-only twin phx_pin_schedule) is phx_schedule_groups' with one pin per unit, the world anchor as one
  *     virtual static body (index body_count) and at most `group_pins` pins per group (256; PHX_PIN_GROUP_PINS=n, 1 .. 256, read when a

@@ -173,6 +173,10 @@ _SIGNATURES = {
     "phx_world_set_inverse_masses": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_set_collision_filters": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(_i32)]),
     "phx_world_get_collision_filters": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_add_collision_exclusions": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
+    "phx_world_remove_collision_exclusions": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_clear_collision_exclusions": (C.c_int, [_vp]),
+    "phx_world_get_collision_exclusions": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
     "phx_world_set_materials": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_get_materials": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_set_body_flags": (C.c_int, [_vp, _vp, _vp, _i32]),

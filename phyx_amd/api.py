@@ -1309,6 +1309,64 @@ class World:
         """Every body's filter, in index order: an array of collision_filter_dtype."""
         return self._get(self.L.phx_world_get_collision_filters, collision_filter_dtype, self.counts()[0])
 
+    # ---- collision exclusions (include/phyx_amd.h COLLISION EXCLUSIONS; the specification: tests/exclusion_spec.py) ----
+    @staticmethod
+    def _pairs(pairs, what):
+        p = np.asarray(pairs)
+        if p.size == 0:
+            return np.zeros((0, 2), dtype=np.int32)
+        if p.dtype.kind not in "iu":
+            raise TypeError("%s: the pairs must be integers, got %s" % (what, p.dtype))
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError("%s: the pairs must have shape (n, 2), got %s" % (what, p.shape))
+        if int(p.min()) < -2 ** 31 or int(p.max()) > 2 ** 31 - 1:
+            raise ValueError("%s: a body index is outside the int32 range" % what)
+        return np.ascontiguousarray(p, dtype=np.int32)
+
+    def add_collision_exclusions(self, pairs):
+        """The body pairs (a, b) of `pairs`, shape (n, 2), never collide from now on: set union with the world's exclusion set (a != b;
+        (a, b) and (b, a) are one pair, at most once per call).  Manifolds of pairs that are now excluded are dropped as set_state of
+        exclusion_spec.drop(state(), pairs) would; returns how many were."""
+        p = self._pairs(pairs, "add_collision_exclusions")
+        dropped = C.c_int32(0)
+        check(self.L.phx_world_add_collision_exclusions(self.h, _ptr(p), len(p), C.byref(dropped)))
+        return dropped.value
+
+    def remove_collision_exclusions(self, pairs):
+        """Set difference: the listed pairs may collide again (absent ones are ignored).  No manifold changes; a pair that overlaps is
+        new to the next step."""
+        p = self._pairs(pairs, "remove_collision_exclusions")
+        check(self.L.phx_world_remove_collision_exclusions(self.h, _ptr(p), len(p)))
+
+    def clear_collision_exclusions(self):
+        """Empty the exclusion set."""
+        check(self.L.phx_world_clear_collision_exclusions(self.h))
+
+    def collision_exclusions(self):
+        """The exclusion set: an (n, 2) int32 array of {lo, hi} pairs, ascending by (lo, hi)."""
+        n = C.c_int32(0)
+        st = self.L.phx_world_get_collision_exclusions(self.h, None, 0, C.byref(n))
+        if st != _lib.PHX_ERR_CAPACITY:
+            check(st)
+        out = np.zeros((n.value, 2), dtype=np.int32)
+        check(self.L.phx_world_get_collision_exclusions(self.h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def exclude_joined(self, kinds=None):
+        """collideConnected = false: exclude the body pair of every current unit of `kinds` (any of "pin", "link", "angle", "slider" or
+        0..3; None: all four) that joins two bodies (body2 >= 0).  Units added later are not covered.  Returns what
+        add_collision_exclusions returns."""
+        chosen = range(len(UNIT_KINDS)) if kinds is None else [self._unit_kind(k, "exclude_joined") for k in kinds]
+        pairs = set()
+        for k in chosen:
+            if not 0 <= k < len(UNIT_KINDS):
+                raise ValueError("exclude_joined: kind %r is none of %s" % (k, ", ".join(UNIT_KINDS)))
+            units = getattr(self, UNIT_KINDS[k] + "s")()
+            for a, b in zip(units["body1"].tolist(), units["body2"].tolist()):
+                if b >= 0 and a != b:
+                    pairs.add((min(a, b), max(a, b)))
+        return self.add_collision_exclusions(np.array(sorted(pairs), dtype=np.int32).reshape(-1, 2))
+
     # ---- materials (include/phyx_amd.h MATERIALS; the specification: tests/material_spec.py) ----
     def set_materials(self, bodies, friction=0.3, restitution=0.0):
         """Give the listed bodies (each at most once) the material {friction, restitution}: each a scalar for all of them or one value per

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "common.h"
+#include "exclusions.h"
 
 namespace phx {
 
@@ -20,8 +21,10 @@ public:
     // `carrier` (may be null): the kernel `while_waiting` would queue takes the round trip's post along (Readback::wait)
     // `filters` (may be null; World only): one {category, mask, group, 0} record per body — pairs that fail the collision filter
     // (common.h collision_filter_pass) are not emitted; null sweeps with the unfiltered kernels
+    // `exclusions` (may be null; World only): the excluded body pairs (exclusions.h) — they are not emitted either; null sweeps with
+    // the kernels that know of none
     int update_resident(const float4* d_aabb, int n, const StepPrologue* prologue = nullptr, const std::function<int()>* while_waiting = nullptr,
-                        const MailCarrier* carrier = nullptr, const uint4* filters = nullptr);
+                        const MailCarrier* carrier = nullptr, const uint4* filters = nullptr, const ExclusionView* exclusions = nullptr);
     // the C-ABI edge: 128-byte records (their AABBs are extracted into a scratch array first)
     int update_device(const phx_rigid_body* d_bodies, int n);
     int update_host(const phx_rigid_body* bodies, int n, uint32_t* new_pairs, int cap, int* count);
@@ -75,5 +78,8 @@ private:
 public:
     void set_wait_timeout(double seconds) { rb_.set_timeout(seconds); }      // (a sharded World: the stream carries collectives, common.h Readback)
 };
+
+// a pair table (pair_set.h) of `cap` slots (a power of two) := the `n` distinct pairs of d_pairs, key (x << 32) | y; queued on `stream`
+int pair_table_fill(unsigned long long* table, unsigned cap, const uint2* d_pairs, int n, hipStream_t stream);
 
 } // namespace phx

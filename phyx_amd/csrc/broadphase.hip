@@ -18,6 +18,7 @@
 #include "device_scan.h"
 #include "device_radix.h"
 #include "splitter_sort.h"
+#include "pair_set.h"
 
 #include <algorithm>
 
@@ -82,27 +83,7 @@ __global__ void __launch_bounds__(256) k_gather_entries(const float4* __restrict
     }
 }
 
-// ---- persistent pair set ------------------------------------------------------------------------------
-constexpr unsigned long long PS_EMPTY = 0xFFFFFFFFFFFFFFFFull;
-constexpr unsigned long long PS_TOMB = 0xFFFFFFFFFFFFFFFEull;
-
-__device__ __forceinline__ unsigned ps_hash(unsigned long long k)
-{
-    // same mixing idea as the reference's pair hash (ref: Collider.h:10-18), finished with a multiply
-    const unsigned lb = (unsigned)(k >> 32), rb = (unsigned)k;
-    return (lb ^ (rb + 0x9e3779b9u + (lb << 6) + (lb >> 2))) * 0x9E3779B1u;
-}
-
-__device__ __forceinline__ bool ps_contains(const unsigned long long* __restrict__ table, unsigned mask, unsigned long long k)
-{
-    unsigned p = ps_hash(k) & mask;
-    for (;;) {
-        const unsigned long long s = table[p];
-        if (s == k) return true;
-        if (s == PS_EMPTY) return false;
-        p = (p + 1) & mask;
-    }
-}
+// ---- persistent pair set (the table as the device reads it — PS_EMPTY, ps_hash, ps_contains: pair_set.h) ----------------------
 
 // keys are distinct and known to be absent
 __global__ void __launch_bounds__(256) k_ps_insert(unsigned long long* table, unsigned mask, const uint2* __restrict__ pairs, int n, unsigned long long* __restrict__ end_stamp)
@@ -194,6 +175,34 @@ template <class V> __device__ __forceinline__ uint4 sweep_filter_of(const V& v, 
     else return make_uint4(0u, 0u, 0u, 0u);
 }
 
+// A World with collision exclusions (exclusions.h) sweeps with one of these two views: the second trait of the same kernels.  The test
+// stands behind the collision filter and in front of the pair-set lookup.  A row reads its body's word once, where it reads its filter:
+// a body in no excluded pair makes no probe at all.  Any other row probes the exclusions' table once per y-overlapping candidate that
+// passed the filter — the key is of the UNORDERED pair (ps_unordered_key: ia, ib come in sorted-row order, not index order) — and the
+// probe's first load is issued with the pair-set lookups', so that the row's SWEEP_LOOK loads stay in flight together.  A rejected
+// candidate is what a filtered one is: not new, not cached, not emitted, its overlap counted.  The count pass, the rescan and the
+// chunk kernels apply the same test, or the offsets would lie.
+struct ExcludedSweepView : SweepView {
+    ExclusionView excl;
+};
+struct FilteredExcludedSweepView : FilteredSweepView {
+    ExclusionView excl;
+};
+template <> struct SweepFilter<FilteredExcludedSweepView> { static constexpr bool on = true; };
+template <class V> struct SweepExclude { static constexpr bool on = false; };
+template <> struct SweepExclude<ExcludedSweepView> { static constexpr bool on = true; };
+template <> struct SweepExclude<FilteredExcludedSweepView> { static constexpr bool on = true; };
+template <class V> __device__ __forceinline__ unsigned sweep_member_of(const V& v, unsigned body)       // the row's word: in some excluded pair?
+{
+    if constexpr (SweepExclude<V>::on) return v.excl.member[body];
+    else return 0u;
+}
+template <class V> __device__ __forceinline__ bool sweep_excluded(const V& v, unsigned ia, unsigned ib)
+{
+    if constexpr (SweepExclude<V>::on) return ps_contains(v.excl.table, v.excl.mask, ps_unordered_key(ia, ib));
+    else return false;
+}
+
 constexpr int SWEEP_CAND = 16;       // y-overlapping candidates a row can hold before it must look them up in the pair set
 constexpr int SWEEP_LOOK = 8;        // lookups a row keeps in flight
 constexpr int SWEEP_GROUP = 8;       // candidates the wave reads from its staged block per step of its walk
@@ -267,6 +276,7 @@ __global__ void __launch_bounds__(256) k_sweep_rows(V v, const unsigned* __restr
         }
         const unsigned ia = scanning ? v.idx[i] : 0u;
         const uint4 fa = scanning ? sweep_filter_of(v, ia) : make_uint4(0u, 0u, 0u, 0u);      // (the row's filter: once per row)
+        const unsigned xa = scanning ? sweep_member_of(v, ia) : 0u;                           // (the row's exclusion word: once per row)
         unsigned found = 0;
         // The candidates that overlap in y are only COLLECTED by the scan (their positions, in j order, in LDS); the pair-set
         // lookups — two dependent memory round trips each — are made afterwards, all in flight together.  Done inside the scan
@@ -285,12 +295,28 @@ __global__ void __launch_bounds__(256) k_sweep_rows(V v, const unsigned* __restr
                     for (int k = 0; k < SWEEP_LOOK; ++k)
                         if (h + k < ncand && collision_filter_pass(fa, sweep_filter_of(v, ib[k]))) pass |= 1u << k;
                 }
+                // (the exclusion probes' home slots are loaded here, in front of the pair-set lookups' and in flight with them, and looked
+                //  at behind them; a row of a body in no excluded pair — xa == 0 — loads none)
+                unsigned long long xfirst[SWEEP_LOOK];
+                if constexpr (SweepExclude<V>::on) {
+#pragma unroll
+                    for (int k = 0; k < SWEEP_LOOK; ++k)
+                        xfirst[k] = xa && h + k < ncand && ((pass >> k) & 1u) ? v.excl.table[ps_hash(ps_unordered_key(ia, ib[k])) & v.excl.mask] : PS_EMPTY;
+                }
 #pragma unroll
                 for (int k = 0; k < SWEEP_LOOK; ++k) first[k] = h + k < ncand && ((pass >> k) & 1u) ? v.table[ps_hash(((unsigned long long)ia << 32) | ib[k]) & v.mask] : 0ull;
+                if constexpr (SweepExclude<V>::on) {
+#pragma unroll
+                    for (int k = 0; k < SWEEP_LOOK; ++k) {
+                        if (xfirst[k] == PS_EMPTY) continue;       // nothing at the home slot, or no probe: not excluded
+                        const unsigned long long xkey = ps_unordered_key(ia, ib[k]);
+                        if (xfirst[k] == xkey || ps_contains(v.excl.table, v.excl.mask, xkey)) pass &= ~(1u << k);      // excluded: what a filtered candidate is
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < SWEEP_LOOK; ++k) {
                     if (h + k >= ncand) break;
-                    if (!((pass >> k) & 1u)) continue;             // rejected by the filter: no lookup, not new
+                    if (!((pass >> k) & 1u)) continue;             // rejected by the filter (or excluded): no lookup, not new
                     const unsigned long long key = ((unsigned long long)ia << 32) | ib[k];
                     bool present = first[k] == key;
                     if (!present && first[k] != PS_EMPTY) present = ps_contains(v.table, v.mask, key);       // a collision at the home slot: walk on
@@ -398,6 +424,7 @@ __device__ __forceinline__ void sweep_chunks(const V& v, const unsigned* __restr
         const float4 a = v.entries[ch.x];
         const unsigned ia = v.idx[ch.x];
         const uint4 fa = sweep_filter_of(v, ia);
+        const unsigned xa = sweep_member_of(v, ia);
         unsigned long long overlaps = 0;
         if constexpr (!EMIT) {
             // the count pass only wants the chunk's number of new pairs: every lane counts its own candidates over all tiles (their
@@ -409,6 +436,7 @@ __device__ __forceinline__ void sweep_chunks(const V& v, const unsigned* __restr
                     ++overlaps;
                     const unsigned ib = v.idx[j];
                     if (SweepFilter<V>::on && !collision_filter_pass(fa, sweep_filter_of(v, ib))) continue;
+                    if (SweepExclude<V>::on && xa && sweep_excluded(v, ia, ib)) continue;
                     if (!ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | ib)) ++mine;
                 }
             }
@@ -431,7 +459,8 @@ __device__ __forceinline__ void sweep_chunks(const V& v, const unsigned* __restr
                 if (fabsf(b.z - a.z) <= a.w + b.w) {
                     ib = v.idx[j];
                     ++overlaps;
-                    hit = (!SweepFilter<V>::on || collision_filter_pass(fa, sweep_filter_of(v, ib))) && !ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | ib);
+                    hit = (!SweepFilter<V>::on || collision_filter_pass(fa, sweep_filter_of(v, ib))) && !(SweepExclude<V>::on && xa && sweep_excluded(v, ia, ib)) &&
+                          !ps_contains(v.table, v.mask, ((unsigned long long)ia << 32) | ib);
                 }
             }
             const unsigned long long bal = __ballot(hit);
@@ -574,7 +603,7 @@ int DeviceBroadphase::update_device(const phx_rigid_body* d_bodies, int n)
 }
 
 int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepPrologue* prologue, const std::function<int()>* while_waiting, const MailCarrier* carrier,
-                                      const uint4* filters)
+                                      const uint4* filters, const ExclusionView* exclusions)
 {
     PHX_TRY(use_device(device_));
     PHX_REQUIRE(n >= 0 && (n == 0 || d_bodies), "bad body array");
@@ -660,17 +689,21 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
     v.counters = small_.p + 16;
     unsigned long long host_small[16 + 2 * STAT_SLOTS] = {0};      // [2] chunks needed, [3] new pairs, [16..] statistics slots
     int chunk_grid = 1;
+    // the sweep's four instantiations: plain, filtered, excluded, both — `f` gets `v` as the view the world's settings pick
+    const auto with_view = [&](auto f) {
+        if (filters && exclusions) f(FilteredExcludedSweepView{{v, filters}, *exclusions});
+        else if (filters) f(FilteredSweepView{v, filters});
+        else if (exclusions) f(ExcludedSweepView{v, *exclusions});
+        else f(v);
+    };
     for (int attempt = 0;; ++attempt) {
         v.chunks = chunks_.p; v.chunk_count = chunk_count_.p; v.chunk_cap = chunk_cap;
         chunk_grid = std::min(chunk_cap, 2048);
-        if (filters) {
-            const FilteredSweepView fv{v, filters};
-            hipLaunchKernelGGL((k_sweep_rows<false, FilteredSweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, fv, (const unsigned*)nullptr, (uint2*)nullptr, 0u);
-            hipLaunchKernelGGL((k_sweep_chunks_count<FilteredSweepView>), dim3(chunk_grid), dim3(256), 0, stream_, fv);
-        } else {
-            hipLaunchKernelGGL((k_sweep_rows<false, SweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, v, (const unsigned*)nullptr, (uint2*)nullptr, 0u);
-            hipLaunchKernelGGL((k_sweep_chunks_count<SweepView>), dim3(chunk_grid), dim3(256), 0, stream_, v);
-        }
+        with_view([&](const auto& sv) {
+            using V = std::decay_t<decltype(sv)>;
+            hipLaunchKernelGGL((k_sweep_rows<false, V>), dim3(grid_for(n)), dim3(256), 0, stream_, sv, (const unsigned*)nullptr, (uint2*)nullptr, 0u);
+            hipLaunchKernelGGL((k_sweep_chunks_count<V>), dim3(chunk_grid), dim3(256), 0, stream_, sv);
+        });
         // chunk counts -> per-row bases and the hub rows' totals (one small workgroup)
         PHX_TRY(chunk_scan_.reserve(chunk_cap + 1));
         hipLaunchKernelGGL(k_chunk_bases, dim3(1), dim3(1024), 0, stream_, v, chunk_scan_.p);
@@ -708,12 +741,14 @@ int DeviceBroadphase::update_resident(const float4* d_bodies, int n, const StepP
         v.table = table_.p; v.mask = table_cap_ - 1;
         {
             const int row_blocks = grid_for(n), chunk_blocks = (host_small[2] & 0xFFFFFFFFull) ? std::min((int)(host_small[2] & 0xFFFFFFFFull), chunk_grid) : 0;
-            if (filters) hipLaunchKernelGGL((k_emit_pairs<FilteredSweepView>), dim3(row_blocks + chunk_blocks), dim3(256), 0, stream_, FilteredSweepView{v, filters}, (const unsigned*)row_count_.p, new_pairs_.p, total, row_blocks);
-            else hipLaunchKernelGGL((k_emit_pairs<SweepView>), dim3(row_blocks + chunk_blocks), dim3(256), 0, stream_, v, (const unsigned*)row_count_.p, new_pairs_.p, total, row_blocks);
+            with_view([&](const auto& sv) {
+                hipLaunchKernelGGL((k_emit_pairs<std::decay_t<decltype(sv)>>), dim3(row_blocks + chunk_blocks), dim3(256), 0, stream_, sv, (const unsigned*)row_count_.p, new_pairs_.p, total, row_blocks);
+            });
         }
-        if (host_small[4] & 0xFFFFFFFFull) {    // some row found more than ROW_CACHE new pairs: those rows are rescanned (with the count pass's filter)
-            if (filters) hipLaunchKernelGGL((k_sweep_rows<true, FilteredSweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, FilteredSweepView{v, filters}, (const unsigned*)row_count_.p, new_pairs_.p, total);
-            else hipLaunchKernelGGL((k_sweep_rows<true, SweepView>), dim3(grid_for(n)), dim3(256), 0, stream_, v, (const unsigned*)row_count_.p, new_pairs_.p, total);
+        if (host_small[4] & 0xFFFFFFFFull) {    // some row found more than ROW_CACHE new pairs: those rows are rescanned (with the count pass's filter and exclusions)
+            with_view([&](const auto& sv) {
+                hipLaunchKernelGGL((k_sweep_rows<true, std::decay_t<decltype(sv)>>), dim3(grid_for(n)), dim3(256), 0, stream_, sv, (const unsigned*)row_count_.p, new_pairs_.p, total);
+            });
         }
         // ref: Collider.cpp:313 / :341 — the emitted pairs join the persistent set
         hipLaunchKernelGGL(k_ps_insert, dim3(grid_for((int)total)), dim3(256), 0, stream_, table_.p, table_cap_ - 1, (const uint2*)new_pairs_.p, (int)total, stamps_.p + 1);
@@ -816,6 +851,15 @@ int DeviceBroadphase::reset_pairs_device(const uint2* d_pairs, int count)
     PHX_HIP(hipGetLastError());
     set_size_ = count;
     stats_.set_size = count;
+    return PHX_OK;
+}
+
+int pair_table_fill(unsigned long long* table, unsigned cap, const uint2* d_pairs, int n, hipStream_t stream)
+{
+    PHX_REQUIRE(table && cap && !(cap & (cap - 1u)) && n >= 0 && (unsigned)n <= cap / 2u, "bad pair table");
+    PHX_HIP(hipMemsetAsync(table, 0xFF, (size_t)cap * sizeof(unsigned long long), stream));
+    if (n) hipLaunchKernelGGL(k_ps_insert, dim3(grid_for(n)), dim3(256), 0, stream, table, cap - 1u, d_pairs, n, (unsigned long long*)nullptr);
+    PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
 

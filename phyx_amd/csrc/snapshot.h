@@ -61,6 +61,18 @@ public:
     template <class P> const P* units() const { return std::get<Riders<P>>(riders_).buf.p; }
     template <class P> const float* unit_limits() const { const Riders<P>& r = std::get<Riders<P>>(riders_); return r.limited ? r.limits.p : nullptr; }
     template <class P> int unit_count() const { return std::get<Riders<P>>(riders_).count; }
+    // the collision exclusions (COLLISION EXCLUSIONS) ride the same way: the sorted {lo, hi} list as the world's device side holds it
+    int reserve_exclusions(int n, hipStream_t stream) { return n ? exclusions_.reserve_keep((size_t)n, (size_t)exclusion_count_, stream) : PHX_OK; }
+    int save_exclusions(const uint2* d_src, int count, hipStream_t stream)
+    {
+        exclusion_count_ = count;
+        if (!count) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(exclusions_.p, d_src, (size_t)count * sizeof(uint2), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
+        return PHX_OK;
+    }
+    const uint2* exclusions() const { return exclusions_.p; }
+    int exclusion_count() const { return exclusion_count_; }
     int blob_bytes(size_t* bytes) const;
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
@@ -68,7 +80,7 @@ public:
 private:
     int settle();                        // the host waits for the queued save and loads (export, import, destroy)
     int refuse_empty(const char* what) const;
-    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins, no links, no angles and no sliders
+    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins, no links, no angles, no sliders and no exclusions
     template <class P> struct Riders {            // a list of records beside the blob
         using record = P;
         DevBuf<P> buf; int count = 0;
@@ -81,6 +93,7 @@ private:
     };
     std::tuple<Riders<phx_pin>, Riders<phx_link>, Riders<phx_angle>, Riders<phx_slider>> riders_;      // (the kinds in the pass's order)
     template <class P> Riders<P>& riders() { return std::get<Riders<P>>(riders_); }
+    DevBuf<uint2> exclusions_; int exclusion_count_ = 0;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

@@ -50,6 +50,7 @@ int Snapshot::refuse_pins(const char* what) const
     const char* plural = nullptr;
     auto look = [&](const auto& r) { if (!count && r.count) { count = r.count; plural = UnitKind<typename std::decay_t<decltype(r)>::record>::plural; } };
     std::apply([&](const auto&... r) { (look(r), ...); }, riders_);
+    if (!count && exclusion_count_) { count = exclusion_count_; plural = "collision exclusions"; }
     if (!count) return PHX_OK;
     set_error("%s: the snapshot holds %d %s, which the blob (layout version 1) does not carry", what, count, plural);
     return PHX_ERR_STATE;
@@ -153,6 +154,7 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     if (rest) PHX_HIP(hipMemcpy(buf_.p, static_cast<const unsigned char*>(blob) + SNAP_HEADER_BYTES, rest, hipMemcpyHostToDevice));
     counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true;
     std::apply([](auto&... r) { ((r.count = 0), ...); }, riders_);
+    exclusion_count_ = 0;
     return PHX_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "snapshot.h"
 #include "pins.h"
 #include "fields.h"
+#include "exclusions.h"
 
 #include <algorithm>
 #include <chrono>
@@ -187,6 +188,13 @@ public:
     // their manifolds as set_state of the dropped state would
     int set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped);
     int get_collision_filters(phx_collision_filter* out, int cap);
+    // collision exclusions (phx_world_add_collision_exclusions ... get_collision_exclusions): between steps; an add drops the manifolds
+    // of the pairs it excludes as a change of filters would
+    int add_collision_exclusions(const int32_t* pairs, int count, int* dropped);
+    int remove_collision_exclusions(const int32_t* pairs, int count);
+    int clear_collision_exclusions();
+    int get_collision_exclusions(int32_t* out, int cap, int32_t* count) const;
+    int refuse_exclusions(const char* what) const;      // PHX_ERR_STATE while the set is not empty (the sharded modes carry none)
     // materials (phx_world_set_materials / get_materials): between steps; they change no topology
     int set_materials(const int32_t* bodies, const phx_material* materials, int count);
     int get_materials(phx_material* out, int cap);
@@ -347,6 +355,9 @@ private:
     // picks the solver's material kernels (DeviceSolver::set_materials) — and body flags — an active table picks the sensor variants of
     // the joint match and takes the schedule rebuild's components from the joints (refresh_contact_joints, pre_solve)
     BodyTable<FilterColumn> filters_;
+    // the collision exclusions (exclusions.h): a set that is not empty picks the excluded sweep
+    ExclusionSet exclusions_;
+    int check_exclusion_pairs(const char* what, const int32_t* pairs, int count, std::vector<unsigned long long>* keys);
     BodyTable<MaterialColumn> materials_;
     BodyTable<FlagsColumn> flags_col_;
     // ... and the sleep states (sleep.h): active exactly while sleeping is enabled
@@ -558,9 +569,10 @@ int World::update_pairs()                                                   // r
     };
     // (that launch also CARRIES the post of the new-pair count: its first workgroup posts before it updates — a dispatch fewer per step)
     const MailCarrier old_manifolds_with = [&](const MailRide* ride) -> int { old_ride_ = ride; const int st = old_manifolds(); old_ride_ = nullptr; return st; };
+    PHX_TRY(exclusions_.sync(nb(), stream_));                               // (nothing unless the set or the body count changed since the last step)
     PHX_TRY(broadphase_.update_resident(bodies_.aabb.p, nb(), fuse_velocity_ ? &prologue : nullptr, phase_timing ? nullptr : &old_manifolds,
                                         phase_timing || !nm ? nullptr : &old_manifolds_with,      // same stream; returns once the new-pair count is known
-                                        filters_.ptr()));
+                                        filters_.ptr(), exclusions_.view()));
     fuse_velocity_ = false;
     if (accel_pending_) {                  // IntegrateVelocity of this step has consumed the uploaded accelerations (ref: World.cpp:50, 53)
         accel_pending_ = false;
@@ -1020,6 +1032,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
     pins_.clear();                                                          // ... and no pin or link is left, no break limit and no break event
+    exclusions_.clear();                                                    // ... and no pair is excluded
     break_step_ = 0;
     if (sleep_.on()) {                                                      // sleeping stays enabled: nobody asleep, the totals 0
         sleep_col_.host.assign((size_t)body_count, SleepColumn::initial());
@@ -1098,9 +1111,12 @@ int World::save(Snapshot& s)
     v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
     PHX_TRY(pins_.upload(stream_));
+    PHX_TRY(exclusions_.sync(nb(), stream_));
     PHX_TRY(pins_.each_list([&](auto& l) { return s.reserve_units<typename std::decay_t<decltype(l)>::record>(l.count(), l.limited(), stream_); }));
+    PHX_TRY(s.reserve_exclusions(exclusions_.count(), stream_));
     PHX_TRY(s.save(v, stream_));
-    return pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); });
+    PHX_TRY(pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); }));
+    return s.save_exclusions(exclusions_.device_pairs(), exclusions_.count(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -1139,10 +1155,11 @@ int World::load(Snapshot& s)
     PHX_TRY(forget_step_history());
     pins_.drop_breaks();                                                    // (the abandoned timeline's unsettled breaks and its events go with it)
     break_step_ = 0;
-    return pins_.each_list([&](auto& l) {                                   // 6. add_pins, add_links, add_angles, add_sliders of the saved ones, with their break limits
+    PHX_TRY(pins_.each_list([&](auto& l) {                                  // 6. add_pins, add_links, add_angles, add_sliders of the saved ones, with their break limits
         using P = typename std::decay_t<decltype(l)>::record;
         return pins_.adopt_device(s.units<P>(), s.unit_limits<P>(), s.unit_count<P>(), stream_);
-    });
+    }));
+    return exclusions_.adopt_device(s.exclusions(), s.exclusion_count(), stream_);      // 7. add_collision_exclusions of the saved ones (no manifold holds one)
 }
 
 int World::get_slab_state(const long long* global_index, int count, SlabState* out)
@@ -1320,9 +1337,9 @@ int World::get_poses_device(void* d_out, int cap)
     return PHX_OK;
 }
 
-// ---- the compaction of the contact cache (a removal, a change of collision filters) ------------------------------------------------
+// ---- the compaction of the contact cache (a removal, a change of collision filters, a new collision exclusion) ----------------------
 // Kept manifolds and joints keep their old order: their new positions are exclusive scans of the keep predicate (world_kernels.h
-// BodiesKept / FilterKept; rm_counts_[1], [2] receive the kept counts), and two kernels write them out of place into the spares, with
+// BodiesKept / FilterKept / ExclusionKept; rm_counts_[1], [2] receive the kept counts), and two kernels write them out of place into the spares, with
 // the kept manifolds' pairs in rm_pairs_ (the new broadphase pair set).  Grid-strided over the OLD counts: no host count needed.
 int World::compaction_scratch()
 {
@@ -1433,6 +1450,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     records_stale_ = false;
     accel_pending_ = accel_pending_ && got[3] != 0;                         // (what the upload of the kept records would find)
     PHX_TRY(adopt_compaction(got));
+    PHX_TRY(exclusions_.bodies_removed(rm_remap_.p, rb_, stream_));         // (the excluded pairs of the removed bodies go, the rest through new[])
     return pins_.bodies_removed(rm_remap_.p, rb_, stream_);                 // (the pins of the removed bodies go, the rest through new[])
 }
 
@@ -1560,6 +1578,105 @@ int World::set_collision_filters(const int32_t* bodies, const phx_collision_filt
     if ((int)got[1] == nm) return PHX_OK;                                   // nothing dropped: a true no-op for the topology (the spares are dropped)
     ++contact_epoch_;                                                       // (the touch events' baseline stays: dropped pairs end)
     return adopt_compaction(got);
+}
+
+// ---- collision exclusions ---------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h COLLISION EXCLUSIONS; the set and its device side: exclusions.h.  The broadphase applies it inside the
+// sweep behind the filter (broadphase.hip ExcludedSweepView); what an add does to pairs that exist already is set_collision_filters' own
+// path with "the pair is not in the set" as the keep predicate (ExclusionKept).
+// the checks of a pair list, all of them before anything changes; `keys`: the normalised keys in the call's order
+int World::check_exclusion_pairs(const char* what, const int32_t* pairs, int count, std::vector<unsigned long long>* keys)
+{
+    PHX_TRY(refuse_sharded(what, "collision exclusions"));
+    PHX_TRY(refuse_mid_step(what));
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && !pairs) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    const int n = nb();
+    keys->clear();
+    for (int k = 0; k < count; ++k) {
+        const int a = pairs[2 * (size_t)k], b = pairs[2 * (size_t)k + 1];
+        if (a < 0 || a >= n || b < 0 || b >= n) { set_error("%s: pair %d: body index %d out of range [0, %d)", what, k, a < 0 || a >= n ? a : b, n); return PHX_ERR_INVALID; }
+        if (a == b) { set_error("%s: pair %d names body %d twice", what, k, a); return PHX_ERR_INVALID; }
+        keys->push_back(ps_unordered_key((unsigned)a, (unsigned)b));
+    }
+    if (count > 1) {
+        std::vector<unsigned long long> sorted(*keys);
+        std::sort(sorted.begin(), sorted.end());
+        const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+        if (twice != sorted.end()) {
+            set_error("%s: the pair (%u, %u) appears twice in one call", what, (unsigned)(*twice >> 32), (unsigned)*twice);
+            return PHX_ERR_INVALID;
+        }
+    }
+    return PHX_OK;
+}
+
+int World::add_collision_exclusions(const int32_t* pairs, int count, int* dropped)
+{
+    static const char* const what = "phx_world_add_collision_exclusions";
+    std::vector<unsigned long long> keys;
+    PHX_TRY(check_exclusion_pairs(what, pairs, count, &keys));
+    if (dropped) *dropped = 0;
+    if (!count) return PHX_OK;
+    PHX_TRY(wake_named(pairs, 2 * count));
+    const int before = exclusions_.count();
+    exclusions_.add(keys);
+    if (exclusions_.count() == before || !nm) return PHX_OK;               // nothing new, or no pair exists to drop: the device side follows at the next step
+    // the manifolds whose pair is now excluded go, with their slots and joints; the one round trip brings back the kept counts
+    PHX_TRY(use_device(device_));
+    PHX_TRY(solver_.synchronize());                                         // (an unverified solve is settled before anything moves)
+    PHX_TRY(sync_bodies_to_device());                                       // (host-staged bodies go up as the next step would take them)
+    PHX_TRY(exclusions_.sync(nb(), stream_));
+    PHX_TRY(compaction_scratch());
+    const ExclusionKept kept{exclusions_.view()->table, exclusions_.view()->mask};
+    PHX_TRY(scan_compaction(kept));
+    PHX_TRY(queue_compaction(kept));
+    unsigned got[5] = {0, 0, 0, 0, 0};
+    PHX_TRY(rb_.add(got, rm_counts_.p, sizeof got, stream_));
+    PHX_TRY(rb_.wait(stream_));
+    if (dropped) *dropped = nm - (int)got[1];
+    if ((int)got[1] == nm) return PHX_OK;                                   // nothing dropped: a true no-op for the topology (the spares are dropped)
+    ++contact_epoch_;                                                       // (the touch events' baseline stays: dropped pairs end)
+    return adopt_compaction(got);
+}
+
+int World::remove_collision_exclusions(const int32_t* pairs, int count)
+{
+    std::vector<unsigned long long> keys;
+    PHX_TRY(check_exclusion_pairs("phx_world_remove_collision_exclusions", pairs, count, &keys));
+    if (!count) return PHX_OK;
+    PHX_TRY(wake_named(pairs, 2 * count));
+    exclusions_.remove(keys);                                               // (no manifold changes: an overlapping pair is new to the next step's UpdatePairs)
+    return PHX_OK;
+}
+
+int World::clear_collision_exclusions()
+{
+    static const char* const what = "phx_world_clear_collision_exclusions";
+    PHX_TRY(refuse_sharded(what, "collision exclusions"));
+    PHX_TRY(refuse_mid_step(what));
+    if (exclusions_.empty()) return PHX_OK;
+    std::vector<int> named;
+    for (const unsigned long long k : exclusions_.keys()) { named.push_back((int)(k >> 32)); named.push_back((int)(unsigned)k); }
+    PHX_TRY(wake_named(named.data(), (int)named.size()));
+    exclusions_.clear();
+    return PHX_OK;
+}
+
+int World::get_collision_exclusions(int32_t* out, int cap, int32_t* count) const
+{
+    const int n = exclusions_.count();
+    if (count) *count = n;
+    if (cap < n) { set_error("phx_world_get_collision_exclusions: room for %d pairs, the set holds %d", cap, n); return PHX_ERR_CAPACITY; }
+    for (int i = 0; i < n; ++i) { const unsigned long long k = exclusions_.keys()[(size_t)i]; out[2 * i] = (int32_t)(k >> 32); out[2 * i + 1] = (int32_t)(unsigned)k; }
+    return PHX_OK;
+}
+
+int World::refuse_exclusions(const char* what) const
+{
+    if (exclusions_.empty()) return PHX_OK;
+    set_error("%s: the world holds %d collision exclusions, which a sharded world does not carry", what, exclusions_.count());
+    return PHX_ERR_STATE;
 }
 
 // the two getters: every body's value in the C ABI's form
@@ -2362,6 +2479,7 @@ int phx_world_set_shard(phx_world* w, int32_t shard, int32_t count)
     if (count > 1) PHX_TRY(w->impl.refuse_pins("phx_world_set_shard"));
     if (count > 1) PHX_TRY(w->impl.refuse_tables("phx_world_set_shard"));
     if (count > 1) PHX_TRY(w->impl.refuse_fields("phx_world_set_shard"));
+    if (count > 1) PHX_TRY(w->impl.refuse_exclusions("phx_world_set_shard"));
     w->impl.shard = shard; w->impl.shard_count = count;
     PHX_TRY(w->impl.solver().set_shard(shard, count));
     return PHX_OK;
@@ -2405,6 +2523,7 @@ int phx_world_set_comm(phx_world* w, phx_comm* c)
     if (c) PHX_TRY(w->impl.refuse_pins("phx_world_set_comm"));
     if (c) PHX_TRY(w->impl.refuse_tables("phx_world_set_comm"));
     if (c) PHX_TRY(w->impl.refuse_fields("phx_world_set_comm"));
+    if (c) PHX_TRY(w->impl.refuse_exclusions("phx_world_set_comm"));
     return w->impl.set_comm(c ? &c->impl : nullptr);
 }
 
@@ -2504,6 +2623,31 @@ int phx_world_get_collision_filters(phx_world* w, phx_collision_filter* out, int
     PHX_REQUIRE(w, "null handle");
     PHX_REQUIRE(out || cap == 0, "null buffer");
     return w->impl.get_collision_filters(out, cap);
+}
+
+int phx_world_add_collision_exclusions(phx_world* w, const int32_t* pairs, int32_t count, int32_t* dropped)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.add_collision_exclusions(pairs, count, dropped);
+}
+
+int phx_world_remove_collision_exclusions(phx_world* w, const int32_t* pairs, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.remove_collision_exclusions(pairs, count);
+}
+
+int phx_world_clear_collision_exclusions(phx_world* w)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.clear_collision_exclusions();
+}
+
+int phx_world_get_collision_exclusions(phx_world* w, int32_t* out, int32_t cap, int32_t* count)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap <= 0, "null buffer");
+    return w->impl.get_collision_exclusions(out, cap, count);
 }
 
 int phx_world_set_materials(phx_world* w, const int32_t* bodies, const phx_material* materials, int32_t count)
@@ -2652,6 +2796,7 @@ int phx_world_reslab(phx_world* w, const phx_slab_transport* transport, int64_t*
     PHX_REQUIRE(scene_size >= *body_count && capacity >= *body_count, "bad sizes");
     PHX_TRY(w->impl.refuse_pins("phx_world_reslab"));
     PHX_TRY(w->impl.refuse_tables("phx_world_reslab"));
+    PHX_TRY(w->impl.refuse_exclusions("phx_world_reslab"));
     phx::SlabTransport tp;
     PHX_TRY(slab_transport(transport, w->impl, &tp));
     phx::SlabState st;

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "narrowphase.h"
 #include "sleep.h"
+#include "pair_set.h"
 
 namespace phx {
 
@@ -508,7 +509,7 @@ static __global__ void __launch_bounds__(256) k_keep_inside(const float4* __rest
     }
 }
 
-// The compaction of the contact cache is shared by two callers, which differ in the KEEP PREDICATE: which manifolds stay, and where
+// The compaction of the contact cache is shared by three callers, which differ in the KEEP PREDICATE: which manifolds stay, and where
 // their bodies go.  A removal keeps a manifold iff both of its bodies are kept and renumbers bodies through new[]; a change of collision
 // filters (phx_world_set_collision_filters) keeps it iff its pair passes the filters and leaves the bodies where they are.
 struct BodiesKept {
@@ -519,6 +520,12 @@ struct BodiesKept {
 struct FilterKept {
     const uint4* filters;      // per body {category, mask, group, 0}
     __device__ bool operator()(const phx_manifold& m) const { return collision_filter_pass(filters[m.body1], filters[m.body2]); }
+    __device__ int body(int b) const { return b; }
+};
+// ... and a new collision exclusion (phx_world_add_collision_exclusions) keeps it iff its pair is not in the set (exclusions.h)
+struct ExclusionKept {
+    const unsigned long long* table; unsigned mask;      // the exclusions' keys (pair_set.h)
+    __device__ bool operator()(const phx_manifold& m) const { return !ps_contains(table, mask, ps_unordered_key((unsigned)m.body1, (unsigned)m.body2)); }
     __device__ int body(int b) const { return b; }
 };
 
