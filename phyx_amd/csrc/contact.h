@@ -53,7 +53,7 @@ public:
     // caller has read that count back, baseline_remapped(count) makes it B (a removal that changes nothing does not call it)
     int remap_baseline(const int* d_remap, unsigned* d_count, hipStream_t s);
     void baseline_remapped(unsigned count) { std::swap(base_, base_spare_); base_n_ = (int)count; }
-    // snapshots (world.hip save / load): B as it is — its keys in HBM and their number; a load makes room (the old B goes), queues the
+    // snapshots (world_state.hip save / load): B as it is — its keys in HBM and their number; a load makes room (the old B goes), queues the
     // copy itself and then says how many keys B has
     unsigned long long* baseline() const { return base_.p; }
     int baseline_count() const { return base_n_; }

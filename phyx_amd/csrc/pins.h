@@ -7,7 +7,7 @@
 //
 // Links (include/phyx_amd.h LINKS) are the pass's second kind of unit: the units are the pins followed by the links, one schedule and
 // one pass for both.  UnitList is the one copy of the list machinery (host and device copy, upload, fetch, remap, field edits) for either
-// record, and UnitKind states what the World's one copy of the calls (world.hip, "units") needs to know of a record.
+// record, and UnitKind states what the World's one copy of the calls (world_units.hip) needs to know of a record.
 //
 // Angles (include/phyx_amd.h ANGLES) are the third kind, behind the links: a record without anchors, so nothing here may ask for any
 // but through AnchorFields, which an angle never instantiates.
@@ -144,7 +144,7 @@ public:
     long long builds() const { return builds_; }
     int iterations = 8;
 
-    // the calls (world.hip, "units") work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
+    // the calls (world_units.hip) work on list<P>() with arguments already checked; what is the set's own: an add or a removal ...
     void units_changed() { sched_dirty_ = true; }
     void clear() { each_list([](auto& l) { l.clear(); return PHX_OK; }); sched_dirty_ = true; drop_breaks(); }
     void statics_changed() { if (units()) sched_dirty_ = true; }             // ... and a change of the static set make the schedule stale

@@ -463,7 +463,7 @@ int PinSet::solve(const WorldBodies& bodies, int nb, float dt, int step, Readbac
 
 } // namespace phx
 
-// ---- C ABI: the host-only builder (the world's calls: world.hip) ----
+// ---- C ABI: the host-only builder (the world's calls: c_api_world.hip) ----
 extern "C" int phx_pin_schedule(const int32_t* body1, const int32_t* body2, int32_t pin_count, const uint8_t* is_static, int32_t body_count, int32_t group_pins,
                                 int32_t* order, int32_t* class_offsets, int32_t class_cap, int32_t* class_count,
                                 int32_t* group_offsets, int32_t group_cap, int32_t* group_count, int32_t* lds_group_count)

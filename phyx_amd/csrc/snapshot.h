@@ -1,6 +1,6 @@
 // snapshot.h — a saved world in HBM (include/phyx_amd.h SNAPSHOTS): one device allocation in the blob's own layout
 // (snapshot_blob.h, bytes [128, total)), filled and emptied by the two kernels of snapshot_kernels.h on the stream of the world
-// that saves or loads.  The World (world.hip) hands out its arrays as a SnapshotWorld; everything else lives here: the layout, the
+// that saves or loads.  The World (world_state.hip) hands out its arrays as a SnapshotWorld; everything else lives here: the layout, the
 // growth of the allocation, and the two events that order a save by one world against a load by another without a host wait.
 #pragma once
 

@@ -160,7 +160,7 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
 
 } // namespace phx
 
-// ---- C ABI (phx_world_save / phx_world_load: world.hip) ----------------------------------------------------------------------------
+// ---- C ABI (phx_world_save / phx_world_load: c_api_world.hip) ----------------------------------------------------------------------------
 extern "C" {
 
 int phx_snapshot_create(phx_snapshot** out, int device)

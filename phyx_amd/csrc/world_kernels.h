@@ -113,7 +113,7 @@ static __global__ void __launch_bounds__(256) k_set_inverse_masses(const int* __
 }
 
 // ---- the optional per-body columns ---------------------------------------------------------------------------------------------------
-// A column holds one value per body and exists only once some body's value was set (world.hip BodyTable); until then every body has
+// A column holds one value per body and exists only once some body's value was set (world.h BodyTable); until then every body has
 // the column's default and the step runs the kernels it always ran.  A column states its stored type, its default, and the conversions
 // between the stored value and the C ABI's struct, which is also the form a batch is staged in.
 struct FilterColumn {                  // include/phyx_amd.h COLLISION FILTERS; the rule: common.h collision_filter_pass
@@ -161,7 +161,7 @@ static __global__ void __launch_bounds__(256) k_scatter_column(const int* __rest
 
 // what the spawn and the removal move beside the records and the resident arrays: the pending accelerations (consumed by the next
 // IntegrateVelocity) and the columns above.  Null = absent.  A new column is one member here, one line in each of the two kernels, and its table in the World's
-// each_table / columns() / spare_columns() (world.hip), which is what fills the member.
+// each_table / columns() / spare_columns() (world.h), which is what fills the member.
 struct BodyColumns {
     float4* accel;
     uint4* filters;

@@ -69,7 +69,7 @@ def filter(state, removed):
 
 
 def set_state_problems(state):
-    """What phx_world_set_state would refuse in `state` (its checks, csrc/world.hip World::set_state), plus the record index
+    """What phx_world_set_state would refuse in `state` (its checks, csrc/world_state.hip World::set_state), plus the record index
     invariant AddBody sets up (ref: World.cpp:14); an empty list if none."""
     bodies, manifolds, cps, joints = state
     nb, nm = len(bodies), len(manifolds)

@@ -336,3 +336,37 @@ def test_drag_example_moves_body_1_toward_its_target(tmp_path, built_lib):
     d1 = np.hypot(target[0] - end[0], target[1] - end[1])
     assert d1 < 0.1 * d0, line
     assert "world:" in r.stdout
+
+
+def test_staging_regrown_under_queued_edits(built_lib):
+    """Three edits queued back to back with no read in between, sized so that the second outgrows both the pinned staging buffer (made
+    at its 64 KB floor by the first: 4096 * (4 + 24) B = 112 KB) and the batch's place on the device while the first copy and scatter
+    may still be queued; the third is a bump allocation in the regrown buffer, or its reuse from offset 0.  Every value must arrive."""
+    n, side = 4096, 64
+    k = np.arange(n)
+    spawn = np.stack([(k % side) * 10.0, (k // side) * 10.0, np.zeros(n), np.full(n, 2.0), np.full(n, 2.0)], axis=1).astype(np.float32)
+    pw = phyx_amd.World(0, gravity=0.0)
+    pw.add_bodies(spawn)
+    pw.Update(DT, Configuration(phyx_amd.SOLVE_AVX2, phyx_amd.ISLAND_SINGLE_SLOPPY, 10, 10))      # the device copy is the world
+    rng = np.random.default_rng(11)
+    first, second = np.arange(100, 116, dtype=np.int32), np.arange(3000, 3016, dtype=np.int32)
+    v1 = rng.uniform(-50.0, 50.0, size=(16, 3)).astype(np.float32)
+    v2 = rng.uniform(-50.0, 50.0, size=(16, 3)).astype(np.float32)
+    order = rng.permutation(n).astype(np.int32)
+    angle = rng.uniform(-3.0, 3.0, size=n)
+    poses = np.stack([rng.uniform(-1e4, 1e4, size=n), rng.uniform(-1e4, 1e4, size=n), np.cos(angle), np.sin(angle), -np.sin(angle), np.cos(angle)],
+                     axis=1).astype(np.float32)
+    pw.set_velocities(first, v1)
+    pw.set_poses(order, poses)
+    pw.set_velocities(second, v2)
+    b = pw.bodies
+    assert len(b) == n
+    got_v = np.stack([b["velocity"]["x"], b["velocity"]["y"], b["angular_velocity"]], axis=1)
+    assert got_v[first].tobytes() == v1.tobytes()
+    assert got_v[second].tobytes() == v2.tobytes()
+    got_p = np.stack([b["pos"]["x"], b["pos"]["y"], b["xv"]["x"], b["xv"]["y"], b["yv"]["x"], b["yv"]["y"]], axis=1)
+    assert got_p[order].tobytes() == poses.tobytes()
+    others = np.ones(n, dtype=bool)
+    others[first] = False
+    others[second] = False
+    assert not got_v[others].any()                                           # (no gravity, no contact: the step left every velocity 0)
