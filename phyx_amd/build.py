@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libphyx_amd.so")
-SOURCES = ["runtime.hip", "schedule.hip", "solver.hip", "solver_build.hip", "islands.hip", "exchange.hip", "comm.hip", "c_api_solver.hip", "broadphase.hip", "world.hip", "world_state.hip", "world_edit.hip", "world_units.hip", "world_query.hip", "c_api_world.hip", "reslab.hip", "query.hip", "contact.hip", "snapshot.hip", "pins.hip", "sleep.hip", "fields.hip", "exclusions.hip", "debug_primitives.hip"]
+SOURCES = ["runtime.hip", "schedule.hip", "solver.hip", "solver_build.hip", "islands.hip", "exchange.hip", "comm.hip", "c_api_solver.hip", "broadphase.hip", "c_api_broadphase.hip", "world.hip", "world_state.hip", "world_edit.hip", "world_units.hip", "world_query.hip", "c_api_world.hip", "reslab.hip", "query.hip", "contact.hip", "snapshot.hip", "pins.hip", "sleep.hip", "fields.hip", "exclusions.hip", "debug_primitives.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-result"]
 # per-file extras.  islands.hip: the SLP vectoriser pairs the joint update's multiplies and adds into v_pk_mul_f32 / v_pk_add_f32

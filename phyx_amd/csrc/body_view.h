@@ -33,6 +33,20 @@ struct WorldBodies {
     const struct SleepCell* sleep;      // the queries only (query_kernels.h q_static): the sleep column (sleep.h), null while sleeping is off and in every other view
 };
 
+// IntegrateVelocity (ref: World.cpp:39-55) of one body: its vel granule after `dt` under `accel` = {acceleration.x, .y,
+// angularAcceleration} (zero where the body carries none) and gravity, which only a body with an inverse mass (mpos.x) feels.  The
+// statements keep the reference's form (x + 0 * dt is not x for x = -0).  Its users: k_integrate_velocity (world_kernels.h) and the two
+// first kernels of a broadphase update that take the velocity step along, k_build_keys<true> and k_keys_buckets<true, *>.
+__device__ __forceinline__ float4 integrate_velocity(float4 v, float4 accel, float inv_mass, float gravity, float dt)
+{
+    const float ax = accel.x, aa = accel.z;
+    float ay = accel.y;
+    if (inv_mass > 0.0f) ay += gravity;
+    v.x += ax * dt; v.y += ay * dt;
+    v.z += aa * dt;
+    return v;
+}
+
 // 16-byte non-temporal store (results that nobody re-reads before the kernel ends: they should not wait in L2 for the
 // end-of-kernel write-back)
 typedef float f4v __attribute__((ext_vector_type(4)));

@@ -1,4 +1,4 @@
-// broadphase.h — host side of the device broadphase (kernels + layout notes: broadphase.hip).
+// broadphase.h — host side of the device broadphase (kernels + layout notes: broadphase_kernels.h).
 #pragma once
 
 #include "common.h"
@@ -43,10 +43,20 @@ public:
     hipStream_t stream() const { return stream_; }
 
 private:
+    // update_resident's stages, in their order (broadphase.hip); `Update` is what they hand on
+    struct Update;
+    int reserve_update(Update& u);                     // every buffer of the update; the pair table kept at most half full
+    int empty_update(const StepPrologue* prologue);    // no bodies
+    int sort(const float4* d_aabb, const StepPrologue* prologue, const Update& u);      // either sort, queued; its first kernel takes the update's head along
+    int count_new_pairs(Update& u, const std::function<int()>* while_waiting, const MailCarrier* carrier);      // count pass, scan, the one readback
+    int emit_new_pairs(Update& u);                     // emit pass, insertion into the pair set
+
     int resize_table(unsigned want_cap);
     int exclusive_scan(unsigned* data, int count, unsigned* total_out);
     int queue_erase_check(int* erased);
     int settle_erase_check(int erased);
+    int stage_pairs(const void* pairs, int count);
+    int require_update() const;
 
     int device_;
     hipStream_t stream_ = nullptr;

@@ -350,7 +350,7 @@ private:
 // ---- collision filters (phx_world_set_collision_filters) -------------------------------------------------------------------------
 // The World keeps one 16-byte record per body, {category, mask, (unsigned) group, 0}; the default {1, 0xFFFFFFFF, 0, 0} lets every
 // pair through.  The rule (include/phyx_amd.h): a shared non-zero group decides alone (positive: collide, negative: never), otherwise
-// each body's mask must meet the other's category.  Selects, no branches: it sits inside the predicated sweep (broadphase.hip).
+// each body's mask must meet the other's category.  Selects, no branches: it sits inside the predicated sweep (broadphase_kernels.h).
 constexpr unsigned FILTER_DEFAULT_CATEGORY = 1u, FILTER_DEFAULT_MASK = 0xFFFFFFFFu;
 // ---- materials (phx_world_set_materials): the reference's kFrictionCoefficient (ref: Solver.cpp:9) and bounce (ref: Solver.cpp:658) ----
 constexpr float MATERIAL_DEFAULT_FRICTION = 0.3f, MATERIAL_DEFAULT_RESTITUTION = 0.0f;

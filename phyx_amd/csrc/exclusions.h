@@ -13,7 +13,7 @@
 
 namespace phx {
 
-// what the sweep (broadphase.hip ExcludedSweepView) and the compaction (world_kernels.h ExclusionKept) read
+// what the sweep (broadphase_kernels.h ExcludedSweepView) and the compaction (world_kernels.h ExclusionKept) read
 struct ExclusionView {
     const unsigned long long* table;     // keys ps_unordered_key(a, b)
     unsigned mask;

@@ -1,5 +1,5 @@
 // pair_set.h — the open-addressing table of 64-bit body-pair keys, as the device reads it: the broadphase's persistent pair set
-// (broadphase.hip, which also owns the kernels that write one) and the collision exclusions' table (exclusions.h) are both one.
+// (broadphase_kernels.h, which also owns the kernels that write one) and the collision exclusions' table (exclusions.h) are both one.
 // Linear probing from ps_hash(key) & mask; a table holds PS_EMPTY wherever nothing was ever stored, so a probe ends there.
 #pragma once
 
@@ -28,10 +28,16 @@ __device__ __forceinline__ bool ps_contains(const unsigned long long* __restrict
     }
 }
 
-// the key of an UNORDERED pair: {min, max} (the pair set's own keys are ordered as the sweep met them; an exclusion is not)
+// the pair set's own key: the ORDERED pair, as the sweep met it (a: the row's body, b: the candidate's)
+__host__ __device__ __forceinline__ unsigned long long ps_ordered_key(unsigned a, unsigned b)
+{
+    return ((unsigned long long)a << 32) | b;
+}
+
+// the key of an UNORDERED pair: {min, max} (an exclusion does not know which of its two bodies the sweep meets first)
 __host__ __device__ __forceinline__ unsigned long long ps_unordered_key(unsigned a, unsigned b)
 {
-    return a < b ? ((unsigned long long)a << 32) | b : ((unsigned long long)b << 32) | a;
+    return a < b ? ps_ordered_key(a, b) : ps_ordered_key(b, a);
 }
 
 } // namespace phx

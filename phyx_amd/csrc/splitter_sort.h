@@ -17,7 +17,7 @@
 //                     (ref: Collider.cpp:269-283) and the next update's splitters
 #pragma once
 
-#include "common.h"
+#include "body_view.h"
 
 namespace phx {
 
@@ -54,11 +54,36 @@ struct SplitSortView {
     unsigned* max_bucket;                      // statistics: the largest bucket of this update (atomicMax)
 };
 
-__device__ __forceinline__ unsigned ss_radix_float(float v)      // radixFloat (ref: base/RadixSort.h:19-26)
+// radixFloat (ref: base/RadixSort.h:19-26): the sort key of a body is this of its AABB's min x, in either sort
+__device__ __forceinline__ unsigned radix_float(float v)
 {
     const int f = __float_as_int(v);
     const unsigned mask = (unsigned)(f >> 31) | 0x80000000u;
     return (unsigned)f ^ mask;
+}
+
+// The head of an update: what its first kernel — k_keys_buckets here, k_build_keys (broadphase_kernels.h) where the LSD sort runs —
+// does before it makes keys, so that neither a memset nor a kernel of its own has to (two dispatches fewer), and what it takes along.
+// The host fills one per update (DeviceBroadphase::sort).
+struct UpdateHead {
+    // IntegrateVelocity (ref: World.cpp:39-55) riding along, INTEGRATE instantiations only: what broadphase.h StepPrologue holds
+    float4* vel; const float4* mpos; const float4* accel;      // (accel: null but for the first step after an upload that came with some)
+    unsigned* counters;                                        // the World's eight step counters
+    float gravity, dt;
+    // the update's own words to clear (broadphase_kernels.h SMALL_*, the hub chunks' counts) and its clock
+    unsigned long long* small; int nsmall;
+    unsigned* chunk_count; int nchunks;
+    unsigned long long* stamps;      // [0] := the 100 MHz clock now, [1] := 0; the count pass's mailbox post and the insert kernel raise [1]:
+                                     // the update's device time without HIP events (an event record is a barrier packet of its own, ~5 us of idle queue)
+};
+
+template <bool INTEGRATE>
+__device__ __forceinline__ void update_head(const UpdateHead& h)
+{
+    if (INTEGRATE && blockIdx.x == 0 && threadIdx.x < 8) h.counters[threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x == 0) { h.stamps[0] = (unsigned long long)wall_clock64(); h.stamps[1] = 0ull; }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h.nsmall; i += gridDim.x * blockDim.x) h.small[i] = 0ull;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < h.nchunks; i += gridDim.x * blockDim.x) h.chunk_count[i] = 0u;
 }
 
 // bucket of composite c = number of splitters <= c
@@ -73,18 +98,14 @@ __device__ __forceinline__ int ss_bucket(const unsigned long long* spl, int nspl
     return lo;
 }
 
-// INTEGRATE: IntegrateVelocity (ref: World.cpp:39-55) rides along exactly as in k_build_keys (broadphase.hip)
+// INTEGRATE: IntegrateVelocity (ref: World.cpp:39-55) rides along as in k_build_keys (broadphase_kernels.h)
 template <bool INTEGRATE, int ITEMS>
-__global__ void __launch_bounds__(SS_TILE_T) k_keys_buckets(SplitSortView v, float4* __restrict__ vel, const float4* __restrict__ mpos,
-                                                            unsigned long long* __restrict__ small, int nsmall, unsigned* __restrict__ chunk_count, int nchunks,
-                                                            unsigned long long* __restrict__ stamps, float gravity, float dt, unsigned* __restrict__ counters, const float4* __restrict__ accel)
+__global__ void __launch_bounds__(SS_TILE_T) k_keys_buckets(SplitSortView v, UpdateHead head)
 {
     __shared__ unsigned long long spl[SS_MAX_BUCKETS];
     __shared__ unsigned hist[SS_MAX_BUCKETS];
-    if (INTEGRATE && blockIdx.x == 0 && threadIdx.x < 8) counters[threadIdx.x] = 0u;
-    if (blockIdx.x == 0 && threadIdx.x == 0) { stamps[0] = (unsigned long long)wall_clock64(); stamps[1] = 0ull; *v.max_bucket = 0u; }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nsmall; i += gridDim.x * blockDim.x) small[i] = 0ull;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nchunks; i += gridDim.x * blockDim.x) chunk_count[i] = 0u;
+    update_head<INTEGRATE>(head);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *v.max_bucket = 0u;
     const int tile0 = blockIdx.x * (SS_TILE_T * ITEMS);
     // every load of the lane's ITEMS bodies is issued before anything is done with one of them — and before the splitters are fetched: body after body, a lane of the
     // eight-body shape made eight dependent trips to memory (26 us at 1e6 bodies for 70 MB)
@@ -95,7 +116,7 @@ __global__ void __launch_bounds__(SS_TILE_T) k_keys_buckets(SplitSortView v, flo
         minx[k] = 0.f; w[k] = make_float4(0.f, 0.f, 0.f, 0.f); im[k] = 0.f; acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < v.n) {
             minx[k] = v.aabb[i].x;
-            if (INTEGRATE) { w[k] = vel[i]; im[k] = mpos[i].x; if (accel) acc[k] = accel[i]; }
+            if (INTEGRATE) { w[k] = head.vel[i]; im[k] = head.mpos[i].x; if (head.accel) acc[k] = head.accel[i]; }
         }
     }
     const int nspl = v.buckets - 1;
@@ -108,19 +129,12 @@ __global__ void __launch_bounds__(SS_TILE_T) k_keys_buckets(SplitSortView v, flo
     for (int k = 0; k < ITEMS; ++k) {
         const int i = tile0 + k * SS_TILE_T + threadIdx.x;
         if (i >= v.n) continue;
-        const unsigned key = ss_radix_float(minx[k]);
+        const unsigned key = radix_float(minx[k]);
         const int b = ss_bucket(spl, nspl, steps, ((unsigned long long)key << 32) | (unsigned)i);
         v.keys[i] = key;
         v.bucket_of[i] = (unsigned short)b;
         atomicAdd(&hist[b], 1u);
-        if (INTEGRATE) {
-            float4 u = w[k];
-            float ax = acc[k].x, ay = acc[k].y, aa = acc[k].z;
-            if (im[k] > 0.0f) ay += gravity;
-            u.x += ax * dt; u.y += ay * dt;
-            u.z += aa * dt;
-            vel[i] = u;
-        }
+        if (INTEGRATE) head.vel[i] = integrate_velocity(w[k], acc[k], im[k], head.gravity, head.dt);
     }
     __syncthreads();
     for (int b = threadIdx.x; b < v.buckets; b += SS_TILE_T) if (hist[b]) atomicAdd(&v.count[b], hist[b]);

@@ -358,7 +358,7 @@ int World::set_column(const char* what, BodyTable<Column>& table, const int32_t*
 
 // ---- collision filters ------------------------------------------------------------------------------------------------------------
 // The rule and the defaults: include/phyx_amd.h COLLISION FILTERS, common.h collision_filter_pass.  The broadphase applies it inside the
-// sweep (broadphase.hip FilteredSweepView), so a failing pair is never emitted; what a change of filters does to pairs that exist already
+// sweep (broadphase_kernels.h FilteredSweepView), so a failing pair is never emitted; what a change of filters does to pairs that exist already
 // is the removal's compaction of the contact cache with the filter as its keep predicate (FilterKept), bodies untouched.
 int World::set_collision_filters(const int32_t* bodies, const phx_collision_filter* filters, int count, int* dropped)
 {
@@ -370,7 +370,7 @@ int World::set_collision_filters(const int32_t* bodies, const phx_collision_filt
 
 // ---- collision exclusions ---------------------------------------------------------------------------------------------------------
 // The rule: include/phyx_amd.h COLLISION EXCLUSIONS; the set and its device side: exclusions.h.  The broadphase applies it inside the
-// sweep behind the filter (broadphase.hip ExcludedSweepView); what an add does to pairs that exist already is set_collision_filters' own
+// sweep behind the filter (broadphase_kernels.h ExcludedSweepView); what an add does to pairs that exist already is set_collision_filters' own
 // path with "the pair is not in the set" as the keep predicate (ExclusionKept).
 // the checks of a pair list, all of them before anything changes; `keys`: the normalised keys in the call's order
 int World::check_exclusion_pairs(const char* what, const int32_t* pairs, int count, std::vector<unsigned long long>* keys)
