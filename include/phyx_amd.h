@@ -614,6 +614,60 @@ int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
 int  phx_world_set_body_flags(phx_world* w, const int32_t* bodies, const uint32_t* flags, int32_t count);
 /* every body's flags, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
 int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
+/* SHAPES — round bodies.  Every body has a shape {kind, hx, hy}: its kind, PHX_SHAPE_BOX (the default) or PHX_SHAPE_CIRCLE, and its
+ * geom_size.  A box's size is its half extents; a circle's is {r, r}, its radius twice.  A world that never made a circle launches
+ * exactly the kernels it launched before there were shapes, and one whose shape column is active while every body is a box steps bit
+ * for bit like it.
+ *   - Where it acts: UpdateManifolds (ref: Collider.cpp:211-245).  In front of the separating-axis test the pair's kinds pick the routine;
+ *     box/box is the reference's code.  The round routines produce at most one new point per step and hand it to the reference's
+ *     MergeCollision (ref: Collider.cpp:58-92) unchanged, so warm starting, isNewlyCreated and the two-slot store work as for boxes.  The
+ *     normal keeps the stored convention: it points from body2 towards body1, and (p2 - p1) . n >= 0 is the penetration.  Every operation
+ *     is fp32 and rounded on its own, sqrtf and / correctly rounded, dot(a, b) = a.x*b.x + a.y*b.y; tests/circle_spec.py states what
+ *     follows as the same expressions and the device matches it byte for byte.
+ *       circle/circle (r = size.x):  d = pos1 - pos2, l2 = dot(d, d), R = r1 + r2.  No point if l2 > R*R.  l = sqrtf(l2),
+ *         n = (d.x / l, d.y / l) if l > 0, else (1, 0).  p1 = pos1 - n*r1, p2 = pos2 + n*r2.
+ *       circle C against box B (frame xv, yv, half extents h):  c = C.pos - B.pos, u = dot(c, xv), v = dot(c, yv),
+ *         qu = u < -h.x ? -h.x : (u > h.x ? h.x : u), qv likewise.
+ *         If qu == u && qv == v (the centre is inside or on the box): pu = h.x - |u|, pv = h.y - |v|; if pu <= pv the face is on x:
+ *           N = (u < 0 ? -xv : xv) and qu = (u < 0 ? -h.x : h.x); otherwise on y: N = (v < 0 ? -yv : yv) and qv = (v < 0 ? -h.y : h.y).
+ *           N is an exact copy or negation of a stored vector.
+ *         Otherwise e = (u - qu, v - qv), l2 = dot(e, e); no point if l2 > r*r; l = sqrtf(l2), N = xv*(e.x / l) + yv*(e.y / l).
+ *         Box point = (B.pos + xv*qu) + yv*qv, circle point = C.pos - N*r.  C is body1: n = N, p1 = circle point, p2 = box point;
+ *         C is body2: n = -N, p1 = box point, p2 = circle point.
+ *   - Deliberately unchanged: UpdateGeom, IntegratePosition and the broadphase.  A circle's AABB stays the AABB of its frame square
+ *     {r, r}: a conservative bound, at most sqrt(2) wider than the disc, so nothing upstream of the narrowphase knows the kind.  The
+ *     dead-manifold test (no points and the AABBs apart) and the contact reports stay valid as they are.  The solver sees contact points
+ *     and never the shape; pins, links, angles and sliders use body-local anchors.
+ *   - Setting shapes: the rules of the edits and of set_materials.  Between steps only (PHX_ERR_STATE); checked completely before
+ *     anything is queued (count >= 0, no NULL array when count > 0, every index in [0, body count), none twice, kind in {0, 1}, hx and hy
+ *     finite and > 0, hy == hx for a circle; PHX_ERR_INVALID otherwise, the world unchanged); staged through pinned memory and queued on
+ *     phx_world_stream(w); before the first step it writes the host-staged records.  The call sets the body's kind and its geom_size
+ *     (the record and the resident size) and recomputes the AABB as phx_world_set_poses does (ref: Geom.h:79-85): it is also the edit
+ *     that resizes a box.  A sharded or communicator-attached world gets PHX_ERR_STATE.
+ *   - Cached state: the call changes no joint topology by itself, so the cached schedule stays valid; cached contact points stay, and
+ *     the next step's UpdateManifolds merges or drops them by the ordinary rule; the query index is rebuilt by its next use, as after
+ *     set_poses.
+ *   - Inverse masses are not touched: the shape is geometry, phx_world_set_inverse_masses is the mass.  AddBody's scale for a box of
+ *     half sizes sx, sy is mass = 1e-5f * sx * sy, inertia = mass * (sx*sx + sy*sy) (a quarter of the area, three times the true box
+ *     inertia); the circle formula on the same scale is mass = 1e-5f * 0.785398f * r * r, inertia = mass * 1.5f * r * r
+ *     (phyx_amd.World.add_circles applies it).
+ *   - The other calls: add_body / add_bodies give boxes; remove_bodies / remove_outside move the kind with the kept bodies (through
+ *     new[]); phx_world_set_state resets every kind to box (the sizes are in the records; a world with circles is checkpointed as
+ *     set_state followed by set_shapes); phx_world_save / load and so a fork carry the kinds in HBM beside the blob's layout, as they
+ *     carry pins; phx_snapshot_export and phx_snapshot_blob_bytes of a snapshot in which a saved kind is not a box return
+ *     PHX_ERR_STATE (the blob stays layout version 1).  The edits, set_inverse_masses, filters, materials, flags and contact reports
+ *     leave shapes alone.  Queries: QUERIES below.
+ *   - Sharded worlds carry no circles: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and phx_world_reslab
+ *     return PHX_ERR_STATE while some body is not a box.
+ * The kinds are a column of one uint32 per body that exists only once some phx_world_set_shapes call named a circle (since the last
+ * set_state); a call that names boxes only is the size edit and activates nothing.  Costs and the data path: DESIGN.md. */
+#define PHX_SHAPE_BOX    0
+#define PHX_SHAPE_CIRCLE 1
+typedef struct { int32_t kind; float hx, hy; } phx_shape;   /* 12 B; box: half extents; circle: hx = radius, hy == hx */
+int  phx_world_set_shapes(phx_world* w, const int32_t* bodies, const phx_shape* shapes, int32_t count);
+/* every body's {kind, geom_size.x, geom_size.y}, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise); a world that
+ * never set a shape reports boxes */
+int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
 /* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first, whether a spot is free for a box
  * and how far a box can move before it touches something.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
@@ -660,6 +714,15 @@ int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
  *       normal = (0, 0) if tin < 0 (the boxes overlap at the start); otherwise the entering axis's stored vector (an exact copy of X,
  *                Y, xv or yv), negated when v on that axis is > 0: it points against the motion.
  *     The closest hit is the smallest t, ties to the lowest body index.
+ *   - Circles (SHAPES above; r = geom_size.x; tests/circle_spec.py states these as the same expressions).  The AABB query is unchanged: it
+ *     uses the record's AABB, that of the frame square.  Point p in circle b iff p is inside b's AABB (closed, as for a box) AND, with
+ *     dx = p.x - pos.x, dy = p.y - pos.y:  dx*dx + dy*dy <= r*r.  A ray hits circle b iff b is a candidate (the test on its AABB, as for a
+ *     box) and, with rx = ox - pos.x, ry = oy - pos.y, a = dx*dx + dy*dy, b = rx*dx + ry*dy, c = rx*rx + ry*ry - r*r, D = b*b - a*c:
+ *     D >= 0 (a miss if D < 0 or NaN), s = sqrtf(D), tin = (-b - s) / a, tout = (-b + s) / a, and tin <= tout && tout >= 0 && tin <= max_t,
+ *     the box rule.  Then t = (tin > 0 ? tin : 0), normal = (0, 0) if tin < 0, otherwise ((rx + tin*dx) / r, (ry + tin*dy) / r), point as
+ *     for boxes; ties go to the lowest index, as always.  Oriented-box queries and box casts see a circle as its frame square {r, r} in
+ *     the body's frame: both are conservative (they never miss a disc and never report a later t) and consistent with each other, the
+ *     two halves of "is this slot free, how far can I drop"; the exact disc versions are a later change.
  * flags: PHX_QUERY_SKIP_STATIC leaves static bodies (inv_mass == 0 && inv_inertia == 0) out of every result (picking without the ground).
  *   A body that sleeps (SLEEPING below) is not static to a query although its inverse masses read 0 while it does: picking a box out of a
  *   resting pile finds it.  A world with sleeping off answers as it always did.
@@ -774,7 +837,8 @@ int  phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t bod
  *       the bodies' 128-byte records as phx_world_get_bodies would return them at the save (a record the steps have left stale is brought up
  *       to date from the resident arrays on the way; pending accelerations ride in the records, as they do through phx_world_set_state);
  *       the manifolds, their contact-point slots, the joints with their warm-start impulses;
- *       the three optional columns (collision filters, materials, body flags), each with its "ever set" bit;
+ *       the three optional columns (collision filters, materials, body flags), each with its "ever set" bit (and, beside the blob's
+ *       layout, the shapes' kinds: SHAPES above);
  *       the touch events' baseline B AS IT IS (not T(state): the next phx_world_contact_events after a load reports what it would have
  *       reported had the save and the load never happened).
  *   - What it does NOT hold, and a load leaves alone: gravity, the shard and the communicator, phase timing, the paths chosen from the
@@ -1329,6 +1393,12 @@ int phx_debug_radix_sort(int device, const uint32_t* keys, const uint32_t* vals,
                          uint32_t* vals_out, int32_t* which);
 int phx_debug_primitive_plan(int32_t bits, int32_t scan_count, int32_t* digit_bits, int32_t* passes, int32_t* scan_single,
                              int32_t* scan_tiles);
+/* phx_debug_update_manifold (host only, needs no device): UpdateManifolds of ONE pair by the host instantiation of the function the
+ * device kernel calls (SHAPES above): the records b1, b2 (pos, xvector, yvector and geom_size are read) with their kinds, the pair's
+ * manifold (point_count 0 .. 2 is read and written; the other fields are left alone) and its two contact-point slots pts[0], pts[1],
+ * updated in place. */
+int phx_debug_update_manifold(const phx_rigid_body* b1, int32_t kind1, const phx_rigid_body* b2, int32_t kind2, phx_manifold* manifold,
+                              phx_contact_point pts[2]);
 
 #ifdef __cplusplus
 }

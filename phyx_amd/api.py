@@ -47,6 +47,8 @@ contact_dtype = np.dtype([("other", "<i4"), ("manifold", "<i4"), ("slot", "<i4")
 collision_filter_dtype = np.dtype([("category", "<u4"), ("mask", "<u4"), ("group", "<i4")])      # phx_collision_filter
 material_dtype = np.dtype([("friction", "<f4"), ("restitution", "<f4")])      # phx_material
 assert material_dtype.itemsize == 8
+shape_dtype = np.dtype([("kind", "<i4"), ("hx", "<f4"), ("hy", "<f4")])      # phx_shape
+assert shape_dtype.itemsize == 12
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 pin_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("impulse", "<f4", (2,))])      # phx_pin
@@ -75,6 +77,7 @@ FIELD_FORCE = 1                                                # PHX_FIELD_FORCE
 UNIT_KINDS = ("pin", "link", "angle", "slider")      # PHX_UNIT_PIN ... PHX_UNIT_SLIDER
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
+SHAPE_BOX, SHAPE_CIRCLE = 0, 1            # PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE (phx_shape.kind)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
 
 
@@ -107,6 +110,17 @@ def pinned_inv_inertia(sx, sy):
     mass = np.float32(1e-5) * (np.float32(sx) * np.float32(sy))
     inertia = mass * (np.float32(sx) * np.float32(sx) + np.float32(sy) * np.float32(sy))
     return float(np.float32(1.0) / inertia)
+
+
+def circle_inverse_masses(r):
+    """(K, 2) float32 {invMass, invInertia} of circles of radii r on AddBody's scale (include/phyx_amd.h SHAPES): mass = 1e-5f *
+    0.785398f * r * r, inertia = mass * 1.5f * r * r, every operation a float32 one, left to right."""
+    r = np.atleast_1d(np.asarray(r, dtype=np.float32))
+    f = np.float32
+    with np.errstate(over="ignore", divide="ignore"):
+        mass = f(1e-5) * f(0.785398) * r * r
+        inertia = mass * f(1.5) * r * r
+        return np.stack([f(1.0) / mass, f(1.0) / inertia], axis=1).astype(np.float32)
 
 
 def _or_empty(a, shape, dtype):
@@ -862,7 +876,7 @@ class World:
     # ---- snapshots (include/phyx_amd.h SNAPSHOTS; the blob's specification: tests/snapshot_spec.py) ----
     def save(self, snap=None):
         """snap := this world (phx_world_save), queued on the world's stream; a new Snapshot on the world's device when none is given.
-        Returns the snapshot.  It holds the state and the per-body columns, not settings such as gravity."""
+        Returns the snapshot.  It holds the state and the per-body columns (the shapes' kinds among them), not settings such as gravity."""
         if snap is None:
             snap = Snapshot(self.device)
         check(self.L.phx_world_save(self.h, snap.h))
@@ -1395,6 +1409,42 @@ class World:
     def body_flags(self):
         """Every body's flag word, in index order: a uint32 array."""
         return self._get(self.L.phx_world_get_body_flags, np.uint32, self.counts()[0])
+
+    # ---- shapes (include/phyx_amd.h SHAPES; the specification: tests/circle_spec.py) ----
+    def set_shapes(self, bodies, kind=SHAPE_BOX, hx=None, hy=None):
+        """Give the listed bodies (each at most once) the shape {kind, hx, hy}: each a scalar for all of them or one value per body.
+        kind is SHAPE_BOX (hx, hy: half extents) or SHAPE_CIRCLE (hx: the radius; hy may be left out and must equal hx otherwise).
+        The body's geom_size becomes (hx, hy) and its AABB is recomputed as set_poses recomputes it; the inverse masses stay
+        (set_inverse_masses; circle_inverse_masses has the circle formula).  The library rejects any other kind, sizes that are not
+        finite and positive and a circle whose hy differs from hx (PhxError), the world unchanged."""
+        idx = self._indices(bodies, "set_shapes")
+        if hx is None:
+            raise ValueError("set_shapes: hx (the half extent on x, or the radius) is required")
+        s = np.zeros(len(idx), dtype=shape_dtype)
+        s["kind"] = self._per_body("set_shapes", "kind", kind, len(idx), "iu", -2 ** 31, 2 ** 31 - 1)
+        s["hx"] = self._per_body("set_shapes", "hx", hx, len(idx), "fiu")
+        s["hy"] = s["hx"] if hy is None else self._per_body("set_shapes", "hy", hy, len(idx), "fiu")
+        check(self.L.phx_world_set_shapes(self.h, _ptr(idx), _ptr(s), len(idx)))
+
+    def shapes(self):
+        """Every body's shape {kind, hx, hy}, in index order: an array of shape_dtype (boxes in a world that never set a shape)."""
+        return self._get(self.L.phx_world_get_shapes, shape_dtype, self.counts()[0])
+
+    def add_circles(self, spawn):
+        """Append circles: spawn is a (K, 4) float array {px, py, angle, r}.  add_bodies with half extents (r, r), then set_shapes of
+        the new bodies to SHAPE_CIRCLE, then set_inverse_masses with circle_inverse_masses(r).  Returns the first new index."""
+        a = np.asarray(spawn)
+        if a.dtype.kind != "f":
+            raise TypeError("add_circles: spawn must be a float array, got %s" % (a.dtype,))
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("add_circles: spawn must have shape (K, 4) {px, py, angle, r}, got %s" % (a.shape,))
+        s = np.ascontiguousarray(a, dtype=np.float32)
+        idx = self.add_bodies(np.ascontiguousarray(s[:, [0, 1, 2, 3, 3]]))
+        first = int(idx[0]) if len(idx) else self.counts()[0]
+        if len(idx):
+            self.set_shapes(idx, SHAPE_CIRCLE, s[:, 3])
+            self.set_inverse_masses(idx, circle_inverse_masses(s[:, 3]))
+        return first
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----
     @staticmethod

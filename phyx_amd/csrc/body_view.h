@@ -31,6 +31,7 @@ struct WorldBodies {
     float4* aabb;       // {min.x, min.y, max.x, max.y}
     float2* size;       // geom.size
     const struct SleepCell* sleep;      // the queries only (query_kernels.h q_static): the sleep column (sleep.h), null while sleeping is off and in every other view
+    const uint32_t* kinds;              // the queries only (query_kernels.h q_circle): the shape column (world_kernels.h ShapeColumn), null while no body is a circle and in every other view
 };
 
 // IntegrateVelocity (ref: World.cpp:39-55) of one body: its vel granule after `dt` under `accel` = {acceleration.x, .y,

@@ -240,6 +240,19 @@ int phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap)
     return w->impl.get_body_flags(out, cap);
 }
 
+int phx_world_set_shapes(phx_world* w, const int32_t* bodies, const phx_shape* shapes, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_shapes(bodies, shapes, count);
+}
+
+int phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    PHX_REQUIRE(out || cap == 0, "null buffer");
+    return w->impl.get_shapes(out, cap);
+}
+
 int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
 {
     PHX_REQUIRE(w, "null handle");

@@ -1,8 +1,11 @@
 // debug_primitives.hip — test entry points of the two device primitives (device_scan.h, device_radix.h): the tests call the
 // dispatchers directly, at the sizes where they switch paths, instead of through whatever sizes the features above them reach.
 // Host arrays go in and come out; every call allocates, copies and synchronises.  Nothing in the product calls these.
+// Beside them, host only: the narrowphase's update_manifold (narrowphase.h) on one pair, so that the CPU suite can hold the C++ the
+// device kernel calls to tests/circle_spec.py without a GPU.
 #include "common.h"
 #include "device_radix.h"
+#include "narrowphase.h"
 
 namespace phx {
 namespace {
@@ -132,6 +135,22 @@ int phx_debug_radix_sort(int device, const uint32_t* keys, const uint32_t* vals,
     }
     PHX_HIP(hipStreamSynchronize(st.s));
     *which = where;
+    return PHX_OK;
+}
+
+int phx_debug_update_manifold(const phx_rigid_body* b1, int32_t kind1, const phx_rigid_body* b2, int32_t kind2, phx_manifold* manifold,
+                              phx_contact_point pts[2])
+{
+    using namespace phx;
+    PHX_REQUIRE(b1 && b2 && manifold && pts, "phx_debug_update_manifold: null argument");
+    PHX_REQUIRE((kind1 == PHX_SHAPE_BOX || kind1 == PHX_SHAPE_CIRCLE) && (kind2 == PHX_SHAPE_BOX || kind2 == PHX_SHAPE_CIRCLE), "phx_debug_update_manifold: a kind is 0 or 1");
+    PHX_REQUIRE(manifold->point_count >= 0 && manifold->point_count <= 2, "phx_debug_update_manifold: point_count is 0 .. 2");
+    auto body = [](const phx_rigid_body& b, int32_t kind) {
+        NpBody n;
+        n.pos = v2(b.pos); n.xv = v2(b.xvector); n.yv = v2(b.yvector); n.size = v2(b.geom_size); n.kind = (unsigned)kind;
+        return n;
+    };
+    (void)update_manifold(*manifold, body(*b1, kind1), body(*b2, kind2), pts);
     return PHX_OK;
 }
 

@@ -4,8 +4,9 @@
 // ref: src/Collider.cpp:8-245 and src/Geom.h:10-85 on the fields the resident arrays hold (body_view.h): a body is
 // {pos, xVector, yVector, size} here (the reference's Geom keeps a copy of the frame, refreshed by UpdateGeom,
 // RigidBody.h:38-42: the same values).  The functions are
-// plain IEEE float arithmetic (no libm beyond fabsf) so the host loop and a HIP kernel that call them
-// produce identical bits under -ffp-contract=off.
+// plain IEEE float arithmetic (no libm beyond fabsf, and the correctly rounded sqrtf of the round pairs) so the host loop and a HIP
+// kernel that call them produce identical bits under -ffp-contract=off.  Round bodies (circle/circle, circle/box) have no counterpart
+// in the reference: their rule is include/phyx_amd.h SHAPES.
 #pragma once
 
 #include "common.h"
@@ -24,8 +25,8 @@ __host__ __device__ __attribute__((always_inline)) inline float sqlen(V2 a) { re
 __host__ __device__ __attribute__((always_inline)) inline V2 perp(V2 a) { return v2(-a.y, a.x); }                            // ref: Vector2.h GetPerpendicular
 __host__ __device__ __attribute__((always_inline)) inline phx_vec2 pv(V2 a) { phx_vec2 r; r.x = a.x; r.y = a.y; return r; }
 
-// what the narrowphase reads of a body
-struct NpBody { V2 pos, xv, yv, size; };
+// what the narrowphase reads of a body (`kind`: PHX_SHAPE_BOX or PHX_SHAPE_CIRCLE, include/phyx_amd.h SHAPES; a circle's radius is size.x)
+struct NpBody { V2 pos, xv, yv, size; unsigned kind; };
 
 // ref: Geom.h:79-85 RecomputeAABB: {min.x, min.y, max.x, max.y}
 __host__ __device__ __attribute__((always_inline)) inline void geom_aabb(V2 pos, V2 xv, V2 yv, V2 size, float& minx, float& miny, float& maxx, float& maxy)
@@ -236,8 +237,52 @@ __host__ __device__ __attribute__((always_inline)) inline void generate_contacts
     }
 }
 
+// ---- round bodies (include/phyx_amd.h SHAPES; tests/circle_spec.py states the two routines as the same expressions) ----------------
+// Both feed merge_point with at most one point; the normal points from body2 towards body1 and (p2 - p1) . n >= 0 is the penetration,
+// as for boxes.  Every operation is rounded on its own; sqrtf and / are correctly rounded under the library's flags (pin_kernels.h).
+__host__ __device__ __attribute__((always_inline)) inline void circle_circle_contact(const NpBody& b1, const NpBody& b2, Pts4& pts, int& count)
+{
+    const float r1 = b1.size.x, r2 = b2.size.x;
+    const V2 d = b1.pos - b2.pos;
+    const float l2 = dot(d, d), R = r1 + r2;
+    if (l2 > R * R) return;
+    const float l = sqrtf(l2);
+    const V2 n = l > 0.0f ? v2(d.x / l, d.y / l) : v2(1.0f, 0.0f);
+    merge_point(pts, count, b1.pos - n * r1, b2.pos + n * r2, n, b1, b2);
+}
+
+// circle `c` against box `b`; `circle_first`: the circle is the manifold's body1
+__host__ __device__ __attribute__((always_inline)) inline void circle_box_contact(const NpBody& c, const NpBody& b, bool circle_first, Pts4& pts, int& count,
+                                                                                  const NpBody& b1, const NpBody& b2)
+{
+    const V2 xv = b.xv, yv = b.yv, h = b.size;
+    const float r = c.size.x;
+    const V2 rel = c.pos - b.pos;
+    const float u = dot(rel, xv), v = dot(rel, yv);
+    float qu = u < -h.x ? -h.x : (u > h.x ? h.x : u);
+    float qv = v < -h.y ? -h.y : (v > h.y ? h.y : v);
+    V2 N;
+    if (qu == u && qv == v) {                                           // the centre is inside or on the box: the face of least depth
+        const float pu = h.x - fabsf(u), pv_ = h.y - fabsf(v);
+        if (pu <= pv_) { N = u < 0.0f ? -xv : xv; qu = u < 0.0f ? -h.x : h.x; }
+        else           { N = v < 0.0f ? -yv : yv; qv = v < 0.0f ? -h.y : h.y; }
+    } else {
+        const V2 e = v2(u - qu, v - qv);
+        const float l2 = dot(e, e);
+        if (l2 > r * r) return;
+        const float l = sqrtf(l2);
+        N = xv * (e.x / l) + yv * (e.y / l);
+    }
+    const V2 on_box = (b.pos + xv * qu) + yv * qv;
+    const V2 on_circle = c.pos - N * r;
+    if (circle_first) merge_point(pts, count, on_circle, on_box, N, b1, b2);
+    else              merge_point(pts, count, on_box, on_circle, -N, b1, b2);
+}
+
 // ref: Collider.cpp:211-245.  Returns true if a third merged point had to be dropped: the reference
 // would write it past the manifold's two slots (only an assert guards it).
+// The pair's kinds pick the routine in front of least_penetration_axis; a caller whose kinds are the constant PHX_SHAPE_BOX (a world
+// without a shape column) compiles to the box/box code alone.
 __host__ __device__ __attribute__((always_inline)) inline bool update_manifold(phx_manifold& m, const NpBody& b1, const NpBody& b2, phx_contact_point* pts)
 {
     Pts4 np;
@@ -247,8 +292,12 @@ __host__ __device__ __attribute__((always_inline)) inline bool update_manifold(p
     if (m.point_count > 0) { np.a = cp_load(pts[0]); np.a.flags &= 0xFFFF0000u; }      // isMerged = isNewlyCreated = false
     if (m.point_count > 1) { np.b = cp_load(pts[1]); np.b.flags &= 0xFFFF0000u; }
     int count = m.point_count;
-    V2 axis;
-    if (least_penetration_axis(b1, b2, axis)) generate_contacts(b1, b2, np, count, axis);
+    if ((b1.kind | b2.kind) == 0u) {
+        V2 axis;
+        if (least_penetration_axis(b1, b2, axis)) generate_contacts(b1, b2, np, count, axis);
+    } else if (b1.kind != 0u && b2.kind != 0u) circle_circle_contact(b1, b2, np, count);
+    else if (b1.kind != 0u) circle_box_contact(b1, b2, true, np, count, b1, b2);
+    else circle_box_contact(b2, b1, false, np, count, b1, b2);
     m.point_count = 0;
     bool dropped = false;
     auto keep = [&](const CpR& q, int i) {

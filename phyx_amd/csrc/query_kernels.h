@@ -1,4 +1,4 @@
-// query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box, the closest
+// query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box or disc, the closest
 // ray hit, oriented-box overlap and the closest box-cast hit over the resident arrays (body_view.h).  The predicates below are the
 // header's formulas one for one, each operation rounded on its own (the library is compiled with -ffp-contract=off);
 // tests/query_spec.py and tests/shape_query_spec.py state them again in numpy.
@@ -54,6 +54,22 @@ __device__ __forceinline__ bool q_point_in_box(float4 a, float4 m, float4 f, flo
     return fabsf(u) <= h.x && fabsf(v) <= h.y;
 }
 
+// circles (include/phyx_amd.h SHAPES, QUERIES): `kinds` is the shape column, null while no body is a circle.  A circle's radius is its
+// size.x; the AABB conjunct and the candidate test are the box's.  Oriented boxes and casts see a circle as its frame square.
+__device__ __forceinline__ bool q_circle(const uint32_t* __restrict__ kinds, int i) { return kinds && kinds[i] != (uint32_t)PHX_SHAPE_BOX; }
+
+__device__ __forceinline__ bool q_point_in_circle(float4 a, float4 m, float r, float px, float py)
+{
+    if (!(a.x <= px && a.z >= px && a.y <= py && a.w >= py)) return false;
+    const float dx = px - m.z, dy = py - m.w;
+    return dx * dx + dy * dy <= r * r;
+}
+
+__device__ __forceinline__ bool q_point_in_body(bool circle, float4 a, float4 m, float4 f, float2 h, float px, float py)
+{
+    return circle ? q_point_in_circle(a, m, h.x, px, py) : q_point_in_box(a, m, f, h, px, py);
+}
+
 // one axis's slab: false when it is empty
 __device__ __forceinline__ bool q_slab(float o, float d, float lo, float hi, float& t0, float& t1)
 {
@@ -94,6 +110,30 @@ __device__ __forceinline__ bool q_ray_box(const QRay& r, float4 m, float4 f, flo
     out.dxp = r.dx * f.x + r.dy * f.y;
     out.dyp = r.dx * f.z + r.dy * f.w;
     return q_ray_test(oxp, oyp, out.dxp, out.dyp, -h.x, -h.y, h.x, h.y, r.max_t, out.tin, out.xenter);
+}
+
+// the ray against the disc (after the candidate test): the quadratic's two roots under the box rule; rx, ry = the origin from the centre
+__device__ __forceinline__ bool q_ray_circle(const QRay& r, float4 m, float rad, float& tin, float& rx, float& ry)
+{
+    rx = r.ox - m.z; ry = r.oy - m.w;
+    const float a = r.dx * r.dx + r.dy * r.dy, b = rx * r.dx + ry * r.dy, c = rx * rx + ry * ry - rad * rad;
+    const float D = b * b - a * c;
+    tin = 0.f;
+    if (D < 0.f) return false;
+    const float s = sqrtf(D);
+    tin = (-b - s) / a;
+    const float tout = (-b + s) / a;
+    return tin <= tout && tout >= 0.f && tin <= r.max_t;
+}
+
+// the ray against body b's own shape (after the candidate test): tin alone
+__device__ __forceinline__ bool q_ray_body(bool circle, const QRay& r, float4 m, float4 f, float2 h, float& tin)
+{
+    if (circle) { float rx, ry; return q_ray_circle(r, m, h.x, tin, rx, ry); }
+    QRayBox rb;
+    const bool hit = q_ray_box(r, m, f, h, rb);
+    tin = rb.tin;
+    return hit;
 }
 
 // ---- the shape predicates (include/phyx_amd.h: oriented boxes and box casts) -------------------------------------------------------------
@@ -238,15 +278,24 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
             const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
             const QRay r = q_load_ray(rays, q);
             const float4 m = w.s.mpos[b], f = w.frame[b];
-            QRayBox rb;
-            (void)q_ray_box(r, m, f, w.size[b], rb);
-            const float t = rb.tin > 0.f ? rb.tin : 0.f;
-            h.body = b; h.t = t;
-            if (!(rb.tin < 0.f)) {
-                const float nx = rb.xenter ? f.x : f.z, ny = rb.xenter ? f.y : f.w;
-                const bool flip = (rb.xenter ? rb.dxp : rb.dyp) > 0.f;
-                h.normal.x = flip ? -nx : nx; h.normal.y = flip ? -ny : ny;
+            const float2 sz = w.size[b];
+            float t;
+            if (q_circle(w.kinds, b)) {
+                float tin, rx, ry;
+                (void)q_ray_circle(r, m, sz.x, tin, rx, ry);
+                t = tin > 0.f ? tin : 0.f;
+                if (!(tin < 0.f)) { h.normal.x = (rx + tin * r.dx) / sz.x; h.normal.y = (ry + tin * r.dy) / sz.x; }
+            } else {
+                QRayBox rb;
+                (void)q_ray_box(r, m, f, sz, rb);
+                t = rb.tin > 0.f ? rb.tin : 0.f;
+                if (!(rb.tin < 0.f)) {
+                    const float nx = rb.xenter ? f.x : f.z, ny = rb.xenter ? f.y : f.w;
+                    const bool flip = (rb.xenter ? rb.dxp : rb.dyp) > 0.f;
+                    h.normal.x = flip ? -nx : nx; h.normal.y = flip ? -ny : ny;
+                }
             }
+            h.body = b; h.t = t;
             h.point.x = r.ox + t * r.dx;
             h.point.y = r.oy + t * r.dy;
         }
@@ -300,9 +349,10 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
         float2 h = make_float2(0.f, 0.f);
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
         const bool any = live && !(skip && q_static(m, w.sleep, i));
+        const bool round = live && q_circle(w.kinds, i);
         for (int q = 0; q < nq; ++q) {
             const float2 p = qp[q];
-            const bool hit = any && qok[q] && q_point_in_box(a, m, f, h, p.x, p.y);
+            const bool hit = any && qok[q] && q_point_in_body(round, a, m, f, h, p.x, p.y);
             const unsigned long long mask = __ballot(hit);
             if (mask && (int)(threadIdx.x & 63) == __builtin_ctzll(mask)) atomicMin(&out[base_q + q], (unsigned)i);      // (the lowest lane holds the lowest body)
         }
@@ -340,6 +390,7 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
         float2 h = make_float2(0.f, 0.f);
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
         const bool any = live && !(skip && q_static(m, w.sleep, i));
+        const bool round = !CAST && live && q_circle(w.kinds, i);
         for (int q = 0; q < nq; ++q) {
             bool hit;
             float tin;
@@ -350,9 +401,9 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
                 tin = hit ? cb.tin : 0.f;
             } else {
                 const QRay r = qr[q];
-                QRayBox rb;
-                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_box(r, m, f, h, rb);
-                tin = hit ? rb.tin : 0.f;
+                float t0 = 0.f;
+                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_body(round, r, m, f, h, t0);
+                tin = hit ? t0 : 0.f;
             }
             if (!__ballot(hit)) continue;
             const unsigned long long k = q_wave_min64(hit ? q_ray_key(tin, i) : ~0ull);
@@ -566,11 +617,11 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                         b = (int)t.perm[c];
                         const float4 a = w.aabb[b], m = w.s.mpos[b];
                         if (!(skip && q_static(m, w.sleep, b))) {
-                            if (KIND == QK_POINT) hit = q_point_in_box(a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
+                            if (KIND == QK_POINT) hit = q_point_in_body(q_circle(w.kinds, b), a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
                             else if (KIND == QK_RAY) {
-                                QRayBox rb;
-                                hit = q_ray_aabb(r, a) && q_ray_box(r, m, w.frame[b], w.size[b], rb);
-                                if (hit) { const unsigned long long k = q_ray_key(rb.tin, b); best_key = k < best_key ? k : best_key; }
+                                float t0 = 0.f;
+                                hit = q_ray_aabb(r, a) && q_ray_body(q_circle(w.kinds, b), r, m, w.frame[b], w.size[b], t0);
+                                if (hit) { const unsigned long long k = q_ray_key(t0, b); best_key = k < best_key ? k : best_key; }
                             } else if (KIND == QK_CAST) {
                                 QCastBox cb;
                                 hit = q_cast_aabb(cs, ce, a) && q_cast_box(cs, m, w.frame[b], w.size[b], cb);

@@ -73,14 +73,32 @@ public:
     }
     const uint2* exclusions() const { return exclusions_.p; }
     int exclusion_count() const { return exclusion_count_; }
-    int blob_bytes(size_t* bytes) const;
+    // the shapes' kinds (SHAPES) ride the same way: one word per body of a world whose shape column was active, none otherwise
+    int reserve_shapes(int n, hipStream_t stream) { return n ? shapes_.reserve_keep((size_t)n, (size_t)shape_count_, stream) : PHX_OK; }
+    int save_shapes(const uint32_t* d_src, int count, hipStream_t stream)
+    {
+        shape_count_ = count;
+        if (!count) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(shapes_.p, d_src, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
+        return PHX_OK;
+    }
+    int load_shapes(uint32_t* d_dst, hipStream_t stream)                    // (queued behind Snapshot::load on the same stream)
+    {
+        if (!shape_count_) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(d_dst, shapes_.p, (size_t)shape_count_ * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(loaded_, stream));                           // (the next save into this snapshot waits for this copy too)
+        return PHX_OK;
+    }
+    int shape_count() const { return shape_count_; }
+    int blob_bytes(size_t* bytes);
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
 
 private:
     int settle();                        // the host waits for the queued save and loads (export, import, destroy)
     int refuse_empty(const char* what) const;
-    int refuse_pins(const char* what) const;      // the blob is layout version 1 and holds no pins, no links, no angles, no sliders and no exclusions
+    int refuse_pins(const char* what);            // the blob is layout version 1 and holds no pins, no links, no angles, no sliders, no exclusions and no circles
     template <class P> struct Riders {            // a list of records beside the blob
         using record = P;
         DevBuf<P> buf; int count = 0;
@@ -94,6 +112,7 @@ private:
     std::tuple<Riders<phx_pin>, Riders<phx_link>, Riders<phx_angle>, Riders<phx_slider>> riders_;      // (the kinds in the pass's order)
     template <class P> Riders<P>& riders() { return std::get<Riders<P>>(riders_); }
     DevBuf<uint2> exclusions_; int exclusion_count_ = 0;
+    DevBuf<uint32_t> shapes_; int shape_count_ = 0;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

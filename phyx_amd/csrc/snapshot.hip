@@ -44,13 +44,21 @@ int Snapshot::refuse_empty(const char* what) const
     return PHX_ERR_STATE;
 }
 
-int Snapshot::refuse_pins(const char* what) const
+int Snapshot::refuse_pins(const char* what)
 {
     int count = 0;                                                          // the first kind that has riders names the refusal
     const char* plural = nullptr;
     auto look = [&](const auto& r) { if (!count && r.count) { count = r.count; plural = UnitKind<typename std::decay_t<decltype(r)>::record>::plural; } };
     std::apply([&](const auto&... r) { (look(r), ...); }, riders_);
     if (!count && exclusion_count_) { count = exclusion_count_; plural = "collision exclusions"; }
+    if (!count && shape_count_) {                                           // the saved kinds: refused while one of them is not a box
+        PHX_TRY(use_device(device_));
+        PHX_TRY(settle());
+        std::vector<uint32_t> kinds((size_t)shape_count_);
+        PHX_HIP(hipMemcpy(kinds.data(), shapes_.p, kinds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (const uint32_t k : kinds) count += k != (uint32_t)PHX_SHAPE_BOX;
+        plural = "circles";
+    }
     if (!count) return PHX_OK;
     set_error("%s: the snapshot holds %d %s, which the blob (layout version 1) does not carry", what, count, plural);
     return PHX_ERR_STATE;
@@ -119,7 +127,7 @@ int Snapshot::load(const SnapshotWorld& w, hipStream_t stream)
     return PHX_OK;
 }
 
-int Snapshot::blob_bytes(size_t* bytes) const
+int Snapshot::blob_bytes(size_t* bytes)
 {
     PHX_TRY(refuse_empty("phx_snapshot_blob_bytes"));
     PHX_TRY(refuse_pins("phx_snapshot_blob_bytes"));
@@ -155,6 +163,7 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true;
     std::apply([](auto&... r) { ((r.count = 0), ...); }, riders_);
     exclusion_count_ = 0;
+    shape_count_ = 0;
     return PHX_OK;
 }
 

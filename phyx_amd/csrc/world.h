@@ -269,6 +269,9 @@ public:
     // body flags (phx_world_set_body_flags / get_body_flags): between steps; the joints of a sensor go or come at the next step's refresh
     int set_body_flags(const int32_t* bodies, const uint32_t* flags, int count);
     int get_body_flags(uint32_t* out, int cap);
+    // shapes (phx_world_set_shapes / get_shapes): between steps; the kind and the half extents of a body, the AABB recomputed
+    int set_shapes(const int32_t* bodies, const phx_shape* shapes, int count);
+    int get_shapes(phx_shape* out, int cap);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
     // units: pins, links, angles and sliders, `P` = phx_pin, phx_link, phx_angle or phx_slider (phx_world_add_pins ... phx_world_get_sliders, phx_world_get_pin_schedule): between
     // steps; solved at the end of pre_solve (pins.h)
@@ -321,7 +324,7 @@ private:
     int sync_bodies_to_device();
     int refresh_records();               // resident arrays -> the 128-byte records (getters)
     WorldBodies resident() const { return bodies_.view(); }
-    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); return w; }      // (to a query a sleeper is not static)
+    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); w.kinds = shapes_.ptr(); return w; }      // (to a query a sleeper is not static, and a circle is a disc)
     bool host_staged() const { return bodies_dirty_ || !bodies_.records.p; }      // the host-staged records are the world
     int restage_on_host();               // ... again, after the device copy was: records and tables come down
     int refuse_mid_step(const char* what) const;      // PHX_ERR_STATE between pre_solve / step_begin and finish_step / step_end
@@ -335,6 +338,7 @@ private:
     int fresh_manifolds_ = 0;           // pairs UpdatePairs found this step: their manifolds are created by UpdateManifolds' kernel
     int manifolds_updated_ = 0;         // manifolds [0, this) were updated during update_pairs' round trip (update_manifolds() does the rest)
     int update_manifolds();
+    void queue_update_manifolds(int first, int nm_old, const uint2* new_pairs, const MailRide& ride);
     int finish_pack(int dead, int dropped);
     int pack_manifolds();
     int refresh_contact_joints();
@@ -436,6 +440,9 @@ private:
     BodyTable<FlagsColumn> flags_col_;
     // ... and the sleep states (sleep.h): active exactly while sleeping is enabled
     BodyTable<SleepColumn> sleep_col_;
+    // ... and the shapes' kinds (include/phyx_amd.h SHAPES): active once some set_shapes call named a circle; an active table picks
+    // UpdateManifolds' BodyShapes instantiation and hands the kinds to the queries
+    BodyTable<ShapeColumn> shapes_;
     DeviceSleep sleep_;
     bool sleep_count_pending_ = false;   // the pass or a wake may have changed the static set: the device's count has not been looked at yet
     DevBuf<phx_sleep_state> sleep_out_;
@@ -447,7 +454,7 @@ private:
     template <class P> int wake_units(const int32_t* which, int count);      // both bodies of the listed units
     void take_sleep_count(unsigned changed);      // what set_inverse_masses does when the static set changed
     int settle_sleep_count();            // ... by a readback of its own, where no step's count readback has brought it yet
-    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); return f(sleep_col_); }
+    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); PHX_TRY(f(sleep_col_)); return f(shapes_); }
     // the three setters' skeleton: `rule(k)` is the call's own check of entry k
     template <class Column, class Rule>
     int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
@@ -462,8 +469,8 @@ private:
     int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2);
     // an edit of Fields::width floats per listed unit (already checked): staged for the scatter kernel when the list is on the device
     template <class P, class Fields> int set_unit_fields(const int32_t* which, const float* values, int count);
-    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr()}; }
-    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr()}; }
+    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr(), shapes_.ptr()}; }
+    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr(), shapes_.spare_ptr()}; }
 };
 
 } // namespace phx

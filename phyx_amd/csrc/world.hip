@@ -200,6 +200,17 @@ int World::scratch_for(int n)
     return PHX_OK;
 }
 
+// UpdateManifolds' kernel over manifolds [first, nm): the box/box instantiation, or the one that reads the kinds while the shape column
+// is active (a null column pointer picks the plain instantiation: the kernel of a world that never made a circle)
+void World::queue_update_manifolds(int first, int nm_old, const uint2* new_pairs, const MailRide& ride)
+{
+    const uint32_t* const kinds = shapes_.ptr();
+    if (kinds) hipLaunchKernelGGL(k_update_manifolds<BodyShapes>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
+                                  reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, BodyShapes{kinds});
+    else hipLaunchKernelGGL(k_update_manifolds<AllBoxes>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
+                            reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, AllBoxes{});
+}
+
 int World::update_pairs()                                                   // ref: Collider.cpp:251-345
 {
     const DeviceBroadphase::StepPrologue prologue{gravity, step_dt_, counters_.p, bodies_.vel.p, bodies_.mpos.p, accel_pending_ ? (const float4*)accel_.p : nullptr};
@@ -213,8 +224,7 @@ int World::update_pairs()                                                   // r
         if (!nm) return PHX_OK;
         PHX_TRY(scratch_for(nm));
         PHX_TRY(pack_flags_.reserve((size_t)nm + 2));
-        hipLaunchKernelGGL(k_update_manifolds, dim3(wgrid(nm)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p,
-                           pack_flags_.p, reinterpret_cast<int*>(counters_.p + 3), nm, (const uint2*)nullptr, 0, counters_.p + 2, old_ride_ ? *old_ride_ : MailRide{});
+        queue_update_manifolds(0, nm, nullptr, old_ride_ ? *old_ride_ : MailRide{});
         PHX_HIP(hipGetLastError());
         manifolds_updated_ = nm;
         return PHX_OK;
@@ -247,8 +257,7 @@ int World::update_manifolds()                                               // r
     if (nm <= first) { fresh_manifolds_ = 0; return PHX_OK; }
     PHX_TRY(scratch_for(nm));
     PHX_TRY(pack_flags_.reserve_keep((size_t)nm + 2, (size_t)first, stream_));      // (a pending pack keeps its scan in it until refresh_contact_joints settles it)
-    hipLaunchKernelGGL(k_update_manifolds, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p,
-                       pack_flags_.p, reinterpret_cast<int*>(counters_.p + 3), nm - fresh_manifolds_, broadphase_.new_pairs_device(), first, counters_.p + 2, MailRide{});
+    queue_update_manifolds(first, nm - fresh_manifolds_, broadphase_.new_pairs_device(), MailRide{});
     fresh_manifolds_ = 0;
     PHX_HIP(hipGetLastError());
     return PHX_OK;

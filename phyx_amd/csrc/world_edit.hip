@@ -1,5 +1,5 @@
 // world_edit.hip — World (world.h): what changes bodies and their columns between steps: edits and gathers, removal, spawn, the optional
-// columns (collision filters, materials, body flags), collision exclusions, and the contact cache's compaction behind them.
+// columns (collision filters, materials, body flags, shapes), collision exclusions, and the contact cache's compaction behind them.
 #include "world.h"
 #include "device_scan.h"
 
@@ -484,5 +484,65 @@ int World::set_body_flags(const int32_t* bodies, const uint32_t* flags, int coun
     }, true);
 }
 int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_get_body_flags", flags_col_, out, cap); }
+
+// ---- shapes -------------------------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h SHAPES.  The call is an edit of geom_size (the records and the resident size[], the AABB recomputed by
+// set_poses' geom_aabb) and, once some call has named a circle, a write of the kinds' column.  A call that names boxes only in a world
+// without the column is the size edit alone: it activates nothing.  Inverse masses, manifolds, joints and the schedule stay.
+int World::set_shapes(const int32_t* bodies, const phx_shape* shapes, int count)
+{
+    static const char* const what = "phx_world_set_shapes";
+    PHX_TRY(refuse_sharded(what, "shapes"));
+    PHX_TRY(check_batch(what, bodies, shapes, count, true));
+    bool circle = false;
+    for (int k = 0; k < count; ++k) {                                       // (NaN fails the comparisons)
+        const phx_shape& s = shapes[k];
+        if (s.kind != PHX_SHAPE_BOX && s.kind != PHX_SHAPE_CIRCLE) { set_error("%s: kind %d of body %d is neither PHX_SHAPE_BOX nor PHX_SHAPE_CIRCLE", what, s.kind, bodies[k]); return PHX_ERR_INVALID; }
+        if (!(std::isfinite(s.hx) && std::isfinite(s.hy) && s.hx > 0.f && s.hy > 0.f)) { set_error("%s: the size {%g, %g} of body %d is not finite and positive", what, (double)s.hx, (double)s.hy, bodies[k]); return PHX_ERR_INVALID; }
+        if (s.kind == PHX_SHAPE_CIRCLE && s.hy != s.hx) { set_error("%s: body %d is a circle and hy %g is not its radius hx %g", what, bodies[k], (double)s.hy, (double)s.hx); return PHX_ERR_INVALID; }
+        circle = circle || s.kind == PHX_SHAPE_CIRCLE;
+    }
+    if (!count) return PHX_OK;
+    PHX_TRY(wake_named(bodies, count));
+    const int n = nb();
+    const bool kinds = circle || shapes_.active;
+    if (host_staged()) {                                    // the host-staged records are the world: write into them
+        for (int k = 0; k < count; ++k) {
+            phx_rigid_body& b = host_bodies_[(size_t)bodies[k]];
+            b.geom_size.x = shapes[k].hx; b.geom_size.y = shapes[k].hy;
+            update_geom(b);
+        }
+        if (kinds) shapes_.set_host(bodies, shapes, count, n);              // (the table goes up with the bodies)
+        return PHX_OK;
+    }
+    PHX_TRY(settle_and_upload());                                           // (an unverified solve is settled before the geometry changes)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_.indexed(bodies, reinterpret_cast<const float*>(shapes), count, (int)(sizeof(phx_shape) / sizeof(float)), stream_, &d_bodies, &d_values));
+    if (kinds) PHX_TRY(shapes_.set_device(d_bodies, d_values, count, n, stream_));
+    hipLaunchKernelGGL(k_set_shapes, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, reinterpret_cast<const phx_shape*>(d_values), count, resident(), bodies_.records.p);
+    PHX_HIP(hipGetLastError());
+    ++geom_epoch_;                                                          // (the query index was built on the old AABBs)
+    return PHX_OK;
+}
+
+// every body's {kind, geom_size}: the kinds from the column (boxes while there is none), the sizes from wherever the bodies are
+int World::get_shapes(phx_shape* out, int cap)
+{
+    static const char* const what = "phx_world_get_shapes";
+    const int n = nb();
+    if (cap < n) { set_error("%s: room for %d bodies, the world has %d", what, cap, n); return PHX_ERR_CAPACITY; }
+    if (!n) return PHX_OK;
+    PHX_TRY(shapes_.visit(n, host_staged(), device_, rb_, stream_, [out](int i, const uint32_t& kind) { out[i].kind = (int32_t)kind; }));
+    if (host_staged()) {
+        for (int i = 0; i < n; ++i) { out[i].hx = host_bodies_[(size_t)i].geom_size.x; out[i].hy = host_bodies_[(size_t)i].geom_size.y; }
+        return PHX_OK;
+    }
+    PHX_TRY(use_device(device_));
+    std::vector<float2> sizes((size_t)n);
+    PHX_TRY(rb_.add(sizes.data(), bodies_.size.p, (size_t)n * sizeof(float2), stream_));
+    PHX_TRY(rb_.wait(stream_));
+    for (int i = 0; i < n; ++i) { out[i].hx = sizes[(size_t)i].x; out[i].hy = sizes[(size_t)i].y; }
+    return PHX_OK;
+}
 
 } // namespace phx

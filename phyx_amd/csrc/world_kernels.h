@@ -143,8 +143,36 @@ struct FlagsColumn {                   // include/phyx_amd.h BODY FLAGS / SENSOR
     static api shown(const value& v) { return v; }
     static bool is_initial(const value& v) { return v == 0u; }
 };
-static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float) && sizeof(uint32_t) == sizeof(float),
-              "a batch is staged as 4-byte words");
+struct ShapeColumn {                   // include/phyx_amd.h SHAPES; the rule: narrowphase.h update_manifold, query_kernels.h
+    using value = uint32_t;            // PHX_SHAPE_BOX or PHX_SHAPE_CIRCLE (the size lives where it always did: the records and size[])
+    using api = phx_shape;
+    static constexpr const char* plural = "circles";
+    static __host__ __device__ value initial() { return (uint32_t)PHX_SHAPE_BOX; }
+    static __host__ __device__ value stored(const api& s) { return (uint32_t)s.kind; }
+    static bool is_initial(const value& v) { return v == (uint32_t)PHX_SHAPE_BOX; }
+    // (no `shown`: the getter joins the kind with the size, World::get_shapes)
+};
+static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float) && sizeof(uint32_t) == sizeof(float) &&
+              sizeof(phx_shape) == 3 * sizeof(float), "a batch is staged as 4-byte words");
+
+// geom_size = {hx, hy} of the listed bodies (phx_world_set_shapes), then UpdateGeom's AABB as k_set_poses computes it: the resident size[]
+// and aabb[], and the records, whose geom_size is what the upload left there (world_record does not refresh it).  The kinds go into
+// their column by k_scatter_column<ShapeColumn>, where the column exists.
+static __global__ void __launch_bounds__(256) k_set_shapes(const int* __restrict__ idx, const phx_shape* __restrict__ v, int count, WorldBodies w,
+                                                           phx_rigid_body* __restrict__ records)
+{
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < count; k += gridDim.x * blockDim.x) {
+        const int i = idx[k];
+        const float4 m = w.s.mpos[i], f = w.frame[i];
+        const V2 size = v2(v[k].hx, v[k].hy);
+        float4 box;
+        geom_aabb(v2(m.z, m.w), v2(f.x, f.y), v2(f.z, f.w), size, box.x, box.y, box.z, box.w);
+        w.size[i] = make_float2(size.x, size.y);
+        w.aabb[i] = box;
+        records[i].geom_size = pv(size);
+        records[i].aabb_min.x = box.x; records[i].aabb_min.y = box.y; records[i].aabb_max.x = box.z; records[i].aabb_max.y = box.w;
+    }
+}
 
 // a column that becomes active is filled with its default, then the staged batch {indices | values} is scattered into it
 template <class Column>
@@ -160,7 +188,7 @@ static __global__ void __launch_bounds__(256) k_scatter_column(const int* __rest
 }
 
 // what the spawn and the removal move beside the records and the resident arrays: the pending accelerations (consumed by the next
-// IntegrateVelocity) and the columns above.  Null = absent.  A new column is one member here, one line in each of the two kernels, and its table in the World's
+// IntegrateVelocity) and the columns above.  Null = absent.  A new column (the shapes' kinds were the last) is one member here, one line in each of the two kernels, and its table in the World's
 // each_table / columns() / spare_columns() (world.h), which is what fills the member.
 struct BodyColumns {
     float4* accel;
@@ -168,6 +196,7 @@ struct BodyColumns {
     float2* materials;
     uint32_t* flags;
     SleepCell* sleep;
+    uint32_t* shapes;
 };
 
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
@@ -201,6 +230,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         if (cols.materials) cols.materials[i] = MaterialColumn::initial();
         if (cols.flags) cols.flags[i] = FlagsColumn::initial();
         if (cols.sleep) cols.sleep[i] = SleepColumn::initial();      // (awake, timer 0)
+        if (cols.shapes) cols.shapes[i] = ShapeColumn::initial();    // (a box)
     }
 }
 
@@ -279,12 +309,25 @@ static __global__ void __launch_bounds__(256) k_x_extent(WorldBodies w, int n, u
     if ((threadIdx.x & 63) == 0) { if (lo != 0xFFFFFFFFu) atomicMin(&out[0], lo); if (hi) atomicMax(&out[1], hi); }
 }
 
-__device__ __forceinline__ NpBody np_load(const WorldBodies& w, int i)
+// The bodies' kinds (include/phyx_amd.h SHAPES) are a parameter of UpdateManifolds' kernel: AllBoxes (a world without an active shape
+// column) gives the constant PHX_SHAPE_BOX, so update_manifold's dispatch folds away and the kernel is the box/box code it always was;
+// BodyShapes reads one 4-byte word per body.
+struct AllBoxes {
+    __device__ unsigned operator()(int) const { return (unsigned)PHX_SHAPE_BOX; }
+};
+struct BodyShapes {
+    const uint32_t* kind;              // per body (ShapeColumn)
+    __device__ unsigned operator()(int i) const { return kind[i]; }
+};
+
+template <class Shapes>
+__device__ __forceinline__ NpBody np_load(const WorldBodies& w, int i, const Shapes& shapes)
 {
     const float4 m = w.s.mpos[i], f = w.frame[i];
     const float2 sz = w.size[i];
     NpBody b;
     b.pos = v2(m.z, m.w); b.xv = v2(f.x, f.y); b.yv = v2(f.z, f.w); b.size = v2(sz.x, sz.y);
+    b.kind = shapes(i);
     return b;
 }
 
@@ -292,10 +335,11 @@ __device__ __forceinline__ NpBody np_load(const WorldBodies& w, int i)
 // Manifolds [nm_old, nm) are the pairs UpdatePairs has just found (ref: Collider.cpp:313-316 — Manifold(index_i, index_j,
 // manifolds.size * kMaxContactPoints), contact slots blank): they are created here, in the lane that updates them, instead of
 // by an append kernel of their own in front of this one.
+template <class Shapes>
 static __global__ void __launch_bounds__(256) k_update_manifolds(phx_manifold* __restrict__ manifolds, int nm, WorldBodies bodies,
                                                                  phx_contact_point* __restrict__ cps, unsigned* __restrict__ dead, int* __restrict__ dropped,
                                                                  int nm_old, const uint2* __restrict__ new_pairs, int first, unsigned* __restrict__ dead_count,
-                                                                 MailRide ride)
+                                                                 MailRide ride, Shapes shapes)
 {
     // (`ride`: the broadphase's new-pair count goes to the host with this launch's first workgroup — common.h post_mail_block)
     if (ride.args.count && blockIdx.x == 0) post_mail_block(ride.args, ride.host_words, ride.host_seq);
@@ -314,7 +358,7 @@ static __global__ void __launch_bounds__(256) k_update_manifolds(phx_manifold* _
             cps[2 * i] = blank; cps[2 * i + 1] = blank;
         } else m = manifolds[i];
         // (two bodies = 2 x 40 bytes of the resident arrays; the 128-byte records cost 2 x 128 for the same fields)
-        const NpBody b1 = np_load(bodies, m.body1), b2 = np_load(bodies, m.body2);
+        const NpBody b1 = np_load(bodies, m.body1, shapes), b2 = np_load(bodies, m.body2, shapes);
         if (update_manifold(m, b1, b2, cps + m.point_index)) atomicAdd(dropped, 1);
         manifolds[i] = m;
         const bool gone = m.point_count == 0 && !aabb_intersects(bodies.aabb[m.body1], bodies.aabb[m.body2]);
@@ -585,6 +629,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
         if (cols.materials) out_cols.materials[to] = cols.materials[i];
         if (cols.flags) out_cols.flags[to] = cols.flags[i];
         if (cols.sleep) out_cols.sleep[to] = cols.sleep[i];
+        if (cols.shapes) out_cols.shapes[to] = cols.shapes[i];
         if (out_cols.accel) {
             out_cols.accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;

@@ -115,9 +115,12 @@ int World::save(Snapshot& s)
     PHX_TRY(exclusions_.sync(nb(), stream_));
     PHX_TRY(pins_.each_list([&](auto& l) { return s.reserve_units<typename std::decay_t<decltype(l)>::record>(l.count(), l.limited(), stream_); }));
     PHX_TRY(s.reserve_exclusions(exclusions_.count(), stream_));
+    const int kinds = shapes_.active ? nb() : 0;                            // the shapes' kinds ride beside the blob too (the sizes are in the records)
+    PHX_TRY(s.reserve_shapes(kinds, stream_));
     PHX_TRY(s.save(v, stream_));
     PHX_TRY(pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); }));
-    return s.save_exclusions(exclusions_.device_pairs(), exclusions_.count(), stream_);
+    PHX_TRY(s.save_exclusions(exclusions_.device_pairs(), exclusions_.count(), stream_));
+    return s.save_shapes(shapes_.dev.p, kinds, stream_);
 }
 
 int World::load(Snapshot& s)
@@ -138,8 +141,11 @@ int World::load(Snapshot& s)
     if (c.columns & SNAP_HAS_FILTERS) PHX_TRY(filters_.dev.reserve(std::max<size_t>(n, 1)));
     if (c.columns & SNAP_HAS_MATERIALS) PHX_TRY(materials_.dev.reserve(std::max<size_t>(n, 1)));
     if (c.columns & SNAP_HAS_FLAGS) PHX_TRY(flags_col_.dev.reserve(std::max<size_t>(n, 1)));
+    if (s.shape_count()) PHX_TRY(shapes_.dev.reserve(std::max<size_t>(n, 1)));
     PHX_TRY(contacts_.reserve_baseline((size_t)c.baseline));
     PHX_TRY(s.load(snapshot_view(), stream_));
+    PHX_TRY(s.load_shapes(shapes_.dev.p, stream_));                         // phx_world_set_shapes of the saved kinds, if that column was active in s (the sizes came with the records)
+    shapes_.active = s.shape_count() != 0;
     // the device copy is the world (host-staged bodies and tables are dropped with the rest of the old world)
     host_bodies_.resize(n);                                                 // (only its size counts while the device copy is the world)
     bodies_dirty_ = false;

@@ -1,0 +1,267 @@
+"""The specification of round bodies (include/phyx_amd.h, SHAPES and the circle rules of QUERIES), in numpy float32: the definition the
+device matches byte for byte (tests/test_circles_gpu.py) and the host instantiation of the C++ the device kernel calls is held to
+(phx_debug_update_manifold, tests/test_circles_cpu.py).  tests/circle_reference.py is its float64 judge.
+
+Every operation is a float32 one, rounded on its own, in the header's order: numpy float32 scalars fuse nothing, and sqrt and / are
+correctly rounded.  dot(a, b) = a.x*b.x + a.y*b.y.
+
+  update_manifold   UpdateManifolds of one pair at least one of whose bodies is a circle: the circle/circle or circle/box routine, the
+                    reference's MergeCollision (ref: Collider.cpp:58-92) and the two-slot store (ref: Collider.cpp:211-245)
+  spawn / remove / set_state / valid    what the state-changing calls do to the per-body kinds, as material_spec has them
+  query_points / raycast                query_spec's with the disc predicates for the bodies that are circles"""
+import numpy as np
+
+from phyx_amd.api import contact_point_dtype, ray_hit_dtype, shape_dtype
+import query_spec as qs
+
+F = np.float32
+BOX, CIRCLE = 0, 1
+MERGE_DISTANCE = F(2.0)
+FLT_MAX = F(3.402823466e+38)
+
+
+# ---- the per-body kinds -----------------------------------------------------------------------------------------------------------------
+def boxes(n):
+    return np.zeros(n, dtype=np.int32)
+
+
+def spawn(kinds, count):
+    """add_body / add_bodies: new bodies are boxes."""
+    return np.concatenate([np.asarray(kinds, dtype=np.int32), boxes(count)])
+
+
+def remove(kinds, keep):
+    """remove_bodies / remove_outside: the kept bodies' kinds move with them, through new[] (kept order)."""
+    return np.asarray(kinds, dtype=np.int32)[np.asarray(keep, dtype=bool)].copy()
+
+
+def set_state(n):
+    """phx_world_set_state: every body is a box again (the sizes are in the records)."""
+    return boxes(n)
+
+
+def valid(kind, hx, hy):
+    """What phx_world_set_shapes accepts: kind 0 or 1, hx and hy finite and > 0, hy == hx for a circle."""
+    kind = np.asarray(kind)
+    hx, hy = np.asarray(hx, dtype=F), np.asarray(hy, dtype=F)
+    with np.errstate(invalid="ignore"):
+        sizes = np.isfinite(hx) & np.isfinite(hy) & (hx > 0) & (hy > 0)
+        return ((kind == BOX) | (kind == CIRCLE)) & sizes & ((kind != CIRCLE) | (hy == hx))
+
+
+def shapes(bodies, kinds):
+    """What phx_world_get_shapes returns for the records `bodies` with the kinds `kinds`."""
+    s = np.zeros(len(bodies), dtype=shape_dtype)
+    s["kind"], s["hx"], s["hy"] = kinds, bodies["geom_size"]["x"], bodies["geom_size"]["y"]
+    return s
+
+
+def circle_masses(r):
+    """{invMass, invInertia} of a circle on AddBody's scale: mass = 1e-5f * 0.785398f * r * r, inertia = mass * 1.5f * r * r."""
+    r = F(r)
+    mass = F(1e-5) * F(0.785398) * r * r
+    inertia = mass * F(1.5) * r * r
+    return F(1.0) / mass, F(1.0) / inertia
+
+
+# ---- the narrowphase ----------------------------------------------------------------------------------------------------------------------
+class Body:
+    """What the narrowphase reads of a 128-byte record: pos, xv, yv, size = geom_size, as float32 scalars."""
+
+    def __init__(self, rec, kind):
+        self.px, self.py = F(rec["pos"]["x"]), F(rec["pos"]["y"])
+        self.xvx, self.xvy = F(rec["xv"]["x"]), F(rec["xv"]["y"])
+        self.yvx, self.yvy = F(rec["yv"]["x"]), F(rec["yv"]["y"])
+        self.hx, self.hy = F(rec["geom_size"]["x"]), F(rec["geom_size"]["y"])
+        self.kind = int(kind)
+
+
+def _dot(ax, ay, bx, by):
+    return ax * bx + ay * by
+
+
+def circle_circle(b1, b2):
+    """None, or (p1, p2, n): the point on body 1, the point on body 2, the normal from body 2 towards body 1."""
+    with np.errstate(all="ignore"):
+        r1, r2 = b1.hx, b2.hx
+        dx, dy = b1.px - b2.px, b1.py - b2.py
+        l2 = _dot(dx, dy, dx, dy)
+        R = r1 + r2
+        if l2 > R * R:
+            return None
+        l = np.sqrt(l2)
+        nx, ny = (dx / l, dy / l) if l > 0 else (F(1), F(0))
+        p1 = (b1.px - nx * r1, b1.py - ny * r1)
+        p2 = (b2.px + nx * r2, b2.py + ny * r2)
+        return p1, p2, (nx, ny)
+
+
+def circle_box(c, b, circle_first):
+    """Circle c against box b.  None, or (p1, p2, n) in the manifold's body order (`circle_first`: the circle is body 1)."""
+    with np.errstate(all="ignore"):
+        r = c.hx
+        cx, cy = c.px - b.px, c.py - b.py
+        u = _dot(cx, cy, b.xvx, b.xvy)
+        v = _dot(cx, cy, b.yvx, b.yvy)
+        qu = -b.hx if u < -b.hx else (b.hx if u > b.hx else u)
+        qv = -b.hy if v < -b.hy else (b.hy if v > b.hy else v)
+        if qu == u and qv == v:
+            pu = b.hx - np.abs(u)
+            pv = b.hy - np.abs(v)
+            if pu <= pv:
+                Nx, Ny = (-b.xvx, -b.xvy) if u < 0 else (b.xvx, b.xvy)
+                qu = -b.hx if u < 0 else b.hx
+            else:
+                Nx, Ny = (-b.yvx, -b.yvy) if v < 0 else (b.yvx, b.yvy)
+                qv = -b.hy if v < 0 else b.hy
+        else:
+            ex, ey = u - qu, v - qv
+            l2 = _dot(ex, ey, ex, ey)
+            if l2 > r * r:
+                return None
+            l = np.sqrt(l2)
+            sx, sy = ex / l, ey / l
+            Nx, Ny = b.xvx * sx + b.yvx * sy, b.xvy * sx + b.yvy * sy
+        on_box = ((b.px + b.xvx * qu) + b.yvx * qv, (b.py + b.xvy * qu) + b.yvy * qv)
+        on_circle = (c.px - Nx * r, c.py - Ny * r)
+        if circle_first:
+            return on_circle, on_box, (Nx, Ny)
+        return on_box, on_circle, (-Nx, -Ny)
+
+
+def contact(b1, b2):
+    """The new point of a pair with at least one circle, or None."""
+    if b1.kind == CIRCLE and b2.kind == CIRCLE:
+        return circle_circle(b1, b2)
+    if b1.kind == CIRCLE:
+        return circle_box(b1, b2, True)
+    if b2.kind == CIRCLE:
+        return circle_box(b2, b1, False)
+    raise ValueError("circle_spec states the pairs with a circle; box/box is the reference's narrowphase")
+
+
+def _sqlen(ax, ay):
+    return ax * ax + ay * ay
+
+
+def update_manifold(rec1, kind1, rec2, kind2, point_count, pts):
+    """UpdateManifolds of one pair: the cached slots pts[0 .. point_count) lose their merged / newly-created marks, the routine's point
+    (if any) is merged into the closest cached point within the merge distance or becomes a new one, and the merged points are stored
+    from slot 0 on.  Returns (point_count, pts) with pts a new array of two contact_point_dtype records; slots that are not written
+    keep their bytes."""
+    b1, b2 = Body(rec1, kind1), Body(rec2, kind2)
+    work = []
+    for k in range(int(point_count)):
+        q = pts[k]
+        work.append({"d1": (F(q["delta1"]["x"]), F(q["delta1"]["y"])), "d2": (F(q["delta2"]["x"]), F(q["delta2"]["y"])),
+                     "n": (F(q["normal"]["x"]), F(q["normal"]["y"])), "merged": 0, "new": 0, "pad": q["pad"].copy(), "si": int(q["solver_index"])})
+    hit = contact(b1, b2)
+    if hit is not None:
+        with np.errstate(all="ignore"):
+            p1, p2, n = hit
+            d1 = (p1[0] - b1.px, p1[1] - b1.py)
+            d2 = (p2[0] - b2.px, p2[1] - b2.py)
+            closest, best = -1, FLT_MAX
+            for i, q in enumerate(work):
+                s1 = _sqlen(q["d1"][0] - d1[0], q["d1"][1] - d1[1])
+                s2 = _sqlen(q["d2"][0] - d2[0], q["d2"][1] - d2[1])
+                if s1 > MERGE_DISTANCE * MERGE_DISTANCE and s2 > MERGE_DISTANCE * MERGE_DISTANCE:
+                    continue
+                depth = _sqlen(d1[0] - q["d1"][0], d1[1] - q["d1"][1]) + _sqlen(d2[0] - q["d2"][0], d2[1] - q["d2"][1])
+                if depth < best:
+                    best, closest = depth, i
+        if closest >= 0:
+            work[closest].update(d1=d1, d2=d2, n=n, merged=1, new=0)
+        else:
+            work.append({"d1": d1, "d2": d2, "n": n, "merged": 1, "new": 1, "pad": np.zeros(2, dtype=np.uint8), "si": -1})
+    out = np.array(pts[:2], dtype=contact_point_dtype).copy()
+    count = 0
+    for q in work:
+        if not q["merged"]:
+            continue
+        assert count < 2
+        o = out[count]
+        o["delta1"]["x"], o["delta1"]["y"] = q["d1"]
+        o["delta2"]["x"], o["delta2"]["y"] = q["d2"]
+        o["normal"]["x"], o["normal"]["y"] = q["n"]
+        o["is_merged"], o["is_newly_created"], o["pad"], o["solver_index"] = q["merged"], q["new"], q["pad"], q["si"]
+        count += 1
+    return count, out
+
+
+# ---- the queries --------------------------------------------------------------------------------------------------------------------------
+def point_in_circle(g, x, y):
+    """The AABB conjunct as for boxes AND dx*dx + dy*dy <= r*r (r = geom_size.x), for every body."""
+    x, y = F(x), F(y)
+    inside = (g.lox <= x) & (g.hix >= x) & (g.loy <= y) & (g.hiy >= y)
+    dx = x - g.px
+    dy = y - g.py
+    return inside & (dx * dx + dy * dy <= g.hx * g.hx)
+
+
+def ray_circle(g, r):
+    """The ray against every body's disc: (pass, tin, rx, ry)."""
+    ox, oy, dx, dy, max_t = (F(v) for v in r)
+    with np.errstate(all="ignore"):
+        rx = ox - g.px
+        ry = oy - g.py
+        a = dx * dx + dy * dy
+        b = rx * dx + ry * dy
+        c = rx * rx + ry * ry - g.hx * g.hx
+        D = b * b - a * c
+        s = np.sqrt(D)
+        tin = ((-b - s) / a).astype(F)
+        tout = ((-b + s) / a).astype(F)
+        hit = ~(D < 0) & (tin <= tout) & (tout >= 0) & (tin <= max_t)
+    return hit, tin, rx, ry
+
+
+def query_points(bodies, kinds, points, skip_static=False):
+    g = qs.Geometry(bodies)
+    round_ = np.asarray(kinds) == CIRCLE
+    pts = np.asarray(points, dtype=F).reshape(-1, 2)
+    out = np.full(len(pts), -1, dtype=np.int32)
+    elig = g.eligible(skip_static)
+    for q, p in enumerate(pts):
+        if not qs.point_ok(p) or not g.n:
+            continue
+        inside = np.where(round_, point_in_circle(g, p[0], p[1]), qs.point_in_box(g, p[0], p[1]))
+        hit = np.flatnonzero(elig & inside)
+        if len(hit):
+            out[q] = hit[0]
+    return out
+
+
+def raycast(bodies, kinds, rays, skip_static=False):
+    g = qs.Geometry(bodies)
+    round_ = np.asarray(kinds) == CIRCLE
+    rs = np.asarray(rays, dtype=F).reshape(-1, 5)
+    out = np.zeros(len(rs), dtype=ray_hit_dtype)
+    out["body"] = -1
+    elig = g.eligible(skip_static)
+    for q, r in enumerate(rs):
+        if not qs.ray_ok(r) or not g.n:
+            continue
+        bhit, btin, xenter, dxp, dyp = qs.ray_box(g, r)
+        chit, ctin, rx, ry = ray_circle(g, r)
+        hit = np.where(round_, chit, bhit) & elig & qs.ray_candidate(g, r)
+        tin = np.where(round_, ctin, btin).astype(F)
+        if not hit.any():
+            continue
+        t = np.where(tin > 0, tin, F(0)).astype(F)
+        tmin = t[hit].min()
+        b = int(np.flatnonzero(hit & (t == tmin))[0])                   # smallest t, then the lowest index
+        ox, oy, dx, dy = F(r[0]), F(r[1]), F(r[2]), F(r[3])
+        out["body"][q] = b
+        out["t"][q] = tmin
+        if not tin[b] < 0:
+            if round_[b]:
+                out["normal"][q] = ((rx[b] + tin[b] * dx) / g.hx[b], (ry[b] + tin[b] * dy) / g.hx[b])
+            elif xenter[b]:
+                n, flip = (g.xvx[b], g.xvy[b]), dxp[b] > 0
+                out["normal"][q] = (-n[0], -n[1]) if flip else n
+            else:
+                n, flip = (g.yvx[b], g.yvy[b]), dyp[b] > 0
+                out["normal"][q] = (-n[0], -n[1]) if flip else n
+        out["point"][q] = (ox + tmin * dx, oy + tmin * dy)
+    return out
