@@ -1399,6 +1399,16 @@ int phx_debug_primitive_plan(int32_t bits, int32_t scan_count, int32_t* digit_bi
  * updated in place. */
 int phx_debug_update_manifold(const phx_rigid_body* b1, int32_t kind1, const phx_rigid_body* b2, int32_t kind2, phx_manifold* manifold,
                               phx_contact_point pts[2]);
+/* phx_debug_schedule_bins (host only, needs no device): the three host rules every schedule builder shares, on `count` components given by
+ * their joint counts sizes[] and unit counts units[] (in body order).  A workgroup shape of L lanes holds L units and 2 L joints.
+ *   *lanes            the shape all groups take: big_lanes iff big_lanes != 0 and some non-empty component fits it but not small_lanes
+ *   bin_of, rank_of   per component: its bin (-1: an empty component, or one that goes to the HBM group — it fits no workgroup, or
+ *                     want_islands is 0) and its rank among the components of its bin
+ *   group_offsets     *bins + 1 entries (room for count + 1): the first slot of every bin, then the slots of all bins
+ *   *island_count, *island_max_size   GatherIslands' numbers: consecutive components coalesced until a run holds >= 256 joints */
+int phx_debug_schedule_bins(const int32_t* sizes, const int32_t* units, int32_t count, int32_t small_lanes, int32_t big_lanes,
+                            int32_t want_islands, int32_t* lanes, int32_t* bin_of, int32_t* rank_of, int32_t* group_offsets, int32_t* bins,
+                            int32_t* island_count, int32_t* island_max_size);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,7 @@ _SIGNATURES = {
     "phx_debug_radix_sort": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(_i32)]),
     "phx_debug_primitive_plan": (C.c_int, [_i32, _i32] + [C.POINTER(_i32)] * 4),
     "phx_debug_update_manifold": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "phx_debug_schedule_bins": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp, _vp, _vp] + [C.POINTER(_i32)] * 3),
     "phx_exchange_layout": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, C.POINTER(C.c_int64)]),
     "phx_solver_set_exchange_buffers": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
     "phx_solver_exchange_pack": (C.c_int, [_vp, _vp, _vp, _i32, C.POINTER(C.c_size_t)]),

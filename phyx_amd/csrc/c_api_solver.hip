@@ -240,4 +240,23 @@ int phx_schedule_islands(const int32_t* b1, const int32_t* b2, int32_t nj, const
     return (int)sz.size();
 }
 
+int phx_debug_schedule_bins(const int32_t* sizes, const int32_t* units, int32_t count, int32_t small_lanes, int32_t big_lanes, int32_t want_islands,
+                            int32_t* lanes, int32_t* bin_of, int32_t* rank_of, int32_t* group_offsets, int32_t* bins, int32_t* island_count, int32_t* island_max_size)
+{
+    PHX_REQUIRE(count >= 0 && (count == 0 || (sizes && units && bin_of && rank_of)) && group_offsets && small_lanes > 0 && big_lanes >= 0, "phx_debug_schedule_bins: bad arguments");
+    for (int c = 0; c < count; ++c) PHX_REQUIRE(sizes[c] >= 0 && units[c] >= 0 && sizes[c] < (1 << 30), "phx_debug_schedule_bins: a component's counts are 0 .. 2^30 - 1");
+    auto caps_of = [](int l) { phx::LdsCaps k; k.max_units = l; k.max_joints = 2 * l; return k; };      // (phx_schedule_groups' shape of `lanes`)
+    const bool big = big_lanes > 0 && phx::needs_big_shape(sizes, units, count, caps_of(small_lanes), caps_of(big_lanes));
+    const phx::LdsCaps caps = caps_of(big ? big_lanes : small_lanes);
+    std::vector<int> goff;
+    const int nbins = phx::bin_components(sizes, units, count, caps, want_islands != 0, bin_of, rank_of, goff);
+    std::copy(goff.begin(), goff.end(), group_offsets);
+    const phx::IslandNumbers isl = phx::coalesce_islands(sizes, count);
+    if (lanes) *lanes = caps.max_units;
+    if (bins) *bins = nbins;
+    if (island_count) *island_count = isl.count;
+    if (island_max_size) *island_max_size = isl.max_size;
+    return PHX_OK;
+}
+
 } // extern "C"

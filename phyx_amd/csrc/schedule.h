@@ -101,6 +101,62 @@ constexpr int BIN_CHUNK = 64;
 constexpr int BINC_MAX = 65536;          // speculative binning (schedule_kernels.h k_bin_components): components at most (tables, indices)
 constexpr int BINC_JOINT_BITS = 30;      // ... and solves of < 2^30 joints (the lanes' scan packs bins << 32 | slots)
 
+struct LdsCaps { int max_joints = 512, max_units = 256, max_bodies = 768, max_colours = 64, max_static = 1 << 30; };
+// (an LDS group's local body table lists its static bodies first, so a static body's local index is also its
+//  slot in the group's small static-tag table)
+
+// The host's three rules over the components (numbered in body order; sizes[c] joints and units[c] units each), each stated ONCE: the
+// host builder (schedule.hip), the device builder's host step (solver_build.hip), the statistics of a speculative build
+// (solver_inspect.hip) and the test entry point phx_debug_schedule_bins call these.  The device's formulation of the binning is
+// k_bin_components (schedule_kernels.h: a lane per chunk); tests/test_host_logic.py restates all three in Python.
+//
+// GatherIslands' published numbers (ref: Solver.cpp:382-413, kIslandMinSize): consecutive components are coalesced into one island
+// until the run holds >= 256 joints — or the components end.  island_of (optional, per component): the island the component joined.
+struct IslandNumbers { int count = 0, max_size = 0; };
+template <class I> inline IslandNumbers coalesce_islands(const I* sizes, int n, int* island_of = nullptr)
+{
+    IslandNumbers out;
+    int run = 0;
+    for (int c = 0; c < n; ++c) {
+        run += (int)sizes[c];
+        if (island_of) island_of[c] = out.count;
+        if (run >= 256 || (run > 0 && c == n - 1)) { ++out.count; out.max_size = std::max(out.max_size, run); run = 0; }
+    }
+    return out;
+}
+// The workgroup shape: ALL groups take the roomier shape iff some non-empty component fits it but not the small one.
+template <class I> inline bool component_fits(I joints, I units, const LdsCaps& k) { return (int)joints <= k.max_joints && (int)units <= k.max_units; }
+template <class I> inline bool needs_big_shape(const I* sizes, const I* units, int n, const LdsCaps& small_caps, const LdsCaps& big)
+{
+    for (int c = 0; c < n; ++c)
+        if (sizes[c] && !component_fits(sizes[c], units[c], small_caps) && component_fits(sizes[c], units[c], big)) return true;
+    return false;
+}
+// The greedy binning (BINNING above) under the chosen shape: bin_of[c] = the component's bin, -1 for an empty component and for one
+// that goes to the HBM group (it fits no workgroup; !want_islands: every component); rank_of[c] = its rank among its bin's
+// components; group_offsets = the bins' first slots, bins + 1 entries.  Returns the number of bins.  A bin exists once a non-empty,
+// fitting component has entered it; a chunk boundary and a misfit close the open bin, an empty component does neither.
+template <class I> inline int bin_components(const I* sizes, const I* units, int n, const LdsCaps& caps, bool want_islands,
+                                             int* bin_of, int* rank_of, std::vector<int>& group_offsets)
+{
+    group_offsets.assign(1, 0);
+    int nbins = 0, size = 0, nunits = 0, rank = 0;
+    bool open = false;
+    for (int c = 0; c < n; ++c) {
+        bin_of[c] = -1; rank_of[c] = 0;
+        if (c % BIN_CHUNK == 0) open = false;
+        const int s = (int)sizes[c], u = (int)units[c];
+        if (s == 0) continue;
+        if (!want_islands || !component_fits(s, u, caps)) { open = false; continue; }
+        if (!open || size + s > caps.max_joints || nunits + u > caps.max_units) { group_offsets.push_back(group_offsets.back()); ++nbins; open = true; size = 0; nunits = 0; rank = 0; }
+        bin_of[c] = nbins - 1;
+        rank_of[c] = rank++;
+        size += s; nunits += u;
+        group_offsets.back() += s;
+    }
+    return nbins;
+}
+
 // PARTITIONED COMPONENTS.  A component of more than COLOUR_B_MAX_JOINTS joints (a settled pile: one island of 1e5-1e6 joints)
 // is swept class by class out of HBM, one launch per class and sweep — a solve is classes x sweeps dependent launches.  Most of
 // such an island is local: cut the bodies into PARTS of PART_BODIES consecutive indices, twice — level 0 at multiples of
@@ -188,9 +244,6 @@ struct Schedule {
     int hbm_end() const { return has_hbm_group() ? hbm_colour_offsets.back() : 0; }
 };
 
-struct LdsCaps { int max_joints = 512, max_units = 256, max_bodies = 768, max_colours = 64, max_static = 1 << 30; };
-// (an LDS group's local body table lists its static bodies first, so a static body's local index is also its
-//  slot in the group's small static-tag table)
 
 // Colouring rule (every group, host and device builders alike; stated in full above): UNITS take their class FIRST-FIT IN ORDER
 // OF DECREASING colour_priority(id, joint index, lower body index) of their leader — parity of the lower body first, then a fixed

@@ -358,13 +358,8 @@ void gather_islands(const int* body1, const int* body2, int nj, const unsigned c
     for (int j = 0; j < nj; ++j) { const int i = island_of(j); if (i >= 0) raw_size[i]++; }
     // coalesce consecutive islands until >= kIslandMinSize joints (ref: Solver.cpp:382-413)
     std::vector<int> merged(count, 0);
-    island_size.clear();
-    int run = 0;
-    for (int i = 0; i < count; ++i) {
-        run += raw_size[i];
-        merged[i] = (int)island_size.size();
-        if (run >= 256 || (run > 0 && i == count - 1)) { island_size.push_back(run); run = 0; }
-    }
+    island_size.assign((size_t)coalesce_islands(raw_size.data(), count, merged.data()).count, 0);
+    for (int i = 0; i < count; ++i) if (raw_size[i]) island_size[merged[i]] += raw_size[i];
     joint_island.resize(nj);
     for (int j = 0; j < nj; ++j) { const int i = island_of(j); joint_island[j] = i < 0 ? -1 : merged[i]; }
 }
@@ -536,44 +531,23 @@ void build_island_schedule(const int* body1, const int* body2, int nj, const uns
         std::vector<int> cur(comp_count.begin(), comp_count.end() - 1);
         for (int j = 0; j < nj; ++j) if (comp_of[j] >= 0) comp_joints[cur[comp_of[j]]++] = j;
     }
-    // GatherIslands' published numbers (ref: Solver.cpp:382-413 coalescing rule), from the same components
-    {
-        int run = 0, count = 0, mx = 0;
-        for (int c = 0; c < ncomp; ++c) {
-            run += comp_count[c + 1] - comp_count[c];
-            if (run >= 256 || (run > 0 && c == ncomp - 1)) { ++count; mx = std::max(mx, run); run = 0; }
-        }
-        out.island_count = count; out.island_max_size = mx;
-    }
-    // pick the workgroup shape: the roomier one only if some component needs it and fits it
-    auto fits = [&](int c, const LdsCaps& k) { return comp_count[c + 1] - comp_count[c] <= k.max_joints && comp_units[c] <= k.max_units; };
-    LdsCaps caps = small_caps;
-    if (big) {
-        bool need = false;
-        for (int c = 0; c < ncomp; ++c) if (comp_count[c + 1] > comp_count[c] && !fits(c, small_caps) && fits(c, *big)) need = true;
-        if (need) caps = *big;
-    }
+    // GatherIslands' published numbers, the workgroup shape and the bins (schedule.h: the three rules), from the same components
+    std::vector<int> comp_size(std::max(ncomp, 1), 0);
+    for (int c = 0; c < ncomp; ++c) comp_size[c] = comp_count[c + 1] - comp_count[c];
+    const IslandNumbers isl = coalesce_islands(comp_size.data(), ncomp);
+    out.island_count = isl.count; out.island_max_size = isl.max_size;
+    const LdsCaps caps = big && needs_big_shape(comp_size.data(), comp_units.data(), ncomp, small_caps, *big) ? *big : small_caps;
     out.lds_lanes = caps.max_units;
-    // greedy binning of consecutive components (serial, one pass); oversized components go to the HBM group whole
+    std::vector<int> bin_of(std::max(ncomp, 1)), rank_of(std::max(ncomp, 1)), bin_first;
+    const int nbins = bin_components(comp_size.data(), comp_units.data(), ncomp, caps, true, bin_of.data(), rank_of.data(), bin_first);
+    // a bin's components are consecutive but for empty ones; the components without a bin go to the HBM group whole
     std::vector<int> rest;
-    std::vector<std::pair<int, int>> bins;       // [first component, last component)
-    {
-        int begin = -1, size = 0, units = 0;
-        auto flush = [&](int end) { if (begin >= 0 && size > 0) bins.emplace_back(begin, end); begin = -1; size = 0; units = 0; };
-        for (int c = 0; c < ncomp; ++c) {
-            if (c % BIN_CHUNK == 0) flush(c);              // (schedule.h BINNING: a bin never spans a chunk boundary)
-            const int n = comp_count[c + 1] - comp_count[c];
-            if (n == 0) continue;
-            if (!fits(c, caps)) {
-                flush(c);
-                rest.insert(rest.end(), comp_joints.begin() + comp_count[c], comp_joints.begin() + comp_count[c + 1]);
-                continue;
-            }
-            if (size + n > caps.max_joints || units + comp_units[c] > caps.max_units) flush(c);
-            if (begin < 0) begin = c;
-            size += n; units += comp_units[c];
-        }
-        flush(ncomp);
+    std::vector<std::pair<int, int>> bins(nbins, {-1, -1});       // [first component, last component)
+    for (int c = 0; c < ncomp; ++c) {
+        if (bin_of[c] < 0) { rest.insert(rest.end(), comp_joints.begin() + comp_count[c], comp_joints.begin() + comp_count[c + 1]); continue; }
+        std::pair<int, int>& b = bins[bin_of[c]];
+        if (b.first < 0) b.first = c;
+        b.second = c + 1;
     }
     // bins are independent: build them on the host's cores
     std::vector<BinOut> built(bins.size());

@@ -1,4 +1,6 @@
 // solver.h — host side of the device solver: schedule (colouring / islands), residency, launches.
+// One class, one translation unit per concern: solver.hip (construction, the gate, the launch sequence of a solve and its settling),
+// solver_build.hip (the schedule builders), solver_inspect.hip (what a caller asks for after the fact), solver_bench.hip.
 #pragma once
 
 #include "common.h"
@@ -52,6 +54,9 @@ struct PartsView {
     int nb;                     // the body count the parts were laid out for (part_first_body): the schedule's, which appended bodies do not move
 };
 constexpr int PARTS_CLASS_STRIDE = 64;      // = JP_MAX_COLOURS, the device schedule builder's class limit
+
+// what Schedule::fingerprint holds: the topology hash of the joints with the joint and body counts mixed in
+inline unsigned long long mixed_fingerprint(unsigned long long fp, int nb, int nj) { return fp ^ ((unsigned long long)(unsigned)nj << 32) ^ (unsigned)nb; }
 
 class DeviceSolver {
 public:
@@ -147,6 +152,7 @@ private:
     int edge_view(const void* d_bodies_aos, int nb, Arrays* out);      // converts the records into this handle's edge arrays
     int ensure_schedule(const float4* d_mpos, int nb, const phx_contact_joint* d_joints, int nj, int ncp, const phx_config& cfg, bool force_rebuild,
                         bool known_changed = false);
+    int build_schedule_host(const float4* d_mpos, int nb, const phx_contact_joint* d_joints, int nj, bool want_islands, unsigned long long raw_fingerprint);
     int build_schedule_device(const float4* d_mpos, int nb, const phx_contact_joint* d_joints, int nj, bool want_islands, bool* fallback);
     int build_bins_speculative(const float4* d_mpos, int nb, const phx_contact_joint* d_joints, int nj, Schedule& sc, bool from_manifolds);
     int spec_grid() const;                // the launch grid of a speculative build's per-bin kernels
@@ -163,9 +169,14 @@ private:
     int enqueue(const Arrays& a, int nb, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, const phx_config& cfg);
     int enqueue_pre(const BodyView& bodies, int nb, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj);
     int enqueue_sweeps(const BodyView& bodies, const phx_contact_point* d_cps, phx_contact_joint* d_joints, int nj, int ci, int pi, int mode_override = -1);
-    int enqueue_post(const BodyView& bodies, int nb, phx_contact_joint* d_joints, int nj);
+    int enqueue_post(const BodyView& bodies, phx_contact_joint* d_joints, int nj);
     int collect_stats(unsigned long long* extra = nullptr, const unsigned long long* extra_src = nullptr, const std::function<int()>* while_waiting = nullptr,
                       const MailCarrier* carrier = nullptr);
+    // stats_' island_count, island_max_size, colour_count and lds_islands, from sched_ (the island numbers only under the splitting island modes)
+    void publish_schedule_stats(int island_mode, int nj);
+    int copy_trace(unsigned long long* out, long long cap_words, int skip, int words, bool per_wave, const char* too_small, int* groups, int* waves_per_group);      // (solver_inspect.hip)
+    // the launch grid of the solver's element-wise kernels (grid-stride loops): 256-lane blocks, 2048 of them at most
+    static int grid_for(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }
     SolverView view() const;
     SolverViewMat view_mat() const { SolverViewMat m{}; static_cast<SolverView&>(m) = view(); m.mat = mat_; m.mu = hbm_.mu.p; return m; }
 
@@ -177,8 +188,7 @@ private:
     bool prelabel_marked_ = false, prelabel_pending_ = false; int prelabel_nb_ = 0;
     const phx_manifold* pre_manifolds_ = nullptr; int pre_nm_ = 0, pre_grid_ = 0, pre_lanes_ = 0;      // what the side stream binned from, and for which launch grid / shape
     const phx_contact_point* build_cps_ = nullptr;      // the contact points of the solve being queued (the manifold build pairs the joints through them)
-    hipEvent_t ev_begin_ = nullptr, ev_end_ = nullptr, ev_sweep_begin_ = nullptr, ev_sweep_end_ = nullptr;
-
+    hipEvent_t ev_sweep_begin_ = nullptr, ev_sweep_end_ = nullptr;
 
     // ---- what the handle owns, by path.  Every buffer is a DevBuf (freed with the handle); init() reads the environment once ----
     // the PHX_* knobs (measurement and debugging; README.md lists them)
@@ -263,6 +273,25 @@ private:
         DevBuf<unsigned char> jp_bad_b, jp_kind;
         DevBuf<int> jp_small, jp_counts;
     } bld_;
+    // bench_stage(), bench() and bench_checksum() (solver_bench.hip).  The solve path reads in_loop, trusted and the step hook — and
+    // time_sweeps_ below — and nothing else of it.
+    struct Bench {
+        DevBuf<float4> snap_vel, snap_dvel, snap_mpos;      // the working copy of the input (resident form) a step without a staged copy restores
+        DevBuf<phx_contact_joint> snap_joints;
+        // bench_stage(): private copies of the input, one per timed step, made BEFORE the timed region (the input of every step is
+        // then resident in HBM — in the resident layout — when the clock starts, and no restore copy runs between the solves)
+        DevBuf<float4> stage_vel, stage_dvel, stage_mpos;   // (mpos is read-only: one copy serves every step)
+        DevBuf<phx_contact_joint> stage_joints;
+        const void* staged_src_bodies = nullptr; const void* staged_src_joints = nullptr;
+        int staged_nb = 0, staged_nj = 0, staged_steps = 0;
+        BodyView last_b{}; phx_contact_joint* last_j = nullptr; int last_nb = 0, last_nj = 0;      // bench_checksum: the arrays of the last step
+        std::vector<hipEvent_t> events;
+        bool in_loop = false;                 // bench()'s timed loop: unverified solves are chained on purpose
+        bool trusted = false;                 // bench(): the timed solves run on copies of the input the schedule was built (and verified) for
+        phx_step_hook step_hook = nullptr;    // bench(): called with phase 1 between a step's local preparation and its sweeps
+        void* step_hook_user = nullptr;
+        int step_hook_step = 0;
+    } bench_;
 
     // device state
     DevBuf<float4> edge_vel_, edge_dvel_, edge_mpos_;      // resident form of the records a C-ABI edge call handed over
@@ -296,9 +325,6 @@ private:
     const unsigned* sw_cleared_ = nullptr;          // the static-tag table launch_fingerprint's kernel cleared for the solve in flight
     size_t sw_cleared_words_ = 0;
     unsigned replays_ = 0;                          // solves repeated because nothing could be committed (stale or spoiled schedule)
-    phx_step_hook step_hook_ = nullptr;  // bench(): called with phase 1 between a step's local preparation and its sweeps
-    void* step_hook_user_ = nullptr;
-    int step_hook_step_ = 0;
     int hash_slot_ = 1;                  // which of the two control sets (control word = fingerprint accumulator, island counters, stamps) the solve in flight uses
     bool island_clears_next_ = false;    // no hash pass runs in front of this solve: its island launch clears the next solve's control set
     bool spec_hash_ran_ = false;         // the hash pass ran in front of the speculative build that is being settled
@@ -314,19 +340,7 @@ private:
     DevBuf<phx_rigid_body> st_bodies_;
     DevBuf<phx_contact_point> st_cps_;
     DevBuf<phx_contact_joint> st_joints_;
-    // bench snapshots (resident form)
-    DevBuf<float4> snap_vel_, snap_dvel_, snap_mpos_;
-    DevBuf<phx_contact_joint> snap_joints_;
     long long lite_builds_ = 0, full_builds_ = 0;                                  // (statistics: device builds from the manifolds / from the joints)
-    BodyView bench_last_b_{}; phx_contact_joint* bench_last_j_ = nullptr; int bench_last_nb_ = 0, bench_last_nj_ = 0;      // bench_checksum
-    // bench_stage(): private copies of the input, one per timed step, made BEFORE the timed region (the input of every step is
-    // then resident in HBM — in the resident layout — when the clock starts, and no restore copy runs between the solves)
-    DevBuf<float4> stage_vel_, stage_dvel_, stage_mpos_;      // (mpos is read-only: one copy serves every step)
-    DevBuf<phx_contact_joint> stage_joints_;
-    const void* staged_src_bodies_ = nullptr; const void* staged_src_joints_ = nullptr;
-    int staged_nb_ = 0, staged_nj_ = 0, staged_steps_ = 0;
-    bool in_bench_loop_ = false;                      // bench()'s timed loop: unverified solves are chained on purpose
-    bool bench_trusted_ = false;                      // bench(): the timed solves run on copies of the input the schedule was built (and verified) for
 
     Schedule sched_;
     std::vector<int> h_static_slot_;
@@ -369,7 +383,6 @@ private:
     std::vector<long long> xch_off_host_;
     DevBuf<int> xch_err_;
     bool trace_islands_ = false, trace_waves_ = true;
-    std::vector<hipEvent_t> bench_events_;
 };
 
 } // namespace phx

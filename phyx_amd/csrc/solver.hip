@@ -1,16 +1,13 @@
-// solver.hip — DeviceSolver: residency, the launch sequence of a solve and its settling (schedule construction: solver_build.hip).
+// solver.hip — DeviceSolver: residency, the gate, the launch sequence of a solve and its settling (schedule construction:
+// solver_build.hip; queries: solver_inspect.hip; the bench harness: solver_bench.hip).
 #include "solver.h"
 #include "solver_kernels.h"
 
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
-#include <numeric>
 #include <type_traits>
 
 namespace phx {
-
-static inline int grid_for(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }
 
 constexpr int STATS_SET = 2 * ISL_STAT_SLOTS, VISITS_SET = ISL_STAT_SLOTS + STAMP_WORDS, SHARDS_SET = ISL_SHARDS * ISL_SHARD_STRIDE;      // words of one control set in isl_.stats / isl_.visits / isl_.shards
 
@@ -20,15 +17,13 @@ DeviceSolver::~DeviceSolver()
 {
     if (hipSetDevice(device_) != hipSuccess) return;
     if (stream_) (void)hipStreamSynchronize(stream_);
-    for (hipEvent_t e : bench_events_) (void)hipEventDestroy(e);
+    for (hipEvent_t e : bench_.events) (void)hipEventDestroy(e);
     // (every device buffer is a DevBuf member: freed with the object, after this body — the device is selected above)
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_join_) (void)hipEventDestroy(ev_join_);
     if (ev_pre_fork_) (void)hipEventDestroy(ev_pre_fork_);
     if (ev_pre_join_) (void)hipEventDestroy(ev_pre_join_);
     if (side_stream_) { (void)hipStreamSynchronize(side_stream_); (void)hipStreamDestroy(side_stream_); }
-    if (ev_begin_) (void)hipEventDestroy(ev_begin_);
-    if (ev_end_) (void)hipEventDestroy(ev_end_);
     if (ev_sweep_begin_) (void)hipEventDestroy(ev_sweep_begin_);
     if (ev_sweep_end_) (void)hipEventDestroy(ev_sweep_end_);
     if (stream_ && owns_stream_) (void)hipStreamDestroy(stream_);
@@ -70,8 +65,6 @@ int DeviceSolver::init()
 {
     PHX_TRY(use_device(device_));
     PHX_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    PHX_HIP(hipEventCreate(&ev_begin_));
-    PHX_HIP(hipEventCreate(&ev_end_));
     PHX_HIP(hipEventCreate(&ev_sweep_begin_));
     PHX_HIP(hipEventCreate(&ev_sweep_end_));
     // the LDS islands of a schedule that also has an HBM group run beside its sweeps (enqueue_sweeps)
@@ -346,7 +339,7 @@ int DeviceSolver::enqueue_sweeps(const BodyView& d_bodies, const phx_contact_poi
     return PHX_OK;
 }
 
-int DeviceSolver::enqueue_post(const BodyView& d_bodies, int nb, phx_contact_joint* d_joints, int nj)
+int DeviceSolver::enqueue_post(const BodyView& d_bodies, phx_contact_joint* d_joints, int nj)
 {
     const SolverView v = view();
     if (nj && owns_hbm_group()) {      // only the HBM group has results parked in the solver arrays
@@ -355,7 +348,6 @@ int DeviceSolver::enqueue_post(const BodyView& d_bodies, int nb, phx_contact_joi
         hipLaunchKernelGGL(k_finish_joints, dim3(grid_for(he - hb)), dim3(256), 0, stream_, v, hb, he, d_joints);
         hipLaunchKernelGGL(k_finish_bodies, dim3(grid_for(hbm_bodies)), dim3(256), 0, stream_, v, (const int*)hbm_.hbm_body_list.p, hbm_bodies, d_bodies);
     }
-    (void)nb;
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
@@ -388,7 +380,7 @@ int DeviceSolver::enqueue(const Arrays& arrays, int nb, const phx_contact_point*
     if (time_sweeps_) PHX_HIP(hipEventRecord(ev_sweep_end_, stream_));
     {
         RoctxRange r("FinishJoints + FinishBodies (HBM group)");                                         // ref: Solver.cpp:213, 114
-        PHX_TRY(enqueue_post(d_bodies, nb, d_joints, nj));
+        PHX_TRY(enqueue_post(d_bodies, d_joints, nj));
         // a solve that came through the C-ABI edge: FinishBodies into the caller's records, behind the same gate
         if (arrays.aos && nb) {
             hipLaunchKernelGGL(k_view_to_bodies, dim3(grid_for(nb)), dim3(256), 0, stream_, d_bodies, nb, arrays.aos, (const unsigned long long*)(hash_.p + hash_slot_), gate_expected_);
@@ -451,7 +443,7 @@ int DeviceSolver::bodies_appended(int old_nb, int new_nb)
     PHX_TRY(hbm_.static_slot.reserve_keep((size_t)new_nb, slots, stream_));
     PHX_HIP(hipMemsetAsync(hbm_.static_slot.p + slots, 0xFF, ((size_t)new_nb - slots) * sizeof(int), stream_));      // (-1: not static)
     if (!h_static_slot_.empty()) h_static_slot_.resize((size_t)new_nb, -1);
-    sched_.fingerprint ^= (unsigned long long)(unsigned)nb_ ^ (unsigned)new_nb;      // (the fingerprint mixes in the body count: ensure_schedule)
+    sched_.fingerprint ^= (unsigned long long)(unsigned)nb_ ^ (unsigned)new_nb;      // (mixed_fingerprint's body count, moved from nb_ to new_nb)
     nb_ = new_nb;
     return PHX_OK;
 }
@@ -468,6 +460,17 @@ void DeviceSolver::register_pending(const Arrays& a, int nb, const void* cps, in
     pending_.active = true; pending_.arrays = a; pending_.cps = cps; pending_.joints = joints;
     pending_.nb = nb; pending_.ncp = ncp; pending_.nj = nj; pending_.cfg = cfg;
     pending_.mode = isl_mode_; pending_.nexpect = isl_nexpect_;
+}
+
+// What phx_solve_stats says about the schedule in hand.  GatherIslands' numbers are published under the island modes that split;
+// every other mode solves one island of all the joints.
+void DeviceSolver::publish_schedule_stats(int island_mode, int nj)
+{
+    const bool split = island_mode == PHX_ISLAND_MULTIPLE || island_mode == PHX_ISLAND_MULTIPLE_SLOPPY;
+    stats_.island_count = split ? sched_.island_count : 1;
+    stats_.island_max_size = split ? sched_.island_max_size : nj;
+    stats_.colour_count = sched_.ncolours();
+    stats_.lds_islands = sched_.lds_groups;
 }
 
 int DeviceSolver::solve_common(const Arrays& a, int nb, const void* d_cps, int ncp, void* d_joints, int nj, const phx_config& cfg, bool topology_changed)
@@ -489,7 +492,7 @@ int DeviceSolver::solve_common(const Arrays& a, int nb, const void* d_cps, int n
     // solve would never be completed (complete_partial) and its late groups would silently get one solve fewer.  Hash-gated repeats
     // share one verdict and commit all or nothing: they may chain.
     // (bench()'s timed loop queues its steps back to back by design and settles them at the end: a measurement, not a caller)
-    if (pending_.active && pending_.mode == ISL_VERIFY && !in_bench_loop_) PHX_TRY(synchronize());
+    if (pending_.active && pending_.mode == ISL_VERIFY && !bench_.in_loop) PHX_TRY(synchronize());
     // a device-built schedule is verified (did every bin fit?) before anything else runs on it: only the solve that was queued
     // with the build is covered by the spoiled control word
     if (build_unverified_) PHX_TRY(synchronize());
@@ -513,7 +516,7 @@ int DeviceSolver::solve_common(const Arrays& a, int nb, const void* d_cps, int n
         // gated by the same topology, so they are verified together — and replayed together if the schedule was stale
         // (bench() on staged copies of the input the schedule was verified for: the device gates all the same, bench() checks the
         //  last control word itself, and nothing is registered for a replay — every step has arrays of its own)
-        if (!bench_trusted_) register_pending(a, nb, d_cps, ncp, d_joints, nj, cfg, true);
+        if (!bench_.trusted) register_pending(a, nb, d_cps, ncp, d_joints, nj, cfg, true);
         stats_.recoloured = 0;
     } else {
         build_cps_ = static_cast<const phx_contact_point*>(d_cps);
@@ -521,12 +524,8 @@ int DeviceSolver::solve_common(const Arrays& a, int nb, const void* d_cps, int n
         // like a speculative solve: verified (and replayed on a host-built schedule if a bin was rejected) by synchronize()
         if (build_unverified_) register_pending(a, nb, d_cps, ncp, d_joints, nj, cfg, false);
     }
-    const bool split = cfg.island_mode == PHX_ISLAND_MULTIPLE || cfg.island_mode == PHX_ISLAND_MULTIPLE_SLOPPY;
-    stats_.island_count = split ? sched_.island_count : 1;
-    stats_.island_max_size = split ? sched_.island_max_size : nj;
-    stats_.colour_count = sched_.ncolours();
-    stats_.lds_islands = sched_.lds_groups;
-    if (step_hook_ && step_hook_(step_hook_user_, step_hook_step_, 1)) { set_error("bench: step hook failed"); return PHX_ERR_STATE; }
+    publish_schedule_stats(cfg.island_mode, nj);
+    if (bench_.step_hook && bench_.step_hook(bench_.step_hook_user, bench_.step_hook_step, 1)) { set_error("bench: step hook failed"); return PHX_ERR_STATE; }
     return enqueue(a, nb, static_cast<const phx_contact_point*>(d_cps), static_cast<phx_contact_joint*>(d_joints), nj, cfg);
 }
 
@@ -568,7 +567,6 @@ int DeviceSolver::collect_stats(unsigned long long* extra, const unsigned long l
         ncol.assign((size_t)unverified_bins_, 0);
         return rb_.add(ncol.data(), isl_.ncol.p, ncol.size() * sizeof(int), stream_);
     };
-    auto rest_of_sizes = [&]() -> int { return PHX_OK; };
     auto settle_build = [&]() {
         if (!build_unverified_) return;
         build_unverified_ = false;
@@ -582,7 +580,7 @@ int DeviceSolver::collect_stats(unsigned long long* extra, const unsigned long l
             unsigned long long hash = 0;
             std::memcpy(&hash, spec + 8, sizeof hash);
             raw_fingerprint_ = hash; have_hash_ = spec_hash_ran_;
-            sched_.fingerprint = hash ^ ((unsigned long long)(unsigned)nj_ << 32) ^ (unsigned)nb_;
+            sched_.fingerprint = mixed_fingerprint(hash, nb_, nj_);
             sched_.lds_groups = nbins;
             spec_bins_guess_ = nbins; ncomp_guess_ = spec[5];
             stats_.lds_islands = nbins;
@@ -593,27 +591,23 @@ int DeviceSolver::collect_stats(unsigned long long* extra, const unsigned long l
         for (int n : ncol) sched_.lds_colours += n;
         stats_.colour_count = sched_.ncolours();
     };
-    if (!stats_pending_) {
-        if (extra) { PHX_TRY(rb_.add(extra, extra_src, sizeof *extra, stream_)); }
-        PHX_TRY(with_build());
-        PHX_TRY(rb_.wait(stream_, nullptr, while_waiting, carrier));
-        PHX_TRY(rest_of_sizes());
-        settle_build();
-        return PHX_OK;
-    }
-    std::vector<int> flags(2 * (size_t)max_iters_);
+    const bool stats = stats_pending_;
+    std::vector<int> flags(stats ? 2 * (size_t)max_iters_ : 0);
     int isl_slots[2 * ISL_STAT_SLOTS] = {0};
     unsigned long long visit_slots[ISL_STAT_SLOTS] = {0};
-    if (extra) PHX_TRY(rb_.add(extra, extra_src, sizeof *extra, stream_));
-    PHX_TRY(rb_.add(flags.data(), hbm_.flags.p, flags.size() * sizeof(int), stream_));
-    PHX_TRY(rb_.add(isl_slots, isl_.stats.p + (size_t)hash_slot_ * STATS_SET, sizeof isl_slots, stream_));
     unsigned long long stamps[STAMP_WORDS] = {0};          // (begin, end, and the island kernel's sharded end words: solver_kernels.h solve_stamp_end)
-    PHX_TRY(rb_.add(visit_slots, isl_.visits.p + (size_t)hash_slot_ * VISITS_SET, sizeof visit_slots, stream_));
-    PHX_TRY(rb_.add(stamps, isl_.visits.p + (size_t)hash_slot_ * VISITS_SET + ISL_STAT_SLOTS, sizeof stamps, stream_));
+    // one mailbox round trip, in this order: the extra word, the statistics' words, the build's
+    if (extra) PHX_TRY(rb_.add(extra, extra_src, sizeof *extra, stream_));
+    if (stats) {
+        PHX_TRY(rb_.add(flags.data(), hbm_.flags.p, flags.size() * sizeof(int), stream_));
+        PHX_TRY(rb_.add(isl_slots, isl_.stats.p + (size_t)hash_slot_ * STATS_SET, sizeof isl_slots, stream_));
+        PHX_TRY(rb_.add(visit_slots, isl_.visits.p + (size_t)hash_slot_ * VISITS_SET, sizeof visit_slots, stream_));
+        PHX_TRY(rb_.add(stamps, isl_.visits.p + (size_t)hash_slot_ * VISITS_SET + ISL_STAT_SLOTS, sizeof stamps, stream_));
+    }
     PHX_TRY(with_build());
     PHX_TRY(rb_.wait(stream_, nullptr, while_waiting, carrier));
-    PHX_TRY(rest_of_sizes());
     settle_build();
+    if (!stats) return PHX_OK;
     int isl[2] = {0, 0};
     unsigned long long isl_visits = 0;
     for (int k = 0; k < ISL_STAT_SLOTS; ++k) { isl[0] = std::max(isl[0], isl_slots[2 * k]); isl[1] = std::max(isl[1], isl_slots[2 * k + 1]); isl_visits += visit_slots[k]; }
@@ -697,11 +691,7 @@ int DeviceSolver::synchronize(const std::function<int()>* while_waiting, const M
             const int rebuilt = ensure_schedule(p.arrays.view.mpos, p.nb, static_cast<const phx_contact_joint*>(p.joints), p.nj, p.ncp, p.cfg, true);
             defer_build_check_ = keep_defer;
             PHX_TRY(rebuilt);
-            stats_.colour_count = sched_.ncolours();
-            stats_.lds_islands = sched_.lds_groups;
-            const bool split = p.cfg.island_mode == PHX_ISLAND_MULTIPLE || p.cfg.island_mode == PHX_ISLAND_MULTIPLE_SLOPPY;
-            stats_.island_count = split ? sched_.island_count : 1;
-            stats_.island_max_size = split ? sched_.island_max_size : p.nj;
+            publish_schedule_stats(p.cfg.island_mode, p.nj);
             // none of the queued solves committed anything: repeat as many as were asked for (e.g. solver-only sub-stepping)
             for (int k = 0; k < std::max(p.count, 1); ++k) {
                 if (k) PHX_TRY(launch_fingerprint(p.arrays.view.mpos, p.nb, static_cast<const phx_contact_joint*>(p.joints), p.nj, p.ncp));
@@ -711,99 +701,6 @@ int DeviceSolver::synchronize(const std::function<int()>* while_waiting, const M
         }
     }
     return collect_stats();
-}
-
-// The tables of the last speculative build, on demand (collect_stats): what a build with a host round trip would have left in
-// sched_ and stats_.  Callers have settled the solve (synchronize()), so nothing queued since can have overwritten them.
-int DeviceSolver::fetch_build_tables()
-{
-    if (!tables_pending_) return PHX_OK;
-    PHX_TRY(use_device(device_));
-    const int nbins = tables_bins_, ncomp = tables_comps_;
-    std::vector<int> goff((size_t)nbins + 1, 0), ncol((size_t)std::max(nbins, 1), 0);
-    std::vector<unsigned> comp_size((size_t)std::max(ncomp, 1), 0u);
-    PHX_TRY(rb_.add(goff.data(), bld_.bin_tables_s[tables_set_].p + 2 * BINC_MAX, goff.size() * sizeof(int), stream_));
-    if (nbins) PHX_TRY(rb_.add(ncol.data(), isl_.ncol.p, (size_t)nbins * sizeof(int), stream_));
-    if (ncomp) PHX_TRY(rb_.add(comp_size.data(), bld_.comp_size_s[tables_set_].p, (size_t)ncomp * sizeof(unsigned), stream_));
-    PHX_TRY(rb_.wait(stream_));
-    tables_pending_ = false;
-    sched_.group_offsets.assign(goff.begin(), goff.end());
-    {   // GatherIslands' published numbers from the component sizes, as the builder's long way computes them
-        int run = 0, count = 0, mx = 0;
-        for (int c = 0; c < ncomp; ++c) {
-            run += (int)comp_size[c];
-            if (run >= 256 || (run > 0 && c == ncomp - 1)) { ++count; mx = std::max(mx, run); run = 0; }
-        }
-        sched_.island_count = count; sched_.island_max_size = mx;
-    }
-    sched_.lds_colours = 0;
-    for (int g = 0; g < nbins; ++g) sched_.lds_colours += ncol[(size_t)g];
-    const bool split = last_island_mode_ == PHX_ISLAND_MULTIPLE || last_island_mode_ == PHX_ISLAND_MULTIPLE_SLOPPY;
-    stats_.island_count = split ? sched_.island_count : 1;
-    stats_.island_max_size = split ? sched_.island_max_size : nj_;
-    stats_.colour_count = sched_.ncolours();
-    return PHX_OK;
-}
-
-int DeviceSolver::get_stats(phx_solve_stats* out)
-{
-    PHX_REQUIRE(out, "null out");
-    if (!have_solve_) { set_error("no solve has run yet"); return PHX_ERR_STATE; }
-    PHX_TRY(synchronize());
-    PHX_TRY(fetch_build_tables());
-    *out = stats_;
-    return PHX_OK;
-}
-
-int DeviceSolver::get_schedule(int* order, int order_cap, int* offsets, int offsets_cap, int* ncolours)
-{
-    if (!sched_.valid) { set_error("no solve has run yet"); return PHX_ERR_STATE; }
-    PHX_TRY(synchronize());                            // (an unverified device build is settled first)
-    PHX_TRY(materialise_schedule());
-    const int ncol = sched_.ncolours();
-    if (ncolours) *ncolours = ncol;
-    if ((order && order_cap < nj_) || (offsets && offsets_cap < ncol + 1)) { set_error("schedule buffers too small"); return PHX_ERR_CAPACITY; }
-    if (order) std::copy(sched_.order.begin(), sched_.order.end(), order);
-    if (offsets) std::copy(sched_.colour_offsets.begin(), sched_.colour_offsets.end(), offsets);
-    return PHX_OK;
-}
-
-// phase stamps of the island kernel's workgroups (diagnostics: tools/island_trace.py)
-int DeviceSolver::get_island_trace(unsigned long long* out, int cap_groups, int* groups)
-{
-    PHX_TRY(synchronize());
-    const int lg = sched_.valid ? sched_.lds_groups : 0;
-    if (groups) *groups = lg;
-    if (!out) return PHX_OK;
-    if (!trace_islands_ || !isl_.trace.p) { set_error("island trace is off (phx_solver_set_trace)"); return PHX_ERR_STATE; }
-    if (cap_groups < lg) { set_error("island trace buffer too small"); return PHX_ERR_CAPACITY; }
-    if (lg) PHX_HIP(hipMemcpy(out, isl_.trace.p, (size_t)lg * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PHX_OK;
-}
-
-int DeviceSolver::get_phase_trace(unsigned long long* out, int cap_words, int* words_per_group)
-{
-    PHX_TRY(synchronize());
-    const int lg = sched_.valid ? sched_.lds_groups : 0;
-    if (words_per_group) *words_per_group = ISL_PHASE_WORDS;
-    if (!out) return PHX_OK;
-    if (!trace_islands_ || !isl_.trace.p) { set_error("island trace is off (phx_solver_set_trace)"); return PHX_ERR_STATE; }
-    if (cap_words < lg * ISL_PHASE_WORDS) { set_error("phase trace buffer too small"); return PHX_ERR_CAPACITY; }
-    if (lg) PHX_HIP(hipMemcpy(out, isl_.trace.p + (size_t)lg * (8 + 128), (size_t)lg * ISL_PHASE_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PHX_OK;
-}
-
-int DeviceSolver::get_wave_trace(unsigned long long* out, int cap_words, int* waves_per_group)
-{
-    PHX_TRY(synchronize());
-    const int lg = sched_.valid ? sched_.lds_groups : 0;
-    const int wpg = sched_.lds_lanes > ISL_T ? ISL_T_BIG / 64 : ISL_T / 64;
-    if (waves_per_group) *waves_per_group = wpg;
-    if (!out) return PHX_OK;
-    if (!trace_islands_ || !isl_.trace.p) { set_error("island trace is off (phx_solver_set_trace)"); return PHX_ERR_STATE; }
-    if (cap_words < lg * wpg * 8) { set_error("wave trace buffer too small"); return PHX_ERR_CAPACITY; }
-    if (lg) PHX_HIP(hipMemcpy(out, isl_.trace.p + (size_t)lg * 8, (size_t)lg * wpg * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PHX_OK;
 }
 
 int DeviceSolver::set_body_state_bits(int bits)
@@ -825,236 +722,6 @@ int DeviceSolver::set_shard(int shard, int count)
         if (count != shard_count_) sched_.valid = false;
         shard_ = shard; shard_count_ = count;
     }
-    return PHX_OK;
-}
-
-int DeviceSolver::get_groups(int* offsets, int cap, int* count, int* lds_count)
-{
-    if (!sched_.valid) { set_error("no solve has run yet"); return PHX_ERR_STATE; }
-    PHX_TRY(synchronize());
-    PHX_TRY(materialise_schedule());
-    if (count) *count = sched_.ngroups();
-    if (lds_count) *lds_count = sched_.lds_groups;
-    if (offsets) {
-        if (cap < (int)sched_.group_offsets.size()) { set_error("group_offsets too small"); return PHX_ERR_CAPACITY; }
-        std::copy(sched_.group_offsets.begin(), sched_.group_offsets.end(), offsets);
-    }
-    return PHX_OK;
-}
-
-int DeviceSolver::get_lanes(int* leader_slot, int* lane, int cap, int* count)
-{
-    if (!sched_.valid) { set_error("no solve has run yet"); return PHX_ERR_STATE; }
-    PHX_TRY(synchronize());
-    PHX_TRY(materialise_schedule());
-    const int lg = sched_.lds_groups, lanes = sched_.lds_lanes;
-    std::vector<int4> recs(2 * (size_t)std::max(lg, 1) * std::max(lanes, 1));
-    PHX_TRY(use_device(device_));
-    if (lg) PHX_HIP(hipMemcpy(recs.data(), isl_.unit_recs.p, 2 * (size_t)lg * lanes * sizeof(int4), hipMemcpyDeviceToHost));
-    int n = 0;
-    for (int g = 0; g < lg; ++g)
-        for (int l = 0; l < lanes; ++l) {
-            const int4 a = recs[2 * ((size_t)g * lanes + l)], b = recs[2 * ((size_t)g * lanes + l) + 1];
-            if (a.x < 0) continue;                                      // nobody's lane
-            if (leader_slot && lane) {
-                if (n >= cap) { set_error("lane arrays too small"); return PHX_ERR_CAPACITY; }
-                leader_slot[n] = b.z; lane[n] = l;
-            }
-            ++n;
-        }
-    if (count) *count = n;
-    return PHX_OK;
-}
-
-int DeviceSolver::get_refreshed(int joint, float out[30])
-{
-    if (!have_solve_) { set_error("no solve has run yet"); return PHX_ERR_STATE; }
-    PHX_REQUIRE(joint >= 0 && joint < nj_ && out, "joint index out of range");
-    PHX_TRY(synchronize());
-    PHX_TRY(materialise_schedule());
-    const int slot = (int)(std::find(sched_.order.begin(), sched_.order.end(), joint) - sched_.order.begin());
-    if (sched_.lds_groups && slot < sched_.group_offsets[sched_.lds_groups]) {
-        set_error("joint %d was solved by the island kernel, whose refreshed constants live only in registers; query it under island mode Single", joint);
-        return PHX_ERR_STATE;
-    }
-    float4 a, f, c; int4 k; float2 acc, d;
-    PHX_HIP(hipMemcpy(&a, hbm_.q0.p + slot, sizeof a, hipMemcpyDeviceToHost));
-    PHX_HIP(hipMemcpy(&f, hbm_.q1.p + slot, sizeof f, hipMemcpyDeviceToHost));
-    PHX_HIP(hipMemcpy(&c, hbm_.q2.p + slot, sizeof c, hipMemcpyDeviceToHost));
-    PHX_HIP(hipMemcpy(&k, hbm_.q3.p + slot, sizeof k, hipMemcpyDeviceToHost));
-    PHX_HIP(hipMemcpy(&acc, hbm_.acc.p + slot, sizeof acc, hipMemcpyDeviceToHost));
-    PHX_HIP(hipMemcpy(&d, hbm_.dd.p + slot, sizeof d, hipMemcpyDeviceToHost));
-    float ii2; std::memcpy(&ii2, &k.x, 4);
-    const float im1 = c.y, ii1 = c.z, im2 = c.w;
-    const float nx = a.x, ny = a.y, tx = -ny, ty = nx;
-    // expand to ContactLimiterPacked order (ref: Solver.h:7-24): projectors, angular, compMass, compInvMass
-    float* o = out;
-    *o++ = nx; *o++ = ny; *o++ = -nx; *o++ = -ny; *o++ = a.z; *o++ = a.w;
-    *o++ = nx * im1; *o++ = ny * im1; *o++ = (-nx) * im2; *o++ = (-ny) * im2; *o++ = a.z * ii1; *o++ = a.w * ii2; *o++ = c.x;
-    *o++ = 0.f; *o++ = f.w; *o++ = d.x; *o++ = d.y;
-    *o++ = tx; *o++ = ty; *o++ = -tx; *o++ = -ty; *o++ = f.x; *o++ = f.y;
-    *o++ = tx * im1; *o++ = ty * im1; *o++ = (-tx) * im2; *o++ = (-ty) * im2; *o++ = f.x * ii1; *o++ = f.y * ii2; *o++ = f.z;
-    (void)acc;
-    return PHX_OK;
-}
-
-// One private copy of the solver's in/out arrays per timed step — the resident velocities (body_view.h) and the joints — made
-// outside the timed region: bench() then solves copy k in step k instead of restoring one working copy in front of every step (copy
-// dispatches that are the bench's own scaffolding, not SolveJoints).  The records the caller hands over are converted to the
-// resident layout here, before the clock starts: the timed solves run on HBM-resident inputs in the layout the World keeps
-// them in.  Consumed by the next bench() call on the same arrays.
-int DeviceSolver::bench_stage(const void* d_bodies, int nb, const void* d_joints, int nj, int steps)
-{
-    PHX_REQUIRE(nb >= 0 && nj >= 0 && steps >= 0 && steps <= 4096, "bad bench_stage arguments");
-    PHX_TRY(use_device(device_));
-    PHX_TRY(synchronize());
-    staged_steps_ = 0;
-    const size_t bytes = (size_t)steps * ((size_t)nb * 2 * sizeof(float4) + (size_t)nj * sizeof(phx_contact_joint));
-    if (!steps || bytes > (8ull << 30)) return PHX_OK;      // too big to stage: bench() restores in front of every step
-    PHX_TRY(stage_vel_.reserve(std::max<size_t>((size_t)steps * nb, 1)));
-    PHX_TRY(stage_dvel_.reserve(std::max<size_t>((size_t)steps * nb, 1)));
-    PHX_TRY(stage_mpos_.reserve(std::max<size_t>(nb, 1)));
-    PHX_TRY(stage_joints_.reserve(std::max<size_t>((size_t)steps * nj, 1)));
-    for (int k = 0; k < steps; ++k) {
-        if (nb) hipLaunchKernelGGL(k_bodies_to_view, dim3(grid_for(nb)), dim3(256), 0, stream_, static_cast<const phx_rigid_body*>(d_bodies), nb,
-                                   BodyView{stage_vel_.p + (size_t)k * nb, stage_dvel_.p + (size_t)k * nb, stage_mpos_.p});
-        if (nj) PHX_HIP(hipMemcpyAsync(stage_joints_.p + (size_t)k * nj, d_joints, (size_t)nj * sizeof(phx_contact_joint), hipMemcpyDeviceToDevice, stream_));
-    }
-    PHX_HIP(hipGetLastError());
-    PHX_HIP(hipStreamSynchronize(stream_));
-    staged_src_bodies_ = d_bodies; staged_src_joints_ = d_joints; staged_nb_ = nb; staged_nj_ = nj; staged_steps_ = steps;
-    return PHX_OK;
-}
-
-int DeviceSolver::bench(const void* d_bodies, int nb, const void* d_cps, int ncp, const void* d_joints, int nj,
-                        const phx_config& cfg, int warmup, int steps, phx_bench_result* out, phx_step_hook hook, void* user)
-{
-    PHX_REQUIRE(out && warmup >= 0 && steps >= 0 && steps <= 4096, "bad bench arguments");
-    PHX_TRY(use_device(device_));
-    PHX_TRY(snap_vel_.reserve(std::max(nb, 1))); PHX_TRY(snap_dvel_.reserve(std::max(nb, 1))); PHX_TRY(snap_mpos_.reserve(std::max(nb, 1)));
-    PHX_TRY(snap_joints_.reserve(std::max(nj, 1)));
-    std::memset(out, 0, sizeof *out);
-    while ((int)bench_events_.size() < 2 * steps + 2) { hipEvent_t e; PHX_HIP(hipEventCreate(&e)); bench_events_.push_back(e); }
-    // every step solves the SAME input: its own staged copy (bench_stage, made before the clock started), or — warm-up steps, or
-    // nothing staged — a working copy restored from the caller's (untouched) arrays in front of the step
-    const bool staged = staged_steps_ >= steps && steps > 0 && staged_src_bodies_ == d_bodies && staged_src_joints_ == d_joints && staged_nb_ == nb && staged_nj_ == nj;
-    staged_steps_ = 0;                                       // (consumed: the solves overwrite the copies)
-    auto one_step = [&](int k) -> int {
-        BodyView b{snap_vel_.p, snap_dvel_.p, snap_mpos_.p}; phx_contact_joint* j = snap_joints_.p;
-        if (staged && k >= 0) { b = BodyView{stage_vel_.p + (size_t)k * nb, stage_dvel_.p + (size_t)k * nb, stage_mpos_.p}; j = stage_joints_.p + (size_t)k * nj; }
-        else {
-            if (nb) hipLaunchKernelGGL(k_bodies_to_view, dim3(grid_for(nb)), dim3(256), 0, stream_, static_cast<const phx_rigid_body*>(d_bodies), nb, b);
-            if (nj) PHX_HIP(hipMemcpyAsync(j, d_joints, (size_t)nj * sizeof(phx_contact_joint), hipMemcpyDeviceToDevice, stream_));
-        }
-        PHX_TRY(solve_resident(b, nb, d_cps, ncp, j, nj, cfg));
-        bench_last_b_ = b; bench_last_j_ = j; bench_last_nb_ = nb; bench_last_nj_ = nj;
-        if (xch_send_) {       // island-sharded solve: pack, the caller's all-gather (hook phase 2), unpack — all on the stream
-            PHX_TRY(exchange_pack_resident(&b, j, nullptr));
-            if (comm_) PHX_TRY(exchange_all_gather());      // native transport: RCCL on this stream, no callback
-            else if (hook && hook(user, step_hook_step_, 2)) { set_error("bench: step hook failed"); return PHX_ERR_STATE; }
-            PHX_TRY(exchange_unpack_resident(b, j));
-        }
-        return PHX_OK;
-    };
-    // the hook's phase 1 fires inside solve_device, between the step's fingerprint and its sweeps
-    struct HookScope {
-        DeviceSolver& s;
-        HookScope(DeviceSolver& s_, phx_step_hook h, void* u) : s(s_) { s.step_hook_ = h; s.step_hook_user_ = u; }
-        ~HookScope() { s.step_hook_ = nullptr; s.step_hook_user_ = nullptr; }
-    } scope(*this, hook, user);
-    for (int i = 0; i < warmup; ++i) {
-        step_hook_step_ = i - warmup;
-        PHX_TRY(one_step(-1));
-        if (hook && hook(user, i - warmup, 0)) { set_error("bench: step hook failed"); return PHX_ERR_STATE; }
-        PHX_TRY(synchronize());
-    }
-    if (!steps) { if (hook && warmup && hook(user, 0, 1)) { set_error("bench: step hook failed"); return PHX_ERR_STATE; } return PHX_OK; }
-    // timed steps are queued back to back; the device never waits for the host between them
-    // (the handle's own sweep events are put back — and the bracketing returned to whole solves — however this function leaves)
-    struct SweepEvents {
-        DeviceSolver& s; hipEvent_t b, e;
-        explicit SweepEvents(DeviceSolver& s_) : s(s_), b(s_.ev_sweep_begin_), e(s_.ev_sweep_end_) { s.time_sweeps_ = true; }
-        ~SweepEvents() { s.ev_sweep_begin_ = b; s.ev_sweep_end_ = e; s.time_sweeps_ = false; s.timed_sweeps_ = false; }
-    } sweep_events(*this);
-    int st = PHX_OK;
-    struct InLoop { DeviceSolver& s; explicit InLoop(DeviceSolver& s_) : s(s_) { s.in_bench_loop_ = true; } ~InLoop() { s.in_bench_loop_ = false; } } in_loop(*this);
-    struct Trusted { DeviceSolver& s; Trusted(DeviceSolver& s_, bool on) : s(s_) { s.bench_trusted_ = on; } ~Trusted() { s.bench_trusted_ = false; } } trusted(*this, staged && reuse_schedule_ && opt_.speculate);
-    PHX_HIP(hipEventRecord(bench_events_[2 * steps], stream_));
-    // HIP events bracket the sweep launches of every 4th step only: an event record is a barrier packet of its own (~3 us of idle
-    // queue), and bracketing every step's sweeps cost 6.4 us per step — 7 % of the value being measured (tools/exp_events.py)
-    // (PHX_BENCH_BRACKET_STRIDE=n, measurement of the measurement: 1 = every step, 0 = no events at all — tools/exp_events.py)
-    const char* bs_env = getenv("PHX_BENCH_BRACKET_STRIDE");
-    const int bracket_stride = bs_env ? (atoi(bs_env) > 0 ? atoi(bs_env) : steps + 1) : (steps >= 8 ? 4 : 1);
-    const bool bracket_any = !(bs_env && atoi(bs_env) <= 0);
-    for (int i = 0; i < steps && st == PHX_OK; ++i) {
-        time_sweeps_ = bracket_any && i % bracket_stride == 0;
-        if (time_sweeps_) { ev_sweep_begin_ = bench_events_[2 * i]; ev_sweep_end_ = bench_events_[2 * i + 1]; }      // (else: still the last bracketed step's pair — a
-                                                                                                                  //  solve settled later reads the pair it recorded)
-        step_hook_step_ = i;
-        st = one_step(i);
-        if (st == PHX_OK && hook && hook(user, i, 0)) { set_error("bench: step hook failed"); st = PHX_ERR_STATE; }
-    }
-    if (st == PHX_OK && hook && hook(user, steps, 1)) { set_error("bench: step hook failed"); st = PHX_ERR_STATE; }      // drain the last exchange
-    PHX_TRY(st);
-    PHX_HIP(hipEventRecord(bench_events_[2 * steps + 1], stream_));
-    const unsigned replays = replays_;
-    if (bench_trusted_ && !pending_.active) {       // staged copies: the last step's fingerprint comes back with its counters
-        unsigned long long fp = 0;
-        PHX_TRY(collect_stats(&fp, hash_.p + hash_slot_));
-        if (fp != gate_expected_) { set_error("bench: a staged copy of the input did not match the schedule's topology"); return PHX_ERR_STATE; }
-    } else PHX_TRY(synchronize());
-    if (replays_ != replays && reuse_schedule_) { set_error("bench: topology changed during the timed region"); return PHX_ERR_STATE; }
-    float ms = 0.f;
-    PHX_HIP(hipEventSynchronize(bench_events_[2 * steps + 1]));      // (reached long ago — the mailbox post ran behind it — but the runtime may not have looked yet)
-    PHX_HIP(hipEventElapsedTime(&ms, bench_events_[2 * steps], bench_events_[2 * steps + 1]));
-    out->total_ms = ms;
-    for (int i = 0; bracket_any && i < steps; i += bracket_stride) {
-        PHX_HIP(hipEventElapsedTime(&ms, bench_events_[2 * i], bench_events_[2 * i + 1]));
-        out->impulse_kernel_ms += ms;
-    }
-    // identical input every step => identical counters every step
-    out->impulse_launches = (long long)sweep_launches_ * steps;
-    out->bracketed_launches = bracket_any ? (long long)sweep_launches_ * ((steps + bracket_stride - 1) / bracket_stride) : 0;
-    out->impulse_iterations = (long long)stats_.impulse_iterations * steps;
-    out->joint_visits = stats_.joint_visits * steps;
-    return PHX_OK;
-}
-
-// position-sensitive sum of the result words (order of the threads does not matter: a sum of mixed (index, bits) terms)
-static __global__ void __launch_bounds__(256) k_result_checksum(BodyView b, int nb, const phx_contact_joint* __restrict__ joints, int nj, unsigned long long* out)
-{
-    unsigned long long h = 0;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nb; i += gridDim.x * blockDim.x) {
-        const float4 v = b.vel[i], d = b.dvel[i];
-        const unsigned w[6] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z)};
-        for (int k = 0; k < 6; ++k) h += mix64(((unsigned long long)(6u * (unsigned)i + k + 1u) << 32) | w[k]);
-    }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nj; i += gridDim.x * blockDim.x) {
-        const phx_contact_joint j = joints[i];
-        h += mix64(0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1) + __float_as_uint(j.normal_accumulated_impulse));
-        h += mix64(0xC2B2AE3D27D4EB4Full * (unsigned long long)(i + 1) + __float_as_uint(j.friction_accumulated_impulse));
-    }
-    for (int off = 32; off > 0; off >>= 1) h += __shfl_down(h, off);
-    if ((threadIdx.x & 63) == 0 && h) atomicAdd(out, h);
-}
-
-int DeviceSolver::bench_checksum(unsigned long long* out)
-{
-    PHX_REQUIRE(out, "null output");
-    PHX_TRY(use_device(device_));
-    PHX_TRY(synchronize());
-    if (!bench_last_j_ && !bench_last_b_.vel) { set_error("bench_checksum: no bench step has run"); return PHX_ERR_STATE; }
-    unsigned long long* d = nullptr;
-    PHX_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof *d));
-    hipError_t e = hipMemsetAsync(d, 0, sizeof *d, stream_);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_result_checksum, dim3(512), dim3(256), 0, stream_, bench_last_b_, bench_last_nb_, bench_last_j_, bench_last_nj_, d);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d, sizeof *out, hipMemcpyDeviceToHost, stream_);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream_);
-    (void)hipFree(d);
-    if (e != hipSuccess) { set_error("bench_checksum: %s", hipGetErrorString(e)); return PHX_ERR_HIP; }
     return PHX_OK;
 }
 

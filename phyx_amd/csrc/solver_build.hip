@@ -9,7 +9,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
-#include <numeric>
 
 namespace phx {
 
@@ -28,7 +27,13 @@ __global__ void __launch_bounds__(256) k_extract_topology(const phx_contact_join
         is_static[i] = (mpos[i].x == 0.f && mpos[i].y == 0.f) ? 1 : 0;
 }
 
-static inline int grid_for(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }
+// the two workgroup shapes of the island kernel as the binning's caps: units = lanes, joints = twice that
+static LdsCaps island_caps(bool big)
+{
+    LdsCaps k;
+    k.max_units = big ? ISL_T_BIG : ISL_T; k.max_joints = 2 * k.max_units; k.max_bodies = big ? ISL_B_BIG : ISL_B; k.max_colours = 64;
+    return k;
+}
 
 int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_contact_joint* d_joints, int nj, int ncp, const phx_config& cfg, bool force_rebuild,
                                   bool known_changed)
@@ -55,12 +60,12 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
     ncp_ = ncp;
     force_host_builder_ = false;
     build_unverified_ = false;
+    // 2. does the cached schedule still hold?
     if (!(known_changed && device_builder)) {
         PHX_TRY(rb_.add(&fp, hash_.p + hash_slot_, sizeof fp, stream_));
         PHX_TRY(rb_.wait(stream_));
         have_fp = true;
-        const unsigned long long mixed = fp ^ ((unsigned long long)(unsigned)nj << 32) ^ (unsigned)nb;
-        if (!force_rebuild && !known_changed && sched_.valid && sched_.fingerprint == mixed && nb == nb_ && nj == nj_ && sched_.islands == want_islands) {
+        if (!force_rebuild && !known_changed && sched_.valid && sched_.fingerprint == mixed_fingerprint(fp, nb, nj) && nb == nb_ && nj == nj_ && sched_.islands == want_islands) {
             raw_fingerprint_ = fp; gate_expected_ = fp; have_hash_ = true;
             return PHX_OK;
         }
@@ -68,7 +73,7 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
 
     tables_pending_ = false;      // (a rebuild: whatever the last speculative build left unfetched on the device is about to be overwritten)
     class_tab_ok_ = false;        // (... and the HBM group's class table belongs to the schedule that is being replaced)
-    // 2. topology changed.  Schedules are built on the device (only component sizes cross PCIe); the host builder below is
+    // 3. topology changed.  Schedules are built on the device (only component sizes cross PCIe); the host builder below is
     //    the specification and the fallback (bins that exceed the caps, more than 64 colours, ...).
     if (device_builder) {
         bool fallback = false;
@@ -82,9 +87,8 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
             PHX_TRY(rb_.add(&fp, hash_.p + hash_slot_, sizeof fp, stream_));
             PHX_TRY(rb_.wait(stream_));
         }
-        have_fp = true;
         if (!fallback) {
-            sched_.fingerprint = fp ^ ((unsigned long long)(unsigned)nj << 32) ^ (unsigned)nb;
+            sched_.fingerprint = mixed_fingerprint(fp, nb, nj);
             raw_fingerprint_ = fp;
             have_hash_ = !no_hash && !spec_bins_pending_;      // (a speculative build's hash comes back when the solve is settled)
             spec_hash_ran_ = !no_hash;
@@ -98,8 +102,13 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
         build_unverified_ = false;                     // (the host builder's schedules need no verification)
         if (opt_.trace_schedule || getenv("PHX_TRACE_SPEC")) fprintf(stderr, "[schedule] the device builder handed %d joints to the host builder\n", nj);
     }
-    const unsigned long long raw = fp;
-    fp ^= ((unsigned long long)(unsigned)nj << 32) ^ (unsigned)nb;
+    // 4. the host builder, on everything the device builder does not take
+    return build_schedule_host(d_bodies, nb, d_joints, nj, want_islands, fp);
+}
+
+// The host builder's leg of ensure_schedule: the joints' topology comes to the host, schedule.hip builds the schedule, its tables go up.
+int DeviceSolver::build_schedule_host(const float4* d_bodies, int nb, const phx_contact_joint* d_joints, int nj, bool want_islands, unsigned long long raw)
+{
     const bool trace = opt_.trace_schedule;
     auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (!trace) return; auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[schedule] %-18s %.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t0).count()); t0 = n; };
@@ -129,10 +138,7 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
         if ((unsigned)b1[j] >= (unsigned)nb || (unsigned)b2[j] >= (unsigned)nb) { sched_.valid = false; set_error("joint %d references body out of range", j); return PHX_ERR_INVALID; }
     }
     if (want_islands) {
-        LdsCaps caps;
-        caps.max_units = ISL_T; caps.max_joints = 2 * ISL_T; caps.max_bodies = ISL_B; caps.max_colours = 64;
-        LdsCaps big;
-        big.max_units = ISL_T_BIG; big.max_joints = 2 * ISL_T_BIG; big.max_bodies = ISL_B_BIG; big.max_colours = 64;
+        const LdsCaps caps = island_caps(false), big = island_caps(true);
         build_island_schedule(b1.data(), b2.data(), nj, is_static.data(), nb, caps, sched_, &big, prio_id.data());
     } else {
         build_colour_schedule(b1.data(), b2.data(), nj, is_static.data(), nb, sched_, prio_id.data());
@@ -212,7 +218,7 @@ int DeviceSolver::ensure_schedule(const float4* d_bodies, int nb, const phx_cont
     PHX_TRY(upload_part_tables());
     PHX_HIP(hipStreamSynchronize(stream_));
     lap("upload");
-    sched_.fingerprint = fp;
+    sched_.fingerprint = mixed_fingerprint(raw, nb, nj);
     raw_fingerprint_ = raw; gate_expected_ = raw; have_hash_ = true;
     sched_.valid = true;
     ++schedule_version_;
@@ -394,38 +400,15 @@ int DeviceSolver::build_schedule_device(const float4* d_bodies, int nb, const ph
     ncomp_guess_ = ncomp;
     for (int c = 0; c < ncomp && !any_partitioned; ++c) any_partitioned = comp_size[c] > (unsigned)COLOUR_B_MAX_JOINTS;      // (schedule.h: such a component is partitioned)
 
-    // 3. host: GatherIslands' published numbers, workgroup shape, greedy binning of consecutive components
-    //    (identical to schedule.hip::build_island_schedule — ncomp integers of work)
-    {
-        int run = 0, count = 0, mx = 0;
-        for (int c = 0; c < ncomp; ++c) {
-            run += (int)comp_size[c];
-            if (run >= 256 || (run > 0 && c == ncomp - 1)) { ++count; mx = std::max(mx, run); run = 0; }
-        }
-        sc.island_count = count; sc.island_max_size = mx;
-    }
-    // the workgroup shape: units = lanes of the island kernel, joints = twice that; the roomier shape only if some component
-    // needs it and fits it (identical to schedule.hip::build_island_schedule)
-    int cap_units = ISL_T, cap_bodies = ISL_B;
-    auto fits = [&](int c, int units) { return (int)comp_size[c] <= 2 * units && (int)comp_units[c] <= units; };
-    for (int c = 0; c < ncomp; ++c) if (comp_size[c] && !fits(c, ISL_T) && fits(c, ISL_T_BIG)) { cap_units = ISL_T_BIG; cap_bodies = ISL_B_BIG; break; }
+    // 3. host: GatherIslands' published numbers, workgroup shape, greedy binning of consecutive components (schedule.h: the three
+    //    rules, shared with schedule.hip::build_island_schedule — ncomp integers of work)
+    const IslandNumbers isl = coalesce_islands(comp_size.data(), ncomp);
+    sc.island_count = isl.count; sc.island_max_size = isl.max_size;
+    const LdsCaps caps = island_caps(needs_big_shape(comp_size.data(), comp_units.data(), ncomp, island_caps(false), island_caps(true)));
+    const int cap_units = caps.max_units, cap_bodies = caps.max_bodies;
     sc.lds_lanes = cap_units;
     std::vector<int> bin_of(std::max(ncomp, 1), -1), rank_of(std::max(ncomp, 1), 0);     // rank of a component inside its bin (schedule.h: the colouring candidate is chosen per component)
-    {
-        int size = 0, units = 0, rank = 0;
-        bool open = false;
-        for (int c = 0; c < ncomp; ++c) {
-            if (c % BIN_CHUNK == 0) { open = false; size = 0; units = 0; }      // (schedule.h BINNING: a bin never spans a chunk boundary)
-            const int n = (int)comp_size[c], u = (int)comp_units[c];
-            if (n == 0) continue;
-            if (!want_islands || !fits(c, cap_units)) { open = false; size = 0; units = 0; continue; }     // -> HBM group (Single mode: every component)
-            if (!open || size + n > 2 * cap_units || units + u > cap_units) { sc.group_offsets.push_back(sc.group_offsets.back()); ++nbins; open = true; size = 0; units = 0; rank = 0; }
-            bin_of[c] = nbins - 1;
-            rank_of[c] = rank++;
-            size += n; units += u;
-            sc.group_offsets.back() += n;
-        }
-    }
+    nbins = bin_components(comp_size.data(), comp_units.data(), ncomp, caps, want_islands, bin_of.data(), rank_of.data(), sc.group_offsets);      // (Single mode: every component -> HBM group)
     lds_slots = sc.group_offsets.back();
     for (int c = 0; c < ncomp; ++c) if (bin_of[c] < 0) bin_of[c] = nbins;
     sc.lds_groups = nbins;
@@ -756,40 +739,6 @@ int DeviceSolver::build_bins_speculative(const float4* d_bodies, int nb, const p
     build_unverified_ = true;
     unverified_bins_ = grid;
     spec_bins_pending_ = true;
-    return PHX_OK;
-}
-
-// The LDS groups of a device-built schedule live in HBM; the query API (and the parity tests that replay the
-// schedule through the oracle) need them on the host.
-int DeviceSolver::materialise_schedule()
-{
-    PHX_TRY(fetch_build_tables());
-    if (sched_.lds_on_host) return PHX_OK;
-    const int lg = sched_.lds_groups;
-    const int lds_slots = lg ? sched_.group_offsets[lg] : 0;
-    std::vector<int> order(std::max(nj_, 1)), ncol(std::max(lg, 1));
-    std::vector<unsigned char> colour(std::max(lds_slots, 1));
-    PHX_TRY(use_device(device_));
-    if (nj_) PHX_HIP(hipMemcpy(order.data(), hbm_.order.p, (size_t)nj_ * sizeof(int), hipMemcpyDeviceToHost));
-    if (lds_slots) {
-        PHX_HIP(hipMemcpy(colour.data(), isl_.slot_colour.p, (size_t)lds_slots, hipMemcpyDeviceToHost));
-        PHX_HIP(hipMemcpy(ncol.data(), isl_.ncol.p, (size_t)lg * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    sched_.order.assign(order.begin(), order.begin() + nj_);
-    sched_.colour_offsets.assign(1, 0);
-    sched_.group_first_colour.assign(1, 0);
-    for (int g = 0; g < lg; ++g) {
-        std::vector<int> count(ncol[g], 0);
-        for (int s = sched_.group_offsets[g]; s < sched_.group_offsets[g + 1]; ++s) count[colour[s]]++;
-        int at = sched_.group_offsets[g];
-        for (int c = 0; c < ncol[g]; ++c) { at += count[c]; sched_.colour_offsets.push_back(at); }
-        sched_.group_first_colour.push_back((int)sched_.colour_offsets.size() - 1);
-    }
-    if (sched_.has_hbm_group()) {
-        for (size_t c = 1; c < sched_.hbm_colour_offsets.size(); ++c) sched_.colour_offsets.push_back(sched_.hbm_colour_offsets[c]);
-        sched_.group_first_colour.push_back((int)sched_.colour_offsets.size() - 1);
-    }
-    sched_.lds_on_host = true;
     return PHX_OK;
 }
 

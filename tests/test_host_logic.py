@@ -1,5 +1,7 @@
 """Host-side logic of the product that needs no GPU: scene generators, the colour schedule and the island
 partition (C++ code inside libphyx_amd.so, reached through its host-only C-ABI entry points)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -298,9 +300,10 @@ def test_exchange_layout_partitions_the_groups_over_the_ranks():
 BIN_CHUNK = 64          # csrc/schedule.h: a bin never spans a multiple of BIN_CHUNK component numbers
 
 
-def _greedy_bins(sizes, units, cap_units):
-    """The host loop of the schedule builder (csrc/solver_build.hip, step 3; csrc/schedule.hip): consecutive components packed greedily,
-    every chunk of BIN_CHUNK component numbers starting a fresh bin."""
+def _greedy_bins(sizes, units, cap_units, want_islands=True):
+    """The host rule of the schedule builders (csrc/schedule.h bin_components), restated: consecutive components packed greedily, every
+    chunk of BIN_CHUNK component numbers starting a fresh bin; a component that fits no workgroup (every one without islands) goes to
+    the HBM group (-1) and closes the bin, an empty one (-1 too) does not."""
     bin_of, rank_of, goff = [-1] * len(sizes), [0] * len(sizes), [0]
     size = unit = rank = 0
     opened = False
@@ -309,11 +312,52 @@ def _greedy_bins(sizes, units, cap_units):
             opened = False
         if n == 0:
             continue
+        if not want_islands or n > 2 * cap_units or u > cap_units:
+            opened = False
+            continue
         if not opened or size + n > 2 * cap_units or unit + u > cap_units:
             goff.append(goff[-1]); opened = True; size = unit = rank = 0
         bin_of[c] = len(goff) - 2; rank_of[c] = rank; rank += 1
         size += n; unit += u; goff[-1] += n
     return bin_of, rank_of, goff
+
+
+def _island_numbers(sizes):
+    """GatherIslands' coalescing rule (csrc/schedule.h coalesce_islands), restated: a run of components closes at >= 256 joints or at the end."""
+    runs = [0]
+    for n in sizes:
+        runs[-1] += n
+        if runs[-1] >= 256:
+            runs.append(0)
+    runs = [r for r in runs if r > 0]
+    return len(runs), max(runs, default=0)
+
+
+def _shape(sizes, units, small, big):
+    """The workgroup shape (csrc/schedule.h needs_big_shape), restated: the roomier one iff a non-empty component fits it but not the small one."""
+    fits = lambda n, u, lanes: n <= 2 * lanes and u <= lanes
+    return big if big and any(n and not fits(n, u, small) and fits(n, u, big) for n, u in zip(sizes, units)) else small
+
+
+def _schedule_bins(lib, sizes, units, small, big, want_islands=1):
+    """phx_debug_schedule_bins: (lanes, bin_of, rank_of, group_offsets, (island count, island max size)) by the library's own rules."""
+    n = len(sizes)
+    a, u = np.asarray(sizes, np.int32).reshape(n), np.asarray(units, np.int32).reshape(n)
+    bin_of, rank_of, goff = np.full(n, -7, np.int32), np.full(n, -7, np.int32), np.full(n + 1, -7, np.int32)
+    lanes, bins, icount, imax = (C.c_int32(-7) for _ in range(4))
+    st = lib.phx_debug_schedule_bins(a.ctypes.data, u.ctypes.data, n, small, big, want_islands, C.byref(lanes), bin_of.ctypes.data, rank_of.ctypes.data,
+                                     goff.ctypes.data, C.byref(bins), C.byref(icount), C.byref(imax))
+    assert st == 0, lib.phx_last_error()
+    assert 0 <= bins.value <= n
+    return lanes.value, bin_of.tolist(), rank_of.tolist(), goff[:bins.value + 1].tolist(), (icount.value, imax.value)
+
+
+def _assert_bins_as_restated(lib, sizes, units, small, big, want_islands=1):
+    got = _schedule_bins(lib, sizes, units, small, big, want_islands)
+    lanes = _shape(sizes, units, small, big)
+    g = _greedy_bins(sizes, units, lanes, bool(want_islands))
+    assert got == (lanes, g[0], g[1], g[2], _island_numbers(sizes)), (sizes, units, small, big, want_islands)
+    return got
 
 
 def _chunk_bins(sizes, units, cap_units):
@@ -347,9 +391,9 @@ def _chunk_bins(sizes, units, cap_units):
     return out
 
 
-def test_binning_by_chunks_equals_the_greedy_loop():
+def test_binning_by_chunks_equals_the_greedy_loop(built_lib):
     """The device's binning (a lane per chunk of 64 components, a scan over the lanes) against the sequential loop of the host
-    builders, on random component sizes incl. empty components, components that fill a bin alone and long runs of tiny ones;
+    builders — restated here AND as the library runs it (phx_debug_schedule_bins) —, on random component sizes incl. empty components, components that fill a bin alone and long runs of tiny ones;
     and what the chunk rule costs in bins against unbroken greedy packing."""
     rng = np.random.default_rng(7)
     for case in range(300):
@@ -370,9 +414,57 @@ def test_binning_by_chunks_equals_the_greedy_loop():
         g = _greedy_bins(list(map(int, sizes)), list(map(int, units)), cap)
         c = _chunk_bins(list(map(int, sizes)), list(map(int, units)), cap)
         assert g[0] == c[0] and g[1] == c[1] and g[2] == c[2], (case, n, cap)
+        lib = _assert_bins_as_restated(built_lib, list(map(int, sizes)), list(map(int, units)), cap, 0)
+        assert lib[0] == cap and (lib[1], lib[2], lib[3]) == c, (case, n, cap)
     # the price of the chunk boundaries: the 1e4 columns of the 1M-box world (206-joint components, two to a bin)
     sizes, units = [206] * 10000, [103] * 10000
     assert len(_greedy_bins(sizes, units, 256)[2]) - 1 == 5000
+
+
+
+
+def test_host_rules_at_their_edges(built_lib):
+    """The binning, shape and island rules of csrc/schedule.h at their edges, through phx_debug_schedule_bins: every case equals the Python
+    restatements above, and shows the property it was made for."""
+    cap, big = 256, 512
+    check = lambda sizes, units, big_lanes=0, want=1: _assert_bins_as_restated(built_lib, sizes, units, cap, big_lanes, want)
+    # exactly 2 * cap joints and cap units: fits, alone in its bin
+    assert check([10, 2 * cap, 10], [5, cap, 5])[1:4] == ([0, 1, 2], [0, 0, 0], [0, 10, 10 + 2 * cap, 20 + 2 * cap])
+    # one joint more: the HBM group, and the bin before it is closed
+    assert check([10, 2 * cap + 1, 10], [5, cap, 5])[1:4] == ([0, -1, 1], [0, 0, 0], [0, 10, 20])
+    # a component whose units overflow the cap while its joints do not, and the other way round
+    assert check([10, cap + 1, 10], [5, cap + 1, 5])[1] == [0, -1, 1]
+    assert check([10, 2 * cap + 2, 10], [5, cap, 5])[1] == [0, -1, 1]
+    # ... and a bin that the next component's units (joints) would overflow while its joints (units) would not
+    assert check([200, 200, 100], [150, 150, 50])[1:3] == ([0, 1, 1], [0, 0, 1])
+    assert check([300, 300, 100], [10, 10, 10])[1:3] == ([0, 1, 1], [0, 0, 1])
+    assert check([256, 256], [128, 128])[1:3] == ([0, 0], [0, 1])                       # (exactly full)
+    # 65 components of one joint: the bin breaks between components 63 and 64
+    assert check([1] * 65, [1] * 65)[1:4] == ([0] * 64 + [1], list(range(64)) + [0], [0, 64, 65])
+    # an empty component at index 64, then a small one: the chunk boundary still opens a fresh bin
+    assert check([1] * 64 + [0, 1], [1] * 64 + [0, 1])[1:4] == ([0] * 64 + [-1, 1], list(range(64)) + [0, 0], [0, 64, 65])
+    assert check([1, 0, 0, 1], [1, 0, 0, 1])[1:3] == ([0, -1, -1, 0], [0, 0, 0, 1])     # (inside a chunk an empty component closes nothing)
+    # nothing to bin
+    assert check([0] * 70, [0] * 70)[1:] == ([-1] * 70, [0] * 70, [0], (0, 0))
+    assert check([], []) == (cap, [], [], [0], (0, 0))
+    # a component that fits only the big shape: every group takes it
+    assert check([10, 600, 10], [5, 300, 5], big)[:4] == (big, [0, 0, 0], [0, 1, 2], [0, 620])
+    assert check([10, 200, 10], [5, 300, 5], big)[0] == big                                # (by its units alone)
+    assert check([10, 600, 10], [5, 300, 5], 0)[:2] == (cap, [0, -1, 1])                   # (no big shape on offer)
+    # a component that fits neither shape: the shape stays small, the component goes to the HBM group
+    assert check([10, 2 * big + 1, 10], [5, big, 5], big)[:2] == (cap, [0, -1, 1])
+    assert check([10, 0, 2 * big, 10], [5, 0, big + 1, 5], big)[:2] == (cap, [0, -1, -1, 1])
+    # no islands wanted: no bins, everything to the HBM group (GatherIslands' numbers stand)
+    assert check([10, 20, 0, 30], [5, 10, 0, 15], big, 0)[1:] == ([-1] * 4, [0] * 4, [0], (1, 60))
+    # island runs: exactly 256, 255 + 1, a trailing remainder, trailing empty components
+    assert check([256], [128])[4] == (1, 256)
+    assert check([255, 1], [128, 1])[4] == (1, 256)
+    assert check([255, 2, 1], [128, 1, 1])[4] == (2, 257)
+    assert check([256, 256, 3], [128, 128, 2])[4] == (3, 256)
+    assert check([100, 300, 100, 155], [50, 150, 50, 78])[4] == (2, 400)
+    assert check([256, 100, 0, 0], [128, 50, 0, 0])[4] == (2, 256)
+    assert check([256, 0, 0], [128, 0, 0])[4] == (1, 256)
+    assert check([0, 0, 7], [0, 0, 4])[4] == (1, 7)
 
 
 def _layout_classes(units, T):
