@@ -1217,7 +1217,7 @@ class World:
         while True:
             out = np.zeros(cap, dtype=break_event_dtype)
             st = self.L.phx_world_break_events(self.h, _ptr(out), cap, C.byref(total))
-            if st != -4 or total.value <= cap:
+            if st != _lib.PHX_ERR_CAPACITY or total.value <= cap:
                 break
             cap = int(total.value)                                 # (grown to what the call reported; the queue was kept)
         check(st)
@@ -1470,19 +1470,23 @@ class World:
             raise ValueError("query_aabb: every box must have min <= max")
         return self._overlaps(self.L.phx_world_query_aabb, b, skip_static)
 
-    def _overlaps(self, fn, b, skip_static):
+    def _listing(self, fn, rows, skip_static, dtype, cap):
+        """The lists of phx_world_query_aabb / _boxes / _contacts: a call with room for `cap` records and, if it reports
+        PHX_ERR_CAPACITY with a total that fits int32, one more with room for exactly that total.  Returns (offsets, records)."""
         flags = 1 if skip_static else 0
-        offsets = np.zeros(len(b) + 1, dtype=np.int32)
+        offsets = np.zeros(len(rows) + 1, dtype=np.int32)
         total = C.c_int64(0)
-        cap = max(1024, 4 * len(b))
-        for _ in range(2):                                         # (the second call with the size the first one reported)
-            hits = np.zeros(cap, dtype=np.int32)
-            st = fn(self.h, _ptr(b), len(b), flags, _ptr(offsets), _ptr(hits), cap, C.byref(total))
-            if st != -4 or total.value > np.iinfo(np.int32).max:
+        for _ in range(2):
+            out = np.zeros(cap, dtype=dtype)
+            st = fn(self.h, _ptr(rows), len(rows), flags, _ptr(offsets), _ptr(out), cap, C.byref(total))
+            if st != _lib.PHX_ERR_CAPACITY or total.value > np.iinfo(np.int32).max:
                 break
             cap = int(total.value)
         check(st)
-        return offsets, hits[:total.value].copy() if total.value < cap else hits
+        return offsets, out[:total.value].copy() if total.value < cap else out
+
+    def _overlaps(self, fn, b, skip_static):
+        return self._listing(fn, b, skip_static, np.int32, max(1024, 4 * len(b)))
 
     def query_points(self, points, skip_static=False):
         """For each point (K, 2), the lowest index of a body whose box contains it, -1 if none (int32)."""
@@ -1554,18 +1558,7 @@ class World:
         idx = self._indices(bodies, "contacts")
         if idx.size and idx.min() < 0:
             raise ValueError("contacts: negative body index")
-        flags = 1 if skip_static else 0
-        offsets = np.zeros(len(idx) + 1, dtype=np.int32)
-        total = C.c_int64(0)
-        cap = max(256, 8 * len(idx))
-        for _ in range(2):                                         # (the second call with the size the first one reported)
-            out = np.zeros(cap, dtype=contact_dtype)
-            st = self.L.phx_world_query_contacts(self.h, _ptr(idx), len(idx), flags, _ptr(offsets), _ptr(out), cap, C.byref(total))
-            if st != -4 or total.value > np.iinfo(np.int32).max:
-                break
-            cap = int(total.value)
-        check(st)
-        return offsets, out[:total.value].copy() if total.value < cap else out
+        return self._listing(self.L.phx_world_query_contacts, idx, skip_static, contact_dtype, max(256, 8 * len(idx)))
 
     def contact_events(self):
         """Touch events since the last call: (begin, end), (K, 2) int32 arrays of {body1, body2} pairs sorted ascending; the pairs that
@@ -1576,7 +1569,7 @@ class World:
             begin = np.zeros((caps[0], 2), dtype=np.int32)
             end = np.zeros((caps[1], 2), dtype=np.int32)
             st = self.L.phx_world_contact_events(self.h, _ptr(begin), caps[0], C.byref(bt), _ptr(end), caps[1], C.byref(et))
-            if st != -4:
+            if st != _lib.PHX_ERR_CAPACITY:
                 break
             caps = [max(caps[0], int(bt.value)), max(caps[1], int(et.value))]
         check(st)

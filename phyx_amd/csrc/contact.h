@@ -2,11 +2,13 @@
 // resident contact cache, its body count, its contact epoch and its stream; everything is queued on that stream.  The contact index (a
 // body -> (other, manifold) incidence in CSR form) is built by the first index-path call after the contact cache changed and kept while
 // the epoch stays.  The events' baseline B (sorted (body1, body2) keys) lives here too.
+// What is left here is the reports' own: the threshold, the index, which kernels count and fill, the events and the markers.  The
+// path choice, the index stamp and the two-pass protocol of the contact lists are listing.h's.
 #pragma once
 
 #include "body_view.h"
 #include "sleep.h"
-#include "device_scan.h"
+#include "listing.h"
 
 #include <cstdint>
 #include <utility>
@@ -25,7 +27,6 @@ struct ContactCache {
 
 class DeviceContacts {
 public:
-    enum Path { AUTO = 0, SCAN = 1, INDEX = 2 };
     // the scan path answers up to this many listed bodies, the index larger batches: the largest batch at which tools/contact_cost.py
     // measured the scan faster at cfg 2, each call after a step so that the index pays its build (512 scan 0.40 ms /
     // index 0.44 ms, 768 scan 0.54 / index 0.49; sizes between two measured ones are not measured)
@@ -34,13 +35,13 @@ public:
     // PHX_CONTACT_PATH=scan|index forces a path; PHX_CONTACT_SCAN_CHUNK=q (1 .. 1024) lowers the listed bodies per chunk of the scan
     // path.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
     int configure_from_env();
-    Path choose(int count) const { return forced_ != AUTO ? forced_ : (count <= SCAN_MAX ? SCAN : INDEX); }
+    ReportPath choose(int count) const { return choose_path(forced_, count, SCAN_MAX); }
 
     // d_bodies: the listed bodies on the device (checked by the caller).  Host outputs; waits through `rb`.
     int contacts(const ContactCache& c, unsigned long long epoch, const int* d_bodies, int count, int flags, int32_t* offsets, phx_contact* out,
                  int cap, int64_t* total, Readback& rb, hipStream_t s);
     int ensure_index(const ContactCache& c, unsigned long long epoch, hipStream_t s);
-    int index_builds() const { return builds_; }
+    int index_builds() const { return index_.builds(); }
 
     // T(s) \ B and B \ T(s) into host memory; B := T(s) only when both fit
     int events(const ContactCache& c, int32_t* begin, int begin_cap, int64_t* begin_total, int32_t* end, int end_cap, int64_t* end_total,
@@ -65,25 +66,23 @@ private:
                       Readback& rb, hipStream_t s);
     int index_contacts(const ContactCache& c, const int* d_bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total,
                        Readback& rb, hipStream_t s);
-    int offsets_from_counts(int count, int32_t* offsets, int cap, int64_t* total, bool* fits);
 
-    Path forced_ = AUTO;
+    ReportPath forced_ = PATH_AUTO;
     int scan_chunk_ = 256;
     // the index
-    bool built_ = false;
-    unsigned long long built_epoch_ = 0;
-    int built_n_ = -1, builds_ = 0;
+    IndexStamp index_;
     const unsigned* entries_ = nullptr;
-    DevBuf<unsigned> offsets_, keys0_, vals0_, keys1_, vals1_, hist_;
+    RadixPairs idx_sort_;
+    DevBuf<unsigned> offsets_, hist_;
     ScanScratch scan_;
     // per-call scratch
-    DevBuf<unsigned> qcount_, qseg_;
+    Listing list_;
     DevBuf<phx_contact> recs_, sorted_;
-    std::vector<unsigned> counts_;
     // events
     DevBuf<unsigned long long> base_, base_spare_, t_;
     int base_n_ = 0;
-    DevBuf<unsigned> ev_k0_, ev_v0_, ev_k1_, ev_v1_, ev_pos_, ev_tot_;
+    RadixPairs ev_sort_;
+    DevBuf<unsigned> ev_pos_, ev_tot_;
     DevBuf<int2> ev_begin_, ev_end_;
 };
 

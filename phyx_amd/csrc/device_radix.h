@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "device_scan.h"
+#include "listing.h"
 
 #include <algorithm>
 
@@ -136,6 +137,16 @@ static inline int device_radix_sort_pairs(unsigned* k0, unsigned* v0, unsigned* 
         }
     PHX_HIP(hipGetLastError());
     *result_buffer = n > 0 ? src : (passes & 1);      // (an empty sort launched nothing: the roles change all the same)
+    return PHX_OK;
+}
+
+// listing.h's RadixPairs (the buffers of a sort and who holds what) sorts here: its declaration is free of kernels, for the headers
+// that hold one.
+inline int RadixPairs::sort(int n, int bits, unsigned* hist, ScanScratch& scan_scratch, hipStream_t stream)
+{
+    int landed = 0;
+    PHX_TRY(device_radix_sort_pairs(keys(), vals(), spare_keys(), spare_vals(), n, bits, hist, scan_scratch, stream, &landed));
+    if (landed) { std::swap(k_, sk_); std::swap(v_, sv_); }
     return PHX_OK;
 }
 

@@ -1,19 +1,21 @@
 // query.h — the World's queries (include/phyx_amd.h, QUERIES): the host side of query_kernels.h.  The World hands over its resident
 // arrays, its body count, its geometry epoch and its stream; everything is queued on that stream.  The query index (a 64-wide tree over
 // the bodies in Morton order) is built by the first index-path query after the geometry changed and kept while the epoch stays.
+// What is left here is the queries' own: the thresholds, the index and its tree, the scan's (query, body block) table and which
+// kernels count and fill.  The path choice, the index stamp and the two-pass protocol of the overlap lists are listing.h's.
 #pragma once
 
 #include "body_view.h"
-#include "device_scan.h"
+#include "listing.h"
 
 #include <cstdint>
-#include <vector>
 
 namespace phx {
 
+struct QTree;
+
 class DeviceQuery {
 public:
-    enum Path { AUTO = 0, SCAN = 1, INDEX = 2 };
     enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2, QUERY_SHAPES = 3, QUERY_CASTS = 4 };      // (BOXES: AABBs; SHAPES: oriented boxes)
     // the scan path answers batches up to this many queries of each kind, the index larger ones: the largest batch size at which
     // tools/query_cost.py measured the scan faster at cfg 2, each call after a step so that the index pays its build (INTEGRATION.md
@@ -25,7 +27,7 @@ public:
     // PHX_QUERY_PATH=scan|index forces a path; PHX_QUERY_SCAN_CHUNK=q (a multiple of 64) lowers the queries per chunk of the scan path's
     // AABB table.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
     int configure_from_env();
-    Path choose(Kind kind, int count) const { return forced_ != AUTO ? forced_ : (count <= SCAN_MAX[kind] ? SCAN : INDEX); }
+    ReportPath choose(Kind kind, int count) const { return choose_path(forced_, count, SCAN_MAX[kind]); }
 
     // device inputs and outputs; d_body gets -1 where no body contains the point
     int points(const WorldBodies& w, int n, unsigned long long epoch, const float* d_pts, int count, int flags, int* d_body, hipStream_t s);
@@ -39,7 +41,7 @@ public:
     int casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s);
     // the index alone (tools/query_cost.py times it): built unless it is current
     int ensure_index(const WorldBodies& w, int n, unsigned long long epoch, hipStream_t s);
-    int index_builds() const { return builds_; }
+    int index_builds() const { return index_.builds(); }
 
 private:
     // OBB: oriented boxes instead of AABBs
@@ -54,25 +56,24 @@ private:
                    int64_t* total, Readback& rb, hipStream_t s);
     template <bool CAST, class Hit>
     int closest(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, Hit* d_out, hipStream_t s);
-    int offsets_from_counts(const char* what, int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits);
+    // the current index over n bodies, as the kernels take it
+    QTree tree(int n) const;
 
-    Path forced_ = AUTO;
+    ReportPath forced_ = PATH_AUTO;
     int scan_chunk_ = INT32_MAX;
-    // the index
-    bool built_ = false;
-    unsigned long long built_epoch_ = 0;
-    int built_n_ = -1, builds_ = 0;
+    // the index: the bodies in Morton order are sort_.vals()
+    IndexStamp index_;
     int levels_ = 0, level_off_[8] = {0}, level_cnt_[8] = {0};
-    const unsigned* perm_ = nullptr;
-    DevBuf<unsigned> keys0_, vals0_, keys1_, vals1_, hist_, bounds_;
+    RadixPairs sort_;
+    DevBuf<unsigned> hist_, bounds_;
     DevBuf<float4> nodes_;
     ScanScratch scan_;
     // per-call scratch
     DevBuf<unsigned long long> ray_keys_;
-    DevBuf<unsigned> qcount_, qseg_, table_;
+    Listing list_;
+    DevBuf<unsigned> table_;
     DevBuf<int> hits_;
     DevBuf<unsigned> sort_k1_, sort_v0_, sort_v1_;
-    std::vector<unsigned> counts_;
 };
 
 } // namespace phx

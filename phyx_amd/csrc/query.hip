@@ -5,55 +5,49 @@
 #include "device_radix.h"
 
 #include <algorithm>
-#include <cstdlib>
-#include <cstring>
 
 static_assert(sizeof(phx_ray_hit) == 24, "phx_ray_hit is 24 bytes (include/phyx_amd.h)");
 static_assert(sizeof(phx_shape_hit) == 16, "phx_shape_hit is 16 bytes (include/phyx_amd.h)");
 
 namespace phx {
 
-static inline int qgrid(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }
 // tiles of one scan launch (gridDim.y): with up to 2048 body workgroups of 256 lanes a launch stays under 2^31 work-items
 constexpr int Q_MAX_TILES = 4096;
 // workgroups of the grid-strided per-query launches (4 queries per workgroup in k_qtree, 1 in k_qsort_segments)
 static inline int qtree_grid(int count) { return std::max(1, std::min(div_up(count, 4), 1 << 20)); }
-static inline int qsort_grid(int count) { return std::max(1, std::min(count, 1 << 16)); }
+// the scan's per-query launches over n bodies: launch(q0, grid) for each run of at most Q_MAX_TILES tiles of queries
+template <class Launch>
+static void scan_in_chunks(int n, int count, Launch launch)
+{
+    for (int q0 = 0; q0 < count; q0 += Q_MAX_TILES * Q_TILE) launch(q0, dim3(stream_grid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)));
+}
 
 int DeviceQuery::configure_from_env()
 {
-    const char* v = getenv("PHX_QUERY_PATH");
-    if (!v || !*v) forced_ = AUTO;
-    else if (!std::strcmp(v, "scan")) forced_ = SCAN;
-    else if (!std::strcmp(v, "index")) forced_ = INDEX;
-    else { set_error("PHX_QUERY_PATH=%s: expected scan or index (or unset)", v); return PHX_ERR_INVALID; }
-    const char* c = getenv("PHX_QUERY_SCAN_CHUNK");
-    if (c && *c) {
-        char* end = nullptr;
-        const long q = std::strtol(c, &end, 10);
-        if (*end || q < Q_TILE || q % Q_TILE) { set_error("PHX_QUERY_SCAN_CHUNK=%s: expected a positive multiple of %d", c, Q_TILE); return PHX_ERR_INVALID; }
-        scan_chunk_ = (int)std::min<long>(q, (long)Q_MAX_TILES * Q_TILE);
-    }
+    PHX_TRY(path_from_env("PHX_QUERY_PATH", &forced_));
+    long q = 0;
+    const char* c = nullptr;
+    const EnvInt got = int_from_env("PHX_QUERY_SCAN_CHUNK", &q, &c);
+    if (got == ENV_UNSET) return PHX_OK;
+    if (got == ENV_MALFORMED || q < Q_TILE || q % Q_TILE) { set_error("PHX_QUERY_SCAN_CHUNK=%s: expected a positive multiple of %d", c, Q_TILE); return PHX_ERR_INVALID; }
+    scan_chunk_ = (int)std::min<long>(q, (long)Q_MAX_TILES * Q_TILE);
     return PHX_OK;
 }
 
 // ---- the index ------------------------------------------------------------------------------------------------------------------
 int DeviceQuery::ensure_index(const WorldBodies& w, int n, unsigned long long epoch, hipStream_t s)
 {
-    if (built_ && built_epoch_ == epoch && built_n_ == n) return PHX_OK;
-    built_ = false;
+    if (index_.current(epoch, n)) return PHX_OK;
+    index_.stale();
     levels_ = 0;
     if (n > 0) {
-        PHX_TRY(keys0_.reserve((size_t)n)); PHX_TRY(vals0_.reserve((size_t)n)); PHX_TRY(keys1_.reserve((size_t)n)); PHX_TRY(vals1_.reserve((size_t)n));
-        PHX_TRY(hist_.reserve(radix_hist_words(n))); PHX_TRY(bounds_.reserve(4));
+        PHX_TRY(sort_.reserve(n)); PHX_TRY(hist_.reserve(radix_hist_words(n))); PHX_TRY(bounds_.reserve(4));
         PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bounds_.p), 0xFFFFFFFFu, 2, s));
         PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bounds_.p + 2), 0u, 2, s));
-        hipLaunchKernelGGL(k_qcentre_bounds, dim3(qgrid(n)), dim3(256), 0, s, (const float4*)w.aabb, n, bounds_.p);
-        hipLaunchKernelGGL(k_qmorton, dim3(qgrid(n)), dim3(256), 0, s, (const float4*)w.aabb, n, (const unsigned*)bounds_.p, keys0_.p, vals0_.p);
+        hipLaunchKernelGGL(k_qcentre_bounds, dim3(stream_grid(n)), dim3(256), 0, s, (const float4*)w.aabb, n, bounds_.p);
+        hipLaunchKernelGGL(k_qmorton, dim3(stream_grid(n)), dim3(256), 0, s, (const float4*)w.aabb, n, (const unsigned*)bounds_.p, sort_.keys(), sort_.vals());
         PHX_HIP(hipGetLastError());
-        int which = 0;
-        PHX_TRY(device_radix_sort_pairs(keys0_.p, vals0_.p, keys1_.p, vals1_.p, n, 32, hist_.p, scan_, s, &which));      // (stable: body order breaks ties)
-        perm_ = which ? vals1_.p : vals0_.p;
+        PHX_TRY(sort_.sort(n, 32, hist_.p, scan_, s));      // (stable: body order breaks ties)
         int total = 0;
         level_cnt_[0] = n;
         while (levels_ == 0 || level_cnt_[levels_] > 1) {
@@ -66,21 +60,20 @@ int DeviceQuery::ensure_index(const WorldBodies& w, int n, unsigned long long ep
         PHX_TRY(nodes_.reserve((size_t)total));
         for (int l = 1; l <= levels_; ++l) {
             const float4* src = l == 1 ? (const float4*)w.aabb : (const float4*)nodes_.p + level_off_[l - 1];
-            hipLaunchKernelGGL(k_qnodes, dim3(div_up(level_cnt_[l], 4)), dim3(256), 0, s, src, l == 1 ? perm_ : (const unsigned*)nullptr,
+            hipLaunchKernelGGL(k_qnodes, dim3(div_up(level_cnt_[l], 4)), dim3(256), 0, s, src, l == 1 ? sort_.vals() : (const unsigned*)nullptr,
                                level_cnt_[l - 1], nodes_.p + level_off_[l], level_cnt_[l]);
         }
         PHX_HIP(hipGetLastError());
     }
-    built_ = true; built_epoch_ = epoch; built_n_ = n;
-    ++builds_;
+    index_.built(epoch, n);
     return PHX_OK;
 }
 
-static QTree make_tree(const float4* nodes, const unsigned* perm, int n, int levels, const int* off, const int* cnt)
+QTree DeviceQuery::tree(int n) const
 {
     QTree t;
-    t.nodes = nodes; t.perm = perm; t.n = n; t.levels = levels;
-    for (int l = 0; l <= Q_MAX_LEVELS; ++l) { t.off[l] = l <= levels ? off[l] : 0; t.cnt[l] = l <= levels ? cnt[l] : 0; }
+    t.nodes = nodes_.p; t.perm = sort_.vals(); t.n = n; t.levels = levels_;
+    for (int l = 0; l <= Q_MAX_LEVELS; ++l) { t.off[l] = l <= levels_ ? level_off_[l] : 0; t.cnt[l] = l <= levels_ ? level_cnt_[l] : 0; }
     return t;
 }
 
@@ -89,14 +82,12 @@ int DeviceQuery::points(const WorldBodies& w, int n, unsigned long long epoch, c
 {
     if (count <= 0) return PHX_OK;
     unsigned* out = reinterpret_cast<unsigned*>(d_body);
-    if (n == 0 || choose(QUERY_POINTS, count) == SCAN) {
+    if (n == 0 || choose(QUERY_POINTS, count) == PATH_SCAN) {
         PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), 0xFFFFFFFFu, (size_t)count, s));      // (-1: no body)
-        if (n)
-            for (int q0 = 0; q0 < count; q0 += Q_MAX_TILES * Q_TILE)
-                hipLaunchKernelGGL(k_qscan_points, dim3(qgrid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)), dim3(256), 0, s, w, n, d_pts, count, q0, flags, out);
+        if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL(k_qscan_points, grid, dim3(256), 0, s, w, n, d_pts, count, q0, flags, out); });
     } else {
         PHX_TRY(ensure_index(w, n, epoch, s));
-        const QTree t = make_tree(nodes_.p, perm_, n, levels_, level_off_, level_cnt_);
+        const QTree t = tree(n);
         hipLaunchKernelGGL((k_qtree<QK_POINT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_pts, count, flags, out, (unsigned long long*)nullptr,
                            (const unsigned*)nullptr, (int*)nullptr);
     }
@@ -109,19 +100,17 @@ int DeviceQuery::closest(const WorldBodies& w, int n, unsigned long long epoch, 
 {
     if (count <= 0) return PHX_OK;
     PHX_TRY(ray_keys_.reserve((size_t)count));
-    if (n == 0 || choose(CAST ? QUERY_CASTS : QUERY_RAYS, count) == SCAN) {
-        hipLaunchKernelGGL(k_qfill_u64, dim3(qgrid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
-        if (n)
-            for (int q0 = 0; q0 < count; q0 += Q_MAX_TILES * Q_TILE)
-                hipLaunchKernelGGL((k_qscan_rays<CAST>), dim3(qgrid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)), dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p);
+    if (n == 0 || choose(CAST ? QUERY_CASTS : QUERY_RAYS, count) == PATH_SCAN) {
+        hipLaunchKernelGGL(k_qfill_u64, dim3(stream_grid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
+        if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_rays<CAST>), grid, dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p); });
     } else {
         PHX_TRY(ensure_index(w, n, epoch, s));
-        const QTree t = make_tree(nodes_.p, perm_, n, levels_, level_off_, level_cnt_);
+        const QTree t = tree(n);
         hipLaunchKernelGGL((k_qtree<CAST ? QK_CAST : QK_RAY>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
                            (const unsigned*)nullptr, (int*)nullptr);
     }
-    if constexpr (CAST) hipLaunchKernelGGL(k_qcast_finish, dim3(qgrid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
-    else hipLaunchKernelGGL(k_qray_finish, dim3(qgrid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    if constexpr (CAST) hipLaunchKernelGGL(k_qcast_finish, dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    else hipLaunchKernelGGL(k_qray_finish, dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
@@ -137,31 +126,12 @@ int DeviceQuery::casts(const WorldBodies& w, int n, unsigned long long epoch, co
 }
 
 // ---- AABB and oriented-box queries ----------------------------------------------------------------------------------------------------
-// offsets[] and *total from the per-query counts read back into counts_; *fits: the total fits hit_cap (and so int32)
-int DeviceQuery::offsets_from_counts(const char* what, int count, int32_t* offsets, int hit_cap, int64_t* total, bool* fits)
-{
-    long long run = 0;
-    offsets[0] = 0;
-    for (int q = 0; q < count; ++q) {
-        run += counts_[(size_t)q];
-        offsets[q + 1] = run <= (long long)INT32_MAX ? (int32_t)run : INT32_MAX;
-    }
-    *total = run;
-    *fits = run <= (long long)hit_cap;
-    if (!*fits) set_error("%s: %lld hits, room for %d", what, run, hit_cap);
-    return PHX_OK;
-}
-
 template <bool OBB>
 int DeviceQuery::overlaps(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
                           int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
 {
-    if (count <= 0 || n == 0) {
-        for (int q = 0; q <= std::max(count, 0); ++q) offsets[q] = 0;
-        *total = 0;
-        return PHX_OK;
-    }
-    if (choose(OBB ? QUERY_SHAPES : QUERY_BOXES, count) == SCAN) return scan_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    if (count <= 0 || n == 0) { Listing::none(count, offsets, total); return PHX_OK; }
+    if (choose(OBB ? QUERY_SHAPES : QUERY_BOXES, count) == PATH_SCAN) return scan_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
     PHX_TRY(ensure_index(w, n, epoch, s));
     return index_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
@@ -186,20 +156,15 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
     // queries per chunk: the chunk's (query, body block) table stays within 2^26 words and one launch's tiles (PHX_QUERY_SCAN_CHUNK
     // lowers it: tests reach the chunked form on small worlds)
     const int chunk = std::max(Q_TILE, std::min(std::min((1 << 26) / bblocks, Q_MAX_TILES * Q_TILE), scan_chunk_) / Q_TILE * Q_TILE);
-    PHX_TRY(qcount_.reserve((size_t)count));
+    PHX_TRY(list_.room(count));
     PHX_TRY(table_.reserve((size_t)std::min(count, chunk) * (size_t)bblocks));
-    PHX_HIP(hipMemsetAsync(qcount_.p, 0, (size_t)count * sizeof(unsigned), s));
+    PHX_HIP(hipMemsetAsync(list_.counts(), 0, (size_t)count * sizeof(unsigned), s));
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0);
-        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, OBB>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, qcount_.p, 0u, (int*)nullptr);
+        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, OBB>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, list_.counts(), 0u, (int*)nullptr);
     }
     PHX_HIP(hipGetLastError());
-    counts_.resize((size_t)count);
-    PHX_TRY(rb.add(counts_.data(), qcount_.p, (size_t)count * sizeof(unsigned), s));
-    PHX_TRY(rb.wait(s));
-    bool fits = false;
-    PHX_TRY(offsets_from_counts(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", count, offsets, hit_cap, total, &fits));
-    if (!fits) return PHX_ERR_CAPACITY;
+    PHX_TRY(list_.settle(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", "hits", count, offsets, hit_cap, total, rb, s));
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
     for (int q0 = 0; q0 < count; q0 += chunk) {
@@ -211,36 +176,29 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
                            (unsigned)offsets[q0], hits_.p);
     }
     PHX_HIP(hipGetLastError());
-    PHX_TRY(rb.add(hits, hits_.p, (size_t)*total * sizeof(int), s));
-    return rb.wait(s);
+    return Listing::deliver(hits, hits_.p, *total, rb, s);
 }
 
 template <bool OBB>
 int DeviceQuery::index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                             int64_t* total, Readback& rb, hipStream_t s)
 {
-    const QTree t = make_tree(nodes_.p, perm_, n, levels_, level_off_, level_cnt_);
-    PHX_TRY(qcount_.reserve((size_t)count)); PHX_TRY(qseg_.reserve((size_t)count));
-    hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_COUNT : QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, qcount_.p, (unsigned long long*)nullptr,
+    const QTree t = tree(n);
+    PHX_TRY(list_.room_with_segments(count));
+    hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_COUNT : QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, list_.counts(), (unsigned long long*)nullptr,
                        (const unsigned*)nullptr, (int*)nullptr);
     PHX_HIP(hipGetLastError());
-    counts_.resize((size_t)count);
-    PHX_TRY(rb.add(counts_.data(), qcount_.p, (size_t)count * sizeof(unsigned), s));
-    PHX_TRY(rb.wait(s));
-    bool fits = false;
-    PHX_TRY(offsets_from_counts(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", count, offsets, hit_cap, total, &fits));
-    if (!fits) return PHX_ERR_CAPACITY;
+    PHX_TRY(list_.settle(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", "hits", count, offsets, hit_cap, total, rb, s));
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
-    PHX_HIP(hipMemcpyAsync(qseg_.p, qcount_.p, (size_t)count * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
-    PHX_TRY(device_exclusive_scan(qseg_.p, count, nullptr, scan_, s));
+    PHX_TRY(list_.segments_from_counts(count, scan_, s));
     hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_FILL : QK_AABB_FILL>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
-                       (const unsigned*)qseg_.p, hits_.p);
+                       list_.segments(), hits_.p);
     // ascending order: short segments in LDS, long ones by the radix sort (31-bit keys: the body indices)
-    hipLaunchKernelGGL(k_qsort_segments, dim3(qsort_grid(count)), dim3(256), 0, s, (const unsigned*)qseg_.p, (const unsigned*)qcount_.p, count, hits_.p);
+    hipLaunchKernelGGL(k_qsort_segments, dim3(segment_grid(count)), dim3(256), 0, s, list_.segments(), (const unsigned*)list_.counts(), count, hits_.p);
     PHX_HIP(hipGetLastError());
     for (int q = 0; q < count; ++q) {
-        const unsigned len = counts_[(size_t)q];
+        const unsigned len = list_.host_count(q);
         if (len <= (unsigned)Q_SORT_MAX) continue;
         PHX_TRY(sort_k1_.reserve(len)); PHX_TRY(sort_v0_.reserve(len)); PHX_TRY(sort_v1_.reserve(len)); PHX_TRY(hist_.reserve(radix_hist_words((int)len)));
         unsigned* seg = reinterpret_cast<unsigned*>(hits_.p) + offsets[q];
@@ -248,8 +206,7 @@ int DeviceQuery::index_aabb(const WorldBodies& w, int n, const float* d_boxes, i
         PHX_TRY(device_radix_sort_pairs(seg, sort_v0_.p, sort_k1_.p, sort_v1_.p, (int)len, 31, hist_.p, scan_, s, &which));
         if (which) PHX_HIP(hipMemcpyAsync(seg, sort_k1_.p, (size_t)len * sizeof(unsigned), hipMemcpyDeviceToDevice, s));
     }
-    PHX_TRY(rb.add(hits, hits_.p, (size_t)*total * sizeof(int), s));
-    return rb.wait(s);
+    return Listing::deliver(hits, hits_.p, *total, rb, s);
 }
 
 } // namespace phx

@@ -24,8 +24,7 @@
 
 namespace phx {
 
-inline int wgrid(int n) { return std::max(1, std::min(div_up(n, 256), 4096)); }
-inline int rgrid(int n) { return std::max(1, std::min(div_up(n, 256), 2048)); }      // the removal's streaming passes (grid-stride beyond 2048 workgroups)
+inline int wgrid(int n) { return std::max(1, std::min(div_up(n, 256), 4096)); }      // (the removal's streaming passes take listing.h's stream_grid)
 
 // ref: World.cpp:11-17, RigidBody.h:15-36: the record AddBody makes, index aside (world.hip; add_body and add_bodies both build from it)
 phx_rigid_body body_record(float px, float py, float angle, float sx, float sy);

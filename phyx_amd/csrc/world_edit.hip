@@ -145,9 +145,9 @@ int World::scan_compaction(const Keep& kept)
 template <class Keep>
 int World::queue_compaction(const Keep& kept)
 {
-    if (nm) hipLaunchKernelGGL((k_remove_manifolds<Keep>), dim3(rgrid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, (const phx_contact_point*)d_cps_.p, nm,
+    if (nm) hipLaunchKernelGGL((k_remove_manifolds<Keep>), dim3(stream_grid(nm)), dim3(256), 0, stream_, (const phx_manifold*)d_manifolds_.p, (const phx_contact_point*)d_cps_.p, nm,
                                kept, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, (const unsigned*)(rm_counts_.p + 2), nj, spare_.manifolds.p, spare_.cps.p, rm_pairs_.p);
-    if (nj) hipLaunchKernelGGL((k_remove_joints<Keep>), dim3(rgrid(nj)), dim3(256), 0, stream_, (const phx_contact_joint*)d_joints_.p, nj, (const phx_manifold*)d_manifolds_.p,
+    if (nj) hipLaunchKernelGGL((k_remove_joints<Keep>), dim3(stream_grid(nj)), dim3(256), 0, stream_, (const phx_contact_joint*)d_joints_.p, nj, (const phx_manifold*)d_manifolds_.p,
                                kept, (const unsigned*)rm_mnew_.p, (const unsigned*)rm_jnew_.p, spare_.joints.p);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
@@ -211,12 +211,12 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(compaction_scratch());
     // 1. keep flags per body
     if (box) {
-        hipLaunchKernelGGL(k_keep_inside, dim3(rgrid(n)), dim3(256), 0, stream_, (const float4*)bodies_.aabb.p, n, make_float4(box[0], box[1], box[2], box[3]), rm_keep_.p);
+        hipLaunchKernelGGL(k_keep_inside, dim3(stream_grid(n)), dim3(256), 0, stream_, (const float4*)bodies_.aabb.p, n, make_float4(box[0], box[1], box[2], box[3]), rm_keep_.p);
     } else {
         const int* d_bodies = nullptr;
         PHX_TRY(stage_.indices(bodies, count, stream_, &d_bodies));
         PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(rm_keep_.p), 1, (size_t)n, stream_));
-        hipLaunchKernelGGL(k_remove_listed, dim3(rgrid(count)), dim3(256), 0, stream_, d_bodies, count, rm_keep_.p);
+        hipLaunchKernelGGL(k_remove_listed, dim3(stream_grid(count)), dim3(256), 0, stream_, d_bodies, count, rm_keep_.p);
     }
     PHX_HIP(hipGetLastError());
     PHX_TRY(wake_named(nullptr, 0, rm_keep_.p));                            // (the sleeping components that lose a member wake before anything moves)
@@ -226,7 +226,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     PHX_TRY(scan_compaction(kept));
     PHX_HIP(hipMemsetAsync(rm_counts_.p + 3, 0, sizeof(unsigned), stream_));
     // 3. compaction into the spares
-    hipLaunchKernelGGL(k_remove_bodies, dim3(rgrid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)bodies_.records.p, resident(), n, records_stale_ ? 1 : 0,
+    hipLaunchKernelGGL(k_remove_bodies, dim3(stream_grid(n)), dim3(256), 0, stream_, (const phx_rigid_body*)bodies_.records.p, resident(), n, records_stale_ ? 1 : 0,
                        (const unsigned*)rm_keep_.p, (const unsigned*)rm_bnew_.p, spare_.bodies.records.p, spare_.bodies.view(), rm_remap_.p, rm_counts_.p + 3,
                        columns(), spare_columns());
     PHX_TRY(queue_compaction(kept));

@@ -7,10 +7,16 @@ namespace phx {
 // Answered on the world's stream from the resident arrays (query.h / query_kernels.h).  The host forms check everything first, stage the
 // queries through the world's pinned staging and wait for their results; the device forms only queue.  Nothing of the world changes:
 // the upload of host-staged bodies is the one the next step would make.
+static int flags_check(const char* what, int flags)      // (the queries' and the contact lists')
+{
+    if (flags != 0 && flags != PHX_QUERY_SKIP_STATIC) { set_error("%s: flags %d (0 or PHX_QUERY_SKIP_STATIC)", what, flags); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
 static int query_check(const char* what, const float* v, int count, int width, int flags, bool device, const void* out)
 {
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
-    if (flags != 0 && flags != PHX_QUERY_SKIP_STATIC) { set_error("%s: flags %d (0 or PHX_QUERY_SKIP_STATIC)", what, flags); return PHX_ERR_INVALID; }
+    PHX_TRY(flags_check(what, flags));
     if (count && (!v || !out)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
     if (device) return PHX_OK;
     for (int k = 0; k < count; ++k) {
@@ -109,12 +115,12 @@ int World::contact_prepare(const char* what, bool host_wait)
 int World::query_contacts(const int32_t* bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total)
 {
     static const char* const what = "phx_world_query_contacts";
-    PHX_TRY(refuse_mid_step(what));
-    if (flags != 0 && flags != PHX_QUERY_SKIP_STATIC) { set_error("%s: flags %d (0 or PHX_QUERY_SKIP_STATIC)", what, flags); return PHX_ERR_INVALID; }
+    PHX_TRY(refuse_mid_step(what));                                         // (first: it wins over every complaint about the arguments)
+    PHX_TRY(flags_check(what, flags));
     if (!offsets || !total) { set_error("%s: null offsets / total", what); return PHX_ERR_INVALID; }
     if (cap < 0 || (cap > 0 && !out)) { set_error("%s: bad output buffer (cap %d)", what, cap); return PHX_ERR_INVALID; }
     PHX_TRY(check_batch(what, bodies, bodies, count, false));               // (count >= 0, indices in range; repeats allowed)
-    PHX_TRY(contact_prepare(what, true));
+    PHX_TRY(query_prepare(true));                                           // (contact_prepare less the refusal made above)
     const int* d_bodies = nullptr;
     if (count && nm) PHX_TRY(stage_.indices(bodies, count, stream_, &d_bodies));
     return contacts_.contacts(contact_cache(), contact_epoch_, d_bodies, count, flags, offsets, out, cap, total, rb_, stream_);

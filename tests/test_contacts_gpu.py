@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import contact_spec as spec
+import listing_cases
 import phyx_amd
 from phyx_amd import Configuration, DeviceBuffer, PhxError, scenes
 from phyx_amd.api import contact_dtype, contact_marker_dtype
@@ -231,6 +232,31 @@ def test_capacity_leaves_the_baseline(built_lib):
     assert total.value == len(sr) and off.tobytes() == so.tobytes()
     assert L.phx_world_query_contacts(w.h, vp(listed), n, 0, vp(off), vp(out), len(sr), C.byref(total)) == 0
     assert out.tobytes() == sr.tobytes()
+
+
+def _every_body(w):
+    listed = np.arange(w.counts()[0], dtype=np.int32)
+    return (listed,) + spec.contacts(*w.state(), listed)
+
+
+@pytest.mark.parametrize("path", ("scan", "index"), indirect=True)
+def test_listing_protocol(built_lib, path):
+    """phx_world_query_contacts with cap one short and exact (test_capacity_leaves_the_baseline's contacts half, on both paths), and a
+    listed body that touches nothing in a world with manifolds."""
+    w = listing_cases.world()
+    listing_cases.one_short(w, "phx_world_query_contacts", "records", *_every_body(w))
+    n, nm = w.counts()[:2]
+    assert nm > 0
+    w.add_bodies(np.array([[0.0, 5000.0, 0.0, 5.0, 5.0]], dtype=F))      # (far above the stack)
+    listing_cases.counted_none(w, "phx_world_query_contacts", np.array([n, n], dtype=np.int32))
+
+
+def test_scan_chunks_one_short(built_lib, monkeypatch):
+    """cap one short on the chunked scan: 121 listed bodies in chunks of 7."""
+    monkeypatch.setenv("PHX_CONTACT_PATH", "scan")
+    monkeypatch.setenv("PHX_CONTACT_SCAN_CHUNK", "7")
+    w = listing_cases.world()
+    listing_cases.one_short(w, "phx_world_query_contacts", "records", *_every_body(w))
 
 
 @pytest.mark.parametrize("scene", ("stack", "piles"))

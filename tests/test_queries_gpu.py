@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import listing_cases
 import phyx_amd
 import query_spec as spec
 from phyx_amd import Configuration, DeviceBuffer, scenes
@@ -311,6 +312,31 @@ def test_scan_aabb_beyond_one_chunk_at_cfg2(built_lib, monkeypatch):
     sel = np.concatenate([rng.choice(k, 100, replace=False), [0, 85759, 85760, k - 1]])
     so, sh = spec.query_aabb(bodies, boxes[sel])
     _segments_equal(got["scan"][0], got["scan"][1], so, sh, sel, "cfg 2 scan")
+
+
+@pytest.mark.parametrize("path", ("scan", "index"), indirect=True)
+def test_listing_protocol(built_lib, path):
+    """phx_world_query_aabb with hit_cap one short and exact, and boxes that count no hit at all, on both paths."""
+    w = listing_cases.world()
+    bodies = w.bodies
+    boxes = np.array([[-1e4, -1e4, 1e4, 1e4], [5000, 5000, 5010, 5010], [-5, 12, 5, 28]], dtype=F)      # everything, nothing, two boxes
+    so, sh = spec.query_aabb(bodies, boxes)
+    assert np.diff(so).tolist() == [len(bodies), 0, 2]
+    listing_cases.one_short(w, "phx_world_query_aabb", "hits", boxes, so, sh)
+    listing_cases.counted_none(w, "phx_world_query_aabb", np.tile(boxes[1], (3, 1)))
+
+
+def test_scan_aabb_in_chunks_one_short(built_lib, monkeypatch):
+    """hit_cap one short on the chunked scan: the later chunks are counted again between the offsets and the fill."""
+    monkeypatch.setenv("PHX_QUERY_PATH", "scan")
+    monkeypatch.setenv("PHX_QUERY_SCAN_CHUNK", "64")
+    w = listing_cases.world()
+    bodies = w.bodies
+    boxes, _, _ = _queries(bodies, np.random.default_rng(64), 150)
+    assert len(boxes) > 2 * 64 and len(boxes) % 64
+    so, sh = spec.query_aabb(bodies, boxes)
+    assert so[64] < so[128] < so[-1]                                    # (every chunk has hits)
+    listing_cases.one_short(w, "phx_world_query_aabb", "hits", boxes, so, sh)
 
 
 @pytest.mark.parametrize("var,value", [("PHX_QUERY_PATH", "indx"), ("PHX_QUERY_SCAN_CHUNK", "100"), ("PHX_QUERY_SCAN_CHUNK", "x")])

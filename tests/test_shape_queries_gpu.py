@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import listing_cases
 import phyx_amd
 import shape_query_spec as spec
 from phyx_amd import Configuration, DeviceBuffer, scenes
@@ -191,6 +192,18 @@ def test_capacity(built_lib, path):
     n = len(bodies)
     off, hits = w.query_boxes(np.tile(box_from_angle(0.0, 50.0, 0.3, 500.0, 500.0), (8, 1)))      # (the wrapper's retry: 8 n > 1024 hits)
     assert 8 * n > 1024 and off.tolist() == [n * k for k in range(9)] and hits.tolist() == list(range(n)) * 8
+
+
+def test_listing_protocol(built_lib, path):
+    """phx_world_query_boxes with hit_cap one short and exact, and boxes that count no hit at all, on both paths."""
+    w = listing_cases.world()
+    bodies = w.bodies
+    boxes = np.stack([box_from_angle(0.0, 100.0, 0.3, 500.0, 500.0), box_from_angle(5000.0, 5000.0, 0.3, 2.0, 2.0),
+                      box_from_angle(0.0, 20.0, 0.3, 4.0, 4.0)]).astype(F)                            # everything, nothing, two boxes
+    so, sh = spec.query_boxes(bodies, boxes)
+    assert np.diff(so).tolist() == [len(bodies), 0, 2]
+    listing_cases.one_short(w, "phx_world_query_boxes", "hits", boxes, so, sh)
+    listing_cases.counted_none(w, "phx_world_query_boxes", np.tile(boxes[1], (3, 1)))
 
 
 def test_device_form(built_lib, path):
