@@ -717,11 +717,14 @@ int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
  *   - Circles (SHAPES above; r = geom_size.x; tests/circle_spec.py states these as the same expressions).  The AABB query is unchanged: it
  *     uses the record's AABB, that of the frame square.  Point p in circle b iff p is inside b's AABB (closed, as for a box) AND, with
  *     dx = p.x - pos.x, dy = p.y - pos.y:  dx*dx + dy*dy <= r*r.  A ray hits circle b iff b is a candidate (the test on its AABB, as for a
- *     box) and, with rx = ox - pos.x, ry = oy - pos.y, a = dx*dx + dy*dy, b = rx*dx + ry*dy, c = rx*rx + ry*ry - r*r, D = b*b - a*c:
- *     D >= 0 (a miss if D < 0 or NaN), s = sqrtf(D), tin = (-b - s) / a, tout = (-b + s) / a, and tin <= tout && tout >= 0 && tin <= max_t,
- *     the box rule.  Then t = (tin > 0 ? tin : 0), normal = (0, 0) if tin < 0, otherwise ((rx + tin*dx) / r, (ry + tin*dy) / r), point as
- *     for boxes; ties go to the lowest index, as always.  Oriented-box queries and box casts see a circle as its frame square {r, r} in
- *     the body's frame: both are conservative (they never miss a disc and never report a later t) and consistent with each other, the
+ *     box) and, with rx = ox - pos.x, ry = oy - pos.y, a = dx*dx + dy*dy, b = rx*dx + ry*dy, tc = -b / a (where the line passes the
+ *     centre closest), ex = rx + tc*dx, ey = ry + tc*dy (the offset there), h2 = r*r - (ex*ex + ey*ey):
+ *     h2 >= 0 (a miss if h2 < 0 or NaN), s = sqrtf(h2 / a), tin = tc - s, tout = tc + s, and tin <= tout && tout >= 0 && tin <= max_t,
+ *     the box rule.  Then t = (tin > 0 ? tin : 0), normal = (0, 0) if tin < 0, otherwise ((ex - s*dx) / r, (ey - s*dy) / r), point as
+ *     for boxes; ties go to the lowest index, as always.  (The closest-approach form, not the quadratic's discriminant b*b - a*c: that
+ *     one squares the origin's distance and loses a small disc's chord a few thousand units away; this one stays within a few
+ *     2^-24 * the largest coordinate of the true entry at any distance, tests/query_reference.py.)
+ *     Oriented-box queries and box casts see a circle as its frame square {r, r} in the body's frame: both are conservative (they never miss a disc and never report a later t) and consistent with each other, the
  *     two halves of "is this slot free, how far can I drop"; the exact disc versions are a later change.
  * flags: PHX_QUERY_SKIP_STATIC leaves static bodies (inv_mass == 0 && inv_inertia == 0) out of every result (picking without the ground).
  *   A body that sleeps (SLEEPING below) is not static to a query although its inverse masses read 0 while it does: picking a box out of a

@@ -112,24 +112,29 @@ __device__ __forceinline__ bool q_ray_box(const QRay& r, float4 m, float4 f, flo
     return q_ray_test(oxp, oyp, out.dxp, out.dyp, -h.x, -h.y, h.x, h.y, r.max_t, out.tin, out.xenter);
 }
 
-// the ray against the disc (after the candidate test): the quadratic's two roots under the box rule; rx, ry = the origin from the centre
-__device__ __forceinline__ bool q_ray_circle(const QRay& r, float4 m, float rad, float& tin, float& rx, float& ry)
+// the ray against the disc (after the candidate test), by the closest approach: tc is where the line passes the centre closest, e the
+// offset there, s half the chord in units of t, under the box rule; nx, ny = the entry point from the centre (the normal is n / r).
+// Nothing of the size of the origin's distance is squared: a small disc seen from far away keeps its chord.
+__device__ __forceinline__ bool q_ray_circle(const QRay& r, float4 m, float rad, float& tin, float& nx, float& ny)
 {
-    rx = r.ox - m.z; ry = r.oy - m.w;
-    const float a = r.dx * r.dx + r.dy * r.dy, b = rx * r.dx + ry * r.dy, c = rx * rx + ry * ry - rad * rad;
-    const float D = b * b - a * c;
-    tin = 0.f;
-    if (D < 0.f) return false;
-    const float s = sqrtf(D);
-    tin = (-b - s) / a;
-    const float tout = (-b + s) / a;
+    const float rx = r.ox - m.z, ry = r.oy - m.w;
+    const float a = r.dx * r.dx + r.dy * r.dy, b = rx * r.dx + ry * r.dy;
+    const float tc = -b / a;
+    const float ex = rx + tc * r.dx, ey = ry + tc * r.dy;
+    const float h2 = rad * rad - (ex * ex + ey * ey);
+    tin = 0.f; nx = 0.f; ny = 0.f;
+    if (!(h2 >= 0.f)) return false;
+    const float s = sqrtf(h2 / a);
+    tin = tc - s;
+    const float tout = tc + s;
+    nx = ex - s * r.dx; ny = ey - s * r.dy;
     return tin <= tout && tout >= 0.f && tin <= r.max_t;
 }
 
 // the ray against body b's own shape (after the candidate test): tin alone
 __device__ __forceinline__ bool q_ray_body(bool circle, const QRay& r, float4 m, float4 f, float2 h, float& tin)
 {
-    if (circle) { float rx, ry; return q_ray_circle(r, m, h.x, tin, rx, ry); }
+    if (circle) { float nx, ny; return q_ray_circle(r, m, h.x, tin, nx, ny); }
     QRayBox rb;
     const bool hit = q_ray_box(r, m, f, h, rb);
     tin = rb.tin;
@@ -281,10 +286,10 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
             const float2 sz = w.size[b];
             float t;
             if (q_circle(w.kinds, b)) {
-                float tin, rx, ry;
-                (void)q_ray_circle(r, m, sz.x, tin, rx, ry);
+                float tin, nx, ny;
+                (void)q_ray_circle(r, m, sz.x, tin, nx, ny);
                 t = tin > 0.f ? tin : 0.f;
-                if (!(tin < 0.f)) { h.normal.x = (rx + tin * r.dx) / sz.x; h.normal.y = (ry + tin * r.dy) / sz.x; }
+                if (!(tin < 0.f)) { h.normal.x = nx / sz.x; h.normal.y = ny / sz.x; }
             } else {
                 QRayBox rb;
                 (void)q_ray_box(r, m, f, sz, rb);

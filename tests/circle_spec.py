@@ -200,20 +200,24 @@ def point_in_circle(g, x, y):
 
 
 def ray_circle(g, r):
-    """The ray against every body's disc: (pass, tin, rx, ry)."""
+    """The ray against every body's disc: (pass, tin, nx, ny), n = the entry point from the centre (the normal is n / r).  The closest
+    approach form: tc is where the line passes the centre closest, e the offset there, s half the chord in units of t; nothing of the
+    size of the origin's distance is squared, so a small disc seen from far away keeps its chord."""
     ox, oy, dx, dy, max_t = (F(v) for v in r)
     with np.errstate(all="ignore"):
         rx = ox - g.px
         ry = oy - g.py
         a = dx * dx + dy * dy
         b = rx * dx + ry * dy
-        c = rx * rx + ry * ry - g.hx * g.hx
-        D = b * b - a * c
-        s = np.sqrt(D)
-        tin = ((-b - s) / a).astype(F)
-        tout = ((-b + s) / a).astype(F)
-        hit = ~(D < 0) & (tin <= tout) & (tout >= 0) & (tin <= max_t)
-    return hit, tin, rx, ry
+        tc = -b / a
+        ex = rx + tc * dx
+        ey = ry + tc * dy
+        h2 = g.hx * g.hx - (ex * ex + ey * ey)
+        s = np.sqrt(h2 / a)
+        tin = (tc - s).astype(F)
+        tout = (tc + s).astype(F)
+        hit = (h2 >= 0) & (tin <= tout) & (tout >= 0) & (tin <= max_t)
+    return hit, tin, (ex - s * dx).astype(F), (ey - s * dy).astype(F)
 
 
 def query_points(bodies, kinds, points, skip_static=False):
@@ -243,7 +247,7 @@ def raycast(bodies, kinds, rays, skip_static=False):
         if not qs.ray_ok(r) or not g.n:
             continue
         bhit, btin, xenter, dxp, dyp = qs.ray_box(g, r)
-        chit, ctin, rx, ry = ray_circle(g, r)
+        chit, ctin, nx, ny = ray_circle(g, r)
         hit = np.where(round_, chit, bhit) & elig & qs.ray_candidate(g, r)
         tin = np.where(round_, ctin, btin).astype(F)
         if not hit.any():
@@ -256,7 +260,7 @@ def raycast(bodies, kinds, rays, skip_static=False):
         out["t"][q] = tmin
         if not tin[b] < 0:
             if round_[b]:
-                out["normal"][q] = ((rx[b] + tin[b] * dx) / g.hx[b], (ry[b] + tin[b] * dy) / g.hx[b])
+                out["normal"][q] = (nx[b] / g.hx[b], ny[b] / g.hx[b])
             elif xenter[b]:
                 n, flip = (g.xvx[b], g.xvy[b]), dxp[b] > 0
                 out["normal"][q] = (-n[0], -n[1]) if flip else n

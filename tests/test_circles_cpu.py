@@ -10,6 +10,8 @@ import pytest
 import circle_corpus as cc
 import circle_reference as ref
 import circle_spec as spec
+import query_corpus as qc
+import query_spec
 from phyx_amd.api import contact_point_dtype, manifold_dtype, rigid_body_dtype, circle_inverse_masses
 
 F = np.float32
@@ -213,3 +215,45 @@ def test_ray_against_disc_by_hand():
             n = h["normal"][k].astype(np.float64)
             assert abs(np.hypot(*n) - 1.0) < 1e-6
             assert abs(np.hypot(*(h["point"][k].astype(np.float64) - (10.0, 5.0))) - 2.0) < 1e-5
+
+
+# ---- the disc predicates against the float64 judge -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c.name for c in qc.cases()])
+def test_spec_queries_against_the_float64_judge(name):
+    """A corpus case (tests/query_corpus.py: discs and boxes, rays from 1 to 10^6 units away, bodies out to 10^5), circle_spec against
+    the float64 judge (tests/query_reference.py):
+      - every (ray, body) and (point, body) pair: the rule's verdict is the judge's wherever the clearance exceeds NEAR = 32 u,
+        u = 2^-24 * scale; the pairs excused are at most CAP = 0.02 of the case's, by the judge alone;
+      - the closest hit: the judge's body unless two entries are within 32 u, the normal (0, 0) exactly when the origin is inside, and
+        every deviation() measure (hit point, normal length and angle times r, the returned point's distance from the surface) within
+        BOUND = 16 u.  The ray/disc rule meets 16 at every distance (it measures under 3); only a box's `hit` has a wider bound, for
+        the reason test_queries_cpu.test_spec_box_rules_against_the_float64_judge gives;
+      - the deliberately doubtful rays (grazing at 0.999 r and 1.001 r, max_t an ulp either side of the entry) and points: excused or
+        right, not counted in the share.
+    The quadratic this rule replaced (c = rx*rx + ry*ry - r*r, D = b*b - a*c) fails here from 30 units on: its hit point is off by 25 u
+    at 30 units, 1850 u at 300 and 5500 u at 3000, from where on it also loses clear hits and returns normals of length 0."""
+    c = qc.case(name)
+    g = query_spec.Geometry(c.bodies)
+    round_ = c.kinds == qc.CIRCLE
+    ray_verdicts = lambda r: np.where(round_, spec.ray_circle(g, r)[0], query_spec.ray_box(g, r)[0]) & query_spec.ray_candidate(g, r)      # noqa: E731
+    point_verdicts = lambda p: np.where(round_, spec.point_in_circle(g, p[0], p[1]), query_spec.point_in_box(g, p[0], p[1]))            # noqa: E731
+    if len(c.rays):
+        near = qc.judge_pairs(c.bodies, c.kinds, c.rays, ray_verdicts)
+        assert near.mean() <= qc.CAP, "excluded share %.4f" % near.mean()
+        _, worst = qc.judge_hits(c.bodies, c.kinds, c.rays, spec.raycast(c.bodies, c.kinds, c.rays))
+        print("%s: %d rays, excluded %.4f of the pairs; worst in u: %s" % (name, len(c.rays), near.mean(), qc.table(worst)))
+        qc.assert_bounds(worst, name)
+    if len(c.near_rays):
+        qc.judge_pairs(c.bodies, c.kinds, c.near_rays, ray_verdicts)
+        qc.judge_hits(c.bodies, c.kinds, c.near_rays, spec.raycast(c.bodies, c.kinds, c.near_rays))
+    if len(c.points):
+        near = qc.judge_points(c.bodies, c.kinds, c.points, spec.query_points(c.bodies, c.kinds, c.points), point_verdicts)
+        assert near.mean() <= qc.CAP, "excluded share of the points' pairs %.4f" % near.mean()
+        qc.judge_points(c.bodies, c.kinds, c.near_points, spec.query_points(c.bodies, c.kinds, c.near_points), point_verdicts)
+
+
+def test_the_rows_seen_from_3000_units_name_the_nearest_disc():
+    """Six discs in a row, indices scrambled, seen along the row from 3000 units on either side: the nearest by the judge, not body 0."""
+    c = qc.case("a row of discs from 3000")
+    h = spec.raycast(c.bodies, c.kinds, c.rays)
+    assert h["body"].tolist() == [3, 2, -1, 3, 2, -1, 3, 2, -1, 1, 2, -1]

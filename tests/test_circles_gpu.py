@@ -4,7 +4,8 @@
   - behaviour: a circle rolls down a slope a box rests on; two stacked circles come to rest;
   - twins: an active column of boxes against a world that never heard of shapes; set_state + set_shapes; save / load / fork / export;
   - plumbing: removal, spawn, add_circles; every rejection leaves the world unchanged; a resized box's AABB;
-  - queries on both paths against the spec and against each other."""
+  - queries on both paths against the spec and against each other; the directed corpus (tests/query_corpus.py) on both paths, byte-equal
+    to the spec and held to the float64 judge (tests/query_reference.py)."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +13,7 @@ import pytest
 
 import circle_spec as spec
 import phyx_amd
+import query_corpus as qc
 import shape_query_spec as sqs
 from phyx_amd import Configuration, PhxError, SHAPE_BOX, SHAPE_CIRCLE, scenes
 from phyx_amd.api import contact_point_dtype, manifold_dtype, rigid_body_dtype
@@ -432,3 +434,35 @@ def test_queries_see_the_disc_on_both_paths(monkeypatch):
 def sqs_points(bodies, pts):
     import query_spec
     return query_spec.query_points(bodies, pts)
+
+
+# ---- 6. the directed corpus on both paths: the spec's bytes, and the judge's bounds on the device's own answers ------------------------------
+@pytest.mark.parametrize("path", ("scan", "index"))
+@pytest.mark.parametrize("name", [c.name for c in qc.cases()])
+def test_corpus_queries_equal_the_spec_and_meet_the_judge(monkeypatch, name, path):
+    """A world built from the corpus case's bodies (no step): raycast and query_points are byte-equal to circle_spec, and the device's
+    own answers meet the float64 judge by the bounds and the excused set of test_circles_cpu.test_spec_queries_against_the_float64_judge
+    (a kernel that drifted from the spec would still be held to the truth).  "a row of discs from 3000" is the closest-hit choice
+    among several discs seen from far away; "65 bodies" is one body past a tree node."""
+    monkeypatch.setenv("PHX_QUERY_PATH", path)
+    c = qc.case(name)
+    w = qc.world(c.bodies, c.kinds)
+    bodies, kinds = w.bodies, _kinds(w)
+    assert kinds.tolist() == c.kinds.tolist()
+    for rays in (c.rays, c.near_rays):
+        if not len(rays):
+            continue
+        got, want = w.raycast(rays), spec.raycast(bodies, kinds, rays)
+        assert got.tobytes() == want.tobytes(), "%s %s: rays %s" % (name, path, np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(got, want)])[:8])
+        _, worst = qc.judged("rays", qc.judge_hits, bodies, kinds, rays, got)
+        if rays is c.rays:
+            print("%s %s: worst in u: %s" % (name, path, qc.table(worst)))
+            qc.assert_bounds(worst, "%s %s" % (name, path))
+    for pts in (c.points, c.near_points):
+        if not len(pts):
+            continue
+        got = w.query_points(pts)
+        assert got.tobytes() == spec.query_points(bodies, kinds, pts).tobytes(), "%s %s: points" % (name, path)
+        qc.judged("points", qc.judge_points, bodies, kinds, pts, got)
+    if name == "a row of discs from 3000":
+        assert w.raycast(c.rays)["body"].tolist() == [3, 2, -1, 3, 2, -1, 3, 2, -1, 1, 2, -1]

@@ -1,6 +1,8 @@
 """Queries on the device (include/phyx_amd.h, QUERIES) held byte for byte to tests/query_spec.py: seeded and boundary queries on four
 scenes through the scan path, the index path and the automatic choice; answers after every kind of change (no stale index); no effect
-on the world; the edges of the tree's levels and of the AABB buffer; the device forms; the cfg 2 world; examples/pick.c."""
+on the world; the edges of the tree's levels and of the AABB buffer; the device forms; the cfg 2 world; examples/pick.c; the boxes of
+the directed corpus (tests/query_corpus.py) held to the spec's bytes and to the float64 judge (tests/query_reference.py), and oriented
+boxes and casts on a field moved out to 10^5."""
 import os
 import subprocess
 
@@ -9,7 +11,9 @@ import pytest
 
 import listing_cases
 import phyx_amd
+import query_corpus as qc
 import query_spec as spec
+import shape_query_spec
 from phyx_amd import Configuration, DeviceBuffer, scenes
 from phyx_amd.api import ray_hit_dtype
 
@@ -344,3 +348,55 @@ def test_unknown_knob_values_are_refused(built_lib, monkeypatch, var, value):
     monkeypatch.setenv(var, value)
     with pytest.raises(phyx_amd.PhxError, match=var):
         phyx_amd.World(0)
+
+
+# ---- the directed corpus: the spec's bytes, and the judge's bounds on the device's own answers --------------------------------------------
+@pytest.mark.parametrize("path", ("scan", "index"), indirect=True)
+@pytest.mark.parametrize("name", [c.name for c in qc.cases() if (c.kinds == qc.BOX).any()])
+def test_corpus_boxes_equal_the_spec_and_meet_the_judge(built_lib, name, path):
+    """A world of the corpus case's boxes alone (no shape column, no step): raycast and query_points are byte-equal to query_spec, and
+    the device's own answers meet the float64 judge by the bounds and the excused set of
+    test_queries_cpu.test_spec_box_rules_against_the_float64_judge."""
+    c = qc.case(name)
+    w = qc.world(*qc.boxes_only(c))
+    bodies = w.bodies
+    kinds = np.zeros(len(bodies), dtype=np.int32)
+    for rays in (c.rays, c.near_rays):
+        if not len(rays):
+            continue
+        got, want = w.raycast(rays), spec.raycast(bodies, rays)
+        assert got.tobytes() == want.tobytes(), "%s %s: rays %s" % (name, path, np.flatnonzero([a.tobytes() != b.tobytes() for a, b in zip(got, want)])[:8])
+        _, worst = qc.judged("rays", qc.judge_hits, bodies, kinds, rays, got)
+        if rays is c.rays:
+            print("%s %s: worst in u: %s" % (name, path, qc.table(worst)))
+            qc.assert_bounds(worst, "%s %s" % (name, path))
+    for pts in (c.points, c.near_points):
+        if not len(pts):
+            continue
+        got = w.query_points(pts)
+        assert got.tobytes() == spec.query_points(bodies, pts).tobytes(), "%s %s: points" % (name, path)
+        qc.judged("points", qc.judge_points, bodies, kinds, pts, got)
+
+
+@pytest.mark.parametrize("path", ("scan", "index"), indirect=True)
+@pytest.mark.parametrize("shift", ((3000.0, -7000.0), (1e5, 1e5)), ids=lambda s: "%g,%g" % s)
+def test_shifted_oriented_boxes_and_casts_equal_the_spec(built_lib, shift, path):
+    """The 0 .. 100 field of test_shape_queries_cpu's float64 checks, moved out to where the project's worlds reach: 64 bodies, 128
+    oriented boxes and 128 casts in and around it, byte-equal to shape_query_spec."""
+    rng = np.random.default_rng(20242)
+    field = lambda n, lo, hi, big: np.stack([rng.uniform(lo, hi, n) + shift[0], rng.uniform(lo, hi, n) + shift[1], rng.uniform(0, 2 * np.pi, n),      # noqa: E731
+                                             rng.uniform(0.5, big, n), rng.uniform(0.5, big, n)], axis=1).astype(F)
+    w = phyx_amd.World(0, gravity=0.0)
+    w.add_bodies(field(64, 0, 100, 20))
+    bodies = w.bodies
+    boxes = np.stack([phyx_amd.box_from_angle(*q) for q in field(128, -60, 160, 6)]).astype(F)      # (smaller, and around the field too: some miss)
+    ang = rng.uniform(0, 2 * np.pi, 128)
+    d = np.stack([np.cos(ang), np.sin(ang)], axis=1) * rng.uniform(0.5, 3.0, (128, 1))
+    casts = np.concatenate([boxes, d, rng.uniform(5.0, 60.0, (128, 1))], axis=1).astype(F)
+    off, hits = w.query_boxes(boxes)
+    so, sh = shape_query_spec.query_boxes(bodies, boxes)
+    assert off.tobytes() == so.tobytes() and hits.tobytes() == sh.tobytes(), path
+    assert 0 < len(hits) < 64 * 128
+    got = w.cast_boxes(casts)
+    assert got.tobytes() == shape_query_spec.cast_boxes(bodies, casts).tobytes(), path
+    assert 0 < (got["body"] >= 0).sum() < 128

@@ -1,5 +1,6 @@
 """Shape queries (include/phyx_amd.h, QUERIES: phx_world_query_boxes / phx_world_cast_boxes) without a GPU: the specification
-(tests/shape_query_spec.py) against a float64 separating-axis test and a float64 bisection that share no code with it, the specification
+(tests/shape_query_spec.py) against a float64 separating-axis test and a float64 bisection that share no code with it, on the 0 .. 100
+field and on the same field moved out to (3000, -7000) and (10^5, 10^5), the specification
 on hand-built boundary cases, the refusals of the entry points and of the Python wrappers, and examples/place.c, which builds and fails
 loudly without a device."""
 import ctypes as C
@@ -15,8 +16,27 @@ from phyx_amd.api import box_from_angle, frame_from_angle, rigid_body_dtype
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-MARGIN = 1e-3           # pairs with a float64 axis gap this close to zero may be left out ...
+MARGIN = 1e-3           # pairs with a float64 axis gap this close to zero may be left out (at coordinates 0 .. 100) ...
 CAP = 0.02              # ... and at most this share of the pairs
+SHIFTS = ((3000.0, -7000.0), (1e5, 1e5))      # the 0 .. 100 field moved out to where the project's worlds reach
+
+
+def _margin(shift):
+    """MARGIN widened by the coordinate's ulp.  The rules work on differences of nearby floats (c = P - pos, exact or rounded at the
+    size of c), so moving the field adds nothing to what they lose but for the AABB conjunct and the candidate test, which round
+    a.min - e, a.max + e and the AABB itself at the size of the coordinates: two roundings, 4 ulp with a factor 2 to spare.  (MARGIN
+    times the ratio of the ulps, 1.02 at 10^5, would by the float64 check alone exclude 0.11 of the overlap pairs and 0.23 of the casts
+    of this field, against CAP; this margin is the narrower one and asks more.)"""
+    reach = 100.0 + max(abs(shift[0]), abs(shift[1]))
+    return MARGIN + 4.0 * float(np.spacing(F(reach)) - np.spacing(F(100.0)))
+
+
+def _shifted(rows, shift):
+    """The rows moved by `shift`, their positions rounded to float32 as the records and the query boxes will hold them: the float64
+    check and the specification then start from the same floats."""
+    out = np.array(rows, dtype=np.float64)
+    out[:, 0:2] = (out[:, 0:2] + np.asarray(shift)).astype(F)
+    return out
 
 
 def _records(rows, static=()):
@@ -98,22 +118,33 @@ def _random_rows(rng, n):
 NQ, NB = 200, 110                                                      # 22 000 pairs
 
 
-def test_spec_overlap_agrees_with_a_float64_separating_axis_test():
+def _overlap_against_float64(shift):
     rng = np.random.default_rng(20240)
-    brow, qrow = _random_rows(rng, NB), _random_rows(rng, NQ)
+    brow, qrow = _shifted(_random_rows(rng, NB), shift), _shifted(_random_rows(rng, NQ), shift)
+    margin = _margin(shift)
     g = Geometry(_records(brow))
     gaps = _gaps64(_intervals64(*_corners64(qrow), *_corners64(brow)))
     want = (gaps <= 0).all(axis=2)
-    near = np.abs(gaps).min(axis=2) < MARGIN
+    near = np.abs(gaps).min(axis=2) < margin
     assert NQ * NB >= 20000 and near.mean() <= CAP, "excluded share %.4f" % near.mean()
     got = np.stack([spec.box_overlap(g, box_from_angle(*q)) for q in qrow])
     assert want.sum() > 1000 and (~want).sum() > 1000
     assert (got == want)[~near].all(), "%d of %d pairs disagree" % ((got != want)[~near].sum(), (~near).sum())
 
 
-def test_spec_cast_t_agrees_with_a_float64_bisection():
+def test_spec_overlap_agrees_with_a_float64_separating_axis_test():
+    _overlap_against_float64((0.0, 0.0))
+
+
+@pytest.mark.parametrize("shift", SHIFTS, ids=lambda s: "%g,%g" % s)
+def test_spec_overlap_agrees_with_float64_on_a_field_far_from_the_origin(shift):
+    _overlap_against_float64(shift)
+
+
+def _cast_t_against_float64(shift):
     rng = np.random.default_rng(20241)
-    brow, qrow = _random_rows(rng, NB), _random_rows(rng, NQ)
+    brow, qrow = _shifted(_random_rows(rng, NB), shift), _shifted(_random_rows(rng, NQ), shift)
+    margin = _margin(shift)
     ang = rng.uniform(0, 2 * np.pi, NQ)
     d = np.stack([np.cos(ang), np.sin(ang)], axis=1) * rng.uniform(0.5, 3.0, (NQ, 1))
     max_t = rng.uniform(5.0, 60.0, NQ)
@@ -149,8 +180,8 @@ def test_spec_cast_t_agrees_with_a_float64_bisection():
         hi = np.where(over, mid, hi)
         lo = np.where(over, lo, mid)
     want_t = np.where(inside0, 0.0, hi)
-    near = (closest_to_zero(zero) < MARGIN) | (closest_to_zero(tmin) < MARGIN) | (closest_to_zero(end) < MARGIN)
-    near |= want_hit & ~inside0 & (np.abs(want_t - end) < MARGIN)
+    near = (closest_to_zero(zero) < margin) | (closest_to_zero(tmin) < margin) | (closest_to_zero(end) < margin)
+    near |= want_hit & ~inside0 & (np.abs(want_t - end) < margin)
     assert near.mean() <= CAP, "excluded share %.4f" % near.mean()
     got_hit, got_t = np.zeros((NQ, NB), dtype=bool), np.zeros((NQ, NB))
     for q, c in enumerate(casts):
@@ -162,7 +193,16 @@ def test_spec_cast_t_agrees_with_a_float64_bisection():
     assert (got_hit == want_hit)[keep].all(), "%d pairs disagree on the hit" % (got_hit != want_hit)[keep].sum()
     both = keep & want_hit
     err = np.abs(got_t - want_t)[both]
-    assert (err <= 1e-3 * np.abs(want_t[both]) + 1e-3).all(), "largest t error %g" % err.max()
+    assert (err <= 1e-3 * np.abs(want_t[both]) + margin).all(), "largest t error %g" % err.max()
+
+
+def test_spec_cast_t_agrees_with_a_float64_bisection():
+    _cast_t_against_float64((0.0, 0.0))
+
+
+@pytest.mark.parametrize("shift", SHIFTS, ids=lambda s: "%g,%g" % s)
+def test_spec_cast_t_agrees_with_float64_on_a_field_far_from_the_origin(shift):
+    _cast_t_against_float64(shift)
 
 
 # ---- the specification on hand-built cases ------------------------------------------------------------------------------------------
