@@ -669,7 +669,7 @@ int  phx_world_set_shapes(phx_world* w, const int32_t* bodies, const phx_shape* 
  * never set a shape reports boxes */
 int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
 /* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first, whether a spot is free for a box
- * and how far a box can move before it touches something.  Batched, answered on the device
+ * or a circle and how far a box or a circle can move before it touches something.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
  * its AABB {aabb_min, aabb_max} and its box {pos, xvector = xv, yvector = yv, geom_size = h (half extents)} (UpdateGeom copies the
  * first three into geom_pos / geom_xvector / geom_yvector, ref: RigidBody.h:38-42).  Every
@@ -725,7 +725,37 @@ int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
  *     one squares the origin's distance and loses a small disc's chord a few thousand units away; this one stays within a few
  *     2^-24 * the largest coordinate of the true entry at any distance, tests/query_reference.py.)
  *     Oriented-box queries and box casts see a circle as its frame square {r, r} in the body's frame: both are conservative (they never miss a disc and never report a later t) and consistent with each other, the
- *     two halves of "is this slot free, how far can I drop"; the exact disc versions are a later change.
+ *     two halves of "is this slot free, how far can I drop"; exact discs inside these two are a later change (their bytes are pinned).
+ *     A round query shape, exact against boxes and discs alike, is next:
+ *   - Query circle {c, r} (phx_world_query_circles; tests/round_query_spec.py states what follows as the same expressions): exact
+ *     against box bodies and circle bodies alike; rb = geom_size.x of a circle body.  The circle overlaps body b (closed) iff
+ *       a.min.x - r <= c.x && a.max.x + r >= c.x && a.min.y - r <= c.y && a.max.y + r >= c.y     (the oriented box's AABB conjunct with
+ *     extents (r, r): part of the result, so pruning can never change it; a NaN AABB overlaps nothing)  AND, with e = c - pos (per component),
+ *       box body:     u = e.x*xv.x + e.y*xv.y,  v = e.x*yv.x + e.y*yv.y,
+ *                     qu = (u < -h.x ? -h.x : (u > h.x ? h.x : u)),  qv = (v < -h.y ? -h.y : (v > h.y ? h.y : v))   (the box's closest point),
+ *                     gx = u - qu,  gy = v - qv,  and  gx*gx + gy*gy <= r*r;
+ *       circle body:  R = r + rb,  and  e.x*e.x + e.y*e.y <= R*R.
+ *   - Circle cast {c, r, d, max_t} (phx_world_cast_circles): the circle moves as c + t*d for t in [0, max_t].  Body b is a candidate iff
+ *     its AABB has min <= max on both axes and the ray's two-axis test passes with origin c, direction d, lo = a.min - (r, r),
+ *     hi = a.max + (r, r) (the box cast's candidate test with extents (r, r)).  The centre may not enter the body widened by the disc:
+ *       circle body:  the ray/disc rule above with origin c and R = r + rb wherever that rule has the radius, the normal's divisor
+ *                     included: normal = ((ex - s*dx) / R, (ey - s*dy) / R).
+ *       box body:     in the body's frame (o', d' formed as in the ray rule from r = c - pos) the widened box is the union of six convex
+ *                     parts, tested in this order: 0 the wide box, lo = (-(h.x + r), -h.y), hi = (h.x + r, h.y); 1 the tall box,
+ *                     lo = (-h.x, -(h.y + r)), hi = (h.x, h.y + r); 2 .. 5 the discs of radius r at the corners (-h.x, -h.y),
+ *                     (h.x, -h.y), (-h.x, h.y), (h.x, h.y).  A box part is the ray's two-axis slab test on o', d'; a disc part is the
+ *                     ray/disc rule with rx = o'.x - corner.x, ry = o'.y - corner.y and direction d'.  A part passes by its rule's own
+ *                     final condition, tin <= tout && tout >= 0 && tin <= max_t (and h2 >= 0 for a disc part).  The cast hits b iff
+ *                     some part passes; tin is the smallest passing tin, the first part in order on a tie.
+ *     Then t = (tin > 0 ? tin : 0) (never -0); normal = (0, 0) if tin < 0 (the circle overlaps b at the start); otherwise the winning
+ *     part's: a box part gives the stored vector of the face the centre is on at the entry: with p = (o'.x + tin*d'.x, o'.y + tin*d'.y),
+ *     xv if |p.x| - h.x >= |p.y| - h.y, else yv, negated when p on that axis is < 0: an exact copy, as in the ray rule; a disc part gives, with nx = (ex - s*d'.x) / r and ny = (ey - s*d'.y) / r of the ray/disc rule in
+ *     the frame, normal = (xv.x*nx + yv.x*ny, xv.y*nx + yv.y*ny).  The closest hit is the smallest t, ties to the lowest body index.
+ *     (Held to a float64 judge that works by signed distances, tests/round_query_reference.py.  One part of the rule was changed for
+ *     what it found: a box part's normal was first the slab test's entering axis, as in the ray rule, but a cast through the point
+ *     where a face of the widened box meets a corner's arc enters the wide or the tall box through its corner, the two axes tie to a
+ *     rounding, and the entering axis gave a normal a quarter turn off where the true one is continuous.  The face is now chosen by
+ *     where the centre is, which has a margin of r.  DESIGN.md, Queries: circles, has the figures.)
  * flags: PHX_QUERY_SKIP_STATIC leaves static bodies (inv_mass == 0 && inv_inertia == 0) out of every result (picking without the ground).
  *   A body that sleeps (SLEEPING below) is not static to a query although its inverse masses read 0 while it does: picking a box out of a
  *   resting pile finds it.  A world with sleeping off answers as it always did.
@@ -735,10 +765,10 @@ int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
  *   - Host-staged bodies (before the first step, after add_body / set_body_static / set_body_inverse_mass) are uploaded first, as the
  *     removal uploads them.
  *   - The host forms check all their input before anything is queued: count >= 0, no NULL array when count > 0, every value finite,
- *     min <= max for boxes, max_t >= 0 and d != (0, 0) for rays and casts, H > 0 on both axes for oriented boxes, flags in
+ *     min <= max for boxes, max_t >= 0 and d != (0, 0) for rays and casts, H > 0 on both axes for oriented boxes, r > 0 for circles, flags in
  *     {0, PHX_QUERY_SKIP_STATIC}; PHX_ERR_INVALID otherwise.
  *   - The device forms cannot check values: a query with a non-finite component, a ray or cast with max_t < 0 or d == (0, 0), an oriented
- *     box with H.x <= 0 or H.y <= 0 matches nothing.
+ *     box with H.x <= 0 or H.y <= 0, a circle with r <= 0 matches nothing.
  *   - An empty world and count == 0 are valid.
  *   - Sharded worlds (replica or slab) answer from their own world, in its local indices; there is no query across ranks.
  *   - A query changes nothing: not the records, the cached solver schedule, the broadphase's state or the next step's result.
@@ -768,6 +798,13 @@ typedef struct { int32_t body; float t; phx_vec2 normal; } phx_shape_hit;      /
 int  phx_world_cast_boxes(phx_world* w, const float* casts, int32_t count, int32_t flags, phx_shape_hit* out);
 /* the same on caller-owned device memory (4-byte aligned), queued on phx_world_stream(w) */
 int  phx_world_cast_boxes_device(phx_world* w, const void* d_casts, int32_t count, int32_t flags, void* d_out);
+/* circles: 3 floats per query {c.x, c.y, r}; the bodies whose box or disc overlaps the query circle (closed).  Output as
+ * phx_world_query_aabb (offsets, ascending hits, *total, PHX_ERR_CAPACITY); no device form: the output size depends on the data. */
+int  phx_world_query_circles(phx_world* w, const float* circles, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total);
+/* casts: 6 floats per query {c.x, c.y, r, dx, dy, max_t}; out[q] = the first body the circle touches moving c + t*d, t in [0, max_t] */
+int  phx_world_cast_circles(phx_world* w, const float* casts, int32_t count, int32_t flags, phx_shape_hit* out);
+/* the same on caller-owned device memory (4-byte aligned), queued on phx_world_stream(w) */
+int  phx_world_cast_circles_device(phx_world* w, const void* d_casts, int32_t count, int32_t flags, void* d_out);
 /* CONTACTS — what touches what, and how hard.  Answered on the device from the resident contact cache; nothing of the world crosses
  * PCIe but the answers.  Write s for the state the four getters would return at the call: bodies, manifolds, contact points (cps) and
  * joints.  A manifold m's live slots are k in [0, m.point_count); slot k is contact point cps[m.point_index + k].

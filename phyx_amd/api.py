@@ -1545,6 +1545,32 @@ class World:
         """cast_boxes on device memory (11 floats per cast in, a 16-byte shape_hit_dtype record per cast out), queued on the world's stream."""
         check(self.L.phx_world_cast_boxes_device(self.h, _dev_ptr(casts_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
 
+    def query_circles(self, circles, skip_static=False):
+        """Bodies whose box or disc overlaps each query circle (closed); circles (K, 3) {c.x, c.y, r}.  Returns (offsets, hits) as
+        query_aabb."""
+        c = self._queries(circles, 3, "query_circles", "{c.x, c.y, r}")
+        if (c[:, 2] <= 0).any():
+            raise ValueError("query_circles: the radius must be positive")
+        return self._overlaps(self.L.phx_world_query_circles, c, skip_static)
+
+    def cast_circles(self, casts, skip_static=False):
+        """The first body each circle touches moving c + t * d, t in [0, max_t]; casts (K, 6) {c.x, c.y, r, dx, dy, max_t}: a
+        shape_hit_dtype array (body -1 and zeros: no hit)."""
+        c = self._queries(casts, 6, "cast_circles", "{c.x, c.y, r, dx, dy, max_t}")
+        if (c[:, 2] <= 0).any():
+            raise ValueError("cast_circles: the radius must be positive")
+        if (c[:, 5] < 0).any():
+            raise ValueError("cast_circles: max_t must be >= 0")
+        if ((c[:, 3] == 0) & (c[:, 4] == 0)).any():
+            raise ValueError("cast_circles: a cast's direction must not be zero")
+        out = np.zeros(len(c), dtype=shape_hit_dtype)
+        check(self.L.phx_world_cast_circles(self.h, _ptr(c), len(c), 1 if skip_static else 0, _ptr(out)))
+        return out
+
+    def cast_circles_device(self, casts_ptr, count, out_ptr, skip_static=False):
+        """cast_circles on device memory (6 floats per cast in, a 16-byte shape_hit_dtype record per cast out), queued on the world's stream."""
+        check(self.L.phx_world_cast_circles_device(self.h, _dev_ptr(casts_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
+
     def query_index(self):
         """Queue the build of the query index unless it is current; returns how many times this world has built it."""
         n = C.c_int64(0)

@@ -301,6 +301,24 @@ int phx_world_cast_boxes_device(phx_world* w, const void* d_casts, int32_t count
     return w->impl.cast_boxes_device(d_casts, count, flags, d_out);
 }
 
+int phx_world_query_circles(phx_world* w, const float* circles, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_circles(circles, count, flags, offsets, hits, hit_cap, total);
+}
+
+int phx_world_cast_circles(phx_world* w, const float* casts, int32_t count, int32_t flags, phx_shape_hit* out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.cast_circles(casts, count, flags, out);
+}
+
+int phx_world_cast_circles_device(phx_world* w, const void* d_casts, int32_t count, int32_t flags, void* d_out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.cast_circles_device(d_casts, count, flags, d_out);
+}
+
 int phx_world_query_contacts(phx_world* w, const int32_t* bodies, int32_t count, int32_t flags, int32_t* offsets, phx_contact* out, int32_t cap, int64_t* total)
 {
     PHX_REQUIRE(w, "null handle");

@@ -16,13 +16,15 @@ struct QTree;
 
 class DeviceQuery {
 public:
-    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2, QUERY_SHAPES = 3, QUERY_CASTS = 4 };      // (BOXES: AABBs; SHAPES: oriented boxes)
+    // (BOXES: AABBs; SHAPES: oriented boxes; DISCS: circles)
+    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2, QUERY_SHAPES = 3, QUERY_CASTS = 4, QUERY_DISCS = 5, QUERY_DISC_CASTS = 6 };
     // the scan path answers batches up to this many queries of each kind, the index larger ones: the largest batch size at which
     // tools/query_cost.py measured the scan faster at cfg 2, each call after a step so that the index pays its build (INTEGRATION.md
     // §4b: points 2048 scan / 4096 index, rays 512 / 1024, boxes 1024 / 2048; sizes between two measured ones are not measured)
     // Oriented boxes and box casts take the thresholds of the AABB queries and the rays: they share their data path, and their own
-    // crossover was not measured.
-    static constexpr int SCAN_MAX[5] = {2048, 512, 1024, 1024, 512};
+    // crossover was not measured when they were made.  Circles and circle casts take 512, by the rule above:
+    // tools/round_query_cost.py measured both with the scan faster at 512 and the index faster at 1024 (Queries: circles).
+    static constexpr int SCAN_MAX[7] = {2048, 512, 1024, 1024, 512, 512, 512};
 
     // PHX_QUERY_PATH=scan|index forces a path; PHX_QUERY_SCAN_CHUNK=q (a multiple of 64) lowers the queries per chunk of the scan path's
     // AABB table.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
@@ -39,22 +41,26 @@ public:
     int shapes(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
                int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
     int casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s);
+    // circles (3 floats per query) and circle casts (6): as shapes and casts
+    int discs(const WorldBodies& w, int n, unsigned long long epoch, const float* d_circles, int count, int flags, int32_t* offsets, int32_t* hits,
+              int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
+    int disc_casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s);
     // the index alone (tools/query_cost.py times it): built unless it is current
     int ensure_index(const WorldBodies& w, int n, unsigned long long epoch, hipStream_t s);
     int index_builds() const { return index_.builds(); }
 
 private:
-    // OBB: oriented boxes instead of AABBs
-    template <bool OBB>
+    // SHAPE (query_kernels.h QSHAPE_*): AABBs or rays, oriented boxes, circles
+    template <int SHAPE>
     int overlaps(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
                  int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
-    template <bool OBB>
+    template <int SHAPE>
     int scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                   int64_t* total, Readback& rb, hipStream_t s);
-    template <bool OBB>
+    template <int SHAPE>
     int index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                    int64_t* total, Readback& rb, hipStream_t s);
-    template <bool CAST, class Hit>
+    template <int SHAPE, class Hit>
     int closest(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, Hit* d_out, hipStream_t s);
     // the current index over n bodies, as the kernels take it
     QTree tree(int n) const;

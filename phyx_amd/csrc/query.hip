@@ -95,21 +95,26 @@ int DeviceQuery::points(const WorldBodies& w, int n, unsigned long long epoch, c
     return PHX_OK;
 }
 
-template <bool CAST, class Hit>
+// the overlap lists' entry point, by query shape (the capacity complaint names it)
+static constexpr const char* OVERLAP_NAME[3] = {"phx_world_query_aabb", "phx_world_query_boxes", "phx_world_query_circles"};
+
+template <int SHAPE, class Hit>
 int DeviceQuery::closest(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, Hit* d_out, hipStream_t s)
 {
     if (count <= 0) return PHX_OK;
     PHX_TRY(ray_keys_.reserve((size_t)count));
-    if (n == 0 || choose(CAST ? QUERY_CASTS : QUERY_RAYS, count) == PATH_SCAN) {
+    constexpr Kind kind = SHAPE == QSHAPE_BOX ? QUERY_CASTS : SHAPE == QSHAPE_DISC ? QUERY_DISC_CASTS : QUERY_RAYS;
+    constexpr int tree_kind = SHAPE == QSHAPE_BOX ? QK_CAST : SHAPE == QSHAPE_DISC ? QK_DISC_CAST : QK_RAY;
+    if (n == 0 || choose(kind, count) == PATH_SCAN) {
         hipLaunchKernelGGL(k_qfill_u64, dim3(stream_grid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
-        if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_rays<CAST>), grid, dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p); });
+        if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_rays<SHAPE>), grid, dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p); });
     } else {
         PHX_TRY(ensure_index(w, n, epoch, s));
         const QTree t = tree(n);
-        hipLaunchKernelGGL((k_qtree<CAST ? QK_CAST : QK_RAY>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
+        hipLaunchKernelGGL((k_qtree<tree_kind>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
                            (const unsigned*)nullptr, (int*)nullptr);
     }
-    if constexpr (CAST) hipLaunchKernelGGL(k_qcast_finish, dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    if constexpr (SHAPE != QSHAPE_NONE) hipLaunchKernelGGL((k_qcast_finish<SHAPE>), dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
     else hipLaunchKernelGGL(k_qray_finish, dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
     PHX_HIP(hipGetLastError());
     return PHX_OK;
@@ -117,38 +122,50 @@ int DeviceQuery::closest(const WorldBodies& w, int n, unsigned long long epoch, 
 
 int DeviceQuery::rays(const WorldBodies& w, int n, unsigned long long epoch, const float* d_rays, int count, int flags, phx_ray_hit* d_out, hipStream_t s)
 {
-    return closest<false>(w, n, epoch, d_rays, count, flags, d_out, s);
+    return closest<QSHAPE_NONE>(w, n, epoch, d_rays, count, flags, d_out, s);
 }
 
 int DeviceQuery::casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s)
 {
-    return closest<true>(w, n, epoch, d_casts, count, flags, d_out, s);
+    return closest<QSHAPE_BOX>(w, n, epoch, d_casts, count, flags, d_out, s);
 }
 
-// ---- AABB and oriented-box queries ----------------------------------------------------------------------------------------------------
-template <bool OBB>
+int DeviceQuery::disc_casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s)
+{
+    return closest<QSHAPE_DISC>(w, n, epoch, d_casts, count, flags, d_out, s);
+}
+
+// ---- AABB, oriented-box and circle queries ----------------------------------------------------------------------------------------------------
+template <int SHAPE>
 int DeviceQuery::overlaps(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
                           int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
 {
     if (count <= 0 || n == 0) { Listing::none(count, offsets, total); return PHX_OK; }
-    if (choose(OBB ? QUERY_SHAPES : QUERY_BOXES, count) == PATH_SCAN) return scan_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    constexpr Kind kind = SHAPE == QSHAPE_BOX ? QUERY_SHAPES : SHAPE == QSHAPE_DISC ? QUERY_DISCS : QUERY_BOXES;
+    if (choose(kind, count) == PATH_SCAN) return scan_aabb<SHAPE>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
     PHX_TRY(ensure_index(w, n, epoch, s));
-    return index_aabb<OBB>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return index_aabb<SHAPE>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
 
 int DeviceQuery::aabb(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
                       int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
 {
-    return overlaps<false>(w, n, epoch, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return overlaps<QSHAPE_NONE>(w, n, epoch, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
 
 int DeviceQuery::shapes(const WorldBodies& w, int n, unsigned long long epoch, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits,
                         int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
 {
-    return overlaps<true>(w, n, epoch, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return overlaps<QSHAPE_BOX>(w, n, epoch, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
 
-template <bool OBB>
+int DeviceQuery::discs(const WorldBodies& w, int n, unsigned long long epoch, const float* d_circles, int count, int flags, int32_t* offsets, int32_t* hits,
+                       int hit_cap, int64_t* total, Readback& rb, hipStream_t s)
+{
+    return overlaps<QSHAPE_DISC>(w, n, epoch, d_circles, count, flags, offsets, hits, hit_cap, total, rb, s);
+}
+
+template <int SHAPE>
 int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                            int64_t* total, Readback& rb, hipStream_t s)
 {
@@ -161,38 +178,38 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
     PHX_HIP(hipMemsetAsync(list_.counts(), 0, (size_t)count * sizeof(unsigned), s));
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0);
-        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, OBB>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, list_.counts(), 0u, (int*)nullptr);
+        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, SHAPE>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, list_.counts(), 0u, (int*)nullptr);
     }
     PHX_HIP(hipGetLastError());
-    PHX_TRY(list_.settle(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", "hits", count, offsets, hit_cap, total, rb, s));
+    PHX_TRY(list_.settle(OVERLAP_NAME[SHAPE], "hits", count, offsets, hit_cap, total, rb, s));
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0), tiles = div_up(nq, Q_TILE);
         if (count > chunk)                                                  // (the table holds the last chunk's counts: count this one again)
-            hipLaunchKernelGGL((k_qscan_aabb<QS_RECOUNT, OBB>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr, 0u, (int*)nullptr);
+            hipLaunchKernelGGL((k_qscan_aabb<QS_RECOUNT, SHAPE>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr, 0u, (int*)nullptr);
         PHX_TRY(device_exclusive_scan(table_.p, nq * bblocks, nullptr, scan_, s));
-        hipLaunchKernelGGL((k_qscan_aabb<QS_FILL, OBB>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr,
+        hipLaunchKernelGGL((k_qscan_aabb<QS_FILL, SHAPE>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr,
                            (unsigned)offsets[q0], hits_.p);
     }
     PHX_HIP(hipGetLastError());
     return Listing::deliver(hits, hits_.p, *total, rb, s);
 }
 
-template <bool OBB>
+template <int SHAPE>
 int DeviceQuery::index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                             int64_t* total, Readback& rb, hipStream_t s)
 {
     const QTree t = tree(n);
     PHX_TRY(list_.room_with_segments(count));
-    hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_COUNT : QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, list_.counts(), (unsigned long long*)nullptr,
+    hipLaunchKernelGGL((k_qtree<SHAPE == QSHAPE_BOX ? QK_BOX_COUNT : SHAPE == QSHAPE_DISC ? QK_DISC_COUNT : QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, list_.counts(), (unsigned long long*)nullptr,
                        (const unsigned*)nullptr, (int*)nullptr);
     PHX_HIP(hipGetLastError());
-    PHX_TRY(list_.settle(OBB ? "phx_world_query_boxes" : "phx_world_query_aabb", "hits", count, offsets, hit_cap, total, rb, s));
+    PHX_TRY(list_.settle(OVERLAP_NAME[SHAPE], "hits", count, offsets, hit_cap, total, rb, s));
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
     PHX_TRY(list_.segments_from_counts(count, scan_, s));
-    hipLaunchKernelGGL((k_qtree<OBB ? QK_BOX_FILL : QK_AABB_FILL>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
+    hipLaunchKernelGGL((k_qtree<SHAPE == QSHAPE_BOX ? QK_BOX_FILL : SHAPE == QSHAPE_DISC ? QK_DISC_FILL : QK_AABB_FILL>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
                        list_.segments(), hits_.p);
     // ascending order: short segments in LDS, long ones by the radix sort (31-bit keys: the body indices)
     hipLaunchKernelGGL(k_qsort_segments, dim3(segment_grid(count)), dim3(256), 0, s, list_.segments(), (const unsigned*)list_.counts(), count, hits_.p);

@@ -1,11 +1,12 @@
 // query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box or disc, the closest
-// ray hit, oriented-box overlap and the closest box-cast hit over the resident arrays (body_view.h).  The predicates below are the
-// header's formulas one for one, each operation rounded on its own (the library is compiled with -ffp-contract=off);
-// tests/query_spec.py and tests/shape_query_spec.py state them again in numpy.
+// ray hit, oriented-box overlap and the closest box-cast hit, circle overlap and the closest circle-cast hit over the resident arrays
+// (body_view.h).  The predicates below are the header's formulas one for one, each operation rounded on its own (the library is
+// compiled with -ffp-contract=off); tests/query_spec.py, tests/shape_query_spec.py and tests/round_query_spec.py state them again in
+// numpy.
 //
 // Two paths give byte-identical results:
 //   scan   bodies in lanes, a tile of Q_TILE queries in LDS, one coalesced pass over the resident arrays per tile; points and rays
-//          and casts reduce with atomicMin (the body index; (bits(t) << 32) | body), AABB and box queries count per (query,
+//          and casts reduce with atomicMin (the body index; (bits(t) << 32) | body), AABB, box and circle queries count per (query,
 //          workgroup), scan, fill;
 //   index  a tree of 64-wide nodes over the bodies in Morton order (leaves: 64 consecutive sorted bodies), one wave per query: the
 //          64 lanes test one node's 64 children and __ballot picks the ones to descend into; the stack lives in LDS.
@@ -29,6 +30,10 @@ constexpr int Q_SKIP_STATIC = 1;        // PHX_QUERY_SKIP_STATIC
 struct QRay { float ox, oy, dx, dy, max_t; };
 struct QBox { float px, py, xx, xy, yx, yy, hx, hy; };      // a query box {pos, xv, yv, h}
 struct QCast { QBox b; float dx, dy, max_t; };
+struct QDisc { float cx, cy, r; };                          // a query circle {c, r}
+struct QDiscCast { QDisc c; float dx, dy, max_t; };
+// the shape a query brings: none (an AABB, a ray), an oriented box, a circle
+enum { QSHAPE_NONE = 0, QSHAPE_BOX = 1, QSHAPE_DISC = 2 };
 
 // the tree: level 0 is the sorted bodies (perm), level L >= 1 holds cnt[L] nodes at nodes[off[L] ..]; node i of level L bounds
 // children 64i .. 64i + 63 of level L - 1; the root is the one node of level `levels`
@@ -55,7 +60,8 @@ __device__ __forceinline__ bool q_point_in_box(float4 a, float4 m, float4 f, flo
 }
 
 // circles (include/phyx_amd.h SHAPES, QUERIES): `kinds` is the shape column, null while no body is a circle.  A circle's radius is its
-// size.x; the AABB conjunct and the candidate test are the box's.  Oriented boxes and casts see a circle as its frame square.
+// size.x; the AABB conjunct and the candidate test are the box's.  Oriented boxes and box casts see a circle as its frame square; query
+// circles and circle casts (the round predicates below) see the disc.
 __device__ __forceinline__ bool q_circle(const uint32_t* __restrict__ kinds, int i) { return kinds && kinds[i] != (uint32_t)PHX_SHAPE_BOX; }
 
 __device__ __forceinline__ bool q_point_in_circle(float4 a, float4 m, float r, float px, float py)
@@ -115,20 +121,26 @@ __device__ __forceinline__ bool q_ray_box(const QRay& r, float4 m, float4 f, flo
 // the ray against the disc (after the candidate test), by the closest approach: tc is where the line passes the centre closest, e the
 // offset there, s half the chord in units of t, under the box rule; nx, ny = the entry point from the centre (the normal is n / r).
 // Nothing of the size of the origin's distance is squared: a small disc seen from far away keeps its chord.
-__device__ __forceinline__ bool q_ray_circle(const QRay& r, float4 m, float rad, float& tin, float& nx, float& ny)
+// (q_ray_disc: the rule with the origin already taken relative to the centre: (rx, ry); a circle cast's corner discs use it in the
+// body's frame)
+__device__ __forceinline__ bool q_ray_disc(float rx, float ry, float dx, float dy, float max_t, float rad, float& tin, float& nx, float& ny)
 {
-    const float rx = r.ox - m.z, ry = r.oy - m.w;
-    const float a = r.dx * r.dx + r.dy * r.dy, b = rx * r.dx + ry * r.dy;
+    const float a = dx * dx + dy * dy, b = rx * dx + ry * dy;
     const float tc = -b / a;
-    const float ex = rx + tc * r.dx, ey = ry + tc * r.dy;
+    const float ex = rx + tc * dx, ey = ry + tc * dy;
     const float h2 = rad * rad - (ex * ex + ey * ey);
     tin = 0.f; nx = 0.f; ny = 0.f;
     if (!(h2 >= 0.f)) return false;
     const float s = sqrtf(h2 / a);
     tin = tc - s;
     const float tout = tc + s;
-    nx = ex - s * r.dx; ny = ey - s * r.dy;
-    return tin <= tout && tout >= 0.f && tin <= r.max_t;
+    nx = ex - s * dx; ny = ey - s * dy;
+    return tin <= tout && tout >= 0.f && tin <= max_t;
+}
+
+__device__ __forceinline__ bool q_ray_circle(const QRay& r, float4 m, float rad, float& tin, float& nx, float& ny)
+{
+    return q_ray_disc(r.ox - m.z, r.oy - m.w, r.dx, r.dy, r.max_t, rad, tin, nx, ny);
 }
 
 // the ray against body b's own shape (after the candidate test): tin alone
@@ -211,6 +223,77 @@ __device__ __forceinline__ bool q_cast_box(const QCast& c, float4 m, float4 f, f
     return ok && out.tin <= tout && tout >= 0.f && out.tin <= c.max_t;
 }
 
+// ---- the round predicates (include/phyx_amd.h: circles and circle casts) ------------------------------------------------------------------
+// the AABB conjunct (a body's AABB or a node's bounds, widened by the radius): q_box_near with the extents (r, r)
+__device__ __forceinline__ bool q_disc_near(const QDisc& c, float4 a)
+{
+    return a.x - c.r <= c.cx && a.z + c.r >= c.cx && a.y - c.r <= c.cy && a.w + c.r >= c.cy;
+}
+
+// the circle against body b's own shape: the centre's offset from the closest point of the box, or the two radii's sum
+__device__ __forceinline__ bool q_disc_overlap(const QDisc& c, float4 a, bool circle, float4 m, float4 f, float2 h)
+{
+    if (!q_disc_near(c, a)) return false;
+    const float ex = c.cx - m.z, ey = c.cy - m.w;
+    if (circle) { const float R = c.r + h.x; return ex * ex + ey * ey <= R * R; }
+    const float u = ex * f.x + ey * f.y, v = ex * f.z + ey * f.w;
+    const float qu = u < -h.x ? -h.x : (u > h.x ? h.x : u), qv = v < -h.y ? -h.y : (v > h.y ? h.y : v);
+    const float gx = u - qu, gy = v - qv;
+    return gx * gx + gy * gy <= c.r * c.r;
+}
+
+// candidate test of a circle cast against an AABB (a body's or a node's bounds): q_cast_aabb with the extents (r, r)
+__device__ __forceinline__ bool q_cast_aabb(const QDiscCast& c, float4 a)
+{
+    if (!(a.x <= a.z && a.y <= a.w)) return false;
+    float tin; bool xe;
+    return q_ray_test(c.c.cx, c.c.cy, c.dx, c.dy, a.x - c.c.r, a.y - c.c.r, a.z + c.c.r, a.w + c.c.r, c.max_t, tin, xe);
+}
+
+// part: 0 the wide box, 1 the tall box, 2 .. 5 the corner discs (-,-) (+,-) (-,+) (+,+), Q_PART_BODY a circle body's own disc.
+// ox, oy, dxp, dyp: o' and d', the cast in a box's frame (q_ray_box);  nx, ny: a disc part's entry point from its centre (q_ray_disc)
+constexpr int Q_PART_BODY = 6;
+struct QCastDisc { float tin; int part; float ox, oy, dxp, dyp, nx, ny; };
+
+// the centre's ray against the body widened by the radius (after the candidate test): a circle body is the disc of radius r + rb; a
+// box is the union of six convex parts, each met by its own rule, and the earliest entry wins (the first part in order on a tie).
+// Every part is evaluated and the winner kept by selects on named values: no run-time-indexed array (narrowphase.h).
+__device__ __forceinline__ bool q_cast_disc(const QDiscCast& c, bool circle, float4 m, float4 f, float2 h, QCastDisc& out)
+{
+    out.tin = 0.f; out.part = 0; out.ox = 0.f; out.oy = 0.f; out.dxp = 0.f; out.dyp = 0.f; out.nx = 0.f; out.ny = 0.f;
+    const float rx = c.c.cx - m.z, ry = c.c.cy - m.w;
+    if (circle) {
+        out.part = Q_PART_BODY;
+        return q_ray_disc(rx, ry, c.dx, c.dy, c.max_t, c.c.r + h.x, out.tin, out.nx, out.ny);
+    }
+    const float ox = rx * f.x + ry * f.y, oy = rx * f.z + ry * f.w;
+    out.ox = ox; out.oy = oy;
+    out.dxp = c.dx * f.x + c.dy * f.y;
+    out.dyp = c.dx * f.z + c.dy * f.w;
+    const float wx = h.x + c.c.r, wy = h.y + c.c.r;
+    float tin = 0.f;
+    bool xe = false;
+    bool hit = q_ray_test(ox, oy, out.dxp, out.dyp, -wx, -h.y, wx, h.y, c.max_t, tin, xe);
+    out.tin = hit ? tin : 0.f;
+    {
+        const bool pass = q_ray_test(ox, oy, out.dxp, out.dyp, -h.x, -wy, h.x, wy, c.max_t, tin, xe);
+        const bool better = pass && (!hit || tin < out.tin);
+        out.tin = better ? tin : out.tin; out.part = better ? 1 : out.part;
+        hit = hit || pass;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float kx = (k & 1) ? h.x : -h.x, ky = (k & 2) ? h.y : -h.y;
+        float nx, ny;
+        const bool pass = q_ray_disc(ox - kx, oy - ky, out.dxp, out.dyp, c.max_t, c.c.r, tin, nx, ny);
+        const bool better = pass && (!hit || tin < out.tin);
+        out.tin = better ? tin : out.tin; out.part = better ? 2 + k : out.part;
+        out.nx = better ? nx : out.nx; out.ny = better ? ny : out.ny;
+        hit = hit || pass;
+    }
+    return hit;
+}
+
 __device__ __forceinline__ unsigned long long q_ray_key(float tin, int body)
 {
     const float t = tin > 0.f ? tin : 0.f;                       // t >= 0: its bits order like its value
@@ -234,6 +317,12 @@ __device__ __forceinline__ bool q_cast_ok(const QCast& c)
     return q_shape_ok(c.b) && isfinite(c.dx) && isfinite(c.dy) && isfinite(c.max_t) && c.max_t >= 0.f && (c.dx != 0.f || c.dy != 0.f);
 }
 
+__device__ __forceinline__ bool q_disc_ok(const QDisc& c) { return isfinite(c.cx) && isfinite(c.cy) && isfinite(c.r) && c.r > 0.f; }
+__device__ __forceinline__ bool q_cast_ok(const QDiscCast& c)
+{
+    return q_disc_ok(c.c) && isfinite(c.dx) && isfinite(c.dy) && isfinite(c.max_t) && c.max_t >= 0.f && (c.dx != 0.f || c.dy != 0.f);
+}
+
 __device__ __forceinline__ QRay q_load_ray(const float* __restrict__ rays, int q)
 {
     const float* p = rays + 5 * (size_t)q;
@@ -245,6 +334,13 @@ __device__ __forceinline__ QCast q_load_cast(const float* __restrict__ casts, in
 {
     const float* p = casts + 11 * (size_t)q;
     return QCast{q_load_box(p), p[8], p[9], p[10]};
+}
+
+__device__ __forceinline__ QDisc q_load_disc(const float* __restrict__ p) { return QDisc{p[0], p[1], p[2]}; }
+__device__ __forceinline__ QDiscCast q_load_disc_cast(const float* __restrict__ casts, int q)
+{
+    const float* p = casts + 6 * (size_t)q;
+    return QDiscCast{q_load_disc(p), p[3], p[4], p[5]};
 }
 
 __device__ __forceinline__ unsigned long long q_lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
@@ -308,7 +404,8 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
     }
 }
 
-// the cast results from the winners' keys, as k_qray_finish
+// the cast results from the winners' keys, as k_qray_finish (SHAPE: QSHAPE_BOX box casts, QSHAPE_DISC circle casts)
+template <int SHAPE>
 static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, const float* __restrict__ casts, int count,
                                                              const unsigned long long* __restrict__ keys, phx_shape_hit* __restrict__ out)
 {
@@ -316,7 +413,30 @@ static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, cons
         const unsigned long long k = keys[q];
         phx_shape_hit h;
         h.body = -1; h.t = 0.f; h.normal.x = h.normal.y = 0.f;
-        if (k != ~0ull) {
+        if (k != ~0ull && SHAPE == QSHAPE_DISC) {
+            const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
+            const QDiscCast c = q_load_disc_cast(casts, q);
+            const float4 f = w.frame[b];
+            const float2 sz = w.size[b];
+            QCastDisc cd;
+            (void)q_cast_disc(c, q_circle(w.kinds, b), w.s.mpos[b], f, sz, cd);
+            h.body = b; h.t = cd.tin > 0.f ? cd.tin : 0.f;
+            if (!(cd.tin < 0.f)) {
+                if (cd.part < 2) {                                          // a face, by where the centre is at the entry: an exact copy
+                    const float px = cd.ox + cd.tin * cd.dxp, py = cd.oy + cd.tin * cd.dyp;
+                    const bool xface = fabsf(px) - sz.x >= fabsf(py) - sz.y;
+                    const float nx = xface ? f.x : f.z, ny = xface ? f.y : f.w;
+                    const bool flip = (xface ? px : py) < 0.f;
+                    h.normal.x = flip ? -nx : nx; h.normal.y = flip ? -ny : ny;
+                } else if (cd.part == Q_PART_BODY) {
+                    const float R = c.c.r + sz.x;
+                    h.normal.x = cd.nx / R; h.normal.y = cd.ny / R;
+                } else {                                                    // a corner: the local normal through the frame
+                    const float nx = cd.nx / c.c.r, ny = cd.ny / c.c.r;
+                    h.normal.x = f.x * nx + f.z * ny; h.normal.y = f.y * nx + f.w * ny;
+                }
+            }
+        } else if (k != ~0ull) {
             const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
             const QCast c = q_load_cast(casts, q);
             const float4 f = w.frame[b];
@@ -364,21 +484,27 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
     }
 }
 
-// CAST: box casts (11 floats per query) instead of rays (5)
-template <bool CAST>
+// SHAPE: rays (5 floats per query), box casts (11) or circle casts (6)
+template <int SHAPE>
 static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n, const float* __restrict__ rays, int count, int q0, int flags,
                                                            unsigned long long* __restrict__ keys)
 {
     __shared__ QRay qr[Q_TILE];
     __shared__ QCast qc[Q_TILE];
+    __shared__ QDiscCast qd[Q_TILE];
     __shared__ float2 qe[Q_TILE];
     __shared__ int qok[Q_TILE];
+    constexpr bool CAST = SHAPE == QSHAPE_BOX, DISC = SHAPE == QSHAPE_DISC;
     const int base_q = q0 + blockIdx.y * Q_TILE, nq = min(Q_TILE, count - base_q);
     if ((int)threadIdx.x < nq) {
         if (CAST) {
             const QCast c = q_load_cast(rays, base_q + threadIdx.x);
             qc[threadIdx.x] = c;
             qe[threadIdx.x] = q_box_extents(c.b);
+            qok[threadIdx.x] = q_cast_ok(c);
+        } else if (DISC) {
+            const QDiscCast c = q_load_disc_cast(rays, base_q + threadIdx.x);
+            qd[threadIdx.x] = c;
             qok[threadIdx.x] = q_cast_ok(c);
         } else {
             const QRay r = q_load_ray(rays, base_q + threadIdx.x);
@@ -404,6 +530,11 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
                 QCastBox cb;
                 hit = any && qok[q] && q_cast_aabb(c, qe[q], a) && q_cast_box(c, m, f, h, cb);
                 tin = hit ? cb.tin : 0.f;
+            } else if (DISC) {
+                const QDiscCast c = qd[q];
+                QCastDisc cd;
+                hit = any && qok[q] && q_cast_aabb(c, a) && q_cast_disc(c, round, m, f, h, cd);
+                tin = hit ? cd.tin : 0.f;
             } else {
                 const QRay r = qr[q];
                 float t0 = 0.f;
@@ -417,22 +548,24 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
     }
 }
 
-// AABB queries (OBB: oriented-box queries, 8 floats per query), one workgroup per 256 consecutive bodies (blockIdx.x = body block of
+// AABB queries (SHAPE: oriented-box queries, 8 floats per query, or circle queries, 3), one workgroup per 256 consecutive bodies (blockIdx.x = body block of
 // `bblocks`), blockIdx.y = tile.
 //   QS_COUNT    writes the hit count of every (query, body block) to table[(q - q0) * bblocks + block] (query-major: its exclusive scan
 //               places the blocks' hits of a query one after the other, in body order) and adds it to qcount[q];
 //   QS_RECOUNT  the table alone (a later chunk of queries counted again: the table holds one chunk);
 //   QS_FILL     writes the hits at base + table[...] + rank.
 enum { QS_COUNT = 0, QS_RECOUNT = 1, QS_FILL = 2 };
-template <int MODE, bool OBB>
+template <int MODE, int SHAPE>
 static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n, const float* __restrict__ boxes, int count, int q0, int flags, int bblocks,
                                                            unsigned* __restrict__ table, unsigned* __restrict__ qcount, unsigned base, int* __restrict__ hits)
 {
     __shared__ float4 qb[Q_TILE];
     __shared__ QBox qo[Q_TILE];
+    __shared__ QDisc qd[Q_TILE];
     __shared__ float2 qe[Q_TILE];
     __shared__ int qok[Q_TILE];
     __shared__ unsigned long long masks[Q_TILE][4];
+    constexpr bool OBB = SHAPE == QSHAPE_BOX, DISC = SHAPE == QSHAPE_DISC;
     const int tile_q = blockIdx.y * Q_TILE, base_q = q0 + tile_q, nq = min(Q_TILE, count - base_q);
     if ((int)threadIdx.x < nq) {
         if (OBB) {
@@ -440,6 +573,10 @@ static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n,
             qo[threadIdx.x] = q;
             qe[threadIdx.x] = q_box_extents(q);
             qok[threadIdx.x] = q_shape_ok(q);
+        } else if (DISC) {
+            const QDisc q = q_load_disc(boxes + 3 * (size_t)(base_q + threadIdx.x));
+            qd[threadIdx.x] = q;
+            qok[threadIdx.x] = q_disc_ok(q);
         } else {
             const float* p = boxes + 4 * (size_t)(base_q + threadIdx.x);
             const float4 q = make_float4(p[0], p[1], p[2], p[3]);
@@ -452,14 +589,15 @@ static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n,
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool live = i < n;
     const float4 a = live ? w.aabb[i] : make_float4(NAN, NAN, NAN, NAN);
-    const float4 m = (OBB || (flags & Q_SKIP_STATIC)) ? w.s.mpos[live ? i : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 m = (OBB || DISC || (flags & Q_SKIP_STATIC)) ? w.s.mpos[live ? i : 0] : make_float4(0.f, 0.f, 0.f, 0.f);
     const bool any = live && !((flags & Q_SKIP_STATIC) && q_static(m, w.sleep, i));
     float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
     float2 h = make_float2(0.f, 0.f);
-    if (OBB && live) { f = w.frame[i]; h = w.size[i]; }
+    if ((OBB || DISC) && live) { f = w.frame[i]; h = w.size[i]; }
+    const bool round = DISC && live && q_circle(w.kinds, i);
     unsigned long long mine = 0;
     for (int q = 0; q < nq; ++q) {
-        const bool hit = any && qok[q] && (OBB ? q_box_overlap(qo[q], qe[q], a, m, f, h) : q_overlap(a, qb[q]));
+        const bool hit = any && qok[q] && (OBB ? q_box_overlap(qo[q], qe[q], a, m, f, h) : DISC ? q_disc_overlap(qd[q], a, round, m, f, h) : q_overlap(a, qb[q]));
         const unsigned long long mask = __ballot(hit);
         if (lane == 0) masks[q][wave] = mask;
         mine |= (unsigned long long)hit << q;
@@ -556,7 +694,8 @@ static __global__ void __launch_bounds__(256) k_qnodes(const float4* __restrict_
 }
 
 // ---- index path: traversal ----------------------------------------------------------------------------------------------------------
-enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COUNT = 4, QK_BOX_FILL = 5, QK_CAST = 6 };
+enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COUNT = 4, QK_BOX_FILL = 5, QK_CAST = 6,
+       QK_DISC_COUNT = 7, QK_DISC_FILL = 8, QK_DISC_CAST = 9 };
 
 // one wave per query, 4 per workgroup.  A stack entry is (level << 26) | node; a popped node's 64 children are tested by the 64 lanes,
 // the passing inner nodes pushed in lane order.  Depth bound: a pop pushes at most 64 entries of the level below, so the stack never
@@ -566,7 +705,9 @@ enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COU
 //   QK_AABB_COUNT  out_u32[q] = the number of hits
 //   QK_AABB_FILL   the hits at hits[seg[q] ..], in traversal order (sorted afterwards)
 //   QK_BOX_COUNT, QK_BOX_FILL   the same two for oriented boxes;   QK_CAST   as QK_RAY for box casts
-// A lane tests a child's bounds with the query's AABB conjunct: the bounds widened by the box's extents for the last three kinds.
+//   QK_DISC_COUNT, QK_DISC_FILL, QK_DISC_CAST   the same three for circles
+// A lane tests a child's bounds with the query's AABB conjunct: the bounds widened by the box's extents or the circle's radius for the
+// last six kinds.
 template <int KIND>
 static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, const float* __restrict__ queries, int count, int flags,
                                                       unsigned* __restrict__ out_u32, unsigned long long* __restrict__ out_key,
@@ -575,15 +716,24 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
     __shared__ unsigned stack_mem[4][Q_MAX_LEVELS * Q_FANOUT];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const bool skip = (flags & Q_SKIP_STATIC) != 0;
-    constexpr bool OBB = KIND == QK_BOX_COUNT || KIND == QK_BOX_FILL, COUNT = KIND == QK_AABB_COUNT || KIND == QK_BOX_COUNT;
-    constexpr bool FILL = KIND == QK_AABB_FILL || KIND == QK_BOX_FILL, KEY = KIND == QK_RAY || KIND == QK_CAST;
+    constexpr bool OBB = KIND == QK_BOX_COUNT || KIND == QK_BOX_FILL, DISC = KIND == QK_DISC_COUNT || KIND == QK_DISC_FILL;
+    constexpr bool COUNT = KIND == QK_AABB_COUNT || KIND == QK_BOX_COUNT || KIND == QK_DISC_COUNT;
+    constexpr bool FILL = KIND == QK_AABB_FILL || KIND == QK_BOX_FILL || KIND == QK_DISC_FILL;
+    constexpr bool KEY = KIND == QK_RAY || KIND == QK_CAST || KIND == QK_DISC_CAST;
     for (int q = blockIdx.x * 4 + wave; q < count; q += gridDim.x * 4) {      // (the whole wave: grid-strided over the queries)
         float4 qbox = make_float4(0.f, 0.f, 0.f, 0.f);
         QRay r{0.f, 0.f, 0.f, 0.f, 0.f};
         QCast cs{{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, 0.f};      // (a box query uses cs.b)
         float2 ce = make_float2(0.f, 0.f);
+        QDiscCast ds{{0.f, 0.f, 0.f}, 0.f, 0.f, 0.f};                          // (a circle query uses ds.c)
         bool ok;
-        if (KIND == QK_POINT) {
+        if (KIND == QK_DISC_CAST) {
+            ds = q_load_disc_cast(queries, q);
+            ok = q_cast_ok(ds);
+        } else if (DISC) {
+            ds.c = q_load_disc(queries + 3 * (size_t)q);
+            ok = q_disc_ok(ds.c);
+        } else if (KIND == QK_POINT) {
             const float px = queries[2 * (size_t)q], py = queries[2 * (size_t)q + 1];
             ok = q_point_ok(px, py);
             qbox = make_float4(px, py, px, py);                            // (the point's closed AABB test is the overlap test with this box)
@@ -631,7 +781,12 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                                 QCastBox cb;
                                 hit = q_cast_aabb(cs, ce, a) && q_cast_box(cs, m, w.frame[b], w.size[b], cb);
                                 if (hit) { const unsigned long long k = q_ray_key(cb.tin, b); best_key = k < best_key ? k : best_key; }
+                            } else if (KIND == QK_DISC_CAST) {
+                                QCastDisc cd;
+                                hit = q_cast_aabb(ds, a) && q_cast_disc(ds, q_circle(w.kinds, b), m, w.frame[b], w.size[b], cd);
+                                if (hit) { const unsigned long long k = q_ray_key(cd.tin, b); best_key = k < best_key ? k : best_key; }
                             } else if (OBB) hit = q_box_overlap(cs.b, ce, a, m, w.frame[b], w.size[b]);
+                            else if (DISC) hit = q_disc_overlap(ds.c, a, q_circle(w.kinds, b), m, w.frame[b], w.size[b]);
                             else hit = q_overlap(a, qbox);
                         }
                     }
@@ -646,7 +801,8 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                     bool pass = false;
                     if (c < t.cnt[level - 1]) {
                         const float4 nb = t.nodes[t.off[level - 1] + c];
-                        pass = KIND == QK_RAY ? q_ray_aabb(r, nb) : KIND == QK_CAST ? q_cast_aabb(cs, ce, nb) : OBB ? q_box_near(cs.b, ce, nb) : q_overlap(nb, qbox);
+                        pass = KIND == QK_RAY ? q_ray_aabb(r, nb) : KIND == QK_CAST ? q_cast_aabb(cs, ce, nb) : OBB ? q_box_near(cs.b, ce, nb)
+                             : KIND == QK_DISC_CAST ? q_cast_aabb(ds, nb) : DISC ? q_disc_near(ds.c, nb) : q_overlap(nb, qbox);
                     }
                     const unsigned long long mask = __ballot(pass);
                     if (pass) st[sp + __popcll(mask & q_lanes_below())] = ((unsigned)(level - 1) << 26) | (unsigned)c;

@@ -13,22 +13,34 @@ static int flags_check(const char* what, int flags)      // (the queries' and th
     return PHX_OK;
 }
 
-static int query_check(const char* what, const float* v, int count, int width, int flags, bool device, const void* out)
+// what a row of each kind of query holds (World::QueryRows): its width in floats, what the messages call it, and where the values
+// with a rule of their own are (-1: none): an AABB's min <= max, an oriented box's half extents, a circle's radius, a direction, max_t
+struct RowRule { int width; const char* noun; bool ordered; int half, radius, dir, max_t; };
+static const RowRule ROW_RULES[] = {
+    {2, "point", false, -1, -1, -1, -1},      // ROWS_POINTS
+    {4, "box", true, -1, -1, -1, -1},         // ROWS_BOXES
+    {5, "ray", false, -1, -1, 2, 4},          // ROWS_RAYS
+    {8, "box", false, 6, -1, -1, -1},         // ROWS_SHAPES
+    {11, "cast", false, 6, -1, 8, 10},        // ROWS_CASTS
+    {3, "circle", false, -1, 2, -1, -1},      // ROWS_CIRCLES
+    {6, "cast", false, -1, 2, 3, 5},          // ROWS_CIRCLE_CASTS
+};
+
+static int query_check(const char* what, const float* v, int count, const RowRule& r, int flags, bool device, const void* out)
 {
     if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
     PHX_TRY(flags_check(what, flags));
     if (count && (!v || !out)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
     if (device) return PHX_OK;
     for (int k = 0; k < count; ++k) {
-        const float* q = v + (size_t)width * k;
-        for (int c = 0; c < width; ++c)
+        const float* q = v + (size_t)r.width * k;
+        for (int c = 0; c < r.width; ++c)
             if (!std::isfinite(q[c])) { set_error("%s: query %d: value %d is not finite", what, k, c); return PHX_ERR_INVALID; }
-        if (width == 4 && !(q[0] <= q[2] && q[1] <= q[3])) { set_error("%s: box %d: min exceeds max", what, k); return PHX_ERR_INVALID; }
-        if (width == 5 && !(q[4] >= 0.f)) { set_error("%s: ray %d: max_t < 0", what, k); return PHX_ERR_INVALID; }
-        if (width == 5 && q[2] == 0.f && q[3] == 0.f) { set_error("%s: ray %d: zero direction", what, k); return PHX_ERR_INVALID; }
-        if (width >= 8 && !(q[6] > 0.f && q[7] > 0.f)) { set_error("%s: box %d: half extents must be positive", what, k); return PHX_ERR_INVALID; }
-        if (width == 11 && !(q[10] >= 0.f)) { set_error("%s: cast %d: max_t < 0", what, k); return PHX_ERR_INVALID; }
-        if (width == 11 && q[8] == 0.f && q[9] == 0.f) { set_error("%s: cast %d: zero direction", what, k); return PHX_ERR_INVALID; }
+        if (r.ordered && !(q[0] <= q[2] && q[1] <= q[3])) { set_error("%s: box %d: min exceeds max", what, k); return PHX_ERR_INVALID; }
+        if (r.half >= 0 && !(q[r.half] > 0.f && q[r.half + 1] > 0.f)) { set_error("%s: box %d: half extents must be positive", what, k); return PHX_ERR_INVALID; }
+        if (r.radius >= 0 && !(q[r.radius] > 0.f)) { set_error("%s: circle %d: the radius must be positive", what, k); return PHX_ERR_INVALID; }
+        if (r.max_t >= 0 && !(q[r.max_t] >= 0.f)) { set_error("%s: %s %d: max_t < 0", what, r.noun, k); return PHX_ERR_INVALID; }
+        if (r.dir >= 0 && q[r.dir] == 0.f && q[r.dir + 1] == 0.f) { set_error("%s: %s %d: zero direction", what, r.noun, k); return PHX_ERR_INVALID; }
     }
     return PHX_OK;
 }
@@ -42,14 +54,15 @@ int World::query_prepare(bool host_wait)
 
 // one result per query, to the host: check, prepare, `miss` for every query of an empty world, stage, reserve, run, read back
 template <class Hit>
-int World::query_rows(const char* what, const float* rows, int count, int width, int flags, Hit* out, const Hit& miss, DevBuf<Hit>& buf, QueryRun<Hit> run)
+int World::query_rows(const char* what, const float* rows, int count, QueryRows kind, int flags, Hit* out, const Hit& miss, DevBuf<Hit>& buf, QueryRun<Hit> run)
 {
-    PHX_TRY(query_check(what, rows, count, width, flags, false, out));
+    const RowRule& rule = ROW_RULES[kind];
+    PHX_TRY(query_check(what, rows, count, rule, flags, false, out));
     if (!count) return PHX_OK;
     PHX_TRY(query_prepare(true));
     if (!nb()) { std::fill(out, out + count, miss); return PHX_OK; }
     const float* d_rows = nullptr;
-    PHX_TRY(stage_.values(rows, count, width, stream_, &d_rows));
+    PHX_TRY(stage_.values(rows, count, rule.width, stream_, &d_rows));
     PHX_TRY(buf.reserve((size_t)count));
     PHX_TRY((query_.*run)(query_view(), nb(), geom_epoch_, d_rows, count, flags, buf.p, stream_));
     PHX_TRY(rb_.add(out, buf.p, (size_t)count * sizeof(Hit), stream_));
@@ -58,9 +71,9 @@ int World::query_rows(const char* what, const float* rows, int count, int width,
 
 // ... on caller-owned device memory: only queued
 template <class Hit>
-int World::query_rows_device(const char* what, const void* d_rows, int count, int width, int flags, void* d_out, QueryRun<Hit> run)
+int World::query_rows_device(const char* what, const void* d_rows, int count, QueryRows kind, int flags, void* d_out, QueryRun<Hit> run)
 {
-    PHX_TRY(query_check(what, static_cast<const float*>(d_rows), count, width, flags, true, d_out));
+    PHX_TRY(query_check(what, static_cast<const float*>(d_rows), count, ROW_RULES[kind], flags, true, d_out));
     if (count && ((reinterpret_cast<uintptr_t>(d_rows) | reinterpret_cast<uintptr_t>(d_out)) & 3u)) { set_error("%s: the arrays must be 4-byte aligned", what); return PHX_ERR_INVALID; }
     if (!count) return PHX_OK;
     PHX_TRY(query_prepare(false));
@@ -68,14 +81,15 @@ int World::query_rows_device(const char* what, const void* d_rows, int count, in
 }
 
 // the overlap lists (offsets, ascending hits, total): DeviceQuery waits for them itself
-int World::query_overlaps(const char* what, const float* boxes, int count, int width, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total, OverlapRun run)
+int World::query_overlaps(const char* what, const float* boxes, int count, QueryRows kind, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total, OverlapRun run)
 {
-    PHX_TRY(query_check(what, boxes, count, width, flags, false, boxes));
+    const RowRule& rule = ROW_RULES[kind];
+    PHX_TRY(query_check(what, boxes, count, rule, flags, false, boxes));
     if (!offsets || !total) { set_error("%s: null offsets / total", what); return PHX_ERR_INVALID; }
     if (hit_cap < 0 || (hit_cap > 0 && !hits)) { set_error("%s: bad hits buffer (cap %d)", what, hit_cap); return PHX_ERR_INVALID; }
     PHX_TRY(query_prepare(true));
     const float* d_boxes = nullptr;
-    if (count && nb()) PHX_TRY(stage_.values(boxes, count, width, stream_, &d_boxes));
+    if (count && nb()) PHX_TRY(stage_.values(boxes, count, rule.width, stream_, &d_boxes));
     return (query_.*run)(query_view(), nb(), geom_epoch_, d_boxes, count, flags, offsets, hits, hit_cap, total, rb_, stream_);
 }
 
@@ -84,18 +98,24 @@ static const phx_shape_hit SHAPE_MISS = {-1, 0.f, {0.f, 0.f}};
 
 int World::query_aabb(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
 {
-    return query_overlaps("phx_world_query_aabb", boxes, count, 4, flags, offsets, hits, hit_cap, total, &DeviceQuery::aabb);
+    return query_overlaps("phx_world_query_aabb", boxes, count, ROWS_BOXES, flags, offsets, hits, hit_cap, total, &DeviceQuery::aabb);
 }
 int World::query_boxes(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
 {
-    return query_overlaps("phx_world_query_boxes", boxes, count, 8, flags, offsets, hits, hit_cap, total, &DeviceQuery::shapes);
+    return query_overlaps("phx_world_query_boxes", boxes, count, ROWS_SHAPES, flags, offsets, hits, hit_cap, total, &DeviceQuery::shapes);
 }
-int World::query_points(const float* points, int count, int flags, int32_t* body) { return query_rows<int>("phx_world_query_points", points, count, 2, flags, body, -1, q_body_, &DeviceQuery::points); }
-int World::raycast(const float* rays, int count, int flags, phx_ray_hit* out) { return query_rows("phx_world_raycast", rays, count, 5, flags, out, RAY_MISS, q_hits_, &DeviceQuery::rays); }
-int World::cast_boxes(const float* casts, int count, int flags, phx_shape_hit* out) { return query_rows("phx_world_cast_boxes", casts, count, 11, flags, out, SHAPE_MISS, q_shape_hits_, &DeviceQuery::casts); }
-int World::query_points_device(const void* d_points, int count, int flags, void* d_body) { return query_rows_device<int>("phx_world_query_points_device", d_points, count, 2, flags, d_body, &DeviceQuery::points); }
-int World::raycast_device(const void* d_rays, int count, int flags, void* d_out) { return query_rows_device<phx_ray_hit>("phx_world_raycast_device", d_rays, count, 5, flags, d_out, &DeviceQuery::rays); }
-int World::cast_boxes_device(const void* d_casts, int count, int flags, void* d_out) { return query_rows_device<phx_shape_hit>("phx_world_cast_boxes_device", d_casts, count, 11, flags, d_out, &DeviceQuery::casts); }
+int World::query_circles(const float* circles, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
+{
+    return query_overlaps("phx_world_query_circles", circles, count, ROWS_CIRCLES, flags, offsets, hits, hit_cap, total, &DeviceQuery::discs);
+}
+int World::query_points(const float* points, int count, int flags, int32_t* body) { return query_rows<int>("phx_world_query_points", points, count, ROWS_POINTS, flags, body, -1, q_body_, &DeviceQuery::points); }
+int World::raycast(const float* rays, int count, int flags, phx_ray_hit* out) { return query_rows("phx_world_raycast", rays, count, ROWS_RAYS, flags, out, RAY_MISS, q_hits_, &DeviceQuery::rays); }
+int World::cast_boxes(const float* casts, int count, int flags, phx_shape_hit* out) { return query_rows("phx_world_cast_boxes", casts, count, ROWS_CASTS, flags, out, SHAPE_MISS, q_shape_hits_, &DeviceQuery::casts); }
+int World::cast_circles(const float* casts, int count, int flags, phx_shape_hit* out) { return query_rows("phx_world_cast_circles", casts, count, ROWS_CIRCLE_CASTS, flags, out, SHAPE_MISS, q_shape_hits_, &DeviceQuery::disc_casts); }
+int World::query_points_device(const void* d_points, int count, int flags, void* d_body) { return query_rows_device<int>("phx_world_query_points_device", d_points, count, ROWS_POINTS, flags, d_body, &DeviceQuery::points); }
+int World::raycast_device(const void* d_rays, int count, int flags, void* d_out) { return query_rows_device<phx_ray_hit>("phx_world_raycast_device", d_rays, count, ROWS_RAYS, flags, d_out, &DeviceQuery::rays); }
+int World::cast_boxes_device(const void* d_casts, int count, int flags, void* d_out) { return query_rows_device<phx_shape_hit>("phx_world_cast_boxes_device", d_casts, count, ROWS_CASTS, flags, d_out, &DeviceQuery::casts); }
+int World::cast_circles_device(const void* d_casts, int count, int flags, void* d_out) { return query_rows_device<phx_shape_hit>("phx_world_cast_circles_device", d_casts, count, ROWS_CIRCLE_CASTS, flags, d_out, &DeviceQuery::disc_casts); }
 
 int World::query_index_build()
 {
