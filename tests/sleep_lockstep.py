@@ -26,8 +26,11 @@ class Twins:
         self.slept, self.woken = [], []      # per step, the spec's decisions
 
     # ---- the spec's side ----
+    def unit_pairs(self):
+        return sleep_spec.unit_pairs(lists_of(self.b) if self.units else None)
+
     def graph(self):
-        return self.b.manifolds, sleep_spec.unit_pairs(lists_of(self.b) if self.units else None), (self.b.body_flags() if self.flags else None)
+        return self.b.manifolds, self.unit_pairs(), (self.b.body_flags() if self.flags else None)
 
     def put_to_sleep(self, slept):
         if slept:
@@ -53,10 +56,11 @@ class Twins:
 
     # ---- the step ----
     def step(self, s, dt=DT):
+        units = self.unit_pairs()      # the lists as this step's pin pass solves them: a unit that breaks in this step is still an edge in it
         self.a.Update(dt, self.cfg)
         self.b.Update(dt, self.cfg)
         bodies = self.b.bodies
-        manifolds, units, flags = self.graph()
+        manifolds, flags = self.b.manifolds, (self.b.body_flags() if self.flags else None)
         slept, woken = sleep_spec.decide(self.state, bodies["inv_mass"], bodies["inv_inertia"], bodies["velocity"]["x"], bodies["velocity"]["y"],
                                          bodies["angular_velocity"], manifolds, units, flags, self.params, dt)
         self.put_to_sleep(slept)
@@ -72,6 +76,13 @@ class Twins:
             for kind, x, y in zip(KINDS, lists_of(self.a), lists_of(self.b)):
                 assert x.tobytes() == y.tobytes(), "%s differ %s" % (kind.plural, what)
         self.same_states(what)
+
+    def same_schedules(self, what):
+        """the pin pass's schedule of the next step, the static set (the sleepers) part of it"""
+        x, y = self.a.pin_schedule(), self.b.pin_schedule()
+        assert sorted(x) == sorted(y)
+        for key in x:
+            assert np.array_equal(x[key], y[key]), "the pin schedules' %s differ %s" % (key, what)
 
     def same_states(self, what):
         b = self.b.bodies
