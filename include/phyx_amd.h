@@ -614,13 +614,18 @@ int  phx_world_get_materials(phx_world* w, phx_material* out, int32_t cap);
 int  phx_world_set_body_flags(phx_world* w, const int32_t* bodies, const uint32_t* flags, int32_t count);
 /* every body's flags, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise) */
 int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
-/* SHAPES — round bodies.  Every body has a shape {kind, hx, hy}: its kind, PHX_SHAPE_BOX (the default) or PHX_SHAPE_CIRCLE, and its
- * geom_size.  A box's size is its half extents; a circle's is {r, r}, its radius twice.  A world that never made a circle launches
- * exactly the kernels it launched before there were shapes, and one whose shape column is active while every body is a box steps bit
- * for bit like it.
+/* SHAPES — round bodies.  Every body has a shape {kind, hx, hy}: its kind, PHX_SHAPE_BOX (the default), PHX_SHAPE_CIRCLE or
+ * PHX_SHAPE_CAPSULE, and its geom_size.  A box's size is its half extents; a circle's is {r, r}, its radius twice; a capsule's is the half
+ * extents of its bounding box in the body's frame, hx > hy > 0: its radius is r = hy and its core segment runs along the body's x axis
+ * from pos - xv*a to pos + xv*a with a = hx - hy, one fp32 subtraction, formed the same way wherever it is needed.  A world that never
+ * made a circle or a capsule launches exactly the kernels it launched before there were shapes, one whose shape column is active while
+ * every body is a box steps bit for bit like it, and one that never made a capsule launches exactly the kernels of a world of boxes and
+ * circles: the capsule routines live in instantiations of their own (UpdateManifolds' third, and the queries'), picked by a bit that
+ * the first call naming a capsule sets and set_state or a load clears (a load takes the saved world's bit).
  *   - Where it acts: UpdateManifolds (ref: Collider.cpp:211-245).  In front of the separating-axis test the pair's kinds pick the routine;
  *     box/box is the reference's code.  The round routines produce at most one new point per step and hand it to the reference's
- *     MergeCollision (ref: Collider.cpp:58-92) unchanged, so warm starting, isNewlyCreated and the two-slot store work as for boxes.  The
+ *     MergeCollision (ref: Collider.cpp:58-92) unchanged, so warm starting, isNewlyCreated and the two-slot store work as for boxes (a
+ *     pair with a capsule produces up to two, below).  The
  *     normal keeps the stored convention: it points from body2 towards body1, and (p2 - p1) . n >= 0 is the penetration.  Every operation
  *     is fp32 and rounded on its own, sqrtf and / correctly rounded, dot(a, b) = a.x*b.x + a.y*b.y; tests/circle_spec.py states what
  *     follows as the same expressions and the device matches it byte for byte.
@@ -634,13 +639,43 @@ int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
  *         Otherwise e = (u - qu, v - qv), l2 = dot(e, e); no point if l2 > r*r; l = sqrtf(l2), N = xv*(e.x / l) + yv*(e.y / l).
  *         Box point = (B.pos + xv*qu) + yv*qv, circle point = C.pos - N*r.  C is body1: n = N, p1 = circle point, p2 = box point;
  *         C is body2: n = -N, p1 = box point, p2 = circle point.
+ *     Capsules (tests/capsule_spec.py states what follows as the same expressions; a capsule is the first round shape that rests on a
+ *     face, so one point is not enough).  Two building blocks, each yielding a candidate {point on the disc, point on the other shape,
+ *     N from the other shape towards the disc, depth}:
+ *       disc {c, r} against box B:  the circle/box arithmetic above with the centre c and the radius r; depth = r - l outside, and
+ *         r + pu (or r + pv) in the centre-inside branch.
+ *       disc {c, rc} against capsule K (frame xv, yv, r = K.size.y, a = K.size.x - K.size.y):  e = c - K.pos, u = dot(e, xv),
+ *         v = dot(e, yv), qu = u < -a ? -a : (u > a ? a : u), g = (u - qu, v), l2 = dot(g, g), R = r + rc.  No candidate if l2 > R*R.
+ *         l = sqrtf(l2), N = xv*(g.x / l) + yv*(g.y / l) if l > 0, else yv.  Capsule point = (K.pos + xv*qu) + N*r, disc point =
+ *         c - N*rc, depth = R - l.  The candidate is unclamped iff qu == u.
+ *     The disc's owner is body1: n = N, p1 = disc point, p2 = the other's point; it is body2: n = -N and the points change places.
+ *     Candidates per pair, in this order (A = body1 where both are capsules):
+ *       capsule / circle:  the circle's disc {pos, size.x} against the capsule.
+ *       capsule K / box B: K's end discs {pos - xv*a, r}, {pos + xv*a, r} against B; then B's corners (B.pos + xv*cx) + yv*cy for
+ *         (cx, cy) = (-h.x, -h.y), (h.x, -h.y), (-h.x, h.y), (h.x, h.y) as discs of radius 0 against K, each only if unclamped (a
+ *         corner nearest an end of the core is the end disc's business).
+ *       capsule A / capsule B: A's end discs (radius rA) against B; then B's end discs (radius rB) against A, each only if unclamped
+ *         (end against end comes once, from A's side).
+ *     Selection: the first point is the candidate of largest depth, the first in order on a tie.  The second is chosen among the
+ *     others that are distinct from the first under ContactPoint::Equals(2.0f): sqlen(p1_k - p1_first) > 4.0f AND
+ *     sqlen(p2_k - p2_first) > 4.0f; of those the one with the largest sqlen(p1_k - p1_first), the first in order on a tie; none
+ *     qualifies: no second point.  First, then second, go through MergeCollision.
+ *     What the float64 judge (tests/capsule_reference.py) found and the rule keeps: a second point that comes from an end disc lies on
+ *     that disc's circle along the contact normal; where the normal leans by theta from the side's own, that is r*(1 - cos(theta))
+ *     inside the capsule's side (second order in the lean, zero at rest on a face); and an end's centre is formed in fp32, so its
+ *     normal carries that rounding seen from the distance l.  Known limit: where the core segment itself passes through the other
+ *     core (a capsule skewering a box with both ends outside, two crossed segments) the candidates are the nearest end features and
+ *     not the minimum translation, and a point may lie on an end disc's circle inside the capsule.  That state is already a tunnelled
+ *     one; the rule stays defined and deterministic there.  tests/capsule_corpus.py has the figures.
  *   - Deliberately unchanged: UpdateGeom, IntegratePosition and the broadphase.  A circle's AABB stays the AABB of its frame square
- *     {r, r}: a conservative bound, at most sqrt(2) wider than the disc, so nothing upstream of the narrowphase knows the kind.  The
+ *     {r, r}: a conservative bound, at most sqrt(2) wider than the disc, so nothing upstream of the narrowphase knows the kind; a
+ *     capsule's is that of its frame box {hx, hy}, which contains it and is tight in the body's frame.  The
  *     dead-manifold test (no points and the AABBs apart) and the contact reports stay valid as they are.  The solver sees contact points
  *     and never the shape; pins, links, angles and sliders use body-local anchors.
  *   - Setting shapes: the rules of the edits and of set_materials.  Between steps only (PHX_ERR_STATE); checked completely before
- *     anything is queued (count >= 0, no NULL array when count > 0, every index in [0, body count), none twice, kind in {0, 1}, hx and hy
- *     finite and > 0, hy == hx for a circle; PHX_ERR_INVALID otherwise, the world unchanged); staged through pinned memory and queued on
+ *     anything is queued (count >= 0, no NULL array when count > 0, every index in [0, body count), none twice, kind in {0, 1, 2}, hx and hy
+ *     finite and > 0, hy == hx for a circle, hx > hy for a capsule (hx == hy: use PHX_SHAPE_CIRCLE); PHX_ERR_INVALID otherwise, the
+ *     world unchanged); staged through pinned memory and queued on
  *     phx_world_stream(w); before the first step it writes the host-staged records.  The call sets the body's kind and its geom_size
  *     (the record and the resident size) and recomputes the AABB as phx_world_set_poses does (ref: Geom.h:79-85): it is also the edit
  *     that resizes a box.  A sharded or communicator-attached world gets PHX_ERR_STATE.
@@ -650,20 +685,24 @@ int  phx_world_get_body_flags(phx_world* w, uint32_t* out, int32_t cap);
  *   - Inverse masses are not touched: the shape is geometry, phx_world_set_inverse_masses is the mass.  AddBody's scale for a box of
  *     half sizes sx, sy is mass = 1e-5f * sx * sy, inertia = mass * (sx*sx + sy*sy) (a quarter of the area, three times the true box
  *     inertia); the circle formula on the same scale is mass = 1e-5f * 0.785398f * r * r, inertia = mass * 1.5f * r * r
- *     (phyx_amd.World.add_circles applies it).
+ *     (phyx_amd.World.add_circles applies it); the capsule's, with a = hx - hy and r = hy, in this order: mb = 1e-5f*a*r,
+ *     mc = 1e-5f*0.785398f*r*r, mass = mb + mc, inertia = mb*(a*a + r*r) + mc*(1.5f*r*r + 3.0f*a*a + 2.546479f*a*r) (the
+ *     rectangle's term is the box formula, a -> 0 gives the circle's; phyx_amd.World.add_capsules applies it).
  *   - The other calls: add_body / add_bodies give boxes; remove_bodies / remove_outside move the kind with the kept bodies (through
- *     new[]); phx_world_set_state resets every kind to box (the sizes are in the records; a world with circles is checkpointed as
- *     set_state followed by set_shapes); phx_world_save / load and so a fork carry the kinds in HBM beside the blob's layout, as they
+ *     new[]); phx_world_set_state resets every kind to box (the sizes are in the records; a world with circles or capsules is
+ *     checkpointed as set_state followed by set_shapes); phx_world_save / load and so a fork carry the kinds in HBM beside the blob's layout, as they
  *     carry pins; phx_snapshot_export and phx_snapshot_blob_bytes of a snapshot in which a saved kind is not a box return
  *     PHX_ERR_STATE (the blob stays layout version 1).  The edits, set_inverse_masses, filters, materials, flags and contact reports
  *     leave shapes alone.  Queries: QUERIES below.
- *   - Sharded worlds carry no circles: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and phx_world_reslab
+ *   - Sharded worlds carry no circles or capsules: phx_world_set_shard (shard_count > 1), phx_world_set_comm (a communicator) and phx_world_reslab
  *     return PHX_ERR_STATE while some body is not a box.
- * The kinds are a column of one uint32 per body that exists only once some phx_world_set_shapes call named a circle (since the last
- * set_state); a call that names boxes only is the size edit and activates nothing.  Costs and the data path: DESIGN.md. */
+ * Every rule above that names circles is written once for "a shape that is not a box" and covers capsules.
+ * The kinds are a column of one uint32 per body that exists only once some phx_world_set_shapes call named a circle or a capsule (since
+ * the last set_state); a call that names boxes only is the size edit and activates nothing.  Costs and the data path: DESIGN.md. */
 #define PHX_SHAPE_BOX    0
 #define PHX_SHAPE_CIRCLE 1
-typedef struct { int32_t kind; float hx, hy; } phx_shape;   /* 12 B; box: half extents; circle: hx = radius, hy == hx */
+#define PHX_SHAPE_CAPSULE 2
+typedef struct { int32_t kind; float hx, hy; } phx_shape;   /* 12 B; box: half extents; circle: hx = radius, hy == hx; capsule: the frame box's half extents, hx > hy = radius */
 int  phx_world_set_shapes(phx_world* w, const int32_t* bodies, const phx_shape* shapes, int32_t count);
 /* every body's {kind, geom_size.x, geom_size.y}, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise); a world that
  * never set a shape reports boxes */
@@ -727,6 +766,22 @@ int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
  *     Oriented-box queries and box casts see a circle as its frame square {r, r} in the body's frame: both are conservative (they never miss a disc and never report a later t) and consistent with each other, the
  *     two halves of "is this slot free, how far can I drop"; exact discs inside these two are a later change (their bytes are pinned).
  *     A round query shape, exact against boxes and discs alike, is next:
+ *   - Capsules (SHAPES above; r = geom_size.y, a = geom_size.x - geom_size.y; tests/capsule_spec.py states these as the same expressions).
+ *     Every rule keeps the AABB conjunct the box and the circle have, so pruning can never change a result; the AABB query is
+ *     unchanged.  Point p in capsule b iff p is inside b's AABB (closed) AND, with u, v the point in the frame (as for a box) and
+ *     qu = (u < -a ? -a : (u > a ? a : u)):  (u-qu)*(u-qu) + v*v <= r*r.  A ray hits capsule b iff b is a candidate and, in the frame
+ *     (o', d' as in the ray rule), some part of three passes, tested in this order: 0 the box lo = (-a, -r), hi = (a, r) by the two-axis
+ *     slab test; 1 and 2 the discs of radius r at (-a, 0) and (a, 0) by the ray/disc rule with rx = o'.x - centre.x, ry = o'.y and
+ *     direction d'.  Each part passes by its own final condition; tin is the smallest passing tin, the first part on a tie; t, point and
+ *     the start-inside normal (0, 0) as for the other shapes.  The box part's normal is yv, negated when o'.y + tin*d'.y < 0 (its x
+ *     faces are interior: the face is chosen by where the point is, as in the circle cast); a disc part's is the frame normal
+ *     (nx / r, ny / r) turned into the world, normal = (xv.x*nx' + yv.x*ny', xv.y*nx' + yv.y*ny').
+ *     A query circle {c, r} overlaps capsule b iff the AABB conjunct holds and, with R = r + rb (rb = geom_size.y), u, v of e = c - pos
+ *     and qu as above: (u-qu)*(u-qu) + v*v <= R*R.  A circle cast against a capsule body is the ray/capsule rule with origin c and
+ *     R = r + rb wherever that rule has the radius, the normals' divisor included.  Oriented-box queries and box casts see a capsule as
+ *     its frame box {hx, hy}: conservative, and consistent with each other, exactly as they see a circle as its frame square; their
+ *     bytes for worlds without capsules do not move.  (Held to a float64 judge that works by signed distances,
+ *     tests/capsule_reference.py.)
  *   - Query circle {c, r} (phx_world_query_circles; tests/round_query_spec.py states what follows as the same expressions): exact
  *     against box bodies and circle bodies alike; rb = geom_size.x of a circle body.  The circle overlaps body b (closed) iff
  *       a.min.x - r <= c.x && a.max.x + r >= c.x && a.min.y - r <= c.y && a.max.y + r >= c.y     (the oriented box's AABB conjunct with

@@ -77,7 +77,7 @@ FIELD_FORCE = 1                                                # PHX_FIELD_FORCE
 UNIT_KINDS = ("pin", "link", "angle", "slider")      # PHX_UNIT_PIN ... PHX_UNIT_SLIDER
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
-SHAPE_BOX, SHAPE_CIRCLE = 0, 1            # PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE (phx_shape.kind)
+SHAPE_BOX, SHAPE_CIRCLE, SHAPE_CAPSULE = 0, 1, 2            # PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE, PHX_SHAPE_CAPSULE (phx_shape.kind)
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
 
 
@@ -120,6 +120,21 @@ def circle_inverse_masses(r):
     with np.errstate(over="ignore", divide="ignore"):
         mass = f(1e-5) * f(0.785398) * r * r
         inertia = mass * f(1.5) * r * r
+        return np.stack([f(1.0) / mass, f(1.0) / inertia], axis=1).astype(np.float32)
+
+
+def capsule_inverse_masses(hx, hy):
+    """(K, 2) float32 {invMass, invInertia} of capsules of frame half extents hx > hy on AddBody's scale (include/phyx_amd.h SHAPES), with
+    a = hx - hy and r = hy: mb = 1e-5f*a*r, mc = 1e-5f*0.785398f*r*r, mass = mb + mc, inertia = mb*(a*a + r*r) + mc*(1.5f*r*r + 3.0f*a*a +
+    2.546479f*a*r), every operation a float32 one, left to right.  The rectangle's term is the box formula; a -> 0 gives the circle's."""
+    f = np.float32
+    hx, hy = np.broadcast_arrays(np.atleast_1d(np.asarray(hx, dtype=f)), np.atleast_1d(np.asarray(hy, dtype=f)))
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        a, r = hx - hy, hy
+        mb = f(1e-5) * a * r
+        mc = f(1e-5) * f(0.785398) * r * r
+        mass = mb + mc
+        inertia = mb * (a * a + r * r) + mc * (f(1.5) * r * r + f(3.0) * a * a + f(2.546479) * a * r)
         return np.stack([f(1.0) / mass, f(1.0) / inertia], axis=1).astype(np.float32)
 
 
@@ -1413,10 +1428,11 @@ class World:
     # ---- shapes (include/phyx_amd.h SHAPES; the specification: tests/circle_spec.py) ----
     def set_shapes(self, bodies, kind=SHAPE_BOX, hx=None, hy=None):
         """Give the listed bodies (each at most once) the shape {kind, hx, hy}: each a scalar for all of them or one value per body.
-        kind is SHAPE_BOX (hx, hy: half extents) or SHAPE_CIRCLE (hx: the radius; hy may be left out and must equal hx otherwise).
+        kind is SHAPE_BOX (hx, hy: half extents), SHAPE_CIRCLE (hx: the radius; hy may be left out and must equal hx otherwise) or
+        SHAPE_CAPSULE (hx > hy: the half extents of its frame box; the radius is hy, the core segment runs hx - hy either way along x).
         The body's geom_size becomes (hx, hy) and its AABB is recomputed as set_poses recomputes it; the inverse masses stay
         (set_inverse_masses; circle_inverse_masses has the circle formula).  The library rejects any other kind, sizes that are not
-        finite and positive and a circle whose hy differs from hx (PhxError), the world unchanged."""
+        finite and positive, a circle whose hy differs from hx and a capsule whose hx is not above hy (PhxError), the world unchanged."""
         idx = self._indices(bodies, "set_shapes")
         if hx is None:
             raise ValueError("set_shapes: hx (the half extent on x, or the radius) is required")
@@ -1444,6 +1460,25 @@ class World:
         if len(idx):
             self.set_shapes(idx, SHAPE_CIRCLE, s[:, 3])
             self.set_inverse_masses(idx, circle_inverse_masses(s[:, 3]))
+        return first
+
+    def add_capsules(self, spawn):
+        """Append capsules: spawn is a (K, 5) float array {px, py, angle, hx, hy}, hx > hy (the frame box's half extents; the radius is
+        hy).  add_bodies with those half extents, then set_shapes of the new bodies to SHAPE_CAPSULE, then set_inverse_masses with
+        capsule_inverse_masses(hx, hy).  Returns the first new index."""
+        a = np.asarray(spawn)
+        if a.dtype.kind != "f":
+            raise TypeError("add_capsules: spawn must be a float array, got %s" % (a.dtype,))
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise ValueError("add_capsules: spawn must have shape (K, 5) {px, py, angle, hx, hy}, got %s" % (a.shape,))
+        s = np.ascontiguousarray(a, dtype=np.float32)
+        if not (s[:, 3] > s[:, 4]).all():
+            raise ValueError("add_capsules: hx must be above hy (a capsule with hx == hy is a circle: add_circles)")
+        idx = self.add_bodies(s)
+        first = int(idx[0]) if len(idx) else self.counts()[0]
+        if len(idx):
+            self.set_shapes(idx, SHAPE_CAPSULE, s[:, 3], s[:, 4])
+            self.set_inverse_masses(idx, capsule_inverse_masses(s[:, 3], s[:, 4]))
         return first
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----

@@ -32,6 +32,7 @@ struct WorldBodies {
     float2* size;       // geom.size
     const struct SleepCell* sleep;      // the queries only (query_kernels.h q_static): the sleep column (sleep.h), null while sleeping is off and in every other view
     const uint32_t* kinds;              // the queries only (query_kernels.h q_circle): the shape column (world_kernels.h ShapeColumn), null while no body is a circle and in every other view
+    uint32_t capsules;                  // the queries only, read by the host alone: a kind may be PHX_SHAPE_CAPSULE, which picks the kernels' capsule instantiations (query.hip)
 };
 
 // IntegrateVelocity (ref: World.cpp:39-55) of one body: its vel granule after `dt` under `accel` = {acceleration.x, .y,

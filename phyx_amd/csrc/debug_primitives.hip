@@ -143,14 +143,16 @@ int phx_debug_update_manifold(const phx_rigid_body* b1, int32_t kind1, const phx
 {
     using namespace phx;
     PHX_REQUIRE(b1 && b2 && manifold && pts, "phx_debug_update_manifold: null argument");
-    PHX_REQUIRE((kind1 == PHX_SHAPE_BOX || kind1 == PHX_SHAPE_CIRCLE) && (kind2 == PHX_SHAPE_BOX || kind2 == PHX_SHAPE_CIRCLE), "phx_debug_update_manifold: a kind is 0 or 1");
+    PHX_REQUIRE(kind1 >= PHX_SHAPE_BOX && kind1 <= PHX_SHAPE_CAPSULE && kind2 >= PHX_SHAPE_BOX && kind2 <= PHX_SHAPE_CAPSULE, "phx_debug_update_manifold: a kind is 0, 1 or 2");
     PHX_REQUIRE(manifold->point_count >= 0 && manifold->point_count <= 2, "phx_debug_update_manifold: point_count is 0 .. 2");
     auto body = [](const phx_rigid_body& b, int32_t kind) {
         NpBody n;
         n.pos = v2(b.pos); n.xv = v2(b.xvector); n.yv = v2(b.yvector); n.size = v2(b.geom_size); n.kind = (unsigned)kind;
         return n;
     };
-    (void)update_manifold(*manifold, body(*b1, kind1), body(*b2, kind2), pts);
+    // (the instantiation the world would launch: the capsule one only for a pair that holds a capsule)
+    if (kind1 == PHX_SHAPE_CAPSULE || kind2 == PHX_SHAPE_CAPSULE) (void)update_manifold<true>(*manifold, body(*b1, kind1), body(*b2, kind2), pts);
+    else (void)update_manifold<false>(*manifold, body(*b1, kind1), body(*b2, kind2), pts);
     return PHX_OK;
 }
 

@@ -5,7 +5,7 @@
 // {pos, xVector, yVector, size} here (the reference's Geom keeps a copy of the frame, refreshed by UpdateGeom,
 // RigidBody.h:38-42: the same values).  The functions are
 // plain IEEE float arithmetic (no libm beyond fabsf, and the correctly rounded sqrtf of the round pairs) so the host loop and a HIP
-// kernel that call them produce identical bits under -ffp-contract=off.  Round bodies (circle/circle, circle/box) have no counterpart
+// kernel that call them produce identical bits under -ffp-contract=off.  Round bodies (circle/circle, circle/box, the capsule pairs) have no counterpart
 // in the reference: their rule is include/phyx_amd.h SHAPES.
 #pragma once
 
@@ -25,7 +25,8 @@ __host__ __device__ __attribute__((always_inline)) inline float sqlen(V2 a) { re
 __host__ __device__ __attribute__((always_inline)) inline V2 perp(V2 a) { return v2(-a.y, a.x); }                            // ref: Vector2.h GetPerpendicular
 __host__ __device__ __attribute__((always_inline)) inline phx_vec2 pv(V2 a) { phx_vec2 r; r.x = a.x; r.y = a.y; return r; }
 
-// what the narrowphase reads of a body (`kind`: PHX_SHAPE_BOX or PHX_SHAPE_CIRCLE, include/phyx_amd.h SHAPES; a circle's radius is size.x)
+// what the narrowphase reads of a body (`kind`: PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE or PHX_SHAPE_CAPSULE, include/phyx_amd.h SHAPES; a circle's radius
+// is size.x, a capsule's size.y with the core segment size.x - size.y either way along xv)
 struct NpBody { V2 pos, xv, yv, size; unsigned kind; };
 
 // ref: Geom.h:79-85 RecomputeAABB: {min.x, min.y, max.x, max.y}
@@ -279,10 +280,135 @@ __host__ __device__ __attribute__((always_inline)) inline void circle_box_contac
     else              merge_point(pts, count, on_box, on_circle, -N, b1, b2);
 }
 
+// ---- capsules (include/phyx_amd.h SHAPES; tests/capsule_spec.py states what follows as the same expressions) -----------------------
+// A capsule is the segment pos -+ xv*a, a = size.x - size.y, with the radius r = size.y.  A pair with a capsule yields up to six
+// candidates, each a disc (an end of a capsule, a circle, a box's corner as a disc of radius 0) against the other shape, and up to two
+// of them are merged.  A candidate is kept in the manifold's order: p1 on body1, p2 on body2, n from body2 towards body1.
+struct Cand { V2 p1, p2, n; float depth; bool ok; };
+__host__ __device__ __attribute__((always_inline)) inline Cand cand_none()
+{
+    Cand c;
+    c.p1 = c.p2 = c.n = v2(0.f, 0.f); c.depth = 0.f; c.ok = false;
+    return c;
+}
+// `disc_first`: the disc belongs to body1; N points from the other shape towards the disc
+__host__ __device__ __attribute__((always_inline)) inline Cand cand_make(V2 on_disc, V2 on_other, V2 N, float depth, bool disc_first)
+{
+    Cand c;
+    c.p1 = disc_first ? on_disc : on_other; c.p2 = disc_first ? on_other : on_disc; c.n = disc_first ? N : -N;
+    c.depth = depth; c.ok = true;
+    return c;
+}
+__host__ __device__ __attribute__((always_inline)) inline float capsule_half(const NpBody& k) { return k.size.x - k.size.y; }
+
+// the disc {cpos, r} against box b: circle_box_contact's arithmetic, with the depth
+__host__ __device__ __attribute__((always_inline)) inline Cand disc_box_cand(V2 cpos, float r, const NpBody& b, bool disc_first)
+{
+    const V2 xv = b.xv, yv = b.yv, h = b.size;
+    const V2 rel = cpos - b.pos;
+    const float u = dot(rel, xv), v = dot(rel, yv);
+    float qu = u < -h.x ? -h.x : (u > h.x ? h.x : u);
+    float qv = v < -h.y ? -h.y : (v > h.y ? h.y : v);
+    V2 N;
+    float depth;
+    if (qu == u && qv == v) {
+        const float pu = h.x - fabsf(u), pv_ = h.y - fabsf(v);
+        if (pu <= pv_) { N = u < 0.0f ? -xv : xv; qu = u < 0.0f ? -h.x : h.x; depth = r + pu; }
+        else           { N = v < 0.0f ? -yv : yv; qv = v < 0.0f ? -h.y : h.y; depth = r + pv_; }
+    } else {
+        const V2 e = v2(u - qu, v - qv);
+        const float l2 = dot(e, e);
+        if (l2 > r * r) return cand_none();
+        const float l = sqrtf(l2);
+        N = xv * (e.x / l) + yv * (e.y / l);
+        depth = r - l;
+    }
+    const V2 on_box = (b.pos + xv * qu) + yv * qv;
+    return cand_make(cpos - N * r, on_box, N, depth, disc_first);
+}
+
+// the disc {c, rc} against capsule k; `unclamped`: the nearest point of the core segment is not an end (qu == u)
+__host__ __device__ __attribute__((always_inline)) inline Cand disc_capsule_cand(V2 c, float rc, const NpBody& k, bool disc_first, bool& unclamped)
+{
+    const V2 xv = k.xv, yv = k.yv;
+    const float r = k.size.y, a = capsule_half(k);
+    const V2 e = c - k.pos;
+    const float u = dot(e, xv), v = dot(e, yv);
+    const float qu = u < -a ? -a : (u > a ? a : u);
+    const V2 g = v2(u - qu, v);
+    const float l2 = dot(g, g), R = r + rc;
+    unclamped = qu == u;
+    if (l2 > R * R) return cand_none();
+    const float l = sqrtf(l2);
+    const V2 N = l > 0.0f ? xv * (g.x / l) + yv * (g.y / l) : yv;
+    const V2 on_capsule = (k.pos + xv * qu) + N * r;
+    return cand_make(c - N * rc, on_capsule, N, R - l, disc_first);
+}
+
+// The selection: the first point is the deepest candidate (the first in order on a tie); the second is, among the others that are
+// distinct from the first under ContactPoint::Equals(2.0f) (both points more than 2 apart), the one whose p1 is farthest from the
+// first's (the first in order on a tie).  A running best over named candidates: no array under a run-time index (Pts4).
+__host__ __device__ __attribute__((always_inline)) inline void capsule_select(const Cand& c0, const Cand& c1, const Cand& c2, const Cand& c3, const Cand& c4,
+                                                                              const Cand& c5, Pts4& pts, int& count, const NpBody& b1, const NpBody& b2)
+{
+    Cand first = cand_none();
+    int fi = -1;
+    auto deeper = [&](const Cand& c, int i) { if (c.ok && (fi < 0 || c.depth > first.depth)) { first = c; fi = i; } };
+    deeper(c0, 0); deeper(c1, 1); deeper(c2, 2); deeper(c3, 3); deeper(c4, 4); deeper(c5, 5);
+    if (fi < 0) return;
+    Cand second = cand_none();
+    int si = -1;
+    float sep = 0.0f;
+    auto farther = [&](const Cand& c, int i) {
+        if (!c.ok || i == fi) return;
+        const float s1 = sqlen(c.p1 - first.p1), s2 = sqlen(c.p2 - first.p2);
+        if (!(s1 > 2.0f * 2.0f && s2 > 2.0f * 2.0f)) return;
+        if (si < 0 || s1 > sep) { second = c; sep = s1; si = i; }
+    };
+    farther(c0, 0); farther(c1, 1); farther(c2, 2); farther(c3, 3); farther(c4, 4); farther(c5, 5);
+    merge_point(pts, count, first.p1, first.p2, first.n, b1, b2);
+    if (si >= 0) merge_point(pts, count, second.p1, second.p2, second.n, b1, b2);
+}
+
+// a pair with a capsule (`b1`, `b2` in the manifold's order)
+__host__ __device__ __attribute__((always_inline)) inline void capsule_contact(const NpBody& b1, const NpBody& b2, Pts4& pts, int& count)
+{
+    const unsigned CAPSULE = (unsigned)PHX_SHAPE_CAPSULE, CIRCLE = (unsigned)PHX_SHAPE_CIRCLE;
+    Cand c0 = cand_none(), c1 = c0, c2 = c0, c3 = c0, c4 = c0, c5 = c0;
+    bool free_ = false;
+    if (b1.kind == CAPSULE && b2.kind == CAPSULE) {                     // A's ends against B, then B's ends against A where they meet its side
+        const float a1 = capsule_half(b1), a2 = capsule_half(b2);
+        c0 = disc_capsule_cand(b1.pos - b1.xv * a1, b1.size.y, b2, true, free_);
+        c1 = disc_capsule_cand(b1.pos + b1.xv * a1, b1.size.y, b2, true, free_);
+        c2 = disc_capsule_cand(b2.pos - b2.xv * a2, b2.size.y, b1, false, free_); c2.ok = c2.ok && free_;
+        c3 = disc_capsule_cand(b2.pos + b2.xv * a2, b2.size.y, b1, false, free_); c3.ok = c3.ok && free_;
+    } else if (b1.kind == CIRCLE || b2.kind == CIRCLE) {                // the circle's disc against the capsule
+        const bool circle_first = b1.kind == CIRCLE;
+        const NpBody& c = circle_first ? b1 : b2;
+        const NpBody& k = circle_first ? b2 : b1;
+        c0 = disc_capsule_cand(c.pos, c.size.x, k, circle_first, free_);
+    } else {                                                            // the capsule's ends against the box, then the box's corners against the capsule's side
+        const bool capsule_first = b1.kind == CAPSULE;
+        const NpBody& k = capsule_first ? b1 : b2;
+        const NpBody& b = capsule_first ? b2 : b1;
+        const float a = capsule_half(k);
+        const V2 h = b.size;
+        c0 = disc_box_cand(k.pos - k.xv * a, k.size.y, b, capsule_first);
+        c1 = disc_box_cand(k.pos + k.xv * a, k.size.y, b, capsule_first);
+        c2 = disc_capsule_cand((b.pos + b.xv * -h.x) + b.yv * -h.y, 0.0f, k, !capsule_first, free_); c2.ok = c2.ok && free_;
+        c3 = disc_capsule_cand((b.pos + b.xv * h.x) + b.yv * -h.y, 0.0f, k, !capsule_first, free_); c3.ok = c3.ok && free_;
+        c4 = disc_capsule_cand((b.pos + b.xv * -h.x) + b.yv * h.y, 0.0f, k, !capsule_first, free_); c4.ok = c4.ok && free_;
+        c5 = disc_capsule_cand((b.pos + b.xv * h.x) + b.yv * h.y, 0.0f, k, !capsule_first, free_); c5.ok = c5.ok && free_;
+    }
+    capsule_select(c0, c1, c2, c3, c4, c5, pts, count, b1, b2);
+}
+
 // ref: Collider.cpp:211-245.  Returns true if a third merged point had to be dropped: the reference
 // would write it past the manifold's two slots (only an assert guards it).
 // The pair's kinds pick the routine in front of least_penetration_axis; a caller whose kinds are the constant PHX_SHAPE_BOX (a world
-// without a shape column) compiles to the box/box code alone.
+// without a shape column) compiles to the box/box code alone.  CAPSULES: a kind may be PHX_SHAPE_CAPSULE (a world that made one);
+// without it every kind that is not a box is a circle and the capsule routines are not compiled in.
+template <bool CAPSULES = false>
 __host__ __device__ __attribute__((always_inline)) inline bool update_manifold(phx_manifold& m, const NpBody& b1, const NpBody& b2, phx_contact_point* pts)
 {
     Pts4 np;
@@ -295,7 +421,8 @@ __host__ __device__ __attribute__((always_inline)) inline bool update_manifold(p
     if ((b1.kind | b2.kind) == 0u) {
         V2 axis;
         if (least_penetration_axis(b1, b2, axis)) generate_contacts(b1, b2, np, count, axis);
-    } else if (b1.kind != 0u && b2.kind != 0u) circle_circle_contact(b1, b2, np, count);
+    } else if (CAPSULES && (b1.kind == (unsigned)PHX_SHAPE_CAPSULE || b2.kind == (unsigned)PHX_SHAPE_CAPSULE)) capsule_contact(b1, b2, np, count);
+    else if (b1.kind != 0u && b2.kind != 0u) circle_circle_contact(b1, b2, np, count);
     else if (b1.kind != 0u) circle_box_contact(b1, b2, true, np, count, b1, b2);
     else circle_box_contact(b2, b1, false, np, count, b1, b2);
     m.point_count = 0;

@@ -60,6 +60,13 @@ private:
     template <int SHAPE>
     int index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                    int64_t* total, Readback& rb, hipStream_t s);
+    // (C: the kernels' capsule instantiations, for circle queries of a world in which a capsule was named)
+    template <int SHAPE, bool C>
+    int scan_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
+                     int64_t* total, Readback& rb, hipStream_t s);
+    template <int SHAPE, bool C>
+    int index_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
+                      int64_t* total, Readback& rb, hipStream_t s);
     template <int SHAPE, class Hit>
     int closest(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, Hit* d_out, hipStream_t s);
     // the current index over n bodies, as the kernels take it

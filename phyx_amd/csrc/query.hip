@@ -5,6 +5,7 @@
 #include "device_radix.h"
 
 #include <algorithm>
+#include <type_traits>
 
 static_assert(sizeof(phx_ray_hit) == 24, "phx_ray_hit is 24 bytes (include/phyx_amd.h)");
 static_assert(sizeof(phx_shape_hit) == 16, "phx_shape_hit is 16 bytes (include/phyx_amd.h)");
@@ -20,6 +21,15 @@ template <class Launch>
 static void scan_in_chunks(int n, int count, Launch launch)
 {
     for (int q0 = 0; q0 < count; q0 += Q_MAX_TILES * Q_TILE) launch(q0, dim3(stream_grid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)));
+}
+
+// f(std::bool_constant<CAPS>): the kernels' capsule instantiations for a world in which a capsule was named, the plain ones otherwise
+// (query_kernels.h q_kind).  A kernel that never reads the kinds (AABBs, oriented boxes, box casts) has the plain one alone.
+template <class F>
+static void q_caps(const WorldBodies& w, F f)
+{
+    if (w.capsules) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 int DeviceQuery::configure_from_env()
@@ -84,12 +94,17 @@ int DeviceQuery::points(const WorldBodies& w, int n, unsigned long long epoch, c
     unsigned* out = reinterpret_cast<unsigned*>(d_body);
     if (n == 0 || choose(QUERY_POINTS, count) == PATH_SCAN) {
         PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), 0xFFFFFFFFu, (size_t)count, s));      // (-1: no body)
-        if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL(k_qscan_points, grid, dim3(256), 0, s, w, n, d_pts, count, q0, flags, out); });
+        if (n) q_caps(w, [&](auto caps) {
+            constexpr bool C = decltype(caps)::value;
+            scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_points<C>), grid, dim3(256), 0, s, w, n, d_pts, count, q0, flags, out); });
+        });
     } else {
         PHX_TRY(ensure_index(w, n, epoch, s));
         const QTree t = tree(n);
-        hipLaunchKernelGGL((k_qtree<QK_POINT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_pts, count, flags, out, (unsigned long long*)nullptr,
-                           (const unsigned*)nullptr, (int*)nullptr);
+        q_caps(w, [&](auto caps) {
+            hipLaunchKernelGGL((k_qtree<QK_POINT, decltype(caps)::value>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_pts, count, flags, out, (unsigned long long*)nullptr,
+                               (const unsigned*)nullptr, (int*)nullptr);
+        });
     }
     PHX_HIP(hipGetLastError());
     return PHX_OK;
@@ -105,17 +120,21 @@ int DeviceQuery::closest(const WorldBodies& w, int n, unsigned long long epoch, 
     PHX_TRY(ray_keys_.reserve((size_t)count));
     constexpr Kind kind = SHAPE == QSHAPE_BOX ? QUERY_CASTS : SHAPE == QSHAPE_DISC ? QUERY_DISC_CASTS : QUERY_RAYS;
     constexpr int tree_kind = SHAPE == QSHAPE_BOX ? QK_CAST : SHAPE == QSHAPE_DISC ? QK_DISC_CAST : QK_RAY;
-    if (n == 0 || choose(kind, count) == PATH_SCAN) {
-        hipLaunchKernelGGL(k_qfill_u64, dim3(stream_grid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
-        if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_rays<SHAPE>), grid, dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p); });
-    } else {
-        PHX_TRY(ensure_index(w, n, epoch, s));
-        const QTree t = tree(n);
-        hipLaunchKernelGGL((k_qtree<tree_kind>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
-                           (const unsigned*)nullptr, (int*)nullptr);
-    }
-    if constexpr (SHAPE != QSHAPE_NONE) hipLaunchKernelGGL((k_qcast_finish<SHAPE>), dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
-    else hipLaunchKernelGGL(k_qray_finish, dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    const bool scan = n == 0 || choose(kind, count) == PATH_SCAN;
+    if (!scan) PHX_TRY(ensure_index(w, n, epoch, s));
+    q_caps(w, [&](auto caps) {
+        constexpr bool C = SHAPE != QSHAPE_BOX && decltype(caps)::value;      // (a box cast sees every body as its frame box)
+        if (scan) {
+            hipLaunchKernelGGL(k_qfill_u64, dim3(stream_grid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
+            if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_rays<SHAPE, C>), grid, dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p); });
+        } else {
+            const QTree t = tree(n);
+            hipLaunchKernelGGL((k_qtree<tree_kind, C>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
+                               (const unsigned*)nullptr, (int*)nullptr);
+        }
+        if constexpr (SHAPE != QSHAPE_NONE) hipLaunchKernelGGL((k_qcast_finish<SHAPE, C>), dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+        else hipLaunchKernelGGL((k_qray_finish<C>), dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    });
     PHX_HIP(hipGetLastError());
     return PHX_OK;
 }
@@ -169,6 +188,14 @@ template <int SHAPE>
 int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                            int64_t* total, Readback& rb, hipStream_t s)
 {
+    if (SHAPE == QSHAPE_DISC && w.capsules) return scan_aabb_as<SHAPE, SHAPE == QSHAPE_DISC>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return scan_aabb_as<SHAPE, false>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+}
+
+template <int SHAPE, bool C>
+int DeviceQuery::scan_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
+                              int64_t* total, Readback& rb, hipStream_t s)
+{
     const int bblocks = div_up(n, 256);
     // queries per chunk: the chunk's (query, body block) table stays within 2^26 words and one launch's tiles (PHX_QUERY_SCAN_CHUNK
     // lowers it: tests reach the chunked form on small worlds)
@@ -178,7 +205,7 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
     PHX_HIP(hipMemsetAsync(list_.counts(), 0, (size_t)count * sizeof(unsigned), s));
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0);
-        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, SHAPE>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, list_.counts(), 0u, (int*)nullptr);
+        hipLaunchKernelGGL((k_qscan_aabb<QS_COUNT, SHAPE, C>), dim3(bblocks, div_up(nq, Q_TILE)), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, list_.counts(), 0u, (int*)nullptr);
     }
     PHX_HIP(hipGetLastError());
     PHX_TRY(list_.settle(OVERLAP_NAME[SHAPE], "hits", count, offsets, hit_cap, total, rb, s));
@@ -187,9 +214,9 @@ int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, in
     for (int q0 = 0; q0 < count; q0 += chunk) {
         const int nq = std::min(chunk, count - q0), tiles = div_up(nq, Q_TILE);
         if (count > chunk)                                                  // (the table holds the last chunk's counts: count this one again)
-            hipLaunchKernelGGL((k_qscan_aabb<QS_RECOUNT, SHAPE>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr, 0u, (int*)nullptr);
+            hipLaunchKernelGGL((k_qscan_aabb<QS_RECOUNT, SHAPE, C>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr, 0u, (int*)nullptr);
         PHX_TRY(device_exclusive_scan(table_.p, nq * bblocks, nullptr, scan_, s));
-        hipLaunchKernelGGL((k_qscan_aabb<QS_FILL, SHAPE>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr,
+        hipLaunchKernelGGL((k_qscan_aabb<QS_FILL, SHAPE, C>), dim3(bblocks, tiles), dim3(256), 0, s, w, n, d_boxes, count, q0, flags, bblocks, table_.p, (unsigned*)nullptr,
                            (unsigned)offsets[q0], hits_.p);
     }
     PHX_HIP(hipGetLastError());
@@ -200,16 +227,24 @@ template <int SHAPE>
 int DeviceQuery::index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                             int64_t* total, Readback& rb, hipStream_t s)
 {
+    if (SHAPE == QSHAPE_DISC && w.capsules) return index_aabb_as<SHAPE, SHAPE == QSHAPE_DISC>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return index_aabb_as<SHAPE, false>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+}
+
+template <int SHAPE, bool C>
+int DeviceQuery::index_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
+                               int64_t* total, Readback& rb, hipStream_t s)
+{
     const QTree t = tree(n);
     PHX_TRY(list_.room_with_segments(count));
-    hipLaunchKernelGGL((k_qtree<SHAPE == QSHAPE_BOX ? QK_BOX_COUNT : SHAPE == QSHAPE_DISC ? QK_DISC_COUNT : QK_AABB_COUNT>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, list_.counts(), (unsigned long long*)nullptr,
+    hipLaunchKernelGGL((k_qtree<SHAPE == QSHAPE_BOX ? QK_BOX_COUNT : SHAPE == QSHAPE_DISC ? QK_DISC_COUNT : QK_AABB_COUNT, C>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, list_.counts(), (unsigned long long*)nullptr,
                        (const unsigned*)nullptr, (int*)nullptr);
     PHX_HIP(hipGetLastError());
     PHX_TRY(list_.settle(OVERLAP_NAME[SHAPE], "hits", count, offsets, hit_cap, total, rb, s));
     if (*total == 0) return PHX_OK;
     PHX_TRY(hits_.reserve((size_t)*total));
     PHX_TRY(list_.segments_from_counts(count, scan_, s));
-    hipLaunchKernelGGL((k_qtree<SHAPE == QSHAPE_BOX ? QK_BOX_FILL : SHAPE == QSHAPE_DISC ? QK_DISC_FILL : QK_AABB_FILL>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
+    hipLaunchKernelGGL((k_qtree<SHAPE == QSHAPE_BOX ? QK_BOX_FILL : SHAPE == QSHAPE_DISC ? QK_DISC_FILL : QK_AABB_FILL, C>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_boxes, count, flags, (unsigned*)nullptr, (unsigned long long*)nullptr,
                        list_.segments(), hits_.p);
     // ascending order: short segments in LDS, long ones by the radix sort (31-bit keys: the body indices)
     hipLaunchKernelGGL(k_qsort_segments, dim3(segment_grid(count)), dim3(256), 0, s, list_.segments(), (const unsigned*)list_.counts(), count, hits_.p);

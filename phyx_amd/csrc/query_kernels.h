@@ -1,8 +1,8 @@
 // query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box or disc, the closest
 // ray hit, oriented-box overlap and the closest box-cast hit, circle overlap and the closest circle-cast hit over the resident arrays
 // (body_view.h).  The predicates below are the header's formulas one for one, each operation rounded on its own (the library is
-// compiled with -ffp-contract=off); tests/query_spec.py, tests/shape_query_spec.py and tests/round_query_spec.py state them again in
-// numpy.
+// compiled with -ffp-contract=off); tests/query_spec.py, tests/shape_query_spec.py, tests/round_query_spec.py and tests/capsule_spec.py
+// state them again in numpy.
 //
 // Two paths give byte-identical results:
 //   scan   bodies in lanes, a tile of Q_TILE queries in LDS, one coalesced pass over the resident arrays per tile; points and rays
@@ -63,6 +63,26 @@ __device__ __forceinline__ bool q_point_in_box(float4 a, float4 m, float4 f, flo
 // size.x; the AABB conjunct and the candidate test are the box's.  Oriented boxes and box casts see a circle as its frame square; query
 // circles and circle casts (the round predicates below) see the disc.
 __device__ __forceinline__ bool q_circle(const uint32_t* __restrict__ kinds, int i) { return kinds && kinds[i] != (uint32_t)PHX_SHAPE_BOX; }
+// Capsules: every kernel that reads the kinds has a second instantiation, CAPS, which a world launches once some call has named a capsule
+// (WorldBodies::capsules; query.hip q_caps).  Without it a kind is 0 or 1, q_circle's answer, and no capsule predicate is compiled in: a
+// world of boxes and circles runs the code it always ran.  A capsule's core segment runs along the frame's x from -a to a, a = h.x - h.y,
+// its radius is h.y.  Oriented boxes and box casts see a capsule as its frame box {h.x, h.y}, as they see a circle as its frame square.
+template <bool CAPS>
+__device__ __forceinline__ unsigned q_kind(const uint32_t* __restrict__ kinds, int i)
+{
+    if (CAPS) return kinds ? kinds[i] : (unsigned)PHX_SHAPE_BOX;
+    return q_circle(kinds, i) ? 1u : 0u;
+}
+__device__ __forceinline__ float q_clamp(float u, float a) { return u < -a ? -a : (u > a ? a : u); }
+
+__device__ __forceinline__ bool q_point_in_capsule(float4 a, float4 m, float4 f, float2 h, float px, float py)
+{
+    if (!(a.x <= px && a.z >= px && a.y <= py && a.w >= py)) return false;
+    const float dx = px - m.z, dy = py - m.w;
+    const float u = dx * f.x + dy * f.y, v = dx * f.z + dy * f.w;
+    const float ha = h.x - h.y, gx = u - q_clamp(u, ha);
+    return gx * gx + v * v <= h.y * h.y;
+}
 
 __device__ __forceinline__ bool q_point_in_circle(float4 a, float4 m, float r, float px, float py)
 {
@@ -71,9 +91,11 @@ __device__ __forceinline__ bool q_point_in_circle(float4 a, float4 m, float r, f
     return dx * dx + dy * dy <= r * r;
 }
 
-__device__ __forceinline__ bool q_point_in_body(bool circle, float4 a, float4 m, float4 f, float2 h, float px, float py)
+template <bool CAPS>
+__device__ __forceinline__ bool q_point_in_body(unsigned kind, float4 a, float4 m, float4 f, float2 h, float px, float py)
 {
-    return circle ? q_point_in_circle(a, m, h.x, px, py) : q_point_in_box(a, m, f, h, px, py);
+    if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) return q_point_in_capsule(a, m, f, h, px, py);
+    return kind != 0u ? q_point_in_circle(a, m, h.x, px, py) : q_point_in_box(a, m, f, h, px, py);
 }
 
 // one axis's slab: false when it is empty
@@ -143,10 +165,62 @@ __device__ __forceinline__ bool q_ray_circle(const QRay& r, float4 m, float rad,
     return q_ray_disc(r.ox - m.z, r.oy - m.w, r.dx, r.dy, r.max_t, rad, tin, nx, ny);
 }
 
-// the ray against body b's own shape (after the candidate test): tin alone
-__device__ __forceinline__ bool q_ray_body(bool circle, const QRay& r, float4 m, float4 f, float2 h, float& tin)
+// part: 0 the wide box, 1 the tall box, 2 .. 5 the corner discs (-,-) (+,-) (-,+) (+,+), Q_PART_BODY a circle body's own disc;
+// of a capsule body: Q_PART_SIDE the box between its ends, Q_PART_END an end disc.
+// ox, oy, dxp, dyp: o' and d', the cast in a box's frame (q_ray_box);  nx, ny: a disc part's entry point from its centre (q_ray_disc)
+constexpr int Q_PART_BODY = 6, Q_PART_SIDE = 7, Q_PART_END = 8;
+struct QCastDisc { float tin; int part; float ox, oy, dxp, dyp, nx, ny; };
+
+// the ray (origin relative to the body: rx, ry) against a capsule of radius R about the core segment of half length ha: the union of
+// three convex parts in the frame, each met by its own rule: the box lo = (-ha, -R), hi = (ha, R), then the discs of radius R at (-ha, 0)
+// and (ha, 0); the earliest entry wins, the first part in order on a tie.  A ray has R = h.y, a circle cast R = r + h.y.
+__device__ __forceinline__ bool q_ray_capsule(float rx, float ry, float dx, float dy, float max_t, float4 f, float ha, float R, QCastDisc& out)
 {
-    if (circle) { float nx, ny; return q_ray_circle(r, m, h.x, tin, nx, ny); }
+    const float ox = rx * f.x + ry * f.y, oy = rx * f.z + ry * f.w;
+    out.ox = ox; out.oy = oy;
+    out.dxp = dx * f.x + dy * f.y;
+    out.dyp = dx * f.z + dy * f.w;
+    out.nx = 0.f; out.ny = 0.f; out.part = Q_PART_SIDE;
+    float tin = 0.f;
+    bool xe = false;
+    bool hit = q_ray_test(ox, oy, out.dxp, out.dyp, -ha, -R, ha, R, max_t, tin, xe);
+    out.tin = hit ? tin : 0.f;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const float kx = k ? ha : -ha;
+        float nx, ny;
+        const bool pass = q_ray_disc(ox - kx, oy, out.dxp, out.dyp, max_t, R, tin, nx, ny);
+        const bool better = pass && (!hit || tin < out.tin);
+        out.tin = better ? tin : out.tin; out.part = better ? Q_PART_END : out.part;
+        out.nx = better ? nx : out.nx; out.ny = better ? ny : out.ny;
+        hit = hit || pass;
+    }
+    return hit;
+}
+
+// a capsule hit's normal (tin >= 0): the side's is yv, negated where the entry point lies below the axis (the box part's x faces are
+// interior: the face is chosen by where the point is); an end's is the frame normal n / R turned into the world
+__device__ __forceinline__ float2 q_capsule_normal(const QCastDisc& cd, float4 f, float R)
+{
+    if (cd.part == Q_PART_SIDE) {
+        const bool flip = cd.oy + cd.tin * cd.dyp < 0.f;
+        return make_float2(flip ? -f.z : f.z, flip ? -f.w : f.w);
+    }
+    const float nx = cd.nx / R, ny = cd.ny / R;
+    return make_float2(f.x * nx + f.z * ny, f.y * nx + f.w * ny);
+}
+
+// the ray against body b's own shape (after the candidate test): tin alone
+template <bool CAPS>
+__device__ __forceinline__ bool q_ray_body(unsigned kind, const QRay& r, float4 m, float4 f, float2 h, float& tin)
+{
+    if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
+        QCastDisc cd;
+        const bool hit = q_ray_capsule(r.ox - m.z, r.oy - m.w, r.dx, r.dy, r.max_t, f, h.x - h.y, h.y, cd);
+        tin = cd.tin;
+        return hit;
+    }
+    if (kind != 0u) { float nx, ny; return q_ray_circle(r, m, h.x, tin, nx, ny); }
     QRayBox rb;
     const bool hit = q_ray_box(r, m, f, h, rb);
     tin = rb.tin;
@@ -231,11 +305,17 @@ __device__ __forceinline__ bool q_disc_near(const QDisc& c, float4 a)
 }
 
 // the circle against body b's own shape: the centre's offset from the closest point of the box, or the two radii's sum
-__device__ __forceinline__ bool q_disc_overlap(const QDisc& c, float4 a, bool circle, float4 m, float4 f, float2 h)
+template <bool CAPS>
+__device__ __forceinline__ bool q_disc_overlap(const QDisc& c, float4 a, unsigned kind, float4 m, float4 f, float2 h)
 {
     if (!q_disc_near(c, a)) return false;
     const float ex = c.cx - m.z, ey = c.cy - m.w;
-    if (circle) { const float R = c.r + h.x; return ex * ex + ey * ey <= R * R; }
+    if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
+        const float u = ex * f.x + ey * f.y, v = ex * f.z + ey * f.w;
+        const float R = c.r + h.y, gx = u - q_clamp(u, h.x - h.y);
+        return gx * gx + v * v <= R * R;
+    }
+    if (kind != 0u) { const float R = c.r + h.x; return ex * ex + ey * ey <= R * R; }
     const float u = ex * f.x + ey * f.y, v = ex * f.z + ey * f.w;
     const float qu = u < -h.x ? -h.x : (u > h.x ? h.x : u), qv = v < -h.y ? -h.y : (v > h.y ? h.y : v);
     const float gx = u - qu, gy = v - qv;
@@ -250,19 +330,16 @@ __device__ __forceinline__ bool q_cast_aabb(const QDiscCast& c, float4 a)
     return q_ray_test(c.c.cx, c.c.cy, c.dx, c.dy, a.x - c.c.r, a.y - c.c.r, a.z + c.c.r, a.w + c.c.r, c.max_t, tin, xe);
 }
 
-// part: 0 the wide box, 1 the tall box, 2 .. 5 the corner discs (-,-) (+,-) (-,+) (+,+), Q_PART_BODY a circle body's own disc.
-// ox, oy, dxp, dyp: o' and d', the cast in a box's frame (q_ray_box);  nx, ny: a disc part's entry point from its centre (q_ray_disc)
-constexpr int Q_PART_BODY = 6;
-struct QCastDisc { float tin; int part; float ox, oy, dxp, dyp, nx, ny; };
-
-// the centre's ray against the body widened by the radius (after the candidate test): a circle body is the disc of radius r + rb; a
-// box is the union of six convex parts, each met by its own rule, and the earliest entry wins (the first part in order on a tie).
+// the centre's ray against the body widened by the radius (after the candidate test): a circle body is the disc of radius r + rb, a
+// capsule body the capsule of radius r + rb (q_ray_capsule); a box is the union of six convex parts, each met by its own rule, and the earliest entry wins (the first part in order on a tie).
 // Every part is evaluated and the winner kept by selects on named values: no run-time-indexed array (narrowphase.h).
-__device__ __forceinline__ bool q_cast_disc(const QDiscCast& c, bool circle, float4 m, float4 f, float2 h, QCastDisc& out)
+template <bool CAPS>
+__device__ __forceinline__ bool q_cast_disc(const QDiscCast& c, unsigned kind, float4 m, float4 f, float2 h, QCastDisc& out)
 {
     out.tin = 0.f; out.part = 0; out.ox = 0.f; out.oy = 0.f; out.dxp = 0.f; out.dyp = 0.f; out.nx = 0.f; out.ny = 0.f;
     const float rx = c.c.cx - m.z, ry = c.c.cy - m.w;
-    if (circle) {
+    if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) return q_ray_capsule(rx, ry, c.dx, c.dy, c.max_t, f, h.x - h.y, c.c.r + h.y, out);
+    if (kind != 0u) {
         out.part = Q_PART_BODY;
         return q_ray_disc(rx, ry, c.dx, c.dy, c.max_t, c.c.r + h.x, out.tin, out.nx, out.ny);
     }
@@ -368,6 +445,7 @@ static __global__ void __launch_bounds__(256) k_qfill_u64(unsigned long long* __
 }
 
 // the ray results from the winners' keys: the winner's test is made again, by the same code, for its normal
+template <bool CAPS>
 static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const float* __restrict__ rays, int count,
                                                             const unsigned long long* __restrict__ keys, phx_ray_hit* __restrict__ out)
 {
@@ -381,7 +459,13 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
             const float4 m = w.s.mpos[b], f = w.frame[b];
             const float2 sz = w.size[b];
             float t;
-            if (q_circle(w.kinds, b)) {
+            const unsigned kind = q_kind<CAPS>(w.kinds, b);
+            if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
+                QCastDisc cd;
+                (void)q_ray_capsule(r.ox - m.z, r.oy - m.w, r.dx, r.dy, r.max_t, f, sz.x - sz.y, sz.y, cd);
+                t = cd.tin > 0.f ? cd.tin : 0.f;
+                if (!(cd.tin < 0.f)) { const float2 nn = q_capsule_normal(cd, f, sz.y); h.normal.x = nn.x; h.normal.y = nn.y; }
+            } else if (kind != 0u) {
                 float tin, nx, ny;
                 (void)q_ray_circle(r, m, sz.x, tin, nx, ny);
                 t = tin > 0.f ? tin : 0.f;
@@ -405,7 +489,7 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
 }
 
 // the cast results from the winners' keys, as k_qray_finish (SHAPE: QSHAPE_BOX box casts, QSHAPE_DISC circle casts)
-template <int SHAPE>
+template <int SHAPE, bool CAPS>
 static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, const float* __restrict__ casts, int count,
                                                              const unsigned long long* __restrict__ keys, phx_shape_hit* __restrict__ out)
 {
@@ -419,10 +503,13 @@ static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, cons
             const float4 f = w.frame[b];
             const float2 sz = w.size[b];
             QCastDisc cd;
-            (void)q_cast_disc(c, q_circle(w.kinds, b), w.s.mpos[b], f, sz, cd);
+            (void)q_cast_disc<CAPS>(c, q_kind<CAPS>(w.kinds, b), w.s.mpos[b], f, sz, cd);
             h.body = b; h.t = cd.tin > 0.f ? cd.tin : 0.f;
             if (!(cd.tin < 0.f)) {
-                if (cd.part < 2) {                                          // a face, by where the centre is at the entry: an exact copy
+                if (CAPS && cd.part >= Q_PART_SIDE) {
+                    const float2 nn = q_capsule_normal(cd, f, c.c.r + sz.y);
+                    h.normal.x = nn.x; h.normal.y = nn.y;
+                } else if (cd.part < 2) {                                          // a face, by where the centre is at the entry: an exact copy
                     const float px = cd.ox + cd.tin * cd.dxp, py = cd.oy + cd.tin * cd.dyp;
                     const bool xface = fabsf(px) - sz.x >= fabsf(py) - sz.y;
                     const float nx = xface ? f.x : f.z, ny = xface ? f.y : f.w;
@@ -454,6 +541,7 @@ static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, cons
 
 // ---- scan path --------------------------------------------------------------------------------------------------------------------
 // blockIdx.y = the tile of queries [q0, q0 + Q_TILE); bodies grid-strided in lanes.  out: 0xFFFFFFFF (= -1) where nothing was found.
+template <bool CAPS>
 static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int n, const float* __restrict__ pts, int count, int q0, int flags,
                                                              unsigned* __restrict__ out)
 {
@@ -474,10 +562,10 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
         float2 h = make_float2(0.f, 0.f);
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
         const bool any = live && !(skip && q_static(m, w.sleep, i));
-        const bool round = live && q_circle(w.kinds, i);
+        const unsigned round = live ? q_kind<CAPS>(w.kinds, i) : 0u;
         for (int q = 0; q < nq; ++q) {
             const float2 p = qp[q];
-            const bool hit = any && qok[q] && q_point_in_body(round, a, m, f, h, p.x, p.y);
+            const bool hit = any && qok[q] && q_point_in_body<CAPS>(round, a, m, f, h, p.x, p.y);
             const unsigned long long mask = __ballot(hit);
             if (mask && (int)(threadIdx.x & 63) == __builtin_ctzll(mask)) atomicMin(&out[base_q + q], (unsigned)i);      // (the lowest lane holds the lowest body)
         }
@@ -485,7 +573,7 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
 }
 
 // SHAPE: rays (5 floats per query), box casts (11) or circle casts (6)
-template <int SHAPE>
+template <int SHAPE, bool CAPS>
 static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n, const float* __restrict__ rays, int count, int q0, int flags,
                                                            unsigned long long* __restrict__ keys)
 {
@@ -521,7 +609,7 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
         float2 h = make_float2(0.f, 0.f);
         if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
         const bool any = live && !(skip && q_static(m, w.sleep, i));
-        const bool round = !CAST && live && q_circle(w.kinds, i);
+        const unsigned round = !CAST && live ? q_kind<CAPS>(w.kinds, i) : 0u;
         for (int q = 0; q < nq; ++q) {
             bool hit;
             float tin;
@@ -533,12 +621,12 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
             } else if (DISC) {
                 const QDiscCast c = qd[q];
                 QCastDisc cd;
-                hit = any && qok[q] && q_cast_aabb(c, a) && q_cast_disc(c, round, m, f, h, cd);
+                hit = any && qok[q] && q_cast_aabb(c, a) && q_cast_disc<CAPS>(c, round, m, f, h, cd);
                 tin = hit ? cd.tin : 0.f;
             } else {
                 const QRay r = qr[q];
                 float t0 = 0.f;
-                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_body(round, r, m, f, h, t0);
+                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_body<CAPS>(round, r, m, f, h, t0);
                 tin = hit ? t0 : 0.f;
             }
             if (!__ballot(hit)) continue;
@@ -555,7 +643,7 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
 //   QS_RECOUNT  the table alone (a later chunk of queries counted again: the table holds one chunk);
 //   QS_FILL     writes the hits at base + table[...] + rank.
 enum { QS_COUNT = 0, QS_RECOUNT = 1, QS_FILL = 2 };
-template <int MODE, int SHAPE>
+template <int MODE, int SHAPE, bool CAPS>
 static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n, const float* __restrict__ boxes, int count, int q0, int flags, int bblocks,
                                                            unsigned* __restrict__ table, unsigned* __restrict__ qcount, unsigned base, int* __restrict__ hits)
 {
@@ -594,10 +682,10 @@ static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n,
     float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
     float2 h = make_float2(0.f, 0.f);
     if ((OBB || DISC) && live) { f = w.frame[i]; h = w.size[i]; }
-    const bool round = DISC && live && q_circle(w.kinds, i);
+    const unsigned round = DISC && live ? q_kind<CAPS>(w.kinds, i) : 0u;
     unsigned long long mine = 0;
     for (int q = 0; q < nq; ++q) {
-        const bool hit = any && qok[q] && (OBB ? q_box_overlap(qo[q], qe[q], a, m, f, h) : DISC ? q_disc_overlap(qd[q], a, round, m, f, h) : q_overlap(a, qb[q]));
+        const bool hit = any && qok[q] && (OBB ? q_box_overlap(qo[q], qe[q], a, m, f, h) : DISC ? q_disc_overlap<CAPS>(qd[q], a, round, m, f, h) : q_overlap(a, qb[q]));
         const unsigned long long mask = __ballot(hit);
         if (lane == 0) masks[q][wave] = mask;
         mine |= (unsigned long long)hit << q;
@@ -708,7 +796,7 @@ enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COU
 //   QK_DISC_COUNT, QK_DISC_FILL, QK_DISC_CAST   the same three for circles
 // A lane tests a child's bounds with the query's AABB conjunct: the bounds widened by the box's extents or the circle's radius for the
 // last six kinds.
-template <int KIND>
+template <int KIND, bool CAPS>
 static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, const float* __restrict__ queries, int count, int flags,
                                                       unsigned* __restrict__ out_u32, unsigned long long* __restrict__ out_key,
                                                       const unsigned* __restrict__ seg, int* __restrict__ hits)
@@ -772,10 +860,10 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                         b = (int)t.perm[c];
                         const float4 a = w.aabb[b], m = w.s.mpos[b];
                         if (!(skip && q_static(m, w.sleep, b))) {
-                            if (KIND == QK_POINT) hit = q_point_in_body(q_circle(w.kinds, b), a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
+                            if (KIND == QK_POINT) hit = q_point_in_body<CAPS>(q_kind<CAPS>(w.kinds, b), a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
                             else if (KIND == QK_RAY) {
                                 float t0 = 0.f;
-                                hit = q_ray_aabb(r, a) && q_ray_body(q_circle(w.kinds, b), r, m, w.frame[b], w.size[b], t0);
+                                hit = q_ray_aabb(r, a) && q_ray_body<CAPS>(q_kind<CAPS>(w.kinds, b), r, m, w.frame[b], w.size[b], t0);
                                 if (hit) { const unsigned long long k = q_ray_key(t0, b); best_key = k < best_key ? k : best_key; }
                             } else if (KIND == QK_CAST) {
                                 QCastBox cb;
@@ -783,10 +871,10 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                                 if (hit) { const unsigned long long k = q_ray_key(cb.tin, b); best_key = k < best_key ? k : best_key; }
                             } else if (KIND == QK_DISC_CAST) {
                                 QCastDisc cd;
-                                hit = q_cast_aabb(ds, a) && q_cast_disc(ds, q_circle(w.kinds, b), m, w.frame[b], w.size[b], cd);
+                                hit = q_cast_aabb(ds, a) && q_cast_disc<CAPS>(ds, q_kind<CAPS>(w.kinds, b), m, w.frame[b], w.size[b], cd);
                                 if (hit) { const unsigned long long k = q_ray_key(cd.tin, b); best_key = k < best_key ? k : best_key; }
                             } else if (OBB) hit = q_box_overlap(cs.b, ce, a, m, w.frame[b], w.size[b]);
-                            else if (DISC) hit = q_disc_overlap(ds.c, a, q_circle(w.kinds, b), m, w.frame[b], w.size[b]);
+                            else if (DISC) hit = q_disc_overlap<CAPS>(ds.c, a, q_kind<CAPS>(w.kinds, b), m, w.frame[b], w.size[b]);
                             else hit = q_overlap(a, qbox);
                         }
                     }

@@ -75,9 +75,10 @@ public:
     int exclusion_count() const { return exclusion_count_; }
     // the shapes' kinds (SHAPES) ride the same way: one word per body of a world whose shape column was active, none otherwise
     int reserve_shapes(int n, hipStream_t stream) { return n ? shapes_.reserve_keep((size_t)n, (size_t)shape_count_, stream) : PHX_OK; }
-    int save_shapes(const uint32_t* d_src, int count, hipStream_t stream)
+    // (`capsules`: the world's "a capsule was named" bit, which a load hands to the loading world)
+    int save_shapes(const uint32_t* d_src, int count, bool capsules, hipStream_t stream)
     {
-        shape_count_ = count;
+        shape_count_ = count; shape_capsules_ = count && capsules;
         if (!count) return PHX_OK;
         PHX_HIP(hipMemcpyAsync(shapes_.p, d_src, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
         PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
@@ -91,6 +92,7 @@ public:
         return PHX_OK;
     }
     int shape_count() const { return shape_count_; }
+    bool shape_capsules() const { return shape_capsules_; }
     int blob_bytes(size_t* bytes);
     int export_blob(void* blob, size_t cap);
     int import_blob(const void* blob, size_t bytes);
@@ -112,7 +114,7 @@ private:
     std::tuple<Riders<phx_pin>, Riders<phx_link>, Riders<phx_angle>, Riders<phx_slider>> riders_;      // (the kinds in the pass's order)
     template <class P> Riders<P>& riders() { return std::get<Riders<P>>(riders_); }
     DevBuf<uint2> exclusions_; int exclusion_count_ = 0;
-    DevBuf<uint32_t> shapes_; int shape_count_ = 0;
+    DevBuf<uint32_t> shapes_; int shape_count_ = 0; bool shape_capsules_ = false;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

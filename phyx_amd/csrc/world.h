@@ -326,7 +326,7 @@ private:
     int sync_bodies_to_device();
     int refresh_records();               // resident arrays -> the 128-byte records (getters)
     WorldBodies resident() const { return bodies_.view(); }
-    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); w.kinds = shapes_.ptr(); return w; }      // (to a query a sleeper is not static, and a circle is a disc)
+    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); w.kinds = shapes_.ptr(); w.capsules = capsules() ? 1u : 0u; return w; }      // (to a query a sleeper is not static, and a circle is a disc)
     bool host_staged() const { return bodies_dirty_ || !bodies_.records.p; }      // the host-staged records are the world
     int restage_on_host();               // ... again, after the device copy was: records and tables come down
     int refuse_mid_step(const char* what) const;      // PHX_ERR_STATE between pre_solve / step_begin and finish_step / step_end
@@ -445,8 +445,12 @@ private:
     // ... and the sleep states (sleep.h): active exactly while sleeping is enabled
     BodyTable<SleepColumn> sleep_col_;
     // ... and the shapes' kinds (include/phyx_amd.h SHAPES): active once some set_shapes call named a circle; an active table picks
-    // UpdateManifolds' BodyShapes instantiation and hands the kinds to the queries
+    // UpdateManifolds' BodyShapes instantiation and hands the kinds to the queries.  capsules_: some call named a capsule since the last
+    // set_state / load (a load takes the saved world's bit); with the table active it picks the BodyCapsules instantiation and the
+    // queries' capsule instantiations, so a world of boxes and circles launches the kernels it always did
     BodyTable<ShapeColumn> shapes_;
+    bool capsules_ = false;
+    bool capsules() const { return capsules_ && shapes_.active; }
     DeviceSleep sleep_;
     bool sleep_count_pending_ = false;   // the pass or a wake may have changed the static set: the device's count has not been looked at yet
     DevBuf<phx_sleep_state> sleep_out_;

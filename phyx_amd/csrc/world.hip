@@ -201,11 +201,14 @@ int World::scratch_for(int n)
 }
 
 // UpdateManifolds' kernel over manifolds [first, nm): the box/box instantiation, or the one that reads the kinds while the shape column
-// is active (a null column pointer picks the plain instantiation: the kernel of a world that never made a circle)
+// is active (a null column pointer picks the plain instantiation: the kernel of a world that never made a circle), or the third, with
+// the capsule routines, once some call has named a capsule
 void World::queue_update_manifolds(int first, int nm_old, const uint2* new_pairs, const MailRide& ride)
 {
     const uint32_t* const kinds = shapes_.ptr();
-    if (kinds) hipLaunchKernelGGL(k_update_manifolds<BodyShapes>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
+    if (kinds && capsules()) hipLaunchKernelGGL(k_update_manifolds<BodyCapsules>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
+                                                reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, BodyCapsules{kinds});
+    else if (kinds) hipLaunchKernelGGL(k_update_manifolds<BodyShapes>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
                                   reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, BodyShapes{kinds});
     else hipLaunchKernelGGL(k_update_manifolds<AllBoxes>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
                             reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, AllBoxes{});

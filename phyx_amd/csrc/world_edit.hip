@@ -487,22 +487,25 @@ int World::get_body_flags(uint32_t* out, int cap) { return get_table("phx_world_
 
 // ---- shapes -------------------------------------------------------------------------------------------------------------------------
 // The rule: include/phyx_amd.h SHAPES.  The call is an edit of geom_size (the records and the resident size[], the AABB recomputed by
-// set_poses' geom_aabb) and, once some call has named a circle, a write of the kinds' column.  A call that names boxes only in a world
+// set_poses' geom_aabb) and, once some call has named a circle or a capsule, a write of the kinds' column.  A call that names boxes only in a world
 // without the column is the size edit alone: it activates nothing.  Inverse masses, manifolds, joints and the schedule stay.
 int World::set_shapes(const int32_t* bodies, const phx_shape* shapes, int count)
 {
     static const char* const what = "phx_world_set_shapes";
     PHX_TRY(refuse_sharded(what, "shapes"));
     PHX_TRY(check_batch(what, bodies, shapes, count, true));
-    bool circle = false;
+    bool circle = false, capsule = false;                                   // (`circle`: some entry is not a box)
     for (int k = 0; k < count; ++k) {                                       // (NaN fails the comparisons)
         const phx_shape& s = shapes[k];
-        if (s.kind != PHX_SHAPE_BOX && s.kind != PHX_SHAPE_CIRCLE) { set_error("%s: kind %d of body %d is neither PHX_SHAPE_BOX nor PHX_SHAPE_CIRCLE", what, s.kind, bodies[k]); return PHX_ERR_INVALID; }
+        if (s.kind != PHX_SHAPE_BOX && s.kind != PHX_SHAPE_CIRCLE && s.kind != PHX_SHAPE_CAPSULE) { set_error("%s: kind %d of body %d is none of PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE, PHX_SHAPE_CAPSULE", what, s.kind, bodies[k]); return PHX_ERR_INVALID; }
         if (!(std::isfinite(s.hx) && std::isfinite(s.hy) && s.hx > 0.f && s.hy > 0.f)) { set_error("%s: the size {%g, %g} of body %d is not finite and positive", what, (double)s.hx, (double)s.hy, bodies[k]); return PHX_ERR_INVALID; }
         if (s.kind == PHX_SHAPE_CIRCLE && s.hy != s.hx) { set_error("%s: body %d is a circle and hy %g is not its radius hx %g", what, bodies[k], (double)s.hy, (double)s.hx); return PHX_ERR_INVALID; }
-        circle = circle || s.kind == PHX_SHAPE_CIRCLE;
+        if (s.kind == PHX_SHAPE_CAPSULE && !(s.hx > s.hy)) { set_error("%s: body %d is a capsule and hx %g is not above its radius hy %g (hx == hy: use PHX_SHAPE_CIRCLE)", what, bodies[k], (double)s.hx, (double)s.hy); return PHX_ERR_INVALID; }
+        circle = circle || s.kind != PHX_SHAPE_BOX;
+        capsule = capsule || s.kind == PHX_SHAPE_CAPSULE;
     }
     if (!count) return PHX_OK;
+    capsules_ = (capsules_ && shapes_.active) || capsule;                   // (a column that went away took the bit with it)
     PHX_TRY(wake_named(bodies, count));
     const int n = nb();
     const bool kinds = circle || shapes_.active;

@@ -144,9 +144,9 @@ struct FlagsColumn {                   // include/phyx_amd.h BODY FLAGS / SENSOR
     static bool is_initial(const value& v) { return v == 0u; }
 };
 struct ShapeColumn {                   // include/phyx_amd.h SHAPES; the rule: narrowphase.h update_manifold, query_kernels.h
-    using value = uint32_t;            // PHX_SHAPE_BOX or PHX_SHAPE_CIRCLE (the size lives where it always did: the records and size[])
+    using value = uint32_t;            // PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE or PHX_SHAPE_CAPSULE (the size lives where it always did: the records and size[])
     using api = phx_shape;
-    static constexpr const char* plural = "circles";
+    static constexpr const char* plural = "circles or capsules";
     static __host__ __device__ value initial() { return (uint32_t)PHX_SHAPE_BOX; }
     static __host__ __device__ value stored(const api& s) { return (uint32_t)s.kind; }
     static bool is_initial(const value& v) { return v == (uint32_t)PHX_SHAPE_BOX; }
@@ -311,12 +311,20 @@ static __global__ void __launch_bounds__(256) k_x_extent(WorldBodies w, int n, u
 
 // The bodies' kinds (include/phyx_amd.h SHAPES) are a parameter of UpdateManifolds' kernel: AllBoxes (a world without an active shape
 // column) gives the constant PHX_SHAPE_BOX, so update_manifold's dispatch folds away and the kernel is the box/box code it always was;
-// BodyShapes reads one 4-byte word per body.
+// BodyShapes reads one 4-byte word per body and knows boxes and circles; BodyCapsules (a world in which some call named a capsule) reads
+// the same word and compiles the capsule routines in, so that they cost a circle world no register.
 struct AllBoxes {
+    static constexpr bool capsules = false;
     __device__ unsigned operator()(int) const { return (unsigned)PHX_SHAPE_BOX; }
 };
 struct BodyShapes {
+    static constexpr bool capsules = false;
     const uint32_t* kind;              // per body (ShapeColumn)
+    __device__ unsigned operator()(int i) const { return kind[i]; }
+};
+struct BodyCapsules {
+    static constexpr bool capsules = true;
+    const uint32_t* kind;
     __device__ unsigned operator()(int i) const { return kind[i]; }
 };
 
@@ -359,7 +367,7 @@ static __global__ void __launch_bounds__(256) k_update_manifolds(phx_manifold* _
         } else m = manifolds[i];
         // (two bodies = 2 x 40 bytes of the resident arrays; the 128-byte records cost 2 x 128 for the same fields)
         const NpBody b1 = np_load(bodies, m.body1, shapes), b2 = np_load(bodies, m.body2, shapes);
-        if (update_manifold(m, b1, b2, cps + m.point_index)) atomicAdd(dropped, 1);
+        if (update_manifold<Shapes::capsules>(m, b1, b2, cps + m.point_index)) atomicAdd(dropped, 1);
         manifolds[i] = m;
         const bool gone = m.point_count == 0 && !aabb_intersects(bodies.aabb[m.body1], bodies.aabb[m.body2]);
         dead[i] = gone ? 1u : 0u;

@@ -34,6 +34,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
+    capsules_ = false;
     pins_.clear();                                                          // ... and no pin or link is left, no break limit and no break event
     exclusions_.clear();                                                    // ... and no pair is excluded
     break_step_ = 0;
@@ -120,7 +121,7 @@ int World::save(Snapshot& s)
     PHX_TRY(s.save(v, stream_));
     PHX_TRY(pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); }));
     PHX_TRY(s.save_exclusions(exclusions_.device_pairs(), exclusions_.count(), stream_));
-    return s.save_shapes(shapes_.dev.p, kinds, stream_);
+    return s.save_shapes(shapes_.dev.p, kinds, capsules(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -146,6 +147,7 @@ int World::load(Snapshot& s)
     PHX_TRY(s.load(snapshot_view(), stream_));
     PHX_TRY(s.load_shapes(shapes_.dev.p, stream_));                         // phx_world_set_shapes of the saved kinds, if that column was active in s (the sizes came with the records)
     shapes_.active = s.shape_count() != 0;
+    capsules_ = s.shape_capsules();
     // the device copy is the world (host-staged bodies and tables are dropped with the rest of the old world)
     host_bodies_.resize(n);                                                 // (only its size counts while the device copy is the world)
     bodies_dirty_ = false;
