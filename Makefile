@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest wind fold marbles fit logs clean
+.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest wind fold marbles fit logs ramp clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -46,6 +46,9 @@ fold: build                 ## collision exclusions: a folded chain dropped on i
 logs: build                 ## shapes: a dozen capsules dropped onto a shelf between two posts, one that topples from its end (PHX_SHAPE_CAPSULE)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/logs.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/logs
 
+ramp: build                 ## shapes: boxes slide, marbles roll and a hexagon tumbles down a static wedge into a trapezoid tray; a ray onto the slope (PHX_SHAPE_POLYGON, phx_world_set_polygons)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/ramp.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/ramp
+
 marbles: build              ## shapes: circles dropped through a funnel of static boxes into a tray, a round wheel on a motor (phx_world_set_shapes)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/marbles.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/marbles
 
@@ -53,5 +56,5 @@ fit: build                  ## the marble emitter that looks first (phx_world_qu
 	gcc -std=c11 -O2 -Wall -Iinclude examples/fit.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/fit
 
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest examples/wind examples/fold examples/marbles examples/fit examples/logs
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest examples/wind examples/fold examples/marbles examples/fit examples/logs examples/ramp
 	rm -rf oracle/_ref

@@ -707,6 +707,67 @@ int  phx_world_set_shapes(phx_world* w, const int32_t* bodies, const phx_shape* 
 /* every body's {kind, geom_size.x, geom_size.y}, in index order (cap: room for that many; PHX_ERR_CAPACITY otherwise); a world that
  * never set a shape reports boxes */
 int  phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap);
+/* POLYGONS — convex polygon bodies, the fourth kind (PHX_SHAPE_POLYGON).  A polygon is `count` vertices, 3 .. PHX_POLYGON_MAX_VERTICES,
+ * in the body's frame (x along xv, y along yv, relative to pos), counter-clockwise; unused slots are stored as +0 and returned as +0.
+ * phx_world_set_shapes keeps refusing kind 3 (it names this call); called on a polygon body it turns the body into a box, a circle or a
+ * capsule and resets its polygon record to the default (count 0).  phx_world_get_shapes reports kind 3 with the frame box.
+ *   - Validity, decided on the host in fp32 (tests/polygon_spec.py poly_valid states the same expressions), all of it before anything is
+ *     queued, PHX_ERR_INVALID otherwise and the world unchanged: count in range and every coordinate finite; with e_k = v_(k+1) - v_k
+ *     (indices mod count), cross(a, b) = a.x*b.y - a.y*b.x, l_k = sqrtf(dot(e_k, e_k)) and n_k = (e_k.y / l_k, -e_k.x / l_k): every
+ *     cross(e_k, e_(k+1)) > 0 (strictly convex, counter-clockwise) and every dot(n_k, v_k) > 0 (the origin strictly inside: it is the
+ *     centre of rotation and, by phyx_amd.polygon_inverse_masses, meant to be the centre of mass).  The body-list rules are those of
+ *     phx_world_set_shapes: indices in range, none twice, between steps only, PHX_ERR_STATE for a sharded or communicator-attached world.
+ *   - What the call sets: the kind; the polygon record {count, v[8], n[8]} with n_k as above, formed by the same fp32 expressions on the
+ *     host path (before the first step) and on the device path, so both give the same bytes; the frame box geom_size =
+ *     {max |v_k.x|, max |v_k.y|}; the AABB through the unchanged UpdateGeom.  The frame box contains the polygon, so UpdateGeom,
+ *     IntegratePosition, the broadphase, the dead-manifold test and the contact reports stay as they are and stay valid.  Staging,
+ *     the stream, sleepers, cached points and the query index: as phx_world_set_shapes.
+ *   - The records are a column of 132 B per body that exists only once some call named a polygon; a "polygons" bit, set by that call and
+ *     cleared by set_state (a load takes the saved world's bit), picks UpdateManifolds' fourth instantiation and the queries' polygon
+ *     instantiations.  A world that never made a polygon launches exactly what it launched before.
+ *   - The rule (tests/polygon_spec.py is the definition, byte for byte; narrowphase.h restates it).  The box/box, circle and capsule pairs
+ *     stay the code they are; a pair with at least one polygon takes the routines below, in which a box is the 4-gon (-hx,-hy), (hx,-hy),
+ *     (hx,hy), (-hx,hy) with the exact normals (0,-1), (1,0), (0,1), (-1,0).  World vertex w_k = (pos + xv*v_k.x) + yv*v_k.y, world normal
+ *     N_k = xv*n_k.x + yv*n_k.y; every operation fp32, rounded on its own.
+ *       polygon / polygon (and polygon / box), A = body1, B = body2:  for each edge i of A, s_i = min_j dot(NA_i, wB_j - wA_i) (the first
+ *         j's value, then `<`); sA = the largest s_i, the first on a tie.  No point if sA > 0.  sB likewise, no point if sB > 0.  The
+ *         reference face is A's unless sB > sA.  With r0 = wRef_i, r1 = wRef_(i+1), Nr = NRef_i: the incident edge j of the other body
+ *         is the one with the smallest dot(Nr, NInc_j), the first on a tie; p0 = wInc_j, p1 = wInc_(j+1).  Clip against the side planes,
+ *         with e = r1 - r0:  d0 = dot(p0 - r0, e), d1 = dot(p1 - r0, e); both < 0: no point; d0 < 0: p0 = p0 + (p1 - p0)*(d0 / (d0 - d1));
+ *         else d1 < 0: p1 = p1 + (p0 - p1)*(d1 / (d1 - d0)).  Then the same with d0 = dot(r1 - p0, e), d1 = dot(r1 - p1, e).  Each of
+ *         p0, p1 in this order with s = dot(Nr, p - r0) <= 0 is a contact: the incident body's point is p, the reference body's
+ *         p - Nr*s; the normal is -Nr if the reference is body1, Nr if it is body2.  At most two points, through MergeCollision.
+ *       disc {c, r} against polygon P (a candidate as in SHAPES):  g = c - pos, p = (dot(g, xv), dot(g, yv)); s_k = dot(n_k, p - v_k), k
+ *         the largest, the first on a tie, s its value.  No candidate if s > r.  If s > 0, with e = v_(k+1) - v_k and t = dot(p - v_k, e):
+ *         t < 0 picks the vertex q = v_k, t > dot(e, e) the vertex q = v_(k+1); there h = p - q, l2 = dot(h, h), no candidate if
+ *         l2 > r*r, l = sqrtf(l2), N' = (h.x / l, h.y / l), depth = r - l.  Otherwise (s <= 0, or the face region) N' = n_k,
+ *         depth = r - s, q = p - n_k*s.  N = xv*N'.x + yv*N'.y, polygon point = (pos + xv*q.x) + yv*q.y, disc point = c - N*r.
+ *       circle / polygon:  that one candidate.
+ *       capsule K / polygon P:  K's two end discs against P, then P's vertices w_k in index order as discs of radius 0 against K, each
+ *         only if unclamped: up to ten candidates, selected by the capsule rule word for word (the deepest first, then the farthest
+ *         distinct one under Equals(2.0f), the first in order on ties), as a running selection over the stream of candidates.
+ *     Known limit: a deep state in which the face of least penetration is no longer the touching one (a small polygon pushed more than
+ *     half way through a thin one): the rule reports the least-penetration face, which is the minimum translation and not the face the
+ *     body came in through; the float64 judge (tests/polygon_reference.py) agrees on the depth there and the state is a tunnelled one.
+ *   - Queries.  Point p in polygon b iff p is inside b's AABB (closed) AND, with p' the point in the frame (as for a box), every
+ *     dot(n_k, p' - v_k) <= 0.  A ray hits polygon b iff b is a candidate and, in the frame (o', d' as in the ray rule), with tin = -inf,
+ *     tout = +inf and for k in index order den = dot(n_k, d'), num = dot(n_k, v_k - o'):  den < 0: t = num / den, if t > tin then tin = t
+ *     and the entering edge is k;  den > 0: t = num / den, if t < tout then tout = t;  den == 0 and num < 0: a miss.  Then the box rule's
+ *     final condition (tin <= tout, tout >= 0, tin <= max_t) and its conventions: t = max(tin, 0), the origin inside gives the normal
+ *     (0, 0), otherwise the normal is the entering edge's, xv*n_k.x + yv*n_k.y; ties to the lowest body index.  Oriented-box overlap, box
+ *     casts, circle overlap and circle casts see a polygon as its frame box: conservative and mutually consistent, as box queries see
+ *     circles and capsules; exact forms are a later change.
+ *   - The other calls: add_body / add_bodies give boxes; remove_bodies / remove_outside and spawns carry the column; set_state resets every
+ *     kind to box and drops the column; save / load / fork carry it in HBM beside the blob; export of a snapshot with a polygon and
+ *     sharding return PHX_ERR_STATE, as for the other kinds that are not boxes.
+ * Out of scope: concave or compound bodies, more than 8 vertices, exact polygons in the box and circle overlap and cast queries, polygons
+ * in exported blobs and in sharded worlds. */
+#define PHX_SHAPE_POLYGON 3
+#define PHX_POLYGON_MAX_VERTICES 8
+typedef struct { int32_t count; phx_vec2 v[8]; } phx_polygon;   /* 68 B; body-local vertices, counter-clockwise, count in 3 .. 8 */
+int  phx_world_set_polygons(phx_world* w, const int32_t* bodies, const phx_polygon* polygons, int32_t count);
+/* the polygons of the listed bodies (any order, repeats allowed); a body that is not a polygon gives count 0 and zeros */
+int  phx_world_get_polygons(phx_world* w, const int32_t* bodies, phx_polygon* out, int32_t count);
 /* QUERIES — where things are: what overlaps a region, what is under a point, what a ray hits first, whether a spot is free for a box
  * or a circle and how far a box or a circle can move before it touches something.  Batched, answered on the device
  * from the resident geometry; nothing of the world crosses PCIe.  Body b's geometry is that of its record (phx_world_get_bodies()[b]):
@@ -1494,6 +1555,11 @@ int phx_debug_primitive_plan(int32_t bits, int32_t scan_count, int32_t* digit_bi
  * updated in place. */
 int phx_debug_update_manifold(const phx_rigid_body* b1, int32_t kind1, const phx_rigid_body* b2, int32_t kind2, phx_manifold* manifold,
                               phx_contact_point pts[2]);
+/* ... and the same through the instantiation a world launches once a polygon was named (POLYGONS): a kind may be PHX_SHAPE_POLYGON, whose
+ * body's polygon (poly1, poly2; NULL for a body that is none) is stored as the set call stores it, the normals formed from the vertices.
+ * A pair without a polygon gives phx_debug_update_manifold's bytes. */
+int phx_debug_update_manifold_polygons(const phx_rigid_body* b1, int32_t kind1, const phx_polygon* poly1, const phx_rigid_body* b2, int32_t kind2,
+                                       const phx_polygon* poly2, phx_manifold* manifold, phx_contact_point pts[2]);
 /* phx_debug_schedule_bins (host only, needs no device): the three host rules every schedule builder shares, on `count` components given by
  * their joint counts sizes[] and unit counts units[] (in body order).  A workgroup shape of L lanes holds L units and 2 L joints.
  *   *lanes            the shape all groups take: big_lanes iff big_lanes != 0 and some non-empty component fits it but not small_lanes

@@ -84,6 +84,7 @@ _SIGNATURES = {
     "phx_debug_radix_sort": (C.c_int, [C.c_int, _vp, _vp, _i32, _i32, _vp, _vp, C.POINTER(_i32)]),
     "phx_debug_primitive_plan": (C.c_int, [_i32, _i32] + [C.POINTER(_i32)] * 4),
     "phx_debug_update_manifold": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "phx_debug_update_manifold_polygons": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp]),
     "phx_debug_schedule_bins": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.POINTER(_i32), _vp, _vp, _vp] + [C.POINTER(_i32)] * 3),
     "phx_exchange_layout": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, C.POINTER(C.c_int64)]),
     "phx_solver_set_exchange_buffers": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -185,6 +186,8 @@ _SIGNATURES = {
     "phx_world_get_body_flags": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_set_shapes": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_get_shapes": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_set_polygons": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_get_polygons": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_query_aabb": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "phx_world_query_points": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_raycast": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),

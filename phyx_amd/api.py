@@ -49,6 +49,8 @@ material_dtype = np.dtype([("friction", "<f4"), ("restitution", "<f4")])      # 
 assert material_dtype.itemsize == 8
 shape_dtype = np.dtype([("kind", "<i4"), ("hx", "<f4"), ("hy", "<f4")])      # phx_shape
 assert shape_dtype.itemsize == 12
+polygon_dtype = np.dtype([("count", "<i4"), ("v", "<f4", (8, 2))])      # phx_polygon
+assert polygon_dtype.itemsize == 68
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 pin_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("impulse", "<f4", (2,))])      # phx_pin
@@ -78,6 +80,7 @@ UNIT_KINDS = ("pin", "link", "angle", "slider")      # PHX_UNIT_PIN ... PHX_UNIT
 CONTACT_NEW, CONTACT_NO_JOINT = 1, 2      # phx_contact.flags
 BODY_SENSOR = 1                           # PHX_BODY_SENSOR (phx_world_set_body_flags)
 SHAPE_BOX, SHAPE_CIRCLE, SHAPE_CAPSULE = 0, 1, 2            # PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE, PHX_SHAPE_CAPSULE (phx_shape.kind)
+SHAPE_POLYGON, POLYGON_MAX_VERTICES = 3, 8                  # PHX_SHAPE_POLYGON, PHX_POLYGON_MAX_VERTICES
 assert manifold_dtype.itemsize == 16 and contact_joint_dtype.itemsize == 20 and broadphase_entry_dtype.itemsize == 20
 
 
@@ -136,6 +139,51 @@ def capsule_inverse_masses(hx, hy):
         mass = mb + mc
         inertia = mb * (a * a + r * r) + mc * (f(1.5) * r * r + f(3.0) * a * a + f(2.546479) * a * r)
         return np.stack([f(1.0) / mass, f(1.0) / inertia], axis=1).astype(np.float32)
+
+
+def polygon_inverse_masses(vertices):
+    """(2,) float32 {invMass, invInertia} of the convex polygon with the given (N, 2) body-local vertices, counter-clockwise, on AddBody's
+    scale (include/phyx_amd.h POLYGONS): with the float64 shoelace area A and the second moment J about the origin,
+    mass = 1e-5 * A / 4 and inertia = 3 * mass * J / A, both rounded to float32.  A rectangle's corners give the box formula."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 2)
+    w = np.roll(v, -1, axis=0)
+    c = v[:, 0] * w[:, 1] - w[:, 0] * v[:, 1]
+    area = 0.5 * c.sum()
+    second = (c * ((v * v).sum(axis=1) + (v * w).sum(axis=1) + (w * w).sum(axis=1))).sum() / 12.0
+    mass = 1e-5 * area / 4.0
+    inertia = 3.0 * mass * second / area
+    f = np.float32
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        return np.array([f(1.0) / f(mass), f(1.0) / f(inertia)], dtype=np.float32)
+
+
+def _polygons(polygons, count, what):
+    """`count` phx_polygon records from an array of polygon_dtype, one (N, 2) vertex list for all bodies, or one vertex list per body."""
+    if isinstance(polygons, np.ndarray) and polygons.dtype == polygon_dtype:
+        p = np.ascontiguousarray(polygons).reshape(-1)
+        if len(p) == 1 and count != 1:
+            p = np.repeat(p, count)
+        if len(p) != count:
+            raise ValueError("%s: %d polygons for %d bodies" % (what, len(p), count))
+        return p
+    try:
+        one = np.asarray(polygons, dtype=np.float32)
+    except (ValueError, TypeError):
+        one = None
+    lists = [one] * count if one is not None and one.ndim == 2 else list(polygons)
+    if len(lists) != count:
+        raise ValueError("%s: %d polygons for %d bodies" % (what, len(lists), count))
+    p = np.zeros(count, dtype=polygon_dtype)
+    for k, v in enumerate(lists):
+        if getattr(v, "dtype", None) == polygon_dtype:
+            p[k] = v
+            continue
+        v = np.asarray(v, dtype=np.float32)
+        if v.ndim != 2 or v.shape[1] != 2:
+            raise ValueError("%s: polygon %d must have shape (N, 2), got %s" % (what, k, v.shape))
+        p["count"][k] = len(v)                                              # (the library rejects a count outside 3 .. 8)
+        p["v"][k][:min(len(v), POLYGON_MAX_VERTICES)] = v[:POLYGON_MAX_VERTICES]
+    return p
 
 
 def _or_empty(a, shape, dtype):
@@ -1479,6 +1527,47 @@ class World:
         if len(idx):
             self.set_shapes(idx, SHAPE_CAPSULE, s[:, 3], s[:, 4])
             self.set_inverse_masses(idx, capsule_inverse_masses(s[:, 3], s[:, 4]))
+        return first
+
+    # ---- polygons (include/phyx_amd.h POLYGONS; the specification: tests/polygon_spec.py) ----
+    def set_polygons(self, bodies, polygons):
+        """Make the listed bodies (each at most once) convex polygons: `polygons` is one (N, 2) list of body-local vertices for all of
+        them, one such list per body, or an array of polygon_dtype.  The vertices are counter-clockwise, 3 to 8 of them, strictly convex,
+        with the body's origin strictly inside.  The body's kind becomes SHAPE_POLYGON, its geom_size the frame box
+        (max |x|, max |y|) and its AABB is recomputed; the inverse masses stay (set_inverse_masses; polygon_inverse_masses has the
+        formula).  The library rejects anything else (PhxError), the world unchanged.  set_shapes turns a polygon back into a box, a
+        circle or a capsule."""
+        idx = self._indices(bodies, "set_polygons")
+        p = _polygons(polygons, len(idx), "set_polygons")
+        check(self.L.phx_world_set_polygons(self.h, _ptr(idx), _ptr(p), len(idx)))
+
+    def polygons(self, bodies=None):
+        """The polygons of the listed bodies (all of them if None), in that order: an array of polygon_dtype; count 0 and zeros for a
+        body that is not a polygon."""
+        idx = np.arange(self.counts()[0], dtype=np.int32) if bodies is None else np.ascontiguousarray(np.asarray(bodies).reshape(-1), dtype=np.int32)
+        out = np.zeros(len(idx), dtype=polygon_dtype)
+        check(self.L.phx_world_get_polygons(self.h, _ptr(idx), _ptr(out), len(idx)))
+        return out
+
+    def add_polygons(self, spawn, polygons):
+        """Append polygons: spawn is a (K, 3) float array {px, py, angle}, `polygons` as in set_polygons.  add_bodies with each polygon's
+        frame box as half extents, then set_polygons of the new bodies, then set_inverse_masses with polygon_inverse_masses.  Returns
+        the first new index."""
+        a = np.asarray(spawn)
+        if a.dtype.kind != "f":
+            raise TypeError("add_polygons: spawn must be a float array, got %s" % (a.dtype,))
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError("add_polygons: spawn must have shape (K, 3) {px, py, angle}, got %s" % (a.shape,))
+        s = np.ascontiguousarray(a, dtype=np.float32)
+        p = _polygons(polygons, len(s), "add_polygons")
+        if ((p["count"] < 3) | (p["count"] > POLYGON_MAX_VERTICES)).any():
+            raise ValueError("add_polygons: a polygon has 3 to %d vertices" % POLYGON_MAX_VERTICES)
+        half = np.array([np.abs(q["v"][:q["count"]]).max(axis=0) for q in p], dtype=np.float32).reshape(-1, 2)
+        idx = self.add_bodies(np.ascontiguousarray(np.column_stack([s, half])))
+        first = int(idx[0]) if len(idx) else self.counts()[0]
+        if len(idx):
+            self.set_polygons(idx, p)
+            self.set_inverse_masses(idx, np.array([polygon_inverse_masses(q["v"][:q["count"]]) for q in p], dtype=np.float32))
         return first
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----

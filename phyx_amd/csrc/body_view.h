@@ -24,6 +24,11 @@ struct BodyView {
     float4* mpos;
 };
 
+// a polygon body's stored record (include/phyx_amd.h POLYGONS; formed by narrowphase.h poly_record): the body-local vertices and the unit
+// outward normal of each edge v_k -> v_(k+1), as {x, y} pairs; count 0: the body is no polygon
+struct PolyRec { int32_t count; float v[2 * PHX_POLYGON_MAX_VERTICES]; float n[2 * PHX_POLYGON_MAX_VERTICES]; };      // {count, v[8], n[8]}: 33 words
+static_assert(sizeof(PolyRec) == 132, "a polygon record is 33 words");
+
 // everything the World keeps per body: the solver's view + frame, AABB and half size
 struct WorldBodies {
     BodyView s;
@@ -32,6 +37,7 @@ struct WorldBodies {
     float2* size;       // geom.size
     const struct SleepCell* sleep;      // the queries only (query_kernels.h q_static): the sleep column (sleep.h), null while sleeping is off and in every other view
     const uint32_t* kinds;              // the queries only (query_kernels.h q_circle): the shape column (world_kernels.h ShapeColumn), null while no body is a circle and in every other view
+    const PolyRec* polys;        // the queries only: the polygon column (world_kernels.h PolygonColumn), null unless some call named a polygon: picks the kernels' polygon instantiations (query.hip)
     uint32_t capsules;                  // the queries only, read by the host alone: a kind may be PHX_SHAPE_CAPSULE, which picks the kernels' capsule instantiations (query.hip)
 };
 

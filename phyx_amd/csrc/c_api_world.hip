@@ -253,6 +253,18 @@ int phx_world_get_shapes(phx_world* w, phx_shape* out, int32_t cap)
     return w->impl.get_shapes(out, cap);
 }
 
+int phx_world_set_polygons(phx_world* w, const int32_t* bodies, const phx_polygon* polygons, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_polygons(bodies, polygons, count);
+}
+
+int phx_world_get_polygons(phx_world* w, const int32_t* bodies, phx_polygon* out, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.get_polygons(bodies, out, count);
+}
+
 int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
 {
     PHX_REQUIRE(w, "null handle");

@@ -147,12 +147,35 @@ int phx_debug_update_manifold(const phx_rigid_body* b1, int32_t kind1, const phx
     PHX_REQUIRE(manifold->point_count >= 0 && manifold->point_count <= 2, "phx_debug_update_manifold: point_count is 0 .. 2");
     auto body = [](const phx_rigid_body& b, int32_t kind) {
         NpBody n;
-        n.pos = v2(b.pos); n.xv = v2(b.xvector); n.yv = v2(b.yvector); n.size = v2(b.geom_size); n.kind = (unsigned)kind;
+        n.pos = v2(b.pos); n.xv = v2(b.xvector); n.yv = v2(b.yvector); n.size = v2(b.geom_size); n.kind = (unsigned)kind; n.poly = nullptr;
         return n;
     };
     // (the instantiation the world would launch: the capsule one only for a pair that holds a capsule)
     if (kind1 == PHX_SHAPE_CAPSULE || kind2 == PHX_SHAPE_CAPSULE) (void)update_manifold<true>(*manifold, body(*b1, kind1), body(*b2, kind2), pts);
     else (void)update_manifold<false>(*manifold, body(*b1, kind1), body(*b2, kind2), pts);
+    return PHX_OK;
+}
+
+int phx_debug_update_manifold_polygons(const phx_rigid_body* b1, int32_t kind1, const phx_polygon* poly1, const phx_rigid_body* b2, int32_t kind2,
+                                       const phx_polygon* poly2, phx_manifold* manifold, phx_contact_point pts[2])
+{
+    using namespace phx;
+    PHX_REQUIRE(b1 && b2 && manifold && pts, "phx_debug_update_manifold_polygons: null argument");
+    PHX_REQUIRE(kind1 >= PHX_SHAPE_BOX && kind1 <= PHX_SHAPE_POLYGON && kind2 >= PHX_SHAPE_BOX && kind2 <= PHX_SHAPE_POLYGON, "phx_debug_update_manifold_polygons: a kind is 0 .. 3");
+    PHX_REQUIRE((kind1 != PHX_SHAPE_POLYGON || poly1) && (kind2 != PHX_SHAPE_POLYGON || poly2), "phx_debug_update_manifold_polygons: a polygon body needs its polygon");
+    PHX_REQUIRE((kind1 != PHX_SHAPE_POLYGON || (poly1->count >= 3 && poly1->count <= PHX_POLYGON_MAX_VERTICES)) &&
+                (kind2 != PHX_SHAPE_POLYGON || (poly2->count >= 3 && poly2->count <= PHX_POLYGON_MAX_VERTICES)), "phx_debug_update_manifold_polygons: a vertex count is 3 .. 8");
+    PHX_REQUIRE(manifold->point_count >= 0 && manifold->point_count <= 2, "phx_debug_update_manifold_polygons: point_count is 0 .. 2");
+    PolyRec r1 = {}, r2 = {};                                               // (the records the set call would store)
+    if (kind1 == PHX_SHAPE_POLYGON) r1 = poly_record(*poly1);
+    if (kind2 == PHX_SHAPE_POLYGON) r2 = poly_record(*poly2);
+    auto body = [](const phx_rigid_body& b, int32_t kind, const PolyRec* rec) {
+        NpBody n;
+        n.pos = v2(b.pos); n.xv = v2(b.xvector); n.yv = v2(b.yvector); n.size = v2(b.geom_size); n.kind = (unsigned)kind; n.poly = rec;
+        return n;
+    };
+    // (the fourth instantiation: what a world in which a polygon was named launches for every pair)
+    (void)update_manifold<true, true>(*manifold, body(*b1, kind1, &r1), body(*b2, kind2, &r2), pts);
     return PHX_OK;
 }
 

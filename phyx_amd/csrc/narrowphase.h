@@ -6,10 +6,10 @@
 // RigidBody.h:38-42: the same values).  The functions are
 // plain IEEE float arithmetic (no libm beyond fabsf, and the correctly rounded sqrtf of the round pairs) so the host loop and a HIP
 // kernel that call them produce identical bits under -ffp-contract=off.  Round bodies (circle/circle, circle/box, the capsule pairs) have no counterpart
-// in the reference: their rule is include/phyx_amd.h SHAPES.
+// in the reference: their rule is include/phyx_amd.h SHAPES; nor have convex polygons (include/phyx_amd.h POLYGONS).
 #pragma once
 
-#include "common.h"
+#include "body_view.h"
 
 namespace phx {
 
@@ -27,7 +27,10 @@ __host__ __device__ __attribute__((always_inline)) inline phx_vec2 pv(V2 a) { ph
 
 // what the narrowphase reads of a body (`kind`: PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE or PHX_SHAPE_CAPSULE, include/phyx_amd.h SHAPES; a circle's radius
 // is size.x, a capsule's size.y with the core segment size.x - size.y either way along xv)
-struct NpBody { V2 pos, xv, yv, size; unsigned kind; };
+// `poly`: the body's polygon record (PHX_SHAPE_POLYGON; include/phyx_amd.h POLYGONS), read by the polygon routines alone: null, and never
+// looked at, in every instantiation without them
+// (PolyRec: body_view.h)
+struct NpBody { V2 pos, xv, yv, size; unsigned kind; const PolyRec* poly; };
 
 // ref: Geom.h:79-85 RecomputeAABB: {min.x, min.y, max.x, max.y}
 __host__ __device__ __attribute__((always_inline)) inline void geom_aabb(V2 pos, V2 xv, V2 yv, V2 size, float& minx, float& miny, float& maxx, float& maxy)
@@ -403,12 +406,193 @@ __host__ __device__ __attribute__((always_inline)) inline void capsule_contact(c
     capsule_select(c0, c1, c2, c3, c4, c5, pts, count, b1, b2);
 }
 
+// ---- convex polygons (include/phyx_amd.h POLYGONS; tests/polygon_spec.py is the definition and states what follows as the same expressions) ----
+// The stored record of a polygon: the vertices and n_k, the unit outward normal of the edge v_k -> v_(k+1): e = v_next - v_k,
+// l = sqrtf(dot(e, e)), n = (e.y / l, -e.x / l).  One function for the host path and the device path: the same bytes.
+__host__ __device__ inline PolyRec poly_record(const phx_polygon& p)
+{
+    PolyRec r;
+    r.count = p.count;
+    for (int k = 0; k < PHX_POLYGON_MAX_VERTICES; ++k) { r.v[2 * k] = 0.f; r.v[2 * k + 1] = 0.f; r.n[2 * k] = 0.f; r.n[2 * k + 1] = 0.f; }
+    const int c = p.count < 0 ? 0 : (p.count > PHX_POLYGON_MAX_VERTICES ? PHX_POLYGON_MAX_VERTICES : p.count);
+    for (int k = 0; k < c; ++k) {
+        const int k1 = k + 1 < c ? k + 1 : 0;
+        const V2 a = v2(p.v[k]), e = v2(p.v[k1]) - a;
+        const float l = sqrtf(dot(e, e));
+        r.v[2 * k] = a.x; r.v[2 * k + 1] = a.y;
+        r.n[2 * k] = e.y / l; r.n[2 * k + 1] = -e.x / l;
+    }
+    return r;
+}
+
+// In a pair with a polygon a box is the 4-gon (-hx,-hy), (hx,-hy), (hx,hy), (-hx,hy) with the exact normals (0,-1), (1,0), (0,1), (-1,0).
+// Vertices and normals are read through the record's pointer (memory under a run-time index) or formed by selects: no private array.
+__host__ __device__ __attribute__((always_inline)) inline bool is_polygon(const NpBody& b) { return b.kind == (unsigned)PHX_SHAPE_POLYGON; }
+__host__ __device__ __attribute__((always_inline)) inline int poly_count(const NpBody& b) { return is_polygon(b) ? b.poly->count : 4; }
+__host__ __device__ __attribute__((always_inline)) inline V2 poly_v(const NpBody& b, int k)
+{
+    if (is_polygon(b)) return v2(b.poly->v[2 * k], b.poly->v[2 * k + 1]);
+    return v2((k == 1 || k == 2) ? b.size.x : -b.size.x, k >= 2 ? b.size.y : -b.size.y);
+}
+__host__ __device__ __attribute__((always_inline)) inline V2 poly_n(const NpBody& b, int k)
+{
+    if (is_polygon(b)) return v2(b.poly->n[2 * k], b.poly->n[2 * k + 1]);
+    return v2(k == 1 ? 1.0f : (k == 3 ? -1.0f : 0.0f), k == 0 ? -1.0f : (k == 2 ? 1.0f : 0.0f));
+}
+__host__ __device__ __attribute__((always_inline)) inline V2 poly_wv(const NpBody& b, int k) { const V2 v = poly_v(b, k); return (b.pos + b.xv * v.x) + b.yv * v.y; }
+__host__ __device__ __attribute__((always_inline)) inline V2 poly_wn(const NpBody& b, int k) { const V2 n = poly_n(b, k); return b.xv * n.x + b.yv * n.y; }
+
+// one of two bodies by value, member by member: a reference chosen at run time and read inside a loop is a pointer into private memory,
+// which puts both bodies in scratch (Support, above)
+__host__ __device__ __attribute__((always_inline)) inline NpBody np_pick(bool first, const NpBody& a, const NpBody& b)
+{
+    NpBody r;
+    r.pos = v2(first ? a.pos.x : b.pos.x, first ? a.pos.y : b.pos.y); r.xv = v2(first ? a.xv.x : b.xv.x, first ? a.xv.y : b.xv.y);
+    r.yv = v2(first ? a.yv.x : b.yv.x, first ? a.yv.y : b.yv.y); r.size = v2(first ? a.size.x : b.size.x, first ? a.size.y : b.size.y);
+    r.kind = first ? a.kind : b.kind; r.poly = first ? a.poly : b.poly;
+    return r;
+}
+
+// the face of `a` of largest separation from `b`: s_i = min_j dot(NA_i, wB_j - wA_i), the largest s_i, the first on a tie
+struct FaceSep { float s; int i; };
+__host__ __device__ __attribute__((always_inline)) inline FaceSep poly_face_sep(const NpBody& a, const NpBody& b)
+{
+    FaceSep out;
+    out.s = 0.f; out.i = 0;
+    const int na = poly_count(a), nb = poly_count(b);
+    for (int i = 0; i < na; ++i) {
+        const V2 w = poly_wv(a, i), N = poly_wn(a, i);
+        float s = dot(N, poly_wv(b, 0) - w);
+        for (int j = 1; j < nb; ++j) { const float d = dot(N, poly_wv(b, j) - w); if (d < s) s = d; }
+        if (i == 0 || s > out.s) { out.s = s; out.i = i; }
+    }
+    return out;
+}
+
+// one side plane: the segment p0 p1 cut to d >= 0; false when nothing is left
+__host__ __device__ __attribute__((always_inline)) inline bool poly_clip(V2& p0, V2& p1, float d0, float d1)
+{
+    if (d0 < 0.0f && d1 < 0.0f) return false;
+    if (d0 < 0.0f) p0 = p0 + (p1 - p0) * (d0 / (d0 - d1));
+    else if (d1 < 0.0f) p1 = p1 + (p0 - p1) * (d1 / (d1 - d0));
+    return true;
+}
+
+// polygon / polygon and polygon / box (`b1`, `b2` in the manifold's order)
+__host__ __device__ __attribute__((always_inline)) inline void polygon_polygon_contact(const NpBody& b1, const NpBody& b2, Pts4& pts, int& count)
+{
+    const FaceSep fa = poly_face_sep(b1, b2);
+    if (fa.s > 0.0f) return;
+    const FaceSep fb = poly_face_sep(b2, b1);
+    if (fb.s > 0.0f) return;
+    const bool ref_first = !(fb.s > fa.s);
+    const NpBody R = np_pick(ref_first, b1, b2), I = np_pick(ref_first, b2, b1);
+    const int ri = ref_first ? fa.i : fb.i, nr = poly_count(R), ni = poly_count(I);
+    const V2 r0 = poly_wv(R, ri), r1 = poly_wv(R, ri + 1 < nr ? ri + 1 : 0), Nr = poly_wn(R, ri);
+    int inc = 0;
+    float least = dot(Nr, poly_wn(I, 0));
+    for (int j = 1; j < ni; ++j) { const float d = dot(Nr, poly_wn(I, j)); if (d < least) { least = d; inc = j; } }
+    V2 p0 = poly_wv(I, inc), p1 = poly_wv(I, inc + 1 < ni ? inc + 1 : 0);
+    const V2 e = r1 - r0;
+    if (!poly_clip(p0, p1, dot(p0 - r0, e), dot(p1 - r0, e))) return;
+    if (!poly_clip(p0, p1, dot(r1 - p0, e), dot(r1 - p1, e))) return;
+    const float s0 = dot(Nr, p0 - r0), s1 = dot(Nr, p1 - r0);
+    if (s0 <= 0.0f) { if (ref_first) merge_point(pts, count, p0 - Nr * s0, p0, -Nr, b1, b2); else merge_point(pts, count, p0, p0 - Nr * s0, Nr, b1, b2); }
+    if (s1 <= 0.0f) { if (ref_first) merge_point(pts, count, p1 - Nr * s1, p1, -Nr, b1, b2); else merge_point(pts, count, p1, p1 - Nr * s1, Nr, b1, b2); }
+}
+
+// the disc {c, r} against polygon (or 4-gon box) P: the building block, as disc_box_cand is for boxes
+__host__ __device__ __attribute__((always_inline)) inline Cand disc_polygon_cand(V2 c, float r, const NpBody& P, bool disc_first)
+{
+    const V2 g = c - P.pos;
+    const V2 p = v2(dot(g, P.xv), dot(g, P.yv));
+    const int n = poly_count(P);
+    int k = 0;
+    float s = dot(poly_n(P, 0), p - poly_v(P, 0));
+    for (int j = 1; j < n; ++j) { const float d = dot(poly_n(P, j), p - poly_v(P, j)); if (d > s) { s = d; k = j; } }
+    if (s > r) return cand_none();
+    const V2 vk = poly_v(P, k), nk = poly_n(P, k);
+    V2 Nl = nk, q = p - nk * s;
+    float depth = r - s;
+    if (s > 0.0f) {
+        const V2 vn = poly_v(P, k + 1 < n ? k + 1 : 0);
+        const V2 e = vn - vk;
+        const float t = dot(p - vk, e);
+        const bool lo = t < 0.0f, hi = !lo && t > dot(e, e);
+        if (lo || hi) {
+            q = lo ? vk : vn;
+            const V2 h = p - q;
+            const float l2 = dot(h, h);
+            if (l2 > r * r) return cand_none();
+            const float l = sqrtf(l2);
+            Nl = v2(h.x / l, h.y / l);
+            depth = r - l;
+        }
+    }
+    const V2 N = P.xv * Nl.x + P.yv * Nl.y;
+    const V2 on_poly = (P.pos + P.xv * q.x) + P.yv * q.y;
+    return cand_make(c - N * r, on_poly, N, depth, disc_first);
+}
+
+// capsule K against polygon P: candidate i of the stream: 0, 1 K's end discs against P; 2 + k P's vertex k as a disc of radius 0
+// against K, only if unclamped
+__host__ __device__ __attribute__((always_inline)) inline Cand capsule_polygon_cand(const NpBody& K, const NpBody& P, bool capsule_first, int i)
+{
+    if (i < 2) {
+        const float a = capsule_half(K);
+        return disc_polygon_cand(i == 0 ? K.pos - K.xv * a : K.pos + K.xv * a, K.size.y, P, capsule_first);
+    }
+    bool free_ = false;
+    Cand c = disc_capsule_cand(poly_wv(P, i - 2), 0.0f, K, !capsule_first, free_);
+    c.ok = c.ok && free_;
+    return c;
+}
+
+// capsule_select's rule, word for word, as a running selection over a stream of `n` candidates gen(i): the stream is walked twice and
+// nothing is kept but the two bests, in named registers
+template <class Gen>
+__host__ __device__ __attribute__((always_inline)) inline void select_stream(Gen gen, int n, Pts4& pts, int& count, const NpBody& b1, const NpBody& b2)
+{
+    Cand first = cand_none();
+    int fi = -1;
+    for (int i = 0; i < n; ++i) { const Cand c = gen(i); if (c.ok && (fi < 0 || c.depth > first.depth)) { first = c; fi = i; } }
+    if (fi < 0) return;
+    Cand second = cand_none();
+    int si = -1;
+    float sep = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        if (i == fi) continue;
+        const Cand c = gen(i);
+        if (!c.ok) continue;
+        const float s1 = sqlen(c.p1 - first.p1), s2 = sqlen(c.p2 - first.p2);
+        if (!(s1 > 2.0f * 2.0f && s2 > 2.0f * 2.0f)) continue;
+        if (si < 0 || s1 > sep) { second = c; sep = s1; si = i; }
+    }
+    merge_point(pts, count, first.p1, first.p2, first.n, b1, b2);
+    if (si >= 0) merge_point(pts, count, second.p1, second.p2, second.n, b1, b2);
+}
+
+// a pair with a polygon (`b1`, `b2` in the manifold's order)
+__host__ __device__ __attribute__((always_inline)) inline void polygon_contact(const NpBody& b1, const NpBody& b2, Pts4& pts, int& count)
+{
+    const unsigned CAPSULE = (unsigned)PHX_SHAPE_CAPSULE, CIRCLE = (unsigned)PHX_SHAPE_CIRCLE;
+    const bool poly_first = is_polygon(b1);
+    const NpBody P = np_pick(poly_first, b1, b2), O = np_pick(poly_first, b2, b1);      // (the other body: any kind; a polygon only when both are)
+    if (O.kind == CIRCLE) {
+        const Cand c = disc_polygon_cand(O.pos, O.size.x, P, !poly_first);
+        if (c.ok) merge_point(pts, count, c.p1, c.p2, c.n, b1, b2);
+    } else if (O.kind == CAPSULE) {
+        select_stream([&](int i) { return capsule_polygon_cand(O, P, !poly_first, i); }, 2 + poly_count(P), pts, count, b1, b2);
+    } else polygon_polygon_contact(b1, b2, pts, count);
+}
+
 // ref: Collider.cpp:211-245.  Returns true if a third merged point had to be dropped: the reference
 // would write it past the manifold's two slots (only an assert guards it).
 // The pair's kinds pick the routine in front of least_penetration_axis; a caller whose kinds are the constant PHX_SHAPE_BOX (a world
 // without a shape column) compiles to the box/box code alone.  CAPSULES: a kind may be PHX_SHAPE_CAPSULE (a world that made one);
-// without it every kind that is not a box is a circle and the capsule routines are not compiled in.
-template <bool CAPSULES = false>
+// without it every kind that is not a box is a circle and the capsule routines are not compiled in.  POLYGONS: a kind may be
+// PHX_SHAPE_POLYGON (a world that made one); a pair with one takes polygon_contact, every other pair the code above, unchanged.
+template <bool CAPSULES = false, bool POLYGONS = false>
 __host__ __device__ __attribute__((always_inline)) inline bool update_manifold(phx_manifold& m, const NpBody& b1, const NpBody& b2, phx_contact_point* pts)
 {
     Pts4 np;
@@ -418,7 +602,8 @@ __host__ __device__ __attribute__((always_inline)) inline bool update_manifold(p
     if (m.point_count > 0) { np.a = cp_load(pts[0]); np.a.flags &= 0xFFFF0000u; }      // isMerged = isNewlyCreated = false
     if (m.point_count > 1) { np.b = cp_load(pts[1]); np.b.flags &= 0xFFFF0000u; }
     int count = m.point_count;
-    if ((b1.kind | b2.kind) == 0u) {
+    if (POLYGONS && (is_polygon(b1) || is_polygon(b2))) polygon_contact(b1, b2, np, count);
+    else if ((b1.kind | b2.kind) == 0u) {
         V2 axis;
         if (least_penetration_axis(b1, b2, axis)) generate_contacts(b1, b2, np, count, axis);
     } else if (CAPSULES && (b1.kind == (unsigned)PHX_SHAPE_CAPSULE || b2.kind == (unsigned)PHX_SHAPE_CAPSULE)) capsule_contact(b1, b2, np, count);

@@ -61,10 +61,10 @@ private:
     int index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                    int64_t* total, Readback& rb, hipStream_t s);
     // (C: the kernels' capsule instantiations, for circle queries of a world in which a capsule was named)
-    template <int SHAPE, bool C>
+    template <int SHAPE, int C>
     int scan_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                      int64_t* total, Readback& rb, hipStream_t s);
-    template <int SHAPE, bool C>
+    template <int SHAPE, int C>
     int index_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                       int64_t* total, Readback& rb, hipStream_t s);
     template <int SHAPE, class Hit>

@@ -23,13 +23,15 @@ static void scan_in_chunks(int n, int count, Launch launch)
     for (int q0 = 0; q0 < count; q0 += Q_MAX_TILES * Q_TILE) launch(q0, dim3(stream_grid(n), std::min(div_up(count - q0, Q_TILE), Q_MAX_TILES)));
 }
 
-// f(std::bool_constant<CAPS>): the kernels' capsule instantiations for a world in which a capsule was named, the plain ones otherwise
+// f(std::integral_constant<int, CAPS>): the kernels' polygon instantiations (2) for a world in which a polygon was named, the capsule
+// instantiations (1) for one in which a capsule was, the plain ones (0) otherwise
 // (query_kernels.h q_kind).  A kernel that never reads the kinds (AABBs, oriented boxes, box casts) has the plain one alone.
 template <class F>
 static void q_caps(const WorldBodies& w, F f)
 {
-    if (w.capsules) f(std::true_type{});
-    else f(std::false_type{});
+    if (w.polys) f(std::integral_constant<int, 2>{});                       // (the polygon instantiations hold the capsule predicates too)
+    else if (w.capsules) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
 }
 
 int DeviceQuery::configure_from_env()
@@ -95,7 +97,7 @@ int DeviceQuery::points(const WorldBodies& w, int n, unsigned long long epoch, c
     if (n == 0 || choose(QUERY_POINTS, count) == PATH_SCAN) {
         PHX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), 0xFFFFFFFFu, (size_t)count, s));      // (-1: no body)
         if (n) q_caps(w, [&](auto caps) {
-            constexpr bool C = decltype(caps)::value;
+            constexpr int C = decltype(caps)::value;
             scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_points<C>), grid, dim3(256), 0, s, w, n, d_pts, count, q0, flags, out); });
         });
     } else {
@@ -123,7 +125,7 @@ int DeviceQuery::closest(const WorldBodies& w, int n, unsigned long long epoch, 
     const bool scan = n == 0 || choose(kind, count) == PATH_SCAN;
     if (!scan) PHX_TRY(ensure_index(w, n, epoch, s));
     q_caps(w, [&](auto caps) {
-        constexpr bool C = SHAPE != QSHAPE_BOX && decltype(caps)::value;      // (a box cast sees every body as its frame box)
+        constexpr int C = SHAPE != QSHAPE_BOX ? decltype(caps)::value : 0;      // (a box cast sees every body as its frame box)
         if (scan) {
             hipLaunchKernelGGL(k_qfill_u64, dim3(stream_grid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
             if (n) scan_in_chunks(n, count, [&](int q0, dim3 grid) { hipLaunchKernelGGL((k_qscan_rays<SHAPE, C>), grid, dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p); });
@@ -188,11 +190,12 @@ template <int SHAPE>
 int DeviceQuery::scan_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                            int64_t* total, Readback& rb, hipStream_t s)
 {
-    if (SHAPE == QSHAPE_DISC && w.capsules) return scan_aabb_as<SHAPE, SHAPE == QSHAPE_DISC>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
-    return scan_aabb_as<SHAPE, false>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    if (SHAPE == QSHAPE_DISC && w.polys) return scan_aabb_as<SHAPE, SHAPE == QSHAPE_DISC ? 2 : 0>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    if (SHAPE == QSHAPE_DISC && w.capsules) return scan_aabb_as<SHAPE, SHAPE == QSHAPE_DISC ? 1 : 0>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return scan_aabb_as<SHAPE, 0>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
 
-template <int SHAPE, bool C>
+template <int SHAPE, int C>
 int DeviceQuery::scan_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                               int64_t* total, Readback& rb, hipStream_t s)
 {
@@ -227,11 +230,12 @@ template <int SHAPE>
 int DeviceQuery::index_aabb(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                             int64_t* total, Readback& rb, hipStream_t s)
 {
-    if (SHAPE == QSHAPE_DISC && w.capsules) return index_aabb_as<SHAPE, SHAPE == QSHAPE_DISC>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
-    return index_aabb_as<SHAPE, false>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    if (SHAPE == QSHAPE_DISC && w.polys) return index_aabb_as<SHAPE, SHAPE == QSHAPE_DISC ? 2 : 0>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    if (SHAPE == QSHAPE_DISC && w.capsules) return index_aabb_as<SHAPE, SHAPE == QSHAPE_DISC ? 1 : 0>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
+    return index_aabb_as<SHAPE, 0>(w, n, d_boxes, count, flags, offsets, hits, hit_cap, total, rb, s);
 }
 
-template <int SHAPE, bool C>
+template <int SHAPE, int C>
 int DeviceQuery::index_aabb_as(const WorldBodies& w, int n, const float* d_boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap,
                                int64_t* total, Readback& rb, hipStream_t s)
 {

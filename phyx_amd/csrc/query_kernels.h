@@ -67,12 +67,49 @@ __device__ __forceinline__ bool q_circle(const uint32_t* __restrict__ kinds, int
 // (WorldBodies::capsules; query.hip q_caps).  Without it a kind is 0 or 1, q_circle's answer, and no capsule predicate is compiled in: a
 // world of boxes and circles runs the code it always ran.  A capsule's core segment runs along the frame's x from -a to a, a = h.x - h.y,
 // its radius is h.y.  Oriented boxes and box casts see a capsule as its frame box {h.x, h.y}, as they see a circle as its frame square.
-template <bool CAPS>
+template <int CAPS>
 __device__ __forceinline__ unsigned q_kind(const uint32_t* __restrict__ kinds, int i)
 {
     if (CAPS) return kinds ? kinds[i] : (unsigned)PHX_SHAPE_BOX;
     return q_circle(kinds, i) ? 1u : 0u;
 }
+// Polygons (include/phyx_amd.h POLYGONS): a third instantiation, CAPS == 2, which a world launches once some call has named a polygon
+// (WorldBodies::polys).  It holds the capsule predicates too.  Points and rays see the polygon's true outline; query circles, circle casts,
+// oriented boxes and box casts see its frame box: wherever a rule says "a kind that is not a box" a polygon takes the box's arm.
+template <int CAPS>
+__device__ __forceinline__ const PolyRec* q_poly(const WorldBodies& w, int i) { return CAPS == 2 ? w.polys + i : nullptr; }
+
+__device__ __forceinline__ bool q_point_in_polygon(float4 a, float4 m, float4 f, const PolyRec* __restrict__ poly, float px, float py)
+{
+    if (!(a.x <= px && a.z >= px && a.y <= py && a.w >= py)) return false;
+    const float dx = px - m.z, dy = py - m.w;
+    const float u = dx * f.x + dy * f.y, v = dx * f.z + dy * f.w;
+    const int n = poly->count;
+    bool in = true;
+    for (int k = 0; k < n; ++k) in = in && poly->n[2 * k] * (u - poly->v[2 * k]) + poly->n[2 * k + 1] * (v - poly->v[2 * k + 1]) <= 0.f;
+    return in;
+}
+
+// the ray against the polygon's half planes in the body's frame (after the candidate test); `edge`: the entering edge, -1 if none entered
+__device__ __forceinline__ bool q_ray_polygon(const QRay& r, float4 m, float4 f, const PolyRec* __restrict__ poly, float& tin, int& edge)
+{
+    const float rx = r.ox - m.z, ry = r.oy - m.w;
+    const float oxp = rx * f.x + ry * f.y, oyp = rx * f.z + ry * f.w;
+    const float dxp = r.dx * f.x + r.dy * f.y, dyp = r.dx * f.z + r.dy * f.w;
+    const int n = poly->count;
+    float tout = INFINITY;
+    bool miss = false;
+    tin = -INFINITY; edge = -1;
+    for (int k = 0; k < n; ++k) {
+        const float nx = poly->n[2 * k], ny = poly->n[2 * k + 1];
+        const float den = nx * dxp + ny * dyp, num = nx * (poly->v[2 * k] - oxp) + ny * (poly->v[2 * k + 1] - oyp);
+        if (den < 0.f) { const float t = num / den; if (t > tin) { tin = t; edge = k; } }
+        else if (den > 0.f) { const float t = num / den; if (t < tout) tout = t; }
+        else if (num < 0.f) miss = true;
+    }
+    return !miss && tin <= tout && tout >= 0.f && tin <= r.max_t;
+}
+
 __device__ __forceinline__ float q_clamp(float u, float a) { return u < -a ? -a : (u > a ? a : u); }
 
 __device__ __forceinline__ bool q_point_in_capsule(float4 a, float4 m, float4 f, float2 h, float px, float py)
@@ -91,9 +128,10 @@ __device__ __forceinline__ bool q_point_in_circle(float4 a, float4 m, float r, f
     return dx * dx + dy * dy <= r * r;
 }
 
-template <bool CAPS>
-__device__ __forceinline__ bool q_point_in_body(unsigned kind, float4 a, float4 m, float4 f, float2 h, float px, float py)
+template <int CAPS>
+__device__ __forceinline__ bool q_point_in_body(unsigned kind, float4 a, float4 m, float4 f, float2 h, float px, float py, const PolyRec* poly)
 {
+    if (CAPS == 2 && kind == (unsigned)PHX_SHAPE_POLYGON) return q_point_in_polygon(a, m, f, poly, px, py);
     if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) return q_point_in_capsule(a, m, f, h, px, py);
     return kind != 0u ? q_point_in_circle(a, m, h.x, px, py) : q_point_in_box(a, m, f, h, px, py);
 }
@@ -211,9 +249,10 @@ __device__ __forceinline__ float2 q_capsule_normal(const QCastDisc& cd, float4 f
 }
 
 // the ray against body b's own shape (after the candidate test): tin alone
-template <bool CAPS>
-__device__ __forceinline__ bool q_ray_body(unsigned kind, const QRay& r, float4 m, float4 f, float2 h, float& tin)
+template <int CAPS>
+__device__ __forceinline__ bool q_ray_body(unsigned kind, const QRay& r, float4 m, float4 f, float2 h, float& tin, const PolyRec* poly)
 {
+    if (CAPS == 2 && kind == (unsigned)PHX_SHAPE_POLYGON) { int edge; return q_ray_polygon(r, m, f, poly, tin, edge); }
     if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
         QCastDisc cd;
         const bool hit = q_ray_capsule(r.ox - m.z, r.oy - m.w, r.dx, r.dy, r.max_t, f, h.x - h.y, h.y, cd);
@@ -305,9 +344,10 @@ __device__ __forceinline__ bool q_disc_near(const QDisc& c, float4 a)
 }
 
 // the circle against body b's own shape: the centre's offset from the closest point of the box, or the two radii's sum
-template <bool CAPS>
+template <int CAPS>
 __device__ __forceinline__ bool q_disc_overlap(const QDisc& c, float4 a, unsigned kind, float4 m, float4 f, float2 h)
 {
+    if (CAPS == 2 && kind == (unsigned)PHX_SHAPE_POLYGON) kind = 0u;      // (a polygon is its frame box here)
     if (!q_disc_near(c, a)) return false;
     const float ex = c.cx - m.z, ey = c.cy - m.w;
     if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
@@ -333,9 +373,10 @@ __device__ __forceinline__ bool q_cast_aabb(const QDiscCast& c, float4 a)
 // the centre's ray against the body widened by the radius (after the candidate test): a circle body is the disc of radius r + rb, a
 // capsule body the capsule of radius r + rb (q_ray_capsule); a box is the union of six convex parts, each met by its own rule, and the earliest entry wins (the first part in order on a tie).
 // Every part is evaluated and the winner kept by selects on named values: no run-time-indexed array (narrowphase.h).
-template <bool CAPS>
+template <int CAPS>
 __device__ __forceinline__ bool q_cast_disc(const QDiscCast& c, unsigned kind, float4 m, float4 f, float2 h, QCastDisc& out)
 {
+    if (CAPS == 2 && kind == (unsigned)PHX_SHAPE_POLYGON) kind = 0u;      // (a polygon is its frame box here)
     out.tin = 0.f; out.part = 0; out.ox = 0.f; out.oy = 0.f; out.dxp = 0.f; out.dyp = 0.f; out.nx = 0.f; out.ny = 0.f;
     const float rx = c.c.cx - m.z, ry = c.c.cy - m.w;
     if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) return q_ray_capsule(rx, ry, c.dx, c.dy, c.max_t, f, h.x - h.y, c.c.r + h.y, out);
@@ -445,7 +486,7 @@ static __global__ void __launch_bounds__(256) k_qfill_u64(unsigned long long* __
 }
 
 // the ray results from the winners' keys: the winner's test is made again, by the same code, for its normal
-template <bool CAPS>
+template <int CAPS>
 static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const float* __restrict__ rays, int count,
                                                             const unsigned long long* __restrict__ keys, phx_ray_hit* __restrict__ out)
 {
@@ -460,7 +501,16 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
             const float2 sz = w.size[b];
             float t;
             const unsigned kind = q_kind<CAPS>(w.kinds, b);
-            if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
+            if (CAPS == 2 && kind == (unsigned)PHX_SHAPE_POLYGON) {
+                const PolyRec* poly = q_poly<CAPS>(w, b);
+                float tin; int edge;
+                (void)q_ray_polygon(r, m, f, poly, tin, edge);
+                t = tin > 0.f ? tin : 0.f;
+                if (!(tin < 0.f) && edge >= 0) {
+                    const float nx = poly->n[2 * edge], ny = poly->n[2 * edge + 1];
+                    h.normal.x = f.x * nx + f.z * ny; h.normal.y = f.y * nx + f.w * ny;
+                }
+            } else if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
                 QCastDisc cd;
                 (void)q_ray_capsule(r.ox - m.z, r.oy - m.w, r.dx, r.dy, r.max_t, f, sz.x - sz.y, sz.y, cd);
                 t = cd.tin > 0.f ? cd.tin : 0.f;
@@ -489,7 +539,7 @@ static __global__ void __launch_bounds__(256) k_qray_finish(WorldBodies w, const
 }
 
 // the cast results from the winners' keys, as k_qray_finish (SHAPE: QSHAPE_BOX box casts, QSHAPE_DISC circle casts)
-template <int SHAPE, bool CAPS>
+template <int SHAPE, int CAPS>
 static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, const float* __restrict__ casts, int count,
                                                              const unsigned long long* __restrict__ keys, phx_shape_hit* __restrict__ out)
 {
@@ -541,7 +591,7 @@ static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, cons
 
 // ---- scan path --------------------------------------------------------------------------------------------------------------------
 // blockIdx.y = the tile of queries [q0, q0 + Q_TILE); bodies grid-strided in lanes.  out: 0xFFFFFFFF (= -1) where nothing was found.
-template <bool CAPS>
+template <int CAPS>
 static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int n, const float* __restrict__ pts, int count, int q0, int flags,
                                                              unsigned* __restrict__ out)
 {
@@ -565,7 +615,7 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
         const unsigned round = live ? q_kind<CAPS>(w.kinds, i) : 0u;
         for (int q = 0; q < nq; ++q) {
             const float2 p = qp[q];
-            const bool hit = any && qok[q] && q_point_in_body<CAPS>(round, a, m, f, h, p.x, p.y);
+            const bool hit = any && qok[q] && q_point_in_body<CAPS>(round, a, m, f, h, p.x, p.y, q_poly<CAPS>(w, i));
             const unsigned long long mask = __ballot(hit);
             if (mask && (int)(threadIdx.x & 63) == __builtin_ctzll(mask)) atomicMin(&out[base_q + q], (unsigned)i);      // (the lowest lane holds the lowest body)
         }
@@ -573,7 +623,7 @@ static __global__ void __launch_bounds__(256) k_qscan_points(WorldBodies w, int 
 }
 
 // SHAPE: rays (5 floats per query), box casts (11) or circle casts (6)
-template <int SHAPE, bool CAPS>
+template <int SHAPE, int CAPS>
 static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n, const float* __restrict__ rays, int count, int q0, int flags,
                                                            unsigned long long* __restrict__ keys)
 {
@@ -626,7 +676,7 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
             } else {
                 const QRay r = qr[q];
                 float t0 = 0.f;
-                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_body<CAPS>(round, r, m, f, h, t0);
+                hit = any && qok[q] && q_ray_aabb(r, a) && q_ray_body<CAPS>(round, r, m, f, h, t0, q_poly<CAPS>(w, i));
                 tin = hit ? t0 : 0.f;
             }
             if (!__ballot(hit)) continue;
@@ -643,7 +693,7 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
 //   QS_RECOUNT  the table alone (a later chunk of queries counted again: the table holds one chunk);
 //   QS_FILL     writes the hits at base + table[...] + rank.
 enum { QS_COUNT = 0, QS_RECOUNT = 1, QS_FILL = 2 };
-template <int MODE, int SHAPE, bool CAPS>
+template <int MODE, int SHAPE, int CAPS>
 static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n, const float* __restrict__ boxes, int count, int q0, int flags, int bblocks,
                                                            unsigned* __restrict__ table, unsigned* __restrict__ qcount, unsigned base, int* __restrict__ hits)
 {
@@ -796,7 +846,7 @@ enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COU
 //   QK_DISC_COUNT, QK_DISC_FILL, QK_DISC_CAST   the same three for circles
 // A lane tests a child's bounds with the query's AABB conjunct: the bounds widened by the box's extents or the circle's radius for the
 // last six kinds.
-template <int KIND, bool CAPS>
+template <int KIND, int CAPS>
 static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, const float* __restrict__ queries, int count, int flags,
                                                       unsigned* __restrict__ out_u32, unsigned long long* __restrict__ out_key,
                                                       const unsigned* __restrict__ seg, int* __restrict__ hits)
@@ -860,10 +910,10 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                         b = (int)t.perm[c];
                         const float4 a = w.aabb[b], m = w.s.mpos[b];
                         if (!(skip && q_static(m, w.sleep, b))) {
-                            if (KIND == QK_POINT) hit = q_point_in_body<CAPS>(q_kind<CAPS>(w.kinds, b), a, m, w.frame[b], w.size[b], qbox.x, qbox.y);
+                            if (KIND == QK_POINT) hit = q_point_in_body<CAPS>(q_kind<CAPS>(w.kinds, b), a, m, w.frame[b], w.size[b], qbox.x, qbox.y, q_poly<CAPS>(w, b));
                             else if (KIND == QK_RAY) {
                                 float t0 = 0.f;
-                                hit = q_ray_aabb(r, a) && q_ray_body<CAPS>(q_kind<CAPS>(w.kinds, b), r, m, w.frame[b], w.size[b], t0);
+                                hit = q_ray_aabb(r, a) && q_ray_body<CAPS>(q_kind<CAPS>(w.kinds, b), r, m, w.frame[b], w.size[b], t0, q_poly<CAPS>(w, b));
                                 if (hit) { const unsigned long long k = q_ray_key(t0, b); best_key = k < best_key ? k : best_key; }
                             } else if (KIND == QK_CAST) {
                                 QCastBox cb;

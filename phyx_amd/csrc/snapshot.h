@@ -92,6 +92,27 @@ public:
         return PHX_OK;
     }
     int shape_count() const { return shape_count_; }
+    // the polygon records (POLYGONS) ride the same way: 33 words per body of a world whose polygon column was active, with its
+    // "a polygon was named" bit
+    static constexpr size_t POLY_WORDS = 33;
+    int reserve_polygons(int n, hipStream_t stream) { return n ? polygons_.reserve_keep((size_t)n * POLY_WORDS, (size_t)polygon_count_ * POLY_WORDS, stream) : PHX_OK; }
+    int save_polygons(const void* d_src, int count, bool named, hipStream_t stream)
+    {
+        polygon_count_ = count; polygons_named_ = count && named;
+        if (!count) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(polygons_.p, d_src, (size_t)count * POLY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
+        return PHX_OK;
+    }
+    int load_polygons(void* d_dst, hipStream_t stream)                      // (queued behind Snapshot::load on the same stream)
+    {
+        if (!polygon_count_) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(d_dst, polygons_.p, (size_t)polygon_count_ * POLY_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(loaded_, stream));
+        return PHX_OK;
+    }
+    int polygon_count() const { return polygon_count_; }
+    bool polygons_named() const { return polygons_named_; }
     bool shape_capsules() const { return shape_capsules_; }
     int blob_bytes(size_t* bytes);
     int export_blob(void* blob, size_t cap);
@@ -115,6 +136,7 @@ private:
     template <class P> Riders<P>& riders() { return std::get<Riders<P>>(riders_); }
     DevBuf<uint2> exclusions_; int exclusion_count_ = 0;
     DevBuf<uint32_t> shapes_; int shape_count_ = 0; bool shape_capsules_ = false;
+    DevBuf<uint32_t> polygons_; int polygon_count_ = 0; bool polygons_named_ = false;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

@@ -57,7 +57,7 @@ int Snapshot::refuse_pins(const char* what)
         std::vector<uint32_t> kinds((size_t)shape_count_);
         PHX_HIP(hipMemcpy(kinds.data(), shapes_.p, kinds.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         for (const uint32_t k : kinds) count += k != (uint32_t)PHX_SHAPE_BOX;
-        plural = "circles or capsules";
+        plural = "circles, capsules or polygons";
     }
     if (!count) return PHX_OK;
     set_error("%s: the snapshot holds %d %s, which the blob (layout version 1) does not carry", what, count, plural);
@@ -164,6 +164,7 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     std::apply([](auto&... r) { ((r.count = 0), ...); }, riders_);
     exclusion_count_ = 0;
     shape_count_ = 0; shape_capsules_ = false;
+    polygon_count_ = 0; polygons_named_ = false;
     return PHX_OK;
 }
 

@@ -274,6 +274,11 @@ public:
     // shapes (phx_world_set_shapes / get_shapes): between steps; the kind and the half extents of a body, the AABB recomputed
     int set_shapes(const int32_t* bodies, const phx_shape* shapes, int count);
     int get_shapes(phx_shape* out, int cap);
+    // polygons (phx_world_set_polygons / get_polygons): the fourth kind; the record, the frame box and the AABB
+    int set_polygons(const int32_t* bodies, const phx_polygon* polygons, int count);
+    int get_polygons(const int32_t* bodies, phx_polygon* out, int count);
+    int queue_shapes(const int32_t* bodies, const phx_shape* shapes, int count, bool kinds);
+    int queue_polygons(const int32_t* bodies, const phx_polygon* polygons, int count);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
     // units: pins, links, angles and sliders, `P` = phx_pin, phx_link, phx_angle or phx_slider (phx_world_add_pins ... phx_world_get_sliders, phx_world_get_pin_schedule): between
     // steps; solved at the end of pre_solve (pins.h)
@@ -326,7 +331,7 @@ private:
     int sync_bodies_to_device();
     int refresh_records();               // resident arrays -> the 128-byte records (getters)
     WorldBodies resident() const { return bodies_.view(); }
-    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); w.kinds = shapes_.ptr(); w.capsules = capsules() ? 1u : 0u; return w; }      // (to a query a sleeper is not static, and a circle is a disc)
+    WorldBodies query_view() const { WorldBodies w = bodies_.view(); w.sleep = sleep_col_.ptr(); w.kinds = shapes_.ptr(); w.capsules = capsules() ? 1u : 0u; w.polys = polygons() ? polys_.ptr() : nullptr; return w; }      // (to a query a sleeper is not static, and a circle is a disc)
     bool host_staged() const { return bodies_dirty_ || !bodies_.records.p; }      // the host-staged records are the world
     int restage_on_host();               // ... again, after the device copy was: records and tables come down
     int refuse_mid_step(const char* what) const;      // PHX_ERR_STATE between pre_solve / step_begin and finish_step / step_end
@@ -451,6 +456,12 @@ private:
     BodyTable<ShapeColumn> shapes_;
     bool capsules_ = false;
     bool capsules() const { return capsules_ && shapes_.active; }
+    // ... and the polygon records (include/phyx_amd.h POLYGONS): active once some set_polygons call named a polygon.  polygons_: the bit
+    // that call sets and set_state clears (a load takes the saved world's); with both tables active it picks the BodyPolygons
+    // instantiation and the queries' polygon instantiations
+    BodyTable<PolygonColumn> polys_;
+    bool polygons_ = false;
+    bool polygons() const { return polygons_ && shapes_.active && polys_.active; }
     DeviceSleep sleep_;
     bool sleep_count_pending_ = false;   // the pass or a wake may have changed the static set: the device's count has not been looked at yet
     DevBuf<phx_sleep_state> sleep_out_;
@@ -462,7 +473,7 @@ private:
     template <class P> int wake_units(const int32_t* which, int count);      // both bodies of the listed units
     void take_sleep_count(unsigned changed);      // what set_inverse_masses does when the static set changed
     int settle_sleep_count();            // ... by a readback of its own, where no step's count readback has brought it yet
-    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); PHX_TRY(f(sleep_col_)); return f(shapes_); }
+    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); PHX_TRY(f(sleep_col_)); PHX_TRY(f(shapes_)); return f(polys_); }
     // the three setters' skeleton: `rule(k)` is the call's own check of entry k
     template <class Column, class Rule>
     int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
@@ -477,8 +488,8 @@ private:
     int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2);
     // an edit of Fields::width floats per listed unit (already checked): staged for the scatter kernel when the list is on the device
     template <class P, class Fields> int set_unit_fields(const int32_t* which, const float* values, int count);
-    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr(), shapes_.ptr()}; }
-    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr(), shapes_.spare_ptr()}; }
+    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr(), shapes_.ptr(), polys_.ptr()}; }
+    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr(), shapes_.spare_ptr(), polys_.spare_ptr()}; }
 };
 
 } // namespace phx

@@ -206,7 +206,10 @@ int World::scratch_for(int n)
 void World::queue_update_manifolds(int first, int nm_old, const uint2* new_pairs, const MailRide& ride)
 {
     const uint32_t* const kinds = shapes_.ptr();
-    if (kinds && capsules()) hipLaunchKernelGGL(k_update_manifolds<BodyCapsules>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
+    // (the fourth, with the polygon routines and the polygon column, once some call has named a polygon)
+    if (kinds && polygons()) hipLaunchKernelGGL(k_update_manifolds<BodyPolygons>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
+                                                reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, BodyPolygons{kinds, polys_.ptr()});
+    else if (kinds && capsules())hipLaunchKernelGGL(k_update_manifolds<BodyCapsules>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
                                                 reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, BodyCapsules{kinds});
     else if (kinds) hipLaunchKernelGGL(k_update_manifolds<BodyShapes>, dim3(wgrid(nm - first)), dim3(256), 0, stream_, d_manifolds_.p, nm, resident(), d_cps_.p, pack_flags_.p,
                                   reinterpret_cast<int*>(counters_.p + 3), nm_old, new_pairs, first, counters_.p + 2, ride, BodyShapes{kinds});

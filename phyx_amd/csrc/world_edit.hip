@@ -497,7 +497,7 @@ int World::set_shapes(const int32_t* bodies, const phx_shape* shapes, int count)
     bool circle = false, capsule = false;                                   // (`circle`: some entry is not a box)
     for (int k = 0; k < count; ++k) {                                       // (NaN fails the comparisons)
         const phx_shape& s = shapes[k];
-        if (s.kind != PHX_SHAPE_BOX && s.kind != PHX_SHAPE_CIRCLE && s.kind != PHX_SHAPE_CAPSULE) { set_error("%s: kind %d of body %d is none of PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE, PHX_SHAPE_CAPSULE", what, s.kind, bodies[k]); return PHX_ERR_INVALID; }
+        if (s.kind != PHX_SHAPE_BOX && s.kind != PHX_SHAPE_CIRCLE && s.kind != PHX_SHAPE_CAPSULE) { set_error("%s: kind %d of body %d is none of PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE, PHX_SHAPE_CAPSULE (a polygon is made by phx_world_set_polygons)", what, s.kind, bodies[k]); return PHX_ERR_INVALID; }
         if (!(std::isfinite(s.hx) && std::isfinite(s.hy) && s.hx > 0.f && s.hy > 0.f)) { set_error("%s: the size {%g, %g} of body %d is not finite and positive", what, (double)s.hx, (double)s.hy, bodies[k]); return PHX_ERR_INVALID; }
         if (s.kind == PHX_SHAPE_CIRCLE && s.hy != s.hx) { set_error("%s: body %d is a circle and hy %g is not its radius hx %g", what, bodies[k], (double)s.hy, (double)s.hx); return PHX_ERR_INVALID; }
         if (s.kind == PHX_SHAPE_CAPSULE && !(s.hx > s.hy)) { set_error("%s: body %d is a capsule and hx %g is not above its radius hy %g (hx == hy: use PHX_SHAPE_CIRCLE)", what, bodies[k], (double)s.hx, (double)s.hy); return PHX_ERR_INVALID; }
@@ -516,15 +516,105 @@ int World::set_shapes(const int32_t* bodies, const phx_shape* shapes, int count)
             update_geom(b);
         }
         if (kinds) shapes_.set_host(bodies, shapes, count, n);              // (the table goes up with the bodies)
+        if (polys_.active) { const std::vector<phx_polygon> none((size_t)count); polys_.set_host(bodies, none.data(), count, n); }      // (a polygon named here is one no longer)
         return PHX_OK;
     }
     PHX_TRY(settle_and_upload());                                           // (an unverified solve is settled before the geometry changes)
+    PHX_TRY(queue_shapes(bodies, shapes, count, kinds));
+    if (polys_.active) { const std::vector<phx_polygon> none((size_t)count); PHX_TRY(queue_polygons(bodies, none.data(), count)); }
+    return PHX_OK;
+}
+
+// the device path of set_shapes and set_polygons: the batch staged and scattered behind whatever the stream holds
+int World::queue_shapes(const int32_t* bodies, const phx_shape* shapes, int count, bool kinds)
+{
     const int* d_bodies = nullptr; const float* d_values = nullptr;
     PHX_TRY(stage_.indexed(bodies, reinterpret_cast<const float*>(shapes), count, (int)(sizeof(phx_shape) / sizeof(float)), stream_, &d_bodies, &d_values));
-    if (kinds) PHX_TRY(shapes_.set_device(d_bodies, d_values, count, n, stream_));
+    if (kinds) PHX_TRY(shapes_.set_device(d_bodies, d_values, count, nb(), stream_));
     hipLaunchKernelGGL(k_set_shapes, dim3(wgrid(count)), dim3(256), 0, stream_, d_bodies, reinterpret_cast<const phx_shape*>(d_values), count, resident(), bodies_.records.p);
     PHX_HIP(hipGetLastError());
     ++geom_epoch_;                                                          // (the query index was built on the old AABBs)
+    return PHX_OK;
+}
+int World::queue_polygons(const int32_t* bodies, const phx_polygon* polygons, int count)
+{
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_.indexed(bodies, reinterpret_cast<const float*>(polygons), count, (int)(sizeof(phx_polygon) / sizeof(float)), stream_, &d_bodies, &d_values));
+    return polys_.set_device(d_bodies, d_values, count, nb(), stream_);
+}
+
+// ---- polygons -----------------------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h POLYGONS.  Validity in fp32, by the expressions tests/polygon_spec.py poly_valid states; then the call is
+// set_shapes of {PHX_SHAPE_POLYGON, the frame box} and a write of the polygon column, whose stored value (the normals) is formed by
+// poly_record on either path.
+static const char* polygon_fault(const phx_polygon& p)
+{
+    if (p.count < 3 || p.count > PHX_POLYGON_MAX_VERTICES) return "its vertex count is not in 3 .. 8";
+    for (int k = 0; k < p.count; ++k)
+        if (!(std::isfinite(p.v[k].x) && std::isfinite(p.v[k].y))) return "a coordinate is not finite";
+    const PolyRec r = poly_record(p);
+    for (int k = 0; k < p.count; ++k) {
+        const int k1 = k + 1 < p.count ? k + 1 : 0, k2 = k1 + 1 < p.count ? k1 + 1 : 0;
+        const V2 e0 = v2(p.v[k1]) - v2(p.v[k]), e1 = v2(p.v[k2]) - v2(p.v[k1]);
+        if (!(e0.x * e1.y - e0.y * e1.x > 0.0f)) return "it is not strictly convex and counter-clockwise";
+        if (!(dot(v2(r.n[2 * k], r.n[2 * k + 1]), v2(p.v[k])) > 0.0f)) return "the origin is not strictly inside";
+    }
+    return nullptr;
+}
+
+int World::set_polygons(const int32_t* bodies, const phx_polygon* polygons, int count)
+{
+    static const char* const what = "phx_world_set_polygons";
+    PHX_TRY(refuse_sharded(what, "polygons"));
+    PHX_TRY(check_batch(what, bodies, polygons, count, true));
+    std::vector<phx_polygon> clean((size_t)count);                          // (unused slots are stored as +0)
+    std::vector<phx_shape> frame((size_t)count);
+    for (int k = 0; k < count; ++k) {
+        if (const char* bad = polygon_fault(polygons[k])) { set_error("%s: the polygon of body %d is refused: %s", what, bodies[k], bad); return PHX_ERR_INVALID; }
+        phx_polygon& c = clean[(size_t)k];
+        c = phx_polygon{};
+        c.count = polygons[k].count;
+        float hx = 0.f, hy = 0.f;
+        for (int j = 0; j < c.count; ++j) {
+            c.v[j] = polygons[k].v[j];
+            hx = fabsf(c.v[j].x) > hx ? fabsf(c.v[j].x) : hx; hy = fabsf(c.v[j].y) > hy ? fabsf(c.v[j].y) : hy;
+        }
+        frame[(size_t)k] = phx_shape{PHX_SHAPE_POLYGON, hx, hy};
+    }
+    if (!count) return PHX_OK;
+    capsules_ = capsules_ && shapes_.active;                                // (a column that went away took the bits with it)
+    polygons_ = true;
+    PHX_TRY(wake_named(bodies, count));
+    const int n = nb();
+    if (host_staged()) {                                    // the host-staged records are the world: write into them
+        for (int k = 0; k < count; ++k) {
+            phx_rigid_body& b = host_bodies_[(size_t)bodies[k]];
+            b.geom_size.x = frame[(size_t)k].hx; b.geom_size.y = frame[(size_t)k].hy;
+            update_geom(b);
+        }
+        shapes_.set_host(bodies, frame.data(), count, n);
+        polys_.set_host(bodies, clean.data(), count, n);
+        return PHX_OK;
+    }
+    PHX_TRY(settle_and_upload());
+    PHX_TRY(queue_shapes(bodies, frame.data(), count, true));
+    return queue_polygons(bodies, clean.data(), count);
+}
+
+// the listed bodies' polygons in the C ABI's form (count 0 and zeros for a body that is none)
+int World::get_polygons(const int32_t* bodies, phx_polygon* out, int count)
+{
+    static const char* const what = "phx_world_get_polygons";
+    PHX_TRY(refuse_mid_step(what));
+    if (count < 0) { set_error("%s: negative count %d", what, count); return PHX_ERR_INVALID; }
+    if (count && (!bodies || !out)) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    const int n = nb();
+    for (int k = 0; k < count; ++k)
+        if (bodies[k] < 0 || bodies[k] >= n) { set_error("%s: body index %d out of range [0, %d)", what, bodies[k], n); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    std::vector<phx_polygon> all((size_t)n);
+    PHX_TRY(polys_.visit(n, host_staged(), device_, rb_, stream_, [&](int i, const PolyRec& v) { all[(size_t)i] = PolygonColumn::shown(v); }));
+    for (int k = 0; k < count; ++k) out[k] = all[(size_t)bodies[k]];
     return PHX_OK;
 }
 

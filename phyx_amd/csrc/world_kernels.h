@@ -146,12 +146,28 @@ struct FlagsColumn {                   // include/phyx_amd.h BODY FLAGS / SENSOR
 struct ShapeColumn {                   // include/phyx_amd.h SHAPES; the rule: narrowphase.h update_manifold, query_kernels.h
     using value = uint32_t;            // PHX_SHAPE_BOX, PHX_SHAPE_CIRCLE or PHX_SHAPE_CAPSULE (the size lives where it always did: the records and size[])
     using api = phx_shape;
-    static constexpr const char* plural = "circles or capsules";
+    static constexpr const char* plural = "circles, capsules or polygons";
     static __host__ __device__ value initial() { return (uint32_t)PHX_SHAPE_BOX; }
     static __host__ __device__ value stored(const api& s) { return (uint32_t)s.kind; }
     static bool is_initial(const value& v) { return v == (uint32_t)PHX_SHAPE_BOX; }
     // (no `shown`: the getter joins the kind with the size, World::get_shapes)
 };
+struct PolygonColumn {                 // include/phyx_amd.h POLYGONS; the rule: narrowphase.h polygon_contact, query_kernels.h
+    using value = PolyRec;             // {count, v[8], n[8]}: 132 B per body, paid only once some call named a polygon; count 0: not a polygon
+    using api = phx_polygon;
+    static constexpr const char* plural = "polygons";
+    static __host__ __device__ value initial() { phx_polygon none = {}; return poly_record(none); }
+    static __host__ __device__ value stored(const api& p) { return poly_record(p); }
+    static api shown(const value& v)
+    {
+        api p = {};
+        p.count = v.count;
+        for (int k = 0; k < v.count; ++k) { p.v[k].x = v.v[2 * k]; p.v[k].y = v.v[2 * k + 1]; }
+        return p;
+    }
+    static bool is_initial(const value& v) { return v.count == 0; }
+};
+static_assert(sizeof(phx_polygon) == 17 * sizeof(float), "a batch is staged as 4-byte words");
 static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float) && sizeof(uint32_t) == sizeof(float) &&
               sizeof(phx_shape) == 3 * sizeof(float), "a batch is staged as 4-byte words");
 
@@ -197,6 +213,7 @@ struct BodyColumns {
     uint32_t* flags;
     SleepCell* sleep;
     uint32_t* shapes;
+    PolyRec* polygons;
 };
 
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
@@ -231,6 +248,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         if (cols.flags) cols.flags[i] = FlagsColumn::initial();
         if (cols.sleep) cols.sleep[i] = SleepColumn::initial();      // (awake, timer 0)
         if (cols.shapes) cols.shapes[i] = ShapeColumn::initial();    // (a box)
+        if (cols.polygons) cols.polygons[i] = PolygonColumn::initial();
     }
 }
 
@@ -312,20 +330,31 @@ static __global__ void __launch_bounds__(256) k_x_extent(WorldBodies w, int n, u
 // The bodies' kinds (include/phyx_amd.h SHAPES) are a parameter of UpdateManifolds' kernel: AllBoxes (a world without an active shape
 // column) gives the constant PHX_SHAPE_BOX, so update_manifold's dispatch folds away and the kernel is the box/box code it always was;
 // BodyShapes reads one 4-byte word per body and knows boxes and circles; BodyCapsules (a world in which some call named a capsule) reads
-// the same word and compiles the capsule routines in, so that they cost a circle world no register.
+// the same word and compiles the capsule routines in, so that they cost a circle world no register; BodyPolygons (a world in which some
+// call named a polygon) carries the polygon column's pointer too and is the only one in which NpBody::poly is set or read.
 struct AllBoxes {
-    static constexpr bool capsules = false;
+    static constexpr bool capsules = false, polygons = false;
     __device__ unsigned operator()(int) const { return (unsigned)PHX_SHAPE_BOX; }
+    __device__ const PolyRec* poly(int) const { return nullptr; }
 };
 struct BodyShapes {
-    static constexpr bool capsules = false;
+    static constexpr bool capsules = false, polygons = false;
     const uint32_t* kind;              // per body (ShapeColumn)
     __device__ unsigned operator()(int i) const { return kind[i]; }
+    __device__ const PolyRec* poly(int) const { return nullptr; }
 };
 struct BodyCapsules {
-    static constexpr bool capsules = true;
+    static constexpr bool capsules = true, polygons = false;
     const uint32_t* kind;
     __device__ unsigned operator()(int i) const { return kind[i]; }
+    __device__ const PolyRec* poly(int) const { return nullptr; }
+};
+struct BodyPolygons {
+    static constexpr bool capsules = true, polygons = true;
+    const uint32_t* kind;
+    const PolyRec* polys;              // per body (PolygonColumn)
+    __device__ unsigned operator()(int i) const { return kind[i]; }
+    __device__ const PolyRec* poly(int i) const { return polys + i; }
 };
 
 template <class Shapes>
@@ -336,6 +365,7 @@ __device__ __forceinline__ NpBody np_load(const WorldBodies& w, int i, const Sha
     NpBody b;
     b.pos = v2(m.z, m.w); b.xv = v2(f.x, f.y); b.yv = v2(f.z, f.w); b.size = v2(sz.x, sz.y);
     b.kind = shapes(i);
+    b.poly = shapes.poly(i);
     return b;
 }
 
@@ -367,7 +397,7 @@ static __global__ void __launch_bounds__(256) k_update_manifolds(phx_manifold* _
         } else m = manifolds[i];
         // (two bodies = 2 x 40 bytes of the resident arrays; the 128-byte records cost 2 x 128 for the same fields)
         const NpBody b1 = np_load(bodies, m.body1, shapes), b2 = np_load(bodies, m.body2, shapes);
-        if (update_manifold<Shapes::capsules>(m, b1, b2, cps + m.point_index)) atomicAdd(dropped, 1);
+        if (update_manifold<Shapes::capsules, Shapes::polygons>(m, b1, b2, cps + m.point_index)) atomicAdd(dropped, 1);
         manifolds[i] = m;
         const bool gone = m.point_count == 0 && !aabb_intersects(bodies.aabb[m.body1], bodies.aabb[m.body2]);
         dead[i] = gone ? 1u : 0u;
@@ -638,6 +668,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
         if (cols.flags) out_cols.flags[to] = cols.flags[i];
         if (cols.sleep) out_cols.sleep[to] = cols.sleep[i];
         if (cols.shapes) out_cols.shapes[to] = cols.shapes[i];
+        if (cols.polygons) out_cols.polygons[to] = cols.polygons[i];
         if (out_cols.accel) {
             out_cols.accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;

@@ -34,7 +34,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     host_bodies_.assign(bodies, bodies + body_count);
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
-    capsules_ = false;
+    capsules_ = false; polygons_ = false;
     pins_.clear();                                                          // ... and no pin or link is left, no break limit and no break event
     exclusions_.clear();                                                    // ... and no pair is excluded
     break_step_ = 0;
@@ -118,10 +118,13 @@ int World::save(Snapshot& s)
     PHX_TRY(s.reserve_exclusions(exclusions_.count(), stream_));
     const int kinds = shapes_.active ? nb() : 0;                            // the shapes' kinds ride beside the blob too (the sizes are in the records)
     PHX_TRY(s.reserve_shapes(kinds, stream_));
+    const int polys = polys_.active ? nb() : 0;                             // ... and the polygon records
+    PHX_TRY(s.reserve_polygons(polys, stream_));
     PHX_TRY(s.save(v, stream_));
     PHX_TRY(pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); }));
     PHX_TRY(s.save_exclusions(exclusions_.device_pairs(), exclusions_.count(), stream_));
-    return s.save_shapes(shapes_.dev.p, kinds, capsules(), stream_);
+    PHX_TRY(s.save_shapes(shapes_.dev.p, kinds, capsules(), stream_));
+    return s.save_polygons(polys_.dev.p, polys, polygons(), stream_);
 }
 
 int World::load(Snapshot& s)
@@ -143,11 +146,15 @@ int World::load(Snapshot& s)
     if (c.columns & SNAP_HAS_MATERIALS) PHX_TRY(materials_.dev.reserve(std::max<size_t>(n, 1)));
     if (c.columns & SNAP_HAS_FLAGS) PHX_TRY(flags_col_.dev.reserve(std::max<size_t>(n, 1)));
     if (s.shape_count()) PHX_TRY(shapes_.dev.reserve(std::max<size_t>(n, 1)));
+    if (s.polygon_count()) PHX_TRY(polys_.dev.reserve(std::max<size_t>(n, 1)));
     PHX_TRY(contacts_.reserve_baseline((size_t)c.baseline));
     PHX_TRY(s.load(snapshot_view(), stream_));
     PHX_TRY(s.load_shapes(shapes_.dev.p, stream_));                         // phx_world_set_shapes of the saved kinds, if that column was active in s (the sizes came with the records)
     shapes_.active = s.shape_count() != 0;
     capsules_ = s.shape_capsules();
+    PHX_TRY(s.load_polygons(polys_.dev.p, stream_));                        // ... and phx_world_set_polygons of the saved records
+    polys_.active = s.polygon_count() != 0;
+    polygons_ = s.polygons_named();
     // the device copy is the world (host-staged bodies and tables are dropped with the rest of the old world)
     host_bodies_.resize(n);                                                 // (only its size counts while the device copy is the world)
     bodies_dirty_ = false;
