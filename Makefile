@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest wind fold marbles fit logs ramp clean
+.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest wind fold marbles fit logs ramp bullet clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -49,6 +49,9 @@ logs: build                 ## shapes: a dozen capsules dropped onto a shelf bet
 ramp: build                 ## shapes: boxes slide, marbles roll and a hexagon tumbles down a static wedge into a trapezoid tray; a ray onto the slope (PHX_SHAPE_POLYGON, phx_world_set_polygons)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/ramp.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/ramp
 
+bullet: build               ## continuous bodies: marbles at 120 units/s against a thin wall and ramp's wedge, once discrete (they tunnel) and once continuous (phx_world_set_continuous, phx_world_sweep_hits)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/bullet.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/bullet
+
 marbles: build              ## shapes: circles dropped through a funnel of static boxes into a tray, a round wheel on a motor (phx_world_set_shapes)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/marbles.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/marbles
 
@@ -56,5 +59,5 @@ fit: build                  ## the marble emitter that looks first (phx_world_qu
 	gcc -std=c11 -O2 -Wall -Iinclude examples/fit.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/fit
 
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest examples/wind examples/fold examples/marbles examples/fit examples/logs examples/ramp
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest examples/wind examples/fold examples/marbles examples/fit examples/logs examples/ramp examples/bullet
 	rm -rf oracle/_ref

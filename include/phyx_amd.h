@@ -1034,6 +1034,8 @@ int  phx_world_set_state(phx_world* w, const phx_rigid_body* bodies, int32_t bod
  *       rounded up to 16:  bodies n x 128 (phx_rigid_body) | manifolds m x 16 | contact points 2m x 32 | joints j x 20 |
  *       filters n x 16 ({category, mask, group, 0}: the device's own granule) | materials n x 8 | flags n x 4 |
  *       baseline t x 8 (uint64 (body1 << 32) | body2, strictly increasing).
+ *       Column bit 8 (CONTINUOUS BODIES) adds a ninth section behind the baseline, n x 16 {rc, start.x, start.y, 0}, whose offset is the
+ *       uint64 at byte 112 (bytes 120 .. 127 stay zero); without the bit bytes 112 .. 127 are zero and nothing else changes.
  *     The device side of a snapshot has this layout too: export and import are one copy each.  phx_snapshot_blob_check is the single
  *     validator (host only): the header, every size and offset against `bytes` in 64-bit arithmetic that cannot overflow, everything
  *     phx_world_set_state checks, the ranges the setters enforce (friction finite in [0, 1e6], restitution in [0, 1], no unknown flag bit,
@@ -1415,6 +1417,80 @@ int  phx_world_get_fields(phx_world* w, phx_field* out, int32_t cap, int32_t* co
 int  phx_world_pulse_fields(phx_world* w, const phx_field* fields, int32_t count);
 int  phx_world_apply_impulses(phx_world* w, const int32_t* bodies, const float* impulses /* 4 per body: J.x, J.y, point.x, point.y */, int32_t count);
 int  phx_world_field_passes(phx_world* w, int64_t* passes);
+/* CONTINUOUS BODIES — fast bodies swept so that they cannot tunnel.  IntegratePosition moves a body by dvel + vel*dt in one jump and the
+ * broadphase sees only where it lands: a marble of radius 0.25 at 120 units/s covers 2 units per step at 60 Hz and passes a shelf half a
+ * unit thick without one manifold ever existing.  A body marked continuous with a core radius rc > 0 is, after each step's
+ * IntegratePosition, swept on the device: its core disc {s, rc} is cast along the translation d = e - s the step just gave it (s: the
+ * position before the integrator ran, e: after it) against every static body it collides with, and if the disc would have entered one the
+ * body is put back to the point of first touch.  The rotation and the velocities stay as the integrator left them; the AABB is recomputed
+ * from the new position (UpdateGeom).  The core is strictly smaller than the outline, so a stopped body's outline overlaps the obstacle by
+ * at least inradius - rc and the next step's ordinary narrowphase makes the manifold that turns it round.  A world that never named a
+ * continuous body launches what it launched before and computes the same bytes.
+ *   - phx_world_set_continuous(w, bodies, radii, count): radii[k] > 0 makes body k continuous with that core radius, radii[k] == 0 a
+ *     discrete one again.  (A call of its own: phx_world_set_body_flags goes on refusing every bit but PHX_BODY_SENSOR.)  Checked on the
+ *     host before anything is queued, PHX_ERR_INVALID otherwise and the world unchanged: indices in range, none twice; every radius finite
+ *     and >= 0; rc strictly below the body's inradius about its origin: min(hx, hy) of a box, r of a circle, hy of a capsule,
+ *     min_k dot(n_k, v_k) of a polygon (fp32, the stored normals).  phx_continuous_check is that last rule alone (host only, no device):
+ *     "<what>: the core radius <rc> of body <b> is not below its inradius <r>".  A later phx_world_set_shapes / phx_world_set_polygons that
+ *     would leave a continuous body's rc at or above its new inradius is refused in the same words, the world unchanged.
+ *     Between steps only (PHX_ERR_STATE between pre_solve and finish_step); host-staged bodies go up first; PHX_ERR_STATE for a sharded or
+ *     communicator-attached world, and a world that holds a continuous body refuses phx_world_set_shard / set_comm / reslab.
+ *   - phx_world_get_continuous: every body's core radius in index order, 0 for a discrete body (cap: room for that many).
+ *   - The rule (tests/sweep_spec.py is the definition, byte for byte; every operation fp32, rounded on its own).  d = e - s per component;
+ *     d == (0, 0): no cast.  A body whose two inverse masses read 0 at the pass (a static body, a sleeper) is never swept, nor is a sensor.
+ *     A target is another body whose two inverse masses read 0 when the pass runs (sleepers included), that is no sensor, whose collision
+ *     filter passes against the swept body's and that is in no exclusion pair with it: the step's own three tests.  Targets are taken where
+ *     they stand when the pass runs: the motion of a static body moved by phx_world_set_poses during the step is not swept.
+ *       per target: the circle cast {s, rc, d, max_t = 1} of QUERIES, operation for operation, its AABB conjunct included: a box by its six
+ *         parts, a circle body by the disc of radius rc + r, a capsule by its three parts.  tin < 0 (the core overlaps the target at the
+ *         start): no hit, the discrete contact owns the pair.  Otherwise t = max(tin, 0) and the normal is the circle cast's.
+ *       a polygon target, in its frame (o' = the frame coordinates of s - pos, d' those of d):
+ *         start overlap: s_k = dot(n_k, o' - v_k), k the largest, the first on a tie, sm its value; sm <= 0: no hit.  With
+ *           e = v_(k+1) - v_k and u = dot(o' - v_k, e): u < 0 picks q = v_k, otherwise u > dot(e, e) picks q = v_(k+1); there h = o' - q
+ *           and dot(h, h) < rc*rc: no hit; in the face region sm < rc: no hit.
+ *         faces, k in index order: den = dot(n_k, d'); den < 0; t = (dot(n_k, v_k - o') + rc) / den with 0 <= t <= 1; p = o' + d'*t,
+ *           u = dot(p - v_k, e_k) with 0 <= u <= dot(e_k, e_k) (the face pushed out by rc, kept to its own extent); normal n_k.
+ *         vertices, k in index order: the ray/disc rule about v_k with radius rc, max_t = 1; tin >= 0; normal (nx, ny) / rc.
+ *         The smallest t, the first candidate in this order on a tie; the normal through the frame: xv*n.x + yv*n.y.
+ *       the skin, skin = rc * 2^-6, enters in two places, and only here.
+ *         A target's hit counts only if the step approaches it by more than the skin: dot(normal, d) < -skin.  The smallest t wins, ties
+ *         to the lowest target index.
+ *         On a hit the body is put back a skin short of the first touch: approach = -dot(normal, d), t' = max(t - skin / approach, 0),
+ *         pos = (s.x + d.x*t', s.y + d.y*t'), the AABB by UpdateGeom, and one phx_sweep_hit is recorded, whose t is t'.
+ *         Why: the contact rule (SolveJoints) lets a touching pair go on approaching at 0.1 units/s while it is less than 1 unit deep.  A
+ *         body put back to the touch itself would start the next step on the touch to a rounding: overlapping by an ulp it would be the
+ *         contact's while it may still come on at full speed, touching by an ulp it would be held at t = 0 step after step by that creep,
+ *         its sideways motion with it.  A skin short of the touch the next step is decided by what the body does, not by a rounding: one
+ *         that still comes on fast is held (t' = 0) until the contact has turned it, one that creeps is let go and sinks into the
+ *         contact's care, one that leaves is not approaching.  A creeping body cannot tunnel: it moves less than rc / 64 per step.  The
+ *         outline still overlaps the target by inradius - rc - skin where the body stands, so keep rc below inradius / (1 + 2^-6) if the
+ *         next step's narrowphase is to find the pair.
+ *   - phx_world_sweep_hits: the clamps of the last pass, ascending by body; the list stays on the device and comes down on demand.
+ *     *total always receives their number; PHX_ERR_CAPACITY (nothing written) when cap is smaller.  The indices are those of the pass.
+ *   - phx_world_sweep_counts: the passes launched and the clamps made since the world was created.  passes stays 0 in a world without a
+ *     continuous body, and stops counting when the last one is made discrete.
+ *   - The column {rc, s} (16 B per body) exists only once some call named a continuous body.  New bodies are discrete; removals carry the
+ *     column; set_state drops it; save / load / fork carry it in HBM; an exported blob carries it as a ninth section {rc, s.x, s.y, 0}
+ *     per body behind the baseline, named by column bit 8 and an offset at header byte 112: a blob of a world without the column has
+ *     neither and is byte for byte what it was before the bit existed, and such blobs import as they always did.
+ *   - Resting bodies, a limit.  The contact rule corrects a penetration only beyond 2 units (SolveJoints' displacement target), so a
+ *     body at rest lies up to 2 units inside what it rests on, and a pile that lands drives its lowest bodies in faster than a creep.  A
+ *     core that stays clear of that, inradius - rc > 2, is never clamped in a settling pile and the world computes the bytes of its
+ *     discrete twin.  A larger core (any body of ordinary size at factor 0.8: marbles.c's marbles) can be clamped while the pile lands
+ *     on it: the body is held where its core meets the floor, and from then on the world's bytes are not the discrete twin's.  At
+ *     rest a body sinks at 0.1 units/s at most, which is a creep for rc > 0.11 at 60 Hz, and is not held.
+ *   - Cost: one wave per continuous body striding over all bodies, O(continuous x bodies) per step: right for tens to thousands of
+ *     bullets, wrong for "everything continuous" in a world of 200k bodies.  Routing the pass through the query index is a later change.
+ * Out of scope: sweeps against moving bodies, the rotation of the swept body, the core as anything but a disc. */
+typedef struct { int32_t body, target; float t; phx_vec2 normal; } phx_sweep_hit;   /* 20 B */
+int  phx_continuous_check(const char* what, int32_t body, const phx_shape* shape, const phx_polygon* polygon /* NULL unless shape->kind is PHX_SHAPE_POLYGON */, float rc);
+int  phx_world_set_continuous(phx_world* w, const int32_t* bodies, const float* radii, int32_t count);
+int  phx_world_get_continuous(phx_world* w, float* out_radii, int32_t cap);
+int  phx_world_sweep_hits(phx_world* w, phx_sweep_hit* out, int32_t cap, int64_t* total);
+int  phx_world_sweep_counts(phx_world* w, int64_t* passes, int64_t* clamps_total);
+/* the measurement (tools/sweep_cost.py): *last_pass_ms (may be NULL) receives the device time of the last pass's kernel that stood between
+ * two HIP events, 0 if none did (the call waits for it); then, while `enable` is non-zero, every later pass's kernel is timed so */
+int  phx_world_sweep_timing(phx_world* w, int32_t enable, double* last_pass_ms);
 
 int  phx_world_get_solve_stats(phx_world* w, phx_solve_stats* out);
 int  phx_world_get_broadphase_stats(phx_world* w, phx_broadphase_stats* out);

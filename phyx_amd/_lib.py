@@ -188,6 +188,12 @@ _SIGNATURES = {
     "phx_world_get_shapes": (C.c_int, [_vp, _vp, _i32]),
     "phx_world_set_polygons": (C.c_int, [_vp, _vp, _vp, _i32]),
     "phx_world_get_polygons": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_continuous_check": (C.c_int, [C.c_char_p, _i32, _vp, _vp, C.c_float]),
+    "phx_world_set_continuous": (C.c_int, [_vp, _vp, _vp, _i32]),
+    "phx_world_get_continuous": (C.c_int, [_vp, _vp, _i32]),
+    "phx_world_sweep_hits": (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int64)]),
+    "phx_world_sweep_timing": (C.c_int, [_vp, _i32, C.POINTER(C.c_double)]),
+    "phx_world_sweep_counts": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "phx_world_query_aabb": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "phx_world_query_points": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_raycast": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),

@@ -51,6 +51,8 @@ shape_dtype = np.dtype([("kind", "<i4"), ("hx", "<f4"), ("hy", "<f4")])      # p
 assert shape_dtype.itemsize == 12
 polygon_dtype = np.dtype([("count", "<i4"), ("v", "<f4", (8, 2))])      # phx_polygon
 assert polygon_dtype.itemsize == 68
+sweep_hit_dtype = np.dtype([("body", "<i4"), ("target", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,))])      # phx_sweep_hit
+assert sweep_hit_dtype.itemsize == 20
 contact_marker_dtype = np.dtype([("point1", "<f4", (2,)), ("point2", "<f4", (2,)), ("live", "<i4"), ("newly_created", "<i4")])     # phx_contact_marker
 assert contact_dtype.itemsize == 40 and contact_marker_dtype.itemsize == 24
 pin_dtype = np.dtype([("body1", "<i4"), ("body2", "<i4"), ("anchor1", "<f4", (2,)), ("anchor2", "<f4", (2,)), ("impulse", "<f4", (2,))])      # phx_pin
@@ -155,6 +157,15 @@ def polygon_inverse_masses(vertices):
     f = np.float32
     with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
         return np.array([f(1.0) / f(mass), f(1.0) / f(inertia)], dtype=np.float32)
+
+
+def continuous_check(body, kind, hx, hy, rc, polygon=None, what="continuous_check"):
+    """phx_continuous_check: raises PhxError unless rc is finite, >= 0 and (where above 0) strictly below the inradius of the shape
+    {kind, hx, hy} (with `polygon`, an (N, 2) vertex list, for SHAPE_POLYGON); no device needed."""
+    s = np.zeros(1, dtype=shape_dtype)
+    s["kind"], s["hx"], s["hy"] = kind, hx, hy
+    p = None if polygon is None else _polygons(polygon, 1, what)
+    check(_lib.load().phx_continuous_check(what.encode(), int(body), _ptr(s), None if p is None else _ptr(p), float(np.float32(rc))))
 
 
 def _polygons(polygons, count, what):
@@ -1569,6 +1580,67 @@ class World:
             self.set_polygons(idx, p)
             self.set_inverse_masses(idx, np.array([polygon_inverse_masses(q["v"][:q["count"]]) for q in p], dtype=np.float32))
         return first
+
+    # ---- continuous bodies (include/phyx_amd.h CONTINUOUS BODIES; the specification: tests/sweep_spec.py) ----
+    def inradii(self, bodies=None):
+        """The inradius about its origin of the listed bodies (all of them if None), computed on the host from shapes() and polygons():
+        min(hx, hy) of a box, r of a circle, hy of a capsule, min_k dot(n_k, v_k) of a polygon (float32)."""
+        idx = np.arange(self.counts()[0], dtype=np.int32) if bodies is None else self._indices(bodies, "inradii")
+        s = self.shapes()[idx]
+        out = np.minimum(s["hx"], s["hy"]).astype(np.float32)
+        out = np.where(s["kind"] == SHAPE_CIRCLE, s["hx"], out).astype(np.float32)
+        which = np.flatnonzero(s["kind"] == SHAPE_POLYGON)
+        if len(which):
+            f = np.float32
+            for k, p in zip(which, self.polygons(idx[which])):
+                v = p["v"][:p["count"]].astype(f)
+                e = (np.roll(v, -1, axis=0) - v).astype(f)
+                l = np.sqrt((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]).astype(f)).astype(f)
+                nx, ny = (e[:, 1] / l).astype(f), (-e[:, 0] / l).astype(f)
+                out[k] = ((nx * v[:, 0]).astype(f) + (ny * v[:, 1]).astype(f)).astype(f).min()
+        return out
+
+    def set_continuous(self, bodies, radii=None, factor=0.8):
+        """Make the listed bodies (each at most once) continuous: after every step's IntegratePosition the core disc of radius radii[k]
+        about the body's origin is cast along the translation the step gave the body, against every static body it collides with, and
+        the body is put back to the point of first touch.  radii: a scalar for all of them or one value per body, each below the body's
+        inradius; 0 makes a body discrete again; None takes factor x inradii(bodies).  The library rejects anything else (PhxError),
+        the world unchanged."""
+        idx = self._indices(bodies, "set_continuous")
+        r = np.zeros(len(idx), dtype=np.float32)
+        if radii is None:
+            if len(idx):
+                r[:] = (np.float32(factor) * self.inradii(idx)).astype(np.float32)
+        else:
+            r[:] = self._per_body("set_continuous", "radii", radii, len(idx), "fiu")
+        check(self.L.phx_world_set_continuous(self.h, _ptr(idx), _ptr(r), len(idx)))
+
+    def continuous(self):
+        """Every body's core radius, in index order: a float32 array, 0 for a discrete body."""
+        return self._get(self.L.phx_world_get_continuous, np.float32, self.counts()[0])
+
+    def sweep_hits(self):
+        """The clamps of the last step's pass, ascending by body: an array of sweep_hit_dtype {body, target, t, normal}."""
+        total = C.c_int64(0)
+        st = self.L.phx_world_sweep_hits(self.h, None, 0, C.byref(total))
+        if st == 0 and total.value == 0:
+            return np.zeros(0, dtype=sweep_hit_dtype)
+        out = np.zeros(max(int(total.value), 1), dtype=sweep_hit_dtype)
+        check(self.L.phx_world_sweep_hits(self.h, _ptr(out), len(out), C.byref(total)))
+        return out[:total.value]
+
+    def sweep_counts(self):
+        """(passes launched, clamps made) since the world was created; passes stays 0 in a world without a continuous body."""
+        passes, clamps = C.c_int64(0), C.c_int64(0)
+        check(self.L.phx_world_sweep_counts(self.h, C.byref(passes), C.byref(clamps)))
+        return passes.value, clamps.value
+
+    def sweep_timing(self, enable=True):
+        """The device time in ms of the last pass's kernel that was timed (0.0 if none was); then every later pass is timed by two HIP
+        events while `enable` holds (tools/sweep_cost.py)."""
+        ms = C.c_double(0.0)
+        check(self.L.phx_world_sweep_timing(self.h, 1 if enable else 0, C.byref(ms)))
+        return ms.value
 
     # ---- queries (include/phyx_amd.h: phx_world_query_aabb / _points / raycast; the specification: tests/query_spec.py) ----
     @staticmethod

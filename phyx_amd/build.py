@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 OUT = os.path.join(HERE, "libphyx_amd.so")
-SOURCES = ["runtime.hip", "schedule.hip", "solver.hip", "solver_build.hip", "solver_inspect.hip", "solver_bench.hip", "islands.hip", "exchange.hip", "comm.hip", "c_api_solver.hip", "broadphase.hip", "c_api_broadphase.hip", "world.hip", "world_state.hip", "world_edit.hip", "world_units.hip", "world_query.hip", "c_api_world.hip", "reslab.hip", "query.hip", "contact.hip", "snapshot.hip", "pins.hip", "sleep.hip", "fields.hip", "exclusions.hip", "debug_primitives.hip"]
+SOURCES = ["runtime.hip", "schedule.hip", "solver.hip", "solver_build.hip", "solver_inspect.hip", "solver_bench.hip", "islands.hip", "exchange.hip", "comm.hip", "c_api_solver.hip", "broadphase.hip", "c_api_broadphase.hip", "world.hip", "world_state.hip", "world_edit.hip", "world_units.hip", "world_query.hip", "c_api_world.hip", "reslab.hip", "query.hip", "contact.hip", "snapshot.hip", "pins.hip", "sleep.hip", "sweep.hip", "fields.hip", "exclusions.hip", "debug_primitives.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
          "-Wall", "-Wno-unused-result"]
 # per-file extras.  islands.hip: the SLP vectoriser pairs the joint update's multiplies and adds into v_pk_mul_f32 / v_pk_add_f32
@@ -27,6 +27,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # launch 61.5 us under iterative-ilp, 60.5 under the default, 60.4 under max-ilp, 61.5 / 62.0 under max-memory-clause / iterative-minreg
 FILE_FLAGS = {"islands.hip": ["-fno-slp-vectorize", "-Wno-unused-function"],      # (it includes solver_kernels.h for the shared device helpers only)
               "sleep.hip": ["-Wno-unused-function"],      # (it includes schedule_kernels.h for the two flattening kernels only)
+              "sweep.hip": ["-Wno-unused-function"],      # (it includes query_kernels.h for the circle casts' device routines only)
               "solver_bench.hip": ["-Wno-unused-function"]}      # (it includes solver_kernels.h for the checksum kernel's mix64 only)
 # the World's files all see world_kernels.h through world.h: world.hip and world_edit.hip launch their own share of it each, the other four nothing
 FILE_FLAGS.update({f: ["-Wno-unused-function"] for f in ("world.hip", "world_state.hip", "world_edit.hip", "world_units.hip", "world_query.hip", "c_api_world.hip")})

@@ -265,6 +265,36 @@ int phx_world_get_polygons(phx_world* w, const int32_t* bodies, phx_polygon* out
     return w->impl.get_polygons(bodies, out, count);
 }
 
+int phx_world_set_continuous(phx_world* w, const int32_t* bodies, const float* radii, int32_t count)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.set_continuous(bodies, radii, count);
+}
+
+int phx_world_get_continuous(phx_world* w, float* out_radii, int32_t cap)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.get_continuous(out_radii, cap);
+}
+
+int phx_world_sweep_hits(phx_world* w, phx_sweep_hit* out, int32_t cap, int64_t* total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.sweep_hits(out, cap, total);
+}
+
+int phx_world_sweep_counts(phx_world* w, int64_t* passes, int64_t* clamps_total)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.sweep_counts(passes, clamps_total);
+}
+
+int phx_world_sweep_timing(phx_world* w, int32_t enable, double* last_pass_ms)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.sweep_timing(enable, last_pass_ms);
+}
+
 int phx_world_query_aabb(phx_world* w, const float* boxes, int32_t count, int32_t flags, int32_t* offsets, int32_t* hits, int32_t hit_cap, int64_t* total)
 {
     PHX_REQUIRE(w, "null handle");

@@ -412,6 +412,24 @@ __device__ __forceinline__ bool q_cast_disc(const QDiscCast& c, unsigned kind, f
     return hit;
 }
 
+// a circle cast's normal from what q_cast_disc left of the winner (tin >= 0; r: the cast circle's radius): the circle casts' finish and
+// the continuous bodies' pass (sweep_kernels.h) both take it from here
+template <int CAPS>
+__device__ __forceinline__ float2 q_cast_disc_normal(const QCastDisc& cd, float4 f, float2 sz, float r)
+{
+    if (CAPS && cd.part >= Q_PART_SIDE) return q_capsule_normal(cd, f, r + sz.y);
+    if (cd.part < 2) {                                                      // a face, by where the centre is at the entry: an exact copy
+        const float px = cd.ox + cd.tin * cd.dxp, py = cd.oy + cd.tin * cd.dyp;
+        const bool xface = fabsf(px) - sz.x >= fabsf(py) - sz.y;
+        const float nx = xface ? f.x : f.z, ny = xface ? f.y : f.w;
+        const bool flip = (xface ? px : py) < 0.f;
+        return make_float2(flip ? -nx : nx, flip ? -ny : ny);
+    }
+    if (cd.part == Q_PART_BODY) { const float R = r + sz.x; return make_float2(cd.nx / R, cd.ny / R); }
+    const float nx = cd.nx / r, ny = cd.ny / r;                             // a corner: the local normal through the frame
+    return make_float2(f.x * nx + f.z * ny, f.y * nx + f.w * ny);
+}
+
 __device__ __forceinline__ unsigned long long q_ray_key(float tin, int body)
 {
     const float t = tin > 0.f ? tin : 0.f;                       // t >= 0: its bits order like its value
@@ -555,24 +573,7 @@ static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, cons
             QCastDisc cd;
             (void)q_cast_disc<CAPS>(c, q_kind<CAPS>(w.kinds, b), w.s.mpos[b], f, sz, cd);
             h.body = b; h.t = cd.tin > 0.f ? cd.tin : 0.f;
-            if (!(cd.tin < 0.f)) {
-                if (CAPS && cd.part >= Q_PART_SIDE) {
-                    const float2 nn = q_capsule_normal(cd, f, c.c.r + sz.y);
-                    h.normal.x = nn.x; h.normal.y = nn.y;
-                } else if (cd.part < 2) {                                          // a face, by where the centre is at the entry: an exact copy
-                    const float px = cd.ox + cd.tin * cd.dxp, py = cd.oy + cd.tin * cd.dyp;
-                    const bool xface = fabsf(px) - sz.x >= fabsf(py) - sz.y;
-                    const float nx = xface ? f.x : f.z, ny = xface ? f.y : f.w;
-                    const bool flip = (xface ? px : py) < 0.f;
-                    h.normal.x = flip ? -nx : nx; h.normal.y = flip ? -ny : ny;
-                } else if (cd.part == Q_PART_BODY) {
-                    const float R = c.c.r + sz.x;
-                    h.normal.x = cd.nx / R; h.normal.y = cd.ny / R;
-                } else {                                                    // a corner: the local normal through the frame
-                    const float nx = cd.nx / c.c.r, ny = cd.ny / c.c.r;
-                    h.normal.x = f.x * nx + f.z * ny; h.normal.y = f.y * nx + f.w * ny;
-                }
-            }
+            if (!(cd.tin < 0.f)) { const float2 nn = q_cast_disc_normal<CAPS>(cd, f, sz, c.c.r); h.normal.x = nn.x; h.normal.y = nn.y; }
         } else if (k != ~0ull) {
             const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
             const QCast c = q_load_cast(casts, q);

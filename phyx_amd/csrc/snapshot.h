@@ -112,6 +112,24 @@ public:
         return PHX_OK;
     }
     int polygon_count() const { return polygon_count_; }
+    // ... and the continuous bodies' column (CONTINUOUS BODIES): one 16-byte granule {rc, start} per body of a world whose column was active
+    int reserve_sweep(int n, hipStream_t stream) { return n ? sweep_.reserve_keep((size_t)n, (size_t)sweep_count_, stream) : PHX_OK; }
+    int save_sweep(const void* d_src, int count, hipStream_t stream)
+    {
+        sweep_count_ = count;
+        if (!count) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(sweep_.p, d_src, (size_t)count * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(saved_, stream));                            // (the event moves behind the copy)
+        return PHX_OK;
+    }
+    int load_sweep(void* d_dst, hipStream_t stream)                         // (queued behind Snapshot::load on the same stream)
+    {
+        if (!sweep_count_) return PHX_OK;
+        PHX_HIP(hipMemcpyAsync(d_dst, sweep_.p, (size_t)sweep_count_ * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        PHX_HIP(hipEventRecord(loaded_, stream));
+        return PHX_OK;
+    }
+    int sweep_count() const { return sweep_count_; }
     bool polygons_named() const { return polygons_named_; }
     bool shape_capsules() const { return shape_capsules_; }
     int blob_bytes(size_t* bytes);
@@ -137,6 +155,7 @@ private:
     DevBuf<uint2> exclusions_; int exclusion_count_ = 0;
     DevBuf<uint32_t> shapes_; int shape_count_ = 0; bool shape_capsules_ = false;
     DevBuf<uint32_t> polygons_; int polygon_count_ = 0; bool polygons_named_ = false;
+    DevBuf<float4> sweep_; int sweep_count_ = 0;
 
     int device_;
     DevBuf<uint4> buf_;                  // the blob behind its header; grows geometrically, reused by every save

@@ -145,8 +145,9 @@ int Snapshot::export_blob(void* blob, size_t cap)
     PHX_TRY(settle());
     unsigned char* out = static_cast<unsigned char*>(blob);
     snap_write_header(out, counts_, layout_);
-    const size_t rest = (size_t)(layout_.total - SNAP_HEADER_BYTES);
+    const size_t rest = (size_t)(layout_.sweep_offset - SNAP_HEADER_BYTES);      // (the eight sections; the continuous bodies' column rides beside them)
     if (rest) PHX_HIP(hipMemcpy(out + SNAP_HEADER_BYTES, buf_.p, rest, hipMemcpyDeviceToHost));
+    if (layout_.sweep_bytes) PHX_HIP(hipMemcpy(out + layout_.sweep_offset, sweep_.p, (size_t)layout_.sweep_bytes, hipMemcpyDeviceToHost));
     return PHX_OK;
 }
 
@@ -157,14 +158,19 @@ int Snapshot::import_blob(const void* blob, size_t bytes)
     if (snap_blob_check(blob, bytes, why, sizeof why, &c, &l, &accelerations) != PHX_OK) { set_error("phx_snapshot_import: %s", why); return PHX_ERR_INVALID; }
     PHX_TRY(use_device(device_));
     PHX_TRY(settle());
-    const size_t rest = (size_t)(l.total - SNAP_HEADER_BYTES);
+    const size_t rest = (size_t)(l.sweep_offset - SNAP_HEADER_BYTES);
     PHX_TRY(buf_.reserve(rest / 16));
     if (rest) PHX_HIP(hipMemcpy(buf_.p, static_cast<const unsigned char*>(blob) + SNAP_HEADER_BYTES, rest, hipMemcpyHostToDevice));
+    if (l.sweep_bytes) {
+        PHX_TRY(sweep_.reserve((size_t)c.bodies));
+        PHX_HIP(hipMemcpy(sweep_.p, static_cast<const unsigned char*>(blob) + l.sweep_offset, (size_t)l.sweep_bytes, hipMemcpyHostToDevice));
+    }
     counts_ = c; layout_ = l; accel_pending_ = accelerations; filled_ = true;
     std::apply([](auto&... r) { ((r.count = 0), ...); }, riders_);
     exclusion_count_ = 0;
     shape_count_ = 0; shape_capsules_ = false;
     polygon_count_ = 0; polygons_named_ = false;
+    sweep_count_ = l.sweep_bytes ? c.bodies : 0;
     return PHX_OK;
 }
 

@@ -11,7 +11,8 @@
 //    20  int32     manifold count m
 //    24  int32     contact point count (2 m)
 //    28  int32     joint count j
-//    32  uint32    column bits: 1 collision filters, 2 materials, 4 body flags (a clear bit: every body has the default, no section)
+//    32  uint32    column bits: 1 collision filters, 2 materials, 4 body flags, 8 continuous bodies (a clear bit: every body has the
+//                  default, no section)
 //    36  int32     baseline count t
 //    40  uint64    total bytes of the blob
 //    48  uint64[8] section offsets, in this order (a section of no bytes still has the offset the layout gives it):
@@ -23,7 +24,9 @@
 //                    materials       n x 8     phx_material
 //                    flags           n x 4     uint32
 //                    baseline        t x 8     uint64 (body1 << 32) | body2, strictly increasing
-//   112  16 bytes  zero
+//   112  uint64    offset of the continuous bodies' section, n x 16 {rc, start.x, start.y, 0}, behind the baseline: written only with
+//                  column bit 8; without it these bytes are zero and the blob is what it was before the bit existed
+//   120  8 bytes   zero
 // The first section starts at 128, every other at the end of the one before rounded up to 16, and the total is the last end rounded
 // up to 16.  The device side of a snapshot (snapshot.h) holds bytes [128, total) of this, so export and import are one copy each.
 #pragma once
@@ -42,7 +45,8 @@ constexpr unsigned char SNAP_MAGIC[8] = {'P', 'H', 'X', 'S', 'N', 'A', 'P', 0};
 constexpr uint32_t SNAP_VERSION = 1;
 constexpr uint64_t SNAP_HEADER_BYTES = 128;
 enum { SNAP_BODIES = 0, SNAP_MANIFOLDS, SNAP_CPS, SNAP_JOINTS, SNAP_FILTERS, SNAP_MATERIALS, SNAP_FLAGS, SNAP_BASELINE, SNAP_SECTIONS };
-enum { SNAP_HAS_FILTERS = 1, SNAP_HAS_MATERIALS = 2, SNAP_HAS_FLAGS = 4, SNAP_COLUMN_BITS = 7 };
+enum { SNAP_HAS_FILTERS = 1, SNAP_HAS_MATERIALS = 2, SNAP_HAS_FLAGS = 4, SNAP_HAS_SWEEP = 8, SNAP_COLUMN_BITS = 15 };
+constexpr uint64_t SNAP_SWEEP_OFFSET_AT = 112;      // (the ninth offset: not one of the kernels' sections, the column rides beside them: snapshot.h)
 constexpr const char* SNAP_SECTION_NAME[SNAP_SECTIONS] = {"bodies", "manifolds", "contact points", "joints", "filters", "materials", "flags", "baseline"};
 constexpr uint64_t SNAP_ELEMENT_BYTES[SNAP_SECTIONS] = {128, 16, 32, 20, 16, 8, 4, 8};
 
@@ -52,6 +56,7 @@ struct SnapCounts {
 };
 struct SnapLayout {
     uint64_t offset[SNAP_SECTIONS], bytes[SNAP_SECTIONS], total;
+    uint64_t sweep_offset, sweep_bytes;      // the continuous bodies' section (SNAP_HAS_SWEEP), behind the eight: no bytes without the bit
 };
 
 // counts are non-negative int32: the largest section is 2^31 x 128 bytes, nothing here can overflow 64 bits
@@ -68,7 +73,9 @@ inline SnapLayout snap_layout(const SnapCounts& c)
         l.bytes[k] = elements[k] * SNAP_ELEMENT_BYTES[k];
         at = (at + l.bytes[k] + 15) & ~uint64_t(15);
     }
-    l.total = at;
+    l.sweep_offset = at;
+    l.sweep_bytes = (c.columns & SNAP_HAS_SWEEP) ? n * 16 : 0;
+    l.total = at + l.sweep_bytes;
     return l;
 }
 
@@ -92,6 +99,7 @@ inline void snap_write_header(unsigned char* h, const SnapCounts& c, const SnapL
     snap_put32(h + 28, (uint32_t)c.joints); snap_put32(h + 32, c.columns); snap_put32(h + 36, (uint32_t)c.baseline);
     snap_put64(h + 40, l.total);
     for (int k = 0; k < SNAP_SECTIONS; ++k) snap_put64(h + 48 + 8 * k, l.offset[k]);
+    if (c.columns & SNAP_HAS_SWEEP) snap_put64(h + SNAP_SWEEP_OFFSET_AT, l.sweep_offset);
 }
 
 // The invariants the step's kernels rely on, shared by phx_world_set_state and the blob's validator: manifold i owns slots 2i and
@@ -139,7 +147,7 @@ inline int snap_blob_check(const void* blob, size_t bytes, char* msg, size_t msg
     if (c.bodies < 0 || c.manifolds < 0 || c.joints < 0 || c.baseline < 0 || cp_count < 0) PHX_SNAP_FAIL("snapshot blob: negative count");
     if ((int64_t)cp_count != 2 * (int64_t)c.manifolds) PHX_SNAP_FAIL("snapshot blob: %d contact points for %d manifolds (two slots per manifold)", cp_count, c.manifolds);
     if (c.columns & ~(uint32_t)SNAP_COLUMN_BITS) PHX_SNAP_FAIL("snapshot blob: unknown column bit in 0x%x", c.columns);
-    for (int k = 112; k < 128; ++k)
+    for (int k = (c.columns & SNAP_HAS_SWEEP) ? 120 : 112; k < 128; ++k)
         if (h[k]) PHX_SNAP_FAIL("snapshot blob: reserved header byte %d is not zero", k);
     // sizes and offsets against `bytes`: every comparison is between values that exist, nothing is added before it is known to fit
     const SnapLayout l = snap_layout(c);
@@ -151,8 +159,10 @@ inline int snap_blob_check(const void* blob, size_t bytes, char* msg, size_t msg
         if (off != l.offset[k]) PHX_SNAP_FAIL("snapshot blob: section %s is at offset %llu, the layout puts it at %llu", SNAP_SECTION_NAME[k], (unsigned long long)off, (unsigned long long)l.offset[k]);
     }
     if (l.total != (uint64_t)bytes) PHX_SNAP_FAIL("snapshot blob: %zu bytes, its counts need %llu", bytes, (unsigned long long)l.total);
+    if ((c.columns & SNAP_HAS_SWEEP) && snap_get64(h + SNAP_SWEEP_OFFSET_AT) != l.sweep_offset)
+        PHX_SNAP_FAIL("snapshot blob: section continuous bodies is at offset %llu, the layout puts it at %llu", (unsigned long long)snap_get64(h + SNAP_SWEEP_OFFSET_AT), (unsigned long long)l.sweep_offset);
     for (int k = 0; k < SNAP_SECTIONS; ++k) {
-        const uint64_t end = k + 1 < SNAP_SECTIONS ? l.offset[k + 1] : l.total;
+        const uint64_t end = k + 1 < SNAP_SECTIONS ? l.offset[k + 1] : l.sweep_offset;
         for (uint64_t at = l.offset[k] + l.bytes[k]; at < end; ++at)
             if (h[at]) PHX_SNAP_FAIL("snapshot blob: byte %llu behind section %s is not zero", (unsigned long long)at, SNAP_SECTION_NAME[k]);
     }
@@ -172,6 +182,14 @@ inline int snap_blob_check(const void* blob, size_t bytes, char* msg, size_t msg
         for (int i = 0; i < c.bodies; ++i) {
             const uint32_t f = snap_get32(h + l.offset[SNAP_FLAGS] + 4 * (uint64_t)i);
             if (!snap_flags_ok(f)) PHX_SNAP_FAIL("snapshot blob: flags 0x%x of body %d hold an unknown bit", f, i);
+        }
+    if (c.columns & SNAP_HAS_SWEEP)
+        for (int i = 0; i < c.bodies; ++i) {
+            float v[4];
+            std::memcpy(v, h + l.sweep_offset + 16 * (uint64_t)i, sizeof v);
+            if (!(v[0] >= 0.f && v[0] <= 3.0e38f)) PHX_SNAP_FAIL("snapshot blob: core radius %g of body %d is not finite and >= 0", (double)v[0], i);
+            if (!(v[1] >= -3.0e38f && v[1] <= 3.0e38f && v[2] >= -3.0e38f && v[2] <= 3.0e38f)) PHX_SNAP_FAIL("snapshot blob: start of body %d is not finite", i);
+            if (snap_get32(h + l.sweep_offset + 16 * (uint64_t)i + 12)) PHX_SNAP_FAIL("snapshot blob: continuous body %d: the fourth word is not zero", i);
         }
     // the baseline: strictly increasing keys of pairs of bodies
     uint64_t before = 0;

@@ -18,6 +18,7 @@
 #include "pins.h"
 #include "fields.h"
 #include "exclusions.h"
+#include "sweep.h"
 
 #include <algorithm>
 #include <cmath>
@@ -279,6 +280,12 @@ public:
     int get_polygons(const int32_t* bodies, phx_polygon* out, int count);
     int queue_shapes(const int32_t* bodies, const phx_shape* shapes, int count, bool kinds);
     int queue_polygons(const int32_t* bodies, const phx_polygon* polygons, int count);
+    // continuous bodies (phx_world_set_continuous ... phx_world_sweep_counts): between steps; the pass runs behind IntegratePosition (sweep.h)
+    int set_continuous(const int32_t* bodies, const float* radii, int count);
+    int get_continuous(float* out, int cap);
+    int sweep_hits(phx_sweep_hit* out, int cap, int64_t* total);
+    int sweep_counts(int64_t* passes, int64_t* clamps_total);
+    int sweep_timing(int enable, double* last_pass_ms);
     template <class Column> int get_table(const char* what, BodyTable<Column>& table, typename Column::api* out, int cap);
     // units: pins, links, angles and sliders, `P` = phx_pin, phx_link, phx_angle or phx_slider (phx_world_add_pins ... phx_world_get_sliders, phx_world_get_pin_schedule): between
     // steps; solved at the end of pre_solve (pins.h)
@@ -462,6 +469,13 @@ private:
     BodyTable<PolygonColumn> polys_;
     bool polygons_ = false;
     bool polygons() const { return polygons_ && shapes_.active && polys_.active; }
+    // ... and the continuous bodies' {rc, start} (include/phyx_amd.h CONTINUOUS BODIES): active once some set_continuous call named one
+    BodyTable<SweepColumn> sweep_col_;
+    DeviceSweep sweep_;
+    int sweep_begin();                   // queued in front of the integrator: start := pos of the continuous bodies; a world without queues nothing
+    int sweep_pass();                    // queued behind IntegratePosition, in front of the sleep pass
+    // set_shapes / set_polygons: no listed continuous body's core radius is left at or above its new inradius (`polygons`: null unless polygons are set)
+    int check_core_radii(const char* what, const int32_t* bodies, const phx_shape* shapes, const phx_polygon* polygons, int count);
     DeviceSleep sleep_;
     bool sleep_count_pending_ = false;   // the pass or a wake may have changed the static set: the device's count has not been looked at yet
     DevBuf<phx_sleep_state> sleep_out_;
@@ -473,7 +487,7 @@ private:
     template <class P> int wake_units(const int32_t* which, int count);      // both bodies of the listed units
     void take_sleep_count(unsigned changed);      // what set_inverse_masses does when the static set changed
     int settle_sleep_count();            // ... by a readback of its own, where no step's count readback has brought it yet
-    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); PHX_TRY(f(sleep_col_)); PHX_TRY(f(shapes_)); return f(polys_); }
+    template <class F> int each_table(F f) { PHX_TRY(f(filters_)); PHX_TRY(f(materials_)); PHX_TRY(f(flags_col_)); PHX_TRY(f(sleep_col_)); PHX_TRY(f(shapes_)); PHX_TRY(f(polys_)); return f(sweep_col_); }
     // the three setters' skeleton: `rule(k)` is the call's own check of entry k
     template <class Column, class Rule>
     int set_column(const char* what, BodyTable<Column>& table, const int32_t* bodies, const typename Column::api* values, int count, Rule rule, bool host_path_ok);
@@ -488,8 +502,8 @@ private:
     int check_unit_bodies(const char* what, const char* noun, int k, int body1, int body2);
     // an edit of Fields::width floats per listed unit (already checked): staged for the scatter kernel when the list is on the device
     template <class P, class Fields> int set_unit_fields(const int32_t* which, const float* values, int count);
-    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr(), shapes_.ptr(), polys_.ptr()}; }
-    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr(), shapes_.spare_ptr(), polys_.spare_ptr()}; }
+    BodyColumns columns() const { return BodyColumns{accel_pending_ ? accel_.p : nullptr, filters_.ptr(), materials_.ptr(), flags_col_.ptr(), sleep_col_.ptr(), shapes_.ptr(), polys_.ptr(), sweep_col_.ptr()}; }
+    BodyColumns spare_columns() const { return BodyColumns{accel_pending_ ? spare_.accel.p : nullptr, filters_.spare_ptr(), materials_.spare_ptr(), flags_col_.spare_ptr(), sleep_col_.spare_ptr(), shapes_.spare_ptr(), polys_.spare_ptr(), sweep_col_.spare_ptr()}; }
 };
 
 } // namespace phx

@@ -18,6 +18,7 @@ World::~World()
 {
     if (hipSetDevice(device_) != hipSuccess) return;
     if (stream_) (void)hipStreamSynchronize(stream_);
+    sweep_.release();
     stage_.release();                                                       // (only here: the device is current and no copy is queued any more)
     // (device buffers are DevBuf members: freed with the object)
     // (stream_ belongs to the broadphase handle, which is destroyed after this body and after the solver handle)
@@ -637,6 +638,7 @@ int World::finish_step(float dt, const phx_config& cfg)
     PHX_TRY(sync_bodies_to_device());
     auto t = clk::now();
     auto lap = [&](int phase) { if (!phase_timing) return; (void)hipStreamSynchronize(stream_); auto n = clk::now(); phase_ms[phase] = std::chrono::duration<double, std::milli>(n - t).count(); t = n; };
+    if (sweep_col_.active) PHX_TRY(sweep_begin());                          // (the continuous bodies' start: positions do not move before the integrator)
     if (phase_timing) {                                                     // (per-phase host timing: settle the solve before the integrator)
         { RoctxRange r("SolveJoints"); PHX_TRY(solve(cfg, true)); lap(6); }
         RoctxRange r("IntegratePosition");
@@ -645,6 +647,8 @@ int World::finish_step(float dt, const phx_config& cfg)
         PHX_HIP(hipGetLastError());
     } else PHX_TRY(solve_and_integrate(dt, cfg));
     records_stale_ = true;
+    // (by now the integrator that counts, a repeat included, is queued: the continuous bodies' pass goes behind it, in front of the sleep pass)
+    if (sweep_col_.active) PHX_TRY(sweep_pass());                           // (a world that never named a continuous body queues nothing here)
     if (sleep_.on()) PHX_TRY(sleep_pass(dt));                               // (a world that never enabled sleeping queues nothing here)
     lap(7);
     return PHX_OK;

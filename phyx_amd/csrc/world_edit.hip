@@ -244,6 +244,7 @@ int World::remove(const char* what, const int* bodies, int count, const float* b
     std::swap(bodies_, spare_.bodies);
     if (accel_pending_) std::swap(accel_, spare_.accel);
     each_table([](auto& t) { t.adopt_spare(); return PHX_OK; });
+    sweep_.changed();                                                       // (the continuous bodies' list holds the old numbering)
     host_bodies_.resize((size_t)kept_bodies);                               // (only its size counts while the device copy is the world)
     ++geom_epoch_;
     ++contact_epoch_;
@@ -505,6 +506,7 @@ int World::set_shapes(const int32_t* bodies, const phx_shape* shapes, int count)
         capsule = capsule || s.kind == PHX_SHAPE_CAPSULE;
     }
     if (!count) return PHX_OK;
+    PHX_TRY(check_core_radii(what, bodies, shapes, nullptr, count));
     capsules_ = (capsules_ && shapes_.active) || capsule;                   // (a column that went away took the bit with it)
     PHX_TRY(wake_named(bodies, count));
     const int n = nb();
@@ -582,6 +584,7 @@ int World::set_polygons(const int32_t* bodies, const phx_polygon* polygons, int 
         frame[(size_t)k] = phx_shape{PHX_SHAPE_POLYGON, hx, hy};
     }
     if (!count) return PHX_OK;
+    PHX_TRY(check_core_radii(what, bodies, frame.data(), clean.data(), count));
     capsules_ = capsules_ && shapes_.active;                                // (a column that went away took the bits with it)
     polygons_ = true;
     PHX_TRY(wake_named(bodies, count));
@@ -616,6 +619,110 @@ int World::get_polygons(const int32_t* bodies, phx_polygon* out, int count)
     PHX_TRY(polys_.visit(n, host_staged(), device_, rb_, stream_, [&](int i, const PolyRec& v) { all[(size_t)i] = PolygonColumn::shown(v); }));
     for (int k = 0; k < count; ++k) out[k] = all[(size_t)bodies[k]];
     return PHX_OK;
+}
+
+// ---- continuous bodies ---------------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h CONTINUOUS BODIES.  The call writes the column's core radii and nothing else; the next step's two launches
+// (sweep.h) do the rest.  What is checked: the batch, every radius, and rc against the body's inradius about its origin.
+static float inradius_of(const phx_shape& s, const phx_polygon* polygon)
+{
+    if (s.kind == PHX_SHAPE_CIRCLE) return s.hx;
+    if (s.kind == PHX_SHAPE_CAPSULE) return s.hy;
+    if (s.kind == PHX_SHAPE_POLYGON && polygon) {
+        const PolyRec r = poly_record(*polygon);
+        float least = INFINITY;
+        for (int k = 0; k < r.count && k < PHX_POLYGON_MAX_VERTICES; ++k) {
+            const float d = dot(v2(r.n[2 * k], r.n[2 * k + 1]), v2(r.v[2 * k], r.v[2 * k + 1]));
+            least = d < least ? d : least;
+        }
+        return least;
+    }
+    return s.hx < s.hy ? s.hx : s.hy;
+}
+
+extern "C" int phx_continuous_check(const char* what, int32_t body, const phx_shape* shape, const phx_polygon* polygon, float rc)
+{
+    if (!what) what = "phx_continuous_check";
+    if (!shape) { set_error("%s: null shape", what); return PHX_ERR_INVALID; }
+    if (shape->kind == PHX_SHAPE_POLYGON && !polygon) { set_error("%s: body %d is a polygon and no polygon was given", what, body); return PHX_ERR_INVALID; }
+    if (!(std::isfinite(rc) && rc >= 0.f)) { set_error("%s: the core radius %g of body %d is not finite and >= 0", what, (double)rc, body); return PHX_ERR_INVALID; }
+    const float r = inradius_of(*shape, polygon);
+    if (rc > 0.f && !(rc < r)) { set_error("%s: the core radius %g of body %d is not below its inradius %g", what, (double)rc, body, (double)r); return PHX_ERR_INVALID; }
+    return PHX_OK;
+}
+
+int World::check_core_radii(const char* what, const int32_t* bodies, const phx_shape* shapes, const phx_polygon* polygons, int count)
+{
+    if (!sweep_col_.active || !count) return PHX_OK;
+    std::vector<float> rc((size_t)nb());
+    PHX_TRY(sweep_col_.visit(nb(), host_staged(), device_, rb_, stream_, [&](int i, const float4& v) { rc[(size_t)i] = v.x; }));
+    for (int k = 0; k < count; ++k)
+        if (rc[(size_t)bodies[k]] > 0.f) PHX_TRY(phx_continuous_check(what, bodies[k], shapes + k, polygons ? polygons + k : nullptr, rc[(size_t)bodies[k]]));
+    return PHX_OK;
+}
+
+int World::set_continuous(const int32_t* bodies, const float* radii, int count)
+{
+    static const char* const what = "phx_world_set_continuous";
+    PHX_TRY(refuse_sharded(what, SweepColumn::plural));
+    PHX_TRY(check_batch(what, bodies, radii, count, true));
+    for (int k = 0; k < count; ++k)
+        if (!(std::isfinite(radii[k]) && radii[k] >= 0.f)) { set_error("%s: the core radius %g of body %d is not finite and >= 0", what, (double)radii[k], bodies[k]); return PHX_ERR_INVALID; }
+    if (!count) return PHX_OK;
+    const int n = nb();
+    std::vector<phx_shape> shapes((size_t)n);
+    PHX_TRY(get_shapes(shapes.data(), n));
+    std::vector<phx_polygon> polys;
+    if (polys_.active) {
+        polys.resize((size_t)n);
+        PHX_TRY(polys_.visit(n, host_staged(), device_, rb_, stream_, [&](int i, const PolyRec& v) { polys[(size_t)i] = PolygonColumn::shown(v); }));
+    }
+    for (int k = 0; k < count; ++k) {
+        const phx_shape& s = shapes[(size_t)bodies[k]];
+        if (s.kind == PHX_SHAPE_POLYGON && polys.empty()) { set_error("%s: body %d is a polygon without a record", what, bodies[k]); return PHX_ERR_STATE; }
+        PHX_TRY(phx_continuous_check(what, bodies[k], &s, polys.empty() ? nullptr : &polys[(size_t)bodies[k]], radii[k]));
+    }
+    bool any = sweep_col_.active;
+    for (int k = 0; k < count; ++k) any = any || radii[k] > 0.f;
+    if (!any) return PHX_OK;                                                // (discrete bodies made discrete in a world without the column: nothing to write)
+    PHX_TRY(settle_and_upload());                                           // (host-staged bodies go up first: the column lives beside the resident arrays)
+    const int* d_bodies = nullptr; const float* d_values = nullptr;
+    PHX_TRY(stage_.indexed(bodies, radii, count, 1, stream_, &d_bodies, &d_values));
+    PHX_TRY(sweep_col_.set_device(d_bodies, d_values, count, n, stream_));
+    sweep_.changed();
+    return PHX_OK;
+}
+
+int World::get_continuous(float* out, int cap)
+{
+    static const char* const what = "phx_world_get_continuous";
+    PHX_TRY(refuse_mid_step(what));
+    if (nb() && !out) { set_error("%s: null array", what); return PHX_ERR_INVALID; }
+    return get_table(what, sweep_col_, out, cap);
+}
+
+int World::sweep_hits(phx_sweep_hit* out, int cap, int64_t* total)
+{
+    static const char* const what = "phx_world_sweep_hits";
+    PHX_TRY(refuse_mid_step(what));
+    if (cap < 0 || (cap && !out)) { set_error("%s: bad capacity or null array", what); return PHX_ERR_INVALID; }
+    PHX_TRY(settle_on_device());
+    return sweep_.hits(out, cap, total, rb_, stream_);
+}
+
+int World::sweep_counts(int64_t* passes, int64_t* clamps_total)
+{
+    PHX_TRY(refuse_mid_step("phx_world_sweep_counts"));
+    PHX_TRY(settle_on_device());
+    return sweep_.counts(passes, clamps_total, rb_, stream_);
+}
+
+int World::sweep_timing(int enable, double* last_pass_ms)
+{
+    PHX_TRY(refuse_mid_step("phx_world_sweep_timing"));
+    PHX_TRY(use_device(device_));
+    if (last_pass_ms) PHX_TRY(sweep_.pass_ms(last_pass_ms));
+    return sweep_.timing(enable != 0);
 }
 
 // every body's {kind, geom_size}: the kinds from the column (boxes while there is none), the sizes from wherever the bodies are

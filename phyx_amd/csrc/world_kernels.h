@@ -167,6 +167,15 @@ struct PolygonColumn {                 // include/phyx_amd.h POLYGONS; the rule:
     }
     static bool is_initial(const value& v) { return v.count == 0; }
 };
+struct SweepColumn {                   // include/phyx_amd.h CONTINUOUS BODIES; the rule: sweep_kernels.h k_sweep_bodies
+    using value = float4;              // {rc, start.x, start.y, 0}: the core radius (0: a discrete body) and where the body stood before the step's integrator ran
+    using api = float;                 // the core radius
+    static constexpr const char* plural = "continuous bodies";
+    static __host__ __device__ value initial() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __host__ __device__ value stored(const api& rc) { return make_float4(rc, 0.f, 0.f, 0.f); }
+    static api shown(const value& v) { return v.x; }
+    static bool is_initial(const value& v) { return v.x == 0.f; }
+};
 static_assert(sizeof(phx_polygon) == 17 * sizeof(float), "a batch is staged as 4-byte words");
 static_assert(sizeof(phx_collision_filter) == 3 * sizeof(float) && sizeof(phx_material) == 2 * sizeof(float) && sizeof(uint32_t) == sizeof(float) &&
               sizeof(phx_shape) == 3 * sizeof(float), "a batch is staged as 4-byte words");
@@ -214,6 +223,7 @@ struct BodyColumns {
     SleepCell* sleep;
     uint32_t* shapes;
     PolyRec* polygons;
+    float4* sweep;
 };
 
 // spawn (phx_world_add_bodies): body first + k from row k = {pos, half size, invMass, invInertia, xVector, yVector}, which the host built
@@ -249,6 +259,7 @@ static __global__ void __launch_bounds__(256) k_spawn_bodies(const float* __rest
         if (cols.sleep) cols.sleep[i] = SleepColumn::initial();      // (awake, timer 0)
         if (cols.shapes) cols.shapes[i] = ShapeColumn::initial();    // (a box)
         if (cols.polygons) cols.polygons[i] = PolygonColumn::initial();
+        if (cols.sweep) cols.sweep[i] = SweepColumn::initial();      // (a discrete body)
     }
 }
 
@@ -669,6 +680,7 @@ static __global__ void __launch_bounds__(256) k_remove_bodies(const phx_rigid_bo
         if (cols.sleep) out_cols.sleep[to] = cols.sleep[i];
         if (cols.shapes) out_cols.shapes[to] = cols.shapes[i];
         if (cols.polygons) out_cols.polygons[to] = cols.polygons[i];
+        if (cols.sweep) out_cols.sweep[to] = cols.sweep[i];
         if (out_cols.accel) {
             out_cols.accel[to] = make_float4(b.acceleration.x, b.acceleration.y, b.angular_acceleration, 0.f);
             if (b.acceleration.x != 0.f || b.acceleration.y != 0.f || b.angular_acceleration != 0.f) ++nonzero;

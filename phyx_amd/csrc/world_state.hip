@@ -35,6 +35,7 @@ int World::set_state(const phx_rigid_body* bodies, int body_count, const phx_man
     bodies_dirty_ = true;
     each_table([](auto& t) { t.reset(); return PHX_OK; });                  // every optional column is the default again
     capsules_ = false; polygons_ = false;
+    sweep_.forget();                                                        // ... and no body is continuous
     pins_.clear();                                                          // ... and no pin or link is left, no break limit and no break event
     exclusions_.clear();                                                    // ... and no pair is excluded
     break_step_ = 0;
@@ -110,7 +111,8 @@ int World::save(Snapshot& s)
     PHX_TRY(settle_breaks());
     SnapshotWorld v = snapshot_view();
     v.counts.bodies = nb(); v.counts.manifolds = nm; v.counts.joints = nj; v.counts.baseline = contacts_.baseline_count();
-    v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0);
+    v.counts.columns = (filters_.active ? SNAP_HAS_FILTERS : 0) | (materials_.active ? SNAP_HAS_MATERIALS : 0) | (flags_col_.active ? SNAP_HAS_FLAGS : 0) |
+                       (sweep_col_.active ? SNAP_HAS_SWEEP : 0);      // (the last: its section is not the kernel's, it rides beside the blob and joins it at export)
     v.accel_pending = accel_pending_;      // (while it is clear every record's accelerations are zero: IntegrateVelocity clears them)
     PHX_TRY(pins_.upload(stream_));
     PHX_TRY(exclusions_.sync(nb(), stream_));
@@ -120,11 +122,14 @@ int World::save(Snapshot& s)
     PHX_TRY(s.reserve_shapes(kinds, stream_));
     const int polys = polys_.active ? nb() : 0;                             // ... and the polygon records
     PHX_TRY(s.reserve_polygons(polys, stream_));
+    const int cores = sweep_col_.active ? nb() : 0;                         // ... and the continuous bodies' column
+    PHX_TRY(s.reserve_sweep(cores, stream_));
     PHX_TRY(s.save(v, stream_));
     PHX_TRY(pins_.each_list([&](auto& l) { return s.save_units(l.device(), l.device_limits(), l.count(), stream_); }));
     PHX_TRY(s.save_exclusions(exclusions_.device_pairs(), exclusions_.count(), stream_));
     PHX_TRY(s.save_shapes(shapes_.dev.p, kinds, capsules(), stream_));
-    return s.save_polygons(polys_.dev.p, polys, polygons(), stream_);
+    PHX_TRY(s.save_polygons(polys_.dev.p, polys, polygons(), stream_));
+    return s.save_sweep(sweep_col_.dev.p, cores, stream_);
 }
 
 int World::load(Snapshot& s)
@@ -147,6 +152,7 @@ int World::load(Snapshot& s)
     if (c.columns & SNAP_HAS_FLAGS) PHX_TRY(flags_col_.dev.reserve(std::max<size_t>(n, 1)));
     if (s.shape_count()) PHX_TRY(shapes_.dev.reserve(std::max<size_t>(n, 1)));
     if (s.polygon_count()) PHX_TRY(polys_.dev.reserve(std::max<size_t>(n, 1)));
+    if (s.sweep_count()) PHX_TRY(sweep_col_.dev.reserve(std::max<size_t>(n, 1)));
     PHX_TRY(contacts_.reserve_baseline((size_t)c.baseline));
     PHX_TRY(s.load(snapshot_view(), stream_));
     PHX_TRY(s.load_shapes(shapes_.dev.p, stream_));                         // phx_world_set_shapes of the saved kinds, if that column was active in s (the sizes came with the records)
@@ -155,6 +161,9 @@ int World::load(Snapshot& s)
     PHX_TRY(s.load_polygons(polys_.dev.p, stream_));                        // ... and phx_world_set_polygons of the saved records
     polys_.active = s.polygon_count() != 0;
     polygons_ = s.polygons_named();
+    PHX_TRY(s.load_sweep(sweep_col_.dev.p, stream_));                       // ... and phx_world_set_continuous of the saved core radii
+    sweep_col_.active = s.sweep_count() != 0;
+    sweep_.forget();
     // the device copy is the world (host-staged bodies and tables are dropped with the rest of the old world)
     host_bodies_.resize(n);                                                 // (only its size counts while the device copy is the world)
     bodies_dirty_ = false;

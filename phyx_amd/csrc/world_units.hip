@@ -286,6 +286,27 @@ int World::sleep_pass(float dt)
     return PHX_OK;
 }
 
+// ---- continuous bodies ---------------------------------------------------------------------------------------------------------------
+// The rule: include/phyx_amd.h CONTINUOUS BODIES, tests/sweep_spec.py; the list, the launches and the hits: sweep.h.  Here: the place of
+// the two launches in the step.  The pass moves a clamped body's position and AABB behind IntegratePosition, inside the step whose
+// integrator has already moved the geometry epoch and whose pre_solve the contact epoch: neither index needs anything new.
+int World::sweep_begin()
+{
+    if (!nb()) return PHX_OK;
+    return sweep_.begin(bodies_.mpos.p, sweep_col_.dev.p, nb(), rb_, stream_);
+}
+
+int World::sweep_pass()
+{
+    if (!nb()) return PHX_OK;                                               // (an empty list still ends the last pass's hits)
+    WorldBodies w = bodies_.view();
+    w.kinds = shapes_.ptr(); w.polys = polygons() ? polys_.ptr() : nullptr;
+    const ExclusionView* x = exclusions_.view();
+    const SweepTables tables = {filters_.ptr(), flags_col_.ptr(), x ? x->table : nullptr, x ? x->mask : 0u, x ? x->member : nullptr};
+    const int shapes = !shapes_.ptr() ? SWEEP_BOXES : (polygons() ? SWEEP_POLYGONS : (capsules() ? SWEEP_CAPSULES : SWEEP_SHAPES));
+    return sweep_.pass(w, sweep_col_.dev.p, nb(), tables, shapes, stream_);
+}
+
 void World::take_sleep_count(unsigned changed)
 {
     sleep_count_pending_ = false;
