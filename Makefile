@@ -1,5 +1,5 @@
 # Convenience targets; the driver's contract is __graft_entry__.build()/smoke() and bench.py.
-.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest wind fold marbles fit logs ramp bullet clean
+.PHONY: build test test-gpu bench smoke example place bridge crank piston snap rest wind fold marbles fit reach logs ramp bullet clean
 
 build:                      ## hipcc --offload-arch=gfx950 -> phyx_amd/libphyx_amd.so; gcc -> oracle/liboracle.so (+ oracle/_ref shims if /root/reference exists)
 	python -c "import __graft_entry__ as g; g.build()"
@@ -58,6 +58,9 @@ marbles: build              ## shapes: circles dropped through a funnel of stati
 fit: build                  ## the marble emitter that looks first (phx_world_query_circles, phx_world_cast_circles)
 	gcc -std=c11 -O2 -Wall -Iinclude examples/fit.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/fit
 
+reach: build                ## a pick with a tolerance and the marbles' clearance from the funnel (phx_world_query_nearest)
+	gcc -std=c11 -O2 -Wall -Iinclude examples/reach.c -Lphyx_amd -lphyx_amd -Wl,-rpath,$(CURDIR)/phyx_amd -lm -o examples/reach
+
 clean:
-	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest examples/wind examples/fold examples/marbles examples/fit examples/logs examples/ramp examples/bullet
+	rm -f phyx_amd/libphyx_amd.so oracle/liboracle.so examples/drop_in examples/place examples/bridge examples/crank examples/piston examples/snap examples/rest examples/wind examples/fold examples/marbles examples/fit examples/reach examples/logs examples/ramp examples/bullet
 	rm -rf oracle/_ref

@@ -7,7 +7,7 @@ libphyx_amd.so (include/phyx_amd.h).  All compute runs in hand-written HIP kerne
 from .api import (Configuration, Solver, Collider, World, Snapshot, Comm, SOLVE_SCALAR, SOLVE_SSE2, SOLVE_AVX2,  # noqa: F401
                   ISLAND_SINGLE, ISLAND_MULTIPLE, ISLAND_SINGLE_SLOPPY, ISLAND_MULTIPLE_SLOPPY,
                   rigid_body_dtype, contact_point_dtype, manifold_dtype, contact_joint_dtype, ray_hit_dtype,
-                  shape_hit_dtype, box_from_angle,
+                  shape_hit_dtype, near_hit_dtype, box_from_angle,
                   field_dtype, uniform_field, radial_field, drag_field, field_check, MAX_FIELDS, FIELD_UNIFORM, FIELD_RADIAL, FIELD_DRAG,
                   REGION_ALL, REGION_BOX, REGION_DISC, FIELD_FORCE,
                   contact_dtype, contact_marker_dtype, collision_filter_dtype, material_dtype, BODY_SENSOR, shape_dtype, SHAPE_BOX, SHAPE_CIRCLE, SHAPE_CAPSULE, SHAPE_POLYGON, POLYGON_MAX_VERTICES, polygon_dtype, sweep_hit_dtype, continuous_check, circle_inverse_masses, capsule_inverse_masses, polygon_inverse_masses,

@@ -205,6 +205,8 @@ _SIGNATURES = {
     "phx_world_query_circles": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "phx_world_cast_circles": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_cast_circles_device": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "phx_world_query_nearest": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+    "phx_world_query_nearest_device": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
     "phx_world_query_index": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "phx_world_query_contacts": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, C.POINTER(C.c_int64)]),
     "phx_world_contact_events": (C.c_int, [_vp, _vp, _i32, C.POINTER(C.c_int64), _vp, _i32, C.POINTER(C.c_int64)]),

@@ -42,6 +42,8 @@ ray_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,))
 assert ray_hit_dtype.itemsize == 24
 shape_hit_dtype = np.dtype([("body", "<i4"), ("t", "<f4"), ("normal", "<f4", (2,))])      # phx_shape_hit
 assert shape_hit_dtype.itemsize == 16
+near_hit_dtype = np.dtype([("body", "<i4"), ("distance", "<f4"), ("normal", "<f4", (2,)), ("point", "<f4", (2,))])      # phx_near_hit
+assert near_hit_dtype.itemsize == 24
 contact_dtype = np.dtype([("other", "<i4"), ("manifold", "<i4"), ("slot", "<i4"), ("flags", "<i4"), ("point", "<f4", (2,)), ("normal", "<f4", (2,)),
                           ("normal_impulse", "<f4"), ("friction_impulse", "<f4")])                                     # phx_contact
 collision_filter_dtype = np.dtype([("category", "<u4"), ("mask", "<u4"), ("group", "<i4")])      # phx_collision_filter
@@ -1766,6 +1768,20 @@ class World:
     def cast_circles_device(self, casts_ptr, count, out_ptr, skip_static=False):
         """cast_circles on device memory (6 floats per cast in, a 16-byte shape_hit_dtype record per cast out), queued on the world's stream."""
         check(self.L.phx_world_cast_circles_device(self.h, _dev_ptr(casts_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
+
+    def query_nearest(self, queries, skip_static=False):
+        """The body nearest to each point within max_dist; queries (K, 3) {p.x, p.y, max_dist} (np.finfo(np.float32).max: anywhere): a
+        near_hit_dtype array of the signed distance (negative inside), the outward normal and the surface point (body -1 and zeros: none)."""
+        q = self._queries(queries, 3, "query_nearest", "{p.x, p.y, max_dist}")
+        if (q[:, 2] < 0).any():
+            raise ValueError("query_nearest: max_dist must be >= 0")
+        out = np.zeros(len(q), dtype=near_hit_dtype)
+        check(self.L.phx_world_query_nearest(self.h, _ptr(q), len(q), 1 if skip_static else 0, _ptr(out)))
+        return out
+
+    def query_nearest_device(self, queries_ptr, count, out_ptr, skip_static=False):
+        """query_nearest on device memory (3 floats per query in, a 24-byte near_hit_dtype record per query out), queued on the world's stream."""
+        check(self.L.phx_world_query_nearest_device(self.h, _dev_ptr(queries_ptr), int(count), 1 if skip_static else 0, _dev_ptr(out_ptr)))
 
     def query_index(self):
         """Queue the build of the query index unless it is current; returns how many times this world has built it."""

@@ -361,6 +361,18 @@ int phx_world_cast_circles_device(phx_world* w, const void* d_casts, int32_t cou
     return w->impl.cast_circles_device(d_casts, count, flags, d_out);
 }
 
+int phx_world_query_nearest(phx_world* w, const float* queries, int32_t count, int32_t flags, phx_near_hit* out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_nearest(queries, count, flags, out);
+}
+
+int phx_world_query_nearest_device(phx_world* w, const void* d_queries, int32_t count, int32_t flags, void* d_out)
+{
+    PHX_REQUIRE(w, "null handle");
+    return w->impl.query_nearest_device(d_queries, count, flags, d_out);
+}
+
 int phx_world_query_contacts(phx_world* w, const int32_t* bodies, int32_t count, int32_t flags, int32_t* offsets, phx_contact* out, int32_t cap, int64_t* total)
 {
     PHX_REQUIRE(w, "null handle");

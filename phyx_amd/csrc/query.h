@@ -17,17 +17,20 @@ struct QTree;
 class DeviceQuery {
 public:
     // (BOXES: AABBs; SHAPES: oriented boxes; DISCS: circles)
-    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2, QUERY_SHAPES = 3, QUERY_CASTS = 4, QUERY_DISCS = 5, QUERY_DISC_CASTS = 6 };
+    enum Kind { QUERY_POINTS = 0, QUERY_RAYS = 1, QUERY_BOXES = 2, QUERY_SHAPES = 3, QUERY_CASTS = 4, QUERY_DISCS = 5, QUERY_DISC_CASTS = 6, QUERY_NEAR = 7 };
     // the scan path answers batches up to this many queries of each kind, the index larger ones: the largest batch size at which
     // tools/query_cost.py measured the scan faster at cfg 2, each call after a step so that the index pays its build (INTEGRATION.md
     // §4b: points 2048 scan / 4096 index, rays 512 / 1024, boxes 1024 / 2048; sizes between two measured ones are not measured)
     // Oriented boxes and box casts take the thresholds of the AABB queries and the rays: they share their data path, and their own
     // crossover was not measured when they were made.  Circles and circle casts take 512, by the rule above:
     // tools/round_query_cost.py measured both with the scan faster at 512 and the index faster at 1024 (Queries: circles).
-    static constexpr int SCAN_MAX[7] = {2048, 512, 1024, 1024, 512, 512, 512};
+    // Nearest queries: 1.  tools/near_cost.py measured the scan faster up to 2 048 queries at max_dist 2 and 50 but at a batch of 1 only at
+    // FLT_MAX, where every pair is a candidate and the scan has nothing to skip (0.78 ms against the index's 0.38 at 64 queries, 43.6
+    // against 1.5 at 65 536): 1 is the largest measured size at which the scan was faster at every max_dist (Queries: nearest).
+    static constexpr int SCAN_MAX[8] = {2048, 512, 1024, 1024, 512, 512, 512, 1};
 
     // PHX_QUERY_PATH=scan|index forces a path; PHX_QUERY_SCAN_CHUNK=q (a multiple of 64) lowers the queries per chunk of the scan path's
-    // AABB table.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
+    // AABB table and per launch of the nearest scan.  Read when the world is created; any other value is refused (PHX_ERR_INVALID).
     int configure_from_env();
     ReportPath choose(Kind kind, int count) const { return choose_path(forced_, count, SCAN_MAX[kind]); }
 
@@ -45,6 +48,8 @@ public:
     int discs(const WorldBodies& w, int n, unsigned long long epoch, const float* d_circles, int count, int flags, int32_t* offsets, int32_t* hits,
               int hit_cap, int64_t* total, Readback& rb, hipStream_t s);
     int disc_casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s);
+    // nearest bodies (3 floats per query {p, max_dist}): as rays; the scan's launches hold at most PHX_QUERY_SCAN_CHUNK queries each
+    int near(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, phx_near_hit* d_out, hipStream_t s);
     // the index alone (tools/query_cost.py times it): built unless it is current
     int ensure_index(const WorldBodies& w, int n, unsigned long long epoch, hipStream_t s);
     int index_builds() const { return index_.builds(); }

@@ -9,6 +9,7 @@
 
 static_assert(sizeof(phx_ray_hit) == 24, "phx_ray_hit is 24 bytes (include/phyx_amd.h)");
 static_assert(sizeof(phx_shape_hit) == 16, "phx_shape_hit is 16 bytes (include/phyx_amd.h)");
+static_assert(sizeof(phx_near_hit) == 24, "phx_near_hit is 24 bytes (include/phyx_amd.h)");
 
 namespace phx {
 
@@ -154,6 +155,32 @@ int DeviceQuery::casts(const WorldBodies& w, int n, unsigned long long epoch, co
 int DeviceQuery::disc_casts(const WorldBodies& w, int n, unsigned long long epoch, const float* d_casts, int count, int flags, phx_shape_hit* d_out, hipStream_t s)
 {
     return closest<QSHAPE_DISC>(w, n, epoch, d_casts, count, flags, d_out, s);
+}
+
+// nearest bodies: closest<>'s shape (keys filled or walked, then a finish kernel) with kernels of its own; the scan goes chunk by chunk of
+// PHX_QUERY_SCAN_CHUNK queries, as the overlap lists' scan does
+int DeviceQuery::near(const WorldBodies& w, int n, unsigned long long epoch, const float* d_queries, int count, int flags, phx_near_hit* d_out, hipStream_t s)
+{
+    if (count <= 0) return PHX_OK;
+    PHX_TRY(ray_keys_.reserve((size_t)count));
+    const bool scan = n == 0 || choose(QUERY_NEAR, count) == PATH_SCAN;
+    if (!scan) PHX_TRY(ensure_index(w, n, epoch, s));
+    q_caps(w, [&](auto caps) {
+        constexpr int C = decltype(caps)::value;
+        if (scan) {
+            hipLaunchKernelGGL(k_qfill_u64, dim3(stream_grid(count)), dim3(256), 0, s, ray_keys_.p, count, ~0ull);
+            const int chunk = std::max(Q_TILE, std::min(scan_chunk_, Q_MAX_TILES * Q_TILE) / Q_TILE * Q_TILE);
+            for (int q0 = 0; n && q0 < count; q0 += chunk)
+                hipLaunchKernelGGL((k_qscan_near<C>), dim3(stream_grid(n), div_up(std::min(chunk, count - q0), Q_TILE)), dim3(256), 0, s, w, n, d_queries, count, q0, flags, ray_keys_.p);
+        } else {
+            const QTree t = tree(n);
+            hipLaunchKernelGGL((k_qtree<QK_NEAR, C>), dim3(qtree_grid(count)), dim3(256), 0, s, w, t, d_queries, count, flags, (unsigned*)nullptr, ray_keys_.p,
+                               (const unsigned*)nullptr, (int*)nullptr);
+        }
+        hipLaunchKernelGGL((k_qnear_finish<C>), dim3(stream_grid(count)), dim3(256), 0, s, w, d_queries, count, (const unsigned long long*)ray_keys_.p, d_out);
+    });
+    PHX_HIP(hipGetLastError());
+    return PHX_OK;
 }
 
 // ---- AABB, oriented-box and circle queries ----------------------------------------------------------------------------------------------------

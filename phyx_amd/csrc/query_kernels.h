@@ -1,8 +1,8 @@
 // query_kernels.h — the device side of the World's queries (include/phyx_amd.h, QUERIES): AABB overlap, point in box or disc, the closest
-// ray hit, oriented-box overlap and the closest box-cast hit, circle overlap and the closest circle-cast hit over the resident arrays
+// ray hit, oriented-box overlap and the closest box-cast hit, circle overlap and the closest circle-cast hit, the nearest body of a point over the resident arrays
 // (body_view.h).  The predicates below are the header's formulas one for one, each operation rounded on its own (the library is
-// compiled with -ffp-contract=off); tests/query_spec.py, tests/shape_query_spec.py, tests/round_query_spec.py and tests/capsule_spec.py
-// state them again in numpy.
+// compiled with -ffp-contract=off); tests/query_spec.py, tests/shape_query_spec.py, tests/round_query_spec.py, tests/capsule_spec.py and
+// tests/near_spec.py state them again in numpy.
 //
 // Two paths give byte-identical results:
 //   scan   bodies in lanes, a tile of Q_TILE queries in LDS, one coalesced pass over the resident arrays per tile; points and rays
@@ -436,6 +436,121 @@ __device__ __forceinline__ unsigned long long q_ray_key(float tin, int body)
     return ((unsigned long long)__float_as_uint(t) << 32) | (unsigned)body;
 }
 
+// an unsigned key that orders like the float (the index build's bounds of the centres; the nearest query's distances, which may be negative)
+__device__ __forceinline__ unsigned q_fkey(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float q_funkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+
+// ---- the nearest-body predicates (include/phyx_amd.h: phx_world_query_nearest; tests/near_spec.py) ------------------------------------------
+// what body b is to the point p: the signed distance (negative inside), the outward normal there and the surface point
+struct QNear { float sd, nx, ny, px, py; };
+
+// (gx / l, gy / l); a length of 0 gives (0, 0)
+__device__ __forceinline__ float2 q_unit(float gx, float gy, float l) { return l > 0.f ? make_float2(gx / l, gy / l) : make_float2(0.f, 0.f); }
+
+// Each kind by its closed form, with e = p - pos and (u, v) its frame coordinates: the box by the clamp of q_disc_overlap (inside: the
+// face of the smaller depth, x on a tie), the circle by its centre, the capsule by the qu clamp, the polygon by the region selection of
+// the disc / polygon candidate rule (narrowphase.h).  A stored face normal is an exact copy; a corner's, a vertex's or a round body's
+// goes through the frame.  The scan and the tree read .sd alone (the rest is dead code there); k_qnear_finish reads the rest.
+template <int CAPS>
+__device__ __forceinline__ QNear q_near_body(unsigned kind, float4 m, float4 f, float2 h, const PolyRec* __restrict__ poly, float x, float y)
+{
+    const float ex = x - m.z, ey = y - m.w;
+    const float u = ex * f.x + ey * f.y, v = ex * f.z + ey * f.w;
+    QNear o;
+    if (CAPS == 2 && kind == (unsigned)PHX_SHAPE_POLYGON) {
+        const int n = poly->count;
+        int k = 0;
+        float s = 0.f;
+        for (int j = 0; j < n; ++j) {
+            const float d = poly->n[2 * j] * (u - poly->v[2 * j]) + poly->n[2 * j + 1] * (v - poly->v[2 * j + 1]);
+            if (j == 0 || d > s) { s = d; k = j; }
+        }
+        const float vkx = poly->v[2 * k], vky = poly->v[2 * k + 1];
+        if (s > 0.f) {
+            const int k1 = k + 1 < n ? k + 1 : 0;
+            const float vnx = poly->v[2 * k1], vny = poly->v[2 * k1 + 1];
+            const float e0 = vnx - vkx, e1 = vny - vky;
+            const float t = (u - vkx) * e0 + (v - vky) * e1, ee = e0 * e0 + e1 * e1;
+            const bool lo = t < 0.f, hi = !lo && t > ee;
+            if (lo || hi) {
+                const float qx = lo ? vkx : vnx, qy = lo ? vky : vny;
+                const float gx = u - qx, gy = v - qy;
+                o.sd = sqrtf(gx * gx + gy * gy);
+                const float2 l = q_unit(gx, gy, o.sd);
+                o.nx = f.x * l.x + f.z * l.y; o.ny = f.y * l.x + f.w * l.y;
+                o.px = (m.z + f.x * qx) + f.z * qy; o.py = (m.w + f.y * qx) + f.w * qy;
+                return o;
+            }
+        }
+        const float nx = poly->n[2 * k], ny = poly->n[2 * k + 1];
+        o.sd = s;
+        o.nx = f.x * nx + f.z * ny; o.ny = f.y * nx + f.w * ny;
+        o.px = x - o.nx * s; o.py = y - o.ny * s;
+        return o;
+    }
+    if (CAPS && kind == (unsigned)PHX_SHAPE_CAPSULE) {
+        const float r = h.y, qu = q_clamp(u, h.x - h.y), gx = u - qu;
+        const float len = sqrtf(gx * gx + v * v);
+        const float2 l = q_unit(gx, v, len);
+        o.sd = len - r;
+        o.nx = f.x * l.x + f.z * l.y; o.ny = f.y * l.x + f.w * l.y;
+        o.px = (m.z + f.x * qu) + o.nx * r; o.py = (m.w + f.y * qu) + o.ny * r;
+        return o;
+    }
+    if (kind != 0u) {
+        const float len = sqrtf(ex * ex + ey * ey);
+        const float2 l = q_unit(ex, ey, len);
+        o.sd = len - h.x;
+        o.nx = l.x; o.ny = l.y;
+        o.px = m.z + l.x * h.x; o.py = m.w + l.y * h.x;
+        return o;
+    }
+    const float ax = fabsf(u) - h.x, ay = fabsf(v) - h.y;
+    if (ax <= 0.f && ay <= 0.f) {
+        const bool xface = ax >= ay, flip = (xface ? u : v) < 0.f;
+        const float nx = xface ? f.x : f.z, ny = xface ? f.y : f.w;
+        o.sd = xface ? ax : ay;
+        o.nx = flip ? -nx : nx; o.ny = flip ? -ny : ny;
+        o.px = x - o.nx * o.sd; o.py = y - o.ny * o.sd;
+        return o;
+    }
+    const float qu = q_clamp(u, h.x), qv = q_clamp(v, h.y);
+    const float gx = u - qu, gy = v - qv;
+    o.sd = sqrtf(gx * gx + gy * gy);
+    if (gy == 0.f) { const bool flip = u < 0.f; o.nx = flip ? -f.x : f.x; o.ny = flip ? -f.y : f.y; }              // a face region: x first
+    else if (gx == 0.f) { const bool flip = v < 0.f; o.nx = flip ? -f.z : f.z; o.ny = flip ? -f.w : f.w; }
+    else { const float2 l = q_unit(gx, gy, o.sd); o.nx = f.x * l.x + f.z * l.y; o.ny = f.y * l.x + f.w * l.y; }
+    o.px = (m.z + f.x * qu) + f.z * qv; o.py = (m.w + f.y * qu) + f.w * qv;
+    return o;
+}
+
+// la: the point's distance from an AABB (a body's or a node's bounds), 0 inside
+__device__ __forceinline__ float q_near_gap(float4 a, float x, float y)
+{
+    const float gx = fmaxf(fmaxf(a.x - x, x - a.z), 0.f), gy = fmaxf(fmaxf(a.y - y, y - a.w), 0.f);
+    return sqrtf(gx * gx + gy * gy);
+}
+
+// D = (la > 0 ? max(sd, la) : sd), never -0.  The fp32 sd may fall a rounding short of la; with the max D >= la holds bit for bit, and la
+// is monotone in the box: a node whose la exceeds the best D so far holds no body that can win or tie (k_qtree, QK_NEAR).
+__device__ __forceinline__ float q_near_distance(float sd, float la)
+{
+    const float d = la > 0.f ? (sd >= la ? sd : la) : sd;
+    return d == 0.f ? 0.f : d;
+}
+
+// a nearest query {p, max_dist} travels as a QDisc {p, r = max_dist}: max_dist == 0 is valid
+__device__ __forceinline__ bool q_near_ok(const QDisc& c) { return isfinite(c.cx) && isfinite(c.cy) && isfinite(c.r) && c.r >= 0.f; }
+
+// (q_fkey(D) << 32) | body of a candidate, ~0 of any other body: the smallest key is the smallest D, ties to the lowest body index
+template <int CAPS>
+__device__ __forceinline__ unsigned long long q_near_key(const QDisc& c, float4 a, unsigned kind, float4 m, float4 f, float2 h, const PolyRec* __restrict__ poly, int body)
+{
+    if (!(a.x <= a.z && a.y <= a.w) || !q_disc_near(c, a)) return ~0ull;
+    const float D = q_near_distance(q_near_body<CAPS>(kind, m, f, h, poly, c.cx, c.cy).sd, q_near_gap(a, c.cx, c.cy));
+    return D <= c.r ? ((unsigned long long)q_fkey(D) << 32) | (unsigned)body : ~0ull;
+}
+
 __device__ __forceinline__ bool q_point_ok(float px, float py) { return isfinite(px) && isfinite(py); }
 __device__ __forceinline__ bool q_ray_ok(const QRay& r)
 {
@@ -590,6 +705,27 @@ static __global__ void __launch_bounds__(256) k_qcast_finish(WorldBodies w, cons
     }
 }
 
+// the nearest results from the winners' keys: the distance is the key's, the winner's normal and point are made again by the same code
+template <int CAPS>
+static __global__ void __launch_bounds__(256) k_qnear_finish(WorldBodies w, const float* __restrict__ queries, int count,
+                                                             const unsigned long long* __restrict__ keys, phx_near_hit* __restrict__ out)
+{
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < count; q += gridDim.x * blockDim.x) {
+        const unsigned long long k = keys[q];
+        phx_near_hit h;
+        h.body = -1; h.distance = 0.f; h.normal.x = h.normal.y = 0.f; h.point.x = h.point.y = 0.f;
+        if (k != ~0ull) {
+            const int b = (int)(unsigned)(k & 0xFFFFFFFFull);
+            const QDisc c = q_load_disc(queries + 3 * (size_t)q);
+            const QNear o = q_near_body<CAPS>(q_kind<CAPS>(w.kinds, b), w.s.mpos[b], w.frame[b], w.size[b], q_poly<CAPS>(w, b), c.cx, c.cy);
+            h.body = b; h.distance = q_funkey((unsigned)(k >> 32));
+            h.normal.x = o.nx; h.normal.y = o.ny;
+            h.point.x = o.px; h.point.y = o.py;
+        }
+        out[q] = h;
+    }
+}
+
 // ---- scan path --------------------------------------------------------------------------------------------------------------------
 // blockIdx.y = the tile of queries [q0, q0 + Q_TILE); bodies grid-strided in lanes.  out: 0xFFFFFFFF (= -1) where nothing was found.
 template <int CAPS>
@@ -687,6 +823,40 @@ static __global__ void __launch_bounds__(256) k_qscan_rays(WorldBodies w, int n,
     }
 }
 
+// nearest queries (3 floats per query), a sibling of k_qscan_rays: the plain statement of the rule, every body against every query of the
+// tile, nothing skipped by what was found so far
+template <int CAPS>
+static __global__ void __launch_bounds__(256) k_qscan_near(WorldBodies w, int n, const float* __restrict__ queries, int count, int q0, int flags,
+                                                           unsigned long long* __restrict__ keys)
+{
+    __shared__ QDisc qd[Q_TILE];
+    __shared__ int qok[Q_TILE];
+    const int base_q = q0 + blockIdx.y * Q_TILE, nq = min(Q_TILE, count - base_q);
+    if ((int)threadIdx.x < nq) {
+        const QDisc c = q_load_disc(queries + 3 * (size_t)(base_q + threadIdx.x));
+        qd[threadIdx.x] = c;
+        qok[threadIdx.x] = q_near_ok(c);
+    }
+    __syncthreads();
+    const bool skip = (flags & Q_SKIP_STATIC) != 0;
+    for (int base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x) {      // (uniform trip count: the ballots below)
+        const int i = base + threadIdx.x;
+        const bool live = i < n;
+        float4 a = make_float4(NAN, NAN, NAN, NAN), m = make_float4(0.f, 0.f, 0.f, 0.f), f = m;
+        float2 h = make_float2(0.f, 0.f);
+        if (live) { a = w.aabb[i]; m = w.s.mpos[i]; f = w.frame[i]; h = w.size[i]; }
+        const bool any = live && !(skip && q_static(m, w.sleep, i));
+        const unsigned kind = live ? q_kind<CAPS>(w.kinds, i) : 0u;
+        for (int q = 0; q < nq; ++q) {
+            unsigned long long k = ~0ull;
+            if (any && qok[q]) k = q_near_key<CAPS>(qd[q], a, kind, m, f, h, q_poly<CAPS>(w, i), i);
+            if (!__ballot(k != ~0ull)) continue;
+            k = q_wave_min64(k);
+            if ((threadIdx.x & 63) == 0) atomicMin(&keys[base_q + q], k);
+        }
+    }
+}
+
 // AABB queries (SHAPE: oriented-box queries, 8 floats per query, or circle queries, 3), one workgroup per 256 consecutive bodies (blockIdx.x = body block of
 // `bblocks`), blockIdx.y = tile.
 //   QS_COUNT    writes the hit count of every (query, body block) to table[(q - q0) * bblocks + block] (query-major: its exclusive scan
@@ -760,9 +930,6 @@ static __global__ void __launch_bounds__(256) k_qscan_aabb(WorldBodies w, int n,
 }
 
 // ---- index path: build ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned q_fkey(float f) { const unsigned u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float q_funkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
 // bounds of the AABB centres (bounds = {min x, min y, max x, max y} as order keys; NaN centres left out)
 static __global__ void __launch_bounds__(256) k_qcentre_bounds(const float4* __restrict__ aabb, int n, unsigned* __restrict__ bounds)
 {
@@ -834,7 +1001,7 @@ static __global__ void __launch_bounds__(256) k_qnodes(const float4* __restrict_
 
 // ---- index path: traversal ----------------------------------------------------------------------------------------------------------
 enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COUNT = 4, QK_BOX_FILL = 5, QK_CAST = 6,
-       QK_DISC_COUNT = 7, QK_DISC_FILL = 8, QK_DISC_CAST = 9 };
+       QK_DISC_COUNT = 7, QK_DISC_FILL = 8, QK_DISC_CAST = 9, QK_NEAR = 10 };
 
 // one wave per query, 4 per workgroup.  A stack entry is (level << 26) | node; a popped node's 64 children are tested by the 64 lanes,
 // the passing inner nodes pushed in lane order.  Depth bound: a pop pushes at most 64 entries of the level below, so the stack never
@@ -845,8 +1012,13 @@ enum { QK_POINT = 0, QK_RAY = 1, QK_AABB_COUNT = 2, QK_AABB_FILL = 3, QK_BOX_COU
 //   QK_AABB_FILL   the hits at hits[seg[q] ..], in traversal order (sorted afterwards)
 //   QK_BOX_COUNT, QK_BOX_FILL   the same two for oriented boxes;   QK_CAST   as QK_RAY for box casts
 //   QK_DISC_COUNT, QK_DISC_FILL, QK_DISC_CAST   the same three for circles
+//   QK_NEAR        out_key[q] = min over the candidates of q_near_key (~0: none).  The one kind whose walk is pruned by what it has found:
+//                  the best key is reduced over the wave after every leaf, a node (when its children are tested, and again when it is
+//                  popped) is skipped iff la_node > 0 && la_node > the best D so far (q_near_distance: never a change to a result), and
+//                  the passing children are pushed farthest first, so that the nearest is popped next.  The other kinds' code is
+//                  untouched by it: every addition sits under `if constexpr`.
 // A lane tests a child's bounds with the query's AABB conjunct: the bounds widened by the box's extents or the circle's radius for the
-// last six kinds.
+// six kinds before QK_NEAR, by max_dist for QK_NEAR.
 template <int KIND, int CAPS>
 static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, const float* __restrict__ queries, int count, int flags,
                                                       unsigned* __restrict__ out_u32, unsigned long long* __restrict__ out_key,
@@ -858,7 +1030,7 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
     constexpr bool OBB = KIND == QK_BOX_COUNT || KIND == QK_BOX_FILL, DISC = KIND == QK_DISC_COUNT || KIND == QK_DISC_FILL;
     constexpr bool COUNT = KIND == QK_AABB_COUNT || KIND == QK_BOX_COUNT || KIND == QK_DISC_COUNT;
     constexpr bool FILL = KIND == QK_AABB_FILL || KIND == QK_BOX_FILL || KIND == QK_DISC_FILL;
-    constexpr bool KEY = KIND == QK_RAY || KIND == QK_CAST || KIND == QK_DISC_CAST;
+    constexpr bool KEY = KIND == QK_RAY || KIND == QK_CAST || KIND == QK_DISC_CAST || KIND == QK_NEAR;
     for (int q = blockIdx.x * 4 + wave; q < count; q += gridDim.x * 4) {      // (the whole wave: grid-strided over the queries)
         float4 qbox = make_float4(0.f, 0.f, 0.f, 0.f);
         QRay r{0.f, 0.f, 0.f, 0.f, 0.f};
@@ -869,6 +1041,9 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
         if (KIND == QK_DISC_CAST) {
             ds = q_load_disc_cast(queries, q);
             ok = q_cast_ok(ds);
+        } else if (KIND == QK_NEAR) {
+            ds.c = q_load_disc(queries + 3 * (size_t)q);                   // ({p, max_dist})
+            ok = q_near_ok(ds.c);
         } else if (DISC) {
             ds.c = q_load_disc(queries + 3 * (size_t)q);
             ok = q_disc_ok(ds.c);
@@ -903,6 +1078,12 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                 const unsigned e = st[--sp];
                 __builtin_amdgcn_wave_barrier();
                 const int level = (int)(e >> 26), node = (int)(e & ((1u << 26) - 1u));
+                if constexpr (KIND == QK_NEAR) {                            // (pushed before the bound came this far down: looked at again)
+                    if (best_key != ~0ull) {
+                        const float la = q_near_gap(t.nodes[t.off[level] + node], ds.c.cx, ds.c.cy);
+                        if (la > 0.f && la > q_funkey((unsigned)(best_key >> 32))) continue;
+                    }
+                }
                 const int c = node * Q_FANOUT + lane;
                 if (level == 1) {
                     bool hit = false;
@@ -924,6 +1105,9 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                                 QCastDisc cd;
                                 hit = q_cast_aabb(ds, a) && q_cast_disc<CAPS>(ds, q_kind<CAPS>(w.kinds, b), m, w.frame[b], w.size[b], cd);
                                 if (hit) { const unsigned long long k = q_ray_key(cd.tin, b); best_key = k < best_key ? k : best_key; }
+                            } else if (KIND == QK_NEAR) {
+                                const unsigned long long k = q_near_key<CAPS>(ds.c, a, q_kind<CAPS>(w.kinds, b), m, w.frame[b], w.size[b], q_poly<CAPS>(w, b), b);
+                                best_key = k < best_key ? k : best_key;
                             } else if (OBB) hit = q_box_overlap(cs.b, ce, a, m, w.frame[b], w.size[b]);
                             else if (DISC) hit = q_disc_overlap<CAPS>(ds.c, a, q_kind<CAPS>(w.kinds, b), m, w.frame[b], w.size[b]);
                             else hit = q_overlap(a, qbox);
@@ -936,12 +1120,31 @@ static __global__ void __launch_bounds__(256) k_qtree(WorldBodies w, QTree t, co
                         if (hit) hits[seg[q] + cursor + (unsigned)__popcll(mask & q_lanes_below())] = b;
                         cursor += (unsigned)__popcll(mask);
                     }
+                    if constexpr (KIND == QK_NEAR) best_key = q_wave_min64(best_key);      // (wave-uniform: the bound every lane prunes by)
                 } else {
                     bool pass = false;
                     if (c < t.cnt[level - 1]) {
                         const float4 nb = t.nodes[t.off[level - 1] + c];
                         pass = KIND == QK_RAY ? q_ray_aabb(r, nb) : KIND == QK_CAST ? q_cast_aabb(cs, ce, nb) : OBB ? q_box_near(cs.b, ce, nb)
-                             : KIND == QK_DISC_CAST ? q_cast_aabb(ds, nb) : DISC ? q_disc_near(ds.c, nb) : q_overlap(nb, qbox);
+                             : KIND == QK_DISC_CAST ? q_cast_aabb(ds, nb) : (DISC || KIND == QK_NEAR) ? q_disc_near(ds.c, nb) : q_overlap(nb, qbox);
+                    }
+                    if constexpr (KIND == QK_NEAR) {
+                        float la = 0.f;
+                        if (pass) {
+                            la = q_near_gap(t.nodes[t.off[level - 1] + c], ds.c.cx, ds.c.cy);
+                            pass = !(best_key != ~0ull && la > 0.f && la > q_funkey((unsigned)(best_key >> 32)));
+                        }
+                        const unsigned long long mask = __ballot(pass);
+                        int below = 0;                                      // the passing children that are farther: they go under this one
+                        for (unsigned long long rest = mask; rest; rest &= rest - 1) {
+                            const int j = __builtin_ctzll(rest);
+                            const float other = __shfl(la, j);
+                            below += (other > la || (other == la && j < lane)) ? 1 : 0;
+                        }
+                        if (pass) st[sp + below] = ((unsigned)(level - 1) << 26) | (unsigned)c;
+                        sp += __popcll(mask);
+                        __builtin_amdgcn_wave_barrier();
+                        continue;
                     }
                     const unsigned long long mask = __ballot(pass);
                     if (pass) st[sp + __popcll(mask & q_lanes_below())] = ((unsigned)(level - 1) << 26) | (unsigned)c;

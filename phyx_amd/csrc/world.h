@@ -248,7 +248,9 @@ public:
     int query_circles(const float* circles, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total);
     int cast_circles(const float* casts, int count, int flags, phx_shape_hit* out);
     int cast_circles_device(const void* d_casts, int count, int flags, void* d_out);
-    int query_index_build();             // the query index alone, built unless current (tools/query_cost.py)
+    int query_nearest(const float* queries, int count, int flags, phx_near_hit* out);
+    int query_nearest_device(const void* d_queries, int count, int flags, void* d_out);
+    int query_index_build();            // the query index alone, built unless current (tools/query_cost.py)
     int query_index_builds() const { return query_.index_builds(); }
     // contact reports (phx_world_query_contacts ... phx_world_contact_index): between steps; only the events' baseline changes
     int query_contacts(const int32_t* bodies, int count, int flags, int32_t* offsets, phx_contact* out, int cap, int64_t* total);
@@ -429,11 +431,12 @@ private:
     DevBuf<int> q_body_;
     DevBuf<phx_ray_hit> q_hits_;
     DevBuf<phx_shape_hit> q_shape_hits_;
+    DevBuf<phx_near_hit> q_near_hits_;
     int query_prepare(bool host_wait);
     // the three skeletons of the query calls (world_query.hip): one result per query through `buf` to the host (`miss`: what an empty
     // world answers) / the same on caller-owned device memory / the overlap lists.  `run`: the DeviceQuery call; `kind`: what a row
     // holds, and with it its width and the rules its values are checked by.
-    enum QueryRows { ROWS_POINTS, ROWS_BOXES, ROWS_RAYS, ROWS_SHAPES, ROWS_CASTS, ROWS_CIRCLES, ROWS_CIRCLE_CASTS };
+    enum QueryRows { ROWS_POINTS, ROWS_BOXES, ROWS_RAYS, ROWS_SHAPES, ROWS_CASTS, ROWS_CIRCLES, ROWS_CIRCLE_CASTS, ROWS_NEAR };
     template <class Hit> using QueryRun = int (DeviceQuery::*)(const WorldBodies&, int, unsigned long long, const float*, int, int, Hit*, hipStream_t);
     using OverlapRun = int (DeviceQuery::*)(const WorldBodies&, int, unsigned long long, const float*, int, int, int32_t*, int32_t*, int, int64_t*, Readback&, hipStream_t);
     template <class Hit> int query_rows(const char* what, const float* rows, int count, QueryRows kind, int flags, Hit* out, const Hit& miss, DevBuf<Hit>& buf, QueryRun<Hit> run);

@@ -14,16 +14,18 @@ static int flags_check(const char* what, int flags)      // (the queries' and th
 }
 
 // what a row of each kind of query holds (World::QueryRows): its width in floats, what the messages call it, and where the values
-// with a rule of their own are (-1: none): an AABB's min <= max, an oriented box's half extents, a circle's radius, a direction, max_t
-struct RowRule { int width; const char* noun; bool ordered; int half, radius, dir, max_t; };
+// with a rule of their own are (-1: none): an AABB's min <= max, an oriented box's half extents, a circle's radius, a direction, max_t, a
+// nearest query's max_dist
+struct RowRule { int width; const char* noun; bool ordered; int half, radius, dir, max_t, max_dist; };
 static const RowRule ROW_RULES[] = {
-    {2, "point", false, -1, -1, -1, -1},      // ROWS_POINTS
-    {4, "box", true, -1, -1, -1, -1},         // ROWS_BOXES
-    {5, "ray", false, -1, -1, 2, 4},          // ROWS_RAYS
-    {8, "box", false, 6, -1, -1, -1},         // ROWS_SHAPES
-    {11, "cast", false, 6, -1, 8, 10},        // ROWS_CASTS
-    {3, "circle", false, -1, 2, -1, -1},      // ROWS_CIRCLES
-    {6, "cast", false, -1, 2, 3, 5},          // ROWS_CIRCLE_CASTS
+    {2, "point", false, -1, -1, -1, -1, -1},      // ROWS_POINTS
+    {4, "box", true, -1, -1, -1, -1, -1},         // ROWS_BOXES
+    {5, "ray", false, -1, -1, 2, 4, -1},          // ROWS_RAYS
+    {8, "box", false, 6, -1, -1, -1, -1},         // ROWS_SHAPES
+    {11, "cast", false, 6, -1, 8, 10, -1},        // ROWS_CASTS
+    {3, "circle", false, -1, 2, -1, -1, -1},      // ROWS_CIRCLES
+    {6, "cast", false, -1, 2, 3, 5, -1},          // ROWS_CIRCLE_CASTS
+    {3, "point", false, -1, -1, -1, -1, 2},       // ROWS_NEAR
 };
 
 static int query_check(const char* what, const float* v, int count, const RowRule& r, int flags, bool device, const void* out)
@@ -40,6 +42,7 @@ static int query_check(const char* what, const float* v, int count, const RowRul
         if (r.half >= 0 && !(q[r.half] > 0.f && q[r.half + 1] > 0.f)) { set_error("%s: box %d: half extents must be positive", what, k); return PHX_ERR_INVALID; }
         if (r.radius >= 0 && !(q[r.radius] > 0.f)) { set_error("%s: circle %d: the radius must be positive", what, k); return PHX_ERR_INVALID; }
         if (r.max_t >= 0 && !(q[r.max_t] >= 0.f)) { set_error("%s: %s %d: max_t < 0", what, r.noun, k); return PHX_ERR_INVALID; }
+        if (r.max_dist >= 0 && !(q[r.max_dist] >= 0.f)) { set_error("%s: %s %d: max_dist < 0", what, r.noun, k); return PHX_ERR_INVALID; }
         if (r.dir >= 0 && q[r.dir] == 0.f && q[r.dir + 1] == 0.f) { set_error("%s: %s %d: zero direction", what, r.noun, k); return PHX_ERR_INVALID; }
     }
     return PHX_OK;
@@ -95,6 +98,7 @@ int World::query_overlaps(const char* what, const float* boxes, int count, Query
 
 static const phx_ray_hit RAY_MISS = {-1, 0.f, {0.f, 0.f}, {0.f, 0.f}};      // (include/phyx_amd.h: no hit: body -1, every other field 0)
 static const phx_shape_hit SHAPE_MISS = {-1, 0.f, {0.f, 0.f}};
+static const phx_near_hit NEAR_MISS = {-1, 0.f, {0.f, 0.f}, {0.f, 0.f}};
 
 int World::query_aabb(const float* boxes, int count, int flags, int32_t* offsets, int32_t* hits, int hit_cap, int64_t* total)
 {
@@ -112,10 +116,12 @@ int World::query_points(const float* points, int count, int flags, int32_t* body
 int World::raycast(const float* rays, int count, int flags, phx_ray_hit* out) { return query_rows("phx_world_raycast", rays, count, ROWS_RAYS, flags, out, RAY_MISS, q_hits_, &DeviceQuery::rays); }
 int World::cast_boxes(const float* casts, int count, int flags, phx_shape_hit* out) { return query_rows("phx_world_cast_boxes", casts, count, ROWS_CASTS, flags, out, SHAPE_MISS, q_shape_hits_, &DeviceQuery::casts); }
 int World::cast_circles(const float* casts, int count, int flags, phx_shape_hit* out) { return query_rows("phx_world_cast_circles", casts, count, ROWS_CIRCLE_CASTS, flags, out, SHAPE_MISS, q_shape_hits_, &DeviceQuery::disc_casts); }
+int World::query_nearest(const float* queries, int count, int flags, phx_near_hit* out) { return query_rows("phx_world_query_nearest", queries, count, ROWS_NEAR, flags, out, NEAR_MISS, q_near_hits_, &DeviceQuery::near); }
 int World::query_points_device(const void* d_points, int count, int flags, void* d_body) { return query_rows_device<int>("phx_world_query_points_device", d_points, count, ROWS_POINTS, flags, d_body, &DeviceQuery::points); }
 int World::raycast_device(const void* d_rays, int count, int flags, void* d_out) { return query_rows_device<phx_ray_hit>("phx_world_raycast_device", d_rays, count, ROWS_RAYS, flags, d_out, &DeviceQuery::rays); }
 int World::cast_boxes_device(const void* d_casts, int count, int flags, void* d_out) { return query_rows_device<phx_shape_hit>("phx_world_cast_boxes_device", d_casts, count, ROWS_CASTS, flags, d_out, &DeviceQuery::casts); }
 int World::cast_circles_device(const void* d_casts, int count, int flags, void* d_out) { return query_rows_device<phx_shape_hit>("phx_world_cast_circles_device", d_casts, count, ROWS_CIRCLE_CASTS, flags, d_out, &DeviceQuery::disc_casts); }
+int World::query_nearest_device(const void* d_queries, int count, int flags, void* d_out) { return query_rows_device<phx_near_hit>("phx_world_query_nearest_device", d_queries, count, ROWS_NEAR, flags, d_out, &DeviceQuery::near); }
 
 int World::query_index_build()
 {
